@@ -2,11 +2,19 @@
 """bench.py -- queries/sec of the exact (brute-force) scan behind Collection.Search.
 
     python bench.py --gpus N --steps K --warmup W [--workload NAME] [--mode ranks|inproc] [--parallelism rows|replicas]
+                    [--full] [--dump-outputs DIR]
 
 A "step" is one exact query over the whole synthetic corpus (one sweep of the packed
 rows through the fused HIP scan; merges, float64 rerank and result assembly included).
 Default workload = BASELINE.json's headline: 1M x 768 float32, cosine (angular)
 distance, k=10, one query per sweep.
+
+A plain run does only what the headline needs: set-up, the W warm-up steps, ONE timed region of exactly K steps
+("ms_per_step" = that region / K), the result line.  --full adds everything else below: R = 5 timed regions, the
+parity checks against the CPU oracle, "cpu_baseline" and the side legs ("batched", "sketch_prepass",
+"batched_quantized", "lone_call", "other_workloads").  --dump-outputs DIR writes what the last timed step returned to
+its caller: DIR/ids.npy (the row ids, float64 -- exact below 2^53) and DIR/distances.npy (float64).  Corpus and
+queries come from fixed seeds, so the same arguments give the same inputs on every run.
 
 N > 1, two forms of the same row sharding (contiguous 64-row-aligned ranges, every
 query goes to every shard, "scaling": "strong"):
@@ -24,11 +32,11 @@ query goes to every shard, "scaling": "strong"):
                  default stays rows sharded + all-gather (north_star); the line says which mode a number used.
 
 The timed region -- EXACTLY K steps between barrier + synchronize on both sides, results on the host -- is repeated
-R = --repeats times (default 5) on FRESH query sets; "value" is the MEDIAN repeat (ms_per_step x steps = that
-repeat's call), "spread" carries min / max / repeats: one 9 ms call on one box of a pool that differs by +-4 % is not
-a measurement.
+R = --repeats times (default 1, 5 with --full) on FRESH query sets; "value" is the MEDIAN repeat (ms_per_step x steps
+= that repeat's call), "spread" carries min / max / repeats: one 9 ms call on one box of a pool that differs by +-4 %
+is not a measurement.
 
-Rank 0 prints ONE JSON line: metric/value/unit/..., plus
+Rank 0 prints ONE JSON line: metric/value/unit/..., plus (the legs after "roofline": --full only)
   "roofline":     HBM roofline of the fused scan kernel from HIP events recorded on the
                   library's scan stream inside the timed region;
   "cpu_baseline": the CPU oracle (a C port of the reference's Go scan; there is no Go
@@ -407,25 +415,35 @@ def main():
     ap.add_argument("--steps", type=int, default=1024)
     ap.add_argument("--warmup", type=int, default=64)
     ap.add_argument("--workload", default="headline", choices=sorted(WORKLOADS) + ["all"],
-                    help="'all' = the headline plus every other config's roofline (the default at N=1 too)")
+                    help="'all' = the headline plus every other config's roofline (what --full adds at N=1 too)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: 5 timed regions, oracle parity, cpu_baseline, the side legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's ids and distances as DIR/ids.npy, DIR/distances.npy (float64)")
     ap.add_argument("--mode", default="ranks", choices=["ranks", "inproc"],
                     help="N>1: one process per GPU + RCCL all-gather, or one process driving N devices")
     ap.add_argument("--parallelism", default="rows", choices=["rows", "replicas"],
                     help="N>1 ranks: rows sharded over the GPUs + all-gather (default), or every rank holds all rows "
                          "and answers its slice of the queries (no collective)")
-    ap.add_argument("--repeats", type=int, default=5, help="timed regions of K steps on fresh queries; value = the median")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed regions of K steps on fresh queries; value = the median (default 1, 5 with --full)")
     ap.add_argument("--rows", type=int, default=0, help="override the workload's row count")
     ap.add_argument("--exchange-every", type=int, default=0,
                     help="N>1 ranks: queries per all-gather micro-batch (0 = 256, or steps/4 for short runs)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of the cpu_baseline leg")
     ap.add_argument("--settle-seconds", type=float, default=2.0,
                     help="untimed sweeps before the warm-up steps (clock / TLB settling)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip cpu_baseline and the recall check")
-    ap.add_argument("--no-extras", action="store_true", help="skip the batched leg and the other workloads")
-    ap.add_argument("--verify", type=int, default=4, help="queries re-checked against the oracle")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip cpu_baseline and the recall check")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip the batched leg and the other workloads")
+    ap.add_argument("--verify", type=int, default=4, help="--full: queries re-checked against the oracle")
     args = ap.parse_args()
     if args.workload == "all":
-        args.workload, args.no_extras = "headline", False
+        args.workload, args.no_extras, args.full = "headline", False, True
+    if not args.full:
+        # a plain run: the headline only (no oracle, no CPU baseline, no side legs), one timed region
+        args.no_cpu = args.no_extras = True
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
 
     if os.environ.get("SZG_BENCH_FORCE_DIST") == "1" and "RANK" not in os.environ:
         # the N>1 code path with ONE rank (a 1-GPU box): a rendezvous of its own
@@ -626,6 +644,11 @@ def main():
         rep_elapsed.append(el)
         if rep == 0:
             res_rows, res_dist = rr, rd   # (the parity legs check the first repeat's queries)
+    # the last timed step's answer, from the rank that computed it (replicas: the last rank holds the last query)
+    if args.dump_outputs and rank == (world - 1 if replicas else 0) and len(rr) > 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "ids.npy"), np.asarray(rr[-1], dtype=np.uint64).astype(np.float64))
+        np.save(os.path.join(args.dump_outputs, "distances.npy"), np.asarray(rd[-1], dtype=np.float64))
     order = sorted(range(args.repeats), key=lambda i: rep_elapsed[i])
     med = order[len(order) // 2]
     elapsed = rep_elapsed[med]
