@@ -4,7 +4,8 @@
 //   api_common.cpp    error text, container/heap replay, cross-shard merge (host only)
 //   scan_query.cpp    query preparation (swizzle / digit planes) and the key error bounds
 //   scan_handle.cpp   handle lifetime, contexts, mutations, options, statistics
-//   scan_topk.cpp     one-sweep-per-query pipeline, certification, escalation, exact replay
+//   scan_topk.cpp     the batch pipeline of top-k and radius calls; one-sweep-per-query top-k, certification,
+//                     escalation, exact replay
 //   scan_mq.cpp       shared (multi-query) sweeps on the matrix cores
 //   scan_sketch.cpp   8-bit sketch pre-pass
 //   scan_radius.cpp   radius search (single, batch, coalesced)
@@ -24,6 +25,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <deque>
+#include <functional>
 #include <mutex>
 #include <new>
 #include <string>
@@ -345,13 +347,9 @@ struct szg_index {
     // settled by measurement (rounds 1-3): compile-time facts since round 4, A/B through -D and `make variant`
     static constexpr int blocks_per_cu = 0;     // 0 = waves per CU chosen from the row format (scan_geometry)
     static constexpr int block_threads = 256;
-    static constexpr int first_batch = 4;       // queries of a call's first launch: the card starts sweeping sooner
-    static constexpr int short_call = 32;       // calls of up to this many one-sweep queries are ONE batch on the scan stream
-    static constexpr int radius_sort = 1;       // a radius batch's re-ranked hits are sorted by distance on the device
     static constexpr int shape_kernels = 1;     // row-shape-specialised kernels where they exist
     static constexpr int ring = 0;              // 8 = always the deep piece ring
     static constexpr int mq_i8 = 1;             // 8- / 4-bit rows: exact integer shared sweep (v_mfma_i32_16x16x64_i8)
-    static constexpr int mq_i8_groups = 2;      // ... one launch walks the passes of up to two groups of 48 queries
     static constexpr int mq_bf16 = 1;           // 64- / 32- / 16-bit rows: shared sweep on bfloat16 roundings, certified
                                                 // against its own bound and re-ranked in float64 like every other path
     static constexpr int mq_overlap = 1;        // a batch's threshold pass and tail on the context's stream beside the
@@ -498,33 +496,107 @@ int ensure_host(T **p, size_t *cap, size_t need)
 }
 
 
-struct Ticket {
-    int first = 0, nq = 0;       // queries [first, first+nq) of the call
-    std::vector<Ctx *> ctx;      // one per shard
-    std::vector<QMeta> meta;
-    int kp = 0, kp_wide = 0;
-    bool failed = false;         // enqueueing failed part-way: drain and release only
-    bool any_mask = false;       // some query of the batch carries a filter mask
-    bool lazy_single = false;    // shared sweep: the queries' single-query form (h_qsw / d_qsw) has not been built
-    szg_index *owner = nullptr;
-    Ticket() = default;
-    Ticket(Ticket &&) = default;
-    Ticket(const Ticket &) = delete;
-    Ticket &operator=(const Ticket &) = delete;
-    // a ticket dropped with contexts still attached (an exception unwinding the call) drains
-    // and returns them, so later calls do not wait for contexts that never come back
-    ~Ticket()
+// ---- the batch pipeline of a search call (top-k and radius; scan_topk.cpp) ----------------------------------------
+//
+// A call's queries travel in batches (up to 16 with one sweep each, or up to 96 sharing one sweep), as many in flight
+// as the shards have free contexts: a batch is planned (plan_batch), borrows one context per shard, is staged (its
+// queries prepared once, uploaded and its sweeps enqueued on every shard) and finished in order (run_batches).
+
+constexpr int kFirstBatch = 4;  // queries of a call's first (and last) one-sweep batch: the card starts sweeping sooner
+constexpr int kShortCall = 32;  // calls of up to this many one-sweep queries are ONE batch on the scan stream
+
+// the filter masks of a call's queries: one pointer per query (null = unfiltered), or masks back to back with one
+// bit per row of the index, or none
+struct QueryMasks {
+    const uint64_t *bits;
+    const uint64_t *const *ptrs;
+    size_t stride = 0;  // words per mask of `bits`
+    QueryMasks(const szg_index *ix, const uint64_t *bits_, const uint64_t *const *ptrs_) : bits(bits_), ptrs(ptrs_)
     {
-        if (!owner) return;
-        for (size_t s = 0; s < ctx.size(); s++) {
-            if (!ctx[s]) continue;
-            (void)hipSetDevice(owner->shards[s]->device);
-            (void)hipStreamSynchronize(ctx[s]->work);
-            (void)hipStreamSynchronize(ctx[s]->stream);
-            ctx[s]->mq_fused_used = false;
-            ctx_release(owner->shards[s], ctx[s]);
-        }
+        uint64_t total_rows = 0;
+        for (const Shard *sh : ix->shards) total_rows += sh->n_rows;
+        stride = (total_rows + 63) / 64;
+    }
+    const uint64_t *operator()(int qi) const
+    {
+        if (ptrs) return ptrs[qi];
+        return bits ? bits + (size_t)qi * stride : nullptr;
     }
 };
+
+// one batch of a call: queries [first, first+nq) and the contexts it has borrowed
+struct Batch {
+    szg_index *ix = nullptr;     // owner of the contexts
+    int first = 0, nq = 0;
+    int nb = 0;                  // > 0: the batch shares one sweep (query blocks of 16)
+    bool single = false;         // the whole call is this one batch (a short call)
+    int early_n = 0;             // ... whose first early_n queries' tail runs beside its last sweeps (Ctx::early_n)
+    bool any_mask = false;       // some query of the batch carries a filter mask
+    bool failed = false;         // enqueueing failed part-way: drain and release only
+    std::vector<Ctx *> ctx;      // one per shard (null: the shard is empty)
+    Batch() = default;
+    Batch(Batch &&) = default;
+    Batch(const Batch &) = delete;
+    Batch &operator=(const Batch &) = delete;
+    // a batch dropped with contexts still attached (a failure, an exception unwinding the call) drains and returns
+    // them, so later calls do not wait for contexts that never come back
+    ~Batch() { drain(); }
+    bool acquire(bool may_block);  // one context per non-empty shard; false (holding none) if one is not free
+    void release();
+    void drain();                  // wait for the contexts' streams, then release
+    // the filter masks of the batch's queries (sets any_mask)
+    std::vector<const uint64_t *> masks(const QueryMasks &mask_of);
+};
+
+// How a call splits into batches: the caller's parameters
+struct BatchRules {
+    int batch;        // queries of a one-sweep-per-query batch
+    int edge;         // ... of the call's first and last such batch
+    int short_max;    // a call of up to this many one-sweep queries is ONE batch on the scan stream
+    bool early_tail;  // ... whose first queries' tail runs beside its last sweeps
+    bool radius;      // radius batches (mq_uses_i8)
+};
+// the next batch of a call of n_queries, from query q0; nb = the query blocks of a shared sweep (0: one sweep per query)
+void plan_batch(szg_index *ix, int n_queries, int q0, int nb, const BatchRules &r, Batch *b);
+
+// Prepare the batch's queries q[0, nq) ONCE on its first context -- the single-query form (swizzled floats / digit
+// planes) for a batch of one sweep per query, the integer queries of the int8 shared sweep when int_planes -- and copy
+// the forms and constants to the other shards' contexts.  adjust(j, meta): the caller's touches on query j's constants
+// before they are copied.
+int stage_query_forms(szg_index *ix, Batch &b, const double *q, bool int_planes,
+                      const std::function<void(int, QMeta &)> &adjust);
+// query j of a shared-sweep batch in the single-query kernels' form, built only when it is needed (an escalation, a
+// radius query that overflows the batch's buffers): prepared once, uploaded on every shard's `work` stream;
+// *meta = its constants
+int stage_single_form(szg_index *ix, Batch &b, const double *q, int j, QMeta *meta);
+
+// The in-flight loop of a call: plan a batch, borrow its contexts (none free: finish the oldest batch in flight
+// first), stage it, and in the end finish the rest in order.  hand_over (optional): takes every staged batch instead
+// (a finisher thread: acquire then blocks until it gives contexts back); false once that thread has failed.
+template <class B, class Call>
+int run_batches(Call &call, const std::function<bool(B &&)> &hand_over = nullptr)
+{
+    std::deque<B> inflight;
+    int rc = SZG_OK;
+    for (int q0 = 0; q0 < call.n_queries && rc == SZG_OK;) {
+        B b = call.plan(q0);
+        if (!b.acquire(hand_over || inflight.empty())) {  // no free context: finish the oldest batch first
+            rc = call.finish(inflight.front());
+            inflight.pop_front();
+            continue;
+        }
+        rc = call.stage(b);
+        b.failed = rc != SZG_OK;  // nothing to gather: finish() only drains and releases
+        q0 += b.nq;
+        if (!hand_over) inflight.push_back(std::move(b));
+        else if (!hand_over(std::move(b))) break;
+    }
+    while (!inflight.empty()) {
+        const int r2 = call.finish(inflight.front());
+        if (rc == SZG_OK) rc = r2;
+        inflight.pop_front();
+    }
+    return rc;
+}
 
 }  // namespace szgi

@@ -54,24 +54,11 @@ void radius_assemble(std::vector<HeapItem> &cs, bool presorted, std::vector<Heap
     h.drain(out);
 }
 
-struct RadiusCall;
-struct RadiusTicket {
-    int first = 0, nq = 0;
-    std::vector<Ctx *> ctx;       // one per shard
-    std::vector<float> thr;       // key threshold per query (of the sweep that runs: shared or one per query)
+struct RadiusBatch : Batch {
+    std::vector<float> thr;        // key threshold per query (of the sweep that runs: shared or one per query)
     std::vector<float> thr_single; // ... of the single-query collect sweep (a query that overflows is swept again on its own)
-    int nb = 0;                   // > 0: the batch shares ONE sweep (query blocks of 16)
-    std::vector<size_t> cap;      // per shard: entries per sweep of this batch's buffers
-    std::vector<uint8_t> copied;  // per shard: the block of re-ranked hits was copied back at enqueue time
-    std::vector<uint8_t> sorted;  // per shard: lists of up to kSortHitsMax hits arrive sorted by distance
-    bool any_mask = false;
-    bool failed = false;
-    RadiusCall *owner = nullptr;
-    RadiusTicket() = default;
-    RadiusTicket(RadiusTicket &&) = default;
-    RadiusTicket(const RadiusTicket &) = delete;
-    RadiusTicket &operator=(const RadiusTicket &) = delete;
-    ~RadiusTicket();  // a ticket dropped with contexts attached (error return, exception) drains and returns them
+    std::vector<size_t> cap;       // per shard: entries per sweep of this batch's buffers
+    std::vector<uint8_t> copied;   // per shard: the block of re-ranked hits was copied back at enqueue time
 };
 
 struct RadiusCall {
@@ -79,55 +66,36 @@ struct RadiusCall {
     const double *queries;
     int n_queries;
     const double *radii;
-    const uint64_t *const *masks;  // nullable; null entries unfiltered
+    QueryMasks mask_of;
     std::vector<std::vector<HeapItem>> *results;
     size_t n_sh = 0;
-    bool single_batch = false;  // the whole call is one batch (a short call)
 
-    void release(RadiusTicket &t)
-    {
-        for (size_t s = 0; s < n_sh; s++) {
-            if (!t.ctx[s]) continue;
-            if (t.failed) {
-                (void)hipSetDevice(ix->shards[s]->device);
-                (void)hipStreamSynchronize(t.ctx[s]->work);
-            }
-            ctx_release(ix->shards[s], t.ctx[s]);
-        }
-        t.ctx.assign(n_sh, nullptr);
-    }
-    bool acquire(RadiusTicket &t, bool may_block)
-    {
-        for (size_t s = 0; s < n_sh; s++) {
-            if (ix->shards[s]->n_rows == 0) continue;
-            Ctx *c = may_block ? ctx_acquire(ix->shards[s]) : ctx_try_acquire(ix->shards[s]);
-            if (!c) {
-                release(t);
-                return false;
-            }
-            // (a call that is one batch runs on the scan stream from upload to copy-back: scan_topk.cpp, acquire)
-            if (single_batch && ix->serialize_scans) c->work = ix->shards[s]->scan_stream;
-            t.ctx[s] = c;
-        }
-        return true;
-    }
-    int stage(RadiusTicket &t);
-    int enqueue_shard(RadiusTicket &t, size_t s);
-    int finish(RadiusTicket &t);
-    int run();
+    RadiusBatch plan(int q0);
+    int stage(RadiusBatch &t);
+    int enqueue_shard(RadiusBatch &t, size_t s);
+    int finish(RadiusBatch &t);
 };
 
-RadiusTicket::~RadiusTicket()
+RadiusBatch RadiusCall::plan(int q0)
 {
-    if (!owner) return;
-    bool any = false;
-    for (Ctx *c : ctx) any |= c != nullptr;
-    if (!any) return;
-    failed = true;  // (release() then waits for the streams first)
-    owner->release(*this);
+    RadiusBatch t;
+    const int left = n_queries - q0;
+    const int qpl = std::max(1, std::min(ix->queries_per_launch, szg::kMaxSweepsPerLaunch));
+    // two or more queries left: they share one sweep of the corpus (up to 96 per pass), as top-k batches do
+    const int nb = ix->radius_mq && left >= 2 ? mq_blocks(ix, left, true) : 0;
+    // a small first batch and a small last one, as top-k's; only the smallest calls are ONE batch here: a radius
+    // query's result assembly -- hundreds of hits to sort -- takes the host ~15 us, which a longer call hides behind
+    // the next batch's sweeps
+    const int edge = std::min(qpl, kFirstBatch);
+    plan_batch(ix, n_queries, q0, nb, BatchRules{qpl, edge, edge, false, true}, &t);
+    t.cap.assign(n_sh, 0);
+    t.copied.assign(n_sh, 0);
+    t.thr.assign(t.nq, 0.0f);
+    t.thr_single.assign(t.nq, 0.0f);
+    return t;
 }
 
-int RadiusCall::enqueue_shard(RadiusTicket &t, size_t s)
+int RadiusCall::enqueue_shard(RadiusBatch &t, size_t s)
 {
     Shard *sh = ix->shards[s];
     Ctx *c = t.ctx[s];
@@ -173,8 +141,7 @@ int RadiusCall::enqueue_shard(RadiusTicket &t, size_t s)
     HIPCHK(szg::launch_rerank(ix->bits, ix->metric, sh->rows, ix->layout, ix->dim, c->d_q64, c->d_collect, c->d_count,
                               (uint32_t)cap, t.nq, c->d_out, c->work, szg::kCandCountStride));
     // ... and each query's hits sorted by distance there too (lists of up to kSortHitsMax: the host only filters)
-    if (ix->radius_sort) HIPCHK(szg::launch_sort_hits(c->d_out, c->d_count, szg::kCandCountStride, (uint32_t)cap, t.nq, c->work));
-    t.sorted[s] = ix->radius_sort != 0;
+    HIPCHK(szg::launch_sort_hits(c->d_out, c->d_count, szg::kCandCountStride, (uint32_t)cap, t.nq, c->work));
     HIPCHK(hipMemcpyAsync(c->h_count, c->d_count, sizeof(uint32_t) * (size_t)t.nq * szg::kCandCountStride, hipMemcpyDeviceToHost,
                           c->work));
     // the re-ranked hits: while the batch's buffers are small (the usual hundreds of hits per query) the whole block
@@ -191,52 +158,24 @@ int RadiusCall::enqueue_shard(RadiusTicket &t, size_t s)
     return SZG_OK;
 }
 
-int RadiusCall::stage(RadiusTicket &t)
+int RadiusCall::stage(RadiusBatch &t)
 {
-    int rc = SZG_OK;
     const double *q = queries + (size_t)t.first * ix->dim;
-    std::vector<const uint64_t *> m(t.nq, nullptr);
-    for (int j = 0; j < t.nq; j++) {
-        m[j] = masks ? masks[t.first + j] : nullptr;
-        t.any_mask |= m[j] != nullptr;
-    }
+    const std::vector<const uint64_t *> m = t.masks(mask_of);
     const double t0 = now_us();
-    Ctx *c0 = nullptr;
     const bool int_planes = t.nb > 0 && mq_uses_i8(ix, true);
-    for (size_t s = 0; s < n_sh; s++) {
-        Ctx *c = t.ctx[s];
-        if (!c) continue;
-        if (int_planes && !c->h_mqQ) {
-            c->h_mqQ = (int32_t *)malloc(sizeof(int32_t) * (size_t)kMaxBatch * ix->dim);
-            if (!c->h_mqQ) return fail(SZG_E_NOMEM, "host scratch");
+    int rc = stage_query_forms(ix, t, q, int_planes, [&](int j, QMeta &meta) {
+        const double radius = radii[t.first + j];
+        if (t.nb == 0) {
+            t.thr_single[j] = t.thr[j] = radius_key_threshold(ix, radius, meta);
+            return;
         }
-        if (!c0) {
-            c0 = c;
-            for (int j = 0; j < t.nq; j++) {
-                // (a shared sweep stages its own image: the single-query form -- digit planes / swizzled floats, its
-                // quantization step and the threshold that goes with it -- is built in finish() for a query whose
-                // hits overflow the batch's buffers and which is then swept again on its own.  Building it here for
-                // every query was 1.4 us of the 2.5 us of host preparation per query of a cfg5 batch.)
-                if (t.nb > 0) {
-                    prep_query_meta(ix, q + (size_t)j * ix->dim, &c->meta[j]);
-                } else {
-                    prep_query(ix, q + (size_t)j * ix->dim, c->h_qsw + (size_t)j * ix->qsw_bytes, &c->meta[j]);
-                    t.thr_single[j] = t.thr[j] = radius_key_threshold(ix, radii[t.first + j], c->meta[j]);
-                }
-                if (t.nb > 0) {  // the shared sweep's arithmetic has its own error bound
-                    if (int_planes) prep_mq_int(ix, q + (size_t)j * ix->dim, &c->meta[j], c->h_mqQ + (size_t)j * ix->dim);
-                    QMeta m2 = c->meta[j];
-                    m2.mq = !int_planes;
-                    m2.mq_bf16 = mq_uses_bf16(ix, true);
-                    t.thr[j] = radius_key_threshold(ix, radii[t.first + j], m2);
-                }
-            }
-        } else {
-            if (t.nb == 0) memcpy(c->h_qsw, c0->h_qsw, ix->qsw_bytes * (size_t)t.nq);
-            if (int_planes) memcpy(c->h_mqQ, c0->h_mqQ, sizeof(int32_t) * (size_t)t.nq * ix->dim);
-            for (int j = 0; j < t.nq; j++) c->meta[j] = c0->meta[j];
-        }
-    }
+        QMeta m2 = meta;  // the shared sweep's arithmetic has its own error bound
+        m2.mq = !int_planes;
+        m2.mq_bf16 = mq_uses_bf16(ix, true);
+        t.thr[j] = radius_key_threshold(ix, radius, m2);
+    });
+    if (rc) return rc;
     const double t1 = now_us();
     for (size_t s = 0; s < n_sh && rc == SZG_OK; s++) {
         if (!t.ctx[s]) continue;
@@ -249,10 +188,10 @@ int RadiusCall::stage(RadiusTicket &t)
     return rc;
 }
 
-int RadiusCall::finish(RadiusTicket &t)
+int RadiusCall::finish(RadiusBatch &t)
 {
     if (t.failed) {
-        release(t);
+        t.drain();
         return SZG_OK;
     }
     int rc = SZG_OK;
@@ -306,7 +245,7 @@ int RadiusCall::finish(RadiusTicket &t)
             if (redo[j]) continue;
             cands[j].reserve(cands[j].size() + cnt[j]);
             if (cnt[j]) {
-                if (!t.sorted[s] || cnt[j] > (size_t)szg::kSortHitsMax || ++lists[j] > 1) presorted[j] = 0;
+                if (cnt[j] > (size_t)szg::kSortHitsMax || ++lists[j] > 1) presorted[j] = 0;
             }
             const double rad = radii[t.first + j];
             for (size_t i = off[j]; i < off[j] + cnt[j]; i++) {
@@ -320,21 +259,10 @@ int RadiusCall::finish(RadiusTicket &t)
             cands[j].clear();
             std::vector<Cand> all;
             const double tw = now_us();
-            if (t.nb > 0) {  // the single-query form of this query, now that it is needed (see stage())
-                const double *qj = queries + (size_t)(t.first + j) * ix->dim;
-                for (size_t s = 0; s < n_sh && rc == SZG_OK; s++) {
-                    Ctx *c = t.ctx[s];
-                    if (!c) continue;
-                    QMeta m;
-                    prep_query(ix, qj, c->h_qsw + (size_t)j * ix->qsw_bytes, &m);
-                    c->meta[j] = m;
-                    t.thr_single[j] = radius_key_threshold(ix, radii[t.first + j], m);
-                    hipError_t e = hipSetDevice(ix->shards[s]->device);
-                    if (e == hipSuccess)
-                        e = hipMemcpyAsync(c->d_qsw + (size_t)j * ix->qsw_bytes, c->h_qsw + (size_t)j * ix->qsw_bytes,
-                                           ix->qsw_bytes, hipMemcpyHostToDevice, c->work);
-                    if (e != hipSuccess) rc = fail(SZG_E_DEVICE, "hipMemcpyAsync(single-query form)", e);
-                }
+            if (t.nb > 0) {  // the single-query form of this query, now that it is needed
+                QMeta m;
+                rc = stage_single_form(ix, t, queries + (size_t)(t.first + j) * ix->dim, j, &m);
+                t.thr_single[j] = radius_key_threshold(ix, radii[t.first + j], m);
             }
             for (size_t s = 0; s < n_sh && rc == SZG_OK; s++)
                 if (t.ctx[s]) rc = run_collect(ix, ix->shards[s], t.ctx[s], j, t.thr_single[j], t.any_mask, &all);
@@ -352,62 +280,7 @@ int RadiusCall::finish(RadiusTicket &t)
         ix->stats.host_finish_us += now_us() - t0 - t_wait;
         if (rc == SZG_OK) ix->stats.queries += t.nq;
     }
-    release(t);
-    return rc;
-}
-
-int RadiusCall::run()
-{
-    n_sh = ix->shards.size();
-    results->assign(n_queries, {});
-    std::deque<RadiusTicket> inflight;
-    int rc = SZG_OK;
-    const int qpl = std::max(1, std::min(ix->queries_per_launch, szg::kMaxSweepsPerLaunch));
-    for (int q0 = 0; q0 < n_queries && rc == SZG_OK;) {
-        RadiusTicket t;
-        t.owner = this;
-        t.first = q0;
-        // a small first batch (the card starts sweeping after a few queries' preparation) and a small last one
-        // (what is left to do once the last sweep has ended is that batch's result assembly)
-        const int left = n_queries - q0;
-        const int edge = std::max(1, std::min(qpl, ix->first_batch > 0 ? ix->first_batch : qpl));
-        t.nq = std::min(qpl, left);
-        // two or more queries left: they share one sweep of the corpus (up to 96 per pass), as top-k batches do
-        t.nb = ix->radius_mq && left >= 2 ? mq_blocks(ix, left, true) : 0;
-        if (t.nb > 0) {
-            const int groups = t.nb == 3 && mq_uses_i8(ix, true) && ix->mq_i8_groups > 1 && left > 48 &&
-                                       szg::mq_i8_lds_bytes(ix->bits, ix->map.r16, 3, 2) <= 160u * 1024u
-                                   ? 2 : 1;
-            t.nq = std::min(left, 16 * t.nb * groups);
-        }
-        // (only the smallest calls are ONE batch here: a radius query's result assembly -- hundreds of hits to sort --
-        // takes the host ~15 us, which a longer call hides behind the next batch's sweeps)
-        single_batch = t.nb == 0 && q0 == 0 && ix->short_call > 0 && n_queries <= std::min(edge, ix->short_call);
-        if (single_batch) t.nq = n_queries;
-        else if (t.nb > 0) ;  // (a shared sweep takes what fits its image)
-        else if (q0 == 0 && left > edge) t.nq = edge;
-        else if (left > edge && left <= qpl + edge) t.nq = left - edge;
-        t.ctx.assign(n_sh, nullptr);
-        t.cap.assign(n_sh, 0);
-        t.copied.assign(n_sh, 0);
-        t.sorted.assign(n_sh, 0);
-        t.thr.assign(t.nq, 0.0f);
-        t.thr_single.assign(t.nq, 0.0f);
-        if (!acquire(t, inflight.empty())) {
-            rc = finish(inflight.front());
-            inflight.pop_front();
-            continue;
-        }
-        rc = stage(t);
-        t.failed = rc != SZG_OK;
-        inflight.push_back(std::move(t));
-        q0 += inflight.back().nq;
-    }
-    while (!inflight.empty()) {
-        const int r2 = finish(inflight.front());
-        if (rc == SZG_OK) rc = r2;
-        inflight.pop_front();
-    }
+    t.release();
     return rc;
 }
 
@@ -416,8 +289,9 @@ int RadiusCall::run()
 int search_radius_impl(szg_index *ix, const double *queries, int n_queries, const double *radii,
                        const uint64_t *const *masks, std::vector<std::vector<HeapItem>> *results)
 {
-    RadiusCall call{ix, queries, n_queries, radii, masks, results};
-    return call.run();
+    RadiusCall call{ix, queries, n_queries, radii, QueryMasks(ix, nullptr, masks), results, ix->shards.size()};
+    results->assign(n_queries, {});
+    return run_batches<RadiusBatch>(call);
 }
 
 }  // namespace szgi

@@ -262,13 +262,7 @@ int search_topk_sketch(szg_index *ix, const double *queries, int n_queries, int 
     if (rc) return rc;
     if (ix->sk_disabled) return search_topk_impl(ix, queries, n_queries, k, allow_bits, out_rows, out_dist, out_count, allow_ptrs);
     szg_index *sk = ix->sketch;
-    uint64_t total_rows = 0;
-    for (Shard *sh : ix->shards) total_rows += sh->n_rows;
-    const size_t allow_stride = (total_rows + 63) / 64;
-    auto mask_of = [&](int qi) -> const uint64_t * {
-        if (allow_ptrs) return allow_ptrs[qi];
-        return allow_bits ? allow_bits + (size_t)qi * allow_stride : nullptr;
-    };
+    const QueryMasks mask_of(ix, allow_bits, allow_ptrs);
     auto eligible = [&](const uint64_t *m, uint64_t r) -> bool {
         if (m && !((m[r >> 6] >> (r & 63)) & 1)) return false;
         for (const Shard *sh : ix->shards)

@@ -1,4 +1,5 @@
-// scan_topk.cpp -- the one-sweep-per-query pipeline: enqueue, certification, escalation, exact replay.
+// scan_topk.cpp -- the batch pipeline of search calls (scan_internal.h) and the one-sweep-per-query top-k pipeline:
+// enqueue, certification, escalation, exact replay.
 #include "scan_internal.h"
 
 namespace szgi {
@@ -423,26 +424,20 @@ int run_full_replay(szg_index *ix, std::vector<Ctx *> &ctx, int slot, const uint
 // + row_base) -- one link of the rank-to-rank chain that settles equal distances across shards (scan_comm.cpp)
 int replay_rows_into_heap(szg_index *ix, const double *query, const uint64_t *allow, int k, GoHeap *h)
 {
-    std::vector<Ctx *> ctx(ix->shards.size(), nullptr);
-    struct Release {
-        szg_index *ix;
-        std::vector<Ctx *> &ctx;
-        ~Release()
-        {
-            for (size_t s = 0; s < ctx.size(); s++)
-                if (ctx[s]) ctx_release(ix->shards[s], ctx[s]);
-        }
-    } release{ix, ctx};
+    Batch b;
+    b.ix = ix;
+    b.ctx.assign(ix->shards.size(), nullptr);
+    (void)b.acquire(true);
     for (size_t s = 0; s < ix->shards.size(); s++) {
-        Shard *sh = ix->shards[s];
-        if (sh->n_rows == 0) continue;
-        Ctx *c = ctx[s] = ctx_acquire(sh);
-        HIPCHK(hipSetDevice(sh->device));
+        Ctx *c = b.ctx[s];
+        if (!c) continue;
+        HIPCHK(hipSetDevice(ix->shards[s]->device));
         memcpy(c->h_q64, query, sizeof(double) * ix->dim);
         HIPCHK(hipMemcpyAsync(c->d_q64, c->h_q64, sizeof(double) * ix->dim, hipMemcpyHostToDevice, c->work));
     }
-    const int rc = replay_all_rows(ix, ctx, 0, allow, k, *h, ix->row_base);
+    const int rc = replay_all_rows(ix, b.ctx, 0, allow, k, *h, ix->row_base);
     if (rc == SZG_OK) {
+        b.release();  // (replay_all_rows has waited for every stream)
         std::lock_guard<std::mutex> lk(ix->stats_mu);
         ix->stats.full_replays++;
     }
@@ -541,120 +536,212 @@ int enqueue_sentinels(szg_index *ix, Shard *sh, Ctx *c, const std::vector<std::v
     return launch_sentinel_rerank(ix, sh, c, nq, st);
 }
 
-// ---- one szg_search_topk call -------------------------------------------------------------------------------------
-//
-// The queries travel in batches ("tickets": up to 16 with one sweep each, or up to 96 sharing one sweep), as many in
-// flight as the shards have free contexts.  stage() prepares and enqueues a batch on every shard; finish() waits
-// for it and runs the reference's result assembly per query (settle()).
-constexpr int kShortCallLast = 4;  // queries of a short call whose tail is left for after the final sweep
+// ---- the batch pipeline (scan_internal.h) -------------------------------------------------------------------------
 
-struct TopkCall {
-    szg_index *ix;
-    const double *queries;
-    int n_queries, k;
-    const uint64_t *allow_bits;          // n_queries masks back to back, or nullptr
-    const uint64_t *const *allow_ptrs;   // used instead when given: one mask pointer per query, null = unfiltered
-    uint64_t *out_rows;
-    double *out_dist;
-    int32_t *out_count;
-
-    size_t n_sh = 0, allow_stride = 0;
-    int kp = 0;
-    bool replay_all = false;  // K beyond the fused selection: every query takes the exact replay
-    bool single_batch = false;  // the whole call is one batch of sweeps (a short call)
-    int early_n = 0;            // ... whose first early_n queries' merges / re-rank / copy-back / assembly run beside its
-                                // last sweeps (Ctx::early_n)
-
-    const uint64_t *mask_of(int qi) const
-    {
-        if (allow_ptrs) return allow_ptrs[qi];
-        return allow_bits ? allow_bits + (size_t)qi * allow_stride : nullptr;
-    }
-    void release(Ticket &t)
-    {
-        for (size_t s = 0; s < n_sh; s++)
-            if (t.ctx[s]) ctx_release(ix->shards[s], t.ctx[s]);
-        t.ctx.assign(n_sh, nullptr);
-    }
-
-    int run();
-    bool acquire(Ticket &t, bool may_block);
-    int stage(Ticket &t, int nb, bool bf16_sweep);
-    int wait_shards(Ticket &t);
-    int stage_single_form(Ticket &t, int j);
-    void gather(Ticket &t, std::vector<std::vector<Cand>> *all, std::vector<double> *thr_min,
-                std::vector<uint8_t> *nan_first, int j0, int j1);
-    int settle(Ticket &t, int j, std::vector<Cand> &cands, double thr_min, bool nan_first, double *t_dev,
-               std::vector<HeapItem> *res, bool *defer = nullptr);
-    int finish(Ticket &t);
-};
-
-// one context per shard; never block while holding in-flight work
-bool TopkCall::acquire(Ticket &t, bool may_block)
+bool Batch::acquire(bool may_block)
 {
-    for (size_t s = 0; s < n_sh; s++) {
-        if (ix->shards[s]->n_rows == 0) continue;
-        Ctx *c = may_block ? ctx_acquire(ix->shards[s]) : ctx_try_acquire(ix->shards[s]);
+    for (size_t s = 0; s < ctx.size(); s++) {
+        Shard *sh = ix->shards[s];
+        if (sh->n_rows == 0) continue;
+        Ctx *c = may_block ? ctx_acquire(sh) : ctx_try_acquire(sh);
         if (!c) {
-            release(t);
+            release();
             return false;
         }
         // A call that is ONE batch has nothing to overlap with: uploads, sweeps, merges, re-rank and copy-back go
         // onto the shard's scan stream in order.  On the context's own stream every hand-over to and from the scan
         // stream is a cross-queue event wait, and those cost 20-100 us each on this platform (rocprofv3 timeline of
         // 20-query calls on a 125 K-row shard: the sweeps of a call's batches sat 24-105 us apart).
-        if (single_batch && ix->serialize_scans) {
-            c->work = ix->shards[s]->scan_stream;
+        if (single && ix->serialize_scans) {
+            c->work = sh->scan_stream;
             c->early_n = early_n;
         }
-        t.ctx[s] = c;
+        ctx[s] = c;
     }
     return true;
 }
 
-// prepare the ticket's queries ONCE (swizzled / digit-plane forms, constants; the other shards get copies) and
-// enqueue uploads, the first-k rows' distances and the sweeps on every shard
-int TopkCall::stage(Ticket &t, int nb, bool bf16_sweep)
+void Batch::release()
 {
-    int rc = SZG_OK;
-    const double *q = queries + (size_t)t.first * ix->dim;
-    std::vector<const uint64_t *> masks(t.nq);
-    for (int j = 0; j < t.nq; j++) {
-        masks[j] = mask_of(t.first + j);
-        t.any_mask |= masks[j] != nullptr;
+    for (size_t s = 0; s < ctx.size(); s++)
+        if (ctx[s]) ctx_release(ix->shards[s], ctx[s]);
+    std::fill(ctx.begin(), ctx.end(), nullptr);
+}
+
+void Batch::drain()
+{
+    for (size_t s = 0; s < ctx.size(); s++) {
+        if (!ctx[s]) continue;
+        (void)hipSetDevice(ix->shards[s]->device);
+        (void)hipStreamSynchronize(ctx[s]->work);
+        (void)hipStreamSynchronize(ctx[s]->stream);
+        ctx[s]->mq_fused_used = false;
     }
+    release();
+}
+
+std::vector<const uint64_t *> Batch::masks(const QueryMasks &mask_of)
+{
+    std::vector<const uint64_t *> m(nq);
+    for (int j = 0; j < nq; j++) {
+        m[j] = mask_of(first + j);
+        any_mask |= m[j] != nullptr;
+    }
+    return m;
+}
+
+constexpr int kShortCallLast = 4;  // queries of a short call whose tail is left for after the final sweep
+
+void plan_batch(szg_index *ix, int n_queries, int q0, int nb, const BatchRules &r, Batch *b)
+{
+    const int left = n_queries - q0;
+    b->ix = ix;
+    b->first = q0;
+    b->nb = nb;
+    b->ctx.assign(ix->shards.size(), nullptr);
+    if (nb > 0) {
+        // (int8 sweeps: two groups of 48 per launch when that many queries are waiting and both images fit LDS)
+        const bool two_groups = nb == 3 && mq_uses_i8(ix, r.radius, left) && left > 48 &&
+                                szg::mq_i8_lds_bytes(ix->bits, ix->map.r16, 3, 2) <= 160u * 1024u;
+        b->nq = std::min(left, 16 * nb * (two_groups ? 2 : 1));
+        return;
+    }
+    // A short call with one sweep per query is ONE batch on the scan stream (launches of <= 16 sweeps back to back,
+    // uploads ahead of them, no event on the critical path).  From 8 queries on, the merges, re-rank, copy-back and
+    // host assembly of all but its last few queries run on the context's own stream and the calling thread WHILE the
+    // last sweeps run; only those last queries' tail is left after the final sweep.
+    if (q0 == 0 && n_queries <= r.short_max) {
+        b->single = true;
+        b->nq = n_queries;
+        static const bool no_early = getenv("SZG_NO_EARLY_TAIL") != nullptr;  // (A/B hook of scripts/dev_short.py)
+        if (r.early_tail && n_queries >= 8 && ix->serialize_scans && !no_early)
+            b->early_n = n_queries - std::min(kShortCallLast, n_queries / 2);
+        return;
+    }
+    // the call's FIRST batch is small, so that the card starts sweeping after a few microseconds of preparation
+    // instead of a whole batch's (the next batch is prepared while it sweeps) ... and its LAST one too: what is left
+    // to do once the last sweep has ended is that batch's merges, re-rank, copy-back and result assembly
+    b->nq = std::min(r.batch, left);
+    if (left > r.edge) {
+        if (q0 == 0) b->nq = std::min(b->nq, r.edge);
+        else if (left <= r.batch + r.edge) b->nq = left - r.edge;
+    }
+}
+
+int stage_query_forms(szg_index *ix, Batch &b, const double *q, bool int_planes,
+                      const std::function<void(int, QMeta &)> &adjust)
+{
+    // (a shared sweep stages its own image: the single-query form is built by stage_single_form for a query that
+    // needs it.  Building it here for every query was 1.4 us of the 2.5 us of host preparation per query of a cfg5
+    // radius batch.)
+    const bool single_form = b.nb == 0;
+    Ctx *c0 = nullptr;
+    for (Ctx *c : b.ctx) {
+        if (!c) continue;
+        if (int_planes && !c->h_mqQ) {
+            c->h_mqQ = (int32_t *)malloc(sizeof(int32_t) * (size_t)kMaxBatch * ix->dim);
+            if (!c->h_mqQ) return fail(SZG_E_NOMEM, "host scratch");
+        }
+        if (c0) {
+            if (single_form) memcpy(c->h_qsw, c0->h_qsw, ix->qsw_bytes * (size_t)b.nq);
+            if (int_planes) memcpy(c->h_mqQ, c0->h_mqQ, sizeof(int32_t) * (size_t)b.nq * ix->dim);
+            std::copy(c0->meta, c0->meta + b.nq, c->meta);
+            continue;
+        }
+        c0 = c;
+        for (int j = 0; j < b.nq; j++) {
+            const double *qj = q + (size_t)j * ix->dim;
+            if (single_form) prep_query(ix, qj, c->h_qsw + (size_t)j * ix->qsw_bytes, &c->meta[j]);
+            else prep_query_meta(ix, qj, &c->meta[j]);
+            if (int_planes) prep_mq_int(ix, qj, &c->meta[j], c->h_mqQ + (size_t)j * ix->dim);
+            adjust(j, c->meta[j]);
+        }
+    }
+    return SZG_OK;
+}
+
+int stage_single_form(szg_index *ix, Batch &b, const double *q, int j, QMeta *meta)
+{
+    const size_t off = (size_t)j * ix->qsw_bytes;
+    Ctx *c0 = nullptr;
+    for (size_t s = 0; s < b.ctx.size(); s++) {
+        Ctx *c = b.ctx[s];
+        if (!c) continue;
+        if (c0) {
+            memcpy(c->h_qsw + off, c0->h_qsw + off, ix->qsw_bytes);
+        } else {
+            c0 = c;
+            prep_query(ix, q, c->h_qsw + off, meta);
+        }
+        c->meta[j] = *meta;
+        HIPCHK(hipSetDevice(ix->shards[s]->device));
+        HIPCHK(hipMemcpyAsync(c->d_qsw + off, c->h_qsw + off, ix->qsw_bytes, hipMemcpyHostToDevice, c->work));
+    }
+    return SZG_OK;
+}
+
+// ---- one szg_search_topk call -------------------------------------------------------------------------------------
+//
+// stage() prepares and enqueues a batch on every shard; finish() waits for it and runs the reference's result
+// assembly per query (settle()).
+struct TopkBatch : Batch {
+    std::vector<QMeta> meta;  // the queries' constants, with the flags of the path the batch was staged for
+    bool bf16 = false;        // the shared sweep is the bfloat16 one
+    int kp_wide = 0;          // candidates per query of lists that hold bfloat16-sweep keys
+};
+
+struct TopkCall {
+    szg_index *ix;
+    const double *queries;
+    int n_queries, k;
+    QueryMasks mask_of;
+    uint64_t *out_rows;
+    double *out_dist;
+    int32_t *out_count;
+
+    size_t n_sh = 0;
+    int kp = 0;
+    bool replay_all = false;  // K beyond the fused selection: every query takes the exact replay
+
+    int run();
+    TopkBatch plan(int q0);
+    int stage(TopkBatch &t);
+    int wait_shards(TopkBatch &t);
+    void gather(TopkBatch &t, std::vector<std::vector<Cand>> *all, std::vector<double> *thr_min,
+                std::vector<uint8_t> *nan_first, int j0, int j1);
+    int settle(TopkBatch &t, int j, std::vector<Cand> &cands, double thr_min, bool nan_first, double *t_dev,
+               std::vector<HeapItem> *res, bool *defer = nullptr);
+    int finish(TopkBatch &t);
+};
+
+TopkBatch TopkCall::plan(int q0)
+{
+    TopkBatch t;
+    const int nb = replay_all ? 0 : mq_blocks(ix, n_queries - q0);  // > 0: the batch shares one sweep
+    const int batch = std::max(1, std::min(ix->query_batch, kMaxBatch));
+    plan_batch(ix, n_queries, q0, nb, BatchRules{batch, kFirstBatch, std::min(kShortCall, kMaxBatch), true, false}, &t);
+    t.bf16 = nb > 0 && mq_uses_bf16(ix, false, t.nq);
+    // lists of bfloat16-sweep keys (matrix form): the error band holds more rows than the float32 one's, keep
+    // enough candidates for the k-th result to clear it
+    t.kp_wide = t.bf16 ? std::min(4096, std::max(kp, k + std::max(ix->mq_bf16_slack, k / 2))) : kp;
+    t.meta.assign(t.nq, QMeta{});
+    return t;
+}
+
+// prepare the batch's queries ONCE (swizzled / digit-plane forms, constants; the other shards get copies) and
+// enqueue uploads, the first-k rows' distances and the sweeps on every shard
+int TopkCall::stage(TopkBatch &t)
+{
+    const double *q = queries + (size_t)t.first * ix->dim;
+    const std::vector<const uint64_t *> masks = t.masks(mask_of);
     const uint64_t *const *mptr = t.any_mask ? masks.data() : nullptr;
     const double t_prep0 = now_us();
-    Ctx *c0 = nullptr;
-    const bool int_planes = nb > 0 && mq_uses_i8(ix, false, t.nq);
-    t.lazy_single = nb > 0 && !replay_all;
-    for (size_t s = 0; s < n_sh && rc == SZG_OK; s++) {
-        if (ix->shards[s]->n_rows == 0) continue;
-        Ctx *cx = t.ctx[s];
-        if (int_planes && !cx->h_mqQ) {
-            cx->h_mqQ = (int32_t *)malloc(sizeof(int32_t) * (size_t)kMaxBatch * ix->dim);
-            if (!cx->h_mqQ) {
-                rc = fail(SZG_E_NOMEM, "host scratch");  // the ticket is still finished by the caller
-                break;
-            }
-        }
-        if (!c0) {
-            c0 = cx;
-            for (int j = 0; j < t.nq; j++) {
-                // (a shared sweep stages its own image; the single-query form is built if a query escalates)
-                if (t.lazy_single) prep_query_meta(ix, q + (size_t)j * ix->dim, &t.meta[j]);
-                else prep_query(ix, q + (size_t)j * ix->dim, cx->h_qsw + (size_t)j * ix->qsw_bytes, &t.meta[j]);
-                t.meta[j].mq = nb > 0 && !mq_uses_i8(ix, false, t.nq);  // the integer sweeps keep the integer bound
-                t.meta[j].mq_bf16 = bf16_sweep;
-                if (int_planes) prep_mq_int(ix, q + (size_t)j * ix->dim, &t.meta[j], cx->h_mqQ + (size_t)j * ix->dim);
-                cx->meta[j] = t.meta[j];
-            }
-        } else {
-            if (!t.lazy_single) memcpy(cx->h_qsw, c0->h_qsw, ix->qsw_bytes * (size_t)t.nq);
-            if (int_planes) memcpy(cx->h_mqQ, c0->h_mqQ, sizeof(int32_t) * (size_t)t.nq * ix->dim);
-            for (int j = 0; j < t.nq; j++) cx->meta[j] = t.meta[j];
-        }
-    }
+    const bool int_planes = t.nb > 0 && mq_uses_i8(ix, false, t.nq);
+    int rc = stage_query_forms(ix, t, q, int_planes, [&](int j, QMeta &m) {
+        m.mq = t.nb > 0 && !int_planes;  // the integer sweeps keep the integer bound
+        m.mq_bf16 = t.bf16;
+        t.meta[j] = m;
+    });
     // rows consider() pushes unconditionally: the first k eligible ones per query
     std::vector<std::vector<uint64_t>> sent;
     if (rc == SZG_OK && ix->tie_mode == 0 && !replay_all) {
@@ -670,15 +757,15 @@ int TopkCall::stage(Ticket &t, int nb, bool bf16_sweep)
         if (sh->n_rows == 0) continue;
         t.ctx[s]->sent_n = 0;
         t.ctx[s]->sent_deferred = false;
-        rc = enqueue_queries(ix, sh, t.ctx[s], q, t.nq, mptr, !t.lazy_single);
+        rc = enqueue_queries(ix, sh, t.ctx[s], q, t.nq, mptr, t.nb == 0);
         // (before the sweeps: on the context's stream this runs while the scan stream sweeps; a shared sweep whose
         // tail is the refine launch takes the rows along in its one rerank instead)
         if (rc == SZG_OK && !sent.empty())
             rc = enqueue_sentinels(ix, sh, t.ctx[s], sent, t.nq,
-                                   nb > 0 && mq_tail_takes_sentinels(ix, sh, t.kp, t.kp_wide, t.nq, nb));
+                                   t.nb > 0 && mq_tail_takes_sentinels(ix, sh, kp, t.kp_wide, t.nq, t.nb));
         if (rc == SZG_OK && !replay_all)
-            rc = nb ? enqueue_topk_mq(ix, sh, t.ctx[s], t.kp, t.kp_wide, t.nq, nb, t.any_mask)
-                    : enqueue_topk(ix, sh, t.ctx[s], kp, t.nq, t.any_mask);
+            rc = t.nb ? enqueue_topk_mq(ix, sh, t.ctx[s], kp, t.kp_wide, t.nq, t.nb, t.any_mask)
+                      : enqueue_topk(ix, sh, t.ctx[s], kp, t.nq, t.any_mask);
         if (rc == SZG_OK && replay_all && ix->timing >= 2) {
             const hipError_t e = hipEventRecord(t.ctx[s]->ev_all1, t.ctx[s]->work);
             if (e != hipSuccess) rc = fail(SZG_E_DEVICE, "hipEventRecord", e);
@@ -691,28 +778,9 @@ int TopkCall::stage(Ticket &t, int nb, bool bf16_sweep)
     return rc;
 }
 
-// query j of a shared-sweep batch in the single-query kernels' form (swizzled floats / digit planes + their
-// constants), on every shard: built only when the query escalates
-int TopkCall::stage_single_form(Ticket &t, int j)
-{
-    const double *q = queries + (size_t)(t.first + j) * ix->dim;
-    for (size_t s = 0; s < n_sh; s++) {
-        Ctx *c = t.ctx[s];
-        if (!c) continue;
-        QMeta m;
-        prep_query(ix, q, c->h_qsw + (size_t)j * ix->qsw_bytes, &m);
-        t.meta[j].qscale = c->meta[j].qscale = m.qscale;
-        t.meta[j].qconst = c->meta[j].qconst = m.qconst;
-        HIPCHK(hipSetDevice(ix->shards[s]->device));
-        HIPCHK(hipMemcpyAsync(c->d_qsw + (size_t)j * ix->qsw_bytes, c->h_qsw + (size_t)j * ix->qsw_bytes, ix->qsw_bytes,
-                              hipMemcpyHostToDevice, c->work));
-    }
-    return SZG_OK;
-}
-
-// wait for the ticket's device work; a shared sweep whose candidate buffer overflowed (threshold from the prefix too
+// wait for the batch's device work; a shared sweep whose candidate buffer overflowed (threshold from the prefix too
 // loose: duplicates, sorted corpora) is redone through the score matrix
-int TopkCall::wait_shards(Ticket &t)
+int TopkCall::wait_shards(TopkBatch &t)
 {
     int rc = SZG_OK;
     for (size_t s = 0; s < n_sh && rc == SZG_OK; s++) {
@@ -736,7 +804,7 @@ int TopkCall::wait_shards(Ticket &t)
             ix->stats.mq_bf16_sweeps -= (c->mq_stage2 || c->mq_bf16_used) ? 1 : 0;
             ix->stats.mq_fallbacks += 1;
         }
-        rc = enqueue_topk_mq(ix, sh, c, t.kp, t.kp_wide, t.nq, c->mq_nb, c->mq_has_allow, true);
+        rc = enqueue_topk_mq(ix, sh, c, kp, t.kp_wide, t.nq, c->mq_nb, c->mq_has_allow, true);
         if (rc == SZG_OK) {
             e = hipStreamSynchronize(c->work);
             if (e != hipSuccess) rc = fail(SZG_E_DEVICE, "hipStreamSynchronize", e);
@@ -748,7 +816,7 @@ int TopkCall::wait_shards(Ticket &t)
 
 // every query's candidates, the lists' lower bound and the first-k NaN flag -- taken before anything else, since the
 // escalation and replay paths reuse the contexts' output buffers
-void TopkCall::gather(Ticket &t, std::vector<std::vector<Cand>> *all, std::vector<double> *thr_min,
+void TopkCall::gather(TopkBatch &t, std::vector<std::vector<Cand>> *all, std::vector<double> *thr_min,
                       std::vector<uint8_t> *nan_first, int j0, int j1)
 {
     for (int j = j0; j < j1; j++) {
@@ -773,7 +841,7 @@ void TopkCall::gather(Ticket &t, std::vector<std::vector<Cand>> *all, std::vecto
 // heap history.  *t_dev accumulates the time spent waiting on device passes.
 // defer (non-null): no device pass may be started now (the call's last sweeps are still running and own the
 // contexts' buffers) -- a query that needs one is reported back and settled again once everything has been gathered
-int TopkCall::settle(Ticket &t, int j, std::vector<Cand> &cands, double thr_min, bool nan_first, double *t_dev,
+int TopkCall::settle(TopkBatch &t, int j, std::vector<Cand> &cands, double thr_min, bool nan_first, double *t_dev,
                      std::vector<HeapItem> *res, bool *defer)
 {
     const uint64_t *allow = mask_of(t.first + j);
@@ -819,9 +887,12 @@ int TopkCall::settle(Ticket &t, int j, std::vector<Cand> &cands, double thr_min,
         double thr = INFINITY;
         cands.clear();
         const double td = now_us();
-        if (t.lazy_single) {  // the escalation sweep is the single-query kernel: it wants the query in ITS form
-            rc = stage_single_form(t, j);
+        if (t.nb > 0) {  // the escalation sweep is the single-query kernel: it wants the query in ITS form
+            QMeta m;
+            rc = stage_single_form(ix, t, queries + (size_t)(t.first + j) * ix->dim, j, &m);
             if (rc) return rc;
+            t.meta[j].qscale = m.qscale;
+            t.meta[j].qconst = m.qconst;
         }
         if ((int)res->size() == k && std::isfinite(kmax) && !zero_query) {
             QMeta single = t.meta[j];  // (now with the single-query path's quantization step)
@@ -865,17 +936,10 @@ int TopkCall::settle(Ticket &t, int j, std::vector<Cand> &cands, double thr_min,
 }
 
 // result assembly for one finished batch
-int TopkCall::finish(Ticket &t)
+int TopkCall::finish(TopkBatch &t)
 {
     if (t.failed) {  // enqueueing failed part-way: drain and release; the enqueue error is already the call's return code
-        for (size_t s = 0; s < n_sh; s++) {
-            if (!t.ctx[s]) continue;
-            (void)hipSetDevice(ix->shards[s]->device);
-            (void)hipStreamSynchronize(t.ctx[s]->work);
-            (void)hipStreamSynchronize(t.ctx[s]->stream);
-            t.ctx[s]->mq_fused_used = false;
-        }
-        release(t);
+        t.drain();
         return SZG_OK;
     }
     double t_dev = 0;  // time spent waiting on escalation / replay passes (device work)
@@ -948,16 +1012,13 @@ int TopkCall::finish(Ticket &t)
         ix->stats.host_finish_us += now_us() - t_fin0 - t_dev;
         if (rc == SZG_OK) ix->stats.queries += t.nq;
     }
-    release(t);
+    t.release();
     return rc;
 }
 
 int TopkCall::run()
 {
     n_sh = ix->shards.size();
-    uint64_t total_rows = 0;
-    for (Shard *s : ix->shards) total_rows += s->n_rows;
-    allow_stride = (total_rows + 63) / 64;
     kp = k + std::max(ix->slack_min, k / 2);
     // The reference bounds K by nothing (collection.go:606-619).  The fused selection keeps kp candidates per wave in
     // LDS; beyond that (kp > 4096 or 64 KiB of lists) every query of the call takes the exact replay: float64
@@ -969,18 +1030,14 @@ int TopkCall::run()
     }
     if (replay_all) kp = 1;  // the batches only stage their queries
 
-    std::deque<Ticket> inflight;
-    int rc = SZG_OK;
-    const int B1 = std::max(1, std::min(ix->query_batch, kMaxBatch));
-
     // A call of several shared-sweep batches is bound by its host work (3-4 us per query against 2.7-3.7 us of GPU
     // time for the int8 and 16-bit sweeps): a second thread takes the finished batches -- waits, candidate
-    // assembly, certification, output -- while this one prepares and enqueues.  The hand-over is the ticket queue;
+    // assembly, certification, output -- while this one prepares and enqueues.  The hand-over is the batch queue;
     // contexts are the flow control (acquire blocks until the finisher has released one).
     struct Finisher {
         std::mutex mu;
         std::condition_variable cv;
-        std::deque<Ticket> q;
+        std::deque<TopkBatch> q;
         bool done = false;
         int rc = SZG_OK;
         std::string err;
@@ -996,7 +1053,7 @@ int TopkCall::run()
             cv.notify_one();
             th.join();
         }
-        ~Finisher() { stop(); }  // (an exception unwinding the call: the queued tickets are still finished first)
+        ~Finisher() { stop(); }  // (an exception unwinding the call: the queued batches are still finished first)
     } fin;
     bool threaded = false;
     {
@@ -1010,7 +1067,7 @@ int TopkCall::run()
                     std::unique_lock<std::mutex> lk(fin.mu);
                     fin.cv.wait(lk, [&] { return !fin.q.empty() || fin.done; });
                     if (fin.q.empty()) return;
-                    Ticket t(std::move(fin.q.front()));
+                    TopkBatch t(std::move(fin.q.front()));
                     fin.q.pop_front();
                     lk.unlock();
                     int r;
@@ -1021,7 +1078,7 @@ int TopkCall::run()
                     } catch (...) {
                         r = fail(SZG_E_DEVICE, "unexpected exception");
                     }
-                    if (r != SZG_OK && !fin.failed.load()) {  // (every ticket is still finished: its contexts go back)
+                    if (r != SZG_OK && !fin.failed.load()) {  // (every batch is still finished: its contexts go back)
                         fin.rc = r;
                         fin.err = szg_last_error();
                         fin.failed.store(true);
@@ -1032,77 +1089,21 @@ int TopkCall::run()
             threaded = false;  // no thread to be had: this one does both
         }
     }
-    auto hand_over = [&](Ticket &&t) {
-        {
-            std::lock_guard<std::mutex> lk(fin.mu);
-            fin.q.push_back(std::move(t));
-        }
-        fin.cv.notify_one();
-    };
-    for (int q0 = 0; q0 < n_queries && rc == SZG_OK && !fin.failed.load();) {
-        Ticket t;
-        t.owner = ix;
-        t.first = q0;
-        const int left = n_queries - q0;
-        const int nb = replay_all ? 0 : mq_blocks(ix, left);  // > 0: the batch shares one sweep
-        // (int8 sweeps: two groups of 48 per launch when that many queries are waiting and both images fit LDS)
-        const int groups = nb == 3 && mq_uses_i8(ix, false, left) && ix->mq_i8_groups > 1 && left > 48 &&
-                                   szg::mq_i8_lds_bytes(ix->bits, ix->map.r16, 3, 2) <= 160u * 1024u
-                               ? 2 : 1;
-        t.nq = nb ? std::min(left, 16 * nb * groups) : std::min(B1, left);
-        // A short call with one sweep per query is ONE batch on the scan stream (launches of <= 16 sweeps back to
-        // back, uploads ahead of them, no event on the critical path).  From 8 queries on, the merges, re-rank,
-        // copy-back and host assembly of all but its last few queries run on the context's own stream and the
-        // calling thread WHILE the last sweeps run; only those last queries' tail is left after the final sweep.
-        single_batch = !nb && q0 == 0 && ix->short_call > 0 && n_queries <= std::min(ix->short_call, kMaxBatch);
-        early_n = 0;
-        if (single_batch) {
-            t.nq = n_queries;
-            static const bool no_early = getenv("SZG_NO_EARLY_TAIL") != nullptr;  // (A/B hook of scripts/dev_short.py)
-            if (n_queries >= 8 && ix->serialize_scans && !no_early) early_n = n_queries - std::min(kShortCallLast, n_queries / 2);
-        }
-        // one sweep per query: the call's FIRST batch is small, so that the card starts sweeping after a few
-        // microseconds of preparation instead of a whole batch's (the next batch is prepared while it sweeps)
-        // ... and its LAST one too: what is left to do once the last sweep has ended is that batch's merges,
-        // re-rank, copy-back and result assembly
-        if (!nb && !single_batch && ix->first_batch > 0 && left > ix->first_batch) {
-            if (q0 == 0) t.nq = std::min(t.nq, ix->first_batch);
-            else if (left <= B1 + ix->first_batch) t.nq = left - ix->first_batch;
-        }
-        const bool bf16_sweep = nb > 0 && mq_uses_bf16(ix, false, t.nq);
-        t.kp = kp;
-        // lists of bfloat16-sweep keys (matrix form): the error band holds more rows than the float32 one's, keep
-        // enough candidates for the k-th result to clear it
-        t.kp_wide = bf16_sweep ? std::min(4096, std::max(kp, k + std::max(ix->mq_bf16_slack, k / 2))) : kp;
-        t.ctx.assign(n_sh, nullptr);
-        t.meta.assign(t.nq, QMeta{});
-        if (threaded) {
-            (void)acquire(t, true);  // blocks until the finisher (or another caller) gives a context back
-            rc = stage(t, nb, bf16_sweep);
-            t.failed = rc != SZG_OK;
-            q0 += t.nq;
-            hand_over(std::move(t));
-            continue;
-        }
-        if (!acquire(t, inflight.empty())) {  // no free context: finish the oldest batch first
-            rc = finish(inflight.front());
-            inflight.pop_front();
-            continue;
-        }
-        rc = stage(t, nb, bf16_sweep);
-        t.failed = rc != SZG_OK;  // nothing to gather: finish() only drains and releases
-        inflight.push_back(std::move(t));
-        q0 += inflight.back().nq;
+    std::function<bool(TopkBatch &&)> hand_over;
+    if (threaded) {
+        hand_over = [&fin](TopkBatch &&t) {
+            {
+                std::lock_guard<std::mutex> lk(fin.mu);
+                fin.q.push_back(std::move(t));
+            }
+            fin.cv.notify_one();
+            return !fin.failed.load();
+        };
     }
+    int rc = run_batches<TopkBatch>(*this, hand_over);
     if (threaded) {
         fin.stop();
         if (rc == SZG_OK && fin.failed.load()) rc = fail(fin.rc, fin.err.c_str());  // (this thread's last-error slot)
-        return rc;
-    }
-    while (!inflight.empty()) {
-        const int r2 = finish(inflight.front());
-        if (rc == SZG_OK) rc = r2;
-        inflight.pop_front();
     }
     return rc;
 }
@@ -1110,7 +1111,7 @@ int TopkCall::run()
 int search_topk_impl(szg_index *ix, const double *queries, int n_queries, int k, const uint64_t *allow_bits,
                      uint64_t *out_rows, double *out_dist, int32_t *out_count, const uint64_t *const *allow_ptrs)
 {
-    TopkCall call{ix, queries, n_queries, k, allow_bits, allow_ptrs, out_rows, out_dist, out_count};
+    TopkCall call{ix, queries, n_queries, k, QueryMasks(ix, allow_bits, allow_ptrs), out_rows, out_dist, out_count};
     return call.run();
 }
 
