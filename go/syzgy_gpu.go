@@ -80,11 +80,16 @@ func newGPUMirror(c *Collection, devices []int) (*gpuMirror, error) {
 		return nil, fmt.Errorf("szg_index_create: %s (%s)", C.GoString(C.szg_strerror(rc)),
 			C.GoString(C.szg_last_error()))
 	}
-	// Optional: float32 collections can answer lone Searches from an 8-bit sketch of the rows (a quarter of
-	// the bytes per query, +25 % device memory, same answers: DESIGN.md 4.5).  Off unless asked for.
-	if os.Getenv("SYZGY_GPU_SKETCH") == "1" && c.Quantization == 32 {
+	// Float32 collections answer lone Searches from an 8-bit sketch of the rows (a quarter of the bytes per
+	// query, +25 % device memory, same answers: DESIGN.md 4.5) -- the library's automatic default.
+	// SYZGY_GPU_SKETCH=0 switches it off, =1 forces it on.
+	if v := os.Getenv("SYZGY_GPU_SKETCH"); (v == "0" || v == "1") && c.Quantization == 32 {
 		name := C.CString("sketch")
-		C.szg_set_option(m.h, name, 1)
+		val := C.int64_t(0)
+		if v == "1" {
+			val = 1
+		}
+		C.szg_set_option(m.h, name, val)
 		C.free(unsafe.Pointer(name))
 	}
 	if err := m.reload(c); err != nil {

@@ -341,12 +341,18 @@ int szg_reset_stats(szg_index *ix);
  *     serialize_scans     1   sweeps of one shard never overlap each other (every sweep has the whole HBM bandwidth)
  *     contexts            4   batches in flight per shard
  *   sketch pre-pass (float32 rows)
- *     sketch              0   1 = keep an 8-bit sketch of every row (+25 % memory, built on the device at the first
- *                             search after a load, kept up to date across appends / overwrites / tombstones) and
- *                             answer one-query-per-sweep searches by sweeping the sketch (a quarter of the bytes) for
- *                             k + sketch_extra candidates, re-ranking those on the float32 rows in float64 and
- *                             certifying with the triangle inequality of the reference's distance; unsettled queries
- *                             take the full sweep.  Same answers.  1M x 768 cosine k=10: 2.2 k -> 8.0 k queries/s
+ *     sketch              2   2 = automatic (the default): a handle of float32 rows with >= max(65 536,
+ *                             sketch_min_rows) rows keeps an 8-bit sketch of every row (+25 % memory, built on the
+ *                             device at the first search after a load, kept up to date across appends / overwrites /
+ *                             tombstones) when k + sketch_extra fits the sketch sweep's lists and no test hook is set,
+ *                             and answers one-query-per-sweep searches by sweeping the sketch (a quarter of the bytes)
+ *                             for candidates, re-ranking those on the float32 rows in float64 and certifying with the
+ *                             triangle inequality of the reference's distance; unsettled queries take the full sweep.
+ *                             Same answers.  1M x 768 cosine k=10: 2.25 k -> 7.6 k queries/s.  Auto mode steps aside
+ *                             -- without an error -- until the next load when the sketch would leave less than an
+ *                             eighth of a card's memory (at least 1 GiB) free or an allocation of it fails, and until
+ *                             the next mutation or load once 16 of the last 64 queries it took were handed over to the
+ *                             full sweep.  1 = always (n >= sketch_min_rows; allocation failures are errors), 0 = never
  *     sketch_extra        30  candidates beyond k; the pre-pass serves k + sketch_extra <= 64
  *     sketch_min_rows     4096  collections below this size always take the full sweep
  *   shared sweeps
@@ -367,7 +373,8 @@ int szg_reset_stats(szg_index *ix);
  *     finish_thread       1   a call of three or more shared-sweep batches assembles its finished batches on a
  *                             second host thread while the caller's prepares and enqueues the next ones
  *   test hooks (paths that data takes by itself only rarely): force_escalate, force_matrix (the score-matrix form of
- *   the shared sweeps: small shards, candidate-buffer overflow), force_no_refine (their tail as separate launches: kp > 256)
+ *   the shared sweeps: small shards, candidate-buffer overflow), force_no_refine (their tail as separate launches: kp > 256),
+ *   force_sketch_nomem (the sketch's device allocation is refused: auto mode steps aside, sketch = 1 reports it)
  */
 int szg_set_option(szg_index *ix, const char *name, int64_t value);
 

@@ -66,7 +66,7 @@ class SearchArgs:
 
 
 class Collection:
-    def __init__(self, options: CollectionOptions, devices=None, sketch=False, strict_order=True):
+    def __init__(self, options: CollectionOptions, devices=None, sketch=None, strict_order=True):
         if options.Quantization == 0:
             options.Quantization = 64  # collection.go:254-256
         if options.DistanceMethod not in (Euclidean, Cosine):
@@ -78,9 +78,10 @@ class Collection:
         self.DistanceMethod = options.DistanceMethod
         self._index = ScanIndex(self.DimensionCount, self.Quantization, self.DistanceMethod,
                                 devices=devices)
-        if sketch and self.Quantization == 32:
-            # 8-bit sketch pre-pass for lone Searches on float32 collections (same answers, +25 % device memory)
-            self._index.set_option("sketch", 1)
+        if sketch is not None:
+            # 8-bit sketch pre-pass for lone Searches on float32 collections (same answers, +25 % device memory):
+            # None = the library's default (automatic), True / False force it on / off
+            self._index.set_option("sketch", 1 if sketch else 0)
         self._row_of = {}    # id -> row
         self._id_of = []     # row -> id (None once tombstoned)
         self._meta = []      # row -> metadata bytes

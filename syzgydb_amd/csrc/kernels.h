@@ -236,8 +236,10 @@ hipError_t launch_mq_select(const float *keys, size_t key_stride, uint32_t n_row
                                                               // writes thr[q] and zeroes count_zero[q]
 
 // Lists are [n_queries][n_lists][kp]; the output is [n_queries][n_out][kp].
+// out_stride (a merge down to ONE list per query only): entries between the queries' lists in `out` (0 = kp); the
+// entries behind each list are left alone
 hipError_t launch_merge(const uint64_t *in, int n_lists, int kp, int n_queries, uint64_t *out,
-                        hipStream_t stream);
+                        hipStream_t stream, int out_stride = 0);
 
 struct RerankOut {
     double dist;    // the reference's float64 distance (collection.go:812-832)

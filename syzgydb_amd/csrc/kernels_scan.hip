@@ -823,7 +823,7 @@ __device__ __forceinline__ uint64_t wave_min_u64(uint64_t v)
 // lane; kp rounds of "take the smallest head".  Lists are staged in LDS with
 // coalesced loads first, so each round is a DPP reduction plus one LDS read.
 __global__ __launch_bounds__(256) void merge_heads_kernel(const uint64_t *in, int n_lists, int kp,
-                                                          uint64_t *out)
+                                                          uint64_t *out, int out_stride)
 {
     extern __shared__ __align__(16) uint8_t smem[];
     uint64_t *lists = reinterpret_cast<uint64_t *>(smem);
@@ -832,7 +832,7 @@ __global__ __launch_bounds__(256) void merge_heads_kernel(const uint64_t *in, in
     const int mine = min(kWave, n_lists - first);
     const int total = mine * kp;
     in += (size_t)blockIdx.y * n_lists * kp;     // blockIdx.y = query of the batch
-    out += (size_t)blockIdx.y * gridDim.x * kp;
+    out += (size_t)blockIdx.y * (out_stride ? (size_t)out_stride : (size_t)gridDim.x * kp);
     for (int i = threadIdx.x; i < total; i += blockDim.x) lists[i] = in[(size_t)first * kp + i];
     __syncthreads();
     if (threadIdx.x >= kWave) return;  // the other waves only helped staging
@@ -858,7 +858,7 @@ __global__ __launch_bounds__(256) void merge_heads_kernel(const uint64_t *in, in
 // Rank merge (any kp): every entry finds its rank by binary searches in the
 // other lists.  More work, fully parallel; used when kp is large.
 __global__ __launch_bounds__(1024) void merge_kernel(const uint64_t *in, int n_lists, int kp,
-                                                     int fan, uint64_t *out)
+                                                     int fan, uint64_t *out, int out_stride)
 {
     extern __shared__ __align__(16) uint8_t smem[];
     uint64_t *lists = reinterpret_cast<uint64_t *>(smem);
@@ -866,7 +866,7 @@ __global__ __launch_bounds__(1024) void merge_kernel(const uint64_t *in, int n_l
     const int mine = min(fan, n_lists - first);
     const int total = mine * kp;
     in += (size_t)blockIdx.y * n_lists * kp;     // blockIdx.y = query of the batch
-    out += (size_t)blockIdx.y * gridDim.x * kp;
+    out += (size_t)blockIdx.y * (out_stride ? (size_t)out_stride : (size_t)gridDim.x * kp);
     for (int i = threadIdx.x; i < total; i += blockDim.x) lists[i] = in[(size_t)first * kp + i];
     uint64_t *o = out + (size_t)blockIdx.x * kp;
     for (int i = threadIdx.x; i < kp; i += blockDim.x) o[i] = kInvalidCand;
@@ -1034,19 +1034,20 @@ int merge_fan(int kp)
 }
 
 hipError_t launch_merge(const uint64_t *in, int n_lists, int kp, int n_queries, uint64_t *out,
-                        hipStream_t stream)
+                        hipStream_t stream, int out_stride)
 {
     const int fan = merge_fan(kp);
     const dim3 grid((n_lists + fan - 1) / fan, n_queries);
+    if (out_stride && (grid.x != 1 || out_stride < kp)) return hipErrorInvalidValue;  // (one output list per query only)
     const size_t lds = (size_t)fan * kp * sizeof(uint64_t);
     if (kp <= 128) {
-        hipLaunchKernelGGL(merge_heads_kernel, grid, dim3(256), lds, stream, in, n_lists, kp, out);
+        hipLaunchKernelGGL(merge_heads_kernel, grid, dim3(256), lds, stream, in, n_lists, kp, out, out_stride);
         return hipGetLastError();
     }
     int block = fan * kp;
     if (block > 1024) block = 1024;
     block = (block + 63) & ~63;
-    hipLaunchKernelGGL(merge_kernel, grid, dim3(block), lds, stream, in, n_lists, kp, fan, out);
+    hipLaunchKernelGGL(merge_kernel, grid, dim3(block), lds, stream, in, n_lists, kp, fan, out, out_stride);
     return hipGetLastError();
 }
 

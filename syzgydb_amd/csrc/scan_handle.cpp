@@ -428,7 +428,7 @@ uint64_t szg_index_live_rows(const szg_index *ix)
 int szg_index_load(szg_index *ix, const uint8_t *rows, uint64_t n_rows)
 {
     SZG_TRY
-    if (ix) { ix->gen++; ix->sk_need_full = true; ix->sk_disabled = false; }
+    if (ix) { ix->gen++; sketch_rearm(ix); }
     if (!ix || (!rows && n_rows)) return fail(SZG_E_INVALID, "null argument");
     std::vector<uint64_t> counts;
     split_rows(ix, n_rows, &counts);
@@ -448,7 +448,7 @@ int szg_index_load(szg_index *ix, const uint8_t *rows, uint64_t n_rows)
 int szg_index_synth(szg_index *ix, uint64_t n_rows, uint64_t seed, uint64_t first_row)
 {
     SZG_TRY
-    if (ix) { ix->gen++; ix->sk_need_full = true; ix->sk_disabled = false; }
+    if (ix) { ix->gen++; sketch_rearm(ix); }
     if (!ix) return fail(SZG_E_INVALID, "null argument");
     std::vector<uint64_t> counts;
     split_rows(ix, n_rows, &counts);
@@ -687,7 +687,12 @@ int szg_set_option(szg_index *ix, const char *name, int64_t value)
     if (!ix || !name) return fail(SZG_E_INVALID, "null argument");
     const std::string n(name);
     if (n == "sketch") {
-        ix->sketch_on = value != 0;
+        if (value < 0 || value > 2) return fail(SZG_E_INVALID, "sketch is 0, 1 or 2");
+        ix->sketch_on = (int)value;
+        return SZG_OK;
+    }
+    if (n == "force_sketch_nomem") {
+        ix->force_sketch_nomem = value != 0;
         return SZG_OK;
     }
     if (n == "sketch_min_rows") {

@@ -307,9 +307,9 @@ struct szg_index {
     double norm_bias = 0;     // integer paths: sum n^2 = 4(SQ+SV) + norm_bias (padding removed)
     uint64_t row_base = 0;
     std::vector<szgi::Shard *> shards;
-    // 8-bit sketch pre-pass for float32 cosine collections ("sketch" option, sketch_sync / search_topk_sketch)
-    szg_index *sketch = nullptr;         // an internal 8-bit cosine index over the same rows, same shard ranges
-    int sketch_on = 0;
+    // 8-bit sketch pre-pass for float32 collections ("sketch" option, sketch_sync / search_topk_sketch)
+    szg_index *sketch = nullptr;         // an internal 8-bit index over the same rows, same shard ranges
+    int sketch_on = 2;                   // 0 off, 1 forced on, 2 auto (sketch_applies)
     int sketch_extra = 30;               // sketch neighbours asked for beyond k: k = 10 -> 40, which keeps the sketch
                                          // sweep's lists in registers (kp <= 64); the pre-pass serves k <= 34
     int sketch_min_rows = 4096;          // smaller collections are not worth a second index
@@ -322,6 +322,12 @@ struct szg_index {
     double sk_gscale = 0.0;              // Euclidean collections: the sketch of a row is sk_gscale * n / 255 (0: cosine)
     std::vector<uint64_t> sk_exc;        // rows without a usable sketch (zero rows, non-finite elements): always re-ranked
     bool sk_disabled = false;            // too many such rows
+    // auto mode (sketch_on == 2) steps aside -- until the next load -- when the sketch does not fit the memory rule or
+    // an allocation of it fails; and -- until the next mutation or load -- when too many recent queries fell back
+    bool sk_nomem = false;
+    std::atomic<uint64_t> sk_off_gen{0}; // == gen: stepped aside for the fallback share (gen starts at 1)
+    uint64_t sk_hist = 0;                // the last sk_hist_n eligible queries, newest in bit 0: 1 = handed over
+    int sk_hist_n = 0;                   // (stats_mu)
     std::vector<std::pair<std::string, int64_t>> opt_log;  // tunables set so far (replayed on the sketch index)
     // tunables (szg_set_option; include/syzgy_scan.h lists them)
     int slack_min = 16;
@@ -344,6 +350,7 @@ struct szg_index {
     int force_escalate = 0;   // treat every first pass as uncertified
     int force_matrix = 0;     // shared sweeps: the score-matrix form (what an overflowing candidate buffer falls back to)
     int force_no_refine = 0;  // shared sweeps: the batch's tail as separate re-score / select / rerank launches (kp > 256)
+    int force_sketch_nomem = 0;  // the sketch's device allocation is refused (auto mode steps aside)
     // settled by measurement (rounds 1-3): compile-time facts since round 4, A/B through -D and `make variant`
     static constexpr int blocks_per_cu = 0;     // 0 = waves per CU chosen from the row format (scan_geometry)
     static constexpr int block_threads = 256;
@@ -425,7 +432,19 @@ void fill_scan_args(const szg_index *ix, const Shard *sh, const Ctx *c, bool has
 // timed with its own event pair)
 int launch_scans_chained(szg_index *ix, Shard *sh, Ctx *c, const std::vector<szg::ScanArgs> &a, const LaunchGeom &g,
                          hipStream_t after = nullptr, int part = 0);
-int enqueue_topk(szg_index *ix, Shard *sh, Ctx *c, int kp, int nq, bool has_allow);
+// the sketch pre-pass: the sweep runs over a sketch shard, its merged lists are re-ranked on the float32 rows of the
+// shard it stands for, together with `extra` more rows per query that the caller has uploaded behind each list in
+// c->d_sent (kp + extra entries per query)
+struct RerankOn {
+    const szg_index *ix;
+    const Shard *sh;
+    int extra;
+};
+int enqueue_topk(szg_index *ix, Shard *sh, Ctx *c, int kp, int nq, bool has_allow, const RerankOn *on = nullptr);
+// candidates of staged query `slot` from a finished top-k pass and *lb, the lower bound of the real-number key of every
+// eligible row of the shard that is not among them
+void gather_topk(const szg_index *ix, const Shard *sh, const Ctx *c, const QMeta &m, int slot, std::vector<Cand> *cands,
+                 double *lb);
 // float64 distances of the staged sentinel rows (d_sent) on `stream`, results to h_sent_out
 int launch_sentinel_rerank(szg_index *ix, Shard *sh, Ctx *c, int nq, hipStream_t stream);
 int finish_timing(szg_index *ix, Ctx *c);
@@ -460,6 +479,9 @@ bool mq_tail_takes_sentinels(const szg_index *ix, const Shard *sh, int kp, int k
 int enqueue_collect_mq(szg_index *ix, Shard *sh, Ctx *c, int nq, int nb, bool has_allow, const float *thr, size_t cap);
 
 // ---- scan_sketch.cpp
+bool sketch_applies(const szg_index *ix, int k);
+// a load / synth: auto mode may try the sketch again (mutations are never concurrent with searches)
+void sketch_rearm(szg_index *ix);
 int search_topk_any(szg_index *ix, const double *queries, int n_queries, int k, const uint64_t *allow_bits,
                     uint64_t *out_rows, double *out_dist, int32_t *out_count,
                     const uint64_t *const *allow_ptrs = nullptr);

@@ -106,6 +106,9 @@ static bool row_norms_apply(const szg_index *ix)
     return (ix->bits == 16 && !ix->layout.tiled) || ix->bits == 8 || ix->bits == 4;
 }
 
+// Contract: mutations (load, append, overwrite, tombstone) never overlap a search of the same handle -- the caller
+// holds its write lock, as the reference's collection does -- so the rows behind [0, norm_valid) cannot change while
+// a sweep reads their norms; an overwrite lowers norm_valid (and sketch_sync does for the rows it re-sketches).
 int ensure_row_norms(szg_index *ix, Shard *sh)
 {
     if (!row_norms_apply(ix) || sh->n_rows == 0) return SZG_OK;

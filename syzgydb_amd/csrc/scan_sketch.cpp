@@ -1,28 +1,76 @@
-// scan_sketch.cpp -- 8-bit sketch pre-pass for float32 collections (option "sketch", off by default).
+// scan_sketch.cpp -- 8-bit sketch pre-pass for float32 collections (option "sketch", automatic by default).
 #include "scan_internal.h"
 
 namespace szgi {
 
-// ---- 8-bit sketch pre-pass (float32 rows, cosine) ---------------------------------------------------------------
+// ---- 8-bit sketch pre-pass (float32 rows) ------------------------------------------------------------------------
 //
 // The reference's "cosine" distance IS the angle (acos(cos)/pi, collection.go:821-832), a metric on directions:
-// |d(q, x) - d(q, s)| <= d(x, s) for any sketch s of the row x.  The library keeps an 8-bit sketch of every float32
-// row (a quarter of the bytes) as an internal 8-bit index, sweeps THAT for the K' nearest sketches (its own exact,
-// certified answer: the whole machinery of this file on 8-bit rows), re-ranks those rows -- plus the query's first k
-// rows and the rows that have no usable sketch -- on the float32 rows in float64, and replays consider() over them.
-// With A = max over the rows of d(row, sketch) (measured when the sketch is built) and D = the K'-th sketch
-// distance, every row that is not a candidate has d(q, sketch) >= D, hence d(q, x) >= D - A: the answer is final
-// when its k-th distance is below that.  Otherwise -- and for equal distances or a NaN among the first k rows,
-// where the reference's answer depends on its heap history -- the query takes the float32 path.
+// |d(q, x) - d(q, s)| <= d(x, s) for any sketch s of the row x (Euclidean distance likewise).  The library keeps an
+// 8-bit sketch of every float32 row (a quarter of the bytes) as an internal 8-bit index over the same row ranges.
+// A query sweeps the sketch shards for their kp best sketch keys (the one-sweep pipeline of scan_topk.cpp on the
+// sketch index: sweep, device merges), and ONE rerank launch per batch and shard computes the float64 distances of
+// those rows -- on the float32 rows -- together with the query's first k eligible rows and the rows that have no
+// usable sketch.  consider() is replayed over them on the host.  With A = max over the rows of d(row, sketch)
+// (measured when the sketch is built) and D_lb = a lower bound of the sketch distance of every row outside the
+// lists (from the kp-th merged key and its error bound), d(q, x) >= D_lb - A for every row that was not re-ranked:
+// the answer is final when its k-th distance is below that.  Otherwise -- and for equal distances or a NaN among the
+// first k rows, where the reference's answer depends on its heap history -- the query takes the float32 path.
+
+constexpr uint64_t kAutoMinRows = 65536;  // auto mode: smaller collections keep no second index
+constexpr int kAutoWindow = 64;           // auto mode steps aside once kAutoFallbacks of the last kAutoWindow
+constexpr int kAutoFallbacks = 16;        // eligible queries were handed over to the full sweep
+
 bool sketch_applies(const szg_index *ix, int k)
 {
     if (!ix->sketch_on || ix->sk_disabled || ix->bits != 32) return false;
     uint64_t n = 0;
     for (const Shard *sh : ix->shards) n += sh->n_rows;
+    uint64_t min_rows = (uint64_t)ix->sketch_min_rows;
+    if (ix->sketch_on == 2) {
+        // the test hooks drive rare branches of the full-precision path: a default must not steer around them
+        if (ix->force_escalate || ix->force_matrix || ix->force_no_refine) return false;
+        if (ix->sk_nomem || ix->sk_off_gen.load(std::memory_order_relaxed) == ix->gen) return false;
+        min_rows = std::max(min_rows, kAutoMinRows);
+    }
     // the sketch sweep must keep its lists short: 8-bit rows pass four times as fast as float32 rows, and with
     // LDS-resident lists of hundreds (k = 100: 1.35 ms per sweep) the pre-pass is slower than the sweep it replaces
     const int kk = k + ix->sketch_extra;
-    return n >= (uint64_t)ix->sketch_min_rows && kk + std::max(ix->slack_min, kk / 2) <= 96;
+    return n >= min_rows && kk + std::max(ix->slack_min, kk / 2) <= 96;
+}
+
+void sketch_rearm(szg_index *ix)
+{
+    ix->sk_need_full = true;
+    ix->sk_disabled = false;
+    if (ix->sk_nomem && ix->sketch) {  // (a step aside after a failure in the pipeline kept the sketch index)
+        szg_index_destroy(ix->sketch);
+        ix->sketch = nullptr;
+    }
+    ix->sk_nomem = false;
+    std::lock_guard<std::mutex> lk(ix->stats_mu);
+    ix->sk_hist = 0;
+    ix->sk_hist_n = 0;
+}
+
+// auto mode, before the first build: the sketch (a dim-byte row per row, in 64-byte steps, plus its contexts) must
+// leave an eighth of every card's memory -- at least 1 GiB -- free
+static bool sketch_fits(const szg_index *ix)
+{
+    std::vector<std::pair<int, uint64_t>> need;  // device, bytes
+    for (const Shard *sh : ix->shards) {
+        const uint64_t b = sh->n_rows * (((uint64_t)ix->dim + 63) & ~63ull) + (64ull << 20);
+        auto it = std::find_if(need.begin(), need.end(), [&](const std::pair<int, uint64_t> &p) { return p.first == sh->device; });
+        if (it == need.end()) need.emplace_back(sh->device, b);
+        else it->second += b;
+    }
+    for (const auto &p : need) {
+        size_t free_b = 0, total_b = 0;
+        if (hipSetDevice(p.first) != hipSuccess || hipMemGetInfo(&free_b, &total_b) != hipSuccess) return false;
+        const uint64_t margin = std::max<uint64_t>(total_b / 8, 1ull << 30);
+        if ((uint64_t)free_b < p.second + margin) return false;
+    }
+    return true;
 }
 
 // bring the sketch index up to date with the rows (callers hold ix->sk_mu)
@@ -30,6 +78,7 @@ int sketch_sync(szg_index *ix)
 {
     if (ix->sk_gen == ix->gen && ix->sketch) return SZG_OK;
     if (!ix->sketch) {
+        if (ix->sketch_on == 2 && !sketch_fits(ix)) return fail(SZG_E_NOMEM, "sketch: over the memory rule");
         std::vector<int> devs;
         for (Shard *sh : ix->shards) devs.push_back(sh->device);
         int rc = szg_index_create(&ix->sketch, ix->dim, 8, ix->metric, devs.data(), (int)devs.size());
@@ -107,8 +156,11 @@ int sketch_sync(szg_index *ix)
             for (uint64_t r : ix->sk_dirty_rows)
                 if (r >= a->first && r < a->first + have) list.push_back((uint32_t)(r - a->first));
         if (have == a->n_rows && list.empty()) continue;
+        if (ix->force_sketch_nomem) return fail(SZG_E_NOMEM, "hipMalloc(sketch): refused (force_sketch_nomem)");
         int rc = shard_reserve(sk, b, a->n_rows);
         if (rc) return rc;
+        // rewritten rows: their resident norms (the shared bfloat16 sweep's) are stale from the first of them on
+        for (uint32_t r : list) b->norm_valid = std::min<uint64_t>(b->norm_valid, r);
         unsigned long long *d_ang = nullptr;
         uint32_t *d_exc = nullptr, *d_list = nullptr;
         struct Scratch {  // freed on every exit path
@@ -183,70 +235,252 @@ int sketch_sync(szg_index *ix)
     ix->sk_dirty_rows.clear();
     ix->sk_need_full = false;
     ix->sk_gen = ix->gen;
-    // the sketch index answers with the caller's tunables where they matter for correctness
-    sk->tie_mode = ix->tie_mode;
     return SZG_OK;
 }
 
-// float64 distances of per-query candidate lists (index-level rows) in one rerank launch per shard
-int sketch_exact_distances(szg_index *ix, const double *queries, int nq, const std::vector<std::vector<uint64_t>> &cand,
-                           std::vector<std::vector<double>> *dist)
+// ---- one search call through the sketch ---------------------------------------------------------------------------
+//
+// The batch pipeline of scan_topk.cpp (run_batches) on the sketch index's contexts: stage() uploads a batch's queries
+// and extra rows and enqueues, per shard, the sketch sweeps, the merges and one float32-row rerank; finish() settles
+// the batch's queries on the host -- a short call's first queries while its last sweeps still run -- and collects
+// the ones the certificate does not settle for the full sweep.
+struct SketchCall {
+    szg_index *ix;  // the float32 handle (rows, masks, results)
+    szg_index *sk;  // its sketch index (contexts, sweeps)
+    const double *queries;
+    int n_queries, k;
+    QueryMasks mask_of;
+    uint64_t *out_rows;
+    double *out_dist;
+    int32_t *out_count;
+    std::vector<int> redo;  // queries handed over to the full sweep, ascending
+
+    size_t n_sh = 0;
+    int kp = 0;
+    double gs = 0.0, slack = 0.0;
+    std::vector<int> extra;                     // per shard: entries behind each list (k first rows + remembered rows)
+    std::vector<uint64_t> firstk_open, firstk;  // first k eligible rows of an unfiltered / of the current query
+    std::vector<double> q_scaled;
+    std::vector<Cand> cands;
+    std::vector<HeapItem> res;
+    std::vector<double> dd;
+
+    int run();
+    Batch plan(int q0);
+    int stage(Batch &b);
+    void settle(Batch &b, int j);
+    int finish(Batch &b);
+};
+
+int SketchCall::run()
 {
-    dist->assign(nq, {});
-    size_t most = 0;
-    for (int j = 0; j < nq; j++) {
-        (*dist)[j].assign(cand[j].size(), 0.0);
-        most = std::max(most, cand[j].size());
+    n_sh = ix->shards.size();
+    const int kk = k + ix->sketch_extra;
+    kp = kk + std::max(ix->slack_min, kk / 2);
+    gs = ix->sk_gscale;  // Euclidean: sketch distances are in units of gs (the sketch sweeps see q / gs)
+    slack = ix->sk_max_ang * (1.0 + 1e-9) + (gs > 0.0 ? 0.0 : 1e-7);  // (+ the rounding of the computed angles)
+    sk->timing = ix->timing;
+    extra.assign(n_sh, 0);
+    for (size_t s = 0; s < n_sh; s++) {
+        const Shard *a = ix->shards[s];
+        size_t exc = 0;
+        for (uint64_t r : ix->sk_exc) exc += (r >= a->first && r < a->first + a->n_rows) ? 1 : 0;
+        extra[s] = k + (int)exc;
     }
-    if (most == 0) return SZG_OK;
-    std::vector<uint64_t> local((size_t)nq * most);
-    std::vector<uint32_t> where((size_t)nq * most);
-    for (Shard *sh : ix->shards) {
-        if (sh->n_rows == 0) continue;
-        size_t width = 0;
-        for (int j = 0; j < nq; j++) {
+    first_eligible_rows(ix, nullptr, k, &firstk_open);
+    redo.reserve(n_queries);
+    cands.reserve((size_t)n_sh * kp + ix->sk_exc.size() + (size_t)k);
+    dd.reserve(cands.capacity());
+    return run_batches<Batch>(*this);
+}
+
+Batch SketchCall::plan(int q0)
+{
+    Batch b;
+    const int batch = std::max(1, std::min(ix->query_batch, kMaxBatch));
+    plan_batch(sk, n_queries, q0, 0, BatchRules{batch, kFirstBatch, std::min(kShortCall, kMaxBatch), true, false}, &b);
+    return b;
+}
+
+int SketchCall::stage(Batch &b)
+{
+    const double t_prep0 = now_us();
+    const int dim = ix->dim;
+    const double *q = queries + (size_t)b.first * dim;
+    const std::vector<const uint64_t *> masks = b.masks(mask_of);
+    const uint64_t *const *mptr = b.any_mask ? masks.data() : nullptr;
+    const double *q_sk = q;
+    if (gs > 0.0) {
+        q_scaled.resize((size_t)b.nq * dim);
+        for (size_t i = 0; i < q_scaled.size(); i++) q_scaled[i] = q[i] / gs;
+        q_sk = q_scaled.data();
+    }
+    int rc = stage_query_forms(sk, b, q_sk, false, [](int, QMeta &) {});
+    // behind each query's list: its first k eligible rows of the shard (kInvalidCand-padded to k), then the shard's
+    // eligible rows without a usable sketch
+    for (size_t s = 0; s < n_sh && rc == SZG_OK; s++) {
+        Ctx *c = b.ctx[s];
+        if (!c) continue;
+        const Shard *a = ix->shards[s];
+        const size_t stride = (size_t)kp + extra[s];
+        rc = ensure_host(&c->h_sent, &c->h_sent_cap, (size_t)b.nq * stride);
+        if (rc == SZG_OK) rc = ensure_dev(&c->d_sent, &c->d_sent_cap, (size_t)b.nq * stride);
+        if (rc) break;
+        for (int j = 0; j < b.nq; j++) {
+            const uint64_t *m = masks[j];
+            if (m) first_eligible_rows(ix, m, k, &firstk);
+            const std::vector<uint64_t> &fk = m ? firstk : firstk_open;
+            uint64_t *o = c->h_sent + (size_t)j * stride + kp;
             size_t n = 0;
-            for (size_t i = 0; i < cand[j].size(); i++) {
-                const uint64_t r = cand[j][i];
-                if (r >= sh->first && r < sh->first + sh->n_rows) {
-                    local[(size_t)j * most + n] = r - sh->first;
-                    where[(size_t)j * most + n] = (uint32_t)i;
-                    n++;
-                }
+            for (uint64_t r : fk)
+                if (r >= a->first && r < a->first + a->n_rows) o[n++] = r - a->first;
+            for (; n < (size_t)k; n++) o[n] = szg::kInvalidCand;
+            for (uint64_t r : ix->sk_exc) {
+                if (r < a->first || r >= a->first + a->n_rows) continue;
+                const uint64_t l = r - a->first;
+                const bool ok = ((a->live_host[l >> 6] >> (l & 63)) & 1) && (!m || ((m[r >> 6] >> (r & 63)) & 1));
+                o[n++] = ok ? l : szg::kInvalidCand;
             }
-            width = std::max(width, n);
-            for (; n < most; n++) local[(size_t)j * most + n] = szg::kInvalidCand;
         }
-        if (width == 0) continue;
-        HIPCHK(hipSetDevice(sh->device));
-        std::lock_guard<std::mutex> bl(sh->sk_buf_mu);
-        const size_t q_bytes = (sizeof(double) * (size_t)nq * ix->dim + 255) & ~(size_t)255;
-        const size_t c_bytes = (sizeof(uint64_t) * local.size() + 255) & ~(size_t)255;
-        const size_t o_bytes = sizeof(szg::RerankOut) * local.size();
-        if (sh->sk_buf_cap < q_bytes + c_bytes + o_bytes) {
-            if (sh->sk_buf) (void)hipFree(sh->sk_buf);
-            sh->sk_buf = nullptr;
-            sh->sk_buf_cap = 0;
-            const size_t want = (q_bytes + c_bytes + o_bytes) * 2;
-            if (hipMalloc((void **)&sh->sk_buf, want) != hipSuccess) return fail(SZG_E_NOMEM, "hipMalloc(sketch re-rank)");
-            sh->sk_buf_cap = want;
-        }
-        double *d_q = reinterpret_cast<double *>(sh->sk_buf);
-        uint64_t *d_c = reinterpret_cast<uint64_t *>(sh->sk_buf + q_bytes);
-        szg::RerankOut *d_o = reinterpret_cast<szg::RerankOut *>(sh->sk_buf + q_bytes + c_bytes);
-        std::vector<szg::RerankOut> h_o((size_t)nq * most);
-        hipError_t e = hipMemcpy(d_q, queries, sizeof(double) * (size_t)nq * ix->dim, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(d_c, local.data(), sizeof(uint64_t) * local.size(), hipMemcpyHostToDevice);
+    }
+    const double t_enq0 = now_us();
+    for (size_t s = 0; s < n_sh && rc == SZG_OK; s++) {
+        Ctx *c = b.ctx[s];
+        if (!c) continue;
+        Shard *h = sk->shards[s];
+        const size_t stride = (size_t)kp + extra[s];
+        c->sent_n = 0;
+        c->sent_deferred = false;
+        c->sent_own_stream = false;
+        hipError_t e = hipSetDevice(h->device);
+        // (ahead of the queries' upload: the sweeps wait for that, and the merges and rerank come after the sweeps)
         if (e == hipSuccess)
-            e = szg::launch_rerank(ix->bits, ix->metric, sh->rows, ix->layout, ix->dim, d_q, d_c, nullptr, (uint32_t)most,
-                                   nq, d_o, nullptr);
-        if (e == hipSuccess) e = hipMemcpy(h_o.data(), d_o, sizeof(szg::RerankOut) * h_o.size(), hipMemcpyDeviceToHost);
-        if (e != hipSuccess) return fail(SZG_E_DEVICE, "sketch re-rank", e);
-        for (int j = 0; j < nq; j++)
-            for (size_t n = 0; n < most; n++) {
-                if (local[(size_t)j * most + n] == szg::kInvalidCand) break;
-                (*dist)[j][where[(size_t)j * most + n]] = h_o[(size_t)j * most + n].dist;
-            }
+            e = hipMemcpyAsync(c->d_sent, c->h_sent, sizeof(uint64_t) * b.nq * stride, hipMemcpyHostToDevice, c->work);
+        if (e != hipSuccess) {
+            rc = fail(SZG_E_DEVICE, "sketch candidates upload", e);
+            break;
+        }
+        rc = enqueue_queries(sk, h, c, q, b.nq, mptr);  // (the float64 queries unscaled: the rerank is on the rows)
+        const RerankOn on{ix, ix->shards[s], extra[s]};
+        if (rc == SZG_OK) rc = enqueue_topk(sk, h, c, kp, b.nq, b.any_mask, &on);
+    }
+    std::lock_guard<std::mutex> lk(ix->stats_mu);
+    const double t_end = now_us();
+    ix->stats.host_prep_us += t_enq0 - t_prep0;
+    ix->stats.host_enqueue_us += t_end - t_enq0;
+    return rc;
+}
+
+// one query of a finished batch: its answer, or a hand-over to the full sweep
+void SketchCall::settle(Batch &b, int j)
+{
+    const int qi = b.first + j;
+    cands.clear();
+    double lb = INFINITY;  // lower bound of the real-number sketch key of every eligible row outside the lists
+    bool nan_first = false;
+    bool zero_query = false;
+    for (size_t s = 0; s < n_sh; s++) {
+        const Ctx *c = b.ctx[s];
+        if (!c) continue;
+        double l;
+        gather_topk(sk, sk->shards[s], c, c->meta[j], j, &cands, &l);
+        lb = std::min(lb, l);
+        zero_query |= ix->metric == SZG_COSINE && c->meta[j].m1 == 0;
+        const uint64_t first = ix->shards[s]->first;
+        for (int i = kp; i < c->out_stride; i++) {
+            const szg::RerankOut &r = c->h_out[(size_t)j * c->out_stride + i];
+            if (r.row == 0xFFFFFFFFu) continue;
+            // outside the first k rows a NaN never enters the heap; among them it decides everything
+            if (std::isnan(r.dist) && i < kp + k) nan_first = true;
+            cands.push_back(Cand{first + r.row, r.dist, 0.0f, 0.0});
+        }
+    }
+    cands.erase(std::remove_if(cands.begin(), cands.end(), [](const Cand &c) { return std::isnan(c.dist); }), cands.end());
+    std::sort(cands.begin(), cands.end(), [](const Cand &x, const Cand &y) { return x.row < y.row; });
+    cands.erase(std::unique(cands.begin(), cands.end(), [](const Cand &x, const Cand &y) { return x.row == y.row; }),
+                cands.end());
+    replay_topk(cands, k, &res);
+    bool ok = (!nan_first || ix->tie_mode != 0) && !zero_query;
+    if (ok && lb < INFINITY) {
+        // D_lb: the sketch distance the key bound lb implies -- cosine: key = -cos, distance
+        // acos(cos) / pi; Euclid: key = (255 d)^2 in units of gs
+        double D;
+        if (gs > 0.0) {
+            D = gs * std::sqrt(std::max(lb, 0.0)) / 255.0 * (1.0 - 1e-9);
+        } else {
+            const double x = -lb + 1e-15;  // (an upper bound of the cosine, rounding included)
+            D = x >= 1.0 ? 0.0 : (x <= -1.0 ? 1.0 : std::acos(x) / M_PI * (1.0 - 1e-12));
+        }
+        ok = (int)res.size() == k && res.back().priority * (1.0 + 1e-9) < D - slack;
+    }
+    if (ok && ix->tie_mode == 0) {
+        dd.clear();
+        for (const Cand &c : cands) dd.push_back(c.dist);
+        if (history_dependent(dd.data(), dd.size(), k)) ok = false;  // the float32 path replays every row
+    }
+    if (!ok) {
+        redo.push_back(qi);
+        return;
+    }
+    for (int i = 0; i < k; i++) {
+        const bool have = i < (int)res.size();
+        out_rows[(size_t)qi * k + i] = have ? res[i].row + ix->row_base : UINT64_MAX;
+        out_dist[(size_t)qi * k + i] = have ? res[i].priority : 0.0;
+    }
+    if (out_count) out_count[qi] = (int32_t)res.size();
+}
+
+int SketchCall::finish(Batch &b)
+{
+    if (b.failed) {
+        b.drain();
+        return SZG_OK;
+    }
+    const size_t redo0 = redo.size();
+    int rc = SZG_OK;
+    // a short call's first queries (Ctx::early_n) are complete once the contexts' own streams are
+    int early = 0;
+    for (size_t s = 0; s < n_sh; s++)
+        if (b.ctx[s] && b.ctx[s]->early_n > 0 && b.ctx[s]->early_n < b.nq) early = b.ctx[s]->early_n;
+    double t_host = 0.0;
+    for (int phase = early ? 0 : 1; phase < 2 && rc == SZG_OK; phase++) {
+        for (size_t s = 0; s < n_sh && rc == SZG_OK; s++) {
+            Ctx *c = b.ctx[s];
+            if (!c) continue;
+            hipError_t e = hipSetDevice(ix->shards[s]->device);
+            if (e == hipSuccess) e = hipStreamSynchronize(phase ? c->work : c->stream);
+            if (e == hipSuccess && phase) e = hipStreamSynchronize(c->stream);
+            if (e != hipSuccess) rc = fail(SZG_E_DEVICE, "hipStreamSynchronize", e);
+            if (rc == SZG_OK && phase) rc = finish_timing(sk, c);
+        }
+        if (rc) break;
+        const double t0 = now_us();
+        for (int j = phase ? early : 0; j < (phase ? b.nq : early); j++) settle(b, j);
+        t_host += now_us() - t0;
+    }
+    if (rc) b.drain();
+    else b.release();
+    std::lock_guard<std::mutex> lk(ix->stats_mu);
+    ix->stats.host_finish_us += t_host;
+    if (rc) return rc;
+    const uint64_t fb = redo.size() - redo0, settled = (uint64_t)b.nq - fb;
+    ix->stats.sketch_queries += settled;
+    ix->stats.sketch_fallbacks += fb;
+    ix->stats.queries += settled;
+    if (ix->sketch_on == 2) {  // the recent window of eligible queries (newest in bit 0)
+        const uint64_t off = ix->sk_off_gen.load();
+        if (off != 0 && off != ix->gen) {  // re-armed by a mutation since it stepped aside: a fresh window
+            ix->sk_hist = 0;
+            ix->sk_hist_n = 0;
+            ix->sk_off_gen.store(0);
+        }
+        for (int j = b.first; j < b.first + b.nq; j++) {
+            const bool handed = std::binary_search(redo.begin() + redo0, redo.end(), j);
+            ix->sk_hist = (ix->sk_hist << 1) | (handed ? 1u : 0u);
+            ix->sk_hist_n = std::min(ix->sk_hist_n + 1, kAutoWindow);
+        }
+        if (ix->sk_hist_n == kAutoWindow && __builtin_popcountll(ix->sk_hist) >= kAutoFallbacks)
+            ix->sk_off_gen.store(ix->gen);
     }
     return SZG_OK;
 }
@@ -258,128 +492,52 @@ int search_topk_sketch(szg_index *ix, const double *queries, int n_queries, int 
     {   // (mutations come under the caller's write lock: after the sync, searches run side by side)
         std::lock_guard<std::mutex> lk(ix->sk_mu);
         rc = sketch_sync(ix);
+        if (rc && ix->sketch_on == 2) {
+            // auto mode never turns a working handle into an error: give back what was built, step aside until the
+            // next load
+            if (ix->sketch) szg_index_destroy(ix->sketch);
+            ix->sketch = nullptr;
+            ix->sk_need_full = true;
+            ix->sk_dirty_rows.clear();
+            ix->sk_nomem = true;
+            for (Shard *sh : ix->shards)
+                if (hipSetDevice(sh->device) == hipSuccess) (void)hipGetLastError();
+            rc = SZG_OK;
+        }
     }
     if (rc) return rc;
-    if (ix->sk_disabled) return search_topk_impl(ix, queries, n_queries, k, allow_bits, out_rows, out_dist, out_count, allow_ptrs);
-    szg_index *sk = ix->sketch;
-    const QueryMasks mask_of(ix, allow_bits, allow_ptrs);
-    auto eligible = [&](const uint64_t *m, uint64_t r) -> bool {
-        if (m && !((m[r >> 6] >> (r & 63)) & 1)) return false;
-        for (const Shard *sh : ix->shards)
-            if (r >= sh->first && r < sh->first + sh->n_rows) {
-                const uint64_t l = r - sh->first;
-                return (sh->live_host[l >> 6] >> (l & 63)) & 1;
-            }
-        return false;
-    };
-    const int kk = k + ix->sketch_extra;
-    const double gs = ix->sk_gscale;  // Euclidean: sketch distances are in units of gs (the sketch index sees q / gs)
-    const double slack = ix->sk_max_ang * (1.0 + 1e-9) + (gs > 0.0 ? 0.0 : 1e-7);  // (+ the rounding of the computed angles, ~1e-9 near 0)
-    std::vector<double> q_scaled;
-    std::vector<int> redo;  // queries that go to the float32 path
-    const int chunk = 512;
-    std::vector<uint64_t> s_rows((size_t)chunk * kk);
-    std::vector<double> s_dist((size_t)chunk * kk);
-    std::vector<int32_t> s_count(chunk);
-    for (int q0 = 0; q0 < n_queries; q0 += chunk) {
-        const int nq = std::min(chunk, n_queries - q0);
-        const double *q = queries + (size_t)q0 * ix->dim;
-        std::vector<const uint64_t *> masks(nq);
-        bool any_mask = false;
-        for (int j = 0; j < nq; j++) {
-            masks[j] = mask_of(q0 + j);
-            any_mask |= masks[j] != nullptr;
-        }
-        const double *q_sk = q;
-        if (gs > 0.0) {
-            q_scaled.resize((size_t)nq * ix->dim);
-            for (size_t i = 0; i < q_scaled.size(); i++) q_scaled[i] = q[i] / gs;
-            q_sk = q_scaled.data();
-        }
-        rc = search_topk_impl(sk, q_sk, nq, kk, nullptr, s_rows.data(), s_dist.data(), s_count.data(),
-                              any_mask ? masks.data() : nullptr);
-        if (rc) return rc;
-        // candidates: the sketch neighbours, the query's first k eligible rows, the rows without a sketch
-        std::vector<std::vector<uint64_t>> cand(nq);
-        std::vector<std::vector<uint64_t>> firstk(nq);
-        for (int j = 0; j < nq; j++) {
-            if (j > 0 && !masks[j] && !masks[j - 1]) firstk[j] = firstk[j - 1];
-            else first_eligible_rows(ix, masks[j], k, &firstk[j]);
-            std::vector<uint64_t> &c = cand[j];
-            c.assign(s_rows.begin() + (size_t)j * kk, s_rows.begin() + (size_t)j * kk + s_count[j]);
-            c.insert(c.end(), firstk[j].begin(), firstk[j].end());
-            for (uint64_t r : ix->sk_exc)
-                if (eligible(masks[j], r)) c.push_back(r);
-            std::sort(c.begin(), c.end());
-            c.erase(std::unique(c.begin(), c.end()), c.end());
-        }
-        std::vector<std::vector<double>> dist;
-        rc = sketch_exact_distances(ix, q, nq, cand, &dist);
-        if (rc) return rc;
-        for (int j = 0; j < nq; j++) {
-            const int qi = q0 + j;
-            std::vector<Cand> cs;
-            bool nan_first = false;
-            for (size_t i = 0; i < cand[j].size(); i++) {
-                const double d = dist[j][i];
-                if (std::isnan(d)) {
-                    // outside the first k rows a NaN never enters the heap; among them it decides everything
-                    if (std::binary_search(firstk[j].begin(), firstk[j].end(), cand[j][i])) nan_first = true;
-                    continue;
-                }
-                cs.push_back(Cand{cand[j][i], d, 0.0f, 0.0});
-            }
-            std::vector<HeapItem> res;
-            replay_topk(cs, k, &res);
-            bool ok = !nan_first || ix->tie_mode != 0;
-            if (ok && s_count[j] == kk) {  // rows exist that were not re-ranked: d(q, row) >= D - A for all of them
-                double D = s_dist[(size_t)j * kk + kk - 1];
-                if (gs > 0.0) D = D * gs * (1.0 - 1e-9);
-                ok = (int)res.size() == k && res.back().priority * (1.0 + 1e-9) < D - slack;
-            }
-            if (ok && ix->tie_mode == 0) {
-                std::vector<double> d(cs.size());
-                for (size_t i = 0; i < cs.size(); i++) d[i] = cs[i].dist;
-                if (history_dependent(d.data(), d.size(), k)) ok = false;  // the float32 path replays every row
-            }
-            if (!ok) {
-                redo.push_back(qi);
-                continue;
-            }
-            for (int i = 0; i < k; i++) {
-                const bool have = i < (int)res.size();
-                out_rows[(size_t)qi * k + i] = have ? res[i].row + ix->row_base : UINT64_MAX;
-                out_dist[(size_t)qi * k + i] = have ? res[i].priority : 0.0;
-            }
-            if (out_count) out_count[qi] = (int32_t)res.size();
-        }
+    if (ix->sk_disabled || ix->sk_nomem)
+        return search_topk_impl(ix, queries, n_queries, k, allow_bits, out_rows, out_dist, out_count, allow_ptrs);
+    SketchCall call{ix, ix->sketch, queries, n_queries, k, QueryMasks(ix, allow_bits, allow_ptrs), out_rows, out_dist,
+                    out_count};
+    rc = call.run();
+    if (rc && ix->sketch_on == 2) {
+        // (a failure inside the pipeline, an allocation of a sketch context: the sketch index stays until the next
+        // load, the whole call goes the full-precision way)
+        ix->sk_nomem = true;
+        return search_topk_impl(ix, queries, n_queries, k, allow_bits, out_rows, out_dist, out_count, allow_ptrs);
     }
-    {
-        std::lock_guard<std::mutex> sl(ix->stats_mu);
-        ix->stats.sketch_queries += (uint64_t)n_queries - redo.size();
-        ix->stats.sketch_fallbacks += redo.size();
-        ix->stats.queries += (uint64_t)n_queries - redo.size();
+    if (rc) return rc;
+    if (call.redo.empty()) return SZG_OK;
+    // the unsettled queries: ONE call of the full-precision path
+    const int m = (int)call.redo.size();
+    std::vector<double> q2((size_t)m * ix->dim);
+    std::vector<const uint64_t *> m2(m);
+    std::vector<uint64_t> r2((size_t)m * k);
+    std::vector<double> d2((size_t)m * k);
+    std::vector<int32_t> c2(m);
+    bool any = false;
+    for (int i = 0; i < m; i++) {
+        memcpy(&q2[(size_t)i * ix->dim], queries + (size_t)call.redo[i] * ix->dim, sizeof(double) * ix->dim);
+        m2[i] = call.mask_of(call.redo[i]);
+        any |= m2[i] != nullptr;
     }
-    if (!redo.empty()) {
-        const int m = (int)redo.size();
-        std::vector<double> q2((size_t)m * ix->dim);
-        std::vector<const uint64_t *> m2(m);
-        std::vector<uint64_t> r2((size_t)m * k);
-        std::vector<double> d2((size_t)m * k);
-        std::vector<int32_t> c2(m);
-        bool any = false;
-        for (int i = 0; i < m; i++) {
-            memcpy(&q2[(size_t)i * ix->dim], queries + (size_t)redo[i] * ix->dim, sizeof(double) * ix->dim);
-            m2[i] = mask_of(redo[i]);
-            any |= m2[i] != nullptr;
-        }
-        rc = search_topk_impl(ix, q2.data(), m, k, nullptr, r2.data(), d2.data(), c2.data(), any ? m2.data() : nullptr);
-        if (rc) return rc;
-        for (int i = 0; i < m; i++) {
-            memcpy(out_rows + (size_t)redo[i] * k, &r2[(size_t)i * k], sizeof(uint64_t) * k);
-            memcpy(out_dist + (size_t)redo[i] * k, &d2[(size_t)i * k], sizeof(double) * k);
-            if (out_count) out_count[redo[i]] = c2[i];
-        }
+    rc = search_topk_impl(ix, q2.data(), m, k, nullptr, r2.data(), d2.data(), c2.data(), any ? m2.data() : nullptr);
+    if (rc) return rc;
+    for (int i = 0; i < m; i++) {
+        memcpy(out_rows + (size_t)call.redo[i] * k, &r2[(size_t)i * k], sizeof(uint64_t) * k);
+        memcpy(out_dist + (size_t)call.redo[i] * k, &d2[(size_t)i * k], sizeof(double) * k);
+        if (out_count) out_count[call.redo[i]] = c2[i];
     }
     return SZG_OK;
 }

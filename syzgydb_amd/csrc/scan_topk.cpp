@@ -171,10 +171,13 @@ double mask_pass_rate(const Shard *sh, const Ctx *c, bool has_allow, int slot)
 }
 
 // top-k pass for the nq staged queries of one shard: scan -> merges -> rerank -> D2H (async)
-int enqueue_topk(szg_index *ix, Shard *sh, Ctx *c, int kp, int nq, bool has_allow)
+// on (the sketch pre-pass): sh is a sketch shard; the last merge writes each query's list in front of the extra rows
+// staged in c->d_sent, and ONE rerank on on->sh's rows takes both
+int enqueue_topk(szg_index *ix, Shard *sh, Ctx *c, int kp, int nq, bool has_allow, const RerankOn *on)
 {
+    const int stride = kp + (on ? on->extra : 0);  // entries per query in d_out / h_out
     c->kp_used = kp;
-    c->out_stride = kp;
+    c->out_stride = stride;
     c->sent_in_out = false;
     c->mq_stage2 = false;
     c->mq_band_used = false;
@@ -191,10 +194,11 @@ int enqueue_topk(szg_index *ix, Shard *sh, Ctx *c, int kp, int nq, bool has_allo
         HIPCHK(hipMalloc((void **)&c->d_lists_b, need * sizeof(uint64_t)));
         c->lists_cap = need;
     }
-    int rc = ensure_dev(&c->d_out, &c->d_out_cap, (size_t)nq * kp);
+    int rc = ensure_dev(&c->d_out, &c->d_out_cap, (size_t)nq * stride);
     if (rc) return rc;
-    rc = ensure_host(&c->h_out, &c->h_out_cap, (size_t)nq * kp);
+    rc = ensure_host(&c->h_out, &c->h_out_cap, (size_t)nq * stride);
     if (rc) return rc;
+    if (on && c->d_sent_cap < (size_t)nq * stride) return fail(SZG_E_INVALID, "sketch candidates not staged");
 
     // Masked sweeps: when most rows pass (a few tombstones, a mild filter) every row is read and
     // the masks decide at the row finish -- the predicate-free dense phase; a selective filter
@@ -229,7 +233,13 @@ int enqueue_topk(szg_index *ix, Shard *sh, Ctx *c, int kp, int nq, bool has_allo
         const int fan = szg::merge_fan(kp);
         {
             SiteScope t_(6);
-            while (n_lists > 1) {
+            while (n_lists > 1 || on) {
+                if (on && (n_lists + fan - 1) / fan == 1) {  // (at least this one merge, even of a single list)
+                    uint64_t *cand = c->d_sent + (size_t)q0 * stride;
+                    HIPCHK(szg::launch_merge(src, n_lists, kp, nqp, cand, tl, stride));
+                    src = cand;
+                    break;
+                }
                 HIPCHK(szg::launch_merge(src, n_lists, kp, nqp, dst, tl));
                 n_lists = (n_lists + fan - 1) / fan;
                 std::swap(src, dst);
@@ -237,13 +247,15 @@ int enqueue_topk(szg_index *ix, Shard *sh, Ctx *c, int kp, int nq, bool has_allo
         }
         {
             SiteScope t_(7);
-            HIPCHK(szg::launch_rerank(ix->bits, ix->metric, sh->rows, ix->layout, ix->dim, c->d_q64 + (size_t)q0 * ix->dim,
-                                      src, nullptr, (uint32_t)kp, nqp, c->d_out + (size_t)q0 * kp, tl));
+            const szg_index *rx = on ? on->ix : ix;
+            HIPCHK(szg::launch_rerank(rx->bits, rx->metric, on ? on->sh->rows : sh->rows, rx->layout, rx->dim,
+                                      c->d_q64 + (size_t)q0 * ix->dim, src, nullptr, (uint32_t)stride, nqp,
+                                      c->d_out + (size_t)q0 * stride, tl));
         }
         {
             SiteScope t_(8);
-            HIPCHK(hipMemcpyAsync(c->h_out + (size_t)q0 * kp, c->d_out + (size_t)q0 * kp, sizeof(szg::RerankOut) * kp * nqp,
-                                  hipMemcpyDeviceToHost, tl));
+            HIPCHK(hipMemcpyAsync(c->h_out + (size_t)q0 * stride, c->d_out + (size_t)q0 * stride,
+                                  sizeof(szg::RerankOut) * stride * nqp, hipMemcpyDeviceToHost, tl));
         }
     }
     if (ix->timing >= 2) {
@@ -280,7 +292,7 @@ int finish_timing(szg_index *ix, Ctx *c)
 // real-number key; *lb = a lower bound of the real-number key of every eligible row of the shard that
 // is NOT among them (+inf if every eligible row is).  `m` = the query's constants with the flags
 // of the path the ticket was prepared for; the shard's context says which arithmetic actually
-// produced the keys.
+// produced the keys.  (The first kp_used entries of the query in h_out: the sketch pre-pass has more behind them.)
 void gather_topk(const szg_index *ix, const Shard *sh, const Ctx *c, const QMeta &m, int slot,
                  std::vector<Cand> *cands, double *lb)
 {
