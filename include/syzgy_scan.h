@@ -354,6 +354,12 @@ int szg_reset_stats(szg_index *ix);
  *                             the next mutation or load once 16 of the last 64 queries it took were handed over to the
  *                             full sweep.  1 = always (n >= sketch_min_rows; allocation failures are errors), 0 = never
  *     sketch_extra        30  candidates beyond k; the pre-pass serves k + sketch_extra <= 64
+ *     sketch_list         0   entries the sketch sweep keeps per wave and per block (m): 0 = automatic (8 at 512
+ *                             blocks, max(8, 2 kp / blocks + 8) in general), >= kp = the full kp-entry lists and the
+ *                             two-level merge (the behaviour before short lists).  With m < kp ONE merge launch per
+ *                             batch selects the kp best and the drop bound (the smallest m-th entry of a full block
+ *                             list), and the certificate takes the lower of it and the kp-th key, so a block holding
+ *                             more than m of the best rows sends the query to the full sweep.  Same answers.
  *     sketch_min_rows     4096  collections below this size always take the full sweep
  *   shared sweeps
  *     multi_query         1   batches of >= mq_min queries share ONE sweep of the corpus, the dot products on the

@@ -240,6 +240,12 @@ hipError_t launch_mq_select(const float *keys, size_t key_stride, uint32_t n_row
 // entries behind each list are left alone
 hipError_t launch_merge(const uint64_t *in, int n_lists, int kp, int n_queries, uint64_t *out,
                         hipStream_t stream, int out_stride = 0);
+// Short lists (the sketch sweep): [n_queries][n_lists][m] sorted block lists, m < kp, merged in ONE launch into the
+// kp best per query at out + q * out_stride, followed by the drop bound at [kp]: the smallest m-th entry of a full
+// list (kInvalidCand if none is full).  merge_short_fits: n_lists <= 1024 and the lists fit one block's LDS.
+bool merge_short_fits(int n_lists, int m, int kp);
+hipError_t launch_merge_short(const uint64_t *in, int n_lists, int m, int kp, int n_queries, uint64_t *out,
+                              int out_stride, hipStream_t stream);
 
 struct RerankOut {
     double dist;    // the reference's float64 distance (collection.go:812-832)

@@ -855,6 +855,107 @@ __global__ __launch_bounds__(256) void merge_heads_kernel(const uint64_t *in, in
     }
 }
 
+// minimum of a 32-bit value over the wave (lanes 0..15 only: ROW0), wave-uniform: four DPP steps reduce each row of
+// 16 lanes, readlanes finish across rows
+template <bool ROW0>
+__device__ __forceinline__ uint32_t wave_min_u32(uint32_t v)
+{
+    v = min(v, (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, 0xB1, 0xF, 0xF, false));   // quad_perm [1,0,3,2]
+    v = min(v, (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x4E, 0xF, 0xF, false));   // quad_perm [2,3,0,1]
+    v = min(v, (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x141, 0xF, 0xF, false));  // row_half_mirror
+    v = min(v, (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x140, 0xF, 0xF, false));  // row_mirror
+    uint32_t m = (uint32_t)__builtin_amdgcn_readlane((int)v, 0);
+    if (!ROW0) {
+        m = min(m, (uint32_t)__builtin_amdgcn_readlane((int)v, 16));
+        m = min(m, (uint32_t)__builtin_amdgcn_readlane((int)v, 32));
+        m = min(m, (uint32_t)__builtin_amdgcn_readlane((int)v, 48));
+    }
+    return m;
+}
+
+// the smallest candidate of the wave (lanes 0..15 only: ROW0; the others hold kInvalidCand), wave-uniform: the
+// minimum of the ordered keys (high words), then -- only when several lanes hold that key -- of their rows.  Half the
+// work of a 64-bit reduction per tournament round.
+template <bool ROW0>
+__device__ __forceinline__ uint64_t wave_min_cand(uint64_t v)
+{
+    const uint32_t hi = (uint32_t)(v >> 32), lo = (uint32_t)v;
+    const uint32_t mhi = wave_min_u32<ROW0>(hi);
+    const uint64_t tie = __ballot(hi == mhi);
+    uint32_t mlo;
+    if (__popcll(tie) == 1)
+        mlo = (uint32_t)__builtin_amdgcn_readlane((int)lo, __ffsll((long long)tie) - 1);
+    else
+        mlo = wave_min_u32<ROW0>(hi == mhi ? lo : 0xFFFFFFFFu);
+    return ((uint64_t)mhi << 32) | mlo;
+}
+
+// Short-list merge (the sketch sweep): ONE block per query (blockIdx.y) selects the kp best of the
+// n_lists sorted block lists of m entries each (m < kp) and writes them, sorted, to out[0, kp); out[kp] gets the drop
+// bound -- the smallest m-th entry of a FULL block list (kInvalidCand if no list is full): every row a block did not
+// output is above its list's m-th entry.  Stage 1: wave w runs a tournament over lists [64w, 64w + 64), one list
+// per lane, each lane's next head fetched one advance ahead; stage 2: wave 0 runs one over the <= 16 results.
+// Needs n_lists <= 1024 and merge_short_lds(n_lists, m, kp) <= 64 KiB (merge_short_fits).
+__global__ __launch_bounds__(1024) void merge_short_kernel(const uint64_t *in, int n_lists, int m, int kp,
+                                                           uint64_t *out, int out_stride)
+{
+    extern __shared__ __align__(16) uint8_t smem[];
+    uint64_t *lists = reinterpret_cast<uint64_t *>(smem);  // [n_lists][m]
+    const int ngroups = (n_lists + kWave - 1) / kWave;
+    uint64_t *sel = lists + (size_t)n_lists * m;           // [ngroups][kp]: each group's kp best
+    uint64_t *drops = sel + (size_t)ngroups * kp;          // [ngroups]
+    const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid >> 6;
+    in += (size_t)blockIdx.y * n_lists * m;
+    out += (size_t)blockIdx.y * out_stride;
+    const int total = n_lists * m;
+    for (int i = tid; i < total; i += blockDim.x) lists[i] = in[i];
+    __syncthreads();
+    if (wave < ngroups) {
+        const int l = wave * kWave + lane;
+        const bool have = l < n_lists;
+        const uint64_t *my = lists + (size_t)(have ? l : 0) * m;
+        // (kInvalidCand is the largest value: lists that are not full drop out of the minimum by themselves)
+        const uint64_t drop = wave_min_cand<false>(have ? my[m - 1] : kInvalidCand);
+        uint64_t head = have ? my[0] : kInvalidCand;
+        uint64_t next = have && m > 1 ? my[1] : kInvalidCand;
+        int pos = 1;  // of `next`
+        uint64_t *o = sel + (size_t)wave * kp;
+        for (int r = 0; r < kp; r++) {
+            const uint64_t w = wave_min_cand<false>(head);
+            if (head == w && w != kInvalidCand) {  // entries are unique: exactly one lane advances
+                head = next;
+                pos++;
+                next = pos < m ? my[pos] : kInvalidCand;
+            }
+            if (lane == 0) o[r] = w;
+        }
+        if (lane == 0) drops[wave] = drop;
+    }
+    __syncthreads();
+    if (wave != 0) return;
+    const uint64_t *my = sel + (size_t)(lane < ngroups ? lane : 0) * kp;
+    uint64_t head = lane < ngroups ? my[0] : kInvalidCand;
+    uint64_t next = lane < ngroups && kp > 1 ? my[1] : kInvalidCand;
+    int pos = 1;
+    uint64_t keep = kInvalidCand;  // lane i keeps output i (+64 per round of 64)
+    for (int r = 0; r < kp; r++) {
+        const uint64_t w = wave_min_cand<true>(head);
+        if (head == w && w != kInvalidCand) {
+            head = next;
+            pos++;
+            next = pos < kp ? my[pos] : kInvalidCand;
+        }
+        if ((r & 63) == lane) keep = w;
+        if ((r & 63) == 63 || r == kp - 1) {
+            const int idx = (r & ~63) + lane;
+            if (idx <= r) out[idx] = keep;
+            keep = kInvalidCand;
+        }
+    }
+    const uint64_t drop = wave_min_cand<true>(lane < ngroups ? drops[lane] : kInvalidCand);
+    if (lane == 0) out[kp] = drop;
+}
+
 // Rank merge (any kp): every entry finds its rank by binary searches in the
 // other lists.  More work, fully parallel; used when kp is large.
 __global__ __launch_bounds__(1024) void merge_kernel(const uint64_t *in, int n_lists, int kp,
@@ -1048,6 +1149,27 @@ hipError_t launch_merge(const uint64_t *in, int n_lists, int kp, int n_queries, 
     if (block > 1024) block = 1024;
     block = (block + 63) & ~63;
     hipLaunchKernelGGL(merge_kernel, grid, dim3(block), lds, stream, in, n_lists, kp, fan, out, out_stride);
+    return hipGetLastError();
+}
+
+static size_t merge_short_lds(int n_lists, int m, int kp)
+{
+    const size_t groups = (size_t)(n_lists + kWave - 1) / kWave;
+    return ((size_t)n_lists * m + groups * kp + groups) * sizeof(uint64_t);
+}
+
+bool merge_short_fits(int n_lists, int m, int kp)
+{
+    return n_lists >= 1 && n_lists <= 16 * kWave && m >= 1 && m < kp && merge_short_lds(n_lists, m, kp) <= 64u * 1024u;
+}
+
+hipError_t launch_merge_short(const uint64_t *in, int n_lists, int m, int kp, int n_queries, uint64_t *out,
+                              int out_stride, hipStream_t stream)
+{
+    if (!merge_short_fits(n_lists, m, kp) || out_stride < kp + 1) return hipErrorInvalidValue;
+    const int block = (n_lists + kWave - 1) / kWave * kWave;  // one wave per group of 64 lists
+    hipLaunchKernelGGL(merge_short_kernel, dim3(1, n_queries), dim3(block), merge_short_lds(n_lists, m, kp), stream,
+                       in, n_lists, m, kp, out, out_stride);
     return hipGetLastError();
 }
 

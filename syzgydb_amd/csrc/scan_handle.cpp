@@ -700,6 +700,11 @@ int szg_set_option(szg_index *ix, const char *name, int64_t value)
         ix->sketch_min_rows = (int)std::min<int64_t>(value, 1 << 30);
         return SZG_OK;
     }
+    if (n == "sketch_list") {
+        if (value < 0 || value > 4096) return fail(SZG_E_INVALID, "sketch_list out of range");
+        ix->sketch_list = (int)value;
+        return SZG_OK;
+    }
     if (n == "sketch_extra") {
         if (value < 0 || value > 900) return fail(SZG_E_INVALID, "sketch_extra out of range");
         ix->sketch_extra = (int)value;

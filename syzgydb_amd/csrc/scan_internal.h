@@ -313,6 +313,8 @@ struct szg_index {
     int sketch_extra = 30;               // sketch neighbours asked for beyond k: k = 10 -> 40, which keeps the sketch
                                          // sweep's lists in registers (kp <= 64); the pre-pass serves k <= 34
     int sketch_min_rows = 4096;          // smaller collections are not worth a second index
+    int sketch_list = 0;                 // the sketch sweep's per-wave / per-block list length (0 = automatic, >= kp:
+                                         // kp, the full lists and the two-level merge)
     std::mutex sk_mu;                    // the sync
     uint64_t gen = 1, sk_gen = 0;        // mutation counter / the value the sketch was synced at
     bool sk_need_full = true;            // load / synth / reset since the last sync
@@ -438,7 +440,8 @@ int launch_scans_chained(szg_index *ix, Shard *sh, Ctx *c, const std::vector<szg
 struct RerankOn {
     const szg_index *ix;
     const Shard *sh;
-    int extra;
+    int extra;  // entries behind each list: the drop bound's slot, then the staged rows
+    int list;   // option sketch_list: the sweep's per-wave / per-block list length (0 = automatic, >= kp = kp)
 };
 int enqueue_topk(szg_index *ix, Shard *sh, Ctx *c, int kp, int nq, bool has_allow, const RerankOn *on = nullptr);
 // candidates of staged query `slot` from a finished top-k pass and *lb, the lower bound of the real-number key of every

@@ -258,7 +258,8 @@ struct SketchCall {
     size_t n_sh = 0;
     int kp = 0;
     double gs = 0.0, slack = 0.0;
-    std::vector<int> extra;                     // per shard: entries behind each list (k first rows + remembered rows)
+    std::vector<int> extra;                     // per shard: entries behind each list (the drop bound's slot, k first
+                                                // rows, remembered rows)
     std::vector<uint64_t> firstk_open, firstk;  // first k eligible rows of an unfiltered / of the current query
     std::vector<double> q_scaled;
     std::vector<Cand> cands;
@@ -285,7 +286,7 @@ int SketchCall::run()
         const Shard *a = ix->shards[s];
         size_t exc = 0;
         for (uint64_t r : ix->sk_exc) exc += (r >= a->first && r < a->first + a->n_rows) ? 1 : 0;
-        extra[s] = k + (int)exc;
+        extra[s] = 1 + k + (int)exc;
     }
     first_eligible_rows(ix, nullptr, k, &firstk_open);
     redo.reserve(n_queries);
@@ -316,8 +317,8 @@ int SketchCall::stage(Batch &b)
         q_sk = q_scaled.data();
     }
     int rc = stage_query_forms(sk, b, q_sk, false, [](int, QMeta &) {});
-    // behind each query's list: its first k eligible rows of the shard (kInvalidCand-padded to k), then the shard's
-    // eligible rows without a usable sketch
+    // behind each query's list: the drop bound's slot (the short-list merge writes it), its first k eligible rows of
+    // the shard (kInvalidCand-padded to k), then the shard's eligible rows without a usable sketch
     for (size_t s = 0; s < n_sh && rc == SZG_OK; s++) {
         Ctx *c = b.ctx[s];
         if (!c) continue;
@@ -331,6 +332,7 @@ int SketchCall::stage(Batch &b)
             if (m) first_eligible_rows(ix, m, k, &firstk);
             const std::vector<uint64_t> &fk = m ? firstk : firstk_open;
             uint64_t *o = c->h_sent + (size_t)j * stride + kp;
+            *o++ = szg::kInvalidCand;  // (no drop bound: the full lists' merge leaves it)
             size_t n = 0;
             for (uint64_t r : fk)
                 if (r >= a->first && r < a->first + a->n_rows) o[n++] = r - a->first;
@@ -361,7 +363,7 @@ int SketchCall::stage(Batch &b)
             break;
         }
         rc = enqueue_queries(sk, h, c, q, b.nq, mptr);  // (the float64 queries unscaled: the rerank is on the rows)
-        const RerankOn on{ix, ix->shards[s], extra[s]};
+        const RerankOn on{ix, ix->shards[s], extra[s], ix->sketch_list};
         if (rc == SZG_OK) rc = enqueue_topk(sk, h, c, kp, b.nq, b.any_mask, &on);
     }
     std::lock_guard<std::mutex> lk(ix->stats_mu);
@@ -384,14 +386,20 @@ void SketchCall::settle(Batch &b, int j)
         if (!c) continue;
         double l;
         gather_topk(sk, sk->shards[s], c, c->meta[j], j, &cands, &l);
+        // short lists: a row the sweep's blocks did not output has a key at or above the drop bound (entry kp)
+        const szg::RerankOut &drop = c->h_out[(size_t)j * c->out_stride + kp];
+        if (drop.row != 0xFFFFFFFFu) {
+            const float key = szg::key_from_ordered(drop.ukey);
+            l = std::min(l, (double)key - key_eps(sk, key, c->meta[j]));
+        }
         lb = std::min(lb, l);
         zero_query |= ix->metric == SZG_COSINE && c->meta[j].m1 == 0;
         const uint64_t first = ix->shards[s]->first;
-        for (int i = kp; i < c->out_stride; i++) {
+        for (int i = kp + 1; i < c->out_stride; i++) {
             const szg::RerankOut &r = c->h_out[(size_t)j * c->out_stride + i];
             if (r.row == 0xFFFFFFFFu) continue;
             // outside the first k rows a NaN never enters the heap; among them it decides everything
-            if (std::isnan(r.dist) && i < kp + k) nan_first = true;
+            if (std::isnan(r.dist) && i < kp + 1 + k) nan_first = true;
             cands.push_back(Cand{first + r.row, r.dist, 0.0f, 0.0});
         }
     }

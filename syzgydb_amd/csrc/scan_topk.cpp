@@ -170,9 +170,22 @@ double mask_pass_rate(const Shard *sh, const Ctx *c, bool has_allow, int slot)
     return live * (seen ? (double)ones / (double)seen : 1.0);
 }
 
+// List length m of a sketch sweep over `grid` blocks (option sketch_list).  The query's kp best rows
+// fall about kp / grid to a block; automatic lists hold twice that plus 8 (8 at 512 blocks), so a block rarely has
+// more of them than its list keeps -- and when it has, the drop bound says so and the query falls back.  m >= kp (or
+// lists the one-launch merge cannot hold): the full lists and the two-level merge.
+static int sketch_list_len(int want, int kp, int grid)
+{
+    const int m = want > 0 ? want : std::max(8, 2 * kp / std::max(grid, 1) + 8);
+    if (m >= kp || !szg::merge_short_fits(grid, m, kp)) return kp;
+    return m;
+}
+
 // top-k pass for the nq staged queries of one shard: scan -> merges -> rerank -> D2H (async)
 // on (the sketch pre-pass): sh is a sketch shard; the last merge writes each query's list in front of the extra rows
-// staged in c->d_sent, and ONE rerank on on->sh's rows takes both
+// staged in c->d_sent, and ONE rerank on on->sh's rows takes both.  Its sweeps keep lists of m < kp entries per wave
+// and block where they can; ONE merge launch per part then selects the kp best and writes the drop bound to entry kp
+// (a candidate like the others: the rerank returns its key).
 int enqueue_topk(szg_index *ix, Shard *sh, Ctx *c, int kp, int nq, bool has_allow, const RerankOn *on)
 {
     const int stride = kp + (on ? on->extra : 0);  // entries per query in d_out / h_out
@@ -184,7 +197,9 @@ int enqueue_topk(szg_index *ix, Shard *sh, Ctx *c, int kp, int nq, bool has_allo
     c->mq_bf16_used = false;
     HIPCHK(hipSetDevice(sh->device));
     const LaunchGeom g = scan_geometry(ix, sh, kp, !has_allow && !sh->has_dead);
-    const size_t need = (size_t)nq * g.grid * kp;
+    const int m = on ? sketch_list_len(on->list, kp, g.grid) : kp;  // entries per wave and block list
+    if (on && on->extra < 1) return fail(SZG_E_INVALID, "sketch: no slot for the drop bound");
+    const size_t need = (size_t)nq * g.grid * m;
     if (c->lists_cap < need) {  // both ping-pong buffers grow together
         if (c->d_lists_a) HIPCHK(hipFree(c->d_lists_a));
         if (c->d_lists_b) HIPCHK(hipFree(c->d_lists_b));
@@ -222,18 +237,23 @@ int enqueue_topk(szg_index *ix, Shard *sh, Ctx *c, int kp, int nq, bool has_allo
                 for (int i = j; i < std::min(q1, j + qpl); i++) lowest = std::min(lowest, pass_rate(i));
                 a.mask_dense = lowest >= 0.5 ? 1 : 0;
             }
-            a.kp = kp;
-            a.block_lists = c->d_lists_a + (size_t)j * g.grid * kp;
+            a.kp = m;
+            a.block_lists = c->d_lists_a + (size_t)j * g.grid * m;
         }
         rc = launch_scans_chained(ix, sh, c, args, g, tl, part);
         if (rc) return rc;
 
         int n_lists = g.grid;
-        uint64_t *src = c->d_lists_a + (size_t)q0 * g.grid * kp, *dst = c->d_lists_b + (size_t)q0 * g.grid * kp;
+        uint64_t *src = c->d_lists_a + (size_t)q0 * g.grid * m, *dst = c->d_lists_b + (size_t)q0 * g.grid * m;
         const int fan = szg::merge_fan(kp);
         {
             SiteScope t_(6);
-            while (n_lists > 1 || on) {
+            if (m < kp) {
+                uint64_t *cand = c->d_sent + (size_t)q0 * stride;
+                HIPCHK(szg::launch_merge_short(src, n_lists, m, kp, nqp, cand, stride, tl));
+                src = cand;
+            }
+            while (m == kp && (n_lists > 1 || on)) {
                 if (on && (n_lists + fan - 1) / fan == 1) {  // (at least this one merge, even of a single list)
                     uint64_t *cand = c->d_sent + (size_t)q0 * stride;
                     HIPCHK(szg::launch_merge(src, n_lists, kp, nqp, cand, tl, stride));
