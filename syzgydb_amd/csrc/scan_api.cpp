@@ -45,11 +45,11 @@ int szg_distances(szg_index *ix, const double *query, const uint64_t *rows, uint
             memcpy(c->h_q64, query, sizeof(double) * ix->dim);
             HIPCHK(hipMemcpyAsync(c->d_q64, c->h_q64, sizeof(double) * ix->dim, hipMemcpyHostToDevice,
                                   c->stream));
-            int r2 = ensure_dev(&c->d_collect, &c->collect_cap, cands.size());
+            int r2 = c->d_collect.ensure(cands.size());
             if (r2) return r2;
-            r2 = ensure_dev(&c->d_out, &c->d_out_cap, cands.size());
+            r2 = c->d_out.ensure(cands.size());
             if (r2) return r2;
-            r2 = ensure_host(&c->h_out, &c->h_out_cap, cands.size());
+            r2 = c->h_out.ensure(cands.size());
             if (r2) return r2;
             HIPCHK(hipMemcpyAsync(c->d_collect, cands.data(), cands.size() * sizeof(uint64_t),
                                   hipMemcpyHostToDevice, c->stream));
@@ -126,11 +126,11 @@ int szg_pair_distances(szg_index *ix, const uint64_t *rows_a, const uint64_t *ro
         CtxGuard guard{sh, c};
         HIPCHK(hipSetDevice(sh->device));
         const size_t n = where.size();
-        int rc = ensure_dev(&c->d_collect, &c->collect_cap, n + (n + 1) / 2);  // right rows (u64) + left rows (u32)
+        int rc = c->d_collect.ensure(n + (n + 1) / 2);  // right rows (u64) + left rows (u32)
         if (rc) return rc;
-        rc = ensure_dev(&c->d_out, &c->d_out_cap, n);
+        rc = c->d_out.ensure(n);
         if (rc) return rc;
-        rc = ensure_host(&c->h_out, &c->h_out_cap, n);
+        rc = c->h_out.ensure(n);
         if (rc) return rc;
         uint32_t *d_left = reinterpret_cast<uint32_t *>(c->d_collect + n);
         HIPCHK(hipMemcpyAsync(c->d_collect, right.data(), n * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));

@@ -18,73 +18,45 @@ int ctx_alloc(szg_index *ix, Shard *sh, Ctx **out)
     HIPCHK(hipEventCreateWithFlags(&c->ev_scan_done, hipEventDisableTiming));
     HIPCHK(hipEventCreateWithFlags(&c->ev_up, hipEventDisableTiming));
     const size_t B = kMaxBatch;
-    HIPCHK(hipHostMalloc((void **)&c->h_qsw, B * ix->qsw_bytes, hipHostMallocDefault));
-    HIPCHK(hipHostMalloc((void **)&c->h_q64, B * sizeof(double) * ix->dim, hipHostMallocDefault));
     // hit counters of the collect sweeps, one 128-byte line per sweep of a launch
     const size_t n_count = (size_t)kMaxBatch * szg::kCandCountStride;  // (a batch may hold kMaxBatch sweeps)
-    HIPCHK(hipHostMalloc((void **)&c->h_count, sizeof(uint32_t) * n_count, hipHostMallocDefault));
-    HIPCHK(hipMalloc((void **)&c->d_qsw, B * ix->qsw_bytes));
-    HIPCHK(hipMalloc((void **)&c->d_q64, B * sizeof(double) * ix->dim));
-    HIPCHK(hipMalloc((void **)&c->d_count, sizeof(uint32_t) * n_count));
-    return SZG_OK;
+    int rc = c->h_qsw.ensure(B * ix->qsw_bytes);
+    if (rc == SZG_OK) rc = c->h_q64.ensure(B * ix->dim);
+    if (rc == SZG_OK) rc = c->h_count.ensure(n_count);
+    if (rc == SZG_OK) rc = c->d_qsw.ensure(B * ix->qsw_bytes);
+    if (rc == SZG_OK) rc = c->d_q64.ensure(B * ix->dim);
+    if (rc == SZG_OK) rc = c->d_count.ensure(n_count);
+    return rc;
 }
 
-void ctx_free(Ctx *c)
+void ctx_free(Ctx *c)  // (the buffers free themselves)
 {
     if (!c) return;
     if (c->stream) (void)hipStreamDestroy(c->stream);
     for (hipEvent_t e : {c->ev_scan0, c->ev_scan1, c->ev_all0, c->ev_all1, c->ev_scan_done, c->ev_up, c->ev_p0, c->ev_p1})
         if (e) (void)hipEventDestroy(e);
-    (void)hipHostFree(c->h_qsw);
-    (void)hipHostFree(c->h_q64);
-    (void)hipHostFree(c->h_out);
-    (void)hipHostFree(c->h_allow);
-    (void)hipHostFree(c->h_count);
-    (void)hipFree(c->d_qsw);
-    (void)hipFree(c->d_q64);
-    (void)hipFree(c->d_lists_a);
-    (void)hipFree(c->d_lists_b);
-    (void)hipFree(c->d_out);
-    (void)hipFree(c->d_allow);
-    (void)hipFree(c->d_collect);
-    (void)hipFree(c->d_count);
-    (void)hipHostFree(c->h_mq);
-    free(c->h_mqQ);
-    (void)hipFree(c->d_mq);
-    (void)hipFree(c->d_thr);
-    (void)hipHostFree(c->h_thr);
-    (void)hipHostFree(c->h_qscale);
-    (void)hipFree(c->d_qscale);
-    (void)hipFree(c->d_cand);
-    (void)hipFree(c->d_cand_count);
-    (void)hipHostFree(c->h_cand_count);
-    (void)hipFree(c->d_keys);
-    (void)hipHostFree(c->h_sent);
-    (void)hipFree(c->d_sent);
-    (void)hipHostFree(c->h_sent_out);
-    (void)hipFree(c->d_sent_out);
     delete c;
 }
 
+// the one place a context is handed out (sh->mu held): the record of the batch that had it before ends here
+static Ctx *ctx_take(Shard *sh)
+{
+    Ctx *c = sh->free_ctx.back();
+    sh->free_ctx.pop_back();
+    c->pass = Pass{};
+    c->pass.work = c->stream;
+    return c;
+}
 Ctx *ctx_acquire(Shard *sh)
 {
     std::unique_lock<std::mutex> lk(sh->mu);
     sh->cv.wait(lk, [&] { return !sh->free_ctx.empty(); });
-    Ctx *c = sh->free_ctx.back();
-    sh->free_ctx.pop_back();
-    c->work = c->stream;
-    c->early_n = 0;
-    return c;
+    return ctx_take(sh);
 }
 Ctx *ctx_try_acquire(Shard *sh)
 {
     std::lock_guard<std::mutex> lk(sh->mu);
-    if (sh->free_ctx.empty()) return nullptr;
-    Ctx *c = sh->free_ctx.back();
-    sh->free_ctx.pop_back();
-    c->work = c->stream;
-    c->early_n = 0;
-    return c;
+    return sh->free_ctx.empty() ? nullptr : ctx_take(sh);
 }
 void ctx_release(Shard *sh, Ctx *c)
 {
@@ -402,7 +374,6 @@ void szg_index_destroy(szg_index *ix)
         if (sh->scan_stream) (void)hipStreamDestroy(sh->scan_stream);
         (void)hipFree(sh->zero16);
         (void)hipFree(sh->stage);
-        (void)hipFree(sh->sk_buf);
         (void)hipFree(sh->rows);
         (void)hipFree(sh->live_bits);
         (void)hipFree(sh->row_norm);

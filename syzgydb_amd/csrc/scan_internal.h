@@ -11,6 +11,11 @@
 //   scan_radius.cpp   radius search (single, batch, coalesced)
 //   scan_comm.cpp     one-process-per-GPU exchange (RCCL all-gather + merge)
 //   scan_api.cpp      remaining C entry points (top-k with caller coalescing, distances)
+//
+// What a batch borrows per shard is a Ctx: a stream, events and scratch that persist between batches -- every buffer
+// a DevBuf / PinnedBuf that frees itself -- and one Pass, the record of the batch in flight.  The Pass is reset as a
+// whole where the context is handed out (ctx_acquire), written by the function that enqueues the work and read by
+// the one that finishes it; results in the pinned output buffer are reached through Ctx::out / sentinel / drop_bound.
 #pragma once
 #include "../../include/syzgy_scan.h"
 #include "kernels.h"
@@ -165,78 +170,159 @@ struct Cand {
     double ub;     // key + the error bound of the arithmetic that produced it: the real-number key is <= ub
 };
 
+// ---- owning buffers -------------------------------------------------------------------------------------------------
+// A pointer and a capacity in elements.  ensure(n) does nothing while the buffer holds n elements; otherwise it frees
+// FIRST (the old and the new block never exist side by side) and allocates max(n, 64): the contents are never carried
+// over.  Move-only; the destructor frees.
+template <typename T, bool kPinned>
+class HipBuf {
+    T *p_ = nullptr;
+    size_t cap_ = 0;
+
+public:
+    HipBuf() = default;
+    HipBuf(HipBuf &&o) noexcept : p_(o.p_), cap_(o.cap_) { o.p_ = nullptr, o.cap_ = 0; }
+    HipBuf &operator=(HipBuf &&o) noexcept
+    {
+        std::swap(p_, o.p_);
+        std::swap(cap_, o.cap_);
+        return *this;
+    }
+    ~HipBuf() { (void)reset(); }
+    T *data() const { return p_; }
+    operator T *() const { return p_; }
+    size_t capacity() const { return cap_; }
+    int reset()
+    {
+        if (p_) HIPCHK(kPinned ? hipHostFree(p_) : hipFree(p_));
+        p_ = nullptr;
+        cap_ = 0;
+        return SZG_OK;
+    }
+    int ensure(size_t need)
+    {
+        if (cap_ >= need) return SZG_OK;
+        if (int rc = reset()) return rc;
+        const size_t n = std::max(need, (size_t)64);
+        HIPCHK(kPinned ? hipHostMalloc((void **)&p_, n * sizeof(T), hipHostMallocDefault) : hipMalloc((void **)&p_, n * sizeof(T)));
+        cap_ = n;
+        return SZG_OK;
+    }
+};
+template <typename T> using DevBuf = HipBuf<T, false>;     // device memory
+template <typename T> using PinnedBuf = HipBuf<T, true>;   // pinned host memory
+
 // ---- one in-flight batch of queries on one shard --------------------------------
-struct Ctx {
-    hipStream_t stream = nullptr;
+
+// the arithmetic that produced the list keys of a finished top-k pass: which error bound certifies them (gather_topk)
+enum class ListKeys : uint8_t {
+    Single,        // one sweep per query (the single-query kernels; the sketch sweep): the bound of the row width
+    SharedInt8,    // int8 shared sweep: exact integers, the integer bound with the sweep's own quantization step
+    SharedBf16,    // bfloat16 shared sweep whose keys are the list keys themselves (score-matrix form)
+    Bf16Rescored,  // bfloat16 sweep -> float32 re-score of its candidates -> selection: float32 list keys, and every row
+                   // the sweep did not collect has a bfloat16 key above h_thr[q], the prefix threshold
+    Bf16Band,      // ... re-scored only inside a band (the refine launch): h_thr[128 + q] = the band's edge as well
+};
+inline bool from_bf16_sweep(ListKeys k) { return k >= ListKeys::SharedBf16; }
+
+// the sentinel rows of the staged queries -- the first k eligible rows of each in visit order (those consider() pushes
+// whatever their distance, collection.go:608) -- and where their float64 distances are: a NaN there poisons the
+// reference's heap, so the query takes the exact replay
+enum class Sentinels : uint8_t {
+    None,    // none staged
+    Staged,  // the rows are up (d_sent), their distances not yet enqueued
+    Own,     // distances in h_sent_out (a rerank launch of their own)
+    InOut,   // distances are entries [kp, out_stride) of each query in h_out (they rode in the batch's one rerank)
+};
+
+// What was enqueued for the batch that has borrowed the context: reset as a whole when the context is handed out
+// (ctx_acquire), written by the enqueue function that stages the work, read when the batch is finished.  Nothing in
+// here outlives the batch.
+struct Pass {
     hipStream_t work = nullptr;    // where this batch's uploads and post-processing go: `stream`, or the shard's scan
-                                   // stream for a call that is a single batch (set at acquire time)
+                                   // stream for a call that is a single batch (Batch::acquire)
     int early_n = 0;               // a short call (one batch on the scan stream): the merges, re-rank and copy-back of its
                                    // first early_n queries go onto `stream` behind one event and run -- like the host's
                                    // assembly of those queries -- beside the call's last sweeps (0 = one tail for all)
+    int kp = 0;                    // candidates per query in h_out
+    int out_stride = 0;            // entries per query in h_out: kp, + what rides behind each list (the sentinels; the
+                                   // sketch pre-pass's drop bound and extra rows)
+    ListKeys keys = ListKeys::Single;
+    Sentinels sent = Sentinels::None;
+    bool sent_own_stream = false;  // their re-rank runs on `stream` while the batch runs on the scan stream (`work`)
+    int sent_n = 0;                // sentinel entries per query
+    // fused selection of a shared sweep: what the rerun of an overflowed candidate buffer needs
+    uint32_t cand_cap = 0;         // > 0: the selection was the fused one, with this many entries per query's buffer
+    int nb = 0;
+    bool has_allow = false;
+    // HIP-event timing: scan launches between ev_scan0 and ev_scan1 / ev_p0 and ev_p1 (0 = that pair was not recorded)
+    int timed_n = 0, timed_part_n = 0;
+};
+
+// A context is what a batch borrows per shard: a stream, events and scratch buffers that persist between batches,
+// and the record of the batch in flight (pass).
+struct Ctx {
+    hipStream_t stream = nullptr;
     hipEvent_t ev_p0 = nullptr, ev_p1 = nullptr;  // HIP-event timing of the early part's sweeps
-    bool timed_part = false;
-    int timed_part_n = 0;
     hipEvent_t ev_scan0 = nullptr, ev_scan1 = nullptr, ev_all0 = nullptr, ev_all1 = nullptr;
-    float mq_qsum[128] = {};             // bfloat16 sweep of 8-bit rows: the sum of each staged query's rounded image values
     hipEvent_t ev_scan_done = nullptr;   // this batch's scans have finished (scan stream)
     hipEvent_t ev_up = nullptr;          // this batch's uploads have finished (ctx stream)
-    // pinned host staging, kMaxBatch queries
-    uint8_t *h_qsw = nullptr;      // swizzled queries for the scan
-    double *h_q64 = nullptr;       // float64 queries for the rerank
-    szg::RerankOut *h_out = nullptr;
-    size_t h_out_cap = 0;
-    uint64_t *h_allow = nullptr;
-    size_t h_allow_cap = 0;        // words
-    uint32_t *h_count = nullptr;
-    // device scratch
-    uint8_t *d_qsw = nullptr;
-    double *d_q64 = nullptr;
-    uint64_t *d_lists_a = nullptr, *d_lists_b = nullptr;
-    size_t lists_cap = 0;          // entries per buffer
-    szg::RerankOut *d_out = nullptr;
-    size_t d_out_cap = 0;
-    uint64_t *d_allow = nullptr;
-    size_t allow_cap = 0;          // words
-    uint64_t *d_collect = nullptr;
-    size_t collect_cap = 0;        // entries
-    uint32_t *d_count = nullptr;   // hit counters of collect sweeps, one 128-byte line per sweep of a launch
+    Pass pass;
+    // overwritten by staging (not part of the per-acquire reset: 8 KB)
+    QMeta meta[kMaxBatch];               // constants of the staged queries
+    float mq_qsum[128] = {};             // bfloat16 sweep of 8-bit rows: the sum of each staged query's rounded image values
     size_t radius_cap = 0;         // radius batches: entries per sweep the next batch's buffers get (follows the hit counts seen)
+    // pinned host staging, kMaxBatch queries
+    PinnedBuf<uint8_t> h_qsw;      // swizzled queries for the scan
+    PinnedBuf<double> h_q64;       // float64 queries for the rerank
+    PinnedBuf<szg::RerankOut> h_out;
+    PinnedBuf<uint64_t> h_allow;   // words
+    PinnedBuf<uint32_t> h_count;
+    // device scratch
+    DevBuf<uint8_t> d_qsw;
+    DevBuf<double> d_q64;
+    DevBuf<uint64_t> d_lists_a, d_lists_b;  // merge ping-pong (ensure_lists)
+    DevBuf<szg::RerankOut> d_out;
+    DevBuf<uint64_t> d_allow;      // words
+    DevBuf<uint64_t> d_collect;    // entries
+    DevBuf<uint32_t> d_count;      // hit counters of collect sweeps, one 128-byte line per sweep of a launch
     // multi-query sweep: LDS image of the batch, score matrix
-    uint8_t *h_mq = nullptr, *d_mq = nullptr;
-    int32_t *h_mqQ = nullptr;      // 4-bit int8 sweep: the queries as integers (kMaxBatch x dim)
-    size_t h_mq_cap = 0, d_mq_cap = 0;
-    float *d_keys = nullptr;
-    size_t keys_cap = 0;           // floats
+    PinnedBuf<uint8_t> h_mq;
+    DevBuf<uint8_t> d_mq;
+    std::vector<int32_t> h_mqQ;    // 4-bit int8 sweep: the queries as integers (kMaxBatch x dim)
+    DevBuf<float> d_keys;
     // fused selection of the shared sweep: thresholds, candidate buffers, hit counts
-    float *d_thr = nullptr;
-    float *h_thr = nullptr;        // (pinned) the prefix thresholds of a two-stage batch, for certification
-    double *h_qscale = nullptr, *d_qscale = nullptr;  // [128] float32-query scale per staged query (re-score)
-    int kp_used = 0;               // candidates per query in h_out for the batch in flight
-    int out_stride = 0;            // entries per query in h_out: kp_used, + sent_n when the sentinels ride along
-    bool sent_deferred = false;    // the sentinel rows are staged (d_sent) but their distances not yet enqueued
-    bool sent_in_out = false;      // their distances are entries [kp_used, out_stride) of each query in h_out
-    bool sent_own_stream = false;  // their re-rank runs on `stream` while the batch runs on the scan stream (`work`)
-    bool mq_band_used = false;     // bfloat16 sweep refined by the band form: h_thr[128 + q] = the band's edge
-    bool mq_stage2 = false;        // bfloat16 sweep -> float32 re-score of its candidates -> selection
-    bool mq_bf16_used = false;     // the list keys of this batch are bfloat16-sweep keys (matrix form)
-    uint64_t *d_cand = nullptr;
-    size_t cand_cap_total = 0;     // entries
-    uint32_t *d_cand_count = nullptr, *h_cand_count = nullptr;
-    bool mq_fused_used = false;
-    uint32_t mq_cand_cap = 0;
-    int mq_nb = 0;
-    bool mq_has_allow = false;
-    bool timed_scan = false;
-    int timed_n = 0;               // scan launches between ev_scan0 and ev_scan1
-    // the first k eligible rows of each staged query in visit order (those consider() pushes
-    // whatever their distance, collection.go:608) and their float64 distances: a NaN there
-    // poisons the reference's heap, so the query takes the exact replay
-    uint64_t *h_sent = nullptr, *d_sent = nullptr;
-    size_t h_sent_cap = 0, d_sent_cap = 0;
-    szg::RerankOut *h_sent_out = nullptr, *d_sent_out = nullptr;
-    size_t h_sent_out_cap = 0, d_sent_out_cap = 0;
-    int sent_n = 0;                // entries per query (0 = none staged)
-    QMeta meta[kMaxBatch];         // constants of the staged queries
+    DevBuf<float> d_thr;           // [256] thresholds | band edges
+    PinnedBuf<float> h_thr;        // the prefix thresholds of a two-stage batch, for certification
+    PinnedBuf<double> h_qscale;    // [256] float32-query scale per staged query (re-score) | |g|^2
+    DevBuf<double> d_qscale;
+    DevBuf<uint64_t> d_cand;
+    DevBuf<uint32_t> d_cand_count;
+    PinnedBuf<uint32_t> h_cand_count;
+    // the sentinel rows (Sentinels) and their distances; the sketch pre-pass keeps each query's candidates -- its
+    // merged list, the drop bound's slot, the extra rows -- in h_sent / d_sent instead
+    PinnedBuf<uint64_t> h_sent;
+    DevBuf<uint64_t> d_sent;
+    PinnedBuf<szg::RerankOut> h_sent_out;
+    DevBuf<szg::RerankOut> d_sent_out;
+
+    // both ping-pong buffers grow together, and both are freed before either comes back
+    int ensure_lists(size_t need)
+    {
+        if (d_lists_b.capacity() >= need) return SZG_OK;  // (allocated last: it has the room only if d_lists_a has)
+        int rc = d_lists_a.reset();
+        if (rc == SZG_OK) rc = d_lists_b.reset();
+        if (rc == SZG_OK) rc = d_lists_a.ensure(need);
+        return rc ? rc : d_lists_b.ensure(need);
+    }
+    // entry i of staged query j in h_out: i < pass.kp its list, then what rides behind it
+    const szg::RerankOut &out(int j, int i) const { return h_out[(size_t)j * pass.out_stride + i]; }
+    const szg::RerankOut &sentinel(int j, int i) const  // i < pass.sent_n
+    {
+        return pass.sent == Sentinels::InOut ? out(j, pass.kp + i) : h_sent_out[(size_t)j * pass.sent_n + i];
+    }
+    // sketch pre-pass with short lists: every row the sweep's blocks did not output has a key at or above this one
+    const szg::RerankOut &drop_bound(int j) const { return out(j, pass.kp); }
 };
 
 struct Shard {
@@ -273,10 +359,6 @@ struct Shard {
     uint8_t *stage = nullptr;
     size_t stage_cap = 0;
     std::mutex stage_mu;         // szg_index_read_rows may run beside other readers (szg_pair_distances)
-    // second stage of the sketch pre-pass: queries | candidate lists | distances, kept between calls
-    uint8_t *sk_buf = nullptr;
-    size_t sk_buf_cap = 0;
-    std::mutex sk_buf_mu;
 };
 
 }  // namespace szgi
@@ -430,8 +512,8 @@ int enqueue_queries(szg_index *ix, Shard *sh, Ctx *c, const double *q, int nq, c
                     bool with_single_form = true);
 void fill_scan_args(const szg_index *ix, const Shard *sh, const Ctx *c, bool has_allow, int slot, int nq,
                     szg::ScanArgs *a);
-// (after: the stream that goes on once the sweeps are done -- default c->work; part 1: the early part of a short call,
-// timed with its own event pair)
+// (after: the stream that goes on once the sweeps are done -- default the work stream; part 1: the early part of a short
+// call, timed with its own event pair)
 int launch_scans_chained(szg_index *ix, Shard *sh, Ctx *c, const std::vector<szg::ScanArgs> &a, const LaunchGeom &g,
                          hipStream_t after = nullptr, int part = 0);
 // the sketch pre-pass: the sweep runs over a sketch shard, its merged lists are re-ranked on the float32 rows of the
@@ -448,9 +530,16 @@ int enqueue_topk(szg_index *ix, Shard *sh, Ctx *c, int kp, int nq, bool has_allo
 // eligible row of the shard that is not among them
 void gather_topk(const szg_index *ix, const Shard *sh, const Ctx *c, const QMeta &m, int slot, std::vector<Cand> *cands,
                  double *lb);
-// float64 distances of the staged sentinel rows (d_sent) on `stream`, results to h_sent_out
+// float64 distances of the staged sentinel rows (Sentinels::Staged, d_sent) on `stream`, results to h_sent_out
 int launch_sentinel_rerank(szg_index *ix, Shard *sh, Ctx *c, int nq, hipStream_t stream);
 int finish_timing(szg_index *ix, Ctx *c);
+// the rows of `rows` (index-level) that fall into the shard: how many, and shard-local to out[] (null: only counted)
+size_t rows_in_shard(const Shard *sh, const std::vector<uint64_t> &rows, uint64_t *out);
+// the k result slots of query qi of a call (rows + row_base; unused slots UINT64_MAX / 0.0)
+void emit_topk(const szg_index *ix, const std::vector<HeapItem> &res, int k, int qi, uint64_t *out_rows, double *out_dist,
+               int32_t *out_count);
+// the end of a call's stage(): host time of the preparation [t_prep0, t_enq0) and of the enqueueing [t_enq0, now)
+void note_stage_times(szg_index *ix, double t_prep0, double t_enq0);
 int run_collect(szg_index *ix, Shard *sh, Ctx *c, int slot, float thr_key, bool has_allow, std::vector<Cand> *cands);
 // fraction of the shard's rows that staged query `slot` may visit (tombstones, and a sample of its filter mask's words)
 double mask_pass_rate(const Shard *sh, const Ctx *c, bool has_allow, int slot);
@@ -472,8 +561,9 @@ int search_radius_impl(szg_index *ix, const double *queries, int n_queries, cons
 // ---- scan_mq.cpp
 // the shard's resident row norms are complete (16-bit rows; no-op otherwise): called before a shared sweep is enqueued
 int ensure_row_norms(szg_index *ix, Shard *sh);
+// (rerun: the fused selection of this batch overflowed on this context -- again, through the score matrix)
 int enqueue_topk_mq(szg_index *ix, Shard *sh, Ctx *c, int kp, int kp_wide, int nq, int nb, bool has_allow,
-                    bool force_matrix = false);
+                    bool rerun = false);
 
 // the batch's tail will compute the sentinel rows' distances itself (stage them, do not launch their own rerank)
 bool mq_tail_takes_sentinels(const szg_index *ix, const Shard *sh, int kp, int kp_wide, int nq, int nb);
@@ -489,37 +579,46 @@ int search_topk_any(szg_index *ix, const double *queries, int n_queries, int k, 
                     uint64_t *out_rows, double *out_dist, int32_t *out_count,
                     const uint64_t *const *allow_ptrs = nullptr);
 
+// One link of the shard's scan chain: under chain_mu, launch(st) puts the sweeps onto the shard's scan stream behind the
+// batch's uploads (ev_up, recorded on the work stream by the caller), and `after` goes on once they are done.  With
+// timing on the sweeps sit between an event pair (part 1: the early part's own) and count as n launches.  `what`
+// names the launch in the error text.
+template <class Launch>
+int chain_sweeps(szg_index *ix, Shard *sh, Ctx *c, hipStream_t after, int part, int n, const char *what, Launch &&launch)
+{
+    std::lock_guard<std::mutex> lk(sh->chain_mu);
+    hipStream_t st = ix->serialize_scans ? sh->scan_stream : c->pass.work;
+    if (st != c->pass.work) {
+        SiteScope t_(1);
+        HIPCHK(hipStreamWaitEvent(st, c->ev_up, 0));
+    }
+    if (ix->timing) {
+        SiteScope t_(2);
+        HIPCHK(hipEventRecord(part ? c->ev_p0 : c->ev_scan0, st));
+    }
+    {
+        SiteScope t_(3);
+        const hipError_t e = launch(st);
+        if (e != hipSuccess) return fail(SZG_E_DEVICE, what, e);
+    }
+    if (ix->timing) {
+        SiteScope t_(4);
+        HIPCHK(hipEventRecord(part ? c->ev_p1 : c->ev_scan1, st));
+        (part ? c->pass.timed_part_n : c->pass.timed_n) = n;
+    }
+    if (st != after) {
+        SiteScope t_(5);
+        HIPCHK(hipEventRecord(c->ev_scan_done, st));
+        HIPCHK(hipStreamWaitEvent(after, c->ev_scan_done, 0));
+    }
+    return SZG_OK;
+}
+
 struct CtxGuard {  // returns a borrowed context on every exit path
     Shard *sh;
     Ctx *c;
     ~CtxGuard() { ctx_release(sh, c); }
 };
-
-template <typename T>
-int ensure_dev(T **p, size_t *cap, size_t need)
-{
-    if (*cap >= need) return SZG_OK;
-    if (*p) HIPCHK(hipFree(*p));
-    *p = nullptr;
-    *cap = 0;
-    size_t n = std::max(need, (size_t)64);
-    HIPCHK(hipMalloc((void **)p, n * sizeof(T)));
-    *cap = n;
-    return SZG_OK;
-}
-template <typename T>
-int ensure_host(T **p, size_t *cap, size_t need)
-{
-    if (*cap >= need) return SZG_OK;
-    if (*p) HIPCHK(hipHostFree(*p));
-    *p = nullptr;
-    *cap = 0;
-    size_t n = std::max(need, (size_t)64);
-    HIPCHK(hipHostMalloc((void **)p, n * sizeof(T), hipHostMallocDefault));
-    *cap = n;
-    return SZG_OK;
-}
-
 
 // ---- the batch pipeline of a search call (top-k and radius; scan_topk.cpp) ----------------------------------------
 //
@@ -555,7 +654,8 @@ struct Batch {
     int first = 0, nq = 0;
     int nb = 0;                  // > 0: the batch shares one sweep (query blocks of 16)
     bool single = false;         // the whole call is this one batch (a short call)
-    int early_n = 0;             // ... whose first early_n queries' tail runs beside its last sweeps (Ctx::early_n)
+    int early_n = 0;             // ... whose first early_n queries' tail runs beside its last sweeps (Pass::early_n;
+                                 // settled by acquire: 0 unless the batch runs on the scan stream)
     bool any_mask = false;       // some query of the batch carries a filter mask
     bool failed = false;         // enqueueing failed part-way: drain and release only
     std::vector<Ctx *> ctx;      // one per shard (null: the shard is empty)

@@ -9,7 +9,7 @@ namespace szgi {
 // step]; cosine: q/|q|.
 void build_image_bf16(const szg_index *ix, Ctx *c, int nq, int nb)
 {
-    uint16_t *im = reinterpret_cast<uint16_t *>(c->h_mq);
+    uint16_t *im = reinterpret_cast<uint16_t *>(c->h_mq.data());
     const int dim = ix->dim;
     for (int q = 0; q < nq; q++) {
         const double *src = c->h_q64 + (size_t)q * dim;
@@ -54,7 +54,7 @@ void build_image_i8(const szg_index *ix, Ctx *c, int nq, int nb, size_t group_st
     const size_t plane = (size_t)T * nb * 64 * 16;  // bytes between digit planes of a step
     const size_t half = (size_t)nb * 64 * 16;       // 4-bit rows: bytes from the even elements' operand to the odd elements'
     for (int q = 0; q < nq; q++) {
-        const int32_t *Qv = c->h_mqQ + (size_t)q * dim;
+        const int32_t *Qv = c->h_mqQ.data() + (size_t)q * dim;
         const int ql = q % (16 * nb);  // position inside its group
         uint8_t *im8 = c->h_mq + (size_t)(q / (16 * nb)) * group_stride;
         const int b = ql / 16, qi = ql % 16;
@@ -180,42 +180,29 @@ MqPlan mq_plan(const szg_index *ix, const Shard *sh, int kp, int kp_wide, int nq
 int mq_buffers(szg_index *ix, Ctx *c, const MqPlan &p, int nq, int n_out)
 {
     const int sb = 16;  // select blocks per query (score-matrix form)
-    const size_t need = (size_t)nq * std::max<size_t>((size_t)sb * p.kp, (size_t)n_out);
-    if (c->lists_cap < need) {
-        if (c->d_lists_a) HIPCHK(hipFree(c->d_lists_a));
-        if (c->d_lists_b) HIPCHK(hipFree(c->d_lists_b));
-        c->d_lists_a = c->d_lists_b = nullptr;
-        c->lists_cap = 0;
-        HIPCHK(hipMalloc((void **)&c->d_lists_a, need * sizeof(uint64_t)));
-        HIPCHK(hipMalloc((void **)&c->d_lists_b, need * sizeof(uint64_t)));
-        c->lists_cap = need;
+    int rc = c->ensure_lists((size_t)nq * std::max<size_t>((size_t)sb * p.kp, (size_t)n_out));
+    if (rc == SZG_OK) rc = c->d_out.ensure((size_t)nq * n_out);
+    if (rc == SZG_OK) rc = c->h_out.ensure((size_t)nq * n_out);
+    if (rc == SZG_OK) rc = c->d_keys.ensure(p.key_stride * nq);
+    if (rc == SZG_OK && p.fused) {
+        rc = c->d_thr.ensure(256);  // thresholds | band edges
+        if (rc == SZG_OK) rc = c->h_thr.ensure(256);
+        if (rc == SZG_OK) rc = c->d_cand_count.ensure(128 * szg::kCandCountStride);
+        if (rc == SZG_OK) rc = c->h_cand_count.ensure(128 * szg::kCandCountStride);
+        if (rc == SZG_OK) rc = c->d_cand.ensure((size_t)p.cand_cap * nq);
     }
-    int rc = ensure_dev(&c->d_out, &c->d_out_cap, (size_t)nq * n_out);
+    if (rc || !p.stage2) return rc;
+    // float32 re-score: 1/|q| (cosine) or 1 per query, then |g|^2 (the euclid band's width)
+    rc = c->h_qscale.ensure(256);
+    if (rc == SZG_OK) rc = c->d_qscale.ensure(256);
     if (rc) return rc;
-    rc = ensure_host(&c->h_out, &c->h_out_cap, (size_t)nq * n_out);
-    if (rc) return rc;
-    rc = ensure_dev(&c->d_keys, &c->keys_cap, p.key_stride * nq);
-    if (rc) return rc;
-    if (p.fused) {
-        if (!c->d_thr) HIPCHK(hipMalloc((void **)&c->d_thr, 256 * sizeof(float)));  // thresholds | band edges
-        if (!c->h_thr) HIPCHK(hipHostMalloc((void **)&c->h_thr, 256 * sizeof(float), hipHostMallocDefault));
-        if (!c->d_cand_count) HIPCHK(hipMalloc((void **)&c->d_cand_count, 128 * szg::kCandCountStride * sizeof(uint32_t)));
-        if (!c->h_cand_count)
-            HIPCHK(hipHostMalloc((void **)&c->h_cand_count, 128 * szg::kCandCountStride * sizeof(uint32_t), hipHostMallocDefault));
-        rc = ensure_dev(&c->d_cand, &c->cand_cap_total, (size_t)p.cand_cap * nq);
-        if (rc) return rc;
+    for (int q = 0; q < nq; q++) {
+        const double m1 = c->meta[q].m1;
+        c->h_qscale[q] = ix->metric == SZG_COSINE ? (m1 > 0 ? 1.0 / std::sqrt(m1) : 0.0)
+                                                  : (ix->bits == 16 ? 65535.0 : (ix->bits == 8 ? 255.0 : 1.0));  // euclid: the prepared query, maxInt * q
+        c->h_qscale[128 + q] = c->meta[q].qnorm2;
     }
-    if (p.stage2) {  // float32 re-score: 1/|q| (cosine) or 1 per query, then |g|^2 (the euclid band's width)
-        if (!c->h_qscale) HIPCHK(hipHostMalloc((void **)&c->h_qscale, 256 * sizeof(double), hipHostMallocDefault));
-        if (!c->d_qscale) HIPCHK(hipMalloc((void **)&c->d_qscale, 256 * sizeof(double)));
-        for (int q = 0; q < nq; q++) {
-            const double m1 = c->meta[q].m1;
-            c->h_qscale[q] = ix->metric == SZG_COSINE ? (m1 > 0 ? 1.0 / std::sqrt(m1) : 0.0)
-                                                      : (ix->bits == 16 ? 65535.0 : (ix->bits == 8 ? 255.0 : 1.0));  // euclid: the prepared query, maxInt * q
-            c->h_qscale[128 + q] = c->meta[q].qnorm2;
-        }
-        HIPCHK(hipMemcpyAsync(c->d_qscale, c->h_qscale, sizeof(double) * 256, hipMemcpyHostToDevice, c->stream));
-    }
+    HIPCHK(hipMemcpyAsync(c->d_qscale, c->h_qscale, sizeof(double) * 256, hipMemcpyHostToDevice, c->stream));
     return SZG_OK;
 }
 
@@ -230,9 +217,9 @@ bool mq_tail_takes_sentinels(const szg_index *ix, const Shard *sh, int kp, int k
 static int upload_mq_image(szg_index *ix, Ctx *c, int nq, int nb, bool bf16, bool i8, size_t img, size_t group_stride,
                            hipStream_t st)
 {
-    int rc = ensure_host(&c->h_mq, &c->h_mq_cap, img);
+    int rc = c->h_mq.ensure(img);
     if (rc) return rc;
-    rc = ensure_dev(&c->d_mq, &c->d_mq_cap, img);
+    rc = c->d_mq.ensure(img);
     if (rc) return rc;
     memset(c->h_mq, 0, img);
     if (bf16) build_image_bf16(ix, c, nq, nb);
@@ -277,12 +264,12 @@ static szg::MqArgs mq_args_base(const szg_index *ix, const Shard *sh, const Ctx 
 // kp_wide: the list length when the lists hold bfloat16-sweep keys themselves (matrix form), whose error band needs
 // more candidates than kp.
 int enqueue_topk_mq(szg_index *ix, Shard *sh, Ctx *c, int kp, int kp_wide, int nq, int nb, bool has_allow,
-                    bool force_matrix)
+                    bool rerun)
 {
     HIPCHK(hipSetDevice(sh->device));
     int rc_norm = ensure_row_norms(ix, sh);
     if (rc_norm) return rc_norm;
-    const MqPlan p = mq_plan(ix, sh, kp, kp_wide, nq, nb, force_matrix);
+    const MqPlan p = mq_plan(ix, sh, kp, kp_wide, nq, nb, rerun);
     // (the kernel indexes thresholds, keys and candidates of group g by 48 g + q: a second group needs full groups)
     if (p.groups > 2 || (p.groups == 2 && nb != 3)) return fail(SZG_E_INVALID, "int8 shared sweep: two groups need 48 queries each");
     kp = p.kp;
@@ -290,22 +277,22 @@ int enqueue_topk_mq(szg_index *ix, Shard *sh, Ctx *c, int kp, int kp_wide, int n
     if (rc) return rc;
 
     // sentinel rows staged by the caller ride in the batch's one rerank when the tail is the refine launch;
-    // otherwise (score-matrix form, an overflow rerun) they get their own
-    const int n_sent = c->sent_deferred ? c->sent_n : 0;
+    // otherwise (score-matrix form, an overflow rerun) they get their own.  (A rerun: rows that rode in the first
+    // pass's rerank are staged, not yet launched, once more -- d_sent still holds them.)
+    if (rerun && c->pass.sent == Sentinels::InOut) c->pass.sent = Sentinels::Staged;
+    const int n_sent = c->pass.sent == Sentinels::Staged ? c->pass.sent_n : 0;
     const bool merge_sent = p.refine && n_sent > 0;
     const int n_out = kp + (merge_sent ? n_sent : 0);
     rc = mq_buffers(ix, c, p, nq, n_out);
     if (rc) return rc;
-    c->mq_fused_used = p.fused;
-    c->mq_cand_cap = p.cand_cap;
-    c->mq_nb = nb;
-    c->mq_has_allow = has_allow;
-    c->kp_used = kp;
-    c->out_stride = n_out;
-    c->sent_in_out = merge_sent;
-    c->mq_stage2 = p.stage2;
-    c->mq_band_used = p.stage2 && p.refine;
-    c->mq_bf16_used = p.bf16 && !p.stage2;
+    c->pass.cand_cap = p.fused ? p.cand_cap : 0;
+    c->pass.nb = nb;
+    c->pass.has_allow = has_allow;
+    c->pass.kp = kp;
+    c->pass.out_stride = n_out;
+    if (merge_sent) c->pass.sent = Sentinels::InOut;
+    c->pass.keys = p.stage2 ? (p.refine ? ListKeys::Bf16Band : ListKeys::Bf16Rescored)
+                            : (p.bf16 ? ListKeys::SharedBf16 : ListKeys::SharedInt8);
 
     szg::MqArgs a = mq_args_base(ix, sh, c, nq, p.groups, p.group_stride);
     a.keys = c->d_keys;
@@ -354,8 +341,7 @@ int enqueue_topk_mq(szg_index *ix, Shard *sh, Ctx *c, int kp, int kp_wide, int n
         HIPCHK(launch_score(a, st));
         if (ix->timing) {
             HIPCHK(hipEventRecord(c->ev_scan1, st));
-            c->timed_scan = true;
-            c->timed_n = p.groups;  // (passes: an int8 launch may walk two)
+            c->pass.timed_n = p.groups;  // (passes: an int8 launch may walk two)
         }
         hipStream_t tail = st;
         if ((ix->mq_tail_overlap || overlap) && st != c->stream) {
@@ -368,7 +354,7 @@ int enqueue_topk_mq(szg_index *ix, Shard *sh, Ctx *c, int kp, int kp_wide, int n
             const int mode = !p.stage2 ? 0 : (ix->metric == SZG_COSINE ? 1 : 2);
             HIPCHK(szg::launch_cand_refine(mode, sh->rows, ix->layout, ix->dim, c->d_q64, c->d_qscale,
                                            c->d_qscale ? c->d_qscale + 128 : nullptr, c->d_cand, c->d_cand_count,
-                                           p.cand_cap, kp, nq, merge_sent ? c->d_sent : nullptr, merge_sent ? n_sent : 0,
+                                           p.cand_cap, kp, nq, merge_sent ? c->d_sent.data() : nullptr, merge_sent ? n_sent : 0,
                                            c->d_lists_a, c->d_thr + 128, ix->bits, tail));
         } else if (p.fused) {
             if (p.stage2)
@@ -436,12 +422,13 @@ int enqueue_collect_mq(szg_index *ix, Shard *sh, Ctx *c, int nq, int nb, bool ha
     const size_t group_stride = i8 ? ((szg::mq_i8_image_bytes(ix->bits, r16, nb) + 3 * 48 * sizeof(float) + 255) & ~(size_t)255) : 0;
     if (!bf16 && !i8) return fail(SZG_E_INVALID, "no shared sweep for this row width");
     const size_t img = bf16 ? szg::mq_bf16_image_bytes(ix->bits, r16, nb) : group_stride * groups;
-    int rc = upload_mq_image(ix, c, nq, nb, bf16, i8, img, group_stride, c->work);
+    int rc = upload_mq_image(ix, c, nq, nb, bf16, i8, img, group_stride, c->pass.work);
     if (rc) return rc;
-    if (!c->d_thr) HIPCHK(hipMalloc((void **)&c->d_thr, 256 * sizeof(float)));
-    if (!c->h_thr) HIPCHK(hipHostMalloc((void **)&c->h_thr, 256 * sizeof(float), hipHostMallocDefault));
+    rc = c->d_thr.ensure(256);
+    if (rc == SZG_OK) rc = c->h_thr.ensure(256);
+    if (rc) return rc;
     for (int q = 0; q < nq; q++) c->h_thr[q] = thr[q];
-    HIPCHK(hipMemcpyAsync(c->d_thr, c->h_thr, sizeof(float) * nq, hipMemcpyHostToDevice, c->work));
+    HIPCHK(hipMemcpyAsync(c->d_thr, c->h_thr, sizeof(float) * nq, hipMemcpyHostToDevice, c->pass.work));
 
     szg::MqArgs a = mq_args_base(ix, sh, c, nq, groups, group_stride);
     a.collect = 1;
@@ -452,26 +439,13 @@ int enqueue_collect_mq(szg_index *ix, Shard *sh, Ctx *c, int nq, int nb, bool ha
     a.live_bits = sh->has_dead ? sh->live_bits : nullptr;
     a.allow_bits = has_allow ? c->d_allow : nullptr;
     a.allow_stride = (uint32_t)shard_words(sh);
-    {
-        std::lock_guard<std::mutex> lk(sh->chain_mu);
-        hipStream_t st = ix->serialize_scans ? sh->scan_stream : c->work;
-        if (st != c->work) {  // the sweep must see the image, the thresholds, the masks and the zeroed counters
-            HIPCHK(hipEventRecord(c->ev_up, c->work));
-            HIPCHK(hipStreamWaitEvent(st, c->ev_up, 0));
-        }
-        if (ix->timing) HIPCHK(hipEventRecord(c->ev_scan0, st));
-        if (bf16) HIPCHK(szg::launch_mq_score_bf16(ix->bits, a, nb, sh->cu_count, st));
-        else HIPCHK(szg::launch_mq_score_i8(ix->bits, a, nb, sh->cu_count, st));
-        if (ix->timing) {
-            HIPCHK(hipEventRecord(c->ev_scan1, st));
-            c->timed_scan = true;
-            c->timed_n = groups;
-        }
-        if (st != c->work) {
-            HIPCHK(hipEventRecord(c->ev_scan_done, st));
-            HIPCHK(hipStreamWaitEvent(c->work, c->ev_scan_done, 0));
-        }
-    }
+    // the sweep must see the image, the thresholds, the masks and the zeroed counters (on the work stream itself: in order)
+    if (ix->serialize_scans && sh->scan_stream != c->pass.work) HIPCHK(hipEventRecord(c->ev_up, c->pass.work));
+    rc = chain_sweeps(ix, sh, c, c->pass.work, 0, groups, bf16 ? "szg::launch_mq_score_bf16" : "szg::launch_mq_score_i8", [&](hipStream_t st) {
+        return bf16 ? szg::launch_mq_score_bf16(ix->bits, a, nb, sh->cu_count, st)
+                    : szg::launch_mq_score_i8(ix->bits, a, nb, sh->cu_count, st);
+    });
+    if (rc) return rc;
     std::lock_guard<std::mutex> lk(ix->stats_mu);
     ix->stats.scan_launches += (uint64_t)groups;
     ix->stats.scan_bytes += (uint64_t)groups * sh->n_rows * (uint64_t)ix->row_bytes;

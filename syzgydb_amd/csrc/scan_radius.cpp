@@ -106,12 +106,12 @@ int RadiusCall::enqueue_shard(RadiusBatch &t, size_t s)
     // its share is swept again on its own)
     if (t.nb > 0) cap = std::min(cap, std::max(kRadiusCapMin, ((size_t)8 << 20) / (size_t)t.nq));
     t.cap[s] = cap;
-    int rc = ensure_dev(&c->d_collect, &c->collect_cap, cap * (size_t)t.nq);
+    int rc = c->d_collect.ensure(cap * (size_t)t.nq);
     if (rc) return rc;
-    rc = ensure_dev(&c->d_out, &c->d_out_cap, cap * (size_t)t.nq);
+    rc = c->d_out.ensure(cap * (size_t)t.nq);
     if (rc) return rc;
-    HIPCHK(hipMemsetAsync(c->d_count, 0, sizeof(uint32_t) * (size_t)t.nq * szg::kCandCountStride, c->work));
-    HIPCHK(hipEventRecord(c->ev_up, c->work));  // the sweeps must see the queries, the masks and the zeroed counters
+    HIPCHK(hipMemsetAsync(c->d_count, 0, sizeof(uint32_t) * (size_t)t.nq * szg::kCandCountStride, c->pass.work));
+    HIPCHK(hipEventRecord(c->ev_up, c->pass.work));  // the sweeps must see the queries, the masks and the zeroed counters
     if (t.nb > 0) {  // one shared sweep for the whole batch
         rc = enqueue_collect_mq(ix, sh, c, t.nq, t.nb, t.any_mask, t.thr.data(), cap);
         if (rc) return rc;
@@ -139,21 +139,21 @@ int RadiusCall::enqueue_shard(RadiusBatch &t, size_t s)
     }
     // float64 distances of the hits: the counts stay on the device
     HIPCHK(szg::launch_rerank(ix->bits, ix->metric, sh->rows, ix->layout, ix->dim, c->d_q64, c->d_collect, c->d_count,
-                              (uint32_t)cap, t.nq, c->d_out, c->work, szg::kCandCountStride));
+                              (uint32_t)cap, t.nq, c->d_out, c->pass.work, szg::kCandCountStride));
     // ... and each query's hits sorted by distance there too (lists of up to kSortHitsMax: the host only filters)
-    HIPCHK(szg::launch_sort_hits(c->d_out, c->d_count, szg::kCandCountStride, (uint32_t)cap, t.nq, c->work));
+    HIPCHK(szg::launch_sort_hits(c->d_out, c->d_count, szg::kCandCountStride, (uint32_t)cap, t.nq, c->pass.work));
     HIPCHK(hipMemcpyAsync(c->h_count, c->d_count, sizeof(uint32_t) * (size_t)t.nq * szg::kCandCountStride, hipMemcpyDeviceToHost,
-                          c->work));
+                          c->pass.work));
     // the re-ranked hits: while the batch's buffers are small (the usual hundreds of hits per query) the whole block
     // follows in ONE copy right here -- finish() then needs a single wait; larger ones are copied hit list by hit
     // list once the counts are known
     // (a shared sweep's batch of up to 96 queries: a copy call per hit list costs more than 64 KiB of transfer each)
     t.copied[s] = cap * (size_t)t.nq * sizeof(szg::RerankOut) <= std::max(kRadiusBlockCopyBytes, (size_t)t.nq * (64u << 10));
     if (t.copied[s]) {
-        rc = ensure_host(&c->h_out, &c->h_out_cap, cap * (size_t)t.nq);
+        rc = c->h_out.ensure(cap * (size_t)t.nq);
         if (rc) return rc;
         HIPCHK(hipMemcpyAsync(c->h_out, c->d_out, cap * (size_t)t.nq * sizeof(szg::RerankOut), hipMemcpyDeviceToHost,
-                              c->work));
+                              c->pass.work));
     }
     return SZG_OK;
 }
@@ -182,9 +182,7 @@ int RadiusCall::stage(RadiusBatch &t)
         rc = enqueue_queries(ix, ix->shards[s], t.ctx[s], q, t.nq, t.any_mask ? m.data() : nullptr, t.nb == 0);
         if (rc == SZG_OK) rc = enqueue_shard(t, s);
     }
-    std::lock_guard<std::mutex> lk(ix->stats_mu);
-    ix->stats.host_prep_us += t1 - t0;
-    ix->stats.host_enqueue_us += now_us() - t1;
+    note_stage_times(ix, t0, t1);
     return rc;
 }
 
@@ -207,7 +205,7 @@ int RadiusCall::finish(RadiusBatch &t)
         Shard *sh = ix->shards[s];
         const double tw = now_us();
         hipError_t e = hipSetDevice(sh->device);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->work);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->pass.work);
         if (e != hipSuccess) return fail(SZG_E_DEVICE, "hipStreamSynchronize", e);
         rc = finish_timing(ix, c);
         if (rc) break;
@@ -229,15 +227,15 @@ int RadiusCall::finish(RadiusBatch &t)
             for (int j = 0; j < t.nq; j++) off[j] = (size_t)j * cap;
         } else if (off[t.nq]) {
             // exact-size copies of each sweep's re-ranked hits, back to back in the pinned buffer
-            rc = ensure_host(&c->h_out, &c->h_out_cap, off[t.nq]);
+            rc = c->h_out.ensure(off[t.nq]);
             if (rc) break;
             for (int j = 0; j < t.nq; j++) {
                 if (!cnt[j]) continue;
                 e = hipMemcpyAsync(c->h_out + off[j], c->d_out + (size_t)j * cap, cnt[j] * sizeof(szg::RerankOut),
-                                   hipMemcpyDeviceToHost, c->work);
+                                   hipMemcpyDeviceToHost, c->pass.work);
                 if (e != hipSuccess) return fail(SZG_E_DEVICE, "hipMemcpyAsync(radius hits)", e);
             }
-            e = hipStreamSynchronize(c->work);
+            e = hipStreamSynchronize(c->pass.work);
             if (e != hipSuccess) return fail(SZG_E_DEVICE, "hipStreamSynchronize", e);
         }
         t_wait += now_us() - tw;

@@ -324,8 +324,8 @@ int SketchCall::stage(Batch &b)
         if (!c) continue;
         const Shard *a = ix->shards[s];
         const size_t stride = (size_t)kp + extra[s];
-        rc = ensure_host(&c->h_sent, &c->h_sent_cap, (size_t)b.nq * stride);
-        if (rc == SZG_OK) rc = ensure_dev(&c->d_sent, &c->d_sent_cap, (size_t)b.nq * stride);
+        rc = c->h_sent.ensure((size_t)b.nq * stride);
+        if (rc == SZG_OK) rc = c->d_sent.ensure((size_t)b.nq * stride);
         if (rc) break;
         for (int j = 0; j < b.nq; j++) {
             const uint64_t *m = masks[j];
@@ -333,9 +333,7 @@ int SketchCall::stage(Batch &b)
             const std::vector<uint64_t> &fk = m ? firstk : firstk_open;
             uint64_t *o = c->h_sent + (size_t)j * stride + kp;
             *o++ = szg::kInvalidCand;  // (no drop bound: the full lists' merge leaves it)
-            size_t n = 0;
-            for (uint64_t r : fk)
-                if (r >= a->first && r < a->first + a->n_rows) o[n++] = r - a->first;
+            size_t n = rows_in_shard(a, fk, o);
             for (; n < (size_t)k; n++) o[n] = szg::kInvalidCand;
             for (uint64_t r : ix->sk_exc) {
                 if (r < a->first || r >= a->first + a->n_rows) continue;
@@ -351,13 +349,10 @@ int SketchCall::stage(Batch &b)
         if (!c) continue;
         Shard *h = sk->shards[s];
         const size_t stride = (size_t)kp + extra[s];
-        c->sent_n = 0;
-        c->sent_deferred = false;
-        c->sent_own_stream = false;
         hipError_t e = hipSetDevice(h->device);
         // (ahead of the queries' upload: the sweeps wait for that, and the merges and rerank come after the sweeps)
         if (e == hipSuccess)
-            e = hipMemcpyAsync(c->d_sent, c->h_sent, sizeof(uint64_t) * b.nq * stride, hipMemcpyHostToDevice, c->work);
+            e = hipMemcpyAsync(c->d_sent, c->h_sent, sizeof(uint64_t) * b.nq * stride, hipMemcpyHostToDevice, c->pass.work);
         if (e != hipSuccess) {
             rc = fail(SZG_E_DEVICE, "sketch candidates upload", e);
             break;
@@ -366,10 +361,7 @@ int SketchCall::stage(Batch &b)
         const RerankOn on{ix, ix->shards[s], extra[s], ix->sketch_list};
         if (rc == SZG_OK) rc = enqueue_topk(sk, h, c, kp, b.nq, b.any_mask, &on);
     }
-    std::lock_guard<std::mutex> lk(ix->stats_mu);
-    const double t_end = now_us();
-    ix->stats.host_prep_us += t_enq0 - t_prep0;
-    ix->stats.host_enqueue_us += t_end - t_enq0;
+    note_stage_times(ix, t_prep0, t_enq0);
     return rc;
 }
 
@@ -387,7 +379,7 @@ void SketchCall::settle(Batch &b, int j)
         double l;
         gather_topk(sk, sk->shards[s], c, c->meta[j], j, &cands, &l);
         // short lists: a row the sweep's blocks did not output has a key at or above the drop bound (entry kp)
-        const szg::RerankOut &drop = c->h_out[(size_t)j * c->out_stride + kp];
+        const szg::RerankOut &drop = c->drop_bound(j);
         if (drop.row != 0xFFFFFFFFu) {
             const float key = szg::key_from_ordered(drop.ukey);
             l = std::min(l, (double)key - key_eps(sk, key, c->meta[j]));
@@ -395,8 +387,8 @@ void SketchCall::settle(Batch &b, int j)
         lb = std::min(lb, l);
         zero_query |= ix->metric == SZG_COSINE && c->meta[j].m1 == 0;
         const uint64_t first = ix->shards[s]->first;
-        for (int i = kp + 1; i < c->out_stride; i++) {
-            const szg::RerankOut &r = c->h_out[(size_t)j * c->out_stride + i];
+        for (int i = kp + 1; i < c->pass.out_stride; i++) {
+            const szg::RerankOut &r = c->out(j, i);
             if (r.row == 0xFFFFFFFFu) continue;
             // outside the first k rows a NaN never enters the heap; among them it decides everything
             if (std::isnan(r.dist) && i < kp + 1 + k) nan_first = true;
@@ -430,12 +422,7 @@ void SketchCall::settle(Batch &b, int j)
         redo.push_back(qi);
         return;
     }
-    for (int i = 0; i < k; i++) {
-        const bool have = i < (int)res.size();
-        out_rows[(size_t)qi * k + i] = have ? res[i].row + ix->row_base : UINT64_MAX;
-        out_dist[(size_t)qi * k + i] = have ? res[i].priority : 0.0;
-    }
-    if (out_count) out_count[qi] = (int32_t)res.size();
+    emit_topk(ix, res, k, qi, out_rows, out_dist, out_count);
 }
 
 int SketchCall::finish(Batch &b)
@@ -446,17 +433,15 @@ int SketchCall::finish(Batch &b)
     }
     const size_t redo0 = redo.size();
     int rc = SZG_OK;
-    // a short call's first queries (Ctx::early_n) are complete once the contexts' own streams are
-    int early = 0;
-    for (size_t s = 0; s < n_sh; s++)
-        if (b.ctx[s] && b.ctx[s]->early_n > 0 && b.ctx[s]->early_n < b.nq) early = b.ctx[s]->early_n;
+    // a short call's first queries (Batch::early_n) are complete once the contexts' own streams are
+    const int early = b.early_n;
     double t_host = 0.0;
     for (int phase = early ? 0 : 1; phase < 2 && rc == SZG_OK; phase++) {
         for (size_t s = 0; s < n_sh && rc == SZG_OK; s++) {
             Ctx *c = b.ctx[s];
             if (!c) continue;
             hipError_t e = hipSetDevice(ix->shards[s]->device);
-            if (e == hipSuccess) e = hipStreamSynchronize(phase ? c->work : c->stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(phase ? c->pass.work : c->stream);
             if (e == hipSuccess && phase) e = hipStreamSynchronize(c->stream);
             if (e != hipSuccess) rc = fail(SZG_E_DEVICE, "hipStreamSynchronize", e);
             if (rc == SZG_OK && phase) rc = finish_timing(sk, c);

@@ -48,20 +48,20 @@ int enqueue_queries(szg_index *ix, Shard *sh, Ctx *c, const double *q, int nq, c
     memcpy(c->h_q64, q, sizeof(double) * ix->dim * nq);
     if (ix->timing >= 2) {
         SiteScope t_(10);
-        HIPCHK(hipEventRecord(c->ev_all0, c->work));
+        HIPCHK(hipEventRecord(c->ev_all0, c->pass.work));
     }
     {
         SiteScope t_(0);
         if (with_single_form)
-            HIPCHK(hipMemcpyAsync(c->d_qsw, c->h_qsw, ix->qsw_bytes * nq, hipMemcpyHostToDevice, c->work));
+            HIPCHK(hipMemcpyAsync(c->d_qsw, c->h_qsw, ix->qsw_bytes * nq, hipMemcpyHostToDevice, c->pass.work));
         HIPCHK(hipMemcpyAsync(c->d_q64, c->h_q64, sizeof(double) * ix->dim * nq, hipMemcpyHostToDevice,
-                              c->work));
+                              c->pass.work));
     }
     if (masks) {
         const size_t words = shard_words(sh);
-        int rc = ensure_dev(&c->d_allow, &c->allow_cap, words * nq);
+        int rc = c->d_allow.ensure(words * nq);
         if (rc) return rc;
-        rc = ensure_host(&c->h_allow, &c->h_allow_cap, words * nq);
+        rc = c->h_allow.ensure(words * nq);
         if (rc) return rc;
         for (int i = 0; i < nq; i++) {
             if (masks[i])
@@ -70,11 +70,11 @@ int enqueue_queries(szg_index *ix, Shard *sh, Ctx *c, const double *q, int nq, c
                 memset(c->h_allow + (size_t)i * words, 0xFF, words * sizeof(uint64_t));
         }
         HIPCHK(hipMemcpyAsync(c->d_allow, c->h_allow, words * nq * sizeof(uint64_t),
-                              hipMemcpyHostToDevice, c->work));
+                              hipMemcpyHostToDevice, c->pass.work));
     }
     // what the sweeps wait for ends here: work enqueued on this stream afterwards (the first-k
     // rows' distances) runs beside the sweeps
-    HIPCHK(hipEventRecord(c->ev_up, c->work));
+    HIPCHK(hipEventRecord(c->ev_up, c->pass.work));
     return SZG_OK;
 }
 
@@ -111,41 +111,14 @@ void fill_scan_args(const szg_index *ix, const Shard *sh, const Ctx *c, bool has
 int launch_scans_chained(szg_index *ix, Shard *sh, Ctx *c, const std::vector<szg::ScanArgs> &a,
                          const LaunchGeom &g, hipStream_t after, int part)
 {
-    if (!after) after = c->work;
     const int n = (int)a.size();
-    {
-        std::lock_guard<std::mutex> lk(sh->chain_mu);
-        hipStream_t st = ix->serialize_scans ? sh->scan_stream : c->work;
-        if (st != c->work) {
-            SiteScope t_(1);
-            HIPCHK(hipStreamWaitEvent(st, c->ev_up, 0));  // recorded by enqueue_queries
-        }
-        if (ix->timing) {
-            SiteScope t_(2);
-            HIPCHK(hipEventRecord(part ? c->ev_p0 : c->ev_scan0, st));
-        }
-        {
-            SiteScope t_(3);
-            for (int j = 0; j < n; j++)
-                HIPCHK(szg::launch_scan(ix->bits, ix->metric, a[j], g.grid, g.block, st));
-        }
-        if (ix->timing) {
-            SiteScope t_(4);
-            HIPCHK(hipEventRecord(part ? c->ev_p1 : c->ev_scan1, st));
-            if (part) {
-                c->timed_part = true;
-                c->timed_part_n = n;
-            } else {
-                c->timed_scan = true;
-                c->timed_n = n;
-            }
-        }
-        if (st != after) {
-            SiteScope t_(5);
-            HIPCHK(hipEventRecord(c->ev_scan_done, st));
-            HIPCHK(hipStreamWaitEvent(after, c->ev_scan_done, 0));
-        }
-    }
+    // (ev_up: recorded by enqueue_queries)
+    int rc = chain_sweeps(ix, sh, c, after ? after : c->pass.work, part, n, "szg::launch_scan", [&](hipStream_t st) {
+        hipError_t e = hipSuccess;
+        for (int j = 0; j < n && e == hipSuccess; j++) e = szg::launch_scan(ix->bits, ix->metric, a[j], g.grid, g.block, st);
+        return e;
+    });
+    if (rc) return rc;
     std::lock_guard<std::mutex> lk(ix->stats_mu);
     uint64_t sweeps = 0;
     for (const szg::ScanArgs &x : a) sweeps += (uint64_t)x.n_queries;
@@ -189,31 +162,18 @@ static int sketch_list_len(int want, int kp, int grid)
 int enqueue_topk(szg_index *ix, Shard *sh, Ctx *c, int kp, int nq, bool has_allow, const RerankOn *on)
 {
     const int stride = kp + (on ? on->extra : 0);  // entries per query in d_out / h_out
-    c->kp_used = kp;
-    c->out_stride = stride;
-    c->sent_in_out = false;
-    c->mq_stage2 = false;
-    c->mq_band_used = false;
-    c->mq_bf16_used = false;
+    c->pass.kp = kp;
+    c->pass.out_stride = stride;
+    c->pass.keys = ListKeys::Single;
     HIPCHK(hipSetDevice(sh->device));
     const LaunchGeom g = scan_geometry(ix, sh, kp, !has_allow && !sh->has_dead);
     const int m = on ? sketch_list_len(on->list, kp, g.grid) : kp;  // entries per wave and block list
     if (on && on->extra < 1) return fail(SZG_E_INVALID, "sketch: no slot for the drop bound");
-    const size_t need = (size_t)nq * g.grid * m;
-    if (c->lists_cap < need) {  // both ping-pong buffers grow together
-        if (c->d_lists_a) HIPCHK(hipFree(c->d_lists_a));
-        if (c->d_lists_b) HIPCHK(hipFree(c->d_lists_b));
-        c->d_lists_a = c->d_lists_b = nullptr;
-        c->lists_cap = 0;
-        HIPCHK(hipMalloc((void **)&c->d_lists_a, need * sizeof(uint64_t)));
-        HIPCHK(hipMalloc((void **)&c->d_lists_b, need * sizeof(uint64_t)));
-        c->lists_cap = need;
-    }
-    int rc = ensure_dev(&c->d_out, &c->d_out_cap, (size_t)nq * stride);
+    int rc = c->ensure_lists((size_t)nq * g.grid * m);
+    if (rc == SZG_OK) rc = c->d_out.ensure((size_t)nq * stride);
+    if (rc == SZG_OK) rc = c->h_out.ensure((size_t)nq * stride);
     if (rc) return rc;
-    rc = ensure_host(&c->h_out, &c->h_out_cap, (size_t)nq * stride);
-    if (rc) return rc;
-    if (on && c->d_sent_cap < (size_t)nq * stride) return fail(SZG_E_INVALID, "sketch candidates not staged");
+    if (on && c->d_sent.capacity() < (size_t)nq * stride) return fail(SZG_E_INVALID, "sketch candidates not staged");
 
     // Masked sweeps: when most rows pass (a few tombstones, a mild filter) every row is read and
     // the masks decide at the row finish -- the predicate-free dense phase; a selective filter
@@ -221,13 +181,13 @@ int enqueue_topk(szg_index *ix, Shard *sh, Ctx *c, int kp, int nq, bool has_allo
     auto pass_rate = [&](int j) { return mask_pass_rate(sh, c, has_allow, j); };
     const bool masked = has_allow || sh->has_dead;
     const int qpl = std::max(1, ix->queries_per_launch);
-    // One part -- or, for a short call (c->early_n), two: the sweeps of queries [0, early_n), whose merges, re-rank and
+    // One part -- or, for a short call (Pass::early_n), two: the sweeps of queries [0, early_n), whose merges, re-rank and
     // copy-back leave the scan stream for the context's own (one event), and the last few queries, whose tail is all
     // that is left to do after the call's final sweep.
-    const int early = c->early_n > 0 && c->early_n < nq ? c->early_n : 0;
+    const int early = c->pass.early_n > 0 && c->pass.early_n < nq ? c->pass.early_n : 0;
     for (int part = early ? 1 : 0; part >= 0; part--) {
         const int q0 = part ? 0 : early, q1 = part ? early : nq, nqp = q1 - q0;
-        hipStream_t tl = part ? c->stream : c->work;
+        hipStream_t tl = part ? c->stream : c->pass.work;
         std::vector<szg::ScanArgs> args((nqp + qpl - 1) / qpl);
         for (int j = q0; j < q1; j += qpl) {  // one sweep per query, results side by side
             szg::ScanArgs &a = args[(j - q0) / qpl];
@@ -280,7 +240,7 @@ int enqueue_topk(szg_index *ix, Shard *sh, Ctx *c, int kp, int nq, bool has_allo
     }
     if (ix->timing >= 2) {
         SiteScope t_(10);
-        HIPCHK(hipEventRecord(c->ev_all1, c->work));
+        HIPCHK(hipEventRecord(c->ev_all1, c->pass.work));
     }
     return SZG_OK;
 }
@@ -288,23 +248,16 @@ int enqueue_topk(szg_index *ix, Shard *sh, Ctx *c, int kp, int nq, bool has_allo
 int finish_timing(szg_index *ix, Ctx *c)
 {
     if (!ix->timing) return SZG_OK;
+    Pass &p = c->pass;
     float ms_scan = 0, ms_all = 0, ms_part = 0;
-    if (c->timed_scan) HIPCHK(hipEventElapsedTime(&ms_scan, c->ev_scan0, c->ev_scan1));
-    if (c->timed_part) {  // the early part of a short call
-        HIPCHK(hipEventElapsedTime(&ms_part, c->ev_p0, c->ev_p1));
-        ms_scan += ms_part;
-        c->timed_n = (c->timed_scan ? c->timed_n : 0) + c->timed_part_n;
-        c->timed_scan = true;
-        c->timed_part = false;
-    }
+    if (p.timed_n) HIPCHK(hipEventElapsedTime(&ms_scan, c->ev_scan0, c->ev_scan1));
+    if (p.timed_part_n) HIPCHK(hipEventElapsedTime(&ms_part, c->ev_p0, c->ev_p1));  // the early part of a short call
     if (ix->timing >= 2) HIPCHK(hipEventElapsedTime(&ms_all, c->ev_all0, c->ev_all1));
     std::lock_guard<std::mutex> lk(ix->stats_mu);
-    if (c->timed_scan) {
-        ix->stats.scan_ms += ms_scan;
-        ix->stats.timed_launches += c->timed_n;
-    }
+    ix->stats.scan_ms += ms_scan + ms_part;
+    ix->stats.timed_launches += p.timed_n + p.timed_part_n;
     ix->stats.total_ms += ms_all;
-    c->timed_scan = false;
+    p.timed_n = p.timed_part_n = 0;  // (consumed: an escalation or a rerun on this context records anew)
     return SZG_OK;
 }
 
@@ -312,17 +265,27 @@ int finish_timing(szg_index *ix, Ctx *c)
 // real-number key; *lb = a lower bound of the real-number key of every eligible row of the shard that
 // is NOT among them (+inf if every eligible row is).  `m` = the query's constants with the flags
 // of the path the ticket was prepared for; the shard's context says which arithmetic actually
-// produced the keys.  (The first kp_used entries of the query in h_out: the sketch pre-pass has more behind them.)
+// produced the keys (Pass::keys).  (The first Pass::kp entries of the query in h_out: more may ride behind them.)
 void gather_topk(const szg_index *ix, const Shard *sh, const Ctx *c, const QMeta &m, int slot,
                  std::vector<Cand> *cands, double *lb)
 {
-    const int kp = c->kp_used;
+    const int kp = c->pass.kp;
     QMeta lm = m;  // class of the list's keys
-    if (m.mq) lm.mq_bf16 = c->mq_bf16_used;
+    bool thr_bound = false, band_bound = false;  // rows left out ahead of the lists, by their bfloat16 key
+    switch (c->pass.keys) {
+    case ListKeys::Single:
+    case ListKeys::SharedInt8: break;  // (what the ticket was prepared for)
+    case ListKeys::SharedBf16: lm.mq_bf16 = true; break;
+    case ListKeys::Bf16Band: band_bound = true; [[fallthrough]];
+    case ListKeys::Bf16Rescored:
+        lm.mq_bf16 = false;
+        thr_bound = true;
+        break;
+    }
     int valid = 0;
     float worst = -INFINITY;
     for (int i = 0; i < kp; i++) {
-        const szg::RerankOut &r = c->h_out[(size_t)slot * c->out_stride + i];
+        const szg::RerankOut &r = c->out(slot, i);
         if (r.row == 0xFFFFFFFFu) continue;
         valid++;
         const float key = szg::key_from_ordered(r.ukey);
@@ -334,14 +297,14 @@ void gather_topk(const szg_index *ix, const Shard *sh, const Ctx *c, const QMeta
         cands->push_back(Cand{sh->first + r.row, r.dist, key, ub});
     }
     *lb = valid == kp ? (double)worst - key_eps(ix, worst, lm) : INFINITY;
-    if (c->mq_stage2) {
+    if (thr_bound) {
         // rows the bfloat16 sweep did not collect: bfloat16 key above the prefix threshold
         QMeta bm = m;
         bm.mq_bf16 = true;
         const float thr = c->h_thr[slot];
         if (thr < 3.0e38f) *lb = std::min(*lb, (double)thr - key_eps(ix, thr, bm));
         // collected, but outside the band that was scored again in float32: bfloat16 key above the band's edge
-        if (c->mq_band_used) {
+        if (band_bound) {
             const float edge = c->h_thr[128 + slot];
             if (edge < 3.0e38f) *lb = std::min(*lb, (double)edge - key_eps(ix, edge, bm));
         }
@@ -356,45 +319,45 @@ int run_collect(szg_index *ix, Shard *sh, Ctx *c, int slot, float thr_key, bool 
 {
     HIPCHK(hipSetDevice(sh->device));
     if (sh->n_rows == 0) return SZG_OK;
-    size_t want = std::max<size_t>(c->collect_cap, 1u << 16);
+    size_t want = std::max<size_t>(c->d_collect.capacity(), 1u << 16);
     for (;;) {
-        int rc = ensure_dev(&c->d_collect, &c->collect_cap, want);
+        int rc = c->d_collect.ensure(want);
         if (rc) return rc;
-        if (ix->timing >= 2) HIPCHK(hipEventRecord(c->ev_all0, c->work));
-        HIPCHK(hipMemsetAsync(c->d_count, 0, sizeof(uint32_t), c->work));
-        HIPCHK(hipEventRecord(c->ev_up, c->work));  // the sweep must see the zeroed counter
+        if (ix->timing >= 2) HIPCHK(hipEventRecord(c->ev_all0, c->pass.work));
+        HIPCHK(hipMemsetAsync(c->d_count, 0, sizeof(uint32_t), c->pass.work));
+        HIPCHK(hipEventRecord(c->ev_up, c->pass.work));  // the sweep must see the zeroed counter
         std::vector<szg::ScanArgs> a(1);
         fill_scan_args(ix, sh, c, has_allow, slot, 1, &a[0]);
         a[0].collect = 1;
         a[0].thr_ukeys[0] = szg::ordered_key(thr_key);
         a[0].collect_buf = c->d_collect;
-        a[0].collect_cap = (uint32_t)std::min<size_t>(c->collect_cap, 0xFFFFFFFFu);
+        a[0].collect_cap = (uint32_t)std::min<size_t>(c->d_collect.capacity(), 0xFFFFFFFFu);
         a[0].collect_count = c->d_count;
         const LaunchGeom g = scan_geometry(ix, sh, 0);
         rc = launch_scans_chained(ix, sh, c, a, g);
         if (rc) return rc;
         HIPCHK(hipMemcpyAsync(c->h_count, c->d_count, sizeof(uint32_t), hipMemcpyDeviceToHost,
-                              c->work));
-        if (ix->timing >= 2) HIPCHK(hipEventRecord(c->ev_all1, c->work));
-        HIPCHK(hipStreamSynchronize(c->work));
+                              c->pass.work));
+        if (ix->timing >= 2) HIPCHK(hipEventRecord(c->ev_all1, c->pass.work));
+        HIPCHK(hipStreamSynchronize(c->pass.work));
         rc = finish_timing(ix, c);
         if (rc) return rc;
         const uint32_t count = c->h_count[0];
-        if (count > c->collect_cap) {
+        if (count > c->d_collect.capacity()) {
             want = (size_t)count + count / 8 + 1024;
             continue;
         }
         if (count == 0) return SZG_OK;
-        rc = ensure_dev(&c->d_out, &c->d_out_cap, (size_t)count);
+        rc = c->d_out.ensure((size_t)count);
         if (rc) return rc;
-        rc = ensure_host(&c->h_out, &c->h_out_cap, (size_t)count);
+        rc = c->h_out.ensure((size_t)count);
         if (rc) return rc;
         HIPCHK(szg::launch_rerank(ix->bits, ix->metric, sh->rows, ix->layout, ix->dim,
                                   c->d_q64 + (size_t)slot * ix->dim, c->d_collect, nullptr, count, 1,
-                                  c->d_out, c->work));
+                                  c->d_out, c->pass.work));
         HIPCHK(hipMemcpyAsync(c->h_out, c->d_out, sizeof(szg::RerankOut) * count,
-                              hipMemcpyDeviceToHost, c->work));
-        HIPCHK(hipStreamSynchronize(c->work));
+                              hipMemcpyDeviceToHost, c->pass.work));
+        HIPCHK(hipStreamSynchronize(c->pass.work));
         cands->reserve(cands->size() + count);
         for (uint32_t i = 0; i < count; i++) {
             const szg::RerankOut &r = c->h_out[i];
@@ -418,20 +381,20 @@ static int replay_all_rows(szg_index *ix, std::vector<Ctx *> &ctx, int slot, con
         Ctx *c = ctx[s];
         HIPCHK(hipSetDevice(sh->device));
         const size_t n = sh->n_rows;
-        int rc = ensure_dev(&c->d_out, &c->d_out_cap, n);
+        int rc = c->d_out.ensure(n);
         if (rc) return rc;
-        rc = ensure_host(&c->h_out, &c->h_out_cap, n);
+        rc = c->h_out.ensure(n);
         if (rc) return rc;
         HIPCHK(szg::launch_rerank(ix->bits, ix->metric, sh->rows, ix->layout, ix->dim,
                                   c->d_q64 + (size_t)slot * ix->dim, nullptr, nullptr, (uint32_t)n, 1,
-                                  c->d_out, c->work));
+                                  c->d_out, c->pass.work));
         HIPCHK(hipMemcpyAsync(c->h_out, c->d_out, sizeof(szg::RerankOut) * n, hipMemcpyDeviceToHost,
-                              c->work));
+                              c->pass.work));
         std::vector<uint64_t> live((n + 63) / 64, ~0ull);
         if (sh->has_dead)
             HIPCHK(hipMemcpyAsync(live.data(), sh->live_bits, live.size() * sizeof(uint64_t),
-                                  hipMemcpyDeviceToHost, c->work));
-        HIPCHK(hipStreamSynchronize(c->work));
+                                  hipMemcpyDeviceToHost, c->pass.work));
+        HIPCHK(hipStreamSynchronize(c->pass.work));
         const uint64_t *aw = allow ? allow + sh->first / 64 : nullptr;
         for (size_t r = 0; r < n; r++) {
             if (!((live[r >> 6] >> (r & 63)) & 1)) continue;       // removed record
@@ -465,7 +428,7 @@ int replay_rows_into_heap(szg_index *ix, const double *query, const uint64_t *al
         if (!c) continue;
         HIPCHK(hipSetDevice(ix->shards[s]->device));
         memcpy(c->h_q64, query, sizeof(double) * ix->dim);
-        HIPCHK(hipMemcpyAsync(c->d_q64, c->h_q64, sizeof(double) * ix->dim, hipMemcpyHostToDevice, c->work));
+        HIPCHK(hipMemcpyAsync(c->d_q64, c->h_q64, sizeof(double) * ix->dim, hipMemcpyHostToDevice, c->pass.work));
     }
     const int rc = replay_all_rows(ix, b.ctx, 0, allow, k, *h, ix->row_base);
     if (rc == SZG_OK) {
@@ -509,61 +472,63 @@ void first_eligible_rows(const szg_index *ix, const uint64_t *allow, int k, std:
     }
 }
 
-// Stage the sentinel rows of the batch that fall into this shard and enqueue their float64
-// distances on the ctx stream (lists: one vector of index-level rows per staged query).
+size_t rows_in_shard(const Shard *sh, const std::vector<uint64_t> &rows, uint64_t *out)
+{
+    size_t n = 0;
+    for (uint64_t r : rows) {
+        if (r < sh->first || r >= sh->first + sh->n_rows) continue;
+        if (out) out[n] = r - sh->first;
+        n++;
+    }
+    return n;
+}
+
 int launch_sentinel_rerank(szg_index *ix, Shard *sh, Ctx *c, int nq, hipStream_t stream)
 {
-    const size_t total = (size_t)c->sent_n * (size_t)nq;
+    const size_t total = (size_t)c->pass.sent_n * (size_t)nq;
     if (!total) return SZG_OK;
-    int rc = ensure_host(&c->h_sent_out, &c->h_sent_out_cap, total);
+    int rc = c->h_sent_out.ensure(total);
     if (rc) return rc;
-    rc = ensure_dev(&c->d_sent_out, &c->d_sent_out_cap, total);
+    rc = c->d_sent_out.ensure(total);
     if (rc) return rc;
     HIPCHK(szg::launch_rerank(ix->bits, ix->metric, sh->rows, ix->layout, ix->dim, c->d_q64, c->d_sent, nullptr,
-                              (uint32_t)c->sent_n, nq, c->d_sent_out, stream));
+                              (uint32_t)c->pass.sent_n, nq, c->d_sent_out, stream));
     HIPCHK(hipMemcpyAsync(c->h_sent_out, c->d_sent_out, total * sizeof(szg::RerankOut), hipMemcpyDeviceToHost, stream));
-    c->sent_deferred = false;
+    c->pass.sent = Sentinels::Own;
     return SZG_OK;
 }
 
+// Stage the sentinel rows of the batch that fall into this shard and enqueue their float64
+// distances on the ctx stream (lists: one vector of index-level rows per staged query).
 // defer: only stage the rows (the batch's tail computes their distances in its one rerank launch).
 // The sentinels always ride on the context's OWN stream: they have the whole batch's sweeps to finish in, so when
 // the batch itself runs on the scan stream (a short call) they wait for its uploads through an event and stay off
 // the critical path.
 int enqueue_sentinels(szg_index *ix, Shard *sh, Ctx *c, const std::vector<std::vector<uint64_t>> &lists, int nq, bool defer)
 {
-    c->sent_n = 0;
-    c->sent_deferred = false;
-    c->sent_own_stream = false;
     size_t most = 0;
-    for (int j = 0; j < nq; j++) {
-        size_t n = 0;
-        for (uint64_t r : lists[j]) n += (r >= sh->first && r < sh->first + sh->n_rows) ? 1 : 0;
-        most = std::max(most, n);
-    }
+    for (int j = 0; j < nq; j++) most = std::max(most, rows_in_shard(sh, lists[j], nullptr));
     if (most == 0) return SZG_OK;
     SiteScope t_(9);
     HIPCHK(hipSetDevice(sh->device));
     const size_t total = most * (size_t)nq;
-    int rc = ensure_host(&c->h_sent, &c->h_sent_cap, total);
+    int rc = c->h_sent.ensure(total);
     if (rc) return rc;
-    rc = ensure_dev(&c->d_sent, &c->d_sent_cap, total);
+    rc = c->d_sent.ensure(total);
     if (rc) return rc;
     for (int j = 0; j < nq; j++) {
-        size_t n = 0;
-        for (uint64_t r : lists[j])
-            if (r >= sh->first && r < sh->first + sh->n_rows) c->h_sent[(size_t)j * most + n++] = r - sh->first;
-        for (; n < most; n++) c->h_sent[(size_t)j * most + n] = szg::kInvalidCand;
+        uint64_t *o = c->h_sent + (size_t)j * most;
+        std::fill(o + rows_in_shard(sh, lists[j], o), o + most, szg::kInvalidCand);
     }
-    hipStream_t st = c->work;
-    if (!defer && c->work != c->stream) {
+    hipStream_t st = c->pass.work;
+    if (!defer && c->pass.work != c->stream) {
         st = c->stream;
-        c->sent_own_stream = true;
-        HIPCHK(hipStreamWaitEvent(st, c->ev_up, 0));  // the queries are up (recorded by enqueue_queries on c->work)
+        c->pass.sent_own_stream = true;
+        HIPCHK(hipStreamWaitEvent(st, c->ev_up, 0));  // the queries are up (recorded by enqueue_queries on the work stream)
     }
     HIPCHK(hipMemcpyAsync(c->d_sent, c->h_sent, total * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-    c->sent_n = (int)most;
-    c->sent_deferred = true;
+    c->pass.sent_n = (int)most;
+    c->pass.sent = Sentinels::Staged;
     if (defer) return SZG_OK;
     return launch_sentinel_rerank(ix, sh, c, nq, st);
 }
@@ -572,6 +537,8 @@ int enqueue_sentinels(szg_index *ix, Shard *sh, Ctx *c, const std::vector<std::v
 
 bool Batch::acquire(bool may_block)
 {
+    const bool on_scan_stream = single && ix->serialize_scans;
+    if (!on_scan_stream) early_n = 0;  // (the early part's tail needs a second stream to run on)
     for (size_t s = 0; s < ctx.size(); s++) {
         Shard *sh = ix->shards[s];
         if (sh->n_rows == 0) continue;
@@ -584,9 +551,9 @@ bool Batch::acquire(bool may_block)
         // onto the shard's scan stream in order.  On the context's own stream every hand-over to and from the scan
         // stream is a cross-queue event wait, and those cost 20-100 us each on this platform (rocprofv3 timeline of
         // 20-query calls on a 125 K-row shard: the sweeps of a call's batches sat 24-105 us apart).
-        if (single && ix->serialize_scans) {
-            c->work = sh->scan_stream;
-            c->early_n = early_n;
+        if (on_scan_stream) {
+            c->pass.work = sh->scan_stream;
+            c->pass.early_n = early_n;
         }
         ctx[s] = c;
     }
@@ -605,9 +572,8 @@ void Batch::drain()
     for (size_t s = 0; s < ctx.size(); s++) {
         if (!ctx[s]) continue;
         (void)hipSetDevice(ix->shards[s]->device);
-        (void)hipStreamSynchronize(ctx[s]->work);
+        (void)hipStreamSynchronize(ctx[s]->pass.work);
         (void)hipStreamSynchronize(ctx[s]->stream);
-        ctx[s]->mq_fused_used = false;
     }
     release();
 }
@@ -670,13 +636,10 @@ int stage_query_forms(szg_index *ix, Batch &b, const double *q, bool int_planes,
     Ctx *c0 = nullptr;
     for (Ctx *c : b.ctx) {
         if (!c) continue;
-        if (int_planes && !c->h_mqQ) {
-            c->h_mqQ = (int32_t *)malloc(sizeof(int32_t) * (size_t)kMaxBatch * ix->dim);
-            if (!c->h_mqQ) return fail(SZG_E_NOMEM, "host scratch");
-        }
+        if (int_planes) c->h_mqQ.resize((size_t)kMaxBatch * ix->dim);  // (grows once per context; bad_alloc: SZG_CATCH)
         if (c0) {
             if (single_form) memcpy(c->h_qsw, c0->h_qsw, ix->qsw_bytes * (size_t)b.nq);
-            if (int_planes) memcpy(c->h_mqQ, c0->h_mqQ, sizeof(int32_t) * (size_t)b.nq * ix->dim);
+            if (int_planes) memcpy(c->h_mqQ.data(), c0->h_mqQ.data(), sizeof(int32_t) * (size_t)b.nq * ix->dim);
             std::copy(c0->meta, c0->meta + b.nq, c->meta);
             continue;
         }
@@ -685,7 +648,7 @@ int stage_query_forms(szg_index *ix, Batch &b, const double *q, bool int_planes,
             const double *qj = q + (size_t)j * ix->dim;
             if (single_form) prep_query(ix, qj, c->h_qsw + (size_t)j * ix->qsw_bytes, &c->meta[j]);
             else prep_query_meta(ix, qj, &c->meta[j]);
-            if (int_planes) prep_mq_int(ix, qj, &c->meta[j], c->h_mqQ + (size_t)j * ix->dim);
+            if (int_planes) prep_mq_int(ix, qj, &c->meta[j], c->h_mqQ.data() + (size_t)j * ix->dim);
             adjust(j, c->meta[j]);
         }
     }
@@ -707,9 +670,28 @@ int stage_single_form(szg_index *ix, Batch &b, const double *q, int j, QMeta *me
         }
         c->meta[j] = *meta;
         HIPCHK(hipSetDevice(ix->shards[s]->device));
-        HIPCHK(hipMemcpyAsync(c->d_qsw + off, c->h_qsw + off, ix->qsw_bytes, hipMemcpyHostToDevice, c->work));
+        HIPCHK(hipMemcpyAsync(c->d_qsw + off, c->h_qsw + off, ix->qsw_bytes, hipMemcpyHostToDevice, c->pass.work));
     }
     return SZG_OK;
+}
+
+void emit_topk(const szg_index *ix, const std::vector<HeapItem> &res, int k, int qi, uint64_t *out_rows, double *out_dist,
+               int32_t *out_count)
+{
+    for (int i = 0; i < k; i++) {
+        const bool have = i < (int)res.size();
+        out_rows[(size_t)qi * k + i] = have ? res[i].row + ix->row_base : UINT64_MAX;
+        out_dist[(size_t)qi * k + i] = have ? res[i].priority : 0.0;
+    }
+    if (out_count) out_count[qi] = (int32_t)res.size();
+}
+
+void note_stage_times(szg_index *ix, double t_prep0, double t_enq0)
+{
+    std::lock_guard<std::mutex> lk(ix->stats_mu);
+    const double t_end = now_us();
+    ix->stats.host_prep_us += t_enq0 - t_prep0;
+    ix->stats.host_enqueue_us += t_end - t_enq0;
 }
 
 // ---- one szg_search_topk call -------------------------------------------------------------------------------------
@@ -787,8 +769,6 @@ int TopkCall::stage(TopkBatch &t)
     for (size_t s = 0; s < n_sh && rc == SZG_OK; s++) {
         Shard *sh = ix->shards[s];
         if (sh->n_rows == 0) continue;
-        t.ctx[s]->sent_n = 0;
-        t.ctx[s]->sent_deferred = false;
         rc = enqueue_queries(ix, sh, t.ctx[s], q, t.nq, mptr, t.nb == 0);
         // (before the sweeps: on the context's stream this runs while the scan stream sweeps; a shared sweep whose
         // tail is the refine launch takes the rows along in its one rerank instead)
@@ -799,14 +779,11 @@ int TopkCall::stage(TopkBatch &t)
             rc = t.nb ? enqueue_topk_mq(ix, sh, t.ctx[s], kp, t.kp_wide, t.nq, t.nb, t.any_mask)
                       : enqueue_topk(ix, sh, t.ctx[s], kp, t.nq, t.any_mask);
         if (rc == SZG_OK && replay_all && ix->timing >= 2) {
-            const hipError_t e = hipEventRecord(t.ctx[s]->ev_all1, t.ctx[s]->work);
+            const hipError_t e = hipEventRecord(t.ctx[s]->ev_all1, t.ctx[s]->pass.work);
             if (e != hipSuccess) rc = fail(SZG_E_DEVICE, "hipEventRecord", e);
         }
     }
-    std::lock_guard<std::mutex> lk(ix->stats_mu);
-    const double t_end = now_us();
-    ix->stats.host_prep_us += t_enq0 - t_prep0;
-    ix->stats.host_enqueue_us += t_end - t_enq0;
+    note_stage_times(ix, t_prep0, t_enq0);
     return rc;
 }
 
@@ -819,26 +796,25 @@ int TopkCall::wait_shards(TopkBatch &t)
         Shard *sh = ix->shards[s];
         if (sh->n_rows == 0) continue;
         hipError_t e = hipSetDevice(sh->device);
-        if (e == hipSuccess) e = hipStreamSynchronize(t.ctx[s]->work);
-        if (e == hipSuccess && (t.ctx[s]->sent_own_stream || t.ctx[s]->early_n > 0)) e = hipStreamSynchronize(t.ctx[s]->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(t.ctx[s]->pass.work);
+        if (e == hipSuccess && (t.ctx[s]->pass.sent_own_stream || t.early_n > 0)) e = hipStreamSynchronize(t.ctx[s]->stream);
         if (e != hipSuccess) rc = fail(SZG_E_DEVICE, "hipStreamSynchronize", e);
         if (rc == SZG_OK) rc = finish_timing(ix, t.ctx[s]);
         Ctx *c = t.ctx[s];
-        if (rc != SZG_OK || !c->mq_fused_used) continue;
+        if (rc != SZG_OK || !c->pass.cand_cap) continue;  // (not the fused selection: nothing to overflow)
         bool overflow = false;
-        for (int j = 0; j < t.nq; j++) overflow |= c->h_cand_count[j * szg::kCandCountStride] > c->mq_cand_cap;
-        c->mq_fused_used = false;
+        for (int j = 0; j < t.nq; j++) overflow |= c->h_cand_count[j * szg::kCandCountStride] > c->pass.cand_cap;
         if (!overflow) continue;
         {
             std::lock_guard<std::mutex> lk(ix->stats_mu);
-            ix->stats.mq_launches -= (uint64_t)((t.nq + 16 * c->mq_nb - 1) / (16 * c->mq_nb));  // counted again by the rerun
+            ix->stats.mq_launches -= (uint64_t)((t.nq + 16 * c->pass.nb - 1) / (16 * c->pass.nb));  // counted again by the rerun
             ix->stats.mq_queries -= (uint64_t)t.nq;
-            ix->stats.mq_bf16_sweeps -= (c->mq_stage2 || c->mq_bf16_used) ? 1 : 0;
+            ix->stats.mq_bf16_sweeps -= from_bf16_sweep(c->pass.keys) ? 1 : 0;
             ix->stats.mq_fallbacks += 1;
         }
-        rc = enqueue_topk_mq(ix, sh, c, kp, t.kp_wide, t.nq, c->mq_nb, c->mq_has_allow, true);
+        rc = enqueue_topk_mq(ix, sh, c, kp, t.kp_wide, t.nq, c->pass.nb, c->pass.has_allow, true);
         if (rc == SZG_OK) {
-            e = hipStreamSynchronize(c->work);
+            e = hipStreamSynchronize(c->pass.work);
             if (e != hipSuccess) rc = fail(SZG_E_DEVICE, "hipStreamSynchronize", e);
         }
         if (rc == SZG_OK) rc = finish_timing(ix, c);
@@ -859,9 +835,8 @@ void TopkCall::gather(TopkBatch &t, std::vector<std::vector<Cand>> *all, std::ve
             gather_topk(ix, sh, t.ctx[s], t.meta[j], j, &(*all)[j], &lb);
             (*thr_min)[j] = std::min((*thr_min)[j], lb);
             const Ctx *c = t.ctx[s];
-            for (int i = 0; i < c->sent_n; i++) {
-                const szg::RerankOut &r = c->sent_in_out ? c->h_out[(size_t)j * c->out_stride + c->kp_used + i]
-                                                         : c->h_sent_out[(size_t)j * c->sent_n + i];
+            for (int i = 0; i < c->pass.sent_n; i++) {
+                const szg::RerankOut &r = c->sentinel(j, i);
                 if (r.row != 0xFFFFFFFFu && std::isnan(r.dist)) (*nan_first)[j] = 1;
             }
         }
@@ -981,23 +956,13 @@ int TopkCall::finish(TopkBatch &t)
     std::vector<uint8_t> nan_first(t.nq, 0);  // a NaN distance among the query's first k eligible rows
     std::vector<uint8_t> done(t.nq, 0);
     std::vector<HeapItem> res;
-    auto emit = [&](int j) {
-        const int qi = t.first + j;
-        for (int i = 0; i < k; i++) {
-            const bool have = i < (int)res.size();
-            out_rows[(size_t)qi * k + i] = have ? res[i].row + ix->row_base : UINT64_MAX;
-            out_dist[(size_t)qi * k + i] = have ? res[i].priority : 0.0;
-        }
-        if (out_count) out_count[qi] = (int32_t)res.size();
-    };
+    auto emit = [&](int j) { emit_topk(ix, res, k, t.first + j, out_rows, out_dist, out_count); };
     int rc = SZG_OK;
-    // A short call's early part (Ctx::early_n): those queries' lists and the sentinel rows' distances are complete once
+    // A short call's early part (Batch::early_n): those queries' lists and the sentinel rows' distances are complete once
     // the contexts' own streams are; they are assembled here while the scan streams run the call's last sweeps.  A
     // query that needs a device pass of its own (escalation, exact replay) waits for the second phase.
-    int early = 0;
-    for (size_t s = 0; s < n_sh; s++)
-        if (t.ctx[s] && t.ctx[s]->early_n > 0) early = t.ctx[s]->early_n;
-    if (early > 0 && early < t.nq && !replay_all) {
+    const int early = replay_all ? 0 : t.early_n;
+    if (early > 0) {
         for (size_t s = 0; s < n_sh && rc == SZG_OK; s++) {
             if (!t.ctx[s]) continue;
             hipError_t e = hipSetDevice(ix->shards[s]->device);
@@ -1015,8 +980,6 @@ int TopkCall::finish(TopkBatch &t)
             }
         }
         t_early = now_us() - te0;
-    } else {
-        early = 0;
     }
     if (rc == SZG_OK) rc = wait_shards(t);
     else (void)wait_shards(t);
