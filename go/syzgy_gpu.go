@@ -53,12 +53,37 @@ type gpuMirror struct {
 	orderStale bool
 	version uint64 // bumped by add / remove: filter verdicts are cached per (key, version)
 	masks   map[string]cachedMask
+	retired []*C.szg_mask // evicted while searches may still hold them: destroyed by the next mutator / close
 }
 
-// cachedMask is one filter's verdicts, one bit per row, valid for one collection version.
+// cachedMask is one filter's verdicts, one bit per row, valid for one collection version: the host words and the
+// same bits as a mask that lives on the card (szg_mask_create), which the searches take by handle -- nothing is
+// staged or uploaded again.  The library wants a mask destroyed only while no search uses it: that holds inside the
+// mutators (c.mutex.Lock), a reload (m.mu.Lock) and close, so eviction from the full cache only retires a mask.
 type cachedMask struct {
 	version uint64
 	bits    []C.uint64_t
+	mask    *C.szg_mask
+}
+
+// bump moves the collection version; every cached mask is stale from here on and is destroyed now.  Called with
+// exclusive access (c.mutex.Lock or m.mu.Lock): no search is in flight.
+func (m *gpuMirror) bump() {
+	m.version++
+	m.dropMasks()
+}
+
+func (m *gpuMirror) dropMasks() {
+	maskCacheMu.Lock()
+	for _, e := range m.masks {
+		C.szg_mask_destroy(e.mask) // (NULL is fine)
+	}
+	for _, mk := range m.retired {
+		C.szg_mask_destroy(mk)
+	}
+	m.masks = map[string]cachedMask{}
+	m.retired = nil
+	maskCacheMu.Unlock()
 }
 
 // newGPUMirror pages every record's stream 1 (the packed vector, exactly the
@@ -113,7 +138,7 @@ func (m *gpuMirror) reload(c *Collection) error {
 	m.ids = m.ids[:0]
 	m.rowOf = map[uint64]uint64{}
 	m.lastID = ""
-	m.version++ // rows are renumbered: cached filter masks no longer apply
+	m.bump() // rows are renumbered: cached filter masks no longer apply
 	for _, rid := range recordIDs {
 		id, err := strconv.ParseUint(rid, 10, 64)
 		if err != nil {
@@ -144,7 +169,7 @@ func (m *gpuMirror) reload(c *Collection) error {
 // is in flight.  A new row is always appended in place (one small H2D copy); see orderStale for
 // what the reference's deterministic visit order asks for on top of that.
 func (m *gpuMirror) add(id uint64, encoded []byte) {
-	m.version++
+	m.bump()
 	p := (*C.uint8_t)(unsafe.Pointer(&encoded[0]))
 	if row, ok := m.rowOf[id]; ok {
 		if C.szg_index_overwrite(m.h, C.uint64_t(row), p) != C.SZG_OK {
@@ -184,7 +209,7 @@ func (m *gpuMirror) addBulk(ids []uint64, vectors []float64, dim int) bool {
 			return false
 		}
 	}
-	m.version++
+	m.bump()
 	if C.szg_index_append_f64(m.h, (*C.double)(unsafe.Pointer(&vectors[0])), C.uint64_t(len(ids))) != C.SZG_OK {
 		m.dirty = true
 		return false
@@ -206,7 +231,7 @@ func (m *gpuMirror) addBulk(ids []uint64, vectors []float64, dim int) bool {
 
 // remove mirrors removeDocument (collection.go:511-521); called under c.mutex.Lock.
 func (m *gpuMirror) remove(id uint64) {
-	m.version++
+	m.bump()
 	if row, ok := m.rowOf[id]; ok {
 		if C.szg_index_tombstone(m.h, C.uint64_t(row)) != C.SZG_OK {
 			m.dirty = true
@@ -217,10 +242,11 @@ func (m *gpuMirror) remove(id uint64) {
 
 // touch mirrors UpdateDocument (collection.go:490-509): the vectors do not change, but filters
 // see metadata, so cached filter masks no longer apply.  Called under c.mutex.Lock.
-func (m *gpuMirror) touch() { m.version++ }
+func (m *gpuMirror) touch() { m.bump() }
 
 func (m *gpuMirror) close() {
 	if m.h != nil {
+		m.dropMasks() // masks are destroyed before their handle
 		C.szg_index_destroy(m.h)
 		m.h = nil
 	}
@@ -261,12 +287,46 @@ func (m *gpuMirror) allowBitsKeyed(c *Collection, filter FilterFn, key string) [
 	maskCacheMu.Unlock()
 	bits := m.allowBits(c, filter)
 	maskCacheMu.Lock()
-	if len(m.masks) > 32 {
-		m.masks = map[string]cachedMask{}
-	}
-	m.masks[key] = cachedMask{version: m.version, bits: bits}
+	m.storeMask(key, cachedMask{version: m.version, bits: bits})
 	maskCacheMu.Unlock()
 	return bits
+}
+
+// storeMask puts an entry into the cache (maskCacheMu held); a full cache is emptied, its device masks retired.
+func (m *gpuMirror) storeMask(key string, e cachedMask) {
+	if old, ok := m.masks[key]; ok && old.mask != nil && old.mask != e.mask {
+		m.retired = append(m.retired, old.mask)
+	}
+	if len(m.masks) > 32 {
+		for _, old := range m.masks {
+			if old.mask != nil {
+				m.retired = append(m.retired, old.mask)
+			}
+		}
+		m.masks = map[string]cachedMask{}
+	}
+	m.masks[key] = e
+}
+
+// maskKeyed is the filter's verdicts as a device-resident mask, created once per (key, version).  nil: the library
+// could not create it (the caller falls back to the words).  Called with m.mu read-locked.
+func (m *gpuMirror) maskKeyed(c *Collection, filter FilterFn, key string) *C.szg_mask {
+	bits := m.allowBitsKeyed(c, filter, key)
+	maskCacheMu.Lock()
+	defer maskCacheMu.Unlock()
+	hit, ok := m.masks[key]
+	if ok && hit.version == m.version && hit.mask != nil {
+		return hit.mask
+	}
+	if len(bits) == 0 {
+		return nil
+	}
+	var mk *C.szg_mask
+	if C.szg_mask_create(m.h, &bits[0], &mk) != C.SZG_OK {
+		return nil
+	}
+	m.storeMask(key, cachedMask{version: m.version, bits: bits, mask: mk})
+	return mk
 }
 
 // searchExact replaces the hot loop of Collection.Search (collection.go:672-684
@@ -365,7 +425,11 @@ func (m *gpuMirror) searchRows(c *Collection, args SearchArgs, filterKey string)
 	}
 	var allow *C.uint64_t
 	var keep []C.uint64_t
-	if args.Filter != nil {
+	var mask *C.szg_mask // a keyed filter: its resident mask, searched by handle
+	if args.Filter != nil && filterKey != "" {
+		mask = m.maskKeyed(c, args.Filter, filterKey)
+	}
+	if args.Filter != nil && mask == nil {
 		keep = m.allowBitsKeyed(c, args.Filter, filterKey)
 		allow = &keep[0]
 	}
@@ -376,8 +440,17 @@ func (m *gpuMirror) searchRows(c *Collection, args SearchArgs, filterKey string)
 			rows = make([]C.uint64_t, capacity)
 			dist = make([]C.double, capacity)
 			var total C.uint64_t
-			rc := C.szg_search_radius(m.h, q, C.double(args.Radius), allow, &rows[0], &dist[0],
-				C.uint64_t(capacity), &total)
+			var rc C.int
+			if mask != nil {
+				radius := C.double(args.Radius)
+				var off [2]C.uint64_t
+				rc = C.szg_search_radius_masked(m.h, q, 1, &radius, &mask, 1, &rows[0], &dist[0],
+					C.uint64_t(capacity), &off[0])
+				total = off[1]
+			} else {
+				rc = C.szg_search_radius(m.h, q, C.double(args.Radius), allow, &rows[0], &dist[0],
+					C.uint64_t(capacity), &total)
+			}
 			if rc == C.SZG_E_TRUNCATED {
 				capacity = int(total)
 				continue
@@ -391,7 +464,12 @@ func (m *gpuMirror) searchRows(c *Collection, args SearchArgs, filterKey string)
 	rows = make([]C.uint64_t, args.K)
 	dist = make([]C.double, args.K)
 	var count C.int32_t
-	rc := C.szg_search_topk(m.h, q, 1, C.int(args.K), allow, &rows[0], &dist[0], &count)
+	var rc C.int
+	if mask != nil { // (one query: coalesced with the other goroutines' like szg_search_topk)
+		rc = C.szg_search_topk_masked(m.h, q, 1, C.int(args.K), &mask, 1, &rows[0], &dist[0], &count)
+	} else {
+		rc = C.szg_search_topk(m.h, q, 1, C.int(args.K), allow, &rows[0], &dist[0], &count)
+	}
 	_ = keep
 	if rc != C.SZG_OK {
 		return nil, nil, false
@@ -447,15 +525,38 @@ func (m *gpuMirror) searchExactBatch(c *Collection, args []SearchArgs, filterKey
 	words := (len(m.ids) + 63) / 64
 	var masks []C.uint64_t
 	anyFilter := false
-	for _, a := range args {
+	allKeyed := true // every filter of the batch has a key: the batch goes by handles
+	for i, a := range args {
 		anyFilter = anyFilter || a.Filter != nil
+		if a.Filter != nil && (i >= len(filterKeys) || filterKeys[i] == "") {
+			allKeyed = false
+		}
 	}
-	if anyFilter {
+	// one handle per query (nil = unfiltered); queries that share a key share the handle, and a batch that holds a
+	// single one passes just that: its sweeps read the resident mask in place
+	var handles []*C.szg_mask
+	if anyFilter && allKeyed {
+		handles = make([]*C.szg_mask, nq)
+		same := true
+		for i, a := range args {
+			if a.Filter != nil {
+				if handles[i] = m.maskKeyed(c, a.Filter, filterKeys[i]); handles[i] == nil {
+					handles = nil
+					break
+				}
+			}
+			same = same && handles[i] == handles[0]
+		}
+		if handles != nil && same {
+			handles = handles[:1]
+		}
+	}
+	if anyFilter && handles == nil {
 		masks = make([]C.uint64_t, nq*words)
 	}
 	for i, a := range args {
 		copy(q[i*dim:(i+1)*dim], a.Vector)
-		if !anyFilter {
+		if !anyFilter || handles != nil {
 			continue
 		}
 		if a.Filter == nil {
@@ -471,7 +572,7 @@ func (m *gpuMirror) searchExactBatch(c *Collection, args []SearchArgs, filterKey
 		copy(masks[i*words:(i+1)*words], m.allowBitsKeyed(c, a.Filter, key))
 	}
 	var allow *C.uint64_t
-	if anyFilter {
+	if anyFilter && handles == nil {
 		allow = &masks[0]
 	}
 	qp := (*C.double)(unsafe.Pointer(&q[0]))
@@ -487,8 +588,14 @@ func (m *gpuMirror) searchExactBatch(c *Collection, args []SearchArgs, filterKey
 		for {
 			rows = make([]C.uint64_t, capacity)
 			dist = make([]C.double, capacity)
-			rc := C.szg_search_radius_batch(m.h, qp, C.int(nq), &radii[0], allow, &rows[0], &dist[0],
-				C.uint64_t(capacity), &off[0])
+			var rc C.int
+			if handles != nil {
+				rc = C.szg_search_radius_masked(m.h, qp, C.int(nq), &radii[0], &handles[0], C.int(len(handles)),
+					&rows[0], &dist[0], C.uint64_t(capacity), &off[0])
+			} else {
+				rc = C.szg_search_radius_batch(m.h, qp, C.int(nq), &radii[0], allow, &rows[0], &dist[0],
+					C.uint64_t(capacity), &off[0])
+			}
 			if rc == C.SZG_E_TRUNCATED {
 				capacity = int(off[nq])
 				continue
@@ -509,7 +616,14 @@ func (m *gpuMirror) searchExactBatch(c *Collection, args []SearchArgs, filterKey
 	rows := make([]C.uint64_t, nq*k)
 	dist := make([]C.double, nq*k)
 	count := make([]C.int32_t, nq)
-	if C.szg_search_topk(m.h, qp, C.int(nq), C.int(k), allow, &rows[0], &dist[0], &count[0]) != C.SZG_OK {
+	var rc C.int
+	if handles != nil {
+		rc = C.szg_search_topk_masked(m.h, qp, C.int(nq), C.int(k), &handles[0], C.int(len(handles)), &rows[0], &dist[0],
+			&count[0])
+	} else {
+		rc = C.szg_search_topk(m.h, qp, C.int(nq), C.int(k), allow, &rows[0], &dist[0], &count[0])
+	}
+	if rc != C.SZG_OK {
 		return nil, false
 	}
 	for i := 0; i < nq; i++ {

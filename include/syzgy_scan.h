@@ -139,6 +139,64 @@ int szg_search_radius_batch(szg_index *ix, const double *queries, int n_queries,
                             const uint64_t *allow_bits, uint64_t *out_rows, double *out_dist, uint64_t capacity,
                             uint64_t *out_offsets);
 
+/* ---- device-resident filter masks (added under ABI 4, additive) -------------
+ *
+ * args.Filter's verdicts (collection.go:592-594) as an object on the card: the host creates a mask once per
+ * (filter, collection version) -- from words, from a row list, or composed on the device from other masks with the
+ * operators of the reference's filter language -- and searches take the handle instead of uploading
+ * n_queries x ceil(rows/64) words with every call.
+ *
+ * Same answers as allow_bits: a masked search returns what szg_search_topk / szg_search_radius_batch return when
+ *   given szg_mask_read's words -- ids, float64 distances and order -- on every path: one sweep per query (dense and
+ *   selective form), shared sweeps, radius batches, the sketch pre-pass, escalation, the full replay under tie_mode 0
+ *   and handles whose shards share a process.
+ * Tail bits: bits at positions >= rows are stored as 0, after SZG_MASK_NOT as well; szg_mask_count never counts them.
+ * Mutations: szg_index_tombstone and the overwrites leave a mask valid (tombstones are applied through the live
+ *   bits, as ever).  szg_index_load, szg_index_synth and the appends -- which change the row count -- make every
+ *   older mask of the handle STALE: a search or combine with a stale mask returns SZG_E_INVALID ("stale mask" in
+ *   szg_last_error) and never reads past the mask; so does a mask of another handle.  Stale masks can still be read,
+ *   counted and destroyed.
+ * Lifetime and threads: masks are destroyed before their handle.  Any number of threads may search with one mask
+ *   concurrently; create / combine / destroy may run beside searches that do not use that mask.
+ * Coalescing: szg_search_topk_masked with ONE query goes through the combiner like szg_search_topk; callers that all
+ *   hold the same handle form a batch that reads the resident mask in place.  A coalesced batch that mixes raw-word
+ *   callers and handle callers is staged through the host path, with the handles' host copy of the words.
+ * Out of scope: szg_search_*_sharded keep allow_bits only.
+ */
+typedef struct szg_mask szg_mask;
+#define SZG_MASK_AND 0      /* a & b */
+#define SZG_MASK_OR 1       /* a | b */
+#define SZG_MASK_ANDNOT 2   /* a & ~b */
+#define SZG_MASK_NOT 3      /* ~a, b must be NULL */
+
+/* bit r = row r may be visited; ceil(rows/64) words, copied. */
+int szg_mask_create(szg_index *ix, const uint64_t *allow_bits, szg_mask **out);
+/* exactly the listed rows (numbered as searches return them: local + row base); duplicates allowed;
+   a row >= rows -> SZG_E_RANGE; n_rows == 0 -> the empty mask */
+int szg_mask_create_rows(szg_index *ix, const uint64_t *rows, uint64_t n_rows, szg_mask **out);
+/* composed on the device; a and b belong to the same handle and the same row count */
+int szg_mask_combine(int op, const szg_mask *a, const szg_mask *b, szg_mask **out);
+uint64_t szg_mask_count(const szg_mask *m);            /* rows allowed, exact */
+int szg_mask_read(const szg_mask *m, uint64_t *out_bits); /* ceil(rows/64) words */
+void szg_mask_destroy(szg_mask *m);                    /* NULL is fine */
+
+/* n_masks == 1: masks[0] filters every query; n_masks == n_queries: one per query, NULL entry = unfiltered;
+   masks == NULL / n_masks == 0: unfiltered.  Everything else as szg_search_topk / szg_search_radius_batch. */
+int szg_search_topk_masked(szg_index *ix, const double *queries, int n_queries, int k,
+                           const szg_mask *const *masks, int n_masks,
+                           uint64_t *out_rows, double *out_dist, int32_t *out_count);
+int szg_search_radius_masked(szg_index *ix, const double *queries, int n_queries, const double *radii,
+                             const szg_mask *const *masks, int n_masks,
+                             uint64_t *out_rows, double *out_dist, uint64_t capacity, uint64_t *out_offsets);
+
+typedef struct szg_mask_stats {
+    uint64_t live_masks, device_bytes;  /* masks alive on this handle, their device memory */
+    uint64_t h2d_bytes;       /* filter words searches uploaded from host memory (the allow_bits path) */
+    uint64_t d2d_bytes;       /* filter words copied card-to-card into a batch's per-query slots */
+    uint64_t shared_batches;  /* batches whose sweeps read ONE resident mask in place (no copy at all) */
+} szg_mask_stats;
+int szg_index_mask_stats(szg_index *ix, szg_mask_stats *out);   /* szg_reset_stats clears the three counters */
+
 /*
  * The reference's float64 distance (c.distance, collection.go:596, :812-832) from
  * one query to each listed row, bit-identical to the reference: the gather-by-row

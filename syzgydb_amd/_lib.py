@@ -35,7 +35,11 @@ EXPORTS = [
     "szg_comm_reserve", "szg_index_attach_comm", "szg_search_topk_sharded", "szg_search_radius_sharded",
     "szg_comm_merge_topk", "szg_comm_merge_radius", "szg_comm_get_stats", "szg_comm_reset_stats",
     "szg_comm_last_radius", "szg_comm_chain_topk", "szg_comm_debug_inject",
+    # device-resident filter masks (added under ABI 4)
+    "szg_mask_create", "szg_mask_create_rows", "szg_mask_combine", "szg_mask_count", "szg_mask_read",
+    "szg_mask_destroy", "szg_search_topk_masked", "szg_search_radius_masked", "szg_index_mask_stats",
 ]
+SZG_MASK_AND, SZG_MASK_OR, SZG_MASK_ANDNOT, SZG_MASK_NOT = 0, 1, 2, 3
 SZG_COMM_ID_BYTES = 128
 # int (*szg_allgather_fn)(void *user, const void *send, void *recv, uint64_t bytes_per_rank)
 ALLGATHER_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64)
@@ -78,6 +82,11 @@ class SzgStats(ctypes.Structure):
         ("sketch_fallbacks", ctypes.c_uint64),
         ("mq_bf16_sweeps", ctypes.c_uint64),
     ]
+
+
+class SzgMaskStats(ctypes.Structure):
+    _fields_ = [("live_masks", ctypes.c_uint64), ("device_bytes", ctypes.c_uint64), ("h2d_bytes", ctypes.c_uint64),
+                ("d2d_bytes", ctypes.c_uint64), ("shared_batches", ctypes.c_uint64)]
 
 
 class SzgError(RuntimeError):
@@ -169,6 +178,28 @@ def load():
     L.szg_pair_distances.argtypes = [vp, u64p, u64p, ctypes.c_uint64, f64p]
     L.szg_search_radius_batch.restype = ctypes.c_int
     L.szg_search_radius_batch.argtypes = [vp, f64p, ctypes.c_int, f64p, u64p, u64p, f64p, ctypes.c_uint64, u64p]
+    # (an older build selected through SZG_LIB_PATH for an A/B run has no masks: masks= then fails at the call)
+    if hasattr(L, "szg_mask_create"):
+        L.szg_mask_create.restype = ctypes.c_int
+        L.szg_mask_create.argtypes = [vp, u64p, ctypes.POINTER(vp)]
+        L.szg_mask_create_rows.restype = ctypes.c_int
+        L.szg_mask_create_rows.argtypes = [vp, u64p, ctypes.c_uint64, ctypes.POINTER(vp)]
+        L.szg_mask_combine.restype = ctypes.c_int
+        L.szg_mask_combine.argtypes = [ctypes.c_int, vp, vp, ctypes.POINTER(vp)]
+        L.szg_mask_count.restype = ctypes.c_uint64
+        L.szg_mask_count.argtypes = [vp]
+        L.szg_mask_read.restype = ctypes.c_int
+        L.szg_mask_read.argtypes = [vp, u64p]
+        L.szg_mask_destroy.restype = None
+        L.szg_mask_destroy.argtypes = [vp]
+        L.szg_search_topk_masked.restype = ctypes.c_int
+        L.szg_search_topk_masked.argtypes = [vp, f64p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(vp), ctypes.c_int, u64p,
+                                             f64p, i32p]
+        L.szg_search_radius_masked.restype = ctypes.c_int
+        L.szg_search_radius_masked.argtypes = [vp, f64p, ctypes.c_int, f64p, ctypes.POINTER(vp), ctypes.c_int, u64p, f64p,
+                                               ctypes.c_uint64, u64p]
+        L.szg_index_mask_stats.restype = ctypes.c_int
+        L.szg_index_mask_stats.argtypes = [vp, ctypes.POINTER(SzgMaskStats)]
     L.szg_comm_unique_id.restype = ctypes.c_int
     L.szg_comm_unique_id.argtypes = [u8p]
     L.szg_comm_create.restype = ctypes.c_int

@@ -87,9 +87,10 @@ class Collection:
         self._meta = []      # row -> metadata bytes
         self._closed = False
         # filter -> allow-bitmask cache: a filter's verdicts only change when the
-        # collection does, so they are kept per (filter key, collection version)
+        # collection does, so they are kept per (filter key, collection version) -- the host words and, beside them,
+        # the ScanMask that holds the same bits on the card: searches pass the handle, nothing is uploaded again
         self._version = 0
-        self._mask_cache = {}
+        self._mask_cache = {}   # (key, version) -> [words, filter, ScanMask or None]
         # Row order only matters where the reference's own answer depends on its visit order: ties at the k
         # boundary, equal distances in a radius result (collection.go:608).  Production iterates a Go map (random
         # order per run, spanfile.go:525): every order is a reference order, rows are simply appended
@@ -243,7 +244,8 @@ class Collection:
 
     def Close(self):
         if not self._closed:
-            self._index.close()
+            self._mask_cache.clear()
+            self._index.close()   # (closes the masks it still holds first)
             self._closed = True
 
     # -- Search ---------------------------------------------------------------
@@ -253,19 +255,36 @@ class Collection:
         without it the filter object itself is the key."""
         if flt is None:
             return None
+        return self._mask_entry(flt, key)[0]
+
+    def _mask_entry(self, flt, key):
         ck = (key if key is not None else id(flt), self._version)
         hit = self._mask_cache.get(ck)
         if hit is not None and (key is not None or hit[1] is flt):
-            return hit[0]
+            return hit
+        # the version has moved: entries of older versions can never be hit again, their device masks go now
+        for old in [k for k in self._mask_cache if k[1] != self._version]:
+            m = self._mask_cache.pop(old)[2]
+            if m is not None:
+                m.close()
         mask = np.zeros(len(self._id_of), dtype=bool)
         for row, id_ in enumerate(self._id_of):
             if id_ is not None:
                 mask[row] = bool(flt(id_, self._meta[row]))
         bits = pack_allow_bits(mask)
         if len(self._mask_cache) > 16:
-            self._mask_cache.clear()
-        self._mask_cache[ck] = (bits, flt)
-        return bits
+            self._mask_cache.clear()   # (a mask a batch in the making still refers to lives on until that drops it)
+        hit = self._mask_cache[ck] = [bits, flt, None]
+        return hit
+
+    def _allow_handle(self, flt, key=None):
+        """The filter's verdicts as a ScanMask on the card, made once per (filter key, collection version)."""
+        if flt is None:
+            return None
+        hit = self._mask_entry(flt, key)
+        if hit[2] is None:
+            hit[2] = self._index.mask(hit[0])
+        return hit[2]
 
     def Search(self, args: SearchArgs) -> SearchResults:
         """collection.go:569-711."""
@@ -292,12 +311,12 @@ class Collection:
                 raise ValueError("query length %d != dimension %d" % (q.size, self.DimensionCount))
 
             def scan():
-                allow = self._allow_mask(args.Filter, getattr(args, "FilterKey", None)) if n_records else None
                 if n_records == 0:
                     return [], []
+                mask = self._allow_handle(args.Filter, getattr(args, "FilterKey", None))
                 if args.Radius > 0:  # K is ignored (collection.go:598-605)
-                    return self._index.search_radius(q, args.Radius, allow=allow)
-                r, d, c = self._index.search_topk(q, args.K, allow=allow)
+                    return self._index.search_radius(q, args.Radius, masks=mask)
+                r, d, c = self._index.search_topk(q, args.K, masks=mask)
                 return r[0, : c[0]], d[0, : c[0]]
             if self._order_stale and self._index.options.get("tie_mode", 0) != 0:
                 # tie_mode 1 keeps the fast answer for ties and counts no replay: the test below would never see one,
@@ -343,18 +362,18 @@ class Collection:
         Q = np.stack([np.asarray(a.Vector, dtype=np.float64).reshape(-1) for a in args_list])
         if Q.shape[1] != self.DimensionCount:
             raise ValueError("query length %d != dimension %d" % (Q.shape[1], self.DimensionCount))
-        allow = None
+        masks = None
         if any(a.Filter is not None for a in args_list):
-            words = (len(self._id_of) + 63) // 64
-            allow = np.full((len(args_list), words), np.uint64(0xFFFFFFFFFFFFFFFF), dtype=np.uint64)
-            for i, a in enumerate(args_list):
-                if a.Filter is not None:
-                    allow[i] = self._allow_mask(a.Filter, getattr(a, "FilterKey", None)).reshape(-1)
+            # one handle per query (None = unfiltered); queries that share a FilterKey share the handle, and a batch
+            # that holds a single one passes just that: its sweeps read the resident mask in place
+            masks = [self._allow_handle(a.Filter, getattr(a, "FilterKey", None)) for a in args_list]
+            if all(m is masks[0] for m in masks):
+                masks = masks[0]
         out = []
         if radius:
-            hits = self._index.search_radius_batch(Q, [a.Radius for a in args_list], allow=allow)
+            hits = self._index.search_radius_batch(Q, [a.Radius for a in args_list], masks=masks)
         else:
-            r, d, c = self._index.search_topk(Q, args_list[0].K, allow=allow)
+            r, d, c = self._index.search_topk(Q, args_list[0].K, masks=masks)
             hits = [(r[i, : c[i]], d[i, : c[i]]) for i in range(len(args_list))]
         for rows, dist in hits:
             res = [SearchResult(ID=self._id_of[int(row)], Metadata=self._meta[int(row)], Distance=float(dd))

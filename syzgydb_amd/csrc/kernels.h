@@ -307,4 +307,18 @@ hipError_t launch_f64_probe(int op, const double *a, const double *b, double *ou
 // live-bit maintenance
 hipError_t launch_fill_bits(uint64_t *bits, uint64_t n_rows, uint64_t n_words, hipStream_t stream);
 
+// ---- device-resident filter masks (kernels_mask.hip): the words of one shard per launch.  A shard's mask is n_pairs
+// 16-byte pairs of words (ceil(n_rows / 64) words rounded up to an even count); bits at positions >= n_rows are 0.
+// bit (r - first) of the zeroed `words` is set for every listed row r in [first, first + n_rows) (64-bit atomic OR)
+hipError_t launch_mask_from_rows(const uint64_t *rows, uint64_t n_listed, uint64_t first, uint64_t n_rows, uint64_t *words,
+                                 hipStream_t stream);
+// out = a op b (SZG_MASK_*; b null for NOT; out may be a), the tail cleared; *count += the bits set in out
+hipError_t launch_mask_combine(int op, const uint64_t *a, const uint64_t *b, uint64_t *out, uint64_t n_pairs, uint64_t n_rows,
+                               uint64_t *count, hipStream_t stream);
+// the per-query mask slots of a batch, n_pairs pairs each, from resident masks: src[q] null = all ones
+struct MaskGatherTable {
+    const uint64_t *src[kMqMaxQueries];
+};
+hipError_t launch_mask_gather(const MaskGatherTable &t, int n_queries, uint64_t *dst, uint64_t n_pairs, hipStream_t stream);
+
 }  // namespace szg

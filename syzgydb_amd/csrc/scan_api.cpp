@@ -185,6 +185,7 @@ struct BatchScratch {
     std::vector<uint64_t> rows;
     std::vector<int32_t> count;
     std::vector<const uint64_t *> masks;
+    std::vector<const szg_mask *> handles;
     std::vector<std::vector<HeapItem>> hits;
 };
 
@@ -196,12 +197,24 @@ void serve_batch(szg_index *ix, const std::vector<PendingSearch *> &batch, Batch
     try {
         w.q.resize((size_t)nq * ix->dim);
         w.masks.resize(nq);
-        bool any = false;
+        w.handles.resize(nq);
+        bool any = false, raw = false, resident = false;
         for (int i = 0; i < nq; i++) {
             memcpy(&w.q[(size_t)i * ix->dim], batch[i]->query, sizeof(double) * ix->dim);
             w.masks[i] = batch[i]->allow;  // each caller's own filter, if it has one
-            any |= w.masks[i] != nullptr;
+            w.handles[i] = batch[i]->handle;  // ... or its resident mask
+            raw |= w.masks[i] != nullptr;
+            resident |= w.handles[i] != nullptr;
         }
+        // callers with raw words beside callers with resident masks: everything through the host path, with the
+        // handles' host words
+        if (raw && resident) {
+            for (int i = 0; i < nq; i++)
+                if (w.handles[i]) w.masks[i] = mask_host_words(w.handles[i]);
+            resident = false;
+        }
+        any = raw || resident;
+        const szg_mask *const *hptr = resident ? w.handles.data() : nullptr;
         if (radius) {
             w.radii.resize(nq);
             for (int i = 0; i < nq; i++) w.radii[i] = batch[i]->radius;
@@ -215,13 +228,14 @@ void serve_batch(szg_index *ix, const std::vector<PendingSearch *> &batch, Batch
         const int kk = batch[0]->k;
         if (nq == 1) {
             PendingSearch *p = batch[0];
-            rc = search_topk_any(ix, p->query, 1, kk, p->allow, p->out_rows, p->out_dist, p->out_count);
+            rc = search_topk_any(ix, p->query, 1, kk, p->allow, p->out_rows, p->out_dist, p->out_count, nullptr,
+                                 p->handle ? &p->handle : nullptr);
         } else {
             w.rows.resize((size_t)nq * kk);
             w.dist.resize((size_t)nq * kk);
             w.count.resize(nq);
             rc = search_topk_any(ix, w.q.data(), nq, kk, nullptr, w.rows.data(), w.dist.data(), w.count.data(),
-                                 any ? w.masks.data() : nullptr);
+                                 any && !hptr ? w.masks.data() : nullptr, hptr);
             for (int i = 0; i < nq && rc == SZG_OK; i++) {
                 memcpy(batch[i]->out_rows, &w.rows[(size_t)i * kk], sizeof(uint64_t) * kk);
                 memcpy(batch[i]->out_dist, &w.dist[(size_t)i * kk], sizeof(double) * kk);
@@ -317,6 +331,27 @@ int szg_search_topk(szg_index *ix, const double *queries, int n_queries, int k,
     PendingSearch me;
     me.query = queries;
     me.allow = allow_bits;
+    me.k = k;
+    me.out_rows = out_rows;
+    me.out_dist = out_dist;
+    me.out_count = out_count;
+    return combine(ix, me);
+}
+
+int szg_search_topk_masked(szg_index *ix, const double *queries, int n_queries, int k, const szg_mask *const *masks,
+                           int n_masks, uint64_t *out_rows, double *out_dist, int32_t *out_count)
+{
+    const szg_mask *lone = nullptr;
+    {
+        SZG_TRY
+        const int rc = search_topk_masked_prepare(ix, queries, n_queries, k, masks, n_masks, out_rows, out_dist, out_count, &lone);
+        if (rc || !lone) return rc;
+        SZG_CATCH
+    }
+    PendingSearch me;  // a lone query: answered together with whoever else is waiting (combine)
+    me.query = queries;
+    me.allow = nullptr;
+    me.handle = lone;
     me.k = k;
     me.out_rows = out_rows;
     me.out_dist = out_dist;

@@ -399,7 +399,7 @@ uint64_t szg_index_live_rows(const szg_index *ix)
 int szg_index_load(szg_index *ix, const uint8_t *rows, uint64_t n_rows)
 {
     SZG_TRY
-    if (ix) { ix->gen++; sketch_rearm(ix); }
+    if (ix) { ix->gen++; ix->mask_epoch++; sketch_rearm(ix); }  // (masks made before are stale from here on)
     if (!ix || (!rows && n_rows)) return fail(SZG_E_INVALID, "null argument");
     std::vector<uint64_t> counts;
     split_rows(ix, n_rows, &counts);
@@ -419,7 +419,7 @@ int szg_index_load(szg_index *ix, const uint8_t *rows, uint64_t n_rows)
 int szg_index_synth(szg_index *ix, uint64_t n_rows, uint64_t seed, uint64_t first_row)
 {
     SZG_TRY
-    if (ix) { ix->gen++; sketch_rearm(ix); }
+    if (ix) { ix->gen++; ix->mask_epoch++; sketch_rearm(ix); }  // (masks made before are stale from here on)
     if (!ix) return fail(SZG_E_INVALID, "null argument");
     std::vector<uint64_t> counts;
     split_rows(ix, n_rows, &counts);
@@ -441,7 +441,7 @@ int szg_index_synth(szg_index *ix, uint64_t n_rows, uint64_t seed, uint64_t firs
 int szg_index_append(szg_index *ix, const uint8_t *rows, uint64_t n_rows)
 {
     SZG_TRY
-    if (ix) ix->gen++;
+    if (ix) { ix->gen++; ix->mask_epoch++; }  // (the row count moves: masks made before are stale)
     if (!ix || (!rows && n_rows)) return fail(SZG_E_INVALID, "null argument");
     if (n_rows == 0) return SZG_OK;
     Shard *sh = append_target(ix);
@@ -463,7 +463,7 @@ int szg_index_append(szg_index *ix, const uint8_t *rows, uint64_t n_rows)
 int szg_index_append_f64(szg_index *ix, const double *vectors, uint64_t n_rows)
 {
     SZG_TRY
-    if (ix) ix->gen++;
+    if (ix) { ix->gen++; ix->mask_epoch++; }  // (the row count moves: masks made before are stale)
     if (!ix || (!vectors && n_rows)) return fail(SZG_E_INVALID, "null argument");
     if (n_rows == 0) return SZG_OK;
     Shard *sh = append_target(ix);
@@ -645,9 +645,11 @@ int szg_reset_stats(szg_index *ix)
     if (!ix) return fail(SZG_E_INVALID, "null argument");
     std::lock_guard<std::mutex> lk(ix->stats_mu);
     ix->stats = szg_stats{};
+    ix->mask_h2d = ix->mask_d2d = ix->mask_shared = 0;  // (szg_mask_stats' counters; live masks stay counted)
     if (ix->sketch) {
         std::lock_guard<std::mutex> lk2(ix->sketch->stats_mu);
         ix->sketch->stats = szg_stats{};
+        ix->sketch->mask_h2d = ix->sketch->mask_d2d = ix->sketch->mask_shared = 0;
     }
     return SZG_OK;
 }

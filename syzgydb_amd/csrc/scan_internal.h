@@ -10,6 +10,7 @@
 //   scan_sketch.cpp   8-bit sketch pre-pass
 //   scan_radius.cpp   radius search (single, batch, coalesced)
 //   scan_comm.cpp     one-process-per-GPU exchange (RCCL all-gather + merge)
+//   scan_mask.cpp     device-resident filter masks (szg_mask) and the searches that take them
 //   scan_api.cpp      remaining C entry points (top-k with caller coalescing, distances)
 //
 // What a batch borrows per shard is a Ctx: a stream, events and scratch that persist between batches -- every buffer
@@ -255,6 +256,10 @@ struct Pass {
     uint32_t cand_cap = 0;         // > 0: the selection was the fused one, with this many entries per query's buffer
     int nb = 0;
     bool has_allow = false;
+    // the filter masks of the batch on the device (enqueue_queries): query j's words are allow_base + j * allow_stride
+    // -- the context's d_allow slots, or ONE resident mask read in place by every query (stride 0)
+    const uint64_t *allow_base = nullptr;
+    uint32_t allow_stride = 0;
     // HIP-event timing: scan launches between ev_scan0 and ev_scan1 / ev_p0 and ev_p1 (0 = that pair was not recorded)
     int timed_n = 0, timed_part_n = 0;
 };
@@ -271,6 +276,8 @@ struct Ctx {
     // overwritten by staging (not part of the per-acquire reset: 8 KB)
     QMeta meta[kMaxBatch];               // constants of the staged queries
     float mq_qsum[128] = {};             // bfloat16 sweep of 8-bit rows: the sum of each staged query's rounded image values
+    int64_t mask_count[kMaxBatch];       // rows of the shard each staged query's resident mask allows, exact (-1: the
+                                         // query's words came from the host, mask_pass_rate samples h_allow)
     size_t radius_cap = 0;         // radius batches: entries per sweep the next batch's buffers get (follows the hit counts seen)
     // pinned host staging, kMaxBatch queries
     PinnedBuf<uint8_t> h_qsw;      // swizzled queries for the scan
@@ -367,6 +374,7 @@ struct Shard {
 struct PendingSearch {
     const double *query;
     const uint64_t *allow;  // the caller's filter mask, or nullptr
+    const szg_mask *handle = nullptr;  // ... or its resident mask (szg_search_topk_masked); never both
     int k;                  // top-k search (radius == 0)
     double radius = 0;      // > 0: radius search (k ignored, collection.go:598-605)
     uint64_t *out_rows;
@@ -450,6 +458,10 @@ struct szg_index {
     static constexpr int mq_blocks_max = 6;     // query blocks of 16 per shared sweep (LDS image permitting)
     int timing = 0;           // 0 off, 1 HIP events around the scan launches, 2 + around the whole per-batch pipeline
     std::mutex stats_mu;
+    // device-resident filter masks (scan_mask.cpp)
+    std::atomic<uint64_t> mask_epoch{1};  // moves whenever the row count may (load, synth, appends): older masks are stale
+    std::atomic<uint64_t> mask_live{0}, mask_dev_bytes{0};
+    std::atomic<uint64_t> mask_h2d{0}, mask_d2d{0}, mask_shared{0};  // szg_mask_stats (with the sketch index's own)
     // coalescing of concurrent single-query searches (szg_search_topk, n_queries == 1)
     std::mutex comb_mu;
     std::deque<struct PendingSearch *> comb_waiting;
@@ -508,8 +520,10 @@ void note_overwritten(szg_index *ix, uint64_t row);
 // ---- scan_topk.cpp
 LaunchGeom scan_geometry(const szg_index *ix, const Shard *sh, int kp, bool plain_topk = false);
 size_t shard_words(const Shard *sh);
+// (handles: null, or the resident masks of the batch's queries -- then `masks` holds their host words -- and `shard_no`,
+// the shard's position in its index, which is also the position of its words in every handle)
 int enqueue_queries(szg_index *ix, Shard *sh, Ctx *c, const double *q, int nq, const uint64_t *const *masks,
-                    bool with_single_form = true);
+                    bool with_single_form = true, const szg_mask *const *handles = nullptr, size_t shard_no = 0);
 void fill_scan_args(const szg_index *ix, const Shard *sh, const Ctx *c, bool has_allow, int slot, int nq,
                     szg::ScanArgs *a);
 // (after: the stream that goes on once the sweeps are done -- default the work stream; part 1: the early part of a short
@@ -541,19 +555,21 @@ void emit_topk(const szg_index *ix, const std::vector<HeapItem> &res, int k, int
 // the end of a call's stage(): host time of the preparation [t_prep0, t_enq0) and of the enqueueing [t_enq0, now)
 void note_stage_times(szg_index *ix, double t_prep0, double t_enq0);
 int run_collect(szg_index *ix, Shard *sh, Ctx *c, int slot, float thr_key, bool has_allow, std::vector<Cand> *cands);
-// fraction of the shard's rows that staged query `slot` may visit (tombstones, and a sample of its filter mask's words)
+// fraction of the shard's rows that staged query `slot` may visit (tombstones, and its filter mask: the exact count of
+// a resident mask, a sample of the words of one that came from the host)
 double mask_pass_rate(const Shard *sh, const Ctx *c, bool has_allow, int slot);
 void first_eligible_rows(const szg_index *ix, const uint64_t *allow, int k, std::vector<uint64_t> *rows_out);
 int search_topk_impl(szg_index *ix, const double *queries, int n_queries, int k, const uint64_t *allow_bits,
                      uint64_t *out_rows, double *out_dist, int32_t *out_count,
-                     const uint64_t *const *allow_ptrs = nullptr);
+                     const uint64_t *const *allow_ptrs = nullptr, const szg_mask *const *handles = nullptr);
 // consider()'s top-k branch over every row of the handle in visit order, continuing the heap *h (rows + row_base)
 int replay_rows_into_heap(szg_index *ix, const double *query, const uint64_t *allow, int k, GoHeap *h);
 
 // ---- scan_radius.cpp
 // radius searches for a batch of queries (own radius and filter mask each): results[i] = the hits of query i, ascending
 int search_radius_impl(szg_index *ix, const double *queries, int n_queries, const double *radii,
-                       const uint64_t *const *masks, std::vector<std::vector<HeapItem>> *results);
+                       const uint64_t *const *masks, std::vector<std::vector<HeapItem>> *results,
+                       const szg_mask *const *handles = nullptr);
 
 #ifndef SZG_BF16_8BIT_DEFAULT
 #define SZG_BF16_8BIT_DEFAULT 1  // tiled 8-bit rows take the bfloat16 sweep for top-k batches (SZG_BF16_8BIT=0: the int8 sweep)
@@ -577,7 +593,20 @@ bool sketch_applies(const szg_index *ix, int k);
 void sketch_rearm(szg_index *ix);
 int search_topk_any(szg_index *ix, const double *queries, int n_queries, int k, const uint64_t *allow_bits,
                     uint64_t *out_rows, double *out_dist, int32_t *out_count,
-                    const uint64_t *const *allow_ptrs = nullptr);
+                    const uint64_t *const *allow_ptrs = nullptr, const szg_mask *const *handles = nullptr);
+
+// ---- scan_mask.cpp
+// SZG_OK, or SZG_E_INVALID when the mask belongs to another handle or was made before the row count last changed
+int mask_check(const szg_index *ix, const szg_mask *m);
+const uint64_t *mask_host_words(const szg_mask *m);                 // index-level, ceil(rows / 64) words
+const uint64_t *mask_shard_words(const szg_mask *m, size_t shard);  // device, shard-local (an even number of words)
+uint64_t mask_shard_count(const szg_mask *m, size_t shard);         // rows of the shard the mask allows, exact
+// szg_search_topk_masked up to the combiner (scan_api.cpp): the checks, and the search itself unless the call is a lone
+// query that may be coalesced -- then *lone is its mask and nothing has been searched yet
+int search_topk_masked_prepare(szg_index *ix, const double *queries, int n_queries, int k, const szg_mask *const *masks,
+                               int n_masks, uint64_t *out_rows, double *out_dist, int32_t *out_count, const szg_mask **lone);
+// words per slot of a batch's d_allow when resident masks are gathered into it (16-byte pairs)
+inline size_t mask_slot_words(const Shard *sh) { return (size_t)(((sh->n_rows + 63) / 64 + 1) & ~1ull); }
 
 // One link of the shard's scan chain: under chain_mu, launch(st) puts the sweeps onto the shard's scan stream behind the
 // batch's uploads (ev_up, recorded on the work stream by the caller), and `after` goes on once they are done.  With
@@ -630,19 +659,25 @@ constexpr int kFirstBatch = 4;  // queries of a call's first (and last) one-swee
 constexpr int kShortCall = 32;  // calls of up to this many one-sweep queries are ONE batch on the scan stream
 
 // the filter masks of a call's queries: one pointer per query (null = unfiltered), or masks back to back with one
-// bit per row of the index, or none
+// bit per row of the index, or resident masks (one handle per query, null = unfiltered), or none.  operator() gives
+// the host words in every case (a handle keeps a host copy of its words)
 struct QueryMasks {
     const uint64_t *bits;
     const uint64_t *const *ptrs;
+    const szg_mask *const *handles;
     size_t stride = 0;  // words per mask of `bits`
-    QueryMasks(const szg_index *ix, const uint64_t *bits_, const uint64_t *const *ptrs_) : bits(bits_), ptrs(ptrs_)
+    QueryMasks(const szg_index *ix, const uint64_t *bits_, const uint64_t *const *ptrs_,
+               const szg_mask *const *handles_ = nullptr)
+        : bits(bits_), ptrs(ptrs_), handles(handles_)
     {
         uint64_t total_rows = 0;
         for (const Shard *sh : ix->shards) total_rows += sh->n_rows;
         stride = (total_rows + 63) / 64;
     }
+    const szg_mask *handle(int qi) const { return handles ? handles[qi] : nullptr; }
     const uint64_t *operator()(int qi) const
     {
+        if (handles) return handles[qi] ? mask_host_words(handles[qi]) : nullptr;
         if (ptrs) return ptrs[qi];
         return bits ? bits + (size_t)qi * stride : nullptr;
     }
@@ -671,6 +706,8 @@ struct Batch {
     void drain();                  // wait for the contexts' streams, then release
     // the filter masks of the batch's queries (sets any_mask)
     std::vector<const uint64_t *> masks(const QueryMasks &mask_of);
+    // ... and their resident masks (empty when the call carries none)
+    std::vector<const szg_mask *> handles(const QueryMasks &mask_of) const;
 };
 
 // How a call splits into batches: the caller's parameters

@@ -298,8 +298,8 @@ int enqueue_topk_mq(szg_index *ix, Shard *sh, Ctx *c, int kp, int kp_wide, int n
     a.keys = c->d_keys;
     a.key_stride = p.key_stride;
     const uint64_t *live = sh->has_dead ? sh->live_bits : nullptr;
-    const uint64_t *allow = has_allow ? c->d_allow : nullptr;
-    const uint32_t words = (uint32_t)shard_words(sh);
+    const uint64_t *allow = has_allow ? c->pass.allow_base : nullptr;
+    const uint32_t words = c->pass.allow_stride;  // between the queries' masks
     auto launch_score = [&](const szg::MqArgs &x, hipStream_t s2) -> hipError_t {
         if (p.bf16) return szg::launch_mq_score_bf16(ix->bits, x, nb, sh->cu_count, s2);
         return szg::launch_mq_score_i8(ix->bits, x, nb, sh->cu_count, s2);
@@ -437,8 +437,8 @@ int enqueue_collect_mq(szg_index *ix, Shard *sh, Ctx *c, int nq, int nb, bool ha
     a.cand_count = c->d_count;
     a.cand_cap = (uint32_t)std::min<size_t>(cap, 0xFFFFFFFFu);
     a.live_bits = sh->has_dead ? sh->live_bits : nullptr;
-    a.allow_bits = has_allow ? c->d_allow : nullptr;
-    a.allow_stride = (uint32_t)shard_words(sh);
+    a.allow_bits = has_allow ? c->pass.allow_base : nullptr;
+    a.allow_stride = c->pass.allow_stride;
     // the sweep must see the image, the thresholds, the masks and the zeroed counters (on the work stream itself: in order)
     if (ix->serialize_scans && sh->scan_stream != c->pass.work) HIPCHK(hipEventRecord(c->ev_up, c->pass.work));
     rc = chain_sweeps(ix, sh, c, c->pass.work, 0, groups, bf16 ? "szg::launch_mq_score_bf16" : "szg::launch_mq_score_i8", [&](hipStream_t st) {

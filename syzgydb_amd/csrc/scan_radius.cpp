@@ -162,6 +162,7 @@ int RadiusCall::stage(RadiusBatch &t)
 {
     const double *q = queries + (size_t)t.first * ix->dim;
     const std::vector<const uint64_t *> m = t.masks(mask_of);
+    const std::vector<const szg_mask *> handles = t.handles(mask_of);
     const double t0 = now_us();
     const bool int_planes = t.nb > 0 && mq_uses_i8(ix, true);
     int rc = stage_query_forms(ix, t, q, int_planes, [&](int j, QMeta &meta) {
@@ -179,7 +180,8 @@ int RadiusCall::stage(RadiusBatch &t)
     const double t1 = now_us();
     for (size_t s = 0; s < n_sh && rc == SZG_OK; s++) {
         if (!t.ctx[s]) continue;
-        rc = enqueue_queries(ix, ix->shards[s], t.ctx[s], q, t.nq, t.any_mask ? m.data() : nullptr, t.nb == 0);
+        rc = enqueue_queries(ix, ix->shards[s], t.ctx[s], q, t.nq, t.any_mask ? m.data() : nullptr, t.nb == 0,
+                             handles.empty() ? nullptr : handles.data(), s);
         if (rc == SZG_OK) rc = enqueue_shard(t, s);
     }
     note_stage_times(ix, t0, t1);
@@ -285,9 +287,10 @@ int RadiusCall::finish(RadiusBatch &t)
 }  // namespace
 
 int search_radius_impl(szg_index *ix, const double *queries, int n_queries, const double *radii,
-                       const uint64_t *const *masks, std::vector<std::vector<HeapItem>> *results)
+                       const uint64_t *const *masks, std::vector<std::vector<HeapItem>> *results,
+                       const szg_mask *const *handles)
 {
-    RadiusCall call{ix, queries, n_queries, radii, QueryMasks(ix, nullptr, masks), results, ix->shards.size()};
+    RadiusCall call{ix, queries, n_queries, radii, QueryMasks(ix, nullptr, masks, handles), results, ix->shards.size()};
     results->assign(n_queries, {});
     return run_batches<RadiusBatch>(call);
 }

@@ -310,6 +310,7 @@ int SketchCall::stage(Batch &b)
     const double *q = queries + (size_t)b.first * dim;
     const std::vector<const uint64_t *> masks = b.masks(mask_of);
     const uint64_t *const *mptr = b.any_mask ? masks.data() : nullptr;
+    const std::vector<const szg_mask *> handles = b.handles(mask_of);
     const double *q_sk = q;
     if (gs > 0.0) {
         q_scaled.resize((size_t)b.nq * dim);
@@ -357,7 +358,9 @@ int SketchCall::stage(Batch &b)
             rc = fail(SZG_E_DEVICE, "sketch candidates upload", e);
             break;
         }
-        rc = enqueue_queries(sk, h, c, q, b.nq, mptr);  // (the float64 queries unscaled: the rerank is on the rows)
+        // (the float64 queries unscaled: the rerank is on the rows; a resident mask's shard words serve the sketch
+        // shard too: same rows, same device)
+        rc = enqueue_queries(sk, h, c, q, b.nq, mptr, true, handles.empty() ? nullptr : handles.data(), s);
         const RerankOn on{ix, ix->shards[s], extra[s], ix->sketch_list};
         if (rc == SZG_OK) rc = enqueue_topk(sk, h, c, kp, b.nq, b.any_mask, &on);
     }
@@ -479,7 +482,8 @@ int SketchCall::finish(Batch &b)
 }
 
 int search_topk_sketch(szg_index *ix, const double *queries, int n_queries, int k, const uint64_t *allow_bits,
-                       uint64_t *out_rows, double *out_dist, int32_t *out_count, const uint64_t *const *allow_ptrs)
+                       uint64_t *out_rows, double *out_dist, int32_t *out_count, const uint64_t *const *allow_ptrs,
+                       const szg_mask *const *handles)
 {
     int rc;
     {   // (mutations come under the caller's write lock: after the sync, searches run side by side)
@@ -500,15 +504,15 @@ int search_topk_sketch(szg_index *ix, const double *queries, int n_queries, int 
     }
     if (rc) return rc;
     if (ix->sk_disabled || ix->sk_nomem)
-        return search_topk_impl(ix, queries, n_queries, k, allow_bits, out_rows, out_dist, out_count, allow_ptrs);
-    SketchCall call{ix, ix->sketch, queries, n_queries, k, QueryMasks(ix, allow_bits, allow_ptrs), out_rows, out_dist,
-                    out_count};
+        return search_topk_impl(ix, queries, n_queries, k, allow_bits, out_rows, out_dist, out_count, allow_ptrs, handles);
+    SketchCall call{ix, ix->sketch, queries, n_queries, k, QueryMasks(ix, allow_bits, allow_ptrs, handles), out_rows,
+                    out_dist, out_count};
     rc = call.run();
     if (rc && ix->sketch_on == 2) {
         // (a failure inside the pipeline, an allocation of a sketch context: the sketch index stays until the next
         // load, the whole call goes the full-precision way)
         ix->sk_nomem = true;
-        return search_topk_impl(ix, queries, n_queries, k, allow_bits, out_rows, out_dist, out_count, allow_ptrs);
+        return search_topk_impl(ix, queries, n_queries, k, allow_bits, out_rows, out_dist, out_count, allow_ptrs, handles);
     }
     if (rc) return rc;
     if (call.redo.empty()) return SZG_OK;
@@ -516,6 +520,7 @@ int search_topk_sketch(szg_index *ix, const double *queries, int n_queries, int 
     const int m = (int)call.redo.size();
     std::vector<double> q2((size_t)m * ix->dim);
     std::vector<const uint64_t *> m2(m);
+    std::vector<const szg_mask *> h2(handles ? m : 0);
     std::vector<uint64_t> r2((size_t)m * k);
     std::vector<double> d2((size_t)m * k);
     std::vector<int32_t> c2(m);
@@ -523,9 +528,13 @@ int search_topk_sketch(szg_index *ix, const double *queries, int n_queries, int 
     for (int i = 0; i < m; i++) {
         memcpy(&q2[(size_t)i * ix->dim], queries + (size_t)call.redo[i] * ix->dim, sizeof(double) * ix->dim);
         m2[i] = call.mask_of(call.redo[i]);
+        if (handles) h2[i] = handles[call.redo[i]];
         any |= m2[i] != nullptr;
     }
-    rc = search_topk_impl(ix, q2.data(), m, k, nullptr, r2.data(), d2.data(), c2.data(), any ? m2.data() : nullptr);
+    if (handles)
+        rc = search_topk_impl(ix, q2.data(), m, k, nullptr, r2.data(), d2.data(), c2.data(), nullptr, any ? h2.data() : nullptr);
+    else
+        rc = search_topk_impl(ix, q2.data(), m, k, nullptr, r2.data(), d2.data(), c2.data(), any ? m2.data() : nullptr);
     if (rc) return rc;
     for (int i = 0; i < m; i++) {
         memcpy(out_rows + (size_t)call.redo[i] * k, &r2[(size_t)i * k], sizeof(uint64_t) * k);
@@ -536,13 +545,14 @@ int search_topk_sketch(szg_index *ix, const double *queries, int n_queries, int 
 }
 
 int search_topk_any(szg_index *ix, const double *queries, int n_queries, int k, const uint64_t *allow_bits,
-                    uint64_t *out_rows, double *out_dist, int32_t *out_count, const uint64_t *const *allow_ptrs)
+                    uint64_t *out_rows, double *out_dist, int32_t *out_count, const uint64_t *const *allow_ptrs,
+                    const szg_mask *const *handles)
 {
     // (a batch that shares one sweep on the matrix cores is cheaper per query than any pre-pass)
     const bool shared = ix->multi_query && n_queries >= ix->mq_min;
     if (!shared && sketch_applies(ix, k))
-        return search_topk_sketch(ix, queries, n_queries, k, allow_bits, out_rows, out_dist, out_count, allow_ptrs);
-    return search_topk_impl(ix, queries, n_queries, k, allow_bits, out_rows, out_dist, out_count, allow_ptrs);
+        return search_topk_sketch(ix, queries, n_queries, k, allow_bits, out_rows, out_dist, out_count, allow_ptrs, handles);
+    return search_topk_impl(ix, queries, n_queries, k, allow_bits, out_rows, out_dist, out_count, allow_ptrs, handles);
 }
 
 }  // namespace szgi

@@ -41,8 +41,12 @@ size_t shard_words(const Shard *sh) { return (size_t)((sh->n_rows + 63) / 64); }
 // Enqueue H2D of nq prepared queries (+ their masks) on the ctx stream.
 // masks: nullptr (no query of the batch is filtered), or nq pointers to index-level masks
 // ((total_rows + 63) / 64 words each); a null entry allows every row.
+// The masks reach the sweeps by one of three routes (Pass::allow_base / allow_stride say where they are):
+//   every query holds the SAME resident mask   its shard words are read in place, stride 0, nothing is copied
+//   resident masks that differ, or some null   one mask_gather launch fills the batch's d_allow slots card-to-card
+//   words from the host                        staged in pinned memory and uploaded, as before
 int enqueue_queries(szg_index *ix, Shard *sh, Ctx *c, const double *q, int nq, const uint64_t *const *masks,
-                    bool with_single_form)
+                    bool with_single_form, const szg_mask *const *handles, size_t shard_no)
 {
     HIPCHK(hipSetDevice(sh->device));
     memcpy(c->h_q64, q, sizeof(double) * ix->dim * nq);
@@ -57,10 +61,34 @@ int enqueue_queries(szg_index *ix, Shard *sh, Ctx *c, const double *q, int nq, c
         HIPCHK(hipMemcpyAsync(c->d_q64, c->h_q64, sizeof(double) * ix->dim * nq, hipMemcpyHostToDevice,
                               c->pass.work));
     }
-    if (masks) {
+    if (masks && handles) {
+        bool same = handles[0] != nullptr;
+        for (int i = 1; i < nq && same; i++) same = handles[i] == handles[0];
+        for (int i = 0; i < nq; i++)
+            c->mask_count[i] = handles[i] ? (int64_t)mask_shard_count(handles[i], shard_no) : (int64_t)sh->n_rows;
+        if (same) {
+            c->pass.allow_base = mask_shard_words(handles[0], shard_no);
+            c->pass.allow_stride = 0;
+            ix->mask_shared++;
+        } else {
+            const size_t slot = mask_slot_words(sh);
+            int rc = c->d_allow.ensure(slot * nq);
+            if (rc) return rc;
+            szg::MaskGatherTable t{};
+            for (int i = 0; i < nq; i++) t.src[i] = handles[i] ? mask_shard_words(handles[i], shard_no) : nullptr;
+            HIPCHK(szg::launch_mask_gather(t, nq, c->d_allow, slot / 2, c->pass.work));
+            c->pass.allow_base = c->d_allow;
+            c->pass.allow_stride = (uint32_t)slot;
+            ix->mask_d2d += (uint64_t)slot * nq * sizeof(uint64_t);
+        }
+    } else if (masks) {
         const size_t words = shard_words(sh);
         int rc = c->d_allow.ensure(words * nq);
         if (rc) return rc;
+        c->pass.allow_base = c->d_allow;
+        c->pass.allow_stride = (uint32_t)words;
+        ix->mask_h2d += (uint64_t)words * nq * sizeof(uint64_t);
+        std::fill(c->mask_count, c->mask_count + nq, (int64_t)-1);
         rc = c->h_allow.ensure(words * nq);
         if (rc) return rc;
         for (int i = 0; i < nq; i++) {
@@ -91,8 +119,8 @@ void fill_scan_args(const szg_index *ix, const Shard *sh, const Ctx *c, bool has
     a->dim = ix->dim;
     a->map = ix->map;
     a->live_bits = sh->has_dead ? sh->live_bits : nullptr;
-    a->allow_stride = (uint32_t)shard_words(sh);
-    a->allow_bits = has_allow ? c->d_allow + (size_t)slot * a->allow_stride : nullptr;
+    a->allow_stride = c->pass.allow_stride;
+    a->allow_bits = has_allow ? c->pass.allow_base + (size_t)slot * a->allow_stride : nullptr;
     a->query_stride = (uint32_t)ix->qsw_bytes;
     a->query = c->d_qsw + (size_t)slot * ix->qsw_bytes;
     a->n_queries = nq;
@@ -127,11 +155,12 @@ int launch_scans_chained(szg_index *ix, Shard *sh, Ctx *c, const std::vector<szg
     return SZG_OK;
 }
 
-// Pass rates are estimated from a sample of each mask's words.
+// A resident mask knows its exact count; the pass rate of words that came from the host is estimated from a sample.
 double mask_pass_rate(const Shard *sh, const Ctx *c, bool has_allow, int slot)
 {
     const double live = sh->n_rows ? (double)sh->n_live / (double)sh->n_rows : 1.0;
     if (!has_allow) return live;
+    if (c->mask_count[slot] >= 0) return live * (double)c->mask_count[slot] / (double)sh->n_rows;
     const size_t words = shard_words(sh);
     const uint64_t *m = c->h_allow + (size_t)slot * words;
     const size_t step = std::max<size_t>(1, words / 256);
@@ -588,6 +617,15 @@ std::vector<const uint64_t *> Batch::masks(const QueryMasks &mask_of)
     return m;
 }
 
+std::vector<const szg_mask *> Batch::handles(const QueryMasks &mask_of) const
+{
+    std::vector<const szg_mask *> h;
+    if (!mask_of.handles) return h;
+    h.resize(nq);
+    for (int j = 0; j < nq; j++) h[j] = mask_of.handle(first + j);
+    return h;
+}
+
 constexpr int kShortCallLast = 4;  // queries of a short call whose tail is left for after the final sweep
 
 void plan_batch(szg_index *ix, int n_queries, int q0, int nb, const BatchRules &r, Batch *b)
@@ -749,6 +787,8 @@ int TopkCall::stage(TopkBatch &t)
     const double *q = queries + (size_t)t.first * ix->dim;
     const std::vector<const uint64_t *> masks = t.masks(mask_of);
     const uint64_t *const *mptr = t.any_mask ? masks.data() : nullptr;
+    const std::vector<const szg_mask *> handles = t.handles(mask_of);
+    const szg_mask *const *hptr = handles.empty() ? nullptr : handles.data();
     const double t_prep0 = now_us();
     const bool int_planes = t.nb > 0 && mq_uses_i8(ix, false, t.nq);
     int rc = stage_query_forms(ix, t, q, int_planes, [&](int j, QMeta &m) {
@@ -769,7 +809,7 @@ int TopkCall::stage(TopkBatch &t)
     for (size_t s = 0; s < n_sh && rc == SZG_OK; s++) {
         Shard *sh = ix->shards[s];
         if (sh->n_rows == 0) continue;
-        rc = enqueue_queries(ix, sh, t.ctx[s], q, t.nq, mptr, t.nb == 0);
+        rc = enqueue_queries(ix, sh, t.ctx[s], q, t.nq, mptr, t.nb == 0, hptr, s);
         // (before the sweeps: on the context's stream this runs while the scan stream sweeps; a shared sweep whose
         // tail is the refine launch takes the rows along in its one rerank instead)
         if (rc == SZG_OK && !sent.empty())
@@ -1104,9 +1144,10 @@ int TopkCall::run()
 }
 
 int search_topk_impl(szg_index *ix, const double *queries, int n_queries, int k, const uint64_t *allow_bits,
-                     uint64_t *out_rows, double *out_dist, int32_t *out_count, const uint64_t *const *allow_ptrs)
+                     uint64_t *out_rows, double *out_dist, int32_t *out_count, const uint64_t *const *allow_ptrs,
+                     const szg_mask *const *handles)
 {
-    TopkCall call{ix, queries, n_queries, k, QueryMasks(ix, allow_bits, allow_ptrs), out_rows, out_dist, out_count};
+    TopkCall call{ix, queries, n_queries, k, QueryMasks(ix, allow_bits, allow_ptrs, handles), out_rows, out_dist, out_count};
     return call.run();
 }
 

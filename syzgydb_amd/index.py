@@ -5,11 +5,12 @@ vectors.  All compute happens in libsyzgy_scan.so (HIP, gfx950).
 """
 import ctypes
 import os
+import weakref
 
 import numpy as np
 
 from . import _lib
-from ._lib import SZG_COSINE, SZG_EUCLIDEAN, SzgError, SzgStats, check  # noqa: F401
+from ._lib import SZG_COSINE, SZG_EUCLIDEAN, SzgError, SzgMaskStats, SzgStats, check  # noqa: F401
 
 
 def _u8(a):
@@ -35,6 +36,76 @@ def pack_allow_bits(mask):
     return np.ascontiguousarray(packed).view(np.uint64).reshape(nq, words)
 
 
+class ScanMask:
+    """A filter mask that lives on the card (szg_mask): made once per (filter, collection version) by
+    ScanIndex.mask / mask_rows or composed from other masks with & | ~ and andnot, then passed to the searches as
+    masks=.  It keeps its ScanIndex alive; the index closes the masks it still holds before it closes itself.  A load
+    or an append makes older masks stale: searches with them raise SzgError (SZG_E_INVALID), read() and count still
+    work."""
+
+    def __init__(self, index, handle, words):
+        self._index = index
+        self._L = index._L
+        self._h = handle
+        self._words = words   # per mask, as of its creation
+        index._masks[id(self)] = weakref.ref(self)
+
+    def close(self):
+        if self._h:
+            self._L.szg_mask_destroy(self._h)
+            self._h = ctypes.c_void_p()
+            self._index._masks.pop(id(self), None)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def _live(self):
+        if not self._h:
+            raise ValueError("mask is closed")
+        return self._h
+
+    @property
+    def count(self):
+        """Rows the mask allows (exact; tail bits are never set)."""
+        return int(self._L.szg_mask_count(self._live()))
+
+    def read(self):
+        """The mask's words, uint64[ceil(rows / 64)], rows as of the mask's creation."""
+        out = np.zeros(self._words, dtype=np.uint64)
+        check(self._L.szg_mask_read(self._live(), _u64(out) if out.size else None), "szg_mask_read")
+        return out
+
+    def _combine(self, op, other):
+        if other is not None and not isinstance(other, ScanMask):
+            return NotImplemented
+        h = ctypes.c_void_p()
+        check(self._L.szg_mask_combine(op, self._live(), other._live() if other is not None else None, ctypes.byref(h)),
+              "szg_mask_combine")
+        return ScanMask(self._index, h, self._words)
+
+    def __and__(self, other):
+        return self._combine(_lib.SZG_MASK_AND, other)
+
+    def __or__(self, other):
+        return self._combine(_lib.SZG_MASK_OR, other)
+
+    def andnot(self, other):
+        """self & ~other."""
+        return self._combine(_lib.SZG_MASK_ANDNOT, other)
+
+    def __invert__(self):
+        return self._combine(_lib.SZG_MASK_NOT, None)
+
+
 class ScanIndex:
     def __init__(self, dim, quant_bits, metric, devices=None):
         self._L = _lib.load()
@@ -53,6 +124,7 @@ class ScanIndex:
         self.row_bytes = int(self._L.szg_row_bytes(self.quant_bits, self.dim))
         self.options = {}   # tunables set through this object (the host mirrors consult tie_mode)
         self._comm = None
+        self._masks = {}    # id -> weak reference of every ScanMask of this handle that is still open
         # SZG_OPTIONS="name=value,...": tunables applied to every new handle (test sweeps)
         for item in os.environ.get("SZG_OPTIONS", "").split(","):
             if "=" in item:
@@ -61,6 +133,10 @@ class ScanIndex:
 
     # -- lifetime -----------------------------------------------------------
     def close(self):
+        for ref in list(getattr(self, "_masks", {}).values()):  # masks are destroyed before their handle
+            m = ref()
+            if m is not None:
+                m.close()
         if self._h:
             self._L.szg_index_destroy(self._h)
             self._h = ctypes.c_void_p()
@@ -173,8 +249,45 @@ class ScanIndex:
                              % (a.shape[1], words))
         return a, _u64(a)
 
-    def search_topk(self, queries, k, allow=None):
-        """Returns (rows uint64[nq,k], dist float64[nq,k], count int32[nq])."""
+    # -- device-resident filter masks ------------------------------------------
+    def mask(self, allow):
+        """A ScanMask from bool[rows] or uint64 words (bit r = row r may be visited)."""
+        if allow is None:
+            raise ValueError("mask() needs the allowed rows")
+        keep, allow_p = self._allow_arg(allow, 1)
+        h = ctypes.c_void_p()
+        check(self._L.szg_mask_create(self._h, allow_p, ctypes.byref(h)), "szg_mask_create")
+        del keep
+        return ScanMask(self, h, (self.rows + 63) // 64)
+
+    def mask_rows(self, rows):
+        """A ScanMask that allows exactly the listed rows (numbered as searches return them; duplicates allowed)."""
+        r = np.ascontiguousarray(rows, dtype=np.uint64).reshape(-1)
+        h = ctypes.c_void_p()
+        check(self._L.szg_mask_create_rows(self._h, _u64(r) if r.size else None, r.size, ctypes.byref(h)),
+              "szg_mask_create_rows")
+        return ScanMask(self, h, (self.rows + 63) // 64)
+
+    def mask_stats(self):
+        s = SzgMaskStats()
+        check(self._L.szg_index_mask_stats(self._h, ctypes.byref(s)), "szg_index_mask_stats")
+        return {name: int(getattr(s, name)) for name, _ in SzgMaskStats._fields_}
+
+    def _masks_arg(self, masks, allow, n_queries):
+        """masks= as the C array of handles: one ScanMask for every query, or a list with None entries."""
+        if allow is not None:
+            raise ValueError("masks= and allow= are exclusive")
+        if isinstance(masks, ScanMask):
+            masks = [masks]
+        masks = list(masks)
+        if len(masks) not in (1, n_queries):
+            raise ValueError("masks= takes one ScanMask or one entry per query")
+        arr = (ctypes.c_void_p * len(masks))(*[m._live() if m is not None else None for m in masks])
+        return arr, len(masks)
+
+    def search_topk(self, queries, k, allow=None, masks=None):
+        """Returns (rows uint64[nq,k], dist float64[nq,k], count int32[nq]).  allow: host words or booleans per
+        query; masks: one ScanMask for all queries or a list with None entries (exclusive with allow)."""
         q = np.ascontiguousarray(queries, dtype=np.float64)
         if q.ndim == 1:
             q = q.reshape(1, -1)
@@ -185,6 +298,12 @@ class ScanIndex:
         out_rows = np.zeros((nq, max(k, 0)), dtype=np.uint64)
         out_dist = np.zeros((nq, max(k, 0)), dtype=np.float64)
         out_count = np.zeros(nq, dtype=np.int32)
+        if masks is not None:
+            arr, n_masks = self._masks_arg(masks, allow, nq)
+            check(self._L.szg_search_topk_masked(self._h, _f64(q), nq, k, arr, n_masks, _u64(out_rows), _f64(out_dist),
+                                                 out_count.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))),
+                  "szg_search_topk_masked")
+            return out_rows, out_dist, out_count
         keep, allow_p = self._allow_arg(allow, nq)
         check(self._L.szg_search_topk(self._h, _f64(q), nq, k, allow_p, _u64(out_rows),
                                       _f64(out_dist),
@@ -193,11 +312,15 @@ class ScanIndex:
         del keep
         return out_rows, out_dist, out_count
 
-    def search_radius(self, query, radius, allow=None, capacity=None):
+    def search_radius(self, query, radius, allow=None, capacity=None, masks=None):
         """Returns (rows uint64[n], dist float64[n]); grows the buffer on SZG_E_TRUNCATED."""
         q = np.ascontiguousarray(query, dtype=np.float64).reshape(-1)
         if q.size != self.dim:
             raise ValueError("query length %d != dimension %d" % (q.size, self.dim))
+        if masks is not None:
+            if capacity is not None:
+                raise ValueError("masks= answers in full: no capacity")
+            return self.search_radius_batch(q, radius, allow=allow, masks=masks)[0]
         keep, allow_p = self._allow_arg(allow, 1)
         cap = int(capacity) if capacity is not None else 1 << 16  # a too-small buffer costs a second sweep
         while True:
@@ -219,7 +342,7 @@ class ScanIndex:
                 return out_rows[:n], out_dist[:n]
             return out_rows[:n], out_dist[:n], n
 
-    def _radius_csr(self, fn, name, queries, radii, allow, refetch=None):
+    def _radius_csr(self, fn, name, queries, radii, allow, refetch=None, masks=None):
         q = np.ascontiguousarray(queries, dtype=np.float64)
         if q.ndim == 1:
             q = q.reshape(1, -1)
@@ -227,13 +350,17 @@ class ScanIndex:
             raise ValueError("query length %d != dimension %d" % (q.shape[1], self.dim))
         nq = q.shape[0]
         rad = np.ascontiguousarray(np.broadcast_to(np.asarray(radii, dtype=np.float64), (nq,)))
-        keep, allow_p = self._allow_arg(allow, nq)
+        if masks is not None:   # (fn takes the handles and their count where the others take the words)
+            filt = keep = self._masks_arg(masks, allow, nq)
+        else:
+            keep, allow_p = self._allow_arg(allow, nq)
+            filt = (allow_p,)
         cap = max(1 << 16, nq << 12)  # (a truncated call is answered again from scratch: start generous)
         while True:
             out_rows = np.empty(max(cap, 1), dtype=np.uint64)
             out_dist = np.empty(max(cap, 1), dtype=np.float64)
             off = np.zeros(nq + 1, dtype=np.uint64)
-            rc = fn(self._h, _f64(q), nq, _f64(rad), allow_p, _u64(out_rows), _f64(out_dist), cap, _u64(off))
+            rc = fn(self._h, _f64(q), nq, _f64(rad), *filt, _u64(out_rows), _f64(out_dist), cap, _u64(off))
             if rc == _lib.SZG_E_TRUNCATED:
                 cap = int(off[nq])
                 if refetch is None:
@@ -247,9 +374,12 @@ class ScanIndex:
             del keep
             return [(out_rows[int(off[i]):int(off[i + 1])], out_dist[int(off[i]):int(off[i + 1])]) for i in range(nq)]
 
-    def search_radius_batch(self, queries, radii, allow=None):
+    def search_radius_batch(self, queries, radii, allow=None, masks=None):
         """Radius searches for a batch (radii: one value or one per query): a list of (rows, dist) per query,
-        ascending distance.  The collect sweeps of the batch share query-major launches."""
+        ascending distance.  The collect sweeps of the batch share query-major launches.  masks: as search_topk's."""
+        if masks is not None:
+            return self._radius_csr(self._L.szg_search_radius_masked, "szg_search_radius_masked", queries, radii, allow,
+                                    masks=masks)
         return self._radius_csr(self._L.szg_search_radius_batch, "szg_search_radius_batch", queries, radii, allow)
 
     # -- one process per GPU: the exchange inside the library (syzgydb_amd/sharded.py: Comm) ------------
