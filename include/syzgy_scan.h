@@ -460,6 +460,27 @@ int szg_index_set_row_base(szg_index *ix, uint64_t base);
  * failure on ONE rank of a job would. */
 int szg_comm_debug_inject(szg_comm *c, int what, int value);
 
+/*
+ * Test hook, host only (no device is touched): how the one-sweep scan would walk n_rows rows of (dim, quant_bits) --
+ * computed by the functions the launch path itself calls.  kp: candidates kept per list (k + slack; ignored for a
+ * collect sweep), collect: a radius / escalation sweep, masked: a filter mask or tombstones are present, cu_count:
+ * compute units of the card (0 = 256).  SZG_E_INVALID / SZG_E_UNSUPPORTED as szg_index_create.
+ */
+typedef struct szg_scan_plan {
+    int32_t r16;            /* 16-byte pieces per row */
+    int32_t L, P, gpw;      /* lanes per row, pieces per lane, rows per wave step */
+    int32_t pow2;           /* L is a power of two */
+    int32_t dense;          /* L*P == r16 and gpw*L == 64 */
+    int32_t tiled;          /* rows live in 16-row tiles */
+    int32_t grid, block;    /* launch geometry */
+    int32_t ring_depth;     /* 16-byte loads each lane keeps in flight */
+    int32_t shaped;         /* 0, or L*100 + P of the row-shape-specialised kernel */
+    int32_t nontemporal;    /* rows are loaded past the caches */
+    int32_t rows_per_block; /* rows one block covers per wave step */
+} szg_scan_plan;
+int szg_debug_scan_plan(int dim, int quant_bits, uint64_t n_rows, int kp, int collect, int masked, int cu_count,
+                        szg_scan_plan *out);
+
 #ifdef __cplusplus
 }
 #endif

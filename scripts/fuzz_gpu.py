@@ -4,17 +4,27 @@ Random shapes (dim, quantization, metric, rows, k, batch size), filter masks, to
 two-shard handles, duplicate-heavy and scaled corpora, random tunables.  Every answer must be
 the oracle's: same rows in the same order, bit-equal float64 distances (NaN == NaN).
 
-    python scripts/fuzz_gpu.py [seconds] [seed]
+    python scripts/fuzz_gpu.py [seconds] [seed] [--iterations N]
+
+--iterations N runs exactly N cases instead of a time budget: a seed then means the same cases on every run.
+Dimensions come from a fixed list and from the scan kernel's shape lattice (syzgydb_amd/scan_lattice.py: one dimension per
+lane-map class of the drawn row width); about a third of the filtered cases pass their filters as resident masks.
 """
-import os, sys, time
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import argparse, os, sys, time
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
 import numpy as np
 import oracle as orc
-from syzgydb_amd import ScanIndex
+from syzgydb_amd import ScanIndex, scan_lattice
 
-budget = float(sys.argv[1]) if len(sys.argv) > 1 else 60.0
-seed = int(sys.argv[2]) if len(sys.argv) > 2 else 1
+ap = argparse.ArgumentParser()
+ap.add_argument("seconds", nargs="?", type=float, default=60.0)
+ap.add_argument("seed", nargs="?", type=int, default=1)
+ap.add_argument("--iterations", type=int, default=0, help="run exactly this many cases (0: run for `seconds`)")
+args = ap.parse_args()
+budget, seed = args.seconds, args.seed
 rng = np.random.default_rng(seed)
+DIMS = [1, 2, 3, 5, 16, 17, 31, 32, 33, 64, 100, 128, 129, 384, 500, 768, 1024]
 OPTS = [("queries_per_launch", [1, 3, 16]), ("multi_query", [0, 1]), ("force_matrix", [0, 0, 1]),
         ("serialize_scans", [0, 1]), ("mq_min", [2, 8]), ("slack", [0, 16, 40]), ("mq_hits", [64, 1024]),
         ("sketch", [0, 1, 1]), ("sketch_extra", [0, 30]), ("sketch_min_rows", [1, 1, 4096]),
@@ -33,11 +43,11 @@ def same(got_r, got_d, want_r, want_d):
 
 t_end = time.time() + budget
 it = fails = 0
-while time.time() < t_end:
+while (it < args.iterations) if args.iterations else (time.time() < t_end):
     it += 1
     bits = int(rng.choice([4, 8, 16, 32, 64]))
     metric = int(rng.integers(0, 2))
-    dim = int(rng.choice([1, 2, 3, 5, 16, 17, 31, 32, 33, 64, 100, 128, 129, 384, 500, 768, 1024]))
+    dim = int(rng.choice(DIMS + [c.dim for c in scan_lattice.cells(bits)]))
     n = int(rng.choice([1, 2, 15, 16, 17, 63, 64, 65, 200, 1000, 3000, 5000, 9000]))
     if dim * n > 4_000_000:
         n = max(1, 4_000_000 // dim)
@@ -75,11 +85,12 @@ while time.time() < t_end:
     allow = None
     if rng.random() < 0.4:
         allow = rng.random((nq, n)) < rng.choice([0.05, 0.5, 0.95])
+    resident = allow is not None and rng.random() < 1 / 3   # the filters go up once, as masks on the card
     devices = [0, 0] if rng.random() < 0.25 else [0]
     opts = {name: int(rng.choice(vals)) for name, vals in OPTS if rng.random() < 0.3}
     dead = []
     desc = dict(it=it, bits=bits, metric=metric, dim=dim, n=n, nq=nq, k=k, kind=kind, masked=allow is not None,
-                devices=devices, opts=opts)
+                resident=resident, devices=devices, opts=opts)
     try:
         with ScanIndex(dim, bits, metric, devices=devices) as ix:
             split = int(rng.integers(1, n)) if (n > 1 and rng.random() < 0.3) else n
@@ -104,7 +115,13 @@ while time.time() < t_end:
                     ix.tombstone(r)
             live = np.ones(n, dtype=bool)
             live[dead] = False
-            r, d, c = ix.search_topk(Q, k, allow=allow)
+            handles = [ix.mask(allow[qi]) for qi in range(nq)] if resident else None
+
+            def filt(lo, hi):   # the filters of queries [lo, hi) as the searches take them
+                if allow is None:
+                    return {}
+                return dict(masks=handles[lo:hi]) if resident else dict(allow=allow[lo:hi])
+            r, d, c = ix.search_topk(Q, k, **filt(0, nq))
             for qi in range(nq):
                 m = live if allow is None else (live & allow[qi])
                 o_rows, o_dist, _ = orc.search_exact(rows, dim, bits, metric, Q[qi], k=k, allow=m.astype(np.uint8))
@@ -121,7 +138,7 @@ while time.time() < t_end:
             finite = [x for x in o_dist if x == x and x > 0]
             if finite:
                 radius = float(finite[-1])
-                rr, dd = ix.search_radius(Q[qi], radius, allow=None if allow is None else allow[qi])
+                rr, dd = ix.search_radius(Q[qi], radius, **filt(qi, qi + 1))
                 w_rows, w_dist, _ = orc.search_exact(rows, dim, bits, metric, Q[qi], radius=radius,
                                                      allow=m.astype(np.uint8))
                 if not same(rr, dd, w_rows, w_dist):
@@ -135,7 +152,7 @@ while time.time() < t_end:
                 od = orc.search_exact(rows, dim, bits, metric, Q[qj], k=int(rng.choice([1, 5, 60])), allow=mj.astype(np.uint8))[1]
                 fin = [x for x in od if x == x and x > 0]
                 radii.append(float(fin[-1]) if fin else 0.5)
-            hits = ix.search_radius_batch(Q[:nb_], radii, allow=None if allow is None else allow[:nb_])
+            hits = ix.search_radius_batch(Q[:nb_], radii, **filt(0, nb_))
             for qj in range(nb_):
                 mj = live if allow is None else (live & allow[qj])
                 w_r, w_d, _ = orc.search_exact(rows, dim, bits, metric, Q[qj], radius=radii[qj], allow=mj.astype(np.uint8))

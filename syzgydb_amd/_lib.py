@@ -38,6 +38,8 @@ EXPORTS = [
     # device-resident filter masks (added under ABI 4)
     "szg_mask_create", "szg_mask_create_rows", "szg_mask_combine", "szg_mask_count", "szg_mask_read",
     "szg_mask_destroy", "szg_search_topk_masked", "szg_search_radius_masked", "szg_index_mask_stats",
+    # host-only test hook
+    "szg_debug_scan_plan",
 ]
 SZG_MASK_AND, SZG_MASK_OR, SZG_MASK_ANDNOT, SZG_MASK_NOT = 0, 1, 2, 3
 SZG_COMM_ID_BYTES = 128
@@ -82,6 +84,12 @@ class SzgStats(ctypes.Structure):
         ("sketch_fallbacks", ctypes.c_uint64),
         ("mq_bf16_sweeps", ctypes.c_uint64),
     ]
+
+
+class SzgScanPlan(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_int32) for name in (
+        "r16", "L", "P", "gpw", "pow2", "dense", "tiled", "grid", "block", "ring_depth", "shaped", "nontemporal",
+        "rows_per_block")]
 
 
 class SzgMaskStats(ctypes.Structure):
@@ -248,6 +256,10 @@ def load():
     L.szg_pager_metadata.argtypes = [vp, ctypes.c_uint64, ctypes.POINTER(u8p), u64p]
     L.szg_pager_load.restype = ctypes.c_int
     L.szg_pager_load.argtypes = [vp, vp]
+    if hasattr(L, "szg_debug_scan_plan"):   # (as the masks: an older build for an A/B run has no plan hook)
+        L.szg_debug_scan_plan.restype = ctypes.c_int
+        L.szg_debug_scan_plan.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_uint64, ctypes.c_int, ctypes.c_int,
+                                          ctypes.c_int, ctypes.c_int, ctypes.POINTER(SzgScanPlan)]
     L.szg_debug_f64_probe.restype = ctypes.c_int
     L.szg_debug_f64_probe.argtypes = [ctypes.c_int, f64p, f64p, f64p, ctypes.c_uint64]
     _lib = L

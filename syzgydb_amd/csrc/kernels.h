@@ -143,6 +143,17 @@ struct ScanArgs {
     uint32_t *collect_count;
 };
 
+// Which scan_kernel instantiation a launch takes: decided on the host by scan_variant -- the launcher dispatches on
+// its answer, szg_debug_scan_plan reports it.
+struct ScanVariant {
+    int shaped;       // 0: the any-shape kernel; L * 100 + P: the kernel specialised for that row shape
+    int deep;         // the any-shape kernel with the deep piece ring
+    int ring_depth;   // 16-byte loads each lane keeps in flight
+    int nontemporal;  // rows are loaded past the caches
+};
+ScanVariant scan_variant(int qbits, const RowMap &m, bool tiled, int kp, bool collect, bool masked, int ring,
+                         bool no_shape_kernels);
+
 // Fused dequantize + distance + select.  QBITS in {4,8,16,32,64}.
 hipError_t launch_scan(int qbits, int metric, const ScanArgs &a, int grid, int block,
                        hipStream_t stream);

@@ -989,7 +989,6 @@ __global__ __launch_bounds__(1024) void merge_kernel(const uint64_t *in, int n_l
 
 #endif  // SZG_QBITS == 0
 
-#if SZG_QBITS != 0
 // Ring depth.  HBM streams fastest with about 6-9 MB of reads in flight on the chip
 // (scripts/readbw; deeper queues only lengthen the DRAM queues), so the ring is kept SHORT:
 // 4 loads per lane for the any-shape kernels (8 when the candidate lists live in LDS, kp > 64,
@@ -1008,10 +1007,21 @@ constexpr int kRingShort = 4, kRingDeep = 8;
 #define SZG_SHAPE_RING(d) d
 #endif
 
+// The row-shape kernels that exist, X(L, P, D) per row width: read by scan_variant (which launch takes one) and by
+// the launcher of that width (which instantiates them).
+#define SZG_SHAPES_4(X) X(4, 3, 3) X(4, 6, 6)    // tiled rows walk 4 lanes per row: 384 / 768 dims
+#define SZG_SHAPES_8(X) X(4, 6, 6) X(4, 12, 4)
+#define SZG_SHAPES_16(X)
+#define SZG_SHAPES_32(X) X(8, 12, 4)             // linear rows, 8 lanes per row; (8, 24) unrolled over a whole row
+                                                 // spills registers and measured slower than any-shape
+#define SZG_SHAPES_64(X)
+
+#if SZG_QBITS != 0
+
 template <int QBITS, int METRIC, bool COLLECT, int LL, int PP, int D>
-hipError_t launch_shaped(const ScanArgs &a, dim3 g, dim3 b, size_t lds, hipStream_t stream)
+hipError_t launch_shaped(const ScanArgs &a, bool nt, dim3 g, dim3 b, size_t lds, hipStream_t stream)
 {
-    if (LL >= 8 || a.tiled)
+    if (nt)
         hipLaunchKernelGGL((scan_kernel<QBITS, METRIC, D, COLLECT, false, true, LL, PP>), g, b, lds, stream, a);
     else
         hipLaunchKernelGGL((scan_kernel<QBITS, METRIC, D, COLLECT, false, false, LL, PP>), g, b, lds, stream, a);
@@ -1019,9 +1029,9 @@ hipError_t launch_shaped(const ScanArgs &a, dim3 g, dim3 b, size_t lds, hipStrea
 }
 
 template <int QBITS, int METRIC, bool COLLECT, bool MASKED, int D>
-hipError_t launch_any_shape(const ScanArgs &a, dim3 g, dim3 b, size_t lds, hipStream_t stream)
+hipError_t launch_any_shape(const ScanArgs &a, bool nt, dim3 g, dim3 b, size_t lds, hipStream_t stream)
 {
-    if (a.map.L >= 8 || a.tiled)  // whole lines per load instruction: stream past the caches
+    if (nt)  // whole lines per load instruction: stream past the caches
         hipLaunchKernelGGL((scan_kernel<QBITS, METRIC, D, COLLECT, MASKED, true>), g, b, lds, stream, a);
     else
         hipLaunchKernelGGL((scan_kernel<QBITS, METRIC, D, COLLECT, MASKED, false>), g, b, lds, stream, a);
@@ -1032,26 +1042,27 @@ template <int QBITS, int METRIC, bool COLLECT, bool MASKED>
 hipError_t launch_scan_qmcm(const ScanArgs &a, int grid, int block, size_t lds, hipStream_t stream)
 {
     const dim3 g(grid), b(block);
-    const bool deep = (!COLLECT && a.kp > 64) || a.ring >= 8;
+    const ScanVariant v = scan_variant(QBITS, a.map, a.tiled != 0, a.kp, COLLECT, MASKED, a.ring, a.no_shape_kernels != 0);
     if constexpr (!MASKED) {
-        if (a.map.dense && a.map.L * a.map.gpw == kWave && !a.no_shape_kernels && !deep) {
-            const int L = a.map.L, P = a.map.P;
 #define SZG_TRY_SHAPE(l, p, d)                                                                 \
-    if (L == l && P == p) return launch_shaped<QBITS, METRIC, COLLECT, l, p, SZG_SHAPE_RING(d)>(a, g, b, lds, stream);
-            if constexpr (QBITS == 4) {   // tiled rows walk 4 lanes per row: 384 / 768 dims
-                SZG_TRY_SHAPE(4, 3, 3)
-                SZG_TRY_SHAPE(4, 6, 6)
-            } else if constexpr (QBITS == 8) {
-                SZG_TRY_SHAPE(4, 6, 6)
-                SZG_TRY_SHAPE(4, 12, 4)
-            } else if constexpr (QBITS == 32) {   // linear rows, 8 lanes per row; (8, 24) unrolled over a whole
-                SZG_TRY_SHAPE(8, 12, 4)           // row spills registers and measured slower than any-shape
-            }
-#undef SZG_TRY_SHAPE
+    if (v.shaped == l * 100 + p)                                                               \
+        return launch_shaped<QBITS, METRIC, COLLECT, l, p, SZG_SHAPE_RING(d)>(a, v.nontemporal != 0, g, b, lds, stream);
+        if constexpr (QBITS == 4) {
+            SZG_SHAPES_4(SZG_TRY_SHAPE)
+        } else if constexpr (QBITS == 8) {
+            SZG_SHAPES_8(SZG_TRY_SHAPE)
+        } else if constexpr (QBITS == 16) {
+            SZG_SHAPES_16(SZG_TRY_SHAPE)
+        } else if constexpr (QBITS == 32) {
+            SZG_SHAPES_32(SZG_TRY_SHAPE)
+        } else {
+            SZG_SHAPES_64(SZG_TRY_SHAPE)
         }
+#undef SZG_TRY_SHAPE
     }
-    if (deep) return launch_any_shape<QBITS, METRIC, COLLECT, MASKED, kRingDeep>(a, g, b, lds, stream);
-    return launch_any_shape<QBITS, METRIC, COLLECT, MASKED, kRingShort>(a, g, b, lds, stream);
+    if (v.shaped) return hipErrorInvalidValue;  // (scan_variant named a kernel this unit does not carry)
+    if (v.deep) return launch_any_shape<QBITS, METRIC, COLLECT, MASKED, kRingDeep>(a, v.nontemporal != 0, g, b, lds, stream);
+    return launch_any_shape<QBITS, METRIC, COLLECT, MASKED, kRingShort>(a, v.nontemporal != 0, g, b, lds, stream);
 }
 
 template <int QBITS, int METRIC>
@@ -1102,6 +1113,33 @@ SZG_DECL_SCAN(16)
 SZG_DECL_SCAN(32)
 SZG_DECL_SCAN(64)
 #undef SZG_DECL_SCAN
+
+// The instantiation a launch takes.  Row-shape kernels serve unmasked sweeps over dense maps whose lists stay in
+// registers; everything else is the any-shape kernel, with the deep ring when the lists live in LDS (kp > 64).
+ScanVariant scan_variant(int qbits, const RowMap &m, bool tiled, int kp, bool collect, bool masked, int ring,
+                         bool no_shape_kernels)
+{
+    ScanVariant v{};
+    v.deep = ((!collect && kp > 64) || ring >= 8) ? 1 : 0;
+    v.ring_depth = v.deep ? kRingDeep : kRingShort;
+    v.nontemporal = (m.L >= 8 || tiled) ? 1 : 0;  // whole 128-byte lines per load instruction (load_piece)
+    if (!masked && m.dense && m.L * m.gpw == kWave && !no_shape_kernels && !v.deep) {
+#define SZG_IS_SHAPE(l, p, d)                  \
+    if (m.L == l && m.P == p) {                \
+        v.shaped = l * 100 + p;                \
+        v.ring_depth = SZG_SHAPE_RING(d);      \
+    }
+        switch (qbits) {
+        case 4: SZG_SHAPES_4(SZG_IS_SHAPE) break;
+        case 8: SZG_SHAPES_8(SZG_IS_SHAPE) break;
+        case 16: SZG_SHAPES_16(SZG_IS_SHAPE) break;
+        case 32: SZG_SHAPES_32(SZG_IS_SHAPE) break;
+        default: SZG_SHAPES_64(SZG_IS_SHAPE) break;
+        }
+#undef SZG_IS_SHAPE
+    }
+    return v;
+}
 
 size_t scan_lds_bytes(int qbits, const RowMap &m, int kp, int block)
 {

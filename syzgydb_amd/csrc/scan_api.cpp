@@ -450,4 +450,26 @@ int szg_debug_f64_probe(int op, const double *a, const double *b, double *out, u
     return SZG_OK;
 }
 
+// test hook, host only: the lane map, launch geometry and kernel variant a sweep over n_rows rows would take -- from
+// the functions the launch path calls (row_format, scan_geometry, scan_variant), so tests derive their shapes from
+// the code's own rules
+int szg_debug_scan_plan(int dim, int quant_bits, uint64_t n_rows, int kp, int collect, int masked, int cu_count,
+                        szg_scan_plan *out)
+{
+    if (!out) return fail(SZG_E_INVALID, "out is null");
+    if (kp < 0 || cu_count < 0) return fail(SZG_E_INVALID, "kp or cu_count negative");
+    RowFormat f;
+    const int rc = row_format(dim, quant_bits, &f);
+    if (rc == SZG_E_UNSUPPORTED) return fail(rc, "dimension too large for the LDS-resident query");
+    if (rc) return rc;
+    const int list_kp = collect ? 0 : kp;  // collect sweeps keep no lists
+    const LaunchGeom g = scan_geometry(quant_bits, f.map, f.row_bytes, f.layout.tiled != 0, n_rows,
+                                       cu_count ? cu_count : 256, list_kp);
+    const szg::ScanVariant v = szg::scan_variant(quant_bits, f.map, f.layout.tiled != 0, list_kp, collect != 0, masked != 0,
+                                                 szg_index::ring, !szg_index::shape_kernels);
+    *out = szg_scan_plan{f.map.r16, f.map.L,      f.map.P, f.map.gpw,    f.map.pow2, f.map.dense,  (int32_t)f.layout.tiled,
+                         g.grid,    g.block, v.ring_depth, v.shaped, v.nontemporal, g.rows_per_block};
+    return SZG_OK;
+}
+
 }  // extern "C"

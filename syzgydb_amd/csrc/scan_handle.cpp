@@ -265,38 +265,29 @@ int szg_index_create(szg_index **out, int dim, int quant_bits, int metric, const
     SZG_TRY
     if (!out) return fail(SZG_E_INVALID, "out is null");
     *out = nullptr;
-    if (dim <= 0 || dim > (1 << 20)) return fail(SZG_E_INVALID, "dim out of range");
-    const int64_t rb = row_bytes_of(quant_bits, dim);
-    if (rb < 0) return fail(SZG_E_INVALID, "unsupported quantization (reference panics, collection.go:809)");
+    RowFormat fmt;
+    const int fmt_rc = row_format(dim, quant_bits, &fmt);
+    if (fmt_rc == SZG_E_INVALID) return fmt_rc;
     if (metric != SZG_EUCLIDEAN && metric != SZG_COSINE)
         return fail(SZG_E_INVALID, "unsupported distance method (collection.go:282)");
     int count = 0;
     hipError_t e = hipGetDeviceCount(&count);
     if (e != hipSuccess || count <= 0) return fail(SZG_E_NODEVICE, "hipGetDeviceCount", e);
+    if (fmt_rc) return fail(SZG_E_UNSUPPORTED, "dimension too large for the LDS-resident query");
 
     szg_index *ix = new szg_index();
     ix->dim = dim;
     ix->bits = quant_bits;
     ix->metric = metric;
-    ix->row_bytes = (uint32_t)rb;
-    ix->pitch = (uint32_t)((rb + 15) & ~15ll);
-    // 4- and 8-bit rows of whole 64-byte steps live in 16-row tiles (kernels.h, RowLayout): their
-    // single-query walk and the shared sweeps then read 1 KiB runs instead of 64-byte segments
-    // (+8-12 % on 4-bit rows, +2.5 % on 8-bit rows; float rows measured -1..0 % and stay linear:
-    // scripts/dev_tiles.sh, dev_tiles_all.sh).  SZG_TILES_ALL / SZG_NO_TILES override for A/B runs.
-    const bool tiled = (quant_bits <= 8 || getenv("SZG_TILES_ALL") != nullptr) && ix->pitch % 64 == 0 &&
-                       getenv("SZG_NO_TILES") == nullptr;
-    ix->layout = szg::RowLayout{ix->pitch, tiled ? 1u : 0u, tiled ? ix->pitch / 64u : 0u};
-    ix->map = choose_map((int)(ix->pitch / 16), tiled);
-    ix->qsw_bytes = szg::query_lds_bytes(quant_bits, ix->map.r16);
+    ix->row_bytes = fmt.row_bytes;
+    ix->pitch = fmt.pitch;
+    ix->layout = fmt.layout;
+    ix->map = fmt.map;
+    ix->qsw_bytes = fmt.qsw_bytes;
     if (quant_bits == 8 || quant_bits == 4) {
         const double M = (double)((1u << quant_bits) - 1u);
         const double slots = (double)ix->map.r16 * (128 / quant_bits);  // elements incl. padding
         ix->norm_bias = slots - (slots - dim) * M * M;  // each padding slot decodes to n = -maxInt
-    }
-    if (ix->qsw_bytes > 48u * 1024u) {
-        delete ix;
-        return fail(SZG_E_UNSUPPORTED, "dimension too large for the LDS-resident query");
     }
     std::vector<int> devs;
     if (devices && n_devices > 0) {

@@ -474,6 +474,16 @@ namespace szgi {
 
 struct LaunchGeom {
     int grid, block;
+    int rows_per_block;  // rows one block covers per wave step (waves of the block x the map's rows per wave step)
+};
+
+// What a (dimension, row width) pair fixes before any device is touched: the packed row, its resident layout, the
+// lane map of the one-sweep scan and the size of the prepared query.
+struct RowFormat {
+    uint32_t row_bytes = 0, pitch = 0;
+    szg::RowLayout layout{};
+    szg::RowMap map{};
+    size_t qsw_bytes = 0;
 };
 
 // ---- api_common.cpp
@@ -485,6 +495,9 @@ bool history_dependent(const double *dist, size_t n, int k);
 
 // ---- scan_query.cpp
 szg::RowMap choose_map(int r16, bool tiled = false);
+// SZG_OK; SZG_E_INVALID (dimension or row width out of range, with the error text set); SZG_E_UNSUPPORTED: the format is
+// filled in, but the prepared query does not fit the scan's LDS budget (the caller reports it)
+int row_format(int dim, int quant_bits, RowFormat *f);
 void prep_query(const szg_index *ix, const double *q, uint8_t *out_sw, QMeta *meta);
 void prep_query_meta(const szg_index *ix, const double *q, QMeta *meta);  // the constants only (shared sweeps)
 double key_eps(const szg_index *ix, double key, const QMeta &m);
@@ -518,6 +531,9 @@ Shard *append_target(szg_index *ix);
 void note_overwritten(szg_index *ix, uint64_t row);
 
 // ---- scan_topk.cpp
+// grid and block of a sweep over n_rows rows (kp = 0: a collect sweep); the second form reads them off a shard
+LaunchGeom scan_geometry(int bits, const szg::RowMap &map, uint32_t row_bytes, bool tiled, uint64_t n_rows, int cu_count,
+                         int kp);
 LaunchGeom scan_geometry(const szg_index *ix, const Shard *sh, int kp, bool plain_topk = false);
 size_t shard_words(const Shard *sh);
 // (handles: null, or the resident masks of the batch's queries -- then `masks` holds their host words -- and `shard_no`,

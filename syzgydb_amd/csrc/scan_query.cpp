@@ -39,6 +39,25 @@ szg::RowMap choose_map(int r16, bool tiled)
     return best;
 }
 
+int row_format(int dim, int quant_bits, RowFormat *f)
+{
+    if (dim <= 0 || dim > (1 << 20)) return fail(SZG_E_INVALID, "dim out of range");
+    const int64_t rb = row_bytes_of(quant_bits, dim);
+    if (rb < 0) return fail(SZG_E_INVALID, "unsupported quantization (reference panics, collection.go:809)");
+    f->row_bytes = (uint32_t)rb;
+    f->pitch = (uint32_t)((rb + 15) & ~15ll);
+    // 4- and 8-bit rows of whole 64-byte steps live in 16-row tiles (kernels.h, RowLayout): their
+    // single-query walk and the shared sweeps then read 1 KiB runs instead of 64-byte segments
+    // (+8-12 % on 4-bit rows, +2.5 % on 8-bit rows; float rows measured -1..0 % and stay linear:
+    // scripts/dev_tiles.sh, dev_tiles_all.sh).  SZG_TILES_ALL / SZG_NO_TILES override for A/B runs.
+    const bool tiled = (quant_bits <= 8 || getenv("SZG_TILES_ALL") != nullptr) && f->pitch % 64 == 0 &&
+                       getenv("SZG_NO_TILES") == nullptr;
+    f->layout = szg::RowLayout{f->pitch, tiled ? 1u : 0u, tiled ? f->pitch / 64u : 0u};
+    f->map = choose_map((int)(f->pitch / 16), tiled);
+    f->qsw_bytes = szg::query_lds_bytes(quant_bits, f->map.r16);
+    return f->qsw_bytes > 48u * 1024u ? SZG_E_UNSUPPORTED : SZG_OK;
+}
+
 // round to nearest (ties away from zero) without a libm call; NaN -> 0, clamped to +-lim.
 // Any rounding rule serves: Q only has to be within 1/2 of v/qscale (key_eps).
 inline long long round_clamp(double t, double lim)

@@ -4,36 +4,42 @@
 
 namespace szgi {
 
-LaunchGeom scan_geometry(const szg_index *ix, const Shard *sh, int kp, bool plain_topk)
+LaunchGeom scan_geometry(int bits, const szg::RowMap &map, uint32_t row_bytes, bool tiled, uint64_t n_rows, int cu_count,
+                         int kp)
 {
-    int block = ix->block_threads;
+    int block = szg_index::block_threads;
     // keep query + per-wave lists within 64 KiB of LDS
-    while (block > 64 && szg::scan_lds_bytes(ix->bits, ix->map, kp, block) > 64u * 1024u) block >>= 1;
+    while (block > 64 && szg::scan_lds_bytes(bits, map, kp, block) > 64u * 1024u) block >>= 1;
     const int nwaves = block / 64;
-    const uint64_t rows_per_block = (uint64_t)nwaves * ix->map.gpw;
-    uint64_t need = (sh->n_rows + rows_per_block - 1) / rows_per_block;
-    int waves_per_cu = ix->blocks_per_cu * nwaves;
-    if (ix->blocks_per_cu <= 0) {
+    const uint64_t rows_per_block = (uint64_t)nwaves * map.gpw;
+    uint64_t need = (n_rows + rows_per_block - 1) / rows_per_block;
+    int waves_per_cu = szg_index::blocks_per_cu * nwaves;
+    if (szg_index::blocks_per_cu <= 0) {
         // Measured on MI355X (scripts/dev_bpc.sh, scripts/readbw): HBM streams fastest with
         // 6-8 MB of reads in flight; more requests only lengthen the DRAM queues.  8 waves
         // per CU for float rows of >= 1 KB and for LDS-resident candidate lists (kp > 64);
         // the integer / 16-bit decodes and short rows need 12 to hide their ALU work.
         // (4 waves per CU is another 0.5 % faster on 3 KB rows at 1M rows but 10 % slower
         // on a 125 K-row shard, where the sweep's ramp-up and tail weigh more.)
-        (void)plain_topk;
         // Collect sweeps (kp == 0: radius search, escalation) keep no lists; on short 4-bit rows (cfg5's 192 bytes)
         // they stream best with 8 (same-box A/B, scripts/ab_opts.sh: 6.2-6.7 -> 6.85-6.91 TB/s; top-k on the same rows
         // wants its 12: 6.8-6.9 against 6.5).
-        const bool short_collect = kp == 0 && ix->bits == 4 && ix->row_bytes <= 256;
-        if (kp > 64 || short_collect || (ix->bits >= 32 && ix->row_bytes >= 1024) || (ix->bits == 8 && ix->layout.tiled))
+        const bool short_collect = kp == 0 && bits == 4 && row_bytes <= 256;
+        if (kp > 64 || short_collect || (bits >= 32 && row_bytes >= 1024) || (bits == 8 && tiled))
             waves_per_cu = 8;
         else
             waves_per_cu = 12;
     }
-    uint64_t grid = (uint64_t)sh->cu_count * (uint64_t)std::max(1, waves_per_cu / nwaves);
+    uint64_t grid = (uint64_t)cu_count * (uint64_t)std::max(1, waves_per_cu / nwaves);
     if (need < grid) grid = need;
     if (grid < 1) grid = 1;
-    return LaunchGeom{(int)grid, block};
+    return LaunchGeom{(int)grid, block, (int)rows_per_block};
+}
+
+LaunchGeom scan_geometry(const szg_index *ix, const Shard *sh, int kp, bool plain_topk)
+{
+    (void)plain_topk;
+    return scan_geometry(ix->bits, ix->map, ix->row_bytes, ix->layout.tiled != 0, sh->n_rows, sh->cu_count, kp);
 }
 
 size_t shard_words(const Shard *sh) { return (size_t)((sh->n_rows + 63) / 64); }

@@ -10,7 +10,7 @@ import weakref
 import numpy as np
 
 from . import _lib
-from ._lib import SZG_COSINE, SZG_EUCLIDEAN, SzgError, SzgMaskStats, SzgStats, check  # noqa: F401
+from ._lib import SZG_COSINE, SZG_EUCLIDEAN, SzgError, SzgMaskStats, SzgScanPlan, SzgStats, check  # noqa: F401
 
 
 def _u8(a):
@@ -440,3 +440,13 @@ def f64_probe(op, a, b=None):
     out = np.zeros_like(a)
     check(L.szg_debug_f64_probe(int(op), _f64(a), _f64(bb), _f64(out), a.size), "szg_debug_f64_probe")
     return out
+
+
+def scan_plan(dim, quant_bits, n_rows, kp=10, collect=False, masked=False, cu_count=0):
+    """Host-only test hook (no device needed): the lane map, launch geometry and kernel variant of a one-sweep scan
+    over n_rows rows, as a dict of szg_scan_plan's fields.  Raises SzgError as szg_index_create would."""
+    L = _lib.load()
+    p = SzgScanPlan()
+    check(L.szg_debug_scan_plan(int(dim), int(quant_bits), int(n_rows), int(kp), int(bool(collect)), int(bool(masked)),
+                                int(cu_count), ctypes.byref(p)), "szg_debug_scan_plan")
+    return {name: int(getattr(p, name)) for name, _ in SzgScanPlan._fields_}

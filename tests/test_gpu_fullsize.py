@@ -13,7 +13,8 @@ import numpy as np
 import pytest
 
 import oracle as orc
-from syzgydb_amd import ScanIndex
+import scan_lattice as lat
+from syzgydb_amd import ScanIndex, scan_plan
 from syzgydb_amd.synth import synth_vectors
 
 pytestmark = pytest.mark.gpu
@@ -150,3 +151,75 @@ def test_cfg5_full_radius_search():
             # the k nearest by top-k search are the head of the radius result
             r10, d10, _ = ix.search_topk(q[qi], 10)
             assert (d10[0] <= R).all() and set(int(x) for x in r10[0]) <= hits
+
+
+# ---- step compaction of selective masks at scale (kernels_scan.hip, general phase) ---------------------------------------
+# A wave under a selective mask first compacts the row steps that hold a passing row into its LDS step list, 64 steps
+# per loop iteration, and rings over the list once it holds more than 192 entries (or the steps are used up); what is
+# left goes into further rounds.  Small corpora give a wave a handful of steps: one iteration, one round.  Here a cell
+# with ONE row per wave step (L = 64) gets so many rows that every wave has more than 256 steps.
+
+COMPACT_STEPS = 300   # row steps per wave: > 64 (a second loop iteration), > 256 (steps are left for a second round)
+
+
+def _compaction_cell():
+    """64-bit rows, one row per wave step: the lattice's L = 64, P = 1 cell (the fewest elements per row for the oracle)."""
+    c = next(c for c in lat.cells(64) if c.L == 64 and c.P == 1)
+    p = scan_plan(c.dim, 64, 1 << 40, lat.kp_of(10), masked=True)
+    assert p["gpw"] == 1 and p["rows_per_block"] == p["block"] // 64
+    stride = p["grid"] * p["rows_per_block"]          # rows between two steps of a wave
+    return c, stride, COMPACT_STEPS * stride + 1      # (+1: a partial mask word, and one wave with a step more)
+
+
+_compaction_kept = {}
+
+
+def _compaction_corpus():
+    if not _compaction_kept:
+        c, stride, n = _compaction_cell()
+        seed = 0x53595A4700000500
+        ix = ScanIndex(c.dim, 64, 1)
+        ix.synth(n, seed)
+        ix.set_option("multi_query", 0)
+        ix.set_option("sketch", 0)
+        _compaction_kept.update(ix=ix, rows=ix.read_rows(0, n), q=synth_vectors(seed + 1, 0, 1, c.dim)[0], seed=seed)
+        assert (_compaction_kept["rows"][n - 3:] == orc.synth_rows(seed, n - 3, 3, c.dim, 64)).all()
+    return _compaction_kept
+
+
+@pytest.mark.parametrize("form", ["second-iteration", "second-round"])
+def test_step_compaction_at_scale(form):
+    """second-iteration: a 2 % filter over 300 steps per wave -- the compaction loop runs five iterations and lists
+    about six steps.  second-round: a 90 % filter with the dense masked form switched off -- the first 256 steps of a
+    wave list more than 192 passing ones, the ring runs, and the rest is compacted in a second round.  One query each,
+    against a complete oracle scan."""
+    c, stride, n = _compaction_cell()
+    kept = _compaction_corpus()
+    ix, rows, q = kept["ix"], kept["rows"], kept["q"]
+    rng = np.random.default_rng(5)
+    allow = rng.random(n) < (0.02 if form == "second-iteration" else 0.9)
+    per_wave = allow[: COMPACT_STEPS * stride].reshape(COMPACT_STEPS, stride)   # [step, wave]: gpw == 1
+    p = scan_plan(c.dim, 64, n, lat.kp_of(10), masked=True)
+    assert p["grid"] * p["rows_per_block"] == stride   # the grid is at its cap
+    if form == "second-iteration":
+        assert COMPACT_STEPS > 64 and per_wave.sum(axis=0).max() <= 192     # several iterations, one round
+        ix.set_option("mask_dense", 1)                                     # (selective by its pass rate)
+    else:
+        first = per_wave[:256].sum(axis=0)
+        assert COMPACT_STEPS > 256 and (first > 192).mean() > 0.99, first.min()   # a second round in nearly every wave
+        ix.set_option("mask_dense", 0)
+    ix.reset_stats()
+    r, d, cnt = ix.search_topk(q, 10, allow=allow)
+    with ix.mask(allow) as m:
+        rm, dm, cm = ix.search_topk(q, 10, masks=m)
+        hits = ix.search_radius(q, float(d[0, 9]), masks=m)
+    st = ix.stats()
+    assert st["mq_queries"] == 0 and st["sketch_queries"] == 0 and st["scan_launches"] > 0, st
+    o_rows, o_dist, _ = orc.search_exact(rows, c.dim, 64, 1, q, k=10, allow=allow.astype(np.uint8))
+    for got_r, got_d in ((r[0, : cnt[0]], d[0, : cnt[0]]), (rm[0, : cm[0]], dm[0, : cm[0]]), (hits[0][:10], hits[1][:10])):
+        assert [int(x) for x in got_r] == [int(x) for x in o_rows]
+        assert (np.asarray(got_d) == o_dist).all()
+    assert len(hits[0]) == 10 or hits[1][10] == hits[1][9]
+    if form == "second-round":   # the last form: the shared handle goes
+        ix.close()
+        _compaction_kept.clear()
