@@ -348,7 +348,9 @@ typedef struct szg_stats {
     uint64_t queries;          /* top-k + radius queries served */
     uint64_t scan_launches;    /* launches of the fused scan kernel */
     uint64_t escalations;      /* top-k queries whose first pass could not be certified */
-    uint64_t scan_bytes;       /* algorithmic bytes swept: sum over launches of rows x row_bytes */
+    uint64_t scan_bytes;       /* bytes swept: rows x row_bytes per pass over the rows -- one pass per query of a
+                                  one-sweep launch, or per group of scan_group queries where the launch forms groups;
+                                  one per query group of a shared sweep */
     double scan_ms;            /* HIP-event time of the scan kernel launches (timing on) */
     double total_ms;           /* HIP-event time of the whole per-query pipeline (timing on) */
     uint64_t timed_launches;   /* launches included in scan_ms */
@@ -378,7 +380,7 @@ int szg_get_stats(szg_index *ix, szg_stats *out);
 int szg_reset_stats(szg_index *ix);
 
 /*
- * Tunables (name, default, meaning): the sixteen a deployment could want.  All are safe to change between calls.
+ * Tunables (name, default, meaning): the seventeen a deployment could want.  All are safe to change between calls.
  * (Rounds 1-3 exposed another fifteen -- ring depths, waves per CU, stream placement, sweep kinds per row width --
  * whose values measurement settled; they are compile-time constants now, csrc/scan_internal.h, and A/B runs go
  * through `make variant`.)
@@ -392,6 +394,13 @@ int szg_reset_stats(szg_index *ix);
  *   one sweep per query
  *     queries_per_launch  16  sweeps one scan launch walks back to back (query-major): no launch gap or chip-wide
  *                             tail between the sweeps of a batch
+ *     scan_group          0   queries of a launch the one-sweep kernel scores per row read.  8-bit rows (plain 8-bit
+ *                             collections and the sketch pre-pass), top-k, no filter and no tombstones, lists in
+ *                             registers (kp <= 64): the launch walks its queries in groups of up to this many and reads
+ *                             every row once per GROUP.  The 8-bit arithmetic is exact, so keys, lists and answers are
+ *                             those of 1, bit for bit.  0 = automatic (4), 1 = one query per row read, 2 / 4 = that
+ *                             group size where the launch qualifies; a launch of one query always reads at 1.  Other
+ *                             row widths, radius / escalation sweeps, masked launches and longer lists are always 1
  *     query_batch         16  queries staged, merged, re-ranked and copied back together
  *     mask_dense          1   sweeps whose filter / tombstone masks pass at least half the rows read every row and
  *                             apply the masks at the row finish; selective masks (and 0) compact the row steps that
@@ -426,7 +435,9 @@ int szg_reset_stats(szg_index *ix);
  *                             bfloat16 bound) -- and top-k batches of more than 48 queries on 8-bit rows in whole 64-byte steps, whose codes
  *                             are exact in bfloat16 (only the query is rounded) --, 4-bit rows, the other 8-bit
  *                             shapes and every radius batch on 8-bit rows in exact integer arithmetic
- *                             (v_mfma_i32_16x16x64_i8, 48 per pass, two passes per launch); 0 = one sweep per query
+ *                             (v_mfma_i32_16x16x64_i8, 48 per pass, two passes per launch); 0 = no shared sweep on
+ *                             the matrix cores: the one-sweep kernel, which on 8-bit rows scores up to scan_group
+ *                             queries of a launch per row read
  *     mq_min              2   smallest batch worth a shared sweep
  *     mq_hits             1024 candidates per query the threshold from the prefix pass aims at
  *     coalesce            1   concurrent szg_search_topk calls with ONE query each -- the reference's Searches under
@@ -480,6 +491,14 @@ typedef struct szg_scan_plan {
 } szg_scan_plan;
 int szg_debug_scan_plan(int dim, int quant_bits, uint64_t n_rows, int kp, int collect, int masked, int cu_count,
                         szg_scan_plan *out);
+
+/*
+ * Test hook, host only: how a one-sweep call of n_queries queries forms groups (option scan_group) -- by the functions
+ * the launch path calls.  The call is split into launches of queries_per_launch queries; *group = the group size of the
+ * first launch, *lds_bytes = the LDS that launch asks for, *passes = passes over the rows of the whole call.
+ */
+int szg_debug_scan_group(int dim, int quant_bits, int kp, int collect, int masked, int scan_group, int n_queries,
+                         int queries_per_launch, int32_t *group, uint64_t *lds_bytes, int32_t *passes);
 
 #ifdef __cplusplus
 }

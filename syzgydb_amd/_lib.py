@@ -39,7 +39,7 @@ EXPORTS = [
     "szg_mask_create", "szg_mask_create_rows", "szg_mask_combine", "szg_mask_count", "szg_mask_read",
     "szg_mask_destroy", "szg_search_topk_masked", "szg_search_radius_masked", "szg_index_mask_stats",
     # host-only test hook
-    "szg_debug_scan_plan",
+    "szg_debug_scan_plan", "szg_debug_scan_group",
 ]
 SZG_MASK_AND, SZG_MASK_OR, SZG_MASK_ANDNOT, SZG_MASK_NOT = 0, 1, 2, 3
 SZG_COMM_ID_BYTES = 128
@@ -260,6 +260,10 @@ def load():
         L.szg_debug_scan_plan.restype = ctypes.c_int
         L.szg_debug_scan_plan.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_uint64, ctypes.c_int, ctypes.c_int,
                                           ctypes.c_int, ctypes.c_int, ctypes.POINTER(SzgScanPlan)]
+    if hasattr(L, "szg_debug_scan_group"):
+        L.szg_debug_scan_group.restype = ctypes.c_int
+        L.szg_debug_scan_group.argtypes = [ctypes.c_int] * 8 + [ctypes.POINTER(ctypes.c_int32), u64p,
+                                                                ctypes.POINTER(ctypes.c_int32)]
     L.szg_debug_f64_probe.restype = ctypes.c_int
     L.szg_debug_f64_probe.argtypes = [ctypes.c_int, f64p, f64p, f64p, ctypes.c_uint64]
     _lib = L

@@ -131,6 +131,8 @@ struct ScanArgs {
     int ring;                   // tuning hook: >= 8 forces the deep ring (0 = chosen from kp)
     int mask_dense;             // masked sweep that reads every row and applies the masks at the row finish
                                 // (most rows pass); 0 = rows are tested before their loads are issued
+    int group;                  // option scan_group: queries of the launch scored per row read where the launch
+                                // qualifies (scan_variant); 0 = automatic, 1 = one query per row read
     int kp;                     // candidates kept per list (top-k mode)
     uint64_t *block_lists;      // [n_queries][grid][kp] sorted ascending (top-k mode)
     // collect mode (radius search / escalation): every row of sweep s with key <= thr_ukeys[s] is appended to
@@ -150,15 +152,23 @@ struct ScanVariant {
     int deep;         // the any-shape kernel with the deep piece ring
     int ring_depth;   // 16-byte loads each lane keeps in flight
     int nontemporal;  // rows are loaded past the caches
+    int group;        // queries of the launch scored per row read (1, 2 or 4)
 };
+// What "automatic" (scan_group = 0) asks for, where a launch qualifies.
+constexpr int kScanGroupAuto = 4;
+// group: the scan_group option (0 = automatic), n_queries: the launch's, block: its threads (the group's query images
+// and lists have to fit 64 KiB of LDS)
 ScanVariant scan_variant(int qbits, const RowMap &m, bool tiled, int kp, bool collect, bool masked, int ring,
-                         bool no_shape_kernels);
+                         bool no_shape_kernels, int group = 1, int n_queries = 1, int block = 256);
+inline bool scan_masked(const ScanArgs &a) { return a.live_bits != nullptr || a.allow_bits != nullptr; }
+// passes over the rows that launch_scan makes for `a`: one per group of its queries
+int scan_passes(int qbits, const ScanArgs &a, int block);
 
 // Fused dequantize + distance + select.  QBITS in {4,8,16,32,64}.
 hipError_t launch_scan(int qbits, int metric, const ScanArgs &a, int grid, int block,
                        hipStream_t stream);
-// LDS bytes launch_scan needs for (qbits, map, kp, block)
-size_t scan_lds_bytes(int qbits, const RowMap &m, int kp, int block);
+// LDS bytes launch_scan needs for (qbits, map, kp, block) at `group` queries per row read
+size_t scan_lds_bytes(int qbits, const RowMap &m, int kp, int block, int group = 1);
 
 // Merge n_lists sorted lists of kp candidates into ceil(n_lists/merge_fan(kp)) lists.
 int merge_fan(int kp);

@@ -16,6 +16,8 @@
 #include "kernels.h"
 #include "device_lists.h"
 
+#include <type_traits>
+
 // Built six times: -DSZG_QBITS=4/8/16/32/64 each carry the scan kernels of one
 // quantization (80 instantiations in one unit took minutes to compile); the unit
 // without it (0) has the list-merge kernels and the dispatcher.
@@ -36,6 +38,9 @@ constexpr int kWave = 64;
 #ifndef SZG_QPF
 #define SZG_QPF 0  // integer paths: fetch the query's digit planes of the NEXT piece from LDS before this piece's dots
 #endif
+// G > 1 kernels hold G lists and G accumulator triples per lane: two blocks per CU (256 registers) keep them free of
+// spills, and two blocks of four waves are what the sweeps over tiled 8-bit rows run per CU anyway (scan_geometry)
+constexpr int kGroupMinBlocks = 2;
 [[maybe_unused]] constexpr int kStepList = 256;  // row steps a wave compacts at a time (selective masks)  // 16-byte loads each lane keeps in flight
 
 template <int QBITS>
@@ -289,10 +294,74 @@ struct RowAcc<8, METRIC> {
         int nrm = 4 * (SQ + SV);
         dot = grp_sum(dot, g);
         nrm = grp_sum(nrm, g);
-        const float norm = (float)nrm + a.norm_bias;
+        return key_of(dot, (float)nrm + a.norm_bias, a);
+    }
+    // the ranking key from the row's reduced sums: dot = 16384 H + 128 M + L, norm = sum n^2
+    static __device__ __forceinline__ float key_of(float dot, float norm, const QConst &a)
+    {
         const float d2 = fmaf(2.0f, dot, a.qconst);  // sum Q n
         if (METRIC == kCosine) return -(d2 * a.qscale) * __frsqrt_rn(norm);
         return fmaf(-2.0f * a.qscale, d2, a.qnorm2 + norm);
+    }
+};
+
+// 8-bit rows, G queries scored per row read: the G query images lie side by side in LDS, `qbytes`
+// apart.  A piece of the row is loaded, xor-ed and summed into the row norm (SQ, SV) once; each query of the group
+// then costs its three plane reads and 12 v_dot4.  The arithmetic is RowAcc<8>'s, integer and exact, and the key
+// is formed by the same float operations: a query's key for a row does not depend on how the queries are grouped.
+template <int METRIC, int G>
+struct RowAccGroup8 {
+    static constexpr bool kPrefetch = false;
+    int H[G], M[G], L[G], SQ, SV;
+    __device__ __forceinline__ void reset()
+    {
+#pragma unroll
+        for (int x = 0; x < G; x++) H[x] = M[x] = L[x] = 0;
+        SQ = SV = 0;
+    }
+    __device__ __forceinline__ void fetch(const uint8_t *, int, int) {}
+    __device__ __forceinline__ void piece_pf(const uint4, const uint8_t *, int, int) {}
+    __device__ __forceinline__ void piece(const uint4 raw, const uint8_t *q, int j, const int r16, const int dim)
+    {
+        const uint32_t w[4] = {raw.x ^ 0x80808080u, raw.y ^ 0x80808080u, raw.z ^ 0x80808080u,
+                               raw.w ^ 0x80808080u};
+#pragma unroll
+        for (int d = 0; d < 4; d++) {
+            SQ = __builtin_amdgcn_sdot4((int)w[d], (int)w[d], SQ, false);
+            SV = __builtin_amdgcn_sdot4((int)w[d], 0x01010101, SV, false);
+        }
+        const int qbytes = (int)query_lds_bytes(8, r16);
+#pragma unroll
+        for (int x = 0; x < G; x++) {
+            const uint4 *q4 = reinterpret_cast<const uint4 *>(q + x * qbytes);
+            const uint4 qh = q4[j], qm = q4[r16 + j], ql = q4[2 * r16 + j];
+            const uint32_t h[4] = {qh.x, qh.y, qh.z, qh.w};
+            const uint32_t m[4] = {qm.x, qm.y, qm.z, qm.w};
+            const uint32_t l[4] = {ql.x, ql.y, ql.z, ql.w};
+#pragma unroll
+            for (int d = 0; d < 4; d++) {
+                H[x] = __builtin_amdgcn_sdot4((int)h[d], (int)w[d], H[x], false);
+                M[x] = __builtin_amdgcn_sdot4((int)m[d], (int)w[d], M[x], false);
+                L[x] = __builtin_amdgcn_sdot4((int)l[d], (int)w[d], L[x], false);
+            }
+        }
+        // The sums are due HERE (an empty asm that takes and returns them; no instruction).  Left free, instruction
+        // selection puts the dots of the group's later queries off to the end of an unrolled row: their digit planes and
+        // the row's xor-ed pieces then stay in registers for the whole row -- 256 registers and spills at G = 2 already.
+#pragma unroll
+        for (int x = 0; x < G; x++) asm volatile("" : "+v"(H[x]), "+v"(M[x]), "+v"(L[x]));
+    }
+    // the row's norm, reduced once for the whole group (norm_bias is the launch's)
+    __device__ __forceinline__ float finish_norm(const QConst &a, const Grp &g)
+    {
+        const int nrm = grp_sum(4 * (SQ + SV), g);
+        return (float)nrm + a.norm_bias;
+    }
+    __device__ __forceinline__ float finish_key(int x, float norm, const QConst &a, const Grp &g)
+    {
+        float dot = fmaf(16384.0f, (float)H[x], fmaf(128.0f, (float)M[x], (float)L[x]));
+        dot = grp_sum(dot, g);
+        return RowAcc<8, METRIC>::key_of(dot, norm, a);
     }
 };
 
@@ -379,10 +448,16 @@ struct RowAcc<4, METRIC> {
 // LL, PP > 0: the row shape (lanes per row, pieces per lane) is a compile-time constant
 // -- the common dims (384, 768, ...) get kernels whose addressing, reductions and query
 // offsets are folded; 0, 0 = any shape, from a.map.
-template <int QBITS, int METRIC, int D, bool COLLECT, bool MASKED, bool NT, int LL = 0, int PP = 0>
-__global__ __launch_bounds__(256, SZG_MIN_BLOCKS) void scan_kernel(const ScanArgs a)
+//
+// G > 1 (8-bit top-k sweeps without masks, lists in registers): the launch's queries are walked in groups of up to G
+// consecutive ones, every group in ONE pass over the rows -- G query images, G wave lists and G accumulator triples
+// per lane against one load of each piece (RowAccGroup8).  G = 1 is the kernel without groups.
+template <int QBITS, int METRIC, int D, bool COLLECT, bool MASKED, bool NT, int LL = 0, int PP = 0, int G = 1>
+__global__ __launch_bounds__(256, G > 1 ? kGroupMinBlocks : SZG_MIN_BLOCKS) void scan_kernel(const ScanArgs a)
 {
     static_assert((LL == 0) == (PP == 0), "shape is fixed as a whole or not at all");
+    static_assert(G == 1 || (QBITS == 8 && !COLLECT && !MASKED), "groups: unmasked 8-bit top-k sweeps only");
+    using Acc = std::conditional_t<G == 1, RowAcc<QBITS, METRIC>, RowAccGroup8<METRIC, G>>;
     extern __shared__ __align__(16) uint8_t smem[];
 
     const int tid = threadIdx.x;
@@ -392,10 +467,11 @@ __global__ __launch_bounds__(256, SZG_MIN_BLOCKS) void scan_kernel(const ScanArg
     const int r16 = LL ? LL * PP : a.map.r16;
     const int qbytes = (int)query_lds_bytes(QBITS, r16);  // multiple of 16
 
-    uint64_t *lists = reinterpret_cast<uint64_t *>(smem + qbytes);
+    // LDS: G query images | G x nwaves wave lists ([query of the group][wave][kp]) | step lists
+    uint64_t *lists = reinterpret_cast<uint64_t *>(smem + G * qbytes);
     uint64_t *mylist = lists + (size_t)wave * a.kp;
     [[maybe_unused]] uint32_t *steplist =
-        reinterpret_cast<uint32_t *>(smem + qbytes + (size_t)nwaves * (COLLECT ? 0 : a.kp) * sizeof(uint64_t)) +
+        reinterpret_cast<uint32_t *>(smem + G * qbytes + (size_t)G * nwaves * (COLLECT ? 0 : a.kp) * sizeof(uint64_t)) +
         (size_t)wave * kStepList;
     const int L = LL ? LL : a.map.L, P = PP ? PP : a.map.P, gpw = LL ? kWave / LL : a.map.gpw;
     const int grp = lane / L;
@@ -407,19 +483,30 @@ __global__ __launch_bounds__(256, SZG_MIN_BLOCKS) void scan_kernel(const ScanArg
     // Query-major batch: one launch walks the corpus once per query, back to
     // back.  Blocks move from query to query on their own (block-level barriers
     // only), so there is no chip-wide tail or launch gap between queries.
-    for (int qi = 0; qi < a.n_queries; qi++) {
+    // (G > 1: qi is the group's first query; slot x of the group holds query min(qi + x, n_queries - 1) -- the idle
+    // slots of the launch's last group score its last query again and write no lists)
+    for (int qi = 0; qi < a.n_queries; qi += G) {
     if (qi) __syncthreads();  // the previous query's lists have been merged
-    {   // stage the query into LDS (it is L2-resident after the first block)
+    auto slot_query = [&](int x) -> int { return G == 1 ? qi : min(qi + x, a.n_queries - 1); };
+#pragma unroll
+    for (int x = 0; x < G; x++) {   // stage the query into LDS (it is L2-resident after the first block)
         const uint4 *src = reinterpret_cast<const uint4 *>(
-            reinterpret_cast<const uint8_t *>(a.query) + (size_t)qi * a.query_stride);
-        uint4 *dst = reinterpret_cast<uint4 *>(smem);
+            reinterpret_cast<const uint8_t *>(a.query) + (size_t)slot_query(x) * a.query_stride);
+        uint4 *dst = reinterpret_cast<uint4 *>(smem + x * qbytes);
         for (int i = tid; i < qbytes / 16; i += blockDim.x) dst[i] = src[i];
     }
-    WaveList wl;
-    wl.init(mylist, COLLECT ? 0 : a.kp, lane);
+    WaveList wls[G];
+    QConst qcs[G];
+#pragma unroll
+    for (int x = 0; x < G; x++) {
+        wls[x].init(mylist + (size_t)x * nwaves * a.kp, COLLECT ? 0 : a.kp, lane);
+        const int q = slot_query(x);
+        qcs[x] = QConst{a.qscale[q], a.qconst[q], a.qnorm2[q], (float)a.norm_bias};
+    }
+    [[maybe_unused]] WaveList &wl = wls[0];
+    [[maybe_unused]] const QConst &qc = qcs[0];
     __syncthreads();
     const uint64_t *allow_bits = a.allow_bits ? a.allow_bits + (size_t)qi * a.allow_stride : nullptr;
-    const QConst qc{a.qscale[qi], a.qconst[qi], a.qnorm2[qi], (float)a.norm_bias};
 
     // is the row of this lane's group at wave-row `row0` to be scanned?
     auto row_valid = [&](uint64_t row0) -> bool {
@@ -455,34 +542,48 @@ __global__ __launch_bounds__(256, SZG_MIN_BLOCKS) void scan_kernel(const ScanArg
     [[maybe_unused]] const float thr_key = COLLECT ? key_from_ordered(thr_ukey) : 0.0f;
     [[maybe_unused]] uint64_t *const cbuf = COLLECT ? a.collect_buf + (size_t)qi * a.collect_cap : nullptr;
     [[maybe_unused]] uint32_t *const ccount = COLLECT ? a.collect_count + (size_t)qi * kCandCountStride : nullptr;
-    auto finish_row = [&](uint64_t row0, bool valid, RowAcc<QBITS, METRIC> &acc) {
-        float key;
-        if constexpr (QBITS == 4 && LL != 0 && PP <= 12)
-            key = acc.template finish<true>(qc, grp_info, valid && lig == 0);
-        else
-            key = acc.finish(qc, grp_info, valid && lig == 0);
-        const bool leader = valid && lig == 0;
-        key = fminf(key, 3.0e38f);              // +inf (overflow) and NaN (minNum returns the number): worst finite
-        const bool maybe = leader && !(key > (COLLECT ? thr_key : wl.worst_key));
-        if (!__ballot(maybe)) return;
-        const uint32_t row = (uint32_t)(row0 + grp);
-        const uint64_t c = ((uint64_t)ordered_key(key) << 32) | row;
-
-        if (COLLECT) {
-            const bool hit = maybe && (uint32_t)(c >> 32) <= thr_ukey;
-            const uint64_t m = __ballot(hit);
-            if (m) {
-                const int first = __ffsll((long long)m) - 1;
-                uint32_t base = 0;
-                if (lane == first) base = atomicAdd(ccount, (uint32_t)__popcll(m));
-                base = __shfl(base, first);
-                if (hit) {
-                    const uint32_t idx = base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-                    if (idx < a.collect_cap) cbuf[idx] = c;
-                }
+    auto finish_row = [&](uint64_t row0, bool valid, Acc &acc) {
+        if constexpr (G > 1) {  // one norm for the row, then each query of the group: its key, its pre-filter, its list
+            const bool leader = valid && lig == 0;
+            const float norm = acc.finish_norm(qcs[0], grp_info);
+            const uint32_t row = (uint32_t)(row0 + grp);
+#pragma unroll
+            for (int x = 0; x < G; x++) {
+                float key = acc.finish_key(x, norm, qcs[x], grp_info);
+                key = fminf(key, 3.0e38f);
+                const bool maybe = leader && !(key > wls[x].worst_key);
+                if (!__ballot(maybe)) continue;
+                wls[x].offer(maybe, ((uint64_t)ordered_key(key) << 32) | row, lane);
             }
         } else {
-            wl.offer(maybe, c, lane);
+            float key;
+            if constexpr (QBITS == 4 && LL != 0 && PP <= 12)
+                key = acc.template finish<true>(qc, grp_info, valid && lig == 0);
+            else
+                key = acc.finish(qc, grp_info, valid && lig == 0);
+            const bool leader = valid && lig == 0;
+            key = fminf(key, 3.0e38f);              // +inf (overflow) and NaN (minNum returns the number): worst finite
+            const bool maybe = leader && !(key > (COLLECT ? thr_key : wl.worst_key));
+            if (!__ballot(maybe)) return;
+            const uint32_t row = (uint32_t)(row0 + grp);
+            const uint64_t c = ((uint64_t)ordered_key(key) << 32) | row;
+
+            if (COLLECT) {
+                const bool hit = maybe && (uint32_t)(c >> 32) <= thr_ukey;
+                const uint64_t m = __ballot(hit);
+                if (m) {
+                    const int first = __ffsll((long long)m) - 1;
+                    uint32_t base = 0;
+                    if (lane == first) base = atomicAdd(ccount, (uint32_t)__popcll(m));
+                    base = __shfl(base, first);
+                    if (hit) {
+                        const uint32_t idx = base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+                        if (idx < a.collect_cap) cbuf[idx] = c;
+                    }
+                }
+            } else {
+                wl.offer(maybe, c, lane);
+            }
         }
     };
 
@@ -495,7 +596,7 @@ __global__ __launch_bounds__(256, SZG_MIN_BLOCKS) void scan_kernel(const ScanArg
     // counted s_waitcnt vmcnt(D-1) instead of draining the queue.
     u32x4 ring[D];
     const uint64_t n_it = row_first < a.n_rows ? (a.n_rows - row_first + stride - 1) / stride : 0;
-    RowAcc<QBITS, METRIC> acc;
+    Acc acc;
     acc.reset();
 
 // prologue (fill the ring), steady state (every slot consumed is re-issued), drain
@@ -642,7 +743,7 @@ __global__ __launch_bounds__(256, SZG_MIN_BLOCKS) void scan_kernel(const ScanArg
 #define SZG_DN_CONSUME(u)                                                               \
     {                                                                                   \
         const u32x4 v_ = ring[u];                                                       \
-        if constexpr (RowAcc<QBITS, METRIC>::kPrefetch)                                 \
+        if constexpr (Acc::kPrefetch)                                                   \
             acc.piece_pf(make_uint4(v_.x, v_.y, v_.z, v_.w), smem, cp + 1 == P ? lig : jc + L, r16); \
         else                                                                            \
             acc.piece(make_uint4(v_.x, v_.y, v_.z, v_.w), smem, jc, r16, a.dim);        \
@@ -775,14 +876,18 @@ __global__ __launch_bounds__(256, SZG_MIN_BLOCKS) void scan_kernel(const ScanArg
     if (COLLECT) continue;
 
     // block-wide k-select over the waves' lists
-    wl.flush(lane);
+#pragma unroll
+    for (int x = 0; x < G; x++) wls[x].flush(lane);
     __syncthreads();
-    block_merge_lists(lists, nwaves, a.kp, a.block_lists + ((size_t)qi * gridDim.x + blockIdx.x) * a.kp,
-                      tid, blockDim.x);
+#pragma unroll
+    for (int x = 0; x < G; x++)
+        if (qi + x < a.n_queries)  // (block-uniform)
+            block_merge_lists(lists + (size_t)x * nwaves * a.kp, nwaves, a.kp,
+                              a.block_lists + ((size_t)(qi + x) * gridDim.x + blockIdx.x) * a.kp, tid, blockDim.x);
     // gfx9 counts loads and stores in one vmcnt and retires them out of order with respect
     // to each other: with the list stores above possibly pending at the top of the next
     // query's sweep, every ring wait would have to be vmcnt(0) -- which also waits for the
-    // load just issued.  Drain here, once per query, so the ring gets counted waits.
+    // load just issued.  Drain here, once per query (group), so the ring gets counted waits.
     __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0); expcnt, lgkmcnt untouched
     }  // for qi
 }
@@ -1018,35 +1123,34 @@ constexpr int kRingShort = 4, kRingDeep = 8;
 
 #if SZG_QBITS != 0
 
-template <int QBITS, int METRIC, bool COLLECT, int LL, int PP, int D>
+template <int QBITS, int METRIC, bool COLLECT, int LL, int PP, int D, int G = 1>
 hipError_t launch_shaped(const ScanArgs &a, bool nt, dim3 g, dim3 b, size_t lds, hipStream_t stream)
 {
     if (nt)
-        hipLaunchKernelGGL((scan_kernel<QBITS, METRIC, D, COLLECT, false, true, LL, PP>), g, b, lds, stream, a);
+        hipLaunchKernelGGL((scan_kernel<QBITS, METRIC, D, COLLECT, false, true, LL, PP, G>), g, b, lds, stream, a);
     else
-        hipLaunchKernelGGL((scan_kernel<QBITS, METRIC, D, COLLECT, false, false, LL, PP>), g, b, lds, stream, a);
+        hipLaunchKernelGGL((scan_kernel<QBITS, METRIC, D, COLLECT, false, false, LL, PP, G>), g, b, lds, stream, a);
     return hipGetLastError();
 }
 
-template <int QBITS, int METRIC, bool COLLECT, bool MASKED, int D>
+template <int QBITS, int METRIC, bool COLLECT, bool MASKED, int D, int G = 1>
 hipError_t launch_any_shape(const ScanArgs &a, bool nt, dim3 g, dim3 b, size_t lds, hipStream_t stream)
 {
     if (nt)  // whole lines per load instruction: stream past the caches
-        hipLaunchKernelGGL((scan_kernel<QBITS, METRIC, D, COLLECT, MASKED, true>), g, b, lds, stream, a);
+        hipLaunchKernelGGL((scan_kernel<QBITS, METRIC, D, COLLECT, MASKED, true, 0, 0, G>), g, b, lds, stream, a);
     else
-        hipLaunchKernelGGL((scan_kernel<QBITS, METRIC, D, COLLECT, MASKED, false>), g, b, lds, stream, a);
+        hipLaunchKernelGGL((scan_kernel<QBITS, METRIC, D, COLLECT, MASKED, false, 0, 0, G>), g, b, lds, stream, a);
     return hipGetLastError();
 }
 
-template <int QBITS, int METRIC, bool COLLECT, bool MASKED>
-hipError_t launch_scan_qmcm(const ScanArgs &a, int grid, int block, size_t lds, hipStream_t stream)
+// the kernels of group size G (scan_variant's choice; G > 1 exists for unmasked 8-bit top-k sweeps with the short ring)
+template <int QBITS, int METRIC, bool COLLECT, bool MASKED, int G>
+hipError_t launch_scan_group(const ScanArgs &a, const ScanVariant &v, dim3 g, dim3 b, size_t lds, hipStream_t stream)
 {
-    const dim3 g(grid), b(block);
-    const ScanVariant v = scan_variant(QBITS, a.map, a.tiled != 0, a.kp, COLLECT, MASKED, a.ring, a.no_shape_kernels != 0);
     if constexpr (!MASKED) {
 #define SZG_TRY_SHAPE(l, p, d)                                                                 \
     if (v.shaped == l * 100 + p)                                                               \
-        return launch_shaped<QBITS, METRIC, COLLECT, l, p, SZG_SHAPE_RING(d)>(a, v.nontemporal != 0, g, b, lds, stream);
+        return launch_shaped<QBITS, METRIC, COLLECT, l, p, SZG_SHAPE_RING(d), G>(a, v.nontemporal != 0, g, b, lds, stream);
         if constexpr (QBITS == 4) {
             SZG_SHAPES_4(SZG_TRY_SHAPE)
         } else if constexpr (QBITS == 8) {
@@ -1061,28 +1165,40 @@ hipError_t launch_scan_qmcm(const ScanArgs &a, int grid, int block, size_t lds, 
 #undef SZG_TRY_SHAPE
     }
     if (v.shaped) return hipErrorInvalidValue;  // (scan_variant named a kernel this unit does not carry)
-    if (v.deep) return launch_any_shape<QBITS, METRIC, COLLECT, MASKED, kRingDeep>(a, v.nontemporal != 0, g, b, lds, stream);
-    return launch_any_shape<QBITS, METRIC, COLLECT, MASKED, kRingShort>(a, v.nontemporal != 0, g, b, lds, stream);
+    if constexpr (G == 1) {
+        if (v.deep)
+            return launch_any_shape<QBITS, METRIC, COLLECT, MASKED, kRingDeep>(a, v.nontemporal != 0, g, b, lds, stream);
+    } else if (v.deep) {
+        return hipErrorInvalidValue;
+    }
+    return launch_any_shape<QBITS, METRIC, COLLECT, MASKED, kRingShort, G>(a, v.nontemporal != 0, g, b, lds, stream);
+}
+
+template <int QBITS, int METRIC, bool COLLECT, bool MASKED>
+hipError_t launch_scan_qmcm(const ScanArgs &a, int grid, int block, hipStream_t stream)
+{
+    const dim3 g(grid), b(block);
+    const ScanVariant v = scan_variant(QBITS, a.map, a.tiled != 0, a.kp, COLLECT, MASKED, a.ring, a.no_shape_kernels != 0,
+                                       a.group, a.n_queries, block);
+    const size_t lds = scan_lds_bytes(QBITS, a.map, COLLECT ? 0 : a.kp, block, v.group);
+    if constexpr (QBITS == 8 && !COLLECT && !MASKED) {
+        if (v.group == 4) return launch_scan_group<QBITS, METRIC, COLLECT, MASKED, 4>(a, v, g, b, lds, stream);
+        if (v.group == 2) return launch_scan_group<QBITS, METRIC, COLLECT, MASKED, 2>(a, v, g, b, lds, stream);
+    }
+    if (v.group != 1) return hipErrorInvalidValue;
+    return launch_scan_group<QBITS, METRIC, COLLECT, MASKED, 1>(a, v, g, b, lds, stream);
 }
 
 template <int QBITS, int METRIC>
-hipError_t launch_scan_qm(const ScanArgs &a, int grid, int block, size_t lds, hipStream_t stream)
+hipError_t launch_scan_qm(const ScanArgs &a, int grid, int block, hipStream_t stream)
 {
-    const bool masked = a.live_bits != nullptr || a.allow_bits != nullptr;
+    const bool masked = scan_masked(a);
     if (a.collect) {
-        if (masked) return launch_scan_qmcm<QBITS, METRIC, true, true>(a, grid, block, lds, stream);
-        return launch_scan_qmcm<QBITS, METRIC, true, false>(a, grid, block, lds, stream);
+        if (masked) return launch_scan_qmcm<QBITS, METRIC, true, true>(a, grid, block, stream);
+        return launch_scan_qmcm<QBITS, METRIC, true, false>(a, grid, block, stream);
     }
-    if (masked) return launch_scan_qmcm<QBITS, METRIC, false, true>(a, grid, block, lds, stream);
-    return launch_scan_qmcm<QBITS, METRIC, false, false>(a, grid, block, lds, stream);
-}
-
-template <int QBITS>
-hipError_t launch_scan_q(int metric, const ScanArgs &a, int grid, int block, size_t lds,
-                         hipStream_t stream)
-{
-    if (metric == kCosine) return launch_scan_qm<QBITS, kCosine>(a, grid, block, lds, stream);
-    return launch_scan_qm<QBITS, kEuclidean>(a, grid, block, lds, stream);
+    if (masked) return launch_scan_qmcm<QBITS, METRIC, false, true>(a, grid, block, stream);
+    return launch_scan_qmcm<QBITS, METRIC, false, false>(a, grid, block, stream);
 }
 
 #endif  // SZG_QBITS != 0
@@ -1099,14 +1215,14 @@ hipError_t launch_scan_q(int metric, const ScanArgs &a, int grid, int block, siz
 #error "kernels_scan.hip with SZG_QBITS needs SZG_SCAN_METRIC (0 or 1)"
 #endif
 hipError_t SZG_CAT(SZG_CAT(launch_scan_q, SZG_QBITS), SZG_CAT(m, SZG_SCAN_METRIC))(const ScanArgs &a, int grid, int block,
-                                                                                 size_t lds, hipStream_t stream)
+                                                                                 hipStream_t stream)
 {
-    return launch_scan_qm<SZG_QBITS, SZG_SCAN_METRIC>(a, grid, block, lds, stream);
+    return launch_scan_qm<SZG_QBITS, SZG_SCAN_METRIC>(a, grid, block, stream);
 }
 #else
 #define SZG_DECL_SCAN(q)                                                          \
-    hipError_t launch_scan_q##q##m0(const ScanArgs &, int, int, size_t, hipStream_t); \
-    hipError_t launch_scan_q##q##m1(const ScanArgs &, int, int, size_t, hipStream_t);
+    hipError_t launch_scan_q##q##m0(const ScanArgs &, int, int, hipStream_t); \
+    hipError_t launch_scan_q##q##m1(const ScanArgs &, int, int, hipStream_t);
 SZG_DECL_SCAN(4)
 SZG_DECL_SCAN(8)
 SZG_DECL_SCAN(16)
@@ -1117,7 +1233,7 @@ SZG_DECL_SCAN(64)
 // The instantiation a launch takes.  Row-shape kernels serve unmasked sweeps over dense maps whose lists stay in
 // registers; everything else is the any-shape kernel, with the deep ring when the lists live in LDS (kp > 64).
 ScanVariant scan_variant(int qbits, const RowMap &m, bool tiled, int kp, bool collect, bool masked, int ring,
-                         bool no_shape_kernels)
+                         bool no_shape_kernels, int group, int n_queries, int block)
 {
     ScanVariant v{};
     v.deep = ((!collect && kp > 64) || ring >= 8) ? 1 : 0;
@@ -1138,23 +1254,40 @@ ScanVariant scan_variant(int qbits, const RowMap &m, bool tiled, int kp, bool co
         }
 #undef SZG_IS_SHAPE
     }
+    // Queries scored per row read (option scan_group; 0 = kScanGroupAuto): 8-bit top-k sweeps without masks whose lists
+    // stay in registers (v.deep: kp > 64, or the deep ring asked for).  No larger than the launch can fill -- 1 query
+    // takes G = 1, 2 take G = 2 -- and than fits 64 KiB of LDS beside the block's lists.
+    v.group = 1;
+    if (qbits == 8 && !collect && !masked && !v.deep) {
+        int g = group == 0 ? kScanGroupAuto : group;
+        if (g != 2 && g != 4) g = 1;
+        while (g > 1 && g / 2 >= n_queries) g /= 2;
+        while (g > 1 && scan_lds_bytes(qbits, m, kp, block, g) > 64u * 1024u) g /= 2;
+        v.group = g;
+    }
     return v;
 }
 
-size_t scan_lds_bytes(int qbits, const RowMap &m, int kp, int block)
+size_t scan_lds_bytes(int qbits, const RowMap &m, int kp, int block, int group)
 {
-    // query image + per-wave candidate lists + per-wave lists of row steps that survive the masks
-    return query_lds_bytes(qbits, m.r16) + (size_t)(block / kWave) * kp * sizeof(uint64_t) +
+    // per query of a group: query image + per-wave candidate lists; per-wave lists of row steps that survive the masks
+    return (size_t)group * (query_lds_bytes(qbits, m.r16) + (size_t)(block / kWave) * kp * sizeof(uint64_t)) +
            (size_t)(block / kWave) * kStepList * sizeof(uint32_t);
+}
+
+int scan_passes(int qbits, const ScanArgs &a, int block)
+{
+    const ScanVariant v = scan_variant(qbits, a.map, a.tiled != 0, a.kp, a.collect != 0, scan_masked(a), a.ring,
+                                       a.no_shape_kernels != 0, a.group, a.n_queries, block);
+    return (a.n_queries + v.group - 1) / v.group;
 }
 
 hipError_t launch_scan(int qbits, int metric, const ScanArgs &a, int grid, int block,
                        hipStream_t stream)
 {
-    const size_t lds = scan_lds_bytes(qbits, a.map, a.collect ? 0 : a.kp, block);
     static_assert(kEuclidean == 0 && kCosine == 1, "the scan objects are named by the metric's number");
 #define SZG_CASE_SCAN(q)                                                                                            \
-    case q: return metric == kCosine ? launch_scan_q##q##m1(a, grid, block, lds, stream) : launch_scan_q##q##m0(a, grid, block, lds, stream);
+    case q: return metric == kCosine ? launch_scan_q##q##m1(a, grid, block, stream) : launch_scan_q##q##m0(a, grid, block, stream);
     switch (qbits) {
     SZG_CASE_SCAN(4)
     SZG_CASE_SCAN(8)

@@ -472,4 +472,34 @@ int szg_debug_scan_plan(int dim, int quant_bits, uint64_t n_rows, int kp, int co
     return SZG_OK;
 }
 
+// test hook, host only: the groups a one-sweep call forms (scan_variant's choice per launch, scan_lds_bytes, and the pass
+// count launch_scans_chained adds to szg_stats.scan_bytes)
+int szg_debug_scan_group(int dim, int quant_bits, int kp, int collect, int masked, int scan_group, int n_queries,
+                         int queries_per_launch, int32_t *group, uint64_t *lds_bytes, int32_t *passes)
+{
+    if (!group || !lds_bytes || !passes) return fail(SZG_E_INVALID, "null argument");
+    if (kp < 0 || n_queries < 1 || queries_per_launch < 1 || queries_per_launch > szg::kMaxSweepsPerLaunch)
+        return fail(SZG_E_INVALID, "kp, n_queries or queries_per_launch out of range");
+    if (scan_group != 0 && scan_group != 1 && scan_group != 2 && scan_group != 4)
+        return fail(SZG_E_INVALID, "scan_group is 0, 1, 2 or 4");
+    RowFormat f;
+    const int rc = row_format(dim, quant_bits, &f);
+    if (rc == SZG_E_UNSUPPORTED) return fail(rc, "dimension too large for the LDS-resident query");
+    if (rc) return rc;
+    const int list_kp = collect ? 0 : kp;
+    const LaunchGeom g = scan_geometry(quant_bits, f.map, f.row_bytes, f.layout.tiled != 0, 1u << 22, 256, list_kp);
+    *passes = 0;
+    for (int j = 0; j < n_queries; j += queries_per_launch) {
+        const int n = std::min(queries_per_launch, n_queries - j);
+        const szg::ScanVariant v = szg::scan_variant(quant_bits, f.map, f.layout.tiled != 0, list_kp, collect != 0, masked != 0,
+                                                     szg_index::ring, !szg_index::shape_kernels, scan_group, n, g.block);
+        if (j == 0) {
+            *group = v.group;
+            *lds_bytes = szg::scan_lds_bytes(quant_bits, f.map, list_kp, g.block, v.group);
+        }
+        *passes += (n + v.group - 1) / v.group;
+    }
+    return SZG_OK;
+}
+
 }  // extern "C"

@@ -681,6 +681,9 @@ int szg_set_option(szg_index *ix, const char *name, int64_t value)
         if (value < 1 || value > szg::kMaxSweepsPerLaunch)
             return fail(SZG_E_INVALID, "queries_per_launch out of range");
         ix->queries_per_launch = (int)value;
+    } else if (n == "scan_group") {
+        if (value != 0 && value != 1 && value != 2 && value != 4) return fail(SZG_E_INVALID, "scan_group is 0, 1, 2 or 4");
+        ix->scan_group = (int)value;
     } else if (n == "query_batch") {
         if (value < 1 || value > kMaxBatch) return fail(SZG_E_INVALID, "query_batch out of range");
         ix->query_batch = (int)value;

@@ -430,6 +430,8 @@ struct szg_index {
     int finish_thread = 1;    // shared-sweep calls of 3+ batches: a second host thread assembles the finished batches
                               // while the caller's prepares and enqueues the next ones (0 = one thread does both)
     int queries_per_launch = 16;  // sweeps one scan launch walks back to back (query-major)
+    int scan_group = 0;       // queries of a launch the one-sweep kernel scores per row read, where the launch qualifies
+                              // (8-bit rows, top-k, no masks, lists in registers): 0 = automatic, 1, 2 or 4
     int tie_mode = 0;         // 0: exact full replay on ties/NaN, 1: keep the fast answer
     int serialize_scans = 1;  // scan launches of a shard never overlap each other
     int multi_query = 1;      // share one sweep between the queries of a batch (MFMA path)

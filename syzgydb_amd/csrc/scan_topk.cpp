@@ -138,6 +138,7 @@ void fill_scan_args(const szg_index *ix, const Shard *sh, const Ctx *c, bool has
     a->norm_bias = ix->norm_bias;
     a->no_shape_kernels = ix->shape_kernels ? 0 : 1;
     a->ring = ix->ring;
+    a->group = ix->scan_group;
 }
 
 // Launch the fused scan for each of the batch's queries (n = a->size()) as the
@@ -154,8 +155,9 @@ int launch_scans_chained(szg_index *ix, Shard *sh, Ctx *c, const std::vector<szg
     });
     if (rc) return rc;
     std::lock_guard<std::mutex> lk(ix->stats_mu);
-    uint64_t sweeps = 0;
-    for (const szg::ScanArgs &x : a) sweeps += (uint64_t)x.n_queries;
+    uint64_t sweeps = 0;  // passes over the rows: one per group of a launch's queries (one per query where the launch
+                          // does not qualify for groups)
+    for (const szg::ScanArgs &x : a) sweeps += (uint64_t)szg::scan_passes(ix->bits, x, g.block);
     ix->stats.scan_launches += n;
     ix->stats.scan_bytes += sweeps * sh->n_rows * (uint64_t)ix->row_bytes;
     return SZG_OK;

@@ -442,6 +442,17 @@ def f64_probe(op, a, b=None):
     return out
 
 
+def scan_group_plan(dim, quant_bits, n_queries, kp=10, scan_group=0, queries_per_launch=16, collect=False, masked=False):
+    """Host-only test hook: how a one-sweep call of n_queries queries forms groups under option scan_group -- the group
+    size and LDS bytes of its first launch and the passes over the rows of the whole call."""
+    L = _lib.load()
+    g, lds, passes = ctypes.c_int32(), ctypes.c_uint64(), ctypes.c_int32()
+    check(L.szg_debug_scan_group(int(dim), int(quant_bits), int(kp), int(bool(collect)), int(bool(masked)), int(scan_group),
+                                 int(n_queries), int(queries_per_launch), ctypes.byref(g), ctypes.byref(lds),
+                                 ctypes.byref(passes)), "szg_debug_scan_group")
+    return {"group": g.value, "lds_bytes": lds.value, "passes": passes.value}
+
+
 def scan_plan(dim, quant_bits, n_rows, kp=10, collect=False, masked=False, cu_count=0):
     """Host-only test hook (no device needed): the lane map, launch geometry and kernel variant of a one-sweep scan
     over n_rows rows, as a dict of szg_scan_plan's fields.  Raises SzgError as szg_index_create would."""
