@@ -1,12 +1,17 @@
 #!/bin/bash
-# Register / scratch / LDS use of every kernel of one shared-sweep part (or a scan part):
-#   scripts/kernel_resources.sh mq 2          -> kernels_mq.hip -DSZG_MQ_PART=2 (the 4-bit int8 sweeps)
+# Register / scratch / LDS use of every kernel of one object of the build:
+#   scripts/kernel_resources.sh mq i8 4       -> kernels_mq_i8.hip -DSZG_ROW_BITS=4 (the 4-bit int8 sweeps)
+#   scripts/kernel_resources.sh mq bf16 32    -> kernels_mq_bf16.hip -DSZG_ROW_BITS=32    (also: mq bf16d)
+#   scripts/kernel_resources.sh mq select     -> kernels_mq.hip (the selection kernels)
 #   scripts/kernel_resources.sh scan 32       -> kernels_scan.hip -DSZG_QBITS=32
 # (hipcc -Rpass-analysis=kernel-resource-usage, device code only; no GPU needed)
 set -euo pipefail
 cd "$(dirname "$0")/../syzgydb_amd/csrc"
-kind=${1:-mq}; part=${2:-2}
-if [ "$kind" = mq ]; then src=kernels_mq.hip; def=-DSZG_MQ_PART=$part; else src=kernels_scan.hip; def=-DSZG_QBITS=$part; fi
+kind=${1:-mq}; part=${2:-i8}
+if [ "$kind" = scan ]; then src=kernels_scan.hip; def=-DSZG_QBITS=$part
+elif [ "$part" = select ]; then src=kernels_mq.hip; def=
+elif [ "$part" = bf16d ]; then src=kernels_mq_bf16d.hip; def=
+else src=kernels_mq_$part.hip; def=-DSZG_ROW_BITS=${3:?row width}; fi
 /opt/rocm/bin/hipcc -O3 -std=c++17 --offload-arch=gfx950 $def ${VFLAGS:-} --cuda-device-only -c $src -o /dev/null \
     -Rpass-analysis=kernel-resource-usage 2>&1 | python3 -c '
 import re, sys

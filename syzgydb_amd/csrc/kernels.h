@@ -172,9 +172,10 @@ size_t scan_lds_bytes(int qbits, const RowMap &m, int kp, int block, int group =
 
 // Merge n_lists sorted lists of kp candidates into ceil(n_lists/merge_fan(kp)) lists.
 int merge_fan(int kp);
-// ---- multi-query sweep (kernels_mq.hip): 4/8/16/32-bit rows, cosine -------------
-// queries per shared sweep: 48 (3 blocks of 16) for the float32 and int8 sweeps, whose LDS images are
-// 4 and 2-4 bytes per element and query; 96 for the bfloat16 sweep (2 bytes)
+// ---- shared (multi-query) sweeps (mq_device.h, kernels_mq*.hip): every row width, cosine and Euclidean ----------
+// queries per shared sweep: 48 (3 blocks of 16) for the int8 sweeps (4- and 8-bit rows), whose LDS images are 2-4
+// bytes per element and query; 96 for the bfloat16 sweeps (16-, 32- and 64-bit rows, and 8-bit rows in batches of
+// more than 48 top-k queries): 2 bytes
 constexpr int kMqMaxQueries = 96;
 struct MqArgs {
     const uint8_t *rows;      // resident mirror
@@ -211,8 +212,6 @@ struct MqArgs {
                                  // sweep then sums its own) and 8-/4-bit rows (the shape kernels REQUIRE them; without,
                                  // the any-shape kernel runs)
 };
-// thr[q] = key of the kp-th entry of query q's sorted list (3.0e38 if the list is shorter)
-hipError_t launch_mq_thr(const uint64_t *lists, int kp, int n_queries, float *thr, hipStream_t stream);
 // per query: the kp best of its candidate buffer, sorted, as one list [n_queries][kp]
 hipError_t launch_cand_select(const uint64_t *cand_buf, const uint32_t *cand_count, uint32_t cand_cap,
                               int kp, int n_queries, uint64_t *lists, hipStream_t stream);
@@ -233,7 +232,7 @@ hipError_t launch_cand_rescore(int metric, const uint8_t *rows, RowLayout layout
                                const double *qscale, uint64_t *cand_buf, const uint32_t *cand_count,
                                uint32_t cand_cap, int n_queries, int row_bits, hipStream_t stream);
 
-// Exact integer shared sweep for 8-bit rows (v_mfma_i32_16x16x64_i8).  MqArgs.queries is
+// Exact integer shared sweep for 8- and 4-bit rows, both metrics (v_mfma_i32_16x16x64_i8).  MqArgs.queries is
 // the image [64-byte step][digit plane h,m,l][query block][lane = chunk*16 + query][16 bytes]
 // of the queries' balanced int8 digit planes (prep_query), followed by the float table
 // [qscale | qconst | qnorm2][48]; MqArgs.norm_bias as ScanArgs.norm_bias.
@@ -242,13 +241,15 @@ hipError_t launch_cand_rescore(int metric, const uint8_t *rows, RowLayout layout
 // entries hold -15 * sum Q (n = 2x - 15).
 size_t mq_i8_image_bytes(int row_bits, int r16, int nb);   // digit image only
 size_t mq_i8_lds_bytes(int row_bits, int r16, int nb, int groups = 1);  // groups x (image + constants + thresholds) + hit buffers
-hipError_t launch_mq_score_i8(int row_bits, const MqArgs &a, int nb, int grid, hipStream_t stream);
-// bfloat16 shared sweep for 32-bit rows of whole 64-byte steps (v_mfma_f32_16x16x32_bf16): MqArgs.queries is the
-// image [32-element step][query block][lane = k-group*16 + query][8 bf16 = elements 8*k-group + 0..7 of the step]
-// (zeros where the row has ended).
+hipError_t launch_mq_score_i8(int row_bits, const MqArgs &a, int nb, int grid, hipStream_t stream);  // nb = 1..3
+// bfloat16 shared sweep, both metrics (v_mfma_f32_16x16x32_bf16): 64-, 32- and 16-bit rows of any dimension in the
+// row-major layout (16-bit rows with resident norms take the direct form, without them the LDS-staged one), and tiled
+// 8-bit rows (whole 64-byte steps; needs MqArgs::row_norm and qsum).  MqArgs.queries is the image
+// [32-element step][query block][lane = k-group*16 + query][8 bf16 = elements 8*k-group + 0..7 of the step]
+// (zeros where the row has ended).  Its keys only rank: launch_cand_refine / launch_cand_rescore score again.
 size_t mq_bf16_image_bytes(int row_bits, int r16, int nb);
 size_t mq_bf16_lds_bytes(int row_bits, int r16, int nb);
-hipError_t launch_mq_score_bf16(int row_bits, const MqArgs &a, int nb, int grid, hipStream_t stream);  // 64-, 32- or 16-bit rows
+hipError_t launch_mq_score_bf16(int row_bits, const MqArgs &a, int nb, int grid, hipStream_t stream);  // nb = 1..6
 hipError_t launch_mq_select(const float *keys, size_t key_stride, uint32_t n_rows,
                             const uint64_t *live_bits, const uint64_t *allow_bits,
                             uint32_t allow_stride, int kp, int n_queries, int blocks_per_query,

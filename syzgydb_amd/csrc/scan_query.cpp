@@ -244,7 +244,7 @@ double key_eps(const szg_index *ix, double key, const QMeta &m)
 // ---- shared sweeps: B queries share one pass of the corpus ------------
 
 // 8-bit rows in whole 64-byte steps (the tiled layout) through the bfloat16 sweep -- their codes are exact in bfloat16,
-// 96 queries share a pass instead of 48 (kernels_mq.hip, part 108).  SZG_BF16_8BIT=0 keeps them on the int8 sweep.
+// 96 queries share a pass instead of 48 (kernels_mq_bf16d.hip: mq_score_bf16d8_kernel).  SZG_BF16_8BIT=0 keeps them on the int8 sweep.
 static bool bf16_takes_8bit(const szg_index *ix, bool radius, int nq)
 {
     if (radius || nq <= 48) return false;  // (a radius IS the threshold: the band of the rounded query would be collected too)
