@@ -348,12 +348,116 @@ func (m *gpuMirror) ensureFresh(c *Collection, alsoOrder bool) bool {
 	}
 	m.mu.Lock()
 	defer m.mu.Unlock()
+	if !m.dirty && alsoOrder && m.orderStale && m.repageOnDevice() {
+		return true // the lazy re-page: the rows were reordered on the card, nothing went through the host
+	}
 	if m.dirty || (alsoOrder && m.orderStale) {
 		if err := m.reload(c); err != nil {
 			return false
 		}
 	}
 	return true
+}
+
+// repageOnDevice puts the live rows into sort.Strings order of their ids with szg_index_reorder: the rows
+// move on the card instead of being reloaded from the spanfile.  Tombstoned rows are dropped on the way.  Called with
+// m.mu locked for writing.  No mask is carried (the numbering changes arbitrarily).  false: nothing has changed, the
+// caller reloads.
+func (m *gpuMirror) repageOnDevice() bool {
+	type entry struct {
+		rid string
+		id  uint64
+		row uint64
+	}
+	live := make([]entry, 0, len(m.rowOf))
+	for id, row := range m.rowOf {
+		live = append(live, entry{strconv.FormatUint(id, 10), id, row})
+	}
+	sort.Slice(live, func(i, j int) bool { return live[i].rid < live[j].rid })
+	src := make([]C.uint64_t, len(live))
+	for i, e := range live {
+		src[i] = C.uint64_t(e.row)
+	}
+	var p *C.uint64_t
+	if len(src) > 0 {
+		p = &src[0]
+	}
+	if C.szg_index_reorder(m.h, p, C.uint64_t(len(src)), nil, 0) != C.SZG_OK {
+		return false
+	}
+	m.bump() // rows are renumbered: cached filter masks no longer apply (the library has made them stale)
+	m.ids = m.ids[:0]
+	m.rowOf = make(map[uint64]uint64, len(live))
+	m.lastID = ""
+	for i, e := range live {
+		m.ids = append(m.ids, e.id)
+		m.rowOf[e.id] = uint64(i)
+		m.lastID = e.rid
+	}
+	m.orderStale = false
+	return true
+}
+
+// compact drops the tombstoned rows from the card (szg_index_compact) and rewrites the row -> id table from the map
+// the library returns.  The live rows keep their order, so no answer changes; the sweeps read fewer bytes, the memory
+// is returned, and a mirror without tombstones is back on the unmasked launches.  Called under c.mutex.Lock (no
+// search is in flight) -- e.g. from removeDocument once the dead rows pass a share of the mirror, or from a
+// maintenance endpoint.  The cached masks of the current version are carried: renumbered on the card, they stay
+// valid, and their host words are read back.  Returns the rows dropped.
+func (m *gpuMirror) compact() (uint64, error) {
+	if m.dirty {
+		return 0, nil // the next search reloads everything anyway
+	}
+	before := uint64(C.szg_index_rows(m.h))
+	if before == uint64(C.szg_index_live_rows(m.h)) {
+		return 0, nil
+	}
+	maskCacheMu.Lock()
+	defer maskCacheMu.Unlock()
+	for _, mk := range m.retired { // (no search is in flight: retired masks can go now)
+		C.szg_mask_destroy(mk)
+	}
+	m.retired = nil
+	carry := make([]*C.szg_mask, 0, len(m.masks))
+	for key, e := range m.masks {
+		if e.version == m.version && e.mask != nil {
+			carry = append(carry, e.mask)
+		} else {
+			C.szg_mask_destroy(e.mask)
+			delete(m.masks, key)
+		}
+	}
+	var cp **C.szg_mask
+	if len(carry) > 0 {
+		cp = &carry[0]
+	}
+	newOfOld := make([]C.uint64_t, before)
+	var rows C.uint64_t
+	if rc := C.szg_index_compact(m.h, &newOfOld[0], &rows, cp, C.int(len(carry))); rc != C.SZG_OK {
+		return 0, fmt.Errorf("szg_index_compact: %s", C.GoString(C.szg_last_error()))
+	}
+	ids := make([]uint64, uint64(rows))
+	for old, nw := range newOfOld {
+		if uint64(nw) != ^uint64(0) {
+			ids[uint64(nw)] = m.ids[old]
+		}
+	}
+	m.ids = ids
+	m.rowOf = make(map[uint64]uint64, len(ids))
+	for row, id := range ids {
+		m.rowOf[id] = uint64(row)
+	}
+	m.version++ // the carried entries move to the new version with their rewritten words
+	words := (len(ids) + 63) / 64
+	for key, e := range m.masks {
+		e.version = m.version
+		e.bits = make([]C.uint64_t, words)
+		if words > 0 {
+			C.szg_mask_read(e.mask, &e.bits[0])
+		}
+		m.masks[key] = e
+	}
+	return before - uint64(rows), nil
 }
 
 // fullReplays reads the library's count of queries it re-answered by the exact replay in ROW order (equal

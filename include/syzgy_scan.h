@@ -155,7 +155,8 @@ int szg_search_radius_batch(szg_index *ix, const double *queries, int n_queries,
  *   bits, as ever).  szg_index_load, szg_index_synth and the appends -- which change the row count -- make every
  *   older mask of the handle STALE: a search or combine with a stale mask returns SZG_E_INVALID ("stale mask" in
  *   szg_last_error) and never reads past the mask; so does a mask of another handle.  Stale masks can still be read,
- *   counted and destroyed.
+ *   counted and destroyed.  szg_index_compact / szg_index_reorder rewrite the masks they are asked to carry and make
+ *   the others stale.
  * Lifetime and threads: masks are destroyed before their handle.  Any number of threads may search with one mask
  *   concurrently; create / combine / destroy may run beside searches that do not use that mask.
  * Coalescing: szg_search_topk_masked with ONE query goes through the combiner like szg_search_topk; callers that all
@@ -196,6 +197,43 @@ typedef struct szg_mask_stats {
     uint64_t shared_batches;  /* batches whose sweeps read ONE resident mask in place (no copy at all) */
 } szg_mask_stats;
 int szg_index_mask_stats(szg_index *ix, szg_mask_stats *out);   /* szg_reset_stats clears the three counters */
+
+/* ---- compaction and reorder on the device (added under ABI 4, additive) ------
+ *
+ * A tombstoned row keeps its bytes in device memory, is still read by every sweep, and its mere presence makes every
+ * launch of its shard a masked one (no grouped 8-bit sweep, no unmasked launch geometry).  These two calls renumber
+ * the resident rows without a trip through the host: one gather kernel copies the kept rows, 16 bytes per lane, into
+ * a NEW allocation sized for them, then the old one is freed -- so compaction gives device memory back, and the peak
+ * during the call is the old plus the new allocation (per shard).
+ *
+ * Both need exclusive access, like every mutation, and synchronise the handle's devices first.  Afterwards the handle
+ * is what a fresh one is after szg_index_load of the same rows in the same order: szg_index_rows ==
+ * szg_index_live_rows, no tombstones, shard ranges and capacities as a load gives them (appends go on working), row
+ * norms and the sketch rebuilt on the device by the next search that wants them.
+ * Masks: carry[0 .. n_carry) are masks of this handle that are not stale; their words are rewritten for the new
+ *   numbering on the device in the same call (new bit i = old bit of the row that became row i), count and
+ *   szg_mask_read follow, and they STAY VALID.  Every other mask of the handle becomes stale, as after
+ *   szg_index_load.  A null, foreign or stale entry in carry is SZG_E_INVALID.
+ * Failure: every check happens on the host before anything moves, and any error -- bad arguments, SZG_E_NOMEM from
+ *   the new allocation, a refused mask -- leaves rows, live bits, masks and the sketch exactly as they were.
+ * Handles of several shards move rows between devices through the shards' staging buffers, at most 64 MiB at a time:
+ *   two passes over the rows instead of one, at a cost that does not depend on how the list interleaves the shards.
+ *   The internal sketch index of a float32 handle is dropped with the old rows (its memory is returned too) and built
+ *   again by the next search that wants it.  Sharded-search communicators are unaffected.
+ */
+
+/* New row i = old row src_rows[i] (rows numbered as searches return them: local + row base); rows not listed are
+ * dropped.  Every listed row must be in range (else SZG_E_RANGE), live and listed once (else SZG_E_INVALID).
+ * n_rows == 0 empties the index. */
+int szg_index_reorder(szg_index *ix, const uint64_t *src_rows, uint64_t n_rows,
+                      szg_mask *const *carry, int n_carry);
+
+/* Drop the tombstoned rows, keeping the order of the live ones (the reference's visit order).
+ * out_new_of_old: nullable, szg_index_rows() entries before the call: the new number of each old row (+ row base),
+ * UINT64_MAX for a dropped one.  *out_rows (nullable) = rows afterwards.  No tombstones: returns SZG_OK, moves
+ * nothing, and no mask becomes stale. */
+int szg_index_compact(szg_index *ix, uint64_t *out_new_of_old, uint64_t *out_rows,
+                      szg_mask *const *carry, int n_carry);
 
 /*
  * The reference's float64 distance (c.distance, collection.go:596, :812-832) from
@@ -499,6 +537,15 @@ int szg_debug_scan_plan(int dim, int quant_bits, uint64_t n_rows, int kp, int co
  */
 int szg_debug_scan_group(int dim, int quant_bits, int kp, int collect, int masked, int scan_group, int n_queries,
                          int queries_per_launch, int32_t *group, uint64_t *lds_bytes, int32_t *passes);
+
+/*
+ * Test hook, host only: the checks szg_index_reorder makes on its list before anything moves, and the split of the
+ * new rows over n_shards shards -- the same code, the same return codes and error text.  live_words: ceil(n_rows / 64)
+ * words, bit r == 0 -> row r is tombstoned (NULL: every row is live); src_rows[0 .. n): the list (no row base);
+ * out_counts: nullable, n_shards entries.
+ */
+int szg_debug_reorder_plan(uint64_t n_rows, const uint64_t *live_words, const uint64_t *src_rows, uint64_t n,
+                           int n_shards, uint64_t *out_counts);
 
 #ifdef __cplusplus
 }

@@ -4,11 +4,15 @@
 #   scripts/kernel_resources.sh mq bf16 32    -> kernels_mq_bf16.hip -DSZG_ROW_BITS=32    (also: mq bf16d)
 #   scripts/kernel_resources.sh mq select     -> kernels_mq.hip (the selection kernels)
 #   scripts/kernel_resources.sh scan 32       -> kernels_scan.hip -DSZG_QBITS=32
+#   scripts/kernel_resources.sh exact         -> kernels_exact.hip (re-rank, page-in, row gather, ...)
+#   scripts/kernel_resources.sh mask          -> kernels_mask.hip (device-resident filter masks)
 # (hipcc -Rpass-analysis=kernel-resource-usage, device code only; no GPU needed)
 set -euo pipefail
 cd "$(dirname "$0")/../syzgydb_amd/csrc"
 kind=${1:-mq}; part=${2:-i8}
 if [ "$kind" = scan ]; then src=kernels_scan.hip; def=-DSZG_QBITS=$part
+elif [ "$kind" = exact ]; then src=kernels_exact.hip; def=-ffp-contract=off
+elif [ "$kind" = mask ]; then src=kernels_mask.hip; def=
 elif [ "$part" = select ]; then src=kernels_mq.hip; def=
 elif [ "$part" = bf16d ]; then src=kernels_mq_bf16d.hip; def=
 else src=kernels_mq_$part.hip; def=-DSZG_ROW_BITS=${3:?row width}; fi

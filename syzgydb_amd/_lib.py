@@ -38,8 +38,10 @@ EXPORTS = [
     # device-resident filter masks (added under ABI 4)
     "szg_mask_create", "szg_mask_create_rows", "szg_mask_combine", "szg_mask_count", "szg_mask_read",
     "szg_mask_destroy", "szg_search_topk_masked", "szg_search_radius_masked", "szg_index_mask_stats",
+    # compaction / reorder on the device (added under ABI 4)
+    "szg_index_reorder", "szg_index_compact",
     # host-only test hook
-    "szg_debug_scan_plan", "szg_debug_scan_group",
+    "szg_debug_scan_plan", "szg_debug_scan_group", "szg_debug_reorder_plan",
 ]
 SZG_MASK_AND, SZG_MASK_OR, SZG_MASK_ANDNOT, SZG_MASK_NOT = 0, 1, 2, 3
 SZG_COMM_ID_BYTES = 128
@@ -208,6 +210,13 @@ def load():
                                                ctypes.c_uint64, u64p]
         L.szg_index_mask_stats.restype = ctypes.c_int
         L.szg_index_mask_stats.argtypes = [vp, ctypes.POINTER(SzgMaskStats)]
+    if hasattr(L, "szg_index_reorder"):   # (as the masks: an older build for an A/B run cannot compact)
+        L.szg_index_reorder.restype = ctypes.c_int
+        L.szg_index_reorder.argtypes = [vp, u64p, ctypes.c_uint64, ctypes.POINTER(vp), ctypes.c_int]
+        L.szg_index_compact.restype = ctypes.c_int
+        L.szg_index_compact.argtypes = [vp, u64p, u64p, ctypes.POINTER(vp), ctypes.c_int]
+        L.szg_debug_reorder_plan.restype = ctypes.c_int
+        L.szg_debug_reorder_plan.argtypes = [ctypes.c_uint64, u64p, u64p, ctypes.c_uint64, ctypes.c_int, u64p]
     L.szg_comm_unique_id.restype = ctypes.c_int
     L.szg_comm_unique_id.argtypes = [u8p]
     L.szg_comm_create.restype = ctypes.c_int

@@ -66,7 +66,7 @@ class SearchArgs:
 
 
 class Collection:
-    def __init__(self, options: CollectionOptions, devices=None, sketch=None, strict_order=True):
+    def __init__(self, options: CollectionOptions, devices=None, sketch=None, strict_order=True, auto_compact=None):
         if options.Quantization == 0:
             options.Quantization = 64  # collection.go:254-256
         if options.DistanceMethod not in (Euclidean, Cosine):
@@ -82,6 +82,13 @@ class Collection:
             # 8-bit sketch pre-pass for lone Searches on float32 collections (same answers, +25 % device memory):
             # None = the library's default (automatic), True / False force it on / off
             self._index.set_option("sketch", 1 if sketch else 0)
+        # removeDocument only tombstones a row: its bytes stay on the card and are swept by every search until
+        # Compact() drops them.  auto_compact = a fraction f: removeDocument compacts by itself once the tombstoned
+        # rows exceed f of the mirror's rows; None (the default) = never
+        if auto_compact is not None and not 0.0 <= float(auto_compact) < 1.0:
+            raise ValueError("auto_compact is None or a fraction in [0, 1)")
+        self.auto_compact = None if auto_compact is None else float(auto_compact)
+        self.compactions = 0
         self._row_of = {}    # id -> row
         self._id_of = []     # row -> id (None once tombstoned)
         self._meta = []      # row -> metadata bytes
@@ -131,12 +138,13 @@ class Collection:
             self._last_idstr = s
 
     def _resort(self):
-        """Re-page the live rows in sorted decimal-string id order (reload of the mirror)."""
+        """Re-page the live rows in sorted decimal-string id order: the rows are reordered on the card
+        (ScanIndex.reorder), nothing travels through the host.  No mask is carried: the numbering changes
+        arbitrarily, and the version moves."""
         live = sorted((str(id), id, row) for id, row in self._row_of.items())
-        data = self._index.read_rows(0, self._index.rows) if self._index.rows else None
         rows = [row for _, _, row in live]
         new_meta = [self._meta[r] for r in rows]
-        self._index.load(data[rows] if rows else np.zeros((0, self._index.row_bytes), np.uint8))
+        self._index.reorder(np.asarray(rows, dtype=np.uint64))
         self._id_of = [id for _, id, _ in live]
         self._meta = new_meta
         self._row_of = {id: i for i, id in enumerate(self._id_of)}
@@ -207,6 +215,42 @@ class Collection:
         self._index.tombstone(row)
         self._id_of[row] = None
         self._meta[row] = b""
+        if self.auto_compact is not None:
+            rows = self._index.rows
+            if rows - self._index.live_rows > self.auto_compact * rows:
+                self.Compact()
+
+    def Compact(self) -> int:
+        """Drop the tombstoned rows from the card (not in the reference, whose spanfile reclaims space by itself):
+        the live rows keep their order, so answers do not change -- the sweeps read fewer bytes, the memory is
+        returned, and a shard without tombstones is back on the unmasked fast paths.  The cached filters of the
+        current version are carried: their device masks are renumbered on the card, so the next Search with one of
+        them costs neither an evaluation of the filter nor an upload.  Returns the rows dropped."""
+        dropped = self._index.rows - self._index.live_rows
+        if dropped == 0:
+            return 0
+        for old in [k for k in self._mask_cache if k[1] != self._version]:   # (as _mask_entry: never hit again)
+            m = self._mask_cache.pop(old)[2]
+            if m is not None:
+                m.close()
+        current = list(self._mask_cache.items())
+        new_of_old = self._index.compact(carry=[e[2] for _, e in current if e[2] is not None])
+        keep = np.flatnonzero(new_of_old != np.uint64(0xFFFFFFFFFFFFFFFF))   # the old row of every new row, ascending
+        n_old = len(self._id_of)
+        self._id_of = [self._id_of[r] for r in keep]
+        self._meta = [self._meta[r] for r in keep]
+        self._row_of = {id_: i for i, id_ in enumerate(self._id_of)}
+        self._version += 1
+        self._mask_cache = {}
+        for (key, _), (words, flt, mask) in current:
+            if mask is not None:
+                words = mask.read().reshape(1, -1)
+            else:   # host words only: the same selection with numpy
+                bits = np.unpackbits(np.ascontiguousarray(words).view(np.uint8), bitorder="little")[:n_old]
+                words = pack_allow_bits(bits[keep].astype(bool))
+            self._mask_cache[(key, self._version)] = [words, flt, mask]
+        self.compactions += 1
+        return dropped
 
     def GetDocumentCount(self) -> int:
         return len(self._row_of)

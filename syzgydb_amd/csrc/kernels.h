@@ -309,6 +309,12 @@ hipError_t launch_sketch_build(const uint8_t *src, RowLayout src_lay, int dim, u
 hipError_t launch_repack(int qbits, uint8_t *ref, uint32_t row_bytes, uint8_t *rows, RowLayout layout,
                          uint64_t first_row, uint64_t n_rows, int to_reference, hipStream_t stream);
 
+// Row gather (szg_index_compact / szg_index_reorder): row dst_first_row + i of `dst` = row list[i] of `src`, i < n, each
+// side in its own layout (linear or tiled, r16 16-byte pieces per row); list == nullptr: the identity -- the "place"
+// step from a linear stage into the resident layout.  No decode: a piece's bytes do not depend on its row's number.
+hipError_t launch_gather_rows(const uint8_t *src, RowLayout src_lay, uint8_t *dst, RowLayout dst_lay, uint32_t r16,
+                              const uint64_t *list, uint64_t n, uint64_t dst_first_row, hipStream_t stream);
+
 // Rows [dst_first_row, +n_rows) of the mirror directly in the resident layout: synthetic
 // (src == nullptr, see szg_index_synth; seed_first_row indexes the PRNG stream) or
 // quantized + packed from float64 vectors on the device.
@@ -342,5 +348,9 @@ struct MaskGatherTable {
     const uint64_t *src[kMqMaxQueries];
 };
 hipError_t launch_mask_gather(const MaskGatherTable &t, int n_queries, uint64_t *dst, uint64_t n_pairs, hipStream_t stream);
+// a mask carried across a compaction / reorder: bit i of new_words = bit list[i] of old_words, i < n; bits at
+// positions >= n of the n_pairs pairs are stored as 0 (list[i] < the rows old_words cover)
+hipError_t launch_mask_gather_rows(const uint64_t *old_words, const uint64_t *list, uint64_t n, uint64_t *new_words,
+                                   uint64_t n_pairs, hipStream_t stream);
 
 }  // namespace szg

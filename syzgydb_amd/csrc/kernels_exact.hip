@@ -9,6 +9,8 @@
 //    as encodeDocument/quantize (collection.go:713-743, quantization.go:5-23).
 //  * repack_kernel: page-in transform between the reference's big-endian
 //    element encoding and the resident little-endian, 16-byte-pitched layout.
+//  * gather_rows_kernel: rows copied piece by piece from one resident (or linear)
+//    layout into another, by a row list (compaction / reorder of the mirror).
 #include "kernels.h"
 
 #pragma clang fp contract(off)
@@ -483,6 +485,36 @@ __global__ void repack_vec_kernel(uint4 *ref, uint8_t *rows, RowLayout lay, uint
         *res = v;
 }
 
+// ---- row gather (compaction / reorder) ------------------------------------------
+// dst row dst_first_row + i = src row list[i] (list == nullptr: src row i), as 16-byte pieces, each in its own
+// layout.  The resident bytes of a piece do not depend on the row's number (repack_*_kernel and synth_kernel
+// address by piece_offset only; padding is zeros), so nothing is decoded.  Groups of G = 1 << g_shift lanes take one
+// row each, lane s of a group the pieces s, s + G, ...: consecutive lanes move consecutive pieces, whole 64-byte
+// segments of a tiled row.  The group's first lane reads list[i] and hands it to the others.
+__global__ __launch_bounds__(256) void gather_rows_kernel(const uint8_t *__restrict__ src, RowLayout src_lay,
+                                                          uint8_t *__restrict__ dst, RowLayout dst_lay, uint32_t r16,
+                                                          const uint64_t *__restrict__ list, uint64_t n,
+                                                          uint64_t dst_first_row, int g_shift)
+{
+    const uint32_t G = 1u << g_shift;
+    const uint32_t sub = threadIdx.x & (G - 1);
+    const uint64_t i = (uint64_t)blockIdx.x * (256u >> g_shift) + (threadIdx.x >> g_shift);
+    const bool have = i < n;
+    uint64_t from = i;
+    if (list) {
+        uint64_t v = 0;
+        if (have && sub == 0) v = list[i];
+        const int lead = (int)((threadIdx.x & 63u) & ~(G - 1));
+        const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)v, lead, 64);
+        const uint32_t hi = (uint32_t)__shfl((int)(uint32_t)(v >> 32), lead, 64);
+        from = ((uint64_t)hi << 32) | lo;
+    }
+    if (!have) return;
+    for (uint32_t j = sub; j < r16; j += G)
+        *reinterpret_cast<uint4 *>(dst + piece_offset(dst_lay, dst_first_row + i, j)) =
+            *reinterpret_cast<const uint4 *>(src + piece_offset(src_lay, from, j));
+}
+
 // ---- 8-bit sketch of float32 rows (cosine) --------------------------------------
 // One wave per row.  x_i / max|x| is quantized to the library's own 8-bit element form (byte v, value
 // n = 2v - 255: odd integers; cosine does not see the scale), written in the sketch shard's resident
@@ -704,6 +736,20 @@ hipError_t launch_repack(int qbits, uint8_t *ref, uint32_t row_bytes, uint8_t *r
     const uint64_t grid = (total + 255) / 256;
     hipLaunchKernelGGL(repack_bytes_kernel, dim3((unsigned)grid), dim3(256), 0, stream, ref, row_bytes, rows,
                        lay, first_row, es, n_rows, to_reference);
+    return hipGetLastError();
+}
+
+hipError_t launch_gather_rows(const uint8_t *src, RowLayout src_lay, uint8_t *dst, RowLayout dst_lay, uint32_t r16,
+                              const uint64_t *list, uint64_t n, uint64_t dst_first_row, hipStream_t stream)
+{
+    if (n == 0 || r16 == 0) return hipSuccess;
+    int g_shift = 0;  // lanes per row: the power of two that covers r16, one wave at the most
+    while (g_shift < 6 && (1u << g_shift) < r16) g_shift++;
+    const uint64_t rows_per_block = 256u >> g_shift;
+    const uint64_t grid = (n + rows_per_block - 1) / rows_per_block;
+    if (grid > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)grid), dim3(256), 0, stream, src, src_lay, dst, dst_lay, r16,
+                       list, n, dst_first_row, g_shift);
     return hipGetLastError();
 }
 

@@ -75,6 +75,24 @@ __global__ __launch_bounds__(256) void mask_gather_kernel(MaskGatherTable t, ulo
         out[i] = src ? src[i] : make_ulonglong2(~0ull, ~0ull);
 }
 
+// A mask carried across a compaction / reorder: new bit i = old bit list[i], i < n.  One thread per output word of
+// the 2 * n_pairs; bits at positions >= n -- the tail of the last word, the padding word -- are stored as 0.
+__global__ __launch_bounds__(256) void mask_gather_rows_kernel(const uint64_t *__restrict__ old_words,
+                                                               const uint64_t *__restrict__ list, uint64_t n,
+                                                               uint64_t *__restrict__ new_words, uint64_t n_words)
+{
+    const uint64_t w = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (w >= n_words) return;
+    uint64_t out = 0;
+    const uint64_t lo = w * 64;
+    const uint64_t hi = lo + 64 < n ? lo + 64 : n;
+    for (uint64_t i = lo; i < hi; i++) {
+        const uint64_t r = list[i];
+        out |= ((old_words[r >> 6] >> (r & 63)) & 1ull) << (i - lo);
+    }
+    new_words[w] = out;
+}
+
 static unsigned blocks_for(uint64_t items, unsigned cap)
 {
     const uint64_t g = (items + 255) / 256;
@@ -109,6 +127,18 @@ hipError_t launch_mask_gather(const MaskGatherTable &t, int n_queries, uint64_t 
     if (n_queries > kMqMaxQueries) return hipErrorInvalidValue;
     hipLaunchKernelGGL(mask_gather_kernel, dim3(blocks_for(n_pairs, 256), (unsigned)n_queries), dim3(256), 0, stream, t,
                        reinterpret_cast<ulonglong2 *>(dst), n_pairs);
+    return hipGetLastError();
+}
+
+hipError_t launch_mask_gather_rows(const uint64_t *old_words, const uint64_t *list, uint64_t n, uint64_t *new_words,
+                                   uint64_t n_pairs, hipStream_t stream)
+{
+    if (n_pairs == 0) return hipSuccess;
+    if (n > n_pairs * 128) return hipErrorInvalidValue;
+    const uint64_t grid = (2 * n_pairs + 255) / 256;
+    if (grid > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(mask_gather_rows_kernel, dim3((unsigned)grid), dim3(256), 0, stream, old_words, list, n, new_words,
+                       2 * n_pairs);
     return hipGetLastError();
 }
 

@@ -171,19 +171,10 @@ int shard_set_live(Shard *sh, uint64_t lo, uint64_t hi)
 }
 
 // rows of the index are split over shards in contiguous ranges whose boundaries
-// are multiples of 64 (so filter words slice cleanly)
+// are multiples of 64 (so filter words slice cleanly): split_counts, reorder_plan.h
 void split_rows(const szg_index *ix, uint64_t n_rows, std::vector<uint64_t> *counts)
 {
-    const size_t g = ix->shards.size();
-    counts->assign(g, 0);
-    uint64_t per = (n_rows + g - 1) / g;
-    per = (per + 63) & ~63ull;
-    uint64_t left = n_rows;
-    for (size_t s = 0; s < g; s++) {
-        const uint64_t m = std::min(per, left);
-        (*counts)[s] = m;
-        left -= m;
-    }
+    split_counts(ix->shards.size(), n_rows, counts);
 }
 
 Shard *shard_of(szg_index *ix, uint64_t row, uint64_t *local)

@@ -11,6 +11,7 @@
 //   scan_radius.cpp   radius search (single, batch, coalesced)
 //   scan_comm.cpp     one-process-per-GPU exchange (RCCL all-gather + merge)
 //   scan_mask.cpp     device-resident filter masks (szg_mask) and the searches that take them
+//   scan_reorder.cpp  compaction and reorder of the resident rows on the device (reorder_plan.h: its host-only checks)
 //   scan_api.cpp      remaining C entry points (top-k with caller coalescing, distances)
 //
 // What a batch borrows per shard is a Ctx: a stream, events and scratch that persist between batches -- every buffer
@@ -20,6 +21,7 @@
 #pragma once
 #include "../../include/syzgy_scan.h"
 #include "kernels.h"
+#include "reorder_plan.h"
 
 #include <algorithm>
 #include <atomic>
@@ -472,6 +474,27 @@ struct szg_index {
     szg_comm *comm = nullptr;    // one process per GPU: the attached communicator (borrowed; scan_comm.cpp)
 };
 
+// A device-resident filter mask (scan_mask.cpp).  Words and counts never change after creation -- except that a
+// compaction / reorder of the handle rewrites the masks it is asked to carry (scan_reorder.cpp), under the exclusive
+// access every mutation has.
+struct szg_mask {
+    szg_index *owner = nullptr;
+    uint64_t epoch = 0;     // the owner's mask_epoch this mask was made at
+    uint64_t rows = 0;      // row count of the handle then
+    struct Part {
+        int device = 0;
+        uint64_t first = 0, n_rows = 0;
+        size_t pairs = 0;             // 16-byte pairs of words
+        szgi::DevBuf<uint64_t> words; // 2 * pairs words, then the popcount counter (2 words)
+        uint64_t count = 0;           // rows of the shard the mask allows
+    };
+    std::vector<Part> parts;          // one per shard of the owner
+    std::vector<uint64_t> host;       // index-level words, tail bits 0
+    uint64_t count = 0;
+    uint64_t dev_bytes = 0;
+    bool counted = false;             // in the owner's live_masks / device_bytes
+};
+
 namespace szgi {
 
 struct LaunchGeom {
@@ -624,7 +647,10 @@ uint64_t mask_shard_count(const szg_mask *m, size_t shard);         // rows of t
 int search_topk_masked_prepare(szg_index *ix, const double *queries, int n_queries, int k, const szg_mask *const *masks,
                                int n_masks, uint64_t *out_rows, double *out_dist, int32_t *out_count, const szg_mask **lone);
 // words per slot of a batch's d_allow when resident masks are gathered into it (16-byte pairs)
-inline size_t mask_slot_words(const Shard *sh) { return (size_t)(((sh->n_rows + 63) / 64 + 1) & ~1ull); }
+inline size_t mask_slot_words(uint64_t n_rows) { return (size_t)(((n_rows + 63) / 64 + 1) & ~1ull); }
+inline size_t mask_slot_words(const Shard *sh) { return mask_slot_words(sh->n_rows); }
+// words of a mask with one bit per row (no padding): the host copy of a mask, a shard's slice of it
+inline size_t index_words(uint64_t rows) { return (size_t)((rows + 63) / 64); }
 
 // One link of the shard's scan chain: under chain_mu, launch(st) puts the sweeps onto the shard's scan stream behind the
 // batch's uploads (ev_up, recorded on the work stream by the caller), and `after` goes on once they are done.  With

@@ -10,27 +10,7 @@
 
 using namespace szgi;
 
-struct szg_mask {
-    szg_index *owner = nullptr;
-    uint64_t epoch = 0;     // the owner's mask_epoch this mask was made at
-    uint64_t rows = 0;      // row count of the handle then
-    struct Part {
-        int device = 0;
-        uint64_t first = 0, n_rows = 0;
-        size_t pairs = 0;             // 16-byte pairs of words
-        DevBuf<uint64_t> words;       // 2 * pairs words, then the popcount counter (2 words)
-        uint64_t count = 0;           // rows of the shard the mask allows
-    };
-    std::vector<Part> parts;          // one per shard of the owner
-    std::vector<uint64_t> host;       // index-level words, tail bits 0
-    uint64_t count = 0;
-    uint64_t dev_bytes = 0;
-    bool counted = false;             // in the owner's live_masks / device_bytes
-};
-
 namespace {
-
-size_t index_words(uint64_t rows) { return (size_t)((rows + 63) / 64); }
 
 // an empty mask shaped after the handle's shards, its device words allocated (not yet written)
 int mask_alloc(szg_index *ix, szg_mask **out)

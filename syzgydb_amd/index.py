@@ -224,6 +224,40 @@ class ScanIndex:
                                           _u8(out) if n_rows else None), "szg_index_read_rows")
         return out
 
+    # -- compaction / reorder on the device ---------------------------------------
+    def _carry_arg(self, carry):
+        if isinstance(carry, ScanMask):
+            carry = [carry]
+        carry = list(carry)
+        arr = (ctypes.c_void_p * len(carry))(*[m._live() for m in carry]) if carry else None
+        return carry, arr
+
+    def _carried(self, carry):
+        words = (self.rows + 63) // 64
+        for m in carry:
+            m._words = words
+
+    def reorder(self, src_rows, carry=()):
+        """New row i = old row src_rows[i]; rows not listed are dropped.  The rows move on the device.  Every listed
+        row must be in range, live and listed once.  carry: ScanMasks of this index that are rewritten for the new
+        numbering and stay valid; every other mask becomes stale."""
+        r = np.ascontiguousarray(src_rows, dtype=np.uint64).reshape(-1)
+        carry, arr = self._carry_arg(carry)
+        check(self._L.szg_index_reorder(self._h, _u64(r) if r.size else None, r.size, arr, len(carry)),
+              "szg_index_reorder")
+        self._carried(carry)
+
+    def compact(self, carry=()):
+        """Drop the tombstoned rows on the device, keeping the order of the live ones.  Returns new_of_old,
+        uint64[rows before]: the new number of each old row, 2**64 - 1 for a dropped one.  carry: as reorder's.
+        Without tombstones nothing moves and no mask becomes stale."""
+        new_of_old = np.zeros(self.rows, dtype=np.uint64)
+        carry, arr = self._carry_arg(carry)
+        check(self._L.szg_index_compact(self._h, _u64(new_of_old) if new_of_old.size else None, None, arr, len(carry)),
+              "szg_index_compact")
+        self._carried(carry)
+        return new_of_old
+
     def set_row_base(self, base):
         check(self._L.szg_index_set_row_base(self._h, int(base)), "szg_index_set_row_base")
 
@@ -451,6 +485,19 @@ def scan_group_plan(dim, quant_bits, n_queries, kp=10, scan_group=0, queries_per
                                  int(n_queries), int(queries_per_launch), ctypes.byref(g), ctypes.byref(lds),
                                  ctypes.byref(passes)), "szg_debug_scan_group")
     return {"group": g.value, "lds_bytes": lds.value, "passes": passes.value}
+
+
+def reorder_plan(n_rows, src_rows, n_shards=1, live=None):
+    """Host-only test hook (no device needed): the checks ScanIndex.reorder makes on its list -- SzgError with the same
+    code and text -- and the new rows per shard.  live: bool[n_rows] (None: every row is live)."""
+    L = _lib.load()
+    r = np.ascontiguousarray(src_rows, dtype=np.uint64).reshape(-1)
+    words = pack_allow_bits(np.asarray(live, dtype=bool))[0] if live is not None else None
+    counts = np.zeros(int(n_shards), dtype=np.uint64)
+    check(L.szg_debug_reorder_plan(int(n_rows), _u64(words) if words is not None and words.size else None,
+                                   _u64(r) if r.size else None, r.size, int(n_shards), _u64(counts)),
+          "szg_debug_reorder_plan")
+    return [int(c) for c in counts]
 
 
 def scan_plan(dim, quant_bits, n_rows, kp=10, collect=False, masked=False, cu_count=0):
