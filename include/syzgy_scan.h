@@ -235,6 +235,77 @@ int szg_index_reorder(szg_index *ix, const uint64_t *src_rows, uint64_t n_rows,
 int szg_index_compact(szg_index *ix, uint64_t *out_new_of_old, uint64_t *out_rows,
                       szg_mask *const *carry, int n_carry);
 
+/* ---- resident metadata columns (added under ABI 4, additive) -----------------
+ *
+ * The leaves of the reference's filter language on the card.  A top-level metadata field becomes a column resident
+ * beside the rows -- one value and one present bit per row -- and a comparison against a constant is ONE
+ * bandwidth-bound kernel per shard that writes the words and the count of an ordinary szg_mask.  A new filter text
+ * (`price < 37.5`) then costs a few small launches and never walks the per-row metadata on the host; the masks compose
+ * with szg_mask_combine like any others.
+ *
+ * Kinds: SZG_COL_F64 holds doubles; SZG_COL_U32 holds codes of a dictionary the HOST owns (the library never sees the
+ *   strings: the host evaluates a string operator once per dictionary entry into a bitmap over codes).
+ * Predicate of every szg_mask_where_*: bit r = present(r) && pred(value[r]) (&& base's bit r).  Float64 comparisons
+ *   follow IEEE, i.e. Go's == and < on float64 (query/compiler.go:175, :288-303): -0.0 == 0.0, and a NaN fails every
+ *   operator but SZG_CMP_NE.  Tail bits are 0, as in every mask.
+ * Create and append: a column belongs to one handle and covers its rows [0, n): n_rows <= szg_index_rows(ix), else
+ *   SZG_E_RANGE -- it may be shorter, so the host can append rows to the index first and bring the column up
+ *   afterwards.  present_bits == NULL: every row is present; otherwise bit i = the i-th row OF THE CALL (for an append,
+ *   the i-th appended row: the library shifts the bits into place, no alignment is asked of the caller).  Values and
+ *   bits are copied.  An append past szg_index_rows returns SZG_E_RANGE.  Capacity grows geometrically.
+ * Rows are numbered as searches return them (local + row base) in szg_column_set and szg_column_read.
+ * Storage: each shard's part lives on the shard's device -- 8 or 4 bytes per row plus one bit -- next to a host copy
+ *   of the present words.
+ * szg_mask_where_*: need szg_column_rows(c) == szg_index_rows(owner), else SZG_E_INVALID ("short column" in
+ *   szg_last_error).  base is nullable; when given it must be a mask of the same handle that is not stale (else
+ *   SZG_E_INVALID), and the result is base & pred.  The result is an ordinary szg_mask in every respect: count, read,
+ *   combine, searches, carry across compaction, szg_index_mask_stats; its host copy of the words is downloaded once,
+ *   at creation.  An operator outside SZG_CMP_EQ..SZG_CMP_GE, or a column whose kind does not match the call, is
+ *   SZG_E_INVALID.
+ * Mutations: szg_index_tombstone and the overwrites leave a column valid; the appends leave it valid but short.
+ *   szg_index_load, szg_index_synth, szg_index_reorder and a szg_index_compact that moves rows (one without
+ *   tombstones does not) make it STALE: every call except szg_column_rows, szg_column_read and szg_column_destroy
+ *   then returns SZG_E_INVALID ("stale column") and never reads past the column.  Columns are not carried across a
+ *   reorder: the host creates them again, 8 bytes per row, once per compaction.
+ * Threads: szg_mask_where_* and szg_column_read may run beside searches and beside each other; create / append / set /
+ *   destroy need the exclusive access mutations have.  Columns are destroyed before their handle.
+ * Failure: every check happens on the host before anything is allocated or launched; an error leaves the column as
+ *   it was and *out untouched.
+ */
+typedef struct szg_column szg_column;
+#define SZG_COL_F64 0   /* values: double */
+#define SZG_COL_U32 1   /* values: uint32_t codes; the host owns the dictionary */
+#define SZG_CMP_EQ 0
+#define SZG_CMP_NE 1
+#define SZG_CMP_LT 2
+#define SZG_CMP_LE 3
+#define SZG_CMP_GT 4
+#define SZG_CMP_GE 5
+
+int szg_column_create(szg_index *ix, int kind, const void *values, const uint64_t *present_bits,
+                      uint64_t n_rows, szg_column **out);
+int szg_column_append(szg_column *c, const void *values, const uint64_t *present_bits, uint64_t n_rows);
+/* one row: its value and present bit; value == NULL marks the row absent (its stored value stays) */
+int szg_column_set(szg_column *c, uint64_t row, const void *value);
+uint64_t szg_column_rows(const szg_column *c);
+/* rows [first_row, first_row + n_rows) of the column: n_rows values and ceil(n_rows/64) words, bit i = row
+   first_row + i, tail bits 0; either output may be NULL; past szg_column_rows -> SZG_E_RANGE.  Works on a stale column */
+int szg_column_read(const szg_column *c, uint64_t first_row, uint64_t n_rows, void *out_values,
+                    uint64_t *out_present_bits);
+void szg_column_destroy(szg_column *c);   /* NULL is fine; before its handle */
+
+/* present && value op constant (SZG_CMP_*) */
+int szg_mask_where_f64(const szg_column *c, int op, double value, const szg_mask *base, szg_mask **out);
+/* present && value == one of values[0 .. n_values): duplicates allowed, a NaN among them matches nothing, n_values == 0
+   gives the empty mask; more than 1024 -> SZG_E_UNSUPPORTED */
+int szg_mask_where_in_f64(const szg_column *c, const double *values, uint32_t n_values,
+                          const szg_mask *base, szg_mask **out);
+/* present && bit `code` of code_bits (n_codes bits, ceil(n_codes/64) words, copied); a code >= n_codes fails */
+int szg_mask_where_u32(const szg_column *c, const uint64_t *code_bits, uint32_t n_codes,
+                       const szg_mask *base, szg_mask **out);
+/* the present bits (either kind) */
+int szg_mask_where_present(const szg_column *c, const szg_mask *base, szg_mask **out);
+
 /*
  * The reference's float64 distance (c.distance, collection.go:596, :812-832) from
  * one query to each listed row, bit-identical to the reference: the gather-by-row

@@ -6,6 +6,7 @@
 #   scripts/kernel_resources.sh scan 32       -> kernels_scan.hip -DSZG_QBITS=32
 #   scripts/kernel_resources.sh exact         -> kernels_exact.hip (re-rank, page-in, row gather, ...)
 #   scripts/kernel_resources.sh mask          -> kernels_mask.hip (device-resident filter masks)
+#   scripts/kernel_resources.sh column        -> kernels_column.hip (resident metadata columns)
 # (hipcc -Rpass-analysis=kernel-resource-usage, device code only; no GPU needed)
 set -euo pipefail
 cd "$(dirname "$0")/../syzgydb_amd/csrc"
@@ -13,6 +14,7 @@ kind=${1:-mq}; part=${2:-i8}
 if [ "$kind" = scan ]; then src=kernels_scan.hip; def=-DSZG_QBITS=$part
 elif [ "$kind" = exact ]; then src=kernels_exact.hip; def=-ffp-contract=off
 elif [ "$kind" = mask ]; then src=kernels_mask.hip; def=
+elif [ "$kind" = column ]; then src=kernels_column.hip; def=
 elif [ "$part" = select ]; then src=kernels_mq.hip; def=
 elif [ "$part" = bf16d ]; then src=kernels_mq_bf16d.hip; def=
 else src=kernels_mq_$part.hip; def=-DSZG_ROW_BITS=${3:?row width}; fi

@@ -40,10 +40,15 @@ EXPORTS = [
     "szg_mask_destroy", "szg_search_topk_masked", "szg_search_radius_masked", "szg_index_mask_stats",
     # compaction / reorder on the device (added under ABI 4)
     "szg_index_reorder", "szg_index_compact",
+    # resident metadata columns (added under ABI 4)
+    "szg_column_create", "szg_column_append", "szg_column_set", "szg_column_rows", "szg_column_read",
+    "szg_column_destroy", "szg_mask_where_f64", "szg_mask_where_in_f64", "szg_mask_where_u32", "szg_mask_where_present",
     # host-only test hook
     "szg_debug_scan_plan", "szg_debug_scan_group", "szg_debug_reorder_plan",
 ]
 SZG_MASK_AND, SZG_MASK_OR, SZG_MASK_ANDNOT, SZG_MASK_NOT = 0, 1, 2, 3
+SZG_COL_F64, SZG_COL_U32 = 0, 1
+SZG_CMP_EQ, SZG_CMP_NE, SZG_CMP_LT, SZG_CMP_LE, SZG_CMP_GT, SZG_CMP_GE = range(6)
 SZG_COMM_ID_BYTES = 128
 # int (*szg_allgather_fn)(void *user, const void *send, void *recv, uint64_t bytes_per_rank)
 ALLGATHER_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64)
@@ -217,6 +222,27 @@ def load():
         L.szg_index_compact.argtypes = [vp, u64p, u64p, ctypes.POINTER(vp), ctypes.c_int]
         L.szg_debug_reorder_plan.restype = ctypes.c_int
         L.szg_debug_reorder_plan.argtypes = [ctypes.c_uint64, u64p, u64p, ctypes.c_uint64, ctypes.c_int, u64p]
+    if hasattr(L, "szg_column_create"):   # (as the masks: an older build for an A/B run has no columns)
+        L.szg_column_create.restype = ctypes.c_int
+        L.szg_column_create.argtypes = [vp, ctypes.c_int, vp, u64p, ctypes.c_uint64, ctypes.POINTER(vp)]
+        L.szg_column_append.restype = ctypes.c_int
+        L.szg_column_append.argtypes = [vp, vp, u64p, ctypes.c_uint64]
+        L.szg_column_set.restype = ctypes.c_int
+        L.szg_column_set.argtypes = [vp, ctypes.c_uint64, vp]
+        L.szg_column_rows.restype = ctypes.c_uint64
+        L.szg_column_rows.argtypes = [vp]
+        L.szg_column_read.restype = ctypes.c_int
+        L.szg_column_read.argtypes = [vp, ctypes.c_uint64, ctypes.c_uint64, vp, u64p]
+        L.szg_column_destroy.restype = None
+        L.szg_column_destroy.argtypes = [vp]
+        L.szg_mask_where_f64.restype = ctypes.c_int
+        L.szg_mask_where_f64.argtypes = [vp, ctypes.c_int, ctypes.c_double, vp, ctypes.POINTER(vp)]
+        L.szg_mask_where_in_f64.restype = ctypes.c_int
+        L.szg_mask_where_in_f64.argtypes = [vp, f64p, ctypes.c_uint32, vp, ctypes.POINTER(vp)]
+        L.szg_mask_where_u32.restype = ctypes.c_int
+        L.szg_mask_where_u32.argtypes = [vp, u64p, ctypes.c_uint32, vp, ctypes.POINTER(vp)]
+        L.szg_mask_where_present.restype = ctypes.c_int
+        L.szg_mask_where_present.argtypes = [vp, vp, ctypes.POINTER(vp)]
     L.szg_comm_unique_id.restype = ctypes.c_int
     L.szg_comm_unique_id.argtypes = [u8p]
     L.szg_comm_create.restype = ctypes.c_int

@@ -16,7 +16,7 @@ from typing import Callable, List, Optional
 
 import numpy as np
 
-from . import codec
+from . import _lib, codec, where as _where
 from .index import ScanIndex, pack_allow_bits
 
 Euclidean = 0  # collection.go:186-189
@@ -63,6 +63,29 @@ class SearchArgs:
     Limit: int = 0
     Precision: str = ""
     FilterKey: Optional[str] = None  # not in the reference: names the filter for the bitmask cache
+    Where: Optional[object] = None   # not in the reference: the filter as a where.Expr (exclusive with Filter); fields
+                                     # indexed with Collection.IndexField are compared on the card
+
+
+class _FieldIndex:
+    """One indexed metadata field: its column on the card and, for strings, the dictionary value -> code."""
+
+    def __init__(self, name, kind):
+        self.name = name
+        self.kind = kind        # "number" / "string"
+        self.column = None      # ScanColumn
+        self.codes = {}         # string fields: value -> code, append-only, first-seen order
+
+    def value_of(self, data):
+        """(value, present) of one document for the column: data = its parsed metadata (None: not a JSON object)."""
+        v = data.get(self.name) if data is not None else None
+        if self.kind == "number":
+            if _where._is_number(v):
+                return _where._number(v), True
+            return 0.0, False
+        if isinstance(v, str):
+            return self.codes.setdefault(v, len(self.codes)), True
+        return 0, False
 
 
 class Collection:
@@ -98,6 +121,12 @@ class Collection:
         # the ScanMask that holds the same bits on the card: searches pass the handle, nothing is uploaded again
         self._version = 0
         self._mask_cache = {}   # (key, version) -> [words, filter, ScanMask or None]
+        # metadata fields resident on the card (IndexField): name -> _FieldIndex, and beside them the hidden column
+        # "the metadata is a JSON object" (code 1 / 0), which exists once any field is indexed
+        self._fields = {}
+        self._object_col = None
+        self.where_compiled = 0    # Where expressions turned into a mask through the columns
+        self.where_fallbacks = 0   # ... answered through the Filter path (a field not indexed, a constant of another type)
         # Row order only matters where the reference's own answer depends on its visit order: ties at the k
         # boundary, equal distances in a radius result (collection.go:608).  Production iterates a Go map (random
         # order per run, spanfile.go:525): every order is a reference order, rows are simply appended
@@ -152,6 +181,7 @@ class Collection:
         self._order_stale = False
         self.resorts += 1
         self._version += 1  # rows are renumbered: cached filter masks no longer apply
+        self._rebuild_columns()
 
     # -- CRUD (host bookkeeping + mirror maintenance) ---------------------------
     def AddDocument(self, id: int, vector, metadata: bytes = b""):
@@ -167,12 +197,14 @@ class Collection:
             row = self._row_of[id]
             self._index.overwrite(row, row_bytes)
             self._meta[row] = bytes(metadata)
+            self._columns_set(row)
         else:
             self._index.append(row_bytes)
             self._row_of[id] = len(self._id_of)
             self._id_of.append(id)
             self._meta.append(bytes(metadata))
             self._note_appended(id)
+            self._columns_append(1)
 
     def AddDocuments(self, ids, vectors, metadatas=None):
         """Bulk ingest (not in the reference; same effect as AddDocument in a loop for new ids)."""
@@ -191,6 +223,7 @@ class Collection:
             self._id_of.append(i)
             self._meta.append(bytes(metadatas[j]) if metadatas else b"")
             self._note_appended(i)
+        self._columns_append(len(ids))
 
     def GetDocument(self, id: int) -> Document:
         row = self._row_of.get(int(id))
@@ -206,6 +239,7 @@ class Collection:
             raise KeyError("record not found")
         self._version += 1
         self._meta[row] = bytes(new_metadata)
+        self._columns_set(row)
 
     def removeDocument(self, id: int):
         row = self._row_of.pop(int(id), None)
@@ -215,6 +249,7 @@ class Collection:
         self._index.tombstone(row)
         self._id_of[row] = None
         self._meta[row] = b""
+        self._columns_set(row)
         if self.auto_compact is not None:
             rows = self._index.rows
             if rows - self._index.live_rows > self.auto_compact * rows:
@@ -249,6 +284,7 @@ class Collection:
                 bits = np.unpackbits(np.ascontiguousarray(words).view(np.uint8), bitorder="little")[:n_old]
                 words = pack_allow_bits(bits[keep].astype(bool))
             self._mask_cache[(key, self._version)] = [words, flt, mask]
+        self._rebuild_columns()
         self.compactions += 1
         return dropped
 
@@ -292,7 +328,192 @@ class Collection:
             self._index.close()   # (closes the masks it still holds first)
             self._closed = True
 
+    # -- metadata fields resident on the card ------------------------------------
+    def IndexField(self, name: str, kind: str):
+        """Keep the top-level metadata field `name` as a column on the card (not in the reference): kind "number"
+        holds the rows whose value is a JSON number, kind "string" those whose value is a string, as codes of an
+        append-only dictionary kept here.  The resident metadata is parsed once, now; from then on AddDocument(s)
+        append to the column, UpdateDocument sets the row, and Compact() and the re-sort rebuild it.  Search with
+        SearchArgs.Where then compares the field on the card."""
+        if kind not in ("number", "string"):
+            raise ValueError('kind is "number" or "string"')
+        _where.Field(name)   # (the name must be an identifier of the filter language)
+        old = self._fields.pop(name, None)
+        if old is not None and old.column is not None:
+            old.column.close()
+        f = self._fields[name] = _FieldIndex(name, kind)
+        parsed = [_where.parse_metadata(m) for m in self._meta]
+        self._build_column(f, parsed)
+        if self._object_col is None:
+            self._object_col = self._index.column(np.array([d is not None for d in parsed], dtype=np.uint32),
+                                                  kind=_lib.SZG_COL_U32)
+        self._version += 1   # (cached Where masks that took the fallback for this field are re-made through the column)
+
+    def _build_column(self, f, parsed):
+        pairs = [f.value_of(d) for d in parsed]
+        values = np.array([v for v, _ in pairs], dtype=np.float64 if f.kind == "number" else np.uint32)
+        present = np.array([p for _, p in pairs], dtype=bool)
+        f.column = self._index.column(values, present=present,
+                                      kind=_lib.SZG_COL_F64 if f.kind == "number" else _lib.SZG_COL_U32)
+
+    def _rebuild_columns(self):
+        """The rows were renumbered (Compact, the re-sort): the columns are made again from the resident metadata."""
+        if not self._fields:
+            return
+        parsed = [_where.parse_metadata(m) for m in self._meta]
+        for f in self._fields.values():
+            f.column.close()
+            self._build_column(f, parsed)
+        self._object_col.close()
+        self._object_col = self._index.column(np.array([d is not None for d in parsed], dtype=np.uint32),
+                                              kind=_lib.SZG_COL_U32)
+
+    def _columns_append(self, n):
+        """The last n rows are new: bring every column up to the index."""
+        if not self._fields or n == 0:
+            return
+        parsed = [_where.parse_metadata(m) for m in self._meta[len(self._meta) - n:]]
+        for f in self._fields.values():
+            pairs = [f.value_of(d) for d in parsed]
+            f.column.append([v for v, _ in pairs], present=np.array([p for _, p in pairs], dtype=bool))
+        self._object_col.append(np.array([d is not None for d in parsed], dtype=np.uint32))
+
+    def _columns_set(self, row):
+        """Row `row`'s metadata changed."""
+        if not self._fields:
+            return
+        data = _where.parse_metadata(self._meta[row])
+        for f in self._fields.values():
+            v, present = f.value_of(data)
+            f.column.set(row, v if present else None)
+        self._object_col.set(row, 1 if data is not None else 0)
+
+    def _leaf_mask(self, e):
+        """(mask, can_error) of one leaf through its field's column: mask = the rows where the leaf is true AND the
+        field holds a value of the indexed type.  None: the leaf cannot be answered by the columns (field not indexed,
+        a constant of another type than the index, an IN-list beyond the kernel's) -- the caller falls back."""
+        f = self._fields.get(e.field)
+        if f is None:
+            return None
+        want = float if f.kind == "number" else str
+        col = f.column
+        if isinstance(e, _where.Cmp):
+            if not isinstance(e.constant, want):
+                return None
+            positive = _where.Cmp(e.field, "==", e.constant) if e.op == "!=" else e
+            if f.kind == "number":
+                m = col.where(positive.op, positive.constant)
+            else:
+                m = col.codes([positive.test(s) for s in f.codes])
+            if e.op == "!=":   # true for nil and every value of another type as well: the complement
+                m, pos = ~m, m
+                pos.close()
+            return m, e.op in _where._ORDERED
+        if isinstance(e, _where.In):
+            if not all(isinstance(c, want) for c in e.constants) or len(e.constants) > 1024:
+                return None
+            if f.kind == "number":
+                m = col.isin(e.constants)
+            else:
+                inside = set(e.constants)
+                m = col.codes([s in inside for s in f.codes])
+            if e.negate:
+                m, pos = ~m, m
+                pos.close()
+            return m, False
+        if isinstance(e, _where.StrOp):
+            if f.kind != "string":
+                return None
+            return col.codes([e.test(s) for s in f.codes]), True
+        return None
+
+    def _where_device_mask(self, expr):
+        """The expression as a ScanMask through the columns: V(expr) -- plain mask algebra over the leaves -- &
+        "the metadata is a JSON object" & present(field) of every leaf that can error (where.py has the rules).
+        None: some leaf needs the host (the masks made so far are closed)."""
+        made, need = [], set()
+
+        def V(e):
+            if isinstance(e, (_where.And, _where.Or)):
+                a = V(e.a)
+                b = V(e.b) if a is not None else None
+                if b is None:
+                    return None
+                m = (a & b) if isinstance(e, _where.And) else (a | b)
+            elif isinstance(e, _where.Not):
+                a = V(e.a)
+                if a is None:
+                    return None
+                m = ~a
+            else:
+                leaf = self._leaf_mask(e)
+                if leaf is None:
+                    return None
+                m, can_error = leaf
+                if can_error:
+                    need.add(e.field)
+            made.append(m)
+            return m
+
+        try:
+            v = V(expr)
+            if v is None:
+                return None
+            guard = self._object_col.codes([False, True])
+            made.append(guard)
+            for name in sorted(need):
+                guard = self._fields[name].column.present(base=guard)
+                made.append(guard)
+            result = v & guard
+        finally:
+            for m in made:   # (the temporaries; the result is a mask of its own)
+                m.close()
+        return result
+
+    def _where_filter(self, expr):
+        return lambda id_, meta: expr.evaluate(meta)
+
+    def _where_handle(self, expr):
+        """The Where expression's verdicts as a ScanMask, cached per (expr.text(), collection version) beside the
+        Filter masks: compiled through the columns, or -- when a leaf cannot be -- evaluated on the host like a Filter
+        with expr.text() as its key."""
+        key = expr.text()
+        hit = self._mask_cache.get((key, self._version))
+        if hit is None and self._fields:
+            self._drop_old_masks()
+            mask = self._where_device_mask(expr)
+            if mask is not None:
+                self.where_compiled += 1
+                if len(self._mask_cache) > 16:
+                    self._mask_cache.clear()
+                hit = self._mask_cache[(key, self._version)] = [mask.read().reshape(1, -1), self._where_filter(expr), mask]
+        if hit is None:
+            self.where_fallbacks += 1
+        return self._allow_handle(self._where_filter(expr), key)
+
+    def _search_filter(self, args):
+        """(filter callable, cache key, where expression) of a Search: Filter and Where are exclusive."""
+        expr = getattr(args, "Where", None)
+        if expr is None:
+            return args.Filter, getattr(args, "FilterKey", None), None
+        if args.Filter is not None:
+            raise ValueError("SearchArgs: Filter and Where are exclusive")
+        if not isinstance(expr, _where.Expr):
+            raise TypeError("SearchArgs.Where is a where.Expr")
+        return self._where_filter(expr), expr.text(), expr
+
+    def _search_handle(self, args):
+        flt, key, expr = self._search_filter(args)
+        return self._where_handle(expr) if expr is not None else self._allow_handle(flt, key)
+
     # -- Search ---------------------------------------------------------------
+    def _drop_old_masks(self):
+        # the version has moved: entries of older versions can never be hit again, their device masks go now
+        for old in [k for k in self._mask_cache if k[1] != self._version]:
+            m = self._mask_cache.pop(old)[2]
+            if m is not None:
+                m.close()
+
     def _allow_mask(self, flt, key=None):
         """One bit per row from the caller's filter (collection.go:592-594).  `key` (e.g. the
         REST layer's filter text) makes the verdicts reusable until the collection changes;
@@ -306,11 +527,7 @@ class Collection:
         hit = self._mask_cache.get(ck)
         if hit is not None and (key is not None or hit[1] is flt):
             return hit
-        # the version has moved: entries of older versions can never be hit again, their device masks go now
-        for old in [k for k in self._mask_cache if k[1] != self._version]:
-            m = self._mask_cache.pop(old)[2]
-            if m is not None:
-                m.close()
+        self._drop_old_masks()
         mask = np.zeros(len(self._id_of), dtype=bool)
         for row, id_ in enumerate(self._id_of):
             if id_ is not None:
@@ -336,11 +553,12 @@ class Collection:
         results: List[SearchResult] = []
         points_searched = 0
 
+        flt = self._search_filter(args)[0]
         if args.Radius == 0 and args.K == 0:
             # listing mode (collection.go:633-669): sorted *string* id order
             for id in sorted(self._row_of, key=lambda i: str(i)):
                 row = self._row_of[id]
-                if args.Filter is not None and not args.Filter(id, self._meta[row]):
+                if flt is not None and not flt(id, self._meta[row]):
                     continue
                 points_searched += 1
                 if args.Offset > 0 and points_searched <= args.Offset:
@@ -357,7 +575,7 @@ class Collection:
             def scan():
                 if n_records == 0:
                     return [], []
-                mask = self._allow_handle(args.Filter, getattr(args, "FilterKey", None))
+                mask = self._search_handle(args)
                 if args.Radius > 0:  # K is ignored (collection.go:598-605)
                     return self._index.search_radius(q, args.Radius, masks=mask)
                 r, d, c = self._index.search_topk(q, args.K, masks=mask)
@@ -407,10 +625,10 @@ class Collection:
         if Q.shape[1] != self.DimensionCount:
             raise ValueError("query length %d != dimension %d" % (Q.shape[1], self.DimensionCount))
         masks = None
-        if any(a.Filter is not None for a in args_list):
+        if any(a.Filter is not None or getattr(a, "Where", None) is not None for a in args_list):
             # one handle per query (None = unfiltered); queries that share a FilterKey share the handle, and a batch
             # that holds a single one passes just that: its sweeps read the resident mask in place
-            masks = [self._allow_handle(a.Filter, getattr(a, "FilterKey", None)) for a in args_list]
+            masks = [self._search_handle(a) for a in args_list]
             if all(m is masks[0] for m in masks):
                 masks = masks[0]
         out = []

@@ -353,4 +353,26 @@ hipError_t launch_mask_gather(const MaskGatherTable &t, int n_queries, uint64_t 
 hipError_t launch_mask_gather_rows(const uint64_t *old_words, const uint64_t *list, uint64_t n, uint64_t *new_words,
                                    uint64_t n_pairs, hipStream_t stream);
 
+// ---- kernels_column.hip: resident metadata columns, ONE shard's part per launch -------------------------------------
+// Where a comparison's verdicts go: pair i of `out` = the verdicts of rows [128 i, 128 i + 128) & pair i of `present`
+// (null: every row present) & pair i of `base` (null: none), bits at positions >= n_rows stored as 0;
+// *count += the bits set in out.  n_rows <= 128 * n_pairs; no element at a position >= n_rows is loaded.
+struct ColumnWhere {
+    const uint64_t *present;
+    const uint64_t *base;
+    uint64_t *out;
+    uint64_t n_pairs, n_rows;
+    uint64_t *count;
+};
+constexpr int kColumnInMax = 1024;  // constants of an IN-list (held in LDS)
+// op: SZG_CMP_* (EQ NE LT LE GT GE), IEEE rules
+hipError_t launch_column_cmp_f64(const double *values, int op, double constant, const ColumnWhere &w, hipStream_t stream);
+// sorted: device, ascending, no NaN, n_sorted <= kColumnInMax
+hipError_t launch_column_in_f64(const double *values, const double *sorted, uint32_t n_sorted, const ColumnWhere &w,
+                                hipStream_t stream);
+// code_bits: device, ceil(n_codes / 64) words; a code >= n_codes fails
+hipError_t launch_column_codes_u32(const uint32_t *values, const uint64_t *code_bits, uint32_t n_codes, const ColumnWhere &w,
+                                   hipStream_t stream);
+hipError_t launch_column_present(const ColumnWhere &w, hipStream_t stream);
+
 }  // namespace szg

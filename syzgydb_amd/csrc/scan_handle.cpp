@@ -381,7 +381,7 @@ uint64_t szg_index_live_rows(const szg_index *ix)
 int szg_index_load(szg_index *ix, const uint8_t *rows, uint64_t n_rows)
 {
     SZG_TRY
-    if (ix) { ix->gen++; ix->mask_epoch++; sketch_rearm(ix); }  // (masks made before are stale from here on)
+    if (ix) { ix->gen++; ix->mask_epoch++; ix->col_epoch++; sketch_rearm(ix); }  // (masks and columns made before are stale from here on)
     if (!ix || (!rows && n_rows)) return fail(SZG_E_INVALID, "null argument");
     std::vector<uint64_t> counts;
     split_rows(ix, n_rows, &counts);
@@ -401,7 +401,7 @@ int szg_index_load(szg_index *ix, const uint8_t *rows, uint64_t n_rows)
 int szg_index_synth(szg_index *ix, uint64_t n_rows, uint64_t seed, uint64_t first_row)
 {
     SZG_TRY
-    if (ix) { ix->gen++; ix->mask_epoch++; sketch_rearm(ix); }  // (masks made before are stale from here on)
+    if (ix) { ix->gen++; ix->mask_epoch++; ix->col_epoch++; sketch_rearm(ix); }  // (masks and columns made before are stale from here on)
     if (!ix) return fail(SZG_E_INVALID, "null argument");
     std::vector<uint64_t> counts;
     split_rows(ix, n_rows, &counts);

@@ -11,6 +11,7 @@
 //   scan_radius.cpp   radius search (single, batch, coalesced)
 //   scan_comm.cpp     one-process-per-GPU exchange (RCCL all-gather + merge)
 //   scan_mask.cpp     device-resident filter masks (szg_mask) and the searches that take them
+//   scan_column.cpp   resident metadata columns (szg_column): comparisons against constants that write masks
 //   scan_reorder.cpp  compaction and reorder of the resident rows on the device (reorder_plan.h: its host-only checks)
 //   scan_api.cpp      remaining C entry points (top-k with caller coalescing, distances)
 //
@@ -464,6 +465,8 @@ struct szg_index {
     std::mutex stats_mu;
     // device-resident filter masks (scan_mask.cpp)
     std::atomic<uint64_t> mask_epoch{1};  // moves whenever the row count may (load, synth, appends): older masks are stale
+    std::atomic<uint64_t> col_epoch{1};   // moves whenever rows are renumbered or replaced (load, synth, a reorder or
+                                          // compaction that moves rows) -- NOT by appends: older columns are stale
     std::atomic<uint64_t> mask_live{0}, mask_dev_bytes{0};
     std::atomic<uint64_t> mask_h2d{0}, mask_d2d{0}, mask_shared{0};  // szg_mask_stats (with the sketch index's own)
     // coalescing of concurrent single-query searches (szg_search_topk, n_queries == 1)
@@ -493,6 +496,25 @@ struct szg_mask {
     uint64_t count = 0;
     uint64_t dev_bytes = 0;
     bool counted = false;             // in the owner's live_masks / device_bytes
+};
+
+// A resident metadata column (scan_column.cpp): one value and one present bit per row, each shard's part on the shard's
+// own device.  It covers rows [0, rows) of its handle, rows <= szg_index_rows: index appends leave it short until
+// szg_column_append catches up.
+struct szg_column {
+    szg_index *owner = nullptr;
+    int kind = 0;           // SZG_COL_F64 / SZG_COL_U32
+    uint64_t epoch = 0;     // the owner's col_epoch this column was made at
+    uint64_t rows = 0;
+    struct Part {
+        int device = 0;
+        uint64_t first = 0, n_rows = 0, cap_rows = 0;  // cap_rows: a multiple of 128
+        void *values = nullptr;            // device, cap_rows elements
+        uint64_t *present = nullptr;       // device, cap_rows / 64 words in the masks' 16-byte-pair layout, tail bits 0
+        std::vector<uint64_t> present_host;  // the same words
+    };
+    std::vector<Part> parts;              // one per shard of the owner
+    size_t elem() const { return kind == SZG_COL_F64 ? sizeof(double) : sizeof(uint32_t); }
 };
 
 namespace szgi {
@@ -637,6 +659,20 @@ int search_topk_any(szg_index *ix, const double *queries, int n_queries, int k, 
                     const uint64_t *const *allow_ptrs = nullptr, const szg_mask *const *handles = nullptr);
 
 // ---- scan_mask.cpp
+// an empty mask shaped after the handle's shards, its device words allocated (not yet written); *out is set even on
+// failure (mask_free it)
+int mask_alloc(szg_index *ix, szg_mask **out);
+void mask_free(szg_mask *m);  // null is fine
+struct MaskGuard {  // frees a mask under construction on every exit path but the successful one
+    szg_mask *m = nullptr;
+    ~MaskGuard() { mask_free(m); }
+    szg_mask *release()
+    {
+        szg_mask *r = m;
+        m = nullptr;
+        return r;
+    }
+};
 // SZG_OK, or SZG_E_INVALID when the mask belongs to another handle or was made before the row count last changed
 int mask_check(const szg_index *ix, const szg_mask *m);
 const uint64_t *mask_host_words(const szg_mask *m);                 // index-level, ceil(rows / 64) words

@@ -10,7 +10,7 @@
 
 using namespace szgi;
 
-namespace {
+namespace szgi {
 
 // an empty mask shaped after the handle's shards, its device words allocated (not yet written)
 int mask_alloc(szg_index *ix, szg_mask **out)
@@ -56,6 +56,10 @@ void mask_free(szg_mask *m)
     delete m;
 }
 
+}  // namespace szgi
+
+namespace {
+
 // Part p's words are written (tail bits possibly set): clear the tail and count on the device -- a & a through the
 // combine kernel, the one popcount code -- then bring the count (and, when `download`, the words) to the host.
 int mask_finish_part(szg_mask *m, size_t s, bool download)
@@ -71,17 +75,6 @@ int mask_finish_part(szg_mask *m, size_t s, bool download)
     m->count += p.count;
     return SZG_OK;
 }
-
-struct MaskGuard {  // frees a mask under construction on every exit path but the successful one
-    szg_mask *m = nullptr;
-    ~MaskGuard() { mask_free(m); }
-    szg_mask *release()
-    {
-        szg_mask *r = m;
-        m = nullptr;
-        return r;
-    }
-};
 
 int stale(const char *what) { return fail(SZG_E_INVALID, what); }
 

@@ -247,6 +247,7 @@ int reorder_checked(szg_index *ix, const std::vector<uint64_t> &src, const std::
     }
     ix->gen++;
     const uint64_t epoch = ++ix->mask_epoch;
+    ix->col_epoch++;  // (columns are not carried: the host re-creates them)
     if (ix->sketch) {
         // the sketch index only ever grows its shards: it goes, with what it counted kept, and the next search that
         // wants a sketch builds one sized for the new rows -- so a compaction returns the sketch's memory as well

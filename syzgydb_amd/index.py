@@ -106,6 +106,135 @@ class ScanMask:
         return self._combine(_lib.SZG_MASK_NOT, None)
 
 
+_CMP_OPS = {"==": _lib.SZG_CMP_EQ, "!=": _lib.SZG_CMP_NE, "<": _lib.SZG_CMP_LT, "<=": _lib.SZG_CMP_LE,
+            ">": _lib.SZG_CMP_GT, ">=": _lib.SZG_CMP_GE}
+
+
+class ScanColumn:
+    """A metadata column that lives on the card beside the rows (szg_column): one value and one present bit per row,
+    float64 values (kind F64) or uint32 codes of a dictionary the caller owns (kind U32).  Made by ScanIndex.column;
+    where / isin / codes / present compare it against constants ON THE DEVICE and return a ScanMask.  Index appends
+    leave it short until append() catches up; a load, synth, reorder or a compaction that moves rows makes it stale
+    (every call but rows / read / close then raises SzgError, SZG_E_INVALID)."""
+
+    def __init__(self, index, handle, kind):
+        self._index = index
+        self._L = index._L
+        self._h = handle
+        self.kind = kind
+        self._dtype = np.float64 if kind == _lib.SZG_COL_F64 else np.uint32
+        index._columns[id(self)] = weakref.ref(self)
+
+    def close(self):
+        if self._h:
+            self._L.szg_column_destroy(self._h)
+            self._h = ctypes.c_void_p()
+            self._index._columns.pop(id(self), None)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def _live(self):
+        if not self._h:
+            raise ValueError("column is closed")
+        return self._h
+
+    @staticmethod
+    def _present_arg(present, n):
+        """present -> (keep-alive array, pointer): None = all present; bool[n] or uint64 words, bit i = row i."""
+        if present is None:
+            return None, None
+        a = np.asarray(present)
+        if a.dtype != np.uint64:
+            a = pack_allow_bits(a.reshape(-1).astype(bool))[0]
+        a = np.ascontiguousarray(a, dtype=np.uint64).reshape(-1)
+        if a.size != (n + 63) // 64:
+            raise ValueError("present has %d words, %d rows need %d" % (a.size, n, (n + 63) // 64))
+        return a, (_u64(a) if a.size else None)
+
+    def append(self, values, present=None):
+        """Rows behind the column's last (the index holds them already); present refers to THESE rows."""
+        v = np.ascontiguousarray(values, dtype=self._dtype).reshape(-1)
+        keep, pp = self._present_arg(present, v.size)
+        check(self._L.szg_column_append(self._live(), v.ctypes.data_as(ctypes.c_void_p) if v.size else None, pp, v.size),
+              "szg_column_append")
+        del keep
+
+    def set(self, row, value):
+        """One row's value; None marks it absent."""
+        v = None if value is None else np.asarray([value], dtype=self._dtype)
+        check(self._L.szg_column_set(self._live(), int(row), v.ctypes.data_as(ctypes.c_void_p) if v is not None else None),
+              "szg_column_set")
+
+    @property
+    def rows(self):
+        return int(self._L.szg_column_rows(self._live()))
+
+    def read(self):
+        """(values, present bool[rows]) of the whole column."""
+        n = self.rows
+        v = np.zeros(n, dtype=self._dtype)
+        w = np.zeros((n + 63) // 64, dtype=np.uint64)
+        check(self._L.szg_column_read(self._live(), self._index._row_base, n, v.ctypes.data_as(ctypes.c_void_p) if n else None,
+                                      _u64(w) if n else None), "szg_column_read")
+        return v, np.unpackbits(w.view(np.uint8), bitorder="little")[:n].astype(bool)
+
+    def _mask(self, fn, name, *args, base=None):
+        if base is not None and not isinstance(base, ScanMask):
+            raise TypeError("base is a ScanMask or None")
+        h = ctypes.c_void_p()
+        check(fn(self._live(), *args, base._live() if base is not None else None, ctypes.byref(h)), name)
+        return ScanMask(self._index, h, (self._index.rows + 63) // 64)
+
+    def where(self, op, value, base=None):
+        """Rows that are present and whose value `op` the constant (op: == != < <= > >=, or SZG_CMP_*), & base."""
+        return self._mask(self._L.szg_mask_where_f64, "szg_mask_where_f64", int(_CMP_OPS.get(op, op)), float(value),
+                          base=base)
+
+    def isin(self, values, base=None):
+        """Rows that are present and whose value equals one of up to 1024 constants, & base."""
+        v = np.ascontiguousarray(values, dtype=np.float64).reshape(-1)
+        return self._mask(self._L.szg_mask_where_in_f64, "szg_mask_where_in_f64", _f64(v) if v.size else None, v.size,
+                          base=base)
+
+    def codes(self, allowed, base=None):
+        """U32 columns: rows that are present and whose code c has allowed[c] true (a code >= len(allowed) fails)."""
+        a = np.asarray(allowed, dtype=bool).reshape(-1)
+        w = pack_allow_bits(a)[0]
+        return self._mask(self._L.szg_mask_where_u32, "szg_mask_where_u32", _u64(w) if w.size else None, a.size, base=base)
+
+    def present(self, base=None):
+        """The present rows, & base."""
+        return self._mask(self._L.szg_mask_where_present, "szg_mask_where_present", base=base)
+
+    def eq(self, value, base=None):
+        return self.where("==", value, base)
+
+    def ne(self, value, base=None):
+        return self.where("!=", value, base)
+
+    def __lt__(self, value):
+        return self.where("<", value)
+
+    def __le__(self, value):
+        return self.where("<=", value)
+
+    def __gt__(self, value):
+        return self.where(">", value)
+
+    def __ge__(self, value):
+        return self.where(">=", value)
+
+
 class ScanIndex:
     def __init__(self, dim, quant_bits, metric, devices=None):
         self._L = _lib.load()
@@ -125,6 +254,8 @@ class ScanIndex:
         self.options = {}   # tunables set through this object (the host mirrors consult tie_mode)
         self._comm = None
         self._masks = {}    # id -> weak reference of every ScanMask of this handle that is still open
+        self._columns = {}  # ... and of every ScanColumn
+        self._row_base = 0
         # SZG_OPTIONS="name=value,...": tunables applied to every new handle (test sweeps)
         for item in os.environ.get("SZG_OPTIONS", "").split(","):
             if "=" in item:
@@ -133,10 +264,11 @@ class ScanIndex:
 
     # -- lifetime -----------------------------------------------------------
     def close(self):
-        for ref in list(getattr(self, "_masks", {}).values()):  # masks are destroyed before their handle
-            m = ref()
-            if m is not None:
-                m.close()
+        for held in ("_columns", "_masks"):   # columns and masks are destroyed before their handle
+            for ref in list(getattr(self, held, {}).values()):
+                m = ref()
+                if m is not None:
+                    m.close()
         if self._h:
             self._L.szg_index_destroy(self._h)
             self._h = ctypes.c_void_p()
@@ -260,6 +392,7 @@ class ScanIndex:
 
     def set_row_base(self, base):
         check(self._L.szg_index_set_row_base(self._h, int(base)), "szg_index_set_row_base")
+        self._row_base = int(base)
 
     @property
     def rows(self):
@@ -301,6 +434,29 @@ class ScanIndex:
         check(self._L.szg_mask_create_rows(self._h, _u64(r) if r.size else None, r.size, ctypes.byref(h)),
               "szg_mask_create_rows")
         return ScanMask(self, h, (self.rows + 63) // 64)
+
+    def column(self, values, present=None, kind=None):
+        """A ScanColumn over the first len(values) rows.  kind: SZG_COL_F64 / SZG_COL_U32, or inferred from the dtype
+        (floating -> F64, integer -> U32); present: None = every row, bool per row, or uint64 words."""
+        a = np.asarray(values)
+        if kind is None:
+            if a.dtype.kind == "f":
+                kind = _lib.SZG_COL_F64
+            elif a.dtype.kind in "ui":
+                kind = _lib.SZG_COL_U32
+            else:
+                raise ValueError("cannot infer a column kind from dtype %s" % a.dtype)
+        if kind not in (_lib.SZG_COL_F64, _lib.SZG_COL_U32):
+            raise ValueError("kind is SZG_COL_F64 or SZG_COL_U32")
+        if kind == _lib.SZG_COL_U32 and a.dtype.kind in "ui" and a.size and (a.min() < 0 or a.max() > 0xFFFFFFFF):
+            raise ValueError("codes do not fit uint32")
+        v = np.ascontiguousarray(a, dtype=np.float64 if kind == _lib.SZG_COL_F64 else np.uint32).reshape(-1)
+        keep, pp = ScanColumn._present_arg(present, v.size)
+        h = ctypes.c_void_p()
+        check(self._L.szg_column_create(self._h, kind, v.ctypes.data_as(ctypes.c_void_p) if v.size else None, pp, v.size,
+                                        ctypes.byref(h)), "szg_column_create")
+        del keep
+        return ScanColumn(self, h, kind)
 
     def mask_stats(self):
         s = SzgMaskStats()
