@@ -510,6 +510,16 @@ int szg_reset_stats(szg_index *ix);
  *                             those of 1, bit for bit.  0 = automatic (4), 1 = one query per row read, 2 / 4 = that
  *                             group size where the launch qualifies; a launch of one query always reads at 1.  Other
  *                             row widths, radius / escalation sweeps, masked launches and longer lists are always 1
+ *     scan_norms          0   launches that form groups (scan_group) take every row's norm from a resident array --
+ *                             4 bytes per row, brought up to date before the sweep is enqueued when rows were added --
+ *                             instead of summing it in the sweep; the value is the same float, so keys do not change.
+ *                             0 = automatic, 1 = always sum the norms in the sweep (test and A/B hook; the environment
+ *                             variable SZG_NO_ROW_NORMS switches every resident norm off).  Without memory for the
+ *                             array the sweep sums the norms; szg_stats.scan_bytes counts row bytes only
+ *     sketch_planes       0   int8 digit planes (radix 128) of a query prepared for a sweep of the sketch: 0 = automatic
+ *                             (2: |Q| <= 16 000, the quantization step enters the certificate's bound), 3 = |Q| <= 10^6
+ *                             as on plain 8-bit handles, which always take 3.  Only queries are prepared differently:
+ *                             changing it invalidates nothing resident.  Other values are refused
  *     query_batch         16  queries staged, merged, re-ranked and copied back together
  *     mask_dense          1   sweeps whose filter / tombstone masks pass at least half the rows read every row and
  *                             apply the masks at the row finish; selective masks (and 0) compact the row steps that
@@ -608,6 +618,12 @@ int szg_debug_scan_plan(int dim, int quant_bits, uint64_t n_rows, int kp, int co
  */
 int szg_debug_scan_group(int dim, int quant_bits, int kp, int collect, int masked, int scan_group, int n_queries,
                          int queries_per_launch, int32_t *group, uint64_t *lds_bytes, int32_t *passes);
+
+/*
+ * Test hook, host only: would szg_set_option accept `value` for the one-sweep kernel's option `name` (scan_group,
+ * scan_norms, sketch_planes)?  SZG_OK, or SZG_E_INVALID with szg_set_option's text; any other name is refused.
+ */
+int szg_debug_option_check(const char *name, int64_t value);
 
 /*
  * Test hook, host only: the checks szg_index_reorder makes on its list before anything moves, and the split of the

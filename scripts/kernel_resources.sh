@@ -4,6 +4,9 @@
 #   scripts/kernel_resources.sh mq bf16 32    -> kernels_mq_bf16.hip -DSZG_ROW_BITS=32    (also: mq bf16d)
 #   scripts/kernel_resources.sh mq select     -> kernels_mq.hip (the selection kernels)
 #   scripts/kernel_resources.sh scan 32       -> kernels_scan.hip -DSZG_QBITS=32
+#   VFLAGS="-DSZG_SCAN_METRIC=1 -DSZG_GROUP_FORM=3" scripts/kernel_resources.sh scan 8
+#                                             -> one metric's G > 1 kernels of one form (bit 0: two planes, bit 1: resident
+#                                                norms); without SZG_GROUP_FORM: the metric's G = 1 kernels
 #   scripts/kernel_resources.sh exact         -> kernels_exact.hip (re-rank, page-in, row gather, ...)
 #   scripts/kernel_resources.sh mask          -> kernels_mask.hip (device-resident filter masks)
 #   scripts/kernel_resources.sh column        -> kernels_column.hip (resident metadata columns)

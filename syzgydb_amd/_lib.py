@@ -44,7 +44,7 @@ EXPORTS = [
     "szg_column_create", "szg_column_append", "szg_column_set", "szg_column_rows", "szg_column_read",
     "szg_column_destroy", "szg_mask_where_f64", "szg_mask_where_in_f64", "szg_mask_where_u32", "szg_mask_where_present",
     # host-only test hook
-    "szg_debug_scan_plan", "szg_debug_scan_group", "szg_debug_reorder_plan",
+    "szg_debug_scan_plan", "szg_debug_scan_group", "szg_debug_reorder_plan", "szg_debug_option_check",
 ]
 SZG_MASK_AND, SZG_MASK_OR, SZG_MASK_ANDNOT, SZG_MASK_NOT = 0, 1, 2, 3
 SZG_COL_F64, SZG_COL_U32 = 0, 1
@@ -299,6 +299,9 @@ def load():
         L.szg_debug_scan_group.restype = ctypes.c_int
         L.szg_debug_scan_group.argtypes = [ctypes.c_int] * 8 + [ctypes.POINTER(ctypes.c_int32), u64p,
                                                                 ctypes.POINTER(ctypes.c_int32)]
+    if hasattr(L, "szg_debug_option_check"):
+        L.szg_debug_option_check.restype = ctypes.c_int
+        L.szg_debug_option_check.argtypes = [ctypes.c_char_p, ctypes.c_int64]
     L.szg_debug_f64_probe.restype = ctypes.c_int
     L.szg_debug_f64_probe.argtypes = [ctypes.c_int, f64p, f64p, f64p, ctypes.c_uint64]
     _lib = L

@@ -143,6 +143,11 @@ struct ScanArgs {
     uint64_t *collect_buf;
     uint32_t collect_cap;
     uint32_t *collect_count;
+    // (behind everything the kernels without groups read: their argument offsets, and so their code, stay as they were)
+    const float *row_norm;      // nullable: resident norms of rows [0, n_rows) (launch_row_norms' 8-bit form).  A launch
+                                // that takes a G > 1 variant reads them instead of summing the norm in the sweep.
+    int planes;                 // 8-bit rows: int8 digit planes the queries carry, 3 (0 means 3) or 2 -- the h plane of
+                                // the image is all zero; G > 1 variants then neither stage nor read it
 };
 
 // Which scan_kernel instantiation a launch takes: decided on the host by scan_variant -- the launcher dispatches on
@@ -157,18 +162,21 @@ struct ScanVariant {
 // What "automatic" (scan_group = 0) asks for, where a launch qualifies.
 constexpr int kScanGroupAuto = 4;
 // group: the scan_group option (0 = automatic), n_queries: the launch's, block: its threads (the group's query images
-// and lists have to fit 64 KiB of LDS)
+// -- of `planes` digit planes each -- and lists have to fit 64 KiB of LDS)
 ScanVariant scan_variant(int qbits, const RowMap &m, bool tiled, int kp, bool collect, bool masked, int ring,
-                         bool no_shape_kernels, int group = 1, int n_queries = 1, int block = 256);
+                         bool no_shape_kernels, int group = 1, int n_queries = 1, int block = 256, int planes = 3);
 inline bool scan_masked(const ScanArgs &a) { return a.live_bits != nullptr || a.allow_bits != nullptr; }
 // passes over the rows that launch_scan makes for `a`: one per group of its queries
 int scan_passes(int qbits, const ScanArgs &a, int block);
+// queries per row read of the variant launch_scan takes for `a`
+int scan_group_of(int qbits, const ScanArgs &a, int block);
 
 // Fused dequantize + distance + select.  QBITS in {4,8,16,32,64}.
 hipError_t launch_scan(int qbits, int metric, const ScanArgs &a, int grid, int block,
                        hipStream_t stream);
-// LDS bytes launch_scan needs for (qbits, map, kp, block) at `group` queries per row read
-size_t scan_lds_bytes(int qbits, const RowMap &m, int kp, int block, int group = 1);
+// LDS bytes launch_scan needs for (qbits, map, kp, block) at `group` queries per row read; planes = 2: the images of a
+// group (group > 1, 8-bit rows) hold two digit planes
+size_t scan_lds_bytes(int qbits, const RowMap &m, int kp, int block, int group = 1, int planes = 3);
 
 // Merge n_lists sorted lists of kp candidates into ceil(n_lists/merge_fan(kp)) lists.
 int merge_fan(int kp);

@@ -27,6 +27,30 @@
 
 namespace szg {
 
+#if SZG_QBITS != 0 && !defined(SZG_GROUP_FORM)
+// the G > 1 kernels of 8-bit rows, one object per metric and form (see SZG_GROUP_FORM below)
+#define SZG_DECL_G8(mm, ff) \
+    hipError_t launch_scan_g8m##mm##f##ff(const ScanArgs &, const ScanVariant &, int, int, size_t, hipStream_t);
+SZG_DECL_G8(0, 0) SZG_DECL_G8(0, 1) SZG_DECL_G8(0, 2) SZG_DECL_G8(0, 3)
+SZG_DECL_G8(1, 0) SZG_DECL_G8(1, 1) SZG_DECL_G8(1, 2) SZG_DECL_G8(1, 3)
+#undef SZG_DECL_G8
+static hipError_t launch_scan_g8(int metric, int form, const ScanArgs &a, const ScanVariant &v, int grid, int block, size_t lds,
+                                 hipStream_t stream)
+{
+#define SZG_CASE_G8(ff)                                                                       \
+    case ff: return metric == kCosine ? launch_scan_g8m1f##ff(a, v, grid, block, lds, stream) \
+                                      : launch_scan_g8m0f##ff(a, v, grid, block, lds, stream);
+    switch (form) {
+    SZG_CASE_G8(0)
+    SZG_CASE_G8(1)
+    SZG_CASE_G8(2)
+    SZG_CASE_G8(3)
+    default: return hipErrorInvalidValue;
+    }
+#undef SZG_CASE_G8
+}
+#endif
+
 namespace {
 
 constexpr int kWave = 64;
@@ -309,14 +333,22 @@ struct RowAcc<8, METRIC> {
 // apart.  A piece of the row is loaded, xor-ed and summed into the row norm (SQ, SV) once; each query of the group
 // then costs its three plane reads and 12 v_dot4.  The arithmetic is RowAcc<8>'s, integer and exact, and the key
 // is formed by the same float operations: a query's key for a row does not depend on how the queries are grouped.
-template <int METRIC, int G>
+// PL = 2: the queries carry two digit planes (|Q| <= 16000, a sketch index): the images in LDS hold the m and l planes
+// only, `2 * r16 * 16` bytes apart, and a query costs two reads and 8 v_dot4; the key fmaf(128, M, L) is the float the
+// three-plane form computes on the all-zero h plane.  NF: the row's norm comes from the resident array (the kernel
+// loads it), SQ / SV are not summed.
+template <int METRIC, int G, int PL = 3, bool NF = false>
 struct RowAccGroup8 {
+    static_assert(PL == 2 || PL == 3, "two or three digit planes");
     static constexpr bool kPrefetch = false;
-    int H[G], M[G], L[G], SQ, SV;
+    int H[PL == 3 ? G : 1], M[G], L[G], SQ, SV;
     __device__ __forceinline__ void reset()
     {
 #pragma unroll
-        for (int x = 0; x < G; x++) H[x] = M[x] = L[x] = 0;
+        for (int x = 0; x < G; x++) {
+            if constexpr (PL == 3) H[x] = 0;
+            M[x] = L[x] = 0;
+        }
         SQ = SV = 0;
     }
     __device__ __forceinline__ void fetch(const uint8_t *, int, int) {}
@@ -325,22 +357,28 @@ struct RowAccGroup8 {
     {
         const uint32_t w[4] = {raw.x ^ 0x80808080u, raw.y ^ 0x80808080u, raw.z ^ 0x80808080u,
                                raw.w ^ 0x80808080u};
+        if constexpr (!NF) {
 #pragma unroll
-        for (int d = 0; d < 4; d++) {
-            SQ = __builtin_amdgcn_sdot4((int)w[d], (int)w[d], SQ, false);
-            SV = __builtin_amdgcn_sdot4((int)w[d], 0x01010101, SV, false);
+            for (int d = 0; d < 4; d++) {
+                SQ = __builtin_amdgcn_sdot4((int)w[d], (int)w[d], SQ, false);
+                SV = __builtin_amdgcn_sdot4((int)w[d], 0x01010101, SV, false);
+            }
         }
-        const int qbytes = (int)query_lds_bytes(8, r16);
+        const int qbytes = PL * r16 * 16;
 #pragma unroll
         for (int x = 0; x < G; x++) {
             const uint4 *q4 = reinterpret_cast<const uint4 *>(q + x * qbytes);
-            const uint4 qh = q4[j], qm = q4[r16 + j], ql = q4[2 * r16 + j];
-            const uint32_t h[4] = {qh.x, qh.y, qh.z, qh.w};
+            if constexpr (PL == 3) {
+                const uint4 qh = q4[j];
+                const uint32_t h[4] = {qh.x, qh.y, qh.z, qh.w};
+#pragma unroll
+                for (int d = 0; d < 4; d++) H[x] = __builtin_amdgcn_sdot4((int)h[d], (int)w[d], H[x], false);
+            }
+            const uint4 qm = q4[(PL - 2) * r16 + j], ql = q4[(PL - 1) * r16 + j];
             const uint32_t m[4] = {qm.x, qm.y, qm.z, qm.w};
             const uint32_t l[4] = {ql.x, ql.y, ql.z, ql.w};
 #pragma unroll
             for (int d = 0; d < 4; d++) {
-                H[x] = __builtin_amdgcn_sdot4((int)h[d], (int)w[d], H[x], false);
                 M[x] = __builtin_amdgcn_sdot4((int)m[d], (int)w[d], M[x], false);
                 L[x] = __builtin_amdgcn_sdot4((int)l[d], (int)w[d], L[x], false);
             }
@@ -349,7 +387,10 @@ struct RowAccGroup8 {
         // selection puts the dots of the group's later queries off to the end of an unrolled row: their digit planes and
         // the row's xor-ed pieces then stay in registers for the whole row -- 256 registers and spills at G = 2 already.
 #pragma unroll
-        for (int x = 0; x < G; x++) asm volatile("" : "+v"(H[x]), "+v"(M[x]), "+v"(L[x]));
+        for (int x = 0; x < G; x++) {
+            if constexpr (PL == 3) asm volatile("" : "+v"(H[x]));
+            asm volatile("" : "+v"(M[x]), "+v"(L[x]));
+        }
     }
     // the row's norm, reduced once for the whole group (norm_bias is the launch's)
     __device__ __forceinline__ float finish_norm(const QConst &a, const Grp &g)
@@ -359,7 +400,8 @@ struct RowAccGroup8 {
     }
     __device__ __forceinline__ float finish_key(int x, float norm, const QConst &a, const Grp &g)
     {
-        float dot = fmaf(16384.0f, (float)H[x], fmaf(128.0f, (float)M[x], (float)L[x]));
+        float dot = fmaf(128.0f, (float)M[x], (float)L[x]);
+        if constexpr (PL == 3) dot = fmaf(16384.0f, (float)H[x], dot);  // (H == 0: the same float as without)
         dot = grp_sum(dot, g);
         return RowAcc<8, METRIC>::key_of(dot, norm, a);
     }
@@ -452,12 +494,19 @@ struct RowAcc<4, METRIC> {
 // G > 1 (8-bit top-k sweeps without masks, lists in registers): the launch's queries are walked in groups of up to G
 // consecutive ones, every group in ONE pass over the rows -- G query images, G wave lists and G accumulator triples
 // per lane against one load of each piece (RowAccGroup8).  G = 1 is the kernel without groups.
-template <int QBITS, int METRIC, int D, bool COLLECT, bool MASKED, bool NT, int LL = 0, int PP = 0, int G = 1>
+// Two compile-time forms of the G > 1 kernels beside today's (PL = 3, NF = false):
+//  PL = 2  the launch's queries carry two digit planes (ScanArgs::planes): G images of 2 * r16 * 16 bytes in LDS.
+//  NF      the rows' norms are resident (ScanArgs::row_norm): a row's norm is loaded a whole row ahead, in front of the
+//          load of the row's first piece -- loads return in order, so the ring's counted wait for that piece covers it
+//          and no wait changes -- and sits in the ring slot's own register (nring) until the piece is consumed.
+template <int QBITS, int METRIC, int D, bool COLLECT, bool MASKED, bool NT, int LL = 0, int PP = 0, int G = 1, int PL = 3,
+          bool NF = false>
 __global__ __launch_bounds__(256, G > 1 ? kGroupMinBlocks : SZG_MIN_BLOCKS) void scan_kernel(const ScanArgs a)
 {
     static_assert((LL == 0) == (PP == 0), "shape is fixed as a whole or not at all");
     static_assert(G == 1 || (QBITS == 8 && !COLLECT && !MASKED), "groups: unmasked 8-bit top-k sweeps only");
-    using Acc = std::conditional_t<G == 1, RowAcc<QBITS, METRIC>, RowAccGroup8<METRIC, G>>;
+    static_assert(G > 1 || (PL == 3 && !NF), "the kernel without groups has one form");
+    using Acc = std::conditional_t<G == 1, RowAcc<QBITS, METRIC>, RowAccGroup8<METRIC, G, PL, NF>>;
     extern __shared__ __align__(16) uint8_t smem[];
 
     const int tid = threadIdx.x;
@@ -465,7 +514,8 @@ __global__ __launch_bounds__(256, G > 1 ? kGroupMinBlocks : SZG_MIN_BLOCKS) void
     const int wave = tid >> 6;
     const int nwaves = blockDim.x >> 6;
     const int r16 = LL ? LL * PP : a.map.r16;
-    const int qbytes = (int)query_lds_bytes(QBITS, r16);  // multiple of 16
+    const int qbytes = PL == 2 ? 2 * r16 * 16 : (int)query_lds_bytes(QBITS, r16);  // an image in LDS; multiple of 16
+    const int qskip = PL == 2 ? r16 * 16 : 0;  // two planes: the (all-zero) h plane in front of the image stays behind
 
     // LDS: G query images | G x nwaves wave lists ([query of the group][wave][kp]) | step lists
     uint64_t *lists = reinterpret_cast<uint64_t *>(smem + G * qbytes);
@@ -491,7 +541,7 @@ __global__ __launch_bounds__(256, G > 1 ? kGroupMinBlocks : SZG_MIN_BLOCKS) void
 #pragma unroll
     for (int x = 0; x < G; x++) {   // stage the query into LDS (it is L2-resident after the first block)
         const uint4 *src = reinterpret_cast<const uint4 *>(
-            reinterpret_cast<const uint8_t *>(a.query) + (size_t)slot_query(x) * a.query_stride);
+            reinterpret_cast<const uint8_t *>(a.query) + (size_t)slot_query(x) * a.query_stride + qskip);
         uint4 *dst = reinterpret_cast<uint4 *>(smem + x * qbytes);
         for (int i = tid; i < qbytes / 16; i += blockDim.x) dst[i] = src[i];
     }
@@ -542,10 +592,14 @@ __global__ __launch_bounds__(256, G > 1 ? kGroupMinBlocks : SZG_MIN_BLOCKS) void
     [[maybe_unused]] const float thr_key = COLLECT ? key_from_ordered(thr_ukey) : 0.0f;
     [[maybe_unused]] uint64_t *const cbuf = COLLECT ? a.collect_buf + (size_t)qi * a.collect_cap : nullptr;
     [[maybe_unused]] uint32_t *const ccount = COLLECT ? a.collect_count + (size_t)qi * kCandCountStride : nullptr;
+    [[maybe_unused]] float nring[NF ? D : 1];  // NF: the norm loaded with the piece in ring slot u (a row's first)
+    [[maybe_unused]] float norm_cur = 0.0f;    // NF: the norm of the row being consumed
     auto finish_row = [&](uint64_t row0, bool valid, Acc &acc) {
         if constexpr (G > 1) {  // one norm for the row, then each query of the group: its key, its pre-filter, its list
             const bool leader = valid && lig == 0;
-            const float norm = acc.finish_norm(qcs[0], grp_info);
+            float norm;
+            if constexpr (NF) norm = norm_cur;
+            else norm = acc.finish_norm(qcs[0], grp_info);
             const uint32_t row = (uint32_t)(row0 + grp);
 #pragma unroll
             for (int x = 0; x < G; x++) {
@@ -730,8 +784,15 @@ __global__ __launch_bounds__(256, G > 1 ? kGroupMinBlocks : SZG_MIN_BLOCKS) void
                                   (uint64_t)(P - 1) * piece_step;
         int ip = 0, cp = 0, jc = lig;
         acc.fetch(smem, lig, r16);
+        [[maybe_unused]] const float *nptr = NF ? a.row_norm + row_first + grp : nullptr;  // (rows of the dense phase: in range)
 #define SZG_DN_ISSUE(u)                                                                 \
     {                                                                                   \
+        if constexpr (NF) {                                                             \
+            if (ip == 0) {                                                              \
+                nring[u] = *nptr;                                                       \
+                nptr += stride;                                                         \
+            }                                                                           \
+        }                                                                               \
         ring[u] = load_piece<NT>(iptr);                                                     \
         if (++ip == P) {                                                                \
             ip = 0;                                                                     \
@@ -742,6 +803,9 @@ __global__ __launch_bounds__(256, G > 1 ? kGroupMinBlocks : SZG_MIN_BLOCKS) void
     }
 #define SZG_DN_CONSUME(u)                                                               \
     {                                                                                   \
+        if constexpr (NF) {                                                             \
+            if (cp == 0) norm_cur = nring[u];                                           \
+        }                                                                               \
         const u32x4 v_ = ring[u];                                                       \
         if constexpr (Acc::kPrefetch)                                                   \
             acc.piece_pf(make_uint4(v_.x, v_.y, v_.z, v_.w), smem, cp + 1 == P ? lig : jc + L, r16); \
@@ -830,6 +894,9 @@ __global__ __launch_bounds__(256, G > 1 ? kGroupMinBlocks : SZG_MIN_BLOCKS) void
     {                                                                                   \
         const int j_ = ip * L + lig;                                                    \
         const bool ok_ = ivalid && j_ < r16;                                            \
+        if constexpr (NF) {                                                             \
+            if (ip == 0) nring[u] = a.row_norm[ivalid ? irow : 0]; /* (n_rows > 0) */   \
+        }                                                                               \
         ring[u] = load_piece<NT>(ok_ ? a.rows + piece_offset(glay, irow, (uint32_t)j_) : a.rows); \
         okmask = (okmask & ~(1u << (u))) | ((uint32_t)ok_ << (u));                      \
         if (++ip == P) {                                                                \
@@ -851,6 +918,9 @@ __global__ __launch_bounds__(256, G > 1 ? kGroupMinBlocks : SZG_MIN_BLOCKS) void
         const int j_ = cp * L + lig;                                                    \
         const bool ok_ = (okmask >> (u)) & 1u;                                          \
         if (cp == 0) cvalid = ok_; /* piece 0 of the group's first lane is in range */  \
+        if constexpr (NF) {                                                             \
+            if (cp == 0) norm_cur = nring[u];                                           \
+        }                                                                               \
         if (ok_) {                                                                      \
             const u32x4 v_ = ring[u];                                                   \
             acc.piece(make_uint4(v_.x, v_.y, v_.z, v_.w), smem, j_, r16, a.dim);                 \
@@ -1123,34 +1193,35 @@ constexpr int kRingShort = 4, kRingDeep = 8;
 
 #if SZG_QBITS != 0
 
-template <int QBITS, int METRIC, bool COLLECT, int LL, int PP, int D, int G = 1>
+template <int QBITS, int METRIC, bool COLLECT, int LL, int PP, int D, int G = 1, int PL = 3, bool NF = false>
 hipError_t launch_shaped(const ScanArgs &a, bool nt, dim3 g, dim3 b, size_t lds, hipStream_t stream)
 {
     if (nt)
-        hipLaunchKernelGGL((scan_kernel<QBITS, METRIC, D, COLLECT, false, true, LL, PP, G>), g, b, lds, stream, a);
+        hipLaunchKernelGGL((scan_kernel<QBITS, METRIC, D, COLLECT, false, true, LL, PP, G, PL, NF>), g, b, lds, stream, a);
     else
-        hipLaunchKernelGGL((scan_kernel<QBITS, METRIC, D, COLLECT, false, false, LL, PP, G>), g, b, lds, stream, a);
+        hipLaunchKernelGGL((scan_kernel<QBITS, METRIC, D, COLLECT, false, false, LL, PP, G, PL, NF>), g, b, lds, stream, a);
     return hipGetLastError();
 }
 
-template <int QBITS, int METRIC, bool COLLECT, bool MASKED, int D, int G = 1>
+template <int QBITS, int METRIC, bool COLLECT, bool MASKED, int D, int G = 1, int PL = 3, bool NF = false>
 hipError_t launch_any_shape(const ScanArgs &a, bool nt, dim3 g, dim3 b, size_t lds, hipStream_t stream)
 {
     if (nt)  // whole lines per load instruction: stream past the caches
-        hipLaunchKernelGGL((scan_kernel<QBITS, METRIC, D, COLLECT, MASKED, true, 0, 0, G>), g, b, lds, stream, a);
+        hipLaunchKernelGGL((scan_kernel<QBITS, METRIC, D, COLLECT, MASKED, true, 0, 0, G, PL, NF>), g, b, lds, stream, a);
     else
-        hipLaunchKernelGGL((scan_kernel<QBITS, METRIC, D, COLLECT, MASKED, false, 0, 0, G>), g, b, lds, stream, a);
+        hipLaunchKernelGGL((scan_kernel<QBITS, METRIC, D, COLLECT, MASKED, false, 0, 0, G, PL, NF>), g, b, lds, stream, a);
     return hipGetLastError();
 }
 
 // the kernels of group size G (scan_variant's choice; G > 1 exists for unmasked 8-bit top-k sweeps with the short ring)
-template <int QBITS, int METRIC, bool COLLECT, bool MASKED, int G>
+// in the form (PL digit planes, NF: resident norms) the launch's arguments ask for
+template <int QBITS, int METRIC, bool COLLECT, bool MASKED, int G, int PL = 3, bool NF = false>
 hipError_t launch_scan_group(const ScanArgs &a, const ScanVariant &v, dim3 g, dim3 b, size_t lds, hipStream_t stream)
 {
     if constexpr (!MASKED) {
 #define SZG_TRY_SHAPE(l, p, d)                                                                 \
     if (v.shaped == l * 100 + p)                                                               \
-        return launch_shaped<QBITS, METRIC, COLLECT, l, p, SZG_SHAPE_RING(d), G>(a, v.nontemporal != 0, g, b, lds, stream);
+        return launch_shaped<QBITS, METRIC, COLLECT, l, p, SZG_SHAPE_RING(d), G, PL, NF>(a, v.nontemporal != 0, g, b, lds, stream);
         if constexpr (QBITS == 4) {
             SZG_SHAPES_4(SZG_TRY_SHAPE)
         } else if constexpr (QBITS == 8) {
@@ -1171,19 +1242,22 @@ hipError_t launch_scan_group(const ScanArgs &a, const ScanVariant &v, dim3 g, di
     } else if (v.deep) {
         return hipErrorInvalidValue;
     }
-    return launch_any_shape<QBITS, METRIC, COLLECT, MASKED, kRingShort, G>(a, v.nontemporal != 0, g, b, lds, stream);
+    return launch_any_shape<QBITS, METRIC, COLLECT, MASKED, kRingShort, G, PL, NF>(a, v.nontemporal != 0, g, b, lds, stream);
 }
+
+#ifndef SZG_GROUP_FORM
 
 template <int QBITS, int METRIC, bool COLLECT, bool MASKED>
 hipError_t launch_scan_qmcm(const ScanArgs &a, int grid, int block, hipStream_t stream)
 {
     const dim3 g(grid), b(block);
     const ScanVariant v = scan_variant(QBITS, a.map, a.tiled != 0, a.kp, COLLECT, MASKED, a.ring, a.no_shape_kernels != 0,
-                                       a.group, a.n_queries, block);
-    const size_t lds = scan_lds_bytes(QBITS, a.map, COLLECT ? 0 : a.kp, block, v.group);
+                                       a.group, a.n_queries, block, a.planes);
+    const size_t lds = scan_lds_bytes(QBITS, a.map, COLLECT ? 0 : a.kp, block, v.group, a.planes);
     if constexpr (QBITS == 8 && !COLLECT && !MASKED) {
-        if (v.group == 4) return launch_scan_group<QBITS, METRIC, COLLECT, MASKED, 4>(a, v, g, b, lds, stream);
-        if (v.group == 2) return launch_scan_group<QBITS, METRIC, COLLECT, MASKED, 2>(a, v, g, b, lds, stream);
+        // G > 1: the form of the kernel -- two digit planes where the queries carry two (bit 0), resident norms where
+        // the launch has them (bit 1); every form is an object of its own (SZG_GROUP_FORM)
+        if (v.group > 1) return launch_scan_g8(METRIC, (a.planes == 2 ? 1 : 0) | (a.row_norm ? 2 : 0), a, v, grid, block, lds, stream);
     }
     if (v.group != 1) return hipErrorInvalidValue;
     return launch_scan_group<QBITS, METRIC, COLLECT, MASKED, 1>(a, v, g, b, lds, stream);
@@ -1200,6 +1274,7 @@ hipError_t launch_scan_qm(const ScanArgs &a, int grid, int block, hipStream_t st
     if (masked) return launch_scan_qmcm<QBITS, METRIC, false, true>(a, grid, block, stream);
     return launch_scan_qmcm<QBITS, METRIC, false, false>(a, grid, block, stream);
 }
+#endif  // !SZG_GROUP_FORM
 
 #endif  // SZG_QBITS != 0
 
@@ -1214,11 +1289,28 @@ hipError_t launch_scan_qm(const ScanArgs &a, int grid, int block, hipStream_t st
 #ifndef SZG_SCAN_METRIC
 #error "kernels_scan.hip with SZG_QBITS needs SZG_SCAN_METRIC (0 or 1)"
 #endif
+#ifdef SZG_GROUP_FORM
+// ... or, with -DSZG_GROUP_FORM=0..3 (8-bit rows), the G = 2 and G = 4 kernels of ONE form and nothing else: bit 0 = two
+// digit planes, bit 1 = resident norms.  Eight objects of twelve kernels: in one unit per metric they took five minutes.
+hipError_t SZG_CAT(SZG_CAT(launch_scan_g8m, SZG_SCAN_METRIC), SZG_CAT(f, SZG_GROUP_FORM))(const ScanArgs &a, const ScanVariant &v,
+                                                                                      int grid, int block, size_t lds,
+                                                                                      hipStream_t stream)
+{
+    static_assert(SZG_QBITS == 8, "groups: 8-bit rows");
+    constexpr int PL = (SZG_GROUP_FORM & 1) ? 2 : 3;
+    constexpr bool NF = (SZG_GROUP_FORM & 2) != 0;
+    const dim3 g(grid), b(block);
+    if (v.group == 4) return launch_scan_group<8, SZG_SCAN_METRIC, false, false, 4, PL, NF>(a, v, g, b, lds, stream);
+    if (v.group == 2) return launch_scan_group<8, SZG_SCAN_METRIC, false, false, 2, PL, NF>(a, v, g, b, lds, stream);
+    return hipErrorInvalidValue;
+}
+#else
 hipError_t SZG_CAT(SZG_CAT(launch_scan_q, SZG_QBITS), SZG_CAT(m, SZG_SCAN_METRIC))(const ScanArgs &a, int grid, int block,
                                                                                  hipStream_t stream)
 {
     return launch_scan_qm<SZG_QBITS, SZG_SCAN_METRIC>(a, grid, block, stream);
 }
+#endif  // SZG_GROUP_FORM
 #else
 #define SZG_DECL_SCAN(q)                                                          \
     hipError_t launch_scan_q##q##m0(const ScanArgs &, int, int, hipStream_t); \
@@ -1233,7 +1325,7 @@ SZG_DECL_SCAN(64)
 // The instantiation a launch takes.  Row-shape kernels serve unmasked sweeps over dense maps whose lists stay in
 // registers; everything else is the any-shape kernel, with the deep ring when the lists live in LDS (kp > 64).
 ScanVariant scan_variant(int qbits, const RowMap &m, bool tiled, int kp, bool collect, bool masked, int ring,
-                         bool no_shape_kernels, int group, int n_queries, int block)
+                         bool no_shape_kernels, int group, int n_queries, int block, int planes)
 {
     ScanVariant v{};
     v.deep = ((!collect && kp > 64) || ring >= 8) ? 1 : 0;
@@ -1262,24 +1354,32 @@ ScanVariant scan_variant(int qbits, const RowMap &m, bool tiled, int kp, bool co
         int g = group == 0 ? kScanGroupAuto : group;
         if (g != 2 && g != 4) g = 1;
         while (g > 1 && g / 2 >= n_queries) g /= 2;
-        while (g > 1 && scan_lds_bytes(qbits, m, kp, block, g) > 64u * 1024u) g /= 2;
+        while (g > 1 && scan_lds_bytes(qbits, m, kp, block, g, planes) > 64u * 1024u) g /= 2;
         v.group = g;
     }
     return v;
 }
 
-size_t scan_lds_bytes(int qbits, const RowMap &m, int kp, int block, int group)
+size_t scan_lds_bytes(int qbits, const RowMap &m, int kp, int block, int group, int planes)
 {
     // per query of a group: query image + per-wave candidate lists; per-wave lists of row steps that survive the masks
-    return (size_t)group * (query_lds_bytes(qbits, m.r16) + (size_t)(block / kWave) * kp * sizeof(uint64_t)) +
+    // (the two-plane images exist in the G > 1 kernels only: a lone query stages the whole image, its h plane all zero)
+    const size_t image = qbits == 8 && group > 1 && planes == 2 ? (size_t)m.r16 * 32 : query_lds_bytes(qbits, m.r16);
+    return (size_t)group * (image + (size_t)(block / kWave) * kp * sizeof(uint64_t)) +
            (size_t)(block / kWave) * kStepList * sizeof(uint32_t);
+}
+
+int scan_group_of(int qbits, const ScanArgs &a, int block)
+{
+    return scan_variant(qbits, a.map, a.tiled != 0, a.kp, a.collect != 0, scan_masked(a), a.ring, a.no_shape_kernels != 0,
+                        a.group, a.n_queries, block, a.planes)
+        .group;
 }
 
 int scan_passes(int qbits, const ScanArgs &a, int block)
 {
-    const ScanVariant v = scan_variant(qbits, a.map, a.tiled != 0, a.kp, a.collect != 0, scan_masked(a), a.ring,
-                                       a.no_shape_kernels != 0, a.group, a.n_queries, block);
-    return (a.n_queries + v.group - 1) / v.group;
+    const int group = scan_group_of(qbits, a, block);
+    return (a.n_queries + group - 1) / group;
 }
 
 hipError_t launch_scan(int qbits, int metric, const ScanArgs &a, int grid, int block,

@@ -636,11 +636,34 @@ int szg_reset_stats(szg_index *ix)
     return SZG_OK;
 }
 
+// the value ranges of the one-sweep kernel's options: the refusal's text, null when the value is accepted (*known:
+// the name is one of them).  szg_set_option and the host-only szg_debug_option_check ask here.
+static const char *scan_option_refusal(const std::string &n, int64_t value, bool *known)
+{
+    *known = true;
+    if (n == "scan_group") return value == 0 || value == 1 || value == 2 || value == 4 ? nullptr : "scan_group is 0, 1, 2 or 4";
+    if (n == "scan_norms") return value == 0 || value == 1 ? nullptr : "scan_norms is 0 or 1";
+    if (n == "sketch_planes") return value == 0 || value == 2 || value == 3 ? nullptr : "sketch_planes is 0, 2 or 3";
+    *known = false;
+    return nullptr;
+}
+
+int szg_debug_option_check(const char *name, int64_t value)
+{
+    if (!name) return fail(SZG_E_INVALID, "null argument");
+    bool known;
+    const char *why = scan_option_refusal(name, value, &known);
+    if (!known) return fail(SZG_E_INVALID, "not an option of the one-sweep kernel");
+    return why ? fail(SZG_E_INVALID, why) : SZG_OK;
+}
+
 int szg_set_option(szg_index *ix, const char *name, int64_t value)
 {
     SZG_TRY
     if (!ix || !name) return fail(SZG_E_INVALID, "null argument");
     const std::string n(name);
+    bool scan_opt;
+    if (const char *why = scan_option_refusal(n, value, &scan_opt)) return fail(SZG_E_INVALID, why);
     if (n == "sketch") {
         if (value < 0 || value > 2) return fail(SZG_E_INVALID, "sketch is 0, 1 or 2");
         ix->sketch_on = (int)value;
@@ -673,8 +696,12 @@ int szg_set_option(szg_index *ix, const char *name, int64_t value)
             return fail(SZG_E_INVALID, "queries_per_launch out of range");
         ix->queries_per_launch = (int)value;
     } else if (n == "scan_group") {
-        if (value != 0 && value != 1 && value != 2 && value != 4) return fail(SZG_E_INVALID, "scan_group is 0, 1, 2 or 4");
         ix->scan_group = (int)value;
+    } else if (n == "scan_norms") {
+        ix->scan_norms = (int)value;
+    } else if (n == "sketch_planes") {
+        // (only queries are prepared differently: nothing resident depends on it)
+        ix->sketch_planes = (int)value;
     } else if (n == "query_batch") {
         if (value < 1 || value > kMaxBatch) return fail(SZG_E_INVALID, "query_batch out of range");
         ix->query_batch = (int)value;

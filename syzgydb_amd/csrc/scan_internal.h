@@ -435,6 +435,11 @@ struct szg_index {
     int queries_per_launch = 16;  // sweeps one scan launch walks back to back (query-major)
     int scan_group = 0;       // queries of a launch the one-sweep kernel scores per row read, where the launch qualifies
                               // (8-bit rows, top-k, no masks, lists in registers): 0 = automatic, 1, 2 or 4
+    int scan_norms = 0;       // grouped one-sweep launches take the rows' norms from the resident array (ensure_row_norms):
+                              // 0 = automatic, 1 = always sum them in the sweep
+    int sketch_planes = 0;    // digit planes of a query prepared for a sketch sweep: 0 = automatic (2, |Q| <= 16000),
+                              // 3 = the plain 8-bit handles' (|Q| <= 10^6).  Only is_sketch indexes read it (scan_planes).
+    bool is_sketch = false;   // this index is the internal sketch of a float32 handle: its keys only bound
     int tie_mode = 0;         // 0: exact full replay on ties/NaN, 1: keep the fast answer
     int serialize_scans = 1;  // scan launches of a shard never overlap each other
     int multi_query = 1;      // share one sweep between the queries of a batch (MFMA path)
@@ -548,6 +553,11 @@ int row_format(int dim, int quant_bits, RowFormat *f);
 void prep_query(const szg_index *ix, const double *q, uint8_t *out_sw, QMeta *meta);
 void prep_query_meta(const szg_index *ix, const double *q, QMeta *meta);  // the constants only (shared sweeps)
 double key_eps(const szg_index *ix, double key, const QMeta &m);
+// int8 digit planes of a query prepared for a one-sweep scan of ix's 8-bit rows, and the largest |Q| they carry: a
+// sketch index takes 2 (16000, option sketch_planes), every other handle 3 (10^6).  prep_query, key_eps and the
+// launch (ScanArgs::planes) all ask here.
+int scan_planes(const szg_index *ix);
+inline double scan_qmax8(const szg_index *ix) { return scan_planes(ix) == 2 ? 16000.0 : 1000000.0; }
 // (radius: the batch is a radius batch -- tiled 8-bit rows then stay on the exact int8 sweep: the bfloat16 sweep's
 // band around every radius would collect several times the hits)
 // nq: the queries of the batch in question -- 8-bit rows take the bfloat16 sweep only for MORE than 48 of them (up to 48
@@ -640,6 +650,10 @@ int search_radius_impl(szg_index *ix, const double *queries, int n_queries, cons
 // ---- scan_mq.cpp
 // the shard's resident row norms are complete (16-bit rows; no-op otherwise): called before a shared sweep is enqueued
 int ensure_row_norms(szg_index *ix, Shard *sh);
+// ... and the grouped one-sweep launches (8-bit rows): the shard's complete norm array, or null -- norms switched off
+// (scan_norms = 1, SZG_NO_ROW_NORMS), no array (its allocation failed: no error, the sweep sums the norms itself).
+// *err: any other failure of ensure_row_norms (a launch, a stream), which the caller returns
+const float *scan_row_norms(szg_index *ix, Shard *sh, int *err);
 // (rerun: the fused selection of this batch overflowed on this context -- again, through the score matrix)
 int enqueue_topk_mq(szg_index *ix, Shard *sh, Ctx *c, int kp, int kp_wide, int nq, int nb, bool has_allow,
                     bool rerun = false);

@@ -134,6 +134,22 @@ int ensure_row_norms(szg_index *ix, Shard *sh)
     return SZG_OK;
 }
 
+const float *scan_row_norms(szg_index *ix, Shard *sh, int *err)
+{
+    *err = SZG_OK;
+    if (ix->bits != 8 || ix->scan_norms == 1 || !row_norms_apply(ix) || sh->n_rows == 0) return nullptr;
+    const int rc = ensure_row_norms(ix, sh);
+    if (rc == SZG_E_NOMEM) {  // (no memory for the array: the sweep sums the norms, as it did; nothing else is swallowed)
+        (void)hipGetLastError();
+        return nullptr;
+    }
+    if (rc) {
+        *err = rc;
+        return nullptr;
+    }
+    return sh->row_norm && sh->norm_valid >= sh->n_rows ? sh->row_norm : nullptr;
+}
+
 // ---- one batch through ONE shared sweep --------------------------------------------------------------------------
 
 namespace {

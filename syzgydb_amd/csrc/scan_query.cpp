@@ -119,7 +119,9 @@ void prep_query(const szg_index *ix, const double *q, uint8_t *out_sw, QMeta *me
     double scale;
     const double vmax = prep_query_norms(ix, q, meta, &scale);
     if (bits == 8 || bits == 4) {
-        const double Qmax = bits == 8 ? 1000000.0 : szg::kQmax4;
+        // (a sketch index quantizes to two planes: |Q| <= 16000 leaves the h plane all zero, scan_planes)
+        const double Qmax = bits == 8 ? scan_qmax8(ix) : szg::kQmax4;
+        const int top8 = 3 - scan_planes(ix);  // the plane that takes what is left of Q (|m| <= 125 with two planes)
         const double qs = (vmax > 0 && std::isfinite(vmax)) ? vmax / Qmax : 1.0;
         meta->qscale = qs;
         double sumQ = 0.0;
@@ -130,9 +132,9 @@ void prep_query(const szg_index *ix, const double *q, uint8_t *out_sw, QMeta *me
             const int j = e / E, i = e % E;
             if (bits == 8) {
                 const int d = i / 4, kb = i % 4;
-                for (int x = 2; x >= 0; x--) {  // planes: 0 = h (x16384), 1 = m (x128), 2 = l
+                for (int x = 2; x >= top8; x--) {  // planes: 0 = h (x16384), 1 = m (x128), 2 = l
                     long long dig;
-                    if (x > 0) {
+                    if (x > top8) {
                         dig = ((Q + 64) & 127) - 64;
                         Q = (Q - dig) >> 7;
                     } else {
@@ -169,6 +171,11 @@ void prep_query(const szg_index *ix, const double *q, uint8_t *out_sw, QMeta *me
             reinterpret_cast<float *>(out_sw)[((size_t)c * r16 + j) * 4 + m] = (float)v;
         }
     }
+}
+
+int scan_planes(const szg_index *ix)
+{
+    return ix->bits == 8 && ix->is_sketch && ix->sketch_planes != 3 ? 2 : 3;
 }
 
 // Bound on |scan key - real-number key| (see DESIGN.md "certification").
@@ -223,9 +230,14 @@ double key_eps(const szg_index *ix, double key, const QMeta &m)
         // the row finish: the plane combination and the reduction over the lanes act on
         // terms bounded by sum |Q_i||v'_i| <= Qmax*V*dim (V = 128 resp. 8), i.e. an
         // absolute error <= 16*2^-24 * qscale*Qmax*V*dim in units of sum v n.
+        // Two planes on a sketch index (scan_planes; Qmax = 16000, qscale = vmax / 16000 the two-plane step): nothing
+        // in (a) or (b) depends on the plane count but through qscale and Qmax.  (a) grows with the step -- cosine:
+        // 0.5 qscale sqrt(dim), Euclid: qscale M dim, 62.5 times the three-plane terms.  (b) does not move: qscale*Qmax
+        // = vmax whatever Qmax is, and the two-plane key fmaf(128, M, L) rounds once where the three-plane one rounds
+        // twice, with |128 M + L| <= Qmax*V*(elements of the lane) as before.
         const double M = (double)((1u << ix->bits) - 1u);
         const double V = ix->bits == 8 ? 128.0 : 8.0;
-        const double Qmax = ix->bits == 8 ? 1000000.0 : szg::kQmax4;
+        const double Qmax = ix->bits == 8 ? scan_qmax8(ix) : szg::kQmax4;
         const double fl = 16.0 * 0x1p-24 * m.qscale * Qmax * V * (double)ix->dim;
         if (ix->metric == SZG_COSINE)  // divided by |n| >= sqrt(dim) (every n is odd)
             return 0.5 * m.qscale * std::sqrt((double)ix->dim) + fl / std::sqrt((double)ix->dim) + 0x1p-21;

@@ -84,6 +84,7 @@ int sketch_sync(szg_index *ix)
         int rc = szg_index_create(&ix->sketch, ix->dim, 8, ix->metric, devs.data(), (int)devs.size());
         if (rc) return rc;
         ix->sk_need_full = true;
+        ix->sketch->is_sketch = true;  // (its queries take two digit planes: scan_planes)
         ix->sketch->timing = ix->timing;
         for (const auto &o : ix->opt_log) (void)szg_set_option(ix->sketch, o.first.c_str(), o.second);
     }

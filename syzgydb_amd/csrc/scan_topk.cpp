@@ -139,6 +139,7 @@ void fill_scan_args(const szg_index *ix, const Shard *sh, const Ctx *c, bool has
     a->no_shape_kernels = ix->shape_kernels ? 0 : 1;
     a->ring = ix->ring;
     a->group = ix->scan_group;
+    a->planes = scan_planes(ix);  // (as prep_query quantized the staged queries)
 }
 
 // Launch the fused scan for each of the batch's queries (n = a->size()) as the
@@ -236,6 +237,20 @@ int enqueue_topk(szg_index *ix, Shard *sh, Ctx *c, int kp, int nq, bool has_allo
             }
             a.kp = m;
             a.block_lists = c->d_lists_a + (size_t)j * g.grid * m;
+        }
+        // launches that score groups of queries per row read take the rows' norms from the resident array (complete
+        // before the sweeps are enqueued; it only has work to do after rows were added)
+        const float *norms = nullptr;
+        bool asked = false;
+        for (szg::ScanArgs &a : args) {
+            if (szg::scan_group_of(ix->bits, a, g.block) < 2) continue;
+            if (!asked) {
+                int nrc = SZG_OK;
+                norms = scan_row_norms(ix, sh, &nrc);
+                if (nrc) return nrc;
+            }
+            asked = true;
+            a.row_norm = norms;
         }
         rc = launch_scans_chained(ix, sh, c, args, g, tl, part);
         if (rc) return rc;

@@ -643,6 +643,13 @@ def scan_group_plan(dim, quant_bits, n_queries, kp=10, scan_group=0, queries_per
     return {"group": g.value, "lds_bytes": lds.value, "passes": passes.value}
 
 
+def option_check(name, value):
+    """Host-only test hook (no device needed): raises SzgError where ScanIndex.set_option would refuse `value` for the
+    one-sweep kernel's option `name` (scan_group, scan_norms, sketch_planes)."""
+    L = _lib.load()
+    check(L.szg_debug_option_check(name.encode(), int(value)), "szg_debug_option_check")
+
+
 def reorder_plan(n_rows, src_rows, n_shards=1, live=None):
     """Host-only test hook (no device needed): the checks ScanIndex.reorder makes on its list -- SzgError with the same
     code and text -- and the new rows per shard.  live: bool[n_rows] (None: every row is live)."""
