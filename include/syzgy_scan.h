@@ -244,7 +244,9 @@ int szg_index_compact(szg_index *ix, uint64_t *out_new_of_old, uint64_t *out_row
  * with szg_mask_combine like any others.
  *
  * Kinds: SZG_COL_F64 holds doubles; SZG_COL_U32 holds codes of a dictionary the HOST owns (the library never sees the
- *   strings: the host evaluates a string operator once per dictionary entry into a bitmap over codes).
+ *   strings: the host evaluates a string operator once per dictionary entry into a bitmap over codes) -- the kind for
+ *   a string field with few distinct values; SZG_COL_STR holds the strings themselves, for a field whose values are
+ *   mostly distinct (see "Text columns" below).
  * Predicate of every szg_mask_where_*: bit r = present(r) && pred(value[r]) (&& base's bit r).  Float64 comparisons
  *   follow IEEE, i.e. Go's == and < on float64 (query/compiler.go:175, :288-303): -0.0 == 0.0, and a NaN fails every
  *   operator but SZG_CMP_NE.  Tail bits are 0, as in every mask.
@@ -271,16 +273,41 @@ int szg_index_compact(szg_index *ix, uint64_t *out_new_of_old, uint64_t *out_row
  *   destroy need the exclusive access mutations have.  Columns are destroyed before their handle.
  * Failure: every check happens on the host before anything is allocated or launched; an error leaves the column as
  *   it was and *out untouched.
+ * Text columns (SZG_COL_STR): values are BYTES, not text -- embedded NUL bytes and bytes >= 0x80 are ordinary -- and
+ *   the card compares them as Go compares strings (query/compiler.go:304-319; strings.Contains / HasPrefix /
+ *   HasSuffix, :393-418): unsigned, lexicographic, a proper prefix being the smaller.  They have calls of their own
+ *   (szg_column_create_str / _append_str / _set_str / _read_str, szg_mask_where_str); szg_column_create keeps refusing
+ *   the kind, and szg_column_append, szg_column_set, szg_column_read with out_values != NULL and
+ *   szg_mask_where_f64 / _in_f64 / _u32 on a text column -- like szg_mask_where_str and the *_str calls on another
+ *   kind -- return SZG_E_INVALID ("kind does not match").  szg_column_rows, szg_column_read with out_values == NULL,
+ *   szg_mask_where_present and szg_column_destroy work on every kind.  Everything above -- row numbering, short and
+ *   stale columns, base, threads, failure -- holds for them unchanged.
+ *   Storage per shard part: one 8-byte reference {uint32 start, uint32 len} per row into the part's byte heap, the
+ *   heap, and the present bits.  Create and append write a call's strings back to back in row order; an absent row
+ *   has length 0.  The heap grows geometrically; its capacity is a multiple of 16 bytes that ends at least 16 zero
+ *   bytes past the last used byte, and stays below 4 GiB per part: a call that would exceed that returns
+ *   SZG_E_UNSUPPORTED with the column unchanged.  Dead bytes (szg_column_set_str) are reclaimed only by making the
+ *   column again.
+ *   szg_mask_where_str: op is SZG_CMP_EQ..SZG_CMP_GE or SZG_STR_STARTS_WITH / ENDS_WITH / CONTAINS, anything else
+ *   SZG_E_INVALID ("operator" in szg_last_error); a constant of more than SZG_STR_PATTERN_MAX bytes is
+ *   SZG_E_UNSUPPORTED, a NULL constant with len > 0 SZG_E_INVALID.  The empty constant is legal: the three string
+ *   operators then hold for every present row, the comparisons run against "".  One kernel per shard, a lane per
+ *   row: a match lies wholly inside its row.
  */
 typedef struct szg_column szg_column;
 #define SZG_COL_F64 0   /* values: double */
 #define SZG_COL_U32 1   /* values: uint32_t codes; the host owns the dictionary */
+#define SZG_COL_STR 2   /* values: byte strings, resident beside the rows */
 #define SZG_CMP_EQ 0
 #define SZG_CMP_NE 1
 #define SZG_CMP_LT 2
 #define SZG_CMP_LE 3
 #define SZG_CMP_GT 4
 #define SZG_CMP_GE 5
+#define SZG_STR_STARTS_WITH 6   /* szg_mask_where_str only: continue SZG_CMP_EQ..SZG_CMP_GE */
+#define SZG_STR_ENDS_WITH 7
+#define SZG_STR_CONTAINS 8
+#define SZG_STR_PATTERN_MAX 256 /* bytes of a constant */
 
 int szg_column_create(szg_index *ix, int kind, const void *values, const uint64_t *present_bits,
                       uint64_t n_rows, szg_column **out);
@@ -294,6 +321,22 @@ int szg_column_read(const szg_column *c, uint64_t first_row, uint64_t n_rows, vo
                     uint64_t *out_present_bits);
 void szg_column_destroy(szg_column *c);   /* NULL is fine; before its handle */
 
+/* text columns.  offsets: n_rows + 1 entries, offsets[0] == 0, non-decreasing (else SZG_E_INVALID, "offsets" in
+   szg_last_error); row i of the call = bytes[offsets[i] .. offsets[i + 1]).  present_bits as szg_column_create */
+int szg_column_create_str(szg_index *ix, const uint8_t *bytes, const uint64_t *offsets,
+                          const uint64_t *present_bits, uint64_t n_rows, szg_column **out);
+int szg_column_append_str(szg_column *c, const uint8_t *bytes, const uint64_t *offsets,
+                          const uint64_t *present_bits, uint64_t n_rows);
+/* one row: value == NULL marks the row absent (its bytes stay).  len <= the stored len: rewritten in place.  Longer:
+   the bytes go to the end of the heap and the row points there; the old bytes are dead until the column is made again */
+int szg_column_set_str(szg_column *c, uint64_t row, const uint8_t *value, uint64_t len);
+/* rows [first_row, first_row + n_rows): out_offsets (nullable) gets n_rows + 1 entries, row i = out_bytes[out_offsets[i]
+   .. out_offsets[i + 1]); out_bytes is nullable; capacity < out_offsets[n_rows] -> SZG_E_TRUNCATED with the offsets
+   still valid.  Present words as szg_column_read.  Works on a stale column.  A test and debug path: it downloads the
+   parts' references and heaps */
+int szg_column_read_str(const szg_column *c, uint64_t first_row, uint64_t n_rows, uint64_t *out_offsets,
+                        uint8_t *out_bytes, uint64_t capacity, uint64_t *out_present_bits);
+
 /* present && value op constant (SZG_CMP_*) */
 int szg_mask_where_f64(const szg_column *c, int op, double value, const szg_mask *base, szg_mask **out);
 /* present && value == one of values[0 .. n_values): duplicates allowed, a NaN among them matches nothing, n_values == 0
@@ -303,7 +346,10 @@ int szg_mask_where_in_f64(const szg_column *c, const double *values, uint32_t n_
 /* present && bit `code` of code_bits (n_codes bits, ceil(n_codes/64) words, copied); a code >= n_codes fails */
 int szg_mask_where_u32(const szg_column *c, const uint64_t *code_bits, uint32_t n_codes,
                        const szg_mask *base, szg_mask **out);
-/* the present bits (either kind) */
+/* text columns: present && value op constant[0 .. len), op SZG_CMP_* or SZG_STR_* */
+int szg_mask_where_str(const szg_column *c, int op, const uint8_t *constant, uint32_t len,
+                       const szg_mask *base, szg_mask **out);
+/* the present bits (every kind) */
 int szg_mask_where_present(const szg_column *c, const szg_mask *base, szg_mask **out);
 
 /*

@@ -36,7 +36,8 @@ for ln in sys.stdin:
         import subprocess
         dem = subprocess.run(["c++filt", name], capture_output=True, text=True).stdout.strip()
         dem = re.sub(r"szg::\(anonymous namespace\)::", "", dem).split("(")[0]
-        print("%-64s vgpr %3d agpr %3d scratch %4d B  vgpr-spill %3d  occupancy %d" % (
-            dem[:64], row.get("VGPRs:", -1), row.get("AGPRs", 0), row.get("ScratchSize", 0), row.get("VGPRs Spill", 0), row.get("Occupancy", 0)))
+        print("%-64s vgpr %3d agpr %3d scratch %4d B  vgpr-spill %3d  lds %5d B  occupancy %d" % (
+            dem[:64], row.get("VGPRs:", -1), row.get("AGPRs", 0), row.get("ScratchSize", 0), row.get("VGPRs Spill", 0), row.get("LDS Size", 0),
+            row.get("Occupancy", 0)))
         name = None
 '

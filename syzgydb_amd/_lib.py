@@ -43,12 +43,16 @@ EXPORTS = [
     # resident metadata columns (added under ABI 4)
     "szg_column_create", "szg_column_append", "szg_column_set", "szg_column_rows", "szg_column_read",
     "szg_column_destroy", "szg_mask_where_f64", "szg_mask_where_in_f64", "szg_mask_where_u32", "szg_mask_where_present",
+    # text columns (added under ABI 4)
+    "szg_column_create_str", "szg_column_append_str", "szg_column_set_str", "szg_column_read_str", "szg_mask_where_str",
     # host-only test hook
     "szg_debug_scan_plan", "szg_debug_scan_group", "szg_debug_reorder_plan", "szg_debug_option_check",
 ]
 SZG_MASK_AND, SZG_MASK_OR, SZG_MASK_ANDNOT, SZG_MASK_NOT = 0, 1, 2, 3
-SZG_COL_F64, SZG_COL_U32 = 0, 1
+SZG_COL_F64, SZG_COL_U32, SZG_COL_STR = 0, 1, 2
 SZG_CMP_EQ, SZG_CMP_NE, SZG_CMP_LT, SZG_CMP_LE, SZG_CMP_GT, SZG_CMP_GE = range(6)
+SZG_STR_STARTS_WITH, SZG_STR_ENDS_WITH, SZG_STR_CONTAINS = 6, 7, 8   # szg_mask_where_str only
+SZG_STR_PATTERN_MAX = 256
 SZG_COMM_ID_BYTES = 128
 # int (*szg_allgather_fn)(void *user, const void *send, void *recv, uint64_t bytes_per_rank)
 ALLGATHER_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64)
@@ -243,6 +247,17 @@ def load():
         L.szg_mask_where_u32.argtypes = [vp, u64p, ctypes.c_uint32, vp, ctypes.POINTER(vp)]
         L.szg_mask_where_present.restype = ctypes.c_int
         L.szg_mask_where_present.argtypes = [vp, vp, ctypes.POINTER(vp)]
+    if hasattr(L, "szg_column_create_str"):   # (an older build for an A/B run has no text columns)
+        L.szg_column_create_str.restype = ctypes.c_int
+        L.szg_column_create_str.argtypes = [vp, u8p, u64p, u64p, ctypes.c_uint64, ctypes.POINTER(vp)]
+        L.szg_column_append_str.restype = ctypes.c_int
+        L.szg_column_append_str.argtypes = [vp, u8p, u64p, u64p, ctypes.c_uint64]
+        L.szg_column_set_str.restype = ctypes.c_int
+        L.szg_column_set_str.argtypes = [vp, ctypes.c_uint64, u8p, ctypes.c_uint64]
+        L.szg_column_read_str.restype = ctypes.c_int
+        L.szg_column_read_str.argtypes = [vp, ctypes.c_uint64, ctypes.c_uint64, u64p, u8p, ctypes.c_uint64, u64p]
+        L.szg_mask_where_str.restype = ctypes.c_int
+        L.szg_mask_where_str.argtypes = [vp, ctypes.c_int, u8p, ctypes.c_uint32, vp, ctypes.POINTER(vp)]
     L.szg_comm_unique_id.restype = ctypes.c_int
     L.szg_comm_unique_id.argtypes = [u8p]
     L.szg_comm_create.restype = ctypes.c_int

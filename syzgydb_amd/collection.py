@@ -68,11 +68,11 @@ class SearchArgs:
 
 
 class _FieldIndex:
-    """One indexed metadata field: its column on the card and, for strings, the dictionary value -> code."""
+    """One indexed metadata field: its column on the card and, for kind "string", the dictionary value -> code."""
 
     def __init__(self, name, kind):
         self.name = name
-        self.kind = kind        # "number" / "string"
+        self.kind = kind        # "number" / "string" / "text"
         self.column = None      # ScanColumn
         self.codes = {}         # string fields: value -> code, append-only, first-seen order
 
@@ -83,6 +83,8 @@ class _FieldIndex:
             if _where._is_number(v):
                 return _where._number(v), True
             return 0.0, False
+        if self.kind == "text":
+            return (v, True) if isinstance(v, str) else (None, False)
         if isinstance(v, str):
             return self.codes.setdefault(v, len(self.codes)), True
         return 0, False
@@ -331,12 +333,15 @@ class Collection:
     # -- metadata fields resident on the card ------------------------------------
     def IndexField(self, name: str, kind: str):
         """Keep the top-level metadata field `name` as a column on the card (not in the reference): kind "number"
-        holds the rows whose value is a JSON number, kind "string" those whose value is a string, as codes of an
-        append-only dictionary kept here.  The resident metadata is parsed once, now; from then on AddDocument(s)
-        append to the column, UpdateDocument sets the row, and Compact() and the re-sort rebuild it.  Search with
-        SearchArgs.Where then compares the field on the card."""
-        if kind not in ("number", "string"):
-            raise ValueError('kind is "number" or "string"')
+        holds the rows whose value is a JSON number; kinds "string" and "text" both hold those whose value is a string.
+        "string" suits a field with few distinct values (a brand, a status): one 4-byte code per row of an append-only
+        dictionary kept here, and a filter is evaluated on the host once per DISTINCT value.  "text" suits a field
+        whose values are mostly distinct (an email, a name, an id): the strings' bytes live on the card, with no
+        dictionary, and the card compares them (constants of up to 256 bytes, IN-lists of up to 16).  The resident
+        metadata is parsed once, now; from then on AddDocument(s) append to the column, UpdateDocument sets the row,
+        and Compact() and the re-sort rebuild it.  Search with SearchArgs.Where then compares the field on the card."""
+        if kind not in ("number", "string", "text"):
+            raise ValueError('kind is "number", "string" or "text"')
         _where.Field(name)   # (the name must be an identifier of the filter language)
         old = self._fields.pop(name, None)
         if old is not None and old.column is not None:
@@ -351,8 +356,11 @@ class Collection:
 
     def _build_column(self, f, parsed):
         pairs = [f.value_of(d) for d in parsed]
-        values = np.array([v for v, _ in pairs], dtype=np.float64 if f.kind == "number" else np.uint32)
         present = np.array([p for _, p in pairs], dtype=bool)
+        if f.kind == "text":
+            f.column = self._index.text_column([v for v, _ in pairs], present=present)
+            return
+        values = np.array([v for v, _ in pairs], dtype=np.float64 if f.kind == "number" else np.uint32)
         f.column = self._index.column(values, present=present,
                                       kind=_lib.SZG_COL_F64 if f.kind == "number" else _lib.SZG_COL_U32)
 
@@ -397,6 +405,8 @@ class Collection:
             return None
         want = float if f.kind == "number" else str
         col = f.column
+        if f.kind == "text":
+            return self._text_leaf_mask(e, col)
         if isinstance(e, _where.Cmp):
             if not isinstance(e.constant, want):
                 return None
@@ -425,6 +435,49 @@ class Collection:
             if f.kind != "string":
                 return None
             return col.codes([e.test(s) for s in f.codes]), True
+        return None
+
+    @staticmethod
+    def _text_leaf_mask(e, col):
+        """_leaf_mask for a "text" field: the card compares the bytes.  None (the host answers) for a constant that is
+        not a string or is longer than the kernel's 256 bytes, and for an IN-list of more than 16 strings."""
+        def fits(c):
+            return isinstance(c, str) and len(_where._bytes(c)) <= _lib.SZG_STR_PATTERN_MAX
+
+        if isinstance(e, _where.Cmp):
+            if not fits(e.constant):
+                return None
+            if e.op == "!=":   # true for nil and every value of another type as well: the complement of ==
+                pos = col.where("==", e.constant)
+                m = ~pos
+                pos.close()
+                return m, False
+            return col.where(e.op, e.constant), e.op in _where._ORDERED
+        if isinstance(e, _where.In):
+            if not all(fits(c) for c in e.constants) or len(e.constants) > 16:
+                return None
+            m = None
+            for c in dict.fromkeys(e.constants):   # the OR of the == masks
+                eq = col.where("==", c)
+                if m is None:
+                    m = eq
+                else:
+                    m, old = m | eq, m
+                    old.close()
+                    eq.close()
+            if m is None:   # an empty list: no row
+                everyone = col.present()
+                m = everyone.andnot(everyone)
+                everyone.close()
+            if e.negate:
+                m, pos = ~m, m
+                pos.close()
+            return m, False
+        if isinstance(e, _where.StrOp):
+            if not fits(e.constant):
+                return None
+            fn = {"STARTS_WITH": col.startswith, "ENDS_WITH": col.endswith, "CONTAINS": col.contains}[e.op]
+            return fn(e.constant), True
         return None
 
     def _where_device_mask(self, expr):

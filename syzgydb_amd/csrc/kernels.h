@@ -382,5 +382,10 @@ hipError_t launch_column_in_f64(const double *values, const double *sorted, uint
 hipError_t launch_column_codes_u32(const uint32_t *values, const uint64_t *code_bits, uint32_t n_codes, const ColumnWhere &w,
                                    hipStream_t stream);
 hipError_t launch_column_present(const ColumnWhere &w, hipStream_t stream);
+// text columns (column_str.h): refs = one {uint32 start, uint32 len} per row into `heap` (device, 16-byte aligned, every
+// reference inside it); op: SZG_CMP_* / SZG_STR_*; constant: device, ceil(len / 4) dwords, the last one zero-padded,
+// len <= SZG_STR_PATTERN_MAX
+hipError_t launch_column_str(const uint64_t *refs, const uint8_t *heap, int op, const uint32_t *constant, uint32_t len,
+                             const ColumnWhere &w, hipStream_t stream);
 
 }  // namespace szg

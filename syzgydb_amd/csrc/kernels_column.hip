@@ -5,7 +5,9 @@
 // One wave step covers 128 rows = one pair: lane l holds elements base + l and base + 64 + l (two contiguous wave loads),
 // two ballots give the pair's words, lane 0 stores them with one 16-byte store.  kSteps steps of a wave are loaded
 // before the first is used.  No element at a position >= n_rows is loaded.  Plain C++ and vector memory operations only.
+// A text column's element is a row's 8-byte reference into a byte heap that the predicate then reads (column_str.h).
 #include "kernels.h"
+#include "column_str.h"
 
 namespace szg {
 
@@ -79,6 +81,34 @@ struct Always {
     static constexpr bool kLoads = false;
     __device__ void init() {}
     __device__ bool operator()(uint32_t) const { return true; }
+};
+
+// a text column's row against a constant of up to 256 bytes (column_str.h has the predicate): the value is the row's
+// 8-byte reference into the part's heap, which each lane reads for its own row with aligned dword loads; the constant is
+// staged in LDS, one dword per thread.  A row at a position >= n_rows arrives as the reference 0: length 0, nothing read.
+struct StrWhere {
+    using T = uint64_t;   // {uint32 start, uint32 len}, little-endian
+    static constexpr bool kLoads = true;
+    struct Heap {
+        const uint32_t *dwords;
+        __device__ uint32_t operator()(uint32_t i) const { return dwords[i]; }
+    };
+    int op;
+    Heap heap;
+    const uint32_t *constant;  // device, ceil(len / 4) dwords
+    uint32_t len;
+    const uint32_t *lds;
+    __device__ void init()
+    {
+        __shared__ uint32_t s[szgi::kStrPatternDwords];
+        if (threadIdx.x < (len + 3) / 4) s[threadIdx.x] = constant[threadIdx.x];
+        __syncthreads();
+        lds = s;
+    }
+    __device__ bool operator()(uint64_t ref) const
+    {
+        return szgi::str_predicate(op, heap, (uint32_t)ref, (uint32_t)(ref >> 32), lds, len);
+    }
 };
 
 // the bits of word w that stand for rows < n_rows
@@ -181,6 +211,16 @@ hipError_t launch_column_codes_u32(const uint32_t *values, const uint64_t *code_
 {
     if ((!code_bits && n_codes) || (!values && w.n_pairs)) return hipErrorInvalidValue;
     return launch_where(CodeBits{code_bits, n_codes}, values, w, stream);
+}
+
+hipError_t launch_column_str(const uint64_t *refs, const uint8_t *heap, int op, const uint32_t *constant, uint32_t len,
+                             const ColumnWhere &w, hipStream_t stream)
+{
+    static_assert(szgi::kStrPatternDwords <= 256, "StrWhere::init stages one dword per thread of the block");
+    if (op < 0 || op > szgi::kStrOpContains || len > szgi::kStrPatternMax || (!constant && len) ||
+        ((!refs || !heap) && w.n_pairs))
+        return hipErrorInvalidValue;
+    return launch_where(StrWhere{op, {reinterpret_cast<const uint32_t *>(heap)}, constant, len, nullptr}, refs, w, stream);
 }
 
 hipError_t launch_column_present(const ColumnWhere &w, hipStream_t stream)

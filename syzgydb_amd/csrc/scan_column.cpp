@@ -1,13 +1,15 @@
 // scan_column.cpp -- resident metadata columns (include/syzgy_scan.h, szg_column) and the masks made from them.
 //
-// A column holds, per shard of its handle, that shard's part on the shard's device: the values (float64, or uint32
-// codes whose dictionary the host owns), the present bits in the masks' layout of 16-byte pairs of words, and a host copy
-// of the present words (what appends and single-row updates edit before they upload the words they touched).  Parts
+// A column holds, per shard of its handle, that shard's part on the shard's device: the values (float64, uint32 codes
+// whose dictionary the host owns, or -- a text column -- 8-byte references into a byte heap of the part's own), the
+// present bits in the masks' layout of 16-byte pairs of words, and a host copy of the present words (what appends and
+// single-row updates edit before they upload the words they touched).  Parts
 // follow Shard::first; index appends only extend the last shard that holds rows or start the next one, so a part never
 // moves -- it grows geometrically, in place of its old allocation.  szg_mask_where_* run one compare kernel per shard
 // (kernels_column.hip) that writes the words and the count of an ordinary szg_mask.
 #include "scan_internal.h"
 #include "column_bits.h"
+#include "column_str.h"
 
 using namespace szgi;
 
@@ -23,6 +25,7 @@ void column_free(szg_column *c)
         (void)hipSetDevice(p.device);
         (void)hipFree(p.values);
         (void)hipFree(p.present);
+        (void)hipFree(p.heap);
     }
     delete c;
 }
@@ -67,23 +70,62 @@ int column_check(const szg_column *c)
     return SZG_OK;
 }
 
+// room for `used` bytes in part p's heap (str_heap_fits(used)): as part_reserve, the new bytes zero
+int heap_reserve(szg_column::Part &p, uint64_t used)
+{
+    if (p.heap_cap && str_heap_capacity(used) <= p.heap_cap) return SZG_OK;
+    const uint64_t cap = str_heap_grow(p.heap_cap, used);
+    HIPCHK(hipSetDevice(p.device));
+    uint8_t *heap = nullptr;
+    if (hipMalloc((void **)&heap, cap) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(SZG_E_NOMEM, "out of device memory (column heap)");
+    }
+    hipError_t e = hipMemset(heap, 0, cap);
+    if (e == hipSuccess && p.heap_used) e = hipMemcpy(heap, p.heap, p.heap_used, hipMemcpyDeviceToDevice);
+    if (e != hipSuccess) {
+        (void)hipFree(heap);
+        return fail(SZG_E_DEVICE, "column heap growth", e);
+    }
+    (void)hipFree(p.heap);
+    p.heap = heap;
+    p.heap_cap = cap;
+    return SZG_OK;
+}
+
+// how many more rows each part has room for: what its shard holds beyond it
+std::vector<uint64_t> column_room(const szg_column *c)
+{
+    std::vector<uint64_t> room(c->parts.size(), 0);
+    for (size_t s = 0; s < room.size(); s++) {
+        const uint64_t have = c->owner->shards[s]->n_rows;
+        if (have > c->parts[s].n_rows) room[s] = have - c->parts[s].n_rows;
+    }
+    return room;
+}
+
+// the parts that take rows of an append continue the column's rows: the shards' ranges are contiguous in row order
+int column_take_check(const szg_column *c, const std::vector<uint64_t> &take)
+{
+    uint64_t at = c->rows;
+    for (size_t s = 0; s < take.size(); s++) {
+        if (!take[s]) continue;
+        if (c->owner->shards[s]->first + c->parts[s].n_rows != at) return stale_column();
+        at += take[s];
+    }
+    return SZG_OK;
+}
+
 // n more rows behind the column's last: values and present bits (bit i = the i-th of these rows; null = all present)
 int column_extend(szg_column *c, const void *values, const uint64_t *present_bits, uint64_t n)
 {
     szg_index *ix = c->owner;
     if (c->rows + n > szg_index_rows(ix)) return fail(SZG_E_RANGE, "column append past the handle's rows");
-    // which part takes how many: the shards' ranges are contiguous in row order
+    // which part takes how many
+    const std::vector<uint64_t> room = column_room(c);
     std::vector<uint64_t> take(c->parts.size(), 0);
-    uint64_t at = c->rows, left = n;
-    for (size_t s = 0; s < c->parts.size() && left; s++) {
-        const Shard *sh = ix->shards[s];
-        const szg_column::Part &p = c->parts[s];
-        if (sh->n_rows <= p.n_rows) continue;
-        if (sh->first + p.n_rows != at) return stale_column();
-        take[s] = std::min(left, sh->n_rows - p.n_rows);
-        at += take[s], left -= take[s];
-    }
-    if (left) return stale_column();
+    if (split_rows(room.data(), room.size(), n, take.data())) return stale_column();
+    if (int rc = column_take_check(c, take)) return rc;
     for (size_t s = 0; s < c->parts.size(); s++)
         if (take[s])
             if (int rc = part_reserve(c, c->parts[s], c->parts[s].n_rows + take[s])) return rc;
@@ -105,6 +147,77 @@ int column_extend(szg_column *c, const void *values, const uint64_t *present_bit
     return SZG_OK;
 }
 
+// n more rows of a text column: row i of the call = bytes[offsets[i] .. offsets[i + 1]).  Each part that takes rows
+// receives its slice of the bytes behind its heap's used bytes, and references rebased to there; an absent row gets
+// length 0.  Every size is settled (str_plan_append) before anything is allocated.
+int column_extend_str(szg_column *c, const uint8_t *bytes, const uint64_t *offsets, const uint64_t *present_bits, uint64_t n)
+{
+    szg_index *ix = c->owner;
+    if (c->rows + n > szg_index_rows(ix)) return fail(SZG_E_RANGE, "column append past the handle's rows");
+    if (n == 0) return SZG_OK;
+    const std::vector<uint64_t> room = column_room(c);
+    std::vector<uint64_t> used(c->parts.size()), take(c->parts.size(), 0), nbytes(c->parts.size(), 0);
+    for (size_t s = 0; s < used.size(); s++) used[s] = c->parts[s].heap_used;
+    switch (str_plan_append(offsets, n, room.data(), used.data(), room.size(), take.data(), nbytes.data())) {
+    case kStrPlanOk: break;
+    case kStrPlanOffsets: return fail(SZG_E_INVALID, "offsets start at 0 and never decrease");
+    case kStrPlanRows: return stale_column();
+    default: return fail(SZG_E_UNSUPPORTED, "a part's text heap stays below 4 GiB");
+    }
+    if (int rc = column_take_check(c, take)) return rc;
+    for (size_t s = 0; s < c->parts.size(); s++) {
+        if (!take[s]) continue;
+        if (int rc = part_reserve(c, c->parts[s], c->parts[s].n_rows + take[s])) return rc;
+        if (int rc = heap_reserve(c->parts[s], c->parts[s].heap_used + nbytes[s])) return rc;
+    }
+    uint64_t done = 0;
+    std::vector<uint64_t> refs;
+    for (size_t s = 0; s < c->parts.size(); s++) {
+        if (!take[s]) continue;
+        szg_column::Part &p = c->parts[s];
+        HIPCHK(hipSetDevice(p.device));
+        if (p.n_rows == 0) p.first = ix->shards[s]->first;
+        refs.resize((size_t)take[s]);
+        for (uint64_t i = 0; i < take[s]; i++) {
+            const uint64_t r = done + i;
+            const bool there = !present_bits || ((present_bits[r >> 6] >> (r & 63)) & 1ull);
+            const uint64_t start = p.heap_used + (offsets[r] - offsets[done]);
+            refs[(size_t)i] = start | ((there ? offsets[r + 1] - offsets[r] : 0ull) << 32);
+        }
+        if (nbytes[s])
+            HIPCHK(hipMemcpy(p.heap + p.heap_used, bytes + offsets[done], nbytes[s], hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy((uint64_t *)p.values + p.n_rows, refs.data(), take[s] * sizeof(uint64_t), hipMemcpyHostToDevice));
+        copy_bits(p.present_host.data(), p.n_rows, present_bits, done, take[s]);
+        const size_t w0 = (size_t)(p.n_rows / 64), w1 = index_words(p.n_rows + take[s]);
+        HIPCHK(hipMemcpy(p.present + w0, p.present_host.data() + w0, (w1 - w0) * sizeof(uint64_t), hipMemcpyHostToDevice));
+        p.heap_used += nbytes[s];
+        p.n_rows += take[s];
+        c->rows += take[s];
+        done += take[s];
+    }
+    return SZG_OK;
+}
+
+// the part that holds the column's local row `row`, or null
+szg_column::Part *part_of(szg_column *c, uint64_t row)
+{
+    for (szg_column::Part &p : c->parts)
+        if (row >= p.first && row - p.first < p.n_rows) return &p;
+    return nullptr;
+}
+
+// row l of part p present or absent: the host word and its copy on the device
+int set_present(szg_column::Part &p, uint64_t l, bool there)
+{
+    uint64_t w = p.present_host[l / 64];
+    w = there ? (w | (1ull << (l & 63))) : (w & ~(1ull << (l & 63)));
+    HIPCHK(hipMemcpy(p.present + l / 64, &w, sizeof(w), hipMemcpyHostToDevice));
+    p.present_host[l / 64] = w;
+    return SZG_OK;
+}
+
+int kind_mismatch() { return fail(SZG_E_INVALID, "the column's kind does not match the call"); }
+
 // What the szg_mask_where_* calls share: every check on the host, then one launch per shard through `launch(s, w)`,
 // the count and the host copy of the words brought back once.
 template <class Launch>
@@ -114,7 +227,7 @@ int mask_where(const szg_column *c, int kind, const szg_mask *base, szg_mask **o
     szg_index *ix = c->owner;
     int rc = column_check(c);
     if (rc) return rc;
-    if (kind >= 0 && c->kind != kind) return fail(SZG_E_INVALID, "the column's kind does not match the call");
+    if (kind >= 0 && c->kind != kind) return kind_mismatch();
     if (c->rows != szg_index_rows(ix)) return fail(SZG_E_INVALID, "short column: rows were appended to the handle but not to the column");
     for (size_t s = 0; s < c->parts.size(); s++)
         if (c->parts[s].n_rows != ix->shards[s]->n_rows || (c->parts[s].n_rows && c->parts[s].first != ix->shards[s]->first))
@@ -191,6 +304,7 @@ int szg_column_append(szg_column *c, const void *values, const uint64_t *present
     SZG_TRY
     if (!c || (!values && n_rows)) return fail(SZG_E_INVALID, "null argument");
     if (int rc = column_check(c)) return rc;
+    if (c->kind == SZG_COL_STR) return kind_mismatch();
     if (n_rows == 0) return SZG_OK;
     return column_extend(c, values, present_bits, n_rows);
     SZG_CATCH
@@ -201,20 +315,15 @@ int szg_column_set(szg_column *c, uint64_t row, const void *value)
     SZG_TRY
     if (!c) return fail(SZG_E_INVALID, "null argument");
     if (int rc = column_check(c)) return rc;
+    if (c->kind == SZG_COL_STR) return kind_mismatch();
     if (row < c->owner->row_base || row - c->owner->row_base >= c->rows) return fail(SZG_E_RANGE, "row out of range");
     row -= c->owner->row_base;
-    for (szg_column::Part &p : c->parts) {
-        if (row < p.first || row - p.first >= p.n_rows) continue;
-        const uint64_t l = row - p.first;
-        HIPCHK(hipSetDevice(p.device));
-        if (value) HIPCHK(hipMemcpy((uint8_t *)p.values + l * c->elem(), value, c->elem(), hipMemcpyHostToDevice));
-        uint64_t w = p.present_host[l / 64];
-        w = value ? (w | (1ull << (l & 63))) : (w & ~(1ull << (l & 63)));
-        HIPCHK(hipMemcpy(p.present + l / 64, &w, sizeof(w), hipMemcpyHostToDevice));
-        p.present_host[l / 64] = w;
-        return SZG_OK;
-    }
-    return stale_column();
+    szg_column::Part *p = part_of(c, row);
+    if (!p) return stale_column();
+    const uint64_t l = row - p->first;
+    HIPCHK(hipSetDevice(p->device));
+    if (value) HIPCHK(hipMemcpy((uint8_t *)p->values + l * c->elem(), value, c->elem(), hipMemcpyHostToDevice));
+    return set_present(*p, l, value != nullptr);
     SZG_CATCH
 }
 
@@ -224,6 +333,7 @@ int szg_column_read(const szg_column *c, uint64_t first_row, uint64_t n_rows, vo
 {
     SZG_TRY
     if (!c) return fail(SZG_E_INVALID, "null argument");
+    if (out_values && c->kind == SZG_COL_STR) return kind_mismatch();
     if (first_row < c->owner->row_base) return fail(SZG_E_RANGE, "row range out of bounds");
     first_row -= c->owner->row_base;
     if (first_row > c->rows || n_rows > c->rows - first_row) return fail(SZG_E_RANGE, "row range out of bounds");
@@ -238,6 +348,124 @@ int szg_column_read(const szg_column *c, uint64_t first_row, uint64_t n_rows, vo
                              hipMemcpyDeviceToHost));
         }
         if (out_present_bits) copy_bits(out_present_bits, lo - first_row, p.present_host.data(), lo - p.first, hi - lo);
+    }
+    return SZG_OK;
+    SZG_CATCH
+}
+
+int szg_column_create_str(szg_index *ix, const uint8_t *bytes, const uint64_t *offsets, const uint64_t *present_bits,
+                          uint64_t n_rows, szg_column **out)
+{
+    SZG_TRY
+    if (!out || (!offsets && n_rows)) return fail(SZG_E_INVALID, "null argument");
+    if (n_rows && !str_offsets_valid(offsets, n_rows)) return fail(SZG_E_INVALID, "offsets start at 0 and never decrease");
+    if (!ix || (!bytes && n_rows && offsets[n_rows])) return fail(SZG_E_INVALID, "null argument");
+    if (n_rows > szg_index_rows(ix)) return fail(SZG_E_RANGE, "column longer than the handle's rows");
+    szg_column *c = new szg_column();
+    c->owner = ix;
+    c->kind = SZG_COL_STR;
+    c->epoch = ix->col_epoch.load();
+    c->parts.resize(ix->shards.size());
+    for (size_t s = 0; s < ix->shards.size(); s++) {
+        c->parts[s].device = ix->shards[s]->device;
+        c->parts[s].first = ix->shards[s]->first;
+    }
+    const int rc = column_extend_str(c, bytes, offsets, present_bits, n_rows);
+    if (rc) {
+        column_free(c);
+        return rc;
+    }
+    *out = c;
+    return SZG_OK;
+    SZG_CATCH
+}
+
+int szg_column_append_str(szg_column *c, const uint8_t *bytes, const uint64_t *offsets, const uint64_t *present_bits,
+                          uint64_t n_rows)
+{
+    SZG_TRY
+    if (!offsets && n_rows) return fail(SZG_E_INVALID, "null argument");
+    if (n_rows && !str_offsets_valid(offsets, n_rows)) return fail(SZG_E_INVALID, "offsets start at 0 and never decrease");
+    if (!c || (!bytes && n_rows && offsets[n_rows])) return fail(SZG_E_INVALID, "null argument");
+    if (int rc = column_check(c)) return rc;
+    if (c->kind != SZG_COL_STR) return kind_mismatch();
+    return column_extend_str(c, bytes, offsets, present_bits, n_rows);
+    SZG_CATCH
+}
+
+int szg_column_set_str(szg_column *c, uint64_t row, const uint8_t *value, uint64_t len)
+{
+    SZG_TRY
+    if (!c) return fail(SZG_E_INVALID, "null argument");
+    if (int rc = column_check(c)) return rc;
+    if (c->kind != SZG_COL_STR) return kind_mismatch();
+    if (row < c->owner->row_base || row - c->owner->row_base >= c->rows) return fail(SZG_E_RANGE, "row out of range");
+    row -= c->owner->row_base;
+    szg_column::Part *p = part_of(c, row);
+    if (!p) return stale_column();
+    const uint64_t l = row - p->first;
+    HIPCHK(hipSetDevice(p->device));
+    if (!value) return set_present(*p, l, false);
+    uint64_t *slot = (uint64_t *)p->values + l, ref = 0;
+    HIPCHK(hipMemcpy(&ref, slot, sizeof(ref), hipMemcpyDeviceToHost));
+    if (len <= (ref >> 32)) {   // in place
+        if (len) HIPCHK(hipMemcpy(p->heap + (uint32_t)ref, value, len, hipMemcpyHostToDevice));
+        ref = (uint64_t)(uint32_t)ref | (len << 32);
+        HIPCHK(hipMemcpy(slot, &ref, sizeof(ref), hipMemcpyHostToDevice));
+    } else {                    // behind the heap's last byte; the old bytes are dead
+        if (len > kStrHeapLimit || !str_heap_fits(p->heap_used + len))
+            return fail(SZG_E_UNSUPPORTED, "a part's text heap stays below 4 GiB");
+        if (int rc = heap_reserve(*p, p->heap_used + len)) return rc;
+        HIPCHK(hipMemcpy(p->heap + p->heap_used, value, len, hipMemcpyHostToDevice));
+        ref = p->heap_used | (len << 32);
+        HIPCHK(hipMemcpy(slot, &ref, sizeof(ref), hipMemcpyHostToDevice));
+        p->heap_used += len;
+    }
+    return set_present(*p, l, true);
+    SZG_CATCH
+}
+
+int szg_column_read_str(const szg_column *c, uint64_t first_row, uint64_t n_rows, uint64_t *out_offsets, uint8_t *out_bytes,
+                        uint64_t capacity, uint64_t *out_present_bits)
+{
+    SZG_TRY
+    if (!c) return fail(SZG_E_INVALID, "null argument");
+    if (c->kind != SZG_COL_STR) return kind_mismatch();
+    if (first_row < c->owner->row_base) return fail(SZG_E_RANGE, "row range out of bounds");
+    first_row -= c->owner->row_base;
+    if (first_row > c->rows || n_rows > c->rows - first_row) return fail(SZG_E_RANGE, "row range out of bounds");
+    if (out_present_bits) std::fill(out_present_bits, out_present_bits + index_words(n_rows), 0ull);
+    // the references of the rows, part by part, then the bytes from a copy of each part's heap
+    std::vector<uint64_t> refs((size_t)n_rows);
+    for (const szg_column::Part &p : c->parts) {
+        const uint64_t lo = std::max(first_row, p.first), hi = std::min(first_row + n_rows, p.first + p.n_rows);
+        if (lo >= hi) continue;
+        HIPCHK(hipSetDevice(p.device));
+        HIPCHK(hipMemcpy(refs.data() + (lo - first_row), (const uint64_t *)p.values + (lo - p.first),
+                         (hi - lo) * sizeof(uint64_t), hipMemcpyDeviceToHost));
+        if (out_present_bits) copy_bits(out_present_bits, lo - first_row, p.present_host.data(), lo - p.first, hi - lo);
+    }
+    uint64_t total = 0;
+    for (uint64_t i = 0; i < n_rows; i++) {
+        if (out_offsets) out_offsets[i] = total;
+        total += refs[(size_t)i] >> 32;
+    }
+    if (out_offsets) out_offsets[n_rows] = total;
+    if (!out_bytes) return SZG_OK;
+    if (capacity < total) return fail(SZG_E_TRUNCATED, "the rows' bytes do not fit the buffer");
+    std::vector<uint8_t> heap;
+    uint64_t at = 0;
+    for (const szg_column::Part &p : c->parts) {
+        const uint64_t lo = std::max(first_row, p.first), hi = std::min(first_row + n_rows, p.first + p.n_rows);
+        if (lo >= hi) continue;
+        heap.resize((size_t)p.heap_used);
+        HIPCHK(hipSetDevice(p.device));
+        if (p.heap_used) HIPCHK(hipMemcpy(heap.data(), p.heap, p.heap_used, hipMemcpyDeviceToHost));
+        for (uint64_t r = lo; r < hi; r++) {
+            const uint64_t ref = refs[(size_t)(r - first_row)], len = ref >> 32;
+            if (len) std::copy_n(heap.data() + (uint32_t)ref, len, out_bytes + at);
+            at += len;
+        }
     }
     return SZG_OK;
     SZG_CATCH
@@ -286,6 +514,26 @@ int szg_mask_where_u32(const szg_column *c, const uint64_t *code_bits, uint32_t 
         DevBuf<uint64_t> bits;
         if (int rc = upload_small(&bits, code_bits, index_words(n_codes))) return rc;
         HIPCHK(szg::launch_column_codes_u32(static_cast<const uint32_t *>(c->parts[s].values), bits, n_codes, w, nullptr));
+        HIPCHK(hipStreamSynchronize(nullptr));
+        return SZG_OK;
+    });
+    SZG_CATCH
+}
+
+int szg_mask_where_str(const szg_column *c, int op, const uint8_t *constant, uint32_t len, const szg_mask *base,
+                       szg_mask **out)
+{
+    SZG_TRY
+    if (op < SZG_CMP_EQ || op > SZG_STR_CONTAINS) return fail(SZG_E_INVALID, "unknown comparison or string operator");
+    if (len > SZG_STR_PATTERN_MAX) return fail(SZG_E_UNSUPPORTED, "a text constant holds at most 256 bytes");
+    if (!constant && len) return fail(SZG_E_INVALID, "null argument");
+    std::vector<uint32_t> dwords((len + 3) / 4, 0u);   // (the last one zero-padded)
+    if (len) std::memcpy(dwords.data(), constant, len);
+    return mask_where(c, SZG_COL_STR, base, out, [&](size_t s, const szg::ColumnWhere &w) -> int {
+        DevBuf<uint32_t> k;   // (freed after the launch: mask_where's copies wait for the kernel)
+        if (int rc = upload_small(&k, dwords.data(), dwords.size())) return rc;
+        HIPCHK(szg::launch_column_str(static_cast<const uint64_t *>(c->parts[s].values), c->parts[s].heap, op, k, len, w,
+                                      nullptr));
         HIPCHK(hipStreamSynchronize(nullptr));
         return SZG_OK;
     });

@@ -505,10 +505,11 @@ struct szg_mask {
 
 // A resident metadata column (scan_column.cpp): one value and one present bit per row, each shard's part on the shard's
 // own device.  It covers rows [0, rows) of its handle, rows <= szg_index_rows: index appends leave it short until
-// szg_column_append catches up.
+// szg_column_append catches up.  A text column's value is an 8-byte reference {uint32 start, uint32 len} into the
+// part's byte heap (column_str.h has its size rules).
 struct szg_column {
     szg_index *owner = nullptr;
-    int kind = 0;           // SZG_COL_F64 / SZG_COL_U32
+    int kind = 0;           // SZG_COL_F64 / SZG_COL_U32 / SZG_COL_STR
     uint64_t epoch = 0;     // the owner's col_epoch this column was made at
     uint64_t rows = 0;
     struct Part {
@@ -517,9 +518,11 @@ struct szg_column {
         void *values = nullptr;            // device, cap_rows elements
         uint64_t *present = nullptr;       // device, cap_rows / 64 words in the masks' 16-byte-pair layout, tail bits 0
         std::vector<uint64_t> present_host;  // the same words
+        uint8_t *heap = nullptr;           // text columns: device, heap_cap bytes, zero behind heap_used
+        uint64_t heap_used = 0, heap_cap = 0;  // heap_cap: 0 or a multiple of 16, >= the used bytes rounded up to 16, + 16
     };
     std::vector<Part> parts;              // one per shard of the owner
-    size_t elem() const { return kind == SZG_COL_F64 ? sizeof(double) : sizeof(uint32_t); }
+    size_t elem() const { return kind == SZG_COL_U32 ? sizeof(uint32_t) : 8; }   // (a double, or a text reference)
 };
 
 namespace szgi {

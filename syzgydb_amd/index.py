@@ -11,6 +11,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import SZG_COSINE, SZG_EUCLIDEAN, SzgError, SzgMaskStats, SzgScanPlan, SzgStats, check  # noqa: F401
+from .where import _bytes
 
 
 def _u8(a):
@@ -108,12 +109,32 @@ class ScanMask:
 
 _CMP_OPS = {"==": _lib.SZG_CMP_EQ, "!=": _lib.SZG_CMP_NE, "<": _lib.SZG_CMP_LT, "<=": _lib.SZG_CMP_LE,
             ">": _lib.SZG_CMP_GT, ">=": _lib.SZG_CMP_GE}
+_TEXT = (bytes, bytearray, memoryview, str)
+
+
+def _text(value):
+    """One text value or constant as bytes: a str is encoded as the filter evaluator encodes it (where._bytes)."""
+    return _bytes(value) if isinstance(value, str) else bytes(value)
+
+
+def _text_arg(values, present):
+    """A sequence of bytes / str / None as the *_str calls take it: (keep-alive array, bytes pointer, uint64
+    offsets[n + 1], present).  None is an absent row unless `present` is given."""
+    vals = [None if v is None else _text(v) for v in values]
+    if present is None and any(v is None for v in vals):
+        present = np.array([v is not None for v in vals], dtype=bool)
+    offsets = np.zeros(len(vals) + 1, dtype=np.uint64)
+    if vals:
+        np.cumsum([0 if v is None else len(v) for v in vals], out=offsets[1:])
+    data = np.frombuffer(b"".join(v for v in vals if v is not None), dtype=np.uint8)
+    return data, (_u8(data) if data.size else None), offsets, present
 
 
 class ScanColumn:
     """A metadata column that lives on the card beside the rows (szg_column): one value and one present bit per row,
-    float64 values (kind F64) or uint32 codes of a dictionary the caller owns (kind U32).  Made by ScanIndex.column;
-    where / isin / codes / present compare it against constants ON THE DEVICE and return a ScanMask.  Index appends
+    float64 values (kind F64), uint32 codes of a dictionary the caller owns (kind U32), or the strings themselves as
+    bytes (kind STR, a text column).  Made by ScanIndex.column / text_column; where / isin / codes / startswith /
+    endswith / contains / present compare it against constants ON THE DEVICE and return a ScanMask.  Index appends
     leave it short until append() catches up; a load, synth, reorder or a compaction that moves rows makes it stale
     (every call but rows / read / close then raises SzgError, SZG_E_INVALID)."""
 
@@ -163,6 +184,12 @@ class ScanColumn:
 
     def append(self, values, present=None):
         """Rows behind the column's last (the index holds them already); present refers to THESE rows."""
+        if self.kind == _lib.SZG_COL_STR:
+            data, dp, offsets, present = _text_arg(values, present)
+            keep, pp = self._present_arg(present, offsets.size - 1)
+            check(self._L.szg_column_append_str(self._live(), dp, _u64(offsets), pp, offsets.size - 1), "szg_column_append_str")
+            del keep, data
+            return
         v = np.ascontiguousarray(values, dtype=self._dtype).reshape(-1)
         keep, pp = self._present_arg(present, v.size)
         check(self._L.szg_column_append(self._live(), v.ctypes.data_as(ctypes.c_void_p) if v.size else None, pp, v.size),
@@ -171,6 +198,11 @@ class ScanColumn:
 
     def set(self, row, value):
         """One row's value; None marks it absent."""
+        if self.kind == _lib.SZG_COL_STR:
+            b = None if value is None else _text(value)
+            buf = None if b is None else (ctypes.c_uint8 * max(len(b), 1)).from_buffer_copy(b or b"\0")
+            check(self._L.szg_column_set_str(self._live(), int(row), buf, len(b) if b is not None else 0), "szg_column_set_str")
+            return
         v = None if value is None else np.asarray([value], dtype=self._dtype)
         check(self._L.szg_column_set(self._live(), int(row), v.ctypes.data_as(ctypes.c_void_p) if v is not None else None),
               "szg_column_set")
@@ -180,8 +212,19 @@ class ScanColumn:
         return int(self._L.szg_column_rows(self._live()))
 
     def read(self):
-        """(values, present bool[rows]) of the whole column."""
+        """(values, present bool[rows]) of the whole column; a text column's values are a list of bytes."""
         n = self.rows
+        if self.kind == _lib.SZG_COL_STR:
+            offsets = np.zeros(n + 1, dtype=np.uint64)
+            w = np.zeros((n + 63) // 64, dtype=np.uint64)
+            check(self._L.szg_column_read_str(self._live(), self._index._row_base, n, _u64(offsets), None, 0, None),
+                  "szg_column_read_str")
+            data = np.zeros(max(int(offsets[n]), 1), dtype=np.uint8)
+            check(self._L.szg_column_read_str(self._live(), self._index._row_base, n, _u64(offsets), _u8(data), data.size,
+                                              _u64(w) if n else None), "szg_column_read_str")
+            raw = data.tobytes()
+            values = [raw[int(offsets[i]):int(offsets[i + 1])] for i in range(n)]
+            return values, np.unpackbits(w.view(np.uint8), bitorder="little")[:n].astype(bool)
         v = np.zeros(n, dtype=self._dtype)
         w = np.zeros((n + 63) // 64, dtype=np.uint64)
         check(self._L.szg_column_read(self._live(), self._index._row_base, n, v.ctypes.data_as(ctypes.c_void_p) if n else None,
@@ -196,7 +239,10 @@ class ScanColumn:
         return ScanMask(self._index, h, (self._index.rows + 63) // 64)
 
     def where(self, op, value, base=None):
-        """Rows that are present and whose value `op` the constant (op: == != < <= > >=, or SZG_CMP_*), & base."""
+        """Rows that are present and whose value `op` the constant (op: == != < <= > >=, or SZG_CMP_*), & base.  A
+        bytes / str constant is compared with a text column's values, bytewise."""
+        if isinstance(value, _TEXT):
+            return self._where_str(int(_CMP_OPS.get(op, op)), value, base)
         return self._mask(self._L.szg_mask_where_f64, "szg_mask_where_f64", int(_CMP_OPS.get(op, op)), float(value),
                           base=base)
 
@@ -211,6 +257,21 @@ class ScanColumn:
         a = np.asarray(allowed, dtype=bool).reshape(-1)
         w = pack_allow_bits(a)[0]
         return self._mask(self._L.szg_mask_where_u32, "szg_mask_where_u32", _u64(w) if w.size else None, a.size, base=base)
+
+    def _where_str(self, op, constant, base):
+        b = _text(constant)
+        buf = (ctypes.c_uint8 * max(len(b), 1)).from_buffer_copy(b or b"\0")
+        return self._mask(self._L.szg_mask_where_str, "szg_mask_where_str", op, buf, len(b), base=base)
+
+    def startswith(self, constant, base=None):
+        """Text columns: rows that are present and whose value starts with the constant (at most 256 bytes), & base."""
+        return self._where_str(_lib.SZG_STR_STARTS_WITH, constant, base)
+
+    def endswith(self, constant, base=None):
+        return self._where_str(_lib.SZG_STR_ENDS_WITH, constant, base)
+
+    def contains(self, constant, base=None):
+        return self._where_str(_lib.SZG_STR_CONTAINS, constant, base)
 
     def present(self, base=None):
         """The present rows, & base."""
@@ -457,6 +518,19 @@ class ScanIndex:
                                         ctypes.byref(h)), "szg_column_create")
         del keep
         return ScanColumn(self, h, kind)
+
+    def text_column(self, values, present=None):
+        """A text ScanColumn (kind SZG_COL_STR) over the first len(values) rows: values is a sequence of bytes / str /
+        None -- a str is stored as its UTF-8 bytes, None is an absent row unless `present` (as for column) says
+        otherwise.  For a field whose values are mostly distinct; one with few distinct values is cheaper as codes of
+        a dictionary (column, kind SZG_COL_U32)."""
+        data, dp, offsets, present = _text_arg(values, present)
+        keep, pp = ScanColumn._present_arg(present, offsets.size - 1)
+        h = ctypes.c_void_p()
+        check(self._L.szg_column_create_str(self._h, dp, _u64(offsets), pp, offsets.size - 1, ctypes.byref(h)),
+              "szg_column_create_str")
+        del keep, data
+        return ScanColumn(self, h, _lib.SZG_COL_STR)
 
     def mask_stats(self):
         s = SzgMaskStats()
