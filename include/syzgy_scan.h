@@ -267,8 +267,9 @@ int szg_index_compact(szg_index *ix, uint64_t *out_new_of_old, uint64_t *out_row
  * Mutations: szg_index_tombstone and the overwrites leave a column valid; the appends leave it valid but short.
  *   szg_index_load, szg_index_synth, szg_index_reorder and a szg_index_compact that moves rows (one without
  *   tombstones does not) make it STALE: every call except szg_column_rows, szg_column_read and szg_column_destroy
- *   then returns SZG_E_INVALID ("stale column") and never reads past the column.  Columns are not carried across a
- *   reorder: the host creates them again, 8 bytes per row, once per compaction.
+ *   then returns SZG_E_INVALID ("stale column") and never reads past the column.  szg_index_reorder_carry and
+ *   szg_index_compact_carry take the columns they are given along on the device, and those stay valid (see "Columns
+ *   carried across compaction and reorder" below); a column they are not given goes stale all the same.
  * Threads: szg_mask_where_* and szg_column_read may run beside searches and beside each other; create / append / set /
  *   destroy need the exclusive access mutations have.  Columns are destroyed before their handle.
  * Failure: every check happens on the host before anything is allocated or launched; an error leaves the column as
@@ -286,8 +287,8 @@ int szg_index_compact(szg_index *ix, uint64_t *out_new_of_old, uint64_t *out_row
  *   heap, and the present bits.  Create and append write a call's strings back to back in row order; an absent row
  *   has length 0.  The heap grows geometrically; its capacity is a multiple of 16 bytes that ends at least 16 zero
  *   bytes past the last used byte, and stays below 4 GiB per part: a call that would exceed that returns
- *   SZG_E_UNSUPPORTED with the column unchanged.  Dead bytes (szg_column_set_str) are reclaimed only by making the
- *   column again.
+ *   SZG_E_UNSUPPORTED with the column unchanged.  Dead bytes (szg_column_set_str) are reclaimed by a carry across a
+ *   compaction or reorder, which repacks the heap, or by making the column again.
  *   szg_mask_where_str: op is SZG_CMP_EQ..SZG_CMP_GE or SZG_STR_STARTS_WITH / ENDS_WITH / CONTAINS, anything else
  *   SZG_E_INVALID ("operator" in szg_last_error); a constant of more than SZG_STR_PATTERN_MAX bytes is
  *   SZG_E_UNSUPPORTED, a NULL constant with len > 0 SZG_E_INVALID.  The empty constant is legal: the three string
@@ -351,6 +352,50 @@ int szg_mask_where_str(const szg_column *c, int op, const uint8_t *constant, uin
                        const szg_mask *base, szg_mask **out);
 /* the present bits (every kind) */
 int szg_mask_where_present(const szg_column *c, const szg_mask *base, szg_mask **out);
+
+/* ---- columns carried across compaction and reorder (added under ABI 4, additive) ----
+ *
+ * szg_index_reorder and szg_index_compact with columns to take along: everything said of those two calls holds, and
+ * they ARE these calls with n_columns == 0 (every column of the handle then goes stale).
+ * Columns: columns[0 .. n_columns) are columns of this handle that are neither stale nor short; a duplicate is taken
+ *   once.  Same reads: after the call a carried column reads at new row i exactly what it read at the old row that
+ *   became row i -- through szg_column_read and szg_column_read_str alike: the value bit for bit (NaN payloads and
+ *   -0.0 included), the present bit, and for a row marked absent its stored value or stored bytes too.  State
+ *   afterwards: szg_column_rows == the new row count, the column is valid, its parts follow the new shard ranges, and
+ *   capacities, present words (tail bits 0) and the heap's sizing are those of a freshly created column of these rows;
+ *   szg_column_append, szg_column_set, the _str calls and every szg_mask_where_* go on working.  Every column NOT in
+ *   the list becomes stale, as before.
+ * Text columns: afterwards the heap of each part holds each carried row's bytes exactly once, back to back, and nothing
+ *   else: szg_column_info.heap_used == the sum of the carried rows' lengths, the bytes behind it are zero, and the
+ *   capacity is that of a fresh column of these bytes.  Dead bytes (szg_column_set_str) and the bytes of dropped rows
+ *   are reclaimed.  The order of the bytes inside a part is not specified.  A destination part whose carried bytes
+ *   would reach the 4 GiB heap limit returns SZG_E_UNSUPPORTED.
+ * Refusals: a null entry, a column of another handle, a stale column ("stale column") and a short one ("short column",
+ *   szg_column_rows != szg_index_rows) are SZG_E_INVALID.
+ * szg_index_compact_carry on a handle without tombstones moves nothing, makes nothing stale and leaves heaps as they
+ *   are.
+ * Failure: every check and every allocation -- a text part's byte total, which comes from a scan on the device and is
+ *   read back, included -- happens before the switch.  On any error the rows, live bits, masks and ALL columns, carried
+ *   or not, are exactly as they were, and still valid.
+ * Memory: the peak during the call is the old plus the new column allocations, beside what the rows take; a handle of
+ *   one shard adds 24 bytes per row of scratch while a text column is repacked (the list, which rows and columns share,
+ *   the gathered references and the new starts), a handle of several 16 bytes per row of a destination part for the
+ *   lists, 16 more per row of a text column, and four staging buffers of at most 64 MiB.
+ */
+int szg_index_reorder_carry(szg_index *ix, const uint64_t *src_rows, uint64_t n_rows,
+                            szg_mask *const *masks, int n_masks,
+                            szg_column *const *columns, int n_columns);
+int szg_index_compact_carry(szg_index *ix, uint64_t *out_new_of_old, uint64_t *out_rows,
+                            szg_mask *const *masks, int n_masks,
+                            szg_column *const *columns, int n_columns);
+typedef struct szg_column_info {
+    int32_t kind;            /* SZG_COL_* */
+    uint64_t rows;           /* szg_column_rows */
+    uint64_t device_bytes;   /* values, present words and heaps as allocated, summed over the parts */
+    uint64_t heap_used;      /* text columns: bytes in use, dead ones included, summed over the parts; else 0 */
+    uint64_t heap_capacity;  /* text columns: bytes allocated, summed over the parts; else 0 */
+} szg_column_info;
+int szg_column_get_info(const szg_column *c, szg_column_info *out);   /* works on a stale column */
 
 /*
  * The reference's float64 distance (c.distance, collection.go:596, :812-832) from
@@ -614,7 +659,9 @@ int szg_reset_stats(szg_index *ix);
  *                             second host thread while the caller's prepares and enqueues the next ones
  *   test hooks (paths that data takes by itself only rarely): force_escalate, force_matrix (the score-matrix form of
  *   the shared sweeps: small shards, candidate-buffer overflow), force_no_refine (their tail as separate launches: kp > 256),
- *   force_sketch_nomem (the sketch's device allocation is refused: auto mode steps aside, sketch = 1 reports it)
+ *   force_sketch_nomem (the sketch's device allocation is refused: auto mode steps aside, sketch = 1 reports it),
+ *   carry_stage_bytes (the staging window of carried columns on a handle of several shards: 0 = 64 MiB, else a multiple
+ *   of 16 up to that, so that a small column travels in several windows)
  */
 int szg_set_option(szg_index *ix, const char *name, int64_t value);
 

@@ -10,6 +10,7 @@
 #   scripts/kernel_resources.sh exact         -> kernels_exact.hip (re-rank, page-in, row gather, ...)
 #   scripts/kernel_resources.sh mask          -> kernels_mask.hip (device-resident filter masks)
 #   scripts/kernel_resources.sh column        -> kernels_column.hip (resident metadata columns)
+#   scripts/kernel_resources.sh column carry  -> kernels_column_carry.hip (columns carried across compaction / reorder)
 # (hipcc -Rpass-analysis=kernel-resource-usage, device code only; no GPU needed)
 set -euo pipefail
 cd "$(dirname "$0")/../syzgydb_amd/csrc"
@@ -17,6 +18,7 @@ kind=${1:-mq}; part=${2:-i8}
 if [ "$kind" = scan ]; then src=kernels_scan.hip; def=-DSZG_QBITS=$part
 elif [ "$kind" = exact ]; then src=kernels_exact.hip; def=-ffp-contract=off
 elif [ "$kind" = mask ]; then src=kernels_mask.hip; def=
+elif [ "$kind" = column ] && [ "$part" = carry ]; then src=kernels_column_carry.hip; def=
 elif [ "$kind" = column ]; then src=kernels_column.hip; def=
 elif [ "$part" = select ]; then src=kernels_mq.hip; def=
 elif [ "$part" = bf16d ]; then src=kernels_mq_bf16d.hip; def=

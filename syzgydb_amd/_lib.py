@@ -45,6 +45,8 @@ EXPORTS = [
     "szg_column_destroy", "szg_mask_where_f64", "szg_mask_where_in_f64", "szg_mask_where_u32", "szg_mask_where_present",
     # text columns (added under ABI 4)
     "szg_column_create_str", "szg_column_append_str", "szg_column_set_str", "szg_column_read_str", "szg_mask_where_str",
+    # columns carried across compaction / reorder (added under ABI 4)
+    "szg_index_reorder_carry", "szg_index_compact_carry", "szg_column_get_info",
     # host-only test hook
     "szg_debug_scan_plan", "szg_debug_scan_group", "szg_debug_reorder_plan", "szg_debug_option_check",
 ]
@@ -101,6 +103,11 @@ class SzgScanPlan(ctypes.Structure):
     _fields_ = [(name, ctypes.c_int32) for name in (
         "r16", "L", "P", "gpw", "pow2", "dense", "tiled", "grid", "block", "ring_depth", "shaped", "nontemporal",
         "rows_per_block")]
+
+
+class SzgColumnInfo(ctypes.Structure):
+    _fields_ = [("kind", ctypes.c_int32), ("rows", ctypes.c_uint64), ("device_bytes", ctypes.c_uint64),
+                ("heap_used", ctypes.c_uint64), ("heap_capacity", ctypes.c_uint64)]
 
 
 class SzgMaskStats(ctypes.Structure):
@@ -258,6 +265,15 @@ def load():
         L.szg_column_read_str.argtypes = [vp, ctypes.c_uint64, ctypes.c_uint64, u64p, u8p, ctypes.c_uint64, u64p]
         L.szg_mask_where_str.restype = ctypes.c_int
         L.szg_mask_where_str.argtypes = [vp, ctypes.c_int, u8p, ctypes.c_uint32, vp, ctypes.POINTER(vp)]
+    if hasattr(L, "szg_index_reorder_carry"):   # (an older build for an A/B run carries no columns)
+        L.szg_index_reorder_carry.restype = ctypes.c_int
+        L.szg_index_reorder_carry.argtypes = [vp, u64p, ctypes.c_uint64, ctypes.POINTER(vp), ctypes.c_int,
+                                              ctypes.POINTER(vp), ctypes.c_int]
+        L.szg_index_compact_carry.restype = ctypes.c_int
+        L.szg_index_compact_carry.argtypes = [vp, u64p, u64p, ctypes.POINTER(vp), ctypes.c_int, ctypes.POINTER(vp),
+                                              ctypes.c_int]
+        L.szg_column_get_info.restype = ctypes.c_int
+        L.szg_column_get_info.argtypes = [vp, ctypes.POINTER(SzgColumnInfo)]
     L.szg_comm_unique_id.restype = ctypes.c_int
     L.szg_comm_unique_id.argtypes = [u8p]
     L.szg_comm_create.restype = ctypes.c_int

@@ -114,6 +114,7 @@ class Collection:
             raise ValueError("auto_compact is None or a fraction in [0, 1)")
         self.auto_compact = None if auto_compact is None else float(auto_compact)
         self.compactions = 0
+        self.column_rebuilds = 0   # calls of _rebuild_columns (the columns made again from the metadata); the package itself makes none
         self._row_of = {}    # id -> row
         self._id_of = []     # row -> id (None once tombstoned)
         self._meta = []      # row -> metadata bytes
@@ -170,12 +171,12 @@ class Collection:
 
     def _resort(self):
         """Re-page the live rows in sorted decimal-string id order: the rows are reordered on the card
-        (ScanIndex.reorder), nothing travels through the host.  No mask is carried: the numbering changes
-        arbitrarily, and the version moves."""
+        (ScanIndex.reorder), nothing travels through the host, and the resident columns follow their rows there.  No
+        mask is carried: the numbering changes arbitrarily, and the version moves."""
         live = sorted((str(id), id, row) for id, row in self._row_of.items())
         rows = [row for _, _, row in live]
         new_meta = [self._meta[r] for r in rows]
-        self._index.reorder(np.asarray(rows, dtype=np.uint64))
+        self._index.reorder(np.asarray(rows, dtype=np.uint64), carry=self._resident_columns())
         self._id_of = [id for _, id, _ in live]
         self._meta = new_meta
         self._row_of = {id: i for i, id in enumerate(self._id_of)}
@@ -183,7 +184,6 @@ class Collection:
         self._order_stale = False
         self.resorts += 1
         self._version += 1  # rows are renumbered: cached filter masks no longer apply
-        self._rebuild_columns()
 
     # -- CRUD (host bookkeeping + mirror maintenance) ---------------------------
     def AddDocument(self, id: int, vector, metadata: bytes = b""):
@@ -262,7 +262,10 @@ class Collection:
         the live rows keep their order, so answers do not change -- the sweeps read fewer bytes, the memory is
         returned, and a shard without tombstones is back on the unmasked fast paths.  The cached filters of the
         current version are carried: their device masks are renumbered on the card, so the next Search with one of
-        them costs neither an evaluation of the filter nor an upload.  Returns the rows dropped."""
+        them costs neither an evaluation of the filter nor an upload.  The columns of the indexed fields are carried
+        the same way: the card gathers their values and present bits and repacks the text heaps (which reclaims the
+        bytes of dropped rows and of values that were replaced by longer ones); no metadata is parsed again.  Returns
+        the rows dropped."""
         dropped = self._index.rows - self._index.live_rows
         if dropped == 0:
             return 0
@@ -271,7 +274,7 @@ class Collection:
             if m is not None:
                 m.close()
         current = list(self._mask_cache.items())
-        new_of_old = self._index.compact(carry=[e[2] for _, e in current if e[2] is not None])
+        new_of_old = self._index.compact(carry=[e[2] for _, e in current if e[2] is not None] + self._resident_columns())
         keep = np.flatnonzero(new_of_old != np.uint64(0xFFFFFFFFFFFFFFFF))   # the old row of every new row, ascending
         n_old = len(self._id_of)
         self._id_of = [self._id_of[r] for r in keep]
@@ -286,7 +289,6 @@ class Collection:
                 bits = np.unpackbits(np.ascontiguousarray(words).view(np.uint8), bitorder="little")[:n_old]
                 words = pack_allow_bits(bits[keep].astype(bool))
             self._mask_cache[(key, self._version)] = [words, flt, mask]
-        self._rebuild_columns()
         self.compactions += 1
         return dropped
 
@@ -339,7 +341,7 @@ class Collection:
         whose values are mostly distinct (an email, a name, an id): the strings' bytes live on the card, with no
         dictionary, and the card compares them (constants of up to 256 bytes, IN-lists of up to 16).  The resident
         metadata is parsed once, now; from then on AddDocument(s) append to the column, UpdateDocument sets the row,
-        and Compact() and the re-sort rebuild it.  Search with SearchArgs.Where then compares the field on the card."""
+        and Compact() and the re-sort carry it along on the card.  Search with SearchArgs.Where then compares the field on the card."""
         if kind not in ("number", "string", "text"):
             raise ValueError('kind is "number", "string" or "text"')
         _where.Field(name)   # (the name must be an identifier of the filter language)
@@ -364,8 +366,19 @@ class Collection:
         f.column = self._index.column(values, present=present,
                                       kind=_lib.SZG_COL_F64 if f.kind == "number" else _lib.SZG_COL_U32)
 
+    def _resident_columns(self):
+        """Every indexed field's column and the hidden object column: what a compaction or a re-sort carries.  (A
+        "string" field's dictionary stays as it is: the codes are what travels.)"""
+        if not self._fields:
+            return []
+        return [f.column for f in self._fields.values()] + [self._object_col]
+
     def _rebuild_columns(self):
-        """The rows were renumbered (Compact, the re-sort): the columns are made again from the resident metadata."""
+        """Every column made again from the resident metadata (a json.loads per document, every column uploaded).
+        Nothing in the package calls this today: Compact, auto_compact and the re-sort carry the columns on the card.
+        It is kept as the way back for a path that would replace the rows without a list to carry by, and as the
+        parent's route that scripts/dev_compact_columns.py times; column_rebuilds counts its calls."""
+        self.column_rebuilds += 1
         if not self._fields:
             return
         parsed = [_where.parse_metadata(m) for m in self._meta]

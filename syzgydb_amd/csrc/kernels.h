@@ -388,4 +388,23 @@ hipError_t launch_column_present(const ColumnWhere &w, hipStream_t stream);
 hipError_t launch_column_str(const uint64_t *refs, const uint8_t *heap, int op, const uint32_t *constant, uint32_t len,
                              const ColumnWhere &w, hipStream_t stream);
 
+// ---- kernels_column_carry.hip: columns carried across a compaction / reorder, ONE part per launch --------------------
+// out[at[i]] = values[list[i]], i < n, elements of `elem` = 8 or 4 bytes; at null: out[i]; list null: values[i]
+hipError_t launch_carry_gather(const void *values, uint32_t elem, const uint64_t *list, const uint64_t *at, void *out,
+                               uint64_t n, hipStream_t stream);
+// A text part's rows list[0 .. n) (null: rows 0 .. n - 1): refs_out[i] = refs[list[i]], starts[i] = the lengths of
+// refs_out[0 .. i) added up (64-bit), sums[carry_scan_blocks(n)] = the lengths of all of them.  sums: scratch of
+// carry_scan_blocks(n) + 1 words.  Three launches, none of whose blocks waits for another.
+uint64_t carry_scan_blocks(uint64_t n);
+hipError_t launch_carry_ref_starts(const uint64_t *refs, const uint64_t *list, uint64_t n, uint64_t *refs_out,
+                                   uint64_t *starts, uint64_t *sums, hipStream_t stream);
+// The 16-byte pieces [piece0, piece0 + n_pieces) of the rows' bytes laid back to back (row i's at starts[i], `total`
+// in all, zero from there on) into dst (16-byte aligned, n_pieces pieces), read from old_heap through refs (both as
+// launch_carry_ref_starts left them).  Only dwords of old_heap that hold a byte of a row are read.
+hipError_t launch_carry_move_bytes(const uint8_t *old_heap, const uint64_t *refs, const uint64_t *starts, uint64_t n,
+                                   uint64_t total, uint64_t piece0, uint64_t n_pieces, uint8_t *dst, hipStream_t stream);
+// out[at[i]] (at null: out[i]) = the reference {base + starts[i], length of refs[i]}; base + total < 2^32
+hipError_t launch_carry_new_refs(const uint64_t *refs, const uint64_t *starts, uint64_t n, uint64_t base, const uint64_t *at,
+                                 uint64_t *out, hipStream_t stream);
+
 }  // namespace szg

@@ -6,16 +6,17 @@
 // single-row updates edit before they upload the words they touched).  Parts
 // follow Shard::first; index appends only extend the last shard that holds rows or start the next one, so a part never
 // moves -- it grows geometrically, in place of its old allocation.  szg_mask_where_* run one compare kernel per shard
-// (kernels_column.hip) that writes the words and the count of an ordinary szg_mask.
+// (kernels_column.hip) that writes the words and the count of an ordinary szg_mask.  A compaction / reorder that is
+// asked to carry a column replaces its parts as a whole (scan_column_carry.cpp).
 #include "scan_internal.h"
 #include "column_bits.h"
 #include "column_str.h"
 
 using namespace szgi;
 
-namespace {
+int szgi::stale_column() { return fail(SZG_E_INVALID, "stale column: the handle's rows were loaded or renumbered after the column was made"); }
 
-int stale_column() { return fail(SZG_E_INVALID, "stale column: the handle's rows were loaded or renumbered after the column was made"); }
+namespace {
 
 void column_free(szg_column *c)
 {
@@ -328,6 +329,23 @@ int szg_column_set(szg_column *c, uint64_t row, const void *value)
 }
 
 uint64_t szg_column_rows(const szg_column *c) { return c ? c->rows : 0; }
+
+int szg_column_get_info(const szg_column *c, szg_column_info *out)
+{
+    SZG_TRY
+    if (!c || !out) return fail(SZG_E_INVALID, "null argument");
+    szg_column_info info{};
+    info.kind = c->kind;
+    info.rows = c->rows;
+    for (const szg_column::Part &p : c->parts) {
+        info.device_bytes += p.cap_rows * c->elem() + p.cap_rows / 8 + p.heap_cap;
+        info.heap_used += p.heap_used;
+        info.heap_capacity += p.heap_cap;
+    }
+    *out = info;
+    return SZG_OK;
+    SZG_CATCH
+}
 
 int szg_column_read(const szg_column *c, uint64_t first_row, uint64_t n_rows, void *out_values, uint64_t *out_present_bits)
 {

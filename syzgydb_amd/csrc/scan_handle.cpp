@@ -1,5 +1,6 @@
 // scan_handle.cpp -- the handle: lifetime, per-shard contexts, mutations, tunables, statistics.
 #include "scan_internal.h"
+#include "column_carry.h"
 
 namespace szgi {
 
@@ -671,6 +672,12 @@ int szg_set_option(szg_index *ix, const char *name, int64_t value)
     }
     if (n == "force_sketch_nomem") {
         ix->force_sketch_nomem = value != 0;
+        return SZG_OK;
+    }
+    if (n == "carry_stage_bytes") {   // (0 = the default; pieces of 16 bytes travel, so a window is a multiple of 16)
+        if (value < 0 || value % 16 || (uint64_t)value > kCarryStageBytes)
+            return fail(SZG_E_INVALID, "carry_stage_bytes is 0 or a multiple of 16 up to 64 MiB");
+        ix->carry_stage_bytes = (uint64_t)value;
         return SZG_OK;
     }
     if (n == "sketch_min_rows") {

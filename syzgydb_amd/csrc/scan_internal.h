@@ -12,6 +12,7 @@
 //   scan_comm.cpp     one-process-per-GPU exchange (RCCL all-gather + merge)
 //   scan_mask.cpp     device-resident filter masks (szg_mask) and the searches that take them
 //   scan_column.cpp   resident metadata columns (szg_column): comparisons against constants that write masks
+//   scan_column_carry.cpp  columns carried across a compaction / reorder (column_carry.h: its index arithmetic)
 //   scan_reorder.cpp  compaction and reorder of the resident rows on the device (reorder_plan.h: its host-only checks)
 //   scan_api.cpp      remaining C entry points (top-k with caller coalescing, distances)
 //
@@ -453,6 +454,7 @@ struct szg_index {
     int force_matrix = 0;     // shared sweeps: the score-matrix form (what an overflowing candidate buffer falls back to)
     int force_no_refine = 0;  // shared sweeps: the batch's tail as separate re-score / select / rerank launches (kp > 256)
     int force_sketch_nomem = 0;  // the sketch's device allocation is refused (auto mode steps aside)
+    uint64_t carry_stage_bytes = 0;  // a carried column's staging window between two parts; 0 = kCarryStageBytes
     // settled by measurement (rounds 1-3): compile-time facts since round 4, A/B through -D and `make variant`
     static constexpr int blocks_per_cu = 0;     // 0 = waves per CU chosen from the row format (scan_geometry)
     static constexpr int block_threads = 256;
@@ -704,6 +706,29 @@ inline size_t mask_slot_words(uint64_t n_rows) { return (size_t)(((n_rows + 63) 
 inline size_t mask_slot_words(const Shard *sh) { return mask_slot_words(sh->n_rows); }
 // words of a mask with one bit per row (no padding): the host copy of a mask, a shard's slice of it
 inline size_t index_words(uint64_t rows) { return (size_t)((rows + 63) / 64); }
+
+// ---- scan_column.cpp
+int stale_column();  // SZG_E_INVALID, "stale column: ..."
+
+// ---- scan_column_carry.cpp: the columns a compaction / reorder carries (scan_reorder.cpp calls these in this order)
+// the new parts of the carried columns until the switch; what has not been handed to its column is freed on every exit
+struct CarriedColumns {
+    std::vector<szg_column *> cols;
+    std::vector<std::vector<szg_column::Part>> parts;  // [column][shard]
+    CarriedColumns() = default;
+    CarriedColumns(const CarriedColumns &) = delete;
+    CarriedColumns &operator=(const CarriedColumns &) = delete;
+    ~CarriedColumns();
+};
+// every entry is a valid, complete column of ix; *out takes each once
+int column_carry_check(szg_index *ix, szg_column *const *columns, int n_columns, std::vector<szg_column *> *out);
+// new row first[d] + i of shard d (counts[d] rows) = old row src[first[d] + i] (index-level): every allocation, launch
+// and check; the columns and the handle are untouched.  d_src: the whole list where the rows' move left it resident on
+// the device of a handle of one shard (it is not uploaded again), else null
+int column_carry_build(szg_index *ix, const std::vector<uint64_t> &src, const uint64_t *d_src, const std::vector<uint64_t> &counts,
+                       const std::vector<uint64_t> &first, const std::vector<szg_column *> &cols, CarriedColumns *out);
+// the old parts are freed, the new ones handed over, the columns valid at `epoch` with `rows` rows: nothing here fails
+void column_carry_switch(CarriedColumns *cc, uint64_t rows, uint64_t epoch);
 
 // One link of the shard's scan chain: under chain_mu, launch(st) puts the sweeps onto the shard's scan stream behind the
 // batch's uploads (ev_up, recorded on the work stream by the caller), and `after` goes on once they are done.  With

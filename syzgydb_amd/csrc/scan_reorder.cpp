@@ -1,13 +1,14 @@
 // scan_reorder.cpp -- compaction and reorder of the resident rows on the device (szg_index_compact,
-// szg_index_reorder).
+// szg_index_reorder, and their _carry forms that take columns along).
 //
 // New row i = old row list[i].  The list is checked on the host (reorder_plan.h) before anything moves; the rows then
 // go OUT OF PLACE into allocations sized for the new row count -- one gather launch for a handle of one shard; for a
 // handle of several, per destination shard in windows of at most 64 MiB: every source shard gathers its rows of the
 // window into a linear stage, the stages are copied side by side into the destination device's stage, and one launch
 // of the same kernel places the window into the resident layout by a list of stage rows.  The masks the caller wants
-// carried get their new words on the device as well.  Only when all of that has succeeded are the old allocations freed and the
-// shards, the live bits and the carried masks switched over: an error before that point leaves the handle as it was.
+// carried get their new words on the device as well, and the columns their new parts (scan_column_carry.cpp).  Only when
+// all of that has succeeded are the old allocations freed and the shards, the live bits, the carried masks and the
+// carried columns switched over: an error before that point leaves the handle, its masks and ALL its columns as they were.
 // Afterwards the handle looks as after szg_index_load of the same rows in the same order.
 #include "scan_internal.h"
 
@@ -124,7 +125,7 @@ int move_window(szg_index *ix, size_t d, const NewShard &to, uint64_t w0, const 
 
 // the body of both entry points: src = the checked list (index-level old rows), counts = the new rows per shard
 int reorder_checked(szg_index *ix, const std::vector<uint64_t> &src, const std::vector<uint64_t> &counts,
-                    const std::vector<szg_mask *> &carry)
+                    const std::vector<szg_mask *> &carry, const std::vector<szg_column *> &columns)
 {
     const size_t S = ix->shards.size();
     const uint64_t n = src.size(), old_rows = szg_index_rows(ix);
@@ -220,6 +221,9 @@ int reorder_checked(szg_index *ix, const std::vector<uint64_t> &src, const std::
         }
         HIPCHK(hipStreamSynchronize(nullptr));  // (before `list` and `old_all` go)
     }
+    // ---- the carried columns: new row i reads what old row src[i] read
+    CarriedColumns cols;
+    if (int rc = column_carry_build(ix, src, S == 1 ? d_lists[0].data() : nullptr, counts, first, columns, &cols)) return rc;
     for (const NewShard &t : fresh.v) {
         HIPCHK(hipSetDevice(t.device));
         HIPCHK(hipDeviceSynchronize());
@@ -247,7 +251,7 @@ int reorder_checked(szg_index *ix, const std::vector<uint64_t> &src, const std::
     }
     ix->gen++;
     const uint64_t epoch = ++ix->mask_epoch;
-    ix->col_epoch++;  // (columns are not carried: the host re-creates them)
+    column_carry_switch(&cols, n, ++ix->col_epoch);  // (every other column is stale from here on)
     if (ix->sketch) {
         // the sketch index only ever grows its shards: it goes, with what it counted kept, and the next search that
         // wants a sketch builds one sized for the new rows -- so a compaction returns the sketch's memory as well
@@ -287,12 +291,15 @@ int reorder_checked(szg_index *ix, const std::vector<uint64_t> &src, const std::
 
 extern "C" {
 
-int szg_index_reorder(szg_index *ix, const uint64_t *src_rows, uint64_t n_rows, szg_mask *const *carry, int n_carry)
+int szg_index_reorder_carry(szg_index *ix, const uint64_t *src_rows, uint64_t n_rows, szg_mask *const *carry, int n_carry,
+                            szg_column *const *columns, int n_columns)
 {
     SZG_TRY
     if (!ix || (!src_rows && n_rows)) return fail(SZG_E_INVALID, "null argument");
     std::vector<szg_mask *> masks;
+    std::vector<szg_column *> cols;
     int rc = check_carry(ix, carry, n_carry, &masks);
+    if (rc == SZG_OK) rc = column_carry_check(ix, columns, n_columns, &cols);
     if (rc) return rc;
     std::vector<uint64_t> live, local, counts;
     live_words_of(ix, &live);
@@ -300,16 +307,24 @@ int szg_index_reorder(szg_index *ix, const uint64_t *src_rows, uint64_t n_rows, 
     rc = reorder_plan(szg_index_rows(ix), live.data(), ix->row_base, src_rows, n_rows, ix->shards.size(), &local, &counts,
                       &what);
     if (rc) return fail(rc, what);
-    return reorder_checked(ix, local, counts, masks);
+    return reorder_checked(ix, local, counts, masks, cols);
     SZG_CATCH
 }
 
-int szg_index_compact(szg_index *ix, uint64_t *out_new_of_old, uint64_t *out_rows, szg_mask *const *carry, int n_carry)
+int szg_index_reorder(szg_index *ix, const uint64_t *src_rows, uint64_t n_rows, szg_mask *const *carry, int n_carry)
+{
+    return szg_index_reorder_carry(ix, src_rows, n_rows, carry, n_carry, nullptr, 0);
+}
+
+int szg_index_compact_carry(szg_index *ix, uint64_t *out_new_of_old, uint64_t *out_rows, szg_mask *const *carry, int n_carry,
+                            szg_column *const *columns, int n_columns)
 {
     SZG_TRY
     if (!ix) return fail(SZG_E_INVALID, "null argument");
     std::vector<szg_mask *> masks;
+    std::vector<szg_column *> cols;
     int rc = check_carry(ix, carry, n_carry, &masks);
+    if (rc == SZG_OK) rc = column_carry_check(ix, columns, n_columns, &cols);
     if (rc) return rc;
     const uint64_t old_rows = szg_index_rows(ix);
     std::vector<uint64_t> live_list;
@@ -320,7 +335,7 @@ int szg_index_compact(szg_index *ix, uint64_t *out_new_of_old, uint64_t *out_row
     if (live_list.size() != old_rows) {  // (no tombstones: nothing moves, no mask becomes stale)
         std::vector<uint64_t> counts;
         split_rows(ix, live_list.size(), &counts);
-        rc = reorder_checked(ix, live_list, counts, masks);
+        rc = reorder_checked(ix, live_list, counts, masks, cols);
         if (rc) return rc;
     }
     if (out_new_of_old) {
@@ -330,6 +345,11 @@ int szg_index_compact(szg_index *ix, uint64_t *out_new_of_old, uint64_t *out_row
     if (out_rows) *out_rows = live_list.size();
     return SZG_OK;
     SZG_CATCH
+}
+
+int szg_index_compact(szg_index *ix, uint64_t *out_new_of_old, uint64_t *out_rows, szg_mask *const *carry, int n_carry)
+{
+    return szg_index_compact_carry(ix, out_new_of_old, out_rows, carry, n_carry, nullptr, 0);
 }
 
 int szg_debug_reorder_plan(uint64_t n_rows, const uint64_t *live_words, const uint64_t *src_rows, uint64_t n, int n_shards,

@@ -10,7 +10,8 @@ import weakref
 import numpy as np
 
 from . import _lib
-from ._lib import SZG_COSINE, SZG_EUCLIDEAN, SzgError, SzgMaskStats, SzgScanPlan, SzgStats, check  # noqa: F401
+from ._lib import (SZG_COSINE, SZG_EUCLIDEAN, SzgColumnInfo, SzgError, SzgMaskStats, SzgScanPlan, SzgStats,  # noqa: F401
+                   check)
 from .where import _bytes
 
 
@@ -135,8 +136,9 @@ class ScanColumn:
     float64 values (kind F64), uint32 codes of a dictionary the caller owns (kind U32), or the strings themselves as
     bytes (kind STR, a text column).  Made by ScanIndex.column / text_column; where / isin / codes / startswith /
     endswith / contains / present compare it against constants ON THE DEVICE and return a ScanMask.  Index appends
-    leave it short until append() catches up; a load, synth, reorder or a compaction that moves rows makes it stale
-    (every call but rows / read / close then raises SzgError, SZG_E_INVALID)."""
+    leave it short until append() catches up; a load, a synth, and a reorder or a compaction that moves rows and is not
+    given the column in carry= make it stale (every call but rows / read / info / close then raises SzgError,
+    SZG_E_INVALID)."""
 
     def __init__(self, index, handle, kind):
         self._index = index
@@ -210,6 +212,13 @@ class ScanColumn:
     @property
     def rows(self):
         return int(self._L.szg_column_rows(self._live()))
+
+    def info(self):
+        """szg_column_get_info as a dict: kind, rows, device_bytes, and -- text columns -- heap_used and heap_capacity
+        summed over the parts.  Works on a stale column."""
+        out = SzgColumnInfo()
+        check(self._L.szg_column_get_info(self._live(), ctypes.byref(out)), "szg_column_get_info")
+        return {name: int(getattr(out, name)) for name, _ in SzgColumnInfo._fields_}
 
     def read(self):
         """(values, present bool[rows]) of the whole column; a text column's values are a list of bytes."""
@@ -419,36 +428,53 @@ class ScanIndex:
 
     # -- compaction / reorder on the device ---------------------------------------
     def _carry_arg(self, carry):
-        if isinstance(carry, ScanMask):
+        """carry -> (the masks, their array, the columns, their array); the arrays are None where there is nothing."""
+        if isinstance(carry, (ScanMask, ScanColumn)):
             carry = [carry]
         carry = list(carry)
-        arr = (ctypes.c_void_p * len(carry))(*[m._live() for m in carry]) if carry else None
-        return carry, arr
-
-    def _carried(self, carry):
-        words = (self.rows + 63) // 64
         for m in carry:
+            if not isinstance(m, (ScanMask, ScanColumn)):
+                raise TypeError("carry holds ScanMasks and ScanColumns")
+        masks = [m for m in carry if isinstance(m, ScanMask)]
+        columns = [c for c in carry if isinstance(c, ScanColumn)]
+        marr = (ctypes.c_void_p * len(masks))(*[m._live() for m in masks]) if masks else None
+        carr = (ctypes.c_void_p * len(columns))(*[c._live() for c in columns]) if columns else None
+        return masks, marr, columns, carr
+
+    def _carried(self, masks):
+        words = (self.rows + 63) // 64
+        for m in masks:
             m._words = words
 
     def reorder(self, src_rows, carry=()):
         """New row i = old row src_rows[i]; rows not listed are dropped.  The rows move on the device.  Every listed
-        row must be in range, live and listed once.  carry: ScanMasks of this index that are rewritten for the new
-        numbering and stay valid; every other mask becomes stale."""
+        row must be in range, live and listed once.  carry: ScanMasks and ScanColumns of this index, in any mix.  The
+        masks are rewritten for the new numbering and stay valid; the columns follow their rows on the card -- new row
+        i reads what old row src_rows[i] read, a text column's heap is repacked -- and stay valid.  Every other mask
+        and column becomes stale."""
         r = np.ascontiguousarray(src_rows, dtype=np.uint64).reshape(-1)
-        carry, arr = self._carry_arg(carry)
-        check(self._L.szg_index_reorder(self._h, _u64(r) if r.size else None, r.size, arr, len(carry)),
-              "szg_index_reorder")
-        self._carried(carry)
+        masks, marr, columns, carr = self._carry_arg(carry)
+        if columns:
+            check(self._L.szg_index_reorder_carry(self._h, _u64(r) if r.size else None, r.size, marr, len(masks), carr,
+                                                  len(columns)), "szg_index_reorder_carry")
+        else:
+            check(self._L.szg_index_reorder(self._h, _u64(r) if r.size else None, r.size, marr, len(masks)),
+                  "szg_index_reorder")
+        self._carried(masks)
 
     def compact(self, carry=()):
         """Drop the tombstoned rows on the device, keeping the order of the live ones.  Returns new_of_old,
         uint64[rows before]: the new number of each old row, 2**64 - 1 for a dropped one.  carry: as reorder's.
-        Without tombstones nothing moves and no mask becomes stale."""
+        Without tombstones nothing moves, and no mask or column becomes stale."""
         new_of_old = np.zeros(self.rows, dtype=np.uint64)
-        carry, arr = self._carry_arg(carry)
-        check(self._L.szg_index_compact(self._h, _u64(new_of_old) if new_of_old.size else None, None, arr, len(carry)),
-              "szg_index_compact")
-        self._carried(carry)
+        masks, marr, columns, carr = self._carry_arg(carry)
+        out = _u64(new_of_old) if new_of_old.size else None
+        if columns:
+            check(self._L.szg_index_compact_carry(self._h, out, None, marr, len(masks), carr, len(columns)),
+                  "szg_index_compact_carry")
+        else:
+            check(self._L.szg_index_compact(self._h, out, None, marr, len(masks)), "szg_index_compact")
+        self._carried(masks)
         return new_of_old
 
     def set_row_base(self, base):
