@@ -727,6 +727,18 @@ int szg_debug_option_check(const char *name, int64_t value);
 int szg_debug_reorder_plan(uint64_t n_rows, const uint64_t *live_words, const uint64_t *src_rows, uint64_t n,
                            int n_shards, uint64_t *out_counts);
 
+/*
+ * Test hooks, host only: the device memory this process's handles, columns and masks own.  Every device block of theirs
+ * -- rows, live bits, norms, staging, column parts, mask words, per-batch scratch -- comes from one function, which
+ * counts them (pinned host memory and the one-process-per-GPU exchange's staging are not counted):
+ *   szg_debug_device_memory       the blocks alive now and their bytes (either pointer may be NULL);
+ *   szg_debug_refuse_device_alloc the nth device allocation from now on (nth >= 1) is refused before the device is
+ *                                 asked: its call returns SZG_E_NOMEM with "(refused: test hook)" in the error text, and
+ *                                 the countdown disarms itself.  0 disarms.  Process-wide: not for concurrent callers.
+ */
+int szg_debug_device_memory(uint64_t *out_blocks, uint64_t *out_bytes);
+int szg_debug_refuse_device_alloc(int64_t nth);
+
 #ifdef __cplusplus
 }
 #endif

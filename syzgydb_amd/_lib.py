@@ -49,6 +49,8 @@ EXPORTS = [
     "szg_index_reorder_carry", "szg_index_compact_carry", "szg_column_get_info",
     # host-only test hook
     "szg_debug_scan_plan", "szg_debug_scan_group", "szg_debug_reorder_plan", "szg_debug_option_check",
+    # who owns device memory: the counters and the refusal countdown (added under ABI 4)
+    "szg_debug_device_memory", "szg_debug_refuse_device_alloc",
 ]
 SZG_MASK_AND, SZG_MASK_OR, SZG_MASK_ANDNOT, SZG_MASK_NOT = 0, 1, 2, 3
 SZG_COL_F64, SZG_COL_U32, SZG_COL_STR = 0, 1, 2
@@ -333,6 +335,11 @@ def load():
     if hasattr(L, "szg_debug_option_check"):
         L.szg_debug_option_check.restype = ctypes.c_int
         L.szg_debug_option_check.argtypes = [ctypes.c_char_p, ctypes.c_int64]
+    if hasattr(L, "szg_debug_device_memory"):   # (as the masks: an older build for an A/B run does not count)
+        L.szg_debug_device_memory.restype = ctypes.c_int
+        L.szg_debug_device_memory.argtypes = [u64p, u64p]
+        L.szg_debug_refuse_device_alloc.restype = ctypes.c_int
+        L.szg_debug_refuse_device_alloc.argtypes = [ctypes.c_int64]
     L.szg_debug_f64_probe.restype = ctypes.c_int
     L.szg_debug_f64_probe.argtypes = [ctypes.c_int, f64p, f64p, f64p, ctypes.c_uint64]
     _lib = L

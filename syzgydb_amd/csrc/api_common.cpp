@@ -16,6 +16,14 @@ int fail(int code, const char *what, hipError_t e)
     return code;
 }
 
+// what the owning buffers (dev_mem.h) report: a refusal by the test hook and a failed hipMalloc of owned memory are out
+// of memory, everything else a device error
+int dev_mem_error(DevErr kind, const char *what, hipError_t e)
+{
+    if (kind != kDevRefused) return fail(kind == kDevNoMem ? SZG_E_NOMEM : SZG_E_DEVICE, what, e);
+    return fail(SZG_E_NOMEM, (std::string(what) + " (refused: test hook)").c_str());
+}
+
 SiteTimers g_sites;
 
 int64_t row_bytes_of(int bits, int dim)

@@ -87,12 +87,8 @@ inline uint64_t carry_heap_capacity(uint64_t used) { return str_heap_grow(0, use
 // Whether a destination part may take `more` bytes behind the `used` it has been given so far.
 inline bool carry_heap_takes(uint64_t used, uint64_t more) { return more <= kStrHeapLimit && str_heap_fits(used + more); }
 
-// The rows a part has room for after a carry of n_rows > 0 rows: part_reserve's rule for a part that starts empty.
-inline uint64_t carry_cap_rows(uint64_t n_rows)
-{
-    if (n_rows == 0) return 0;
-    return ((n_rows < 1024 ? 1024 : n_rows) + 127) & ~127ull;
-}
+// The rows a part has room for after a carry of n_rows rows: column_grow_rows from nothing (no rows, no allocation).
+inline uint64_t carry_cap_rows(uint64_t n_rows) { return n_rows ? column_grow_rows(0, n_rows) : 0; }
 
 // Handles of several shards stage what travels between devices in windows: at most stage_bytes of values (or
 // references), and at most stage_bytes of a group's bytes in whole pieces, at a time.  kCarryStageBytes unless the

@@ -111,6 +111,13 @@ inline uint64_t str_heap_grow(uint64_t cap, uint64_t used)
     return std::min(want, kStrHeapLimit);
 }
 
+// the rows to allocate when a part with room for `cap_rows` rows must hold `need` > cap_rows: at least twice the old
+// capacity and at least 1024, a multiple of 128
+inline uint64_t column_grow_rows(uint64_t cap_rows, uint64_t need)
+{
+    return (std::max<uint64_t>(std::max<uint64_t>(need, 2 * cap_rows), 1024) + 127) & ~127ull;
+}
+
 // offsets[0 .. n_rows]: starts at 0 and never decreases
 inline bool str_offsets_valid(const uint64_t *offsets, uint64_t n_rows)
 {

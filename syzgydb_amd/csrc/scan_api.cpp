@@ -435,18 +435,31 @@ int szg_debug_f64_probe(int op, const double *a, const double *b, double *out, u
     int count = 0;
     if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
         return fail(SZG_E_NODEVICE, "hipGetDeviceCount");
-    double *da = nullptr, *db = nullptr, *dout = nullptr;
-    HIPCHK(hipMalloc((void **)&da, n * sizeof(double)));
-    HIPCHK(hipMalloc((void **)&db, n * sizeof(double)));
-    HIPCHK(hipMalloc((void **)&dout, n * sizeof(double)));
+    DevBuf<double> da, db, dout;
+    int rc = da.ensure((size_t)n);
+    if (rc == SZG_OK) rc = db.ensure((size_t)n);
+    if (rc == SZG_OK) rc = dout.ensure((size_t)n);
+    if (rc) return rc;
     HIPCHK(hipMemcpy(da, a, n * sizeof(double), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(db, b ? b : a, n * sizeof(double), hipMemcpyHostToDevice));
-    hipError_t e = szg::launch_f64_probe(op, da, db, dout, n, nullptr);
-    if (e == hipSuccess) e = hipMemcpy(out, dout, n * sizeof(double), hipMemcpyDeviceToHost);
-    (void)hipFree(da);
-    (void)hipFree(db);
-    (void)hipFree(dout);
-    if (e != hipSuccess) return fail(SZG_E_DEVICE, "f64 probe", e);
+    HIPCHK(szg::launch_f64_probe(op, da, db, dout, n, nullptr));
+    HIPCHK(hipMemcpy(out, dout, n * sizeof(double), hipMemcpyDeviceToHost));
+    return SZG_OK;
+}
+
+// test hooks, host only (dev_mem.h): the device blocks the library's owning buffers hold in this process and their bytes;
+// and the countdown that refuses the nth device allocation from now on (0 disarms)
+int szg_debug_device_memory(uint64_t *out_blocks, uint64_t *out_bytes)
+{
+    if (out_blocks) *out_blocks = dev_alloc_state().blocks.load();
+    if (out_bytes) *out_bytes = dev_alloc_state().bytes.load();
+    return SZG_OK;
+}
+
+int szg_debug_refuse_device_alloc(int64_t nth)
+{
+    if (nth < 0) return fail(SZG_E_INVALID, "nth is 0 (disarm) or the allocation to refuse, counted from 1");
+    dev_alloc_state().refuse_in.store(nth);
     return SZG_OK;
 }
 

@@ -16,51 +16,70 @@ using namespace szgi;
 
 int szgi::stale_column() { return fail(SZG_E_INVALID, "stale column: the handle's rows were loaded or renumbered after the column was made"); }
 
-namespace {
-
-void column_free(szg_column *c)
-{
-    if (!c) return;
-    for (szg_column::Part &p : c->parts) {
-        if (!p.values && !p.present) continue;
-        (void)hipSetDevice(p.device);
-        (void)hipFree(p.values);
-        (void)hipFree(p.present);
-        (void)hipFree(p.heap);
-    }
-    delete c;
-}
-
-// room for `need` rows in part p: a new allocation of at least twice the old capacity, the old contents carried over
-int part_reserve(szg_column *c, szg_column::Part &p, uint64_t need)
+// room for `need` rows in part p: a new allocation by column_grow_rows, the old contents carried over
+int szgi::part_reserve(const szg_column *c, szg_column::Part &p, uint64_t need)
 {
     if (need <= p.cap_rows) return SZG_OK;
-    uint64_t cap = std::max<uint64_t>(std::max<uint64_t>(need, 2 * p.cap_rows), 1024);
-    cap = (cap + 127) & ~127ull;
-    HIPCHK(hipSetDevice(p.device));
-    void *values = nullptr;
-    uint64_t *present = nullptr;
-    if (hipMalloc(&values, cap * c->elem()) != hipSuccess || hipMalloc((void **)&present, cap / 8) != hipSuccess) {
-        (void)hipGetLastError();
-        (void)hipFree(values);
-        return fail(SZG_E_NOMEM, "out of device memory (column)");
-    }
+    const uint64_t cap = column_grow_rows(p.cap_rows, need);
+    DevMem<uint8_t> values(p.device);
+    DevMem<uint64_t> present(p.device);
+    if (int rc = values.alloc_exact(cap * c->elem(), "out of device memory (column)")) return rc;
+    if (int rc = present.alloc_exact(cap / 64, "out of device memory (column)")) return rc;
     hipError_t e = hipMemset(present, 0, cap / 8);
     if (e == hipSuccess && p.n_rows) e = hipMemcpy(values, p.values, p.n_rows * c->elem(), hipMemcpyDeviceToDevice);
     if (e == hipSuccess && p.n_rows)
         e = hipMemcpy(present, p.present_host.data(), index_words(p.n_rows) * sizeof(uint64_t), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        (void)hipFree(values);
-        (void)hipFree(present);
-        return fail(SZG_E_DEVICE, "column growth", e);
-    }
+    if (e != hipSuccess) return fail(SZG_E_DEVICE, "column growth", e);
     p.present_host.resize((size_t)(cap / 64), 0ull);
-    (void)hipFree(p.values);
-    (void)hipFree(p.present);
-    p.values = values;
-    p.present = present;
+    p.values = std::move(values);
+    p.present = std::move(present);
     p.cap_rows = cap;
     return SZG_OK;
+}
+
+// room for `used` bytes in part p's heap (str_heap_fits(used)): as part_reserve, the new bytes zero -- unless the
+// caller writes every byte of the new heap itself (zeroed == false)
+int szgi::heap_reserve(szg_column::Part &p, uint64_t used, bool zeroed)
+{
+    if (p.heap_cap && str_heap_capacity(used) <= p.heap_cap) return SZG_OK;
+    const uint64_t cap = str_heap_grow(p.heap_cap, used);
+    DevMem<uint8_t> heap(p.device);
+    if (int rc = heap.alloc_exact(cap, "out of device memory (column heap)")) return rc;
+    hipError_t e = zeroed ? hipMemset(heap, 0, cap) : hipSuccess;
+    if (e == hipSuccess && p.heap_used) e = hipMemcpy(heap, p.heap, p.heap_used, hipMemcpyDeviceToDevice);
+    if (e != hipSuccess) return fail(SZG_E_DEVICE, "column heap growth", e);
+    p.heap = std::move(heap);
+    p.heap_cap = cap;
+    return SZG_OK;
+}
+
+// a complete column of this handle: made at the handle's column epoch, every part as long as its shard
+int szgi::column_complete_check(const szg_index *ix, const szg_column *c)
+{
+    if (c->owner != ix) return fail(SZG_E_INVALID, "column belongs to another handle");
+    if (c->epoch != ix->col_epoch.load() || c->parts.size() != ix->shards.size()) return stale_column();
+    if (c->rows != szg_index_rows(ix))
+        return fail(SZG_E_INVALID, "short column: rows were appended to the handle but not to the column");
+    for (size_t s = 0; s < c->parts.size(); s++)
+        if (c->parts[s].n_rows != ix->shards[s]->n_rows || (c->parts[s].n_rows && c->parts[s].first != ix->shards[s]->first))
+            return stale_column();
+    return SZG_OK;
+}
+
+namespace {
+
+// an empty column of `kind` shaped after the handle's shards
+szg_column *column_new(szg_index *ix, int kind)
+{
+    szg_column *c = new szg_column();
+    c->owner = ix;
+    c->kind = kind;
+    c->epoch = ix->col_epoch.load();
+    for (const Shard *sh : ix->shards) {
+        c->parts.emplace_back(sh->device);
+        c->parts.back().first = sh->first;
+    }
+    return c;
 }
 
 // the checks every call but rows / read / destroy makes first
@@ -68,29 +87,6 @@ int column_check(const szg_column *c)
 {
     if (c->epoch != c->owner->col_epoch.load()) return stale_column();
     if (c->parts.size() != c->owner->shards.size()) return stale_column();
-    return SZG_OK;
-}
-
-// room for `used` bytes in part p's heap (str_heap_fits(used)): as part_reserve, the new bytes zero
-int heap_reserve(szg_column::Part &p, uint64_t used)
-{
-    if (p.heap_cap && str_heap_capacity(used) <= p.heap_cap) return SZG_OK;
-    const uint64_t cap = str_heap_grow(p.heap_cap, used);
-    HIPCHK(hipSetDevice(p.device));
-    uint8_t *heap = nullptr;
-    if (hipMalloc((void **)&heap, cap) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(SZG_E_NOMEM, "out of device memory (column heap)");
-    }
-    hipError_t e = hipMemset(heap, 0, cap);
-    if (e == hipSuccess && p.heap_used) e = hipMemcpy(heap, p.heap, p.heap_used, hipMemcpyDeviceToDevice);
-    if (e != hipSuccess) {
-        (void)hipFree(heap);
-        return fail(SZG_E_DEVICE, "column heap growth", e);
-    }
-    (void)hipFree(p.heap);
-    p.heap = heap;
-    p.heap_cap = cap;
     return SZG_OK;
 }
 
@@ -136,7 +132,7 @@ int column_extend(szg_column *c, const void *values, const uint64_t *present_bit
         szg_column::Part &p = c->parts[s];
         HIPCHK(hipSetDevice(p.device));
         if (p.n_rows == 0) p.first = ix->shards[s]->first;
-        HIPCHK(hipMemcpy((uint8_t *)p.values + p.n_rows * c->elem(), (const uint8_t *)values + done * c->elem(),
+        HIPCHK(hipMemcpy(p.values + p.n_rows * c->elem(), (const uint8_t *)values + done * c->elem(),
                          take[s] * c->elem(), hipMemcpyHostToDevice));
         copy_bits(p.present_host.data(), p.n_rows, present_bits, done, take[s]);
         const size_t w0 = (size_t)(p.n_rows / 64), w1 = index_words(p.n_rows + take[s]);
@@ -187,7 +183,7 @@ int column_extend_str(szg_column *c, const uint8_t *bytes, const uint64_t *offse
         }
         if (nbytes[s])
             HIPCHK(hipMemcpy(p.heap + p.heap_used, bytes + offsets[done], nbytes[s], hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy((uint64_t *)p.values + p.n_rows, refs.data(), take[s] * sizeof(uint64_t), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(p.values_as<uint64_t>() + p.n_rows, refs.data(), take[s] * sizeof(uint64_t), hipMemcpyHostToDevice));
         copy_bits(p.present_host.data(), p.n_rows, present_bits, done, take[s]);
         const size_t w0 = (size_t)(p.n_rows / 64), w1 = index_words(p.n_rows + take[s]);
         HIPCHK(hipMemcpy(p.present + w0, p.present_host.data() + w0, (w1 - w0) * sizeof(uint64_t), hipMemcpyHostToDevice));
@@ -229,10 +225,7 @@ int mask_where(const szg_column *c, int kind, const szg_mask *base, szg_mask **o
     int rc = column_check(c);
     if (rc) return rc;
     if (kind >= 0 && c->kind != kind) return kind_mismatch();
-    if (c->rows != szg_index_rows(ix)) return fail(SZG_E_INVALID, "short column: rows were appended to the handle but not to the column");
-    for (size_t s = 0; s < c->parts.size(); s++)
-        if (c->parts[s].n_rows != ix->shards[s]->n_rows || (c->parts[s].n_rows && c->parts[s].first != ix->shards[s]->first))
-            return stale_column();
+    if ((rc = column_complete_check(ix, c))) return rc;
     if (base && (rc = mask_check(ix, base))) return rc;
     MaskGuard guard;
     rc = mask_alloc(ix, &guard.m);
@@ -281,18 +274,10 @@ int szg_column_create(szg_index *ix, int kind, const void *values, const uint64_
     if (!ix || !out || (!values && n_rows)) return fail(SZG_E_INVALID, "null argument");
     if (kind != SZG_COL_F64 && kind != SZG_COL_U32) return fail(SZG_E_INVALID, "unknown column kind");
     if (n_rows > szg_index_rows(ix)) return fail(SZG_E_RANGE, "column longer than the handle's rows");
-    szg_column *c = new szg_column();
-    c->owner = ix;
-    c->kind = kind;
-    c->epoch = ix->col_epoch.load();
-    c->parts.resize(ix->shards.size());
-    for (size_t s = 0; s < ix->shards.size(); s++) {
-        c->parts[s].device = ix->shards[s]->device;
-        c->parts[s].first = ix->shards[s]->first;
-    }
+    szg_column *c = column_new(ix, kind);
     const int rc = column_extend(c, values, present_bits, n_rows);
     if (rc) {
-        column_free(c);
+        delete c;
         return rc;
     }
     *out = c;
@@ -323,7 +308,7 @@ int szg_column_set(szg_column *c, uint64_t row, const void *value)
     if (!p) return stale_column();
     const uint64_t l = row - p->first;
     HIPCHK(hipSetDevice(p->device));
-    if (value) HIPCHK(hipMemcpy((uint8_t *)p->values + l * c->elem(), value, c->elem(), hipMemcpyHostToDevice));
+    if (value) HIPCHK(hipMemcpy(p->values + l * c->elem(), value, c->elem(), hipMemcpyHostToDevice));
     return set_present(*p, l, value != nullptr);
     SZG_CATCH
 }
@@ -362,7 +347,7 @@ int szg_column_read(const szg_column *c, uint64_t first_row, uint64_t n_rows, vo
         if (out_values) {
             HIPCHK(hipSetDevice(p.device));
             HIPCHK(hipMemcpy((uint8_t *)out_values + (lo - first_row) * c->elem(),
-                             (const uint8_t *)p.values + (lo - p.first) * c->elem(), (hi - lo) * c->elem(),
+                             p.values + (lo - p.first) * c->elem(), (hi - lo) * c->elem(),
                              hipMemcpyDeviceToHost));
         }
         if (out_present_bits) copy_bits(out_present_bits, lo - first_row, p.present_host.data(), lo - p.first, hi - lo);
@@ -379,18 +364,10 @@ int szg_column_create_str(szg_index *ix, const uint8_t *bytes, const uint64_t *o
     if (n_rows && !str_offsets_valid(offsets, n_rows)) return fail(SZG_E_INVALID, "offsets start at 0 and never decrease");
     if (!ix || (!bytes && n_rows && offsets[n_rows])) return fail(SZG_E_INVALID, "null argument");
     if (n_rows > szg_index_rows(ix)) return fail(SZG_E_RANGE, "column longer than the handle's rows");
-    szg_column *c = new szg_column();
-    c->owner = ix;
-    c->kind = SZG_COL_STR;
-    c->epoch = ix->col_epoch.load();
-    c->parts.resize(ix->shards.size());
-    for (size_t s = 0; s < ix->shards.size(); s++) {
-        c->parts[s].device = ix->shards[s]->device;
-        c->parts[s].first = ix->shards[s]->first;
-    }
+    szg_column *c = column_new(ix, SZG_COL_STR);
     const int rc = column_extend_str(c, bytes, offsets, present_bits, n_rows);
     if (rc) {
-        column_free(c);
+        delete c;
         return rc;
     }
     *out = c;
@@ -424,7 +401,7 @@ int szg_column_set_str(szg_column *c, uint64_t row, const uint8_t *value, uint64
     const uint64_t l = row - p->first;
     HIPCHK(hipSetDevice(p->device));
     if (!value) return set_present(*p, l, false);
-    uint64_t *slot = (uint64_t *)p->values + l, ref = 0;
+    uint64_t *slot = p->values_as<uint64_t>() + l, ref = 0;
     HIPCHK(hipMemcpy(&ref, slot, sizeof(ref), hipMemcpyDeviceToHost));
     if (len <= (ref >> 32)) {   // in place
         if (len) HIPCHK(hipMemcpy(p->heap + (uint32_t)ref, value, len, hipMemcpyHostToDevice));
@@ -459,7 +436,7 @@ int szg_column_read_str(const szg_column *c, uint64_t first_row, uint64_t n_rows
         const uint64_t lo = std::max(first_row, p.first), hi = std::min(first_row + n_rows, p.first + p.n_rows);
         if (lo >= hi) continue;
         HIPCHK(hipSetDevice(p.device));
-        HIPCHK(hipMemcpy(refs.data() + (lo - first_row), (const uint64_t *)p.values + (lo - p.first),
+        HIPCHK(hipMemcpy(refs.data() + (lo - first_row), p.values_as<const uint64_t>() + (lo - p.first),
                          (hi - lo) * sizeof(uint64_t), hipMemcpyDeviceToHost));
         if (out_present_bits) copy_bits(out_present_bits, lo - first_row, p.present_host.data(), lo - p.first, hi - lo);
     }
@@ -489,14 +466,14 @@ int szg_column_read_str(const szg_column *c, uint64_t first_row, uint64_t n_rows
     SZG_CATCH
 }
 
-void szg_column_destroy(szg_column *c) { column_free(c); }
+void szg_column_destroy(szg_column *c) { delete c; }  // (its parts free themselves, each on its own device)
 
 int szg_mask_where_f64(const szg_column *c, int op, double value, const szg_mask *base, szg_mask **out)
 {
     SZG_TRY
     if (op < SZG_CMP_EQ || op > SZG_CMP_GE) return fail(SZG_E_INVALID, "unknown comparison operator");
     return mask_where(c, SZG_COL_F64, base, out, [&](size_t s, const szg::ColumnWhere &w) -> int {
-        HIPCHK(szg::launch_column_cmp_f64(static_cast<const double *>(c->parts[s].values), op, value, w, nullptr));
+        HIPCHK(szg::launch_column_cmp_f64(c->parts[s].values_as<const double>(), op, value, w, nullptr));
         return SZG_OK;
     });
     SZG_CATCH
@@ -515,7 +492,7 @@ int szg_mask_where_in_f64(const szg_column *c, const double *values, uint32_t n_
     return mask_where(c, SZG_COL_F64, base, out, [&](size_t s, const szg::ColumnWhere &w) -> int {
         DevBuf<double> list;   // (freed after the launch: mask_where's copies wait for the kernel)
         if (int rc = upload_small(&list, sorted.data(), sorted.size())) return rc;
-        HIPCHK(szg::launch_column_in_f64(static_cast<const double *>(c->parts[s].values), list, (uint32_t)sorted.size(), w,
+        HIPCHK(szg::launch_column_in_f64(c->parts[s].values_as<const double>(), list, (uint32_t)sorted.size(), w,
                                          nullptr));
         HIPCHK(hipStreamSynchronize(nullptr));
         return SZG_OK;
@@ -531,7 +508,7 @@ int szg_mask_where_u32(const szg_column *c, const uint64_t *code_bits, uint32_t 
     return mask_where(c, SZG_COL_U32, base, out, [&](size_t s, const szg::ColumnWhere &w) -> int {
         DevBuf<uint64_t> bits;
         if (int rc = upload_small(&bits, code_bits, index_words(n_codes))) return rc;
-        HIPCHK(szg::launch_column_codes_u32(static_cast<const uint32_t *>(c->parts[s].values), bits, n_codes, w, nullptr));
+        HIPCHK(szg::launch_column_codes_u32(c->parts[s].values_as<const uint32_t>(), bits, n_codes, w, nullptr));
         HIPCHK(hipStreamSynchronize(nullptr));
         return SZG_OK;
     });
@@ -550,7 +527,7 @@ int szg_mask_where_str(const szg_column *c, int op, const uint8_t *constant, uin
     return mask_where(c, SZG_COL_STR, base, out, [&](size_t s, const szg::ColumnWhere &w) -> int {
         DevBuf<uint32_t> k;   // (freed after the launch: mask_where's copies wait for the kernel)
         if (int rc = upload_small(&k, dwords.data(), dwords.size())) return rc;
-        HIPCHK(szg::launch_column_str(static_cast<const uint64_t *>(c->parts[s].values), c->parts[s].heap, op, k, len, w,
+        HIPCHK(szg::launch_column_str(c->parts[s].values_as<const uint64_t>(), c->parts[s].heap, op, k, len, w,
                                       nullptr));
         HIPCHK(hipStreamSynchronize(nullptr));
         return SZG_OK;

@@ -3,7 +3,7 @@
 //
 // New row i of a carried column = what old row list[i] held: the value bit for bit, the present bit, and -- a text column
 // -- the row's bytes, present or not.  Like the rows, every part is built OUT OF PLACE into allocations a freshly created
-// column of the new rows would have (carry_cap_rows, carry_heap_capacity); the old parts stay untouched until
+// column of the new rows would have (part_reserve / heap_reserve on parts that start empty); the old parts stay untouched until
 // column_carry_switch, which cannot fail, so an error anywhere leaves every column as it was.
 //
 // A handle of one shard: one gather launch for the values; a text column's references are gathered, their lengths
@@ -24,59 +24,11 @@ namespace szgi {
 
 namespace {
 
-// a device buffer that is freed with its own device current
-template <typename T>
-struct OnDev {
-    int device = 0;
-    DevBuf<T> buf;
-    explicit OnDev(int device_ = 0) : device(device_) {}
-    OnDev(OnDev &&) = default;
-    ~OnDev()
-    {
-        if (!buf.data()) return;
-        (void)hipSetDevice(device);
-        (void)buf.reset();
-    }
-    int ensure(size_t n)
-    {
-        HIPCHK(hipSetDevice(device));
-        return buf.ensure(n);
-    }
-    T *data() const { return buf.data(); }
-};
-
 int heap_limit() { return fail(SZG_E_UNSUPPORTED, "a part's text heap stays below 4 GiB"); }
-
-// the values, present words and (text) heap of a part of n_rows > 0 rows, sized as a fresh column's; the heap comes later
-int part_alloc(const szg_column *c, szg_column::Part &p)
-{
-    p.cap_rows = carry_cap_rows(p.n_rows);
-    HIPCHK(hipSetDevice(p.device));
-    if (hipMalloc(&p.values, p.cap_rows * c->elem()) != hipSuccess || hipMalloc((void **)&p.present, p.cap_rows / 8) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(SZG_E_NOMEM, "out of device memory (column)");
-    }
-    p.present_host.assign((size_t)(p.cap_rows / 64), 0ull);
-    return SZG_OK;
-}
-
-int heap_alloc(szg_column::Part &p, uint64_t used, bool zeroed)
-{
-    p.heap_cap = carry_heap_capacity(used);
-    HIPCHK(hipSetDevice(p.device));
-    if (hipMalloc((void **)&p.heap, p.heap_cap) != hipSuccess) {
-        (void)hipGetLastError();
-        p.heap_cap = 0;
-        return fail(SZG_E_NOMEM, "out of device memory (column heap)");
-    }
-    if (zeroed) HIPCHK(hipMemset(p.heap, 0, p.heap_cap));
-    p.heap_used = used;
-    return SZG_OK;
-}
 
 // a text group on its source device: the references of the listed rows, their new starts, the bytes they hold in all
 struct TextGroup {
-    OnDev<uint64_t> refs, starts, sums;
+    DevMem<uint64_t> refs, starts, sums;
     uint64_t n = 0, total = 0;
     explicit TextGroup(int device) : refs(device), starts(device), sums(device) {}
 };
@@ -91,7 +43,7 @@ int text_group_scan(const szg_column::Part &old, const uint64_t *d_list, uint64_
     if (rc == SZG_OK) rc = g->starts.ensure((size_t)n);
     if (rc == SZG_OK) rc = g->sums.ensure((size_t)nb + 1);
     if (rc) return rc;
-    HIPCHK(szg::launch_carry_ref_starts(static_cast<const uint64_t *>(old.values), d_list, n, g->refs.data(), g->starts.data(),
+    HIPCHK(szg::launch_carry_ref_starts(old.values_as<const uint64_t>(), d_list, n, g->refs.data(), g->starts.data(),
                                         g->sums.data(), nullptr));
     HIPCHK(hipMemcpy(&g->total, g->sums.data() + nb, sizeof(uint64_t), hipMemcpyDeviceToHost));
     return SZG_OK;
@@ -110,10 +62,11 @@ int carry_part_single(const szg_column *c, const szg_column::Part &old, const ui
     int rc = text_group_scan(old, d_list, n, &g);
     if (rc) return rc;
     if (!carry_heap_takes(0, g.total)) return heap_limit();
-    rc = heap_alloc(np, g.total, false);   // (the mover writes every piece of the new heap, the zero ones too)
+    rc = heap_reserve(np, g.total, false);   // (the mover writes every piece of the new heap, the zero ones too)
     if (rc) return rc;
+    np.heap_used = g.total;
     HIPCHK(szg::launch_carry_move_bytes(old.heap, g.refs.data(), g.starts.data(), n, g.total, 0, np.heap_cap / 16, np.heap, nullptr));
-    HIPCHK(szg::launch_carry_new_refs(g.refs.data(), g.starts.data(), n, 0, nullptr, static_cast<uint64_t *>(np.values), nullptr));
+    HIPCHK(szg::launch_carry_new_refs(g.refs.data(), g.starts.data(), n, 0, nullptr, np.values_as<uint64_t>(), nullptr));
     HIPCHK(hipStreamSynchronize(nullptr));   // (before the group's buffers go)
     return SZG_OK;
 }
@@ -122,12 +75,12 @@ int carry_part_single(const szg_column *c, const szg_column::Part &old, const ui
 // (part-local, on the source's device) and where each goes (on the destination's)
 struct Groups {
     std::vector<std::vector<uint64_t>> sub, at;
-    std::vector<OnDev<uint64_t>> d_sub, d_at;
+    std::vector<DevMem<uint64_t>> d_sub, d_at;
 };
 
 // `n` elements of `elem` bytes, dense in `from` on device dev_s, to out[at[i]] on device dev_d, through the stages
 int place_window(const void *from, int dev_s, uint32_t elem, uint64_t n, const uint64_t *d_at, void *out, int dev_d,
-                 OnDev<uint64_t> *stage_d)
+                 DevMem<uint64_t> *stage_d)
 {
     HIPCHK(hipSetDevice(dev_s));
     HIPCHK(hipStreamSynchronize(nullptr));
@@ -145,12 +98,12 @@ int carry_part_grouped(const szg_column *c, const Groups &gr, uint64_t stage_byt
     const size_t S = c->parts.size();
     const uint32_t elem = (uint32_t)c->elem();
     const uint64_t window = carry_window_rows(stage_bytes, elem), pieces = carry_window_pieces(stage_bytes);
-    OnDev<uint64_t> stage_d(np.device);
+    DevMem<uint64_t> stage_d(np.device);
     if (c->kind != SZG_COL_STR) {
         for (size_t s = 0; s < S; s++) {
             const szg_column::Part &old = c->parts[s];
             const uint64_t cnt = gr.sub[s].size();
-            OnDev<uint64_t> stage_s(old.device);
+            DevMem<uint64_t> stage_s(old.device);
             uint64_t lo = 0, hi = 0;
             for (uint64_t w = 0; carry_window(cnt, window, w, &lo, &hi); w++) {
                 int rc = stage_s.ensure((size_t)(((hi - lo) * elem + 7) / 8));
@@ -173,13 +126,14 @@ int carry_part_grouped(const szg_column *c, const Groups &gr, uint64_t stage_byt
         if (!carry_heap_takes(used, groups[s].total)) return heap_limit();
         used += groups[s].total;
     }
-    int rc = heap_alloc(np, used, true);
+    int rc = heap_reserve(np, used);
     if (rc) return rc;
+    np.heap_used = used;
     uint64_t base = 0;   // where the group's bytes go in the new heap
     for (size_t s = 0; s < S; s++) {
         const szg_column::Part &old = c->parts[s];
         const TextGroup &g = groups[s];
-        OnDev<uint64_t> stage_s(old.device);
+        DevMem<uint64_t> stage_s(old.device);
         uint64_t lo = 0, hi = 0;
         for (uint64_t w = 0; carry_window((g.total + 15) / 16, pieces, w, &lo, &hi); w++) {   // the bytes
             rc = stage_s.ensure((size_t)(2 * (hi - lo)));
@@ -205,31 +159,13 @@ int carry_part_grouped(const szg_column *c, const Groups &gr, uint64_t stage_byt
 
 }  // namespace
 
-CarriedColumns::~CarriedColumns()
-{
-    for (std::vector<szg_column::Part> &ps : parts)
-        for (szg_column::Part &p : ps) {
-            if (!p.values && !p.present && !p.heap) continue;
-            (void)hipSetDevice(p.device);
-            (void)hipFree(p.values);
-            (void)hipFree(p.present);
-            (void)hipFree(p.heap);
-        }
-}
-
 int column_carry_check(szg_index *ix, szg_column *const *columns, int n_columns, std::vector<szg_column *> *out)
 {
     if (n_columns < 0 || (!columns && n_columns)) return fail(SZG_E_INVALID, "null argument");
     for (int i = 0; i < n_columns; i++) {
         const szg_column *c = columns[i];
         if (!c) return fail(SZG_E_INVALID, "null column in carry");
-        if (c->owner != ix) return fail(SZG_E_INVALID, "column belongs to another handle");
-        if (c->epoch != ix->col_epoch.load() || c->parts.size() != ix->shards.size()) return stale_column();
-        if (c->rows != szg_index_rows(ix))
-            return fail(SZG_E_INVALID, "short column: rows were appended to the handle but not to the column");
-        for (size_t s = 0; s < c->parts.size(); s++)
-            if (c->parts[s].n_rows != ix->shards[s]->n_rows || (c->parts[s].n_rows && c->parts[s].first != ix->shards[s]->first))
-                return stale_column();
+        if (int rc = column_complete_check(ix, c)) return rc;
         if (std::find(out->begin(), out->end(), columns[i]) == out->end()) out->push_back(columns[i]);
     }
     return SZG_OK;
@@ -242,15 +178,14 @@ int column_carry_build(szg_index *ix, const std::vector<uint64_t> &src, const ui
     const uint64_t old_rows = szg_index_rows(ix);
     const uint64_t stage_bytes = ix->carry_stage_bytes ? ix->carry_stage_bytes : kCarryStageBytes;
     out->cols = cols;
-    out->parts.assign(cols.size(), std::vector<szg_column::Part>(S));
+    out->parts.resize(cols.size());
     for (size_t k = 0; k < cols.size(); k++)
-        for (size_t d = 0; d < S; d++) {
+        for (size_t d = 0; d < S; d++) {   // what a fresh column of the new rows has: part_reserve on a part that starts empty
+            out->parts[k].emplace_back(ix->shards[d]->device);
             szg_column::Part &np = out->parts[k][d];
-            np.device = ix->shards[d]->device;
             np.first = first[d];
+            if (int rc = part_reserve(cols[k], np, counts[d])) return rc;
             np.n_rows = counts[d];
-            if (np.n_rows)
-                if (int rc = part_alloc(cols[k], np)) return rc;
         }
     std::vector<uint64_t> old_first(S), old_n(S);
     for (size_t s = 0; s < S; s++) old_first[s] = ix->shards[s]->first, old_n[s] = ix->shards[s]->n_rows;
@@ -259,7 +194,7 @@ int column_carry_build(szg_index *ix, const std::vector<uint64_t> &src, const ui
         if (m == 0) continue;
         const int dev = ix->shards[d]->device;
         const uint64_t *list = src.data() + first[d];
-        OnDev<uint64_t> own_list(dev), old_all(dev);
+        DevMem<uint64_t> own_list(dev), old_all(dev);
         const uint64_t *d_list = S == 1 ? d_src : nullptr;   // (one shard: first[0] == 0, the resident list is this part's)
         int rc = SZG_OK;
         if (!d_list) {
@@ -317,14 +252,7 @@ void column_carry_switch(CarriedColumns *cc, uint64_t rows, uint64_t epoch)
 {
     for (size_t k = 0; k < cc->cols.size(); k++) {
         szg_column *c = cc->cols[k];
-        for (szg_column::Part &p : c->parts) {   // the old allocations go on their own device
-            if (!p.values && !p.present && !p.heap) continue;
-            (void)hipSetDevice(p.device);
-            (void)hipFree(p.values);
-            (void)hipFree(p.present);
-            (void)hipFree(p.heap);
-        }
-        c->parts = std::move(cc->parts[k]);
+        c->parts = std::move(cc->parts[k]);   // (the old allocations go, each on its own device)
         c->rows = rows;
         c->epoch = epoch;
     }

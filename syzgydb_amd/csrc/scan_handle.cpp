@@ -68,16 +68,14 @@ void ctx_release(Shard *sh, Ctx *c)
     sh->cv.notify_one();
 }
 
-// the shard's staging buffer, at least `bytes` large (kept up to 64 MiB between calls)
+// the shard's staging buffer, at least `bytes` large (kept up to 64 MiB between calls); nothing in it is kept, so the
+// old block goes before the new one comes
 int shard_stage(Shard *sh, size_t bytes, uint8_t **out)
 {
     if (sh->stage_cap < bytes) {
-        if (sh->stage) (void)hipFree(sh->stage);
-        sh->stage = nullptr;
         sh->stage_cap = 0;
         const size_t want = std::max<size_t>(bytes, 4096);
-        hipError_t e = hipMalloc((void **)&sh->stage, want);
-        if (e != hipSuccess) return fail(SZG_E_NOMEM, "hipMalloc(staging)", e);
+        if (int rc = sh->stage.alloc_exact(want, "hipMalloc(staging)")) return rc;
         sh->stage_cap = want;
     }
     *out = sh->stage;
@@ -109,45 +107,51 @@ int upload_rows(szg_index *ix, Shard *sh, uint64_t dst_row, const uint8_t *rows,
     return SZG_OK;
 }
 
+// room for `rows_needed` rows in the holder (device current): the rows' block of at least one and a half times the old
+// capacity and the live words that go with it (new words zero), what the old blocks held carried over
+int rows_reserve(const szg::RowLayout &layout, ShardRows *h, uint64_t rows_needed)
+{
+    if (rows_needed > 0xFFFFFFF0ull) return fail(SZG_E_UNSUPPORTED, "more than 2^32 rows per shard");
+    if (rows_needed > h->cap_rows) {
+        uint64_t cap = std::max<uint64_t>(rows_needed, h->cap_rows + h->cap_rows / 2);
+        cap = (cap + 63) & ~63ull;
+        DevMem<uint8_t> nr(h->rows.device());
+        if (int rc = nr.alloc_exact(szg::layout_bytes(layout, cap) + 64, "hipMalloc(corpus)")) return rc;
+        if (h->rows && h->n_rows) {
+            const hipError_t e = hipMemcpy(nr, h->rows, szg::layout_bytes(layout, h->n_rows), hipMemcpyDeviceToDevice);
+            if (e != hipSuccess) return fail(SZG_E_DEVICE, "hipMemcpy(corpus)", e);
+        }
+        h->rows = std::move(nr);
+        h->cap_rows = cap;
+    }
+    const uint64_t words = (h->cap_rows + 63) / 64;
+    if (words > h->bits_cap) {
+        DevMem<uint64_t> nb(h->live_bits.device());
+        if (int rc = nb.alloc_exact(words, "hipMalloc(live bits)")) return rc;
+        hipError_t e = hipMemset(nb, 0, words * sizeof(uint64_t));
+        if (e == hipSuccess && h->live_bits && h->bits_cap)
+            e = hipMemcpy(nb, h->live_bits, h->bits_cap * sizeof(uint64_t), hipMemcpyDeviceToDevice);
+        if (e != hipSuccess) return fail(SZG_E_DEVICE, "hipMemcpy(live bits)", e);
+        h->live_bits = std::move(nb);
+        h->bits_cap = words;
+    }
+    return SZG_OK;
+}
+
 int shard_reserve(szg_index *ix, Shard *sh, uint64_t rows_needed)
 {
     HIPCHK(hipSetDevice(sh->device));
-    if (rows_needed > 0xFFFFFFF0ull) return fail(SZG_E_UNSUPPORTED, "more than 2^32 rows per shard");
-    if (rows_needed > sh->cap_rows) {
-        uint64_t cap = std::max<uint64_t>(rows_needed, sh->cap_rows + sh->cap_rows / 2);
-        cap = (cap + 63) & ~63ull;
-        uint8_t *nr = nullptr;
-        hipError_t e = hipMalloc((void **)&nr, szg::layout_bytes(ix->layout, cap) + 64);
-        if (e != hipSuccess) return fail(SZG_E_NOMEM, "hipMalloc(corpus)", e);
-        if (sh->rows && sh->n_rows) {
-            e = hipMemcpy(nr, sh->rows, szg::layout_bytes(ix->layout, sh->n_rows), hipMemcpyDeviceToDevice);
-            if (e != hipSuccess) {
-                (void)hipFree(nr);
-                return fail(SZG_E_DEVICE, "hipMemcpy(corpus)", e);
-            }
-        }
-        if (sh->rows) (void)hipFree(sh->rows);
-        sh->rows = nr;
-        sh->cap_rows = cap;
-    }
-    const uint64_t words = (sh->cap_rows + 63) / 64;
-    if (words > sh->bits_cap) {
-        uint64_t *nb = nullptr;
-        hipError_t e = hipMalloc((void **)&nb, words * sizeof(uint64_t));
-        if (e != hipSuccess) return fail(SZG_E_NOMEM, "hipMalloc(live bits)", e);
-        e = hipMemset(nb, 0, words * sizeof(uint64_t));
-        if (e == hipSuccess && sh->live_bits && sh->bits_cap)
-            e = hipMemcpy(nb, sh->live_bits, sh->bits_cap * sizeof(uint64_t), hipMemcpyDeviceToDevice);
-        if (e != hipSuccess) {
-            (void)hipFree(nb);
-            return fail(SZG_E_DEVICE, "hipMemcpy(live bits)", e);
-        }
-        if (sh->live_bits) (void)hipFree(sh->live_bits);
-        sh->live_bits = nb;
-        sh->bits_cap = words;
-    }
-    if (sh->live_host.size() < words) sh->live_host.resize(words, 0);
+    if (int rc = rows_reserve(ix->layout, sh, rows_needed)) return rc;
+    if (sh->live_host.size() < sh->bits_cap) sh->live_host.resize(sh->bits_cap, 0);
     return SZG_OK;
+}
+
+// the host's live words of a shard that holds `n_rows` rows, none of them dead: ones up to there, zero behind
+void live_host_fill(Shard *sh, uint64_t n_rows)
+{
+    std::fill(sh->live_host.begin(), sh->live_host.end(), 0ull);
+    for (uint64_t w = 0; w * 64 < n_rows; w++)
+        sh->live_host[w] = n_rows - w * 64 >= 64 ? ~0ull : ((1ull << (n_rows - w * 64)) - 1ull);
 }
 
 // set live bits for rows [lo, hi) of a shard: the host copy is the master, the touched words
@@ -205,9 +209,7 @@ int reset_shards(szg_index *ix, const std::vector<uint64_t> &counts)
         if (rc) return rc;
         HIPCHK(szg::launch_fill_bits(sh->live_bits, counts[s], sh->bits_cap, nullptr));
         HIPCHK(hipDeviceSynchronize());
-        std::fill(sh->live_host.begin(), sh->live_host.end(), 0ull);
-        for (uint64_t w = 0; w * 64 < counts[s]; w++)
-            sh->live_host[w] = counts[s] - w * 64 >= 64 ? ~0ull : ((1ull << (counts[s] - w * 64)) - 1ull);
+        live_host_fill(sh, counts[s]);
         first += counts[s];
     }
     return SZG_OK;
@@ -304,8 +306,7 @@ int szg_index_create(szg_index **out, int dim, int quant_bits, int metric, const
             szg_index_destroy(ix);
             return fail(SZG_E_NODEVICE, "device is not gfx950 (kernels are built for MI355X only)");
         }
-        Shard *sh = new Shard();
-        sh->device = d;
+        Shard *sh = new Shard(d);
         sh->cu_count = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
         ix->shards.push_back(sh);
     }
@@ -315,13 +316,15 @@ int szg_index_create(szg_index **out, int dim, int quant_bits, int metric, const
             szg_index_destroy(ix);
             return fail(SZG_E_DEVICE, "hipStreamCreate(scan stream)");
         }
-        if (hipMalloc((void **)&sh->zero16, 64) != hipSuccess || hipMemset(sh->zero16, 0, 64) != hipSuccess) {
+        int rc = sh->zero16.alloc_exact(64, "hipMalloc(zero16)");
+        if (rc == SZG_OK && hipMemset(sh->zero16, 0, 64) != hipSuccess) rc = fail(SZG_E_NOMEM, "hipMemset(zero16)");
+        if (rc) {
             szg_index_destroy(ix);
-            return fail(SZG_E_NOMEM, "hipMalloc(zero16)");
+            return rc;
         }
         for (int i = 0; i < ix->n_ctx; i++) {
             Ctx *c = nullptr;
-            int rc = ctx_alloc(ix, sh, &c);
+            rc = ctx_alloc(ix, sh, &c);
             if (rc) {
                 ctx_free(c);
                 szg_index_destroy(ix);
@@ -355,12 +358,7 @@ void szg_index_destroy(szg_index *ix)
         (void)hipDeviceSynchronize();
         for (Ctx *c : sh->all_ctx) ctx_free(c);
         if (sh->scan_stream) (void)hipStreamDestroy(sh->scan_stream);
-        (void)hipFree(sh->zero16);
-        (void)hipFree(sh->stage);
-        (void)hipFree(sh->rows);
-        (void)hipFree(sh->live_bits);
-        (void)hipFree(sh->row_norm);
-        delete sh;
+        delete sh;  // (its device memory goes with it)
     }
     delete ix;
 }

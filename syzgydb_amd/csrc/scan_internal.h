@@ -16,12 +16,17 @@
 //   scan_reorder.cpp  compaction and reorder of the resident rows on the device (reorder_plan.h: its host-only checks)
 //   scan_api.cpp      remaining C entry points (top-k with caller coalescing, distances)
 //
+// Who owns device memory: dev_mem.h.  Every block is held by a DevBuf / PinnedBuf (scratch of the device that is
+// current) or a DevMem (bound to its device: a shard's rows, live bits, norms and staging, a column's parts, a mask's
+// words) that frees itself; only scan_comm.cpp keeps its exchange staging by hand.
+//
 // What a batch borrows per shard is a Ctx: a stream, events and scratch that persist between batches -- every buffer
-// a DevBuf / PinnedBuf that frees itself -- and one Pass, the record of the batch in flight.  The Pass is reset as a
+// a DevBuf / PinnedBuf -- and one Pass, the record of the batch in flight.  The Pass is reset as a
 // whole where the context is handed out (ctx_acquire), written by the function that enqueues the work and read by
 // the one that finishes it; results in the pinned output buffer are reached through Ctx::out / sentinel / drop_bound.
 #pragma once
 #include "../../include/syzgy_scan.h"
+#include "dev_mem.h"
 #include "kernels.h"
 #include "reorder_plan.h"
 
@@ -175,48 +180,6 @@ struct Cand {
     double ub;     // key + the error bound of the arithmetic that produced it: the real-number key is <= ub
 };
 
-// ---- owning buffers -------------------------------------------------------------------------------------------------
-// A pointer and a capacity in elements.  ensure(n) does nothing while the buffer holds n elements; otherwise it frees
-// FIRST (the old and the new block never exist side by side) and allocates max(n, 64): the contents are never carried
-// over.  Move-only; the destructor frees.
-template <typename T, bool kPinned>
-class HipBuf {
-    T *p_ = nullptr;
-    size_t cap_ = 0;
-
-public:
-    HipBuf() = default;
-    HipBuf(HipBuf &&o) noexcept : p_(o.p_), cap_(o.cap_) { o.p_ = nullptr, o.cap_ = 0; }
-    HipBuf &operator=(HipBuf &&o) noexcept
-    {
-        std::swap(p_, o.p_);
-        std::swap(cap_, o.cap_);
-        return *this;
-    }
-    ~HipBuf() { (void)reset(); }
-    T *data() const { return p_; }
-    operator T *() const { return p_; }
-    size_t capacity() const { return cap_; }
-    int reset()
-    {
-        if (p_) HIPCHK(kPinned ? hipHostFree(p_) : hipFree(p_));
-        p_ = nullptr;
-        cap_ = 0;
-        return SZG_OK;
-    }
-    int ensure(size_t need)
-    {
-        if (cap_ >= need) return SZG_OK;
-        if (int rc = reset()) return rc;
-        const size_t n = std::max(need, (size_t)64);
-        HIPCHK(kPinned ? hipHostMalloc((void **)&p_, n * sizeof(T), hipHostMallocDefault) : hipMalloc((void **)&p_, n * sizeof(T)));
-        cap_ = n;
-        return SZG_OK;
-    }
-};
-template <typename T> using DevBuf = HipBuf<T, false>;     // device memory
-template <typename T> using PinnedBuf = HipBuf<T, true>;   // pinned host memory
-
 // ---- one in-flight batch of queries on one shard --------------------------------
 
 // the arithmetic that produced the list keys of a finished top-k pass: which error bound certifies them (gather_topk)
@@ -336,15 +299,24 @@ struct Ctx {
     const szg::RerankOut &drop_bound(int j) const { return out(j, pass.kp); }
 };
 
-struct Shard {
-    int device = 0;
-    uint64_t first = 0;        // index-level row of this shard's row 0
+// The resident rows of a shard and their live bits: what rows_reserve grows, and what a compaction / reorder builds
+// afresh beside the shard's and then moves into it as a whole.
+struct ShardRows {
+    explicit ShardRows(int device) : rows(device), live_bits(device) {}
+    ShardRows(ShardRows &&) = default;
+    ShardRows &operator=(ShardRows &&) = default;  // (what the target held is released)
     uint64_t n_rows = 0;
     uint64_t cap_rows = 0;
-    uint64_t n_live = 0;
-    uint8_t *rows = nullptr;
-    uint64_t *live_bits = nullptr;
+    DevMem<uint8_t> rows;      // layout_bytes(cap_rows) + 64 bytes
+    DevMem<uint64_t> live_bits;
     uint64_t bits_cap = 0;     // words
+};
+
+struct Shard : ShardRows {
+    explicit Shard(int device_) : ShardRows(device_), device(device_), zero16(device_), row_norm(device_), stage(device_) {}
+    const int device;
+    uint64_t first = 0;        // index-level row of this shard's row 0
+    uint64_t n_live = 0;
     std::vector<uint64_t> live_host;  // host copy of live_bits (tombstone / append bookkeeping, first-k rows)
     bool has_dead = false;
     int cu_count = 256;
@@ -359,15 +331,15 @@ struct Shard {
     // copy work of other batches overlap them on the contexts' own streams.
     std::mutex chain_mu;
     hipStream_t scan_stream = nullptr;
-    uint8_t *zero16 = nullptr;   // 16 zero bytes idle lanes of the multi-query sweep read
+    DevMem<uint8_t> zero16;      // 16 zero bytes idle lanes of the multi-query sweep read
     // resident float32 row norms (16-bit rows, shared bfloat16 sweep): rows [0, norm_valid) are up to date; load /
     // synth reset it, appended rows are caught up before the next shared sweep, an overwritten row at once
-    float *row_norm = nullptr;
+    DevMem<float> row_norm;
     uint64_t norm_cap = 0, norm_valid = 0;
     std::mutex norm_mu;
     // device staging of the mutation entry points (load / append / overwrite / read-back): kept
     // between calls, so AddDocument in a loop pays no hipMalloc / hipFree per row
-    uint8_t *stage = nullptr;
+    DevMem<uint8_t> stage;
     size_t stage_cap = 0;
     std::mutex stage_mu;         // szg_index_read_rows may run beside other readers (szg_pair_distances)
 };
@@ -492,10 +464,11 @@ struct szg_mask {
     uint64_t epoch = 0;     // the owner's mask_epoch this mask was made at
     uint64_t rows = 0;      // row count of the handle then
     struct Part {
-        int device = 0;
+        explicit Part(int device_ = 0) : device(device_), words(device_) {}
+        int device;
         uint64_t first = 0, n_rows = 0;
         size_t pairs = 0;             // 16-byte pairs of words
-        szgi::DevBuf<uint64_t> words; // 2 * pairs words, then the popcount counter (2 words)
+        szgi::DevMem<uint64_t> words; // 2 * pairs words, then the popcount counter (2 words)
         uint64_t count = 0;           // rows of the shard the mask allows
     };
     std::vector<Part> parts;          // one per shard of the owner
@@ -515,13 +488,15 @@ struct szg_column {
     uint64_t epoch = 0;     // the owner's col_epoch this column was made at
     uint64_t rows = 0;
     struct Part {
-        int device = 0;
+        explicit Part(int device_ = 0) : device(device_), values(device_), present(device_), heap(device_) {}
+        int device;
         uint64_t first = 0, n_rows = 0, cap_rows = 0;  // cap_rows: a multiple of 128
-        void *values = nullptr;            // device, cap_rows elements
-        uint64_t *present = nullptr;       // device, cap_rows / 64 words in the masks' 16-byte-pair layout, tail bits 0
+        szgi::DevMem<uint8_t> values;      // cap_rows elements of elem() bytes
+        szgi::DevMem<uint64_t> present;    // cap_rows / 64 words in the masks' 16-byte-pair layout, tail bits 0
         std::vector<uint64_t> present_host;  // the same words
-        uint8_t *heap = nullptr;           // text columns: device, heap_cap bytes, zero behind heap_used
+        szgi::DevMem<uint8_t> heap;        // text columns: heap_cap bytes, zero behind heap_used
         uint64_t heap_used = 0, heap_cap = 0;  // heap_cap: 0 or a multiple of 16, >= the used bytes rounded up to 16, + 16
+        template <typename T> T *values_as() const { return reinterpret_cast<T *>(values.data()); }
     };
     std::vector<Part> parts;              // one per shard of the owner
     size_t elem() const { return kind == SZG_COL_U32 ? sizeof(uint32_t) : 8; }   // (a double, or a text reference)
@@ -584,7 +559,9 @@ Ctx *ctx_try_acquire(Shard *sh);
 void ctx_release(Shard *sh, Ctx *c);
 int shard_stage(Shard *sh, size_t bytes, uint8_t **out);
 int upload_rows(szg_index *ix, Shard *sh, uint64_t dst_row, const uint8_t *rows, uint64_t n);
+int rows_reserve(const szg::RowLayout &layout, ShardRows *h, uint64_t rows_needed);
 int shard_reserve(szg_index *ix, Shard *sh, uint64_t rows_needed);
+void live_host_fill(Shard *sh, uint64_t n_rows);
 int shard_set_live(Shard *sh, uint64_t lo, uint64_t hi);
 void split_rows(const szg_index *ix, uint64_t n_rows, std::vector<uint64_t> *counts);
 Shard *shard_of(szg_index *ix, uint64_t row, uint64_t *local);
@@ -709,16 +686,19 @@ inline size_t index_words(uint64_t rows) { return (size_t)((rows + 63) / 64); }
 
 // ---- scan_column.cpp
 int stale_column();  // SZG_E_INVALID, "stale column: ..."
+// a valid, complete column of ix (SZG_E_INVALID otherwise: another handle's, stale, or short of the handle's rows)
+int column_complete_check(const szg_index *ix, const szg_column *c);
+// room for `need` rows in a part / for `used` bytes in its text heap: a bigger allocation with the old contents carried
+// over, or -- a part that starts empty -- what a freshly created column has (column_str.h has the sizes).  zeroed ==
+// false: the caller writes every byte of a new heap itself
+int part_reserve(const szg_column *c, szg_column::Part &p, uint64_t need);
+int heap_reserve(szg_column::Part &p, uint64_t used, bool zeroed = true);
 
 // ---- scan_column_carry.cpp: the columns a compaction / reorder carries (scan_reorder.cpp calls these in this order)
-// the new parts of the carried columns until the switch; what has not been handed to its column is freed on every exit
+// the new parts of the carried columns until the switch; what has not been handed to its column goes with this
 struct CarriedColumns {
     std::vector<szg_column *> cols;
     std::vector<std::vector<szg_column::Part>> parts;  // [column][shard]
-    CarriedColumns() = default;
-    CarriedColumns(const CarriedColumns &) = delete;
-    CarriedColumns &operator=(const CarriedColumns &) = delete;
-    ~CarriedColumns();
 };
 // every entry is a valid, complete column of ix; *out takes each once
 int column_carry_check(szg_index *ix, szg_column *const *columns, int n_columns, std::vector<szg_column *> *out);

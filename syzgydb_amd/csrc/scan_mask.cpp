@@ -21,11 +21,10 @@ int mask_alloc(szg_index *ix, szg_mask **out)
     m->epoch = ix->mask_epoch.load();
     m->rows = szg_index_rows(ix);
     m->host.assign(index_words(m->rows), 0ull);
-    m->parts.resize(ix->shards.size());
+    for (const Shard *sh : ix->shards) m->parts.emplace_back(sh->device);
     for (size_t s = 0; s < ix->shards.size(); s++) {
         const Shard *sh = ix->shards[s];
         szg_mask::Part &p = m->parts[s];
-        p.device = sh->device;
         p.first = sh->first;
         p.n_rows = sh->n_rows;
         if (sh->n_rows == 0) continue;
@@ -44,11 +43,6 @@ int mask_alloc(szg_index *ix, szg_mask **out)
 void mask_free(szg_mask *m)
 {
     if (!m) return;
-    for (szg_mask::Part &p : m->parts) {
-        if (!p.words.data()) continue;
-        (void)hipSetDevice(p.device);
-        (void)p.words.reset();
-    }
     if (m->counted) {
         m->owner->mask_live--;
         m->owner->mask_dev_bytes -= m->dev_bytes;

@@ -117,14 +117,12 @@ int ensure_row_norms(szg_index *ix, Shard *sh)
     HIPCHK(hipSetDevice(sh->device));
     if (sh->norm_cap < sh->n_rows) {
         const uint64_t cap = std::max<uint64_t>(sh->cap_rows, sh->n_rows);
-        float *nn = nullptr;
-        hipError_t e = hipMalloc((void **)&nn, cap * sizeof(float));
-        if (e != hipSuccess) return fail(SZG_E_NOMEM, "hipMalloc(row norms)", e);
+        DevMem<float> nn(sh->device);
+        if (int rc = nn.alloc_exact(cap, "hipMalloc(row norms)")) return rc;
         HIPCHK(hipStreamSynchronize(sh->scan_stream));  // (sweeps in flight read the old array)
         if (sh->row_norm && sh->norm_valid)
             HIPCHK(hipMemcpy(nn, sh->row_norm, sh->norm_valid * sizeof(float), hipMemcpyDeviceToDevice));
-        (void)hipFree(sh->row_norm);
-        sh->row_norm = nn;
+        sh->row_norm = std::move(nn);
         sh->norm_cap = cap;
     }
     HIPCHK(szg::launch_row_norms(ix->bits, sh->rows, ix->layout, ix->dim, (float)ix->norm_bias, sh->norm_valid,

@@ -11,29 +11,12 @@
 // carried columns switched over: an error before that point leaves the handle, its masks and ALL its columns as they were.
 // Afterwards the handle looks as after szg_index_load of the same rows in the same order.
 #include "scan_internal.h"
+#include "column_carry.h"
 
 using namespace szgi;
 
 namespace {
 
-struct NewShard {
-    int device = 0;
-    uint8_t *rows = nullptr;
-    uint64_t *bits = nullptr;
-    uint64_t cap = 0, words = 0;
-};
-struct NewShards {  // what has not been handed to a shard is freed on every exit path
-    std::vector<NewShard> v;
-    ~NewShards()
-    {
-        for (NewShard &s : v) {
-            if (!s.rows && !s.bits) continue;
-            (void)hipSetDevice(s.device);
-            (void)hipFree(s.rows);
-            (void)hipFree(s.bits);
-        }
-    }
-};
 struct NewMask {
     szg_mask *m = nullptr;
     std::vector<szg_mask::Part> parts;
@@ -66,23 +49,18 @@ int check_carry(szg_index *ix, szg_mask *const *carry, int n_carry, std::vector<
 // window's order, into a linear stage (the shard's own, or -- for the rows shard d keeps -- straight into d's) and
 // copied into d's stage behind the other sources' rows; ONE launch then places the whole window, new row w0 + i from
 // stage row perm[i].  The cost does not depend on how the sources interleave.
-int move_window(szg_index *ix, size_t d, const NewShard &to, uint64_t w0, const uint64_t *src, uint64_t m,
-                std::vector<DevBuf<uint64_t>> *d_lists, DevBuf<uint64_t> *d_perm)
+int move_window(szg_index *ix, size_t d, const ShardRows &to, uint64_t w0, const uint64_t *src, uint64_t m,
+                std::vector<DevMem<uint64_t>> *d_lists, DevMem<uint64_t> *d_perm)
 {
     const size_t S = ix->shards.size();
     Shard *dst = ix->shards[d];
     const uint32_t r16 = ix->pitch / 16;
     const szg::RowLayout linear{ix->pitch, 0, 0};
-    std::vector<std::vector<uint64_t>> sub(S);  // per source shard: its rows of the window (shard-local), in window order
-    std::vector<std::vector<uint64_t>> at(S);   // ... and where in the window each goes
-    for (uint64_t i = 0; i < m; i++) {
-        uint64_t local = 0;
-        Shard *from = shard_of(ix, src[i], &local);
-        if (!from) return fail(SZG_E_RANGE, "row out of range");
-        const size_t s = (size_t)(std::find(ix->shards.begin(), ix->shards.end(), from) - ix->shards.begin());
-        sub[s].push_back(local);
-        at[s].push_back(i);
-    }
+    // per source shard: its rows of the window (shard-local), in window order, and where in the window each goes
+    std::vector<std::vector<uint64_t>> sub, at;
+    std::vector<uint64_t> old_first(S), old_n(S);
+    for (size_t s = 0; s < S; s++) old_first[s] = ix->shards[s]->first, old_n[s] = ix->shards[s]->n_rows;
+    if (!carry_group_rows(src, m, old_first.data(), old_n.data(), S, &sub, &at)) return fail(SZG_E_RANGE, "row out of range");
     std::vector<uint64_t> perm((size_t)m);
     uint8_t *stage_d = nullptr;
     std::lock_guard<std::mutex> lk_d(dst->stage_mu);
@@ -133,61 +111,53 @@ int reorder_checked(szg_index *ix, const std::vector<uint64_t> &src, const std::
         HIPCHK(hipSetDevice(sh->device));
         HIPCHK(hipDeviceSynchronize());
     }
-    // ---- the new allocations (shard_reserve's rules for a shard that starts empty)
-    NewShards fresh;
-    fresh.v.resize(S);
+    // ---- the new allocations: shard_reserve's, for rows that start empty
+    std::vector<ShardRows> fresh;
+    fresh.reserve(S);
     std::vector<uint64_t> first(S, 0);
     for (size_t s = 0; s < S; s++) {
-        NewShard &t = fresh.v[s];
-        t.device = ix->shards[s]->device;
+        fresh.emplace_back(ix->shards[s]->device);
         first[s] = s ? first[s - 1] + counts[s - 1] : 0;
-        if (counts[s] > 0xFFFFFFF0ull) return fail(SZG_E_UNSUPPORTED, "more than 2^32 rows per shard");
-        if (counts[s] == 0) continue;
-        t.cap = (counts[s] + 63) & ~63ull;
-        t.words = t.cap / 64;
-        HIPCHK(hipSetDevice(t.device));
-        hipError_t e = hipMalloc((void **)&t.rows, szg::layout_bytes(ix->layout, t.cap) + 64);
-        if (e != hipSuccess) return fail(SZG_E_NOMEM, "hipMalloc(corpus)", e);
-        e = hipMalloc((void **)&t.bits, t.words * sizeof(uint64_t));
-        if (e != hipSuccess) return fail(SZG_E_NOMEM, "hipMalloc(live bits)", e);
-        HIPCHK(szg::launch_fill_bits(t.bits, counts[s], t.words, nullptr));
+        HIPCHK(hipSetDevice(ix->shards[s]->device));
+        if (int rc = rows_reserve(ix->layout, &fresh[s], counts[s])) return rc;
+        if (counts[s]) HIPCHK(szg::launch_fill_bits(fresh[s].live_bits, counts[s], fresh[s].bits_cap, nullptr));
     }
     // ---- the rows
-    std::vector<DevBuf<uint64_t>> d_lists(S);  // a source shard's list on its device
+    std::vector<DevMem<uint64_t>> d_lists;  // a source shard's list on its device
+    for (const Shard *sh : ix->shards) d_lists.emplace_back(sh->device);
     if (S == 1) {  // old buffer -> new buffer, one launch
         if (n) {
-            HIPCHK(hipSetDevice(fresh.v[0].device));
+            HIPCHK(hipSetDevice(ix->shards[0]->device));
             int rc = d_lists[0].ensure((size_t)n);
             if (rc) return rc;
             HIPCHK(hipMemcpy(d_lists[0].data(), src.data(), n * sizeof(uint64_t), hipMemcpyHostToDevice));
-            HIPCHK(szg::launch_gather_rows(ix->shards[0]->rows, ix->layout, fresh.v[0].rows, ix->layout, ix->pitch / 16,
+            HIPCHK(szg::launch_gather_rows(ix->shards[0]->rows, ix->layout, fresh[0].rows, ix->layout, ix->pitch / 16,
                                            d_lists[0].data(), n, 0, nullptr));
             HIPCHK(hipStreamSynchronize(nullptr));
         }
     } else {
         const uint64_t window = std::max<uint64_t>(1, (64ull << 20) / ix->pitch);
         for (size_t d = 0; d < S; d++) {
-            DevBuf<uint64_t> d_perm;
+            DevMem<uint64_t> d_perm(ix->shards[d]->device);
             for (uint64_t w0 = 0; w0 < counts[d]; w0 += window) {
-                int rc = move_window(ix, d, fresh.v[d], w0, src.data() + first[d] + w0, std::min(window, counts[d] - w0),
+                int rc = move_window(ix, d, fresh[d], w0, src.data() + first[d] + w0, std::min(window, counts[d] - w0),
                                      &d_lists, &d_perm);
                 if (rc) return rc;
             }
-            HIPCHK(hipSetDevice(fresh.v[d].device));  // (d_perm goes on its own device)
-            (void)d_perm.reset();
         }
     }
     // ---- the carried masks: new bit i = old bit src[i], per destination shard
     std::vector<NewMask> masks(carry.size());
     for (size_t k = 0; k < carry.size(); k++) {
         masks[k].m = carry[k];
-        masks[k].parts.resize(S);
+        for (const Shard *sh : ix->shards) masks[k].parts.emplace_back(sh->device);
         masks[k].host.assign(index_words(n), 0ull);
     }
     for (size_t d = 0; d < S && !carry.empty(); d++) {
         if (counts[d] == 0) continue;
-        HIPCHK(hipSetDevice(fresh.v[d].device));
-        DevBuf<uint64_t> list, old_all;
+        const int dev = ix->shards[d]->device;
+        HIPCHK(hipSetDevice(dev));
+        DevMem<uint64_t> list(dev), old_all(dev);
         int rc = list.ensure((size_t)counts[d]);
         if (rc == SZG_OK && S > 1) rc = old_all.ensure(index_words(old_rows));
         if (rc) return rc;
@@ -202,7 +172,6 @@ int reorder_checked(szg_index *ix, const std::vector<uint64_t> &src, const std::
                 old_words = old_all.data();
             }
             szg_mask::Part &p = nm.parts[d];
-            p.device = fresh.v[d].device;
             p.first = first[d];
             p.n_rows = counts[d];
             p.pairs = mask_slot_words(counts[d]) / 2;
@@ -224,30 +193,21 @@ int reorder_checked(szg_index *ix, const std::vector<uint64_t> &src, const std::
     // ---- the carried columns: new row i reads what old row src[i] read
     CarriedColumns cols;
     if (int rc = column_carry_build(ix, src, S == 1 ? d_lists[0].data() : nullptr, counts, first, columns, &cols)) return rc;
-    for (const NewShard &t : fresh.v) {
-        HIPCHK(hipSetDevice(t.device));
+    for (const Shard *sh : ix->shards) {
+        HIPCHK(hipSetDevice(sh->device));
         HIPCHK(hipDeviceSynchronize());
     }
     // ---- the swap: nothing below fails
     for (size_t s = 0; s < S; s++) {
         Shard *sh = ix->shards[s];
-        NewShard &t = fresh.v[s];
-        (void)hipSetDevice(sh->device);
-        (void)hipFree(sh->rows);
-        (void)hipFree(sh->live_bits);
-        sh->rows = t.rows;
-        sh->live_bits = t.bits;
-        t.rows = nullptr;
-        t.bits = nullptr;
-        sh->cap_rows = t.cap;
-        sh->bits_cap = t.words;
+        fresh[s].n_rows = counts[s];
+        static_cast<ShardRows &>(*sh) = std::move(fresh[s]);  // (the old rows and live bits go)
         sh->first = first[s];
-        sh->n_rows = sh->n_live = counts[s];
+        sh->n_live = counts[s];
         sh->has_dead = false;
         sh->norm_valid = 0;
-        sh->live_host.assign((size_t)t.words, 0ull);
-        for (uint64_t w = 0; w * 64 < counts[s]; w++)
-            sh->live_host[w] = counts[s] - w * 64 >= 64 ? ~0ull : ((1ull << (counts[s] - w * 64)) - 1ull);
+        sh->live_host.resize((size_t)sh->bits_cap);
+        live_host_fill(sh, counts[s]);   // (zero behind the rows)
     }
     ix->gen++;
     const uint64_t epoch = ++ix->mask_epoch;
@@ -272,12 +232,7 @@ int reorder_checked(szg_index *ix, const std::vector<uint64_t> &src, const std::
     for (NewMask &nm : masks) {
         szg_mask *m = nm.m;
         if (m->counted) ix->mask_dev_bytes += nm.dev_bytes - m->dev_bytes;
-        for (szg_mask::Part &p : m->parts) {  // the old words go on their own device
-            if (!p.words.data()) continue;
-            (void)hipSetDevice(p.device);
-            (void)p.words.reset();
-        }
-        m->parts = std::move(nm.parts);
+        m->parts = std::move(nm.parts);  // (the old words go, each on its own device)
         m->host = std::move(nm.host);
         m->count = nm.count;
         m->dev_bytes = nm.dev_bytes;

@@ -105,14 +105,14 @@ int sketch_sync(szg_index *ix)
             const uint64_t have = only_new ? b->n_rows : 0;
             if (a->n_rows <= have) continue;
             HIPCHK(hipSetDevice(a->device));
-            unsigned long long *d_max = nullptr, bits = 0;
-            HIPCHK(hipMalloc((void **)&d_max, 16));
+            unsigned long long bits = 0;
+            DevBuf<unsigned long long> d_max;
+            if (int rc = d_max.ensure(2)) return rc;
             hipError_t e = hipMemset(d_max, 0, 16);
             if (e == hipSuccess)
                 e = szg::launch_sketch_build(a->rows, ix->layout, ix->dim, nullptr, sk->layout, have, a->n_rows - have,
                                              nullptr, d_max, nullptr, nullptr, 0, 0.0, 1, nullptr);
             if (e == hipSuccess) e = hipMemcpy(&bits, d_max, sizeof(bits), hipMemcpyDeviceToHost);
-            (void)hipFree(d_max);
             if (e != hipSuccess) return fail(SZG_E_DEVICE, "sketch scale pass", e);
             const uint32_t fb = (uint32_t)bits;
             float f;
@@ -162,20 +162,12 @@ int sketch_sync(szg_index *ix)
         if (rc) return rc;
         // rewritten rows: their resident norms (the shared bfloat16 sweep's) are stale from the first of them on
         for (uint32_t r : list) b->norm_valid = std::min<uint64_t>(b->norm_valid, r);
-        unsigned long long *d_ang = nullptr;
-        uint32_t *d_exc = nullptr, *d_list = nullptr;
-        struct Scratch {  // freed on every exit path
-            unsigned long long *&a;
-            uint32_t *&b, *&c;
-            ~Scratch()
-            {
-                (void)hipFree(a);
-                (void)hipFree(b);
-                (void)hipFree(c);
-            }
-        } scratch{d_ang, d_exc, d_list};
-        HIPCHK(hipMalloc((void **)&d_ang, 16));
-        HIPCHK(hipMalloc((void **)&d_exc, (exc_cap + 1) * sizeof(uint32_t)));
+        DevBuf<unsigned long long> d_ang;
+        DevBuf<uint32_t> d_exc, d_list;
+        rc = d_ang.ensure(2);
+        if (rc == SZG_OK) rc = d_exc.ensure(exc_cap + 1);
+        if (rc == SZG_OK && !list.empty()) rc = d_list.ensure(list.size());
+        if (rc) return rc;
         HIPCHK(hipMemset(d_ang, 0, 16));
         HIPCHK(hipMemset(d_exc, 0, (exc_cap + 1) * sizeof(uint32_t)));
         hipError_t e = hipSuccess;
@@ -183,8 +175,7 @@ int sketch_sync(szg_index *ix)
             e = szg::launch_sketch_build(a->rows, ix->layout, ix->dim, b->rows, sk->layout, have, a->n_rows - have, nullptr,
                                          d_ang, d_exc + 1, d_exc, exc_cap, ix->sk_gscale, 0, nullptr);
         if (e == hipSuccess && !list.empty()) {
-            e = hipMalloc((void **)&d_list, list.size() * sizeof(uint32_t));
-            if (e == hipSuccess) e = hipMemcpy(d_list, list.data(), list.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
+            e = hipMemcpy(d_list, list.data(), list.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
             if (e == hipSuccess)
                 e = szg::launch_sketch_build(a->rows, ix->layout, ix->dim, b->rows, sk->layout, 0, list.size(), d_list,
                                              d_ang, d_exc + 1, d_exc, exc_cap, ix->sk_gscale, 0, nullptr);

@@ -3,6 +3,7 @@
 One ScanIndex == one szg_index == the HBM mirror of one Collection's packed
 vectors.  All compute happens in libsyzgy_scan.so (HIP, gfx950).
 """
+import contextlib
 import ctypes
 import os
 import weakref
@@ -50,13 +51,15 @@ class ScanMask:
         self._L = index._L
         self._h = handle
         self._words = words   # per mask, as of its creation
-        index._masks[id(self)] = weakref.ref(self)
+        index._masks[id(self)] = (weakref.ref(self), handle.value)
 
     def close(self):
         if self._h:
-            self._L.szg_mask_destroy(self._h)
+            # (a closed index has destroyed this mask already: the cycle collector clears weak references before it
+            # runs __del__, so the index may not have seen this object, only its handle)
+            if self._index._masks.pop(id(self), None) is not None:
+                self._L.szg_mask_destroy(self._h)
             self._h = ctypes.c_void_p()
-            self._index._masks.pop(id(self), None)
 
     def __del__(self):
         try:
@@ -146,13 +149,13 @@ class ScanColumn:
         self._h = handle
         self.kind = kind
         self._dtype = np.float64 if kind == _lib.SZG_COL_F64 else np.uint32
-        index._columns[id(self)] = weakref.ref(self)
+        index._columns[id(self)] = (weakref.ref(self), handle.value)
 
     def close(self):
         if self._h:
-            self._L.szg_column_destroy(self._h)
+            if self._index._columns.pop(id(self), None) is not None:   # (as ScanMask.close)
+                self._L.szg_column_destroy(self._h)
             self._h = ctypes.c_void_p()
-            self._index._columns.pop(id(self), None)
 
     def __del__(self):
         try:
@@ -323,7 +326,7 @@ class ScanIndex:
         self.row_bytes = int(self._L.szg_row_bytes(self.quant_bits, self.dim))
         self.options = {}   # tunables set through this object (the host mirrors consult tie_mode)
         self._comm = None
-        self._masks = {}    # id -> weak reference of every ScanMask of this handle that is still open
+        self._masks = {}    # id -> (weak reference, handle) of every ScanMask of this handle that is still open
         self._columns = {}  # ... and of every ScanColumn
         self._row_base = 0
         # SZG_OPTIONS="name=value,...": tunables applied to every new handle (test sweeps)
@@ -334,11 +337,17 @@ class ScanIndex:
 
     # -- lifetime -----------------------------------------------------------
     def close(self):
-        for held in ("_columns", "_masks"):   # columns and masks are destroyed before their handle
-            for ref in list(getattr(self, held, {}).values()):
+        # columns and masks are destroyed before their handle -- also those whose Python object is already garbage
+        # (its weak reference is dead, its __del__ has not run yet): their handles are destroyed here, and the entry
+        # that is gone tells their close() so
+        for held, destroy in (("_columns", self._L.szg_column_destroy), ("_masks", self._L.szg_mask_destroy)):
+            table = getattr(self, held, {})
+            for key, (ref, handle) in list(table.items()):
                 m = ref()
                 if m is not None:
                     m.close()
+                elif table.pop(key, None) is not None:
+                    destroy(ctypes.c_void_p(handle))
         if self._h:
             self._L.szg_index_destroy(self._h)
             self._h = ctypes.c_void_p()
@@ -730,6 +739,25 @@ def f64_probe(op, a, b=None):
     out = np.zeros_like(a)
     check(L.szg_debug_f64_probe(int(op), _f64(a), _f64(bb), _f64(out), a.size), "szg_debug_f64_probe")
     return out
+
+
+def device_memory():
+    """Test hook: (blocks, bytes) of device memory the library's handles, columns, masks and scratch own in this process."""
+    blocks, nbytes = ctypes.c_uint64(), ctypes.c_uint64()
+    check(_lib.load().szg_debug_device_memory(ctypes.byref(blocks), ctypes.byref(nbytes)), "szg_debug_device_memory")
+    return blocks.value, nbytes.value
+
+
+@contextlib.contextmanager
+def refuse_device_alloc(nth):
+    """Test hook: inside the block, the nth device allocation from now on (nth >= 1) is refused on the host -- its call
+    raises SzgError(SZG_E_NOMEM, "... (refused: test hook)").  Always disarmed on exit."""
+    L = _lib.load()
+    check(L.szg_debug_refuse_device_alloc(int(nth)), "szg_debug_refuse_device_alloc")
+    try:
+        yield
+    finally:
+        L.szg_debug_refuse_device_alloc(0)
 
 
 def scan_group_plan(dim, quant_bits, n_queries, kp=10, scan_group=0, queries_per_launch=16, collect=False, masked=False):

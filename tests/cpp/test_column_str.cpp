@@ -166,6 +166,10 @@ static int check_sizes()
     // growth: geometric, never past the limit, never below what is needed
     EXPECT(str_heap_grow(0, 0) == 4096 && str_heap_grow(4096, 4090) == 8192 && str_heap_grow(4096, 100000) == str_heap_capacity(100000));
     EXPECT(str_heap_grow(3ull << 30, (3ull << 30) + 1) == kStrHeapLimit);
+    // the rows of a part that must grow: from nothing at least 1024, then at least twice the old room, a multiple of 128
+    EXPECT(column_grow_rows(0, 1) == 1024 && column_grow_rows(0, 1024) == 1024 && column_grow_rows(0, 1025) == 1152);
+    EXPECT(column_grow_rows(1024, 1025) == 2048 && column_grow_rows(1152, 1153) == 2304 && column_grow_rows(1024, 5000) == 5120);
+    EXPECT(column_grow_rows(2048, 4097) == 4224 && column_grow_rows(0, 1000000) == 1000064);
     EXPECT(str_heap_grow(1ull << 20, kStrHeapLimit - 16) == kStrHeapLimit);
 
     // offsets

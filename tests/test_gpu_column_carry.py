@@ -292,6 +292,26 @@ def test_scan_across_blocks(devices):
         m.close()
 
 
+def watch_index(index, dead_row, n, text, keep_bool):
+    """A valid text column and a valid mask of `index`, one row tombstoned, and a check that the rows, the
+    live bits, the column and the mask are what they are now, and still valid."""
+    good = index.text_column(text, present=np.arange(n) % 2 == 0)
+    mask = index.mask(keep_bool)
+    index.tombstone(dead_row)
+    state = (good.read(), good.info(), mask.read().copy(), index.read_rows(0, n).copy())
+
+    def unchanged():
+        assert index.rows == n and index.live_rows == n - 1
+        assert (index.read_rows(0, n) == state[3]).all()
+        got = good.read()
+        assert got[0] == state[0][0] and (got[1] == state[0][1]).all() and good.info() == state[1]
+        check_mask(good.present(), state[0][1])   # still valid
+        assert (mask.read() == state[2]).all()
+        check_mask(good.present(base=mask), state[0][1] & keep_bool)   # the mask as well
+
+    return good, mask, unchanged
+
+
 # ---- 5. refusals and atomicity ------------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("devices", [None, [0, 0]])
@@ -310,23 +330,7 @@ def test_refusals_leave_everything_as_it_was(devices):
         short = ix.column(v[:n - 10])
 
         def watch(index, dead_row):
-            """A valid text column and a valid mask of `index`, one row tombstoned, and a check that the rows, the
-            live bits, the column and the mask are what they are now, and still valid."""
-            good = index.text_column(text, present=np.arange(n) % 2 == 0)
-            mask = index.mask(keep_bool)
-            index.tombstone(dead_row)
-            state = (good.read(), good.info(), mask.read().copy(), index.read_rows(0, n).copy())
-
-            def unchanged():
-                assert index.rows == n and index.live_rows == n - 1
-                assert (index.read_rows(0, n) == state[3]).all()
-                got = good.read()
-                assert got[0] == state[0][0] and (got[1] == state[0][1]).all() and good.info() == state[1]
-                check_mask(good.present(), state[0][1])   # still valid
-                assert (mask.read() == state[2]).all()
-                check_mask(good.present(base=mask), state[0][1] & keep_bool)   # the mask as well
-
-            return good, mask, unchanged
+            return watch_index(index, dead_row, n, text, keep_bool)
 
         good, mask, unchanged = watch(ix, 7)
         moved_good, moved_mask, moved_unchanged = watch(moved, 9)   # (made after the reorder: valid beside the stale one)
