@@ -240,6 +240,74 @@ func (m *gpuMirror) remove(id uint64) {
 	}
 }
 
+// ---- bulk mutations: thin wrappers of the C calls (argument marshalling only), all called under c.mutex.Lock ----
+
+func u64ptr(s []uint64) *C.uint64_t {
+	if len(s) == 0 {
+		return nil
+	}
+	return (*C.uint64_t)(unsafe.Pointer(&s[0]))
+}
+
+// overwriteRows is szg_index_overwrite_rows: encoded holds len(rows) rows in the reference encoding, back to back.
+func (m *gpuMirror) overwriteRows(rows []uint64, encoded []byte) bool {
+	if len(rows) == 0 {
+		return true
+	}
+	m.bump()
+	return C.szg_index_overwrite_rows(m.h, u64ptr(rows), (*C.uint8_t)(unsafe.Pointer(&encoded[0])), C.uint64_t(len(rows))) == C.SZG_OK
+}
+
+// overwriteVectors is szg_index_overwrite_rows_f64: vectors holds len(rows) x dim float64, quantized on the device.
+func (m *gpuMirror) overwriteVectors(rows []uint64, vectors []float64) bool {
+	if len(rows) == 0 {
+		return true
+	}
+	m.bump()
+	return C.szg_index_overwrite_rows_f64(m.h, u64ptr(rows), (*C.double)(unsafe.Pointer(&vectors[0])), C.uint64_t(len(rows))) == C.SZG_OK
+}
+
+// tombstoneRows is szg_index_tombstone_rows: the rows that were live and no longer are.
+func (m *gpuMirror) tombstoneRows(rows []uint64) (uint64, bool) {
+	var dropped C.uint64_t
+	m.bump()
+	ok := C.szg_index_tombstone_rows(m.h, u64ptr(rows), C.uint64_t(len(rows)), &dropped) == C.SZG_OK
+	return uint64(dropped), ok
+}
+
+// tombstoneMask is szg_index_tombstone_mask: every live row a current mask of this handle allows is dropped.  The
+// mask may be one of the cached filter masks, so the call comes FIRST: bump() destroys the cached masks (dropMasks),
+// and the library itself leaves the mask valid.  After the bump the caller's pointer is dead if it came from the cache.
+func (m *gpuMirror) tombstoneMask(mask *C.szg_mask) (uint64, bool) {
+	var dropped C.uint64_t
+	ok := C.szg_index_tombstone_mask(m.h, mask, &dropped) == C.SZG_OK
+	m.bump()
+	return uint64(dropped), ok
+}
+
+// columnSetRows is szg_column_set_rows: values points at len(rows) float64 or uint32 entries (the column's kind),
+// present is nil (every entry present) or one bit per entry.
+func columnSetRows(col *C.szg_column, rows []uint64, values unsafe.Pointer, present []uint64) bool {
+	return C.szg_column_set_rows(col, u64ptr(rows), values, u64ptr(present), C.uint64_t(len(rows))) == C.SZG_OK
+}
+
+// removeBulk mirrors RemoveDocuments: removeDocument for a list of ids with one szg_index_tombstone_rows.  Ids the
+// mirror does not hold are skipped, as remove skips them; returns the rows dropped.
+func (m *gpuMirror) removeBulk(ids []uint64) uint64 {
+	rows := make([]uint64, 0, len(ids))
+	for _, id := range ids {
+		if row, ok := m.rowOf[id]; ok {
+			rows = append(rows, row)
+			delete(m.rowOf, id)
+		}
+	}
+	dropped, ok := m.tombstoneRows(rows)
+	if !ok {
+		m.dirty = true
+	}
+	return dropped
+}
+
 // touch mirrors UpdateDocument (collection.go:490-509): the vectors do not change, but filters
 // see metadata, so cached filter masks no longer apply.  Called under c.mutex.Lock.
 func (m *gpuMirror) touch() { m.bump() }

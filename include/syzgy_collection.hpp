@@ -190,6 +190,69 @@ public:
         row_of_.erase(it);
     }
 
+    // Bulk upsert (not in the reference; the same state as AddDocument in a loop over the entries): new ids are
+    // appended by ONE szg_index_append_f64 in first-seen order, existing ids rewritten by ONE
+    // szg_index_overwrite_rows_f64; an id listed twice keeps its last entry.  vectors: ids.size() x DimensionCount,
+    // row-major; metadatas: empty, or one per id.
+    void AddDocuments(const std::vector<uint64_t> &ids, const std::vector<double> &vectors,
+                      const std::vector<std::string> &metadatas = {})
+    {
+        const size_t dim = (size_t)opts_.DimensionCount;
+        if (vectors.size() != ids.size() * dim || (!metadatas.empty() && metadatas.size() != ids.size()))
+            throw std::invalid_argument("vector size does not match the expected number of dimensions");
+        std::map<uint64_t, size_t> last;   // id -> its last entry
+        std::vector<uint64_t> fresh;       // new ids, first-seen order
+        for (size_t j = 0; j < ids.size(); j++) {
+            if (!last.count(ids[j]) && !row_of_.count(ids[j])) fresh.push_back(ids[j]);
+            last[ids[j]] = j;
+        }
+        std::vector<uint64_t> rows;
+        std::vector<double> block;
+        for (const auto &kv : last) {
+            const auto it = row_of_.find(kv.first);
+            if (it == row_of_.end()) continue;
+            rows.push_back(it->second);
+            block.insert(block.end(), vectors.begin() + kv.second * dim, vectors.begin() + (kv.second + 1) * dim);
+        }
+        if (!rows.empty())
+            check(szg_index_overwrite_rows_f64(ix_, rows.data(), block.data(), rows.size()), "szg_index_overwrite_rows_f64");
+        for (const auto &kv : last) {
+            const auto it = row_of_.find(kv.first);
+            if (it != row_of_.end()) meta_[it->second] = metadatas.empty() ? std::string() : metadatas[kv.second];
+        }
+        if (fresh.empty()) return;
+        block.clear();
+        for (uint64_t id : fresh)
+            block.insert(block.end(), vectors.begin() + last[id] * dim, vectors.begin() + (last[id] + 1) * dim);
+        check(szg_index_append_f64(ix_, block.data(), fresh.size()), "szg_index_append_f64");
+        for (uint64_t id : fresh) {
+            row_of_[id] = id_of_.size();
+            id_of_.push_back(id);
+            live_.push_back(true);
+            meta_.push_back(metadatas.empty() ? std::string() : metadatas[last[id]]);
+        }
+    }
+
+    // removeDocument for a list, ONE szg_index_tombstone_rows: an unknown id throws before anything changes; an id
+    // listed twice counts once.  Returns the documents removed.
+    uint64_t RemoveDocuments(const std::vector<uint64_t> &ids)
+    {
+        std::vector<uint64_t> rows;
+        for (uint64_t id : ids) {
+            const auto it = row_of_.find(id);
+            if (it == row_of_.end()) throw std::runtime_error("record not found");
+            rows.push_back(it->second);
+        }
+        uint64_t dropped = 0;
+        check(szg_index_tombstone_rows(ix_, rows.data(), rows.size(), &dropped), "szg_index_tombstone_rows");
+        for (size_t j = 0; j < ids.size(); j++) {
+            live_[rows[j]] = false;
+            meta_[rows[j]].clear();
+            row_of_.erase(ids[j]);
+        }
+        return dropped;
+    }
+
     // collection.go:348-400; intn(n) plays rand.Intn
     double computeAverageDistance(int samples, const std::function<int(int)> &intn)
     {

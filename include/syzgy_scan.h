@@ -397,6 +397,47 @@ typedef struct szg_column_info {
 } szg_column_info;
 int szg_column_get_info(const szg_column *c, szg_column_info *out);   /* works on a stale column */
 
+/* ---- bulk mutations: many rows per call (added under ABI 4, additive) ----
+ *
+ * szg_index_overwrite, szg_index_overwrite_f64, szg_index_tombstone and szg_column_set for a LIST of rows, with a
+ * constant number of device synchronisations per shard and per 64 MiB of the caller's data instead of a round trip
+ * per row.  Each call leaves the handle in the state the loop of its single-row form would, with one documented
+ * difference: every argument is checked before anything on the card changes, so a bad entry refuses the whole call
+ * where the loop would have applied the entries before it.
+ * Rows: rows[0 .. n_rows) are numbered as the call's single-row form numbers them (szg_column_set_rows: as
+ *   szg_column_set does).  row_bytes, vectors and values are n_rows consecutive entries, entry i for rows[i]:
+ *   row_bytes in the reference encoding szg_index_overwrite takes; vectors float64, quantized and packed on the
+ *   device exactly as szg_index_overwrite_f64 does; values as szg_column_append's.  present_bits: NULL = every entry
+ *   is present; otherwise bit i belongs to rows[i], and the value of an absent entry is ignored -- the row keeps its
+ *   stored value and reads as absent, as after szg_column_set(row, NULL).
+ * Refusals, nothing changed: a NULL argument (out_dropped and present_bits excepted) is SZG_E_INVALID; a row at or
+ *   past the handle's (the column's) rows is SZG_E_RANGE, "row out of range"; a row listed twice is SZG_E_INVALID,
+ *   "row listed twice", in the overwrite and the column forms -- szg_index_reorder's rule, which keeps the scatter free
+ *   of two writers to one row.  The tombstone forms accept duplicates and rows that are already dead.  n_rows == 0 is
+ *   SZG_OK and changes nothing.
+ * Overwrites: a tombstoned row may be overwritten and stays dead.  Where the handle keeps row norms or an 8-bit
+ *   sketch, the listed rows' norms are refreshed at once -- bit for bit the norms a single-row overwrite leaves -- and
+ *   their sketches at the next search; more than 4 096 rows overwritten since the last search rebuild the sketch.
+ * Tombstones: *out_dropped (nullable) = the rows that were live before the call and are not afterwards.
+ *   szg_index_tombstone_mask drops every live row whose bit is set in `mask`, a current mask of this handle (a stale
+ *   or foreign one is SZG_E_INVALID, as in a search); the mask stays valid and unchanged.
+ * No call makes a mask or a column stale.
+ * Columns: szg_column_set_rows covers SZG_COL_F64 and SZG_COL_U32.  On a text column it is SZG_E_INVALID (the kind
+ *   does not match): text values keep szg_column_set_str, row by row -- a bulk form for the text heap is out of scope.
+ * Memory: the data travels through the shards' staging blocks, which grow to at most 64 MiB of the caller's data plus
+ *   the encoded rows and 12 bytes per row of a chunk.  A failed device allocation is SZG_E_NOMEM with rows, live bits,
+ *   norms, sketch bookkeeping, column values and the process's device blocks as they were.
+ * A device error (SZG_E_DEVICE) is not covered by "nothing changed": it may leave the update partly applied -- the
+ *   shards before the failing one rewritten, the sketch bookkeeping moved -- as a single-row call that fails half-way.
+ * These are mutations: callers hold the write lock, as for the single-row forms.
+ */
+int szg_index_overwrite_rows(szg_index *ix, const uint64_t *rows, const uint8_t *row_bytes, uint64_t n_rows);
+int szg_index_overwrite_rows_f64(szg_index *ix, const uint64_t *rows, const double *vectors, uint64_t n_rows);
+int szg_index_tombstone_rows(szg_index *ix, const uint64_t *rows, uint64_t n_rows, uint64_t *out_dropped);
+int szg_index_tombstone_mask(szg_index *ix, const szg_mask *mask, uint64_t *out_dropped);
+int szg_column_set_rows(szg_column *c, const uint64_t *rows, const void *values, const uint64_t *present_bits,
+                        uint64_t n_rows);
+
 /*
  * The reference's float64 distance (c.distance, collection.go:596, :812-832) from
  * one query to each listed row, bit-identical to the reference: the gather-by-row
@@ -726,6 +767,19 @@ int szg_debug_option_check(const char *name, int64_t value);
  */
 int szg_debug_reorder_plan(uint64_t n_rows, const uint64_t *live_words, const uint64_t *src_rows, uint64_t n,
                            int n_shards, uint64_t *out_counts);
+
+/*
+ * Test hook, host only: the checks the bulk mutations make on their list before anything changes, and its split over
+ * the shards of a handle of n_rows rows freshly loaded on n_shards shards -- the same code, the same return codes and
+ * error text.  rows[0 .. n): the list, rows[i] - row_base the row; allow_duplicates: 0 = the overwrite and column forms
+ * ("row listed twice"), 1 = the tombstone form.  Every out_ pointer is nullable.  out_counts[n_shards]: the entries
+ * that fall into each shard; out_local[n] / out_source[n]: the shards' lists back to back, shard 0's first, each in
+ * the caller's order -- the shard-local row, and the position i it had in rows[]; out_word_lo / out_word_hi[n_shards]:
+ * the first and last 64-row word of the shard that holds a listed row (lo > hi: none).
+ */
+int szg_debug_bulk_plan(uint64_t n_rows, uint64_t row_base, const uint64_t *rows, uint64_t n, int n_shards,
+                        int allow_duplicates, uint64_t *out_counts, uint64_t *out_local, uint64_t *out_source,
+                        uint64_t *out_word_lo, uint64_t *out_word_hi);
 
 /*
  * Test hooks, host only: the device memory this process's handles, columns and masks own.  Every device block of theirs

@@ -47,6 +47,9 @@ EXPORTS = [
     "szg_column_create_str", "szg_column_append_str", "szg_column_set_str", "szg_column_read_str", "szg_mask_where_str",
     # columns carried across compaction / reorder (added under ABI 4)
     "szg_index_reorder_carry", "szg_index_compact_carry", "szg_column_get_info",
+    # bulk mutations: many rows per call (added under ABI 4)
+    "szg_index_overwrite_rows", "szg_index_overwrite_rows_f64", "szg_index_tombstone_rows", "szg_index_tombstone_mask",
+    "szg_column_set_rows", "szg_debug_bulk_plan",
     # host-only test hook
     "szg_debug_scan_plan", "szg_debug_scan_group", "szg_debug_reorder_plan", "szg_debug_option_check",
     # who owns device memory: the counters and the refusal countdown (added under ABI 4)
@@ -276,6 +279,20 @@ def load():
                                               ctypes.c_int]
         L.szg_column_get_info.restype = ctypes.c_int
         L.szg_column_get_info.argtypes = [vp, ctypes.POINTER(SzgColumnInfo)]
+    if hasattr(L, "szg_index_overwrite_rows"):   # (an older build for an A/B run mutates one row per call)
+        L.szg_index_overwrite_rows.restype = ctypes.c_int
+        L.szg_index_overwrite_rows.argtypes = [vp, u64p, u8p, ctypes.c_uint64]
+        L.szg_index_overwrite_rows_f64.restype = ctypes.c_int
+        L.szg_index_overwrite_rows_f64.argtypes = [vp, u64p, f64p, ctypes.c_uint64]
+        L.szg_index_tombstone_rows.restype = ctypes.c_int
+        L.szg_index_tombstone_rows.argtypes = [vp, u64p, ctypes.c_uint64, u64p]
+        L.szg_index_tombstone_mask.restype = ctypes.c_int
+        L.szg_index_tombstone_mask.argtypes = [vp, vp, u64p]
+        L.szg_column_set_rows.restype = ctypes.c_int
+        L.szg_column_set_rows.argtypes = [vp, u64p, vp, u64p, ctypes.c_uint64]
+        L.szg_debug_bulk_plan.restype = ctypes.c_int
+        L.szg_debug_bulk_plan.argtypes = [ctypes.c_uint64, ctypes.c_uint64, u64p, ctypes.c_uint64, ctypes.c_int, ctypes.c_int,
+                                          u64p, u64p, u64p, u64p, u64p]
     L.szg_comm_unique_id.restype = ctypes.c_int
     L.szg_comm_unique_id.argtypes = [u8p]
     L.szg_comm_create.restype = ctypes.c_int

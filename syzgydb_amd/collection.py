@@ -209,23 +209,40 @@ class Collection:
             self._columns_append(1)
 
     def AddDocuments(self, ids, vectors, metadatas=None):
-        """Bulk ingest (not in the reference; same effect as AddDocument in a loop for new ids)."""
+        """Bulk upsert (not in the reference; the same state as AddDocument in a loop over the entries): new ids are
+        appended by ONE append_vectors in first-seen order, existing ids rewritten by ONE overwrite_vectors -- both
+        quantize and pack on the device.  An id listed twice keeps its last entry."""
         V = np.atleast_2d(np.asarray(vectors, dtype=np.float64))
         if V.shape[1] != self.DimensionCount:
             raise ValueError("vector size does not match the expected number of dimensions")
         ids = [int(i) for i in ids]
         self._version += 1
-        if any(i in self._row_of for i in ids) or len(set(ids)) != len(ids):
-            for j, i in enumerate(ids):
-                self.AddDocument(i, V[j], metadatas[j] if metadatas else b"")
-            return
-        self._index.append_vectors(V)  # quantize + pack on the device (szg_index_append_f64)
+        last, fresh = {}, []   # id -> its last entry; the new ids in first-seen order
         for j, i in enumerate(ids):
+            if i not in last and i not in self._row_of:
+                fresh.append(i)
+            last[i] = j
+
+        def meta(j):
+            return bytes(metadatas[j]) if metadatas else b""
+
+        known = [i for i in last if i in self._row_of]
+        if known:  # WriteRecord of an existing id replaces the record
+            rows = [self._row_of[i] for i in known]
+            self._index.overwrite_vectors(rows, V[[last[i] for i in known]])  # szg_index_overwrite_rows_f64
+            for i, row in zip(known, rows):
+                self._meta[row] = meta(last[i])
+            self._columns_set_rows(rows)
+        if not fresh:
+            return
+        # quantize + pack on the device (szg_index_append_f64)
+        self._index.append_vectors(V if len(fresh) == len(ids) else V[[last[i] for i in fresh]])
+        for i in fresh:
             self._row_of[i] = len(self._id_of)
             self._id_of.append(i)
-            self._meta.append(bytes(metadatas[j]) if metadatas else b"")
+            self._meta.append(meta(last[i]))
             self._note_appended(i)
-        self._columns_append(len(ids))
+        self._columns_append(len(fresh))
 
     def GetDocument(self, id: int) -> Document:
         row = self._row_of.get(int(id))
@@ -256,6 +273,52 @@ class Collection:
             rows = self._index.rows
             if rows - self._index.live_rows > self.auto_compact * rows:
                 self.Compact()
+
+    def _removed(self, ids, rows):
+        """Host bookkeeping of rows that have just been tombstoned, then the auto_compact rule, once."""
+        for i, row in zip(ids, rows):
+            del self._row_of[i]
+            self._id_of[row] = None
+            self._meta[row] = b""
+        self._columns_set_rows(rows)
+        if self.auto_compact is not None:
+            n = self._index.rows
+            if n - self._index.live_rows > self.auto_compact * n:
+                self.Compact()
+
+    def RemoveDocuments(self, ids) -> int:
+        """removeDocument for a list (not in the reference), ONE tombstone_rows: an unknown id raises KeyError before
+        anything changes; an id listed twice counts once.  Returns the documents removed."""
+        ids = list(dict.fromkeys(int(i) for i in ids))
+        if any(i not in self._row_of for i in ids):
+            raise KeyError("record not found")
+        if not ids:
+            return 0
+        rows = [self._row_of[i] for i in ids]
+        self._version += 1
+        dropped = self._index.tombstone_rows(rows)
+        self._removed(ids, rows)
+        return dropped
+
+    def RemoveWhere(self, where, key=None) -> int:
+        """Remove every document the filter accepts (not in the reference): `where` is a where.Expr -- compiled through
+        the columns of the indexed fields like SearchArgs.Where -- or a Filter callable, `key` its cache key.  The
+        verdicts are a mask on the card (the filter cache's, when a Search has made it already) and ONE tombstone_mask
+        applies it there; the dropped rows are read back from the mask's words.  Returns the documents removed."""
+        if not self._row_of:
+            return 0
+        if isinstance(where, _where.Expr):
+            mask = self._where_handle(where)
+        elif callable(where):
+            mask = self._allow_handle(where, key)
+        else:
+            raise TypeError("RemoveWhere takes a where.Expr or a filter callable")
+        bits = np.unpackbits(mask.read().view(np.uint8), bitorder="little")[:len(self._id_of)]
+        rows = [int(r) for r in np.flatnonzero(bits) if self._id_of[int(r)] is not None]
+        self._version += 1
+        dropped = self._index.tombstone_mask(mask)
+        self._removed([self._id_of[r] for r in rows], rows)
+        return dropped
 
     def Compact(self) -> int:
         """Drop the tombstoned rows from the card (not in the reference, whose spanfile reclaims space by itself):
@@ -408,6 +471,21 @@ class Collection:
             v, present = f.value_of(data)
             f.column.set(row, v if present else None)
         self._object_col.set(row, 1 if data is not None else 0)
+
+    def _columns_set_rows(self, rows):
+        """The metadata of `rows` (each listed once) changed: number and string fields, and the hidden object column,
+        take their new values in one set_rows each; a text field's values go row by row."""
+        if not self._fields or not rows:
+            return
+        parsed = [_where.parse_metadata(self._meta[row]) for row in rows]
+        for f in self._fields.values():
+            pairs = [f.value_of(d) for d in parsed]
+            if f.kind == "text":
+                for row, (v, present) in zip(rows, pairs):
+                    f.column.set(row, v if present else None)
+                continue
+            f.column.set_rows(rows, [v for v, _ in pairs], present=np.array([p for _, p in pairs], dtype=bool))
+        self._object_col.set_rows(rows, np.array([d is not None for d in parsed], dtype=np.uint32))
 
     def _leaf_mask(self, e):
         """(mask, can_error) of one leaf through its field's column: mask = the rows where the leaf is true AND the

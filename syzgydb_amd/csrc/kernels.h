@@ -323,6 +323,15 @@ hipError_t launch_repack(int qbits, uint8_t *ref, uint32_t row_bytes, uint8_t *r
 hipError_t launch_gather_rows(const uint8_t *src, RowLayout src_lay, uint8_t *dst, RowLayout dst_lay, uint32_t r16,
                               const uint64_t *list, uint64_t n, uint64_t dst_first_row, hipStream_t stream);
 
+// ---- kernels_bulk.hip: the scatters of the bulk mutations ------------------------------------------------------------
+// Row scatter, the mirror image of the gather: row list[i] of `dst` = row i of `src`, i < n, each side in its own
+// layout.  list is never null and holds no row twice; an entry >= dst_rows is skipped.
+hipError_t launch_scatter_rows(const uint8_t *src, RowLayout src_lay, uint8_t *dst, RowLayout dst_lay, uint32_t r16,
+                               const uint64_t *list, uint64_t n, uint64_t dst_rows, hipStream_t stream);
+// out[list[i]] = in[i], i < n, elements of `elem` = 8 or 4 bytes (column values, row norms); an entry >= out_n is skipped
+hipError_t launch_column_scatter(const void *in, uint32_t elem, const uint64_t *list, uint64_t n, void *out, uint64_t out_n,
+                                 hipStream_t stream);
+
 // Rows [dst_first_row, +n_rows) of the mirror directly in the resident layout: synthetic
 // (src == nullptr, see szg_index_synth; seed_first_row indexes the PRNG stream) or
 // quantized + packed from float64 vectors on the device.

@@ -66,6 +66,16 @@ int szgi::column_complete_check(const szg_index *ix, const szg_column *c)
     return SZG_OK;
 }
 
+// the checks every call but rows / read / destroy makes first
+int szgi::column_check(const szg_column *c)
+{
+    if (c->epoch != c->owner->col_epoch.load()) return stale_column();
+    if (c->parts.size() != c->owner->shards.size()) return stale_column();
+    return SZG_OK;
+}
+
+int szgi::kind_mismatch() { return fail(SZG_E_INVALID, "the column's kind does not match the call"); }
+
 namespace {
 
 // an empty column of `kind` shaped after the handle's shards
@@ -80,14 +90,6 @@ szg_column *column_new(szg_index *ix, int kind)
         c->parts.back().first = sh->first;
     }
     return c;
-}
-
-// the checks every call but rows / read / destroy makes first
-int column_check(const szg_column *c)
-{
-    if (c->epoch != c->owner->col_epoch.load()) return stale_column();
-    if (c->parts.size() != c->owner->shards.size()) return stale_column();
-    return SZG_OK;
 }
 
 // how many more rows each part has room for: what its shard holds beyond it
@@ -212,8 +214,6 @@ int set_present(szg_column::Part &p, uint64_t l, bool there)
     p.present_host[l / 64] = w;
     return SZG_OK;
 }
-
-int kind_mismatch() { return fail(SZG_E_INVALID, "the column's kind does not match the call"); }
 
 // What the szg_mask_where_* calls share: every check on the host, then one launch per shard through `launch(s, w)`,
 // the count and the host copy of the words brought back once.

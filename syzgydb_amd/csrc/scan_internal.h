@@ -14,6 +14,8 @@
 //   scan_column.cpp   resident metadata columns (szg_column): comparisons against constants that write masks
 //   scan_column_carry.cpp  columns carried across a compaction / reorder (column_carry.h: its index arithmetic)
 //   scan_reorder.cpp  compaction and reorder of the resident rows on the device (reorder_plan.h: its host-only checks)
+//   scan_bulk.cpp     bulk mutations: lists of rows overwritten, tombstoned or given column values in one call
+//                     (bulk_plan.h: its host-only checks; kernels_bulk.hip: its scatters)
 //   scan_api.cpp      remaining C entry points (top-k with caller coalescing, distances)
 //
 // Who owns device memory: dev_mem.h.  Every block is held by a DevBuf / PinnedBuf (scratch of the device that is
@@ -686,6 +688,10 @@ inline size_t index_words(uint64_t rows) { return (size_t)((rows + 63) / 64); }
 
 // ---- scan_column.cpp
 int stale_column();  // SZG_E_INVALID, "stale column: ..."
+// the checks every call on a column but rows / read / destroy makes first: made at the handle's column epoch, one part
+// per shard (stale_column otherwise); and SZG_E_INVALID, "the column's kind does not match the call"
+int column_check(const szg_column *c);
+int kind_mismatch();
 // a valid, complete column of ix (SZG_E_INVALID otherwise: another handle's, stale, or short of the handle's rows)
 int column_complete_check(const szg_index *ix, const szg_column *c);
 // room for `need` rows in a part / for `used` bytes in its text heap: a bigger allocation with the old contents carried

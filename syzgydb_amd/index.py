@@ -212,6 +212,21 @@ class ScanColumn:
         check(self._L.szg_column_set(self._live(), int(row), v.ctypes.data_as(ctypes.c_void_p) if v is not None else None),
               "szg_column_set")
 
+    def set_rows(self, rows, values, present=None):
+        """Many rows' values in one call (F64 and U32 columns; a text column raises SzgError, SZG_E_INVALID: its values
+        go through set(), row by row).  values[i] belongs to rows[i]; present: None = every entry, bool per entry or
+        uint64 words -- an absent entry marks its row absent and its value is ignored.  A row out of range or listed
+        twice refuses the whole call."""
+        r = np.ascontiguousarray(rows, dtype=np.uint64).reshape(-1)
+        v = np.ascontiguousarray(values, dtype=self._dtype).reshape(-1)
+        if v.size != r.size:
+            raise ValueError("%d values for %d rows" % (v.size, r.size))
+        keep, pp = self._present_arg(present, r.size)
+        check(self._L.szg_column_set_rows(self._live(), _u64(r) if r.size else None,
+                                          v.ctypes.data_as(ctypes.c_void_p) if v.size else None, pp, r.size),
+              "szg_column_set_rows")
+        del keep
+
     @property
     def rows(self):
         return int(self._L.szg_column_rows(self._live()))
@@ -424,6 +439,43 @@ class ScanIndex:
 
     def tombstone(self, row):
         check(self._L.szg_index_tombstone(self._h, int(row)), "szg_index_tombstone")
+
+    # -- bulk mutations: many rows per call, a constant number of round trips --------
+    def overwrite_rows(self, rows, row_bytes):
+        """overwrite() for a list: row_bytes[i] (reference encoding) replaces row rows[i].  A row out of range or listed
+        twice refuses the whole call (SzgError) and nothing changes."""
+        r = np.ascontiguousarray(rows, dtype=np.uint64).reshape(-1)
+        a, n = self._rows_arg(row_bytes)
+        if n != r.size:
+            raise ValueError("%d rows of bytes for %d rows" % (n, r.size))
+        check(self._L.szg_index_overwrite_rows(self._h, _u64(r) if n else None, _u8(a) if n else None, n),
+              "szg_index_overwrite_rows")
+
+    def overwrite_vectors(self, rows, vectors):
+        """overwrite_vector() for a list: float64 vectors[i], quantized and packed on the device, replaces row rows[i]."""
+        r = np.ascontiguousarray(rows, dtype=np.uint64).reshape(-1)
+        v = np.ascontiguousarray(vectors, dtype=np.float64).reshape(-1, self.dim)
+        if v.shape[0] != r.size:
+            raise ValueError("%d vectors for %d rows" % (v.shape[0], r.size))
+        check(self._L.szg_index_overwrite_rows_f64(self._h, _u64(r) if r.size else None, _f64(v) if r.size else None, r.size),
+              "szg_index_overwrite_rows_f64")
+
+    def tombstone_rows(self, rows):
+        """tombstone() for a list (duplicates and dead rows allowed): the rows that were live and no longer are."""
+        r = np.ascontiguousarray(rows, dtype=np.uint64).reshape(-1)
+        dropped = ctypes.c_uint64(0)
+        check(self._L.szg_index_tombstone_rows(self._h, _u64(r) if r.size else None, r.size, ctypes.byref(dropped)),
+              "szg_index_tombstone_rows")
+        return int(dropped.value)
+
+    def tombstone_mask(self, mask):
+        """Tombstone every live row a current ScanMask of this index allows ("delete where"); the mask stays valid.
+        Returns the rows dropped."""
+        if not isinstance(mask, ScanMask):
+            raise TypeError("mask is a ScanMask")
+        dropped = ctypes.c_uint64(0)
+        check(self._L.szg_index_tombstone_mask(self._h, mask._live(), ctypes.byref(dropped)), "szg_index_tombstone_mask")
+        return int(dropped.value)
 
     def synth(self, n_rows, seed, first_row=0):
         check(self._L.szg_index_synth(self._h, int(n_rows), int(seed), int(first_row)),
@@ -789,6 +841,29 @@ def reorder_plan(n_rows, src_rows, n_shards=1, live=None):
                                    _u64(r) if r.size else None, r.size, int(n_shards), _u64(counts)),
           "szg_debug_reorder_plan")
     return [int(c) for c in counts]
+
+
+def bulk_plan(n_rows, rows, n_shards=1, row_base=0, allow_duplicates=False):
+    """Host-only test hook (no device needed): the checks the bulk mutations make on their list -- SzgError with the same
+    code and text -- and its split over the shards of n_rows freshly loaded rows.  Returns one dict per shard: local
+    (the shard-local rows, in the caller's order), source (the position each had in `rows`), and words, the (first,
+    last) 64-row word of the shard that holds a listed row, None for a shard without one."""
+    L = _lib.load()
+    r = np.ascontiguousarray(rows, dtype=np.uint64).reshape(-1)
+    S = int(n_shards)
+    counts, lo, hi = (np.zeros(max(S, 0), dtype=np.uint64) for _ in range(3))
+    local, source = np.zeros(r.size, dtype=np.uint64), np.zeros(r.size, dtype=np.uint64)
+    check(L.szg_debug_bulk_plan(int(n_rows), int(row_base), _u64(r) if r.size else None, r.size, S, int(bool(allow_duplicates)),
+                                _u64(counts) if S > 0 else None, _u64(local) if r.size else None,
+                                _u64(source) if r.size else None, _u64(lo) if S > 0 else None, _u64(hi) if S > 0 else None),
+          "szg_debug_bulk_plan")
+    out, at = [], 0
+    for s in range(S):
+        c = int(counts[s])
+        out.append({"local": [int(x) for x in local[at:at + c]], "source": [int(x) for x in source[at:at + c]],
+                    "words": (int(lo[s]), int(hi[s])) if c else None})
+        at += c
+    return out
 
 
 def scan_plan(dim, quant_bits, n_rows, kp=10, collect=False, masked=False, cu_count=0):
