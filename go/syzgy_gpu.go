@@ -291,6 +291,22 @@ func columnSetRows(col *C.szg_column, rows []uint64, values unsafe.Pointer, pres
 	return C.szg_column_set_rows(col, u64ptr(rows), values, u64ptr(present), C.uint64_t(len(rows))) == C.SZG_OK
 }
 
+// columnWhereDFA is szg_mask_where_dfa: the rows of a text column whose bytes a byte automaton accepts, as a mask.
+// The Go side owns the pattern language: a MATCHES leaf (query/compiler.go:420-431) compiles its pattern with
+// regexp/syntax (syntax.Parse(pattern, syntax.Perl), Simplify, syntax.Compile), determinises the program over bytes
+// with the unanchored search and the assertions built in -- the construction syzgydb_amd/regex_dfa.py documents and
+// tests -- and hands over the table: classOf has 256 entries, next nStates * nClasses, acceptBits one bit per state.
+// The tables must live in C memory or be pinned (runtime.Pinner) for the call: the struct holds pointers to them.
+// Like the rest of this file it has never been compiled.
+func columnWhereDFA(col *C.szg_column, nStates, nClasses, start uint32, classOf *C.uint8_t, next *C.uint16_t,
+	acceptBits *C.uint64_t, base *C.szg_mask) (*C.szg_mask, bool) {
+	dfa := C.szg_dfa{n_states: C.uint32_t(nStates), n_classes: C.uint32_t(nClasses), start: C.uint32_t(start),
+		class_of: classOf, next: next, accept_bits: acceptBits}
+	var out *C.szg_mask
+	ok := C.szg_mask_where_dfa(col, &dfa, base, &out) == C.SZG_OK
+	return out, ok
+}
+
 // removeBulk mirrors RemoveDocuments: removeDocument for a list of ids with one szg_index_tombstone_rows.  Ids the
 // mirror does not hold are skipped, as remove skips them; returns the rows dropped.
 func (m *gpuMirror) removeBulk(ids []uint64) uint64 {

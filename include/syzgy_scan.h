@@ -294,6 +294,18 @@ int szg_index_compact(szg_index *ix, uint64_t *out_new_of_old, uint64_t *out_row
  *   SZG_E_UNSUPPORTED, a NULL constant with len > 0 SZG_E_INVALID.  The empty constant is legal: the three string
  *   operators then hold for every present row, the comparisons run against "".  One kernel per shard, a lane per
  *   row: a match lies wholly inside its row.
+ * Byte automata (szg_mask_where_dfa, text columns): bit r = present(r) && accept[the state after feeding ALL bytes of
+ *   row r, in order, from `start`] (&& base's bit r); a row of length 0 gives accept[start].  The library knows nothing
+ *   of regular expressions: the caller compiles its pattern language -- anchors, "match anywhere" and all -- into the
+ *   table (syzgydb_amd/regex_dfa.py does so for the reference's MATCHES operator, query/compiler.go:420-431).  A byte b
+ *   takes state s to next[s * n_classes + class_of[b]]; bit s of accept_bits says whether s accepts.  The tables are
+ *   copied; everything said above of szg_mask_where_* holds unchanged.  Refusals, all before anything is allocated or
+ *   launched: a NULL dfa or a NULL array is SZG_E_INVALID; n_states or n_classes of 0, n_classes > 256, a start, a
+ *   class_of entry or a next entry out of range are SZG_E_INVALID with "dfa" in szg_last_error -- the table is checked
+ *   in full, the kernel never indexes past it; n_states > SZG_DFA_STATES_MAX or n_states * n_classes >
+ *   SZG_DFA_TABLE_MAX is SZG_E_UNSUPPORTED.  A state whose every transition is to itself is ABSORBING: the library
+ *   finds these, and a lane that reaches one stops reading its row ("already matched", "can no longer match") -- what
+ *   makes an unanchored pattern cheap on long rows.  One kernel per shard, a lane per row.
  */
 typedef struct szg_column szg_column;
 #define SZG_COL_F64 0   /* values: double */
@@ -309,6 +321,16 @@ typedef struct szg_column szg_column;
 #define SZG_STR_ENDS_WITH 7
 #define SZG_STR_CONTAINS 8
 #define SZG_STR_PATTERN_MAX 256 /* bytes of a constant */
+#define SZG_DFA_STATES_MAX 32768u        /* states are uint16; the library keeps bit 15 of a staged entry for itself */
+#define SZG_DFA_TABLE_MAX  (1u << 20)    /* n_states * n_classes entries */
+typedef struct szg_dfa {
+    uint32_t n_states;            /* 1 .. SZG_DFA_STATES_MAX */
+    uint32_t n_classes;           /* 1 .. 256 */
+    uint32_t start;               /* < n_states */
+    const uint8_t  *class_of;     /* 256 entries, each < n_classes: the byte's column in `next` */
+    const uint16_t *next;         /* n_states * n_classes, row-major by state, each < n_states */
+    const uint64_t *accept_bits;  /* ceil(n_states / 64) words */
+} szg_dfa;
 
 int szg_column_create(szg_index *ix, int kind, const void *values, const uint64_t *present_bits,
                       uint64_t n_rows, szg_column **out);
@@ -350,6 +372,8 @@ int szg_mask_where_u32(const szg_column *c, const uint64_t *code_bits, uint32_t 
 /* text columns: present && value op constant[0 .. len), op SZG_CMP_* or SZG_STR_* */
 int szg_mask_where_str(const szg_column *c, int op, const uint8_t *constant, uint32_t len,
                        const szg_mask *base, szg_mask **out);
+/* text columns: present && the automaton accepts the row's bytes (see "Byte automata" above) */
+int szg_mask_where_dfa(const szg_column *c, const szg_dfa *dfa, const szg_mask *base, szg_mask **out);
 /* the present bits (every kind) */
 int szg_mask_where_present(const szg_column *c, const szg_mask *base, szg_mask **out);
 

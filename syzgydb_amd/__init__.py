@@ -8,11 +8,12 @@ from .index import ScanIndex, ScanMask, ScanColumn, pack_allow_bits, f64_probe, 
 from .collection import (Collection, CollectionOptions, Document, SearchArgs, SearchResult,  # noqa: F401
                          SearchResults, Euclidean, Cosine)
 from . import codec  # noqa: F401
+from . import regex_dfa  # noqa: F401
 from . import where  # noqa: F401
 from .where import Field  # noqa: F401
 from . import lsh  # noqa: F401
 from .pager import SpanfilePager  # noqa: F401
 
-__all__ = ["ScanIndex", "ScanMask", "ScanColumn", "Field", "where", "Collection", "CollectionOptions", "Document", "SearchArgs",
+__all__ = ["ScanIndex", "ScanMask", "ScanColumn", "Field", "where", "regex_dfa", "Collection", "CollectionOptions", "Document", "SearchArgs",
            "SearchResult", "SearchResults", "Euclidean", "Cosine", "codec", "SzgError",
            "pack_allow_bits", "f64_probe", "scan_plan", "scan_group_plan", "reorder_plan", "bulk_plan", "option_check", "SpanfilePager", "lsh", "SZG_COSINE", "SZG_EUCLIDEAN", "LIB_PATH"]

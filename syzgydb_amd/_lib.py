@@ -45,6 +45,8 @@ EXPORTS = [
     "szg_column_destroy", "szg_mask_where_f64", "szg_mask_where_in_f64", "szg_mask_where_u32", "szg_mask_where_present",
     # text columns (added under ABI 4)
     "szg_column_create_str", "szg_column_append_str", "szg_column_set_str", "szg_column_read_str", "szg_mask_where_str",
+    # byte automata over text columns (added under ABI 4)
+    "szg_mask_where_dfa",
     # columns carried across compaction / reorder (added under ABI 4)
     "szg_index_reorder_carry", "szg_index_compact_carry", "szg_column_get_info",
     # bulk mutations: many rows per call (added under ABI 4)
@@ -60,6 +62,8 @@ SZG_COL_F64, SZG_COL_U32, SZG_COL_STR = 0, 1, 2
 SZG_CMP_EQ, SZG_CMP_NE, SZG_CMP_LT, SZG_CMP_LE, SZG_CMP_GT, SZG_CMP_GE = range(6)
 SZG_STR_STARTS_WITH, SZG_STR_ENDS_WITH, SZG_STR_CONTAINS = 6, 7, 8   # szg_mask_where_str only
 SZG_STR_PATTERN_MAX = 256
+SZG_DFA_STATES_MAX = 32768     # szg_mask_where_dfa: states of an automaton
+SZG_DFA_TABLE_MAX = 1 << 20    # ... and n_states * n_classes entries of its table
 SZG_COMM_ID_BYTES = 128
 # int (*szg_allgather_fn)(void *user, const void *send, void *recv, uint64_t bytes_per_rank)
 ALLGATHER_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64)
@@ -113,6 +117,12 @@ class SzgScanPlan(ctypes.Structure):
 class SzgColumnInfo(ctypes.Structure):
     _fields_ = [("kind", ctypes.c_int32), ("rows", ctypes.c_uint64), ("device_bytes", ctypes.c_uint64),
                 ("heap_used", ctypes.c_uint64), ("heap_capacity", ctypes.c_uint64)]
+
+
+class SzgDfa(ctypes.Structure):
+    _fields_ = [("n_states", ctypes.c_uint32), ("n_classes", ctypes.c_uint32), ("start", ctypes.c_uint32),
+                ("class_of", ctypes.POINTER(ctypes.c_uint8)), ("next", ctypes.POINTER(ctypes.c_uint16)),
+                ("accept_bits", ctypes.POINTER(ctypes.c_uint64))]
 
 
 class SzgMaskStats(ctypes.Structure):
@@ -270,6 +280,9 @@ def load():
         L.szg_column_read_str.argtypes = [vp, ctypes.c_uint64, ctypes.c_uint64, u64p, u8p, ctypes.c_uint64, u64p]
         L.szg_mask_where_str.restype = ctypes.c_int
         L.szg_mask_where_str.argtypes = [vp, ctypes.c_int, u8p, ctypes.c_uint32, vp, ctypes.POINTER(vp)]
+    if hasattr(L, "szg_mask_where_dfa"):   # (an older build for an A/B run walks no automata)
+        L.szg_mask_where_dfa.restype = ctypes.c_int
+        L.szg_mask_where_dfa.argtypes = [vp, ctypes.POINTER(SzgDfa), vp, ctypes.POINTER(vp)]
     if hasattr(L, "szg_index_reorder_carry"):   # (an older build for an A/B run carries no columns)
         L.szg_index_reorder_carry.restype = ctypes.c_int
         L.szg_index_reorder_carry.argtypes = [vp, u64p, ctypes.c_uint64, ctypes.POINTER(vp), ctypes.c_int,

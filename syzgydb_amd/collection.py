@@ -16,7 +16,7 @@ from typing import Callable, List, Optional
 
 import numpy as np
 
-from . import _lib, codec, where as _where
+from . import _lib, codec, regex_dfa as _regex_dfa, where as _where
 from .index import ScanIndex, pack_allow_bits
 
 Euclidean = 0  # collection.go:186-189
@@ -402,8 +402,8 @@ class Collection:
         "string" suits a field with few distinct values (a brand, a status): one 4-byte code per row of an append-only
         dictionary kept here, and a filter is evaluated on the host once per DISTINCT value.  "text" suits a field
         whose values are mostly distinct (an email, a name, an id): the strings' bytes live on the card, with no
-        dictionary, and the card compares them (constants of up to 256 bytes, IN-lists of up to 16).  The resident
-        metadata is parsed once, now; from then on AddDocument(s) append to the column, UpdateDocument sets the row,
+        dictionary, and the card compares them (constants of up to 256 bytes, IN-lists of up to 16, and MATCHES
+        patterns walked as a byte automaton).  The resident metadata is parsed once, now; from then on AddDocument(s) append to the column, UpdateDocument sets the row,
         and Compact() and the re-sort carry it along on the card.  Search with SearchArgs.Where then compares the field on the card."""
         if kind not in ("number", "string", "text"):
             raise ValueError('kind is "number", "string" or "text"')
@@ -496,6 +496,16 @@ class Collection:
             return None
         want = float if f.kind == "number" else str
         col = f.column
+        if isinstance(e, _where.Matches):
+            if f.kind == "string":   # once per dictionary entry, like a string operator
+                return col.codes([e.test(s) for s in f.codes]), True
+            if f.kind != "text":
+                return None
+            try:   # the pattern's whole table on the card; one beyond the kernel's limits: the host answers
+                dfa = e.matcher.dfa()
+            except _regex_dfa.DfaTooLarge:
+                return None
+            return col.dfa(dfa), True
         if f.kind == "text":
             return self._text_leaf_mask(e, col)
         if isinstance(e, _where.Cmp):

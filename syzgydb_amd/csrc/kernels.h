@@ -396,6 +396,12 @@ hipError_t launch_column_present(const ColumnWhere &w, hipStream_t stream);
 // len <= SZG_STR_PATTERN_MAX
 hipError_t launch_column_str(const uint64_t *refs, const uint8_t *heap, int op, const uint32_t *constant, uint32_t len,
                              const ColumnWhere &w, hipStream_t stream);
+// a byte automaton over each row of a text column (column_dfa.h): image = the class map and the staged table as
+// dfa_stage makes them, accept_bits = ceil(n_states / 64) words, both on the device and checked by dfa_validate on the
+// host.  A table of at most kDfaLdsEntries entries is walked in LDS, a larger one in global memory.
+hipError_t launch_column_dfa(const uint64_t *refs, const uint8_t *heap, const uint32_t *image, const uint64_t *accept_bits,
+                             uint32_t n_states, uint32_t n_classes, uint32_t start_staged, const ColumnWhere &w,
+                             hipStream_t stream);
 
 // ---- kernels_column_carry.hip: columns carried across a compaction / reorder, ONE part per launch --------------------
 // out[at[i]] = values[list[i]], i < n, elements of `elem` = 8 or 4 bytes; at null: out[i]; list null: values[i]

@@ -5,9 +5,11 @@
 // One wave step covers 128 rows = one pair: lane l holds elements base + l and base + 64 + l (two contiguous wave loads),
 // two ballots give the pair's words, lane 0 stores them with one 16-byte store.  kSteps steps of a wave are loaded
 // before the first is used.  No element at a position >= n_rows is loaded.  Plain C++ and vector memory operations only.
-// A text column's element is a row's 8-byte reference into a byte heap that the predicate then reads (column_str.h).
+// A text column's element is a row's 8-byte reference into a byte heap that the predicate then reads (column_str.h;
+// column_dfa.h for the walk of a byte automaton).
 #include "kernels.h"
 #include "column_str.h"
+#include "column_dfa.h"
 
 namespace szg {
 
@@ -111,6 +113,41 @@ struct StrWhere {
     }
 };
 
+// a text column's row through a byte automaton (column_dfa.h has the walk and the image): the block copies the class
+// map -- and, kLdsTable, the staged table of at most kDfaLdsEntries entries -- into dynamic LDS, whose size the launch
+// passes; a larger table is walked where it lies, in global memory, with plain cached loads.  Each lane then reads its
+// own row's bytes with aligned dword loads until they end or an absorbing state is met; the accept bit of the state it
+// ends in is one more global load.  The host has checked every entry of the tables: no index formed here leaves them.
+template <bool kLdsTable>
+struct DfaWhere {
+    using T = uint64_t;   // {uint32 start, uint32 len}, little-endian
+    static constexpr bool kLoads = true;
+    StrWhere::Heap heap;
+    const uint32_t *image;    // device: dfa_image_dwords() dwords
+    const uint64_t *accept;   // device: ceil(n_states / 64) words
+    uint32_t n_entries, n_classes, start;   // (start: staged)
+    const uint8_t *class_of;
+    const uint16_t *table;
+    __device__ void init()
+    {
+        extern __shared__ uint32_t dfa_lds[];
+        const uint32_t n = 64 + (kLdsTable ? (n_entries + 1) / 2 : 0);
+        for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) dfa_lds[i] = image[i];
+        __syncthreads();
+        class_of = reinterpret_cast<const uint8_t *>(dfa_lds);
+        table = reinterpret_cast<const uint16_t *>(kLdsTable ? dfa_lds + 64 : image + 64);
+    }
+    __device__ bool operator()(uint64_t ref) const
+    {
+        const uint8_t *cls = class_of;
+        const uint16_t *tab = table;
+        const uint32_t s = szgi::dfa_walk(
+            heap, (uint32_t)ref, (uint32_t)(ref >> 32), [cls](uint32_t b) -> uint32_t { return cls[b]; },
+            [tab](uint32_t i) -> uint32_t { return tab[i]; }, n_classes, start);
+        return szgi::dfa_accepts(accept, s);
+    }
+};
+
 // the bits of word w that stand for rows < n_rows
 __device__ __forceinline__ uint64_t valid_bits(uint64_t w, uint64_t n_rows)
 {
@@ -177,14 +214,16 @@ __global__ __launch_bounds__(256) void column_where_kernel(Pred pred, const type
     }
 }
 
+// lds: bytes of dynamic LDS the predicate's init() fills
 template <class Pred>
-hipError_t launch_where(const Pred &pred, const typename Pred::T *values, const ColumnWhere &w, hipStream_t stream)
+hipError_t launch_where(const Pred &pred, const typename Pred::T *values, const ColumnWhere &w, hipStream_t stream,
+                        size_t lds = 0)
 {
     if (w.n_pairs == 0) return hipSuccess;
     if (w.n_rows > w.n_pairs * 128 || !w.out || !w.count) return hipErrorInvalidValue;
     const uint64_t blocks = (w.n_pairs + 4 * kSteps - 1) / (4 * kSteps);   // 4 waves x kSteps pairs per block and trip
     const unsigned grid = (unsigned)(blocks < 1 ? 1 : (blocks > 4096 ? 4096 : blocks));
-    hipLaunchKernelGGL(column_where_kernel<Pred>, dim3(grid), dim3(256), 0, stream, pred, values,
+    hipLaunchKernelGGL(column_where_kernel<Pred>, dim3(grid), dim3(256), lds, stream, pred, values,
                        reinterpret_cast<const ulonglong2 *>(w.present), reinterpret_cast<const ulonglong2 *>(w.base),
                        reinterpret_cast<ulonglong2 *>(w.out), w.n_pairs, w.n_rows,
                        reinterpret_cast<unsigned long long *>(w.count));
@@ -221,6 +260,22 @@ hipError_t launch_column_str(const uint64_t *refs, const uint8_t *heap, int op, 
         ((!refs || !heap) && w.n_pairs))
         return hipErrorInvalidValue;
     return launch_where(StrWhere{op, {reinterpret_cast<const uint32_t *>(heap)}, constant, len, nullptr}, refs, w, stream);
+}
+
+hipError_t launch_column_dfa(const uint64_t *refs, const uint8_t *heap, const uint32_t *image, const uint64_t *accept_bits,
+                             uint32_t n_states, uint32_t n_classes, uint32_t start_staged, const ColumnWhere &w,
+                             hipStream_t stream)
+{
+    const uint64_t n_entries = (uint64_t)n_states * n_classes;
+    if (n_states == 0 || n_states > szgi::kDfaStatesMax || n_classes == 0 || n_classes > 256 || n_entries > szgi::kDfaTableMax ||
+        (start_staged & (szgi::kDfaStop - 1)) >= n_states || !image || !accept_bits || ((!refs || !heap) && w.n_pairs))
+        return hipErrorInvalidValue;
+    const StrWhere::Heap h{reinterpret_cast<const uint32_t *>(heap)};
+    if (n_entries <= szgi::kDfaLdsEntries)   // the class map and the table, an odd count of entries rounded up to a dword
+        return launch_where(DfaWhere<true>{h, image, accept_bits, (uint32_t)n_entries, n_classes, start_staged, nullptr, nullptr},
+                            refs, w, stream, 4 * szgi::dfa_image_dwords(n_states, n_classes));
+    return launch_where(DfaWhere<false>{h, image, accept_bits, (uint32_t)n_entries, n_classes, start_staged, nullptr, nullptr},
+                        refs, w, stream, 256);
 }
 
 hipError_t launch_column_present(const ColumnWhere &w, hipStream_t stream)

@@ -11,6 +11,7 @@
 #include "scan_internal.h"
 #include "column_bits.h"
 #include "column_str.h"
+#include "column_dfa.h"
 
 using namespace szgi;
 
@@ -529,6 +530,35 @@ int szg_mask_where_str(const szg_column *c, int op, const uint8_t *constant, uin
         if (int rc = upload_small(&k, dwords.data(), dwords.size())) return rc;
         HIPCHK(szg::launch_column_str(c->parts[s].values_as<const uint64_t>(), c->parts[s].heap, op, k, len, w,
                                       nullptr));
+        HIPCHK(hipStreamSynchronize(nullptr));
+        return SZG_OK;
+    });
+    SZG_CATCH
+}
+
+int szg_mask_where_dfa(const szg_column *c, const szg_dfa *dfa, const szg_mask *base, szg_mask **out)
+{
+    SZG_TRY
+    if (!dfa) return fail(SZG_E_INVALID, "null argument");
+    switch (dfa_validate(dfa->n_states, dfa->n_classes, dfa->start, dfa->class_of, dfa->next, dfa->accept_bits)) {
+    case kDfaOk: break;
+    case kDfaNull: return fail(SZG_E_INVALID, "null argument");
+    case kDfaCounts: return fail(SZG_E_INVALID, "dfa: 1 or more states and 1 to 256 classes");
+    case kDfaTooLarge: return fail(SZG_E_UNSUPPORTED, "dfa: at most 32768 states and 2^20 table entries");
+    case kDfaStart: return fail(SZG_E_INVALID, "dfa: the start state is out of range");
+    case kDfaClass: return fail(SZG_E_INVALID, "dfa: a class_of entry is out of range");
+    default: return fail(SZG_E_INVALID, "dfa: a next entry is out of range");
+    }
+    if (!c || !out) return fail(SZG_E_INVALID, "null argument");
+    uint32_t start = 0;
+    const std::vector<uint32_t> image = dfa_stage(dfa->n_states, dfa->n_classes, dfa->start, dfa->class_of, dfa->next, &start);
+    return mask_where(c, SZG_COL_STR, base, out, [&](size_t s, const szg::ColumnWhere &w) -> int {
+        DevBuf<uint32_t> table;   // (freed after the launch: mask_where's copies wait for the kernel)
+        DevBuf<uint64_t> accept;
+        if (int rc = upload_small(&table, image.data(), image.size())) return rc;
+        if (int rc = upload_small(&accept, dfa->accept_bits, index_words(dfa->n_states))) return rc;
+        HIPCHK(szg::launch_column_dfa(c->parts[s].values_as<const uint64_t>(), c->parts[s].heap, table, accept,
+                                      dfa->n_states, dfa->n_classes, start, w, nullptr));
         HIPCHK(hipStreamSynchronize(nullptr));
         return SZG_OK;
     });

@@ -12,6 +12,8 @@
 //   scan_comm.cpp     one-process-per-GPU exchange (RCCL all-gather + merge)
 //   scan_mask.cpp     device-resident filter masks (szg_mask) and the searches that take them
 //   scan_column.cpp   resident metadata columns (szg_column): comparisons against constants that write masks
+//                     (column_str.h: the text columns' predicate and heap sizes; column_dfa.h: the byte automaton of
+//                     szg_mask_where_dfa -- its walk, the validation of a caller's tables, the staged table)
 //   scan_column_carry.cpp  columns carried across a compaction / reorder (column_carry.h: its index arithmetic)
 //   scan_reorder.cpp  compaction and reorder of the resident rows on the device (reorder_plan.h: its host-only checks)
 //   scan_bulk.cpp     bulk mutations: lists of rows overwritten, tombstoned or given column values in one call

@@ -10,7 +10,7 @@ import weakref
 
 import numpy as np
 
-from . import _lib
+from . import _lib, regex_dfa
 from ._lib import (SZG_COSINE, SZG_EUCLIDEAN, SzgColumnInfo, SzgError, SzgMaskStats, SzgScanPlan, SzgStats,  # noqa: F401
                    check)
 from .where import _bytes
@@ -299,6 +299,26 @@ class ScanColumn:
 
     def contains(self, constant, base=None):
         return self._where_str(_lib.SZG_STR_CONTAINS, constant, base)
+
+    def dfa(self, dfa, base=None):
+        """Text columns: rows that are present and whose bytes -- all of them, from dfa.start -- end in an accepting
+        state of the byte automaton, & base.  dfa: a regex_dfa.Dfa (regex_dfa.compile, regex_dfa.literal_set) or anything
+        with its class_of / next / accept / start; the library checks the table in full before it launches."""
+        class_of = np.ascontiguousarray(dfa.class_of, dtype=np.uint8).reshape(-1)
+        table = np.ascontiguousarray(dfa.next, dtype=np.uint16)
+        accept = np.asarray(dfa.accept, dtype=bool).reshape(-1)
+        if class_of.size != 256 or table.ndim != 2 or table.shape[0] != accept.size:
+            raise ValueError("a dfa has class_of[256], next[n_states, n_classes] and accept[n_states]")
+        bits = pack_allow_bits(accept)[0] if accept.size else np.zeros(1, dtype=np.uint64)
+        arg = _lib.SzgDfa(table.shape[0], table.shape[1], int(dfa.start), _u8(class_of),
+                          table.ctypes.data_as(ctypes.POINTER(ctypes.c_uint16)), _u64(bits))
+        return self._mask(self._L.szg_mask_where_dfa, "szg_mask_where_dfa", ctypes.byref(arg), base=base)
+
+    def matches(self, pattern, base=None):
+        """Text columns: rows that are present and in which the regular expression matches (Go's regexp.MatchString,
+        the subset of regex_dfa), & base.  ValueError for a pattern outside the subset, regex_dfa.DfaTooLarge for one
+        whose table exceeds the kernel's limits."""
+        return self.dfa(regex_dfa.compile(pattern), base=base)
 
     def present(self, base=None):
         """The present rows, & base."""

@@ -21,6 +21,11 @@ indexed, and the yardstick the device path is tested against.  It restates the r
     error (:321, :290-293, :306-309).
   * `IN` is DeepEqual against any list item (compiler.go:377-391), `NOT IN` its negation (:208-213); neither errors.
   * STARTS_WITH, ENDS_WITH and CONTAINS need two strings, otherwise an error (compiler.go:393-418).
+  * MATCHES needs two strings as well, otherwise an error, and is regexp.MatchString(pattern, value)
+    (compiler.go:220, :420-431): an unanchored search.  Deviation: the pattern is compiled here, when the expression
+    is built (regex_dfa.py), and one outside that module's subset of RE2 -- flags such as (?i), \\b, \\p{..}, \\x,
+    named groups -- or one RE2 itself rejects raises ValueError there.  The reference would evaluate the former and
+    fail every row on the latter; for those, SearchArgs.Filter remains the route.
   * An error ANYWHERE makes the row fail: both operands of AND and of OR are evaluated before the operator is applied
     (compiler.go:32-45), so `a OR b` fails when b errors even if a is true, and NOT of an error is an error
     (CreateFilterFunction turns the error into false, compiler.go:485-488).
@@ -28,11 +33,13 @@ indexed, and the yardstick the device path is tested against.  It restates the r
 Hence on the device: result = V(expr) & valid_docs & the conjunction of present(field) over every leaf that can error,
 where V is plain mask algebra over the leaves (collection.py).
 
-Out of scope: MATCHES, LENGTH, ANY / ALL, nested paths, EXISTS / DOES NOT EXIST.  The reference's lexer has no
+Out of scope: LENGTH, ANY / ALL, nested paths, EXISTS / DOES NOT EXIST.  The reference's lexer has no
 negative number literal (query/lexer.go:156): text() writes one as `-5`, which only this module's parse() reads back.
 """
 import json
 import math
+
+from . import regex_dfa
 
 __all__ = ["Field", "Expr", "parse", "parse_metadata"]
 
@@ -256,6 +263,30 @@ class StrOp(Expr):
         return self.test(_value(data, self.field))
 
 
+class Matches(Expr):
+    """field MATCHES "pattern": Go's regexp.MatchString on a string value (the subset of regex_dfa)."""
+
+    def __init__(self, field, pattern):
+        if not isinstance(pattern, str):
+            raise TypeError("MATCHES takes a string constant")
+        self.field, self.pattern = field, pattern
+        self.matcher = regex_dfa.matcher(pattern)   # ValueError: outside the subset, or not a regular expression
+
+    def text(self):
+        return "%s MATCHES %s" % (self.field, _string_text(self.pattern))
+
+    def fields(self):
+        return {self.field}
+
+    def test(self, v):
+        if not isinstance(v, str):
+            raise _Error("MATCHES requires string operands")
+        return self.matcher.match(_bytes(v))
+
+    def _eval(self, data):
+        return self.test(_value(data, self.field))
+
+
 class And(Expr):
     def __init__(self, a, b):
         self.a, self.b = a, b
@@ -343,10 +374,13 @@ class Field:
     def contains(self, s):
         return StrOp(self.name, "CONTAINS", s)
 
+    def matches(self, pattern):
+        return Matches(self.name, pattern)
+
 
 # ---- text -> tree, for the subset text() writes (query/lexer.go, query/parser.go: OR < AND < comparison < NOT) --------
 
-_KEYWORDS = ("AND", "OR", "NOT", "IN") + _STRING_OPS
+_KEYWORDS = ("AND", "OR", "NOT", "IN", "MATCHES") + _STRING_OPS
 
 
 def _tokens(text):
@@ -449,6 +483,8 @@ class _Parser:
             return Cmp(name, what, self.constant())
         if kind == "kw" and what in _STRING_OPS:
             return StrOp(name, what, self.take("str")[1])
+        if (kind, what) == ("kw", "MATCHES"):
+            return Matches(name, self.take("str")[1])
         negate = (kind, what) == ("kw", "NOT")
         if negate:
             kind, what = self.take()
