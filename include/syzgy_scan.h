@@ -817,6 +817,67 @@ int szg_debug_bulk_plan(uint64_t n_rows, uint64_t row_base, const uint64_t *rows
 int szg_debug_device_memory(uint64_t *out_blocks, uint64_t *out_bytes);
 int szg_debug_refuse_device_alloc(int64_t nth);
 
+/*
+ * Test hook: the certificate trace.  Every answer is exact because of a chain of bounds (a sweep's float32 key is
+ * within key_eps of the real-number key; every row a pass left out has a real-number key at or above the bound the
+ * host derives; a collect sweep returns every row under its threshold; the sketch pre-pass's triangle inequality).
+ * With the trace on, a handle keeps what each pass handed to certification -- the values the code used -- so that a
+ * test can check each bound against float64, row by row.
+ *
+ *   szg_debug_trace_certificates(ix, on)   per handle, off by default; switching it on (or off) clears what was kept.
+ *                                          Off, a settled query pays one branch and nothing is allocated.
+ *   szg_debug_certificates(...)            the records of the calls made since, in the two-call style: with records ==
+ *                                          NULL or entries == NULL only the three counts are written; with buffers at
+ *                                          least as large as the counts the records are copied out and the trace is
+ *                                          emptied (SZG_E_TRUNCATED, nothing copied or cleared, when either is smaller).
+ *                                          *out_dropped: records that did not fit the handle's caps (2^18 records,
+ *                                          2^23 entries) since the trace was switched on; such a record is dropped whole, before its
+ *                                          entries are gathered (the bound covers the temporary copies too).
+ *
+ * One record per settled query per pass; its entries are entries[first_entry .. first_entry + n_entries).  A collect
+ * pass run for one query on its own (escalation, a radius query swept again) writes one record per shard; rows
+ * [row_lo, row_hi) are the rows the record speaks for.  Safe beside finish_thread and coalesce (the trace has its own lock).
+ */
+#define SZG_CERT_TOPK 0          /* first top-k pass: keys = ListKeys of the pass */
+#define SZG_CERT_SKETCH 1        /* sketch pre-pass (recorded on the float32 handle) */
+#define SZG_CERT_ESCALATION 2    /* the collect sweep of a query whose first pass was not certified */
+#define SZG_CERT_RADIUS_SINGLE 3 /* radius collect, one sweep per query */
+#define SZG_CERT_RADIUS_SHARED 4 /* radius collect, one shared sweep per batch */
+#define SZG_CERT_KEYS_SINGLE 0
+#define SZG_CERT_KEYS_SHARED_INT8 1
+#define SZG_CERT_KEYS_SHARED_BF16 2
+#define SZG_CERT_KEYS_BF16_BAND 3
+#define SZG_CERT_KEYS_BF16_RESCORED 4
+#define SZG_CERT_ENTRY_NO_KEY 1u /* entry flag: a row re-ranked beside the lists (sketch: first-k / unsketched rows) */
+typedef struct szg_cert_record {
+    int32_t query;       /* index of the query in its call */
+    int32_t pass;        /* SZG_CERT_* */
+    int32_t keys;        /* top-k and sketch passes: SZG_CERT_KEYS_* (which arithmetic made the list keys); else -1 */
+    int32_t sweep;       /* the sweep that ran: 0 one per query, 1 shared on the int8 cores, 2 shared on the bfloat16 cores */
+    int32_t certified;   /* top-k: the first pass was certified; sketch: it settled the query (0: handed over); else -1 */
+    int32_t k;           /* top-k and sketch passes; else -1 */
+    uint64_t row_lo, row_hi;  /* rows of the handle the record speaks for (no row base) */
+    double thr_min;      /* top-k: the bound on the real-number key of every eligible row outside the candidates
+                            (+inf: every eligible row is among them); sketch: lb, that bound on the sketch keys; else NaN */
+    double kmax;         /* top-k: upper bound of the real-number key of the worst result (-inf: not computed); else NaN */
+    double thr;          /* collect passes: the key threshold of the sweep; else NaN */
+    double eps;          /* collect passes: the sweep's key bound at the threshold -- a row with a real-number key at or
+                            below thr - eps is surely collected (computed for the trace, as ub below); else NaN */
+    double D, slack;     /* sketch: the distance lb implies and the largest row-to-sketch distance (D NaN: lb infinite) */
+    uint64_t first_entry, n_entries;
+} szg_cert_record;
+typedef struct szg_cert_entry {
+    uint64_t row;        /* row of the handle (no row base) */
+    double dist;         /* the reference's float64 distance */
+    double ub;           /* key + the bound of the arithmetic that made it: what the host takes the real-number key to
+                            be at most (collect passes: computed for the trace, by the function certification uses) */
+    float key;           /* the sweep's float32 key */
+    uint32_t flags;      /* SZG_CERT_ENTRY_* */
+} szg_cert_entry;
+int szg_debug_trace_certificates(szg_index *ix, int on);
+int szg_debug_certificates(szg_index *ix, szg_cert_record *records, uint64_t record_capacity, szg_cert_entry *entries,
+                           uint64_t entry_capacity, uint64_t *out_records, uint64_t *out_entries, uint64_t *out_dropped);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,61 @@
+"""The certificate margins: how much of each key bound the kernels use.
+
+Runs tests/test_gpu_certificates.py (every claim is asserted there: a failure fails this script too), then writes the
+largest |key - real| / eps the run saw per pass kind, arithmetic, row width and metric -- and, for the bfloat16 sweeps,
+the largest |key - emulated key| / (the float32-accumulation part of the bound) -- to
+profiles/certificate_margins.txt, with the commit it measured.  A ratio that creeps towards 1 after a kernel change
+is margin the change has eaten.
+
+    python scripts/dev_certificates.py [--out profiles/certificate_margins.txt] [--commit NAME] [pytest arguments]
+
+--commit names the commit where the tree is not a git checkout (a copy on a GPU machine).
+"""
+import argparse
+import os
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [os.path.join(ROOT, "tests"), ROOT]
+
+import pytest  # noqa: E402
+
+import test_gpu_certificates as t  # noqa: E402
+
+WANT = [("topk", "Single", "one-sweep"), ("radius", "-", "one-sweep"), ("topk", "SharedInt8", "int8"),
+        ("radius-shared", "-", "int8"), ("topk", "SharedBf16", "bf16"), ("topk", "Bf16Band", "bf16"),
+        ("topk", "Bf16Rescored", "bf16"), ("radius-shared", "-", "bf16"), ("escalation", "-", "one-sweep"),
+        ("bf16-operands", "SharedBf16", "topk"), ("bf16-operands", "-", "radius-shared")]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "certificate_margins.txt"))
+    ap.add_argument("--commit", default=None)
+    args, rest = ap.parse_known_args()
+    rc = pytest.main([t.__file__, "-m", "gpu", "-q", "-p", "no:cacheprovider"] + rest)
+    commit = args.commit
+    if commit is None:
+        try:
+            commit = subprocess.check_output(["git", "-C", ROOT, "describe", "--always", "--dirty"], text=True,
+                                             stderr=subprocess.DEVNULL).strip()
+        except (OSError, subprocess.CalledProcessError):
+            commit = "unknown (no git checkout)"
+    kinds = {(p, k, s) for (p, k, s, _, _) in t.MARGINS.worst}
+    missing = [w for w in WANT if w not in kinds]
+    worst = max(t.MARGINS.worst.values(), default=0.0)
+    lines = ["certificate margins: python scripts/dev_certificates.py on one MI355X",
+             "measured at commit %s" % commit,
+             "tests/test_gpu_certificates.py: exit code %d; largest ratio %.4f; kinds without a margin: %s"
+             % (int(rc), worst, missing or "none"),
+             "ratio = the largest |key - real-number key| / (ub - key) over every key checked (bf16-operands: |key - the",
+             "key of the emulated bfloat16 operands| / the float32-accumulation part of key_eps's bfloat16 branch)", ""]
+    lines += t.MARGINS.lines()
+    with open(args.out, "w") as f:
+        f.write("\n".join(lines) + "\n")
+    print("\n".join(lines))
+    return 1 if rc or missing or worst > 1.0 else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

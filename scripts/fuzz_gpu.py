@@ -4,9 +4,12 @@ Random shapes (dim, quantization, metric, rows, k, batch size), filter masks, to
 two-shard handles, duplicate-heavy and scaled corpora, random tunables.  Every answer must be
 the oracle's: same rows in the same order, bit-equal float64 distances (NaN == NaN).
 
-    python scripts/fuzz_gpu.py [seconds] [seed] [--iterations N]
+    python scripts/fuzz_gpu.py [seconds] [seed] [--iterations N] [--certificates]
 
 --iterations N runs exactly N cases instead of a time budget: a seed then means the same cases on every run.
+--certificates switches the handles' certificate trace on and checks every search call's records against float64
+(syzgydb_amd/cert_check.py: key bounds, left-out bounds, collect completeness, the sketch's bound) beside the answers;
+the cases drawn are the same with and without it.
 Dimensions come from a fixed list and from the scan kernel's shape lattice (syzgydb_amd/scan_lattice.py: one dimension per
 lane-map class of the drawn row width); about a third of the filtered cases pass their filters as resident masks.
 """
@@ -15,12 +18,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import numpy as np
 import oracle as orc
-from syzgydb_amd import ScanIndex, scan_lattice
+from syzgydb_amd import ScanIndex, cert_check, scan_lattice
 
 ap = argparse.ArgumentParser()
 ap.add_argument("seconds", nargs="?", type=float, default=60.0)
 ap.add_argument("seed", nargs="?", type=int, default=1)
 ap.add_argument("--iterations", type=int, default=0, help="run exactly this many cases (0: run for `seconds`)")
+ap.add_argument("--certificates", action="store_true", help="check every call's certificate trace against float64")
 args = ap.parse_args()
 budget, seed = args.seconds, args.seed
 rng = np.random.default_rng(seed)
@@ -39,6 +43,25 @@ def same(got_r, got_d, want_r, want_d):
         return False
     g, w = np.asarray(got_d), np.asarray(want_d)
     return bool(((g == w) | (np.isnan(g) & np.isnan(w))).all())
+
+
+def certificates(ix, rows, dim, bits, metric, Q, eligible, desc, call):
+    """--certificates: the records of the call just made, checked; a failed claim counts like a wrong answer."""
+    if not args.certificates:
+        return 0
+    recs, ents, dropped = ix.certificates()
+    corpus = cert_check.Corpus(rows, dim, bits, metric)
+    Q = np.atleast_2d(Q)
+    dists = None
+    if (recs["pass_"] == 1).any():
+        dists = np.stack([orc.all_distances(rows, dim, bits, metric, q) for q in Q])
+    try:
+        cert_check.check(corpus, Q, recs, ents, dropped, eligible=eligible, dists=dists, what=(call,))
+        cert_check.check_bf16_tight(corpus, Q, recs, ents, what=(call,))
+    except AssertionError as e:
+        print("CERTIFICATE", desc, str(e)[:600], flush=True)
+        return 1
+    return 0
 
 
 t_end = time.time() + budget
@@ -109,6 +132,8 @@ while (it < args.iterations) if args.iterations else (time.time() < t_end):
             assert (ix.read_rows(0, n) == rows).all(), "read_rows != what was written"
             for name, val in opts.items():
                 ix.set_option(name, val)
+            if args.certificates:
+                ix.trace_certificates(True)
             if rng.random() < 0.3 and n > 2:
                 dead = [int(x) for x in rng.choice(n, size=max(1, n // 7), replace=False)]
                 for r in dead:
@@ -122,6 +147,7 @@ while (it < args.iterations) if args.iterations else (time.time() < t_end):
                     return {}
                 return dict(masks=handles[lo:hi]) if resident else dict(allow=allow[lo:hi])
             r, d, c = ix.search_topk(Q, k, **filt(0, nq))
+            fails += certificates(ix, rows, dim, bits, metric, Q, live if allow is None else (allow & live), desc, "topk")
             for qi in range(nq):
                 m = live if allow is None else (live & allow[qi])
                 o_rows, o_dist, _ = orc.search_exact(rows, dim, bits, metric, Q[qi], k=k, allow=m.astype(np.uint8))
@@ -139,6 +165,7 @@ while (it < args.iterations) if args.iterations else (time.time() < t_end):
             if finite:
                 radius = float(finite[-1])
                 rr, dd = ix.search_radius(Q[qi], radius, **filt(qi, qi + 1))
+                fails += certificates(ix, rows, dim, bits, metric, Q[qi], m, desc, "radius")
                 w_rows, w_dist, _ = orc.search_exact(rows, dim, bits, metric, Q[qi], radius=radius,
                                                      allow=m.astype(np.uint8))
                 if not same(rr, dd, w_rows, w_dist):
@@ -153,6 +180,8 @@ while (it < args.iterations) if args.iterations else (time.time() < t_end):
                 fin = [x for x in od if x == x and x > 0]
                 radii.append(float(fin[-1]) if fin else 0.5)
             hits = ix.search_radius_batch(Q[:nb_], radii, **filt(0, nb_))
+            fails += certificates(ix, rows, dim, bits, metric, Q[:nb_], live if allow is None else (allow[:nb_] & live), desc,
+                                  "radius batch")
             for qj in range(nb_):
                 mj = live if allow is None else (live & allow[qj])
                 w_r, w_d, _ = orc.search_exact(rows, dim, bits, metric, Q[qj], radius=radii[qj], allow=mj.astype(np.uint8))
@@ -180,6 +209,7 @@ while (it < args.iterations) if args.iterations else (time.time() < t_end):
             if finite and len(w_rows) > 3:
                 cap = int(rng.integers(1, len(w_rows)))
                 tr, td, total = ix.search_radius(Q[qi], radius, allow=None if allow is None else allow[qi], capacity=cap)
+                fails += certificates(ix, rows, dim, bits, metric, Q[qi], m, desc, "truncated radius")
                 if total != len(w_rows) or not same(tr, td, w_rows[:cap], w_dist[:cap]):
                     fails += 1
                     print("MISMATCH truncated radius", desc, cap, total, len(w_rows), flush=True)
@@ -204,6 +234,7 @@ while (it < args.iterations) if args.iterations else (time.time() < t_end):
                 rows2 = np.concatenate([rows, erows])
                 live2 = np.concatenate([live, np.ones(extra, dtype=bool)])
                 r, d, c = ix.search_topk(Q, k)
+                fails += certificates(ix, rows2, dim, bits, metric, Q, live2, desc, "topk after mutation")
                 for qi in range(nq):
                     o_rows, o_dist, _ = orc.search_exact(rows2, dim, bits, metric, Q[qi], k=k, allow=live2.astype(np.uint8))
                     if not same(r[qi, : c[qi]], d[qi, : c[qi]], o_rows, o_dist):
@@ -217,6 +248,7 @@ while (it < args.iterations) if args.iterations else (time.time() < t_end):
                     fin = [x for x in od if x == x and x > 0]
                     radii.append(float(fin[-1]) if fin else 0.5)
                 hits = ix.search_radius_batch(Q[:nb_], radii)
+                fails += certificates(ix, rows2, dim, bits, metric, Q[:nb_], live2, desc, "radius batch after mutation")
                 for qj in range(nb_):
                     w_r, w_d, _ = orc.search_exact(rows2, dim, bits, metric, Q[qj], radius=radii[qj], allow=live2.astype(np.uint8))
                     if not same(hits[qj][0], hits[qj][1], w_r, w_d):

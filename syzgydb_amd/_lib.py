@@ -56,7 +56,14 @@ EXPORTS = [
     "szg_debug_scan_plan", "szg_debug_scan_group", "szg_debug_reorder_plan", "szg_debug_option_check",
     # who owns device memory: the counters and the refusal countdown (added under ABI 4)
     "szg_debug_device_memory", "szg_debug_refuse_device_alloc",
+    # the certificate trace: what each pass handed to certification (added under ABI 4)
+    "szg_debug_trace_certificates", "szg_debug_certificates",
 ]
+# szg_cert_record.pass / .keys, szg_cert_entry.flags
+SZG_CERT_TOPK, SZG_CERT_SKETCH, SZG_CERT_ESCALATION, SZG_CERT_RADIUS_SINGLE, SZG_CERT_RADIUS_SHARED = range(5)
+(SZG_CERT_KEYS_SINGLE, SZG_CERT_KEYS_SHARED_INT8, SZG_CERT_KEYS_SHARED_BF16, SZG_CERT_KEYS_BF16_BAND,
+ SZG_CERT_KEYS_BF16_RESCORED) = range(5)
+SZG_CERT_ENTRY_NO_KEY = 1
 SZG_MASK_AND, SZG_MASK_OR, SZG_MASK_ANDNOT, SZG_MASK_NOT = 0, 1, 2, 3
 SZG_COL_F64, SZG_COL_U32, SZG_COL_STR = 0, 1, 2
 SZG_CMP_EQ, SZG_CMP_NE, SZG_CMP_LT, SZG_CMP_LE, SZG_CMP_GT, SZG_CMP_GE = range(6)
@@ -112,6 +119,18 @@ class SzgScanPlan(ctypes.Structure):
     _fields_ = [(name, ctypes.c_int32) for name in (
         "r16", "L", "P", "gpw", "pow2", "dense", "tiled", "grid", "block", "ring_depth", "shaped", "nontemporal",
         "rows_per_block")]
+
+
+class SzgCertRecord(ctypes.Structure):
+    _fields_ = ([(name, ctypes.c_int32) for name in ("query", "pass_", "keys", "sweep", "certified", "k")] +
+                [("row_lo", ctypes.c_uint64), ("row_hi", ctypes.c_uint64)] +
+                [(name, ctypes.c_double) for name in ("thr_min", "kmax", "thr", "eps", "D", "slack")] +
+                [("first_entry", ctypes.c_uint64), ("n_entries", ctypes.c_uint64)])
+
+
+class SzgCertEntry(ctypes.Structure):
+    _fields_ = [("row", ctypes.c_uint64), ("dist", ctypes.c_double), ("ub", ctypes.c_double), ("key", ctypes.c_float),
+                ("flags", ctypes.c_uint32)]
 
 
 class SzgColumnInfo(ctypes.Structure):
@@ -370,6 +389,12 @@ def load():
         L.szg_debug_device_memory.argtypes = [u64p, u64p]
         L.szg_debug_refuse_device_alloc.restype = ctypes.c_int
         L.szg_debug_refuse_device_alloc.argtypes = [ctypes.c_int64]
+    if hasattr(L, "szg_debug_trace_certificates"):   # (as the masks: an older build for an A/B run keeps no trace)
+        L.szg_debug_trace_certificates.restype = ctypes.c_int
+        L.szg_debug_trace_certificates.argtypes = [vp, ctypes.c_int]
+        L.szg_debug_certificates.restype = ctypes.c_int
+        L.szg_debug_certificates.argtypes = [vp, ctypes.POINTER(SzgCertRecord), ctypes.c_uint64,
+                                             ctypes.POINTER(SzgCertEntry), ctypes.c_uint64, u64p, u64p, u64p]
     L.szg_debug_f64_probe.restype = ctypes.c_int
     L.szg_debug_f64_probe.argtypes = [ctypes.c_int, f64p, f64p, f64p, ctypes.c_uint64]
     _lib = L

@@ -1,0 +1,335 @@
+"""The certificate trace checked against float64: what tests/test_gpu_certificates.py, scripts/dev_certificates.py and
+scripts/fuzz_gpu.py --certificates share.  Test support, like scan_lattice.py: nothing on the search path imports it.
+
+A Corpus decodes the packed rows once (numpy; check_decode compares rows of it with the oracle's decoder) and computes
+the real-number key of every (query, row) pair in float64, or in longdouble where numpy has one wider than float64 and
+the case is small:
+
+    cosine   -(q . x) / (|q| |x|)
+    Euclid   |q - x|^2 in the key's units: times maxInt^2 for rows of 16 bits or fewer (radius_key_threshold)
+
+together with a bound on the reference's own rounding error, which is added to every tolerance (it is 1e-9 of the
+narrowest bound checked or less).  check() then asserts, for every record the trace kept of a call:
+
+    K  each candidate's float32 key is within ub - key of the real-number key
+    L  (top-k passes) every eligible row outside the candidates has a real-number key >= thr_min
+    C  (collect passes) every hit's key is <= the threshold; every eligible row whose real-number key is <= threshold -
+       eps is among the hits -- every eligible row where the threshold is the "take everything" one (3e38)
+    S  (sketch passes that settled) every eligible row outside the candidates is at reference distance >= D - slack
+
+Candidates the kernels force in carry no bound and are skipped and counted: cosine keys <= -1.5, rows with a non-finite
+element or an overflowing norm, keys clamped to 3e38.  A zero cosine query claims no bound at all.
+"""
+import collections
+
+import numpy as np
+
+from . import _lib
+
+PASS_NAMES = {_lib.SZG_CERT_TOPK: "topk", _lib.SZG_CERT_SKETCH: "sketch", _lib.SZG_CERT_ESCALATION: "escalation",
+              _lib.SZG_CERT_RADIUS_SINGLE: "radius", _lib.SZG_CERT_RADIUS_SHARED: "radius-shared"}
+KEYS_NAMES = {-1: "-", _lib.SZG_CERT_KEYS_SINGLE: "Single", _lib.SZG_CERT_KEYS_SHARED_INT8: "SharedInt8",
+              _lib.SZG_CERT_KEYS_SHARED_BF16: "SharedBf16", _lib.SZG_CERT_KEYS_BF16_BAND: "Bf16Band",
+              _lib.SZG_CERT_KEYS_BF16_RESCORED: "Bf16Rescored"}
+SWEEP_NAMES = {0: "one-sweep", 1: "int8", 2: "bf16"}
+TAKE_ALL = float(np.float32(3.0e38))   # the threshold of a collect sweep that takes every row (and the clamp of a key)
+LD = np.longdouble if np.finfo(np.longdouble).eps < np.finfo(np.float64).eps else np.float64
+WIDE_LIMIT = 2 * 10 ** 7   # (query, row, element) triples up to which the reference is computed in LD, element by element
+
+
+def decode_rows(rows, dim, bits):
+    """Packed rows -> float64[n, dim], the reference's decodeVector (big-endian fields; v / maxInt * 2 - 1)."""
+    rb = {4: (dim + 1) // 2, 8: dim, 16: 2 * dim, 32: 4 * dim, 64: 8 * dim}[bits]
+    r = np.ascontiguousarray(rows, dtype=np.uint8).reshape(-1, rb)
+    if bits == 64:
+        return r.view(">f8").astype(np.float64)
+    if bits == 32:
+        return r.view(">f4").astype(np.float64)
+    if bits == 16:
+        v = r.view(">u2").astype(np.float64)
+    elif bits == 8:
+        v = r.astype(np.float64)
+    else:
+        v = np.empty((r.shape[0], 2 * rb), dtype=np.float64)
+        v[:, 0::2] = r >> 4
+        v[:, 1::2] = r & 15
+        v = v[:, :dim]
+    return v / float((1 << bits) - 1) * 2 - 1
+
+
+class Corpus:
+    """The packed rows of one collection and their real-number keys.  Rows are decoded and scored in slices, so a deep
+    corpus never exists as one float64 matrix; X (every decoded row) is built only when asked for."""
+    SLICE = 8192
+
+    def __init__(self, rows, dim, bits, metric):
+        self.dim, self.bits, self.metric = int(dim), int(bits), int(metric)
+        rb = {4: (self.dim + 1) // 2, 8: self.dim, 16: 2 * self.dim, 32: 4 * self.dim, 64: 8 * self.dim}[self.bits]
+        self.packed = np.ascontiguousarray(rows, dtype=np.uint8).reshape(-1, rb)
+        self.n = self.packed.shape[0]
+        self.scale = float((1 << bits) - 1) if bits <= 16 else 1.0   # Euclidean keys are in units of 1 / maxInt
+        self.finite = np.ones(self.n, dtype=bool)
+        if bits >= 32:
+            for lo in range(0, self.n, self.SLICE):
+                self.finite[lo:lo + self.SLICE] = np.isfinite(self.rows(lo, lo + self.SLICE)).all(axis=1)
+        self._kept = {}
+        self._X = None
+
+    def rows(self, lo, hi):
+        return decode_rows(self.packed[lo:hi], self.dim, self.bits)
+
+    @property
+    def X(self):
+        if self._X is None:
+            self._X = self.rows(0, self.n)
+        return self._X
+
+    def with_metric(self, metric):
+        """The same rows under the other metric (the packed rows are shared)."""
+        return self if metric == self.metric else Corpus(self.packed, self.dim, self.bits, metric)
+
+    def check_decode(self, orc, at=None):
+        """Rows of the numpy decode against the oracle's decoder, bit for bit."""
+        for r in (at if at is not None else sorted({0, self.n // 3, self.n - 1})):
+            want = orc.decode_vector(self.packed[r], self.dim, self.bits)
+            got = self.rows(r, r + 1)[0]
+            assert ((got == want) | (np.isnan(got) & np.isnan(want))).all(), ("decode differs from the oracle's", r)
+
+    def keys(self, Q):
+        """-> (real[nq, n] float64, err[nq, n] float64): the real-number keys and a bound on their own rounding error."""
+        Q = np.atleast_2d(np.asarray(Q, dtype=np.float64))
+        tag = Q.tobytes()
+        if tag in self._kept:
+            return self._kept[tag]
+        nq = Q.shape[0]
+        wide = nq * self.n * self.dim <= WIDE_LIMIT
+        dt = LD if wide else np.float64
+        u = float(np.finfo(dt).eps)
+        real = np.empty((nq, self.n), dtype=np.float64)
+        err = np.empty_like(real)
+        Qd = Q.astype(dt)
+        qn2 = (Qd * Qd).sum(axis=1)
+        with np.errstate(all="ignore"):
+            for lo in range(0, self.n, self.SLICE):
+                X = self.rows(lo, lo + self.SLICE).astype(dt)
+                sl = slice(lo, lo + X.shape[0])
+                xn2 = (X * X).sum(axis=1)
+                if self.metric == _lib.SZG_COSINE:
+                    dot = np.stack([(X * q).sum(axis=1) for q in Qd]) if wide else Qd @ X.T
+                    real[:, sl] = (-dot / np.sqrt(qn2[:, None] * xn2[None, :])).astype(np.float64)
+                    err[:, sl] = (self.dim + 8) * u   # |dot| <= |q||x|: the quotient is off by at most (dim + 8) u
+                elif wide:
+                    k = np.stack([((X - q) ** 2).sum(axis=1) for q in Qd]) * dt(self.scale) ** 2
+                    real[:, sl] = k.astype(np.float64)
+                    err[:, sl] = ((self.dim + 8) * u * k).astype(np.float64)
+                else:   # the expanded form through one matrix product: its terms are bounded by (|x| + |q|)^2
+                    real[:, sl] = (xn2[None, :] + qn2[:, None] - 2 * (Qd @ X.T)) * self.scale ** 2
+                    err[:, sl] = 4 * (self.dim + 8) * u * (np.sqrt(xn2)[None, :] + np.sqrt(qn2)[:, None]) ** 2 * self.scale ** 2
+        self._kept = {tag: (real, err)}
+        return real, err
+
+
+class Margins:
+    """The largest |key - real| / (ub - key) seen per (pass, keys, sweep, row width, metric)."""
+
+    def __init__(self):
+        self.worst = collections.OrderedDict()
+        self.count = collections.Counter()
+
+    def note(self, what, ratio, n):
+        self.worst[what] = max(self.worst.get(what, 0.0), float(ratio))
+        self.count[what] += int(n)
+
+    def lines(self):
+        out = ["%-14s %-13s %-9s %5s %-6s %12s %10s" % ("pass", "keys", "sweep", "bits", "metric", "keys checked", "max ratio")]
+        for (p, k, s, bits, metric), r in sorted(self.worst.items()):
+            out.append("%-14s %-13s %-9s %5d %-6s %12d %10.4f" % (p, k, s, bits, "cosine" if metric else "euclid",
+                                                                 self.count[(p, k, s, bits, metric)], r))
+        return out
+
+
+Summary = collections.namedtuple("Summary", "records kinds skipped skipped_rows checked")
+
+
+def check(corpus, Q, recs, ents, dropped, eligible=None, dists=None, margins=None, what=()):
+    """Assert K, L, C and S for the records of ONE call with queries Q.  eligible: bool[n] or bool[nq, n] (None: every
+    row); dists: float64[nq, n], the oracle's distances (needed for sketch records).  -> Summary; skipped_rows are the
+    rows whose candidates carried no bound."""
+    Q = np.atleast_2d(np.asarray(Q, dtype=np.float64))
+    nq, n = Q.shape[0], corpus.n
+    assert dropped == 0, ("the trace dropped records", dropped, what)
+    real, err = corpus.keys(Q)
+    if eligible is None:
+        eligible = np.ones(n, dtype=bool)
+    eligible = np.broadcast_to(np.asarray(eligible, dtype=bool), (nq, n))
+    zero_q = (Q == 0).all(axis=1) & (corpus.metric == _lib.SZG_COSINE)
+    kinds = collections.Counter()
+    skipped, checked, skipped_rows = 0, 0, set()
+    for rec in recs:
+        qi, p = int(rec["query"]), int(rec["pass_"])
+        assert 0 <= qi < nq, ("query index out of the call", qi, what)
+        e = ents[int(rec["first_entry"]): int(rec["first_entry"] + rec["n_entries"])]
+        kind = (PASS_NAMES[p], KEYS_NAMES[int(rec["keys"])], SWEEP_NAMES[int(rec["sweep"])])
+        kinds[kind] += 1
+        where = what + (kind, "query", qi)
+        rows = e["row"].astype(np.int64)
+        assert ((rows >= 0) & (rows < n)).all(), ("row out of range", where)
+        lo, hi = int(rec["row_lo"]), int(rec["row_hi"])
+        in_range = np.zeros(n, dtype=bool)
+        in_range[lo:hi] = True
+        keyed = (e["flags"] & _lib.SZG_CERT_ENTRY_NO_KEY) == 0
+        key = e["key"].astype(np.float64)
+        ub = e["ub"]
+        # ---- K
+        if p != _lib.SZG_CERT_SKETCH and not zero_q[qi]:   # (a sketch key is the key of the row's 8-bit sketch, not of the row)
+            r_real, r_err = real[qi, rows], err[qi, rows]
+            forced = keyed & ((~corpus.finite[rows]) | ~np.isfinite(r_real) | (key >= TAKE_ALL) |
+                              ((key <= -1.5) if corpus.metric == _lib.SZG_COSINE else False))
+            skipped += int(forced.sum())
+            skipped_rows.update(int(x) for x in rows[forced])
+            ok = keyed & ~forced
+            eps = ub[ok] - key[ok]
+            assert (eps > 0).all(), ("a candidate without a bound", where)
+            off = np.abs(key[ok] - r_real[ok])
+            bad = off > eps + r_err[ok]
+            assert not bad.any(), ("K: key outside its bound", where, "rows", rows[ok][bad][:8], "key", key[ok][bad][:8],
+                                   "real", r_real[ok][bad][:8], "eps", eps[bad][:8], "of", int(ok.sum()))
+            checked += int(ok.sum())
+            if margins is not None and ok.any():
+                margins.note(kind + (corpus.bits, corpus.metric), float((off / eps).max()), int(ok.sum()))
+        outside = eligible[qi] & in_range
+        outside[rows] = False
+        outside &= np.isfinite(real[qi])   # (a row without a real-number key: NaN distance, never a neighbour)
+        # ---- L
+        if p == _lib.SZG_CERT_TOPK and np.isfinite(rec["thr_min"]) and not zero_q[qi]:
+            low = real[qi] + err[qi] < rec["thr_min"]
+            bad = np.flatnonzero(outside & low)
+            assert bad.size == 0, ("L: a left-out row under the bound", where, "thr_min", float(rec["thr_min"]), "rows", bad[:8],
+                                   "real", real[qi, bad[:8]])
+        # ---- C
+        if p in (_lib.SZG_CERT_ESCALATION, _lib.SZG_CERT_RADIUS_SINGLE, _lib.SZG_CERT_RADIUS_SHARED):
+            thr = float(rec["thr"])
+            assert (key <= thr).all(), ("C: a hit above the threshold", where, thr, key[key > thr][:8])
+            if thr >= TAKE_ALL:
+                missed = np.flatnonzero(eligible[qi] & in_range & ~np.isin(np.arange(n), rows))
+            elif zero_q[qi]:
+                missed = np.zeros(0, dtype=np.int64)
+            else:
+                assert np.isfinite(rec["eps"]) and rec["eps"] > 0, ("collect record without its bound", where)
+                missed = np.flatnonzero(outside & (real[qi] + err[qi] <= thr - rec["eps"]))
+            assert missed.size == 0, ("C: an eligible row under the threshold was not collected", where, "thr", thr, "eps",
+                                      float(rec["eps"]), "rows", missed[:8], "real", real[qi, missed[:8]])
+            inel = ~eligible[qi, rows]
+            assert not inel.any(), ("C: a row that is not eligible was collected", where, rows[inel][:8])
+        # ---- S
+        if p == _lib.SZG_CERT_SKETCH and rec["certified"] == 1 and np.isfinite(rec["D"]):
+            assert dists is not None, "sketch records need the oracle's distances"
+            d = dists[qi]
+            bad = np.flatnonzero(outside & (d < rec["D"] - rec["slack"]))
+            assert bad.size == 0, ("S: a row outside the candidates nearer than D - slack", where, float(rec["D"]),
+                                   float(rec["slack"]), "rows", bad[:8], "dist", d[bad[:8]])
+    return Summary(len(recs), kinds, skipped, skipped_rows, checked)
+
+
+# ---- the bfloat16 sweeps, operand by operand ------------------------------------------------------------------------
+
+def bf16_round(a):
+    """float32 -> the nearest bfloat16 (ties to even) as float32, by bit arithmetic (v_cvt_pk_bf16_f32; scan_query.cpp
+    bf16_rne).  Finite values only."""
+    u = np.ascontiguousarray(a, dtype=np.float32).view(np.uint32).astype(np.uint64)
+    u = (u + 0x7FFF + ((u >> 16) & 1)) & 0xFFFF0000
+    return u.astype(np.uint32).view(np.float32)
+
+
+def _bf16_query(corpus, q):
+    """One query as the sweeps stage it: (the bfloat16 image as float64, |g|^2 of the unrounded prepared query)."""
+    m1 = 0.0
+    for v in q:           # (in the order prep_query_norms sums it)
+        m1 += float(v) * float(v)
+    if corpus.metric == _lib.SZG_COSINE:
+        scale = 1.0 / np.sqrt(m1) if m1 > 0 else 0.0
+    else:
+        scale = {16: 65535.0, 8: 255.0}.get(corpus.bits, 1.0)
+    g = (q * scale).astype(np.float32)
+    return bf16_round(g).astype(np.float64), float(((q * scale) ** 2).sum())
+
+
+def bf16_emulated(corpus, Q, queries, rows=None):
+    """The keys the bfloat16 sweeps would give rows `rows` (None: every row) for the listed queries if the matrix core
+    summed exactly, and the float32-accumulation part of key_eps's bfloat16 branch at those keys (4 n u, cosine;
+    3 n u s^2, Euclid): two arrays [len(queries), len(rows)].
+
+    Operands, as build_image_bf16 and the kernels form them: the query is q / |q| (cosine) or maxInt * q (Euclid, rows
+    of 16 or 8 bits; q itself otherwise), narrowed to float32 and rounded to bfloat16.  A row element is the float32
+    value (32-bit rows), the float64 value narrowed to float32 (64-bit rows) or the code n = 2 v - maxInt (16- and
+    8-bit rows, exact in float32); 32-, 64- and 16-bit elements are rounded to bfloat16, an 8-bit row's n enters
+    exactly (the kernel multiplies v - 128, exact in bfloat16, and adds the sum of the rounded query).  The row's norm
+    is the float32 sum of the squares of the UNROUNDED float32 elements -- summed in the sweep or read from the
+    resident array, the same float either way -- and the Euclidean |g|^2 is that of the unrounded prepared query, so no
+    term of the formula beyond the accumulation part is needed for them."""
+    Q = np.atleast_2d(np.asarray(Q, dtype=np.float64))
+    staged = [_bf16_query(corpus, Q[qi]) for qi in queries]
+    GB = np.stack([g for g, _ in staged])
+    qnorm2 = np.array([x for _, x in staged])
+    rows = np.arange(corpus.n) if rows is None else np.asarray(rows, dtype=np.int64)
+    dot = np.empty((len(staged), rows.size))
+    nrm = np.empty(rows.size)
+    for lo in range(0, rows.size, Corpus.SLICE):
+        X = decode_rows(corpus.packed[rows[lo:lo + Corpus.SLICE]], corpus.dim, corpus.bits)
+        if corpus.bits <= 16:
+            x32 = np.rint((X + 1) / 2 * corpus.scale) * 2 - corpus.scale   # n = 2 v - maxInt
+        else:
+            with np.errstate(over="ignore", invalid="ignore"):
+                x32 = X.astype(np.float32).astype(np.float64)
+        with np.errstate(all="ignore"):
+            xb = x32 if corpus.bits == 8 else bf16_round(x32.astype(np.float32)).astype(np.float64)
+            dot[:, lo:lo + X.shape[0]] = GB @ xb.T
+            nrm[lo:lo + X.shape[0]] = (x32 * x32).sum(axis=1)
+    u, nn = 2.0 ** -24, corpus.dim + 16.0 + (4.0 if corpus.bits == 64 else 0.0)
+    with np.errstate(all="ignore"):
+        if corpus.metric == _lib.SZG_COSINE:
+            return -dot / np.sqrt(nrm)[None, :], np.full(dot.shape, 4.0 * nn * u)
+        key = nrm[None, :] + qnorm2[:, None] - 2 * dot
+        s = 2.0 * np.sqrt(qnorm2)[:, None] + np.sqrt(np.abs(key))
+        return key, 3.0 * nn * u * s * s
+
+
+def check_bf16_tight(corpus, Q, recs, ents, margins=None, what=()):
+    """Every keyed, unforced candidate of the records whose keys are the bfloat16 sweep's own -- SharedBf16 lists and
+    collect records of a shared bfloat16 sweep -- lies within the accumulation part of the bound of the emulated key.
+    -> keys checked."""
+    Q = np.atleast_2d(np.asarray(Q, dtype=np.float64))
+    own = [rec for rec in recs
+           if ((rec["pass_"] == _lib.SZG_CERT_TOPK and rec["keys"] == _lib.SZG_CERT_KEYS_SHARED_BF16) or
+               (rec["pass_"] == _lib.SZG_CERT_RADIUS_SHARED and rec["sweep"] == 2)) and
+           not (corpus.metric == _lib.SZG_COSINE and not Q[int(rec["query"])].any())]
+    if not own:
+        return 0
+    # many entries (an all-rows radius batch): every (query, row) pair at once; a few lists: their rows only
+    whole = sum(int(rec["n_entries"]) for rec in own) >= corpus.n
+    if whole:
+        order = sorted({int(rec["query"]) for rec in own})
+        at = {qi: i for i, qi in enumerate(order)}
+        all_emul, all_tol = bf16_emulated(corpus, Q, order)
+    checked = 0
+    for rec in own:
+        qi = int(rec["query"])
+        e = ents[int(rec["first_entry"]): int(rec["first_entry"] + rec["n_entries"])]
+        rows = e["row"].astype(np.int64)
+        key = e["key"].astype(np.float64)
+        if whole:
+            emul, tol = all_emul[at[qi], rows], all_tol[at[qi], rows]
+        else:
+            emul, tol = (x[0] for x in bf16_emulated(corpus, Q, [qi], rows))
+        ok = corpus.finite[rows] & np.isfinite(emul) & (key < TAKE_ALL)
+        if corpus.metric == _lib.SZG_COSINE:
+            ok &= key > -1.5
+        off = np.abs(key - emul)
+        bad = ok & (off > tol)
+        assert not bad.any(), ("bfloat16 key outside the accumulation part of its bound", what, "query", qi, "rows",
+                               rows[bad][:8], "key", key[bad][:8], "emulated", emul[bad][:8], "tolerance", tol[bad][:8])
+        checked += int(ok.sum())
+        if margins is not None and ok.any():
+            margins.note(("bf16-operands", KEYS_NAMES[int(rec["keys"])], PASS_NAMES[int(rec["pass_"])], corpus.bits,
+                          corpus.metric), float((off[ok] / tol[ok]).max()), int(ok.sum()))
+    return checked

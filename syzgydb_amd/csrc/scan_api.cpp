@@ -14,6 +14,51 @@
 
 using namespace szgi;
 
+namespace szgi {
+
+szg_cert_record cert_record(int query, int pass)
+{
+    szg_cert_record r;
+    memset(&r, 0, sizeof(r));
+    r.query = query;
+    r.pass = pass;
+    r.keys = r.certified = r.k = -1;
+    r.thr_min = r.kmax = r.thr = r.eps = r.D = r.slack = NAN;
+    return r;
+}
+
+bool cert_room(szg_index *ix, size_t n)
+{
+    CertTrace &t = ix->cert;
+    std::lock_guard<std::mutex> lk(t.mu);
+    if (!t.on.load()) return false;
+    if (t.recs.size() < kCertMaxRecords && n <= kCertMaxEntries && t.entries.size() + n <= kCertMaxEntries) return true;
+    t.dropped++;
+    return false;
+}
+
+void cert_emit(szg_index *ix, szg_cert_record r, const std::vector<szg_cert_entry> &entries)
+{
+    CertTrace &t = ix->cert;
+    std::lock_guard<std::mutex> lk(t.mu);
+    if (!t.on.load()) return;  // (switched off since the caller looked)
+    if (t.recs.size() >= kCertMaxRecords || t.entries.size() + entries.size() > kCertMaxEntries) {
+        t.dropped++;
+        return;
+    }
+    try {
+        r.first_entry = t.entries.size();
+        r.n_entries = entries.size();
+        t.entries.insert(t.entries.end(), entries.begin(), entries.end());
+        t.recs.push_back(r);
+    } catch (const std::bad_alloc &) {
+        t.entries.resize(std::min<size_t>(t.entries.size(), (size_t)r.first_entry));
+        t.dropped++;
+    }
+}
+
+}  // namespace szgi
+
 extern "C" {
 
 // The reference's float64 distance from one query to each listed row
@@ -460,6 +505,39 @@ int szg_debug_refuse_device_alloc(int64_t nth)
 {
     if (nth < 0) return fail(SZG_E_INVALID, "nth is 0 (disarm) or the allocation to refuse, counted from 1");
     dev_alloc_state().refuse_in.store(nth);
+    return SZG_OK;
+}
+
+// test hook: the certificate trace (include/syzgy_scan.h).  Switching clears; reading copies out and empties.
+int szg_debug_trace_certificates(szg_index *ix, int on)
+{
+    if (!ix) return fail(SZG_E_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(ix->cert.mu);
+    ix->cert.recs.clear();
+    ix->cert.entries.clear();
+    ix->cert.recs.shrink_to_fit();
+    ix->cert.entries.shrink_to_fit();
+    ix->cert.dropped = 0;
+    ix->cert.on.store(on != 0);
+    return SZG_OK;
+}
+
+int szg_debug_certificates(szg_index *ix, szg_cert_record *records, uint64_t record_capacity, szg_cert_entry *entries,
+                           uint64_t entry_capacity, uint64_t *out_records, uint64_t *out_entries, uint64_t *out_dropped)
+{
+    if (!ix) return fail(SZG_E_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(ix->cert.mu);
+    CertTrace &t = ix->cert;
+    if (out_records) *out_records = t.recs.size();
+    if (out_entries) *out_entries = t.entries.size();
+    if (out_dropped) *out_dropped = t.dropped;
+    if (!records || !entries) return SZG_OK;
+    if (record_capacity < t.recs.size() || entry_capacity < t.entries.size())
+        return fail(SZG_E_TRUNCATED, "certificate trace: buffers too small");
+    if (!t.recs.empty()) memcpy(records, t.recs.data(), t.recs.size() * sizeof(szg_cert_record));
+    if (!t.entries.empty()) memcpy(entries, t.entries.data(), t.entries.size() * sizeof(szg_cert_entry));
+    t.recs.clear();
+    t.entries.clear();
     return SZG_OK;
 }
 

@@ -177,6 +177,18 @@ struct QMeta {
     bool mq_bf16 = false;  // (with mq) the shared sweep multiplied bfloat16 roundings of rows and query
 };
 
+// The certificate trace of a handle (szg_debug_trace_certificates): what each pass handed to certification, kept for a
+// test to check against float64.  Off by default: the search path then pays one relaxed load per settled query.
+struct CertTrace {
+    std::atomic<bool> on{false};
+    std::mutex mu;  // (finisher thread, coalesced callers)
+    std::vector<szg_cert_record> recs;
+    std::vector<szg_cert_entry> entries;
+    uint64_t dropped = 0;  // records that did not fit the caps
+};
+constexpr size_t kCertMaxRecords = 1u << 18;
+constexpr size_t kCertMaxEntries = 1u << 23;  // 32 bytes each: 256 MiB at most
+
 struct Cand {
     uint64_t row;  // index-level row
     double dist;   // reference float64 distance
@@ -457,6 +469,7 @@ struct szg_index {
     std::deque<struct PendingSearch *> comb_waiting;
     bool comb_leader = false;
     szg_stats stats{};
+    szgi::CertTrace cert;        // certificate trace (test hook)
     szg_comm *comm = nullptr;    // one process per GPU: the attached communicator (borrowed; scan_comm.cpp)
 };
 
@@ -573,6 +586,21 @@ int reset_shards(szg_index *ix, const std::vector<uint64_t> &counts);
 Shard *append_target(szg_index *ix);
 void note_overwritten(szg_index *ix, uint64_t row);
 
+// ---- scan_api.cpp: the certificate trace
+inline bool cert_tracing(const szg_index *ix) { return ix->cert.on.load(std::memory_order_relaxed); }
+// a fresh record of query `query` of its call for pass `pass`: everything that does not apply is NaN / -1
+szg_cert_record cert_record(int query, int pass);
+// append the record and its entries (dropped as a whole, and counted, when a cap would be passed)
+void cert_emit(szg_index *ix, szg_cert_record r, const std::vector<szg_cert_entry> &entries);
+// room for a record of n entries?  Asked BEFORE the entries are gathered, so that a record that will not fit costs no
+// memory; false counts the record as dropped
+bool cert_room(szg_index *ix, size_t n);
+// what a collect sweep run by run_collect is traced as (null: not traced)
+struct CertTag {
+    int query;   // index in its call
+    int pass;    // SZG_CERT_ESCALATION / SZG_CERT_RADIUS_SINGLE
+};
+
 // ---- scan_topk.cpp
 // grid and block of a sweep over n_rows rows (kp = 0: a collect sweep); the second form reads them off a shard
 LaunchGeom scan_geometry(int bits, const szg::RowMap &map, uint32_t row_bytes, bool tiled, uint64_t n_rows, int cu_count,
@@ -613,14 +641,17 @@ void emit_topk(const szg_index *ix, const std::vector<HeapItem> &res, int k, int
                int32_t *out_count);
 // the end of a call's stage(): host time of the preparation [t_prep0, t_enq0) and of the enqueueing [t_enq0, now)
 void note_stage_times(szg_index *ix, double t_prep0, double t_enq0);
-int run_collect(szg_index *ix, Shard *sh, Ctx *c, int slot, float thr_key, bool has_allow, std::vector<Cand> *cands);
+int run_collect(szg_index *ix, Shard *sh, Ctx *c, int slot, float thr_key, bool has_allow, std::vector<Cand> *cands,
+                const CertTag *tag = nullptr);
 // fraction of the shard's rows that staged query `slot` may visit (tombstones, and its filter mask: the exact count of
 // a resident mask, a sample of the words of one that came from the host)
 double mask_pass_rate(const Shard *sh, const Ctx *c, bool has_allow, int slot);
 void first_eligible_rows(const szg_index *ix, const uint64_t *allow, int k, std::vector<uint64_t> *rows_out);
 int search_topk_impl(szg_index *ix, const double *queries, int n_queries, int k, const uint64_t *allow_bits,
                      uint64_t *out_rows, double *out_dist, int32_t *out_count,
-                     const uint64_t *const *allow_ptrs = nullptr, const szg_mask *const *handles = nullptr);
+                     const uint64_t *const *allow_ptrs = nullptr, const szg_mask *const *handles = nullptr,
+                     const int *trace_index = nullptr);
+// (trace_index: the queries' indexes in the caller's call, for the certificate trace of a call made on its behalf)
 // consider()'s top-k branch over every row of the handle in visit order, continuing the heap *h (rows + row_base)
 int replay_rows_into_heap(szg_index *ix, const double *query, const uint64_t *allow, int k, GoHeap *h);
 

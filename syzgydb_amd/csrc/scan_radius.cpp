@@ -59,6 +59,7 @@ struct RadiusBatch : Batch {
     std::vector<float> thr_single; // ... of the single-query collect sweep (a query that overflows is swept again on its own)
     std::vector<size_t> cap;       // per shard: entries per sweep of this batch's buffers
     std::vector<uint8_t> copied;   // per shard: the block of re-ranked hits was copied back at enqueue time
+    std::vector<QMeta> meta;       // certificate trace only: each query's constants with the flags of the sweep that runs
 };
 
 struct RadiusCall {
@@ -69,6 +70,7 @@ struct RadiusCall {
     QueryMasks mask_of;
     std::vector<std::vector<HeapItem>> *results;
     size_t n_sh = 0;
+    bool tracing = false;  // the handle's certificate trace is on
 
     RadiusBatch plan(int q0);
     int stage(RadiusBatch &t);
@@ -165,16 +167,18 @@ int RadiusCall::stage(RadiusBatch &t)
     const std::vector<const szg_mask *> handles = t.handles(mask_of);
     const double t0 = now_us();
     const bool int_planes = t.nb > 0 && mq_uses_i8(ix, true);
+    if (tracing) t.meta.assign(t.nq, QMeta{});
     int rc = stage_query_forms(ix, t, q, int_planes, [&](int j, QMeta &meta) {
         const double radius = radii[t.first + j];
+        QMeta m2 = meta;  // the shared sweep's arithmetic has its own error bound
         if (t.nb == 0) {
             t.thr_single[j] = t.thr[j] = radius_key_threshold(ix, radius, meta);
-            return;
+        } else {
+            m2.mq = !int_planes;
+            m2.mq_bf16 = mq_uses_bf16(ix, true);
+            t.thr[j] = radius_key_threshold(ix, radius, m2);
         }
-        QMeta m2 = meta;  // the shared sweep's arithmetic has its own error bound
-        m2.mq = !int_planes;
-        m2.mq_bf16 = mq_uses_bf16(ix, true);
-        t.thr[j] = radius_key_threshold(ix, radius, m2);
+        if (tracing) t.meta[j] = m2;
     });
     if (rc) return rc;
     const double t1 = now_us();
@@ -199,6 +203,8 @@ int RadiusCall::finish(RadiusBatch &t)
     std::vector<uint8_t> redo(t.nq, 0);  // more hits than the batch's buffers hold: the query is swept again on its own
     std::vector<uint8_t> presorted(t.nq, 1);  // the query's hits come from ONE shard's device-sorted list
     std::vector<uint8_t> lists(t.nq, 0);
+    std::vector<std::vector<szg_cert_entry>> traced(tracing ? t.nq : 0);  // every collected hit, before the predicate
+    std::vector<uint8_t> untraced(tracing ? t.nq : 0, 0);  // the query's record will not fit the trace: nothing is gathered
     double t_wait = 0;
     const double t0 = now_us();
     for (size_t s = 0; s < n_sh && rc == SZG_OK; s++) {
@@ -248,9 +254,18 @@ int RadiusCall::finish(RadiusBatch &t)
                 if (cnt[j] > (size_t)szg::kSortHitsMax || ++lists[j] > 1) presorted[j] = 0;
             }
             const double rad = radii[t.first + j];
+            if (tracing && !untraced[j] && !cert_room(ix, traced[j].size() + cnt[j])) {
+                untraced[j] = 1;
+                std::vector<szg_cert_entry>().swap(traced[j]);
+            }
+            const bool keep = tracing && !untraced[j];
             for (size_t i = off[j]; i < off[j] + cnt[j]; i++) {
                 const szg::RerankOut &r = c->h_out[i];
                 if (r.dist <= rad) cands[j].push_back(HeapItem{sh->first + r.row, r.dist});
+                if (keep) {
+                    const float key = szg::key_from_ordered(r.ukey);
+                    traced[j].push_back(szg_cert_entry{sh->first + r.row, r.dist, (double)key + key_eps(ix, key, t.meta[j]), key, 0u});
+                }
             }
         }
     }
@@ -264,14 +279,24 @@ int RadiusCall::finish(RadiusBatch &t)
                 rc = stage_single_form(ix, t, queries + (size_t)(t.first + j) * ix->dim, j, &m);
                 t.thr_single[j] = radius_key_threshold(ix, radii[t.first + j], m);
             }
-            for (size_t s = 0; s < n_sh && rc == SZG_OK; s++)
-                if (t.ctx[s]) rc = run_collect(ix, ix->shards[s], t.ctx[s], j, t.thr_single[j], t.any_mask, &all);
+            for (size_t s = 0; s < n_sh && rc == SZG_OK; s++) {
+                if (!t.ctx[s]) continue;
+                const CertTag tag{t.first + j, SZG_CERT_RADIUS_SINGLE};
+                rc = run_collect(ix, ix->shards[s], t.ctx[s], j, t.thr_single[j], t.any_mask, &all, tracing ? &tag : nullptr);
+            }
             t_wait += now_us() - tw;
             if (rc) break;
             const double rad = radii[t.first + j];
             for (const Cand &c : all)
                 if (c.dist <= rad) cands[j].push_back(HeapItem{c.row, c.dist});
             presorted[j] = 0;
+        } else if (tracing && !untraced[j]) {
+            szg_cert_record rec = cert_record(t.first + j, t.nb > 0 ? SZG_CERT_RADIUS_SHARED : SZG_CERT_RADIUS_SINGLE);
+            rec.sweep = t.nb == 0 ? 0 : (t.meta[j].mq_bf16 ? 2 : 1);
+            for (const Shard *sh : ix->shards) rec.row_hi = std::max<uint64_t>(rec.row_hi, sh->first + sh->n_rows);
+            rec.thr = (double)t.thr[j];
+            rec.eps = key_eps(ix, t.thr[j], t.meta[j]);
+            cert_emit(ix, rec, traced[j]);
         }
         radius_assemble(cands[j], presorted[j] != 0, &(*results)[t.first + j]);
     }
@@ -290,7 +315,8 @@ int search_radius_impl(szg_index *ix, const double *queries, int n_queries, cons
                        const uint64_t *const *masks, std::vector<std::vector<HeapItem>> *results,
                        const szg_mask *const *handles)
 {
-    RadiusCall call{ix, queries, n_queries, radii, QueryMasks(ix, nullptr, masks, handles), results, ix->shards.size()};
+    RadiusCall call{ix, queries, n_queries, radii, QueryMasks(ix, nullptr, masks, handles), results, ix->shards.size(),
+                    cert_tracing(ix)};
     results->assign(n_queries, {});
     return run_batches<RadiusBatch>(call);
 }

@@ -257,6 +257,7 @@ struct SketchCall {
     std::vector<Cand> cands;
     std::vector<HeapItem> res;
     std::vector<double> dd;
+    bool tracing = false;  // the float32 handle's certificate trace is on
 
     int run();
     Batch plan(int q0);
@@ -268,6 +269,7 @@ struct SketchCall {
 int SketchCall::run()
 {
     n_sh = ix->shards.size();
+    tracing = cert_tracing(ix);
     const int kk = k + ix->sketch_extra;
     kp = kk + std::max(ix->slack_min, kk / 2);
     gs = ix->sk_gscale;  // Euclidean: sketch distances are in units of gs (the sketch sweeps see q / gs)
@@ -368,11 +370,15 @@ void SketchCall::settle(Batch &b, int j)
     double lb = INFINITY;  // lower bound of the real-number sketch key of every eligible row outside the lists
     bool nan_first = false;
     bool zero_query = false;
+    std::vector<szg_cert_entry> traced;  // certificate trace: each shard's list entries (sketch keys), then the rows beside them
     for (size_t s = 0; s < n_sh; s++) {
         const Ctx *c = b.ctx[s];
         if (!c) continue;
         double l;
+        const size_t n0 = cands.size();
         gather_topk(sk, sk->shards[s], c, c->meta[j], j, &cands, &l);
+        for (size_t i = n0; tracing && i < cands.size(); i++)
+            traced.push_back(szg_cert_entry{cands[i].row, cands[i].dist, cands[i].ub, cands[i].key, 0u});
         // short lists: a row the sweep's blocks did not output has a key at or above the drop bound (entry kp)
         const szg::RerankOut &drop = c->drop_bound(j);
         if (drop.row != 0xFFFFFFFFu) {
@@ -388,6 +394,7 @@ void SketchCall::settle(Batch &b, int j)
             // outside the first k rows a NaN never enters the heap; among them it decides everything
             if (std::isnan(r.dist) && i < kp + 1 + k) nan_first = true;
             cands.push_back(Cand{first + r.row, r.dist, 0.0f, 0.0});
+            if (tracing) traced.push_back(szg_cert_entry{first + r.row, r.dist, 0.0, 0.0f, SZG_CERT_ENTRY_NO_KEY});
         }
     }
     cands.erase(std::remove_if(cands.begin(), cands.end(), [](const Cand &c) { return std::isnan(c.dist); }), cands.end());
@@ -396,6 +403,7 @@ void SketchCall::settle(Batch &b, int j)
                 cands.end());
     replay_topk(cands, k, &res);
     bool ok = (!nan_first || ix->tie_mode != 0) && !zero_query;
+    double D_used = NAN;
     if (ok && lb < INFINITY) {
         // D_lb: the sketch distance the key bound lb implies -- cosine: key = -cos, distance
         // acos(cos) / pi; Euclid: key = (255 d)^2 in units of gs
@@ -407,11 +415,24 @@ void SketchCall::settle(Batch &b, int j)
             D = x >= 1.0 ? 0.0 : (x <= -1.0 ? 1.0 : std::acos(x) / M_PI * (1.0 - 1e-12));
         }
         ok = (int)res.size() == k && res.back().priority * (1.0 + 1e-9) < D - slack;
+        D_used = D;
     }
     if (ok && ix->tie_mode == 0) {
         dd.clear();
         for (const Cand &c : cands) dd.push_back(c.dist);
         if (history_dependent(dd.data(), dd.size(), k)) ok = false;  // the float32 path replays every row
+    }
+    if (tracing) {
+        szg_cert_record rec = cert_record(qi, SZG_CERT_SKETCH);
+        rec.keys = SZG_CERT_KEYS_SINGLE;
+        rec.sweep = 0;
+        rec.certified = ok ? 1 : 0;
+        rec.k = k;
+        for (const Shard *sh : ix->shards) rec.row_hi = std::max<uint64_t>(rec.row_hi, sh->first + sh->n_rows);
+        rec.thr_min = lb;
+        rec.D = D_used;
+        rec.slack = slack;
+        cert_emit(ix, rec, traced);
     }
     if (!ok) {
         redo.push_back(qi);
@@ -524,9 +545,11 @@ int search_topk_sketch(szg_index *ix, const double *queries, int n_queries, int 
         any |= m2[i] != nullptr;
     }
     if (handles)
-        rc = search_topk_impl(ix, q2.data(), m, k, nullptr, r2.data(), d2.data(), c2.data(), nullptr, any ? h2.data() : nullptr);
+        rc = search_topk_impl(ix, q2.data(), m, k, nullptr, r2.data(), d2.data(), c2.data(), nullptr, any ? h2.data() : nullptr,
+                              call.redo.data());
     else
-        rc = search_topk_impl(ix, q2.data(), m, k, nullptr, r2.data(), d2.data(), c2.data(), any ? m2.data() : nullptr);
+        rc = search_topk_impl(ix, q2.data(), m, k, nullptr, r2.data(), d2.data(), c2.data(), any ? m2.data() : nullptr, nullptr,
+                              call.redo.data());
     if (rc) return rc;
     for (int i = 0; i < m; i++) {
         memcpy(out_rows + (size_t)call.redo[i] * k, &r2[(size_t)i * k], sizeof(uint64_t) * k);

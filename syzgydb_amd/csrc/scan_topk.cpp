@@ -313,6 +313,19 @@ int finish_timing(szg_index *ix, Ctx *c)
     return SZG_OK;
 }
 
+// ListKeys as the certificate trace names them (SZG_CERT_KEYS_*)
+static int cert_keys(ListKeys k)
+{
+    switch (k) {
+    case ListKeys::Single: return SZG_CERT_KEYS_SINGLE;
+    case ListKeys::SharedInt8: return SZG_CERT_KEYS_SHARED_INT8;
+    case ListKeys::SharedBf16: return SZG_CERT_KEYS_SHARED_BF16;
+    case ListKeys::Bf16Band: return SZG_CERT_KEYS_BF16_BAND;
+    case ListKeys::Bf16Rescored: return SZG_CERT_KEYS_BF16_RESCORED;
+    }
+    return -1;
+}
+
 // candidates of staged query `slot` from a finished top-k pass, each with the upper bound of its
 // real-number key; *lb = a lower bound of the real-number key of every eligible row of the shard that
 // is NOT among them (+inf if every eligible row is).  `m` = the query's constants with the flags
@@ -367,10 +380,29 @@ void gather_topk(const szg_index *ix, const Shard *sh, const Ctx *c, const QMeta
 // with key <= thr_key, reranked exactly.  Synchronous; grows the buffer and
 // reruns on overflow.
 int run_collect(szg_index *ix, Shard *sh, Ctx *c, int slot, float thr_key, bool has_allow,
-                std::vector<Cand> *cands)
+                std::vector<Cand> *cands, const CertTag *tag)
 {
     HIPCHK(hipSetDevice(sh->device));
     if (sh->n_rows == 0) return SZG_OK;
+    // certificate trace: the sweep's threshold and every hit with its key, as the single-query kernel produced them
+    auto trace = [&](uint32_t count) {
+        if (!cert_room(ix, count)) return;  // (counted as dropped: nothing is gathered for a record that cannot be kept)
+        szg_cert_record rec = cert_record(tag->query, tag->pass);
+        rec.sweep = 0;
+        rec.row_lo = sh->first;
+        rec.row_hi = sh->first + sh->n_rows;
+        rec.thr = (double)thr_key;
+        QMeta single = c->meta[slot];
+        single.mq = single.mq_int = single.mq_bf16 = false;
+        rec.eps = key_eps(ix, thr_key, single);
+        std::vector<szg_cert_entry> ent(count);
+        for (uint32_t i = 0; i < count; i++) {
+            const szg::RerankOut &r = c->h_out[i];
+            const float key = szg::key_from_ordered(r.ukey);
+            ent[i] = szg_cert_entry{sh->first + r.row, r.dist, (double)key + key_eps(ix, key, single), key, 0u};
+        }
+        cert_emit(ix, rec, ent);
+    };
     size_t want = std::max<size_t>(c->d_collect.capacity(), 1u << 16);
     for (;;) {
         int rc = c->d_collect.ensure(want);
@@ -399,7 +431,10 @@ int run_collect(szg_index *ix, Shard *sh, Ctx *c, int slot, float thr_key, bool 
             want = (size_t)count + count / 8 + 1024;
             continue;
         }
-        if (count == 0) return SZG_OK;
+        if (count == 0) {
+            if (tag) trace(0);
+            return SZG_OK;
+        }
         rc = c->d_out.ensure((size_t)count);
         if (rc) return rc;
         rc = c->h_out.ensure((size_t)count);
@@ -415,6 +450,7 @@ int run_collect(szg_index *ix, Shard *sh, Ctx *c, int slot, float thr_key, bool 
             const szg::RerankOut &r = c->h_out[i];
             cands->push_back(Cand{sh->first + r.row, r.dist, szg::key_from_ordered(r.ukey), 0.0});
         }
+        if (tag) trace(count);
         return SZG_OK;
     }
 }
@@ -760,6 +796,7 @@ void note_stage_times(szg_index *ix, double t_prep0, double t_enq0)
 // stage() prepares and enqueues a batch on every shard; finish() waits for it and runs the reference's result
 // assembly per query (settle()).
 struct TopkBatch : Batch {
+    std::vector<uint8_t> traced;  // certificate trace: the query's first pass is on record (a deferred query settles twice)
     std::vector<QMeta> meta;  // the queries' constants, with the flags of the path the batch was staged for
     bool bf16 = false;        // the shared sweep is the bfloat16 one
     int kp_wide = 0;          // candidates per query of lists that hold bfloat16-sweep keys
@@ -774,9 +811,12 @@ struct TopkCall {
     double *out_dist;
     int32_t *out_count;
 
+    const int *trace_index = nullptr;  // certificate trace: the queries' indexes in the call this one was made for
+
     size_t n_sh = 0;
     int kp = 0;
     bool replay_all = false;  // K beyond the fused selection: every query takes the exact replay
+    bool tracing = false;     // the handle's certificate trace is on (read once per call)
 
     int run();
     TopkBatch plan(int q0);
@@ -924,6 +964,12 @@ int TopkCall::settle(TopkBatch &t, int j, std::vector<Cand> &cands, double thr_m
         if (nan_first) return;
         v.erase(std::remove_if(v.begin(), v.end(), [](const Cand &c) { return std::isnan(c.dist); }), v.end());
     };
+    std::vector<szg_cert_entry> traced;  // the candidates as the pass delivered them (the forced-in rows still among them)
+    const bool trace_now = tracing && !(j < (int)t.traced.size() && t.traced[j]);
+    if (trace_now) {
+        traced.reserve(cands.size());
+        for (const Cand &c : cands) traced.push_back(szg_cert_entry{c.row, c.dist, c.ub, c.key, 0u});
+    }
     drop_nan(cands);
     replay_topk(cands, k, res);
     // certification: every row outside the lists has a real-number key >= thr_min (the lists' own lower bound),
@@ -943,6 +989,21 @@ int TopkCall::settle(TopkBatch &t, int j, std::vector<Cand> &cands, double thr_m
     }
     if (ix->force_escalate && thr_min < INFINITY) certified = false;
     if (nan_first && ix->tie_mode == 0) certified = true;  // answered by the replay below
+    const int q_call = trace_index ? trace_index[t.first + j] : t.first + j;
+    if (trace_now) {
+        szg_cert_record rec = cert_record(q_call, SZG_CERT_TOPK);
+        for (size_t s = 0; s < n_sh; s++)
+            if (t.ctx[s]) rec.keys = (int32_t)cert_keys(t.ctx[s]->pass.keys);
+        rec.sweep = t.nb == 0 ? 0 : (t.bf16 ? 2 : 1);
+        rec.certified = certified ? 1 : 0;
+        rec.k = k;
+        for (const Shard *sh : ix->shards) rec.row_hi = std::max<uint64_t>(rec.row_hi, sh->first + sh->n_rows);
+        rec.thr_min = thr_min;
+        rec.kmax = kmax;
+        cert_emit(ix, rec, traced);
+        if (t.traced.empty()) t.traced.assign(t.nq, 0);
+        t.traced[j] = 1;
+    }
     if (!certified) {
         if (defer) {
             *defer = true;
@@ -976,7 +1037,8 @@ int TopkCall::settle(TopkBatch &t, int j, std::vector<Cand> &cands, double thr_m
         for (size_t s = 0; s < n_sh && rc == SZG_OK; s++) {
             Shard *sh = ix->shards[s];
             if (sh->n_rows == 0) continue;
-            rc = run_collect(ix, sh, t.ctx[s], j, thr_f, t.any_mask, &cands);
+            const CertTag tag{q_call, SZG_CERT_ESCALATION};
+            rc = run_collect(ix, sh, t.ctx[s], j, thr_f, t.any_mask, &cands, tracing ? &tag : nullptr);
         }
         *t_dev += now_us() - td;
         if (rc) return rc;
@@ -1077,6 +1139,7 @@ int TopkCall::finish(TopkBatch &t)
 int TopkCall::run()
 {
     n_sh = ix->shards.size();
+    tracing = cert_tracing(ix);
     kp = k + std::max(ix->slack_min, k / 2);
     // The reference bounds K by nothing (collection.go:606-619).  The fused selection keeps kp candidates per wave in
     // LDS; beyond that (kp > 4096 or 64 KiB of lists) every query of the call takes the exact replay: float64
@@ -1168,9 +1231,10 @@ int TopkCall::run()
 
 int search_topk_impl(szg_index *ix, const double *queries, int n_queries, int k, const uint64_t *allow_bits,
                      uint64_t *out_rows, double *out_dist, int32_t *out_count, const uint64_t *const *allow_ptrs,
-                     const szg_mask *const *handles)
+                     const szg_mask *const *handles, const int *trace_index)
 {
-    TopkCall call{ix, queries, n_queries, k, QueryMasks(ix, allow_bits, allow_ptrs, handles), out_rows, out_dist, out_count};
+    TopkCall call{ix, queries, n_queries, k, QueryMasks(ix, allow_bits, allow_ptrs, handles), out_rows, out_dist, out_count,
+                  trace_index};
     return call.run();
 }
 

@@ -713,7 +713,7 @@ class ScanIndex:
                 return out_rows[:n], out_dist[:n]
             return out_rows[:n], out_dist[:n], n
 
-    def _radius_csr(self, fn, name, queries, radii, allow, refetch=None, masks=None):
+    def _radius_csr(self, fn, name, queries, radii, allow, refetch=None, masks=None, capacity=None):
         q = np.ascontiguousarray(queries, dtype=np.float64)
         if q.ndim == 1:
             q = q.reshape(1, -1)
@@ -726,7 +726,8 @@ class ScanIndex:
         else:
             keep, allow_p = self._allow_arg(allow, nq)
             filt = (allow_p,)
-        cap = max(1 << 16, nq << 12)  # (a truncated call is answered again from scratch: start generous)
+        # (a truncated call is answered again from scratch: start generous, or with what the caller expects)
+        cap = max(1 << 16, nq << 12) if capacity is None else max(int(capacity), 1)
         while True:
             out_rows = np.empty(max(cap, 1), dtype=np.uint64)
             out_dist = np.empty(max(cap, 1), dtype=np.float64)
@@ -745,13 +746,16 @@ class ScanIndex:
             del keep
             return [(out_rows[int(off[i]):int(off[i + 1])], out_dist[int(off[i]):int(off[i + 1])]) for i in range(nq)]
 
-    def search_radius_batch(self, queries, radii, allow=None, masks=None):
+    def search_radius_batch(self, queries, radii, allow=None, masks=None, capacity=None):
         """Radius searches for a batch (radii: one value or one per query): a list of (rows, dist) per query,
-        ascending distance.  The collect sweeps of the batch share query-major launches.  masks: as search_topk's."""
+        ascending distance.  The collect sweeps of the batch share query-major launches.  masks: as search_topk's.
+        capacity: hits of the whole batch the first attempt has room for (default 64 Ki, or 4 Ki per query); a batch
+        with more is searched a second time with room for all."""
         if masks is not None:
             return self._radius_csr(self._L.szg_search_radius_masked, "szg_search_radius_masked", queries, radii, allow,
-                                    masks=masks)
-        return self._radius_csr(self._L.szg_search_radius_batch, "szg_search_radius_batch", queries, radii, allow)
+                                    masks=masks, capacity=capacity)
+        return self._radius_csr(self._L.szg_search_radius_batch, "szg_search_radius_batch", queries, radii, allow,
+                                capacity=capacity)
 
     # -- one process per GPU: the exchange inside the library (syzgydb_amd/sharded.py: Comm) ------------
     def attach_comm(self, comm):
@@ -797,6 +801,29 @@ class ScanIndex:
 
     def reset_stats(self):
         check(self._L.szg_reset_stats(self._h), "szg_reset_stats")
+
+    def trace_certificates(self, on=True):
+        """Test hook: keep what every pass hands to certification (szg_debug_trace_certificates).  Switching clears."""
+        check(self._L.szg_debug_trace_certificates(self._h, int(bool(on))), "szg_debug_trace_certificates")
+
+    def certificates(self):
+        """The records of the calls made since the trace was switched on or last read, and empties the trace:
+        (records, entries, dropped) -- two structured arrays with the fields of szg_cert_record (`pass` is named
+        pass_) and szg_cert_entry; record r's entries are entries[r.first_entry : r.first_entry + r.n_entries].
+        dropped: records that did not fit the handle's caps since the trace was switched on."""
+        n_rec, n_ent, dropped = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+        while True:   # (a record that another thread adds between the count and the copy: count again)
+            check(self._L.szg_debug_certificates(self._h, None, 0, None, 0, ctypes.byref(n_rec), ctypes.byref(n_ent),
+                                                 ctypes.byref(dropped)), "szg_debug_certificates")
+            recs = np.zeros(max(1, n_rec.value), dtype=np.dtype(_lib.SzgCertRecord))
+            ents = np.zeros(max(1, n_ent.value), dtype=np.dtype(_lib.SzgCertEntry))
+            rc = self._L.szg_debug_certificates(self._h, recs.ctypes.data_as(ctypes.POINTER(_lib.SzgCertRecord)), recs.size,
+                                                ents.ctypes.data_as(ctypes.POINTER(_lib.SzgCertEntry)), ents.size,
+                                                ctypes.byref(n_rec), ctypes.byref(n_ent), ctypes.byref(dropped))
+            if rc != _lib.SZG_E_TRUNCATED:
+                break
+        check(rc, "szg_debug_certificates")
+        return recs[: n_rec.value], ents[: n_ent.value], int(dropped.value)
 
     def set_option(self, name, value):
         check(self._L.szg_set_option(self._h, name.encode(), int(value)), "szg_set_option")

@@ -67,6 +67,31 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(L, name), "libsyzgy_scan.so does not export %s" % name
 
 
+def test_certificate_trace_surface():
+    """The certificate trace's two entry points are exported and bound, refuse a null handle before touching anything,
+    and the Python mirrors of szg_cert_record / szg_cert_entry have the header's layout (104 and 32 bytes, the
+    field order of the declaration)."""
+    from syzgydb_amd import _lib
+    L = _lib.load()
+    for name in ("szg_debug_trace_certificates", "szg_debug_certificates"):
+        assert name in _lib.EXPORTS and hasattr(L, name)
+    assert L.szg_debug_trace_certificates(None, 1) == _lib.SZG_E_INVALID
+    n = ctypes.c_uint64(7)
+    assert L.szg_debug_certificates(None, None, 0, None, 0, ctypes.byref(n), None, None) == _lib.SZG_E_INVALID
+    assert n.value == 7
+    assert ctypes.sizeof(_lib.SzgCertRecord) == 104 and ctypes.sizeof(_lib.SzgCertEntry) == 32
+    hdr = open(os.path.join(ROOT, "include", "syzgy_scan.h")).read()
+    for struct, mirror in (("szg_cert_record", _lib.SzgCertRecord), ("szg_cert_entry", _lib.SzgCertEntry)):
+        body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (struct, struct), hdr, flags=re.S).group(1)
+        body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+        names = [x.strip() for decl in body.split(";") if decl.strip() for x in decl.split(None, 1)[1].split(",")]
+        assert names == [f[0].rstrip("_") for f in mirror._fields_], (struct, names)
+    for name, value in (("SZG_CERT_TOPK", 0), ("SZG_CERT_SKETCH", 1), ("SZG_CERT_ESCALATION", 2), ("SZG_CERT_RADIUS_SINGLE", 3),
+                        ("SZG_CERT_RADIUS_SHARED", 4), ("SZG_CERT_KEYS_SINGLE", 0), ("SZG_CERT_KEYS_SHARED_INT8", 1),
+                        ("SZG_CERT_KEYS_SHARED_BF16", 2), ("SZG_CERT_KEYS_BF16_BAND", 3), ("SZG_CERT_KEYS_BF16_RESCORED", 4)):
+        assert getattr(_lib, name) == value and re.search(r"#define %s %d\b" % (name, value), hdr), name
+
+
 def test_error_paths_without_gpu_work():
     from syzgydb_amd import _lib
     L = _lib.load()
