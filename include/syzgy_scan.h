@@ -666,6 +666,13 @@ int szg_reset_stats(szg_index *ix);
  *                             those of 1, bit for bit.  0 = automatic (4), 1 = one query per row read, 2 / 4 = that
  *                             group size where the launch qualifies; a launch of one query always reads at 1.  Other
  *                             row widths, radius / escalation sweeps, masked launches and longer lists are always 1
+ *     scan_group_ring     0   16-byte loads a lane of a grouped launch (scan_group) keeps in flight.  A group of G
+ *                             queries spends G times the arithmetic on every piece it loads, so a load has less time
+ *                             to return per unit of work than in the kernel without groups; the grouped kernels of
+ *                             row shapes with 12 pieces per lane (768 dimensions) therefore exist at two depths, 4
+ *                             (the depth of the kernel without groups) and 6.  0 = automatic (6), or one of the two;
+ *                             other values are refused.  Launches without groups and the other shapes keep their one
+ *                             depth whatever the value.  Keys, lists and answers do not depend on it
  *     scan_norms          0   launches that form groups (scan_group) take every row's norm from a resident array --
  *                             4 bytes per row, brought up to date before the sweep is enqueued when rows were added --
  *                             instead of summing it in the sweep; the value is the same float, so keys do not change.
@@ -681,7 +688,11 @@ int szg_reset_stats(szg_index *ix);
  *                             apply the masks at the row finish; selective masks (and 0) compact the row steps that
  *                             hold a passing row first
  *     serialize_scans     1   sweeps of one shard never overlap each other (every sweep has the whole HBM bandwidth)
- *     contexts            4   batches in flight per shard
+ *     contexts            4   batches in flight per shard.  A call with one sweep per query uses at most the first
+ *                             GPU_MAX_HW_QUEUES - 1 of them (3 at HIP's default of four hardware queues), so that
+ *                             the scan stream and every context's stream in use have a hardware queue of their own --
+ *                             as far as the runtime hands streams to queues in the order of their creation, which it
+ *                             does not promise
  *   sketch pre-pass (float32 rows)
  *     sketch              2   2 = automatic (the default): a handle of float32 rows with >= max(65 536,
  *                             sketch_min_rows) rows keeps an 8-bit sketch of every row (+25 % memory, built on the
@@ -778,8 +789,23 @@ int szg_debug_scan_group(int dim, int quant_bits, int kp, int collect, int maske
                          int queries_per_launch, int32_t *group, uint64_t *lds_bytes, int32_t *passes);
 
 /*
+ * Test hook, host only: *fits = the sketch sweep's one-launch short-list merge serves n_lists block lists of m entries
+ * at kp candidates; *sorts = the most entries under its threshold (the kp-th smallest first entry) that its selection
+ * sorts in one network -- with more, and always when *sorts < kp, the launch runs the tournament.
+ */
+int szg_debug_merge_short_plan(int n_lists, int m, int kp, int32_t *fits, int32_t *sorts);
+
+/*
+ * Test hook, host only: *ring_depth = the ring depth the launch of a one-sweep call of n_queries (<= 16) queries takes
+ * under options scan_group and scan_group_ring; depths[0 .. *n_depths) (room for 2) = the values of scan_group_ring the
+ * library accepts beside 0.
+ */
+int szg_debug_scan_group_ring(int dim, int quant_bits, int kp, int scan_group, int n_queries, int scan_group_ring,
+                              int32_t *ring_depth, int32_t *depths, int32_t *n_depths);
+
+/*
  * Test hook, host only: would szg_set_option accept `value` for the one-sweep kernel's option `name` (scan_group,
- * scan_norms, sketch_planes)?  SZG_OK, or SZG_E_INVALID with szg_set_option's text; any other name is refused.
+ * scan_group_ring, scan_norms, sketch_planes)?  SZG_OK, or SZG_E_INVALID with szg_set_option's text; any other name is refused.
  */
 int szg_debug_option_check(const char *name, int64_t value);
 

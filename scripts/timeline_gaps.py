@@ -1,0 +1,53 @@
+"""From a rocprofv3 kernel trace (+ memory-copy trace) of the headline: the gaps between consecutive grouped
+sweeps, what runs inside them and whether merges / reranks overlap a sweep.  usage: timeline_gaps.py <dir>"""
+import csv, glob, re, sys, statistics
+
+path = sys.argv[1]
+ev = []
+for f in glob.glob(path + "/**/*kernel_trace.csv", recursive=True):
+    for r in csv.DictReader(open(f)):
+        n = re.sub(r"szg::\(anonymous namespace\)::", "", r["Kernel_Name"])
+        n = re.sub(r"\(.*", "", n).replace("void ", "")
+        ev.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), n[:60], "q" + r.get("Queue_Id", "")))
+for f in glob.glob(path + "/**/*memory_copy_trace.csv", recursive=True):
+    for r in csv.DictReader(open(f)):
+        ev.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), "copy " + r.get("Direction", ""), "dma"))
+ev.sort()
+sw = [e for e in ev if e[2].startswith("scan_kernel<8") and ", 4, 2, true" in e[2]]
+if not sw:
+    sw = [e for e in ev if e[2].startswith("scan_kernel<8")]
+print("sweeps:", len(sw), "name:", sw[0][2] if sw else None)
+sw = sw[len(sw) // 4:]  # the timed region's (warm-up launches come first)
+durs = [(e - s) / 1e3 for s, e, _, _ in sw]
+print("sweep us: median %.1f min %.1f max %.1f" % (statistics.median(durs), min(durs), max(durs)))
+gaps = []
+for a, b in zip(sw, sw[1:]):
+    gaps.append((b[0] - a[1]) / 1e3)
+print("gap us: median %.1f mean %.1f min %.1f max %.1f (n=%d)" % (statistics.median(gaps), statistics.mean(gaps), min(gaps), max(gaps), len(gaps)))
+gs = sorted(gaps)
+print("gap percentiles 10/25/50/75/90: " + " ".join("%.1f" % gs[int(len(gs) * p)] for p in (0.1, 0.25, 0.5, 0.75, 0.9)))
+# overlap of tails with sweeps
+ov = {}
+for s, e, n, q in ev:
+    if n.startswith("scan_kernel"):
+        continue
+    if s < sw[0][0] or e > sw[-1][1]:
+        continue
+    o = 0
+    for a, b, _, _ in sw:
+        lo, hi = max(s, a), min(e, b)
+        if hi > lo:
+            o += hi - lo
+    d = ov.setdefault(n, [0, 0.0, 0.0])
+    d[0] += 1
+    d[1] += (e - s) / 1e3
+    d[2] += o / 1e3
+print("%-52s %6s %10s %10s" % ("inside the timed window", "calls", "total us", "of it beside a sweep"))
+for n, (c, t, o) in sorted(ov.items(), key=lambda x: -x[1][1]):
+    print("%-52s %6d %10.1f %10.1f" % (n, c, t, o))
+# one window in full
+i0 = ev.index(sw[4]) if len(sw) > 8 else 0
+t0 = ev[i0][0]
+print("--- a window of the timeline (us from its first sweep) ---")
+for s, e, n, q in ev[i0:i0 + 40]:
+    print("%9.1f  +%7.1f  %-5s %s" % ((s - t0) / 1e3, (e - s) / 1e3, q, n))

@@ -54,6 +54,7 @@ EXPORTS = [
     "szg_column_set_rows", "szg_debug_bulk_plan",
     # host-only test hook
     "szg_debug_scan_plan", "szg_debug_scan_group", "szg_debug_reorder_plan", "szg_debug_option_check",
+    "szg_debug_scan_group_ring", "szg_debug_merge_short_plan",
     # who owns device memory: the counters and the refusal countdown (added under ABI 4)
     "szg_debug_device_memory", "szg_debug_refuse_device_alloc",
     # the certificate trace: what each pass handed to certification (added under ABI 4)
@@ -381,6 +382,12 @@ def load():
         L.szg_debug_scan_group.restype = ctypes.c_int
         L.szg_debug_scan_group.argtypes = [ctypes.c_int] * 8 + [ctypes.POINTER(ctypes.c_int32), u64p,
                                                                 ctypes.POINTER(ctypes.c_int32)]
+    if hasattr(L, "szg_debug_scan_group_ring"):
+        L.szg_debug_scan_group_ring.restype = ctypes.c_int
+        L.szg_debug_scan_group_ring.argtypes = [ctypes.c_int] * 6 + [ctypes.POINTER(ctypes.c_int32)] * 3
+    if hasattr(L, "szg_debug_merge_short_plan"):
+        L.szg_debug_merge_short_plan.restype = ctypes.c_int
+        L.szg_debug_merge_short_plan.argtypes = [ctypes.c_int] * 3 + [ctypes.POINTER(ctypes.c_int32)] * 2
     if hasattr(L, "szg_debug_option_check"):
         L.szg_debug_option_check.restype = ctypes.c_int
         L.szg_debug_option_check.argtypes = [ctypes.c_char_p, ctypes.c_int64]

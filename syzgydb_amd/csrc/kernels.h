@@ -148,6 +148,8 @@ struct ScanArgs {
                                 // that takes a G > 1 variant reads them instead of summing the norm in the sweep.
     int planes;                 // 8-bit rows: int8 digit planes the queries carry, 3 (0 means 3) or 2 -- the h plane of
                                 // the image is all zero; G > 1 variants then neither stage nor read it
+    int group_ring;             // option scan_group_ring: ring depth of the G > 1 row-shape kernels that carry more than
+                                // one (scan_variant); 0 = automatic
 };
 
 // Which scan_kernel instantiation a launch takes: decided on the host by scan_variant -- the launcher dispatches on
@@ -163,8 +165,30 @@ struct ScanVariant {
 constexpr int kScanGroupAuto = 4;
 // group: the scan_group option (0 = automatic), n_queries: the launch's, block: its threads (the group's query images
 // -- of `planes` digit planes each -- and lists have to fit 64 KiB of LDS)
+// group_ring: the scan_group_ring option (0 = automatic)
 ScanVariant scan_variant(int qbits, const RowMap &m, bool tiled, int kp, bool collect, bool masked, int ring,
-                         bool no_shape_kernels, int group = 1, int n_queries = 1, int block = 256, int planes = 3);
+                         bool no_shape_kernels, int group = 1, int n_queries = 1, int block = 256, int planes = 3,
+                         int group_ring = 0);
+// Ring depths of the G > 1 kernels.  A row-shape kernel of P pieces per lane exists at its shape's own depth (the
+// G = 1 kernel's) and, where kGroupRingAlt divides P and differs from it, at kGroupRingAlt as well: scan_group_ring
+// picks one of the two, 0 takes kGroupRingAuto where the shape has it and the shape's own depth elsewhere.
+#ifndef SZG_GROUP_RING_ALT
+#define SZG_GROUP_RING_ALT 6
+#endif
+#ifndef SZG_GROUP_RING_AUTO
+#define SZG_GROUP_RING_AUTO SZG_GROUP_RING_ALT
+#endif
+constexpr int kGroupRingBase = 4, kGroupRingAlt = SZG_GROUP_RING_ALT, kGroupRingAuto = SZG_GROUP_RING_AUTO;
+static_assert(kGroupRingAuto == kGroupRingBase || kGroupRingAuto == kGroupRingAlt, "automatic: a depth that is compiled");
+constexpr bool scan_group_ring_known(int64_t v) { return v == 0 || v == kGroupRingBase || v == kGroupRingAlt; }
+// depth of the G > 1 kernel of a shape whose own depth is d, P pieces per lane, under option value `want`
+constexpr int scan_group_ring_of(int p, int d, int want)
+{
+    const bool has_alt = p % kGroupRingAlt == 0 && kGroupRingAlt != d;
+    if (!has_alt) return d;
+    const int w = want == 0 ? kGroupRingAuto : want;
+    return w == kGroupRingAlt ? kGroupRingAlt : d;
+}
 inline bool scan_masked(const ScanArgs &a) { return a.live_bits != nullptr || a.allow_bits != nullptr; }
 // passes over the rows that launch_scan makes for `a`: one per group of its queries
 int scan_passes(int qbits, const ScanArgs &a, int block);
@@ -274,6 +298,16 @@ hipError_t launch_merge(const uint64_t *in, int n_lists, int kp, int n_queries, 
 // kp best per query at out + q * out_stride, followed by the drop bound at [kp]: the smallest m-th entry of a full
 // list (kInvalidCand if none is full).  merge_short_fits: n_lists <= 1024 and the lists fit one block's LDS.
 bool merge_short_fits(int n_lists, int m, int kp);
+// The selection's buffer: words of LDS the kernel compacts the entries under its threshold into (the tournament's
+// per-group result lists, less two control words), and the most entries its bitonic network sorts -- the largest power
+// of two that fits.  More entries under the threshold than that: the tournament.  (0: the launch always takes it.)
+constexpr int merge_short_cap(int n_lists, int kp) { return (n_lists + 63) / 64 * kp - 2; }
+constexpr int merge_short_sorts(int n_lists, int kp)
+{
+    int s = 0;
+    for (int p = 1; p <= merge_short_cap(n_lists, kp); p <<= 1) s = p;
+    return s;
+}
 hipError_t launch_merge_short(const uint64_t *in, int n_lists, int m, int kp, int n_queries, uint64_t *out,
                               int out_stride, hipStream_t stream);
 

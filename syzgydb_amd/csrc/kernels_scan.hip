@@ -1068,8 +1068,16 @@ __device__ __forceinline__ uint64_t wave_min_cand(uint64_t v)
 // Short-list merge (the sketch sweep): ONE block per query (blockIdx.y) selects the kp best of the
 // n_lists sorted block lists of m entries each (m < kp) and writes them, sorted, to out[0, kp); out[kp] gets the drop
 // bound -- the smallest m-th entry of a FULL block list (kInvalidCand if no list is full): every row a block did not
-// output is above its list's m-th entry.  Stage 1: wave w runs a tournament over lists [64w, 64w + 64), one list
-// per lane, each lane's next head fetched one advance ahead; stage 2: wave 0 runs one over the <= 16 results.
+// output is above its list's m-th entry.
+// By selection: let h be the kp-th smallest of the lists' FIRST entries (kInvalidCand with fewer than kp non-empty
+// lists).  kp lists start at or below h, so at least kp entries are <= h and the kp best are among the entries <= h --
+// typically little more than kp of them, since the best rows fall to the blocks almost one each.  Every thread finds
+// the rank of its list's first entry among all first entries (the one of rank kp - 1 publishes h), the entries <= h
+// are compacted into LDS in any order, wave 0 sorts them with one bitonic network and writes the first kp.  Entries
+// are unique, so the sorted result does not depend on the order of the compaction.
+// By tournament, when more entries are <= h than the network's buffer holds (the sel array below, less two words):
+// stage 1: wave w runs a tournament over lists [64w, 64w + 64), one list per lane, each lane's next head fetched one
+// advance ahead; stage 2: wave 0 runs one over the <= 16 results.
 // Needs n_lists <= 1024 and merge_short_lds(n_lists, m, kp) <= 64 KiB (merge_short_fits).
 __global__ __launch_bounds__(1024) void merge_short_kernel(const uint64_t *in, int n_lists, int m, int kp,
                                                            uint64_t *out, int out_stride)
@@ -1084,7 +1092,66 @@ __global__ __launch_bounds__(1024) void merge_short_kernel(const uint64_t *in, i
     out += (size_t)blockIdx.y * out_stride;
     const int total = n_lists * m;
     for (int i = tid; i < total; i += blockDim.x) lists[i] = in[i];
+    // the selection's words in sel: the entries <= h from the front, h and their count in its last two
+    const int cap = merge_short_cap(n_lists, kp);
+    uint64_t *h_word = sel + cap;
+    uint32_t *count_word = reinterpret_cast<uint32_t *>(sel + cap + 1);
+    if (tid == 0) {
+        *h_word = kInvalidCand;
+        *count_word = 0u;
+    }
     __syncthreads();
+    {
+        const bool have = tid < n_lists;
+        const uint64_t *my = lists + (size_t)(have ? tid : 0) * m;
+        // (kInvalidCand is the largest value: lists that are not full drop out of the minimum by themselves)
+        const uint64_t drop = wave_min_cand<false>(have ? my[m - 1] : kInvalidCand);
+        if (lane == 0 && wave < ngroups) drops[wave] = drop;
+        const uint64_t first = have ? my[0] : kInvalidCand;
+        if (first != kInvalidCand) {
+            int rank = 0;
+            for (int j = 0; j < n_lists; j++) rank += lists[(size_t)j * m] < first ? 1 : 0;
+            if (rank == kp - 1) *h_word = first;  // (unique entries: one thread at most)
+        }
+        __syncthreads();
+        const uint64_t h = *h_word;
+        int c = 0;
+        if (have)
+            while (c < m && my[c] <= h && my[c] != kInvalidCand) c++;
+        if (c) {
+            const int at = (int)atomicAdd(count_word, (uint32_t)c);
+            if (at + c <= cap)
+                for (int i = 0; i < c; i++) sel[at + i] = my[i];
+        }
+        __syncthreads();
+        const int found = (int)*count_word;
+        int S = 1;
+        while (S < found) S <<= 1;
+        if (S <= cap) {
+            if (wave != 0) return;
+            for (int i = found + lane; i < S; i += kWave) sel[i] = kInvalidCand;
+            __builtin_amdgcn_wave_barrier();
+            // one wave: its LDS accesses complete in program order, a step's exchanges touch disjoint pairs
+            for (int k = 2; k <= S; k <<= 1)
+                for (int j = k >> 1; j > 0; j >>= 1) {
+                    for (int p = lane; p < S / 2; p += kWave) {
+                        const int i = ((p & ~(j - 1)) << 1) | (p & (j - 1));
+                        const int l = i | j;
+                        const uint64_t a = sel[i], b = sel[l];
+                        if ((a > b) == ((i & k) == 0)) {
+                            sel[i] = b;
+                            sel[l] = a;
+                        }
+                    }
+                    __builtin_amdgcn_wave_barrier();
+                }
+            for (int i = lane; i < kp; i += kWave) out[i] = i < found ? sel[i] : kInvalidCand;
+            const uint64_t dmin = wave_min_cand<true>(lane < ngroups ? drops[lane] : kInvalidCand);
+            if (lane == 0) out[kp] = dmin;
+            return;
+        }
+        __syncthreads();  // (every thread has read the count: the tournament takes sel and drops over)
+    }
     if (wave < ngroups) {
         const int l = wave * kWave + lane;
         const bool have = l < n_lists;
@@ -1219,9 +1286,16 @@ template <int QBITS, int METRIC, bool COLLECT, bool MASKED, int G, int PL = 3, b
 hipError_t launch_scan_group(const ScanArgs &a, const ScanVariant &v, dim3 g, dim3 b, size_t lds, hipStream_t stream)
 {
     if constexpr (!MASKED) {
+// (G > 1: the shape's kernel at the group ring's other depth, where it has one -- scan_group_ring_of, kernels.h)
 #define SZG_TRY_SHAPE(l, p, d)                                                                 \
-    if (v.shaped == l * 100 + p)                                                               \
-        return launch_shaped<QBITS, METRIC, COLLECT, l, p, SZG_SHAPE_RING(d), G, PL, NF>(a, v.nontemporal != 0, g, b, lds, stream);
+    if (v.shaped == l * 100 + p) {                                                             \
+        if constexpr (G > 1 && scan_group_ring_of(p, SZG_SHAPE_RING(d), kGroupRingAlt) != SZG_SHAPE_RING(d)) {        \
+            if (v.ring_depth == kGroupRingAlt)                                                 \
+                return launch_shaped<QBITS, METRIC, COLLECT, l, p, kGroupRingAlt, G, PL, NF>(a, v.nontemporal != 0, g, b, lds, stream); \
+        }                                                                                      \
+        if (v.ring_depth != SZG_SHAPE_RING(d)) return hipErrorInvalidValue;                    \
+        return launch_shaped<QBITS, METRIC, COLLECT, l, p, SZG_SHAPE_RING(d), G, PL, NF>(a, v.nontemporal != 0, g, b, lds, stream); \
+    }
         if constexpr (QBITS == 4) {
             SZG_SHAPES_4(SZG_TRY_SHAPE)
         } else if constexpr (QBITS == 8) {
@@ -1252,7 +1326,7 @@ hipError_t launch_scan_qmcm(const ScanArgs &a, int grid, int block, hipStream_t 
 {
     const dim3 g(grid), b(block);
     const ScanVariant v = scan_variant(QBITS, a.map, a.tiled != 0, a.kp, COLLECT, MASKED, a.ring, a.no_shape_kernels != 0,
-                                       a.group, a.n_queries, block, a.planes);
+                                       a.group, a.n_queries, block, a.planes, a.group_ring);
     const size_t lds = scan_lds_bytes(QBITS, a.map, COLLECT ? 0 : a.kp, block, v.group, a.planes);
     if constexpr (QBITS == 8 && !COLLECT && !MASKED) {
         // G > 1: the form of the kernel -- two digit planes where the queries carry two (bit 0), resident norms where
@@ -1325,9 +1399,10 @@ SZG_DECL_SCAN(64)
 // The instantiation a launch takes.  Row-shape kernels serve unmasked sweeps over dense maps whose lists stay in
 // registers; everything else is the any-shape kernel, with the deep ring when the lists live in LDS (kp > 64).
 ScanVariant scan_variant(int qbits, const RowMap &m, bool tiled, int kp, bool collect, bool masked, int ring,
-                         bool no_shape_kernels, int group, int n_queries, int block, int planes)
+                         bool no_shape_kernels, int group, int n_queries, int block, int planes, int group_ring)
 {
     ScanVariant v{};
+    [[maybe_unused]] int shape_p = 0;  // pieces per lane of the row-shape kernel taken
     v.deep = ((!collect && kp > 64) || ring >= 8) ? 1 : 0;
     v.ring_depth = v.deep ? kRingDeep : kRingShort;
     v.nontemporal = (m.L >= 8 || tiled) ? 1 : 0;  // whole 128-byte lines per load instruction (load_piece)
@@ -1336,6 +1411,7 @@ ScanVariant scan_variant(int qbits, const RowMap &m, bool tiled, int kp, bool co
     if (m.L == l && m.P == p) {                \
         v.shaped = l * 100 + p;                \
         v.ring_depth = SZG_SHAPE_RING(d);      \
+        shape_p = p;                           \
     }
         switch (qbits) {
         case 4: SZG_SHAPES_4(SZG_IS_SHAPE) break;
@@ -1356,6 +1432,9 @@ ScanVariant scan_variant(int qbits, const RowMap &m, bool tiled, int kp, bool co
         while (g > 1 && g / 2 >= n_queries) g /= 2;
         while (g > 1 && scan_lds_bytes(qbits, m, kp, block, g, planes) > 64u * 1024u) g /= 2;
         v.group = g;
+        // The grouped row-shape kernels spend G times the arithmetic per piece, so a slot of the ring comes round
+        // G times later than in the G = 1 kernel: they carry a depth of their own (option scan_group_ring).
+        if (g > 1 && v.shaped) v.ring_depth = scan_group_ring_of(shape_p, v.ring_depth, group_ring);
     }
     return v;
 }
@@ -1372,7 +1451,7 @@ size_t scan_lds_bytes(int qbits, const RowMap &m, int kp, int block, int group, 
 int scan_group_of(int qbits, const ScanArgs &a, int block)
 {
     return scan_variant(qbits, a.map, a.tiled != 0, a.kp, a.collect != 0, scan_masked(a), a.ring, a.no_shape_kernels != 0,
-                        a.group, a.n_queries, block, a.planes)
+                        a.group, a.n_queries, block, a.planes, a.group_ring)
         .group;
 }
 

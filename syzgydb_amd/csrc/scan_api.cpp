@@ -593,4 +593,39 @@ int szg_debug_scan_group(int dim, int quant_bits, int kp, int collect, int maske
     return SZG_OK;
 }
 
+// test hook, host only: does the one-launch short-list merge serve (n_lists, m, kp), and how many entries under its
+// threshold its selection sorts at most (more: the tournament; fewer than kp: the tournament always)
+int szg_debug_merge_short_plan(int n_lists, int m, int kp, int32_t *fits, int32_t *sorts)
+{
+    if (!fits || !sorts) return fail(SZG_E_INVALID, "null argument");
+    *fits = szg::merge_short_fits(n_lists, m, kp) ? 1 : 0;
+    *sorts = *fits ? szg::merge_short_sorts(n_lists, kp) : 0;
+    return SZG_OK;
+}
+
+// test hook, host only: the ring depth a one-sweep launch of n_queries queries takes under options scan_group and
+// scan_group_ring (scan_variant's answer), and the values of scan_group_ring this library accepts beside 0
+int szg_debug_scan_group_ring(int dim, int quant_bits, int kp, int scan_group, int n_queries, int scan_group_ring,
+                              int32_t *ring_depth, int32_t *depths, int32_t *n_depths)
+{
+    if (!ring_depth || !depths || !n_depths) return fail(SZG_E_INVALID, "null argument");
+    if (kp < 0 || n_queries < 1 || n_queries > szg::kMaxSweepsPerLaunch) return fail(SZG_E_INVALID, "kp or n_queries out of range");
+    if (scan_group != 0 && scan_group != 1 && scan_group != 2 && scan_group != 4)
+        return fail(SZG_E_INVALID, "scan_group is 0, 1, 2 or 4");
+    if (!szg::scan_group_ring_known(scan_group_ring))
+        return fail(SZG_E_INVALID, "scan_group_ring is 0 or a ring depth the library carries");
+    RowFormat f;
+    const int rc = row_format(dim, quant_bits, &f);
+    if (rc == SZG_E_UNSUPPORTED) return fail(rc, "dimension too large for the LDS-resident query");
+    if (rc) return rc;
+    const LaunchGeom g = scan_geometry(quant_bits, f.map, f.row_bytes, f.layout.tiled != 0, 1u << 22, 256, kp);
+    *ring_depth = szg::scan_variant(quant_bits, f.map, f.layout.tiled != 0, kp, false, false, szg_index::ring,
+                                    !szg_index::shape_kernels, scan_group, n_queries, g.block, 3, scan_group_ring)
+                      .ring_depth;
+    depths[0] = szg::kGroupRingBase;
+    depths[1] = szg::kGroupRingAlt;
+    *n_depths = szg::kGroupRingAlt != szg::kGroupRingBase ? 2 : 1;
+    return SZG_OK;
+}
+
 }  // extern "C"

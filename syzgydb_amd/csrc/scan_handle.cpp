@@ -40,24 +40,46 @@ void ctx_free(Ctx *c)  // (the buffers free themselves)
 }
 
 // the one place a context is handed out (sh->mu held): the record of the batch that had it before ends here
-static Ctx *ctx_take(Shard *sh)
+// (limit > 0: the most recently freed context among the shard's first `limit`; null when none of them is free -- the
+// caller waits for one.  Should none of them be in rotation at all -- the "contexts" option parks from the highest
+// number down, so this takes an option set while a search held contexts -- the limit is void: any free context)
+static Ctx *ctx_take(Shard *sh, int limit)
 {
-    Ctx *c = sh->free_ctx.back();
-    sh->free_ctx.pop_back();
+    if (limit > 0) {
+        size_t eligible = 0;
+        for (const Ctx *c : sh->all_ctx) eligible += c->no < limit ? 1 : 0;
+        for (const Ctx *c : sh->parked_ctx) eligible -= c->no < limit ? 1 : 0;
+        if (eligible == 0) limit = 0;
+    }
+    size_t at = sh->free_ctx.size();
+    while (at > 0 && limit > 0 && sh->free_ctx[at - 1]->no >= limit) at--;
+    if (at == 0) return nullptr;
+    Ctx *c = sh->free_ctx[at - 1];
+    sh->free_ctx.erase(sh->free_ctx.begin() + (ptrdiff_t)(at - 1));
     c->pass = Pass{};
     c->pass.work = c->stream;
     return c;
 }
-Ctx *ctx_acquire(Shard *sh)
+Ctx *ctx_acquire(Shard *sh, int limit)
 {
     std::unique_lock<std::mutex> lk(sh->mu);
-    sh->cv.wait(lk, [&] { return !sh->free_ctx.empty(); });
-    return ctx_take(sh);
+    Ctx *c = nullptr;
+    sh->cv.wait(lk, [&] { return (c = ctx_take(sh, limit)) != nullptr; });
+    return c;
 }
-Ctx *ctx_try_acquire(Shard *sh)
+Ctx *ctx_try_acquire(Shard *sh, int limit)
 {
     std::lock_guard<std::mutex> lk(sh->mu);
-    return sh->free_ctx.empty() ? nullptr : ctx_take(sh);
+    return ctx_take(sh, limit);
+}
+int one_sweep_contexts(const szg_index *ix)
+{
+    static const int queues = [] {
+        const char *e = getenv("GPU_MAX_HW_QUEUES");
+        const int q = e ? atoi(e) : 0;
+        return q > 0 ? q : 4;
+    }();
+    return std::max(1, std::min(ix->n_ctx, queues - 1));
 }
 void ctx_release(Shard *sh, Ctx *c)
 {
@@ -65,7 +87,7 @@ void ctx_release(Shard *sh, Ctx *c)
         std::lock_guard<std::mutex> lk(sh->mu);
         sh->free_ctx.push_back(c);
     }
-    sh->cv.notify_one();
+    sh->cv.notify_all();  // (waiters may be waiting for different contexts)
 }
 
 // the shard's staging buffer, at least `bytes` large (kept up to 64 MiB between calls); nothing in it is kept, so the
@@ -330,6 +352,7 @@ int szg_index_create(szg_index **out, int dim, int quant_bits, int metric, const
                 szg_index_destroy(ix);
                 return rc;
             }
+            c->no = i;
             sh->all_ctx.push_back(c);
             (i < ix->n_ctx_active ? sh->free_ctx : sh->parked_ctx).push_back(c);
         }
@@ -641,6 +664,7 @@ static const char *scan_option_refusal(const std::string &n, int64_t value, bool
 {
     *known = true;
     if (n == "scan_group") return value == 0 || value == 1 || value == 2 || value == 4 ? nullptr : "scan_group is 0, 1, 2 or 4";
+    if (n == "scan_group_ring") return szg::scan_group_ring_known(value) ? nullptr : "scan_group_ring is 0 or a ring depth the library carries";
     if (n == "scan_norms") return value == 0 || value == 1 ? nullptr : "scan_norms is 0 or 1";
     if (n == "sketch_planes") return value == 0 || value == 2 || value == 3 ? nullptr : "sketch_planes is 0, 2 or 3";
     *known = false;
@@ -702,6 +726,8 @@ int szg_set_option(szg_index *ix, const char *name, int64_t value)
         ix->queries_per_launch = (int)value;
     } else if (n == "scan_group") {
         ix->scan_group = (int)value;
+    } else if (n == "scan_group_ring") {
+        ix->scan_group_ring = (int)value;
     } else if (n == "scan_norms") {
         ix->scan_norms = (int)value;
     } else if (n == "sketch_planes") {
@@ -724,6 +750,9 @@ int szg_set_option(szg_index *ix, const char *name, int64_t value)
                 sh->free_ctx.push_back(sh->parked_ctx.back());
                 sh->parked_ctx.pop_back();
             }
+            // the contexts with the highest numbers leave the rotation, whatever order earlier calls returned them in:
+            // a one-sweep call keeps to the lowest numbers (one_sweep_contexts)
+            std::sort(sh->free_ctx.begin(), sh->free_ctx.end(), [](const Ctx *a, const Ctx *b) { return a->no < b->no; });
             while ((int64_t)sh->free_ctx.size() > value) {
                 sh->parked_ctx.push_back(sh->free_ctx.back());
                 sh->free_ctx.pop_back();

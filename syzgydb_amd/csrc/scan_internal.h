@@ -251,6 +251,7 @@ struct Pass {
 // and the record of the batch in flight (pass).
 struct Ctx {
     hipStream_t stream = nullptr;
+    int no = 0;                          // position among its shard's contexts, in the order their streams were created
     hipEvent_t ev_p0 = nullptr, ev_p1 = nullptr;  // HIP-event timing of the early part's sweeps
     hipEvent_t ev_scan0 = nullptr, ev_scan1 = nullptr, ev_all0 = nullptr, ev_all1 = nullptr;
     hipEvent_t ev_scan_done = nullptr;   // this batch's scans have finished (scan stream)
@@ -424,6 +425,8 @@ struct szg_index {
     int queries_per_launch = 16;  // sweeps one scan launch walks back to back (query-major)
     int scan_group = 0;       // queries of a launch the one-sweep kernel scores per row read, where the launch qualifies
                               // (8-bit rows, top-k, no masks, lists in registers): 0 = automatic, 1, 2 or 4
+    int scan_group_ring = 0;  // ring depth of the grouped row-shape kernels that exist at two: 0 = automatic, or one of the
+                              // depths the library carries (szg::scan_group_ring_known)
     int scan_norms = 0;       // grouped one-sweep launches take the rows' norms from the resident array (ensure_row_norms):
                               // 0 = automatic, 1 = always sum them in the sweep
     int sketch_planes = 0;    // digit planes of a query prepared for a sketch sweep: 0 = automatic (2, |Q| <= 16000),
@@ -571,8 +574,15 @@ float radius_key_threshold(const szg_index *ix, double radius, const QMeta &meta
 // ---- scan_handle.cpp
 int ctx_alloc(szg_index *ix, Shard *sh, Ctx **out);
 void ctx_free(Ctx *c);
-Ctx *ctx_acquire(Shard *sh);
-Ctx *ctx_try_acquire(Shard *sh);
+// limit > 0: only one of the shard's first `limit` contexts (Ctx::no < limit)
+Ctx *ctx_acquire(Shard *sh, int limit = 0);
+Ctx *ctx_try_acquire(Shard *sh, int limit = 0);
+// Contexts a call with one sweep per query keeps in flight per shard.  Its sweeps run on the shard's scan stream and
+// each batch's uploads, merge, re-rank and copy-back on its context's stream; streams take the hardware queues the
+// process opens (GPU_MAX_HW_QUEUES, HIP's default 4) in turn, so the shard's fourth context shares a queue with its scan
+// stream, and that batch's tail packets then wait behind sweeps and hold sweeps up (3.1 -> 1.1 ms
+// of a 38 ms region outside the sweeps with three).  One stream per queue: queues - 1 contexts, at least 1.
+int one_sweep_contexts(const szg_index *ix);
 void ctx_release(Shard *sh, Ctx *c);
 int shard_stage(Shard *sh, size_t bytes, uint8_t **out);
 int upload_rows(szg_index *ix, Shard *sh, uint64_t dst_row, const uint8_t *rows, uint64_t n);
@@ -778,8 +788,11 @@ int chain_sweeps(szg_index *ix, Shard *sh, Ctx *c, hipStream_t after, int part, 
     }
     if (st != after) {
         SiteScope t_(5);
-        HIPCHK(hipEventRecord(c->ev_scan_done, st));
-        HIPCHK(hipStreamWaitEvent(after, c->ev_scan_done, 0));
+        // (with timing on, the event just recorded behind the sweeps marks the same point of the stream: one packet
+        // less between two batches' sweeps)
+        hipEvent_t done = ix->timing ? (part ? c->ev_p1 : c->ev_scan1) : c->ev_scan_done;
+        if (!ix->timing) HIPCHK(hipEventRecord(done, st));
+        HIPCHK(hipStreamWaitEvent(after, done, 0));
     }
     return SZG_OK;
 }
@@ -830,6 +843,7 @@ struct Batch {
     int first = 0, nq = 0;
     int nb = 0;                  // > 0: the batch shares one sweep (query blocks of 16)
     bool single = false;         // the whole call is this one batch (a short call)
+    int ctx_limit = 0;           // > 0: contexts come from the shards' first ctx_limit (one_sweep_contexts)
     int early_n = 0;             // ... whose first early_n queries' tail runs beside its last sweeps (Pass::early_n;
                                  // settled by acquire: 0 unless the batch runs on the scan stream)
     bool any_mask = false;       // some query of the batch carries a filter mask

@@ -139,6 +139,7 @@ void fill_scan_args(const szg_index *ix, const Shard *sh, const Ctx *c, bool has
     a->no_shape_kernels = ix->shape_kernels ? 0 : 1;
     a->ring = ix->ring;
     a->group = ix->scan_group;
+    a->group_ring = ix->scan_group_ring;
     a->planes = scan_planes(ix);  // (as prep_query quantized the staged queries)
 }
 
@@ -630,7 +631,7 @@ bool Batch::acquire(bool may_block)
     for (size_t s = 0; s < ctx.size(); s++) {
         Shard *sh = ix->shards[s];
         if (sh->n_rows == 0) continue;
-        Ctx *c = may_block ? ctx_acquire(sh) : ctx_try_acquire(sh);
+        Ctx *c = may_block ? ctx_acquire(sh, ctx_limit) : ctx_try_acquire(sh, ctx_limit);
         if (!c) {
             release();
             return false;
@@ -694,6 +695,7 @@ void plan_batch(szg_index *ix, int n_queries, int q0, int nb, const BatchRules &
     b->first = q0;
     b->nb = nb;
     b->ctx.assign(ix->shards.size(), nullptr);
+    b->ctx_limit = nb == 0 && ix->serialize_scans ? one_sweep_contexts(ix) : 0;
     if (nb > 0) {
         // (int8 sweeps: two groups of 48 per launch when that many queries are waiting and both images fit LDS)
         const bool two_groups = nb == 3 && mq_uses_i8(ix, r.radius, left) && left > 48 &&

@@ -870,9 +870,31 @@ def scan_group_plan(dim, quant_bits, n_queries, kp=10, scan_group=0, queries_per
     return {"group": g.value, "lds_bytes": lds.value, "passes": passes.value}
 
 
+def scan_group_ring_plan(dim, quant_bits, n_queries, kp=10, scan_group=0, scan_group_ring=0):
+    """Host-only test hook: the ring depth a one-sweep launch of n_queries queries takes under options scan_group and
+    scan_group_ring, and the values of scan_group_ring the library accepts beside 0 (the depths it carries)."""
+    L = _lib.load()
+    depth, n = ctypes.c_int32(), ctypes.c_int32()
+    depths = (ctypes.c_int32 * 2)()
+    check(L.szg_debug_scan_group_ring(int(dim), int(quant_bits), int(kp), int(scan_group), int(n_queries),
+                                      int(scan_group_ring), ctypes.byref(depth), depths, ctypes.byref(n)),
+          "szg_debug_scan_group_ring")
+    return {"ring_depth": depth.value, "depths": [int(depths[i]) for i in range(n.value)]}
+
+
+def merge_short_plan(n_lists, m, kp):
+    """Host-only test hook: whether the one-launch short-list merge serves (n_lists, m, kp) and the most entries under
+    its threshold that its selection sorts (more, or a value below kp: the tournament)."""
+    L = _lib.load()
+    fits, sorts = ctypes.c_int32(), ctypes.c_int32()
+    check(L.szg_debug_merge_short_plan(int(n_lists), int(m), int(kp), ctypes.byref(fits), ctypes.byref(sorts)),
+          "szg_debug_merge_short_plan")
+    return {"fits": bool(fits.value), "sorts": sorts.value}
+
+
 def option_check(name, value):
     """Host-only test hook (no device needed): raises SzgError where ScanIndex.set_option would refuse `value` for the
-    one-sweep kernel's option `name` (scan_group, scan_norms, sketch_planes)."""
+    one-sweep kernel's option `name` (scan_group, scan_group_ring, scan_norms, sketch_planes)."""
     L = _lib.load()
     check(L.szg_debug_option_check(name.encode(), int(value)), "szg_debug_option_check")
 
