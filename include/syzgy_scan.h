@@ -904,6 +904,38 @@ int szg_debug_trace_certificates(szg_index *ix, int on);
 int szg_debug_certificates(szg_index *ix, szg_cert_record *records, uint64_t record_capacity, szg_cert_entry *entries,
                            uint64_t entry_capacity, uint64_t *out_records, uint64_t *out_entries, uint64_t *out_dropped);
 
+/*
+ * Test hook: the state of the 8-bit sketch index of a float32 handle (option "sketch"), read only.  A
+ * settled answer rests on the sketch bytes, on max_ang >= d(row, its sketch) and on the exception list; with these two
+ * calls a test checks each against float64.  Neither call brings the sketch up to date or builds one: a test searches
+ * first and looks at in_sync.  Both take the lock of the sync, allocate nothing on the device beyond what
+ * szg_index_read_rows does, and return SZG_E_INVALID on a NULL argument or a handle whose rows are not float32.
+ *
+ *   szg_debug_sketch_info(ix, out, exc_rows, exc_capacity)   *out is always written.  In the two-call style: with
+ *                                          exc_rows == NULL only *out is written; with exc_capacity >= out->n_exc the
+ *                                          rows without a usable sketch are copied out, ascending (SZG_E_TRUNCATED
+ *                                          when it is smaller).
+ *   szg_debug_sketch_rows(ix, first_row, n_rows, out, live_words, live_capacity)
+ *                                          the sketch rows [first_row, first_row + n_rows) in the reference's packed
+ *                                          8-bit form, dim bytes each: szg_index_read_rows on the sketch index
+ *                                          (SZG_E_RANGE beyond the sketch's rows or without a sketch).  live_words, where
+ *                                          not NULL, receives the live words of the sketch shards, index-level,
+ *                                          ceil(rows / 64) of them (SZG_E_TRUNCATED when live_capacity is smaller).
+ */
+typedef struct szg_sketch_info {
+    int32_t exists;      /* the handle holds a sketch index */
+    int32_t in_sync;     /* ... and it was synced at the handle's current state (no mutation since) */
+    int32_t disabled;    /* too many rows without a usable sketch: the sketch index was given back */
+    int32_t n_shards;    /* shards of the sketch index (0 without one) */
+    uint64_t rows;       /* rows of the sketch index (0 without one) */
+    double max_ang;      /* the largest d(row, its sketch) the builds reported */
+    double gscale;       /* Euclidean collections: the one scale of every sketch row (0: cosine) */
+    uint64_t n_exc;      /* rows without a usable sketch */
+} szg_sketch_info;
+int szg_debug_sketch_info(szg_index *ix, szg_sketch_info *out, uint64_t *out_exc_rows, uint64_t exc_capacity);
+int szg_debug_sketch_rows(szg_index *ix, uint64_t first_row, uint64_t n_rows, uint8_t *out, uint64_t *out_live_words,
+                          uint64_t live_capacity);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,9 +1,11 @@
 """The certificate margins: how much of each key bound the kernels use.
 
-Runs tests/test_gpu_certificates.py (every claim is asserted there: a failure fails this script too), then writes the
-largest |key - real| / eps the run saw per pass kind, arithmetic, row width and metric -- and, for the bfloat16 sweeps,
-the largest |key - emulated key| / (the float32-accumulation part of the bound) -- to
-profiles/certificate_margins.txt, with the commit it measured.  A ratio that creeps towards 1 after a kernel change
+Runs tests/test_gpu_certificates.py and tests/test_gpu_sketch_state.py (every claim is asserted there: a failure fails
+this script too), then writes the largest |key - real| / eps the run saw per pass kind, arithmetic, row width and
+metric -- for the bfloat16 sweeps also the largest |key - emulated key| / (the float32-accumulation part of the bound),
+for the sketch sweep's own keys the K_s lines, and per metric and dimension how close the farthest row comes to the
+slack the search allows between a row and its sketch (B3) -- to profiles/certificate_margins.txt, with the commit it
+measured.  A ratio that creeps towards 1 after a kernel change
 is margin the change has eaten.
 
     python scripts/dev_certificates.py [--out profiles/certificate_margins.txt] [--commit NAME] [pytest arguments]
@@ -21,11 +23,16 @@ sys.path[:0] = [os.path.join(ROOT, "tests"), ROOT]
 import pytest  # noqa: E402
 
 import test_gpu_certificates as t  # noqa: E402
+import test_gpu_sketch_state as ts  # noqa: E402
 
 WANT = [("topk", "Single", "one-sweep"), ("radius", "-", "one-sweep"), ("topk", "SharedInt8", "int8"),
         ("radius-shared", "-", "int8"), ("topk", "SharedBf16", "bf16"), ("topk", "Bf16Band", "bf16"),
         ("topk", "Bf16Rescored", "bf16"), ("radius-shared", "-", "bf16"), ("escalation", "-", "one-sweep"),
-        ("bf16-operands", "SharedBf16", "topk"), ("bf16-operands", "-", "radius-shared")]
+        ("bf16-operands", "SharedBf16", "topk"), ("bf16-operands", "-", "radius-shared"),
+        ("sketch K_s", "Single", "one-sweep")]
+
+
+merged = t.cc.Margins()
 
 
 def main():
@@ -33,7 +40,10 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "certificate_margins.txt"))
     ap.add_argument("--commit", default=None)
     args, rest = ap.parse_known_args()
-    rc = pytest.main([t.__file__, "-m", "gpu", "-q", "-p", "no:cacheprovider"] + rest)
+    rc = pytest.main([t.__file__, ts.__file__, "-m", "gpu", "-q", "-p", "no:cacheprovider"] + rest)
+    for m in (t.MARGINS, ts.MARGINS):   # (each file keeps its own)
+        for what, ratio in m.worst.items():
+            merged.note(what, ratio, m.count[what])
     commit = args.commit
     if commit is None:
         try:
@@ -41,20 +51,25 @@ def main():
                                              stderr=subprocess.DEVNULL).strip()
         except (OSError, subprocess.CalledProcessError):
             commit = "unknown (no git checkout)"
-    kinds = {(p, k, s) for (p, k, s, _, _) in t.MARGINS.worst}
+    kinds = {(p, k, s) for (p, k, s, _, _) in merged.worst}
     missing = [w for w in WANT if w not in kinds]
-    worst = max(t.MARGINS.worst.values(), default=0.0)
+    worst = max(merged.worst.values(), default=0.0)
+    share = max(ts.SHARES.values(), default=0.0)
     lines = ["certificate margins: python scripts/dev_certificates.py on one MI355X",
              "measured at commit %s" % commit,
-             "tests/test_gpu_certificates.py: exit code %d; largest ratio %.4f; kinds without a margin: %s"
+             "tests/test_gpu_certificates.py, tests/test_gpu_sketch_state.py: exit code %d; largest ratio %.4f; kinds without a margin: %s"
              % (int(rc), worst, missing or "none"),
              "ratio = the largest |key - real-number key| / (ub - key) over every key checked (bf16-operands: |key - the",
              "key of the emulated bfloat16 operands| / the float32-accumulation part of key_eps's bfloat16 branch)", ""]
-    lines += t.MARGINS.lines()
+    lines += merged.lines()
+    lines += ["", "B3, the farthest row from its sketch as a share of the slack the search allows (1 - share shown: what is",
+              "left; cosine slack carries the angles' rounding term, Euclidean slack only the factor 1 + 1e-9)",
+              "%-6s %5s %12s" % ("metric", "dim", "1 - share")]
+    lines += ["%-6s %5d %12.3e" % ("cosine" if m else "euclid", d, 1.0 - v) for (m, d), v in sorted(ts.SHARES.items())]
     with open(args.out, "w") as f:
         f.write("\n".join(lines) + "\n")
     print("\n".join(lines))
-    return 1 if rc or missing or worst > 1.0 else 0
+    return 1 if rc or missing or worst > 1.0 or share > 1.0 else 0
 
 
 if __name__ == "__main__":

@@ -52,11 +52,14 @@ def certificates(ix, rows, dim, bits, metric, Q, eligible, desc, call):
     recs, ents, dropped = ix.certificates()
     corpus = cert_check.Corpus(rows, dim, bits, metric)
     Q = np.atleast_2d(Q)
-    dists = None
+    dists = sketch = None
     if (recs["pass_"] == 1).any():
         dists = np.stack([orc.all_distances(rows, dim, bits, metric, q) for q in Q])
+        info = ix.sketch_info()
+        if info["exists"] and info["in_sync"]:   # the sketch sweep's own keys and lists too (K_s, L_s, D)
+            sketch = (cert_check.Corpus(ix.sketch_rows()[0], dim, 8, metric), info["gscale"], info["exc_rows"])
     try:
-        cert_check.check(corpus, Q, recs, ents, dropped, eligible=eligible, dists=dists, what=(call,))
+        cert_check.check(corpus, Q, recs, ents, dropped, eligible=eligible, dists=dists, what=(call,), sketch=sketch)
         cert_check.check_bf16_tight(corpus, Q, recs, ents, what=(call,))
     except AssertionError as e:
         print("CERTIFICATE", desc, str(e)[:600], flush=True)

@@ -59,6 +59,8 @@ EXPORTS = [
     "szg_debug_device_memory", "szg_debug_refuse_device_alloc",
     # the certificate trace: what each pass handed to certification (added under ABI 4)
     "szg_debug_trace_certificates", "szg_debug_certificates",
+    # the sketch index's state, read only (added under ABI 4)
+    "szg_debug_sketch_info", "szg_debug_sketch_rows",
 ]
 # szg_cert_record.pass / .keys, szg_cert_entry.flags
 SZG_CERT_TOPK, SZG_CERT_SKETCH, SZG_CERT_ESCALATION, SZG_CERT_RADIUS_SINGLE, SZG_CERT_RADIUS_SHARED = range(5)
@@ -132,6 +134,12 @@ class SzgCertRecord(ctypes.Structure):
 class SzgCertEntry(ctypes.Structure):
     _fields_ = [("row", ctypes.c_uint64), ("dist", ctypes.c_double), ("ub", ctypes.c_double), ("key", ctypes.c_float),
                 ("flags", ctypes.c_uint32)]
+
+
+class SzgSketchInfo(ctypes.Structure):
+    _fields_ = ([(name, ctypes.c_int32) for name in ("exists", "in_sync", "disabled", "n_shards")] +
+                [("rows", ctypes.c_uint64), ("max_ang", ctypes.c_double), ("gscale", ctypes.c_double),
+                 ("n_exc", ctypes.c_uint64)])
 
 
 class SzgColumnInfo(ctypes.Structure):
@@ -402,6 +410,11 @@ def load():
         L.szg_debug_certificates.restype = ctypes.c_int
         L.szg_debug_certificates.argtypes = [vp, ctypes.POINTER(SzgCertRecord), ctypes.c_uint64,
                                              ctypes.POINTER(SzgCertEntry), ctypes.c_uint64, u64p, u64p, u64p]
+    if hasattr(L, "szg_debug_sketch_info"):   # (as the masks: an older build for an A/B run shows no sketch state)
+        L.szg_debug_sketch_info.restype = ctypes.c_int
+        L.szg_debug_sketch_info.argtypes = [vp, ctypes.POINTER(SzgSketchInfo), u64p, ctypes.c_uint64]
+        L.szg_debug_sketch_rows.restype = ctypes.c_int
+        L.szg_debug_sketch_rows.argtypes = [vp, ctypes.c_uint64, ctypes.c_uint64, u8p, u64p, ctypes.c_uint64]
     L.szg_debug_f64_probe.restype = ctypes.c_int
     L.szg_debug_f64_probe.argtypes = [ctypes.c_int, f64p, f64p, f64p, ctypes.c_uint64]
     _lib = L

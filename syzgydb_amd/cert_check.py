@@ -17,6 +17,10 @@ narrowest bound checked or less).  check() then asserts, for every record the tr
        eps is among the hits -- every eligible row where the threshold is the "take everything" one (3e38)
     S  (sketch passes that settled) every eligible row outside the candidates is at reference distance >= D - slack
 
+With the state of the sketch index (ScanIndex.sketch_info / sketch_rows) check() also asserts K_s, L_s and D -- K and L
+for the sketch sweep's own keys, against the real-number keys of the sketch rows, and that D follows from thr_min --
+and check_sketch_build() asserts B: the sketch bytes, the exception list and max_ang against sketch_reference().
+
 Candidates the kernels force in carry no bound and are skipped and counted: cosine keys <= -1.5, rows with a non-finite
 element or an overflowing norm, keys clamped to 3e38.  A zero cosine query claims no bound at all.
 """
@@ -34,7 +38,8 @@ KEYS_NAMES = {-1: "-", _lib.SZG_CERT_KEYS_SINGLE: "Single", _lib.SZG_CERT_KEYS_S
 SWEEP_NAMES = {0: "one-sweep", 1: "int8", 2: "bf16"}
 TAKE_ALL = float(np.float32(3.0e38))   # the threshold of a collect sweep that takes every row (and the clamp of a key)
 LD = np.longdouble if np.finfo(np.longdouble).eps < np.finfo(np.float64).eps else np.float64
-WIDE_LIMIT = 2 * 10 ** 7   # (query, row, element) triples up to which the reference is computed in LD, element by element
+PI = 4 * np.arctan(LD(1))
+WIDE_LIMIT = 2 * 10 ** 7  # (query, row, element) triples up to which the reference is computed in LD, element by element
 
 
 def decode_rows(rows, dim, bits):
@@ -151,14 +156,32 @@ class Margins:
 Summary = collections.namedtuple("Summary", "records kinds skipped skipped_rows checked")
 
 
-def check(corpus, Q, recs, ents, dropped, eligible=None, dists=None, margins=None, what=()):
+def check(corpus, Q, recs, ents, dropped, eligible=None, dists=None, margins=None, what=(), sketch=None):
     """Assert K, L, C and S for the records of ONE call with queries Q.  eligible: bool[n] or bool[nq, n] (None: every
     row); dists: float64[nq, n], the oracle's distances (needed for sketch records).  -> Summary; skipped_rows are the
-    rows whose candidates carried no bound."""
+    rows whose candidates carried no bound.
+
+    sketch = (Corpus of the handle's sketch bytes at 8 bits, gscale, exc_rows) -- ScanIndex.sketch_rows / sketch_info
+    after the call -- adds, for every sketch record with a finite thr_min (lb):
+
+        K_s  each keyed entry's float32 sketch key is within ub - key of the real-number key of the row's SKETCH for
+             the query the sweep saw (q / gscale under Euclid, q under cosine)
+        L_s  every eligible row in range that is no exception and not among the keyed entries has a real-number
+             sketch key >= thr_min
+        D    the record's D is at most the sketch distance thr_min implies: acos(min(1, -thr_min)) / pi (cosine),
+             gscale sqrt(max(thr_min, 0)) / 255 (Euclid), in LD, plus that expression's own rounding"""
     Q = np.atleast_2d(np.asarray(Q, dtype=np.float64))
     nq, n = Q.shape[0], corpus.n
     assert dropped == 0, ("the trace dropped records", dropped, what)
     real, err = corpus.keys(Q)
+    if sketch is not None:
+        sk_corpus, gscale, exc_rows = sketch
+        assert sk_corpus.bits == 8 and sk_corpus.n == n and sk_corpus.metric == corpus.metric, "the sketch corpus does not fit"
+        euclid_s = corpus.metric != _lib.SZG_COSINE
+        assert (gscale > 0) == euclid_s, ("gscale is positive exactly for Euclidean collections", gscale)
+        real_s, err_s = sk_corpus.keys(Q / gscale if euclid_s else Q)
+        is_exc = np.zeros(n, dtype=bool)
+        is_exc[np.asarray(exc_rows, dtype=np.int64)] = True
     if eligible is None:
         eligible = np.ones(n, dtype=bool)
     eligible = np.broadcast_to(np.asarray(eligible, dtype=bool), (nq, n))
@@ -221,6 +244,36 @@ def check(corpus, Q, recs, ents, dropped, eligible=None, dists=None, margins=Non
                                       float(rec["eps"]), "rows", missed[:8], "real", real[qi, missed[:8]])
             inel = ~eligible[qi, rows]
             assert not inel.any(), ("C: a row that is not eligible was collected", where, rows[inel][:8])
+        # ---- K_s, L_s, D
+        if p == _lib.SZG_CERT_SKETCH and sketch is not None and np.isfinite(rec["thr_min"]) and not zero_q[qi]:
+            lb = float(rec["thr_min"])
+            s_real, s_err = real_s[qi, rows], err_s[qi, rows]
+            forced = keyed & (~np.isfinite(s_real) | (key >= TAKE_ALL) | ((key <= -1.5) if not euclid_s else False))
+            skipped += int(forced.sum())
+            skipped_rows.update(int(x) for x in rows[forced])
+            ok = keyed & ~forced
+            eps = ub[ok] - key[ok]
+            assert (eps > 0).all(), ("K_s: a sketch candidate without a bound", where)
+            off = np.abs(key[ok] - s_real[ok])
+            bad = off > eps + s_err[ok]
+            assert not bad.any(), ("K_s: sketch key outside its bound", where, "rows", rows[ok][bad][:8], "key", key[ok][bad][:8],
+                                   "real", s_real[ok][bad][:8], "eps", eps[bad][:8], "of", int(ok.sum()))
+            checked += int(ok.sum())
+            if margins is not None and ok.any():
+                margins.note(("sketch K_s", kind[1], kind[2], 8, corpus.metric), float((off / eps).max()), int(ok.sum()))
+            left = eligible[qi] & in_range & ~is_exc & np.isfinite(real_s[qi])
+            left[rows[keyed]] = False
+            bad = np.flatnonzero(left & (real_s[qi] + err_s[qi] < lb))
+            assert bad.size == 0, ("L_s: a sketched row outside the lists under the bound", where, "thr_min", lb, "rows", bad[:8],
+                                   "real", real_s[qi, bad[:8]])
+            if np.isfinite(rec["D"]):
+                if euclid_s:
+                    implied = LD(gscale) * np.sqrt(LD(max(lb, 0.0))) / LD(255)
+                else:
+                    implied = np.arccos(LD(max(-1.0, min(1.0, -lb)))) / PI
+                implied = float(implied)
+                assert rec["D"] <= implied + 4 * np.finfo(np.float64).eps * implied, ("D: above the distance thr_min implies",
+                                                                                      where, float(rec["D"]), implied, lb)
         # ---- S
         if p == _lib.SZG_CERT_SKETCH and rec["certified"] == 1 and np.isfinite(rec["D"]):
             assert dists is not None, "sketch records need the oracle's distances"
@@ -229,6 +282,133 @@ def check(corpus, Q, recs, ents, dropped, eligible=None, dists=None, margins=Non
             assert bad.size == 0, ("S: a row outside the candidates nearer than D - slack", where, float(rec["D"]),
                                    float(rec["slack"]), "rows", bad[:8], "dist", d[bad[:8]])
     return Summary(len(recs), kinds, skipped, skipped_rows, checked)
+
+
+# ---- the sketch index: bytes, exceptions and max_ang (B) ---------------------------------------------------------------
+
+def sketch_angle_rounding(dim):
+    """What SketchCall::run adds to max_ang under cosine for the rounding of the build kernel's float64 angles: the
+    device's cosine of (row, sketch) is off by at most (dim + 8) u, which acos turns into at most sqrt(2 (dim + 8) u)
+    near c = 1; twice the root covers a float64 reference beside it.  1e-7 up to dim 222."""
+    return max(1e-7, 2.0 * np.sqrt((dim + 8) * 2.0 ** -52) / np.pi)
+
+
+def sketch_slack(max_ang, gscale, dim):
+    """slack as SketchCall::run forms it from the sketch state."""
+    return max_ang * (1.0 + 1e-9) + (0.0 if gscale > 0 else sketch_angle_rounding(dim))
+
+
+def sketch_reference(vec, metric, gscale):
+    """What sketch_build_kernel is specified to do with float32 rows vec[n, dim] (their values, float64) ->
+    (t[n, dim] in LD, must_exc[n]): the ideal scaled value t = (x / scale + 1) * 127.5, whose nearest integer clipped to
+    0..255 is the row's sketch byte -- scale is the row's largest |x_i| under cosine and gscale under Euclid -- and
+    whether the row has no usable sketch: a non-finite element, no direction (all zero, cosine), an element beyond
+    gscale (Euclid).  t of such a row means nothing."""
+    X = np.asarray(vec, dtype=np.float64)
+    fin = np.isfinite(X)
+    finite = fin.all(axis=1)
+    mx = np.abs(np.where(fin, X, 0.0)).max(axis=1)
+    if metric == _lib.SZG_COSINE:
+        must = ~finite | (mx == 0)
+        scale = mx
+    else:
+        must = ~finite | (mx > gscale)
+        scale = np.full(X.shape[0], float(gscale))
+    scale = np.where(must, 1.0, scale)
+    with np.errstate(all="ignore"):
+        t = (X.astype(LD) / scale.astype(LD)[:, None] + LD(1)) * LD(127.5)
+    return t, must
+
+
+def check_sketch_build(vec, sk_bytes, info, exc_rows, rebuilt, metric=None, rec_slack=None, what=()):
+    """Assert B for the sketch state (info: ScanIndex.sketch_info(); sk_bytes: uint8[n, dim], ScanIndex.sketch_rows())
+    of float32 rows with values vec[n, dim]; rebuilt: the last sync built every row anew.
+
+        B1  every byte of a sketched row is within 0.5 + 1e-9 of clip(t, 0, 255) (the device may fuse the multiply-add:
+            a tie may fall either way); every byte of a row that must be an exception is 128
+        B2  every row that must be an exception is listed; after a rebuild nothing else is
+        B3  d(row, decoded sketch) <= slack for every sketched row, in LD: acos(c) / pi against
+            max_ang (1 + 1e-9) + sketch_angle_rounding(dim), or the norm of row - gscale n / 255 against
+            max_ang (1 + 1e-9); rec_slack, a traced record's, agrees with that slack
+        B4  max_ang >= the largest such distance less the reference's rounding -- and, rebuilt, <= it plus the rounding.
+            The rounding: both cosines are off by at most (dim + 8) u, acos amplifies by 1 / sqrt(1 - c^2), capped at
+            sqrt(2 (dim + 8) u); it must stay below what the search adds for it.  Euclid: (dim + 8) u relative.
+        scale (Euclid)  gscale is the largest |x_i| of the rows without a non-finite element, exactly (1 where there is
+            none), after a rebuild; else at least that of the rows not listed as exceptions
+
+    -> dict: sketched, exceptions, largest (the reference's), allowance, share (largest / slack)."""
+    X = np.asarray(vec, dtype=np.float64)
+    n, dim = X.shape
+    gscale, max_ang = float(info["gscale"]), float(info["max_ang"])
+    if metric is None:
+        metric = _lib.SZG_COSINE if gscale == 0 else 1 - _lib.SZG_COSINE
+    euclid = metric != _lib.SZG_COSINE
+    assert (gscale > 0) == euclid, ("gscale is positive exactly for Euclidean collections", gscale, what)
+    sk_bytes = np.asarray(sk_bytes)
+    assert sk_bytes.dtype == np.uint8 and sk_bytes.shape == (n, dim), ("dim bytes per sketch row", sk_bytes.shape, (n, dim), what)
+    assert int(info["rows"]) == n and int(info["n_exc"]) == len(exc_rows), (what, info)
+    t, must = sketch_reference(X, metric, gscale)
+    exc = np.zeros(n, dtype=bool)
+    exc[np.asarray(exc_rows, dtype=np.int64)] = True
+    # ---- B2
+    missing = np.flatnonzero(must & ~exc)
+    assert missing.size == 0, ("B2: a row without a usable sketch is not an exception", what, missing[:8])
+    if rebuilt:
+        more = np.flatnonzero(exc & ~must)
+        assert more.size == 0, ("B2: an exception after a rebuild that need not be one", what, more[:8])
+    # ---- B1
+    bad = np.flatnonzero((sk_bytes[must] != 128).any(axis=1))
+    assert bad.size == 0, ("B1: an exception row's bytes are not all 128", what, np.flatnonzero(must)[bad][:8])
+    at = np.flatnonzero(~must)
+    v = sk_bytes[at].astype(LD)
+    off = np.abs(v - np.clip(t[at], 0, 255))
+    bad = off > 0.5 + 1e-9
+    assert not bad.any(), ("B1: a sketch byte is not the nearest", what, "rows", at[bad.any(axis=1)][:8], "bytes",
+                           sk_bytes[at][bad][:8], "ideal", t[at][bad][:8].astype(np.float64))
+    # ---- scale
+    fin_rows = np.isfinite(X).all(axis=1)
+    if euclid:
+        if rebuilt:
+            top = np.abs(X[fin_rows]).max() if fin_rows.any() else 0.0
+            assert gscale == (top if top > 0 else 1.0), ("scale: not the largest finite |x_i|", what, gscale, top)
+        else:
+            have = fin_rows & ~exc
+            top = np.abs(X[have]).max() if have.any() else 0.0
+            assert gscale >= top, ("scale: below a sketched row's largest |x_i|", what, gscale, top)
+    # ---- B3
+    slack = sketch_slack(max_ang, gscale, dim)
+    if rec_slack is not None:
+        assert abs(float(rec_slack) - slack) <= 4 * np.finfo(np.float64).eps * slack, ("the search's slack is not the state's",
+                                                                                       what, float(rec_slack), slack)
+    u = float(np.finfo(np.float64).eps) + float(np.finfo(LD).eps)
+    Xs, nvec = X[at].astype(LD), 2 * v - 255
+    with np.errstate(all="ignore"):
+        if euclid:
+            d = np.sqrt(((Xs - LD(gscale) * nvec / 255) ** 2).sum(axis=1))
+            allow = (dim + 8) * u * d
+        else:
+            c = (Xs * nvec).sum(axis=1) / np.sqrt((Xs * Xs).sum(axis=1) * (nvec * nvec).sum(axis=1))
+            c = np.clip(c, -1, 1)
+            d = np.arccos(c) / PI
+            dc = (dim + 8) * u
+            sin = np.sqrt(np.maximum(1 - c * c, 0))
+            allow = np.minimum(dc / np.maximum(sin, LD(1e-300)), np.sqrt(2 * dc)) / PI + 4 * np.finfo(np.float64).eps
+    d, allow = d.astype(np.float64), allow.astype(np.float64)
+    assert np.isfinite(d).all(), ("the reference's own distance is not finite", what, at[~np.isfinite(d)][:8])
+    bad = d > slack
+    assert not bad.any(), ("B3: a row farther from its sketch than slack", what, "rows", at[bad][:8], "dist", d[bad][:8], "slack", slack)
+    # ---- B4
+    largest = float(d.max()) if d.size else 0.0
+    allowance = float(allow.max()) if d.size else 0.0
+    if not euclid:
+        assert allowance < sketch_angle_rounding(dim), ("the angles' rounding is not below what the search adds for it", what,
+                                                        allowance, sketch_angle_rounding(dim))
+    assert max_ang >= largest - allowance, ("B4: max_ang below the largest row-to-sketch distance", what, max_ang, largest, allowance)
+    if rebuilt:
+        assert max_ang <= largest + allowance, ("B4: max_ang above the largest row-to-sketch distance after a rebuild", what,
+                                                max_ang, largest, allowance)
+    return {"sketched": int(at.size), "exceptions": int(exc.sum()), "largest": largest, "allowance": allowance,
+            "share": largest / slack if slack > 0 else 0.0}
 
 
 # ---- the bfloat16 sweeps, operand by operand ------------------------------------------------------------------------

@@ -550,7 +550,7 @@ __global__ __launch_bounds__(256) void sketch_build_kernel(const uint8_t *src, R
             for (int k = 0; k < 4; k++) {
                 if (e0 + k >= dim) continue;
                 const float ax = fabsf(x[k]);
-                if (!(ax <= 3.4e38f)) bad = true;  // Inf or NaN
+                if (!(ax <= 3.402823466e38f)) bad = true;  // Inf or NaN (the largest finite float is a value like any other)
                 mx = fmaxf(mx, ax);
             }
         }
@@ -563,7 +563,9 @@ __global__ __launch_bounds__(256) void sketch_build_kernel(const uint8_t *src, R
         return;
     }
     if (gscale > 0.0) {
-        if ((double)mx > gscale) bad = true;  // (cannot happen after a max pass; such a row would be re-ranked always)
+        // an overwritten row may exceed the scale: the scale pass covers appended rows only, and the listed-rows launch
+        // comes without one.  Its bytes would clip, so it becomes an exception (always re-ranked) until the next rebuild.
+        if ((double)mx > gscale) bad = true;
     } else {
         bad = bad || !(mx > 0.f);
     }

@@ -541,6 +541,26 @@ int szg_debug_certificates(szg_index *ix, szg_cert_record *records, uint64_t rec
     return SZG_OK;
 }
 
+// test hooks: the sketch index's state, read only (scan_sketch.cpp; include/syzgy_scan.h)
+int szg_debug_sketch_info(szg_index *ix, szg_sketch_info *out, uint64_t *out_exc_rows, uint64_t exc_capacity)
+{
+    SZG_TRY
+    if (!ix || !out) return fail(SZG_E_INVALID, "null argument");
+    if (ix->bits != 32) return fail(SZG_E_INVALID, "sketch info: only float32 handles keep a sketch");
+    return sketch_debug_info(ix, out, out_exc_rows, exc_capacity);
+    SZG_CATCH
+}
+
+int szg_debug_sketch_rows(szg_index *ix, uint64_t first_row, uint64_t n_rows, uint8_t *out, uint64_t *out_live_words,
+                          uint64_t live_capacity)
+{
+    SZG_TRY
+    if (!ix || (!out && n_rows)) return fail(SZG_E_INVALID, "null argument");
+    if (ix->bits != 32) return fail(SZG_E_INVALID, "sketch rows: only float32 handles keep a sketch");
+    return sketch_debug_rows(ix, first_row, n_rows, out, out_live_words, live_capacity);
+    SZG_CATCH
+}
+
 // test hook, host only: the lane map, launch geometry and kernel variant a sweep over n_rows rows would take -- from
 // the functions the launch path calls (row_format, scan_geometry, scan_variant), so tests derive their shapes from
 // the code's own rules

@@ -695,6 +695,10 @@ int enqueue_collect_mq(szg_index *ix, Shard *sh, Ctx *c, int nq, int nb, bool ha
 bool sketch_applies(const szg_index *ix, int k);
 // a load / synth: auto mode may try the sketch again (mutations are never concurrent with searches)
 void sketch_rearm(szg_index *ix);
+// test hooks (szg_debug_sketch_info / szg_debug_sketch_rows): the sketch state as it stands, under sk_mu, never a sync
+int sketch_debug_info(szg_index *ix, szg_sketch_info *out, uint64_t *out_exc_rows, uint64_t exc_capacity);
+int sketch_debug_rows(szg_index *ix, uint64_t first_row, uint64_t n_rows, uint8_t *out, uint64_t *out_live_words,
+                      uint64_t live_capacity);
 int search_topk_any(szg_index *ix, const double *queries, int n_queries, int k, const uint64_t *allow_bits,
                     uint64_t *out_rows, double *out_dist, int32_t *out_count,
                     const uint64_t *const *allow_ptrs = nullptr, const szg_mask *const *handles = nullptr);

@@ -230,6 +230,47 @@ int sketch_sync(szg_index *ix)
     return SZG_OK;
 }
 
+// ---- test hooks: the sketch state as it stands ----------------------------------------------------------------------
+
+int sketch_debug_info(szg_index *ix, szg_sketch_info *out, uint64_t *out_exc_rows, uint64_t exc_capacity)
+{
+    std::lock_guard<std::mutex> lk(ix->sk_mu);
+    const szg_index *sk = ix->sketch;
+    memset(out, 0, sizeof(*out));
+    out->exists = sk ? 1 : 0;
+    out->in_sync = sk && ix->sk_gen == ix->gen ? 1 : 0;
+    out->disabled = ix->sk_disabled ? 1 : 0;
+    out->n_shards = sk ? (int32_t)sk->shards.size() : 0;
+    if (sk)
+        for (const Shard *sh : sk->shards) out->rows += sh->n_rows;
+    out->max_ang = ix->sk_max_ang;
+    out->gscale = ix->sk_gscale;
+    out->n_exc = ix->sk_exc.size();
+    if (!out_exc_rows) return SZG_OK;
+    if (exc_capacity < ix->sk_exc.size()) return fail(SZG_E_TRUNCATED, "sketch info: exception buffer too small");
+    if (!ix->sk_exc.empty()) memcpy(out_exc_rows, ix->sk_exc.data(), ix->sk_exc.size() * sizeof(uint64_t));
+    return SZG_OK;
+}
+
+int sketch_debug_rows(szg_index *ix, uint64_t first_row, uint64_t n_rows, uint8_t *out, uint64_t *out_live_words,
+                      uint64_t live_capacity)
+{
+    std::lock_guard<std::mutex> lk(ix->sk_mu);
+    szg_index *sk = ix->sketch;
+    if (!sk) return fail(SZG_E_RANGE, "sketch rows: the handle has no sketch index");
+    if (out_live_words) {
+        const size_t words = index_words(szg_index_rows(sk));
+        if (live_capacity < words) return fail(SZG_E_TRUNCATED, "sketch rows: live word buffer too small");
+        for (const Shard *sh : sk->shards) {  // the words the sweeps read (shard starts are multiples of 64)
+            if (sh->n_rows == 0) continue;
+            HIPCHK(hipSetDevice(sh->device));
+            HIPCHK(hipMemcpy(out_live_words + sh->first / 64, sh->live_bits, index_words(sh->n_rows) * sizeof(uint64_t),
+                             hipMemcpyDeviceToHost));
+        }
+    }
+    return szg_index_read_rows(sk, first_row, n_rows, out);
+}
+
 // ---- one search call through the sketch ---------------------------------------------------------------------------
 //
 // The batch pipeline of scan_topk.cpp (run_batches) on the sketch index's contexts: stage() uploads a batch's queries
@@ -273,7 +314,11 @@ int SketchCall::run()
     const int kk = k + ix->sketch_extra;
     kp = kk + std::max(ix->slack_min, kk / 2);
     gs = ix->sk_gscale;  // Euclidean: sketch distances are in units of gs (the sketch sweeps see q / gs)
-    slack = ix->sk_max_ang * (1.0 + 1e-9) + (gs > 0.0 ? 0.0 : 1e-7);  // (+ the rounding of the computed angles)
+    // + the rounding of the build kernel's angles: its float64 cosine of (row, sketch) is off by at most (dim + 8) u,
+    // which acos turns into at most sqrt(2 (dim + 8) u) where c is near 1 -- a row that its sketch all but reproduces.
+    // Twice the root (a float64 reference beside it; cert_check.sketch_angle_rounding) passes 1e-7 from dim 223 on.
+    const double ang_round = std::max(1e-7, 2.0 * std::sqrt((ix->dim + 8) * 0x1p-52) / M_PI);
+    slack = ix->sk_max_ang * (1.0 + 1e-9) + (gs > 0.0 ? 0.0 : ang_round);
     sk->timing = ix->timing;
     extra.assign(n_sh, 0);
     for (size_t s = 0; s < n_sh; s++) {

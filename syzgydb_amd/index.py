@@ -825,6 +825,28 @@ class ScanIndex:
         check(rc, "szg_debug_certificates")
         return recs[: n_rec.value], ents[: n_ent.value], int(dropped.value)
 
+    def sketch_info(self):
+        """Test hook: the state of the 8-bit sketch index as it stands (szg_debug_sketch_info; never a sync): a dict of
+        szg_sketch_info's fields plus exc_rows, the rows without a usable sketch (uint64, ascending)."""
+        info = _lib.SzgSketchInfo()
+        check(self._L.szg_debug_sketch_info(self._h, ctypes.byref(info), None, 0), "szg_debug_sketch_info")
+        exc = np.zeros(max(1, info.n_exc), dtype=np.uint64)
+        check(self._L.szg_debug_sketch_info(self._h, ctypes.byref(info), _u64(exc), exc.size), "szg_debug_sketch_info")
+        out = {name: getattr(info, name) for name, _ in _lib.SzgSketchInfo._fields_}
+        out["exc_rows"] = exc[: info.n_exc]
+        return out
+
+    def sketch_rows(self, first_row=0, n_rows=None):
+        """Test hook: (sketch rows [first_row, first_row + n_rows) in the packed 8-bit form, uint8[n_rows, dim]; the live
+        words of the sketch shards, uint64[ceil(sketch rows / 64)]) -- szg_debug_sketch_rows; never a sync."""
+        total = self.sketch_info()["rows"]
+        n = total - int(first_row) if n_rows is None else int(n_rows)
+        out = np.zeros((n, self.dim), dtype=np.uint8)
+        live = np.zeros(max(1, (total + 63) // 64), dtype=np.uint64)
+        check(self._L.szg_debug_sketch_rows(self._h, int(first_row), n, _u8(out) if n else None, _u64(live), live.size),
+              "szg_debug_sketch_rows")
+        return out, live[: (total + 63) // 64]
+
     def set_option(self, name, value):
         check(self._L.szg_set_option(self._h, name.encode(), int(value)), "szg_set_option")
         self.options[name] = int(value)   # (what the host mirrors consult: e.g. tie_mode, collection.py)

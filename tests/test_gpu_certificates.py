@@ -100,10 +100,14 @@ def traced_topk(ix, corpus, Q, k, what, eligible=None, skips=0, **filt):
     Q = np.atleast_2d(Q)
     r, d, cnt = ix.search_topk(Q, k, **filt)
     recs, ents, dropped = ix.certificates()
-    dists = None
+    dists = sketch = None
     if (recs["pass_"] == _lib.SZG_CERT_SKETCH).any():
         dists = np.stack(list(POOL.map(lambda q: orc.all_distances(corpus.packed, corpus.dim, corpus.bits, corpus.metric, q), Q)))
-    s = cc.check(corpus, Q, recs, ents, dropped, eligible=eligible, dists=dists, margins=MARGINS, what=what + ("k", k))
+        info = ix.sketch_info()
+        if info["exists"] and info["in_sync"]:   # the sketch sweep's own keys and lists too (K_s, L_s, D)
+            sketch = (cc.Corpus(ix.sketch_rows()[0], corpus.dim, 8, corpus.metric), info["gscale"], info["exc_rows"])
+    s = cc.check(corpus, Q, recs, ents, dropped, eligible=eligible, dists=dists, margins=MARGINS, what=what + ("k", k),
+                 sketch=sketch)
     assert s.skipped <= skips, ("candidates without a bound on a corpus that plants none", what, s.skipped, sorted(s.skipped_rows)[:8])
     first = recs[(recs["pass_"] == _lib.SZG_CERT_TOPK) | (recs["pass_"] == _lib.SZG_CERT_SKETCH)]
     settled = first[(first["pass_"] == _lib.SZG_CERT_TOPK) | (first["certified"] == 1)]

@@ -92,6 +92,30 @@ def test_certificate_trace_surface():
         assert getattr(_lib, name) == value and re.search(r"#define %s %d\b" % (name, value), hdr), name
 
 
+def test_sketch_state_surface():
+    """The sketch state's two entry points are exported and bound, refuse a null handle or a null info before touching
+    anything, and the Python mirror of szg_sketch_info has the header's layout (48 bytes, the declaration's order)."""
+    from syzgydb_amd import _lib
+    L = _lib.load()
+    for name in ("szg_debug_sketch_info", "szg_debug_sketch_rows"):
+        assert name in _lib.EXPORTS and hasattr(L, name)
+    info = _lib.SzgSketchInfo()
+    info.rows = 7
+    assert L.szg_debug_sketch_info(None, ctypes.byref(info), None, 0) == _lib.SZG_E_INVALID
+    assert info.rows == 7
+    assert L.szg_debug_sketch_info(None, None, None, 0) == _lib.SZG_E_INVALID
+    buf = (ctypes.c_uint8 * 4)(9, 9, 9, 9)
+    assert L.szg_debug_sketch_rows(None, 0, 1, buf, None, 0) == _lib.SZG_E_INVALID
+    assert L.szg_debug_sketch_rows(None, 0, 0, None, None, 0) == _lib.SZG_E_INVALID
+    assert list(buf) == [9, 9, 9, 9]
+    assert ctypes.sizeof(_lib.SzgSketchInfo) == 48
+    hdr = open(os.path.join(ROOT, "include", "syzgy_scan.h")).read()
+    body = re.search(r"typedef struct szg_sketch_info \{(.*?)\} szg_sketch_info;", hdr, flags=re.S).group(1)
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    names = [x.strip() for decl in body.split(";") if decl.strip() for x in decl.split(None, 1)[1].split(",")]
+    assert names == [f[0] for f in _lib.SzgSketchInfo._fields_], names
+
+
 def test_error_paths_without_gpu_work():
     from syzgydb_amd import _lib
     L = _lib.load()
