@@ -683,6 +683,14 @@ int szg_reset_stats(szg_index *ix);
  *                             (2: |Q| <= 16 000, the quantization step enters the certificate's bound), 3 = |Q| <= 10^6
  *                             as on plain 8-bit handles, which always take 3.  Only queries are prepared differently:
  *                             changing it invalidates nothing resident.  Other values are refused
+ *     sketch_matrix       0   the matrix sweep: one-sweep launches over tiled 8-bit rows of whole 64-byte steps whose
+ *                             queries carry two digit planes -- the sketch pre-pass -- without filter or tombstones,
+ *                             with lists in registers, resident norms and scan_group = 0 score up to 16 queries per
+ *                             row read on the matrix cores.  0 = automatic (launches of 3 queries or more; a lone query
+ *                             keeps the kernel without groups), 1 = never (the grouped kernels of scan_group), 2 = every
+ *                             launch the shape allows, whatever its query count.  Keys stay inside the same error bound
+ *                             but are not bit-identical to the grouped kernels'; answers are.  szg_stats.scan_bytes
+ *                             counts one pass per 16 queries of such a launch.  Other values are refused
  *     query_batch         16  queries staged, merged, re-ranked and copied back together
  *     mask_dense          1   sweeps whose filter / tombstone masks pass at least half the rows read every row and
  *                             apply the masks at the row finish; selective masks (and 0) compact the row steps that
@@ -789,6 +797,17 @@ int szg_debug_scan_group(int dim, int quant_bits, int kp, int collect, int maske
                          int queries_per_launch, int32_t *group, uint64_t *lds_bytes, int32_t *passes);
 
 /*
+ * Test hook, host only: does the matrix sweep (option sketch_matrix) serve a one-sweep top-k call of n_queries queries,
+ * split into launches of 16?  planes = digit planes of the queries (2 or 3), norms = the rows' norms are resident,
+ * tiled = 0 takes the tiled layout away, masked = a filter or tombstones.  *serves / *steps_form / *lds_bytes describe
+ * the first launch (steps_form: 12 or 6 = the kernel of that many 64-byte steps per row, 0 = the any-steps kernel),
+ * *passes = passes over the rows of the whole call.
+ */
+int szg_debug_scan_matrix(int dim, int quant_bits, int n_queries, int kp, int planes, int norms, int tiled, int masked,
+                          int scan_group, int sketch_matrix, int32_t *serves, int32_t *passes, uint64_t *lds_bytes,
+                          int32_t *steps_form);
+
+/*
  * Test hook, host only: *fits = the sketch sweep's one-launch short-list merge serves n_lists block lists of m entries
  * at kp candidates; *sorts = the most entries under its threshold (the kp-th smallest first entry) that its selection
  * sorts in one network -- with more, and always when *sorts < kp, the launch runs the tournament.
@@ -805,7 +824,7 @@ int szg_debug_scan_group_ring(int dim, int quant_bits, int kp, int scan_group, i
 
 /*
  * Test hook, host only: would szg_set_option accept `value` for the one-sweep kernel's option `name` (scan_group,
- * scan_group_ring, scan_norms, sketch_planes)?  SZG_OK, or SZG_E_INVALID with szg_set_option's text; any other name is refused.
+ * scan_group_ring, scan_norms, sketch_planes, sketch_matrix)?  SZG_OK, or SZG_E_INVALID with szg_set_option's text; any other name is refused.
  */
 int szg_debug_option_check(const char *name, int64_t value);
 

@@ -1,0 +1,36 @@
+"""Launch times of the sketch sweep by the library's HIP events, matrix sweep against the grouped kernels:
+1M x 768 float32 cosine (the headline's handle), calls of 1, 2, 3, 4, 16 and 32 queries under sketch_matrix = 2 (the
+matrix sweep whatever the count) and 1 (G = 1, 2, 4).  SZG_NO_EARLY_TAIL=1 keeps a 16-query call one launch.
+usage: SZG_NO_EARLY_TAIL=1 python scripts/dev_matrix.py [rows] [dim]"""
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import oracle as orc  # noqa: E402
+from syzgydb_amd import ScanIndex, SZG_COSINE  # noqa: E402
+
+n = int(sys.argv[1]) if len(sys.argv) > 1 else 1000000
+dim = int(sys.argv[2]) if len(sys.argv) > 2 else 768
+Q = orc.synth_vectors(11, 0, 32, dim)
+with ScanIndex(dim, 32, SZG_COSINE) as ix:
+    ix.synth(n, 7)
+    for name, v in (("multi_query", 0), ("sketch", 1)):
+        ix.set_option(name, v)
+    ix.search_topk(Q[:16], 10)   # builds the sketch and the norms
+    ix.set_timing(1)
+    for sm, label in ((2, "matrix"), (1, "grouped")):
+        ix.set_option("sketch_matrix", sm)
+        for nq in (1, 2, 3, 4, 16, 32):
+            for _ in range(3):
+                ix.search_topk(Q[:nq], 10)
+            ix.reset_stats()
+            reps = 20
+            for _ in range(reps):
+                ix.search_topk(Q[:nq], 10)
+            st = ix.stats()
+            passes = st["scan_bytes"] / (n * dim)
+            print("%-8s queries %2d  launches/call %.1f  passes/call %.1f  ms/launch %.4f  ms/pass %.4f  settled %d/%d" % (
+                label, nq, st["scan_launches"] / reps, passes / reps, st["scan_ms"] / max(st["timed_launches"], 1),
+                st["scan_ms"] / max(passes, 1), st["sketch_queries"], reps * nq), flush=True)

@@ -7,6 +7,7 @@
 #   VFLAGS="-DSZG_SCAN_METRIC=1 -DSZG_GROUP_FORM=3" scripts/kernel_resources.sh scan 8
 #                                             -> one metric's G > 1 kernels of one form (bit 0: two planes, bit 1: resident
 #                                                norms); without SZG_GROUP_FORM: the metric's G = 1 kernels
+#   scripts/kernel_resources.sh scan mx 1     -> kernels_scan_mx.hip -DSZG_SCAN_METRIC=1 (the matrix sweep, cosine)
 #   scripts/kernel_resources.sh exact         -> kernels_exact.hip (re-rank, page-in, row gather, ...)
 #   scripts/kernel_resources.sh mask          -> kernels_mask.hip (device-resident filter masks)
 #   scripts/kernel_resources.sh column        -> kernels_column.hip (resident metadata columns)
@@ -15,7 +16,8 @@
 set -euo pipefail
 cd "$(dirname "$0")/../syzgydb_amd/csrc"
 kind=${1:-mq}; part=${2:-i8}
-if [ "$kind" = scan ]; then src=kernels_scan.hip; def=-DSZG_QBITS=$part
+if [ "$kind" = scan ] && [ "$part" = mx ]; then src=kernels_scan_mx.hip; def=-DSZG_SCAN_METRIC=${3:-1}
+elif [ "$kind" = scan ]; then src=kernels_scan.hip; def=-DSZG_QBITS=$part
 elif [ "$kind" = exact ]; then src=kernels_exact.hip; def=-ffp-contract=off
 elif [ "$kind" = mask ]; then src=kernels_mask.hip; def=
 elif [ "$kind" = column ] && [ "$part" = carry ]; then src=kernels_column_carry.hip; def=

@@ -1,5 +1,5 @@
-"""From a rocprofv3 kernel trace (+ memory-copy trace) of the headline: the gaps between consecutive grouped
-sweeps, what runs inside them and whether merges / reranks overlap a sweep.  usage: timeline_gaps.py <dir>"""
+"""From a rocprofv3 kernel trace (+ memory-copy trace) of the headline: the gaps between consecutive sketch
+sweeps (the matrix sweep's launches, or the grouped kernel's in a library without it), what runs inside them and whether merges / reranks overlap a sweep.  usage: timeline_gaps.py <dir>"""
 import csv, glob, re, sys, statistics
 
 path = sys.argv[1]
@@ -13,7 +13,9 @@ for f in glob.glob(path + "/**/*memory_copy_trace.csv", recursive=True):
     for r in csv.DictReader(open(f)):
         ev.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), "copy " + r.get("Direction", ""), "dma"))
 ev.sort()
-sw = [e for e in ev if e[2].startswith("scan_kernel<8") and ", 4, 2, true" in e[2]]
+sw = [e for e in ev if e[2].startswith("scan_mx_kernel")]  # the matrix sketch sweep, where the library has it
+if not sw:
+    sw = [e for e in ev if e[2].startswith("scan_kernel<8") and ", 4, 2, true" in e[2]]
 if not sw:
     sw = [e for e in ev if e[2].startswith("scan_kernel<8")]
 print("sweeps:", len(sw), "name:", sw[0][2] if sw else None)
@@ -29,7 +31,7 @@ print("gap percentiles 10/25/50/75/90: " + " ".join("%.1f" % gs[int(len(gs) * p)
 # overlap of tails with sweeps
 ov = {}
 for s, e, n, q in ev:
-    if n.startswith("scan_kernel"):
+    if n.startswith("scan_kernel") or n.startswith("scan_mx_kernel"):
         continue
     if s < sw[0][0] or e > sw[-1][1]:
         continue

@@ -54,7 +54,7 @@ EXPORTS = [
     "szg_column_set_rows", "szg_debug_bulk_plan",
     # host-only test hook
     "szg_debug_scan_plan", "szg_debug_scan_group", "szg_debug_reorder_plan", "szg_debug_option_check",
-    "szg_debug_scan_group_ring", "szg_debug_merge_short_plan",
+    "szg_debug_scan_group_ring", "szg_debug_merge_short_plan", "szg_debug_scan_matrix",
     # who owns device memory: the counters and the refusal countdown (added under ABI 4)
     "szg_debug_device_memory", "szg_debug_refuse_device_alloc",
     # the certificate trace: what each pass handed to certification (added under ABI 4)
@@ -390,6 +390,10 @@ def load():
         L.szg_debug_scan_group.restype = ctypes.c_int
         L.szg_debug_scan_group.argtypes = [ctypes.c_int] * 8 + [ctypes.POINTER(ctypes.c_int32), u64p,
                                                                 ctypes.POINTER(ctypes.c_int32)]
+    if hasattr(L, "szg_debug_scan_matrix"):
+        L.szg_debug_scan_matrix.restype = ctypes.c_int
+        L.szg_debug_scan_matrix.argtypes = [ctypes.c_int] * 10 + [ctypes.POINTER(ctypes.c_int32)] * 2 + [u64p,
+                                                                                                    ctypes.POINTER(ctypes.c_int32)]
     if hasattr(L, "szg_debug_scan_group_ring"):
         L.szg_debug_scan_group_ring.restype = ctypes.c_int
         L.szg_debug_scan_group_ring.argtypes = [ctypes.c_int] * 6 + [ctypes.POINTER(ctypes.c_int32)] * 3

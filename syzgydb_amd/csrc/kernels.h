@@ -150,6 +150,8 @@ struct ScanArgs {
                                 // the image is all zero; G > 1 variants then neither stage nor read it
     int group_ring;             // option scan_group_ring: ring depth of the G > 1 row-shape kernels that carry more than
                                 // one (scan_variant); 0 = automatic
+    int matrix;                 // option sketch_matrix: 0 = automatic (the matrix sweep where the launch qualifies and holds
+                                // kMatrixMinQueries queries), 1 = never, 2 = wherever the shape allows, whatever the count
 };
 
 // Which scan_kernel instantiation a launch takes: decided on the host by scan_variant -- the launcher dispatches on
@@ -159,16 +161,27 @@ struct ScanVariant {
     int deep;         // the any-shape kernel with the deep piece ring
     int ring_depth;   // 16-byte loads each lane keeps in flight
     int nontemporal;  // rows are loaded past the caches
-    int group;        // queries of the launch scored per row read (1, 2 or 4)
+    int group;        // queries of the launch scored per row read (1, 2 or 4; kMatrixQueries: the matrix sweep)
+    int matrix;       // the matrix sweep (kernels_scan_mx.hip) serves the launch: one pass per kMatrixQueries queries
+    int matrix_steps; // its form: 12 or 6 (64-byte steps per row fixed at compile time), 0 = the any-steps kernel
 };
 // What "automatic" (scan_group = 0) asks for, where a launch qualifies.
 constexpr int kScanGroupAuto = 4;
+// The matrix sweep: queries per pass, and the fewest queries of a launch that take it under sketch_matrix = 0 -- a pass
+// costs about what a pass of the G = 1 kernel costs, and less than the G = 4 kernel's from 3 queries on (DESIGN.md 6,
+// round 11).  A lone query keeps the G = 1 kernel.
+constexpr int kMatrixQueries = 16;
+constexpr int kMatrixMinQueries = 3;
+constexpr int matrix_steps_form(int steps) { return steps == 12 || steps == 6 ? steps : 0; }
+constexpr bool sketch_matrix_known(int64_t v) { return v == 0 || v == 1 || v == 2; }
 // group: the scan_group option (0 = automatic), n_queries: the launch's, block: its threads (the group's query images
 // -- of `planes` digit planes each -- and lists have to fit 64 KiB of LDS)
 // group_ring: the scan_group_ring option (0 = automatic)
+// matrix_opt: the sketch_matrix option (1 = off, what callers that do not know it get); norms: the launch has resident
+// row norms (ScanArgs::row_norm) -- the matrix sweep needs them
 ScanVariant scan_variant(int qbits, const RowMap &m, bool tiled, int kp, bool collect, bool masked, int ring,
                          bool no_shape_kernels, int group = 1, int n_queries = 1, int block = 256, int planes = 3,
-                         int group_ring = 0);
+                         int group_ring = 0, int matrix_opt = 1, bool norms = false);
 // Ring depths of the G > 1 kernels.  A row-shape kernel of P pieces per lane exists at its shape's own depth (the
 // G = 1 kernel's) and, where kGroupRingAlt divides P and differs from it, at kGroupRingAlt as well: scan_group_ring
 // picks one of the two, 0 takes kGroupRingAuto where the shape has it and the shape's own depth elsewhere.
@@ -194,13 +207,18 @@ inline bool scan_masked(const ScanArgs &a) { return a.live_bits != nullptr || a.
 int scan_passes(int qbits, const ScanArgs &a, int block);
 // queries per row read of the variant launch_scan takes for `a`
 int scan_group_of(int qbits, const ScanArgs &a, int block);
+// would launch_scan read resident row norms for `a`, if it had them (a G > 1 variant or the matrix sweep)?  The caller
+// then asks for them (scan_row_norms) before it launches.
+bool scan_wants_norms(int qbits, const ScanArgs &a, int block);
 
 // Fused dequantize + distance + select.  QBITS in {4,8,16,32,64}.
 hipError_t launch_scan(int qbits, int metric, const ScanArgs &a, int grid, int block,
                        hipStream_t stream);
 // LDS bytes launch_scan needs for (qbits, map, kp, block) at `group` queries per row read; planes = 2: the images of a
 // group (group > 1, 8-bit rows) hold two digit planes
-size_t scan_lds_bytes(int qbits, const RowMap &m, int kp, int block, int group = 1, int planes = 3);
+// matrix: the matrix sweep's -- kMatrixQueries two-plane images laid out for the matrix cores, their constants, and
+// kMatrixQueries x waves lists of kp entries
+size_t scan_lds_bytes(int qbits, const RowMap &m, int kp, int block, int group = 1, int planes = 3, bool matrix = false);
 
 // Merge n_lists sorted lists of kp candidates into ceil(n_lists/merge_fan(kp)) lists.
 int merge_fan(int kp);

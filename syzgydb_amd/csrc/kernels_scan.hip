@@ -49,6 +49,9 @@ static hipError_t launch_scan_g8(int metric, int form, const ScanArgs &a, const 
     }
 #undef SZG_CASE_G8
 }
+// the matrix sweep, one object per metric (kernels_scan_mx.hip)
+hipError_t launch_scan_mx_m0(const ScanArgs &, const ScanVariant &, int, int, size_t, hipStream_t);
+hipError_t launch_scan_mx_m1(const ScanArgs &, const ScanVariant &, int, int, size_t, hipStream_t);
 #endif
 
 namespace {
@@ -1326,9 +1329,11 @@ hipError_t launch_scan_qmcm(const ScanArgs &a, int grid, int block, hipStream_t 
 {
     const dim3 g(grid), b(block);
     const ScanVariant v = scan_variant(QBITS, a.map, a.tiled != 0, a.kp, COLLECT, MASKED, a.ring, a.no_shape_kernels != 0,
-                                       a.group, a.n_queries, block, a.planes, a.group_ring);
-    const size_t lds = scan_lds_bytes(QBITS, a.map, COLLECT ? 0 : a.kp, block, v.group, a.planes);
+                                       a.group, a.n_queries, block, a.planes, a.group_ring, a.matrix, a.row_norm != nullptr);
+    const size_t lds = scan_lds_bytes(QBITS, a.map, COLLECT ? 0 : a.kp, block, v.group, a.planes, v.matrix != 0);
     if constexpr (QBITS == 8 && !COLLECT && !MASKED) {
+        // the matrix sweep: up to kMatrixQueries queries per row read on the matrix cores (kernels_scan_mx.hip)
+        if (v.matrix) return METRIC == kCosine ? launch_scan_mx_m1(a, v, grid, block, lds, stream) : launch_scan_mx_m0(a, v, grid, block, lds, stream);
         // G > 1: the form of the kernel -- two digit planes where the queries carry two (bit 0), resident norms where
         // the launch has them (bit 1); every form is an object of its own (SZG_GROUP_FORM)
         if (v.group > 1) return launch_scan_g8(METRIC, (a.planes == 2 ? 1 : 0) | (a.row_norm ? 2 : 0), a, v, grid, block, lds, stream);
@@ -1399,7 +1404,8 @@ SZG_DECL_SCAN(64)
 // The instantiation a launch takes.  Row-shape kernels serve unmasked sweeps over dense maps whose lists stay in
 // registers; everything else is the any-shape kernel, with the deep ring when the lists live in LDS (kp > 64).
 ScanVariant scan_variant(int qbits, const RowMap &m, bool tiled, int kp, bool collect, bool masked, int ring,
-                         bool no_shape_kernels, int group, int n_queries, int block, int planes, int group_ring)
+                         bool no_shape_kernels, int group, int n_queries, int block, int planes, int group_ring, int matrix_opt,
+                         bool norms)
 {
     ScanVariant v{};
     [[maybe_unused]] int shape_p = 0;  // pieces per lane of the row-shape kernel taken
@@ -1436,11 +1442,26 @@ ScanVariant scan_variant(int qbits, const RowMap &m, bool tiled, int kp, bool co
         // G times later than in the G = 1 kernel: they carry a depth of their own (option scan_group_ring).
         if (g > 1 && v.shaped) v.ring_depth = scan_group_ring_of(shape_p, v.ring_depth, group_ring);
     }
+    // The matrix sweep (kernels_scan_mx.hip; option sketch_matrix): the same launches -- unmasked 8-bit top-k sweeps with
+    // lists in registers -- over TILED rows of whole 64-byte steps, whose queries carry two digit planes and whose rows'
+    // norms are resident, under scan_group = 0 only (1, 2 and 4 name the VALU kernels).  From kMatrixMinQueries queries
+    // on (sketch_matrix = 2: from one); a lone query of an automatic launch keeps the G = 1 kernel.
+    if (qbits == 8 && !collect && !masked && !v.deep && kp >= 1 && tiled && m.r16 > 0 && m.r16 % 4 == 0 && planes == 2 &&
+        norms && group == 0 && matrix_opt != 1 && n_queries >= (matrix_opt == 2 ? 1 : kMatrixMinQueries) && block >= kWave &&
+        block <= 256 && block % kWave == 0 && scan_lds_bytes(qbits, m, kp, block, kMatrixQueries, planes, true) <= 64u * 1024u) {
+        v.matrix = 1;
+        v.matrix_steps = matrix_steps_form(m.r16 / 4);
+        v.group = kMatrixQueries;
+        v.shaped = 0;
+        v.ring_depth = v.matrix_steps == 12 ? 6 : (v.matrix_steps == 6 ? 3 : 4);
+    }
     return v;
 }
 
-size_t scan_lds_bytes(int qbits, const RowMap &m, int kp, int block, int group, int planes)
+size_t scan_lds_bytes(int qbits, const RowMap &m, int kp, int block, int group, int planes, bool matrix)
 {
+    if (matrix)  // 16 two-plane images (32 bytes per piece and query) | qscale, qconst, qnorm2 | 16 x waves lists
+        return (size_t)kMatrixQueries * ((size_t)m.r16 * 32 + 3 * sizeof(float) + (size_t)(block / kWave) * kp * sizeof(uint64_t));
     // per query of a group: query image + per-wave candidate lists; per-wave lists of row steps that survive the masks
     // (the two-plane images exist in the G > 1 kernels only: a lone query stages the whole image, its h plane all zero)
     const size_t image = qbits == 8 && group > 1 && planes == 2 ? (size_t)m.r16 * 32 : query_lds_bytes(qbits, m.r16);
@@ -1451,8 +1472,15 @@ size_t scan_lds_bytes(int qbits, const RowMap &m, int kp, int block, int group, 
 int scan_group_of(int qbits, const ScanArgs &a, int block)
 {
     return scan_variant(qbits, a.map, a.tiled != 0, a.kp, a.collect != 0, scan_masked(a), a.ring, a.no_shape_kernels != 0,
-                        a.group, a.n_queries, block, a.planes, a.group_ring)
+                        a.group, a.n_queries, block, a.planes, a.group_ring, a.matrix, a.row_norm != nullptr)
         .group;
+}
+
+bool scan_wants_norms(int qbits, const ScanArgs &a, int block)
+{
+    return scan_variant(qbits, a.map, a.tiled != 0, a.kp, a.collect != 0, scan_masked(a), a.ring, a.no_shape_kernels != 0,
+                        a.group, a.n_queries, block, a.planes, a.group_ring, a.matrix, true)
+               .group > 1;
 }
 
 int scan_passes(int qbits, const ScanArgs &a, int block)

@@ -1,0 +1,341 @@
+// kernels_scan_mx.hip -- the one-sweep scan's matrix form: up to 16 queries of a launch scored
+// per row read, on the matrix cores, with the one-sweep kernel's output contract (sorted block lists of a.kp entries).
+//
+// Serves unmasked top-k sweeps over TILED 8-bit rows of whole 64-byte steps whose queries carry two digit planes
+// (ScanArgs::planes == 2), with resident norms (ScanArgs::row_norm) and lists in registers (kp <= 64): today the
+// sketch index.  scan_variant (kernels_scan.hip) decides; everything else keeps scan_kernel.
+//
+// The pass over the rows is mq_score_i8s_kernel's (kernels_mq_i8.hip): one wave per tile of 16 rows; the B operand of
+// a 64-byte step is the row bytes as loaded (lane = chunk * 16 + row holds 16 consecutive elements) xor 0x80808080, the
+// A operand the same elements of a digit plane of 16 queries (lane = chunk * 16 + query) from an image in LDS.  Both
+// operands use the same lane -> K mapping, so the products pair element with element.  One v_mfma_i32_16x16x64_i8 per
+// plane and step: two per step, where the grouped VALU kernel spends 8 v_dot4 per query, row and piece.  After a tile,
+// lane (chunk c, row t) holds the exact integer plane sums M, L of queries 4c .. 4c + 3 against row t.
+//
+// Keys.  v' = v - 128, n = 2 v' + 1, Q = 128 m + l (|Q| <= 16000), so sum Q n = 2 (128 M + L) + sum Q.  M and L are
+// exact integers.  The float chain from there is: one conversion of 128 M + L (the shaped kernels combine the planes
+// as integers, |128 M + L| <= 16000 * 128 * 64 * STEPS < 2^31 for STEPS <= 16; the any-STEPS kernel takes
+// fmaf(128, float(M), float(L)): two conversions and one fused rounding), fmaf(2, dot, qconst), and then cosine:
+// the product with qscale, the reciprocal square root of the resident norm (itself one conversion and one addition)
+// and the last product -- Euclidean: -2 qscale, qnorm2 + norm and one fmaf.  At most 8 roundings of values bounded by
+// Qmax * 128 * dim in units of sum v n, where key_eps' integer branch (scan_query.cpp) allows for 16: the keys of
+// this kernel stay inside that branch's bound for Qmax = 16000, and the same operations as RowAcc<8>::key_of form them.
+// They are NOT bit-identical to the grouped kernel's, which rounds four per-lane partial sums before adding them.
+//
+// Selection.  Per wave and query a WaveList of a.kp entries in registers (16 lists, one VGPR pair each).  Each lane
+// keeps the current worst_key of its four queries; a tile pays one compare per (row, query) pair and ONE ballot, and
+// only a tile with a passing lane goes on to the exact 64-bit offers, query by query.  At the end of a group the lists
+// are flushed and merged per query into the block's sorted list: exactly the block's best a.kp rows, as scan_kernel
+// leaves them.
+#include "kernels.h"
+#include "device_lists.h"
+
+#ifndef SZG_SCAN_METRIC
+#error "kernels_scan_mx.hip needs SZG_SCAN_METRIC (0 or 1)"
+#endif
+
+namespace szg {
+
+namespace {
+
+typedef int v4i32 __attribute__((ext_vector_type(4)));
+using u32x4 = __attribute__((ext_vector_type(4))) uint32_t;
+
+constexpr int kMxQ = kMatrixQueries;
+
+// one 64-byte step of 16 tiled rows is one contiguous KiB read once per pass: stream it past the caches (a template
+// fact -- a run-time flag is folded into one plain load, see mq_device.h)
+template <bool NT>
+__device__ __forceinline__ u32x4 load_rows(const uint8_t *p)
+{
+    if constexpr (NT) return __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(p));
+    else return *reinterpret_cast<const u32x4 *>(p);
+}
+
+// ring depth (16-byte loads a lane keeps in flight) of the shaped kernels; divides STEPS
+#ifndef SZG_MX_S12_RING
+#define SZG_MX_S12_RING 6
+#endif
+#ifndef SZG_MX_S6_RING
+#define SZG_MX_S6_RING 3
+#endif
+template <int STEPS>
+constexpr int mx_ring()
+{
+    return STEPS == 12 ? SZG_MX_S12_RING : (STEPS == 6 ? SZG_MX_S6_RING : 4);
+}
+
+// STEPS = 64-byte steps per row, a compile-time fact (12, 6: the tile's steps are unrolled, slot = step % D, the A
+// operands travel one phase ahead in a double buffer) or 0: any whole-step row, a rotating ring of 4.
+template <int METRIC, int STEPS, bool NT>
+__global__ __launch_bounds__(256, 2) void scan_mx_kernel(const ScanArgs a)
+{
+    static_assert(STEPS == 0 || (STEPS % 2 == 0 && STEPS % mx_ring<STEPS>() == 0), "even phases, ring divides the row");
+    static_assert(STEPS <= 16, "the integer plane combine needs |128 M + L| < 2^31");
+    extern __shared__ __align__(16) uint8_t smem[];
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int nwaves = blockDim.x >> 6;
+    const int steps = STEPS ? STEPS : (int)a.steps;
+    const int n16 = steps * 2 * 64;  // 16-byte words of a group's image: [step][plane m, l][chunk * 16 + query]
+
+    // LDS: the group's image | qscale, qconst, qnorm2 [16] | the wave lists [query of the group][wave][kp]
+    uint4 *image = reinterpret_cast<uint4 *>(smem);
+    float *qtab = reinterpret_cast<float *>(smem + (size_t)n16 * 16);
+    uint64_t *lists = reinterpret_cast<uint64_t *>(smem + (size_t)n16 * 16 + 3 * kMxQ * sizeof(float));
+
+    const int trow = lane & 15;
+    const int c = lane >> 4;
+    const RowLayout lay{a.pitch, a.tiled, a.steps};
+    const uint64_t n_tiles = ((uint64_t)a.n_rows + 15) / 16;
+    const uint64_t tile_stride = (uint64_t)gridDim.x * nwaves;
+    const uint64_t tile_first = (uint64_t)blockIdx.x * nwaves + wave;
+    const uint64_t n_it = tile_first < n_tiles ? (n_tiles - tile_first + tile_stride - 1) / tile_stride : 0;
+    const uint64_t last_row = a.n_rows ? (uint64_t)a.n_rows - 1 : 0;
+    // (a row past the end of the last tile, or a tile past the wave's last: a valid row, read and discarded)
+    auto row_ptr = [&](uint64_t tile) -> const uint8_t * {
+        return a.rows + piece_offset(lay, min(tile * 16 + trow, last_row), (uint32_t)c);
+    };
+
+    for (int qi = 0; qi < a.n_queries; qi += kMxQ) {
+        if (qi) __syncthreads();  // the previous group's lists have been merged, its image is free
+        // column x of the group holds query min(qi + x, n_queries - 1): the idle columns of the launch's last group score
+        // its last query again, offer nothing and write no lists
+        for (int i = tid; i < n16; i += blockDim.x) {
+            const int x = i & 15, chunk = (i >> 4) & 3, p = (i >> 6) & 1, st = i >> 7;
+            const int q = min(qi + x, a.n_queries - 1);
+            // (the staged query is [plane h, m, l][piece]: the all-zero h plane stays behind)
+            const uint4 *src = reinterpret_cast<const uint4 *>(reinterpret_cast<const uint8_t *>(a.query) +
+                                                               (size_t)q * a.query_stride) +
+                               (size_t)(1 + p) * a.map.r16 + (st * 4 + chunk);
+            image[i] = *src;
+        }
+#pragma unroll
+        for (int x = 0; x < kMxQ; x++) {
+            const int q = min(qi + x, a.n_queries - 1);  // (block-uniform: scalar loads of the arguments)
+            const float qs = a.qscale[q], qc = a.qconst[q], qn = a.qnorm2[q];
+            if (tid == x) {
+                qtab[x] = qs;
+                qtab[kMxQ + x] = qc;
+                qtab[2 * kMxQ + x] = qn;
+            }
+        }
+        WaveList wls[kMxQ];
+#pragma unroll
+        for (int x = 0; x < kMxQ; x++) wls[x].init(lists, a.kp, lane);  // (register lists: flushed by hand below)
+        float wk[4];  // worst_key of this lane's four queries (+inf while a list fills)
+        bool live[4];
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+            wk[r] = __builtin_inff();
+            live[r] = qi + c * 4 + r < a.n_queries;
+        }
+        float qsv[4], qcv[4], qnv[4];
+
+        // ---- the tile is done: keys of 4 queries x 1 row per lane, one compare each, one ballot for the tile
+        auto finish_tile = [&](uint64_t tile, const v4i32 &accM, const v4i32 &accL, float norm) {
+            const uint64_t row = tile * 16 + trow;
+            const bool row_ok = row < a.n_rows;
+            float key[4];
+            bool pass[4];
+            bool any = false;
+            [[maybe_unused]] const float inv = __frsqrt_rn(norm);
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+                float dot;
+                if constexpr (STEPS != 0) dot = (float)(accM[r] * 128 + accL[r]);
+                else dot = fmaf(128.0f, (float)accM[r], (float)accL[r]);
+                const float d2 = fmaf(2.0f, dot, qcv[r]);  // sum Q n
+                float k_;
+                if constexpr (METRIC == kCosine) k_ = -(d2 * qsv[r]) * inv;
+                else k_ = fmaf(-2.0f * qsv[r], d2, qnv[r] + norm);
+                k_ = fminf(k_, 3.0e38f);
+                key[r] = k_;
+                pass[r] = row_ok && live[r] && !(k_ > wk[r]);
+                any = any || pass[r];
+            }
+            if (!__ballot(any)) return;
+#pragma unroll
+            for (int x = 0; x < kMxQ; x++) {
+                const int r = x & 3;
+                const bool have = pass[r] && c == (x >> 2);
+                if (!__ballot(have)) continue;
+                wls[x].offer(have, ((uint64_t)ordered_key(key[r]) << 32) | (uint32_t)row, lane);
+                if (c == (x >> 2)) wk[r] = wls[x].worst_key;
+            }
+        };
+        auto read_consts = [&]() {
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+                qsv[r] = qtab[c * 4 + r];
+                qcv[r] = qtab[kMxQ + c * 4 + r];
+                qnv[r] = qtab[2 * kMxQ + c * 4 + r];
+            }
+        };
+        const v4i32 *qimg = reinterpret_cast<const v4i32 *>(smem) + lane;
+
+        if constexpr (STEPS != 0) {
+            constexpr int D = mx_ring<STEPS>();
+            u32x4 ring[D];
+            v4i32 acc[2] = {v4i32{0, 0, 0, 0}, v4i32{0, 0, 0, 0}};
+            uint64_t tile = tile_first;
+            const uint8_t *cur = row_ptr(tile);
+            // the ring's first D steps (D <= STEPS: all inside the first tile); the rows do not depend on the image
+#pragma unroll
+            for (int u = 0; u < D; u++) {
+                ring[u] = load_rows<NT>(cur + (size_t)u * 1024);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            __syncthreads();  // the image and the constants are complete
+            read_consts();
+            // the A operands travel one phase (step) ahead of the matrix instructions that use them, in a double buffer
+            v4i32 qbuf[2][2];
+            auto read_phase = [&](int st_, v4i32 (&dst)[2]) {
+                dst[0] = qimg[(st_ * 2 + 0) * 64];
+                dst[1] = qimg[(st_ * 2 + 1) * 64];
+            };
+            read_phase(0, qbuf[0]);
+            for (uint64_t it = 0; it < n_it; it++, tile += tile_stride) {
+                // (past the wave's last tile: its own tile again -- D loads nobody consumes)
+                const uint8_t *nxt = it + 1 < n_it ? row_ptr(tile + tile_stride) : cur;
+                const float norm = a.row_norm[min(tile * 16 + trow, last_row)];  // arrives while the tile's steps run
+#pragma unroll
+                for (int st = 0; st < STEPS; st++) {
+                    const u32x4 v_ = ring[st % D];
+                    // this slot's next load: the step D ahead, in this tile or the next
+                    ring[st % D] = st + D < STEPS ? load_rows<NT>(cur + (size_t)(st + D) * 1024)
+                                                  : load_rows<NT>(nxt + (size_t)(st + D - STEPS) * 1024);
+                    __builtin_amdgcn_sched_barrier(0);
+                    v4i32 bop;
+                    bop[0] = (int)(v_.x ^ 0x80808080u);
+                    bop[1] = (int)(v_.y ^ 0x80808080u);
+                    bop[2] = (int)(v_.z ^ 0x80808080u);
+                    bop[3] = (int)(v_.w ^ 0x80808080u);
+                    read_phase((st + 1) % STEPS, qbuf[(st + 1) & 1]);
+                    __builtin_amdgcn_sched_barrier(0);
+                    // (the tile's first matrix instructions start from a literal zero: no accumulator clearing per tile)
+                    acc[0] = __builtin_amdgcn_mfma_i32_16x16x64_i8(qbuf[st & 1][0], bop, st == 0 ? v4i32{0, 0, 0, 0} : acc[0], 0, 0, 0);
+                    acc[1] = __builtin_amdgcn_mfma_i32_16x16x64_i8(qbuf[st & 1][1], bop, st == 0 ? v4i32{0, 0, 0, 0} : acc[1], 0, 0, 0);
+                }
+                finish_tile(tile, acc[0], acc[1], norm);
+                cur = nxt;
+            }
+        } else {
+            constexpr int D = 4;
+            u32x4 ring[D];
+            v4i32 accM = v4i32{0, 0, 0, 0}, accL = v4i32{0, 0, 0, 0};
+            const uint64_t NP = n_it * (uint64_t)steps;  // 64-byte steps of this wave's tiles, walked as one stream
+            uint64_t itile = tile_first, ctile = tile_first;
+            int is = 0, cs = 0;
+            const uint8_t *iptr = row_ptr(tile_first);
+            float norm = 0.0f;
+#define SZG_MX_ISSUE(u)                                                                  \
+    {                                                                                    \
+        ring[u] = load_rows<NT>(iptr);                                                   \
+        if (++is == steps) {                                                             \
+            is = 0;                                                                      \
+            itile += tile_stride;                                                        \
+            iptr = row_ptr(itile);                                                       \
+        } else {                                                                         \
+            iptr += 1024;                                                                \
+        }                                                                                \
+    }
+#define SZG_MX_CONSUME(u)                                                                \
+    {                                                                                    \
+        const u32x4 v_ = ring[u];                                                        \
+        if (cs == 0) norm = a.row_norm[min(ctile * 16 + trow, last_row)];                \
+        v4i32 bop_;                                                                      \
+        bop_[0] = (int)(v_.x ^ 0x80808080u);                                             \
+        bop_[1] = (int)(v_.y ^ 0x80808080u);                                             \
+        bop_[2] = (int)(v_.z ^ 0x80808080u);                                             \
+        bop_[3] = (int)(v_.w ^ 0x80808080u);                                             \
+        const v4i32 am_ = qimg[(cs * 2 + 0) * 64], al_ = qimg[(cs * 2 + 1) * 64];        \
+        accM = __builtin_amdgcn_mfma_i32_16x16x64_i8(am_, bop_, accM, 0, 0, 0);          \
+        accL = __builtin_amdgcn_mfma_i32_16x16x64_i8(al_, bop_, accL, 0, 0, 0);          \
+        if (++cs == steps) {                                                             \
+            finish_tile(ctile, accM, accL, norm);                                        \
+            accM = v4i32{0, 0, 0, 0};                                                    \
+            accL = v4i32{0, 0, 0, 0};                                                    \
+            cs = 0;                                                                      \
+            ctile += tile_stride;                                                        \
+        }                                                                                \
+    }
+            uint64_t issued = D, consumed = 0;
+#pragma unroll
+            for (int u = 0; u < D; u++) {
+                SZG_MX_ISSUE(u)
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            __syncthreads();  // the image and the constants are complete
+            read_consts();
+            while (consumed + 2 * D <= NP) {
+#pragma unroll
+                for (int u = 0; u < D; u++) {
+                    SZG_MX_CONSUME(u)
+                    SZG_MX_ISSUE(u)
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+                consumed += D;
+                issued += D;
+            }
+            while (consumed < NP) {
+#pragma unroll
+                for (int u = 0; u < D; u++) {
+                    if (consumed < NP) {
+                        SZG_MX_CONSUME(u)
+                        consumed++;
+                        if (issued < NP) {
+                            SZG_MX_ISSUE(u)
+                            issued++;
+                        }
+                    }
+                }
+            }
+#undef SZG_MX_ISSUE
+#undef SZG_MX_CONSUME
+        }
+
+        // block-wide k-select over the waves' lists, query by query
+#pragma unroll
+        for (int x = 0; x < kMxQ; x++)
+            if (lane < a.kp) lists[((size_t)x * nwaves + wave) * a.kp + lane] = wls[x].mine;
+        __syncthreads();
+        for (int x = 0; x < kMxQ && qi + x < a.n_queries; x++)  // (block-uniform)
+            block_merge_lists(lists + (size_t)x * nwaves * a.kp, nwaves, a.kp,
+                              a.block_lists + ((size_t)(qi + x) * gridDim.x + blockIdx.x) * a.kp, tid, blockDim.x);
+        // loads and stores share one vmcnt on gfx9: drain the list stores once per group, so that the next group's ring
+        // gets counted waits (as scan_kernel does)
+        __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
+    }
+}
+
+template <int STEPS>
+hipError_t launch_mx_steps(const ScanArgs &a, int grid, int block, size_t lds, hipStream_t stream)
+{
+    hipLaunchKernelGGL((scan_mx_kernel<SZG_SCAN_METRIC, STEPS, true>), dim3(grid), dim3(block), lds, stream, a);
+    return hipGetLastError();
+}
+
+}  // namespace
+
+#define SZG_CAT2(a, b) a##b
+#define SZG_CAT(a, b) SZG_CAT2(a, b)
+// the matrix sweep of ONE metric (one object each, as the scan objects): v names the form (ScanVariant::matrix_steps)
+hipError_t SZG_CAT(launch_scan_mx_m, SZG_SCAN_METRIC)(const ScanArgs &a, const ScanVariant &v, int grid, int block, size_t lds,
+                                                    hipStream_t stream)
+{
+    // (scan_variant's conditions, once more: a launch that does not meet them must not reach these kernels)
+    if (!v.matrix || !v.nontemporal || !a.tiled || a.steps == 0 || (int)a.steps * 4 != a.map.r16 || a.planes != 2 ||
+        !a.row_norm || a.kp < 1 || a.kp > 64 || a.collect || scan_masked(a) || block < 64 || block > 256 || block % 64 ||
+        lds > 64u * 1024u)
+        return hipErrorInvalidValue;
+    if (v.matrix_steps != matrix_steps_form((int)a.steps)) return hipErrorInvalidValue;
+    switch (v.matrix_steps) {
+    case 12: return launch_mx_steps<12>(a, grid, block, lds, stream);
+    case 6: return launch_mx_steps<6>(a, grid, block, lds, stream);
+    default: return launch_mx_steps<0>(a, grid, block, lds, stream);
+    }
+}
+
+}  // namespace szg

@@ -613,6 +613,44 @@ int szg_debug_scan_group(int dim, int quant_bits, int kp, int collect, int maske
     return SZG_OK;
 }
 
+// test hook, host only: does the matrix sweep serve a one-sweep launch (scan_variant's answer under the conditions given,
+// with its passes per launch, LDS bytes and STEPS form)?  Additive: szg_debug_scan_group's answers do not change.
+int szg_debug_scan_matrix(int dim, int quant_bits, int n_queries, int kp, int planes, int norms, int tiled, int masked,
+                          int scan_group, int sketch_matrix, int32_t *serves, int32_t *passes, uint64_t *lds_bytes,
+                          int32_t *steps_form)
+{
+    if (!serves || !passes || !lds_bytes || !steps_form) return fail(SZG_E_INVALID, "null argument");
+    if (kp < 0 || n_queries < 1) return fail(SZG_E_INVALID, "kp or n_queries out of range");
+    if (planes != 2 && planes != 3) return fail(SZG_E_INVALID, "planes is 2 or 3");
+    if (scan_group != 0 && scan_group != 1 && scan_group != 2 && scan_group != 4)
+        return fail(SZG_E_INVALID, "scan_group is 0, 1, 2 or 4");
+    if (!szg::sketch_matrix_known(sketch_matrix)) return fail(SZG_E_INVALID, "sketch_matrix is 0, 1 or 2");
+    RowFormat f;
+    const int rc = row_format(dim, quant_bits, &f);
+    if (rc == SZG_E_UNSUPPORTED) return fail(rc, "dimension too large for the LDS-resident query");
+    if (rc) return rc;
+    // (tiled: the caller may only take the tiled layout away from a format that has it)
+    const bool is_tiled = f.layout.tiled != 0 && tiled != 0;
+    const LaunchGeom g = scan_geometry(quant_bits, f.map, f.row_bytes, f.layout.tiled != 0, 1u << 22, 256, kp);
+    *serves = 0;
+    *passes = 0;
+    *lds_bytes = 0;
+    *steps_form = 0;
+    for (int j = 0; j < n_queries; j += szg::kMaxSweepsPerLaunch) {  // (launches of queries_per_launch = 16, the default)
+        const int n = std::min(szg::kMaxSweepsPerLaunch, n_queries - j);
+        const szg::ScanVariant v = szg::scan_variant(quant_bits, f.map, is_tiled, kp, false, masked != 0, szg_index::ring,
+                                                     !szg_index::shape_kernels, scan_group, n, g.block, planes, 0, sketch_matrix,
+                                                     norms != 0);
+        if (j == 0) {
+            *serves = v.matrix;
+            *steps_form = v.matrix_steps;
+            *lds_bytes = szg::scan_lds_bytes(quant_bits, f.map, kp, g.block, v.group, planes, v.matrix != 0);
+        }
+        *passes += (n + v.group - 1) / v.group;
+    }
+    return SZG_OK;
+}
+
 // test hook, host only: does the one-launch short-list merge serve (n_lists, m, kp), and how many entries under its
 // threshold its selection sorts at most (more: the tournament; fewer than kp: the tournament always)
 int szg_debug_merge_short_plan(int n_lists, int m, int kp, int32_t *fits, int32_t *sorts)

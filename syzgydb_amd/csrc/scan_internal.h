@@ -431,6 +431,9 @@ struct szg_index {
                               // 0 = automatic, 1 = always sum them in the sweep
     int sketch_planes = 0;    // digit planes of a query prepared for a sketch sweep: 0 = automatic (2, |Q| <= 16000),
                               // 3 = the plain 8-bit handles' (|Q| <= 10^6).  Only is_sketch indexes read it (scan_planes).
+    int sketch_matrix = 0;    // the matrix sweep (kernels_scan_mx.hip) for one-sweep launches that qualify -- tiled 8-bit rows,
+                              // two-plane queries, resident norms, no masks, scan_group = 0: 0 = automatic (launches of
+                              // szg::kMatrixMinQueries queries or more), 1 = never, 2 = every such launch
     bool is_sketch = false;   // this index is the internal sketch of a float32 handle: its keys only bound
     int tie_mode = 0;         // 0: exact full replay on ties/NaN, 1: keep the fast answer
     int serialize_scans = 1;  // scan launches of a shard never overlap each other

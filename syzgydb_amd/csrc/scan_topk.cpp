@@ -141,6 +141,7 @@ void fill_scan_args(const szg_index *ix, const Shard *sh, const Ctx *c, bool has
     a->group = ix->scan_group;
     a->group_ring = ix->scan_group_ring;
     a->planes = scan_planes(ix);  // (as prep_query quantized the staged queries)
+    a->matrix = ix->sketch_matrix;
 }
 
 // Launch the fused scan for each of the batch's queries (n = a->size()) as the
@@ -237,14 +238,18 @@ int enqueue_topk(szg_index *ix, Shard *sh, Ctx *c, int kp, int nq, bool has_allo
                 a.mask_dense = lowest >= 0.5 ? 1 : 0;
             }
             a.kp = m;
+            // (a call that keeps more than 64 candidates per query -- lists that would not fit registers at full length --
+            // stays with the grouped kernels even where its short lists would fit)
+            if (kp > 64) a.matrix = 1;
             a.block_lists = c->d_lists_a + (size_t)j * g.grid * m;
         }
-        // launches that score groups of queries per row read take the rows' norms from the resident array (complete
-        // before the sweeps are enqueued; it only has work to do after rows were added)
+        // launches that score groups of queries per row read -- the grouped kernels and the matrix sweep, which cannot do
+        // without -- take the rows' norms from the resident array (complete before the sweeps are enqueued; it only has
+        // work to do after rows were added)
         const float *norms = nullptr;
         bool asked = false;
         for (szg::ScanArgs &a : args) {
-            if (szg::scan_group_of(ix->bits, a, g.block) < 2) continue;
+            if (!szg::scan_wants_norms(ix->bits, a, g.block)) continue;
             if (!asked) {
                 int nrc = SZG_OK;
                 norms = scan_row_norms(ix, sh, &nrc);

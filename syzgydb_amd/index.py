@@ -892,6 +892,19 @@ def scan_group_plan(dim, quant_bits, n_queries, kp=10, scan_group=0, queries_per
     return {"group": g.value, "lds_bytes": lds.value, "passes": passes.value}
 
 
+def scan_matrix_plan(dim, quant_bits, n_queries, kp=10, planes=2, norms=True, tiled=True, masked=False, scan_group=0,
+                     sketch_matrix=0):
+    """Host-only test hook: whether the matrix sweep (option sketch_matrix) serves a one-sweep top-k call of n_queries
+    queries -- the first launch's answer, LDS bytes and STEPS form, and the passes over the rows of the whole call."""
+    L = _lib.load()
+    serves, passes, lds, form = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_uint64(), ctypes.c_int32()
+    check(L.szg_debug_scan_matrix(int(dim), int(quant_bits), int(n_queries), int(kp), int(planes), int(bool(norms)),
+                                  int(bool(tiled)), int(bool(masked)), int(scan_group), int(sketch_matrix),
+                                  ctypes.byref(serves), ctypes.byref(passes), ctypes.byref(lds), ctypes.byref(form)),
+          "szg_debug_scan_matrix")
+    return {"serves": bool(serves.value), "passes": passes.value, "lds_bytes": lds.value, "steps": form.value}
+
+
 def scan_group_ring_plan(dim, quant_bits, n_queries, kp=10, scan_group=0, scan_group_ring=0):
     """Host-only test hook: the ring depth a one-sweep launch of n_queries queries takes under options scan_group and
     scan_group_ring, and the values of scan_group_ring the library accepts beside 0 (the depths it carries)."""
@@ -916,7 +929,7 @@ def merge_short_plan(n_lists, m, kp):
 
 def option_check(name, value):
     """Host-only test hook (no device needed): raises SzgError where ScanIndex.set_option would refuse `value` for the
-    one-sweep kernel's option `name` (scan_group, scan_group_ring, scan_norms, sketch_planes)."""
+    one-sweep kernel's option `name` (scan_group, scan_group_ring, scan_norms, sketch_planes, sketch_matrix)."""
     L = _lib.load()
     check(L.szg_debug_option_check(name.encode(), int(value)), "szg_debug_option_check")
 
