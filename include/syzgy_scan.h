@@ -691,6 +691,12 @@ int szg_reset_stats(szg_index *ix);
  *                             launch the shape allows, whatever its query count.  Keys stay inside the same error bound
  *                             but are not bit-identical to the grouped kernels'; answers are.  szg_stats.scan_bytes
  *                             counts one pass per 16 queries of such a launch.  Other values are refused
+ *     sketch_select       0   how the matrix sweep keeps its 16 lists per wave: 0 = automatic -- lists of up to 16
+ *                             entries (sketch_list; 8 by default) live in the 16 lanes of a quarter of the wave, four
+ *                             queries to a register pair, and every round inserts one candidate into each of the 16 --,
+ *                             1 = one whole-wave list per query and one insert at a time, which longer lists always
+ *                             take.  Lists, keys, the drop bound and answers are the same bit for bit; only the
+ *                             sweep's time differs.  Other values are refused
  *     query_batch         16  queries staged, merged, re-ranked and copied back together
  *     mask_dense          1   sweeps whose filter / tombstone masks pass at least half the rows read every row and
  *                             apply the masks at the row finish; selective masks (and 0) compact the row steps that
@@ -808,6 +814,14 @@ int szg_debug_scan_matrix(int dim, int quant_bits, int n_queries, int kp, int pl
                           int32_t *steps_form);
 
 /*
+ * Test hook, host only: which selection (option sketch_select) the first launch of a one-sweep top-k call of n_queries
+ * queries takes, under the conditions of szg_debug_scan_matrix.  *serves = the matrix sweep serves the launch;
+ * *row_lists = 1: it keeps row lists (kp <= 16 under sketch_select = 0), 0: the serial inserts -- or it does not serve.
+ */
+int szg_debug_scan_select(int dim, int quant_bits, int n_queries, int kp, int planes, int norms, int tiled, int masked,
+                          int scan_group, int sketch_matrix, int sketch_select, int32_t *serves, int32_t *row_lists);
+
+/*
  * Test hook, host only: *fits = the sketch sweep's one-launch short-list merge serves n_lists block lists of m entries
  * at kp candidates; *sorts = the most entries under its threshold (the kp-th smallest first entry) that its selection
  * sorts in one network -- with more, and always when *sorts < kp, the launch runs the tournament.
@@ -824,7 +838,7 @@ int szg_debug_scan_group_ring(int dim, int quant_bits, int kp, int scan_group, i
 
 /*
  * Test hook, host only: would szg_set_option accept `value` for the one-sweep kernel's option `name` (scan_group,
- * scan_group_ring, scan_norms, sketch_planes, sketch_matrix)?  SZG_OK, or SZG_E_INVALID with szg_set_option's text; any other name is refused.
+ * scan_group_ring, scan_norms, sketch_planes, sketch_matrix, sketch_select)?  SZG_OK, or SZG_E_INVALID with szg_set_option's text; any other name is refused.
  */
 int szg_debug_option_check(const char *name, int64_t value);
 

@@ -1,6 +1,8 @@
 """Launch times of the sketch sweep by the library's HIP events, matrix sweep against the grouped kernels:
 1M x 768 float32 cosine (the headline's handle), calls of 1, 2, 3, 4, 16 and 32 queries under sketch_matrix = 2 (the
-matrix sweep whatever the count) and 1 (G = 1, 2, 4).  SZG_NO_EARLY_TAIL=1 keeps a 16-query call one launch.
+matrix sweep whatever the count) with row lists (sketch_select = 0) and with the serial inserts (sketch_select = 1),
+and under sketch_matrix = 1 (G = 1, 2, 4).  SZG_NO_EARLY_TAIL=1 keeps a 16-query call one launch.  A library from
+before sketch_select (an A/B run through SZG_LIB_PATH) shows its one matrix sweep.
 usage: SZG_NO_EARLY_TAIL=1 python scripts/dev_matrix.py [rows] [dim]"""
 import os
 import sys
@@ -20,8 +22,14 @@ with ScanIndex(dim, 32, SZG_COSINE) as ix:
         ix.set_option(name, v)
     ix.search_topk(Q[:16], 10)   # builds the sketch and the norms
     ix.set_timing(1)
-    for sm, label in ((2, "matrix"), (1, "grouped")):
+    for sm, sel, label in ((2, 0, "rows"), (2, 1, "serial"), (1, 0, "grouped")):
         ix.set_option("sketch_matrix", sm)
+        try:
+            ix.set_option("sketch_select", sel)
+        except Exception:
+            if sel:
+                continue
+            label = "matrix"
         for nq in (1, 2, 3, 4, 16, 32):
             for _ in range(3):
                 ix.search_topk(Q[:nq], 10)

@@ -55,6 +55,7 @@ EXPORTS = [
     # host-only test hook
     "szg_debug_scan_plan", "szg_debug_scan_group", "szg_debug_reorder_plan", "szg_debug_option_check",
     "szg_debug_scan_group_ring", "szg_debug_merge_short_plan", "szg_debug_scan_matrix",
+    "szg_debug_scan_select",
     # who owns device memory: the counters and the refusal countdown (added under ABI 4)
     "szg_debug_device_memory", "szg_debug_refuse_device_alloc",
     # the certificate trace: what each pass handed to certification (added under ABI 4)
@@ -394,6 +395,9 @@ def load():
         L.szg_debug_scan_matrix.restype = ctypes.c_int
         L.szg_debug_scan_matrix.argtypes = [ctypes.c_int] * 10 + [ctypes.POINTER(ctypes.c_int32)] * 2 + [u64p,
                                                                                                     ctypes.POINTER(ctypes.c_int32)]
+    if hasattr(L, "szg_debug_scan_select"):
+        L.szg_debug_scan_select.restype = ctypes.c_int
+        L.szg_debug_scan_select.argtypes = [ctypes.c_int] * 11 + [ctypes.POINTER(ctypes.c_int32)] * 2
     if hasattr(L, "szg_debug_scan_group_ring"):
         L.szg_debug_scan_group_ring.restype = ctypes.c_int
         L.szg_debug_scan_group_ring.argtypes = [ctypes.c_int] * 6 + [ctypes.POINTER(ctypes.c_int32)] * 3

@@ -122,6 +122,57 @@ struct WaveList {
     }
 };
 
+// within each row of 16 lanes, lane j receives lane j-1's value (a row's lane 0 keeps its own)
+__device__ __forceinline__ uint64_t row_shr1_u64(uint64_t v)
+{
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp((int)(uint32_t)v, (int)(uint32_t)v, 0x111,
+                                                              0xF, 0xF, false);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp((int)(uint32_t)(v >> 32),
+                                                              (int)(uint32_t)(v >> 32), 0x111, 0xF, 0xF,
+                                                              false);
+    return ((uint64_t)hi << 32) | lo;
+}
+
+// RowList: FOUR lists of m <= 16 candidates in one register pair, one per lane-row (lanes 16 c .. 16 c + 15): lane
+// (c, j) holds entry j of lane-row c's list, sorted ascending, entries j >= m stay kInvalidCand.  Where every
+// lane-row has candidates of its own to offer (the matrix sweep: lane-row c scores queries 4 c .. 4 c + 3), one round
+// inserts one candidate into each of the four lists at once, with per-lane VALU work, row-wise DPP and the LDS
+// crossbar only -- no value travels through a scalar register, where WaveList::insert is a chain through three.
+struct RowList {
+    uint64_t mine;   // entry `lane & 15` of this lane-row's list
+    uint64_t worst;  // its entry m - 1 (uniform within the lane-row; kInvalidCand while the list fills)
+
+    __device__ __forceinline__ void init()
+    {
+        mine = kInvalidCand;
+        worst = kInvalidCand;
+    }
+
+    // One round.  act: the ballot of the lanes whose candidate is below their lane-row's `worst`; a lane's candidate is
+    // (ukey << 32) | (row0 + (lane & 15)).  In every lane-row with such a lane the first of them is retired: its
+    // candidate goes into the lane-row's list and its bit of `pass` is cleared.  Lane-rows without one change nothing.
+    __device__ __forceinline__ void round(uint64_t act, bool &pass, uint32_t ukey, uint32_t row0, int lane, int m)
+    {
+        const int j = lane & 15, base = lane & 48;
+        const uint32_t slice = (uint32_t)(act >> base) & 0xFFFFu;  // this lane-row's lanes
+        const bool on = slice != 0;
+        const int first = (__ffs((int)slice) - 1) & 15;            // (slice == 0: lane 0, unused)
+        const uint32_t ck = (uint32_t)__builtin_amdgcn_ds_bpermute((base + first) << 2, (int)ukey);
+        const uint64_t cand = ((uint64_t)ck << 32) | (row0 + (uint32_t)first);
+        // entries are unique and sorted ascending: the entries below the candidate are a prefix of the lane-row
+        const int pos = __popc((uint32_t)(__ballot(mine < cand) >> base) & 0xFFFFu);
+        const uint64_t up = row_shr1_u64(mine);
+        if (on && j >= pos && j < m) mine = j == pos ? cand : up;
+        if (on && j == first) pass = false;
+        worst = shfl_u64(mine, base + m - 1);
+    }
+
+    __device__ __forceinline__ float worst_key() const
+    {
+        return worst == kInvalidCand ? __builtin_inff() : key_from_ordered((uint32_t)(worst >> 32));
+    }
+};
+
 // number of entries of sorted list[0..n) that are < c
 __device__ __forceinline__ int lower_count(const uint64_t *list, int n, uint64_t c)
 {

@@ -152,6 +152,8 @@ struct ScanArgs {
                                 // one (scan_variant); 0 = automatic
     int matrix;                 // option sketch_matrix: 0 = automatic (the matrix sweep where the launch qualifies and holds
                                 // kMatrixMinQueries queries), 1 = never, 2 = wherever the shape allows, whatever the count
+    int select;                 // option sketch_select: how the matrix sweep keeps its lists -- 0 = automatic (row lists
+                                // where kp <= kRowListMax), 1 = the serial inserts (one WaveList per query) everywhere
 };
 
 // Which scan_kernel instantiation a launch takes: decided on the host by scan_variant -- the launcher dispatches on
@@ -164,6 +166,8 @@ struct ScanVariant {
     int group;        // queries of the launch scored per row read (1, 2 or 4; kMatrixQueries: the matrix sweep)
     int matrix;       // the matrix sweep (kernels_scan_mx.hip) serves the launch: one pass per kMatrixQueries queries
     int matrix_steps; // its form: 12 or 6 (64-byte steps per row fixed at compile time), 0 = the any-steps kernel
+    int row_lists;    // the matrix sweep keeps its 16 lists as row lists (RowList, device_lists.h): kp <= kRowListMax
+                      // under sketch_select = 0; else one WaveList per query and the serial inserts
 };
 // What "automatic" (scan_group = 0) asks for, where a launch qualifies.
 constexpr int kScanGroupAuto = 4;
@@ -174,14 +178,20 @@ constexpr int kMatrixQueries = 16;
 constexpr int kMatrixMinQueries = 3;
 constexpr int matrix_steps_form(int steps) { return steps == 12 || steps == 6 ? steps : 0; }
 constexpr bool sketch_matrix_known(int64_t v) { return v == 0 || v == 1 || v == 2; }
+// The matrix sweep's selection (option sketch_select): lists of up to kRowListMax entries live in the 16 lanes of a
+// lane-row, four queries to a register pair, and take one candidate each per round (0 = automatic); 1 = the serial
+// inserts into one WaveList per query, which longer lists always take.
+constexpr int kRowListMax = 16;
+constexpr bool sketch_select_known(int64_t v) { return v == 0 || v == 1; }
+constexpr bool matrix_row_lists(int kp, int select_opt) { return select_opt == 0 && kp >= 1 && kp <= kRowListMax; }
 // group: the scan_group option (0 = automatic), n_queries: the launch's, block: its threads (the group's query images
 // -- of `planes` digit planes each -- and lists have to fit 64 KiB of LDS)
 // group_ring: the scan_group_ring option (0 = automatic)
 // matrix_opt: the sketch_matrix option (1 = off, what callers that do not know it get); norms: the launch has resident
-// row norms (ScanArgs::row_norm) -- the matrix sweep needs them
+// row norms (ScanArgs::row_norm) -- the matrix sweep needs them; select_opt: the sketch_select option
 ScanVariant scan_variant(int qbits, const RowMap &m, bool tiled, int kp, bool collect, bool masked, int ring,
                          bool no_shape_kernels, int group = 1, int n_queries = 1, int block = 256, int planes = 3,
-                         int group_ring = 0, int matrix_opt = 1, bool norms = false);
+                         int group_ring = 0, int matrix_opt = 1, bool norms = false, int select_opt = 0);
 // Ring depths of the G > 1 kernels.  A row-shape kernel of P pieces per lane exists at its shape's own depth (the
 // G = 1 kernel's) and, where kGroupRingAlt divides P and differs from it, at kGroupRingAlt as well: scan_group_ring
 // picks one of the two, 0 takes kGroupRingAuto where the shape has it and the shape's own depth elsewhere.

@@ -1329,7 +1329,7 @@ hipError_t launch_scan_qmcm(const ScanArgs &a, int grid, int block, hipStream_t 
 {
     const dim3 g(grid), b(block);
     const ScanVariant v = scan_variant(QBITS, a.map, a.tiled != 0, a.kp, COLLECT, MASKED, a.ring, a.no_shape_kernels != 0,
-                                       a.group, a.n_queries, block, a.planes, a.group_ring, a.matrix, a.row_norm != nullptr);
+                                       a.group, a.n_queries, block, a.planes, a.group_ring, a.matrix, a.row_norm != nullptr, a.select);
     const size_t lds = scan_lds_bytes(QBITS, a.map, COLLECT ? 0 : a.kp, block, v.group, a.planes, v.matrix != 0);
     if constexpr (QBITS == 8 && !COLLECT && !MASKED) {
         // the matrix sweep: up to kMatrixQueries queries per row read on the matrix cores (kernels_scan_mx.hip)
@@ -1405,7 +1405,7 @@ SZG_DECL_SCAN(64)
 // registers; everything else is the any-shape kernel, with the deep ring when the lists live in LDS (kp > 64).
 ScanVariant scan_variant(int qbits, const RowMap &m, bool tiled, int kp, bool collect, bool masked, int ring,
                          bool no_shape_kernels, int group, int n_queries, int block, int planes, int group_ring, int matrix_opt,
-                         bool norms)
+                         bool norms, int select_opt)
 {
     ScanVariant v{};
     [[maybe_unused]] int shape_p = 0;  // pieces per lane of the row-shape kernel taken
@@ -1454,6 +1454,8 @@ ScanVariant scan_variant(int qbits, const RowMap &m, bool tiled, int kp, bool co
         v.group = kMatrixQueries;
         v.shaped = 0;
         v.ring_depth = v.matrix_steps == 12 ? 6 : (v.matrix_steps == 6 ? 3 : 4);
+        // its selection (option sketch_select): short lists as row lists, one candidate into each of the 16 per round
+        v.row_lists = matrix_row_lists(kp, select_opt) ? 1 : 0;
     }
     return v;
 }
@@ -1472,14 +1474,14 @@ size_t scan_lds_bytes(int qbits, const RowMap &m, int kp, int block, int group, 
 int scan_group_of(int qbits, const ScanArgs &a, int block)
 {
     return scan_variant(qbits, a.map, a.tiled != 0, a.kp, a.collect != 0, scan_masked(a), a.ring, a.no_shape_kernels != 0,
-                        a.group, a.n_queries, block, a.planes, a.group_ring, a.matrix, a.row_norm != nullptr)
+                        a.group, a.n_queries, block, a.planes, a.group_ring, a.matrix, a.row_norm != nullptr, a.select)
         .group;
 }
 
 bool scan_wants_norms(int qbits, const ScanArgs &a, int block)
 {
     return scan_variant(qbits, a.map, a.tiled != 0, a.kp, a.collect != 0, scan_masked(a), a.ring, a.no_shape_kernels != 0,
-                        a.group, a.n_queries, block, a.planes, a.group_ring, a.matrix, true)
+                        a.group, a.n_queries, block, a.planes, a.group_ring, a.matrix, true, a.select)
                .group > 1;
 }
 

@@ -22,11 +22,24 @@
 // this kernel stay inside that branch's bound for Qmax = 16000, and the same operations as RowAcc<8>::key_of form them.
 // They are NOT bit-identical to the grouped kernel's, which rounds four per-lane partial sums before adding them.
 //
-// Selection.  Per wave and query a WaveList of a.kp entries in registers (16 lists, one VGPR pair each).  Each lane
-// keeps the current worst_key of its four queries; a tile pays one compare per (row, query) pair and ONE ballot, and
-// only a tile with a passing lane goes on to the exact 64-bit offers, query by query.  At the end of a group the lists
-// are flushed and merged per query into the block's sorted list: exactly the block's best a.kp rows, as scan_kernel
-// leaves them.
+// Selection.  Each lane keeps the current worst_key of its four queries; a tile pays one compare per (row, query) pair
+// and ONE ballot, and only a tile with a passing lane goes on to the exact 64-bit inserts.  Two forms, a template
+// argument (ROWS; scan_variant decides, option sketch_select):
+//  * row lists (a.kp <= kRowListMax = 16): the 16 rows a tile offers to query 4c + r already sit
+//    in the 16 lanes of lane-row c, so that query's list lives there too -- four RowLists (device_lists.h), slot r of
+//    lane-row c the list of query 4c + r, lane (c, j) entry j: 8 registers for the 16 lists.  A round takes one ballot
+//    per slot, retires the first passing lane of every lane-row (its key comes over the LDS crossbar, its row number
+//    is the tile's first plus its lane), counts the entries below it within the lane-row, shifts by row_shr:1 and
+//    refreshes the lane-row's worst entry: up to 16 inserts per round, no scalar round trip, the four slots four
+//    independent chains; a slot none of whose lanes has a candidate left is skipped (measured: the same at 16 live
+//    queries, 3 % faster at one to three).  At most 16 rounds per tile, the bound in the loop itself.  There is no
+//    serial route beside the rounds for tiles with few passing lanes: launches of one to four live queries, where
+//    few lanes pass in every tile, measure the same under both forms, so it has nothing to win.
+//  * serial inserts (16 < a.kp <= 64, or sketch_select = 1): per wave and query a WaveList of a.kp entries in
+//    registers (16 lists, one VGPR pair each), offered to query by query, one candidate at a time.
+// An insert is a set operation on unique entries: both forms leave the same lists bit for bit.  At the end of a group
+// the lists go to the same LDS slots and are merged per query into the block's sorted list: exactly the block's best
+// a.kp rows, as scan_kernel leaves them.
 #include "kernels.h"
 #include "device_lists.h"
 
@@ -59,6 +72,10 @@ __device__ __forceinline__ u32x4 load_rows(const uint8_t *p)
 #ifndef SZG_MX_S6_RING
 #define SZG_MX_S6_RING 3
 #endif
+// the rounds of the row lists skip a slot none of whose lanes has a candidate left
+#ifndef SZG_MX_ROUND_SKIP
+#define SZG_MX_ROUND_SKIP 1
+#endif
 template <int STEPS>
 constexpr int mx_ring()
 {
@@ -67,7 +84,9 @@ constexpr int mx_ring()
 
 // STEPS = 64-byte steps per row, a compile-time fact (12, 6: the tile's steps are unrolled, slot = step % D, the A
 // operands travel one phase ahead in a double buffer) or 0: any whole-step row, a rotating ring of 4.
-template <int METRIC, int STEPS, bool NT>
+// ROWS: the wave's 16 lists are four RowLists (a.kp <= kRowListMax), else 16 WaveLists -- a template fact, so that the
+// tile loop of either form carries no trace of the other.
+template <int METRIC, int STEPS, bool NT, bool ROWS>
 __global__ __launch_bounds__(256, 2) void scan_mx_kernel(const ScanArgs a)
 {
     static_assert(STEPS == 0 || (STEPS % 2 == 0 && STEPS % mx_ring<STEPS>() == 0), "even phases, ring divides the row");
@@ -121,9 +140,17 @@ __global__ __launch_bounds__(256, 2) void scan_mx_kernel(const ScanArgs a)
                 qtab[2 * kMxQ + x] = qn;
             }
         }
+        // ROWS: slot r of lane-row c is the list of query 4 c + r; else one whole-wave list per query (the unused form
+        // is dead code: no registers)
+        RowList rls[4];
         WaveList wls[kMxQ];
+        if constexpr (ROWS) {
 #pragma unroll
-        for (int x = 0; x < kMxQ; x++) wls[x].init(lists, a.kp, lane);  // (register lists: flushed by hand below)
+            for (int r = 0; r < 4; r++) rls[r].init();
+        } else {
+#pragma unroll
+            for (int x = 0; x < kMxQ; x++) wls[x].init(lists, a.kp, lane);  // (register lists: flushed by hand below)
+        }
         float wk[4];  // worst_key of this lane's four queries (+inf while a list fills)
         bool live[4];
 #pragma unroll
@@ -156,13 +183,39 @@ __global__ __launch_bounds__(256, 2) void scan_mx_kernel(const ScanArgs a)
                 any = any || pass[r];
             }
             if (!__ballot(any)) return;
+            if constexpr (ROWS) {
+                // Rounds: the 16 rows offered to query 4 c + r sit in the 16 lanes of lane-row c, so one round retires
+                // one passing lane of every lane-row and slot -- up to 16 inserts, four independent chains (the slots).
+                // A round retires a lane of every lane-row that still has one: 16 rounds always suffice, and the bound
+                // stands in the loop itself.
+                uint32_t uk[4];
 #pragma unroll
-            for (int x = 0; x < kMxQ; x++) {
-                const int r = x & 3;
-                const bool have = pass[r] && c == (x >> 2);
-                if (!__ballot(have)) continue;
-                wls[x].offer(have, ((uint64_t)ordered_key(key[r]) << 32) | (uint32_t)row, lane);
-                if (c == (x >> 2)) wk[r] = wls[x].worst_key;
+                for (int r = 0; r < 4; r++) uk[r] = ordered_key(key[r]);
+                const uint32_t row0 = (uint32_t)(tile * 16);
+                for (int round = 0; round < 16; round++) {
+                    uint64_t act[4];
+#pragma unroll
+                    for (int r = 0; r < 4; r++)
+                        act[r] = __ballot(pass[r] && (((uint64_t)uk[r] << 32) | (uint32_t)row) < rls[r].worst);
+                    if (!(act[0] | act[1] | act[2] | act[3])) break;
+#pragma unroll
+                    for (int r = 0; r < 4; r++) {
+                        // (wave-uniform: late tiles have a few passing lanes, in one or two of the slots)
+                        if (SZG_MX_ROUND_SKIP && !act[r]) continue;
+                        rls[r].round(act[r], pass[r], uk[r], row0, lane, a.kp);
+                    }
+                }
+#pragma unroll
+                for (int r = 0; r < 4; r++) wk[r] = rls[r].worst_key();
+            } else {
+#pragma unroll
+                for (int x = 0; x < kMxQ; x++) {
+                    const int r = x & 3;
+                    const bool have = pass[r] && c == (x >> 2);
+                    if (!__ballot(have)) continue;
+                    wls[x].offer(have, ((uint64_t)ordered_key(key[r]) << 32) | (uint32_t)row, lane);
+                    if (c == (x >> 2)) wk[r] = wls[x].worst_key;
+                }
             }
         };
         auto read_consts = [&]() {
@@ -297,9 +350,15 @@ __global__ __launch_bounds__(256, 2) void scan_mx_kernel(const ScanArgs a)
         }
 
         // block-wide k-select over the waves' lists, query by query
+        if constexpr (ROWS) {
 #pragma unroll
-        for (int x = 0; x < kMxQ; x++)
-            if (lane < a.kp) lists[((size_t)x * nwaves + wave) * a.kp + lane] = wls[x].mine;
+            for (int r = 0; r < 4; r++)
+                if (trow < a.kp) lists[((size_t)(c * 4 + r) * nwaves + wave) * a.kp + trow] = rls[r].mine;
+        } else {
+#pragma unroll
+            for (int x = 0; x < kMxQ; x++)
+                if (lane < a.kp) lists[((size_t)x * nwaves + wave) * a.kp + lane] = wls[x].mine;
+        }
         __syncthreads();
         for (int x = 0; x < kMxQ && qi + x < a.n_queries; x++)  // (block-uniform)
             block_merge_lists(lists + (size_t)x * nwaves * a.kp, nwaves, a.kp,
@@ -311,9 +370,10 @@ __global__ __launch_bounds__(256, 2) void scan_mx_kernel(const ScanArgs a)
 }
 
 template <int STEPS>
-hipError_t launch_mx_steps(const ScanArgs &a, int grid, int block, size_t lds, hipStream_t stream)
+hipError_t launch_mx_steps(const ScanArgs &a, bool rows, int grid, int block, size_t lds, hipStream_t stream)
 {
-    hipLaunchKernelGGL((scan_mx_kernel<SZG_SCAN_METRIC, STEPS, true>), dim3(grid), dim3(block), lds, stream, a);
+    if (rows) hipLaunchKernelGGL((scan_mx_kernel<SZG_SCAN_METRIC, STEPS, true, true>), dim3(grid), dim3(block), lds, stream, a);
+    else hipLaunchKernelGGL((scan_mx_kernel<SZG_SCAN_METRIC, STEPS, true, false>), dim3(grid), dim3(block), lds, stream, a);
     return hipGetLastError();
 }
 
@@ -331,10 +391,13 @@ hipError_t SZG_CAT(launch_scan_mx_m, SZG_SCAN_METRIC)(const ScanArgs &a, const S
         lds > 64u * 1024u)
         return hipErrorInvalidValue;
     if (v.matrix_steps != matrix_steps_form((int)a.steps)) return hipErrorInvalidValue;
+    // (row lists hold at most kRowListMax entries: a longer list must never reach that form)
+    if ((v.row_lists != 0) != matrix_row_lists(a.kp, a.select)) return hipErrorInvalidValue;
+    const bool rows = v.row_lists != 0;
     switch (v.matrix_steps) {
-    case 12: return launch_mx_steps<12>(a, grid, block, lds, stream);
-    case 6: return launch_mx_steps<6>(a, grid, block, lds, stream);
-    default: return launch_mx_steps<0>(a, grid, block, lds, stream);
+    case 12: return launch_mx_steps<12>(a, rows, grid, block, lds, stream);
+    case 6: return launch_mx_steps<6>(a, rows, grid, block, lds, stream);
+    default: return launch_mx_steps<0>(a, rows, grid, block, lds, stream);
     }
 }
 

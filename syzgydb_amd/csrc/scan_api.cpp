@@ -651,6 +651,33 @@ int szg_debug_scan_matrix(int dim, int quant_bits, int n_queries, int kp, int pl
     return SZG_OK;
 }
 
+// test hook, host only: which selection the first launch (of up to 16 queries) of a one-sweep call takes under option
+// sketch_select -- scan_variant's answer: *row_lists = 1 where the matrix sweep serves the launch and keeps row lists,
+// 0 where it serves it with the serial inserts or does not serve it (*serves says which)
+int szg_debug_scan_select(int dim, int quant_bits, int n_queries, int kp, int planes, int norms, int tiled, int masked,
+                          int scan_group, int sketch_matrix, int sketch_select, int32_t *serves, int32_t *row_lists)
+{
+    if (!serves || !row_lists) return fail(SZG_E_INVALID, "null argument");
+    if (kp < 0 || n_queries < 1) return fail(SZG_E_INVALID, "kp or n_queries out of range");
+    if (planes != 2 && planes != 3) return fail(SZG_E_INVALID, "planes is 2 or 3");
+    if (scan_group != 0 && scan_group != 1 && scan_group != 2 && scan_group != 4)
+        return fail(SZG_E_INVALID, "scan_group is 0, 1, 2 or 4");
+    if (!szg::sketch_matrix_known(sketch_matrix)) return fail(SZG_E_INVALID, "sketch_matrix is 0, 1 or 2");
+    if (!szg::sketch_select_known(sketch_select)) return fail(SZG_E_INVALID, "sketch_select is 0 or 1");
+    RowFormat f;
+    const int rc = row_format(dim, quant_bits, &f);
+    if (rc == SZG_E_UNSUPPORTED) return fail(rc, "dimension too large for the LDS-resident query");
+    if (rc) return rc;
+    const bool is_tiled = f.layout.tiled != 0 && tiled != 0;
+    const LaunchGeom g = scan_geometry(quant_bits, f.map, f.row_bytes, f.layout.tiled != 0, 1u << 22, 256, kp);
+    const szg::ScanVariant v = szg::scan_variant(quant_bits, f.map, is_tiled, kp, false, masked != 0, szg_index::ring,
+                                                 !szg_index::shape_kernels, scan_group, std::min(szg::kMaxSweepsPerLaunch, n_queries),
+                                                 g.block, planes, 0, sketch_matrix, norms != 0, sketch_select);
+    *serves = v.matrix;
+    *row_lists = v.matrix && v.row_lists ? 1 : 0;
+    return SZG_OK;
+}
+
 // test hook, host only: does the one-launch short-list merge serve (n_lists, m, kp), and how many entries under its
 // threshold its selection sorts at most (more: the tournament; fewer than kp: the tournament always)
 int szg_debug_merge_short_plan(int n_lists, int m, int kp, int32_t *fits, int32_t *sorts)

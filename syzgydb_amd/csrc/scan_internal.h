@@ -434,6 +434,8 @@ struct szg_index {
     int sketch_matrix = 0;    // the matrix sweep (kernels_scan_mx.hip) for one-sweep launches that qualify -- tiled 8-bit rows,
                               // two-plane queries, resident norms, no masks, scan_group = 0: 0 = automatic (launches of
                               // szg::kMatrixMinQueries queries or more), 1 = never, 2 = every such launch
+    int sketch_select = 0;    // the matrix sweep's selection: 0 = automatic (row lists where the lists hold at most
+                              // szg::kRowListMax entries), 1 = the serial inserts everywhere
     bool is_sketch = false;   // this index is the internal sketch of a float32 handle: its keys only bound
     int tie_mode = 0;         // 0: exact full replay on ties/NaN, 1: keep the fast answer
     int serialize_scans = 1;  // scan launches of a shard never overlap each other

@@ -142,6 +142,7 @@ void fill_scan_args(const szg_index *ix, const Shard *sh, const Ctx *c, bool has
     a->group_ring = ix->scan_group_ring;
     a->planes = scan_planes(ix);  // (as prep_query quantized the staged queries)
     a->matrix = ix->sketch_matrix;
+    a->select = ix->sketch_select;
 }
 
 // Launch the fused scan for each of the batch's queries (n = a->size()) as the

@@ -905,6 +905,20 @@ def scan_matrix_plan(dim, quant_bits, n_queries, kp=10, planes=2, norms=True, ti
     return {"serves": bool(serves.value), "passes": passes.value, "lds_bytes": lds.value, "steps": form.value}
 
 
+def scan_select_plan(dim, quant_bits, n_queries, kp=8, planes=2, norms=True, tiled=True, masked=False, scan_group=0,
+                     sketch_matrix=0, sketch_select=0):
+    """Host-only test hook: which selection (option sketch_select) the first launch of a one-sweep top-k call of
+    n_queries queries takes -- whether the matrix sweep serves it, and whether it then keeps row lists (lists of at most
+    16 entries under sketch_select = 0) or the serial inserts."""
+    L = _lib.load()
+    serves, rows = ctypes.c_int32(), ctypes.c_int32()
+    check(L.szg_debug_scan_select(int(dim), int(quant_bits), int(n_queries), int(kp), int(planes), int(bool(norms)),
+                                  int(bool(tiled)), int(bool(masked)), int(scan_group), int(sketch_matrix),
+                                  int(sketch_select), ctypes.byref(serves), ctypes.byref(rows)),
+          "szg_debug_scan_select")
+    return {"serves": bool(serves.value), "row_lists": bool(rows.value)}
+
+
 def scan_group_ring_plan(dim, quant_bits, n_queries, kp=10, scan_group=0, scan_group_ring=0):
     """Host-only test hook: the ring depth a one-sweep launch of n_queries queries takes under options scan_group and
     scan_group_ring, and the values of scan_group_ring the library accepts beside 0 (the depths it carries)."""
@@ -929,7 +943,7 @@ def merge_short_plan(n_lists, m, kp):
 
 def option_check(name, value):
     """Host-only test hook (no device needed): raises SzgError where ScanIndex.set_option would refuse `value` for the
-    one-sweep kernel's option `name` (scan_group, scan_group_ring, scan_norms, sketch_planes, sketch_matrix)."""
+    one-sweep kernel's option `name` (scan_group, scan_group_ring, scan_norms, sketch_planes, sketch_matrix, sketch_select)."""
     L = _lib.load()
     check(L.szg_debug_option_check(name.encode(), int(value)), "szg_debug_option_check")
 
