@@ -697,6 +697,15 @@ int szg_reset_stats(szg_index *ix);
  *                             1 = one whole-wave list per query and one insert at a time, which longer lists always
  *                             take.  Lists, keys, the drop bound and answers are the same bit for bit; only the
  *                             sweep's time differs.  Other values are refused
+ *     sketch_wide         0   the matrix sweep's two-block form: launches of 17 to 32 queries with row lists (sketch_select)
+ *                             score 32 queries per row read where both blocks' images and lists fit 64 KiB of LDS (768
+ *                             dimensions: lists of up to 15 entries).  0 = automatic: a sketch call of 72 one-sweep queries
+ *                             or more under the default query_batch and queries_per_launch takes batches of 32 queries,
+ *                             one launch each, between its first and last batch of 4, and settles them on a second host
+ *                             thread (finish_thread); 1 = never; 2 = every sketch call of more than 16 queries takes
+ *                             batches and launches of up to 32, whatever its length.  Lists, keys, the drop bound and
+ *                             answers are the same bit for bit; szg_stats.scan_bytes counts one pass per 32 queries of a
+ *                             wide launch.  Other values are refused
  *     query_batch         16  queries staged, merged, re-ranked and copied back together
  *     mask_dense          1   sweeps whose filter / tombstone masks pass at least half the rows read every row and
  *                             apply the masks at the row finish; selective masks (and 0) compact the row steps that
@@ -822,6 +831,17 @@ int szg_debug_scan_select(int dim, int quant_bits, int n_queries, int kp, int pl
                           int scan_group, int sketch_matrix, int sketch_select, int32_t *serves, int32_t *row_lists);
 
 /*
+ * Test hook, host only: the matrix sweep's two-block form (option sketch_wide) for a one-sweep top-k call of n_queries
+ * queries, under the conditions of szg_debug_scan_select, split as a call with wide batches splits it: launches of up to
+ * 32 queries where a launch of 32 qualifies for the form, of up to 16 where it does not.  *serves = 1: the first launch
+ * scores 32 queries per row read; *lds_bytes = the LDS it asks for -- with b column blocks, 16 b (2 dim64 + 12 +
+ * 8 waves kp), dim64 the row bytes in whole 64-byte steps; *passes = passes over the rows of the whole call.
+ */
+int szg_debug_scan_wide(int dim, int quant_bits, int n_queries, int kp, int planes, int norms, int tiled, int masked,
+                        int scan_group, int sketch_matrix, int sketch_select, int sketch_wide, int32_t *serves,
+                        int32_t *passes, uint64_t *lds_bytes);
+
+/*
  * Test hook, host only: *fits = the sketch sweep's one-launch short-list merge serves n_lists block lists of m entries
  * at kp candidates; *sorts = the most entries under its threshold (the kp-th smallest first entry) that its selection
  * sorts in one network -- with more, and always when *sorts < kp, the launch runs the tournament.
@@ -838,7 +858,7 @@ int szg_debug_scan_group_ring(int dim, int quant_bits, int kp, int scan_group, i
 
 /*
  * Test hook, host only: would szg_set_option accept `value` for the one-sweep kernel's option `name` (scan_group,
- * scan_group_ring, scan_norms, sketch_planes, sketch_matrix, sketch_select)?  SZG_OK, or SZG_E_INVALID with szg_set_option's text; any other name is refused.
+ * scan_group_ring, scan_norms, sketch_planes, sketch_matrix, sketch_select, sketch_wide)?  SZG_OK, or SZG_E_INVALID with szg_set_option's text; any other name is refused.
  */
 int szg_debug_option_check(const char *name, int64_t value);
 

@@ -1,8 +1,9 @@
 """Launch times of the sketch sweep by the library's HIP events, matrix sweep against the grouped kernels:
 1M x 768 float32 cosine (the headline's handle), calls of 1, 2, 3, 4, 16 and 32 queries under sketch_matrix = 2 (the
 matrix sweep whatever the count) with row lists (sketch_select = 0) and with the serial inserts (sketch_select = 1),
-and under sketch_matrix = 1 (G = 1, 2, 4).  SZG_NO_EARLY_TAIL=1 keeps a 16-query call one launch.  A library from
-before sketch_select (an A/B run through SZG_LIB_PATH) shows its one matrix sweep.
+and under sketch_matrix = 1 (G = 1, 2, 4) -- all three with sketch_wide = 1 -- and the wide column: the two-block form
+(sketch_wide = 2, row lists) at 17, 32, 48 and 64 queries, one launch per 32.  SZG_NO_EARLY_TAIL=1 keeps a 16-query
+call one launch.  A library from before sketch_select or sketch_wide (an A/B run through SZG_LIB_PATH) shows what it has.
 usage: SZG_NO_EARLY_TAIL=1 python scripts/dev_matrix.py [rows] [dim]"""
 import os
 import sys
@@ -15,22 +16,27 @@ from syzgydb_amd import ScanIndex, SZG_COSINE  # noqa: E402
 
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 1000000
 dim = int(sys.argv[2]) if len(sys.argv) > 2 else 768
-Q = orc.synth_vectors(11, 0, 32, dim)
+Q = orc.synth_vectors(11, 0, 64, dim)
 with ScanIndex(dim, 32, SZG_COSINE) as ix:
     ix.synth(n, 7)
     for name, v in (("multi_query", 0), ("sketch", 1)):
         ix.set_option(name, v)
     ix.search_topk(Q[:16], 10)   # builds the sketch and the norms
     ix.set_timing(1)
-    for sm, sel, label in ((2, 0, "rows"), (2, 1, "serial"), (1, 0, "grouped")):
+    for sm, sel, label in ((2, 0, "rows"), (2, 0, "wide"), (2, 1, "serial"), (1, 0, "grouped")):
         ix.set_option("sketch_matrix", sm)
+        try:
+            ix.set_option("sketch_wide", 2 if label == "wide" else 1)
+        except Exception:
+            if label == "wide":
+                continue
         try:
             ix.set_option("sketch_select", sel)
         except Exception:
             if sel:
                 continue
             label = "matrix"
-        for nq in (1, 2, 3, 4, 16, 32):
+        for nq in (17, 32, 48, 64) if label == "wide" else (1, 2, 3, 4, 16, 32, 64):
             for _ in range(3):
                 ix.search_topk(Q[:nq], 10)
             ix.reset_stats()

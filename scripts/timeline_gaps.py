@@ -1,5 +1,7 @@
 """From a rocprofv3 kernel trace (+ memory-copy trace) of the headline: the gaps between consecutive sketch
-sweeps (the matrix sweep's launches, or the grouped kernel's in a library without it), what runs inside them and whether merges / reranks overlap a sweep.  usage: timeline_gaps.py <dir>"""
+sweeps (the matrix sweep's launches, or the grouped kernel's in a library without it), what runs inside them and whether
+merges / reranks overlap a sweep.  Where the trace holds launches of the matrix sweep's two-block form, the window is the
+last long call's.  usage: timeline_gaps.py <dir>"""
 import csv, glob, re, sys, statistics
 
 path = sys.argv[1]
@@ -19,7 +21,21 @@ if not sw:
 if not sw:
     sw = [e for e in ev if e[2].startswith("scan_kernel<8")]
 print("sweeps:", len(sw), "name:", sw[0][2] if sw else None)
-sw = sw[len(sw) // 4:]  # the timed region's (warm-up launches come first)
+wide = [e for e in sw if re.search(r"scan_mx_kernel<.*, 2>$", e[2])]  # the two-block form: launches of a long call
+if wide:
+    # the LAST long call (the timed one; the settling loop's 64-query calls keep one block): its run of wide sweeps --
+    # more than a millisecond apart is another call -- with the one-block sweeps of its first and last batches
+    run = [wide[-1]]
+    for e in reversed(wide[:-1]):
+        if run[0][0] - e[1] > 1000000:
+            break
+        run.insert(0, e)
+    sw = [e for e in sw if run[0][0] - 1000000 <= e[0] and e[1] <= run[-1][1] + 1000000]
+    print("the last long call: %d sweeps, %d of them of the two-block form" % (len(sw), len(run)))
+    wd = [(e - s_) / 1e3 for s_, e, _, _ in run]
+    print("two-block sweep us: median %.1f min %.1f max %.1f" % (statistics.median(wd), min(wd), max(wd)))
+else:
+    sw = sw[len(sw) // 4:]  # the timed region's (warm-up launches come first)
 durs = [(e - s) / 1e3 for s, e, _, _ in sw]
 print("sweep us: median %.1f min %.1f max %.1f" % (statistics.median(durs), min(durs), max(durs)))
 gaps = []

@@ -89,6 +89,9 @@ __host__ __device__ inline size_t query_lds_bytes(int qbits, int r16)
 }
 
 constexpr int kMaxSweepsPerLaunch = 16;
+// ... but for the matrix sweep's wide form (two column blocks of 16 queries per row read, kernels_scan_mx.hip): the
+// sketch pre-pass puts up to this many queries of a long call into one launch (option sketch_wide)
+constexpr int kMatrixWideQueries = 32;
 
 // Hit counters of the fused selection sit one per 128-byte line: the waves claim their slots
 // with returning atomics, mostly at the end of the sweep, and atomics on one line serialise
@@ -125,7 +128,8 @@ struct ScanArgs {
     uint32_t allow_stride;      // words between consecutive queries' allow masks
     // integer paths (4/8-bit rows): query ~ qscale * Q, qconst = sum Q, norm_bias turns
     // the row's integer sums into sum n^2 without the padding; qnorm2 = sum g^2 (euclid)
-    float qscale[kMaxSweepsPerLaunch], qconst[kMaxSweepsPerLaunch], qnorm2[kMaxSweepsPerLaunch];
+    // (sized for the matrix sweep's wide launch, kMatrixWideQueries; every other launch holds up to kMaxSweepsPerLaunch)
+    float qscale[kMatrixWideQueries], qconst[kMatrixWideQueries], qnorm2[kMatrixWideQueries];
     double norm_bias;
     int no_shape_kernels;       // tuning hook: always take the any-shape kernel
     int ring;                   // tuning hook: >= 8 forces the deep ring (0 = chosen from kp)
@@ -154,6 +158,9 @@ struct ScanArgs {
                                 // kMatrixMinQueries queries), 1 = never, 2 = wherever the shape allows, whatever the count
     int select;                 // option sketch_select: how the matrix sweep keeps its lists -- 0 = automatic (row lists
                                 // where kp <= kRowListMax), 1 = the serial inserts (one WaveList per query) everywhere
+    int wide;                   // option sketch_wide: 1 = a launch never takes the matrix sweep's two-block form; 0, 2 = a
+                                // launch of more than kMatrixQueries queries takes it where it qualifies (the host decides
+                                // which calls form such launches)
 };
 
 // Which scan_kernel instantiation a launch takes: decided on the host by scan_variant -- the launcher dispatches on
@@ -168,6 +175,7 @@ struct ScanVariant {
     int matrix_steps; // its form: 12 or 6 (64-byte steps per row fixed at compile time), 0 = the any-steps kernel
     int row_lists;    // the matrix sweep keeps its 16 lists as row lists (RowList, device_lists.h): kp <= kRowListMax
                       // under sketch_select = 0; else one WaveList per query and the serial inserts
+    int wide;         // the matrix sweep's two-block form: one pass per kMatrixWideQueries queries (row lists only)
 };
 // What "automatic" (scan_group = 0) asks for, where a launch qualifies.
 constexpr int kScanGroupAuto = 4;
@@ -184,14 +192,20 @@ constexpr bool sketch_matrix_known(int64_t v) { return v == 0 || v == 1 || v == 
 constexpr int kRowListMax = 16;
 constexpr bool sketch_select_known(int64_t v) { return v == 0 || v == 1; }
 constexpr bool matrix_row_lists(int kp, int select_opt) { return select_opt == 0 && kp >= 1 && kp <= kRowListMax; }
+// The wide form (option sketch_wide): a launch of more than kMatrixQueries and up to kMatrixWideQueries queries that the
+// matrix sweep serves with row lists scores two column blocks of 16 queries per row read, where the two-block image,
+// constants and lists fit 64 KiB of LDS (768 dimensions: lists of up to 15 entries; longer ones keep one block).
+// 0 = automatic and 2 = wherever the shape allows differ on the host only (which calls form launches of 32); 1 = never.
+constexpr bool sketch_wide_known(int64_t v) { return v == 0 || v == 1 || v == 2; }
 // group: the scan_group option (0 = automatic), n_queries: the launch's, block: its threads (the group's query images
 // -- of `planes` digit planes each -- and lists have to fit 64 KiB of LDS)
 // group_ring: the scan_group_ring option (0 = automatic)
 // matrix_opt: the sketch_matrix option (1 = off, what callers that do not know it get); norms: the launch has resident
-// row norms (ScanArgs::row_norm) -- the matrix sweep needs them; select_opt: the sketch_select option
+// row norms (ScanArgs::row_norm) -- the matrix sweep needs them; select_opt: the sketch_select option; wide_opt: the sketch_wide option (1 = never, what
+// callers that do not know it get)
 ScanVariant scan_variant(int qbits, const RowMap &m, bool tiled, int kp, bool collect, bool masked, int ring,
                          bool no_shape_kernels, int group = 1, int n_queries = 1, int block = 256, int planes = 3,
-                         int group_ring = 0, int matrix_opt = 1, bool norms = false, int select_opt = 0);
+                         int group_ring = 0, int matrix_opt = 1, bool norms = false, int select_opt = 0, int wide_opt = 1);
 // Ring depths of the G > 1 kernels.  A row-shape kernel of P pieces per lane exists at its shape's own depth (the
 // G = 1 kernel's) and, where kGroupRingAlt divides P and differs from it, at kGroupRingAlt as well: scan_group_ring
 // picks one of the two, 0 takes kGroupRingAuto where the shape has it and the shape's own depth elsewhere.
@@ -226,9 +240,9 @@ hipError_t launch_scan(int qbits, int metric, const ScanArgs &a, int grid, int b
                        hipStream_t stream);
 // LDS bytes launch_scan needs for (qbits, map, kp, block) at `group` queries per row read; planes = 2: the images of a
 // group (group > 1, 8-bit rows) hold two digit planes
-// matrix: the matrix sweep's -- kMatrixQueries two-plane images laid out for the matrix cores, their constants, and
-// kMatrixQueries x waves lists of kp entries
-size_t scan_lds_bytes(int qbits, const RowMap &m, int kp, int block, int group = 1, int planes = 3, bool matrix = false);
+// matrix: the matrix sweep's column blocks (1, or 2: the wide form; 0: not the matrix sweep) -- per block kMatrixQueries
+// two-plane images laid out for the matrix cores, their constants, and kMatrixQueries x waves lists of kp entries
+size_t scan_lds_bytes(int qbits, const RowMap &m, int kp, int block, int group = 1, int planes = 3, int matrix = 0);
 
 // Merge n_lists sorted lists of kp candidates into ceil(n_lists/merge_fan(kp)) lists.
 int merge_fan(int kp);

@@ -1329,8 +1329,11 @@ hipError_t launch_scan_qmcm(const ScanArgs &a, int grid, int block, hipStream_t 
 {
     const dim3 g(grid), b(block);
     const ScanVariant v = scan_variant(QBITS, a.map, a.tiled != 0, a.kp, COLLECT, MASKED, a.ring, a.no_shape_kernels != 0,
-                                       a.group, a.n_queries, block, a.planes, a.group_ring, a.matrix, a.row_norm != nullptr, a.select);
-    const size_t lds = scan_lds_bytes(QBITS, a.map, COLLECT ? 0 : a.kp, block, v.group, a.planes, v.matrix != 0);
+                                       a.group, a.n_queries, block, a.planes, a.group_ring, a.matrix, a.row_norm != nullptr, a.select,
+                                       a.wide);
+    const size_t lds = scan_lds_bytes(QBITS, a.map, COLLECT ? 0 : a.kp, block, v.group, a.planes, v.matrix ? (v.wide ? 2 : 1) : 0);
+    // (the per-query constants of every launch but the wide one are read up to kMaxSweepsPerLaunch queries)
+    if (!v.wide && a.n_queries > kMaxSweepsPerLaunch) return hipErrorInvalidValue;
     if constexpr (QBITS == 8 && !COLLECT && !MASKED) {
         // the matrix sweep: up to kMatrixQueries queries per row read on the matrix cores (kernels_scan_mx.hip)
         if (v.matrix) return METRIC == kCosine ? launch_scan_mx_m1(a, v, grid, block, lds, stream) : launch_scan_mx_m0(a, v, grid, block, lds, stream);
@@ -1405,7 +1408,7 @@ SZG_DECL_SCAN(64)
 // registers; everything else is the any-shape kernel, with the deep ring when the lists live in LDS (kp > 64).
 ScanVariant scan_variant(int qbits, const RowMap &m, bool tiled, int kp, bool collect, bool masked, int ring,
                          bool no_shape_kernels, int group, int n_queries, int block, int planes, int group_ring, int matrix_opt,
-                         bool norms, int select_opt)
+                         bool norms, int select_opt, int wide_opt)
 {
     ScanVariant v{};
     [[maybe_unused]] int shape_p = 0;  // pieces per lane of the row-shape kernel taken
@@ -1448,7 +1451,7 @@ ScanVariant scan_variant(int qbits, const RowMap &m, bool tiled, int kp, bool co
     // on (sketch_matrix = 2: from one); a lone query of an automatic launch keeps the G = 1 kernel.
     if (qbits == 8 && !collect && !masked && !v.deep && kp >= 1 && tiled && m.r16 > 0 && m.r16 % 4 == 0 && planes == 2 &&
         norms && group == 0 && matrix_opt != 1 && n_queries >= (matrix_opt == 2 ? 1 : kMatrixMinQueries) && block >= kWave &&
-        block <= 256 && block % kWave == 0 && scan_lds_bytes(qbits, m, kp, block, kMatrixQueries, planes, true) <= 64u * 1024u) {
+        block <= 256 && block % kWave == 0 && scan_lds_bytes(qbits, m, kp, block, kMatrixQueries, planes, 1) <= 64u * 1024u) {
         v.matrix = 1;
         v.matrix_steps = matrix_steps_form(m.r16 / 4);
         v.group = kMatrixQueries;
@@ -1456,14 +1459,24 @@ ScanVariant scan_variant(int qbits, const RowMap &m, bool tiled, int kp, bool co
         v.ring_depth = v.matrix_steps == 12 ? 6 : (v.matrix_steps == 6 ? 3 : 4);
         // its selection (option sketch_select): short lists as row lists, one candidate into each of the 16 per round
         v.row_lists = matrix_row_lists(kp, select_opt) ? 1 : 0;
+        // The wide form (option sketch_wide): a launch of 17 .. kMatrixWideQueries queries with row lists scores two
+        // column blocks per row read where both blocks' images, constants and lists fit 64 KiB of LDS; where they do
+        // not (768 dimensions with lists of 16), the launch keeps one block and walks its queries in groups of 16.
+        if (v.row_lists && wide_opt != 1 && n_queries > kMatrixQueries && n_queries <= kMatrixWideQueries &&
+            scan_lds_bytes(qbits, m, kp, block, kMatrixWideQueries, planes, 2) <= 64u * 1024u) {
+            v.wide = 1;
+            v.group = kMatrixWideQueries;
+        }
     }
     return v;
 }
 
-size_t scan_lds_bytes(int qbits, const RowMap &m, int kp, int block, int group, int planes, bool matrix)
+size_t scan_lds_bytes(int qbits, const RowMap &m, int kp, int block, int group, int planes, int matrix)
 {
-    if (matrix)  // 16 two-plane images (32 bytes per piece and query) | qscale, qconst, qnorm2 | 16 x waves lists
-        return (size_t)kMatrixQueries * ((size_t)m.r16 * 32 + 3 * sizeof(float) + (size_t)(block / kWave) * kp * sizeof(uint64_t));
+    // per column block: 16 two-plane images (32 bytes per piece and query) | qscale, qconst, qnorm2 | 16 x waves lists
+    if (matrix)
+        return (size_t)matrix * kMatrixQueries *
+               ((size_t)m.r16 * 32 + 3 * sizeof(float) + (size_t)(block / kWave) * kp * sizeof(uint64_t));
     // per query of a group: query image + per-wave candidate lists; per-wave lists of row steps that survive the masks
     // (the two-plane images exist in the G > 1 kernels only: a lone query stages the whole image, its h plane all zero)
     const size_t image = qbits == 8 && group > 1 && planes == 2 ? (size_t)m.r16 * 32 : query_lds_bytes(qbits, m.r16);
@@ -1474,14 +1487,14 @@ size_t scan_lds_bytes(int qbits, const RowMap &m, int kp, int block, int group, 
 int scan_group_of(int qbits, const ScanArgs &a, int block)
 {
     return scan_variant(qbits, a.map, a.tiled != 0, a.kp, a.collect != 0, scan_masked(a), a.ring, a.no_shape_kernels != 0,
-                        a.group, a.n_queries, block, a.planes, a.group_ring, a.matrix, a.row_norm != nullptr, a.select)
+                        a.group, a.n_queries, block, a.planes, a.group_ring, a.matrix, a.row_norm != nullptr, a.select, a.wide)
         .group;
 }
 
 bool scan_wants_norms(int qbits, const ScanArgs &a, int block)
 {
     return scan_variant(qbits, a.map, a.tiled != 0, a.kp, a.collect != 0, scan_masked(a), a.ring, a.no_shape_kernels != 0,
-                        a.group, a.n_queries, block, a.planes, a.group_ring, a.matrix, true, a.select)
+                        a.group, a.n_queries, block, a.planes, a.group_ring, a.matrix, true, a.select, a.wide)
                .group > 1;
 }
 

@@ -37,6 +37,9 @@
 //    few lanes pass in every tile, measure the same under both forms, so it has nothing to win.
 //  * serial inserts (16 < a.kp <= 64, or sketch_select = 1): per wave and query a WaveList of a.kp entries in
 //    registers (16 lists, one VGPR pair each), offered to query by query, one candidate at a time.
+// The row-list form also exists with TWO column blocks (NB = 2; DESIGN.md 4.5 item 10, option sketch_wide): a launch of
+// 17 .. 32 queries scores 32 per row read -- four matrix instructions per step on one load and one xor of the row
+// bytes, eight RowLists per lane-row -- where both blocks' images, constants and lists fit 64 KiB of LDS.
 // An insert is a set operation on unique entries: both forms leave the same lists bit for bit.  At the end of a group
 // the lists go to the same LDS slots and are merged per query into the block's sorted list: exactly the block's best
 // a.kp rows, as scan_kernel leaves them.
@@ -86,9 +89,19 @@ constexpr int mx_ring()
 // operands travel one phase ahead in a double buffer) or 0: any whole-step row, a rotating ring of 4.
 // ROWS: the wave's 16 lists are four RowLists (a.kp <= kRowListMax), else 16 WaveLists -- a template fact, so that the
 // tile loop of either form carries no trace of the other.
-template <int METRIC, int STEPS, bool NT, bool ROWS>
+// NB: column blocks of 16 queries scored per row read, 1 or 2 (the wide form, row lists only).
+// A group is 16 NB queries.  The image, the constants and the lists gain a block index; per 64-byte step the row bytes
+// are loaded and XORed once and feed 2 NB matrix instructions (planes m, l of each block, the same B operand), every
+// block with accumulators and double-buffered A operands of its own.  After a tile lane (c, t) holds the sums of
+// queries 16 b + 4 c + r against row t: lane-row c keeps 4 NB RowLists, slot 4 b + r the list of that query.  The
+// keys of a (query, row) pair are formed by the same operations as with one block: bit-identical.
+template <int METRIC, int STEPS, bool NT, bool ROWS, int NB = 1>
 __global__ __launch_bounds__(256, 2) void scan_mx_kernel(const ScanArgs a)
 {
+    static_assert(NB == 1 || (NB == 2 && ROWS), "two column blocks: row lists only");
+    static_assert(16 * NB <= kMatrixWideQueries, "the launch's constants are sized by kMatrixWideQueries");
+    constexpr int kQ = kMxQ * NB;  // queries of a group
+    constexpr int NS = 4 * NB;     // slots (queries) per lane
     static_assert(STEPS == 0 || (STEPS % 2 == 0 && STEPS % mx_ring<STEPS>() == 0), "even phases, ring divides the row");
     static_assert(STEPS <= 16, "the integer plane combine needs |128 M + L| < 2^31");
     extern __shared__ __align__(16) uint8_t smem[];
@@ -97,12 +110,12 @@ __global__ __launch_bounds__(256, 2) void scan_mx_kernel(const ScanArgs a)
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int nwaves = blockDim.x >> 6;
     const int steps = STEPS ? STEPS : (int)a.steps;
-    const int n16 = steps * 2 * 64;  // 16-byte words of a group's image: [step][plane m, l][chunk * 16 + query]
+    const int n16 = steps * 2 * 64;  // 16-byte words of a block's image: [step][plane m, l][chunk * 16 + query]
 
-    // LDS: the group's image | qscale, qconst, qnorm2 [16] | the wave lists [query of the group][wave][kp]
+    // LDS: the group's image [block] | qscale, qconst, qnorm2 [16 NB] | the wave lists [query of the group][wave][kp]
     uint4 *image = reinterpret_cast<uint4 *>(smem);
-    float *qtab = reinterpret_cast<float *>(smem + (size_t)n16 * 16);
-    uint64_t *lists = reinterpret_cast<uint64_t *>(smem + (size_t)n16 * 16 + 3 * kMxQ * sizeof(float));
+    float *qtab = reinterpret_cast<float *>(smem + (size_t)NB * n16 * 16);
+    uint64_t *lists = reinterpret_cast<uint64_t *>(smem + (size_t)NB * n16 * 16 + 3 * kQ * sizeof(float));
 
     const int trow = lane & 15;
     const int c = lane >> 4;
@@ -117,62 +130,63 @@ __global__ __launch_bounds__(256, 2) void scan_mx_kernel(const ScanArgs a)
         return a.rows + piece_offset(lay, min(tile * 16 + trow, last_row), (uint32_t)c);
     };
 
-    for (int qi = 0; qi < a.n_queries; qi += kMxQ) {
+    for (int qi = 0; qi < a.n_queries; qi += kQ) {
         if (qi) __syncthreads();  // the previous group's lists have been merged, its image is free
         // column x of the group holds query min(qi + x, n_queries - 1): the idle columns of the launch's last group score
         // its last query again, offer nothing and write no lists
-        for (int i = tid; i < n16; i += blockDim.x) {
+        for (int i0 = tid; i0 < NB * n16; i0 += blockDim.x) {
+            const int blk = NB == 1 ? 0 : (i0 >= n16 ? 1 : 0), i = i0 - blk * n16;
             const int x = i & 15, chunk = (i >> 4) & 3, p = (i >> 6) & 1, st = i >> 7;
-            const int q = min(qi + x, a.n_queries - 1);
+            const int q = min(qi + blk * kMxQ + x, a.n_queries - 1);
             // (the staged query is [plane h, m, l][piece]: the all-zero h plane stays behind)
             const uint4 *src = reinterpret_cast<const uint4 *>(reinterpret_cast<const uint8_t *>(a.query) +
                                                                (size_t)q * a.query_stride) +
                                (size_t)(1 + p) * a.map.r16 + (st * 4 + chunk);
-            image[i] = *src;
+            image[i0] = *src;
         }
 #pragma unroll
-        for (int x = 0; x < kMxQ; x++) {
+        for (int x = 0; x < kQ; x++) {
             const int q = min(qi + x, a.n_queries - 1);  // (block-uniform: scalar loads of the arguments)
             const float qs = a.qscale[q], qc = a.qconst[q], qn = a.qnorm2[q];
             if (tid == x) {
                 qtab[x] = qs;
-                qtab[kMxQ + x] = qc;
-                qtab[2 * kMxQ + x] = qn;
+                qtab[kQ + x] = qc;
+                qtab[2 * kQ + x] = qn;
             }
         }
-        // ROWS: slot r of lane-row c is the list of query 4 c + r; else one whole-wave list per query (the unused form
-        // is dead code: no registers)
-        RowList rls[4];
+        // ROWS: slot 4 b + r of lane-row c is the list of query 16 b + 4 c + r; else one whole-wave list per query (the
+        // unused form is dead code: no registers)
+        RowList rls[NS];
         WaveList wls[kMxQ];
         if constexpr (ROWS) {
 #pragma unroll
-            for (int r = 0; r < 4; r++) rls[r].init();
+            for (int r = 0; r < NS; r++) rls[r].init();
         } else {
 #pragma unroll
             for (int x = 0; x < kMxQ; x++) wls[x].init(lists, a.kp, lane);  // (register lists: flushed by hand below)
         }
-        float wk[4];  // worst_key of this lane's four queries (+inf while a list fills)
-        bool live[4];
+        float wk[NS];  // worst_key of this lane's queries (+inf while a list fills)
+        bool live[NS];
 #pragma unroll
-        for (int r = 0; r < 4; r++) {
+        for (int r = 0; r < NS; r++) {
             wk[r] = __builtin_inff();
-            live[r] = qi + c * 4 + r < a.n_queries;
+            live[r] = qi + (r >> 2) * kMxQ + c * 4 + (r & 3) < a.n_queries;
         }
-        float qsv[4], qcv[4], qnv[4];
+        float qsv[NS], qcv[NS], qnv[NS];
 
-        // ---- the tile is done: keys of 4 queries x 1 row per lane, one compare each, one ballot for the tile
-        auto finish_tile = [&](uint64_t tile, const v4i32 &accM, const v4i32 &accL, float norm) {
+        // ---- the tile is done: keys of 4 NB queries x 1 row per lane, one compare each, one ballot for the tile
+        auto finish_tile = [&](uint64_t tile, const v4i32 (&accM)[NB], const v4i32 (&accL)[NB], float norm) {
             const uint64_t row = tile * 16 + trow;
             const bool row_ok = row < a.n_rows;
-            float key[4];
-            bool pass[4];
+            float key[NS];
+            bool pass[NS];
             bool any = false;
             [[maybe_unused]] const float inv = __frsqrt_rn(norm);
 #pragma unroll
-            for (int r = 0; r < 4; r++) {
+            for (int r = 0; r < NS; r++) {
                 float dot;
-                if constexpr (STEPS != 0) dot = (float)(accM[r] * 128 + accL[r]);
-                else dot = fmaf(128.0f, (float)accM[r], (float)accL[r]);
+                if constexpr (STEPS != 0) dot = (float)(accM[r >> 2][r & 3] * 128 + accL[r >> 2][r & 3]);
+                else dot = fmaf(128.0f, (float)accM[r >> 2][r & 3], (float)accL[r >> 2][r & 3]);
                 const float d2 = fmaf(2.0f, dot, qcv[r]);  // sum Q n
                 float k_;
                 if constexpr (METRIC == kCosine) k_ = -(d2 * qsv[r]) * inv;
@@ -185,28 +199,31 @@ __global__ __launch_bounds__(256, 2) void scan_mx_kernel(const ScanArgs a)
             if (!__ballot(any)) return;
             if constexpr (ROWS) {
                 // Rounds: the 16 rows offered to query 4 c + r sit in the 16 lanes of lane-row c, so one round retires
-                // one passing lane of every lane-row and slot -- up to 16 inserts, four independent chains (the slots).
+                // one passing lane of every lane-row and slot -- up to 16 NB inserts, 4 NB independent chains (the slots).
                 // A round retires a lane of every lane-row that still has one: 16 rounds always suffice, and the bound
                 // stands in the loop itself.
-                uint32_t uk[4];
+                uint32_t uk[NS];
 #pragma unroll
-                for (int r = 0; r < 4; r++) uk[r] = ordered_key(key[r]);
+                for (int r = 0; r < NS; r++) uk[r] = ordered_key(key[r]);
                 const uint32_t row0 = (uint32_t)(tile * 16);
                 for (int round = 0; round < 16; round++) {
-                    uint64_t act[4];
+                    uint64_t act[NS];
+                    uint64_t act_any = 0;
 #pragma unroll
-                    for (int r = 0; r < 4; r++)
+                    for (int r = 0; r < NS; r++) {
                         act[r] = __ballot(pass[r] && (((uint64_t)uk[r] << 32) | (uint32_t)row) < rls[r].worst);
-                    if (!(act[0] | act[1] | act[2] | act[3])) break;
+                        act_any |= act[r];
+                    }
+                    if (!act_any) break;
 #pragma unroll
-                    for (int r = 0; r < 4; r++) {
+                    for (int r = 0; r < NS; r++) {
                         // (wave-uniform: late tiles have a few passing lanes, in one or two of the slots)
                         if (SZG_MX_ROUND_SKIP && !act[r]) continue;
                         rls[r].round(act[r], pass[r], uk[r], row0, lane, a.kp);
                     }
                 }
 #pragma unroll
-                for (int r = 0; r < 4; r++) wk[r] = rls[r].worst_key();
+                for (int r = 0; r < NS; r++) wk[r] = rls[r].worst_key();
             } else {
 #pragma unroll
                 for (int x = 0; x < kMxQ; x++) {
@@ -220,10 +237,11 @@ __global__ __launch_bounds__(256, 2) void scan_mx_kernel(const ScanArgs a)
         };
         auto read_consts = [&]() {
 #pragma unroll
-            for (int r = 0; r < 4; r++) {
-                qsv[r] = qtab[c * 4 + r];
-                qcv[r] = qtab[kMxQ + c * 4 + r];
-                qnv[r] = qtab[2 * kMxQ + c * 4 + r];
+            for (int r = 0; r < NS; r++) {
+                const int x = (r >> 2) * kMxQ + c * 4 + (r & 3);  // this slot's column of the group
+                qsv[r] = qtab[x];
+                qcv[r] = qtab[kQ + x];
+                qnv[r] = qtab[2 * kQ + x];
             }
         };
         const v4i32 *qimg = reinterpret_cast<const v4i32 *>(smem) + lane;
@@ -231,7 +249,9 @@ __global__ __launch_bounds__(256, 2) void scan_mx_kernel(const ScanArgs a)
         if constexpr (STEPS != 0) {
             constexpr int D = mx_ring<STEPS>();
             u32x4 ring[D];
-            v4i32 acc[2] = {v4i32{0, 0, 0, 0}, v4i32{0, 0, 0, 0}};
+            v4i32 accM[NB], accL[NB];
+#pragma unroll
+            for (int b = 0; b < NB; b++) accM[b] = accL[b] = v4i32{0, 0, 0, 0};
             uint64_t tile = tile_first;
             const uint8_t *cur = row_ptr(tile);
             // the ring's first D steps (D <= STEPS: all inside the first tile); the rows do not depend on the image
@@ -243,10 +263,13 @@ __global__ __launch_bounds__(256, 2) void scan_mx_kernel(const ScanArgs a)
             __syncthreads();  // the image and the constants are complete
             read_consts();
             // the A operands travel one phase (step) ahead of the matrix instructions that use them, in a double buffer
-            v4i32 qbuf[2][2];
-            auto read_phase = [&](int st_, v4i32 (&dst)[2]) {
-                dst[0] = qimg[(st_ * 2 + 0) * 64];
-                dst[1] = qimg[(st_ * 2 + 1) * 64];
+            v4i32 qbuf[2][NB][2];
+            auto read_phase = [&](int st_, v4i32 (&dst)[NB][2]) {
+#pragma unroll
+                for (int b = 0; b < NB; b++) {
+                    dst[b][0] = qimg[((b * STEPS + st_) * 2 + 0) * 64];
+                    dst[b][1] = qimg[((b * STEPS + st_) * 2 + 1) * 64];
+                }
             };
             read_phase(0, qbuf[0]);
             for (uint64_t it = 0; it < n_it; it++, tile += tile_stride) {
@@ -268,16 +291,21 @@ __global__ __launch_bounds__(256, 2) void scan_mx_kernel(const ScanArgs a)
                     read_phase((st + 1) % STEPS, qbuf[(st + 1) & 1]);
                     __builtin_amdgcn_sched_barrier(0);
                     // (the tile's first matrix instructions start from a literal zero: no accumulator clearing per tile)
-                    acc[0] = __builtin_amdgcn_mfma_i32_16x16x64_i8(qbuf[st & 1][0], bop, st == 0 ? v4i32{0, 0, 0, 0} : acc[0], 0, 0, 0);
-                    acc[1] = __builtin_amdgcn_mfma_i32_16x16x64_i8(qbuf[st & 1][1], bop, st == 0 ? v4i32{0, 0, 0, 0} : acc[1], 0, 0, 0);
+#pragma unroll
+                    for (int b = 0; b < NB; b++) {
+                        accM[b] = __builtin_amdgcn_mfma_i32_16x16x64_i8(qbuf[st & 1][b][0], bop, st == 0 ? v4i32{0, 0, 0, 0} : accM[b], 0, 0, 0);
+                        accL[b] = __builtin_amdgcn_mfma_i32_16x16x64_i8(qbuf[st & 1][b][1], bop, st == 0 ? v4i32{0, 0, 0, 0} : accL[b], 0, 0, 0);
+                    }
                 }
-                finish_tile(tile, acc[0], acc[1], norm);
+                finish_tile(tile, accM, accL, norm);
                 cur = nxt;
             }
         } else {
             constexpr int D = 4;
             u32x4 ring[D];
-            v4i32 accM = v4i32{0, 0, 0, 0}, accL = v4i32{0, 0, 0, 0};
+            v4i32 accM[NB], accL[NB];
+#pragma unroll
+            for (int b = 0; b < NB; b++) accM[b] = accL[b] = v4i32{0, 0, 0, 0};
             const uint64_t NP = n_it * (uint64_t)steps;  // 64-byte steps of this wave's tiles, walked as one stream
             uint64_t itile = tile_first, ctile = tile_first;
             int is = 0, cs = 0;
@@ -303,13 +331,16 @@ __global__ __launch_bounds__(256, 2) void scan_mx_kernel(const ScanArgs a)
         bop_[1] = (int)(v_.y ^ 0x80808080u);                                             \
         bop_[2] = (int)(v_.z ^ 0x80808080u);                                             \
         bop_[3] = (int)(v_.w ^ 0x80808080u);                                             \
-        const v4i32 am_ = qimg[(cs * 2 + 0) * 64], al_ = qimg[(cs * 2 + 1) * 64];        \
-        accM = __builtin_amdgcn_mfma_i32_16x16x64_i8(am_, bop_, accM, 0, 0, 0);          \
-        accL = __builtin_amdgcn_mfma_i32_16x16x64_i8(al_, bop_, accL, 0, 0, 0);          \
+        _Pragma("unroll") for (int b_ = 0; b_ < NB; b_++) {                             \
+            const v4i32 am_ = qimg[((b_ * steps + cs) * 2 + 0) * 64];                    \
+            const v4i32 al_ = qimg[((b_ * steps + cs) * 2 + 1) * 64];                    \
+            accM[b_] = __builtin_amdgcn_mfma_i32_16x16x64_i8(am_, bop_, accM[b_], 0, 0, 0); \
+            accL[b_] = __builtin_amdgcn_mfma_i32_16x16x64_i8(al_, bop_, accL[b_], 0, 0, 0); \
+        }                                                                                \
         if (++cs == steps) {                                                             \
             finish_tile(ctile, accM, accL, norm);                                        \
-            accM = v4i32{0, 0, 0, 0};                                                    \
-            accL = v4i32{0, 0, 0, 0};                                                    \
+            _Pragma("unroll") for (int b_ = 0; b_ < NB; b_++)                            \
+                accM[b_] = accL[b_] = v4i32{0, 0, 0, 0};                                 \
             cs = 0;                                                                      \
             ctile += tile_stride;                                                        \
         }                                                                                \
@@ -352,15 +383,16 @@ __global__ __launch_bounds__(256, 2) void scan_mx_kernel(const ScanArgs a)
         // block-wide k-select over the waves' lists, query by query
         if constexpr (ROWS) {
 #pragma unroll
-            for (int r = 0; r < 4; r++)
-                if (trow < a.kp) lists[((size_t)(c * 4 + r) * nwaves + wave) * a.kp + trow] = rls[r].mine;
+            for (int r = 0; r < NS; r++)
+                if (trow < a.kp)
+                    lists[((size_t)((r >> 2) * kMxQ + c * 4 + (r & 3)) * nwaves + wave) * a.kp + trow] = rls[r].mine;
         } else {
 #pragma unroll
             for (int x = 0; x < kMxQ; x++)
                 if (lane < a.kp) lists[((size_t)x * nwaves + wave) * a.kp + lane] = wls[x].mine;
         }
         __syncthreads();
-        for (int x = 0; x < kMxQ && qi + x < a.n_queries; x++)  // (block-uniform)
+        for (int x = 0; x < kQ && qi + x < a.n_queries; x++)  // (block-uniform)
             block_merge_lists(lists + (size_t)x * nwaves * a.kp, nwaves, a.kp,
                               a.block_lists + ((size_t)(qi + x) * gridDim.x + blockIdx.x) * a.kp, tid, blockDim.x);
         // loads and stores share one vmcnt on gfx9: drain the list stores once per group, so that the next group's ring
@@ -370,9 +402,10 @@ __global__ __launch_bounds__(256, 2) void scan_mx_kernel(const ScanArgs a)
 }
 
 template <int STEPS>
-hipError_t launch_mx_steps(const ScanArgs &a, bool rows, int grid, int block, size_t lds, hipStream_t stream)
+hipError_t launch_mx_steps(const ScanArgs &a, bool rows, bool wide, int grid, int block, size_t lds, hipStream_t stream)
 {
-    if (rows) hipLaunchKernelGGL((scan_mx_kernel<SZG_SCAN_METRIC, STEPS, true, true>), dim3(grid), dim3(block), lds, stream, a);
+    if (wide) hipLaunchKernelGGL((scan_mx_kernel<SZG_SCAN_METRIC, STEPS, true, true, 2>), dim3(grid), dim3(block), lds, stream, a);
+    else if (rows) hipLaunchKernelGGL((scan_mx_kernel<SZG_SCAN_METRIC, STEPS, true, true>), dim3(grid), dim3(block), lds, stream, a);
     else hipLaunchKernelGGL((scan_mx_kernel<SZG_SCAN_METRIC, STEPS, true, false>), dim3(grid), dim3(block), lds, stream, a);
     return hipGetLastError();
 }
@@ -394,10 +427,17 @@ hipError_t SZG_CAT(launch_scan_mx_m, SZG_SCAN_METRIC)(const ScanArgs &a, const S
     // (row lists hold at most kRowListMax entries: a longer list must never reach that form)
     if ((v.row_lists != 0) != matrix_row_lists(a.kp, a.select)) return hipErrorInvalidValue;
     const bool rows = v.row_lists != 0;
+    // the wide form: row lists, a launch of 17 .. kMatrixWideQueries queries (the constants' arrays hold that many),
+    // option sketch_wide not 1, and exactly the two-block LDS; every other launch holds at most kMaxSweepsPerLaunch
+    const bool wide = v.wide != 0;
+    if (wide && (!rows || a.wide == 1 || a.n_queries <= kMatrixQueries || a.n_queries > kMatrixWideQueries ||
+                 lds != scan_lds_bytes(8, a.map, a.kp, block, kMatrixWideQueries, a.planes, 2)))
+        return hipErrorInvalidValue;
+    if (!wide && a.n_queries > kMaxSweepsPerLaunch) return hipErrorInvalidValue;
     switch (v.matrix_steps) {
-    case 12: return launch_mx_steps<12>(a, rows, grid, block, lds, stream);
-    case 6: return launch_mx_steps<6>(a, rows, grid, block, lds, stream);
-    default: return launch_mx_steps<0>(a, rows, grid, block, lds, stream);
+    case 12: return launch_mx_steps<12>(a, rows, wide, grid, block, lds, stream);
+    case 6: return launch_mx_steps<6>(a, rows, wide, grid, block, lds, stream);
+    default: return launch_mx_steps<0>(a, rows, wide, grid, block, lds, stream);
     }
 }
 

@@ -678,6 +678,48 @@ int szg_debug_scan_select(int dim, int quant_bits, int n_queries, int kp, int pl
     return SZG_OK;
 }
 
+// test hook, host only: the matrix sweep's two-block form (option sketch_wide) for a one-sweep top-k call of n_queries
+// queries split as a call with wide batches splits it -- launches of up to 32 where a launch of 32 qualifies for the
+// form, of up to 16 where it does not.  *serves / *lds_bytes describe the first launch (scan_variant's answer),
+// *passes = passes over the rows of the whole call.
+int szg_debug_scan_wide(int dim, int quant_bits, int n_queries, int kp, int planes, int norms, int tiled, int masked,
+                        int scan_group, int sketch_matrix, int sketch_select, int sketch_wide, int32_t *serves,
+                        int32_t *passes, uint64_t *lds_bytes)
+{
+    if (!serves || !passes || !lds_bytes) return fail(SZG_E_INVALID, "null argument");
+    if (kp < 0 || n_queries < 1) return fail(SZG_E_INVALID, "kp or n_queries out of range");
+    if (planes != 2 && planes != 3) return fail(SZG_E_INVALID, "planes is 2 or 3");
+    if (scan_group != 0 && scan_group != 1 && scan_group != 2 && scan_group != 4)
+        return fail(SZG_E_INVALID, "scan_group is 0, 1, 2 or 4");
+    if (!szg::sketch_matrix_known(sketch_matrix)) return fail(SZG_E_INVALID, "sketch_matrix is 0, 1 or 2");
+    if (!szg::sketch_select_known(sketch_select)) return fail(SZG_E_INVALID, "sketch_select is 0 or 1");
+    if (!szg::sketch_wide_known(sketch_wide)) return fail(SZG_E_INVALID, "sketch_wide is 0, 1 or 2");
+    RowFormat f;
+    const int rc = row_format(dim, quant_bits, &f);
+    if (rc == SZG_E_UNSUPPORTED) return fail(rc, "dimension too large for the LDS-resident query");
+    if (rc) return rc;
+    const bool is_tiled = f.layout.tiled != 0 && tiled != 0;
+    const LaunchGeom g = scan_geometry(quant_bits, f.map, f.row_bytes, f.layout.tiled != 0, 1u << 22, 256, kp);
+    auto variant = [&](int n) {
+        return szg::scan_variant(quant_bits, f.map, is_tiled, kp, false, masked != 0, szg_index::ring, !szg_index::shape_kernels,
+                                 scan_group, n, g.block, planes, 0, sketch_matrix, norms != 0, sketch_select, sketch_wide);
+    };
+    const int per_launch = variant(szg::kMatrixWideQueries).wide ? szg::kMatrixWideQueries : szg::kMaxSweepsPerLaunch;
+    *serves = 0;
+    *passes = 0;
+    *lds_bytes = 0;
+    for (int j = 0; j < n_queries; j += per_launch) {
+        const int n = std::min(per_launch, n_queries - j);
+        const szg::ScanVariant v = variant(n);
+        if (j == 0) {
+            *serves = v.wide;
+            *lds_bytes = szg::scan_lds_bytes(quant_bits, f.map, kp, g.block, v.group, planes, v.matrix ? (v.wide ? 2 : 1) : 0);
+        }
+        *passes += (n + v.group - 1) / v.group;
+    }
+    return SZG_OK;
+}
+
 // test hook, host only: does the one-launch short-list merge serve (n_lists, m, kp), and how many entries under its
 // threshold its selection sorts at most (more: the tournament; fewer than kp: the tournament always)
 int szg_debug_merge_short_plan(int n_lists, int m, int kp, int32_t *fits, int32_t *sorts)

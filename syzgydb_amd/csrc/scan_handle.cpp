@@ -669,6 +669,7 @@ static const char *scan_option_refusal(const std::string &n, int64_t value, bool
     if (n == "sketch_planes") return value == 0 || value == 2 || value == 3 ? nullptr : "sketch_planes is 0, 2 or 3";
     if (n == "sketch_matrix") return szg::sketch_matrix_known(value) ? nullptr : "sketch_matrix is 0, 1 or 2";
     if (n == "sketch_select") return szg::sketch_select_known(value) ? nullptr : "sketch_select is 0 or 1";
+    if (n == "sketch_wide") return szg::sketch_wide_known(value) ? nullptr : "sketch_wide is 0, 1 or 2";
     *known = false;
     return nullptr;
 }
@@ -739,6 +740,8 @@ int szg_set_option(szg_index *ix, const char *name, int64_t value)
         ix->sketch_matrix = (int)value;
     } else if (n == "sketch_select") {
         ix->sketch_select = (int)value;
+    } else if (n == "sketch_wide") {
+        ix->sketch_wide = (int)value;
     } else if (n == "query_batch") {
         if (value < 1 || value > kMaxBatch) return fail(SZG_E_INVALID, "query_batch out of range");
         ix->query_batch = (int)value;

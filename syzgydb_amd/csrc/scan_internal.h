@@ -436,6 +436,9 @@ struct szg_index {
                               // szg::kMatrixMinQueries queries or more), 1 = never, 2 = every such launch
     int sketch_select = 0;    // the matrix sweep's selection: 0 = automatic (row lists where the lists hold at most
                               // szg::kRowListMax entries), 1 = the serial inserts everywhere
+    int sketch_wide = 0;      // the matrix sweep's two-block form (32 queries per row read): 0 = automatic (calls of
+                              // kWideCallMin one-sweep queries on, under the default query_batch and queries_per_launch),
+                              // 1 = never, 2 = every call of more than 16 queries where the shape allows
     bool is_sketch = false;   // this index is the internal sketch of a float32 handle: its keys only bound
     int tie_mode = 0;         // 0: exact full replay on ties/NaN, 1: keep the fast answer
     int serialize_scans = 1;  // scan launches of a shard never overlap each other
@@ -640,7 +643,14 @@ struct RerankOn {
     const Shard *sh;
     int extra;  // entries behind each list: the drop bound's slot, then the staged rows
     int list;   // option sketch_list: the sweep's per-wave / per-block list length (0 = automatic, >= kp = kp)
+    bool wide;  // the call takes wide batches: launches hold up to szg::kMatrixWideQueries queries where the matrix
+                // sweep's two-block form serves them (sketch_wide_serves), up to queries_per_launch elsewhere
 };
+// entries per wave and block list of a sketch sweep over `grid` blocks (option sketch_list)
+int sketch_list_len(int want, int kp, int grid);
+// does the matrix sweep's two-block form serve an unmasked launch of szg::kMatrixWideQueries queries of sketch index
+// `sk` on shard `sh`, for calls that keep kp candidates per query (scan_variant's answer for that launch)?
+bool sketch_wide_serves(const szg_index *sk, const Shard *sh, int kp, int list_opt);
 int enqueue_topk(szg_index *ix, Shard *sh, Ctx *c, int kp, int nq, bool has_allow, const RerankOn *on = nullptr);
 // candidates of staged query `slot` from a finished top-k pass and *lb, the lower bound of the real-number key of every
 // eligible row of the shard that is not among them
@@ -820,6 +830,10 @@ struct CtxGuard {  // returns a borrowed context on every exit path
 
 constexpr int kFirstBatch = 4;  // queries of a call's first (and last) one-sweep batch: the card starts sweeping sooner
 constexpr int kShortCall = 32;  // calls of up to this many one-sweep queries are ONE batch on the scan stream
+// Wide batches of the sketch pre-pass (option sketch_wide = 0): a call takes batches of szg::kMatrixWideQueries queries,
+// one launch each, from two of them between its first and last batch of kFirstBatch on -- below that a pipeline of
+// 32-query batches has nothing to overlap with
+constexpr int kWideCallMin = 2 * szg::kMatrixWideQueries + 2 * kFirstBatch;
 
 // the filter masks of a call's queries: one pointer per query (null = unfiltered), or masks back to back with one
 // bit per row of the index, or resident masks (one handle per query, null = unfiltered), or none.  operator() gives
@@ -924,5 +938,82 @@ int run_batches(Call &call, const std::function<bool(B &&)> &hand_over = nullptr
     }
     return rc;
 }
+
+// The second host thread of a long call: it takes the staged batches in order and finishes them -- waits, candidate
+// assembly, certification, output, release of the contexts -- while the calling thread prepares and enqueues.  The
+// hand-over is the batch queue; contexts are the flow control (acquire blocks until the finisher has released one).
+template <class B>
+struct Finisher {
+    std::mutex mu;
+    std::condition_variable cv;
+    std::deque<B> q;
+    bool done = false;
+    int rc = SZG_OK;
+    std::string err;
+    std::atomic<bool> failed{false};
+    std::thread th;
+    // start the thread; finish(B &) settles one batch.  false: no thread to be had, the caller does both
+    bool start(std::function<int(B &)> finish)
+    {
+        try {
+            th = std::thread([this, finish] {
+                for (;;) {
+                    std::unique_lock<std::mutex> lk(mu);
+                    cv.wait(lk, [&] { return !q.empty() || done; });
+                    if (q.empty()) return;
+                    B t(std::move(q.front()));
+                    q.pop_front();
+                    lk.unlock();
+                    int r;
+                    try {
+                        r = finish(t);
+                    } catch (const std::bad_alloc &) {
+                        r = fail(SZG_E_NOMEM, "out of host memory");
+                    } catch (...) {
+                        r = fail(SZG_E_DEVICE, "unexpected exception");
+                    }
+                    if (r != SZG_OK && !failed.load()) {  // (every batch is still finished: its contexts go back)
+                        rc = r;
+                        err = szg_last_error();
+                        failed.store(true);
+                    }
+                }
+            });
+        } catch (...) {
+            return false;
+        }
+        return true;
+    }
+    // run_batches' hand_over
+    std::function<bool(B &&)> hand_over()
+    {
+        return [this](B &&t) {
+            {
+                std::lock_guard<std::mutex> lk(mu);
+                q.push_back(std::move(t));
+            }
+            cv.notify_one();
+            return !failed.load();
+        };
+    }
+    void stop()
+    {
+        if (!th.joinable()) return;
+        {
+            std::lock_guard<std::mutex> lk(mu);
+            done = true;
+        }
+        cv.notify_one();
+        th.join();
+    }
+    // join, and the call's result: the caller's own rc, else the finisher's first failure (in this thread's last-error slot)
+    int join(int rc_caller)
+    {
+        stop();
+        if (rc_caller == SZG_OK && failed.load()) return fail(rc, err.c_str());
+        return rc_caller;
+    }
+    ~Finisher() { stop(); }  // (an exception unwinding the call: the queued batches are still finished first)
+};
 
 }  // namespace szgi

@@ -299,6 +299,8 @@ struct SketchCall {
     std::vector<HeapItem> res;
     std::vector<double> dd;
     bool tracing = false;  // the float32 handle's certificate trace is on
+    int wide = 0;          // the call takes wide batches (32 queries, one launch of the two-block matrix sweep each):
+                           // 1 = under the automatic rule, 2 = forced (option sketch_wide = 2)
 
     int run();
     Batch plan(int q0);
@@ -331,14 +333,43 @@ int SketchCall::run()
     redo.reserve(n_queries);
     cands.reserve((size_t)n_sh * kp + ix->sk_exc.size() + (size_t)k);
     dd.reserve(cands.capacity());
-    return run_batches<Batch>(*this);
+    // Wide batches (option sketch_wide, read from the sketch index): only where every shard's launch of 32 qualifies
+    // for the two-block matrix sweep.  Automatic: long calls under the default batch and launch sizes; 2: every call
+    // of more than 16 queries.
+    wide = 0;
+    if (sk->sketch_wide != 1 && n_queries > szg::kMatrixQueries) {
+        bool serves = true, any = false;
+        for (size_t s = 0; s < n_sh && serves; s++) {
+            if (sk->shards[s]->n_rows == 0) continue;
+            any = true;
+            serves = sketch_wide_serves(sk, sk->shards[s], kp, ix->sketch_list);
+        }
+        if (serves && any) {
+            if (sk->sketch_wide == 2) wide = 2;
+            else if (n_queries >= kWideCallMin && ix->query_batch == 16 && sk->queries_per_launch == 16) wide = 1;
+        }
+    }
+    // A wide call's device step (7.6-8 us per query at 1M x 768) is close above the host's 7.3 us per query on one
+    // thread: a second thread settles the finished batches (option finish_thread), as in long shared-sweep calls, and
+    // leaves the caller 4-4.5 us.
+    Finisher<Batch> fin;
+    bool threaded = wide != 0 && ix->finish_thread && n_queries > 2 * szg::kMatrixWideQueries;
+    if (threaded) threaded = fin.start([this](Batch &b) { return finish(b); });
+    int rc = run_batches<Batch>(*this, threaded ? fin.hand_over() : nullptr);
+    if (threaded) rc = fin.join(rc);
+    return rc;
 }
 
 Batch SketchCall::plan(int q0)
 {
     Batch b;
     const int batch = std::max(1, std::min(ix->query_batch, kMaxBatch));
-    plan_batch(sk, n_queries, q0, 0, BatchRules{batch, kFirstBatch, std::min(kShortCall, kMaxBatch), true, false}, &b);
+    if (wide == 2)  // forced: batches of up to 32 from the call's first query on, no small edges, no early tail
+        plan_batch(sk, n_queries, q0, 0, BatchRules{szg::kMatrixWideQueries, n_queries, szg::kMatrixWideQueries, false, false}, &b);
+    else if (wide)  // (the call is longer than kShortCall: first and last batch of kFirstBatch, 32 between them)
+        plan_batch(sk, n_queries, q0, 0, BatchRules{szg::kMatrixWideQueries, kFirstBatch, std::min(kShortCall, kMaxBatch), true, false}, &b);
+    else
+        plan_batch(sk, n_queries, q0, 0, BatchRules{batch, kFirstBatch, std::min(kShortCall, kMaxBatch), true, false}, &b);
     return b;
 }
 
@@ -400,7 +431,7 @@ int SketchCall::stage(Batch &b)
         // (the float64 queries unscaled: the rerank is on the rows; a resident mask's shard words serve the sketch
         // shard too: same rows, same device)
         rc = enqueue_queries(sk, h, c, q, b.nq, mptr, true, handles.empty() ? nullptr : handles.data(), s);
-        const RerankOn on{ix, ix->shards[s], extra[s], ix->sketch_list};
+        const RerankOn on{ix, ix->shards[s], extra[s], ix->sketch_list, wide != 0};
         if (rc == SZG_OK) rc = enqueue_topk(sk, h, c, kp, b.nq, b.any_mask, &on);
     }
     note_stage_times(ix, t_prep0, t_enq0);

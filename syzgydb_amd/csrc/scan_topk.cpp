@@ -130,7 +130,7 @@ void fill_scan_args(const szg_index *ix, const Shard *sh, const Ctx *c, bool has
     a->query_stride = (uint32_t)ix->qsw_bytes;
     a->query = c->d_qsw + (size_t)slot * ix->qsw_bytes;
     a->n_queries = nq;
-    for (int j = 0; j < nq && j < szg::kMaxSweepsPerLaunch; j++) {
+    for (int j = 0; j < nq && j < szg::kMatrixWideQueries; j++) {
         a->qscale[j] = (float)c->meta[slot + j].qscale;
         a->qconst[j] = (float)c->meta[slot + j].qconst;
         a->qnorm2[j] = (float)c->meta[slot + j].qnorm2;
@@ -143,6 +143,7 @@ void fill_scan_args(const szg_index *ix, const Shard *sh, const Ctx *c, bool has
     a->planes = scan_planes(ix);  // (as prep_query quantized the staged queries)
     a->matrix = ix->sketch_matrix;
     a->select = ix->sketch_select;
+    a->wide = ix->sketch_wide;
 }
 
 // Launch the fused scan for each of the batch's queries (n = a->size()) as the
@@ -188,11 +189,22 @@ double mask_pass_rate(const Shard *sh, const Ctx *c, bool has_allow, int slot)
 // fall about kp / grid to a block; automatic lists hold twice that plus 8 (8 at 512 blocks), so a block rarely has
 // more of them than its list keeps -- and when it has, the drop bound says so and the query falls back.  m >= kp (or
 // lists the one-launch merge cannot hold): the full lists and the two-level merge.
-static int sketch_list_len(int want, int kp, int grid)
+int sketch_list_len(int want, int kp, int grid)
 {
     const int m = want > 0 ? want : std::max(8, 2 * kp / std::max(grid, 1) + 8);
     if (m >= kp || !szg::merge_short_fits(grid, m, kp)) return kp;
     return m;
+}
+
+bool sketch_wide_serves(const szg_index *sk, const Shard *sh, int kp, int list_opt)
+{
+    if (sk->sketch_wide == 1 || sh->has_dead || kp > 64) return false;
+    const LaunchGeom g = scan_geometry(sk, sh, kp, true);
+    const int m = sketch_list_len(list_opt, kp, g.grid);
+    return szg::scan_variant(sk->bits, sk->map, sk->layout.tiled != 0, m, false, false, sk->ring, !sk->shape_kernels,
+                             sk->scan_group, szg::kMatrixWideQueries, g.block, scan_planes(sk), sk->scan_group_ring,
+                             sk->sketch_matrix, true, sk->sketch_select, sk->sketch_wide)
+               .wide != 0;
 }
 
 // top-k pass for the nq staged queries of one shard: scan -> merges -> rerank -> D2H (async)
@@ -221,7 +233,10 @@ int enqueue_topk(szg_index *ix, Shard *sh, Ctx *c, int kp, int nq, bool has_allo
     // keeps the form that tests a row before issuing its loads.
     auto pass_rate = [&](int j) { return mask_pass_rate(sh, c, has_allow, j); };
     const bool masked = has_allow || sh->has_dead;
-    const int qpl = std::max(1, ix->queries_per_launch);
+    // (a wide batch of the sketch pre-pass: launches of up to 32 queries where the two-block matrix sweep serves them --
+    // unmasked, on every row: the same question the call asked before it planned wide batches)
+    const bool wide = on && on->wide && !masked && nq > szg::kMatrixQueries && sketch_wide_serves(ix, sh, kp, on->list);
+    const int qpl = wide ? szg::kMatrixWideQueries : std::max(1, ix->queries_per_launch);
     // One part -- or, for a short call (Pass::early_n), two: the sweeps of queries [0, early_n), whose merges, re-rank and
     // copy-back leave the scan stream for the context's own (one event), and the last few queries, whose tail is all
     // that is left to do after the call's final sweep.
@@ -239,6 +254,9 @@ int enqueue_topk(szg_index *ix, Shard *sh, Ctx *c, int kp, int nq, bool has_allo
                 a.mask_dense = lowest >= 0.5 ? 1 : 0;
             }
             a.kp = m;
+            // (a call with wide batches: its launches take the matrix sweep whatever their count -- a rest of one or two
+            // queries too -- so that a query's keys do not depend on where the batches' edges fall)
+            if (on && on->wide && a.matrix == 0) a.matrix = 2;
             // (a call that keeps more than 64 candidates per query -- lists that would not fit registers at full length --
             // stays with the grouped kernels even where its short lists would fit)
             if (kp > 64) a.matrix = 1;
@@ -1160,80 +1178,17 @@ int TopkCall::run()
     if (replay_all) kp = 1;  // the batches only stage their queries
 
     // A call of several shared-sweep batches is bound by its host work (3-4 us per query against 2.7-3.7 us of GPU
-    // time for the int8 and 16-bit sweeps): a second thread takes the finished batches -- waits, candidate
-    // assembly, certification, output -- while this one prepares and enqueues.  The hand-over is the batch queue;
-    // contexts are the flow control (acquire blocks until the finisher has released one).
-    struct Finisher {
-        std::mutex mu;
-        std::condition_variable cv;
-        std::deque<TopkBatch> q;
-        bool done = false;
-        int rc = SZG_OK;
-        std::string err;
-        std::atomic<bool> failed{false};
-        std::thread th;
-        void stop()
-        {
-            if (!th.joinable()) return;
-            {
-                std::lock_guard<std::mutex> lk(mu);
-                done = true;
-            }
-            cv.notify_one();
-            th.join();
-        }
-        ~Finisher() { stop(); }  // (an exception unwinding the call: the queued batches are still finished first)
-    } fin;
+    // time for the int8 and 16-bit sweeps): a second thread takes the finished batches (Finisher, scan_internal.h)
+    // while this one prepares and enqueues.
+    Finisher<TopkBatch> fin;
     bool threaded = false;
     {
         const int nb0 = replay_all ? 0 : mq_blocks(ix, n_queries);
         threaded = ix->finish_thread && nb0 > 0 && n_queries > 2 * 16 * nb0 * (mq_uses_i8(ix, false, n_queries) ? 2 : 1);
     }
-    if (threaded) {
-        try {
-            fin.th = std::thread([this, &fin] {
-                for (;;) {
-                    std::unique_lock<std::mutex> lk(fin.mu);
-                    fin.cv.wait(lk, [&] { return !fin.q.empty() || fin.done; });
-                    if (fin.q.empty()) return;
-                    TopkBatch t(std::move(fin.q.front()));
-                    fin.q.pop_front();
-                    lk.unlock();
-                    int r;
-                    try {
-                        r = finish(t);
-                    } catch (const std::bad_alloc &) {
-                        r = fail(SZG_E_NOMEM, "out of host memory");
-                    } catch (...) {
-                        r = fail(SZG_E_DEVICE, "unexpected exception");
-                    }
-                    if (r != SZG_OK && !fin.failed.load()) {  // (every batch is still finished: its contexts go back)
-                        fin.rc = r;
-                        fin.err = szg_last_error();
-                        fin.failed.store(true);
-                    }
-                }
-            });
-        } catch (...) {
-            threaded = false;  // no thread to be had: this one does both
-        }
-    }
-    std::function<bool(TopkBatch &&)> hand_over;
-    if (threaded) {
-        hand_over = [&fin](TopkBatch &&t) {
-            {
-                std::lock_guard<std::mutex> lk(fin.mu);
-                fin.q.push_back(std::move(t));
-            }
-            fin.cv.notify_one();
-            return !fin.failed.load();
-        };
-    }
-    int rc = run_batches<TopkBatch>(*this, hand_over);
-    if (threaded) {
-        fin.stop();
-        if (rc == SZG_OK && fin.failed.load()) rc = fail(fin.rc, fin.err.c_str());  // (this thread's last-error slot)
-    }
+    if (threaded) threaded = fin.start([this](TopkBatch &t) { return finish(t); });
+    int rc = run_batches<TopkBatch>(*this, threaded ? fin.hand_over() : nullptr);
+    if (threaded) rc = fin.join(rc);
     return rc;
 }
 

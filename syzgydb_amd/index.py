@@ -919,6 +919,20 @@ def scan_select_plan(dim, quant_bits, n_queries, kp=8, planes=2, norms=True, til
     return {"serves": bool(serves.value), "row_lists": bool(rows.value)}
 
 
+def scan_wide_plan(dim, quant_bits, n_queries, kp=8, planes=2, norms=True, tiled=True, masked=False, scan_group=0,
+                   sketch_matrix=0, sketch_select=0, sketch_wide=0):
+    """Host-only test hook: the matrix sweep's two-block form (option sketch_wide) for a one-sweep top-k call of
+    n_queries queries in launches of up to 32 (16 where a launch of 32 does not qualify) -- whether the form serves the
+    first launch, that launch's LDS bytes, and the passes over the rows of the whole call."""
+    L = _lib.load()
+    serves, passes, lds = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_uint64()
+    check(L.szg_debug_scan_wide(int(dim), int(quant_bits), int(n_queries), int(kp), int(planes), int(bool(norms)),
+                                int(bool(tiled)), int(bool(masked)), int(scan_group), int(sketch_matrix),
+                                int(sketch_select), int(sketch_wide), ctypes.byref(serves), ctypes.byref(passes),
+                                ctypes.byref(lds)), "szg_debug_scan_wide")
+    return {"serves": bool(serves.value), "passes": passes.value, "lds_bytes": lds.value}
+
+
 def scan_group_ring_plan(dim, quant_bits, n_queries, kp=10, scan_group=0, scan_group_ring=0):
     """Host-only test hook: the ring depth a one-sweep launch of n_queries queries takes under options scan_group and
     scan_group_ring, and the values of scan_group_ring the library accepts beside 0 (the depths it carries)."""
@@ -943,7 +957,8 @@ def merge_short_plan(n_lists, m, kp):
 
 def option_check(name, value):
     """Host-only test hook (no device needed): raises SzgError where ScanIndex.set_option would refuse `value` for the
-    one-sweep kernel's option `name` (scan_group, scan_group_ring, scan_norms, sketch_planes, sketch_matrix, sketch_select)."""
+    one-sweep kernel's option `name` (scan_group, scan_group_ring, scan_norms, sketch_planes, sketch_matrix, sketch_select,
+    sketch_wide)."""
     L = _lib.load()
     check(L.szg_debug_option_check(name.encode(), int(value)), "szg_debug_option_check")
 
