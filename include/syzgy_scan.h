@@ -706,6 +706,13 @@ int szg_reset_stats(szg_index *ix);
  *                             batches and launches of up to 32, whatever its length.  Lists, keys, the drop bound and
  *                             answers are the same bit for bit; szg_stats.scan_bytes counts one pass per 32 queries of a
  *                             wide launch.  Other values are refused
+ *     sketch_bulk         0   crowded tiles of the row lists (sketch_select): a tile of 16 rows whose pre-filter lets
+ *                             many (query, row) pairs of a wave through -- a wave's first tiles, while its lists fill --
+ *                             merges each list with its 16 candidates whole, by a fixed sorting network, where the
+ *                             rounds would insert them one per list and round.  0 = automatic (tiles with 48 passing
+ *                             pairs or more), 1 = never (rounds only), n = 2 .. 1024: tiles with n passing pairs or more
+ *                             (2: practically every tile that selects; a tile has at most 512 pairs).  Lists, keys,
+ *                             the drop bound and answers are the same bit for bit.  Other values are refused
  *     query_batch         16  queries staged, merged, re-ranked and copied back together
  *     mask_dense          1   sweeps whose filter / tombstone masks pass at least half the rows read every row and
  *                             apply the masks at the row finish; selective masks (and 0) compact the row steps that
@@ -858,7 +865,7 @@ int szg_debug_scan_group_ring(int dim, int quant_bits, int kp, int scan_group, i
 
 /*
  * Test hook, host only: would szg_set_option accept `value` for the one-sweep kernel's option `name` (scan_group,
- * scan_group_ring, scan_norms, sketch_planes, sketch_matrix, sketch_select, sketch_wide)?  SZG_OK, or SZG_E_INVALID with szg_set_option's text; any other name is refused.
+ * scan_group_ring, scan_norms, sketch_planes, sketch_matrix, sketch_select, sketch_wide, sketch_bulk)?  SZG_OK, or SZG_E_INVALID with szg_set_option's text; any other name is refused.
  */
 int szg_debug_option_check(const char *name, int64_t value);
 

@@ -5,6 +5,7 @@
 #   scripts/kernel_isa_digest.sh > new.txt                      every shared-sweep object of this tree
 #   scripts/kernel_isa_digest.sh -C ../old/syzgydb_amd/csrc kernels_mq.hip kernels_mq.hip:-DSZG_MQ_PART=1 > old.txt
 #   scripts/kernel_isa_digest.sh kernels_scan.hip:-DSZG_QBITS=8,-DSZG_SCAN_METRIC=1
+#   scripts/kernel_isa_digest.sh kernels_scan_mx.hip:-DSZG_SCAN_METRIC=1,-fno-slp-vectorize,-DSZG_MX_NO_SLP   (MX_FLAGS)
 # An argument is SOURCE[:FLAG[,FLAG...]], compiled with the build's flags (CXXFLAGS of syzgydb_amd/csrc/Makefile) plus
 # --cuda-device-only -S.  The text of a kernel is its instructions (label to .Lfunc_end) and its .amdhsa_kernel block;
 # the function index inside local labels (.LBB<n>_<m>, .Lfunc_end<n>, .LJTI<n>_<m>, and BB<n>_<m> in the loop comments), which

@@ -16,7 +16,7 @@
 set -euo pipefail
 cd "$(dirname "$0")/../syzgydb_amd/csrc"
 kind=${1:-mq}; part=${2:-i8}
-if [ "$kind" = scan ] && [ "$part" = mx ]; then src=kernels_scan_mx.hip; def=-DSZG_SCAN_METRIC=${3:-1}
+if [ "$kind" = scan ] && [ "$part" = mx ]; then src=kernels_scan_mx.hip; def="-DSZG_SCAN_METRIC=${3:-1} -fno-slp-vectorize -DSZG_MX_NO_SLP"   # (the Makefile's MX_FLAGS)
 elif [ "$kind" = scan ]; then src=kernels_scan.hip; def=-DSZG_QBITS=$part
 elif [ "$kind" = exact ]; then src=kernels_exact.hip; def=-ffp-contract=off
 elif [ "$kind" = mask ]; then src=kernels_mask.hip; def=

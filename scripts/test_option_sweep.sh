@@ -44,6 +44,14 @@ for opts in ${SWEEP_MQ_SETS-force_matrix=1,serialize_scans=0 force_no_refine=1 f
   run "multiquery tests, $opts" tests/test_gpu_multiquery.py -q -x \
       --deselect tests/test_gpu_multiquery.py::test_fused_selection_overflow_falls_back
 done
+# the row lists' whole-tile merge off (1) and on every tile that selects (2), on the files that open sketched handles
+# (SWEEP_BULK_SETS="" skips them)
+for opts in ${SWEEP_BULK_SETS-sketch_bulk=1 sketch_bulk=2}; do
+  run "sketched handles, $opts" tests/test_gpu_sketch.py tests/test_gpu_sketch_default.py tests/test_gpu_sketch_lists.py \
+      tests/test_gpu_sketch_state.py tests/test_gpu_sketch_planes.py tests/test_gpu_sketch_matrix.py \
+      tests/test_gpu_sketch_select.py tests/test_gpu_sketch_wide.py tests/test_gpu_sketch_bulk.py \
+      tests/test_gpu_certificates.py -m gpu -q -x
+done
 # the shared sweeps without the resident row norms (a test hook of its own: an environment variable read once per process)
 if [ -z "$SWEEP_SKIP_NORMS" ]; then
   opts=""

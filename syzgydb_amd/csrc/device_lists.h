@@ -133,6 +133,41 @@ __device__ __forceinline__ uint64_t row_shr1_u64(uint64_t v)
     return ((uint64_t)hi << 32) | lo;
 }
 
+// both halves of a 64-bit value through one in-row DPP move (CTRL: quad_perm, row_ror, row_mirror, row_half_mirror)
+template <int CTRL>
+__device__ __forceinline__ uint64_t row_dpp_u64(uint64_t v)
+{
+    const int lo = (int)(uint32_t)v, hi = (int)(uint32_t)(v >> 32);
+    return ((uint64_t)(uint32_t)__builtin_amdgcn_update_dpp(hi, hi, CTRL, 0xF, 0xF, false) << 32) |
+           (uint32_t)__builtin_amdgcn_update_dpp(lo, lo, CTRL, 0xF, 0xF, false);
+}
+// the in-row partners of a sorting network over 16 lanes: lane j receives the value of lane ...
+enum RowPartner {
+    kRowXor1 = 0xB1,     // j ^ 1   (quad_perm [1, 0, 3, 2])
+    kRowXor2 = 0x4E,     // j ^ 2   (quad_perm [2, 3, 0, 1])
+    kRowXor3 = 0x1B,     // j ^ 3   (quad_perm [3, 2, 1, 0])
+    kRowXor4 = -4,       // j ^ 4   (two moves: j ^ 7, then j ^ 3)
+    kRowXor7 = 0x141,    // j ^ 7   (row_half_mirror)
+    kRowXor8 = 0x128,    // j ^ 8   (row_ror:8)
+    kRowXor15 = 0x140,   // j ^ 15  (row_mirror)
+};
+template <int P>
+__device__ __forceinline__ uint64_t row_partner_u64(uint64_t v)
+{
+    if constexpr (P == kRowXor4) {
+        return row_dpp_u64<kRowXor3>(row_dpp_u64<kRowXor7>(v));
+    } else {
+        return row_dpp_u64<P>(v);
+    }
+}
+// one compare-exchange step: a lane with `low` keeps the smaller of its value and its partner's, the others the larger
+template <int P>
+__device__ __forceinline__ uint64_t row_cex_u64(uint64_t v, bool low)
+{
+    const uint64_t p = row_partner_u64<P>(v);
+    return ((p < v) == low) ? p : v;
+}
+
 // RowList: FOUR lists of m <= 16 candidates in one register pair, one per lane-row (lanes 16 c .. 16 c + 15): lane
 // (c, j) holds entry j of lane-row c's list, sorted ascending, entries j >= m stay kInvalidCand.  Where every
 // lane-row has candidates of its own to offer (the matrix sweep: lane-row c scores queries 4 c .. 4 c + 3), one round
@@ -148,10 +183,12 @@ struct RowList {
         worst = kInvalidCand;
     }
 
-    // One round.  act: the ballot of the lanes whose candidate is below their lane-row's `worst`; a lane's candidate is
-    // (ukey << 32) | (row0 + (lane & 15)).  In every lane-row with such a lane the first of them is retired: its
-    // candidate goes into the lane-row's list and its bit of `pass` is cleared.  Lane-rows without one change nothing.
-    __device__ __forceinline__ void round(uint64_t act, bool &pass, uint32_t ukey, uint32_t row0, int lane, int m)
+    // One round.  act: the ballot of the lanes that still have a candidate (their bit of `left`) below their lane-row's
+    // `worst`; a lane's candidate is (ukey << 32) | (row0 + (lane & 15)).  In every lane-row with such a lane the first of
+    // them is retired: its candidate goes into the lane-row's list and its bit of `left` is cleared.  Lane-rows without
+    // one change nothing.  (`left` is a wave-wide mask and not a flag per lane: it stays in a scalar register pair
+    // whatever else the tile's code does, and the test of a round is one scalar AND.)
+    __device__ __forceinline__ void round(uint64_t act, uint64_t &left, uint32_t ukey, uint32_t row0, int lane, int m)
     {
         const int j = lane & 15, base = lane & 48;
         const uint32_t slice = (uint32_t)(act >> base) & 0xFFFFu;  // this lane-row's lanes
@@ -163,7 +200,39 @@ struct RowList {
         const int pos = __popc((uint32_t)(__ballot(mine < cand) >> base) & 0xFFFFu);
         const uint64_t up = row_shr1_u64(mine);
         if (on && j >= pos && j < m) mine = j == pos ? cand : up;
-        if (on && j == first) pass = false;
+        left &= ~__ballot(on && j == first);
+        worst = shfl_u64(mine, base + m - 1);
+    }
+
+    // A whole tile at once (crowded tiles, option sketch_bulk): every lane-row's list becomes the m smallest of its
+    // entries and the candidates of its lanes with `pass` set -- what the rounds leave, bit for bit, since an insert is a
+    // set operation on unique entries.  A fixed network of 15 compare-exchange steps over the lane-row: the 16 candidates
+    // (kInvalidCand where `pass` is false: it sorts last and never enters) are sorted ascending by a bitonic sort in its
+    // mirror form (blocks of 2, 4, 8, 16: partner j ^ (block - 1), then j ^ block/4 .. j ^ 1), laid reversed against the
+    // sorted list -- the smaller of each pair are the 16 smallest of the 32, a bitonic sequence -- and that is merged
+    // (j ^ 8, 4, 2, 1).  Per-lane VALU work and in-row DPP only; no loop, no scalar round trip, one broadcast at the end.
+    __device__ __forceinline__ void merge_tile(bool pass, uint32_t ukey, uint32_t row0, int lane, int m)
+    {
+        const int j = lane & 15, base = lane & 48;
+        const bool l1 = !(j & 1), l2 = !(j & 2), l4 = !(j & 4), l8 = !(j & 8);
+        uint64_t v = pass ? (((uint64_t)ukey << 32) | (row0 + (uint32_t)j)) : kInvalidCand;
+        v = row_cex_u64<kRowXor1>(v, l1);
+        v = row_cex_u64<kRowXor3>(v, l2);
+        v = row_cex_u64<kRowXor1>(v, l1);
+        v = row_cex_u64<kRowXor7>(v, l4);
+        v = row_cex_u64<kRowXor2>(v, l2);
+        v = row_cex_u64<kRowXor1>(v, l1);
+        v = row_cex_u64<kRowXor15>(v, l8);
+        v = row_cex_u64<kRowXor4>(v, l4);
+        v = row_cex_u64<kRowXor2>(v, l2);
+        v = row_cex_u64<kRowXor1>(v, l1);
+        const uint64_t rev = row_partner_u64<kRowXor15>(v);
+        v = rev < mine ? rev : mine;
+        v = row_cex_u64<kRowXor8>(v, l8);
+        v = row_cex_u64<kRowXor4>(v, l4);
+        v = row_cex_u64<kRowXor2>(v, l2);
+        v = row_cex_u64<kRowXor1>(v, l1);
+        mine = j < m ? v : kInvalidCand;
         worst = shfl_u64(mine, base + m - 1);
     }
 

@@ -161,6 +161,8 @@ struct ScanArgs {
     int wide;                   // option sketch_wide: 1 = a launch never takes the matrix sweep's two-block form; 0, 2 = a
                                 // launch of more than kMatrixQueries queries takes it where it qualifies (the host decides
                                 // which calls form such launches)
+    int bulk;                   // option sketch_bulk: from how many passing (query, row) pairs on a tile of the row-list matrix
+                                // sweep merges every slot whole (sketch_bulk_min) -- 0 = automatic, 1 = never, n >= 2 = n
 };
 
 // Which scan_kernel instantiation a launch takes: decided on the host by scan_variant -- the launcher dispatches on
@@ -192,6 +194,15 @@ constexpr bool sketch_matrix_known(int64_t v) { return v == 0 || v == 1 || v == 
 constexpr int kRowListMax = 16;
 constexpr bool sketch_select_known(int64_t v) { return v == 0 || v == 1; }
 constexpr bool matrix_row_lists(int kp, int select_opt) { return select_opt == 0 && kp >= 1 && kp <= kRowListMax; }
+// Crowded tiles of the row lists (option sketch_bulk): a tile whose pre-filter lets at least
+// kBulkMin (query, row) pairs of the wave through merges every slot whole (RowList::merge_tile: a fixed sorting network
+// in the lane-row) instead of retiring one lane per lane-row, slot and round.  0 = automatic (kBulkMin), 1 = never (rounds
+// only), n >= 2 = tiles with at least n passing pairs (a tile of two blocks has at most 512: larger values are "never").
+// Both routes leave the same lists bit for bit; routing and scan_variant do not depend on it.
+constexpr uint32_t kBulkMin = 48;
+constexpr uint32_t kBulkNever = 0xFFFFFFFFu;
+constexpr bool sketch_bulk_known(int64_t v) { return v >= 0 && v <= 1024; }
+constexpr uint32_t sketch_bulk_min(int bulk_opt) { return bulk_opt == 0 ? kBulkMin : (bulk_opt == 1 ? kBulkNever : (uint32_t)bulk_opt); }
 // The wide form (option sketch_wide): a launch of more than kMatrixQueries and up to kMatrixWideQueries queries that the
 // matrix sweep serves with row lists scores two column blocks of 16 queries per row read, where the two-block image,
 // constants and lists fit 64 KiB of LDS (768 dimensions: lists of up to 15 entries; longer ones keep one block).

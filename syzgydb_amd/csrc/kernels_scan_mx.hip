@@ -35,6 +35,11 @@
 //    queries, 3 % faster at one to three).  At most 16 rounds per tile, the bound in the loop itself.  There is no
 //    serial route beside the rounds for tiles with few passing lanes: launches of one to four live queries, where
 //    few lanes pass in every tile, measure the same under both forms, so it has nothing to win.
+//    The lanes of a slot that still have a candidate are a 64-bit wave mask in scalar registers (a round's test is one
+//    scalar AND).  A CROWDED tile -- kBulkMin passing (query, row) pairs of the wave or more, option sketch_bulk: a
+//    wave's first few tiles, which would take 16, 9, 7 ... rounds -- skips the rounds: every slot with a passing lane
+//    is merged whole with its 16 candidates by a fixed sorting network in the lane-row (RowList::merge_tile; DESIGN.md
+//    4.5 item 11).
 //  * serial inserts (16 < a.kp <= 64, or sketch_select = 1): per wave and query a WaveList of a.kp entries in
 //    registers (16 lists, one VGPR pair each), offered to query by query, one candidate at a time.
 // The row-list form also exists with TWO column blocks (NB = 2; DESIGN.md 4.5 item 10, option sketch_wide): a launch of
@@ -48,6 +53,13 @@
 
 #ifndef SZG_SCAN_METRIC
 #error "kernels_scan_mx.hip needs SZG_SCAN_METRIC (0 or 1)"
+#endif
+// The row lists keep the pending lanes of every slot as 64-bit wave masks (finish_tile: left[], act[]).  The SLP
+// vectorizer pairs such masks into <2 x i64> values and the gfx950 instruction selector of ROCm 7.2's clang dies on them
+// (a segmentation fault in InstrEmitter::AddRegisterOperand, in whichever kernel form the pairing hits).  This file is
+// compiled with -fno-slp-vectorize, and -DSZG_MX_NO_SLP beside it says so (Makefile MX_FLAGS).
+#ifndef SZG_MX_NO_SLP
+#error "kernels_scan_mx.hip: compile with -fno-slp-vectorize -DSZG_MX_NO_SLP (the Makefile's MX_FLAGS)"
 #endif
 
 namespace szg {
@@ -95,8 +107,10 @@ constexpr int mx_ring()
 // block with accumulators and double-buffered A operands of its own.  After a tile lane (c, t) holds the sums of
 // queries 16 b + 4 c + r against row t: lane-row c keeps 4 NB RowLists, slot 4 b + r the list of that query.  The
 // keys of a (query, row) pair are formed by the same operations as with one block: bit-identical.
+// (the shaped one-block row-list kernels run four waves per SIMD: their bound is 128 registers, said here so that the
+// whole-tile merge cannot cost them that row by a register or two)
 template <int METRIC, int STEPS, bool NT, bool ROWS, int NB = 1>
-__global__ __launch_bounds__(256, 2) void scan_mx_kernel(const ScanArgs a)
+__global__ __launch_bounds__(256, (ROWS && NB == 1 && STEPS != 0) ? 4 : 2) void scan_mx_kernel(const ScanArgs a)
 {
     static_assert(NB == 1 || (NB == 2 && ROWS), "two column blocks: row lists only");
     static_assert(16 * NB <= kMatrixWideQueries, "the launch's constants are sized by kMatrixWideQueries");
@@ -110,6 +124,8 @@ __global__ __launch_bounds__(256, 2) void scan_mx_kernel(const ScanArgs a)
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int nwaves = blockDim.x >> 6;
     const int steps = STEPS ? STEPS : (int)a.steps;
+    // row lists: tiles with this many passing pairs or more are merged whole (option sketch_bulk)
+    [[maybe_unused]] const uint32_t bulk_min = sketch_bulk_min(a.bulk);
     const int n16 = steps * 2 * 64;  // 16-byte words of a block's image: [step][plane m, l][chunk * 16 + query]
 
     // LDS: the group's image [block] | qscale, qconst, qnorm2 [16 NB] | the wave lists [query of the group][wave][kp]
@@ -206,12 +222,31 @@ __global__ __launch_bounds__(256, 2) void scan_mx_kernel(const ScanArgs a)
 #pragma unroll
                 for (int r = 0; r < NS; r++) uk[r] = ordered_key(key[r]);
                 const uint32_t row0 = (uint32_t)(tile * 16);
+                // the lanes whose candidate has not been retired, slot by slot, as scalar masks
+                uint64_t left[NS];
+#pragma unroll
+                for (int r = 0; r < NS; r++) left[r] = __ballot(pass[r]);
+                uint32_t n_pass = 0;
+#pragma unroll
+                for (int r = 0; r < NS; r++) n_pass += (uint32_t)__popcll(left[r]);
+                // A crowded tile (a wave's first few: its lists are filling, or their bounds still loose) would pay as
+                // many rounds as its fullest lane-row and slot has passing lanes.  From bulk_min passing pairs on -- a
+                // scalar count -- every slot with a passing lane is merged whole instead (RowList::merge_tile).
+                if (n_pass >= bulk_min) {
+#pragma unroll
+                    for (int r = 0; r < NS; r++) {
+                        if (!left[r]) continue;  // (wave-uniform)
+                        rls[r].merge_tile(pass[r], uk[r], row0, lane, a.kp);
+                        wk[r] = rls[r].worst_key();
+                    }
+                    return;
+                }
                 for (int round = 0; round < 16; round++) {
                     uint64_t act[NS];
                     uint64_t act_any = 0;
 #pragma unroll
                     for (int r = 0; r < NS; r++) {
-                        act[r] = __ballot(pass[r] && (((uint64_t)uk[r] << 32) | (uint32_t)row) < rls[r].worst);
+                        act[r] = left[r] & __ballot((((uint64_t)uk[r] << 32) | (uint32_t)row) < rls[r].worst);
                         act_any |= act[r];
                     }
                     if (!act_any) break;
@@ -219,7 +254,7 @@ __global__ __launch_bounds__(256, 2) void scan_mx_kernel(const ScanArgs a)
                     for (int r = 0; r < NS; r++) {
                         // (wave-uniform: late tiles have a few passing lanes, in one or two of the slots)
                         if (SZG_MX_ROUND_SKIP && !act[r]) continue;
-                        rls[r].round(act[r], pass[r], uk[r], row0, lane, a.kp);
+                        rls[r].round(act[r], left[r], uk[r], row0, lane, a.kp);
                     }
                 }
 #pragma unroll

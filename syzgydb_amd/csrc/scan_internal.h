@@ -439,6 +439,8 @@ struct szg_index {
     int sketch_wide = 0;      // the matrix sweep's two-block form (32 queries per row read): 0 = automatic (calls of
                               // kWideCallMin one-sweep queries on, under the default query_batch and queries_per_launch),
                               // 1 = never, 2 = every call of more than 16 queries where the shape allows
+    int sketch_bulk = 0;      // the row lists' whole-tile merge: 0 = automatic (tiles with szg::kBulkMin passing pairs or more),
+                              // 1 = never (rounds only), n >= 2 = tiles with n passing pairs or more
     bool is_sketch = false;   // this index is the internal sketch of a float32 handle: its keys only bound
     int tie_mode = 0;         // 0: exact full replay on ties/NaN, 1: keep the fast answer
     int serialize_scans = 1;  // scan launches of a shard never overlap each other

@@ -144,6 +144,7 @@ void fill_scan_args(const szg_index *ix, const Shard *sh, const Ctx *c, bool has
     a->matrix = ix->sketch_matrix;
     a->select = ix->sketch_select;
     a->wide = ix->sketch_wide;
+    a->bulk = ix->sketch_bulk;
 }
 
 // Launch the fused scan for each of the batch's queries (n = a->size()) as the
