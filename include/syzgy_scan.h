@@ -636,6 +636,10 @@ typedef struct szg_stats {
     uint64_t mq_bf16_sweeps;   /* shared sweeps that ran on the bfloat16 matrix cores (64- / 32- / 16-bit rows, top-k batches
                                   on 8-bit rows in whole 64-byte steps; their candidates are re-scored in float32 and
                                   re-ranked in float64 like every other path's) */
+    uint64_t sketch_radius_queries;   /* radius queries answered through the 8-bit sketch ("sketch_radius" option) */
+    uint64_t sketch_radius_fallbacks; /* ... that it handed to the float32 sweep: a zero query under cosine, a non-finite
+                                         query or radius, a widened radius that covers everything, more candidates than
+                                         the batch's buffers hold */
 } szg_stats;
 
 /* HIP-event timing on the library's own streams (off by default): 1 = events around the scan
@@ -744,6 +748,20 @@ int szg_reset_stats(szg_index *ix);
  *                             list), and the certificate takes the lower of it and the kp-th key, so a block holding
  *                             more than m of the best rows sends the query to the full sweep.  Same answers.
  *     sketch_min_rows     4096  collections below this size always take the full sweep
+ *     sketch_radius       0   1 = radius queries that would each take a sweep of their own -- a lone szg_search_radius, or
+ *                             a batch under radius_mq = 0 -- go through the sketch wherever "sketch" applies to the handle
+ *                             (float32 rows, its row-count rule and its steps aside; no rule on k): a collect sweep of the
+ *                             sketch at the radius widened by the largest row-to-sketch distance finds every hit by the
+ *                             triangle inequality (a quarter of the bytes), the float64 re-rank on the float32 rows and
+ *                             `distance <= radius` decide.  Launches of 3 queries or more without filter or tombstones
+ *                             share each row read on the matrix cores (16 per read, 32 under the sketch_wide rules;
+ *                             szg_stats.scan_bytes counts one pass per 16 / 32 queries of such a launch).  A zero query
+ *                             under cosine, a non-finite query or radius, a widened radius of 1 or more under cosine
+ *                             and a query with more candidates than the batch's buffers hold take the float32 sweep.
+ *                             Same answers.  0 = never (the default): the option is new and off, as the top-k pre-pass
+ *                             was -- built as an option, soaked by the fuzzers, made the default by a later change.
+ *                             Batches that share a sweep (radius_mq = 1, two queries or more) keep it.  Other values
+ *                             are refused
  *   shared sweeps
  *     multi_query         1   batches of >= mq_min queries share ONE sweep of the corpus, the dot products on the
  *                             matrix cores: 64- / 32- / 16-bit rows on bfloat16 roundings (v_mfma_f32_16x16x32_bf16,
@@ -849,6 +867,18 @@ int szg_debug_scan_wide(int dim, int quant_bits, int n_queries, int kp, int plan
                         int32_t *passes, uint64_t *lds_bytes);
 
 /*
+ * Test hook, host only: does the matrix sweep's collect form (radius searches through the sketch, option sketch_radius)
+ * serve a collect call of n_queries queries with one sweep each, under the conditions of szg_debug_scan_matrix?  The
+ * call is split into launches of up to 32 queries where sketch_wide = 2 and a launch of 32 qualifies for the two-block
+ * form, of up to 16 otherwise.  *serves / *wide / *steps_form / *lds_bytes describe the first launch (wide: it scores 32
+ * queries per row read; lds_bytes: 16 b (2 dim64 + 16) with b column blocks), *passes = passes over the rows of the
+ * whole call: one per launch the form serves, one per query elsewhere.
+ */
+int szg_debug_scan_collect(int dim, int quant_bits, int n_queries, int planes, int norms, int tiled, int masked,
+                           int scan_group, int sketch_matrix, int sketch_wide, int32_t *serves, int32_t *wide,
+                           int32_t *passes, uint64_t *lds_bytes, int32_t *steps_form);
+
+/*
  * Test hook, host only: *fits = the sketch sweep's one-launch short-list merge serves n_lists block lists of m entries
  * at kp candidates; *sorts = the most entries under its threshold (the kp-th smallest first entry) that its selection
  * sorts in one network -- with more, and always when *sorts < kp, the launch runs the tournament.
@@ -865,7 +895,7 @@ int szg_debug_scan_group_ring(int dim, int quant_bits, int kp, int scan_group, i
 
 /*
  * Test hook, host only: would szg_set_option accept `value` for the one-sweep kernel's option `name` (scan_group,
- * scan_group_ring, scan_norms, sketch_planes, sketch_matrix, sketch_select, sketch_wide, sketch_bulk)?  SZG_OK, or SZG_E_INVALID with szg_set_option's text; any other name is refused.
+ * scan_group_ring, scan_norms, sketch_planes, sketch_matrix, sketch_select, sketch_wide, sketch_bulk, sketch_radius)?  SZG_OK, or SZG_E_INVALID with szg_set_option's text; any other name is refused.
  */
 int szg_debug_option_check(const char *name, int64_t value);
 
@@ -929,6 +959,10 @@ int szg_debug_refuse_device_alloc(int64_t nth);
 #define SZG_CERT_ESCALATION 2    /* the collect sweep of a query whose first pass was not certified */
 #define SZG_CERT_RADIUS_SINGLE 3 /* radius collect, one sweep per query */
 #define SZG_CERT_RADIUS_SHARED 4 /* radius collect, one shared sweep per batch */
+#define SZG_CERT_SKETCH_RADIUS 5 /* radius collect on the sketch (recorded on the float32 handle, one record per query):
+                                    thr / eps of the sketch sweep, D = the sketch-distance radius R (1 + 1e-9) + slack,
+                                    keyed entries = the collected sketch rows with their sketch keys, NO_KEY entries =
+                                    the rows without a usable sketch re-ranked beside them */
 #define SZG_CERT_KEYS_SINGLE 0
 #define SZG_CERT_KEYS_SHARED_INT8 1
 #define SZG_CERT_KEYS_SHARED_BF16 2

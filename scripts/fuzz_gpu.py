@@ -33,7 +33,7 @@ OPTS = [("queries_per_launch", [1, 3, 16]), ("multi_query", [0, 1]), ("force_mat
         ("serialize_scans", [0, 1]), ("mq_min", [2, 8]), ("slack", [0, 16, 40]), ("mq_hits", [64, 1024]),
         ("sketch", [0, 1, 1]), ("sketch_extra", [0, 30]), ("sketch_min_rows", [1, 1, 4096]),
         ("force_no_refine", [0, 0, 1]), ("mask_dense", [0, 1]), ("coalesce", [0, 1]), ("finish_thread", [0, 1, 1]),
-        ("radius_mq", [0, 1, 1]), ("query_batch", [5, 16]), ("scan_group", [0, 1, 2, 4])]
+        ("radius_mq", [0, 1, 1]), ("query_batch", [5, 16]), ("scan_group", [0, 1, 2, 4]), ("sketch_radius", [0, 1, 1])]
 
 
 def same(got_r, got_d, want_r, want_d):
@@ -45,7 +45,7 @@ def same(got_r, got_d, want_r, want_d):
     return bool(((g == w) | (np.isnan(g) & np.isnan(w))).all())
 
 
-def certificates(ix, rows, dim, bits, metric, Q, eligible, desc, call):
+def certificates(ix, rows, dim, bits, metric, Q, eligible, desc, call, radii=None):
     """--certificates: the records of the call just made, checked; a failed claim counts like a wrong answer."""
     if not args.certificates:
         return 0
@@ -53,13 +53,14 @@ def certificates(ix, rows, dim, bits, metric, Q, eligible, desc, call):
     corpus = cert_check.Corpus(rows, dim, bits, metric)
     Q = np.atleast_2d(Q)
     dists = sketch = None
-    if (recs["pass_"] == 1).any():
+    if np.isin(recs["pass_"], (1, 5)).any():   # sketch passes, top-k and radius
         dists = np.stack([orc.all_distances(rows, dim, bits, metric, q) for q in Q])
         info = ix.sketch_info()
         if info["exists"] and info["in_sync"]:   # the sketch sweep's own keys and lists too (K_s, L_s, D)
             sketch = (cert_check.Corpus(ix.sketch_rows()[0], dim, 8, metric), info["gscale"], info["exc_rows"])
     try:
-        cert_check.check(corpus, Q, recs, ents, dropped, eligible=eligible, dists=dists, what=(call,), sketch=sketch)
+        cert_check.check(corpus, Q, recs, ents, dropped, eligible=eligible, dists=dists, what=(call,), sketch=sketch,
+                         radii=radii)
         cert_check.check_bf16_tight(corpus, Q, recs, ents, what=(call,))
     except AssertionError as e:
         print("CERTIFICATE", desc, str(e)[:600], flush=True)
@@ -168,7 +169,7 @@ while (it < args.iterations) if args.iterations else (time.time() < t_end):
             if finite:
                 radius = float(finite[-1])
                 rr, dd = ix.search_radius(Q[qi], radius, **filt(qi, qi + 1))
-                fails += certificates(ix, rows, dim, bits, metric, Q[qi], m, desc, "radius")
+                fails += certificates(ix, rows, dim, bits, metric, Q[qi], m, desc, "radius", radii=radius)
                 w_rows, w_dist, _ = orc.search_exact(rows, dim, bits, metric, Q[qi], radius=radius,
                                                      allow=m.astype(np.uint8))
                 if not same(rr, dd, w_rows, w_dist):
@@ -184,7 +185,7 @@ while (it < args.iterations) if args.iterations else (time.time() < t_end):
                 radii.append(float(fin[-1]) if fin else 0.5)
             hits = ix.search_radius_batch(Q[:nb_], radii, **filt(0, nb_))
             fails += certificates(ix, rows, dim, bits, metric, Q[:nb_], live if allow is None else (allow[:nb_] & live), desc,
-                                  "radius batch")
+                                  "radius batch", radii=radii)
             for qj in range(nb_):
                 mj = live if allow is None else (live & allow[qj])
                 w_r, w_d, _ = orc.search_exact(rows, dim, bits, metric, Q[qj], radius=radii[qj], allow=mj.astype(np.uint8))
@@ -212,7 +213,7 @@ while (it < args.iterations) if args.iterations else (time.time() < t_end):
             if finite and len(w_rows) > 3:
                 cap = int(rng.integers(1, len(w_rows)))
                 tr, td, total = ix.search_radius(Q[qi], radius, allow=None if allow is None else allow[qi], capacity=cap)
-                fails += certificates(ix, rows, dim, bits, metric, Q[qi], m, desc, "truncated radius")
+                fails += certificates(ix, rows, dim, bits, metric, Q[qi], m, desc, "truncated radius", radii=radius)
                 if total != len(w_rows) or not same(tr, td, w_rows[:cap], w_dist[:cap]):
                     fails += 1
                     print("MISMATCH truncated radius", desc, cap, total, len(w_rows), flush=True)
@@ -251,7 +252,7 @@ while (it < args.iterations) if args.iterations else (time.time() < t_end):
                     fin = [x for x in od if x == x and x > 0]
                     radii.append(float(fin[-1]) if fin else 0.5)
                 hits = ix.search_radius_batch(Q[:nb_], radii)
-                fails += certificates(ix, rows2, dim, bits, metric, Q[:nb_], live2, desc, "radius batch after mutation")
+                fails += certificates(ix, rows2, dim, bits, metric, Q[:nb_], live2, desc, "radius batch after mutation", radii=radii)
                 for qj in range(nb_):
                     w_r, w_d, _ = orc.search_exact(rows2, dim, bits, metric, Q[qj], radius=radii[qj], allow=live2.astype(np.uint8))
                     if not same(hits[qj][0], hits[qj][1], w_r, w_d):

@@ -8,6 +8,8 @@
 #                                             -> one metric's G > 1 kernels of one form (bit 0: two planes, bit 1: resident
 #                                                norms); without SZG_GROUP_FORM: the metric's G = 1 kernels
 #   scripts/kernel_resources.sh scan mx 1     -> kernels_scan_mx.hip -DSZG_SCAN_METRIC=1 (the matrix sweep, cosine)
+#   VFLAGS=-DSZG_MX_COLLECT scripts/kernel_resources.sh scan mx 1
+#                                             -> its collect form (radius searches through the sketch)
 #   scripts/kernel_resources.sh exact         -> kernels_exact.hip (re-rank, page-in, row gather, ...)
 #   scripts/kernel_resources.sh mask          -> kernels_mask.hip (device-resident filter masks)
 #   scripts/kernel_resources.sh column        -> kernels_column.hip (resident metadata columns)

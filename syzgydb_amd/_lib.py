@@ -55,7 +55,7 @@ EXPORTS = [
     # host-only test hook
     "szg_debug_scan_plan", "szg_debug_scan_group", "szg_debug_reorder_plan", "szg_debug_option_check",
     "szg_debug_scan_group_ring", "szg_debug_merge_short_plan", "szg_debug_scan_matrix",
-    "szg_debug_scan_select", "szg_debug_scan_wide",
+    "szg_debug_scan_select", "szg_debug_scan_wide", "szg_debug_scan_collect",
     # who owns device memory: the counters and the refusal countdown (added under ABI 4)
     "szg_debug_device_memory", "szg_debug_refuse_device_alloc",
     # the certificate trace: what each pass handed to certification (added under ABI 4)
@@ -65,6 +65,7 @@ EXPORTS = [
 ]
 # szg_cert_record.pass / .keys, szg_cert_entry.flags
 SZG_CERT_TOPK, SZG_CERT_SKETCH, SZG_CERT_ESCALATION, SZG_CERT_RADIUS_SINGLE, SZG_CERT_RADIUS_SHARED = range(5)
+SZG_CERT_SKETCH_RADIUS = 5   # radius collect on the sketch (option sketch_radius), recorded on the float32 handle
 (SZG_CERT_KEYS_SINGLE, SZG_CERT_KEYS_SHARED_INT8, SZG_CERT_KEYS_SHARED_BF16, SZG_CERT_KEYS_BF16_BAND,
  SZG_CERT_KEYS_BF16_RESCORED) = range(5)
 SZG_CERT_ENTRY_NO_KEY = 1
@@ -116,6 +117,8 @@ class SzgStats(ctypes.Structure):
         ("sketch_queries", ctypes.c_uint64),
         ("sketch_fallbacks", ctypes.c_uint64),
         ("mq_bf16_sweeps", ctypes.c_uint64),
+        ("sketch_radius_queries", ctypes.c_uint64),
+        ("sketch_radius_fallbacks", ctypes.c_uint64),
     ]
 
 
@@ -399,6 +402,10 @@ def load():
         L.szg_debug_scan_wide.restype = ctypes.c_int
         L.szg_debug_scan_wide.argtypes = ([ctypes.c_int] * 12 + [ctypes.POINTER(ctypes.c_int32)] * 2 +
                                           [ctypes.POINTER(ctypes.c_uint64)])
+    if hasattr(L, "szg_debug_scan_collect"):
+        L.szg_debug_scan_collect.restype = ctypes.c_int
+        L.szg_debug_scan_collect.argtypes = ([ctypes.c_int] * 10 + [ctypes.POINTER(ctypes.c_int32)] * 3 +
+                                             [ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_int32)])
     if hasattr(L, "szg_debug_scan_select"):
         L.szg_debug_scan_select.restype = ctypes.c_int
         L.szg_debug_scan_select.argtypes = [ctypes.c_int] * 11 + [ctypes.POINTER(ctypes.c_int32)] * 2

@@ -21,6 +21,16 @@ With the state of the sketch index (ScanIndex.sketch_info / sketch_rows) check()
 for the sketch sweep's own keys, against the real-number keys of the sketch rows, and that D follows from thr_min --
 and check_sketch_build() asserts B: the sketch bytes, the exception list and max_ang against sketch_reference().
 
+Radius searches through the sketch (option sketch_radius, pass SZG_CERT_SKETCH_RADIUS) need no answer-dependent
+certificate, only completeness; with the sketch state check() asserts K_s on their keyed entries and
+
+    C_s  every eligible row in range that is no exception and whose real-number SKETCH key plus its rounding is <= thr -
+         eps is among the keyed entries; every keyed entry has key <= thr; no ineligible row is collected
+    T    thr - eps is at or above the real-number key the record's sketch-distance radius D implies: -cos(pi D)
+         (cosine), (255 D / gscale)^2 (Euclid), in LD
+    S_r  D >= radius + slack for the radius the test passed, and every eligible row with distance <= radius is among
+         the record's entries or is an exception row
+
 Candidates the kernels force in carry no bound and are skipped and counted: cosine keys <= -1.5, rows with a non-finite
 element or an overflowing norm, keys clamped to 3e38.  A zero cosine query claims no bound at all.
 """
@@ -31,7 +41,9 @@ import numpy as np
 from . import _lib
 
 PASS_NAMES = {_lib.SZG_CERT_TOPK: "topk", _lib.SZG_CERT_SKETCH: "sketch", _lib.SZG_CERT_ESCALATION: "escalation",
-              _lib.SZG_CERT_RADIUS_SINGLE: "radius", _lib.SZG_CERT_RADIUS_SHARED: "radius-shared"}
+              _lib.SZG_CERT_RADIUS_SINGLE: "radius", _lib.SZG_CERT_RADIUS_SHARED: "radius-shared",
+              _lib.SZG_CERT_SKETCH_RADIUS: "sketch-radius"}
+SKETCH_PASSES = (_lib.SZG_CERT_SKETCH, _lib.SZG_CERT_SKETCH_RADIUS)   # their keys are keys of the rows' sketches
 KEYS_NAMES = {-1: "-", _lib.SZG_CERT_KEYS_SINGLE: "Single", _lib.SZG_CERT_KEYS_SHARED_INT8: "SharedInt8",
               _lib.SZG_CERT_KEYS_SHARED_BF16: "SharedBf16", _lib.SZG_CERT_KEYS_BF16_BAND: "Bf16Band",
               _lib.SZG_CERT_KEYS_BF16_RESCORED: "Bf16Rescored"}
@@ -156,7 +168,7 @@ class Margins:
 Summary = collections.namedtuple("Summary", "records kinds skipped skipped_rows checked")
 
 
-def check(corpus, Q, recs, ents, dropped, eligible=None, dists=None, margins=None, what=(), sketch=None):
+def check(corpus, Q, recs, ents, dropped, eligible=None, dists=None, margins=None, what=(), sketch=None, radii=None):
     """Assert K, L, C and S for the records of ONE call with queries Q.  eligible: bool[n] or bool[nq, n] (None: every
     row); dists: float64[nq, n], the oracle's distances (needed for sketch records).  -> Summary; skipped_rows are the
     rows whose candidates carried no bound.
@@ -169,7 +181,10 @@ def check(corpus, Q, recs, ents, dropped, eligible=None, dists=None, margins=Non
         L_s  every eligible row in range that is no exception and not among the keyed entries has a real-number
              sketch key >= thr_min
         D    the record's D is at most the sketch distance thr_min implies: acos(min(1, -thr_min)) / pi (cosine),
-             gscale sqrt(max(thr_min, 0)) / 255 (Euclid), in LD, plus that expression's own rounding"""
+             gscale sqrt(max(thr_min, 0)) / 255 (Euclid), in LD, plus that expression's own rounding
+
+    and, for every sketch-radius record (which needs sketch=, dists= and radii=, the radius the test passed per query):
+    K_s, C_s, T and S_r as the module's docstring states them."""
     Q = np.atleast_2d(np.asarray(Q, dtype=np.float64))
     nq, n = Q.shape[0], corpus.n
     assert dropped == 0, ("the trace dropped records", dropped, what)
@@ -204,7 +219,7 @@ def check(corpus, Q, recs, ents, dropped, eligible=None, dists=None, margins=Non
         key = e["key"].astype(np.float64)
         ub = e["ub"]
         # ---- K
-        if p != _lib.SZG_CERT_SKETCH and not zero_q[qi]:   # (a sketch key is the key of the row's 8-bit sketch, not of the row)
+        if p not in SKETCH_PASSES and not zero_q[qi]:   # (a sketch key is the key of the row's 8-bit sketch, not of the row)
             r_real, r_err = real[qi, rows], err[qi, rows]
             forced = keyed & ((~corpus.finite[rows]) | ~np.isfinite(r_real) | (key >= TAKE_ALL) |
                               ((key <= -1.5) if corpus.metric == _lib.SZG_COSINE else False))
@@ -245,7 +260,12 @@ def check(corpus, Q, recs, ents, dropped, eligible=None, dists=None, margins=Non
             inel = ~eligible[qi, rows]
             assert not inel.any(), ("C: a row that is not eligible was collected", where, rows[inel][:8])
         # ---- K_s, L_s, D
-        if p == _lib.SZG_CERT_SKETCH and sketch is not None and np.isfinite(rec["thr_min"]) and not zero_q[qi]:
+        if p == _lib.SZG_CERT_SKETCH_RADIUS:
+            assert sketch is not None and dists is not None and radii is not None, \
+                "sketch-radius records need the sketch state, the oracle's distances and the radii"
+            assert not zero_q[qi], ("a zero cosine query is handed over, never recorded", where)
+        if p in SKETCH_PASSES and sketch is not None and not zero_q[qi] and \
+                (p == _lib.SZG_CERT_SKETCH_RADIUS or np.isfinite(rec["thr_min"])):
             lb = float(rec["thr_min"])
             s_real, s_err = real_s[qi, rows], err_s[qi, rows]
             forced = keyed & (~np.isfinite(s_real) | (key >= TAKE_ALL) | ((key <= -1.5) if not euclid_s else False))
@@ -263,6 +283,39 @@ def check(corpus, Q, recs, ents, dropped, eligible=None, dists=None, margins=Non
                 margins.note(("sketch K_s", kind[1], kind[2], 8, corpus.metric), float((off / eps).max()), int(ok.sum()))
             left = eligible[qi] & in_range & ~is_exc & np.isfinite(real_s[qi])
             left[rows[keyed]] = False
+            if p == _lib.SZG_CERT_SKETCH_RADIUS:
+                # ---- C_s
+                thr, r_eps = float(rec["thr"]), float(rec["eps"])
+                assert (key[keyed] <= thr).all(), ("C_s: a collected sketch key above the threshold", where, thr,
+                                                   key[keyed][key[keyed] > thr][:8])
+                assert np.isfinite(r_eps) and r_eps > 0, ("C_s: the record carries no bound", where)
+                if thr >= TAKE_ALL:
+                    missed = np.flatnonzero(left)
+                else:
+                    missed = np.flatnonzero(left & (real_s[qi] + err_s[qi] <= thr - r_eps))
+                assert missed.size == 0, ("C_s: an eligible sketched row under the threshold was not collected", where, "thr",
+                                          thr, "eps", r_eps, "rows", missed[:8], "real", real_s[qi, missed[:8]])
+                inel = ~eligible[qi, rows]
+                assert not inel.any(), ("C_s: a row that is not eligible was collected", where, rows[inel][:8])
+                assert not is_exc[rows[keyed]].any(), ("C_s: a row without a usable sketch among the keyed entries", where)
+                assert is_exc[rows[~keyed]].all(), ("C_s: an entry without a key that is no exception row", where)
+                # ---- T
+                D = LD(float(rec["D"]))
+                assert np.isfinite(float(D)) and (euclid_s or float(D) < 1.0), ("T: a radius that is handed over was recorded", where)
+                implied = float((LD(255) * D / LD(gscale)) ** 2 if euclid_s else -np.cos(PI * D))
+                assert thr - r_eps >= implied - 4 * np.finfo(np.float64).eps * abs(implied), (
+                    "T: thr - eps below the key the sketch-distance radius implies", where, thr, r_eps, implied, float(D))
+                # ---- S_r
+                radius = float(np.broadcast_to(np.asarray(radii, dtype=np.float64), (nq,))[qi])
+                assert rec["D"] >= radius + rec["slack"], ("S_r: the sketch-distance radius does not cover radius + slack", where,
+                                                          float(rec["D"]), radius, float(rec["slack"]))
+                d = dists[qi]
+                hit = eligible[qi] & in_range & (d <= radius)
+                hit[rows] = False
+                bad = np.flatnonzero(hit & ~is_exc)
+                assert bad.size == 0, ("S_r: a row within the radius is neither an entry nor an exception row", where, radius,
+                                       "rows", bad[:8], "dist", d[bad[:8]])
+                continue
             bad = np.flatnonzero(left & (real_s[qi] + err_s[qi] < lb))
             assert bad.size == 0, ("L_s: a sketched row outside the lists under the bound", where, "thr_min", lb, "rows", bad[:8],
                                    "real", real_s[qi, bad[:8]])

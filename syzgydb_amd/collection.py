@@ -107,6 +107,8 @@ class Collection:
             # 8-bit sketch pre-pass for lone Searches on float32 collections (same answers, +25 % device memory):
             # None = the library's default (automatic), True / False force it on / off
             self._index.set_option("sketch", 1 if sketch else 0)
+            # ... and, forced on, for lone radius Searches too (option sketch_radius, off by default)
+            self._index.set_option("sketch_radius", 1 if sketch else 0)
         # removeDocument only tombstones a row: its bytes stay on the card and are swept by every search until
         # Compact() drops them.  auto_compact = a fraction f: removeDocument compacts by itself once the tombstoned
         # rows exceed f of the mirror's rows; None (the default) = never

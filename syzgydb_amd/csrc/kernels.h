@@ -163,7 +163,15 @@ struct ScanArgs {
                                 // which calls form such launches)
     int bulk;                   // option sketch_bulk: from how many passing (query, row) pairs on a tile of the row-list matrix
                                 // sweep merges every slot whole (sketch_bulk_min) -- 0 = automatic, 1 = never, n >= 2 = n
+    // collect mode of the matrix sweep's wide launch: the thresholds of sweeps kMaxSweepsPerLaunch .. kMatrixWideQueries - 1
+    // (behind everything else, like row_norm: the offsets the other kernels read stay as they were)
+    uint32_t thr_ukeys_hi[kMatrixWideQueries - kMaxSweepsPerLaunch];
 };
+// the collect threshold of sweep s of a launch (s < kMatrixWideQueries)
+__host__ __device__ inline uint32_t &scan_thr_ukey(ScanArgs &a, int s)
+{
+    return s < kMaxSweepsPerLaunch ? a.thr_ukeys[s] : a.thr_ukeys_hi[s - kMaxSweepsPerLaunch];
+}
 
 // Which scan_kernel instantiation a launch takes: decided on the host by scan_variant -- the launcher dispatches on
 // its answer, szg_debug_scan_plan reports it.
@@ -253,6 +261,7 @@ hipError_t launch_scan(int qbits, int metric, const ScanArgs &a, int grid, int b
 // group (group > 1, 8-bit rows) hold two digit planes
 // matrix: the matrix sweep's column blocks (1, or 2: the wide form; 0: not the matrix sweep) -- per block kMatrixQueries
 // two-plane images laid out for the matrix cores, their constants, and kMatrixQueries x waves lists of kp entries
+// (its collect form keeps no lists: kp = 0, the images and constants alone -- 48.4 KiB for two blocks at 768 dimensions)
 size_t scan_lds_bytes(int qbits, const RowMap &m, int kp, int block, int group = 1, int planes = 3, int matrix = 0);
 
 // Merge n_lists sorted lists of kp candidates into ceil(n_lists/merge_fan(kp)) lists.

@@ -52,6 +52,9 @@ static hipError_t launch_scan_g8(int metric, int form, const ScanArgs &a, const 
 // the matrix sweep, one object per metric (kernels_scan_mx.hip)
 hipError_t launch_scan_mx_m0(const ScanArgs &, const ScanVariant &, int, int, size_t, hipStream_t);
 hipError_t launch_scan_mx_m1(const ScanArgs &, const ScanVariant &, int, int, size_t, hipStream_t);
+// ... and its collect form (the same source with -DSZG_MX_COLLECT)
+hipError_t launch_scan_mxc_m0(const ScanArgs &, const ScanVariant &, int, int, size_t, hipStream_t);
+hipError_t launch_scan_mxc_m1(const ScanArgs &, const ScanVariant &, int, int, size_t, hipStream_t);
 #endif
 
 namespace {
@@ -1341,6 +1344,10 @@ hipError_t launch_scan_qmcm(const ScanArgs &a, int grid, int block, hipStream_t 
         // the launch has them (bit 1); every form is an object of its own (SZG_GROUP_FORM)
         if (v.group > 1) return launch_scan_g8(METRIC, (a.planes == 2 ? 1 : 0) | (a.row_norm ? 2 : 0), a, v, grid, block, lds, stream);
     }
+    if constexpr (QBITS == 8 && COLLECT && !MASKED) {
+        // ... and its collect form (objects of their own: the top-k kernels' code does not change with it)
+        if (v.matrix) return METRIC == kCosine ? launch_scan_mxc_m1(a, v, grid, block, lds, stream) : launch_scan_mxc_m0(a, v, grid, block, lds, stream);
+    }
     if (v.group != 1) return hipErrorInvalidValue;
     return launch_scan_group<QBITS, METRIC, COLLECT, MASKED, 1>(a, v, g, b, lds, stream);
 }
@@ -1468,15 +1475,34 @@ ScanVariant scan_variant(int qbits, const RowMap &m, bool tiled, int kp, bool co
             v.group = kMatrixWideQueries;
         }
     }
+    // Its collect form (radius searches through the sketch): the same conditions with `collect`
+    // set -- no lists, so neither kp nor the selection matter, and the two-block form needs the images and constants
+    // alone (48.4 KiB at 768 dimensions).  A launch of the caller that must keep the one-query collect kernel (a query
+    // swept again on its own) says matrix_opt = 1.
+    if (qbits == 8 && collect && !masked && ring < 8 && tiled && m.r16 > 0 && m.r16 % 4 == 0 && planes == 2 && norms &&
+        group == 0 && matrix_opt != 1 && n_queries >= (matrix_opt == 2 ? 1 : kMatrixMinQueries) && block >= kWave &&
+        block <= 256 && block % kWave == 0 && scan_lds_bytes(qbits, m, 0, block, kMatrixQueries, planes, 1) <= 64u * 1024u) {
+        v.matrix = 1;
+        v.matrix_steps = matrix_steps_form(m.r16 / 4);
+        v.group = kMatrixQueries;
+        v.shaped = 0;
+        v.ring_depth = v.matrix_steps == 12 ? 6 : (v.matrix_steps == 6 ? 3 : 4);
+        if (wide_opt != 1 && n_queries > kMatrixQueries && n_queries <= kMatrixWideQueries &&
+            scan_lds_bytes(qbits, m, 0, block, kMatrixWideQueries, planes, 2) <= 64u * 1024u) {
+            v.wide = 1;
+            v.group = kMatrixWideQueries;
+        }
+    }
     return v;
 }
 
 size_t scan_lds_bytes(int qbits, const RowMap &m, int kp, int block, int group, int planes, int matrix)
 {
     // per column block: 16 two-plane images (32 bytes per piece and query) | qscale, qconst, qnorm2 | 16 x waves lists
+    // (kp = 0, its collect form: a fourth word per query, the threshold, and no lists)
     if (matrix)
         return (size_t)matrix * kMatrixQueries *
-               ((size_t)m.r16 * 32 + 3 * sizeof(float) + (size_t)(block / kWave) * kp * sizeof(uint64_t));
+               ((size_t)m.r16 * 32 + (kp == 0 ? 4 : 3) * sizeof(float) + (size_t)(block / kWave) * kp * sizeof(uint64_t));
     // per query of a group: query image + per-wave candidate lists; per-wave lists of row steps that survive the masks
     // (the two-plane images exist in the G > 1 kernels only: a lone query stages the whole image, its h plane all zero)
     const size_t image = qbits == 8 && group > 1 && planes == 2 ? (size_t)m.r16 * 32 : query_lds_bytes(qbits, m.r16);

@@ -4,6 +4,9 @@
 // Serves unmasked top-k sweeps over TILED 8-bit rows of whole 64-byte steps whose queries carry two digit planes
 // (ScanArgs::planes == 2), with resident norms (ScanArgs::row_norm) and lists in registers (kp <= 64): today the
 // sketch index.  scan_variant (kernels_scan.hip) decides; everything else keeps scan_kernel.
+// With -DSZG_MX_COLLECT the file builds the COLLECT form instead (objects of their own): the same
+// pass over the rows and the same keys, no lists -- every (query, row) pair whose key is at or below the query's
+// threshold is appended to that query's buffer (radius searches through the sketch, scan_radius.cpp).
 //
 // The pass over the rows is mq_score_i8s_kernel's (kernels_mq_i8.hip): one wave per tile of 16 rows; the B operand of
 // a 64-byte step is the row bytes as loaded (lane = chunk * 16 + row holds 16 consecutive elements) xor 0x80808080, the
@@ -109,10 +112,16 @@ constexpr int mx_ring()
 // keys of a (query, row) pair are formed by the same operations as with one block: bit-identical.
 // (the shaped one-block row-list kernels run four waves per SIMD: their bound is 128 registers, said here so that the
 // whole-tile merge cannot cost them that row by a register or two)
-template <int METRIC, int STEPS, bool NT, bool ROWS, int NB = 1>
+// COLLECT: the collect form (radius searches through the sketch).  The tile loop, the operand
+// traffic, the ring, the norms and the key chain are the ones above -- a (query, row) pair gets the same key bit for
+// bit -- but there are no lists: a slot's key is tested against its query's threshold (ScanArgs::thr_ukeys, staged in
+// LDS beside the constants) and the passing rows are appended to that query's buffer, as scan_kernel's collect form
+// does it.  Instantiated with ROWS set (neither list form is alive in it).
+template <int METRIC, int STEPS, bool NT, bool ROWS, int NB = 1, bool COLLECT = false>
 __global__ __launch_bounds__(256, (ROWS && NB == 1 && STEPS != 0) ? 4 : 2) void scan_mx_kernel(const ScanArgs a)
 {
     static_assert(NB == 1 || (NB == 2 && ROWS), "two column blocks: row lists only");
+    static_assert(!COLLECT || ROWS, "the collect form is instantiated once per shape");
     static_assert(16 * NB <= kMatrixWideQueries, "the launch's constants are sized by kMatrixWideQueries");
     constexpr int kQ = kMxQ * NB;  // queries of a group
     constexpr int NS = 4 * NB;     // slots (queries) per lane
@@ -130,8 +139,9 @@ __global__ __launch_bounds__(256, (ROWS && NB == 1 && STEPS != 0) ? 4 : 2) void 
 
     // LDS: the group's image [block] | qscale, qconst, qnorm2 [16 NB] | the wave lists [query of the group][wave][kp]
     uint4 *image = reinterpret_cast<uint4 *>(smem);
+    // (the collect form: | the thresholds' ordered keys [16 NB], and no lists)
     float *qtab = reinterpret_cast<float *>(smem + (size_t)NB * n16 * 16);
-    uint64_t *lists = reinterpret_cast<uint64_t *>(smem + (size_t)NB * n16 * 16 + 3 * kQ * sizeof(float));
+    [[maybe_unused]] uint64_t *lists = reinterpret_cast<uint64_t *>(smem + (size_t)NB * n16 * 16 + 3 * kQ * sizeof(float));
 
     const int trow = lane & 15;
     const int c = lane >> 4;
@@ -164,24 +174,29 @@ __global__ __launch_bounds__(256, (ROWS && NB == 1 && STEPS != 0) ? 4 : 2) void 
         for (int x = 0; x < kQ; x++) {
             const int q = min(qi + x, a.n_queries - 1);  // (block-uniform: scalar loads of the arguments)
             const float qs = a.qscale[q], qc = a.qconst[q], qn = a.qnorm2[q];
+            [[maybe_unused]] uint32_t tk = 0;
+            if constexpr (COLLECT) tk = q < kMaxSweepsPerLaunch ? a.thr_ukeys[q] : a.thr_ukeys_hi[q - kMaxSweepsPerLaunch];
             if (tid == x) {
                 qtab[x] = qs;
                 qtab[kQ + x] = qc;
                 qtab[2 * kQ + x] = qn;
+                if constexpr (COLLECT) reinterpret_cast<uint32_t *>(qtab)[3 * kQ + x] = tk;
             }
         }
         // ROWS: slot 4 b + r of lane-row c is the list of query 16 b + 4 c + r; else one whole-wave list per query (the
         // unused form is dead code: no registers)
         RowList rls[NS];
         WaveList wls[kMxQ];
-        if constexpr (ROWS) {
+        if constexpr (COLLECT) {
+        } else if constexpr (ROWS) {
 #pragma unroll
             for (int r = 0; r < NS; r++) rls[r].init();
         } else {
 #pragma unroll
             for (int x = 0; x < kMxQ; x++) wls[x].init(lists, a.kp, lane);  // (register lists: flushed by hand below)
         }
-        float wk[NS];  // worst_key of this lane's queries (+inf while a list fills)
+        float wk[NS];  // worst_key of this lane's queries (+inf while a list fills); collect: their thresholds
+        [[maybe_unused]] uint32_t tu[NS];  // collect: the thresholds' ordered keys (the exact test)
         bool live[NS];
 #pragma unroll
         for (int r = 0; r < NS; r++) {
@@ -213,7 +228,30 @@ __global__ __launch_bounds__(256, (ROWS && NB == 1 && STEPS != 0) ? 4 : 2) void 
                 any = any || pass[r];
             }
             if (!__ballot(any)) return;
-            if constexpr (ROWS) {
+            if constexpr (COLLECT) {
+                // Behind the tile's one ballot: per slot the exact test, and one ballot whose four 16-lane slices belong
+                // to four different queries (lane-row c of slot r: query 16 (r >> 2) + 4 c + (r & 3)).  The first hit
+                // lane of a slice claims the slice's popcount on its query's counter, every hit lane writes its entry at
+                // base + rank while that is inside the buffer; the counter keeps counting past the cap (the host's
+                // overflow sign).  Rows past n_rows and idle columns never pass the pre-filter (row_ok, live).
+#pragma unroll
+                for (int r = 0; r < NS; r++) {
+                    const uint32_t uk = ordered_key(key[r]);
+                    const bool hit = pass[r] && uk <= tu[r];
+                    const uint64_t b = __ballot(hit);
+                    if (!b) continue;  // (wave-uniform)
+                    const uint32_t slice = (uint32_t)(b >> (16 * c)) & 0xFFFFu;
+                    const uint32_t rank = (uint32_t)__popc(slice & ((1u << trow) - 1u));
+                    const size_t q = (size_t)(qi + (r >> 2) * kMxQ + c * 4 + (r & 3));
+                    uint32_t base = 0;
+                    if (hit && rank == 0) base = atomicAdd(a.collect_count + q * kCandCountStride, (uint32_t)__popc(slice));
+                    base = __shfl(base, slice ? c * 16 + __ffs((int)slice) - 1 : lane);
+                    if (hit) {
+                        const uint32_t idx = base + rank;
+                        if (idx < a.collect_cap) a.collect_buf[q * a.collect_cap + idx] = ((uint64_t)uk << 32) | (uint32_t)row;
+                    }
+                }
+            } else if constexpr (ROWS) {
                 // Rounds: the 16 rows offered to query 4 c + r sit in the 16 lanes of lane-row c, so one round retires
                 // one passing lane of every lane-row and slot -- up to 16 NB inserts, 4 NB independent chains (the slots).
                 // A round retires a lane of every lane-row that still has one: 16 rounds always suffice, and the bound
@@ -277,6 +315,10 @@ __global__ __launch_bounds__(256, (ROWS && NB == 1 && STEPS != 0) ? 4 : 2) void 
                 qsv[r] = qtab[x];
                 qcv[r] = qtab[kQ + x];
                 qnv[r] = qtab[2 * kQ + x];
+                if constexpr (COLLECT) {  // the float pre-filter's threshold takes the place of the lists' worst key
+                    tu[r] = reinterpret_cast<const uint32_t *>(qtab)[3 * kQ + x];
+                    wk[r] = key_from_ordered(tu[r]);
+                }
             }
         };
         const v4i32 *qimg = reinterpret_cast<const v4i32 *>(smem) + lane;
@@ -416,7 +458,8 @@ __global__ __launch_bounds__(256, (ROWS && NB == 1 && STEPS != 0) ? 4 : 2) void 
         }
 
         // block-wide k-select over the waves' lists, query by query
-        if constexpr (ROWS) {
+        if constexpr (COLLECT) {
+        } else if constexpr (ROWS) {
 #pragma unroll
             for (int r = 0; r < NS; r++)
                 if (trow < a.kp)
@@ -426,16 +469,19 @@ __global__ __launch_bounds__(256, (ROWS && NB == 1 && STEPS != 0) ? 4 : 2) void 
             for (int x = 0; x < kMxQ; x++)
                 if (lane < a.kp) lists[((size_t)x * nwaves + wave) * a.kp + lane] = wls[x].mine;
         }
-        __syncthreads();
-        for (int x = 0; x < kQ && qi + x < a.n_queries; x++)  // (block-uniform)
-            block_merge_lists(lists + (size_t)x * nwaves * a.kp, nwaves, a.kp,
-                              a.block_lists + ((size_t)(qi + x) * gridDim.x + blockIdx.x) * a.kp, tid, blockDim.x);
+        if constexpr (!COLLECT) {
+            __syncthreads();
+            for (int x = 0; x < kQ && qi + x < a.n_queries; x++)  // (block-uniform)
+                block_merge_lists(lists + (size_t)x * nwaves * a.kp, nwaves, a.kp,
+                                  a.block_lists + ((size_t)(qi + x) * gridDim.x + blockIdx.x) * a.kp, tid, blockDim.x);
+        }
         // loads and stores share one vmcnt on gfx9: drain the list stores once per group, so that the next group's ring
         // gets counted waits (as scan_kernel does)
         __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
     }
 }
 
+#ifndef SZG_MX_COLLECT
 template <int STEPS>
 hipError_t launch_mx_steps(const ScanArgs &a, bool rows, bool wide, int grid, int block, size_t lds, hipStream_t stream)
 {
@@ -444,11 +490,45 @@ hipError_t launch_mx_steps(const ScanArgs &a, bool rows, bool wide, int grid, in
     else hipLaunchKernelGGL((scan_mx_kernel<SZG_SCAN_METRIC, STEPS, true, false>), dim3(grid), dim3(block), lds, stream, a);
     return hipGetLastError();
 }
+#else
+template <int STEPS>
+hipError_t launch_mxc_steps(const ScanArgs &a, bool wide, int grid, int block, size_t lds, hipStream_t stream)
+{
+    if (wide) hipLaunchKernelGGL((scan_mx_kernel<SZG_SCAN_METRIC, STEPS, true, true, 2, true>), dim3(grid), dim3(block), lds, stream, a);
+    else hipLaunchKernelGGL((scan_mx_kernel<SZG_SCAN_METRIC, STEPS, true, true, 1, true>), dim3(grid), dim3(block), lds, stream, a);
+    return hipGetLastError();
+}
+#endif
 
 }  // namespace
 
 #define SZG_CAT2(a, b) a##b
 #define SZG_CAT(a, b) SZG_CAT2(a, b)
+#ifdef SZG_MX_COLLECT
+// the collect form of ONE metric (objects of their own, -DSZG_MX_COLLECT): v names the form
+hipError_t SZG_CAT(launch_scan_mxc_m, SZG_SCAN_METRIC)(const ScanArgs &a, const ScanVariant &v, int grid, int block, size_t lds,
+                                                     hipStream_t stream)
+{
+    // (scan_variant's conditions, once more: a launch that does not meet them must not reach these kernels)
+    if (!v.matrix || !v.nontemporal || !a.tiled || a.steps == 0 || (int)a.steps * 4 != a.map.r16 || a.planes != 2 ||
+        !a.row_norm || !a.collect || !a.collect_buf || !a.collect_count || a.n_queries < 1 || scan_masked(a) || block < 64 ||
+        block > 256 || block % 64 || lds > 64u * 1024u)
+        return hipErrorInvalidValue;
+    if (v.matrix_steps != matrix_steps_form((int)a.steps)) return hipErrorInvalidValue;
+    // the wide form: a launch of 17 .. kMatrixWideQueries queries (the constants' and thresholds' arrays hold that many)
+    // and exactly the two-block LDS; every other launch holds at most kMaxSweepsPerLaunch
+    const bool wide = v.wide != 0;
+    if (wide && (a.wide == 1 || a.n_queries <= kMatrixQueries || a.n_queries > kMatrixWideQueries)) return hipErrorInvalidValue;
+    if (!wide && a.n_queries > kMaxSweepsPerLaunch) return hipErrorInvalidValue;
+    if (lds != scan_lds_bytes(8, a.map, 0, block, wide ? kMatrixWideQueries : kMatrixQueries, a.planes, wide ? 2 : 1))
+        return hipErrorInvalidValue;
+    switch (v.matrix_steps) {
+    case 12: return launch_mxc_steps<12>(a, wide, grid, block, lds, stream);
+    case 6: return launch_mxc_steps<6>(a, wide, grid, block, lds, stream);
+    default: return launch_mxc_steps<0>(a, wide, grid, block, lds, stream);
+    }
+}
+#else
 // the matrix sweep of ONE metric (one object each, as the scan objects): v names the form (ScanVariant::matrix_steps)
 hipError_t SZG_CAT(launch_scan_mx_m, SZG_SCAN_METRIC)(const ScanArgs &a, const ScanVariant &v, int grid, int block, size_t lds,
                                                     hipStream_t stream)
@@ -475,5 +555,6 @@ hipError_t SZG_CAT(launch_scan_mx_m, SZG_SCAN_METRIC)(const ScanArgs &a, const S
     default: return launch_mx_steps<0>(a, rows, wide, grid, block, lds, stream);
     }
 }
+#endif  // SZG_MX_COLLECT
 
 }  // namespace szg

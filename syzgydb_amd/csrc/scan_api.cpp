@@ -263,7 +263,7 @@ void serve_batch(szg_index *ix, const std::vector<PendingSearch *> &batch, Batch
         if (radius) {
             w.radii.resize(nq);
             for (int i = 0; i < nq; i++) w.radii[i] = batch[i]->radius;
-            rc = search_radius_impl(ix, w.q.data(), nq, w.radii.data(), any ? w.masks.data() : nullptr, &w.hits);
+            rc = search_radius_any(ix, w.q.data(), nq, w.radii.data(), any ? w.masks.data() : nullptr, &w.hits);
             for (int i = 0; i < nq; i++) {
                 PendingSearch *p = batch[i];
                 p->rc = rc ? rc : radius_output(ix, w.hits[i], p->out_rows, p->out_dist, p->capacity, p->out_total);
@@ -416,7 +416,7 @@ int szg_search_radius(szg_index *ix, const double *query, double radius,
     if (!ix->coalesce) {
         SZG_TRY
         std::vector<std::vector<HeapItem>> hits;
-        const int rc = search_radius_impl(ix, query, 1, &radius, allow_bits ? &allow_bits : nullptr, &hits);
+        const int rc = search_radius_any(ix, query, 1, &radius, allow_bits ? &allow_bits : nullptr, &hits);
         if (rc) return rc;
         return radius_output(ix, hits[0], out_rows, out_dist, capacity, out_total);
         SZG_CATCH
@@ -454,7 +454,7 @@ int szg_search_radius_batch(szg_index *ix, const double *queries, int n_queries,
         for (int i = 0; i < n_queries; i++) masks[i] = allow_bits + (size_t)i * words;
     }
     std::vector<std::vector<HeapItem>> hits;
-    const int rc = search_radius_impl(ix, queries, n_queries, radii, allow_bits ? masks.data() : nullptr, &hits);
+    const int rc = search_radius_any(ix, queries, n_queries, radii, allow_bits ? masks.data() : nullptr, &hits);
     if (rc) return rc;
     uint64_t off = 0;
     for (int i = 0; i < n_queries; i++) {
@@ -714,6 +714,46 @@ int szg_debug_scan_wide(int dim, int quant_bits, int n_queries, int kp, int plan
         if (j == 0) {
             *serves = v.wide;
             *lds_bytes = szg::scan_lds_bytes(quant_bits, f.map, kp, g.block, v.group, planes, v.matrix ? (v.wide ? 2 : 1) : 0);
+        }
+        *passes += (n + v.group - 1) / v.group;
+    }
+    return SZG_OK;
+}
+
+// test hook, host only: the matrix sweep's collect form for a collect call of n_queries queries with one sweep each --
+// scan_variant's answer per launch (launches of 32 under sketch_wide = 2 where the two-block form qualifies, else of 16)
+int szg_debug_scan_collect(int dim, int quant_bits, int n_queries, int planes, int norms, int tiled, int masked,
+                           int scan_group, int sketch_matrix, int sketch_wide, int32_t *serves, int32_t *wide,
+                           int32_t *passes, uint64_t *lds_bytes, int32_t *steps_form)
+{
+    if (!serves || !wide || !passes || !lds_bytes || !steps_form) return fail(SZG_E_INVALID, "null argument");
+    if (n_queries < 1) return fail(SZG_E_INVALID, "n_queries out of range");
+    if (planes != 2 && planes != 3) return fail(SZG_E_INVALID, "planes is 2 or 3");
+    if (scan_group != 0 && scan_group != 1 && scan_group != 2 && scan_group != 4)
+        return fail(SZG_E_INVALID, "scan_group is 0, 1, 2 or 4");
+    if (!szg::sketch_matrix_known(sketch_matrix)) return fail(SZG_E_INVALID, "sketch_matrix is 0, 1 or 2");
+    if (!szg::sketch_wide_known(sketch_wide)) return fail(SZG_E_INVALID, "sketch_wide is 0, 1 or 2");
+    RowFormat f;
+    const int rc = row_format(dim, quant_bits, &f);
+    if (rc == SZG_E_UNSUPPORTED) return fail(rc, "dimension too large for the LDS-resident query");
+    if (rc) return rc;
+    const bool is_tiled = f.layout.tiled != 0 && tiled != 0;
+    const LaunchGeom g = scan_geometry(quant_bits, f.map, f.row_bytes, f.layout.tiled != 0, 1u << 22, 256, 0);
+    auto variant = [&](int n) {
+        return szg::scan_variant(quant_bits, f.map, is_tiled, 0, true, masked != 0, szg_index::ring, !szg_index::shape_kernels,
+                                 scan_group, n, g.block, planes, 0, sketch_matrix, norms != 0, 0, sketch_wide);
+    };
+    const int per_launch = sketch_wide == 2 && variant(szg::kMatrixWideQueries).wide ? szg::kMatrixWideQueries : szg::kMaxSweepsPerLaunch;
+    *serves = *wide = *passes = *steps_form = 0;
+    *lds_bytes = 0;
+    for (int j = 0; j < n_queries; j += per_launch) {
+        const int n = std::min(per_launch, n_queries - j);
+        const szg::ScanVariant v = variant(n);
+        if (j == 0) {
+            *serves = v.matrix;
+            *wide = v.wide;
+            *steps_form = v.matrix_steps;
+            *lds_bytes = szg::scan_lds_bytes(quant_bits, f.map, 0, g.block, v.group, planes, v.matrix ? (v.wide ? 2 : 1) : 0);
         }
         *passes += (n + v.group - 1) / v.group;
     }

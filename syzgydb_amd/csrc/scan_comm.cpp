@@ -824,7 +824,7 @@ int szg_search_radius_sharded(szg_index *ix, const double *queries, int n_querie
                 masks.resize(n_queries);
                 for (int i = 0; i < n_queries; i++) masks[i] = allow_bits + (size_t)i * words;
             }
-            lrc = search_radius_impl(ix, queries, n_queries, radii, allow_bits ? masks.data() : nullptr, &hits);
+            lrc = search_radius_any(ix, queries, n_queries, radii, allow_bits ? masks.data() : nullptr, &hits);
         }
         off.assign((size_t)n_queries + 1, 0);
         for (int i = 0; i < n_queries && lrc == SZG_OK; i++) {

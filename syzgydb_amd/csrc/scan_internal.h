@@ -8,7 +8,7 @@
 //                     escalation, exact replay
 //   scan_mq.cpp       shared (multi-query) sweeps on the matrix cores
 //   scan_sketch.cpp   8-bit sketch pre-pass
-//   scan_radius.cpp   radius search (single, batch, coalesced)
+//   scan_radius.cpp   radius search (single, batch, coalesced), and radius searches through the sketch (sketch_radius)
 //   scan_comm.cpp     one-process-per-GPU exchange (RCCL all-gather + merge)
 //   scan_mask.cpp     device-resident filter masks (szg_mask) and the searches that take them
 //   scan_column.cpp   resident metadata columns (szg_column): comparisons against constants that write masks
@@ -441,6 +441,9 @@ struct szg_index {
                               // 1 = never, 2 = every call of more than 16 queries where the shape allows
     int sketch_bulk = 0;      // the row lists' whole-tile merge: 0 = automatic (tiles with szg::kBulkMin passing pairs or more),
                               // 1 = never (rounds only), n >= 2 = tiles with n passing pairs or more
+    int sketch_radius = 0;    // radius queries that would each take a sweep of their own (a lone query, radius_mq = 0) go
+                              // through the sketch where it applies to the handle: 0 = never (the default: the option
+                              // soaks, as the top-k pre-pass did, before a later change makes it automatic), 1 = always
     bool is_sketch = false;   // this index is the internal sketch of a float32 handle: its keys only bound
     int tie_mode = 0;         // 0: exact full replay on ties/NaN, 1: keep the fast answer
     int serialize_scans = 1;  // scan launches of a shard never overlap each other
@@ -684,9 +687,15 @@ int replay_rows_into_heap(szg_index *ix, const double *query, const uint64_t *al
 
 // ---- scan_radius.cpp
 // radius searches for a batch of queries (own radius and filter mask each): results[i] = the hits of query i, ascending
+// (trace_index: the queries' indexes in the caller's call, for the certificate trace of a call made on its behalf)
 int search_radius_impl(szg_index *ix, const double *queries, int n_queries, const double *radii,
                        const uint64_t *const *masks, std::vector<std::vector<HeapItem>> *results,
-                       const szg_mask *const *handles = nullptr);
+                       const szg_mask *const *handles = nullptr, const int *trace_index = nullptr);
+// the one entry of every radius search: through the sketch (option sketch_radius) where the queries would each take a
+// sweep of their own and the sketch applies to the handle, else search_radius_impl
+int search_radius_any(szg_index *ix, const double *queries, int n_queries, const double *radii,
+                      const uint64_t *const *masks, std::vector<std::vector<HeapItem>> *results,
+                      const szg_mask *const *handles = nullptr);
 
 #ifndef SZG_BF16_8BIT_DEFAULT
 #define SZG_BF16_8BIT_DEFAULT 1  // tiled 8-bit rows take the bfloat16 sweep for top-k batches (SZG_BF16_8BIT=0: the int8 sweep)
@@ -710,6 +719,11 @@ int enqueue_collect_mq(szg_index *ix, Shard *sh, Ctx *c, int nq, int nb, bool ha
 
 // ---- scan_sketch.cpp
 bool sketch_applies(const szg_index *ix, int k);
+// ... without the clause on k: float32 rows, the row count rule, the steps aside (radius searches: sketch_radius)
+bool sketch_applies_rows(const szg_index *ix);
+// the sketch index brought up to date under sk_mu, as a search needs it.  Auto mode never turns a working handle into
+// an error: a failed sync gives back what was built and sets sk_nomem (the caller looks at sk_disabled / sk_nomem)
+int sketch_sync_for_search(szg_index *ix);
 // a load / synth: auto mode may try the sketch again (mutations are never concurrent with searches)
 void sketch_rearm(szg_index *ix);
 // test hooks (szg_debug_sketch_info / szg_debug_sketch_rows): the sketch state as it stands, under sk_mu, never a sync

@@ -258,7 +258,7 @@ int szg_search_radius_masked(szg_index *ix, const double *queries, int n_queries
     for (int i = 0; i <= n_queries; i++) out_offsets[i] = 0;
     if (n_queries == 0 || szg_index_rows(ix) == 0) return SZG_OK;
     std::vector<std::vector<HeapItem>> hits;
-    rc = search_radius_impl(ix, queries, n_queries, radii, nullptr, &hits, handles.data());
+    rc = search_radius_any(ix, queries, n_queries, radii, nullptr, &hits, handles.data());
     if (rc) return rc;
     uint64_t off = 0;
     for (int i = 0; i < n_queries; i++) {

@@ -23,6 +23,15 @@ constexpr int kAutoFallbacks = 16;        // eligible queries were handed over t
 
 bool sketch_applies(const szg_index *ix, int k)
 {
+    if (!sketch_applies_rows(ix)) return false;
+    // the sketch sweep must keep its lists short: 8-bit rows pass four times as fast as float32 rows, and with
+    // LDS-resident lists of hundreds (k = 100: 1.35 ms per sweep) the pre-pass is slower than the sweep it replaces
+    const int kk = k + ix->sketch_extra;
+    return kk + std::max(ix->slack_min, kk / 2) <= 96;
+}
+
+bool sketch_applies_rows(const szg_index *ix)
+{
     if (!ix->sketch_on || ix->sk_disabled || ix->bits != 32) return false;
     uint64_t n = 0;
     for (const Shard *sh : ix->shards) n += sh->n_rows;
@@ -33,10 +42,7 @@ bool sketch_applies(const szg_index *ix, int k)
         if (ix->sk_nomem || ix->sk_off_gen.load(std::memory_order_relaxed) == ix->gen) return false;
         min_rows = std::max(min_rows, kAutoMinRows);
     }
-    // the sketch sweep must keep its lists short: 8-bit rows pass four times as fast as float32 rows, and with
-    // LDS-resident lists of hundreds (k = 100: 1.35 ms per sweep) the pre-pass is slower than the sweep it replaces
-    const int kk = k + ix->sketch_extra;
-    return n >= min_rows && kk + std::max(ix->slack_min, kk / 2) <= 96;
+    return n >= min_rows;
 }
 
 void sketch_rearm(szg_index *ix)
@@ -570,27 +576,31 @@ int SketchCall::finish(Batch &b)
     return SZG_OK;
 }
 
+int sketch_sync_for_search(szg_index *ix)
+{
+    // (mutations come under the caller's write lock: after the sync, searches run side by side)
+    std::lock_guard<std::mutex> lk(ix->sk_mu);
+    int rc = sketch_sync(ix);
+    if (rc && ix->sketch_on == 2) {
+        // auto mode never turns a working handle into an error: give back what was built, step aside until the
+        // next load
+        if (ix->sketch) szg_index_destroy(ix->sketch);
+        ix->sketch = nullptr;
+        ix->sk_need_full = true;
+        ix->sk_dirty_rows.clear();
+        ix->sk_nomem = true;
+        for (Shard *sh : ix->shards)
+            if (hipSetDevice(sh->device) == hipSuccess) (void)hipGetLastError();
+        rc = SZG_OK;
+    }
+    return rc;
+}
+
 int search_topk_sketch(szg_index *ix, const double *queries, int n_queries, int k, const uint64_t *allow_bits,
                        uint64_t *out_rows, double *out_dist, int32_t *out_count, const uint64_t *const *allow_ptrs,
                        const szg_mask *const *handles)
 {
-    int rc;
-    {   // (mutations come under the caller's write lock: after the sync, searches run side by side)
-        std::lock_guard<std::mutex> lk(ix->sk_mu);
-        rc = sketch_sync(ix);
-        if (rc && ix->sketch_on == 2) {
-            // auto mode never turns a working handle into an error: give back what was built, step aside until the
-            // next load
-            if (ix->sketch) szg_index_destroy(ix->sketch);
-            ix->sketch = nullptr;
-            ix->sk_need_full = true;
-            ix->sk_dirty_rows.clear();
-            ix->sk_nomem = true;
-            for (Shard *sh : ix->shards)
-                if (hipSetDevice(sh->device) == hipSuccess) (void)hipGetLastError();
-            rc = SZG_OK;
-        }
-    }
+    int rc = sketch_sync_for_search(ix);
     if (rc) return rc;
     if (ix->sk_disabled || ix->sk_nomem)
         return search_topk_impl(ix, queries, n_queries, k, allow_bits, out_rows, out_dist, out_count, allow_ptrs, handles);

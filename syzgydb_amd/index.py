@@ -933,6 +933,22 @@ def scan_wide_plan(dim, quant_bits, n_queries, kp=8, planes=2, norms=True, tiled
     return {"serves": bool(serves.value), "passes": passes.value, "lds_bytes": lds.value}
 
 
+def scan_collect_plan(dim, quant_bits, n_queries, planes=2, norms=True, tiled=True, masked=False, scan_group=0,
+                      sketch_matrix=0, sketch_wide=0):
+    """Host-only test hook: the matrix sweep's collect form (radius searches through the sketch, option sketch_radius)
+    for a collect call of n_queries queries with one sweep each, in launches of up to 16 (32 under sketch_wide = 2 where
+    the two-block form qualifies) -- whether the form serves the first launch, whether that launch scores 32 queries per
+    row read, its LDS bytes and STEPS form, and the passes over the rows of the whole call."""
+    L = _lib.load()
+    serves, wide, passes, lds, form = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32(), ctypes.c_uint64(), ctypes.c_int32()
+    check(L.szg_debug_scan_collect(int(dim), int(quant_bits), int(n_queries), int(planes), int(bool(norms)), int(bool(tiled)),
+                                   int(bool(masked)), int(scan_group), int(sketch_matrix), int(sketch_wide),
+                                   ctypes.byref(serves), ctypes.byref(wide), ctypes.byref(passes), ctypes.byref(lds),
+                                   ctypes.byref(form)), "szg_debug_scan_collect")
+    return {"serves": bool(serves.value), "wide": bool(wide.value), "passes": passes.value, "lds_bytes": lds.value,
+            "steps": form.value}
+
+
 def scan_group_ring_plan(dim, quant_bits, n_queries, kp=10, scan_group=0, scan_group_ring=0):
     """Host-only test hook: the ring depth a one-sweep launch of n_queries queries takes under options scan_group and
     scan_group_ring, and the values of scan_group_ring the library accepts beside 0 (the depths it carries)."""
@@ -958,7 +974,7 @@ def merge_short_plan(n_lists, m, kp):
 def option_check(name, value):
     """Host-only test hook (no device needed): raises SzgError where ScanIndex.set_option would refuse `value` for the
     one-sweep kernel's option `name` (scan_group, scan_group_ring, scan_norms, sketch_planes, sketch_matrix, sketch_select,
-    sketch_wide, sketch_bulk)."""
+    sketch_wide, sketch_bulk, sketch_radius)."""
     L = _lib.load()
     check(L.szg_debug_option_check(name.encode(), int(value)), "szg_debug_option_check")
 
