@@ -8,7 +8,7 @@
 //                     escalation, exact replay
 //   scan_mq.cpp       shared (multi-query) sweeps on the matrix cores
 //   scan_sketch.cpp   8-bit sketch pre-pass
-//   scan_radius.cpp   radius search (single, batch, coalesced), and radius searches through the sketch (sketch_radius)
+//   scan_radius.cpp   radius search (single, batch, coalesced; through the sketch: sketch_radius; collect_plan.h: its buffers)
 //   scan_comm.cpp     one-process-per-GPU exchange (RCCL all-gather + merge)
 //   scan_mask.cpp     device-resident filter masks (szg_mask) and the searches that take them
 //   scan_column.cpp   resident metadata columns (szg_column): comparisons against constants that write masks
@@ -636,6 +636,11 @@ int enqueue_queries(szg_index *ix, Shard *sh, Ctx *c, const double *q, int nq, c
                     bool with_single_form = true, const szg_mask *const *handles = nullptr, size_t shard_no = 0);
 void fill_scan_args(const szg_index *ix, const Shard *sh, const Ctx *c, bool has_allow, int slot, int nq,
                     szg::ScanArgs *a);
+// ... of a collect launch: query slot + j's key threshold thr[j], its buffer buf + j * cap and its counter
+// count[j * szg::kCandCountStride].  dense_vote: masked launches take the dense phase where most rows pass every mask
+// (false: never -- run_collect)
+void fill_collect_args(const szg_index *ix, const Shard *sh, const Ctx *c, bool has_allow, int slot, int nq, const float *thr,
+                       uint64_t *buf, size_t cap, uint32_t *count, bool dense_vote, szg::ScanArgs *a);
 // (after: the stream that goes on once the sweeps are done -- default the work stream; part 1: the early part of a short
 // call, timed with its own event pair)
 int launch_scans_chained(szg_index *ix, Shard *sh, Ctx *c, const std::vector<szg::ScanArgs> &a, const LaunchGeom &g,
@@ -654,7 +659,8 @@ struct RerankOn {
 // entries per wave and block list of a sketch sweep over `grid` blocks (option sketch_list)
 int sketch_list_len(int want, int kp, int grid);
 // does the matrix sweep's two-block form serve an unmasked launch of szg::kMatrixWideQueries queries of sketch index
-// `sk` on shard `sh`, for calls that keep kp candidates per query (scan_variant's answer for that launch)?
+// `sk` on shard `sh`, for calls that keep kp candidates per query (scan_variant's answer for that launch)?  kp = 0: the
+// collect form (radius searches through the sketch; no lists, list_opt is not read)
 bool sketch_wide_serves(const szg_index *sk, const Shard *sh, int kp, int list_opt);
 int enqueue_topk(szg_index *ix, Shard *sh, Ctx *c, int kp, int nq, bool has_allow, const RerankOn *on = nullptr);
 // candidates of staged query `slot` from a finished top-k pass and *lb, the lower bound of the real-number key of every
@@ -925,6 +931,48 @@ int stage_query_forms(szg_index *ix, Batch &b, const double *q, bool int_planes,
 // radius query that overflows the batch's buffers): prepared once, uploaded on every shard's `work` stream;
 // *meta = its constants
 int stage_single_form(szg_index *ix, Batch &b, const double *q, int j, QMeta *meta);
+
+// ---- scan_sketch.cpp: what a call through ix's sketch index -- the top-k pre-pass, a radius search -- fixes up front
+struct SketchPlan {
+    double gs = 0.0;     // Euclidean: sketch distances are in units of gs (the sketch sweeps see q / gs); 0: cosine
+    double slack = 0.0;  // the largest d(row, its sketch) (1 + 1e-9), + the build kernel's angle rounding under cosine
+    int wide = 0;        // the call takes wide batches (32 queries, one launch of the two-block matrix sweep each):
+                         // 1 = under the automatic rule, 2 = forced (option sketch_wide = 2)
+};
+// (kp: what sketch_wide_serves is asked with -- 0: a collect call)
+SketchPlan sketch_call_plan(const szg_index *ix, int n_queries, int kp);
+// the next batch of such a call, from query q0, on the sketch index's contexts
+void sketch_plan_batch(const szg_index *ix, int n_queries, int q0, int wide, Batch *b);
+// float32 shard a's rows without a usable sketch (sk_exc): f(shard-local row, eligible: live and allowed by mask words m)
+template <class F>
+void sketchless_rows(const szg_index *ix, const Shard *a, const uint64_t *m, F &&f)
+{
+    for (uint64_t r : ix->sk_exc) {
+        if (r < a->first || r >= a->first + a->n_rows) continue;
+        const uint64_t l = r - a->first;
+        f(l, ((a->live_host[l >> 6] >> (l & 63)) & 1) && (!m || ((m[r >> 6] >> (r & 63)) & 1)));
+    }
+}
+// the queries such a call hands over (redo, ascending), gathered for ONE call of the full-precision path: their
+// vectors, and their masks in the form the caller's came in (pointers or resident handles; null: none is filtered)
+struct HandedOver {
+    std::vector<double> q;
+    std::vector<const uint64_t *> masks;
+    std::vector<const szg_mask *> handles;
+    bool any = false;
+    HandedOver(const szg_index *ix, const double *queries, const QueryMasks &mask_of, const std::vector<int> &redo)
+        : q(redo.size() * (size_t)ix->dim), masks(redo.size()), handles(mask_of.handles ? redo.size() : 0)
+    {
+        for (size_t i = 0; i < redo.size(); i++) {
+            memcpy(&q[i * ix->dim], queries + (size_t)redo[i] * ix->dim, sizeof(double) * ix->dim);
+            masks[i] = mask_of(redo[i]);
+            if (!handles.empty()) handles[i] = mask_of.handles[redo[i]];
+            any |= masks[i] != nullptr;
+        }
+    }
+    const uint64_t *const *mask_ptrs() const { return handles.empty() && any ? masks.data() : nullptr; }
+    const szg_mask *const *handle_ptrs() const { return !handles.empty() && any ? handles.data() : nullptr; }
+};
 
 // The in-flight loop of a call: plan a batch, borrow its contexts (none free: finish the oldest batch in flight
 // first), stage it, and in the end finish the rest in order.  hand_over (optional): takes every staged batch instead

@@ -6,6 +6,9 @@
 // ONE launch (per-sweep threshold, buffer and counter in ScanArgs), the re-rank reads the hit counters on the
 // device, and up to three batches are in flight per shard -- no launch gap and no host round trip between the sweeps
 // of a batch, which is what a single query per launch per caller used to cost (5.7 of 6.9 TB/s on cfg5's shard).
+// RadiusCall sweeps the handle's own rows, SketchRadiusCall (option sketch_radius) the 8-bit sketch of float32 rows: what
+// a batch is on the device and how it is read back exists once, in the collect core; its arithmetic is collect_plan.h.
+#include "collect_plan.h"
 #include "scan_internal.h"
 
 namespace szgi {
@@ -27,9 +30,7 @@ float radius_key_threshold(const szg_index *ix, double radius, const QMeta &meta
 
 namespace {
 
-constexpr size_t kRadiusCapMin = 1024;      // entries per sweep a batch's buffers start with
-constexpr size_t kRadiusCapMax = 1u << 20;  // beyond this a query goes through run_collect on its own
-constexpr size_t kRadiusBlockCopyBytes = 2u << 20;  // a batch's re-ranked hits travel as one block up to this size
+static_assert(sizeof(szg::RerankOut) == kCollectEntryBytes, "collect_plan.h sizes the hit buffers in entries of this size");
 
 // consider()'s radius branch (collection.go:598-605) over the candidates in visit order -- every record with
 // distance <= Radius is pushed onto the max-heap -- then the pop loop (:694-697).  Popping a heap of pairwise
@@ -54,12 +55,191 @@ void radius_assemble(std::vector<HeapItem> &cs, bool presorted, std::vector<Heap
     h.drain(out);
 }
 
-struct RadiusBatch : Batch {
-    std::vector<float> thr;        // key threshold per query (of the sweep that runs: shared or one per query)
-    std::vector<float> thr_single; // ... of the single-query collect sweep (a query that overflows is swept again on its own)
-    std::vector<size_t> cap;       // per shard: entries per sweep of this batch's buffers
-    std::vector<uint8_t> copied;   // per shard: the block of re-ranked hits was copied back at enqueue time
-    std::vector<QMeta> meta;       // certificate trace only: each query's constants with the flags of the sweep that runs
+// ---- the collect core: one batch of collect sweeps on the device and back -----------------------------------------------
+// Per shard a batch holds nq buffers of cap entries in d_collect (the sweeps append row and key), the same in d_out (the
+// re-rank's float64 distances, sorted per query) and one counter per query in d_count.  The callers differ in which
+// index is swept, how the counters start and which launches make the sweeps; everything else is here.
+
+constexpr uint32_t kNoKeyUkey = 0xFFFFFFFFu;  // "ordered key" of the entries staged ahead of the sweep: a sweep's keys
+                                              // are clamped to 3e38, so none of them orders that high
+
+struct CollectBatch : Batch {
+    std::vector<float> thr;       // key threshold per query, of the sweep that runs
+    std::vector<size_t> cap;      // per shard: entries per query of this batch's buffers
+    std::vector<uint8_t> copied;  // per shard: the block of re-ranked hits was copied back at enqueue time
+    std::vector<QMeta> meta;      // each query's constants with the flags of the sweep that runs (float32 path: traced calls only)
+    void size() { thr.assign(nq, 0.0f), cap.assign(ctx.size(), 0), copied.assign(ctx.size(), 0); }  // (once planned)
+};
+
+// the buffers of batch t on shard s: cap follows the largest hit count the context has seen (collect_cap has the rules)
+int collect_buffers(CollectBatch &t, size_t s, bool limited, size_t head_max)
+{
+    Ctx *c = t.ctx[s];
+    const size_t cap = t.cap[s] = collect_cap(c->radius_cap, t.nq, limited, head_max);
+    const size_t n = collect_block_entries(cap, t.nq);
+    // (small buffers -- the usual hundreds of hits per query: the whole block follows the sweeps, finish() needs one wait)
+    t.copied[s] = collect_block_copied(cap, t.nq);
+    int rc = c->d_collect.ensure(n);
+    if (rc == SZG_OK) rc = c->d_out.ensure(n);
+    if (rc == SZG_OK && t.copied[s]) rc = c->h_out.ensure(n);
+    return rc;
+}
+
+// collect launches of up to qpl sweeps for queries [q0, q1) of the batch, back to back on the shard's scan chain; `after`
+// goes on once they are done.  wide: the call takes wide batches -- its launches take the matrix sweep whatever their
+// count, as top-k's; norms: the shard's resident row norms for the launches that read them (null: none does)
+int collect_sweeps(szg_index *ix, Shard *sh, Ctx *c, const CollectBatch &t, size_t cap, int q0, int q1, int qpl,
+                   hipStream_t after, int part, bool wide = false, const float *norms = nullptr)
+{
+    const LaunchGeom g = scan_geometry(ix, sh, 0);
+    std::vector<szg::ScanArgs> a((q1 - q0 + qpl - 1) / qpl);
+    for (int j0 = q0; j0 < q1; j0 += qpl) {
+        szg::ScanArgs &x = a[(j0 - q0) / qpl];
+        fill_collect_args(ix, sh, c, t.any_mask, j0, std::min(qpl, q1 - j0), &t.thr[j0], c->d_collect + (size_t)j0 * cap, cap,
+                          c->d_count + (size_t)j0 * szg::kCandCountStride, true, &x);
+        if (wide && x.matrix == 0) x.matrix = 2;
+        if (norms && szg::scan_wants_norms(ix->bits, x, g.block)) x.row_norm = norms;
+    }
+    return launch_scans_chained(ix, sh, c, a, g, after, part);
+}
+
+// the device tail of queries [q0, q1) on stream tl: the float64 distances of what was collected -- on the rows of shard
+// `rows` of index `on`: the sweep's own, or the float32 shard a sketch shard stands for --, the counts staying on the
+// device; each query's hits sorted by distance there too (lists of up to kSortHitsMax: the host only filters); the
+// counters and, where the block is small, the hits on their way back
+int collect_tail(const szg_index *on, const Shard *rows, Ctx *c, const CollectBatch &t, size_t s, int q0, int q1, hipStream_t tl)
+{
+    const uint32_t stride = szg::kCandCountStride;
+    const size_t cap = t.cap[s];
+    const int nqp = q1 - q0;
+    uint32_t *count = c->d_count + (size_t)q0 * stride;
+    szg::RerankOut *out = c->d_out + (size_t)q0 * cap;
+    HIPCHK(szg::launch_rerank(on->bits, on->metric, rows->rows, on->layout, on->dim, c->d_q64 + (size_t)q0 * on->dim,
+                              c->d_collect + (size_t)q0 * cap, count, (uint32_t)cap, nqp, out, tl, stride));
+    HIPCHK(szg::launch_sort_hits(out, count, stride, (uint32_t)cap, nqp, tl));
+    HIPCHK(hipMemcpyAsync(c->h_count + (size_t)q0 * stride, count, sizeof(uint32_t) * (size_t)nqp * stride, hipMemcpyDeviceToHost, tl));
+    if (t.copied[s])
+        HIPCHK(hipMemcpyAsync(c->h_out + (size_t)q0 * cap, out, collect_block_entries(cap, nqp) * sizeof(szg::RerankOut),
+                              hipMemcpyDeviceToHost, tl));
+    return SZG_OK;
+}
+
+// what finish() reads off a batch, per query
+struct Collected {
+    std::vector<std::vector<HeapItem>> cands;         // the hits proper: `distance <= Radius` (collection.go:598) applied here
+    std::vector<uint8_t> over;                        // more candidates on some shard than the batch's buffers hold
+    std::vector<uint8_t> presorted;                   // the query's hits come from ONE shard's device-sorted list
+    std::vector<std::vector<szg_cert_entry>> traced;  // traced calls: every collected entry, before the predicate
+    std::vector<uint8_t> untraced;                    // the query's record will not fit the trace: nothing is gathered
+    double t_wait = 0;                                // of the time spent gathering: waiting for the device
+    const bool tracing;
+    Collected(int nq, bool tr) : cands(nq), over(nq, 0), presorted(nq, 1), traced(tr ? nq : 0), untraced(tr ? nq : 0, 0), tracing(tr) {}
+};
+
+// Wait for batch t shard by shard and gather its queries' hits.  ix: the handle the call was made on (row numbers, the
+// trace); swept: the index whose contexts ran the sweeps and whose key_eps bounds their keys (ix, or its sketch index);
+// handed: null, or per query "collected nothing by design"; exc: null, or sorted rows whose swept entries mean nothing --
+// only an entry staged ahead of the sweep (kNoKeyUkey) counts for them.  A failure leaves the contexts to the caller.
+int collect_gather(szg_index *ix, szg_index *swept, const CollectBatch &t, const double *radii, const uint8_t *handed,
+                   const std::vector<uint64_t> *exc, Collected *out)
+{
+    const bool tracing = out->tracing;
+    std::vector<uint8_t> lists(t.nq, 0);
+    CollectLayout at;
+    for (size_t s = 0; s < t.ctx.size(); s++) {
+        Ctx *c = t.ctx[s];
+        if (!c) continue;
+        const Shard *sh = ix->shards[s];
+        const double tw = now_us();
+        hipError_t e = hipSetDevice(sh->device);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->pass.work);
+        // (a short call's early part ran its tail on the context's own stream)
+        if (e == hipSuccess && c->pass.early_n > 0 && c->pass.early_n < t.nq) e = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess) return fail(SZG_E_DEVICE, "hipStreamSynchronize", e);
+        int rc = finish_timing(swept, c);
+        if (rc) return rc;
+        const size_t cap = t.cap[s];
+        collect_layout(c->h_count, szg::kCandCountStride, t.nq, cap, t.copied[s] != 0, &at);
+        // the next batch on this context starts with room for what this one saw (and shrinks again slowly)
+        c->radius_cap = collect_next_cap(c->radius_cap, at.most);
+        if (!t.copied[s] && at.host_entries) {
+            // exact-size copies of each query's re-ranked hits, back to back in the pinned buffer
+            rc = c->h_out.ensure(at.host_entries);
+            if (rc) return rc;
+            for (int j = 0; j < t.nq && e == hipSuccess; j++)
+                if (at.cnt[j])
+                    e = hipMemcpyAsync(c->h_out + at.off[j], c->d_out + (size_t)j * cap, at.cnt[j] * sizeof(szg::RerankOut),
+                                       hipMemcpyDeviceToHost, c->pass.work);
+            if (e == hipSuccess) e = hipStreamSynchronize(c->pass.work);
+            if (e != hipSuccess) return fail(SZG_E_DEVICE, "hipMemcpyAsync(radius hits)", e);
+        }
+        out->t_wait += now_us() - tw;
+        for (int j = 0; j < t.nq; j++) {
+            if (at.over[j]) out->over[j] = 1;
+            if (out->over[j] || (handed && handed[j])) continue;
+            const size_t cnt = at.cnt[j];
+            std::vector<HeapItem> &cands = out->cands[j];
+            cands.reserve(cands.size() + cnt);
+            if (cnt && (cnt > (size_t)szg::kSortHitsMax || ++lists[j] > 1)) out->presorted[j] = 0;
+            const double rad = radii[t.first + j];
+            if (tracing && !out->untraced[j] && !cert_room(ix, out->traced[j].size() + cnt)) {
+                out->untraced[j] = 1;
+                std::vector<szg_cert_entry>().swap(out->traced[j]);
+            }
+            const bool keep = tracing && !out->untraced[j];
+            for (size_t i = at.off[j]; i < at.off[j] + cnt; i++) {
+                const szg::RerankOut &r = c->h_out[i];
+                const uint64_t row = sh->first + r.row;
+                const bool no_key = r.ukey == kNoKeyUkey;
+                // (the bytes that stand in a sketch shard for a row without a usable sketch mean nothing: should the
+                // sweep collect such a row, the staged entry is the one that counts)
+                if (exc && !no_key && std::binary_search(exc->begin(), exc->end(), row)) continue;
+                if (r.dist <= rad) cands.push_back(HeapItem{row, r.dist});  // (a NaN distance is never a hit)
+                if (!keep) continue;
+                if (no_key) {
+                    out->traced[j].push_back(szg_cert_entry{row, r.dist, 0.0, 0.0f, SZG_CERT_ENTRY_NO_KEY});
+                } else {
+                    const float key = szg::key_from_ordered(r.ukey);
+                    out->traced[j].push_back(szg_cert_entry{row, r.dist, (double)key + key_eps(swept, key, t.meta[j]), key, 0u});
+                }
+            }
+        }
+    }
+    return SZG_OK;
+}
+
+// the certificate record of query j of batch t: what was collected for it on every shard, under its sweep's threshold
+void collect_record(szg_index *ix, const szg_index *swept, const CollectBatch &t, int j, int traced_as, int pass, int keys,
+                    int sweep, double D, double slack, const std::vector<szg_cert_entry> &entries)
+{
+    szg_cert_record rec = cert_record(traced_as, pass);
+    rec.keys = keys;
+    rec.sweep = sweep;
+    for (const Shard *sh : ix->shards) rec.row_hi = std::max<uint64_t>(rec.row_hi, sh->first + sh->n_rows);
+    rec.thr = (double)t.thr[j];
+    rec.eps = key_eps(swept, t.thr[j], t.meta[j]);
+    rec.D = D;
+    rec.slack = slack;
+    cert_emit(ix, rec, entries);
+}
+
+// the one end of finish(): the contexts go back -- drained first after a failure --, and under the stats lock the host's
+// share of the time is noted and, after a success, count(stats) bumps the caller's counters
+template <class Count>
+int collect_end(szg_index *ix, CollectBatch &t, int rc, double t0, double t_wait, Count &&count)
+{
+    if (rc) t.drain();
+    else t.release();
+    std::lock_guard<std::mutex> lk(ix->stats_mu);
+    ix->stats.host_finish_us += now_us() - t0 - t_wait;
+    if (rc == SZG_OK) count(ix->stats);
+    return rc;
+}
+
+// ---- radius searches on the handle's own rows ------------------------------------------------------------------------------
+
+struct RadiusBatch : CollectBatch {
+    std::vector<float> thr_single;  // threshold of the single-query collect sweep (a query that overflows is swept again on its own)
 };
 
 struct RadiusCall {
@@ -92,9 +272,7 @@ RadiusBatch RadiusCall::plan(int q0)
     // the next batch's sweeps
     const int edge = std::min(qpl, kFirstBatch);
     plan_batch(ix, n_queries, q0, nb, BatchRules{qpl, edge, edge, false, true}, &t);
-    t.cap.assign(n_sh, 0);
-    t.copied.assign(n_sh, 0);
-    t.thr.assign(t.nq, 0.0f);
+    t.size();
     t.thr_single.assign(t.nq, 0.0f);
     return t;
 }
@@ -104,62 +282,20 @@ int RadiusCall::enqueue_shard(RadiusBatch &t, size_t s)
     Shard *sh = ix->shards[s];
     Ctx *c = t.ctx[s];
     HIPCHK(hipSetDevice(sh->device));
-    // buffers: t.nq sweeps x cap entries; cap follows the largest hit count this context has seen
-    size_t cap = std::max(kRadiusCapMin, c->radius_cap);
-    // (a shared sweep's batch is up to 96 queries: keep its buffers within 8M entries; a query with more hits than
+    // (a shared sweep's batch is up to 96 queries: its buffers keep within the batch limit; a query with more hits than
     // its share is swept again on its own)
-    if (t.nb > 0) cap = std::min(cap, std::max(kRadiusCapMin, ((size_t)8 << 20) / (size_t)t.nq));
-    t.cap[s] = cap;
-    int rc = c->d_collect.ensure(cap * (size_t)t.nq);
-    if (rc) return rc;
-    rc = c->d_out.ensure(cap * (size_t)t.nq);
+    int rc = collect_buffers(t, s, t.nb > 0, 0);
     if (rc) return rc;
     HIPCHK(hipMemsetAsync(c->d_count, 0, sizeof(uint32_t) * (size_t)t.nq * szg::kCandCountStride, c->pass.work));
     HIPCHK(hipEventRecord(c->ev_up, c->pass.work));  // the sweeps must see the queries, the masks and the zeroed counters
     if (t.nb > 0) {  // one shared sweep for the whole batch
-        rc = enqueue_collect_mq(ix, sh, c, t.nq, t.nb, t.any_mask, t.thr.data(), cap);
-        if (rc) return rc;
+        rc = enqueue_collect_mq(ix, sh, c, t.nq, t.nb, t.any_mask, t.thr.data(), t.cap[s]);
+    } else {  // launches of <= 16 sweeps, back to back
+        const int qpl = std::max(1, std::min(ix->queries_per_launch, szg::kMaxSweepsPerLaunch));
+        rc = collect_sweeps(ix, sh, c, t, t.cap[s], 0, t.nq, qpl, c->pass.work, 0);
     }
-    const int qpl = std::max(1, std::min(ix->queries_per_launch, szg::kMaxSweepsPerLaunch));
-    std::vector<szg::ScanArgs> a(t.nb > 0 ? 0 : (t.nq + qpl - 1) / qpl);
-    for (int j0 = 0; j0 < t.nq && t.nb == 0; j0 += qpl) {  // launches of <= 16 sweeps, back to back
-        szg::ScanArgs &x = a[j0 / qpl];
-        const int m = std::min(qpl, t.nq - j0);
-        fill_scan_args(ix, sh, c, t.any_mask, j0, m, &x);
-        x.collect = 1;
-        for (int j = 0; j < m; j++) x.thr_ukeys[j] = szg::ordered_key(t.thr[j0 + j]);
-        x.collect_buf = c->d_collect + (size_t)j0 * cap;
-        x.collect_cap = (uint32_t)cap;
-        x.collect_count = c->d_count + (size_t)j0 * szg::kCandCountStride;
-        if ((t.any_mask || sh->has_dead) && ix->mask_dense) {  // most rows pass: read every row, masks at the row finish
-            double lowest = 1.0;
-            for (int j = 0; j < m; j++) lowest = std::min(lowest, mask_pass_rate(sh, c, t.any_mask, j0 + j));
-            x.mask_dense = lowest >= 0.5 ? 1 : 0;
-        }
-    }
-    if (t.nb == 0) {
-        rc = launch_scans_chained(ix, sh, c, a, scan_geometry(ix, sh, 0));
-        if (rc) return rc;
-    }
-    // float64 distances of the hits: the counts stay on the device
-    HIPCHK(szg::launch_rerank(ix->bits, ix->metric, sh->rows, ix->layout, ix->dim, c->d_q64, c->d_collect, c->d_count,
-                              (uint32_t)cap, t.nq, c->d_out, c->pass.work, szg::kCandCountStride));
-    // ... and each query's hits sorted by distance there too (lists of up to kSortHitsMax: the host only filters)
-    HIPCHK(szg::launch_sort_hits(c->d_out, c->d_count, szg::kCandCountStride, (uint32_t)cap, t.nq, c->pass.work));
-    HIPCHK(hipMemcpyAsync(c->h_count, c->d_count, sizeof(uint32_t) * (size_t)t.nq * szg::kCandCountStride, hipMemcpyDeviceToHost,
-                          c->pass.work));
-    // the re-ranked hits: while the batch's buffers are small (the usual hundreds of hits per query) the whole block
-    // follows in ONE copy right here -- finish() then needs a single wait; larger ones are copied hit list by hit
-    // list once the counts are known
-    // (a shared sweep's batch of up to 96 queries: a copy call per hit list costs more than 64 KiB of transfer each)
-    t.copied[s] = cap * (size_t)t.nq * sizeof(szg::RerankOut) <= std::max(kRadiusBlockCopyBytes, (size_t)t.nq * (64u << 10));
-    if (t.copied[s]) {
-        rc = c->h_out.ensure(cap * (size_t)t.nq);
-        if (rc) return rc;
-        HIPCHK(hipMemcpyAsync(c->h_out, c->d_out, cap * (size_t)t.nq * sizeof(szg::RerankOut), hipMemcpyDeviceToHost,
-                              c->pass.work));
-    }
-    return SZG_OK;
+    if (rc) return rc;
+    return collect_tail(ix, sh, c, t, s, 0, t.nq, c->pass.work);
 }
 
 int RadiusCall::stage(RadiusBatch &t)
@@ -200,80 +336,13 @@ int RadiusCall::finish(RadiusBatch &t)
         t.drain();
         return SZG_OK;
     }
-    int rc = SZG_OK;
-    std::vector<std::vector<HeapItem>> cands(t.nq);  // the hits proper: `distance <= Radius` (collection.go:598) applied here
-    std::vector<uint8_t> redo(t.nq, 0);  // more hits than the batch's buffers hold: the query is swept again on its own
-    std::vector<uint8_t> presorted(t.nq, 1);  // the query's hits come from ONE shard's device-sorted list
-    std::vector<uint8_t> lists(t.nq, 0);
-    std::vector<std::vector<szg_cert_entry>> traced(tracing ? t.nq : 0);  // every collected hit, before the predicate
-    std::vector<uint8_t> untraced(tracing ? t.nq : 0, 0);  // the query's record will not fit the trace: nothing is gathered
-    double t_wait = 0;
     const double t0 = now_us();
-    for (size_t s = 0; s < n_sh && rc == SZG_OK; s++) {
-        Ctx *c = t.ctx[s];
-        if (!c) continue;
-        Shard *sh = ix->shards[s];
-        const double tw = now_us();
-        hipError_t e = hipSetDevice(sh->device);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->pass.work);
-        if (e != hipSuccess) return fail(SZG_E_DEVICE, "hipStreamSynchronize", e);
-        rc = finish_timing(ix, c);
-        if (rc) break;
-        const size_t cap = t.cap[s];
-        size_t most = 0;
-        std::vector<size_t> cnt(t.nq, 0), off(t.nq + 1, 0);
-        for (int j = 0; j < t.nq; j++) {
-            const size_t n = c->h_count[(size_t)j * szg::kCandCountStride];
-            most = std::max(most, n);
-            if (n > cap) redo[j] = 1;
-            cnt[j] = n > cap ? 0 : n;
-            off[j + 1] = off[j] + cnt[j];
-        }
-        // the next batch on this context starts with room for what this one saw (and shrinks again slowly)
-        size_t want = kRadiusCapMin;
-        while (want < most + most / 4 && want < kRadiusCapMax) want <<= 1;
-        c->radius_cap = std::max(want, c->radius_cap - c->radius_cap / 8);
-        if (t.copied[s]) {  // hits of sweep j at h_out + j * cap
-            for (int j = 0; j < t.nq; j++) off[j] = (size_t)j * cap;
-        } else if (off[t.nq]) {
-            // exact-size copies of each sweep's re-ranked hits, back to back in the pinned buffer
-            rc = c->h_out.ensure(off[t.nq]);
-            if (rc) break;
-            for (int j = 0; j < t.nq; j++) {
-                if (!cnt[j]) continue;
-                e = hipMemcpyAsync(c->h_out + off[j], c->d_out + (size_t)j * cap, cnt[j] * sizeof(szg::RerankOut),
-                                   hipMemcpyDeviceToHost, c->pass.work);
-                if (e != hipSuccess) return fail(SZG_E_DEVICE, "hipMemcpyAsync(radius hits)", e);
-            }
-            e = hipStreamSynchronize(c->pass.work);
-            if (e != hipSuccess) return fail(SZG_E_DEVICE, "hipStreamSynchronize", e);
-        }
-        t_wait += now_us() - tw;
-        for (int j = 0; j < t.nq; j++) {
-            if (redo[j]) continue;
-            cands[j].reserve(cands[j].size() + cnt[j]);
-            if (cnt[j]) {
-                if (cnt[j] > (size_t)szg::kSortHitsMax || ++lists[j] > 1) presorted[j] = 0;
-            }
-            const double rad = radii[t.first + j];
-            if (tracing && !untraced[j] && !cert_room(ix, traced[j].size() + cnt[j])) {
-                untraced[j] = 1;
-                std::vector<szg_cert_entry>().swap(traced[j]);
-            }
-            const bool keep = tracing && !untraced[j];
-            for (size_t i = off[j]; i < off[j] + cnt[j]; i++) {
-                const szg::RerankOut &r = c->h_out[i];
-                if (r.dist <= rad) cands[j].push_back(HeapItem{sh->first + r.row, r.dist});
-                if (keep) {
-                    const float key = szg::key_from_ordered(r.ukey);
-                    traced[j].push_back(szg_cert_entry{sh->first + r.row, r.dist, (double)key + key_eps(ix, key, t.meta[j]), key, 0u});
-                }
-            }
-        }
-    }
+    Collected got(t.nq, tracing);
+    int rc = collect_gather(ix, ix, t, radii, nullptr, nullptr, &got);
     for (int j = 0; j < t.nq && rc == SZG_OK; j++) {
-        if (redo[j]) {
-            cands[j].clear();
+        std::vector<HeapItem> &cands = got.cands[j];
+        if (got.over[j]) {  // more hits than the batch's buffers hold: the query is swept again on its own
+            cands.clear();
             std::vector<Cand> all;
             const double tw = now_us();
             if (t.nb > 0) {  // the single-query form of this query, now that it is needed
@@ -286,29 +355,19 @@ int RadiusCall::finish(RadiusBatch &t)
                 const CertTag tag{traced_as(t.first + j), SZG_CERT_RADIUS_SINGLE};
                 rc = run_collect(ix, ix->shards[s], t.ctx[s], j, t.thr_single[j], t.any_mask, &all, tracing ? &tag : nullptr);
             }
-            t_wait += now_us() - tw;
+            got.t_wait += now_us() - tw;
             if (rc) break;
             const double rad = radii[t.first + j];
             for (const Cand &c : all)
-                if (c.dist <= rad) cands[j].push_back(HeapItem{c.row, c.dist});
-            presorted[j] = 0;
-        } else if (tracing && !untraced[j]) {
-            szg_cert_record rec = cert_record(traced_as(t.first + j), t.nb > 0 ? SZG_CERT_RADIUS_SHARED : SZG_CERT_RADIUS_SINGLE);
-            rec.sweep = t.nb == 0 ? 0 : (t.meta[j].mq_bf16 ? 2 : 1);
-            for (const Shard *sh : ix->shards) rec.row_hi = std::max<uint64_t>(rec.row_hi, sh->first + sh->n_rows);
-            rec.thr = (double)t.thr[j];
-            rec.eps = key_eps(ix, t.thr[j], t.meta[j]);
-            cert_emit(ix, rec, traced[j]);
+                if (c.dist <= rad) cands.push_back(HeapItem{c.row, c.dist});
+            got.presorted[j] = 0;
+        } else if (tracing && !got.untraced[j]) {
+            collect_record(ix, ix, t, j, traced_as(t.first + j), t.nb > 0 ? SZG_CERT_RADIUS_SHARED : SZG_CERT_RADIUS_SINGLE, -1,
+                           t.nb == 0 ? 0 : (t.meta[j].mq_bf16 ? 2 : 1), NAN, NAN, got.traced[j]);
         }
-        radius_assemble(cands[j], presorted[j] != 0, &(*results)[t.first + j]);
+        radius_assemble(cands, got.presorted[j] != 0, &(*results)[t.first + j]);
     }
-    {
-        std::lock_guard<std::mutex> lk(ix->stats_mu);
-        ix->stats.host_finish_us += now_us() - t0 - t_wait;
-        if (rc == SZG_OK) ix->stats.queries += t.nq;
-    }
-    t.release();
-    return rc;
+    return collect_end(ix, t, rc, t0, got.t_wait, [&](szg_stats &st) { st.queries += t.nq; });
 }
 
 // ---- radius searches through the 8-bit sketch (option sketch_radius) --------------------------
@@ -324,35 +383,18 @@ int RadiusCall::finish(RadiusBatch &t)
 //
 // So a collect sweep of the sketch at the widened radius finds every hit; the float64 re-rank on the float32 rows and
 // the host's `dist <= radius` apply the reference's own predicate.  No answer-dependent certificate, no escalation, no
-// drop bound.  The batch is RadiusBatch-shaped, on the sketch index's contexts and in the sketch pre-pass's batch plan
-// (SketchCall::plan); launches of three queries or more without masks or tombstones share each row read on the matrix
-// cores (kernels_scan_mx.hip, the collect form), the others keep scan_kernel's collect form: a quarter of the bytes
-// either way.  Rows without a usable sketch (sk_exc) are staged as the head of each query's collect buffer, the
-// counter starting at their count.  A zero query under cosine, a non-finite query or radius, D >= 1 under cosine and a
-// query whose candidates overflow the batch's buffers are handed to search_radius_impl, all of a call as ONE call.
+// drop bound.  The batch is a collect batch like RadiusCall's, on the sketch index's contexts and in the sketch
+// pre-pass's call and batch plan (sketch_call_plan, sketch_plan_batch); launches of three queries or more without masks
+// or tombstones share each row read on the matrix cores (kernels_scan_mx.hip, the collect form), the others keep
+// scan_kernel's collect form: a quarter of the bytes either way.  Rows without a usable sketch (sk_exc) are staged as
+// the head of each query's collect buffer, the counter starting at their count.  A zero query under cosine, a
+// non-finite query or radius, D >= 1 under cosine and a query whose candidates overflow the batch's buffers are handed
+// to search_radius_impl, all of a call as ONE call.
 
-constexpr uint32_t kNoKeyUkey = 0xFFFFFFFFu;  // "ordered key" of the entries staged ahead of the sweep: a sweep's keys
-                                              // are clamped to 3e38, so none of them orders that high
-
-struct SketchRadiusBatch : Batch {
-    std::vector<float> thr;       // the sketch sweep's key threshold per query
+struct SketchRadiusBatch : CollectBatch {
     std::vector<double> D;        // the sketch-distance radius per query (real units)
     std::vector<uint8_t> handed;  // handed over before any sweep (its slot collects nothing)
-    std::vector<QMeta> meta;      // the queries' constants on the sketch index
-    std::vector<size_t> cap;      // per shard: entries per query of this batch's buffers
-    std::vector<uint8_t> copied;  // per shard: the block of re-ranked hits was copied back at enqueue time
 };
-
-// does the matrix sweep's two-block collect form serve an unmasked launch of 32 queries of sketch index sk on shard sh?
-bool collect_wide_serves(const szg_index *sk, const Shard *sh)
-{
-    if (sk->sketch_wide == 1 || sh->has_dead) return false;
-    const LaunchGeom g = scan_geometry(sk, sh, 0);
-    return szg::scan_variant(sk->bits, sk->map, sk->layout.tiled != 0, 0, true, false, sk->ring, !sk->shape_kernels,
-                             sk->scan_group, szg::kMatrixWideQueries, g.block, scan_planes(sk), sk->scan_group_ring,
-                             sk->sketch_matrix, true, sk->sketch_select, sk->sketch_wide)
-               .wide != 0;
-}
 
 struct SketchRadiusCall {
     szg_index *ix;  // the float32 handle (rows, masks, results, trace)
@@ -363,10 +405,8 @@ struct SketchRadiusCall {
     QueryMasks mask_of;
     std::vector<std::vector<HeapItem>> *results;
     std::vector<int> redo;  // queries handed over to search_radius_impl, ascending
-    size_t n_sh = 0;
     bool tracing = false;
-    double gs = 0.0, slack = 0.0;
-    int wide = 0;  // as SketchCall::wide
+    SketchPlan p;  // gs, slack and whether the call takes wide batches: as the top-k pre-pass's
     std::vector<double> q_sk;
 
     int run();
@@ -378,45 +418,20 @@ struct SketchRadiusCall {
 
 int SketchRadiusCall::run()
 {
-    n_sh = ix->shards.size();
     tracing = cert_tracing(ix);
-    gs = ix->sk_gscale;
-    // slack exactly as SketchCall::run forms it: max_ang (1 + 1e-9), plus the build kernel's angle rounding under cosine
-    const double ang_round = std::max(1e-7, 2.0 * std::sqrt((ix->dim + 8) * 0x1p-52) / M_PI);
-    slack = ix->sk_max_ang * (1.0 + 1e-9) + (gs > 0.0 ? 0.0 : ang_round);
+    p = sketch_call_plan(ix, n_queries, 0);
     sk->timing = ix->timing;
-    wide = 0;
-    if (sk->sketch_wide != 1 && n_queries > szg::kMatrixQueries) {
-        bool serves = true, any = false;
-        for (size_t s = 0; s < n_sh && serves; s++) {
-            if (sk->shards[s]->n_rows == 0) continue;
-            any = true;
-            serves = collect_wide_serves(sk, sk->shards[s]);
-        }
-        if (serves && any) {
-            if (sk->sketch_wide == 2) wide = 2;
-            else if (n_queries >= kWideCallMin && ix->query_batch == 16 && sk->queries_per_launch == 16) wide = 1;
-        }
-    }
     return run_batches<SketchRadiusBatch>(*this);
 }
 
 SketchRadiusBatch SketchRadiusCall::plan(int q0)
 {
     SketchRadiusBatch t;
-    const int batch = std::max(1, std::min(ix->query_batch, kMaxBatch));
-    if (wide == 2)
-        plan_batch(sk, n_queries, q0, 0, BatchRules{szg::kMatrixWideQueries, n_queries, szg::kMatrixWideQueries, false, false}, &t);
-    else if (wide)
-        plan_batch(sk, n_queries, q0, 0, BatchRules{szg::kMatrixWideQueries, kFirstBatch, std::min(kShortCall, kMaxBatch), true, false}, &t);
-    else
-        plan_batch(sk, n_queries, q0, 0, BatchRules{batch, kFirstBatch, std::min(kShortCall, kMaxBatch), true, false}, &t);
-    t.thr.assign(t.nq, 0.0f);
+    sketch_plan_batch(ix, n_queries, q0, p.wide, &t);
+    t.size();
     t.D.assign(t.nq, 0.0);
     t.handed.assign(t.nq, 0);
     t.meta.assign(t.nq, QMeta{});
-    t.cap.assign(n_sh, 0);
-    t.copied.assign(n_sh, 0);
     return t;
 }
 
@@ -424,6 +439,7 @@ int SketchRadiusCall::stage(SketchRadiusBatch &t)
 {
     const double t0 = now_us();
     const int dim = ix->dim;
+    const double gs = p.gs;
     const double *q = queries + (size_t)t.first * dim;
     const std::vector<const uint64_t *> masks = t.masks(mask_of);
     const std::vector<const szg_mask *> handles = t.handles(mask_of);
@@ -438,7 +454,7 @@ int SketchRadiusCall::stage(SketchRadiusBatch &t)
             finite = finite && std::isfinite(qj[i]);
             m1 += qj[i] * qj[i];
         }
-        const double D = R * (1.0 + 1e-9) + slack;
+        const double D = R * (1.0 + 1e-9) + p.slack;
         t.D[j] = D;
         t.handed[j] = !finite || !std::isfinite(m1) || !std::isfinite(D) || (gs <= 0.0 && (m1 == 0.0 || D >= 1.0));
         if (t.handed[j]) continue;
@@ -452,7 +468,7 @@ int SketchRadiusCall::stage(SketchRadiusBatch &t)
     });
     if (rc) return rc;
     const double t1 = now_us();
-    for (size_t s = 0; s < n_sh && rc == SZG_OK; s++) {
+    for (size_t s = 0; s < t.ctx.size() && rc == SZG_OK; s++) {
         if (!t.ctx[s]) continue;
         // (the float64 queries unscaled: the re-rank is on the float32 rows; a resident mask's shard words serve the sketch
         // shard too)
@@ -476,23 +492,15 @@ int SketchRadiusCall::enqueue_shard(SketchRadiusBatch &t, size_t s, const std::v
     size_t head_max = 0;
     for (int j = 0; j < t.nq; j++) {
         if (t.handed[j]) continue;
-        const uint64_t *m = masks[j];
-        for (uint64_t r : ix->sk_exc) {
-            if (r < a->first || r >= a->first + a->n_rows) continue;
-            const uint64_t l = r - a->first;
-            if (((a->live_host[l >> 6] >> (l & 63)) & 1) && (!m || ((m[r >> 6] >> (r & 63)) & 1)))
-                head[j].push_back(((uint64_t)kNoKeyUkey << 32) | l);
-        }
+        sketchless_rows(ix, a, masks[j], [&](uint64_t l, bool ok) {
+            if (ok) head[j].push_back(((uint64_t)kNoKeyUkey << 32) | l);
+        });
         head_max = std::max(head_max, head[j].size());
     }
-    size_t cap = std::max(kRadiusCapMin, c->radius_cap);
-    cap = std::min(cap, std::max(kRadiusCapMin, ((size_t)8 << 20) / (size_t)t.nq));  // (a batch's buffers: 8M entries at most)
-    while (cap < head_max + kRadiusCapMin) cap <<= 1;
-    t.cap[s] = cap;
-    int rc = c->d_collect.ensure(cap * (size_t)t.nq);
-    if (rc == SZG_OK) rc = c->d_out.ensure(cap * (size_t)t.nq);
+    int rc = collect_buffers(t, s, true, head_max);  // (every batch keeps within the batch limit)
     if (rc == SZG_OK && head_max) rc = c->h_sent.ensure(head_max * (size_t)t.nq);
     if (rc) return rc;
+    const size_t cap = t.cap[s];
     // the counters start at the staged rows' counts
     memset(c->h_count, 0, sizeof(uint32_t) * (size_t)t.nq * stride);
     for (int j = 0; j < t.nq; j++) {
@@ -507,61 +515,27 @@ int SketchRadiusCall::enqueue_shard(SketchRadiusBatch &t, size_t s, const std::v
     HIPCHK(hipEventRecord(c->ev_up, c->pass.work));  // the sweeps must see the queries, the masks, the heads and the counters
 
     const bool masked = t.any_mask || h->has_dead;
-    const LaunchGeom g = scan_geometry(sk, h, 0);
     // launches that may share their row reads on the matrix cores take the rows' norms from the resident array
     const float *norms = nullptr;
     if (!masked && sk->scan_group == 0 && sk->sketch_matrix != 1 &&
-        (wide || t.nq >= szg::kMatrixMinQueries || sk->sketch_matrix == 2)) {
+        (p.wide || t.nq >= szg::kMatrixMinQueries || sk->sketch_matrix == 2)) {
         int nrc = SZG_OK;
         norms = scan_row_norms(sk, h, &nrc);
         if (nrc) return nrc;
     }
-    const int qpl16 = std::max(1, std::min(sk->queries_per_launch, szg::kMaxSweepsPerLaunch));
-    const int qpl = wide && norms && t.nq > szg::kMatrixQueries && collect_wide_serves(sk, h) ? szg::kMatrixWideQueries : qpl16;
-    t.copied[s] = cap * (size_t)t.nq * sizeof(szg::RerankOut) <= std::max(kRadiusBlockCopyBytes, (size_t)t.nq * (64u << 10));
-    if (t.copied[s]) {
-        rc = c->h_out.ensure(cap * (size_t)t.nq);
-        if (rc) return rc;
-    }
+    const bool wide32 = p.wide && norms && t.nq > szg::kMatrixQueries && sketch_wide_serves(sk, h, 0, 0);
+    const int qpl = wide32 ? szg::kMatrixWideQueries : std::max(1, std::min(sk->queries_per_launch, szg::kMaxSweepsPerLaunch));
     // one part -- or, for a short call (Pass::early_n), two, as enqueue_topk: the first queries' re-rank, sort and
     // copy-back leave the scan stream for the context's own and run beside the call's last sweeps
     const int early = c->pass.early_n > 0 && c->pass.early_n < t.nq ? c->pass.early_n : 0;
-    for (int part = early ? 1 : 0; part >= 0; part--) {
-        const int q0 = part ? 0 : early, q1 = part ? early : t.nq, nqp = q1 - q0;
+    for (int part = early ? 1 : 0; part >= 0 && rc == SZG_OK; part--) {
+        const int q0 = part ? 0 : early, q1 = part ? early : t.nq;
         hipStream_t tl = part ? c->stream : c->pass.work;
-        std::vector<szg::ScanArgs> args((nqp + qpl - 1) / qpl);
-        for (int j0 = q0; j0 < q1; j0 += qpl) {
-            szg::ScanArgs &x = args[(j0 - q0) / qpl];
-            const int m = std::min(qpl, q1 - j0);
-            fill_scan_args(sk, h, c, t.any_mask, j0, m, &x);
-            x.collect = 1;
-            for (int j = 0; j < m; j++) szg::scan_thr_ukey(x, j) = szg::ordered_key(t.thr[j0 + j]);
-            x.collect_buf = c->d_collect + (size_t)j0 * cap;
-            x.collect_cap = (uint32_t)cap;
-            x.collect_count = c->d_count + (size_t)j0 * stride;
-            if (masked && sk->mask_dense) {
-                double lowest = 1.0;
-                for (int j = 0; j < m; j++) lowest = std::min(lowest, mask_pass_rate(h, c, t.any_mask, j0 + j));
-                x.mask_dense = lowest >= 0.5 ? 1 : 0;
-            }
-            // (a call with wide batches: its launches take the matrix sweep whatever their count, as top-k's)
-            if (wide && x.matrix == 0) x.matrix = 2;
-            if (norms && szg::scan_wants_norms(sk->bits, x, g.block)) x.row_norm = norms;
-        }
-        rc = launch_scans_chained(sk, h, c, args, g, tl, part);
-        if (rc) return rc;
-        // float64 distances on the FLOAT32 shard's rows, the counts staying on the device; then each query's hits sorted
-        HIPCHK(szg::launch_rerank(ix->bits, ix->metric, a->rows, ix->layout, ix->dim, c->d_q64 + (size_t)q0 * ix->dim,
-                                  c->d_collect + (size_t)q0 * cap, c->d_count + (size_t)q0 * stride, (uint32_t)cap, nqp,
-                                  c->d_out + (size_t)q0 * cap, tl, stride));
-        HIPCHK(szg::launch_sort_hits(c->d_out + (size_t)q0 * cap, c->d_count + (size_t)q0 * stride, stride, (uint32_t)cap, nqp, tl));
-        HIPCHK(hipMemcpyAsync(c->h_count + (size_t)q0 * stride, c->d_count + (size_t)q0 * stride,
-                              sizeof(uint32_t) * (size_t)nqp * stride, hipMemcpyDeviceToHost, tl));
-        if (t.copied[s])
-            HIPCHK(hipMemcpyAsync(c->h_out + (size_t)q0 * cap, c->d_out + (size_t)q0 * cap,
-                                  cap * (size_t)nqp * sizeof(szg::RerankOut), hipMemcpyDeviceToHost, tl));
+        rc = collect_sweeps(sk, h, c, t, cap, q0, q1, qpl, tl, part, p.wide != 0, norms);
+        // (the re-rank reads the FLOAT32 shard's rows)
+        if (rc == SZG_OK) rc = collect_tail(ix, a, c, t, s, q0, q1, tl);
     }
-    return SZG_OK;
+    return rc;
 }
 
 int SketchRadiusCall::finish(SketchRadiusBatch &t)
@@ -570,118 +544,26 @@ int SketchRadiusCall::finish(SketchRadiusBatch &t)
         t.drain();
         return SZG_OK;
     }
-    int rc = SZG_OK;
-    std::vector<std::vector<HeapItem>> cands(t.nq);
-    std::vector<uint8_t> over(t.nq, 0);       // more candidates than the batch's buffers hold: handed over
-    std::vector<uint8_t> presorted(t.nq, 1);  // the query's hits come from ONE shard's device-sorted list
-    std::vector<uint8_t> lists(t.nq, 0);
-    std::vector<std::vector<szg_cert_entry>> traced(tracing ? t.nq : 0);
-    std::vector<uint8_t> untraced(tracing ? t.nq : 0, 0);
-    double t_wait = 0;
     const double t0 = now_us();
-    for (size_t s = 0; s < n_sh && rc == SZG_OK; s++) {
-        Ctx *c = t.ctx[s];
-        if (!c) continue;
-        const Shard *a = ix->shards[s];
-        const double tw = now_us();
-        hipError_t e = hipSetDevice(a->device);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->pass.work);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);  // (a short call's early part)
-        if (e != hipSuccess) {
-            rc = fail(SZG_E_DEVICE, "hipStreamSynchronize", e);
-            break;
-        }
-        rc = finish_timing(sk, c);
-        if (rc) break;
-        const size_t cap = t.cap[s];
-        size_t most = 0;
-        std::vector<size_t> cnt(t.nq, 0), off(t.nq + 1, 0);
-        for (int j = 0; j < t.nq; j++) {
-            const size_t n = c->h_count[(size_t)j * szg::kCandCountStride];
-            most = std::max(most, n);
-            if (n > cap) over[j] = 1;
-            cnt[j] = n > cap ? 0 : n;
-            off[j + 1] = off[j] + cnt[j];
-        }
-        // the next batch on this context starts with room for what this one saw (and shrinks again slowly)
-        size_t want = kRadiusCapMin;
-        while (want < most + most / 4 && want < kRadiusCapMax) want <<= 1;
-        c->radius_cap = std::max(want, c->radius_cap - c->radius_cap / 8);
-        if (t.copied[s]) {
-            for (int j = 0; j < t.nq; j++) off[j] = (size_t)j * cap;
-        } else if (off[t.nq]) {
-            rc = c->h_out.ensure(off[t.nq]);
-            if (rc) break;
-            for (int j = 0; j < t.nq && e == hipSuccess; j++)
-                if (cnt[j])
-                    e = hipMemcpyAsync(c->h_out + off[j], c->d_out + (size_t)j * cap, cnt[j] * sizeof(szg::RerankOut),
-                                       hipMemcpyDeviceToHost, c->pass.work);
-            if (e == hipSuccess) e = hipStreamSynchronize(c->pass.work);
-            if (e != hipSuccess) {
-                rc = fail(SZG_E_DEVICE, "hipMemcpyAsync(sketch radius hits)", e);
-                break;
-            }
-        }
-        t_wait += now_us() - tw;
-        for (int j = 0; j < t.nq; j++) {
-            if (over[j] || t.handed[j]) continue;
-            cands[j].reserve(cands[j].size() + cnt[j]);
-            if (cnt[j] && (cnt[j] > (size_t)szg::kSortHitsMax || ++lists[j] > 1)) presorted[j] = 0;
-            const double rad = radii[t.first + j];
-            if (tracing && !untraced[j] && !cert_room(ix, traced[j].size() + cnt[j])) {
-                untraced[j] = 1;
-                std::vector<szg_cert_entry>().swap(traced[j]);
-            }
-            const bool keep = tracing && !untraced[j];
-            for (size_t i = off[j]; i < off[j] + cnt[j]; i++) {
-                const szg::RerankOut &r = c->h_out[i];
-                const uint64_t row = a->first + r.row;
-                const bool no_key = r.ukey == kNoKeyUkey;
-                // (the bytes that stand in a sketch shard for a row without a usable sketch mean nothing: should the
-                // sweep collect such a row, the staged entry is the one that counts)
-                if (!no_key && !ix->sk_exc.empty() && std::binary_search(ix->sk_exc.begin(), ix->sk_exc.end(), row)) continue;
-                if (r.dist <= rad) cands[j].push_back(HeapItem{row, r.dist});  // (a NaN distance is never a hit)
-                if (!keep) continue;
-                if (no_key) {
-                    traced[j].push_back(szg_cert_entry{row, r.dist, 0.0, 0.0f, SZG_CERT_ENTRY_NO_KEY});
-                } else {
-                    const float key = szg::key_from_ordered(r.ukey);
-                    traced[j].push_back(szg_cert_entry{row, r.dist, (double)key + key_eps(sk, key, t.meta[j]), key, 0u});
-                }
-            }
-        }
-    }
+    Collected got(t.nq, tracing);
+    const int rc = collect_gather(ix, sk, t, radii, t.handed.data(), ix->sk_exc.empty() ? nullptr : &ix->sk_exc, &got);
     uint64_t settled = 0, fb = 0;
     for (int j = 0; j < t.nq && rc == SZG_OK; j++) {
-        if (over[j] || t.handed[j]) {
+        if (got.over[j] || t.handed[j]) {  // (more candidates than the batch's buffers hold: handed over as well)
             redo.push_back(t.first + j);
             fb++;
             continue;
         }
         settled++;
-        if (tracing && !untraced[j]) {
-            szg_cert_record rec = cert_record(t.first + j, SZG_CERT_SKETCH_RADIUS);
-            rec.keys = SZG_CERT_KEYS_SINGLE;
-            rec.sweep = 0;
-            for (const Shard *sh : ix->shards) rec.row_hi = std::max<uint64_t>(rec.row_hi, sh->first + sh->n_rows);
-            rec.thr = (double)t.thr[j];
-            rec.eps = key_eps(sk, t.thr[j], t.meta[j]);
-            rec.D = t.D[j];
-            rec.slack = slack;
-            cert_emit(ix, rec, traced[j]);
-        }
-        radius_assemble(cands[j], presorted[j] != 0, &(*results)[t.first + j]);
+        if (tracing && !got.untraced[j])
+            collect_record(ix, sk, t, j, t.first + j, SZG_CERT_SKETCH_RADIUS, SZG_CERT_KEYS_SINGLE, 0, t.D[j], p.slack, got.traced[j]);
+        radius_assemble(got.cands[j], got.presorted[j] != 0, &(*results)[t.first + j]);
     }
-    if (rc) t.drain();
-    else t.release();
-    std::lock_guard<std::mutex> lk(ix->stats_mu);
-    ix->stats.host_finish_us += now_us() - t0 - t_wait;
-    if (rc == SZG_OK) {
-        ix->stats.queries += settled;
-        ix->stats.sketch_radius_queries += settled;
-        ix->stats.sketch_radius_fallbacks += fb;
-    }
-    return rc;
+    return collect_end(ix, t, rc, t0, got.t_wait, [&](szg_stats &st) {
+        st.queries += settled;
+        st.sketch_radius_queries += settled;
+        st.sketch_radius_fallbacks += fb;
+    });
 }
 
 }  // namespace
@@ -711,20 +593,11 @@ int search_radius_any(szg_index *ix, const double *queries, int n_queries, const
     // the queries handed over: ONE call of the float32 path, with their masks and handles (no entry in the top-k auto
     // window, sk_hist: radius hand-overs say nothing about top-k certificates)
     const int m = (int)call.redo.size();
-    std::vector<double> q2((size_t)m * ix->dim), r2(m);
-    std::vector<const uint64_t *> m2(m);
-    std::vector<const szg_mask *> h2(handles ? m : 0);
-    bool any = false;
-    for (int i = 0; i < m; i++) {
-        memcpy(&q2[(size_t)i * ix->dim], queries + (size_t)call.redo[i] * ix->dim, sizeof(double) * ix->dim);
-        r2[i] = radii[call.redo[i]];
-        m2[i] = call.mask_of(call.redo[i]);
-        if (handles) h2[i] = handles[call.redo[i]];
-        any |= m2[i] != nullptr;
-    }
+    const HandedOver h(ix, queries, call.mask_of, call.redo);
+    std::vector<double> r2(m);
+    for (int i = 0; i < m; i++) r2[i] = radii[call.redo[i]];
     std::vector<std::vector<HeapItem>> hits2;
-    rc = search_radius_impl(ix, q2.data(), m, r2.data(), !handles && any ? m2.data() : nullptr, &hits2,
-                            handles && any ? h2.data() : nullptr, call.redo.data());
+    rc = search_radius_impl(ix, h.q.data(), m, r2.data(), h.mask_ptrs(), &hits2, h.handle_ptrs(), call.redo.data());
     if (rc) return rc;
     for (int i = 0; i < m; i++) (*results)[call.redo[i]].swap(hits2[i]);
     return SZG_OK;

@@ -277,6 +277,44 @@ int sketch_debug_rows(szg_index *ix, uint64_t first_row, uint64_t n_rows, uint8_
     return szg_index_read_rows(sk, first_row, n_rows, out);
 }
 
+// ---- what every call through the sketch fixes before its first batch ------------------------------------------------
+
+SketchPlan sketch_call_plan(const szg_index *ix, int n_queries, int kp)
+{
+    const szg_index *sk = ix->sketch;
+    SketchPlan p;
+    p.gs = ix->sk_gscale;
+    // + the rounding of the build kernel's angles: its float64 cosine of (row, sketch) is off by at most (dim + 8) u,
+    // which acos turns into at most sqrt(2 (dim + 8) u) where c is near 1 -- a row that its sketch all but reproduces.
+    // Twice the root (a float64 reference beside it; cert_check.sketch_angle_rounding) passes 1e-7 from dim 223 on.
+    const double ang_round = p.gs > 0.0 ? 0.0 : std::max(1e-7, 2.0 * std::sqrt((ix->dim + 8) * 0x1p-52) / M_PI);
+    p.slack = ix->sk_max_ang * (1.0 + 1e-9) + ang_round;
+    // Wide batches (option sketch_wide, read from the sketch index): only where every shard's launch of 32 qualifies
+    // for the two-block matrix sweep.  Automatic: long calls under the default batch and launch sizes; 2: every call
+    // of more than 16 queries.
+    if (sk->sketch_wide == 1 || n_queries <= szg::kMatrixQueries) return p;
+    bool any = false;
+    for (const Shard *sh : sk->shards) {
+        if (sh->n_rows == 0) continue;
+        any = true;
+        if (!sketch_wide_serves(sk, sh, kp, ix->sketch_list)) return p;
+    }
+    if (!any) return p;
+    if (sk->sketch_wide == 2) p.wide = 2;
+    else if (n_queries >= kWideCallMin && ix->query_batch == 16 && sk->queries_per_launch == 16) p.wide = 1;
+    return p;
+}
+
+void sketch_plan_batch(const szg_index *ix, int n_queries, int q0, int wide, Batch *b)
+{
+    const int batch = std::max(1, std::min(ix->query_batch, kMaxBatch));
+    // (a wide call is longer than kShortCall: first and last batch of kFirstBatch, 32 between them)
+    BatchRules r{wide ? szg::kMatrixWideQueries : batch, kFirstBatch, std::min(kShortCall, kMaxBatch), true, false};
+    // forced: batches of up to 32 from the call's first query on, no small edges, no early tail
+    if (wide == 2) r = BatchRules{szg::kMatrixWideQueries, n_queries, szg::kMatrixWideQueries, false, false};
+    plan_batch(ix->sketch, n_queries, q0, 0, r, b);
+}
+
 // ---- one search call through the sketch ---------------------------------------------------------------------------
 //
 // The batch pipeline of scan_topk.cpp (run_batches) on the sketch index's contexts: stage() uploads a batch's queries
@@ -296,7 +334,7 @@ struct SketchCall {
 
     size_t n_sh = 0;
     int kp = 0;
-    double gs = 0.0, slack = 0.0;
+    SketchPlan p;  // gs, slack, and whether the call takes wide batches
     std::vector<int> extra;                     // per shard: entries behind each list (the drop bound's slot, k first
                                                 // rows, remembered rows)
     std::vector<uint64_t> firstk_open, firstk;  // first k eligible rows of an unfiltered / of the current query
@@ -305,8 +343,6 @@ struct SketchCall {
     std::vector<HeapItem> res;
     std::vector<double> dd;
     bool tracing = false;  // the float32 handle's certificate trace is on
-    int wide = 0;          // the call takes wide batches (32 queries, one launch of the two-block matrix sweep each):
-                           // 1 = under the automatic rule, 2 = forced (option sketch_wide = 2)
 
     int run();
     Batch plan(int q0);
@@ -321,12 +357,7 @@ int SketchCall::run()
     tracing = cert_tracing(ix);
     const int kk = k + ix->sketch_extra;
     kp = kk + std::max(ix->slack_min, kk / 2);
-    gs = ix->sk_gscale;  // Euclidean: sketch distances are in units of gs (the sketch sweeps see q / gs)
-    // + the rounding of the build kernel's angles: its float64 cosine of (row, sketch) is off by at most (dim + 8) u,
-    // which acos turns into at most sqrt(2 (dim + 8) u) where c is near 1 -- a row that its sketch all but reproduces.
-    // Twice the root (a float64 reference beside it; cert_check.sketch_angle_rounding) passes 1e-7 from dim 223 on.
-    const double ang_round = std::max(1e-7, 2.0 * std::sqrt((ix->dim + 8) * 0x1p-52) / M_PI);
-    slack = ix->sk_max_ang * (1.0 + 1e-9) + (gs > 0.0 ? 0.0 : ang_round);
+    p = sketch_call_plan(ix, n_queries, kp);
     sk->timing = ix->timing;
     extra.assign(n_sh, 0);
     for (size_t s = 0; s < n_sh; s++) {
@@ -339,27 +370,11 @@ int SketchCall::run()
     redo.reserve(n_queries);
     cands.reserve((size_t)n_sh * kp + ix->sk_exc.size() + (size_t)k);
     dd.reserve(cands.capacity());
-    // Wide batches (option sketch_wide, read from the sketch index): only where every shard's launch of 32 qualifies
-    // for the two-block matrix sweep.  Automatic: long calls under the default batch and launch sizes; 2: every call
-    // of more than 16 queries.
-    wide = 0;
-    if (sk->sketch_wide != 1 && n_queries > szg::kMatrixQueries) {
-        bool serves = true, any = false;
-        for (size_t s = 0; s < n_sh && serves; s++) {
-            if (sk->shards[s]->n_rows == 0) continue;
-            any = true;
-            serves = sketch_wide_serves(sk, sk->shards[s], kp, ix->sketch_list);
-        }
-        if (serves && any) {
-            if (sk->sketch_wide == 2) wide = 2;
-            else if (n_queries >= kWideCallMin && ix->query_batch == 16 && sk->queries_per_launch == 16) wide = 1;
-        }
-    }
     // A wide call's device step (7.6-8 us per query at 1M x 768) is close above the host's 7.3 us per query on one
     // thread: a second thread settles the finished batches (option finish_thread), as in long shared-sweep calls, and
     // leaves the caller 4-4.5 us.
     Finisher<Batch> fin;
-    bool threaded = wide != 0 && ix->finish_thread && n_queries > 2 * szg::kMatrixWideQueries;
+    bool threaded = p.wide != 0 && ix->finish_thread && n_queries > 2 * szg::kMatrixWideQueries;
     if (threaded) threaded = fin.start([this](Batch &b) { return finish(b); });
     int rc = run_batches<Batch>(*this, threaded ? fin.hand_over() : nullptr);
     if (threaded) rc = fin.join(rc);
@@ -369,13 +384,7 @@ int SketchCall::run()
 Batch SketchCall::plan(int q0)
 {
     Batch b;
-    const int batch = std::max(1, std::min(ix->query_batch, kMaxBatch));
-    if (wide == 2)  // forced: batches of up to 32 from the call's first query on, no small edges, no early tail
-        plan_batch(sk, n_queries, q0, 0, BatchRules{szg::kMatrixWideQueries, n_queries, szg::kMatrixWideQueries, false, false}, &b);
-    else if (wide)  // (the call is longer than kShortCall: first and last batch of kFirstBatch, 32 between them)
-        plan_batch(sk, n_queries, q0, 0, BatchRules{szg::kMatrixWideQueries, kFirstBatch, std::min(kShortCall, kMaxBatch), true, false}, &b);
-    else
-        plan_batch(sk, n_queries, q0, 0, BatchRules{batch, kFirstBatch, std::min(kShortCall, kMaxBatch), true, false}, &b);
+    sketch_plan_batch(ix, n_queries, q0, p.wide, &b);
     return b;
 }
 
@@ -388,9 +397,9 @@ int SketchCall::stage(Batch &b)
     const uint64_t *const *mptr = b.any_mask ? masks.data() : nullptr;
     const std::vector<const szg_mask *> handles = b.handles(mask_of);
     const double *q_sk = q;
-    if (gs > 0.0) {
+    if (p.gs > 0.0) {
         q_scaled.resize((size_t)b.nq * dim);
-        for (size_t i = 0; i < q_scaled.size(); i++) q_scaled[i] = q[i] / gs;
+        for (size_t i = 0; i < q_scaled.size(); i++) q_scaled[i] = q[i] / p.gs;
         q_sk = q_scaled.data();
     }
     int rc = stage_query_forms(sk, b, q_sk, false, [](int, QMeta &) {});
@@ -412,12 +421,7 @@ int SketchCall::stage(Batch &b)
             *o++ = szg::kInvalidCand;  // (no drop bound: the full lists' merge leaves it)
             size_t n = rows_in_shard(a, fk, o);
             for (; n < (size_t)k; n++) o[n] = szg::kInvalidCand;
-            for (uint64_t r : ix->sk_exc) {
-                if (r < a->first || r >= a->first + a->n_rows) continue;
-                const uint64_t l = r - a->first;
-                const bool ok = ((a->live_host[l >> 6] >> (l & 63)) & 1) && (!m || ((m[r >> 6] >> (r & 63)) & 1));
-                o[n++] = ok ? l : szg::kInvalidCand;
-            }
+            sketchless_rows(ix, a, m, [&](uint64_t l, bool ok) { o[n++] = ok ? l : szg::kInvalidCand; });
         }
     }
     const double t_enq0 = now_us();
@@ -437,7 +441,7 @@ int SketchCall::stage(Batch &b)
         // (the float64 queries unscaled: the rerank is on the rows; a resident mask's shard words serve the sketch
         // shard too: same rows, same device)
         rc = enqueue_queries(sk, h, c, q, b.nq, mptr, true, handles.empty() ? nullptr : handles.data(), s);
-        const RerankOn on{ix, ix->shards[s], extra[s], ix->sketch_list, wide != 0};
+        const RerankOn on{ix, ix->shards[s], extra[s], ix->sketch_list, p.wide != 0};
         if (rc == SZG_OK) rc = enqueue_topk(sk, h, c, kp, b.nq, b.any_mask, &on);
     }
     note_stage_times(ix, t_prep0, t_enq0);
@@ -490,13 +494,13 @@ void SketchCall::settle(Batch &b, int j)
         // D_lb: the sketch distance the key bound lb implies -- cosine: key = -cos, distance
         // acos(cos) / pi; Euclid: key = (255 d)^2 in units of gs
         double D;
-        if (gs > 0.0) {
-            D = gs * std::sqrt(std::max(lb, 0.0)) / 255.0 * (1.0 - 1e-9);
+        if (p.gs > 0.0) {
+            D = p.gs * std::sqrt(std::max(lb, 0.0)) / 255.0 * (1.0 - 1e-9);
         } else {
             const double x = -lb + 1e-15;  // (an upper bound of the cosine, rounding included)
             D = x >= 1.0 ? 0.0 : (x <= -1.0 ? 1.0 : std::acos(x) / M_PI * (1.0 - 1e-12));
         }
-        ok = (int)res.size() == k && res.back().priority * (1.0 + 1e-9) < D - slack;
+        ok = (int)res.size() == k && res.back().priority * (1.0 + 1e-9) < D - p.slack;
         D_used = D;
     }
     if (ok && ix->tie_mode == 0) {
@@ -513,7 +517,7 @@ void SketchCall::settle(Batch &b, int j)
         for (const Shard *sh : ix->shards) rec.row_hi = std::max<uint64_t>(rec.row_hi, sh->first + sh->n_rows);
         rec.thr_min = lb;
         rec.D = D_used;
-        rec.slack = slack;
+        rec.slack = p.slack;
         cert_emit(ix, rec, traced);
     }
     if (!ok) {
@@ -617,25 +621,12 @@ int search_topk_sketch(szg_index *ix, const double *queries, int n_queries, int 
     if (call.redo.empty()) return SZG_OK;
     // the unsettled queries: ONE call of the full-precision path
     const int m = (int)call.redo.size();
-    std::vector<double> q2((size_t)m * ix->dim);
-    std::vector<const uint64_t *> m2(m);
-    std::vector<const szg_mask *> h2(handles ? m : 0);
+    const HandedOver h(ix, queries, call.mask_of, call.redo);
     std::vector<uint64_t> r2((size_t)m * k);
     std::vector<double> d2((size_t)m * k);
     std::vector<int32_t> c2(m);
-    bool any = false;
-    for (int i = 0; i < m; i++) {
-        memcpy(&q2[(size_t)i * ix->dim], queries + (size_t)call.redo[i] * ix->dim, sizeof(double) * ix->dim);
-        m2[i] = call.mask_of(call.redo[i]);
-        if (handles) h2[i] = handles[call.redo[i]];
-        any |= m2[i] != nullptr;
-    }
-    if (handles)
-        rc = search_topk_impl(ix, q2.data(), m, k, nullptr, r2.data(), d2.data(), c2.data(), nullptr, any ? h2.data() : nullptr,
-                              call.redo.data());
-    else
-        rc = search_topk_impl(ix, q2.data(), m, k, nullptr, r2.data(), d2.data(), c2.data(), any ? m2.data() : nullptr, nullptr,
-                              call.redo.data());
+    rc = search_topk_impl(ix, h.q.data(), m, k, nullptr, r2.data(), d2.data(), c2.data(), h.mask_ptrs(), h.handle_ptrs(),
+                          call.redo.data());
     if (rc) return rc;
     for (int i = 0; i < m; i++) {
         memcpy(out_rows + (size_t)call.redo[i] * k, &r2[(size_t)i * k], sizeof(uint64_t) * k);

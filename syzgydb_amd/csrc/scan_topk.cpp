@@ -147,6 +147,29 @@ void fill_scan_args(const szg_index *ix, const Shard *sh, const Ctx *c, bool has
     a->bulk = ix->sketch_bulk;
 }
 
+// Masked sweeps: when most rows pass (a few tombstones, a mild filter) every row is read and the masks decide at the
+// row finish -- the predicate-free dense phase; a selective filter keeps the form that tests a row before issuing its
+// loads.  The launch's queries [slot, slot+nq) vote: the lowest pass rate decides.
+static int mask_dense_vote(const szg_index *ix, const Shard *sh, const Ctx *c, bool has_allow, int slot, int nq)
+{
+    if (!(has_allow || sh->has_dead) || !ix->mask_dense) return 0;
+    double lowest = 1.0;
+    for (int j = slot; j < slot + nq; j++) lowest = std::min(lowest, mask_pass_rate(sh, c, has_allow, j));
+    return lowest >= 0.5 ? 1 : 0;
+}
+
+void fill_collect_args(const szg_index *ix, const Shard *sh, const Ctx *c, bool has_allow, int slot, int nq, const float *thr,
+                       uint64_t *buf, size_t cap, uint32_t *count, bool dense_vote, szg::ScanArgs *a)
+{
+    fill_scan_args(ix, sh, c, has_allow, slot, nq, a);
+    a->collect = 1;
+    for (int j = 0; j < nq; j++) szg::scan_thr_ukey(*a, j) = szg::ordered_key(thr[j]);
+    a->collect_buf = buf;
+    a->collect_cap = (uint32_t)std::min<size_t>(cap, 0xFFFFFFFFu);
+    a->collect_count = count;
+    if (dense_vote) a->mask_dense = mask_dense_vote(ix, sh, c, has_allow, slot, nq);
+}
+
 // Launch the fused scan for each of the batch's queries (n = a->size()) as the
 // next links of the shard's scan chain; the ctx stream resumes after the last.
 int launch_scans_chained(szg_index *ix, Shard *sh, Ctx *c, const std::vector<szg::ScanArgs> &a,
@@ -199,10 +222,11 @@ int sketch_list_len(int want, int kp, int grid)
 
 bool sketch_wide_serves(const szg_index *sk, const Shard *sh, int kp, int list_opt)
 {
+    const bool collect = kp == 0;  // (no lists: nothing of kp or list_opt bears on the answer)
     if (sk->sketch_wide == 1 || sh->has_dead || kp > 64) return false;
     const LaunchGeom g = scan_geometry(sk, sh, kp, true);
-    const int m = sketch_list_len(list_opt, kp, g.grid);
-    return szg::scan_variant(sk->bits, sk->map, sk->layout.tiled != 0, m, false, false, sk->ring, !sk->shape_kernels,
+    const int m = collect ? 0 : sketch_list_len(list_opt, kp, g.grid);
+    return szg::scan_variant(sk->bits, sk->map, sk->layout.tiled != 0, m, collect, false, sk->ring, !sk->shape_kernels,
                              sk->scan_group, szg::kMatrixWideQueries, g.block, scan_planes(sk), sk->scan_group_ring,
                              sk->sketch_matrix, true, sk->sketch_select, sk->sketch_wide)
                .wide != 0;
@@ -229,10 +253,6 @@ int enqueue_topk(szg_index *ix, Shard *sh, Ctx *c, int kp, int nq, bool has_allo
     if (rc) return rc;
     if (on && c->d_sent.capacity() < (size_t)nq * stride) return fail(SZG_E_INVALID, "sketch candidates not staged");
 
-    // Masked sweeps: when most rows pass (a few tombstones, a mild filter) every row is read and
-    // the masks decide at the row finish -- the predicate-free dense phase; a selective filter
-    // keeps the form that tests a row before issuing its loads.
-    auto pass_rate = [&](int j) { return mask_pass_rate(sh, c, has_allow, j); };
     const bool masked = has_allow || sh->has_dead;
     // (a wide batch of the sketch pre-pass: launches of up to 32 queries where the two-block matrix sweep serves them --
     // unmasked, on every row: the same question the call asked before it planned wide batches)
@@ -249,11 +269,7 @@ int enqueue_topk(szg_index *ix, Shard *sh, Ctx *c, int kp, int nq, bool has_allo
         for (int j = q0; j < q1; j += qpl) {  // one sweep per query, results side by side
             szg::ScanArgs &a = args[(j - q0) / qpl];
             fill_scan_args(ix, sh, c, has_allow, j, std::min(qpl, q1 - j), &a);
-            if (masked && ix->mask_dense) {
-                double lowest = 1.0;
-                for (int i = j; i < std::min(q1, j + qpl); i++) lowest = std::min(lowest, pass_rate(i));
-                a.mask_dense = lowest >= 0.5 ? 1 : 0;
-            }
+            a.mask_dense = mask_dense_vote(ix, sh, c, has_allow, j, a.n_queries);
             a.kp = m;
             // (a call with wide batches: its launches take the matrix sweep whatever their count -- a rest of one or two
             // queries too -- so that a query's keys do not depend on where the batches' edges fall)
@@ -437,14 +453,8 @@ int run_collect(szg_index *ix, Shard *sh, Ctx *c, int slot, float thr_key, bool 
         HIPCHK(hipMemsetAsync(c->d_count, 0, sizeof(uint32_t), c->pass.work));
         HIPCHK(hipEventRecord(c->ev_up, c->pass.work));  // the sweep must see the zeroed counter
         std::vector<szg::ScanArgs> a(1);
-        fill_scan_args(ix, sh, c, has_allow, slot, 1, &a[0]);
-        a[0].collect = 1;
-        a[0].thr_ukeys[0] = szg::ordered_key(thr_key);
-        a[0].collect_buf = c->d_collect;
-        a[0].collect_cap = (uint32_t)std::min<size_t>(c->d_collect.capacity(), 0xFFFFFFFFu);
-        a[0].collect_count = c->d_count;
-        const LaunchGeom g = scan_geometry(ix, sh, 0);
-        rc = launch_scans_chained(ix, sh, c, a, g);
+        fill_collect_args(ix, sh, c, has_allow, slot, 1, &thr_key, c->d_collect, c->d_collect.capacity(), c->d_count, false, &a[0]);
+        rc = launch_scans_chained(ix, sh, c, a, scan_geometry(ix, sh, 0));
         if (rc) return rc;
         HIPCHK(hipMemcpyAsync(c->h_count, c->d_count, sizeof(uint32_t), hipMemcpyDeviceToHost,
                               c->pass.work));

@@ -92,8 +92,8 @@ def synth_corpus(seed, n, dim):
     return np.concatenate(list(parts))
 
 
-def open_sketched(dim, metric, **options):
-    ix = ScanIndex(dim, 32, metric)
+def open_sketched(dim, metric, devices=None, **options):
+    ix = ScanIndex(dim, 32, metric, devices=devices)
     for name, value in dict({"sketch": 1, "sketch_min_rows": 1, "multi_query": 0, "scan_group": 0, "sketch_matrix": 0},
                             **options).items():
         ix.set_option(name, value)

@@ -29,8 +29,8 @@ DEFAULT_TUNABLES = tsm.DEFAULT_TUNABLES
 MS = (0, 1, 25, 300)
 
 
-def open_radius(dim, metric, **options):
-    return tsm.open_sketched(dim, metric, **dict({"sketch_radius": 1, "radius_mq": 0}, **options))
+def open_radius(dim, metric, devices=None, **options):
+    return tsm.open_sketched(dim, metric, devices=devices, **dict({"sketch_radius": 1, "radius_mq": 0}, **options))
 
 
 def all_dists(corpus, Q):
@@ -50,14 +50,22 @@ def radii_for(dists, ms=MS, eligible=None):
     return np.array([radius_at(d, ms[i % len(ms)], eligible) for i, d in enumerate(dists)])
 
 
-def assert_hits(got, corpus, Q, radii, eligible, what):
-    allow = None if eligible is None else eligible.astype(np.uint8)
-    want = POOL.map(lambda a: orc.search_exact(corpus.packed, corpus.dim, 32, corpus.metric, a[0], radius=float(a[1]), allow=allow)[:2],
-                    zip(Q, radii))
+def oracle_hits(corpus, Q, radii, eligible):
+    """The oracle's radius answers, (rows, distances) per query.  eligible: None, bool[n] for all or bool[nq, n]."""
+    allow = [None] * len(Q) if eligible is None else np.broadcast_to(eligible, (len(Q), eligible.shape[-1])).astype(np.uint8)
+    return list(POOL.map(lambda a: orc.search_exact(corpus.packed, corpus.dim, 32, corpus.metric, a[0], radius=float(a[1]),
+                                                    allow=a[2])[:2], zip(Q, radii, allow)))
+
+
+def assert_same_as(got, want, what):
     for qi, (w_rows, w_dist) in enumerate(want):
         g_rows, g_dist = got[qi]
         assert [int(x) for x in g_rows] == [int(x) for x in w_rows], ("rows differ", what, qi, len(g_rows), len(w_rows))
         assert (np.asarray(g_dist) == w_dist).all(), ("distances not bit-equal", what, qi)
+
+
+def assert_hits(got, corpus, Q, radii, eligible, what):
+    assert_same_as(got, oracle_hits(corpus, Q, radii, eligible), what)
 
 
 def same_hits(a, b):
@@ -343,6 +351,41 @@ def test_overflow_then_a_small_radius():
         assert len(got[0][0]) == 25
 
 
+def test_hit_lists_larger_than_one_block_travel_list_by_list():
+    """Four queries of 30 000 hits each in 60 000 rows.  The first call overflows the fresh contexts' 1 024-entry buffers
+    and hands all four over; the contexts have then seen at least 30 000 candidates per query, so the second call's
+    buffers hold 65 536 entries or more per query -- more than there are rows: no overflow -- and its block, 4 x cap x 16
+    bytes >= 4 MiB, is beyond max(2 MiB, 4 x 64 KiB): the hits come back list by list, each longer than the device sorts
+    (kSortHitsMax = 2 048), so the host does.  The trace is off: records of this size need not fit it."""
+    dim, n, nq = 64, 60000, 4
+    seed = SEED + 9350
+    corpus = cc.Corpus(tsm.synth_corpus(seed, n, dim), dim, 32, COS)
+    Q = orc.synth_vectors(seed + 1, 0, nq, dim) * 0.7
+    dists = all_dists(corpus, Q)
+    big = np.array([radius_at(d, 30000) for d in dists])
+    want = oracle_hits(corpus, Q, big, None)
+    assert all(len(w[0]) == 30000 for w in want)
+    with open_radius(dim, COS) as ix:
+        ix.trace_certificates(False)
+        ix.synth(n, seed)
+        for call in ("first", "second"):
+            ix.reset_stats()
+            got = ix.search_radius_batch(Q, big, capacity=nq * 30000)   # (room for all: the call is made once)
+            st = ix.stats()
+            assert_same_as(got, want, (call, "call"))
+            assert st["sketch_radius_queries"] + st["sketch_radius_fallbacks"] == nq, (call, st)
+            if DEFAULT_TUNABLES:
+                settled = 0 if call == "first" else nq
+                assert (st["sketch_radius_queries"], st["sketch_radius_fallbacks"]) == (settled, nq - settled), (call, st)
+        small = np.array([radius_at(d, 25) for d in dists])
+        ix.reset_stats()
+        got = ix.search_radius_batch(Q, small)
+        st = ix.stats()
+        assert_hits(got, corpus, Q, small, None, ("third call",))
+        assert st["sketch_radius_queries"] + st["sketch_radius_fallbacks"] == nq, st
+        assert all(len(g[0]) == 25 for g in got)
+
+
 # ---- 8. rows without a usable sketch ------------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("metric", (COS, EUC), ids=["cos", "euc"])
@@ -379,6 +422,48 @@ def test_rows_without_a_sketch(metric):
                 assert (r in rows) == bool(dists[qi, r] <= radii[qi]), (qi, r)
         lone = [ix.search_radius(Q[i], float(radii[i])) for i in range(nq)]
         assert same_hits(lone, got)
+
+
+def test_two_shards():
+    """A handle of two shards (both on device 0), a row without a usable sketch in each: every shard stages its own head,
+    and a query's hits come as one list per shard (never presorted).  Then the same call with a mask on three of the
+    twelve queries -- launches of the one-query kernel, heads that differ from query to query."""
+    dim, n, nq = 64, 9000, 12
+    rng = np.random.default_rng(4350)
+    V = rng.standard_normal((n, dim)).astype(np.float32).astype(np.float64)
+    exc = {1000, 8000}
+    V[1000, 3] = np.inf
+    V[8000, 5] = np.inf
+    corpus = cc.Corpus(orc.encode_rows(V, 32), dim, 32, COS)
+    Q = rng.standard_normal((nq, dim))
+    dists = all_dists(corpus, Q)
+    radii = radii_for(dists)
+    allow = np.arange(n) % 3 != 1   # (row 1000 is out, row 8000 is in)
+    masked = (2, 5, 9)
+    eligible = np.ones((nq, n), dtype=bool)
+    eligible[list(masked)] = allow
+    with open_radius(dim, COS, devices=[0, 0]) as ix:
+        ix.load(corpus.packed)
+        got, st, recs_all = checked_call(ix, corpus, Q, radii, ("two shards",), dists)
+        info = ix.sketch_info()
+        assert info["n_shards"] == 2 and set(int(x) for x in info["exc_rows"]) == exc, info
+        recs, ents, _ = recs_all[0]
+        for rec in recs[recs["pass_"] == _lib.SZG_CERT_SKETCH_RADIUS]:
+            e = ents[int(rec["first_entry"]): int(rec["first_entry"] + rec["n_entries"])]
+            no_key = set(int(x) for x in e["row"][(e["flags"] & _lib.SZG_CERT_ENTRY_NO_KEY) != 0])
+            assert no_key == exc, ("one staged row per shard", int(rec["query"]), no_key)
+        if DEFAULT_TUNABLES:
+            assert st["sketch_radius_fallbacks"] == 0, st
+        assert max(len(g[0]) for g in got) >= 300 and min(len(g[0]) for g in got) == 0
+        with ix.mask(allow) as mask:
+            handles = [mask if i in masked else None for i in range(nq)]
+            got_m, st_m, _ = checked_call(ix, corpus, Q, radii, ("two shards, masks",), dists, eligible=eligible, masks=handles)
+            assert_passes(st_m, n, dim, nq, nq, ("two shards, masks",))
+            ix.set_option("sketch_radius", 0)
+            ix.reset_stats()
+            got0, got0_m = ix.search_radius_batch(Q, radii), ix.search_radius_batch(Q, radii, masks=handles)
+            assert ix.stats()["sketch_radius_queries"] + ix.stats()["sketch_radius_fallbacks"] == 0
+        assert same_hits(got, got0) and same_hits(got_m, got0_m)
 
 
 # ---- 9. mutations -------------------------------------------------------------------------------------------------------------
