@@ -4,7 +4,9 @@
 # LDS, occupancy inputs) -- the check for a refactor that only moves code (no GPU needed):
 #   scripts/kernel_isa_digest.sh > new.txt                      every shared-sweep object of this tree
 #   scripts/kernel_isa_digest.sh -C ../old/syzgydb_amd/csrc kernels_mq.hip kernels_mq.hip:-DSZG_MQ_PART=1 > old.txt
-#   scripts/kernel_isa_digest.sh kernels_scan.hip:-DSZG_QBITS=8,-DSZG_SCAN_METRIC=1
+#   scripts/kernel_isa_digest.sh kernels_scan.hip:-DSZG_QBITS=8,-DSZG_SCAN_METRIC=1      (a width and a metric: required)
+#   scripts/kernel_isa_digest.sh kernels_scan.hip:-DSZG_QBITS=8,-DSZG_SCAN_METRIC=1,-DSZG_GROUP_FORM=3   (a G > 1 form)
+#   scripts/kernel_isa_digest.sh kernels_scan_merge.hip                                  (the list-merge kernels)
 #   scripts/kernel_isa_digest.sh kernels_scan_mx.hip:-DSZG_SCAN_METRIC=1,-fno-slp-vectorize,-DSZG_MX_NO_SLP   (MX_FLAGS)
 # An argument is SOURCE[:FLAG[,FLAG...]], compiled with the build's flags (CXXFLAGS of syzgydb_amd/csrc/Makefile) plus
 # --cuda-device-only -S.  The text of a kernel is its instructions (label to .Lfunc_end) and its .amdhsa_kernel block;

@@ -3,10 +3,12 @@
 #   scripts/kernel_resources.sh mq i8 4       -> kernels_mq_i8.hip -DSZG_ROW_BITS=4 (the 4-bit int8 sweeps)
 #   scripts/kernel_resources.sh mq bf16 32    -> kernels_mq_bf16.hip -DSZG_ROW_BITS=32    (also: mq bf16d)
 #   scripts/kernel_resources.sh mq select     -> kernels_mq.hip (the selection kernels)
-#   scripts/kernel_resources.sh scan 32       -> kernels_scan.hip -DSZG_QBITS=32
-#   VFLAGS="-DSZG_SCAN_METRIC=1 -DSZG_GROUP_FORM=3" scripts/kernel_resources.sh scan 8
-#                                             -> one metric's G > 1 kernels of one form (bit 0: two planes, bit 1: resident
-#                                                norms); without SZG_GROUP_FORM: the metric's G = 1 kernels
+#   scripts/kernel_resources.sh scan 32 [m]   -> kernels_scan.hip -DSZG_QBITS=32 -DSZG_SCAN_METRIC=m (the width is
+#                                                required; m: 1 = cosine, the default, 0 = Euclidean): the G = 1 kernels
+#   VFLAGS=-DSZG_GROUP_FORM=3 scripts/kernel_resources.sh scan 8
+#                                             -> instead, the metric's G > 1 kernels of one form (bit 0: two planes, bit 1:
+#                                                resident norms)
+#   scripts/kernel_resources.sh merge         -> kernels_scan_merge.hip (the list-merge kernels)
 #   scripts/kernel_resources.sh scan mx 1     -> kernels_scan_mx.hip -DSZG_SCAN_METRIC=1 (the matrix sweep, cosine)
 #   VFLAGS=-DSZG_MX_COLLECT scripts/kernel_resources.sh scan mx 1
 #                                             -> its collect form (radius searches through the sketch)
@@ -19,7 +21,8 @@ set -euo pipefail
 cd "$(dirname "$0")/../syzgydb_amd/csrc"
 kind=${1:-mq}; part=${2:-i8}
 if [ "$kind" = scan ] && [ "$part" = mx ]; then src=kernels_scan_mx.hip; def="-DSZG_SCAN_METRIC=${3:-1} -fno-slp-vectorize -DSZG_MX_NO_SLP"   # (the Makefile's MX_FLAGS)
-elif [ "$kind" = scan ]; then src=kernels_scan.hip; def=-DSZG_QBITS=$part
+elif [ "$kind" = scan ]; then src=kernels_scan.hip; def="-DSZG_QBITS=${2:?row width (4, 8, 16, 32, 64) or mx} -DSZG_SCAN_METRIC=${3:-1}"
+elif [ "$kind" = merge ]; then src=kernels_scan_merge.hip; def=
 elif [ "$kind" = exact ]; then src=kernels_exact.hip; def=-ffp-contract=off
 elif [ "$kind" = mask ]; then src=kernels_mask.hip; def=
 elif [ "$kind" = column ] && [ "$part" = carry ]; then src=kernels_column_carry.hip; def=

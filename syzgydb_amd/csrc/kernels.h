@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "scan_plan.h"
+
 namespace szg {
 
 constexpr int kEuclidean = 0;  // collection.go:186-189
@@ -29,8 +31,6 @@ __host__ __device__ inline float key_from_ordered(uint32_t u)
     return f;
 }
 
-// How the 64 lanes of a wave are laid over rows of r16 16-byte pieces:
-// groups of L lanes take one row each, every lane P pieces of it.
 // Where a row's 16-byte pieces live in the resident mirror.
 //   linear: row-major, `pitch` bytes per row.
 //   tiled : tiles of 16 rows; inside a tile the 64-byte step s of all 16 rows is one
@@ -53,45 +53,6 @@ __host__ __device__ inline uint64_t layout_bytes(const RowLayout &l, uint64_t ro
 {
     return l.tiled ? ((rows + 15) >> 4) * ((uint64_t)l.steps * 1024) : rows * (uint64_t)l.pitch;
 }
-
-struct RowMap {
-    int r16;  // 16-byte pieces per (pitched) row
-    int L;    // lanes per row
-    int P;    // pieces per lane per row (L*P >= r16)
-    int gpw;  // rows (lane groups) per wave iteration
-    int pow2; // L is a power of two (groups are aligned: DPP reductions apply)
-    int dense; // L*P == r16 and gpw*L == 64: every lane always has a piece of a row
-};
-
-// 4-bit rows, single-query scan: the query is quantized to balanced int4 digit planes of radix
-// 16.  kPlanes4 digits carry |Q| < 16^kPlanes4 / 2; every plane costs one v_dot8_i32_i4 per
-// dword of the row and one 16-byte LDS read per piece.  The quantization step enters the
-// certification bound (key_eps) -- 4 planes (15 bits) still certify: the bound grows to
-// ~4e-5 in cosine units against gaps of ~1e-2 between the k-th and the kp-th best key.
-#ifndef SZG_PLANES4
-#define SZG_PLANES4 4
-#endif
-constexpr int kPlanes4 = SZG_PLANES4;
-constexpr double kQmax4 = kPlanes4 == 5 ? 480000.0 : 30000.0;
-
-// Bytes of one prepared query as the scan stages it in LDS: float32 (float64 for
-// 64-bit rows) per element, or integer digit planes of 16 bytes per piece for the
-// exact-integer paths (3 int8 planes for 8-bit rows, 5 int4 planes for 4-bit rows).
-__host__ __device__ inline size_t query_lds_bytes(int qbits, int r16)
-{
-    switch (qbits) {
-    case 4: return (size_t)r16 * 16 * kPlanes4;
-    case 8: return (size_t)r16 * 16 * 3;
-    case 16: return (size_t)r16 * 8 * 4;
-    case 32: return (size_t)r16 * 4 * 4;
-    default: return (size_t)r16 * 2 * 8;
-    }
-}
-
-constexpr int kMaxSweepsPerLaunch = 16;
-// ... but for the matrix sweep's wide form (two column blocks of 16 queries per row read, kernels_scan_mx.hip): the
-// sketch pre-pass puts up to this many queries of a long call into one launch (option sketch_wide)
-constexpr int kMatrixWideQueries = 32;
 
 // Hit counters of the fused selection sit one per 128-byte line: the waves claim their slots
 // with returning atomics, mostly at the end of the sweep, and atomics on one line serialise
@@ -173,99 +134,60 @@ __host__ __device__ inline uint32_t &scan_thr_ukey(ScanArgs &a, int s)
     return s < kMaxSweepsPerLaunch ? a.thr_ukeys[s] : a.thr_ukeys_hi[s - kMaxSweepsPerLaunch];
 }
 
-// Which scan_kernel instantiation a launch takes: decided on the host by scan_variant -- the launcher dispatches on
-// its answer, szg_debug_scan_plan reports it.
-struct ScanVariant {
-    int shaped;       // 0: the any-shape kernel; L * 100 + P: the kernel specialised for that row shape
-    int deep;         // the any-shape kernel with the deep piece ring
-    int ring_depth;   // 16-byte loads each lane keeps in flight
-    int nontemporal;  // rows are loaded past the caches
-    int group;        // queries of the launch scored per row read (1, 2 or 4; kMatrixQueries: the matrix sweep)
-    int matrix;       // the matrix sweep (kernels_scan_mx.hip) serves the launch: one pass per kMatrixQueries queries
-    int matrix_steps; // its form: 12 or 6 (64-byte steps per row fixed at compile time), 0 = the any-steps kernel
-    int row_lists;    // the matrix sweep keeps its 16 lists as row lists (RowList, device_lists.h): kp <= kRowListMax
-                      // under sketch_select = 0; else one WaveList per query and the serial inserts
-    int wide;         // the matrix sweep's two-block form: one pass per kMatrixWideQueries queries (row lists only)
-};
-// What "automatic" (scan_group = 0) asks for, where a launch qualifies.
-constexpr int kScanGroupAuto = 4;
-// The matrix sweep: queries per pass, and the fewest queries of a launch that take it under sketch_matrix = 0 -- a pass
-// costs about what a pass of the G = 1 kernel costs, and less than the G = 4 kernel's from 3 queries on (DESIGN.md 6,
-// round 11).  A lone query keeps the G = 1 kernel.
-constexpr int kMatrixQueries = 16;
-constexpr int kMatrixMinQueries = 3;
-constexpr int matrix_steps_form(int steps) { return steps == 12 || steps == 6 ? steps : 0; }
-constexpr bool sketch_matrix_known(int64_t v) { return v == 0 || v == 1 || v == 2; }
-// The matrix sweep's selection (option sketch_select): lists of up to kRowListMax entries live in the 16 lanes of a
-// lane-row, four queries to a register pair, and take one candidate each per round (0 = automatic); 1 = the serial
-// inserts into one WaveList per query, which longer lists always take.
-constexpr int kRowListMax = 16;
-constexpr bool sketch_select_known(int64_t v) { return v == 0 || v == 1; }
-constexpr bool matrix_row_lists(int kp, int select_opt) { return select_opt == 0 && kp >= 1 && kp <= kRowListMax; }
-// Crowded tiles of the row lists (option sketch_bulk): a tile whose pre-filter lets at least
-// kBulkMin (query, row) pairs of the wave through merges every slot whole (RowList::merge_tile: a fixed sorting network
-// in the lane-row) instead of retiring one lane per lane-row, slot and round.  0 = automatic (kBulkMin), 1 = never (rounds
-// only), n >= 2 = tiles with at least n passing pairs (a tile of two blocks has at most 512: larger values are "never").
-// Both routes leave the same lists bit for bit; routing and scan_variant do not depend on it.
-constexpr uint32_t kBulkMin = 48;
-constexpr uint32_t kBulkNever = 0xFFFFFFFFu;
-constexpr bool sketch_bulk_known(int64_t v) { return v >= 0 && v <= 1024; }
-constexpr uint32_t sketch_bulk_min(int bulk_opt) { return bulk_opt == 0 ? kBulkMin : (bulk_opt == 1 ? kBulkNever : (uint32_t)bulk_opt); }
-// The wide form (option sketch_wide): a launch of more than kMatrixQueries and up to kMatrixWideQueries queries that the
-// matrix sweep serves with row lists scores two column blocks of 16 queries per row read, where the two-block image,
-// constants and lists fit 64 KiB of LDS (768 dimensions: lists of up to 15 entries; longer ones keep one block).
-// 0 = automatic and 2 = wherever the shape allows differ on the host only (which calls form launches of 32); 1 = never.
-constexpr bool sketch_wide_known(int64_t v) { return v == 0 || v == 1 || v == 2; }
-// group: the scan_group option (0 = automatic), n_queries: the launch's, block: its threads (the group's query images
-// -- of `planes` digit planes each -- and lists have to fit 64 KiB of LDS)
-// group_ring: the scan_group_ring option (0 = automatic)
-// matrix_opt: the sketch_matrix option (1 = off, what callers that do not know it get); norms: the launch has resident
-// row norms (ScanArgs::row_norm) -- the matrix sweep needs them; select_opt: the sketch_select option; wide_opt: the sketch_wide option (1 = never, what
-// callers that do not know it get)
-ScanVariant scan_variant(int qbits, const RowMap &m, bool tiled, int kp, bool collect, bool masked, int ring,
-                         bool no_shape_kernels, int group = 1, int n_queries = 1, int block = 256, int planes = 3,
-                         int group_ring = 0, int matrix_opt = 1, bool norms = false, int select_opt = 0, int wide_opt = 1);
-// Ring depths of the G > 1 kernels.  A row-shape kernel of P pieces per lane exists at its shape's own depth (the
-// G = 1 kernel's) and, where kGroupRingAlt divides P and differs from it, at kGroupRingAlt as well: scan_group_ring
-// picks one of the two, 0 takes kGroupRingAuto where the shape has it and the shape's own depth elsewhere.
-#ifndef SZG_GROUP_RING_ALT
-#define SZG_GROUP_RING_ALT 6
-#endif
-#ifndef SZG_GROUP_RING_AUTO
-#define SZG_GROUP_RING_AUTO SZG_GROUP_RING_ALT
-#endif
-constexpr int kGroupRingBase = 4, kGroupRingAlt = SZG_GROUP_RING_ALT, kGroupRingAuto = SZG_GROUP_RING_AUTO;
-static_assert(kGroupRingAuto == kGroupRingBase || kGroupRingAuto == kGroupRingAlt, "automatic: a depth that is compiled");
-constexpr bool scan_group_ring_known(int64_t v) { return v == 0 || v == kGroupRingBase || v == kGroupRingAlt; }
-// depth of the G > 1 kernel of a shape whose own depth is d, P pieces per lane, under option value `want`
-constexpr int scan_group_ring_of(int p, int d, int want)
-{
-    const bool has_alt = p % kGroupRingAlt == 0 && kGroupRingAlt != d;
-    if (!has_alt) return d;
-    const int w = want == 0 ? kGroupRingAuto : want;
-    return w == kGroupRingAlt ? kGroupRingAlt : d;
-}
 inline bool scan_masked(const ScanArgs &a) { return a.live_bits != nullptr || a.allow_bits != nullptr; }
-// passes over the rows that launch_scan makes for `a`: one per group of its queries
-int scan_passes(int qbits, const ScanArgs &a, int block);
+// what scan_variant decides from (scan_plan.h), for the launch `a` describes at `block` threads
+inline ScanPlanIn scan_plan_in(int qbits, const ScanArgs &a, int block)
+{
+    ScanPlanIn in{qbits, a.map, a.tiled != 0, a.kp, a.collect != 0, scan_masked(a), a.ring, a.no_shape_kernels != 0};
+    in.group = a.group;
+    in.n_queries = a.n_queries;
+    in.block = block;
+    in.planes = a.planes;
+    in.group_ring = a.group_ring;
+    in.matrix_opt = a.matrix;
+    in.norms = a.row_norm != nullptr;
+    in.select_opt = a.select;
+    in.wide_opt = a.wide;
+    return in;
+}
 // queries per row read of the variant launch_scan takes for `a`
-int scan_group_of(int qbits, const ScanArgs &a, int block);
+inline int scan_group_of(int qbits, const ScanArgs &a, int block) { return scan_variant(scan_plan_in(qbits, a, block)).group; }
+// passes over the rows that launch_scan makes for `a`: one per group of its queries
+inline int scan_passes(int qbits, const ScanArgs &a, int block)
+{
+    const int group = scan_group_of(qbits, a, block);
+    return (a.n_queries + group - 1) / group;
+}
 // would launch_scan read resident row norms for `a`, if it had them (a G > 1 variant or the matrix sweep)?  The caller
 // then asks for them (scan_row_norms) before it launches.
-bool scan_wants_norms(int qbits, const ScanArgs &a, int block);
+inline bool scan_wants_norms(int qbits, const ScanArgs &a, int block)
+{
+    ScanPlanIn in = scan_plan_in(qbits, a, block);
+    in.norms = true;
+    return scan_variant(in).group > 1;
+}
 
 // Fused dequantize + distance + select.  QBITS in {4,8,16,32,64}.
 hipError_t launch_scan(int qbits, int metric, const ScanArgs &a, int grid, int block,
                        hipStream_t stream);
-// LDS bytes launch_scan needs for (qbits, map, kp, block) at `group` queries per row read; planes = 2: the images of a
-// group (group > 1, 8-bit rows) hold two digit planes
-// matrix: the matrix sweep's column blocks (1, or 2: the wide form; 0: not the matrix sweep) -- per block kMatrixQueries
-// two-plane images laid out for the matrix cores, their constants, and kMatrixQueries x waves lists of kp entries
-// (its collect form keeps no lists: kp = 0, the images and constants alone -- 48.4 KiB for two blocks at 768 dimensions)
-size_t scan_lds_bytes(int qbits, const RowMap &m, int kp, int block, int group = 1, int planes = 3, int matrix = 0);
-
-// Merge n_lists sorted lists of kp candidates into ceil(n_lists/merge_fan(kp)) lists.
-int merge_fan(int kp);
+// The launchers behind it, one per object of the build (m0 = Euclidean, m1 = cosine), declared once for the object that
+// defines one -- by its qualified name, so a definition that does not match is a compile error -- and for its caller.
+// kernels_scan.hip -DSZG_QBITS=q -DSZG_SCAN_METRIC=m: every launch of that width and metric starts here
+#define SZG_DECL_SCAN(q)                                                                   \
+    hipError_t launch_scan_q##q##m0(const ScanArgs &a, int grid, int block, hipStream_t stream); \
+    hipError_t launch_scan_q##q##m1(const ScanArgs &a, int grid, int block, hipStream_t stream);
+SZG_DECL_SCAN(4) SZG_DECL_SCAN(8) SZG_DECL_SCAN(16) SZG_DECL_SCAN(32) SZG_DECL_SCAN(64)
+#undef SZG_DECL_SCAN
+// ... with -DSZG_GROUP_FORM=f on top: the G > 1 kernels of 8-bit rows in one form (bit 0 = two digit planes, bit 1 =
+// resident norms); kernels_scan_mx.hip: the matrix sweep (mx) and, with -DSZG_MX_COLLECT, its collect form (mxc)
+#define SZG_DECL_SCAN_V(name) \
+    hipError_t name(const ScanArgs &a, const ScanVariant &v, int grid, int block, size_t lds, hipStream_t stream);
+#define SZG_DECL_G8(f) SZG_DECL_SCAN_V(launch_scan_g8m0f##f) SZG_DECL_SCAN_V(launch_scan_g8m1f##f)
+SZG_DECL_G8(0) SZG_DECL_G8(1) SZG_DECL_G8(2) SZG_DECL_G8(3)
+SZG_DECL_SCAN_V(launch_scan_mx_m0) SZG_DECL_SCAN_V(launch_scan_mx_m1)
+SZG_DECL_SCAN_V(launch_scan_mxc_m0) SZG_DECL_SCAN_V(launch_scan_mxc_m1)
+#undef SZG_DECL_G8
+#undef SZG_DECL_SCAN_V
 // ---- shared (multi-query) sweeps (mq_device.h, kernels_mq*.hip): every row width, cosine and Euclidean ----------
 // queries per shared sweep: 48 (3 blocks of 16) for the int8 sweeps (4- and 8-bit rows), whose LDS images are 2-4
 // bytes per element and query; 96 for the bfloat16 sweeps (16-, 32- and 64-bit rows, and 8-bit rows in batches of
@@ -358,18 +280,7 @@ hipError_t launch_merge(const uint64_t *in, int n_lists, int kp, int n_queries, 
                         hipStream_t stream, int out_stride = 0);
 // Short lists (the sketch sweep): [n_queries][n_lists][m] sorted block lists, m < kp, merged in ONE launch into the
 // kp best per query at out + q * out_stride, followed by the drop bound at [kp]: the smallest m-th entry of a full
-// list (kInvalidCand if none is full).  merge_short_fits: n_lists <= 1024 and the lists fit one block's LDS.
-bool merge_short_fits(int n_lists, int m, int kp);
-// The selection's buffer: words of LDS the kernel compacts the entries under its threshold into (the tournament's
-// per-group result lists, less two control words), and the most entries its bitonic network sorts -- the largest power
-// of two that fits.  More entries under the threshold than that: the tournament.  (0: the launch always takes it.)
-constexpr int merge_short_cap(int n_lists, int kp) { return (n_lists + 63) / 64 * kp - 2; }
-constexpr int merge_short_sorts(int n_lists, int kp)
-{
-    int s = 0;
-    for (int p = 1; p <= merge_short_cap(n_lists, kp); p <<= 1) s = p;
-    return s;
-}
+// list (kInvalidCand if none is full).  Serves where merge_short_fits (scan_plan.h) says so.
 hipError_t launch_merge_short(const uint64_t *in, int n_lists, int m, int kp, int n_queries, uint64_t *out,
                               int out_stride, hipStream_t stream);
 

@@ -18,43 +18,30 @@
 
 #include <type_traits>
 
-// Built six times: -DSZG_QBITS=4/8/16/32/64 each carry the scan kernels of one
-// quantization (80 instantiations in one unit took minutes to compile); the unit
-// without it (0) has the list-merge kernels and the dispatcher.
+// One object per quantization and metric: -DSZG_QBITS=4/8/16/32/64 -DSZG_SCAN_METRIC=0/1 carries the scan kernels of
+// that width and metric and their launcher (80 instantiations in one unit took minutes to compile); with
+// -DSZG_GROUP_FORM=0..3 on top (8-bit rows), the G > 1 kernels of one form instead.  scan_plan.cpp decides which kernel
+// a launch takes; the list-merge kernels and the by-width dispatcher are kernels_scan_merge.hip's.
 #ifndef SZG_QBITS
-#define SZG_QBITS 0
+#error "kernels_scan.hip needs SZG_QBITS (4, 8, 16, 32 or 64)"
+#endif
+#ifndef SZG_SCAN_METRIC
+#error "kernels_scan.hip with SZG_QBITS needs SZG_SCAN_METRIC (0 or 1)"
 #endif
 
 namespace szg {
 
-#if SZG_QBITS != 0 && !defined(SZG_GROUP_FORM)
+#ifndef SZG_GROUP_FORM
 // the G > 1 kernels of 8-bit rows, one object per metric and form (see SZG_GROUP_FORM below)
-#define SZG_DECL_G8(mm, ff) \
-    hipError_t launch_scan_g8m##mm##f##ff(const ScanArgs &, const ScanVariant &, int, int, size_t, hipStream_t);
-SZG_DECL_G8(0, 0) SZG_DECL_G8(0, 1) SZG_DECL_G8(0, 2) SZG_DECL_G8(0, 3)
-SZG_DECL_G8(1, 0) SZG_DECL_G8(1, 1) SZG_DECL_G8(1, 2) SZG_DECL_G8(1, 3)
-#undef SZG_DECL_G8
 static hipError_t launch_scan_g8(int metric, int form, const ScanArgs &a, const ScanVariant &v, int grid, int block, size_t lds,
                                  hipStream_t stream)
 {
-#define SZG_CASE_G8(ff)                                                                       \
-    case ff: return metric == kCosine ? launch_scan_g8m1f##ff(a, v, grid, block, lds, stream) \
-                                      : launch_scan_g8m0f##ff(a, v, grid, block, lds, stream);
-    switch (form) {
-    SZG_CASE_G8(0)
-    SZG_CASE_G8(1)
-    SZG_CASE_G8(2)
-    SZG_CASE_G8(3)
-    default: return hipErrorInvalidValue;
-    }
-#undef SZG_CASE_G8
+    static constexpr decltype(&launch_scan_g8m0f0) by_metric_form[2][4] = {
+        {launch_scan_g8m0f0, launch_scan_g8m0f1, launch_scan_g8m0f2, launch_scan_g8m0f3},
+        {launch_scan_g8m1f0, launch_scan_g8m1f1, launch_scan_g8m1f2, launch_scan_g8m1f3}};
+    if (form < 0 || form > 3) return hipErrorInvalidValue;
+    return by_metric_form[metric == kCosine ? 1 : 0][form](a, v, grid, block, lds, stream);
 }
-// the matrix sweep, one object per metric (kernels_scan_mx.hip)
-hipError_t launch_scan_mx_m0(const ScanArgs &, const ScanVariant &, int, int, size_t, hipStream_t);
-hipError_t launch_scan_mx_m1(const ScanArgs &, const ScanVariant &, int, int, size_t, hipStream_t);
-// ... and its collect form (the same source with -DSZG_MX_COLLECT)
-hipError_t launch_scan_mxc_m0(const ScanArgs &, const ScanVariant &, int, int, size_t, hipStream_t);
-hipError_t launch_scan_mxc_m1(const ScanArgs &, const ScanVariant &, int, int, size_t, hipStream_t);
 #endif
 
 namespace {
@@ -71,7 +58,6 @@ constexpr int kWave = 64;
 // G > 1 kernels hold G lists and G accumulator triples per lane: two blocks per CU (256 registers) keep them free of
 // spills, and two blocks of four waves are what the sweeps over tiled 8-bit rows run per CU anyway (scan_geometry)
 constexpr int kGroupMinBlocks = 2;
-[[maybe_unused]] constexpr int kStepList = 256;  // row steps a wave compacts at a time (selective masks)  // 16-byte loads each lane keeps in flight
 
 template <int QBITS>
 struct Traits {
@@ -659,6 +645,32 @@ __global__ __launch_bounds__(256, G > 1 ? kGroupMinBlocks : SZG_MIN_BLOCKS) void
     Acc acc;
     acc.reset();
 
+// The rings are macros, not templates or lambdas: the counted waits depend on how the compiler sees these loops.
+// The drain every ring ends with: the pieces left are consumed (and re-issued while any is left to issue) under guards
+#define SZG_RING_DRAIN(ISSUE, CONSUME)                                                  \
+        while (consumed_ < np_) {                                                       \
+            _Pragma("unroll") for (int u = 0; u < D; u++)                               \
+            {                                                                           \
+                if (consumed_ < np_) {                                                  \
+                    CONSUME(u)                                                          \
+                    consumed_++;                                                        \
+                    if (issued_ < np_) {                                                \
+                        ISSUE(u)                                                        \
+                        issued_++;                                                      \
+                    }                                                                   \
+                }                                                                       \
+            }                                                                           \
+        }
+// the unconditional prologue of the two dense rings (at least 2*D pieces: every slot is filled)
+#define SZG_RING_FILL(NPX, ISSUE)                                                       \
+        const uint64_t np_ = (NPX);                                                     \
+        uint64_t issued_ = D, consumed_ = 0;                                            \
+        _Pragma("unroll") for (int u = 0; u < D; u++)                                   \
+        {                                                                               \
+            ISSUE(u)                                                                    \
+            __builtin_amdgcn_sched_barrier(0);                                          \
+        }
+
 // prologue (fill the ring), steady state (every slot consumed is re-issued), drain
 #define SZG_RUN_RING(NPX, ISSUE, CONSUME)                                               \
     {                                                                                   \
@@ -680,19 +692,7 @@ __global__ __launch_bounds__(256, G > 1 ? kGroupMinBlocks : SZG_MIN_BLOCKS) void
             consumed_ += D;                                                             \
             issued_ += D;                                                               \
         }                                                                               \
-        while (consumed_ < np_) {                                                       \
-            _Pragma("unroll") for (int u = 0; u < D; u++)                               \
-            {                                                                           \
-                if (consumed_ < np_) {                                                  \
-                    CONSUME(u)                                                          \
-                    consumed_++;                                                        \
-                    if (issued_ < np_) {                                                \
-                        ISSUE(u)                                                        \
-                        issued_++;                                                      \
-                    }                                                                   \
-                }                                                                       \
-            }                                                                           \
-        }                                                                               \
+        SZG_RING_DRAIN(ISSUE, CONSUME)                                                  \
     }
 
 // The dense phase's ring: at least 2*D pieces, so the prologue is unconditional and the
@@ -701,13 +701,7 @@ __global__ __launch_bounds__(256, G > 1 ? kGroupMinBlocks : SZG_MIN_BLOCKS) void
 // order it is counting on).
 #define SZG_RUN_RING_DENSE(NPX, ISSUE, CONSUME)                                         \
     {                                                                                   \
-        const uint64_t np_ = (NPX);                                                     \
-        uint64_t issued_ = D, consumed_ = 0;                                            \
-        _Pragma("unroll") for (int u = 0; u < D; u++)                                   \
-        {                                                                               \
-            ISSUE(u)                                                                    \
-            __builtin_amdgcn_sched_barrier(0);                                          \
-        }                                                                               \
+        SZG_RING_FILL(NPX, ISSUE)                                                       \
         while (consumed_ + 2 * D <= np_) {                                              \
             _Pragma("unroll") for (int u = 0; u < D; u++)                               \
             {                                                                           \
@@ -718,19 +712,7 @@ __global__ __launch_bounds__(256, G > 1 ? kGroupMinBlocks : SZG_MIN_BLOCKS) void
             consumed_ += D;                                                             \
             issued_ += D;                                                               \
         }                                                                               \
-        while (consumed_ < np_) {                                                       \
-            _Pragma("unroll") for (int u = 0; u < D; u++)                               \
-            {                                                                           \
-                if (consumed_ < np_) {                                                  \
-                    CONSUME(u)                                                          \
-                    consumed_++;                                                        \
-                    if (issued_ < np_) {                                                \
-                        ISSUE(u)                                                        \
-                        issued_++;                                                      \
-                    }                                                                   \
-                }                                                                       \
-            }                                                                           \
-        }                                                                               \
+        SZG_RING_DRAIN(ISSUE, CONSUME)                                                  \
     }
 
 // Row-shape kernels whose ring depth divides the pieces per lane: the steady state is unrolled
@@ -740,13 +722,7 @@ __global__ __launch_bounds__(256, G > 1 ? kGroupMinBlocks : SZG_MIN_BLOCKS) void
 // from the end) drain through the guarded tail loop.
 #define SZG_RUN_RING_ROWS(NPX, ISSUE, CONSUME)                                          \
     {                                                                                   \
-        const uint64_t np_ = (NPX);                                                     \
-        uint64_t issued_ = D, consumed_ = 0;                                            \
-        _Pragma("unroll") for (int u = 0; u < D; u++)                                   \
-        {                                                                               \
-            ISSUE(u)                                                                    \
-            __builtin_amdgcn_sched_barrier(0);                                          \
-        }                                                                               \
+        SZG_RING_FILL(NPX, ISSUE)                                                       \
         while (consumed_ + D + PP <= np_) {                                             \
             _Pragma("unroll") for (int p_ = 0; p_ < PP; p_++)                           \
             {                                                                           \
@@ -757,19 +733,7 @@ __global__ __launch_bounds__(256, G > 1 ? kGroupMinBlocks : SZG_MIN_BLOCKS) void
             consumed_ += PP;                                                            \
             issued_ += PP;                                                              \
         }                                                                               \
-        while (consumed_ < np_) {                                                       \
-            _Pragma("unroll") for (int u = 0; u < D; u++)                               \
-            {                                                                           \
-                if (consumed_ < np_) {                                                  \
-                    CONSUME(u)                                                          \
-                    consumed_++;                                                        \
-                    if (issued_ < np_) {                                                \
-                        ISSUE(u)                                                        \
-                        issued_++;                                                      \
-                    }                                                                   \
-                }                                                                       \
-            }                                                                           \
-        }                                                                               \
+        SZG_RING_DRAIN(ISSUE, CONSUME)                                                  \
     }
 
     // ---- dense phase: no masks, L*P == r16, gpw*L == 64, every group's row in
@@ -945,6 +909,8 @@ __global__ __launch_bounds__(256, G > 1 ? kGroupMinBlocks : SZG_MIN_BLOCKS) void
 #undef SZG_CONSUME
     }  // rounds
     }
+#undef SZG_RING_DRAIN
+#undef SZG_RING_FILL
 #undef SZG_RUN_RING
 #undef SZG_RUN_RING_DENSE
 #undef SZG_RUN_RING_ROWS
@@ -967,304 +933,6 @@ __global__ __launch_bounds__(256, G > 1 ? kGroupMinBlocks : SZG_MIN_BLOCKS) void
     __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0); expcnt, lgkmcnt untouched
     }  // for qi
 }
-
-#if SZG_QBITS == 0
-// ---- merge of sorted candidate lists ----------------------------------------
-
-// minimum of a 64-bit value over the wave, returned in every lane: four DPP
-// steps reduce each row of 16 lanes, four readlanes finish across rows.
-__device__ __forceinline__ uint64_t wave_min_u64(uint64_t v)
-{
-#define SZG_DPP_MIN(ctrl)                                                                  \
-    {                                                                                      \
-        const uint32_t lo_ = (uint32_t)__builtin_amdgcn_update_dpp(                        \
-            (int)(uint32_t)v, (int)(uint32_t)v, ctrl, 0xF, 0xF, false);                    \
-        const uint32_t hi_ = (uint32_t)__builtin_amdgcn_update_dpp(                        \
-            (int)(uint32_t)(v >> 32), (int)(uint32_t)(v >> 32), ctrl, 0xF, 0xF, false);    \
-        const uint64_t o_ = ((uint64_t)hi_ << 32) | lo_;                                   \
-        v = o_ < v ? o_ : v;                                                               \
-    }
-    SZG_DPP_MIN(0xB1)   // quad_perm [1,0,3,2]
-    SZG_DPP_MIN(0x4E)   // quad_perm [2,3,0,1]
-    SZG_DPP_MIN(0x141)  // row_half_mirror
-    SZG_DPP_MIN(0x140)  // row_mirror
-#undef SZG_DPP_MIN
-    uint64_t m = kInvalidCand;
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-        const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, r * 16);
-        const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), r * 16);
-        const uint64_t o = ((uint64_t)hi << 32) | lo;
-        m = o < m ? o : m;
-    }
-    return m;
-}
-
-// Tournament merge: one wave per group of up to 64 sorted lists, one list per
-// lane; kp rounds of "take the smallest head".  Lists are staged in LDS with
-// coalesced loads first, so each round is a DPP reduction plus one LDS read.
-__global__ __launch_bounds__(256) void merge_heads_kernel(const uint64_t *in, int n_lists, int kp,
-                                                          uint64_t *out, int out_stride)
-{
-    extern __shared__ __align__(16) uint8_t smem[];
-    uint64_t *lists = reinterpret_cast<uint64_t *>(smem);
-    const int lane = threadIdx.x & 63;
-    const int first = blockIdx.x * kWave;
-    const int mine = min(kWave, n_lists - first);
-    const int total = mine * kp;
-    in += (size_t)blockIdx.y * n_lists * kp;     // blockIdx.y = query of the batch
-    out += (size_t)blockIdx.y * (out_stride ? (size_t)out_stride : (size_t)gridDim.x * kp);
-    for (int i = threadIdx.x; i < total; i += blockDim.x) lists[i] = in[(size_t)first * kp + i];
-    __syncthreads();
-    if (threadIdx.x >= kWave) return;  // the other waves only helped staging
-    int pos = 0;
-    uint64_t head = lane < mine ? lists[(size_t)lane * kp] : kInvalidCand;
-    uint64_t *o = out + (size_t)blockIdx.x * kp;
-    uint64_t keep = kInvalidCand;  // lane i keeps output i (+64 per round of 64)
-    for (int r = 0; r < kp; r++) {
-        const uint64_t m = wave_min_u64(head);
-        if (head == m && m != kInvalidCand) {  // entries are unique: exactly one lane advances
-            pos++;
-            head = pos < kp ? lists[(size_t)lane * kp + pos] : kInvalidCand;
-        }
-        if ((r & 63) == lane) keep = m;
-        if ((r & 63) == 63 || r == kp - 1) {
-            const int idx = (r & ~63) + lane;
-            if (idx <= r) o[idx] = keep;
-            keep = kInvalidCand;
-        }
-    }
-}
-
-// minimum of a 32-bit value over the wave (lanes 0..15 only: ROW0), wave-uniform: four DPP steps reduce each row of
-// 16 lanes, readlanes finish across rows
-template <bool ROW0>
-__device__ __forceinline__ uint32_t wave_min_u32(uint32_t v)
-{
-    v = min(v, (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, 0xB1, 0xF, 0xF, false));   // quad_perm [1,0,3,2]
-    v = min(v, (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x4E, 0xF, 0xF, false));   // quad_perm [2,3,0,1]
-    v = min(v, (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x141, 0xF, 0xF, false));  // row_half_mirror
-    v = min(v, (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x140, 0xF, 0xF, false));  // row_mirror
-    uint32_t m = (uint32_t)__builtin_amdgcn_readlane((int)v, 0);
-    if (!ROW0) {
-        m = min(m, (uint32_t)__builtin_amdgcn_readlane((int)v, 16));
-        m = min(m, (uint32_t)__builtin_amdgcn_readlane((int)v, 32));
-        m = min(m, (uint32_t)__builtin_amdgcn_readlane((int)v, 48));
-    }
-    return m;
-}
-
-// the smallest candidate of the wave (lanes 0..15 only: ROW0; the others hold kInvalidCand), wave-uniform: the
-// minimum of the ordered keys (high words), then -- only when several lanes hold that key -- of their rows.  Half the
-// work of a 64-bit reduction per tournament round.
-template <bool ROW0>
-__device__ __forceinline__ uint64_t wave_min_cand(uint64_t v)
-{
-    const uint32_t hi = (uint32_t)(v >> 32), lo = (uint32_t)v;
-    const uint32_t mhi = wave_min_u32<ROW0>(hi);
-    const uint64_t tie = __ballot(hi == mhi);
-    uint32_t mlo;
-    if (__popcll(tie) == 1)
-        mlo = (uint32_t)__builtin_amdgcn_readlane((int)lo, __ffsll((long long)tie) - 1);
-    else
-        mlo = wave_min_u32<ROW0>(hi == mhi ? lo : 0xFFFFFFFFu);
-    return ((uint64_t)mhi << 32) | mlo;
-}
-
-// Short-list merge (the sketch sweep): ONE block per query (blockIdx.y) selects the kp best of the
-// n_lists sorted block lists of m entries each (m < kp) and writes them, sorted, to out[0, kp); out[kp] gets the drop
-// bound -- the smallest m-th entry of a FULL block list (kInvalidCand if no list is full): every row a block did not
-// output is above its list's m-th entry.
-// By selection: let h be the kp-th smallest of the lists' FIRST entries (kInvalidCand with fewer than kp non-empty
-// lists).  kp lists start at or below h, so at least kp entries are <= h and the kp best are among the entries <= h --
-// typically little more than kp of them, since the best rows fall to the blocks almost one each.  Every thread finds
-// the rank of its list's first entry among all first entries (the one of rank kp - 1 publishes h), the entries <= h
-// are compacted into LDS in any order, wave 0 sorts them with one bitonic network and writes the first kp.  Entries
-// are unique, so the sorted result does not depend on the order of the compaction.
-// By tournament, when more entries are <= h than the network's buffer holds (the sel array below, less two words):
-// stage 1: wave w runs a tournament over lists [64w, 64w + 64), one list per lane, each lane's next head fetched one
-// advance ahead; stage 2: wave 0 runs one over the <= 16 results.
-// Needs n_lists <= 1024 and merge_short_lds(n_lists, m, kp) <= 64 KiB (merge_short_fits).
-__global__ __launch_bounds__(1024) void merge_short_kernel(const uint64_t *in, int n_lists, int m, int kp,
-                                                           uint64_t *out, int out_stride)
-{
-    extern __shared__ __align__(16) uint8_t smem[];
-    uint64_t *lists = reinterpret_cast<uint64_t *>(smem);  // [n_lists][m]
-    const int ngroups = (n_lists + kWave - 1) / kWave;
-    uint64_t *sel = lists + (size_t)n_lists * m;           // [ngroups][kp]: each group's kp best
-    uint64_t *drops = sel + (size_t)ngroups * kp;          // [ngroups]
-    const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid >> 6;
-    in += (size_t)blockIdx.y * n_lists * m;
-    out += (size_t)blockIdx.y * out_stride;
-    const int total = n_lists * m;
-    for (int i = tid; i < total; i += blockDim.x) lists[i] = in[i];
-    // the selection's words in sel: the entries <= h from the front, h and their count in its last two
-    const int cap = merge_short_cap(n_lists, kp);
-    uint64_t *h_word = sel + cap;
-    uint32_t *count_word = reinterpret_cast<uint32_t *>(sel + cap + 1);
-    if (tid == 0) {
-        *h_word = kInvalidCand;
-        *count_word = 0u;
-    }
-    __syncthreads();
-    {
-        const bool have = tid < n_lists;
-        const uint64_t *my = lists + (size_t)(have ? tid : 0) * m;
-        // (kInvalidCand is the largest value: lists that are not full drop out of the minimum by themselves)
-        const uint64_t drop = wave_min_cand<false>(have ? my[m - 1] : kInvalidCand);
-        if (lane == 0 && wave < ngroups) drops[wave] = drop;
-        const uint64_t first = have ? my[0] : kInvalidCand;
-        if (first != kInvalidCand) {
-            int rank = 0;
-            for (int j = 0; j < n_lists; j++) rank += lists[(size_t)j * m] < first ? 1 : 0;
-            if (rank == kp - 1) *h_word = first;  // (unique entries: one thread at most)
-        }
-        __syncthreads();
-        const uint64_t h = *h_word;
-        int c = 0;
-        if (have)
-            while (c < m && my[c] <= h && my[c] != kInvalidCand) c++;
-        if (c) {
-            const int at = (int)atomicAdd(count_word, (uint32_t)c);
-            if (at + c <= cap)
-                for (int i = 0; i < c; i++) sel[at + i] = my[i];
-        }
-        __syncthreads();
-        const int found = (int)*count_word;
-        int S = 1;
-        while (S < found) S <<= 1;
-        if (S <= cap) {
-            if (wave != 0) return;
-            for (int i = found + lane; i < S; i += kWave) sel[i] = kInvalidCand;
-            __builtin_amdgcn_wave_barrier();
-            // one wave: its LDS accesses complete in program order, a step's exchanges touch disjoint pairs
-            for (int k = 2; k <= S; k <<= 1)
-                for (int j = k >> 1; j > 0; j >>= 1) {
-                    for (int p = lane; p < S / 2; p += kWave) {
-                        const int i = ((p & ~(j - 1)) << 1) | (p & (j - 1));
-                        const int l = i | j;
-                        const uint64_t a = sel[i], b = sel[l];
-                        if ((a > b) == ((i & k) == 0)) {
-                            sel[i] = b;
-                            sel[l] = a;
-                        }
-                    }
-                    __builtin_amdgcn_wave_barrier();
-                }
-            for (int i = lane; i < kp; i += kWave) out[i] = i < found ? sel[i] : kInvalidCand;
-            const uint64_t dmin = wave_min_cand<true>(lane < ngroups ? drops[lane] : kInvalidCand);
-            if (lane == 0) out[kp] = dmin;
-            return;
-        }
-        __syncthreads();  // (every thread has read the count: the tournament takes sel and drops over)
-    }
-    if (wave < ngroups) {
-        const int l = wave * kWave + lane;
-        const bool have = l < n_lists;
-        const uint64_t *my = lists + (size_t)(have ? l : 0) * m;
-        // (kInvalidCand is the largest value: lists that are not full drop out of the minimum by themselves)
-        const uint64_t drop = wave_min_cand<false>(have ? my[m - 1] : kInvalidCand);
-        uint64_t head = have ? my[0] : kInvalidCand;
-        uint64_t next = have && m > 1 ? my[1] : kInvalidCand;
-        int pos = 1;  // of `next`
-        uint64_t *o = sel + (size_t)wave * kp;
-        for (int r = 0; r < kp; r++) {
-            const uint64_t w = wave_min_cand<false>(head);
-            if (head == w && w != kInvalidCand) {  // entries are unique: exactly one lane advances
-                head = next;
-                pos++;
-                next = pos < m ? my[pos] : kInvalidCand;
-            }
-            if (lane == 0) o[r] = w;
-        }
-        if (lane == 0) drops[wave] = drop;
-    }
-    __syncthreads();
-    if (wave != 0) return;
-    const uint64_t *my = sel + (size_t)(lane < ngroups ? lane : 0) * kp;
-    uint64_t head = lane < ngroups ? my[0] : kInvalidCand;
-    uint64_t next = lane < ngroups && kp > 1 ? my[1] : kInvalidCand;
-    int pos = 1;
-    uint64_t keep = kInvalidCand;  // lane i keeps output i (+64 per round of 64)
-    for (int r = 0; r < kp; r++) {
-        const uint64_t w = wave_min_cand<true>(head);
-        if (head == w && w != kInvalidCand) {
-            head = next;
-            pos++;
-            next = pos < kp ? my[pos] : kInvalidCand;
-        }
-        if ((r & 63) == lane) keep = w;
-        if ((r & 63) == 63 || r == kp - 1) {
-            const int idx = (r & ~63) + lane;
-            if (idx <= r) out[idx] = keep;
-            keep = kInvalidCand;
-        }
-    }
-    const uint64_t drop = wave_min_cand<true>(lane < ngroups ? drops[lane] : kInvalidCand);
-    if (lane == 0) out[kp] = drop;
-}
-
-// Rank merge (any kp): every entry finds its rank by binary searches in the
-// other lists.  More work, fully parallel; used when kp is large.
-__global__ __launch_bounds__(1024) void merge_kernel(const uint64_t *in, int n_lists, int kp,
-                                                     int fan, uint64_t *out, int out_stride)
-{
-    extern __shared__ __align__(16) uint8_t smem[];
-    uint64_t *lists = reinterpret_cast<uint64_t *>(smem);
-    const int first = blockIdx.x * fan;
-    const int mine = min(fan, n_lists - first);
-    const int total = mine * kp;
-    in += (size_t)blockIdx.y * n_lists * kp;     // blockIdx.y = query of the batch
-    out += (size_t)blockIdx.y * (out_stride ? (size_t)out_stride : (size_t)gridDim.x * kp);
-    for (int i = threadIdx.x; i < total; i += blockDim.x) lists[i] = in[(size_t)first * kp + i];
-    uint64_t *o = out + (size_t)blockIdx.x * kp;
-    for (int i = threadIdx.x; i < kp; i += blockDim.x) o[i] = kInvalidCand;
-    __syncthreads();
-    for (int it = threadIdx.x; it < total; it += blockDim.x) {
-        const int w = it / kp;
-        const int i = it - w * kp;
-        const uint64_t c = lists[it];
-        if (c == kInvalidCand) continue;
-        int rank = i;
-        for (int w2 = 0; w2 < mine; w2++) {
-            if (w2 == w) continue;
-            rank += lower_count(lists + (size_t)w2 * kp, kp, c);
-            if (rank >= kp) break;
-        }
-        if (rank < kp) o[rank] = c;
-    }
-}
-
-#endif  // SZG_QBITS == 0
-
-// Ring depth.  HBM streams fastest with about 6-9 MB of reads in flight on the chip
-// (scripts/readbw; deeper queues only lengthen the DRAM queues), so the ring is kept SHORT:
-// 4 loads per lane for the any-shape kernels (8 when the candidate lists live in LDS, kp > 64,
-// whose inserts stall longer).  Measured on one box, ring 8 -> 4: 1M x 768 f32 7.04 -> 7.12 TB/s,
-// 4M x 768 8-bit 6.75 -> 6.97, 12.5M x 384 4-bit 6.31 -> 6.57.
-//
-// Row-shape kernels: lanes per row L, pieces per lane P and a ring depth D that DIVIDES P are
-// compile-time constants, so after unrolling the ring every slot sits at a fixed position of
-// the row: the row-finish test, the query offsets and the row jump are folded, no per-piece
-// branch is left (12.5M x 384 4-bit with D = P = 3: 6.31 -> 6.77 TB/s).
-#ifdef SZG_RING
-constexpr int kRingShort = SZG_RING, kRingDeep = SZG_RING;
-#define SZG_SHAPE_RING(d) SZG_RING
-#else
-constexpr int kRingShort = 4, kRingDeep = 8;
-#define SZG_SHAPE_RING(d) d
-#endif
-
-// The row-shape kernels that exist, X(L, P, D) per row width: read by scan_variant (which launch takes one) and by
-// the launcher of that width (which instantiates them).
-#define SZG_SHAPES_4(X) X(4, 3, 3) X(4, 6, 6)    // tiled rows walk 4 lanes per row: 384 / 768 dims
-#define SZG_SHAPES_8(X) X(4, 6, 6) X(4, 12, 4)
-#define SZG_SHAPES_16(X)
-#define SZG_SHAPES_32(X) X(8, 12, 4)             // linear rows, 8 lanes per row; (8, 24) unrolled over a whole row
-                                                 // spills registers and measured slower than any-shape
-#define SZG_SHAPES_64(X)
-
-#if SZG_QBITS != 0
 
 template <int QBITS, int METRIC, bool COLLECT, int LL, int PP, int D, int G = 1, int PL = 3, bool NF = false>
 hipError_t launch_shaped(const ScanArgs &a, bool nt, dim3 g, dim3 b, size_t lds, hipStream_t stream)
@@ -1292,7 +960,7 @@ template <int QBITS, int METRIC, bool COLLECT, bool MASKED, int G, int PL = 3, b
 hipError_t launch_scan_group(const ScanArgs &a, const ScanVariant &v, dim3 g, dim3 b, size_t lds, hipStream_t stream)
 {
     if constexpr (!MASKED) {
-// (G > 1: the shape's kernel at the group ring's other depth, where it has one -- scan_group_ring_of, kernels.h)
+// (G > 1: the shape's kernel at the group ring's other depth, where it has one -- scan_group_ring_of, scan_plan.h)
 #define SZG_TRY_SHAPE(l, p, d)                                                                 \
     if (v.shaped == l * 100 + p) {                                                             \
         if constexpr (G > 1 && scan_group_ring_of(p, SZG_SHAPE_RING(d), kGroupRingAlt) != SZG_SHAPE_RING(d)) {        \
@@ -1331,10 +999,11 @@ template <int QBITS, int METRIC, bool COLLECT, bool MASKED>
 hipError_t launch_scan_qmcm(const ScanArgs &a, int grid, int block, hipStream_t stream)
 {
     const dim3 g(grid), b(block);
-    const ScanVariant v = scan_variant(QBITS, a.map, a.tiled != 0, a.kp, COLLECT, MASKED, a.ring, a.no_shape_kernels != 0,
-                                       a.group, a.n_queries, block, a.planes, a.group_ring, a.matrix, a.row_norm != nullptr, a.select,
-                                       a.wide);
-    const size_t lds = scan_lds_bytes(QBITS, a.map, COLLECT ? 0 : a.kp, block, v.group, a.planes, v.matrix ? (v.wide ? 2 : 1) : 0);
+    ScanPlanIn in = scan_plan_in(QBITS, a, block);
+    in.collect = COLLECT;  // (the kernel this launcher instantiates: launch_scan_qm chose it from the same two facts)
+    in.masked = MASKED;
+    const ScanVariant v = scan_variant(in);
+    const size_t lds = scan_lds_bytes(QBITS, a.map, COLLECT ? 0 : a.kp, block, v.group, a.planes, v.matrix_blocks());
     // (the per-query constants of every launch but the wide one are read up to kMaxSweepsPerLaunch queries)
     if (!v.wide && a.n_queries > kMaxSweepsPerLaunch) return hipErrorInvalidValue;
     if constexpr (QBITS == 8 && !COLLECT && !MASKED) {
@@ -1365,25 +1034,18 @@ hipError_t launch_scan_qm(const ScanArgs &a, int grid, int block, hipStream_t st
 }
 #endif  // !SZG_GROUP_FORM
 
-#endif  // SZG_QBITS != 0
-
 }  // namespace
 
-#if SZG_QBITS != 0
-// this translation unit carries the scan kernels of ONE quantization
+}  // namespace szg
+
 #define SZG_CAT2(a, b) a##b
 #define SZG_CAT(a, b) SZG_CAT2(a, b)
-// ... and of ONE metric (-DSZG_SCAN_METRIC=0 Euclidean / 1 cosine): ten objects of ~35 s instead of five of ~70 s,
-// which is what a parallel build of the library waits for
-#ifndef SZG_SCAN_METRIC
-#error "kernels_scan.hip with SZG_QBITS needs SZG_SCAN_METRIC (0 or 1)"
-#endif
 #ifdef SZG_GROUP_FORM
-// ... or, with -DSZG_GROUP_FORM=0..3 (8-bit rows), the G = 2 and G = 4 kernels of ONE form and nothing else: bit 0 = two
-// digit planes, bit 1 = resident norms.  Eight objects of twelve kernels: in one unit per metric they took five minutes.
-hipError_t SZG_CAT(SZG_CAT(launch_scan_g8m, SZG_SCAN_METRIC), SZG_CAT(f, SZG_GROUP_FORM))(const ScanArgs &a, const ScanVariant &v,
-                                                                                      int grid, int block, size_t lds,
-                                                                                      hipStream_t stream)
+// -DSZG_GROUP_FORM=0..3 (8-bit rows): the G = 2 and G = 4 kernels of ONE form and nothing else: bit 0 = two digit
+// planes, bit 1 = resident norms.  Eight objects of twelve kernels: in one unit per metric they took five minutes.
+hipError_t szg::SZG_CAT(SZG_CAT(launch_scan_g8m, SZG_SCAN_METRIC), SZG_CAT(f, SZG_GROUP_FORM))(const ScanArgs &a, const ScanVariant &v,
+                                                                                           int grid, int block, size_t lds,
+                                                                                           hipStream_t stream)
 {
     static_assert(SZG_QBITS == 8, "groups: 8-bit rows");
     constexpr int PL = (SZG_GROUP_FORM & 1) ? 2 : 3;
@@ -1394,204 +1056,11 @@ hipError_t SZG_CAT(SZG_CAT(launch_scan_g8m, SZG_SCAN_METRIC), SZG_CAT(f, SZG_GRO
     return hipErrorInvalidValue;
 }
 #else
-hipError_t SZG_CAT(SZG_CAT(launch_scan_q, SZG_QBITS), SZG_CAT(m, SZG_SCAN_METRIC))(const ScanArgs &a, int grid, int block,
-                                                                                 hipStream_t stream)
+// the scan kernels of ONE quantization and ONE metric (0 Euclidean / 1 cosine): ten objects of ~35 s instead of five of
+// ~70 s, which is what a parallel build of the library waits for
+hipError_t szg::SZG_CAT(SZG_CAT(launch_scan_q, SZG_QBITS), SZG_CAT(m, SZG_SCAN_METRIC))(const ScanArgs &a, int grid, int block,
+                                                                                      hipStream_t stream)
 {
     return launch_scan_qm<SZG_QBITS, SZG_SCAN_METRIC>(a, grid, block, stream);
 }
 #endif  // SZG_GROUP_FORM
-#else
-#define SZG_DECL_SCAN(q)                                                          \
-    hipError_t launch_scan_q##q##m0(const ScanArgs &, int, int, hipStream_t); \
-    hipError_t launch_scan_q##q##m1(const ScanArgs &, int, int, hipStream_t);
-SZG_DECL_SCAN(4)
-SZG_DECL_SCAN(8)
-SZG_DECL_SCAN(16)
-SZG_DECL_SCAN(32)
-SZG_DECL_SCAN(64)
-#undef SZG_DECL_SCAN
-
-// The instantiation a launch takes.  Row-shape kernels serve unmasked sweeps over dense maps whose lists stay in
-// registers; everything else is the any-shape kernel, with the deep ring when the lists live in LDS (kp > 64).
-ScanVariant scan_variant(int qbits, const RowMap &m, bool tiled, int kp, bool collect, bool masked, int ring,
-                         bool no_shape_kernels, int group, int n_queries, int block, int planes, int group_ring, int matrix_opt,
-                         bool norms, int select_opt, int wide_opt)
-{
-    ScanVariant v{};
-    [[maybe_unused]] int shape_p = 0;  // pieces per lane of the row-shape kernel taken
-    v.deep = ((!collect && kp > 64) || ring >= 8) ? 1 : 0;
-    v.ring_depth = v.deep ? kRingDeep : kRingShort;
-    v.nontemporal = (m.L >= 8 || tiled) ? 1 : 0;  // whole 128-byte lines per load instruction (load_piece)
-    if (!masked && m.dense && m.L * m.gpw == kWave && !no_shape_kernels && !v.deep) {
-#define SZG_IS_SHAPE(l, p, d)                  \
-    if (m.L == l && m.P == p) {                \
-        v.shaped = l * 100 + p;                \
-        v.ring_depth = SZG_SHAPE_RING(d);      \
-        shape_p = p;                           \
-    }
-        switch (qbits) {
-        case 4: SZG_SHAPES_4(SZG_IS_SHAPE) break;
-        case 8: SZG_SHAPES_8(SZG_IS_SHAPE) break;
-        case 16: SZG_SHAPES_16(SZG_IS_SHAPE) break;
-        case 32: SZG_SHAPES_32(SZG_IS_SHAPE) break;
-        default: SZG_SHAPES_64(SZG_IS_SHAPE) break;
-        }
-#undef SZG_IS_SHAPE
-    }
-    // Queries scored per row read (option scan_group; 0 = kScanGroupAuto): 8-bit top-k sweeps without masks whose lists
-    // stay in registers (v.deep: kp > 64, or the deep ring asked for).  No larger than the launch can fill -- 1 query
-    // takes G = 1, 2 take G = 2 -- and than fits 64 KiB of LDS beside the block's lists.
-    v.group = 1;
-    if (qbits == 8 && !collect && !masked && !v.deep) {
-        int g = group == 0 ? kScanGroupAuto : group;
-        if (g != 2 && g != 4) g = 1;
-        while (g > 1 && g / 2 >= n_queries) g /= 2;
-        while (g > 1 && scan_lds_bytes(qbits, m, kp, block, g, planes) > 64u * 1024u) g /= 2;
-        v.group = g;
-        // The grouped row-shape kernels spend G times the arithmetic per piece, so a slot of the ring comes round
-        // G times later than in the G = 1 kernel: they carry a depth of their own (option scan_group_ring).
-        if (g > 1 && v.shaped) v.ring_depth = scan_group_ring_of(shape_p, v.ring_depth, group_ring);
-    }
-    // The matrix sweep (kernels_scan_mx.hip; option sketch_matrix): the same launches -- unmasked 8-bit top-k sweeps with
-    // lists in registers -- over TILED rows of whole 64-byte steps, whose queries carry two digit planes and whose rows'
-    // norms are resident, under scan_group = 0 only (1, 2 and 4 name the VALU kernels).  From kMatrixMinQueries queries
-    // on (sketch_matrix = 2: from one); a lone query of an automatic launch keeps the G = 1 kernel.
-    if (qbits == 8 && !collect && !masked && !v.deep && kp >= 1 && tiled && m.r16 > 0 && m.r16 % 4 == 0 && planes == 2 &&
-        norms && group == 0 && matrix_opt != 1 && n_queries >= (matrix_opt == 2 ? 1 : kMatrixMinQueries) && block >= kWave &&
-        block <= 256 && block % kWave == 0 && scan_lds_bytes(qbits, m, kp, block, kMatrixQueries, planes, 1) <= 64u * 1024u) {
-        v.matrix = 1;
-        v.matrix_steps = matrix_steps_form(m.r16 / 4);
-        v.group = kMatrixQueries;
-        v.shaped = 0;
-        v.ring_depth = v.matrix_steps == 12 ? 6 : (v.matrix_steps == 6 ? 3 : 4);
-        // its selection (option sketch_select): short lists as row lists, one candidate into each of the 16 per round
-        v.row_lists = matrix_row_lists(kp, select_opt) ? 1 : 0;
-        // The wide form (option sketch_wide): a launch of 17 .. kMatrixWideQueries queries with row lists scores two
-        // column blocks per row read where both blocks' images, constants and lists fit 64 KiB of LDS; where they do
-        // not (768 dimensions with lists of 16), the launch keeps one block and walks its queries in groups of 16.
-        if (v.row_lists && wide_opt != 1 && n_queries > kMatrixQueries && n_queries <= kMatrixWideQueries &&
-            scan_lds_bytes(qbits, m, kp, block, kMatrixWideQueries, planes, 2) <= 64u * 1024u) {
-            v.wide = 1;
-            v.group = kMatrixWideQueries;
-        }
-    }
-    // Its collect form (radius searches through the sketch): the same conditions with `collect`
-    // set -- no lists, so neither kp nor the selection matter, and the two-block form needs the images and constants
-    // alone (48.4 KiB at 768 dimensions).  A launch of the caller that must keep the one-query collect kernel (a query
-    // swept again on its own) says matrix_opt = 1.
-    if (qbits == 8 && collect && !masked && ring < 8 && tiled && m.r16 > 0 && m.r16 % 4 == 0 && planes == 2 && norms &&
-        group == 0 && matrix_opt != 1 && n_queries >= (matrix_opt == 2 ? 1 : kMatrixMinQueries) && block >= kWave &&
-        block <= 256 && block % kWave == 0 && scan_lds_bytes(qbits, m, 0, block, kMatrixQueries, planes, 1) <= 64u * 1024u) {
-        v.matrix = 1;
-        v.matrix_steps = matrix_steps_form(m.r16 / 4);
-        v.group = kMatrixQueries;
-        v.shaped = 0;
-        v.ring_depth = v.matrix_steps == 12 ? 6 : (v.matrix_steps == 6 ? 3 : 4);
-        if (wide_opt != 1 && n_queries > kMatrixQueries && n_queries <= kMatrixWideQueries &&
-            scan_lds_bytes(qbits, m, 0, block, kMatrixWideQueries, planes, 2) <= 64u * 1024u) {
-            v.wide = 1;
-            v.group = kMatrixWideQueries;
-        }
-    }
-    return v;
-}
-
-size_t scan_lds_bytes(int qbits, const RowMap &m, int kp, int block, int group, int planes, int matrix)
-{
-    // per column block: 16 two-plane images (32 bytes per piece and query) | qscale, qconst, qnorm2 | 16 x waves lists
-    // (kp = 0, its collect form: a fourth word per query, the threshold, and no lists)
-    if (matrix)
-        return (size_t)matrix * kMatrixQueries *
-               ((size_t)m.r16 * 32 + (kp == 0 ? 4 : 3) * sizeof(float) + (size_t)(block / kWave) * kp * sizeof(uint64_t));
-    // per query of a group: query image + per-wave candidate lists; per-wave lists of row steps that survive the masks
-    // (the two-plane images exist in the G > 1 kernels only: a lone query stages the whole image, its h plane all zero)
-    const size_t image = qbits == 8 && group > 1 && planes == 2 ? (size_t)m.r16 * 32 : query_lds_bytes(qbits, m.r16);
-    return (size_t)group * (image + (size_t)(block / kWave) * kp * sizeof(uint64_t)) +
-           (size_t)(block / kWave) * kStepList * sizeof(uint32_t);
-}
-
-int scan_group_of(int qbits, const ScanArgs &a, int block)
-{
-    return scan_variant(qbits, a.map, a.tiled != 0, a.kp, a.collect != 0, scan_masked(a), a.ring, a.no_shape_kernels != 0,
-                        a.group, a.n_queries, block, a.planes, a.group_ring, a.matrix, a.row_norm != nullptr, a.select, a.wide)
-        .group;
-}
-
-bool scan_wants_norms(int qbits, const ScanArgs &a, int block)
-{
-    return scan_variant(qbits, a.map, a.tiled != 0, a.kp, a.collect != 0, scan_masked(a), a.ring, a.no_shape_kernels != 0,
-                        a.group, a.n_queries, block, a.planes, a.group_ring, a.matrix, true, a.select, a.wide)
-               .group > 1;
-}
-
-int scan_passes(int qbits, const ScanArgs &a, int block)
-{
-    const int group = scan_group_of(qbits, a, block);
-    return (a.n_queries + group - 1) / group;
-}
-
-hipError_t launch_scan(int qbits, int metric, const ScanArgs &a, int grid, int block,
-                       hipStream_t stream)
-{
-    static_assert(kEuclidean == 0 && kCosine == 1, "the scan objects are named by the metric's number");
-#define SZG_CASE_SCAN(q)                                                                                            \
-    case q: return metric == kCosine ? launch_scan_q##q##m1(a, grid, block, stream) : launch_scan_q##q##m0(a, grid, block, stream);
-    switch (qbits) {
-    SZG_CASE_SCAN(4)
-    SZG_CASE_SCAN(8)
-    SZG_CASE_SCAN(16)
-    SZG_CASE_SCAN(32)
-    SZG_CASE_SCAN(64)
-    default: return hipErrorInvalidValue;
-    }
-#undef SZG_CASE_SCAN
-}
-
-int merge_fan(int kp)
-{
-    if (kp <= 128) return kWave;                       // tournament: one list per lane
-    return kp >= 4096 ? 2 : (8192 / kp < 32 ? 8192 / kp : 32);  // rank merge, <= 64 KiB of LDS
-}
-
-hipError_t launch_merge(const uint64_t *in, int n_lists, int kp, int n_queries, uint64_t *out,
-                        hipStream_t stream, int out_stride)
-{
-    const int fan = merge_fan(kp);
-    const dim3 grid((n_lists + fan - 1) / fan, n_queries);
-    if (out_stride && (grid.x != 1 || out_stride < kp)) return hipErrorInvalidValue;  // (one output list per query only)
-    const size_t lds = (size_t)fan * kp * sizeof(uint64_t);
-    if (kp <= 128) {
-        hipLaunchKernelGGL(merge_heads_kernel, grid, dim3(256), lds, stream, in, n_lists, kp, out, out_stride);
-        return hipGetLastError();
-    }
-    int block = fan * kp;
-    if (block > 1024) block = 1024;
-    block = (block + 63) & ~63;
-    hipLaunchKernelGGL(merge_kernel, grid, dim3(block), lds, stream, in, n_lists, kp, fan, out, out_stride);
-    return hipGetLastError();
-}
-
-static size_t merge_short_lds(int n_lists, int m, int kp)
-{
-    const size_t groups = (size_t)(n_lists + kWave - 1) / kWave;
-    return ((size_t)n_lists * m + groups * kp + groups) * sizeof(uint64_t);
-}
-
-bool merge_short_fits(int n_lists, int m, int kp)
-{
-    return n_lists >= 1 && n_lists <= 16 * kWave && m >= 1 && m < kp && merge_short_lds(n_lists, m, kp) <= 64u * 1024u;
-}
-
-hipError_t launch_merge_short(const uint64_t *in, int n_lists, int m, int kp, int n_queries, uint64_t *out,
-                              int out_stride, hipStream_t stream)
-{
-    if (!merge_short_fits(n_lists, m, kp) || out_stride < kp + 1) return hipErrorInvalidValue;
-    const int block = (n_lists + kWave - 1) / kWave * kWave;  // one wave per group of 64 lists
-    hipLaunchKernelGGL(merge_short_kernel, dim3(1, n_queries), dim3(block), merge_short_lds(n_lists, m, kp), stream,
-                       in, n_lists, m, kp, out, out_stride);
-    return hipGetLastError();
-}
-
-#endif  // SZG_QBITS
-
-}  // namespace szg

@@ -3,7 +3,7 @@
 //
 // Serves unmasked top-k sweeps over TILED 8-bit rows of whole 64-byte steps whose queries carry two digit planes
 // (ScanArgs::planes == 2), with resident norms (ScanArgs::row_norm) and lists in registers (kp <= 64): today the
-// sketch index.  scan_variant (kernels_scan.hip) decides; everything else keeps scan_kernel.
+// sketch index.  scan_variant (scan_plan.cpp) decides; everything else keeps scan_kernel.
 // With -DSZG_MX_COLLECT the file builds the COLLECT form instead (objects of their own): the same
 // pass over the rows and the same keys, no lists -- every (query, row) pair whose key is at or below the query's
 // threshold is appended to that query's buffer (radius searches through the sketch, scan_radius.cpp).
@@ -502,12 +502,15 @@ hipError_t launch_mxc_steps(const ScanArgs &a, bool wide, int grid, int block, s
 
 }  // namespace
 
+}  // namespace szg
+
+// (defined by its qualified name: it has to match its declaration in kernels.h)
 #define SZG_CAT2(a, b) a##b
 #define SZG_CAT(a, b) SZG_CAT2(a, b)
 #ifdef SZG_MX_COLLECT
 // the collect form of ONE metric (objects of their own, -DSZG_MX_COLLECT): v names the form
-hipError_t SZG_CAT(launch_scan_mxc_m, SZG_SCAN_METRIC)(const ScanArgs &a, const ScanVariant &v, int grid, int block, size_t lds,
-                                                     hipStream_t stream)
+hipError_t szg::SZG_CAT(launch_scan_mxc_m, SZG_SCAN_METRIC)(const ScanArgs &a, const ScanVariant &v, int grid, int block,
+                                                          size_t lds, hipStream_t stream)
 {
     // (scan_variant's conditions, once more: a launch that does not meet them must not reach these kernels)
     if (!v.matrix || !v.nontemporal || !a.tiled || a.steps == 0 || (int)a.steps * 4 != a.map.r16 || a.planes != 2 ||
@@ -520,7 +523,7 @@ hipError_t SZG_CAT(launch_scan_mxc_m, SZG_SCAN_METRIC)(const ScanArgs &a, const 
     const bool wide = v.wide != 0;
     if (wide && (a.wide == 1 || a.n_queries <= kMatrixQueries || a.n_queries > kMatrixWideQueries)) return hipErrorInvalidValue;
     if (!wide && a.n_queries > kMaxSweepsPerLaunch) return hipErrorInvalidValue;
-    if (lds != scan_lds_bytes(8, a.map, 0, block, wide ? kMatrixWideQueries : kMatrixQueries, a.planes, wide ? 2 : 1))
+    if (lds != scan_lds_bytes(8, a.map, 0, block, wide ? kMatrixWideQueries : kMatrixQueries, a.planes, v.matrix_blocks()))
         return hipErrorInvalidValue;
     switch (v.matrix_steps) {
     case 12: return launch_mxc_steps<12>(a, wide, grid, block, lds, stream);
@@ -530,8 +533,8 @@ hipError_t SZG_CAT(launch_scan_mxc_m, SZG_SCAN_METRIC)(const ScanArgs &a, const 
 }
 #else
 // the matrix sweep of ONE metric (one object each, as the scan objects): v names the form (ScanVariant::matrix_steps)
-hipError_t SZG_CAT(launch_scan_mx_m, SZG_SCAN_METRIC)(const ScanArgs &a, const ScanVariant &v, int grid, int block, size_t lds,
-                                                    hipStream_t stream)
+hipError_t szg::SZG_CAT(launch_scan_mx_m, SZG_SCAN_METRIC)(const ScanArgs &a, const ScanVariant &v, int grid, int block,
+                                                         size_t lds, hipStream_t stream)
 {
     // (scan_variant's conditions, once more: a launch that does not meet them must not reach these kernels)
     if (!v.matrix || !v.nontemporal || !a.tiled || a.steps == 0 || (int)a.steps * 4 != a.map.r16 || a.planes != 2 ||
@@ -546,7 +549,7 @@ hipError_t SZG_CAT(launch_scan_mx_m, SZG_SCAN_METRIC)(const ScanArgs &a, const S
     // option sketch_wide not 1, and exactly the two-block LDS; every other launch holds at most kMaxSweepsPerLaunch
     const bool wide = v.wide != 0;
     if (wide && (!rows || a.wide == 1 || a.n_queries <= kMatrixQueries || a.n_queries > kMatrixWideQueries ||
-                 lds != scan_lds_bytes(8, a.map, a.kp, block, kMatrixWideQueries, a.planes, 2)))
+                 lds != scan_lds_bytes(8, a.map, a.kp, block, kMatrixWideQueries, a.planes, v.matrix_blocks())))
         return hipErrorInvalidValue;
     if (!wide && a.n_queries > kMaxSweepsPerLaunch) return hipErrorInvalidValue;
     switch (v.matrix_steps) {
@@ -556,5 +559,3 @@ hipError_t SZG_CAT(launch_scan_mx_m, SZG_SCAN_METRIC)(const ScanArgs &a, const S
     }
 }
 #endif  // SZG_MX_COLLECT
-
-}  // namespace szg

@@ -561,202 +561,183 @@ int szg_debug_sketch_rows(szg_index *ix, uint64_t first_row, uint64_t n_rows, ui
     SZG_CATCH
 }
 
-// test hook, host only: the lane map, launch geometry and kernel variant a sweep over n_rows rows would take -- from
-// the functions the launch path calls (row_format, scan_geometry, scan_variant), so tests derive their shapes from
-// the code's own rules
-int szg_debug_scan_plan(int dim, int quant_bits, uint64_t n_rows, int kp, int collect, int masked, int cu_count,
-                        szg_scan_plan *out)
+}  // extern "C"
+
+// ---- the plan hooks (test hooks, host only; include/syzgy_scan.h says what each answers): what a one-sweep call would
+// do, from the functions the launch path calls (row_format, scan_geometry, scan_variant, scan_lds_bytes), so tests derive
+// their shapes from the code's own rules.
+namespace {
+
+// the option arguments the hooks share, checked in this order; null = the hook has no such argument
+int hook_options(const int *planes, const int *scan_group, const int *sketch_matrix, const int *sketch_select, const int *sketch_wide)
 {
-    if (!out) return fail(SZG_E_INVALID, "out is null");
-    if (kp < 0 || cu_count < 0) return fail(SZG_E_INVALID, "kp or cu_count negative");
-    RowFormat f;
-    const int rc = row_format(dim, quant_bits, &f);
-    if (rc == SZG_E_UNSUPPORTED) return fail(rc, "dimension too large for the LDS-resident query");
-    if (rc) return rc;
-    const int list_kp = collect ? 0 : kp;  // collect sweeps keep no lists
-    const LaunchGeom g = scan_geometry(quant_bits, f.map, f.row_bytes, f.layout.tiled != 0, n_rows,
-                                       cu_count ? cu_count : 256, list_kp);
-    const szg::ScanVariant v = szg::scan_variant(quant_bits, f.map, f.layout.tiled != 0, list_kp, collect != 0, masked != 0,
-                                                 szg_index::ring, !szg_index::shape_kernels);
-    *out = szg_scan_plan{f.map.r16, f.map.L,      f.map.P, f.map.gpw,    f.map.pow2, f.map.dense,  (int32_t)f.layout.tiled,
-                         g.grid,    g.block, v.ring_depth, v.shaped, v.nontemporal, g.rows_per_block};
+    if (planes && *planes != 2 && *planes != 3) return fail(SZG_E_INVALID, "planes is 2 or 3");
+    if (scan_group && *scan_group != 0 && *scan_group != 1 && *scan_group != 2 && *scan_group != 4)
+        return fail(SZG_E_INVALID, "scan_group is 0, 1, 2 or 4");
+    if (sketch_matrix && !szg::sketch_matrix_known(*sketch_matrix)) return fail(SZG_E_INVALID, "sketch_matrix is 0, 1 or 2");
+    if (sketch_select && !szg::sketch_select_known(*sketch_select)) return fail(SZG_E_INVALID, "sketch_select is 0 or 1");
+    if (sketch_wide && !szg::sketch_wide_known(*sketch_wide)) return fail(SZG_E_INVALID, "sketch_wide is 0, 1 or 2");
     return SZG_OK;
 }
 
-// test hook, host only: the groups a one-sweep call forms (scan_variant's choice per launch, scan_lds_bytes, and the pass
-// count launch_scans_chained adds to szg_stats.scan_bytes)
+// One hook's call: the rows of (dim, quant_bits), the geometry of a sweep over them, the record of one launch -- the hook
+// names what it sets behind `block` -- and what walking the call's launches over that record finds.
+struct PlanHook {
+    RowFormat f;
+    LaunchGeom g;
+    szg::ScanPlanIn in;
+    szg::ScanVariant first;  // the first launch's variant and LDS bytes
+    uint64_t lds_bytes;
+    int32_t passes;          // over the rows, of all launches (what launch_scans_chained adds to szg_stats.scan_bytes)
+    // (tiled: the caller may only take the tiled layout away from a format that has it)
+    int rows(int dim, int quant_bits, int tiled, int kp, bool collect, int masked, uint64_t n_rows = 1u << 22, int cu_count = 256)
+    {
+        const int rc = row_format(dim, quant_bits, &f);
+        if (rc == SZG_E_UNSUPPORTED) return fail(rc, "dimension too large for the LDS-resident query");
+        if (rc) return rc;
+        g = scan_geometry(quant_bits, f.map, f.row_bytes, f.layout.tiled != 0, n_rows, cu_count, kp);
+        in = szg::ScanPlanIn{quant_bits, f.map, f.layout.tiled != 0 && tiled != 0, kp, collect, masked != 0, szg_index::ring,
+                             !szg_index::shape_kernels};
+        in.block = g.block;
+        return SZG_OK;
+    }
+    // ... for the four hooks of the sketch's launches: the options all four take, checked and filled in
+    int sketch_rows(int dim, int quant_bits, int kp, bool collect, int planes, int norms, int tiled, int masked, int scan_group,
+                    int sketch_matrix, const int *sketch_select, const int *sketch_wide)
+    {
+        if (const int rc = hook_options(&planes, &scan_group, &sketch_matrix, sketch_select, sketch_wide)) return rc;
+        if (const int rc = rows(dim, quant_bits, tiled, kp, collect, masked)) return rc;
+        in.group = scan_group;
+        in.planes = planes;
+        in.matrix_opt = sketch_matrix;
+        in.norms = norms != 0;
+        if (sketch_select) in.select_opt = *sketch_select;
+        if (sketch_wide) in.wide_opt = *sketch_wide;
+        return SZG_OK;
+    }
+    // the call's n_queries queries as launches of up to per_launch
+    void walk(int n_queries, int per_launch)
+    {
+        passes = 0;
+        for (int j = 0; j < n_queries; j += per_launch) {
+            in.n_queries = std::min(per_launch, n_queries - j);
+            const szg::ScanVariant v = szg::scan_variant(in);
+            if (j == 0) {
+                first = v;
+                lds_bytes = szg::scan_lds_bytes(in.qbits, in.map, in.kp, in.block, v.group, in.planes, v.matrix_blocks());
+            }
+            passes += (in.n_queries + v.group - 1) / v.group;
+        }
+    }
+    // launches of 32 where one qualifies for the two-block form, else of 16
+    int wide_launches()
+    {
+        walk(szg::kMatrixWideQueries, szg::kMatrixWideQueries);
+        return first.wide ? szg::kMatrixWideQueries : szg::kMaxSweepsPerLaunch;
+    }
+};
+
+}  // namespace
+
+extern "C" {
+
+// the lane map, launch geometry and kernel variant a sweep over n_rows rows would take
+int szg_debug_scan_plan(int dim, int quant_bits, uint64_t n_rows, int kp, int collect, int masked, int cu_count, szg_scan_plan *out)
+{
+    if (!out) return fail(SZG_E_INVALID, "out is null");
+    if (kp < 0 || cu_count < 0) return fail(SZG_E_INVALID, "kp or cu_count negative");
+    PlanHook h;  // (collect sweeps keep no lists)
+    if (const int rc = h.rows(dim, quant_bits, 1, collect ? 0 : kp, collect != 0, masked, n_rows, cu_count ? cu_count : 256)) return rc;
+    const szg::ScanVariant v = szg::scan_variant(h.in);
+    const szg::RowMap &m = h.f.map;
+    *out = szg_scan_plan{m.r16,    m.L,       m.P,          m.gpw,    m.pow2,        m.dense,           (int32_t)h.f.layout.tiled,
+                         h.g.grid, h.g.block, v.ring_depth, v.shaped, v.nontemporal, h.g.rows_per_block};
+    return SZG_OK;
+}
+
+// the groups a one-sweep call forms
 int szg_debug_scan_group(int dim, int quant_bits, int kp, int collect, int masked, int scan_group, int n_queries,
                          int queries_per_launch, int32_t *group, uint64_t *lds_bytes, int32_t *passes)
 {
     if (!group || !lds_bytes || !passes) return fail(SZG_E_INVALID, "null argument");
     if (kp < 0 || n_queries < 1 || queries_per_launch < 1 || queries_per_launch > szg::kMaxSweepsPerLaunch)
         return fail(SZG_E_INVALID, "kp, n_queries or queries_per_launch out of range");
-    if (scan_group != 0 && scan_group != 1 && scan_group != 2 && scan_group != 4)
-        return fail(SZG_E_INVALID, "scan_group is 0, 1, 2 or 4");
-    RowFormat f;
-    const int rc = row_format(dim, quant_bits, &f);
-    if (rc == SZG_E_UNSUPPORTED) return fail(rc, "dimension too large for the LDS-resident query");
-    if (rc) return rc;
-    const int list_kp = collect ? 0 : kp;
-    const LaunchGeom g = scan_geometry(quant_bits, f.map, f.row_bytes, f.layout.tiled != 0, 1u << 22, 256, list_kp);
-    *passes = 0;
-    for (int j = 0; j < n_queries; j += queries_per_launch) {
-        const int n = std::min(queries_per_launch, n_queries - j);
-        const szg::ScanVariant v = szg::scan_variant(quant_bits, f.map, f.layout.tiled != 0, list_kp, collect != 0, masked != 0,
-                                                     szg_index::ring, !szg_index::shape_kernels, scan_group, n, g.block);
-        if (j == 0) {
-            *group = v.group;
-            *lds_bytes = szg::scan_lds_bytes(quant_bits, f.map, list_kp, g.block, v.group);
-        }
-        *passes += (n + v.group - 1) / v.group;
-    }
+    if (const int rc = hook_options(nullptr, &scan_group, nullptr, nullptr, nullptr)) return rc;
+    PlanHook h;
+    if (const int rc = h.rows(dim, quant_bits, 1, collect ? 0 : kp, collect != 0, masked)) return rc;
+    h.in.group = scan_group;
+    h.walk(n_queries, queries_per_launch);
+    *group = h.first.group;
+    *lds_bytes = h.lds_bytes;
+    *passes = h.passes;
     return SZG_OK;
 }
 
-// test hook, host only: does the matrix sweep serve a one-sweep launch (scan_variant's answer under the conditions given,
-// with its passes per launch, LDS bytes and STEPS form)?  Additive: szg_debug_scan_group's answers do not change.
+// does the matrix sweep serve a one-sweep call, in launches of up to 16 (the default queries_per_launch)?
 int szg_debug_scan_matrix(int dim, int quant_bits, int n_queries, int kp, int planes, int norms, int tiled, int masked,
-                          int scan_group, int sketch_matrix, int32_t *serves, int32_t *passes, uint64_t *lds_bytes,
-                          int32_t *steps_form)
+                          int scan_group, int sketch_matrix, int32_t *serves, int32_t *passes, uint64_t *lds_bytes, int32_t *steps_form)
 {
     if (!serves || !passes || !lds_bytes || !steps_form) return fail(SZG_E_INVALID, "null argument");
     if (kp < 0 || n_queries < 1) return fail(SZG_E_INVALID, "kp or n_queries out of range");
-    if (planes != 2 && planes != 3) return fail(SZG_E_INVALID, "planes is 2 or 3");
-    if (scan_group != 0 && scan_group != 1 && scan_group != 2 && scan_group != 4)
-        return fail(SZG_E_INVALID, "scan_group is 0, 1, 2 or 4");
-    if (!szg::sketch_matrix_known(sketch_matrix)) return fail(SZG_E_INVALID, "sketch_matrix is 0, 1 or 2");
-    RowFormat f;
-    const int rc = row_format(dim, quant_bits, &f);
-    if (rc == SZG_E_UNSUPPORTED) return fail(rc, "dimension too large for the LDS-resident query");
-    if (rc) return rc;
-    // (tiled: the caller may only take the tiled layout away from a format that has it)
-    const bool is_tiled = f.layout.tiled != 0 && tiled != 0;
-    const LaunchGeom g = scan_geometry(quant_bits, f.map, f.row_bytes, f.layout.tiled != 0, 1u << 22, 256, kp);
-    *serves = 0;
-    *passes = 0;
-    *lds_bytes = 0;
-    *steps_form = 0;
-    for (int j = 0; j < n_queries; j += szg::kMaxSweepsPerLaunch) {  // (launches of queries_per_launch = 16, the default)
-        const int n = std::min(szg::kMaxSweepsPerLaunch, n_queries - j);
-        const szg::ScanVariant v = szg::scan_variant(quant_bits, f.map, is_tiled, kp, false, masked != 0, szg_index::ring,
-                                                     !szg_index::shape_kernels, scan_group, n, g.block, planes, 0, sketch_matrix,
-                                                     norms != 0);
-        if (j == 0) {
-            *serves = v.matrix;
-            *steps_form = v.matrix_steps;
-            *lds_bytes = szg::scan_lds_bytes(quant_bits, f.map, kp, g.block, v.group, planes, v.matrix != 0);
-        }
-        *passes += (n + v.group - 1) / v.group;
-    }
+    PlanHook h;
+    if (const int rc = h.sketch_rows(dim, quant_bits, kp, false, planes, norms, tiled, masked, scan_group, sketch_matrix, nullptr, nullptr))
+        return rc;
+    h.walk(n_queries, szg::kMaxSweepsPerLaunch);
+    *serves = h.first.matrix;
+    *steps_form = h.first.matrix_steps;
+    *lds_bytes = h.lds_bytes;
+    *passes = h.passes;
     return SZG_OK;
 }
 
-// test hook, host only: which selection the first launch (of up to 16 queries) of a one-sweep call takes under option
-// sketch_select -- scan_variant's answer: *row_lists = 1 where the matrix sweep serves the launch and keeps row lists,
-// 0 where it serves it with the serial inserts or does not serve it (*serves says which)
+// which selection the first launch (of up to 16 queries) of a one-sweep call takes under option sketch_select
 int szg_debug_scan_select(int dim, int quant_bits, int n_queries, int kp, int planes, int norms, int tiled, int masked,
                           int scan_group, int sketch_matrix, int sketch_select, int32_t *serves, int32_t *row_lists)
 {
     if (!serves || !row_lists) return fail(SZG_E_INVALID, "null argument");
     if (kp < 0 || n_queries < 1) return fail(SZG_E_INVALID, "kp or n_queries out of range");
-    if (planes != 2 && planes != 3) return fail(SZG_E_INVALID, "planes is 2 or 3");
-    if (scan_group != 0 && scan_group != 1 && scan_group != 2 && scan_group != 4)
-        return fail(SZG_E_INVALID, "scan_group is 0, 1, 2 or 4");
-    if (!szg::sketch_matrix_known(sketch_matrix)) return fail(SZG_E_INVALID, "sketch_matrix is 0, 1 or 2");
-    if (!szg::sketch_select_known(sketch_select)) return fail(SZG_E_INVALID, "sketch_select is 0 or 1");
-    RowFormat f;
-    const int rc = row_format(dim, quant_bits, &f);
-    if (rc == SZG_E_UNSUPPORTED) return fail(rc, "dimension too large for the LDS-resident query");
-    if (rc) return rc;
-    const bool is_tiled = f.layout.tiled != 0 && tiled != 0;
-    const LaunchGeom g = scan_geometry(quant_bits, f.map, f.row_bytes, f.layout.tiled != 0, 1u << 22, 256, kp);
-    const szg::ScanVariant v = szg::scan_variant(quant_bits, f.map, is_tiled, kp, false, masked != 0, szg_index::ring,
-                                                 !szg_index::shape_kernels, scan_group, std::min(szg::kMaxSweepsPerLaunch, n_queries),
-                                                 g.block, planes, 0, sketch_matrix, norms != 0, sketch_select);
-    *serves = v.matrix;
-    *row_lists = v.matrix && v.row_lists ? 1 : 0;
+    PlanHook h;
+    if (const int rc = h.sketch_rows(dim, quant_bits, kp, false, planes, norms, tiled, masked, scan_group, sketch_matrix, &sketch_select, nullptr))
+        return rc;
+    h.walk(std::min(szg::kMaxSweepsPerLaunch, n_queries), szg::kMaxSweepsPerLaunch);
+    *serves = h.first.matrix;
+    *row_lists = h.first.matrix && h.first.row_lists ? 1 : 0;
     return SZG_OK;
 }
 
-// test hook, host only: the matrix sweep's two-block form (option sketch_wide) for a one-sweep top-k call of n_queries
-// queries split as a call with wide batches splits it -- launches of up to 32 where a launch of 32 qualifies for the
-// form, of up to 16 where it does not.  *serves / *lds_bytes describe the first launch (scan_variant's answer),
-// *passes = passes over the rows of the whole call.
+// the matrix sweep's two-block form (option sketch_wide) for a one-sweep top-k call, split as a call with wide batches
+// splits it
 int szg_debug_scan_wide(int dim, int quant_bits, int n_queries, int kp, int planes, int norms, int tiled, int masked,
-                        int scan_group, int sketch_matrix, int sketch_select, int sketch_wide, int32_t *serves,
-                        int32_t *passes, uint64_t *lds_bytes)
+                        int scan_group, int sketch_matrix, int sketch_select, int sketch_wide, int32_t *serves, int32_t *passes,
+                        uint64_t *lds_bytes)
 {
     if (!serves || !passes || !lds_bytes) return fail(SZG_E_INVALID, "null argument");
     if (kp < 0 || n_queries < 1) return fail(SZG_E_INVALID, "kp or n_queries out of range");
-    if (planes != 2 && planes != 3) return fail(SZG_E_INVALID, "planes is 2 or 3");
-    if (scan_group != 0 && scan_group != 1 && scan_group != 2 && scan_group != 4)
-        return fail(SZG_E_INVALID, "scan_group is 0, 1, 2 or 4");
-    if (!szg::sketch_matrix_known(sketch_matrix)) return fail(SZG_E_INVALID, "sketch_matrix is 0, 1 or 2");
-    if (!szg::sketch_select_known(sketch_select)) return fail(SZG_E_INVALID, "sketch_select is 0 or 1");
-    if (!szg::sketch_wide_known(sketch_wide)) return fail(SZG_E_INVALID, "sketch_wide is 0, 1 or 2");
-    RowFormat f;
-    const int rc = row_format(dim, quant_bits, &f);
-    if (rc == SZG_E_UNSUPPORTED) return fail(rc, "dimension too large for the LDS-resident query");
-    if (rc) return rc;
-    const bool is_tiled = f.layout.tiled != 0 && tiled != 0;
-    const LaunchGeom g = scan_geometry(quant_bits, f.map, f.row_bytes, f.layout.tiled != 0, 1u << 22, 256, kp);
-    auto variant = [&](int n) {
-        return szg::scan_variant(quant_bits, f.map, is_tiled, kp, false, masked != 0, szg_index::ring, !szg_index::shape_kernels,
-                                 scan_group, n, g.block, planes, 0, sketch_matrix, norms != 0, sketch_select, sketch_wide);
-    };
-    const int per_launch = variant(szg::kMatrixWideQueries).wide ? szg::kMatrixWideQueries : szg::kMaxSweepsPerLaunch;
-    *serves = 0;
-    *passes = 0;
-    *lds_bytes = 0;
-    for (int j = 0; j < n_queries; j += per_launch) {
-        const int n = std::min(per_launch, n_queries - j);
-        const szg::ScanVariant v = variant(n);
-        if (j == 0) {
-            *serves = v.wide;
-            *lds_bytes = szg::scan_lds_bytes(quant_bits, f.map, kp, g.block, v.group, planes, v.matrix ? (v.wide ? 2 : 1) : 0);
-        }
-        *passes += (n + v.group - 1) / v.group;
-    }
+    PlanHook h;
+    if (const int rc = h.sketch_rows(dim, quant_bits, kp, false, planes, norms, tiled, masked, scan_group, sketch_matrix, &sketch_select, &sketch_wide))
+        return rc;
+    h.walk(n_queries, h.wide_launches());
+    *serves = h.first.wide;
+    *lds_bytes = h.lds_bytes;
+    *passes = h.passes;
     return SZG_OK;
 }
 
-// test hook, host only: the matrix sweep's collect form for a collect call of n_queries queries with one sweep each --
-// scan_variant's answer per launch (launches of 32 under sketch_wide = 2 where the two-block form qualifies, else of 16)
-int szg_debug_scan_collect(int dim, int quant_bits, int n_queries, int planes, int norms, int tiled, int masked,
-                           int scan_group, int sketch_matrix, int sketch_wide, int32_t *serves, int32_t *wide,
-                           int32_t *passes, uint64_t *lds_bytes, int32_t *steps_form)
+// the matrix sweep's collect form for a collect call of n_queries queries with one sweep each (launches of 32: sketch_wide = 2)
+int szg_debug_scan_collect(int dim, int quant_bits, int n_queries, int planes, int norms, int tiled, int masked, int scan_group,
+                           int sketch_matrix, int sketch_wide, int32_t *serves, int32_t *wide, int32_t *passes, uint64_t *lds_bytes, int32_t *steps_form)
 {
     if (!serves || !wide || !passes || !lds_bytes || !steps_form) return fail(SZG_E_INVALID, "null argument");
     if (n_queries < 1) return fail(SZG_E_INVALID, "n_queries out of range");
-    if (planes != 2 && planes != 3) return fail(SZG_E_INVALID, "planes is 2 or 3");
-    if (scan_group != 0 && scan_group != 1 && scan_group != 2 && scan_group != 4)
-        return fail(SZG_E_INVALID, "scan_group is 0, 1, 2 or 4");
-    if (!szg::sketch_matrix_known(sketch_matrix)) return fail(SZG_E_INVALID, "sketch_matrix is 0, 1 or 2");
-    if (!szg::sketch_wide_known(sketch_wide)) return fail(SZG_E_INVALID, "sketch_wide is 0, 1 or 2");
-    RowFormat f;
-    const int rc = row_format(dim, quant_bits, &f);
-    if (rc == SZG_E_UNSUPPORTED) return fail(rc, "dimension too large for the LDS-resident query");
-    if (rc) return rc;
-    const bool is_tiled = f.layout.tiled != 0 && tiled != 0;
-    const LaunchGeom g = scan_geometry(quant_bits, f.map, f.row_bytes, f.layout.tiled != 0, 1u << 22, 256, 0);
-    auto variant = [&](int n) {
-        return szg::scan_variant(quant_bits, f.map, is_tiled, 0, true, masked != 0, szg_index::ring, !szg_index::shape_kernels,
-                                 scan_group, n, g.block, planes, 0, sketch_matrix, norms != 0, 0, sketch_wide);
-    };
-    const int per_launch = sketch_wide == 2 && variant(szg::kMatrixWideQueries).wide ? szg::kMatrixWideQueries : szg::kMaxSweepsPerLaunch;
-    *serves = *wide = *passes = *steps_form = 0;
-    *lds_bytes = 0;
-    for (int j = 0; j < n_queries; j += per_launch) {
-        const int n = std::min(per_launch, n_queries - j);
-        const szg::ScanVariant v = variant(n);
-        if (j == 0) {
-            *serves = v.matrix;
-            *wide = v.wide;
-            *steps_form = v.matrix_steps;
-            *lds_bytes = szg::scan_lds_bytes(quant_bits, f.map, 0, g.block, v.group, planes, v.matrix ? (v.wide ? 2 : 1) : 0);
-        }
-        *passes += (n + v.group - 1) / v.group;
-    }
+    PlanHook h;
+    if (const int rc = h.sketch_rows(dim, quant_bits, 0, true, planes, norms, tiled, masked, scan_group, sketch_matrix, nullptr, &sketch_wide))
+        return rc;
+    h.walk(n_queries, sketch_wide == 2 ? h.wide_launches() : szg::kMaxSweepsPerLaunch);
+    *serves = h.first.matrix;
+    *wide = h.first.wide;
+    *steps_form = h.first.matrix_steps;
+    *lds_bytes = h.lds_bytes;
+    *passes = h.passes;
     return SZG_OK;
 }
 
@@ -770,25 +751,21 @@ int szg_debug_merge_short_plan(int n_lists, int m, int kp, int32_t *fits, int32_
     return SZG_OK;
 }
 
-// test hook, host only: the ring depth a one-sweep launch of n_queries queries takes under options scan_group and
-// scan_group_ring (scan_variant's answer), and the values of scan_group_ring this library accepts beside 0
+// the ring depth a one-sweep launch takes under options scan_group and scan_group_ring, and the depths the library carries
 int szg_debug_scan_group_ring(int dim, int quant_bits, int kp, int scan_group, int n_queries, int scan_group_ring,
                               int32_t *ring_depth, int32_t *depths, int32_t *n_depths)
 {
     if (!ring_depth || !depths || !n_depths) return fail(SZG_E_INVALID, "null argument");
     if (kp < 0 || n_queries < 1 || n_queries > szg::kMaxSweepsPerLaunch) return fail(SZG_E_INVALID, "kp or n_queries out of range");
-    if (scan_group != 0 && scan_group != 1 && scan_group != 2 && scan_group != 4)
-        return fail(SZG_E_INVALID, "scan_group is 0, 1, 2 or 4");
+    if (const int rc = hook_options(nullptr, &scan_group, nullptr, nullptr, nullptr)) return rc;
     if (!szg::scan_group_ring_known(scan_group_ring))
         return fail(SZG_E_INVALID, "scan_group_ring is 0 or a ring depth the library carries");
-    RowFormat f;
-    const int rc = row_format(dim, quant_bits, &f);
-    if (rc == SZG_E_UNSUPPORTED) return fail(rc, "dimension too large for the LDS-resident query");
-    if (rc) return rc;
-    const LaunchGeom g = scan_geometry(quant_bits, f.map, f.row_bytes, f.layout.tiled != 0, 1u << 22, 256, kp);
-    *ring_depth = szg::scan_variant(quant_bits, f.map, f.layout.tiled != 0, kp, false, false, szg_index::ring,
-                                    !szg_index::shape_kernels, scan_group, n_queries, g.block, 3, scan_group_ring)
-                      .ring_depth;
+    PlanHook h;
+    if (const int rc = h.rows(dim, quant_bits, 1, kp, false, 0)) return rc;
+    h.in.group = scan_group;
+    h.in.group_ring = scan_group_ring;
+    h.walk(n_queries, szg::kMaxSweepsPerLaunch);
+    *ring_depth = h.first.ring_depth;
     depths[0] = szg::kGroupRingBase;
     depths[1] = szg::kGroupRingAlt;
     *n_depths = szg::kGroupRingAlt != szg::kGroupRingBase ? 2 : 1;

@@ -226,10 +226,17 @@ bool sketch_wide_serves(const szg_index *sk, const Shard *sh, int kp, int list_o
     if (sk->sketch_wide == 1 || sh->has_dead || kp > 64) return false;
     const LaunchGeom g = scan_geometry(sk, sh, kp, true);
     const int m = collect ? 0 : sketch_list_len(list_opt, kp, g.grid);
-    return szg::scan_variant(sk->bits, sk->map, sk->layout.tiled != 0, m, collect, false, sk->ring, !sk->shape_kernels,
-                             sk->scan_group, szg::kMatrixWideQueries, g.block, scan_planes(sk), sk->scan_group_ring,
-                             sk->sketch_matrix, true, sk->sketch_select, sk->sketch_wide)
-               .wide != 0;
+    szg::ScanPlanIn in{sk->bits, sk->map, sk->layout.tiled != 0, m, collect, false, sk->ring, !sk->shape_kernels};
+    in.group = sk->scan_group;
+    in.n_queries = szg::kMatrixWideQueries;
+    in.block = g.block;
+    in.planes = scan_planes(sk);
+    in.group_ring = sk->scan_group_ring;
+    in.matrix_opt = sk->sketch_matrix;
+    in.norms = true;
+    in.select_opt = sk->sketch_select;
+    in.wide_opt = sk->sketch_wide;
+    return szg::scan_variant(in).wide != 0;
 }
 
 // top-k pass for the nq staged queries of one shard: scan -> merges -> rerank -> D2H (async)
