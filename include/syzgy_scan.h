@@ -710,6 +710,15 @@ int szg_reset_stats(szg_index *ix);
  *                             batches and launches of up to 32, whatever its length.  Lists, keys, the drop bound and
  *                             answers are the same bit for bit; szg_stats.scan_bytes counts one pass per 32 queries of a
  *                             wide launch.  Other values are refused
+ *     sketch_share        0   the matrix sweep's shared form: ONE launch of 33 to 64 queries as two column groups of 32 on
+ *                             paired blocks that walk the same rows, so that the second reader of a row finds it on the
+ *                             die -- where the two-block form (sketch_wide) serves the shard and it has no dead rows.
+ *                             0 = automatic: a sketch call of 136 one-sweep queries or more under the default query_batch
+ *                             and queries_per_launch takes batches of 64 queries, one launch each, between its first and
+ *                             last batch of 4 (shorter calls keep their plan); 1 = never; 2 = every sketch call of more
+ *                             than 32 queries takes batches of up to 64 from its first query on.  Keys and answers are
+ *                             the same bit for bit; szg_stats.scan_bytes counts one pass per column group, two for a
+ *                             shared launch.  Other values are refused
  *     sketch_bulk         0   crowded tiles of the row lists (sketch_select): a tile of 16 rows whose pre-filter lets
  *                             many (query, row) pairs of a wave through -- a wave's first tiles, while its lists fill --
  *                             merges each list with its 16 candidates whole, by a fixed sorting network, where the
@@ -867,6 +876,19 @@ int szg_debug_scan_wide(int dim, int quant_bits, int n_queries, int kp, int plan
                         int32_t *passes, uint64_t *lds_bytes);
 
 /*
+ * Test hook, host only: the matrix sweep's shared form (option sketch_share) for a one-sweep top-k call of n_queries
+ * queries through the sketch, under the conditions of szg_debug_scan_wide and the default query_batch and
+ * queries_per_launch.  *serves = 1: a launch of min(n_queries, 64) queries takes the shared form (33 queries or more);
+ * *slices = the row slices S of such a launch (its grid is 2 S, each query gets S block lists), 0 where it does not
+ * serve; *lds_bytes = that launch's LDS.  The call as it is split: batches[0 .. min(*n_batches, batch_capacity)) = the
+ * queries of its batches, *launches = its scan launches, *passes = its passes over the rows (two per shared launch).
+ */
+int szg_debug_scan_share(int dim, int quant_bits, int n_queries, int kp, int planes, int norms, int tiled, int masked,
+                         int scan_group, int sketch_matrix, int sketch_select, int sketch_wide, int sketch_share,
+                         int32_t *serves, int32_t *launches, int32_t *passes, int32_t *slices, uint64_t *lds_bytes,
+                         int32_t *batches, int32_t batch_capacity, int32_t *n_batches);
+
+/*
  * Test hook, host only: does the matrix sweep's collect form (radius searches through the sketch, option sketch_radius)
  * serve a collect call of n_queries queries with one sweep each, under the conditions of szg_debug_scan_matrix?  The
  * call is split into launches of up to 32 queries where sketch_wide = 2 and a launch of 32 qualifies for the two-block
@@ -895,7 +917,7 @@ int szg_debug_scan_group_ring(int dim, int quant_bits, int kp, int scan_group, i
 
 /*
  * Test hook, host only: would szg_set_option accept `value` for the one-sweep kernel's option `name` (scan_group,
- * scan_group_ring, scan_norms, sketch_planes, sketch_matrix, sketch_select, sketch_wide, sketch_bulk, sketch_radius)?  SZG_OK, or SZG_E_INVALID with szg_set_option's text; any other name is refused.
+ * scan_group_ring, scan_norms, sketch_planes, sketch_matrix, sketch_select, sketch_wide, sketch_share, sketch_bulk, sketch_radius)?  SZG_OK, or SZG_E_INVALID with szg_set_option's text; any other name is refused.
  */
 int szg_debug_option_check(const char *name, int64_t value);
 

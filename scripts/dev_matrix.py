@@ -2,7 +2,8 @@
 1M x 768 float32 cosine (the headline's handle), calls of 1, 2, 3, 4, 16 and 32 queries under sketch_matrix = 2 (the
 matrix sweep whatever the count) with row lists (sketch_select = 0) and with the serial inserts (sketch_select = 1),
 and under sketch_matrix = 1 (G = 1, 2, 4) -- all three with sketch_wide = 1 -- and the wide column: the two-block form
-(sketch_wide = 2, row lists) at 17, 32, 48 and 64 queries, one launch per 32.  SZG_NO_EARLY_TAIL=1 keeps a 16-query
+(sketch_wide = 2, row lists) at 17, 32, 48 and 64 queries, one launch per 32.  The share column: the shared form
+(sketch_wide = 2, sketch_share = 2) at 33, 48 and 64 queries in ONE launch, beside the wide column's 64 (two launches).  SZG_NO_EARLY_TAIL=1 keeps a 16-query
 call one launch.  The rows and wide columns run under sketch_bulk = 1 (rounds only) and 0 (crowded tiles merged whole), and
 with SZG_BULK_SWEEP=1 under the thresholds 32, 48, 64, 96 and 128 as well.  A library from before sketch_select, sketch_wide
 or sketch_bulk (an A/B run through SZG_LIB_PATH) shows what it has.
@@ -40,13 +41,23 @@ with ScanIndex(dim, 32, SZG_COSINE) as ix:
                 label, nq, st["scan_launches"] / reps, passes / reps, st["scan_ms"] / max(st["timed_launches"], 1),
                 st["scan_ms"] / max(passes, 1), st["sketch_queries"], reps * nq), flush=True)
 
-    for sm, sel, label in ((2, 0, "rows"), (2, 0, "wide"), (2, 1, "serial"), (1, 0, "grouped")):
+    for sm, sel, label in ((2, 0, "rows"), (2, 0, "wide"), (2, 0, "share"), (2, 1, "serial"), (1, 0, "grouped")):
         ix.set_option("sketch_matrix", sm)
         try:
-            ix.set_option("sketch_wide", 2 if label == "wide" else 1)
+            ix.set_option("sketch_wide", 2 if label in ("wide", "share") else 1)
         except Exception:
-            if label == "wide":
+            if label in ("wide", "share"):
                 continue
+        # the shared form (option sketch_share = 2): 33, 48 and 64 queries in ONE launch of two column groups on paired
+        # blocks, beside the wide column's "64" (two launches); every other column keeps it off
+        try:
+            ix.set_option("sketch_share", 2 if label == "share" else 1)
+        except Exception:
+            if label == "share":
+                continue
+        if label == "share":
+            measure("share", (33, 48, 64))
+            continue
         try:
             ix.set_option("sketch_select", sel)
         except Exception:

@@ -52,6 +52,14 @@ for opts in ${SWEEP_BULK_SETS-sketch_bulk=1 sketch_bulk=2}; do
       tests/test_gpu_sketch_select.py tests/test_gpu_sketch_wide.py tests/test_gpu_sketch_bulk.py \
       tests/test_gpu_certificates.py -m gpu -q -x
 done
+# the matrix sweep's shared form off (1) and in every sketch call of more than 32 queries (2), on the same files and its
+# own (SWEEP_SHARE_SETS="" skips them)
+for opts in ${SWEEP_SHARE_SETS-sketch_share=1 sketch_share=2}; do
+  run "sketched handles, $opts" tests/test_gpu_sketch.py tests/test_gpu_sketch_default.py tests/test_gpu_sketch_lists.py \
+      tests/test_gpu_sketch_state.py tests/test_gpu_sketch_planes.py tests/test_gpu_sketch_matrix.py \
+      tests/test_gpu_sketch_select.py tests/test_gpu_sketch_wide.py tests/test_gpu_sketch_bulk.py \
+      tests/test_gpu_sketch_share.py tests/test_gpu_certificates.py -m gpu -q -x
+done
 # the shared sweeps without the resident row norms (a test hook of its own: an environment variable read once per process)
 if [ -z "$SWEEP_SKIP_NORMS" ]; then
   opts=""

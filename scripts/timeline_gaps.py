@@ -21,7 +21,9 @@ if not sw:
 if not sw:
     sw = [e for e in ev if e[2].startswith("scan_kernel<8")]
 print("sweeps:", len(sw), "name:", sw[0][2] if sw else None)
-wide = [e for e in sw if re.search(r"scan_mx_kernel<.*, 2>$", e[2])]  # the two-block form: launches of a long call
+# the two-block form: launches of a long call -- wide launches of 32 queries, or shared launches of up to 64 (the same
+# name: their argument types, cut off above, tell them apart); the collect flag may follow the block count
+wide = [e for e in sw if re.search(r"scan_mx_kernel<.*, 2(, false)?>$", e[2])]
 if wide:
     # the LAST long call (the timed one; the settling loop's 64-query calls keep one block): its run of wide sweeps --
     # more than a millisecond apart is another call -- with the one-block sweeps of its first and last batches

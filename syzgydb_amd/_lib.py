@@ -55,7 +55,7 @@ EXPORTS = [
     # host-only test hook
     "szg_debug_scan_plan", "szg_debug_scan_group", "szg_debug_reorder_plan", "szg_debug_option_check",
     "szg_debug_scan_group_ring", "szg_debug_merge_short_plan", "szg_debug_scan_matrix",
-    "szg_debug_scan_select", "szg_debug_scan_wide", "szg_debug_scan_collect",
+    "szg_debug_scan_select", "szg_debug_scan_wide", "szg_debug_scan_collect", "szg_debug_scan_share",
     # who owns device memory: the counters and the refusal countdown (added under ABI 4)
     "szg_debug_device_memory", "szg_debug_refuse_device_alloc",
     # the certificate trace: what each pass handed to certification (added under ABI 4)
@@ -402,6 +402,11 @@ def load():
         L.szg_debug_scan_wide.restype = ctypes.c_int
         L.szg_debug_scan_wide.argtypes = ([ctypes.c_int] * 12 + [ctypes.POINTER(ctypes.c_int32)] * 2 +
                                           [ctypes.POINTER(ctypes.c_uint64)])
+    if hasattr(L, "szg_debug_scan_share"):
+        L.szg_debug_scan_share.restype = ctypes.c_int
+        L.szg_debug_scan_share.argtypes = ([ctypes.c_int] * 13 + [ctypes.POINTER(ctypes.c_int32)] * 4 +
+                                           [ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_int32), ctypes.c_int32,
+                                            ctypes.POINTER(ctypes.c_int32)])
     if hasattr(L, "szg_debug_scan_collect"):
         L.szg_debug_scan_collect.restype = ctypes.c_int
         L.szg_debug_scan_collect.argtypes = ([ctypes.c_int] * 10 + [ctypes.POINTER(ctypes.c_int32)] * 3 +

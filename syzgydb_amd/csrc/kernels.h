@@ -134,6 +134,20 @@ __host__ __device__ inline uint32_t &scan_thr_ukey(ScanArgs &a, int s)
     return s < kMaxSweepsPerLaunch ? a.thr_ukeys[s] : a.thr_ukeys_hi[s - kMaxSweepsPerLaunch];
 }
 
+// The matrix sweep's shared launch (option sketch_share; scan_plan.h share_map) holds up to kMatrixShareQueries queries.
+// What it needs beyond ScanArgs rides behind it in a struct of its own, which only the shared kernels take: ScanArgs --
+// its size is part of every scan kernel's descriptor -- and with it the code of every other kernel stay as they were.
+struct ScanShareHi {
+    // the constants of queries kMatrixWideQueries .. kMatrixShareQueries - 1 of the launch (ScanArgs holds the first 32)
+    float qscale[kMatrixShareQueries - kMatrixWideQueries], qconst[kMatrixShareQueries - kMatrixWideQueries],
+        qnorm2[kMatrixShareQueries - kMatrixWideQueries];
+    int share;  // option sketch_share: 1 = a launch never takes the shared form
+};
+struct ScanShareArgs {
+    ScanArgs a;
+    ScanShareHi hi;
+};
+
 inline bool scan_masked(const ScanArgs &a) { return a.live_bits != nullptr || a.allow_bits != nullptr; }
 // what scan_variant decides from (scan_plan.h), for the launch `a` describes at `block` threads
 inline ScanPlanIn scan_plan_in(int qbits, const ScanArgs &a, int block)
@@ -188,6 +202,20 @@ SZG_DECL_SCAN_V(launch_scan_mx_m0) SZG_DECL_SCAN_V(launch_scan_mx_m1)
 SZG_DECL_SCAN_V(launch_scan_mxc_m0) SZG_DECL_SCAN_V(launch_scan_mxc_m1)
 #undef SZG_DECL_G8
 #undef SZG_DECL_SCAN_V
+// The matrix sweep's shared form (kernels_scan_mx.hip with -DSZG_MX_SHARE: objects of their own): ONE launch of 33 ..
+// kMatrixShareQueries top-k queries over 8-bit tiled rows, on a grid of 2 S blocks (share_map); the lists go to
+// a.block_lists as [n_queries][S][a.kp].  Everything that is not exactly that form is hipErrorInvalidValue.
+hipError_t launch_scan_share(int qbits, int metric, const ScanArgs &a, const ScanShareHi &hi, int grid, int block,
+                             hipStream_t stream);
+hipError_t launch_scan_mxs_m0(const ScanShareArgs &s, const ScanVariant &v, int grid, int block, size_t lds, hipStream_t stream);
+hipError_t launch_scan_mxs_m1(const ScanShareArgs &s, const ScanVariant &v, int grid, int block, size_t lds, hipStream_t stream);
+// what scan_variant decides from for a shared launch
+inline ScanPlanIn scan_share_plan_in(int qbits, const ScanArgs &a, const ScanShareHi &hi, int block)
+{
+    ScanPlanIn in = scan_plan_in(qbits, a, block);
+    in.share_opt = hi.share;
+    return in;
+}
 // ---- shared (multi-query) sweeps (mq_device.h, kernels_mq*.hip): every row width, cosine and Euclidean ----------
 // queries per shared sweep: 48 (3 blocks of 16) for the int8 sweeps (4- and 8-bit rows), whose LDS images are 2-4
 // bytes per element and query; 96 for the bfloat16 sweeps (16-, 32- and 64-bit rows, and 8-bit rows in batches of

@@ -292,6 +292,20 @@ hipError_t launch_scan(int qbits, int metric, const ScanArgs &a, int grid, int b
     }
 }
 
+// the matrix sweep's shared launch: scan_variant must name the shared form for exactly this launch
+hipError_t launch_scan_share(int qbits, int metric, const ScanArgs &a, const ScanShareHi &hi, int grid, int block,
+                             hipStream_t stream)
+{
+    if (qbits != 8 || (metric != kCosine && metric != kEuclidean) || a.collect || scan_masked(a)) return hipErrorInvalidValue;
+    const ScanVariant v = scan_variant(scan_share_plan_in(qbits, a, hi, block));
+    if (!v.matrix || !v.share) return hipErrorInvalidValue;
+    const size_t lds = scan_lds_bytes(qbits, a.map, a.kp, block, v.group, a.planes, v.matrix_blocks());
+    ScanShareArgs s;
+    s.a = a;
+    s.hi = hi;
+    return (metric == kCosine ? launch_scan_mxs_m1 : launch_scan_mxs_m0)(s, v, grid, block, lds, stream);
+}
+
 hipError_t launch_merge(const uint64_t *in, int n_lists, int kp, int n_queries, uint64_t *out,
                         hipStream_t stream, int out_stride)
 {

@@ -117,9 +117,25 @@ constexpr int mx_ring()
 // bit -- but there are no lists: a slot's key is tested against its query's threshold (ScanArgs::thr_ukeys, staged in
 // LDS beside the constants) and the passing rows are appended to that query's buffer, as scan_kernel's collect form
 // does it.  Instantiated with ROWS set (neither list form is alive in it).
+// With -DSZG_MX_SHARE the file builds the SHARED form of the two-block row-list kernel instead (objects of their own;
+// DESIGN.md 4.5 item 13, option sketch_share): a launch of 33 .. kMatrixShareQueries queries as two column groups of 32 on
+// a grid of 2 S blocks.  share_map (scan_plan.h) gives a block its row slice and its group; the block stages only its
+// own group's image, constants and lists and takes one turn of the loop over the groups; the two blocks of a slice walk
+// the same tiles, so whichever reads a line second finds it in its XCD's L2 or in the Infinity Cache.  No block waits
+// for another and nothing depends on where or when a partner runs.  The keys are formed by the same operations.
+#ifdef SZG_MX_SHARE
+#define SZG_MX_KERNEL_ARGS const ScanShareArgs sa
+#else
+#define SZG_MX_KERNEL_ARGS const ScanArgs a
+#endif
 template <int METRIC, int STEPS, bool NT, bool ROWS, int NB = 1, bool COLLECT = false>
-__global__ __launch_bounds__(256, (ROWS && NB == 1 && STEPS != 0) ? 4 : 2) void scan_mx_kernel(const ScanArgs a)
+__global__ __launch_bounds__(256, (ROWS && NB == 1 && STEPS != 0) ? 4 : 2) void scan_mx_kernel(SZG_MX_KERNEL_ARGS)
 {
+#ifdef SZG_MX_SHARE
+    static_assert(NB == 2 && ROWS && !COLLECT, "the shared form: two column blocks, row lists, top-k");
+    const ScanArgs &a = sa.a;
+    const ShareSlot slot = share_map(blockIdx.x, gridDim.x);
+#endif
     static_assert(NB == 1 || (NB == 2 && ROWS), "two column blocks: row lists only");
     static_assert(!COLLECT || ROWS, "the collect form is instantiated once per shape");
     static_assert(16 * NB <= kMatrixWideQueries, "the launch's constants are sized by kMatrixWideQueries");
@@ -147,8 +163,13 @@ __global__ __launch_bounds__(256, (ROWS && NB == 1 && STEPS != 0) ? 4 : 2) void 
     const int c = lane >> 4;
     const RowLayout lay{a.pitch, a.tiled, a.steps};
     const uint64_t n_tiles = ((uint64_t)a.n_rows + 15) / 16;
+#ifdef SZG_MX_SHARE
+    const uint64_t tile_stride = (uint64_t)slot.slices * nwaves;
+    const uint64_t tile_first = (uint64_t)slot.slice * nwaves + wave;
+#else
     const uint64_t tile_stride = (uint64_t)gridDim.x * nwaves;
     const uint64_t tile_first = (uint64_t)blockIdx.x * nwaves + wave;
+#endif
     const uint64_t n_it = tile_first < n_tiles ? (n_tiles - tile_first + tile_stride - 1) / tile_stride : 0;
     const uint64_t last_row = a.n_rows ? (uint64_t)a.n_rows - 1 : 0;
     // (a row past the end of the last tile, or a tile past the wave's last: a valid row, read and discarded)
@@ -156,8 +177,13 @@ __global__ __launch_bounds__(256, (ROWS && NB == 1 && STEPS != 0) ? 4 : 2) void 
         return a.rows + piece_offset(lay, min(tile * 16 + trow, last_row), (uint32_t)c);
     };
 
+#ifdef SZG_MX_SHARE
+    // (one turn, for the block's own group; the launcher admits 33 .. 64 queries: both groups hold a live query)
+    for (int qi = (int)slot.group * kQ, turn = 0; turn < 1 && qi < a.n_queries; turn++) {
+#else
     for (int qi = 0; qi < a.n_queries; qi += kQ) {
         if (qi) __syncthreads();  // the previous group's lists have been merged, its image is free
+#endif
         // column x of the group holds query min(qi + x, n_queries - 1): the idle columns of the launch's last group score
         // its last query again, offer nothing and write no lists
         for (int i0 = tid; i0 < NB * n16; i0 += blockDim.x) {
@@ -173,7 +199,14 @@ __global__ __launch_bounds__(256, (ROWS && NB == 1 && STEPS != 0) ? 4 : 2) void 
 #pragma unroll
         for (int x = 0; x < kQ; x++) {
             const int q = min(qi + x, a.n_queries - 1);  // (block-uniform: scalar loads of the arguments)
+#ifdef SZG_MX_SHARE
+            const bool hi_ = q >= kMatrixWideQueries;  // (q < kMatrixShareQueries: the launcher's bound)
+            const float qs = hi_ ? sa.hi.qscale[q - kMatrixWideQueries] : a.qscale[q];
+            const float qc = hi_ ? sa.hi.qconst[q - kMatrixWideQueries] : a.qconst[q];
+            const float qn = hi_ ? sa.hi.qnorm2[q - kMatrixWideQueries] : a.qnorm2[q];
+#else
             const float qs = a.qscale[q], qc = a.qconst[q], qn = a.qnorm2[q];
+#endif
             [[maybe_unused]] uint32_t tk = 0;
             if constexpr (COLLECT) tk = q < kMaxSweepsPerLaunch ? a.thr_ukeys[q] : a.thr_ukeys_hi[q - kMaxSweepsPerLaunch];
             if (tid == x) {
@@ -472,8 +505,13 @@ __global__ __launch_bounds__(256, (ROWS && NB == 1 && STEPS != 0) ? 4 : 2) void 
         if constexpr (!COLLECT) {
             __syncthreads();
             for (int x = 0; x < kQ && qi + x < a.n_queries; x++)  // (block-uniform)
+#ifdef SZG_MX_SHARE
+                block_merge_lists(lists + (size_t)x * nwaves * a.kp, nwaves, a.kp,
+                                  a.block_lists + ((size_t)(qi + x) * slot.slices + slot.slice) * a.kp, tid, blockDim.x);
+#else
                 block_merge_lists(lists + (size_t)x * nwaves * a.kp, nwaves, a.kp,
                                   a.block_lists + ((size_t)(qi + x) * gridDim.x + blockIdx.x) * a.kp, tid, blockDim.x);
+#endif
         }
         // loads and stores share one vmcnt on gfx9: drain the list stores once per group, so that the next group's ring
         // gets counted waits (as scan_kernel does)
@@ -481,7 +519,19 @@ __global__ __launch_bounds__(256, (ROWS && NB == 1 && STEPS != 0) ? 4 : 2) void 
     }
 }
 
-#ifndef SZG_MX_COLLECT
+#if defined(SZG_MX_SHARE)
+// the rows' loads of the shared form: streamed past the caches like the two-block form's (1), or plain (0) -- the second
+// reader of a line has to find it on the die (DESIGN.md 6, round 15 keeps the measured choice)
+#ifndef SZG_MX_SHARE_NT
+#define SZG_MX_SHARE_NT 1
+#endif
+template <int STEPS>
+hipError_t launch_mxs_steps(const ScanShareArgs &s, int grid, int block, size_t lds, hipStream_t stream)
+{
+    hipLaunchKernelGGL((scan_mx_kernel<SZG_SCAN_METRIC, STEPS, SZG_MX_SHARE_NT != 0, true, 2>), dim3(grid), dim3(block), lds, stream, s);
+    return hipGetLastError();
+}
+#elif !defined(SZG_MX_COLLECT)
 template <int STEPS>
 hipError_t launch_mx_steps(const ScanArgs &a, bool rows, bool wide, int grid, int block, size_t lds, hipStream_t stream)
 {
@@ -507,7 +557,30 @@ hipError_t launch_mxc_steps(const ScanArgs &a, bool wide, int grid, int block, s
 // (defined by its qualified name: it has to match its declaration in kernels.h)
 #define SZG_CAT2(a, b) a##b
 #define SZG_CAT(a, b) SZG_CAT2(a, b)
-#ifdef SZG_MX_COLLECT
+#if defined(SZG_MX_SHARE)
+// the shared form of ONE metric (objects of their own, -DSZG_MX_SHARE)
+hipError_t szg::SZG_CAT(launch_scan_mxs_m, SZG_SCAN_METRIC)(const ScanShareArgs &s, const ScanVariant &v, int grid, int block,
+                                                          size_t lds, hipStream_t stream)
+{
+    const ScanArgs &a = s.a;
+    // (scan_variant's conditions, once more; and exactly the planned form: unmasked top-k with row lists, 33 .. 64 queries,
+    // an even grid -- share_map pairs its blocks -- and the two-block LDS)
+    if (!v.matrix || !v.share || v.wide || !v.row_lists || !v.nontemporal || !a.tiled || a.steps == 0 ||
+        (int)a.steps * 4 != a.map.r16 || a.planes != 2 || !a.row_norm || !a.block_lists || a.kp < 1 || a.kp > kRowListMax ||
+        !matrix_row_lists(a.kp, a.select) || a.collect || scan_masked(a) || a.wide == 1 || s.hi.share == 1 || block < 64 ||
+        block > 256 || block % 64 || lds > 64u * 1024u)
+        return hipErrorInvalidValue;
+    if (a.n_queries <= kMatrixWideQueries || a.n_queries > kMatrixShareQueries) return hipErrorInvalidValue;
+    if (grid < 2 || grid % 2) return hipErrorInvalidValue;
+    if (lds != scan_lds_bytes(8, a.map, a.kp, block, kMatrixWideQueries, a.planes, 2)) return hipErrorInvalidValue;
+    if (v.matrix_steps != matrix_steps_form((int)a.steps)) return hipErrorInvalidValue;
+    switch (v.matrix_steps) {
+    case 12: return launch_mxs_steps<12>(s, grid, block, lds, stream);
+    case 6: return launch_mxs_steps<6>(s, grid, block, lds, stream);
+    default: return launch_mxs_steps<0>(s, grid, block, lds, stream);
+    }
+}
+#elif defined(SZG_MX_COLLECT)
 // the collect form of ONE metric (objects of their own, -DSZG_MX_COLLECT): v names the form
 hipError_t szg::SZG_CAT(launch_scan_mxc_m, SZG_SCAN_METRIC)(const ScanArgs &a, const ScanVariant &v, int grid, int block,
                                                           size_t lds, hipStream_t stream)

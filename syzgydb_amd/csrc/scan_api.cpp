@@ -723,6 +723,53 @@ int szg_debug_scan_wide(int dim, int quant_bits, int n_queries, int kp, int plan
     return SZG_OK;
 }
 
+// the matrix sweep's shared form (option sketch_share) for a one-sweep top-k call of n_queries through the sketch under the
+// default query_batch and queries_per_launch: whether a launch of min(n_queries, 64) takes it, and the call's batches,
+// launches and passes as sketch_call_plan, sketch_plan_batch and enqueue_topk split it
+int szg_debug_scan_share(int dim, int quant_bits, int n_queries, int kp, int planes, int norms, int tiled, int masked,
+                         int scan_group, int sketch_matrix, int sketch_select, int sketch_wide, int sketch_share, int32_t *serves,
+                         int32_t *launches, int32_t *passes, int32_t *slices, uint64_t *lds_bytes, int32_t *batches,
+                         int32_t batch_capacity, int32_t *n_batches)
+{
+    if (!serves || !launches || !passes || !slices || !lds_bytes || !n_batches || (!batches && batch_capacity > 0))
+        return fail(SZG_E_INVALID, "null argument");
+    if (kp < 0 || n_queries < 1 || batch_capacity < 0) return fail(SZG_E_INVALID, "kp, n_queries or batch_capacity out of range");
+    if (!szg::sketch_share_known(sketch_share)) return fail(SZG_E_INVALID, "sketch_share is 0, 1 or 2");
+    PlanHook h;
+    if (const int rc = h.sketch_rows(dim, quant_bits, kp, false, planes, norms, tiled, masked, scan_group, sketch_matrix, &sketch_select, &sketch_wide))
+        return rc;
+    h.in.share_opt = sketch_share;
+    const bool wide_serves = h.wide_launches() == szg::kMatrixWideQueries;
+    h.in.n_queries = std::min(n_queries, szg::kMatrixShareQueries);
+    const szg::ScanVariant v = szg::scan_variant(h.in);
+    *serves = v.share;
+    *slices = v.share ? szg::share_slices(szg::share_grid(h.g.grid)) : 0;
+    *lds_bytes = szg::scan_lds_bytes(h.in.qbits, h.in.map, h.in.kp, h.in.block, v.group, h.in.planes, v.matrix_blocks());
+    // the call's plan (sketch_call_plan): shared batches need a shared launch of 64 to be served
+    h.in.n_queries = szg::kMatrixShareQueries;
+    const bool share_serves = wide_serves && szg::scan_variant(h.in).share != 0;
+    const int wide = !wide_serves || n_queries <= szg::kMatrixQueries ? 0 : (sketch_wide == 2 ? 2 : (n_queries >= kWideCallMin ? 1 : 0));
+    const int share = !share_serves || n_queries <= szg::kMatrixWideQueries
+                          ? 0
+                          : (sketch_share == 2 ? 2 : (wide == 1 && n_queries >= kShareCallMin ? 1 : 0));
+    const std::vector<int> sizes = sketch_batch_sizes(n_queries, wide, share, 16);
+    *n_batches = (int32_t)sizes.size();
+    *launches = *passes = 0;
+    for (size_t i = 0; i < sizes.size(); i++) {
+        if ((int32_t)i < batch_capacity) batches[i] = sizes[i];
+        const int nq = sizes[i];
+        const int per = share && nq > szg::kMatrixWideQueries
+                            ? szg::kMatrixShareQueries
+                            : ((wide || share) && nq > szg::kMatrixQueries ? szg::kMatrixWideQueries : szg::kMaxSweepsPerLaunch);
+        for (int j = 0; j < nq; j += per) {
+            h.in.n_queries = std::min(per, nq - j);
+            *launches += 1;
+            *passes += (h.in.n_queries + szg::scan_variant(h.in).group - 1) / szg::scan_variant(h.in).group;
+        }
+    }
+    return SZG_OK;
+}
+
 // the matrix sweep's collect form for a collect call of n_queries queries with one sweep each (launches of 32: sketch_wide = 2)
 int szg_debug_scan_collect(int dim, int quant_bits, int n_queries, int planes, int norms, int tiled, int masked, int scan_group,
                            int sketch_matrix, int sketch_wide, int32_t *serves, int32_t *wide, int32_t *passes, uint64_t *lds_bytes, int32_t *steps_form)

@@ -670,6 +670,7 @@ static const char *scan_option_refusal(const std::string &n, int64_t value, bool
     if (n == "sketch_matrix") return szg::sketch_matrix_known(value) ? nullptr : "sketch_matrix is 0, 1 or 2";
     if (n == "sketch_select") return szg::sketch_select_known(value) ? nullptr : "sketch_select is 0 or 1";
     if (n == "sketch_wide") return szg::sketch_wide_known(value) ? nullptr : "sketch_wide is 0, 1 or 2";
+    if (n == "sketch_share") return szg::sketch_share_known(value) ? nullptr : "sketch_share is 0, 1 or 2";
     if (n == "sketch_bulk") return szg::sketch_bulk_known(value) ? nullptr : "sketch_bulk is 0 to 1024";
     if (n == "sketch_radius") return value == 0 || value == 1 ? nullptr : "sketch_radius is 0 or 1";
     *known = false;
@@ -744,6 +745,8 @@ int szg_set_option(szg_index *ix, const char *name, int64_t value)
         ix->sketch_select = (int)value;
     } else if (n == "sketch_wide") {
         ix->sketch_wide = (int)value;
+    } else if (n == "sketch_share") {
+        ix->sketch_share = (int)value;
     } else if (n == "sketch_bulk") {
         ix->sketch_bulk = (int)value;
     } else if (n == "sketch_radius") {

@@ -439,6 +439,10 @@ struct szg_index {
     int sketch_wide = 0;      // the matrix sweep's two-block form (32 queries per row read): 0 = automatic (calls of
                               // kWideCallMin one-sweep queries on, under the default query_batch and queries_per_launch),
                               // 1 = never, 2 = every call of more than 16 queries where the shape allows
+    int sketch_share = 0;     // the matrix sweep's shared form (64 queries per launch, paired blocks walk the same rows):
+                              // 0 = automatic (calls of kShareCallMin one-sweep queries on, under the default query_batch
+                              // and queries_per_launch), 1 = never, 2 = every sketch call of more than 32 queries, in
+                              // batches of up to 64 from its first query on
     int sketch_bulk = 0;      // the row lists' whole-tile merge: 0 = automatic (tiles with szg::kBulkMin passing pairs or more),
                               // 1 = never (rounds only), n >= 2 = tiles with n passing pairs or more
     int sketch_radius = 0;    // radius queries that would each take a sweep of their own (a lone query, radius_mq = 0) go
@@ -643,8 +647,10 @@ void fill_collect_args(const szg_index *ix, const Shard *sh, const Ctx *c, bool 
                        uint64_t *buf, size_t cap, uint32_t *count, bool dense_vote, szg::ScanArgs *a);
 // (after: the stream that goes on once the sweeps are done -- default the work stream; part 1: the early part of a short
 // call, timed with its own event pair)
+// (hi: null, or one entry per launch -- a launch of more than szg::kMatrixWideQueries queries is then a shared launch of
+// the matrix sweep, on the grid g names: szg::launch_scan_share)
 int launch_scans_chained(szg_index *ix, Shard *sh, Ctx *c, const std::vector<szg::ScanArgs> &a, const LaunchGeom &g,
-                         hipStream_t after = nullptr, int part = 0);
+                         hipStream_t after = nullptr, int part = 0, const std::vector<szg::ScanShareHi> *hi = nullptr);
 // the sketch pre-pass: the sweep runs over a sketch shard, its merged lists are re-ranked on the float32 rows of the
 // shard it stands for, together with `extra` more rows per query that the caller has uploaded behind each list in
 // c->d_sent (kp + extra entries per query)
@@ -655,7 +661,18 @@ struct RerankOn {
     int list;   // option sketch_list: the sweep's per-wave / per-block list length (0 = automatic, >= kp = kp)
     bool wide;  // the call takes wide batches: launches hold up to szg::kMatrixWideQueries queries where the matrix
                 // sweep's two-block form serves them (sketch_wide_serves), up to queries_per_launch elsewhere
+    bool share = false;  // ... and shared batches: a batch of 33 .. szg::kMatrixShareQueries queries is ONE launch of the
+                         // shared form where it serves (sketch_share_serves)
 };
+// does the matrix sweep's shared form serve an unmasked top-k launch of 33 .. szg::kMatrixShareQueries queries of sketch
+// index `sk` on shard `sh`: the wide form serves the shard (sketch_wide_serves), no dead rows, option sketch_share not 1
+bool sketch_share_serves(const szg_index *sk, const Shard *sh, int kp, int list_opt);
+// The geometry of a shared launch on a shard whose plain sweep takes `g`: grid 2 S and S lists of m entries per query.
+// Everything that sizes or walks the lists of a shared launch reads S from here (szg::share_slices, as the kernel does).
+struct ShareGeom {
+    int grid, slices, m;
+};
+ShareGeom share_geometry(const LaunchGeom &g, int list_opt, int kp);
 // entries per wave and block list of a sketch sweep over `grid` blocks (option sketch_list)
 int sketch_list_len(int want, int kp, int grid);
 // does the matrix sweep's two-block form serve an unmasked launch of szg::kMatrixWideQueries queries of sketch index
@@ -856,6 +873,9 @@ constexpr int kShortCall = 32;  // calls of up to this many one-sweep queries ar
 // one launch each, from two of them between its first and last batch of kFirstBatch on -- below that a pipeline of
 // 32-query batches has nothing to overlap with
 constexpr int kWideCallMin = 2 * szg::kMatrixWideQueries + 2 * kFirstBatch;
+// Shared batches (option sketch_share = 0): batches of szg::kMatrixShareQueries queries, one shared launch each, by the
+// same rule -- from two of them between the first and last batch of kFirstBatch on.  Shorter calls keep their plan.
+constexpr int kShareCallMin = 2 * szg::kMatrixShareQueries + 2 * kFirstBatch;
 
 // the filter masks of a call's queries: one pointer per query (null = unfiltered), or masks back to back with one
 // bit per row of the index, or resident masks (one handle per query, null = unfiltered), or none.  operator() gives
@@ -920,6 +940,8 @@ struct BatchRules {
 };
 // the next batch of a call of n_queries, from query q0; nb = the query blocks of a shared sweep (0: one sweep per query)
 void plan_batch(szg_index *ix, int n_queries, int q0, int nb, const BatchRules &r, Batch *b);
+// ... its size when every query takes a sweep of its own (nb = 0): host arithmetic, what plan_batch itself takes
+int one_sweep_batch_size(int n_queries, int q0, const BatchRules &r);
 
 // Prepare the batch's queries q[0, nq) ONCE on its first context -- the single-query form (swizzled floats / digit
 // planes) for a batch of one sweep per query, the integer queries of the int8 shared sweep when int_planes -- and copy
@@ -938,11 +960,15 @@ struct SketchPlan {
     double slack = 0.0;  // the largest d(row, its sketch) (1 + 1e-9), + the build kernel's angle rounding under cosine
     int wide = 0;        // the call takes wide batches (32 queries, one launch of the two-block matrix sweep each):
                          // 1 = under the automatic rule, 2 = forced (option sketch_wide = 2)
+    int share = 0;       // the call takes shared batches (up to 64 queries, one shared launch each; top-k calls only):
+                         // 1 = under the automatic rule, 2 = forced (option sketch_share = 2)
 };
 // (kp: what sketch_wide_serves is asked with -- 0: a collect call)
 SketchPlan sketch_call_plan(const szg_index *ix, int n_queries, int kp);
 // the next batch of such a call, from query q0, on the sketch index's contexts
-void sketch_plan_batch(const szg_index *ix, int n_queries, int q0, int wide, Batch *b);
+void sketch_plan_batch(const szg_index *ix, int n_queries, int q0, int wide, Batch *b, int share = 0);
+// the batch sizes of a top-k call of n_queries through the sketch, by the rules above (host arithmetic: the plan hook)
+std::vector<int> sketch_batch_sizes(int n_queries, int wide, int share, int query_batch);
 // float32 shard a's rows without a usable sketch (sk_exc): f(shard-local row, eligible: live and allowed by mask words m)
 template <class F>
 void sketchless_rows(const szg_index *ix, const Shard *a, const uint64_t *m, F &&f)

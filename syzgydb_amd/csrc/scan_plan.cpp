@@ -74,6 +74,14 @@ ScanVariant scan_variant(const ScanPlanIn &in)
             v.wide = 1;
             v.group = kMatrixWideQueries;
         }
+        // The shared form (option sketch_share): a top-k launch of 33 .. kMatrixShareQueries queries under exactly the
+        // conditions of the wide form -- row lists, the two-block LDS -- as two column groups of 32 on paired blocks.
+        if (v.row_lists && in.wide_opt != 1 && in.share_opt != 1 && in.n_queries > kMatrixWideQueries &&
+            in.n_queries <= kMatrixShareQueries &&
+            scan_lds_bytes(in.qbits, m, list_kp, in.block, kMatrixWideQueries, in.planes, 2) <= kLdsMax) {
+            v.share = 1;
+            v.group = kMatrixWideQueries;
+        }
     }
     return v;
 }

@@ -54,7 +54,28 @@ constexpr int kMaxSweepsPerLaunch = 16;
 // ... but for the matrix sweep's wide form (two column blocks of 16 queries per row read, kernels_scan_mx.hip): the
 // sketch pre-pass puts up to this many queries of a long call into one launch (option sketch_wide)
 constexpr int kMatrixWideQueries = 32;
+// ... and for its shared form (option sketch_share): one launch takes up to this many queries as two column groups of
+// kMatrixWideQueries; paired blocks walk the same rows, one group each (share_map)
+constexpr int kMatrixShareQueries = 64;
 constexpr int kStepList = 256;  // row steps a wave compacts at a time (selective masks)
+
+// The shared form's map from a block of a grid of G = 2 S blocks to its row slice and column group: the only place where
+// the map and the slice count S are computed -- the kernel, its launcher and the host's list buffers all read it.
+// A bijection onto [0, S) x {0, 1} for every even G.  G % 16 == 0: the two blocks of a slice are b and b + 8, which the
+// round-robin dispatch over 8 XCDs places on one XCD (for speed only: nothing waits, nothing depends on placement);
+// other even G: neighbours b, b + 1.
+struct ShareSlot {
+    uint32_t slice, group, slices;
+};
+constexpr int share_slices(int G) { return G / 2; }
+// the grid of a shared launch over rows whose plain launch takes `grid` blocks: 2 S, S = max(1, grid / 2)
+constexpr int share_grid(int grid) { return 2 * (grid / 2 > 1 ? grid / 2 : 1); }
+SZG_PLAN_HD ShareSlot share_map(uint32_t b, uint32_t G)
+{
+    const uint32_t S = G / 2;
+    if (G % 16 == 0) return ShareSlot{(b >> 4) * 8 + (b & 7), (b >> 3) & 1, S};
+    return ShareSlot{b >> 1, b & 1, S};
+}
 
 // Which scan_kernel instantiation a launch takes: decided on the host by scan_variant -- the launcher dispatches on
 // its answer, szg_debug_scan_plan reports it.
@@ -70,7 +91,10 @@ struct ScanVariant {
                       // under sketch_select = 0; else one WaveList per query and the serial inserts
     int wide;         // the matrix sweep's two-block form: one pass per kMatrixWideQueries queries (row lists only)
     // the matrix sweep's column blocks (what scan_lds_bytes takes as `matrix`): 2 = the wide form, 1, 0 = another kernel
-    int matrix_blocks() const { return matrix ? (wide ? 2 : 1) : 0; }
+    int matrix_blocks() const { return matrix ? (wide || share ? 2 : 1) : 0; }
+    int share = 0;    // the two-block form shared between paired blocks (share_map): a launch of kMatrixWideQueries + 1 ..
+                      // kMatrixShareQueries queries, one pass per column group of kMatrixWideQueries, both over one row read
+                      // from HBM where the partner's lines are still on the die (its own launcher: launch_scan_share)
 };
 // What "automatic" (scan_group = 0) asks for, where a launch qualifies.
 constexpr int kScanGroupAuto = 4;
@@ -101,6 +125,10 @@ constexpr uint32_t sketch_bulk_min(int bulk_opt) { return bulk_opt == 0 ? kBulkM
 // constants and lists fit 64 KiB of LDS (768 dimensions: lists of up to 15 entries; longer ones keep one block).
 // 0 = automatic and 2 = wherever the shape allows differ on the host only (which calls form launches of 32); 1 = never.
 constexpr bool sketch_wide_known(int64_t v) { return v == 0 || v == 1 || v == 2; }
+// The shared form (option sketch_share): a launch of kMatrixWideQueries + 1 .. kMatrixShareQueries queries that the wide
+// form would serve at 32 runs as two column groups on paired blocks.  0 = automatic and 2 = every sketch call of more
+// than kMatrixWideQueries queries differ on the host only (which calls form such launches); 1 = never.
+constexpr bool sketch_share_known(int64_t v) { return v == 0 || v == 1 || v == 2; }
 
 // Ring depths of the G > 1 kernels.  A row-shape kernel of P pieces per lane exists at its shape's own depth (the
 // G = 1 kernel's) and, where kGroupRingAlt divides P and differs from it, at kGroupRingAlt as well: scan_group_ring
@@ -169,6 +197,7 @@ struct ScanPlanIn {
     bool norms = false;     // the launch has resident row norms (ScanArgs::row_norm) -- the matrix sweep needs them
     int select_opt = 0;     // the sketch_select option
     int wide_opt = 1;       // the sketch_wide option (1 = never, what callers that do not know it get)
+    int share_opt = 1;      // the sketch_share option (1 = never, what callers that do not know it get)
 };
 ScanVariant scan_variant(const ScanPlanIn &in);
 

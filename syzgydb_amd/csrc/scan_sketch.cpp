@@ -302,17 +302,45 @@ SketchPlan sketch_call_plan(const szg_index *ix, int n_queries, int kp)
     if (!any) return p;
     if (sk->sketch_wide == 2) p.wide = 2;
     else if (n_queries >= kWideCallMin && ix->query_batch == 16 && sk->queries_per_launch == 16) p.wide = 1;
+    // Shared batches (option sketch_share; top-k calls): only where every shard's launch of 33 .. 64 qualifies for the
+    // shared form.  Automatic: long calls under the default batch and launch sizes (they take wide batches too: a rest of
+    // 17 .. 32 queries is a wide launch); 2: every call of more than 32 queries.
+    if (kp < 1 || sk->sketch_share == 1 || n_queries <= szg::kMatrixWideQueries) return p;
+    for (const Shard *sh : sk->shards)
+        if (sh->n_rows != 0 && !sketch_share_serves(sk, sh, kp, ix->sketch_list)) return p;
+    if (sk->sketch_share == 2) p.share = 2;
+    else if (p.wide == 1 && n_queries >= kShareCallMin) p.share = 1;
     return p;
 }
 
-void sketch_plan_batch(const szg_index *ix, int n_queries, int q0, int wide, Batch *b)
+// the rules a call through the sketch splits by (sketch_plan_batch, sketch_batch_sizes)
+static BatchRules sketch_batch_rules(int n_queries, int wide, int share, int query_batch)
 {
-    const int batch = std::max(1, std::min(ix->query_batch, kMaxBatch));
-    // (a wide call is longer than kShortCall: first and last batch of kFirstBatch, 32 between them)
-    BatchRules r{wide ? szg::kMatrixWideQueries : batch, kFirstBatch, std::min(kShortCall, kMaxBatch), true, false};
-    // forced: batches of up to 32 from the call's first query on, no small edges, no early tail
+    const int batch = std::max(1, std::min(query_batch, kMaxBatch));
+    // (a wide call is longer than kShortCall: first and last batch of kFirstBatch, 32 between them -- 64 in a shared call)
+    BatchRules r{share ? szg::kMatrixShareQueries : (wide ? szg::kMatrixWideQueries : batch), kFirstBatch,
+                 std::min(kShortCall, kMaxBatch), true, false};
+    // forced: batches of up to 32 (64) from the call's first query on, no small edges, no early tail
     if (wide == 2) r = BatchRules{szg::kMatrixWideQueries, n_queries, szg::kMatrixWideQueries, false, false};
-    plan_batch(ix->sketch, n_queries, q0, 0, r, b);
+    if (share == 2) r = BatchRules{szg::kMatrixShareQueries, n_queries, szg::kMatrixShareQueries, false, false};
+    return r;
+}
+
+void sketch_plan_batch(const szg_index *ix, int n_queries, int q0, int wide, Batch *b, int share)
+{
+    plan_batch(ix->sketch, n_queries, q0, 0, sketch_batch_rules(n_queries, wide, share, ix->query_batch), b);
+}
+
+std::vector<int> sketch_batch_sizes(int n_queries, int wide, int share, int query_batch)
+{
+    std::vector<int> out;
+    const BatchRules r = sketch_batch_rules(n_queries, wide, share, query_batch);
+    for (int q0 = 0; q0 < n_queries;) {
+        const int nq = std::max(1, one_sweep_batch_size(n_queries, q0, r));
+        out.push_back(nq);
+        q0 += nq;
+    }
+    return out;
 }
 
 // ---- one search call through the sketch ---------------------------------------------------------------------------
@@ -384,7 +412,7 @@ int SketchCall::run()
 Batch SketchCall::plan(int q0)
 {
     Batch b;
-    sketch_plan_batch(ix, n_queries, q0, p.wide, &b);
+    sketch_plan_batch(ix, n_queries, q0, p.wide, &b, p.share);
     return b;
 }
 
@@ -441,7 +469,7 @@ int SketchCall::stage(Batch &b)
         // (the float64 queries unscaled: the rerank is on the rows; a resident mask's shard words serve the sketch
         // shard too: same rows, same device)
         rc = enqueue_queries(sk, h, c, q, b.nq, mptr, true, handles.empty() ? nullptr : handles.data(), s);
-        const RerankOn on{ix, ix->shards[s], extra[s], ix->sketch_list, p.wide != 0};
+        const RerankOn on{ix, ix->shards[s], extra[s], ix->sketch_list, p.wide != 0 || p.share != 0, p.share != 0};
         if (rc == SZG_OK) rc = enqueue_topk(sk, h, c, kp, b.nq, b.any_mask, &on);
     }
     note_stage_times(ix, t_prep0, t_enq0);

@@ -173,20 +173,27 @@ void fill_collect_args(const szg_index *ix, const Shard *sh, const Ctx *c, bool 
 // Launch the fused scan for each of the batch's queries (n = a->size()) as the
 // next links of the shard's scan chain; the ctx stream resumes after the last.
 int launch_scans_chained(szg_index *ix, Shard *sh, Ctx *c, const std::vector<szg::ScanArgs> &a,
-                         const LaunchGeom &g, hipStream_t after, int part)
+                         const LaunchGeom &g, hipStream_t after, int part, const std::vector<szg::ScanShareHi> *hi)
 {
     const int n = (int)a.size();
+    if (hi && (int)hi->size() != n) return fail(SZG_E_INVALID, "shared launches: one record per launch");
+    auto shared = [&](int j) { return hi && a[j].n_queries > szg::kMatrixWideQueries; };
     // (ev_up: recorded by enqueue_queries)
     int rc = chain_sweeps(ix, sh, c, after ? after : c->pass.work, part, n, "szg::launch_scan", [&](hipStream_t st) {
         hipError_t e = hipSuccess;
-        for (int j = 0; j < n && e == hipSuccess; j++) e = szg::launch_scan(ix->bits, ix->metric, a[j], g.grid, g.block, st);
+        for (int j = 0; j < n && e == hipSuccess; j++)
+            e = shared(j) ? szg::launch_scan_share(ix->bits, ix->metric, a[j], (*hi)[j], g.grid, g.block, st)
+                          : szg::launch_scan(ix->bits, ix->metric, a[j], g.grid, g.block, st);
         return e;
     });
     if (rc) return rc;
     std::lock_guard<std::mutex> lk(ix->stats_mu);
     uint64_t sweeps = 0;  // passes over the rows: one per group of a launch's queries (one per query where the launch
-                          // does not qualify for groups)
-    for (const szg::ScanArgs &x : a) sweeps += (uint64_t)szg::scan_passes(ix->bits, x, g.block);
+                          // does not qualify for groups); a shared launch counts one per column group, as requested --
+                          // what its second reader finds on the die is not taken off
+    for (int j = 0; j < n; j++)
+        sweeps += shared(j) ? (uint64_t)((a[j].n_queries + szg::kMatrixWideQueries - 1) / szg::kMatrixWideQueries)
+                            : (uint64_t)szg::scan_passes(ix->bits, a[j], g.block);
     ix->stats.scan_launches += n;
     ix->stats.scan_bytes += sweeps * sh->n_rows * (uint64_t)ix->row_bytes;
     return SZG_OK;
@@ -239,6 +246,33 @@ bool sketch_wide_serves(const szg_index *sk, const Shard *sh, int kp, int list_o
     return szg::scan_variant(in).wide != 0;
 }
 
+ShareGeom share_geometry(const LaunchGeom &g, int list_opt, int kp)
+{
+    const int grid = szg::share_grid(g.grid);
+    const int S = szg::share_slices(grid);
+    return ShareGeom{grid, S, sketch_list_len(list_opt, kp, S)};
+}
+
+bool sketch_share_serves(const szg_index *sk, const Shard *sh, int kp, int list_opt)
+{
+    if (sk->sketch_share == 1 || kp < 1 || sh->has_dead || !sketch_wide_serves(sk, sh, kp, list_opt)) return false;
+    // (the wide form was asked with the plain launch's list length; the shared launch's S lists may be longer)
+    const LaunchGeom g = scan_geometry(sk, sh, kp, true);
+    const ShareGeom s = share_geometry(g, list_opt, kp);
+    szg::ScanPlanIn in{sk->bits, sk->map, sk->layout.tiled != 0, s.m, false, false, sk->ring, !sk->shape_kernels};
+    in.group = sk->scan_group;
+    in.n_queries = szg::kMatrixShareQueries;
+    in.block = g.block;
+    in.planes = scan_planes(sk);
+    in.group_ring = sk->scan_group_ring;
+    in.matrix_opt = sk->sketch_matrix;
+    in.norms = true;
+    in.select_opt = sk->sketch_select;
+    in.wide_opt = sk->sketch_wide;
+    in.share_opt = sk->sketch_share;
+    return szg::scan_variant(in).share != 0;
+}
+
 // top-k pass for the nq staged queries of one shard: scan -> merges -> rerank -> D2H (async)
 // on (the sketch pre-pass): sh is a sketch shard; the last merge writes each query's list in front of the extra rows
 // staged in c->d_sent, and ONE rerank on on->sh's rows takes both.  Its sweeps keep lists of m < kp entries per wave
@@ -251,28 +285,40 @@ int enqueue_topk(szg_index *ix, Shard *sh, Ctx *c, int kp, int nq, bool has_allo
     c->pass.out_stride = stride;
     c->pass.keys = ListKeys::Single;
     HIPCHK(hipSetDevice(sh->device));
-    const LaunchGeom g = scan_geometry(ix, sh, kp, !has_allow && !sh->has_dead);
-    const int m = on ? sketch_list_len(on->list, kp, g.grid) : kp;  // entries per wave and block list
+    LaunchGeom g = scan_geometry(ix, sh, kp, !has_allow && !sh->has_dead);
+    const bool masked = has_allow || sh->has_dead;
+    // One part -- or, for a short call (Pass::early_n), two: the sweeps of queries [0, early_n), whose merges, re-rank and
+    // copy-back leave the scan stream for the context's own (one event), and the last few queries, whose tail is all
+    // that is left to do after the call's final sweep.
+    const int early = c->pass.early_n > 0 && c->pass.early_n < nq ? c->pass.early_n : 0;
+    // (a shared batch of the sketch pre-pass: 33 .. 64 queries in ONE launch of the matrix sweep's shared form, on a grid
+    // of 2 S blocks that leaves S lists per query -- unmasked, on every row, in one part)
+    const bool share = on && on->share && !masked && !early && nq > szg::kMatrixWideQueries &&
+                       nq <= szg::kMatrixShareQueries && sketch_share_serves(ix, sh, kp, on->list);
+    int lists0 = g.grid;                                            // block lists per query the sweeps leave
+    int m = on ? sketch_list_len(on->list, kp, g.grid) : kp;  // entries per wave and block list
+    if (share) {
+        const ShareGeom sg = share_geometry(g, on->list, kp);
+        g.grid = sg.grid;
+        lists0 = sg.slices;
+        m = sg.m;
+    }
     if (on && on->extra < 1) return fail(SZG_E_INVALID, "sketch: no slot for the drop bound");
-    int rc = c->ensure_lists((size_t)nq * g.grid * m);
+    int rc = c->ensure_lists((size_t)nq * lists0 * m);
     if (rc == SZG_OK) rc = c->d_out.ensure((size_t)nq * stride);
     if (rc == SZG_OK) rc = c->h_out.ensure((size_t)nq * stride);
     if (rc) return rc;
     if (on && c->d_sent.capacity() < (size_t)nq * stride) return fail(SZG_E_INVALID, "sketch candidates not staged");
 
-    const bool masked = has_allow || sh->has_dead;
     // (a wide batch of the sketch pre-pass: launches of up to 32 queries where the two-block matrix sweep serves them --
     // unmasked, on every row: the same question the call asked before it planned wide batches)
     const bool wide = on && on->wide && !masked && nq > szg::kMatrixQueries && sketch_wide_serves(ix, sh, kp, on->list);
-    const int qpl = wide ? szg::kMatrixWideQueries : std::max(1, ix->queries_per_launch);
-    // One part -- or, for a short call (Pass::early_n), two: the sweeps of queries [0, early_n), whose merges, re-rank and
-    // copy-back leave the scan stream for the context's own (one event), and the last few queries, whose tail is all
-    // that is left to do after the call's final sweep.
-    const int early = c->pass.early_n > 0 && c->pass.early_n < nq ? c->pass.early_n : 0;
+    const int qpl = share ? szg::kMatrixShareQueries : (wide ? szg::kMatrixWideQueries : std::max(1, ix->queries_per_launch));
     for (int part = early ? 1 : 0; part >= 0; part--) {
         const int q0 = part ? 0 : early, q1 = part ? early : nq, nqp = q1 - q0;
         hipStream_t tl = part ? c->stream : c->pass.work;
         std::vector<szg::ScanArgs> args((nqp + qpl - 1) / qpl);
+        std::vector<szg::ScanShareHi> hi(share ? args.size() : 0);
         for (int j = q0; j < q1; j += qpl) {  // one sweep per query, results side by side
             szg::ScanArgs &a = args[(j - q0) / qpl];
             fill_scan_args(ix, sh, c, has_allow, j, std::min(qpl, q1 - j), &a);
@@ -284,7 +330,17 @@ int enqueue_topk(szg_index *ix, Shard *sh, Ctx *c, int kp, int nq, bool has_allo
             // (a call that keeps more than 64 candidates per query -- lists that would not fit registers at full length --
             // stays with the grouped kernels even where its short lists would fit)
             if (kp > 64) a.matrix = 1;
-            a.block_lists = c->d_lists_a + (size_t)j * g.grid * m;
+            a.block_lists = c->d_lists_a + (size_t)j * lists0 * m;
+            if (share) {  // the constants of the launch's queries 32 .. 63, and the option
+                szg::ScanShareHi &h = hi[(j - q0) / qpl];
+                memset(&h, 0, sizeof(h));
+                for (int x = szg::kMatrixWideQueries; x < a.n_queries; x++) {
+                    h.qscale[x - szg::kMatrixWideQueries] = (float)c->meta[j + x].qscale;
+                    h.qconst[x - szg::kMatrixWideQueries] = (float)c->meta[j + x].qconst;
+                    h.qnorm2[x - szg::kMatrixWideQueries] = (float)c->meta[j + x].qnorm2;
+                }
+                h.share = ix->sketch_share;
+            }
         }
         // launches that score groups of queries per row read -- the grouped kernels and the matrix sweep, which cannot do
         // without -- take the rows' norms from the resident array (complete before the sweeps are enqueued; it only has
@@ -301,11 +357,11 @@ int enqueue_topk(szg_index *ix, Shard *sh, Ctx *c, int kp, int nq, bool has_allo
             asked = true;
             a.row_norm = norms;
         }
-        rc = launch_scans_chained(ix, sh, c, args, g, tl, part);
+        rc = launch_scans_chained(ix, sh, c, args, g, tl, part, share ? &hi : nullptr);
         if (rc) return rc;
 
-        int n_lists = g.grid;
-        uint64_t *src = c->d_lists_a + (size_t)q0 * g.grid * m, *dst = c->d_lists_b + (size_t)q0 * g.grid * m;
+        int n_lists = lists0;
+        uint64_t *src = c->d_lists_a + (size_t)q0 * lists0 * m, *dst = c->d_lists_b + (size_t)q0 * lists0 * m;
         const int fan = szg::merge_fan(kp);
         {
             SiteScope t_(6);
@@ -730,6 +786,18 @@ std::vector<const szg_mask *> Batch::handles(const QueryMasks &mask_of) const
 
 constexpr int kShortCallLast = 4;  // queries of a short call whose tail is left for after the final sweep
 
+int one_sweep_batch_size(int n_queries, int q0, const BatchRules &r)
+{
+    const int left = n_queries - q0;
+    if (q0 == 0 && n_queries <= r.short_max) return n_queries;
+    int nq = std::min(r.batch, left);
+    if (left > r.edge) {
+        if (q0 == 0) nq = std::min(nq, r.edge);
+        else if (left <= r.batch + r.edge) nq = left - r.edge;
+    }
+    return nq;
+}
+
 void plan_batch(szg_index *ix, int n_queries, int q0, int nb, const BatchRules &r, Batch *b)
 {
     const int left = n_queries - q0;
@@ -760,11 +828,7 @@ void plan_batch(szg_index *ix, int n_queries, int q0, int nb, const BatchRules &
     // the call's FIRST batch is small, so that the card starts sweeping after a few microseconds of preparation
     // instead of a whole batch's (the next batch is prepared while it sweeps) ... and its LAST one too: what is left
     // to do once the last sweep has ended is that batch's merges, re-rank, copy-back and result assembly
-    b->nq = std::min(r.batch, left);
-    if (left > r.edge) {
-        if (q0 == 0) b->nq = std::min(b->nq, r.edge);
-        else if (left <= r.batch + r.edge) b->nq = left - r.edge;
-    }
+    b->nq = one_sweep_batch_size(n_queries, q0, r);
 }
 
 int stage_query_forms(szg_index *ix, Batch &b, const double *q, bool int_planes,

@@ -933,6 +933,25 @@ def scan_wide_plan(dim, quant_bits, n_queries, kp=8, planes=2, norms=True, tiled
     return {"serves": bool(serves.value), "passes": passes.value, "lds_bytes": lds.value}
 
 
+def scan_share_plan(dim, quant_bits, n_queries, kp=8, planes=2, norms=True, tiled=True, masked=False, scan_group=0,
+                    sketch_matrix=0, sketch_select=0, sketch_wide=0, sketch_share=0):
+    """Host-only test hook: the matrix sweep's shared form (option sketch_share) for a one-sweep top-k call of n_queries
+    queries through the sketch -- whether a launch of min(n_queries, 64) takes it, its row slices and LDS bytes, and the
+    call as it is split: the queries of its batches, its scan launches and its passes over the rows."""
+    L = _lib.load()
+    serves, launches, passes, slices, nb = (ctypes.c_int32() for _ in range(5))
+    lds = ctypes.c_uint64()
+    cap = max(1, int(n_queries))
+    batches = (ctypes.c_int32 * cap)()
+    check(L.szg_debug_scan_share(int(dim), int(quant_bits), int(n_queries), int(kp), int(planes), int(bool(norms)),
+                                 int(bool(tiled)), int(bool(masked)), int(scan_group), int(sketch_matrix),
+                                 int(sketch_select), int(sketch_wide), int(sketch_share), ctypes.byref(serves),
+                                 ctypes.byref(launches), ctypes.byref(passes), ctypes.byref(slices), ctypes.byref(lds),
+                                 batches, cap, ctypes.byref(nb)), "szg_debug_scan_share")
+    return {"serves": bool(serves.value), "launches": launches.value, "passes": passes.value, "slices": slices.value,
+            "lds_bytes": lds.value, "batches": [int(batches[i]) for i in range(min(nb.value, cap))]}
+
+
 def scan_collect_plan(dim, quant_bits, n_queries, planes=2, norms=True, tiled=True, masked=False, scan_group=0,
                       sketch_matrix=0, sketch_wide=0):
     """Host-only test hook: the matrix sweep's collect form (radius searches through the sketch, option sketch_radius)
@@ -974,7 +993,7 @@ def merge_short_plan(n_lists, m, kp):
 def option_check(name, value):
     """Host-only test hook (no device needed): raises SzgError where ScanIndex.set_option would refuse `value` for the
     one-sweep kernel's option `name` (scan_group, scan_group_ring, scan_norms, sketch_planes, sketch_matrix, sketch_select,
-    sketch_wide, sketch_bulk, sketch_radius)."""
+    sketch_wide, sketch_share, sketch_bulk, sketch_radius)."""
     L = _lib.load()
     check(L.szg_debug_option_check(name.encode(), int(value)), "szg_debug_option_check")
 
