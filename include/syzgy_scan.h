@@ -201,7 +201,8 @@ int szg_index_mask_stats(szg_index *ix, szg_mask_stats *out);   /* szg_reset_sta
 /* ---- compaction and reorder on the device (added under ABI 4, additive) ------
  *
  * A tombstoned row keeps its bytes in device memory, is still read by every sweep, and its mere presence makes every
- * launch of its shard a masked one (no grouped 8-bit sweep, no unmasked launch geometry).  These two calls renumber
+ * launch of its shard a masked one (no grouped 8-bit sweep, no unmasked launch geometry) -- unless sketch_masked = 1, under
+ * which the sketch pre-pass's launches keep the matrix sweep.  These two calls renumber
  * the resident rows without a trip through the host: one gather kernel copies the kept rows, 16 bytes per lane, into
  * a NEW allocation sized for them, then the old one is freed -- so compaction gives device memory back, and the peak
  * during the call is the old plus the new allocation (per shard).
@@ -771,6 +772,16 @@ int szg_reset_stats(szg_index *ix);
  *                             was -- built as an option, soaked by the fuzzers, made the default by a later change.
  *                             Batches that share a sweep (radius_mq = 1, two queries or more) keep it.  Other values
  *                             are refused
+ *     sketch_masked       0   1 = a top-k launch of the sketch pre-pass with tombstones or filter masks (one resident mask
+ *                             for every query, per-query resident masks, words from the host) takes the matrix sweep
+ *                             wherever the same launch without masks would -- 16 queries per row read, 32 and 64 under the
+ *                             sketch_wide and sketch_share rules, the call split as the unmasked call of its size -- with
+ *                             a row's eligibility tested where its keys are; a launch whose queries share one mask (or
+ *                             have tombstones alone) skips every tile of 16 rows none of which is eligible.  szg_stats.
+ *                             scan_bytes counts one pass per group of such a launch.  Same answers.  0 = never (the
+ *                             default): masked launches keep the one-query kernel, one pass per query; the option is new
+ *                             and off while it soaks, as sketch_radius was.  Radius searches, plain 8-bit handles and
+ *                             lists of more than 64 entries stay as they are.  Other values are refused
  *   shared sweeps
  *     multi_query         1   batches of >= mq_min queries share ONE sweep of the corpus, the dot products on the
  *                             matrix cores: 64- / 32- / 16-bit rows on bfloat16 roundings (v_mfma_f32_16x16x32_bf16,
@@ -889,6 +900,34 @@ int szg_debug_scan_share(int dim, int quant_bits, int n_queries, int kp, int pla
                          int32_t *batches, int32_t batch_capacity, int32_t *n_batches);
 
 /*
+ * Test hook, host only: the matrix sweep's masked forms (option sketch_masked) for a one-sweep top-k call of n_queries
+ * queries through the sketch whose launches carry masks, with the arguments of szg_debug_scan_share plus the option and
+ * shared_mask (1: the launch's queries share one mask or have tombstones alone -- its eligibility is wave-uniform; 0:
+ * per-query masks).  *serves = 1: a launch of min(n_queries, 64) queries takes a masked form; *wide / *share: that launch
+ * takes the two-block / the shared form; *tile_skip: it skips tiles without an eligible row (serves and shared_mask);
+ * *steps_form: its kernel's 64-byte steps per row (12, 6, 0 = the any-steps kernel);
+ * *launches / *passes: the call's scan launches and passes over the rows as it is split -- with the option off, or where
+ * the form does not serve, launches of up to 16 and one pass per query.  masked = 0 describes the call without masks:
+ * no masked form (*serves = 0), the launches and passes of szg_debug_scan_share.
+ */
+typedef struct szg_scan_masked_plan {
+    int32_t serves, wide, share, tile_skip, steps_form, launches, passes;
+} szg_scan_masked_plan;
+int szg_debug_scan_masked(int dim, int quant_bits, int n_queries, int kp, int planes, int norms, int tiled, int masked,
+                          int scan_group, int sketch_matrix, int sketch_select, int sketch_wide, int sketch_share,
+                          int sketch_masked, int shared_mask, szg_scan_masked_plan *out);
+
+/*
+ * Test hook: what the masked forms of the matrix sweep (option sketch_masked) served on the handle's sketch index since
+ * szg_reset_stats: launches that took one, those of them with the tile skip, and the queries of all of them.  Zeros for
+ * a handle without a sketch.
+ */
+typedef struct szg_sketch_masked_info {
+    uint64_t launches, skip_launches, queries;
+} szg_sketch_masked_info;
+int szg_debug_sketch_masked(szg_index *ix, szg_sketch_masked_info *out);
+
+/*
  * Test hook, host only: does the matrix sweep's collect form (radius searches through the sketch, option sketch_radius)
  * serve a collect call of n_queries queries with one sweep each, under the conditions of szg_debug_scan_matrix?  The
  * call is split into launches of up to 32 queries where sketch_wide = 2 and a launch of 32 qualifies for the two-block
@@ -917,7 +956,8 @@ int szg_debug_scan_group_ring(int dim, int quant_bits, int kp, int scan_group, i
 
 /*
  * Test hook, host only: would szg_set_option accept `value` for the one-sweep kernel's option `name` (scan_group,
- * scan_group_ring, scan_norms, sketch_planes, sketch_matrix, sketch_select, sketch_wide, sketch_share, sketch_bulk, sketch_radius)?  SZG_OK, or SZG_E_INVALID with szg_set_option's text; any other name is refused.
+ * scan_group_ring, scan_norms, sketch_planes, sketch_matrix, sketch_select, sketch_wide, sketch_share, sketch_bulk, sketch_radius,
+ * sketch_masked)?  SZG_OK, or SZG_E_INVALID with szg_set_option's text; any other name is refused.
  */
 int szg_debug_option_check(const char *name, int64_t value);
 

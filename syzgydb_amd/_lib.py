@@ -62,6 +62,8 @@ EXPORTS = [
     "szg_debug_trace_certificates", "szg_debug_certificates",
     # the sketch index's state, read only (added under ABI 4)
     "szg_debug_sketch_info", "szg_debug_sketch_rows",
+    # the matrix sweep's masked forms (option sketch_masked): the plan hook and the counters
+    "szg_debug_scan_masked", "szg_debug_sketch_masked",
 ]
 # szg_cert_record.pass / .keys, szg_cert_entry.flags
 SZG_CERT_TOPK, SZG_CERT_SKETCH, SZG_CERT_ESCALATION, SZG_CERT_RADIUS_SINGLE, SZG_CERT_RADIUS_SHARED = range(5)
@@ -144,6 +146,14 @@ class SzgSketchInfo(ctypes.Structure):
     _fields_ = ([(name, ctypes.c_int32) for name in ("exists", "in_sync", "disabled", "n_shards")] +
                 [("rows", ctypes.c_uint64), ("max_ang", ctypes.c_double), ("gscale", ctypes.c_double),
                  ("n_exc", ctypes.c_uint64)])
+
+
+class SzgScanMaskedPlan(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_int32) for name in ("serves", "wide", "share", "tile_skip", "steps_form", "launches", "passes")]
+
+
+class SzgSketchMaskedInfo(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_uint64) for name in ("launches", "skip_launches", "queries")]
 
 
 class SzgColumnInfo(ctypes.Structure):
@@ -407,6 +417,11 @@ def load():
         L.szg_debug_scan_share.argtypes = ([ctypes.c_int] * 13 + [ctypes.POINTER(ctypes.c_int32)] * 4 +
                                            [ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_int32), ctypes.c_int32,
                                             ctypes.POINTER(ctypes.c_int32)])
+    if hasattr(L, "szg_debug_scan_masked"):
+        L.szg_debug_scan_masked.restype = ctypes.c_int
+        L.szg_debug_scan_masked.argtypes = [ctypes.c_int] * 15 + [ctypes.POINTER(SzgScanMaskedPlan)]
+        L.szg_debug_sketch_masked.restype = ctypes.c_int
+        L.szg_debug_sketch_masked.argtypes = [vp, ctypes.POINTER(SzgSketchMaskedInfo)]
     if hasattr(L, "szg_debug_scan_collect"):
         L.szg_debug_scan_collect.restype = ctypes.c_int
         L.szg_debug_scan_collect.argtypes = ([ctypes.c_int] * 10 + [ctypes.POINTER(ctypes.c_int32)] * 3 +

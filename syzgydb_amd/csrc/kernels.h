@@ -216,6 +216,33 @@ inline ScanPlanIn scan_share_plan_in(int qbits, const ScanArgs &a, const ScanSha
     in.share_opt = hi.share;
     return in;
 }
+// The matrix sweep's masked forms (option sketch_masked; kernels_scan_mx.hip with -DSZG_MX_MASKED, and with -DSZG_MX_SHARE
+// on top for the shared form: objects of their own): a top-k launch with tombstones (a.live_bits) or filter masks
+// (query q of the launch reads a.allow_bits + q * a.allow_stride) in the form the same launch without masks would take.
+// The option rides behind ScanArgs in a struct that only these kernels take, as ScanShareHi does: ScanArgs, and with it the
+// code of every other kernel, stay as they were.  hi: the shared form's constants (zero for the other forms).
+struct ScanMaskedArgs {
+    ScanArgs a;
+    ScanShareHi hi;
+    int masked;  // option sketch_masked: 1 = masked launches take the matrix sweep where they qualify
+};
+// what scan_variant decides from for a launch that may take a masked form (share_opt: the sketch_share option)
+inline ScanPlanIn scan_masked_plan_in(int qbits, const ScanArgs &a, int share_opt, int masked_opt, int block)
+{
+    ScanPlanIn in = scan_plan_in(qbits, a, block);
+    in.share_opt = share_opt;
+    in.masked_opt = masked_opt;
+    return in;
+}
+// ONE masked top-k launch of the matrix sweep: scan_variant must name the masked form for exactly this launch (up to 16
+// queries, 17 .. 32 wide, 33 .. 64 shared: hi as launch_scan_share takes it, its `share` the option); everything else is
+// hipErrorInvalidValue.  The lists go to a.block_lists as the unmasked form of the same launch leaves them.
+hipError_t launch_scan_masked(int qbits, int metric, const ScanArgs &a, const ScanShareHi &hi, int masked_opt, int grid, int block,
+                              hipStream_t stream);
+hipError_t launch_scan_mxm_m0(const ScanMaskedArgs &s, const ScanVariant &v, int grid, int block, size_t lds, hipStream_t stream);
+hipError_t launch_scan_mxm_m1(const ScanMaskedArgs &s, const ScanVariant &v, int grid, int block, size_t lds, hipStream_t stream);
+hipError_t launch_scan_mxms_m0(const ScanMaskedArgs &s, const ScanVariant &v, int grid, int block, size_t lds, hipStream_t stream);
+hipError_t launch_scan_mxms_m1(const ScanMaskedArgs &s, const ScanVariant &v, int grid, int block, size_t lds, hipStream_t stream);
 // ---- shared (multi-query) sweeps (mq_device.h, kernels_mq*.hip): every row width, cosine and Euclidean ----------
 // queries per shared sweep: 48 (3 blocks of 16) for the int8 sweeps (4- and 8-bit rows), whose LDS images are 2-4
 // bytes per element and query; 96 for the bfloat16 sweeps (16-, 32- and 64-bit rows, and 8-bit rows in batches of

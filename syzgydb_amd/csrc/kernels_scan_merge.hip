@@ -306,6 +306,23 @@ hipError_t launch_scan_share(int qbits, int metric, const ScanArgs &a, const Sca
     return (metric == kCosine ? launch_scan_mxs_m1 : launch_scan_mxs_m0)(s, v, grid, block, lds, stream);
 }
 
+// the matrix sweep's masked launch (option sketch_masked): scan_variant must name the masked form for exactly this launch
+hipError_t launch_scan_masked(int qbits, int metric, const ScanArgs &a, const ScanShareHi &hi, int masked_opt, int grid, int block,
+                              hipStream_t stream)
+{
+    if (qbits != 8 || (metric != kCosine && metric != kEuclidean) || a.collect || !scan_masked(a) || masked_opt != 1)
+        return hipErrorInvalidValue;
+    const ScanVariant v = scan_variant(scan_masked_plan_in(qbits, a, hi.share, masked_opt, block));
+    if (!v.matrix || !v.masked) return hipErrorInvalidValue;
+    const size_t lds = scan_lds_bytes(qbits, a.map, a.kp, block, v.group, a.planes, v.matrix_blocks());
+    ScanMaskedArgs s;
+    s.a = a;
+    s.hi = hi;
+    s.masked = masked_opt;
+    if (v.share) return (metric == kCosine ? launch_scan_mxms_m1 : launch_scan_mxms_m0)(s, v, grid, block, lds, stream);
+    return (metric == kCosine ? launch_scan_mxm_m1 : launch_scan_mxm_m0)(s, v, grid, block, lds, stream);
+}
+
 hipError_t launch_merge(const uint64_t *in, int n_lists, int kp, int n_queries, uint64_t *out,
                         hipStream_t stream, int out_stride)
 {

@@ -53,6 +53,9 @@
 // a.kp rows, as scan_kernel leaves them.
 #include "kernels.h"
 #include "device_lists.h"
+#ifdef SZG_MX_MASKED
+#include "mask_tiles.h"
+#endif
 
 #ifndef SZG_SCAN_METRIC
 #error "kernels_scan_mx.hip needs SZG_SCAN_METRIC (0 or 1)"
@@ -123,17 +126,44 @@ constexpr int mx_ring()
 // own group's image, constants and lists and takes one turn of the loop over the groups; the two blocks of a slice walk
 // the same tiles, so whichever reads a line second finds it in its XCD's L2 or in the Infinity Cache.  No block waits
 // for another and nothing depends on where or when a partner runs.  The keys are formed by the same operations.
-#ifdef SZG_MX_SHARE
+// With -DSZG_MX_MASKED the file builds the MASKED forms of the top-k kernels instead (objects of their own, and with
+// -DSZG_MX_SHARE on top the masked shared form; DESIGN.md 4.5 item 14, option sketch_masked): launches with tombstones
+// (a.live_bits) or filter masks (query q of the launch: a.allow_bits + q * a.allow_stride).  A tile's 16 rows are one
+// aligned 16-bit slice of a mask word (mask_tiles.h).  The pre-filter's pass[r] gains "this row is eligible for this slot's
+// query": an ineligible row never enters a list, never moves a bound and never counts towards a crowded tile, so a block
+// leaves exactly its best a.kp ELIGIBLE rows, as scan_kernel's masked forms do.  The live slice and the allow slice of a
+// launch whose queries share one mask (no allow words, or stride 0) are wave-uniform: mask_next_tile walks the wave from
+// its tile to the next one of its stride with an eligible row -- scalar loads, nothing per lane -- and a tile without one
+// is neither loaded nor multiplied; the ring's look-ahead points at the tile the walk found.  With per-query masks the
+// walk sees the live words alone, and lane t < 4 NB of every lane-row fetches slot t's 16-bit allow slice beside the norm
+// (the idle columns read the launch's last query's); the finish hands slot r's slice to the lane-row's 16 lanes.
+#if defined(SZG_MX_MASKED)
+#define SZG_MX_KERNEL_ARGS const ScanMaskedArgs ma
+#elif defined(SZG_MX_SHARE)
 #define SZG_MX_KERNEL_ARGS const ScanShareArgs sa
 #else
 #define SZG_MX_KERNEL_ARGS const ScanArgs a
 #endif
+// (the masked Euclidean 12-step one-block row-list kernel needs 10 registers more than the 128 of four waves per SIMD: it
+// takes the bound of the other forms, 2 -- no kernel of this file uses scratch)
+#ifdef SZG_MX_MASKED
+#define SZG_MX_FOUR_WAVES(METRIC, STEPS) (!((METRIC) == kEuclidean && (STEPS) == 12))
+#else
+#define SZG_MX_FOUR_WAVES(METRIC, STEPS) true
+#endif
 template <int METRIC, int STEPS, bool NT, bool ROWS, int NB = 1, bool COLLECT = false>
-__global__ __launch_bounds__(256, (ROWS && NB == 1 && STEPS != 0) ? 4 : 2) void scan_mx_kernel(SZG_MX_KERNEL_ARGS)
+__global__ __launch_bounds__(256, (ROWS && NB == 1 && STEPS != 0 && SZG_MX_FOUR_WAVES(METRIC, STEPS)) ? 4 : 2) void scan_mx_kernel(SZG_MX_KERNEL_ARGS)
 {
+#ifdef SZG_MX_MASKED
+    static_assert(!COLLECT, "the masked forms: top-k");
+    const ScanArgs &a = ma.a;
+    [[maybe_unused]] const ScanMaskedArgs &sa = ma;  // (the shared form reads sa.hi)
+#endif
 #ifdef SZG_MX_SHARE
     static_assert(NB == 2 && ROWS && !COLLECT, "the shared form: two column blocks, row lists, top-k");
+#ifndef SZG_MX_MASKED
     const ScanArgs &a = sa.a;
+#endif
     const ShareSlot slot = share_map(blockIdx.x, gridDim.x);
 #endif
     static_assert(NB == 1 || (NB == 2 && ROWS), "two column blocks: row lists only");
@@ -170,12 +200,21 @@ __global__ __launch_bounds__(256, (ROWS && NB == 1 && STEPS != 0) ? 4 : 2) void 
     const uint64_t tile_stride = (uint64_t)gridDim.x * nwaves;
     const uint64_t tile_first = (uint64_t)blockIdx.x * nwaves + wave;
 #endif
-    const uint64_t n_it = tile_first < n_tiles ? (n_tiles - tile_first + tile_stride - 1) / tile_stride : 0;
+    // (the masked forms walk on "no further tile": no fixed count)
+    [[maybe_unused]] const uint64_t n_it = tile_first < n_tiles ? (n_tiles - tile_first + tile_stride - 1) / tile_stride : 0;
     const uint64_t last_row = a.n_rows ? (uint64_t)a.n_rows - 1 : 0;
     // (a row past the end of the last tile, or a tile past the wave's last: a valid row, read and discarded)
     auto row_ptr = [&](uint64_t tile) -> const uint8_t * {
         return a.rows + piece_offset(lay, min(tile * 16 + trow, last_row), (uint32_t)c);
     };
+#ifdef SZG_MX_MASKED
+    // the words the walk reads (wave-uniform); per-query masks are read per slot instead
+    const bool per_query = a.allow_bits != nullptr && a.allow_stride != 0;
+    const uint64_t *const m_live = a.live_bits;
+    const uint64_t *const m_allow = per_query ? nullptr : a.allow_bits;
+    uint32_t m_slice = 0xFFFFu;  // the eligible rows of the tile at hand, by the walk's words
+    uint32_t m_esl = 0xFFFFu;    // per-query masks: the allow slice of slot (lane & (NS - 1)) of this lane-row
+#endif
 
 #ifdef SZG_MX_SHARE
     // (one turn, for the block's own group; the launcher admits 33 .. 64 queries: both groups hold a live query)
@@ -237,6 +276,15 @@ __global__ __launch_bounds__(256, (ROWS && NB == 1 && STEPS != 0) ? 4 : 2) void 
             live[r] = qi + (r >> 2) * kMxQ + c * 4 + (r & 3) < a.n_queries;
         }
         float qsv[NS], qcv[NS], qnv[NS];
+#ifdef SZG_MX_MASKED
+        // per-query masks: the mask of this lane's slot as 16-bit slices, one per tile (little-endian words)
+        const uint16_t *m_q16 = nullptr;
+        if (per_query) {
+            const int s_ = trow & (NS - 1);
+            const int q_ = min(qi + (s_ >> 2) * kMxQ + c * 4 + (s_ & 3), a.n_queries - 1);
+            m_q16 = reinterpret_cast<const uint16_t *>(a.allow_bits + (size_t)q_ * a.allow_stride);
+        }
+#endif
 
         // ---- the tile is done: keys of 4 NB queries x 1 row per lane, one compare each, one ballot for the tile
         auto finish_tile = [&](uint64_t tile, const v4i32 (&accM)[NB], const v4i32 (&accL)[NB], float norm) {
@@ -246,6 +294,22 @@ __global__ __launch_bounds__(256, (ROWS && NB == 1 && STEPS != 0) ? 4 : 2) void 
             bool pass[NS];
             bool any = false;
             [[maybe_unused]] const float inv = __frsqrt_rn(norm);
+#ifdef SZG_MX_MASKED
+            // is this lane's row eligible for slot r's query?  (one mask: the walk's slice; per-query masks: slot r's slice
+            // sits in lane r of the lane-row)
+            bool elig[NS];
+#pragma unroll
+            for (int r = 0; r < NS; r++) elig[r] = ((m_slice >> trow) & 1u) != 0;
+            if (per_query) {  // (wave-uniform)
+#pragma unroll
+                for (int r = 0; r < NS; r++) {
+                    // (every lane takes part in the exchange: no short-circuit in front of it -- a lane whose row is dead
+                    // still holds a slot's slice)
+                    const uint32_t sl = (uint32_t)__shfl((int)m_esl, (lane & 48) + r);
+                    elig[r] = elig[r] & (((sl >> trow) & 1u) != 0);
+                }
+            }
+#endif
 #pragma unroll
             for (int r = 0; r < NS; r++) {
                 float dot;
@@ -257,7 +321,11 @@ __global__ __launch_bounds__(256, (ROWS && NB == 1 && STEPS != 0) ? 4 : 2) void 
                 else k_ = fmaf(-2.0f * qsv[r], d2, qnv[r] + norm);
                 k_ = fminf(k_, 3.0e38f);
                 key[r] = k_;
+#ifdef SZG_MX_MASKED
+                pass[r] = row_ok && live[r] && elig[r] && !(k_ > wk[r]);
+#else
                 pass[r] = row_ok && live[r] && !(k_ > wk[r]);
+#endif
                 any = any || pass[r];
             }
             if (!__ballot(any)) return;
@@ -362,7 +430,14 @@ __global__ __launch_bounds__(256, (ROWS && NB == 1 && STEPS != 0) ? 4 : 2) void 
             v4i32 accM[NB], accL[NB];
 #pragma unroll
             for (int b = 0; b < NB; b++) accM[b] = accL[b] = v4i32{0, 0, 0, 0};
+#ifdef SZG_MX_MASKED
+            // (a wave with no eligible tile: mt.tile == n_tiles -- the ring's first loads read the last row and nobody
+            // consumes them)
+            MaskTile mt = mask_next_tile(m_live, m_allow, tile_first, tile_stride, n_tiles);
+            uint64_t tile = mt.tile;
+#else
             uint64_t tile = tile_first;
+#endif
             const uint8_t *cur = row_ptr(tile);
             // the ring's first D steps (D <= STEPS: all inside the first tile); the rows do not depend on the image
 #pragma unroll
@@ -382,9 +457,18 @@ __global__ __launch_bounds__(256, (ROWS && NB == 1 && STEPS != 0) ? 4 : 2) void 
                 }
             };
             read_phase(0, qbuf[0]);
+#ifdef SZG_MX_MASKED
+            while (tile < n_tiles) {
+                // the look-ahead points at the next tile with an eligible row (none: this tile again, as below)
+                const MaskTile nx = mask_next_tile(m_live, m_allow, tile + tile_stride, tile_stride, n_tiles);
+                const uint8_t *nxt = nx.tile < n_tiles ? row_ptr(nx.tile) : cur;
+                m_slice = mt.slice;
+                if (per_query) m_esl = m_q16[tile];  // (arrives with the norm)
+#else
             for (uint64_t it = 0; it < n_it; it++, tile += tile_stride) {
                 // (past the wave's last tile: its own tile again -- D loads nobody consumes)
                 const uint8_t *nxt = it + 1 < n_it ? row_ptr(tile + tile_stride) : cur;
+#endif
                 const float norm = a.row_norm[min(tile * 16 + trow, last_row)];  // arrives while the tile's steps run
 #pragma unroll
                 for (int st = 0; st < STEPS; st++) {
@@ -409,6 +493,10 @@ __global__ __launch_bounds__(256, (ROWS && NB == 1 && STEPS != 0) ? 4 : 2) void 
                 }
                 finish_tile(tile, accM, accL, norm);
                 cur = nxt;
+#ifdef SZG_MX_MASKED
+                mt = nx;
+                tile = nx.tile;
+#endif
             }
         } else {
             constexpr int D = 4;
@@ -416,17 +504,41 @@ __global__ __launch_bounds__(256, (ROWS && NB == 1 && STEPS != 0) ? 4 : 2) void 
             v4i32 accM[NB], accL[NB];
 #pragma unroll
             for (int b = 0; b < NB; b++) accM[b] = accL[b] = v4i32{0, 0, 0, 0};
+#ifdef SZG_MX_MASKED
+            // the issue side and the consume side walk the same tiles, each on its own (the walk is a function of the
+            // words); a tile past the walk's end (n_tiles) is the last row again, loaded and never consumed
+            const MaskTile mt0 = mask_next_tile(m_live, m_allow, tile_first, tile_stride, n_tiles);
+            uint64_t itile = mt0.tile, ctile = mt0.tile;
+            uint32_t c_slice = mt0.slice;
+            int is = 0, cs = 0;
+            const uint8_t *iptr = row_ptr(mt0.tile);
+            float norm = 0.0f;
+#define SZG_MX_NEXT_I itile = mask_next_tile(m_live, m_allow, itile + tile_stride, tile_stride, n_tiles).tile;
+#define SZG_MX_NEXT_C                                                                                      \
+    {                                                                                                      \
+        const MaskTile n_ = mask_next_tile(m_live, m_allow, ctile + tile_stride, tile_stride, n_tiles);    \
+        ctile = n_.tile;                                                                                   \
+        c_slice = n_.slice;                                                                                \
+    }
+#define SZG_MX_TILE_START if (per_query) m_esl = m_q16[ctile];
+#define SZG_MX_TILE_END m_slice = c_slice;
+#else
             const uint64_t NP = n_it * (uint64_t)steps;  // 64-byte steps of this wave's tiles, walked as one stream
             uint64_t itile = tile_first, ctile = tile_first;
             int is = 0, cs = 0;
             const uint8_t *iptr = row_ptr(tile_first);
             float norm = 0.0f;
+#define SZG_MX_NEXT_I itile += tile_stride;
+#define SZG_MX_NEXT_C ctile += tile_stride;
+#define SZG_MX_TILE_START
+#define SZG_MX_TILE_END
+#endif
 #define SZG_MX_ISSUE(u)                                                                  \
     {                                                                                    \
         ring[u] = load_rows<NT>(iptr);                                                   \
         if (++is == steps) {                                                             \
             is = 0;                                                                      \
-            itile += tile_stride;                                                        \
+            SZG_MX_NEXT_I                                                                \
             iptr = row_ptr(itile);                                                       \
         } else {                                                                         \
             iptr += 1024;                                                                \
@@ -435,7 +547,10 @@ __global__ __launch_bounds__(256, (ROWS && NB == 1 && STEPS != 0) ? 4 : 2) void 
 #define SZG_MX_CONSUME(u)                                                                \
     {                                                                                    \
         const u32x4 v_ = ring[u];                                                        \
-        if (cs == 0) norm = a.row_norm[min(ctile * 16 + trow, last_row)];                \
+        if (cs == 0) {                                                                   \
+            norm = a.row_norm[min(ctile * 16 + trow, last_row)];                         \
+            SZG_MX_TILE_START                                                            \
+        }                                                                                \
         v4i32 bop_;                                                                      \
         bop_[0] = (int)(v_.x ^ 0x80808080u);                                             \
         bop_[1] = (int)(v_.y ^ 0x80808080u);                                             \
@@ -448,14 +563,17 @@ __global__ __launch_bounds__(256, (ROWS && NB == 1 && STEPS != 0) ? 4 : 2) void 
             accL[b_] = __builtin_amdgcn_mfma_i32_16x16x64_i8(al_, bop_, accL[b_], 0, 0, 0); \
         }                                                                                \
         if (++cs == steps) {                                                             \
+            SZG_MX_TILE_END                                                              \
             finish_tile(ctile, accM, accL, norm);                                        \
             _Pragma("unroll") for (int b_ = 0; b_ < NB; b_++)                            \
                 accM[b_] = accL[b_] = v4i32{0, 0, 0, 0};                                 \
             cs = 0;                                                                      \
-            ctile += tile_stride;                                                        \
+            SZG_MX_NEXT_C                                                                \
         }                                                                                \
     }
+#ifndef SZG_MX_MASKED
             uint64_t issued = D, consumed = 0;
+#endif
 #pragma unroll
             for (int u = 0; u < D; u++) {
                 SZG_MX_ISSUE(u)
@@ -463,6 +581,18 @@ __global__ __launch_bounds__(256, (ROWS && NB == 1 && STEPS != 0) ? 4 : 2) void 
             }
             __syncthreads();  // the image and the constants are complete
             read_consts();
+#ifdef SZG_MX_MASKED
+            // (no fixed count of steps: the stream ends on "no further tile")
+            while (ctile < n_tiles) {
+#pragma unroll
+                for (int u = 0; u < D; u++) {
+                    if (ctile < n_tiles) {
+                        SZG_MX_CONSUME(u)
+                        SZG_MX_ISSUE(u)
+                    }
+                }
+            }
+#else
             while (consumed + 2 * D <= NP) {
 #pragma unroll
                 for (int u = 0; u < D; u++) {
@@ -486,8 +616,13 @@ __global__ __launch_bounds__(256, (ROWS && NB == 1 && STEPS != 0) ? 4 : 2) void 
                     }
                 }
             }
+#endif
 #undef SZG_MX_ISSUE
 #undef SZG_MX_CONSUME
+#undef SZG_MX_NEXT_I
+#undef SZG_MX_NEXT_C
+#undef SZG_MX_TILE_START
+#undef SZG_MX_TILE_END
         }
 
         // block-wide k-select over the waves' lists, query by query
@@ -519,7 +654,23 @@ __global__ __launch_bounds__(256, (ROWS && NB == 1 && STEPS != 0) ? 4 : 2) void 
     }
 }
 
-#if defined(SZG_MX_SHARE)
+#if defined(SZG_MX_MASKED) && defined(SZG_MX_SHARE)
+template <int STEPS>
+hipError_t launch_mxms_steps(const ScanMaskedArgs &s, int grid, int block, size_t lds, hipStream_t stream)
+{
+    hipLaunchKernelGGL((scan_mx_kernel<SZG_SCAN_METRIC, STEPS, true, true, 2>), dim3(grid), dim3(block), lds, stream, s);
+    return hipGetLastError();
+}
+#elif defined(SZG_MX_MASKED)
+template <int STEPS>
+hipError_t launch_mxm_steps(const ScanMaskedArgs &s, bool rows, bool wide, int grid, int block, size_t lds, hipStream_t stream)
+{
+    if (wide) hipLaunchKernelGGL((scan_mx_kernel<SZG_SCAN_METRIC, STEPS, true, true, 2>), dim3(grid), dim3(block), lds, stream, s);
+    else if (rows) hipLaunchKernelGGL((scan_mx_kernel<SZG_SCAN_METRIC, STEPS, true, true>), dim3(grid), dim3(block), lds, stream, s);
+    else hipLaunchKernelGGL((scan_mx_kernel<SZG_SCAN_METRIC, STEPS, true, false>), dim3(grid), dim3(block), lds, stream, s);
+    return hipGetLastError();
+}
+#elif defined(SZG_MX_SHARE)
 // the rows' loads of the shared form: streamed past the caches like the two-block form's (1), or plain (0) -- the second
 // reader of a line has to find it on the die (DESIGN.md 6, round 15 keeps the measured choice)
 #ifndef SZG_MX_SHARE_NT
@@ -557,7 +708,62 @@ hipError_t launch_mxc_steps(const ScanArgs &a, bool wide, int grid, int block, s
 // (defined by its qualified name: it has to match its declaration in kernels.h)
 #define SZG_CAT2(a, b) a##b
 #define SZG_CAT(a, b) SZG_CAT2(a, b)
+#if defined(SZG_MX_MASKED)
+// the masked forms of ONE metric (objects of their own, -DSZG_MX_MASKED; with -DSZG_MX_SHARE the masked shared form)
+namespace szg {
+namespace {
+// (scan_variant's conditions, once more, for every masked form: a launch that does not meet them must not reach these kernels)
+bool mx_masked_ok(const ScanMaskedArgs &s, const ScanVariant &v, int block, size_t lds)
+{
+    const ScanArgs &a = s.a;
+    return v.matrix && v.masked && s.masked == 1 && scan_masked(a) && v.nontemporal && a.tiled && a.steps != 0 &&
+           (int)a.steps * 4 == a.map.r16 && a.planes == 2 && a.row_norm && a.block_lists && a.kp >= 1 && a.kp <= 64 && !a.collect &&
+           a.n_queries >= 1 && block >= 64 && block <= 256 && block % 64 == 0 && lds <= 64u * 1024u &&
+           v.matrix_steps == matrix_steps_form((int)a.steps) && (v.row_lists != 0) == matrix_row_lists(a.kp, a.select);
+}
+}  // namespace
+}  // namespace szg
 #if defined(SZG_MX_SHARE)
+hipError_t szg::SZG_CAT(launch_scan_mxms_m, SZG_SCAN_METRIC)(const ScanMaskedArgs &s, const ScanVariant &v, int grid, int block,
+                                                           size_t lds, hipStream_t stream)
+{
+    const ScanArgs &a = s.a;
+    // exactly the planned form: row lists, 33 .. 64 queries, an even grid -- share_map pairs its blocks -- the two-block LDS
+    if (!mx_masked_ok(s, v, block, lds) || !v.share || v.wide || !v.row_lists || a.kp > kRowListMax || a.wide == 1 ||
+        s.hi.share == 1)
+        return hipErrorInvalidValue;
+    if (a.n_queries <= kMatrixWideQueries || a.n_queries > kMatrixShareQueries) return hipErrorInvalidValue;
+    if (grid < 2 || grid % 2) return hipErrorInvalidValue;
+    if (lds != scan_lds_bytes(8, a.map, a.kp, block, kMatrixWideQueries, a.planes, 2)) return hipErrorInvalidValue;
+    switch (v.matrix_steps) {
+    case 12: return launch_mxms_steps<12>(s, grid, block, lds, stream);
+    case 6: return launch_mxms_steps<6>(s, grid, block, lds, stream);
+    default: return launch_mxms_steps<0>(s, grid, block, lds, stream);
+    }
+}
+#else
+hipError_t szg::SZG_CAT(launch_scan_mxm_m, SZG_SCAN_METRIC)(const ScanMaskedArgs &s, const ScanVariant &v, int grid, int block,
+                                                          size_t lds, hipStream_t stream)
+{
+    const ScanArgs &a = s.a;
+    if (!mx_masked_ok(s, v, block, lds) || v.share) return hipErrorInvalidValue;
+    const bool rows = v.row_lists != 0;
+    // the wide form: row lists, 17 .. kMatrixWideQueries queries, exactly the two-block LDS; every other launch holds at most
+    // kMaxSweepsPerLaunch
+    const bool wide = v.wide != 0;
+    if (wide && (!rows || a.wide == 1 || a.n_queries <= kMatrixQueries || a.n_queries > kMatrixWideQueries ||
+                 lds != scan_lds_bytes(8, a.map, a.kp, block, kMatrixWideQueries, a.planes, v.matrix_blocks())))
+        return hipErrorInvalidValue;
+    if (!wide && (a.n_queries > kMaxSweepsPerLaunch || lds != scan_lds_bytes(8, a.map, a.kp, block, kMatrixQueries, a.planes, 1)))
+        return hipErrorInvalidValue;
+    switch (v.matrix_steps) {
+    case 12: return launch_mxm_steps<12>(s, rows, wide, grid, block, lds, stream);
+    case 6: return launch_mxm_steps<6>(s, rows, wide, grid, block, lds, stream);
+    default: return launch_mxm_steps<0>(s, rows, wide, grid, block, lds, stream);
+    }
+}
+#endif
+#elif defined(SZG_MX_SHARE)
 // the shared form of ONE metric (objects of their own, -DSZG_MX_SHARE)
 hipError_t szg::SZG_CAT(launch_scan_mxs_m, SZG_SCAN_METRIC)(const ScanShareArgs &s, const ScanVariant &v, int grid, int block,
                                                           size_t lds, hipStream_t stream)

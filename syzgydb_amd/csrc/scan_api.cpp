@@ -770,6 +770,65 @@ int szg_debug_scan_share(int dim, int quant_bits, int n_queries, int kp, int pla
     return SZG_OK;
 }
 
+// the matrix sweep's masked forms (option sketch_masked) for a one-sweep top-k call of n_queries through the sketch whose
+// launches carry masks: the form a launch of min(n_queries, 64) takes, and the call's launches and passes as
+// sketch_call_plan, sketch_plan_batch and enqueue_topk split it (as szg_debug_scan_share walks the unmasked call)
+int szg_debug_scan_masked(int dim, int quant_bits, int n_queries, int kp, int planes, int norms, int tiled, int masked,
+                          int scan_group, int sketch_matrix, int sketch_select, int sketch_wide, int sketch_share, int sketch_masked,
+                          int shared_mask, szg_scan_masked_plan *out)
+{
+    if (!out) return fail(SZG_E_INVALID, "null argument");
+    if (kp < 0 || n_queries < 1) return fail(SZG_E_INVALID, "kp or n_queries out of range");
+    if (!szg::sketch_share_known(sketch_share)) return fail(SZG_E_INVALID, "sketch_share is 0, 1 or 2");
+    if (!szg::sketch_masked_known(sketch_masked)) return fail(SZG_E_INVALID, "sketch_masked is 0 or 1");
+    PlanHook h;
+    if (const int rc = h.sketch_rows(dim, quant_bits, kp, false, planes, norms, tiled, masked, scan_group, sketch_matrix, &sketch_select, &sketch_wide))
+        return rc;
+    h.in.share_opt = sketch_share;
+    h.in.masked_opt = sketch_masked;
+    const bool wide_serves = h.wide_launches() == szg::kMatrixWideQueries;
+    h.in.n_queries = std::min(n_queries, szg::kMatrixShareQueries);
+    const szg::ScanVariant v = szg::scan_variant(h.in);
+    memset(out, 0, sizeof(*out));
+    out->serves = v.matrix && v.masked ? 1 : 0;
+    out->wide = out->serves && v.wide ? 1 : 0;
+    out->share = out->serves && v.share ? 1 : 0;
+    out->tile_skip = out->serves && shared_mask ? 1 : 0;
+    out->steps_form = out->serves ? v.matrix_steps : 0;
+    h.in.n_queries = szg::kMatrixShareQueries;
+    const bool share_serves = wide_serves && szg::scan_variant(h.in).share != 0;
+    const int wide = !wide_serves || n_queries <= szg::kMatrixQueries ? 0 : (sketch_wide == 2 ? 2 : (n_queries >= kWideCallMin ? 1 : 0));
+    const int share = !share_serves || n_queries <= szg::kMatrixWideQueries
+                          ? 0
+                          : (sketch_share == 2 ? 2 : (wide == 1 && n_queries >= kShareCallMin ? 1 : 0));
+    for (const int nq : sketch_batch_sizes(n_queries, wide, share, 16)) {
+        const int per = share && nq > szg::kMatrixWideQueries
+                            ? szg::kMatrixShareQueries
+                            : ((wide || share) && nq > szg::kMatrixQueries ? szg::kMatrixWideQueries : szg::kMaxSweepsPerLaunch);
+        for (int j = 0; j < nq; j += per) {
+            h.in.n_queries = std::min(per, nq - j);
+            const int group = szg::scan_variant(h.in).group;
+            out->launches += 1;
+            out->passes += (h.in.n_queries + group - 1) / group;
+        }
+    }
+    return SZG_OK;
+}
+
+// what the masked forms served on the handle's sketch index since szg_reset_stats
+int szg_debug_sketch_masked(szg_index *ix, szg_sketch_masked_info *out)
+{
+    if (!ix || !out) return fail(SZG_E_INVALID, "null argument");
+    memset(out, 0, sizeof(*out));
+    std::lock_guard<std::mutex> lk(ix->sk_mu);
+    const szg_index *sk = ix->is_sketch ? ix : ix->sketch;
+    if (!sk) return SZG_OK;
+    out->launches = sk->mx_masked_launches;
+    out->skip_launches = sk->mx_masked_skip;
+    out->queries = sk->mx_masked_queries;
+    return SZG_OK;
+}
+
 // the matrix sweep's collect form for a collect call of n_queries queries with one sweep each (launches of 32: sketch_wide = 2)
 int szg_debug_scan_collect(int dim, int quant_bits, int n_queries, int planes, int norms, int tiled, int masked, int scan_group,
                            int sketch_matrix, int sketch_wide, int32_t *serves, int32_t *wide, int32_t *passes, uint64_t *lds_bytes, int32_t *steps_form)

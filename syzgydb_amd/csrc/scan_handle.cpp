@@ -650,10 +650,12 @@ int szg_reset_stats(szg_index *ix)
     std::lock_guard<std::mutex> lk(ix->stats_mu);
     ix->stats = szg_stats{};
     ix->mask_h2d = ix->mask_d2d = ix->mask_shared = 0;  // (szg_mask_stats' counters; live masks stay counted)
+    ix->mx_masked_launches = ix->mx_masked_skip = ix->mx_masked_queries = 0;  // (szg_debug_sketch_masked's)
     if (ix->sketch) {
         std::lock_guard<std::mutex> lk2(ix->sketch->stats_mu);
         ix->sketch->stats = szg_stats{};
         ix->sketch->mask_h2d = ix->sketch->mask_d2d = ix->sketch->mask_shared = 0;
+        ix->sketch->mx_masked_launches = ix->sketch->mx_masked_skip = ix->sketch->mx_masked_queries = 0;
     }
     return SZG_OK;
 }
@@ -673,6 +675,7 @@ static const char *scan_option_refusal(const std::string &n, int64_t value, bool
     if (n == "sketch_share") return szg::sketch_share_known(value) ? nullptr : "sketch_share is 0, 1 or 2";
     if (n == "sketch_bulk") return szg::sketch_bulk_known(value) ? nullptr : "sketch_bulk is 0 to 1024";
     if (n == "sketch_radius") return value == 0 || value == 1 ? nullptr : "sketch_radius is 0 or 1";
+    if (n == "sketch_masked") return szg::sketch_masked_known(value) ? nullptr : "sketch_masked is 0 or 1";
     *known = false;
     return nullptr;
 }
@@ -751,6 +754,8 @@ int szg_set_option(szg_index *ix, const char *name, int64_t value)
         ix->sketch_bulk = (int)value;
     } else if (n == "sketch_radius") {
         ix->sketch_radius = (int)value;
+    } else if (n == "sketch_masked") {
+        ix->sketch_masked = (int)value;
     } else if (n == "query_batch") {
         if (value < 1 || value > kMaxBatch) return fail(SZG_E_INVALID, "query_batch out of range");
         ix->query_batch = (int)value;

@@ -448,6 +448,9 @@ struct szg_index {
     int sketch_radius = 0;    // radius queries that would each take a sweep of their own (a lone query, radius_mq = 0) go
                               // through the sketch where it applies to the handle: 0 = never (the default: the option
                               // soaks, as the top-k pre-pass did, before a later change makes it automatic), 1 = always
+    int sketch_masked = 0;    // top-k launches of the sketch pre-pass with tombstones or filter masks take the matrix sweep's
+                              // masked forms wherever the same launch without masks would take the matrix sweep: 0 = never
+                              // (the default while the option soaks: masked launches keep the one-query kernel), 1 = always
     bool is_sketch = false;   // this index is the internal sketch of a float32 handle: its keys only bound
     int tie_mode = 0;         // 0: exact full replay on ties/NaN, 1: keep the fast answer
     int serialize_scans = 1;  // scan launches of a shard never overlap each other
@@ -484,6 +487,9 @@ struct szg_index {
                                           // compaction that moves rows) -- NOT by appends: older columns are stale
     std::atomic<uint64_t> mask_live{0}, mask_dev_bytes{0};
     std::atomic<uint64_t> mask_h2d{0}, mask_d2d{0}, mask_shared{0};  // szg_mask_stats (with the sketch index's own)
+    // szg_debug_sketch_masked (counted on the index whose shards were swept: the sketch index): launches that took a masked
+    // form of the matrix sweep, those of them whose eligibility was wave-uniform (the tile skip), and their queries
+    std::atomic<uint64_t> mx_masked_launches{0}, mx_masked_skip{0}, mx_masked_queries{0};
     // coalescing of concurrent single-query searches (szg_search_topk, n_queries == 1)
     std::mutex comb_mu;
     std::deque<struct PendingSearch *> comb_waiting;
@@ -651,6 +657,8 @@ void fill_collect_args(const szg_index *ix, const Shard *sh, const Ctx *c, bool 
 // the matrix sweep, on the grid g names: szg::launch_scan_share)
 int launch_scans_chained(szg_index *ix, Shard *sh, Ctx *c, const std::vector<szg::ScanArgs> &a, const LaunchGeom &g,
                          hipStream_t after = nullptr, int part = 0, const std::vector<szg::ScanShareHi> *hi = nullptr);
+// does launch `a` (8-bit rows, `block` threads) take a masked form of the matrix sweep under the index's options?
+bool scan_takes_masked_form(const szg_index *ix, const szg::ScanArgs &a, int block);
 // the sketch pre-pass: the sweep runs over a sketch shard, its merged lists are re-ranked on the float32 rows of the
 // shard it stands for, together with `extra` more rows per query that the caller has uploaded behind each list in
 // c->d_sent (kp + extra entries per query)
@@ -665,7 +673,8 @@ struct RerankOn {
                          // shared form where it serves (sketch_share_serves)
 };
 // does the matrix sweep's shared form serve an unmasked top-k launch of 33 .. szg::kMatrixShareQueries queries of sketch
-// index `sk` on shard `sh`: the wide form serves the shard (sketch_wide_serves), no dead rows, option sketch_share not 1
+// index `sk` on shard `sh`: the wide form serves the shard (sketch_wide_serves), no dead rows (or sketch_masked = 1: a
+// top-k launch with masks then takes the same form), option sketch_share not 1
 bool sketch_share_serves(const szg_index *sk, const Shard *sh, int kp, int list_opt);
 // The geometry of a shared launch on a shard whose plain sweep takes `g`: grid 2 S and S lists of m entries per query.
 // Everything that sizes or walks the lists of a shared launch reads S from here (szg::share_slices, as the kernel does).

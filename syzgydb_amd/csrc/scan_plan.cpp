@@ -53,12 +53,16 @@ ScanVariant scan_variant(const ScanPlanIn &in)
     // Its collect form (radius searches through the sketch) keeps none, so neither kp nor the
     // selection matter, and the two-block form needs the images and constants alone (48.4 KiB at 768 dimensions).  A
     // launch that must keep the one-query collect kernel (a query swept again on its own) says matrix_opt = 1.
+    // A masked top-k launch takes it under sketch_masked = 1 (the masked form: the same launches, the same LDS -- the
+    // masks need none); a masked collect launch never does.
     const int list_kp = in.collect ? 0 : in.kp;
-    if (in.qbits == 8 && !in.masked && !v.deep && (in.collect || in.kp >= 1) && in.tiled && m.r16 > 0 && m.r16 % 4 == 0 &&
+    const bool masked_form = in.masked && in.masked_opt == 1 && !in.collect;
+    if (in.qbits == 8 && (!in.masked || masked_form) && !v.deep && (in.collect || in.kp >= 1) && in.tiled && m.r16 > 0 && m.r16 % 4 == 0 &&
         in.planes == 2 && in.norms && in.group == 0 && in.matrix_opt != 1 &&
         in.n_queries >= (in.matrix_opt == 2 ? 1 : kMatrixMinQueries) && in.block >= kWave && in.block <= 256 &&
         in.block % kWave == 0 && scan_lds_bytes(in.qbits, m, list_kp, in.block, kMatrixQueries, in.planes, 1) <= kLdsMax) {
         v.matrix = 1;
+        v.masked = masked_form ? 1 : 0;
         v.matrix_steps = matrix_steps_form(m.r16 / 4);
         v.group = kMatrixQueries;
         v.shaped = 0;

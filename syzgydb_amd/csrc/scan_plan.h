@@ -95,6 +95,8 @@ struct ScanVariant {
     int share = 0;    // the two-block form shared between paired blocks (share_map): a launch of kMatrixWideQueries + 1 ..
                       // kMatrixShareQueries queries, one pass per column group of kMatrixWideQueries, both over one row read
                       // from HBM where the partner's lines are still on the die (its own launcher: launch_scan_share)
+    int masked = 0;   // the matrix sweep's masked form (option sketch_masked; objects of their own, launch_scan_masked): the
+                      // launch has tombstones or filter masks and takes the matrix sweep all the same
 };
 // What "automatic" (scan_group = 0) asks for, where a launch qualifies.
 constexpr int kScanGroupAuto = 4;
@@ -129,6 +131,10 @@ constexpr bool sketch_wide_known(int64_t v) { return v == 0 || v == 1 || v == 2;
 // form would serve at 32 runs as two column groups on paired blocks.  0 = automatic and 2 = every sketch call of more
 // than kMatrixWideQueries queries differ on the host only (which calls form such launches); 1 = never.
 constexpr bool sketch_share_known(int64_t v) { return v == 0 || v == 1 || v == 2; }
+// The masked form (option sketch_masked): 1 = a top-k launch with tombstones or filter masks takes
+// the matrix sweep -- one block, wide, shared -- wherever the same launch without masks would; 0 = masked launches keep
+// the one-query kernel.
+constexpr bool sketch_masked_known(int64_t v) { return v == 0 || v == 1; }
 
 // Ring depths of the G > 1 kernels.  A row-shape kernel of P pieces per lane exists at its shape's own depth (the
 // G = 1 kernel's) and, where kGroupRingAlt divides P and differs from it, at kGroupRingAlt as well: scan_group_ring
@@ -198,6 +204,7 @@ struct ScanPlanIn {
     int select_opt = 0;     // the sketch_select option
     int wide_opt = 1;       // the sketch_wide option (1 = never, what callers that do not know it get)
     int share_opt = 1;      // the sketch_share option (1 = never, what callers that do not know it get)
+    int masked_opt = 0;     // the sketch_masked option (0 = off, what callers that do not know it get)
 };
 ScanVariant scan_variant(const ScanPlanIn &in);
 

@@ -178,12 +178,20 @@ int launch_scans_chained(szg_index *ix, Shard *sh, Ctx *c, const std::vector<szg
     const int n = (int)a.size();
     if (hi && (int)hi->size() != n) return fail(SZG_E_INVALID, "shared launches: one record per launch");
     auto shared = [&](int j) { return hi && a[j].n_queries > szg::kMatrixWideQueries; };
+    // launches with masks that take a masked form of the matrix sweep (option sketch_masked; szg::launch_scan_masked)
+    std::vector<char> mxm(n, 0);
+    for (int j = 0; j < n; j++) mxm[j] = scan_takes_masked_form(ix, a[j], g.block) ? 1 : 0;
+    szg::ScanShareHi no_hi;
+    memset(&no_hi, 0, sizeof(no_hi));
+    no_hi.share = ix->sketch_share;
     // (ev_up: recorded by enqueue_queries)
     int rc = chain_sweeps(ix, sh, c, after ? after : c->pass.work, part, n, "szg::launch_scan", [&](hipStream_t st) {
         hipError_t e = hipSuccess;
         for (int j = 0; j < n && e == hipSuccess; j++)
-            e = shared(j) ? szg::launch_scan_share(ix->bits, ix->metric, a[j], (*hi)[j], g.grid, g.block, st)
-                          : szg::launch_scan(ix->bits, ix->metric, a[j], g.grid, g.block, st);
+            e = mxm[j] ? szg::launch_scan_masked(ix->bits, ix->metric, a[j], hi ? (*hi)[j] : no_hi, ix->sketch_masked, g.grid,
+                                                 g.block, st)
+                       : (shared(j) ? szg::launch_scan_share(ix->bits, ix->metric, a[j], (*hi)[j], g.grid, g.block, st)
+                                    : szg::launch_scan(ix->bits, ix->metric, a[j], g.grid, g.block, st));
         return e;
     });
     if (rc) return rc;
@@ -191,12 +199,33 @@ int launch_scans_chained(szg_index *ix, Shard *sh, Ctx *c, const std::vector<szg
     uint64_t sweeps = 0;  // passes over the rows: one per group of a launch's queries (one per query where the launch
                           // does not qualify for groups); a shared launch counts one per column group, as requested --
                           // what its second reader finds on the die is not taken off
-    for (int j = 0; j < n; j++)
-        sweeps += shared(j) ? (uint64_t)((a[j].n_queries + szg::kMatrixWideQueries - 1) / szg::kMatrixWideQueries)
-                            : (uint64_t)szg::scan_passes(ix->bits, a[j], g.block);
+    // (a masked form: one pass per group of the form it takes, as scan_passes counts the unmasked launch)
+    for (int j = 0; j < n; j++) {
+        if (shared(j)) {
+            sweeps += (uint64_t)((a[j].n_queries + szg::kMatrixWideQueries - 1) / szg::kMatrixWideQueries);
+        } else if (mxm[j]) {
+            const int group = szg::scan_variant(szg::scan_masked_plan_in(ix->bits, a[j], ix->sketch_share, ix->sketch_masked, g.block)).group;
+            sweeps += (uint64_t)((a[j].n_queries + group - 1) / group);
+        } else {
+            sweeps += (uint64_t)szg::scan_passes(ix->bits, a[j], g.block);
+        }
+        if (mxm[j]) {
+            ix->mx_masked_launches++;
+            ix->mx_masked_queries += (uint64_t)a[j].n_queries;
+            if (!a[j].allow_bits || a[j].allow_stride == 0) ix->mx_masked_skip++;
+        }
+    }
     ix->stats.scan_launches += n;
     ix->stats.scan_bytes += sweeps * sh->n_rows * (uint64_t)ix->row_bytes;
     return SZG_OK;
+}
+
+bool scan_takes_masked_form(const szg_index *ix, const szg::ScanArgs &a, int block)
+{
+    // (the sketch index's top-k launches: plain 8-bit handles and collect launches stay as they are)
+    if (ix->sketch_masked != 1 || !ix->is_sketch || ix->bits != 8 || a.collect || !szg::scan_masked(a) || !a.row_norm) return false;
+    const szg::ScanVariant v = szg::scan_variant(szg::scan_masked_plan_in(ix->bits, a, ix->sketch_share, ix->sketch_masked, block));
+    return v.matrix != 0 && v.masked != 0;
 }
 
 // A resident mask knows its exact count; the pass rate of words that came from the host is estimated from a sample.
@@ -230,7 +259,8 @@ int sketch_list_len(int want, int kp, int grid)
 bool sketch_wide_serves(const szg_index *sk, const Shard *sh, int kp, int list_opt)
 {
     const bool collect = kp == 0;  // (no lists: nothing of kp or list_opt bears on the answer)
-    if (sk->sketch_wide == 1 || sh->has_dead || kp > 64) return false;
+    // (dead rows: a top-k launch takes the masked form of the same shape under sketch_masked = 1; a collect launch never)
+    if (sk->sketch_wide == 1 || (sh->has_dead && (collect || sk->sketch_masked != 1)) || kp > 64) return false;
     const LaunchGeom g = scan_geometry(sk, sh, kp, true);
     const int m = collect ? 0 : sketch_list_len(list_opt, kp, g.grid);
     szg::ScanPlanIn in{sk->bits, sk->map, sk->layout.tiled != 0, m, collect, false, sk->ring, !sk->shape_kernels};
@@ -255,7 +285,8 @@ ShareGeom share_geometry(const LaunchGeom &g, int list_opt, int kp)
 
 bool sketch_share_serves(const szg_index *sk, const Shard *sh, int kp, int list_opt)
 {
-    if (sk->sketch_share == 1 || kp < 1 || sh->has_dead || !sketch_wide_serves(sk, sh, kp, list_opt)) return false;
+    if (sk->sketch_share == 1 || kp < 1 || (sh->has_dead && sk->sketch_masked != 1) || !sketch_wide_serves(sk, sh, kp, list_opt))
+        return false;
     // (the wide form was asked with the plain launch's list length; the shared launch's S lists may be longer)
     const LaunchGeom g = scan_geometry(sk, sh, kp, true);
     const ShareGeom s = share_geometry(g, list_opt, kp);
@@ -285,8 +316,10 @@ int enqueue_topk(szg_index *ix, Shard *sh, Ctx *c, int kp, int nq, bool has_allo
     c->pass.out_stride = stride;
     c->pass.keys = ListKeys::Single;
     HIPCHK(hipSetDevice(sh->device));
-    LaunchGeom g = scan_geometry(ix, sh, kp, !has_allow && !sh->has_dead);
-    const bool masked = has_allow || sh->has_dead;
+    // (masked: the launches have masks AND keep the one-query kernel; under sketch_masked = 1 they split and launch as the
+    // unmasked call of the same size does, and every launch that qualifies takes the matrix sweep's masked form)
+    const bool masked = (has_allow || sh->has_dead) && !(on && ix->sketch_masked == 1);
+    LaunchGeom g = scan_geometry(ix, sh, kp, !masked);
     // One part -- or, for a short call (Pass::early_n), two: the sweeps of queries [0, early_n), whose merges, re-rank and
     // copy-back leave the scan stream for the context's own (one event), and the last few queries, whose tail is all
     // that is left to do after the call's final sweep.
@@ -348,7 +381,13 @@ int enqueue_topk(szg_index *ix, Shard *sh, Ctx *c, int kp, int nq, bool has_allo
         const float *norms = nullptr;
         bool asked = false;
         for (szg::ScanArgs &a : args) {
-            if (!szg::scan_wants_norms(ix->bits, a, g.block)) continue;
+            bool wants = szg::scan_wants_norms(ix->bits, a, g.block);
+            if (!wants && ix->sketch_masked == 1 && szg::scan_masked(a)) {  // (a masked form of the matrix sweep reads them too)
+                szg::ScanPlanIn in = szg::scan_masked_plan_in(ix->bits, a, ix->sketch_share, ix->sketch_masked, g.block);
+                in.norms = true;
+                wants = szg::scan_variant(in).matrix != 0;
+            }
+            if (!wants) continue;
             if (!asked) {
                 int nrc = SZG_OK;
                 norms = scan_row_norms(ix, sh, &nrc);

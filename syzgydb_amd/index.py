@@ -836,6 +836,14 @@ class ScanIndex:
         out["exc_rows"] = exc[: info.n_exc]
         return out
 
+    def sketch_masked_info(self):
+        """Test hook: what the matrix sweep's masked forms (option sketch_masked) served on the sketch index since
+        reset_stats (szg_debug_sketch_masked): launches that took one, skip_launches of them with the tile skip (one mask
+        for every query, or tombstones alone), and the queries of all of them."""
+        info = _lib.SzgSketchMaskedInfo()
+        check(self._L.szg_debug_sketch_masked(self._h, ctypes.byref(info)), "szg_debug_sketch_masked")
+        return {name: int(getattr(info, name)) for name, _ in _lib.SzgSketchMaskedInfo._fields_}
+
     def sketch_rows(self, first_row=0, n_rows=None):
         """Test hook: (sketch rows [first_row, first_row + n_rows) in the packed 8-bit form, uint8[n_rows, dim]; the live
         words of the sketch shards, uint64[ceil(sketch rows / 64)]) -- szg_debug_sketch_rows; never a sync."""
@@ -952,6 +960,23 @@ def scan_share_plan(dim, quant_bits, n_queries, kp=8, planes=2, norms=True, tile
             "lds_bytes": lds.value, "batches": [int(batches[i]) for i in range(min(nb.value, cap))]}
 
 
+def scan_masked_plan(dim, quant_bits, n_queries, kp=8, planes=2, norms=True, tiled=True, masked=True, scan_group=0,
+                     sketch_matrix=0, sketch_select=0, sketch_wide=0, sketch_share=0, sketch_masked=0, shared_mask=True):
+    """Host-only test hook: the matrix sweep's masked forms (option sketch_masked) for a one-sweep top-k call of n_queries
+    queries through the sketch whose launches carry masks (shared_mask: one mask for every query or tombstones alone) --
+    whether a launch of min(n_queries, 64) takes a masked form, whether that is the two-block (wide) or the shared form,
+    whether it skips tiles without an eligible row, its STEPS form, and the call's scan launches and passes over the rows."""
+    L = _lib.load()
+    p = _lib.SzgScanMaskedPlan()
+    check(L.szg_debug_scan_masked(int(dim), int(quant_bits), int(n_queries), int(kp), int(planes), int(bool(norms)),
+                                  int(bool(tiled)), int(bool(masked)), int(scan_group), int(sketch_matrix),
+                                  int(sketch_select), int(sketch_wide), int(sketch_share), int(sketch_masked),
+                                  int(bool(shared_mask)), ctypes.byref(p)), "szg_debug_scan_masked")
+    out = {name: bool(getattr(p, name)) for name in ("serves", "wide", "share", "tile_skip")}
+    out.update(steps=int(p.steps_form), launches=int(p.launches), passes=int(p.passes))
+    return out
+
+
 def scan_collect_plan(dim, quant_bits, n_queries, planes=2, norms=True, tiled=True, masked=False, scan_group=0,
                       sketch_matrix=0, sketch_wide=0):
     """Host-only test hook: the matrix sweep's collect form (radius searches through the sketch, option sketch_radius)
@@ -993,7 +1018,7 @@ def merge_short_plan(n_lists, m, kp):
 def option_check(name, value):
     """Host-only test hook (no device needed): raises SzgError where ScanIndex.set_option would refuse `value` for the
     one-sweep kernel's option `name` (scan_group, scan_group_ring, scan_norms, sketch_planes, sketch_matrix, sketch_select,
-    sketch_wide, sketch_share, sketch_bulk, sketch_radius)."""
+    sketch_wide, sketch_share, sketch_bulk, sketch_radius, sketch_masked)."""
     L = _lib.load()
     check(L.szg_debug_option_check(name.encode(), int(value)), "szg_debug_option_check")
 
