@@ -962,6 +962,18 @@ int szg_debug_scan_group_ring(int dim, int quant_bits, int kp, int scan_group, i
 int szg_debug_option_check(const char *name, int64_t value);
 
 /*
+ * Test hook, host only: *eps = the bound on |scan key - real-number key| that certification uses for a key `key` (in
+ * the key's units: -cos, or squared distance times maxInt^2 for rows of 16 bits or fewer) of a collection of dim
+ * elements, quant_bits and metric, for the arithmetic `family` -- 0 the one-sweep kernel, 1 the int8 shared sweep, 2 the
+ * bfloat16 shared sweep, 3 the float32 shared sweep.  planes: the digit planes of the one-sweep 8-bit query (2 on a
+ * sketch index, else 3); mq_planes: those of the int8 shared sweep's query (0: this build's); qnorm, qnorm2: |g| and |g|^2 of the prepared query g (q / |q|, maxInt q, or q); qscale,
+ * mq_qscale: the quantization step of the one-sweep integer query and of the int8 shared sweep's.  The arithmetic is
+ * csrc/key_bound.h's, the one every search uses.
+ */
+int szg_debug_key_eps(int dim, int quant_bits, int metric, int planes, int mq_planes, int family, double key, double qnorm,
+                      double qnorm2, double qscale, double mq_qscale, double *eps);
+
+/*
  * Test hook, host only: the checks szg_index_reorder makes on its list before anything moves, and the split of the
  * new rows over n_shards shards -- the same code, the same return codes and error text.  live_words: ceil(n_rows / 64)
  * words, bit r == 0 -> row r is tombstoned (NULL: every row is live); src_rows[0 .. n): the list (no row base);

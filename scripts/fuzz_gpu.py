@@ -1,7 +1,8 @@
 """Differential fuzzing of the C-ABI search entry points against the CPU oracle.
 
 Random shapes (dim, quantization, metric, rows, k, batch size), filter masks, tombstones,
-two-shard handles, duplicate-heavy and scaled corpora, random tunables.  Every answer must be
+two-shard handles, duplicate-heavy and scaled corpora, queries at and within a few float32 spacings of stored rows
+("coincident", at every row width), random tunables.  Every answer must be
 the oracle's: same rows in the same order, bit-equal float64 distances (NaN == NaN).
 
     python scripts/fuzz_gpu.py [seconds] [seed] [--iterations N] [--certificates]
@@ -28,6 +29,7 @@ ap.add_argument("--certificates", action="store_true", help="check every call's 
 args = ap.parse_args()
 budget, seed = args.seconds, args.seed
 rng = np.random.default_rng(seed)
+rng_near = np.random.default_rng([seed, 0x6E656172])   # the coincident queries' own stream: every other draw of a seed stays as it was
 DIMS = [1, 2, 3, 5, 16, 17, 31, 32, 33, 64, 100, 128, 129, 384, 500, 768, 1024]
 OPTS = [("queries_per_launch", [1, 3, 16]), ("multi_query", [0, 1]), ("force_matrix", [0, 0, 1]),
         ("serialize_scans", [0, 1]), ("mq_min", [2, 8]), ("slack", [0, 16, 40]), ("mq_hits", [64, 1024]),
@@ -108,6 +110,21 @@ while (it < args.iterations) if args.iterations else (time.time() < t_end):
         Q = Q * 1e3 + 5e3
     if rng.random() < 0.2:
         Q[0] = orc.decode_vector(rows[int(rng.integers(0, n))], dim, bits)   # a stored row as the query
+    coincident = rng_near.random() < 0.15   # at every width: queries that round to a stored row, or sit 1, 3 or 17 spacings
+    if coincident:                           # off it -- a stored row itself (above) is exact on 32-bit rows; a key of 0 over a
+        for qj in range(min(nq, 4)):         # positive real-number key is not
+            x = orc.decode_vector(rows[int(rng_near.integers(0, n))], dim, bits)
+            if not np.isfinite(x).all():
+                continue
+            g = x * (65535.0 if bits == 16 else 1.0)   # the spacing of the prepared element, back in the query's units
+            sp = np.spacing(np.abs(g).astype(np.float32)).astype(np.float64) / (65535.0 if bits == 16 else 1.0)
+            if bits <= 8:
+                sp = np.full(dim, np.abs(x).max() / float(rng_near.choice([16000.0, 30000.0, 1000000.0])))   # a quantization step
+            move = float(rng_near.choice([0.25, 0.25, 1.0, 3.0, 17.0]))
+            at = rng_near.random(dim) < float(rng_near.choice([0.1, 1.0]))
+            at[int(rng_near.integers(0, dim))] = True
+            step = rng_near.uniform(-1, 1, dim) if move < 1 else rng_near.choice((-1.0, 1.0), dim)
+            Q[qj] = x + at * step * move * sp
     if rng.random() < 0.1:
         Q[-1] = 0.0
     allow = None
@@ -117,7 +134,7 @@ while (it < args.iterations) if args.iterations else (time.time() < t_end):
     devices = [0, 0] if rng.random() < 0.25 else [0]
     opts = {name: int(rng.choice(vals)) for name, vals in OPTS if rng.random() < 0.3}
     dead = []
-    desc = dict(it=it, bits=bits, metric=metric, dim=dim, n=n, nq=nq, k=k, kind=kind, masked=allow is not None,
+    desc = dict(it=it, bits=bits, metric=metric, dim=dim, n=n, nq=nq, k=k, kind=kind, coincident=coincident, masked=allow is not None,
                 resident=resident, devices=devices, opts=opts)
     try:
         with ScanIndex(dim, bits, metric, devices=devices) as ix:

@@ -64,6 +64,8 @@ EXPORTS = [
     "szg_debug_sketch_info", "szg_debug_sketch_rows",
     # the matrix sweep's masked forms (option sketch_masked): the plan hook and the counters
     "szg_debug_scan_masked", "szg_debug_sketch_masked",
+    # the certification bound of a key as a pure function (csrc/key_bound.h), host only
+    "szg_debug_key_eps",
 ]
 # szg_cert_record.pass / .keys, szg_cert_entry.flags
 SZG_CERT_TOPK, SZG_CERT_SKETCH, SZG_CERT_ESCALATION, SZG_CERT_RADIUS_SINGLE, SZG_CERT_RADIUS_SHARED = range(5)
@@ -438,6 +440,9 @@ def load():
     if hasattr(L, "szg_debug_option_check"):
         L.szg_debug_option_check.restype = ctypes.c_int
         L.szg_debug_option_check.argtypes = [ctypes.c_char_p, ctypes.c_int64]
+    if hasattr(L, "szg_debug_key_eps"):   # (an older build for an A/B run has no such hook)
+        L.szg_debug_key_eps.restype = ctypes.c_int
+        L.szg_debug_key_eps.argtypes = [ctypes.c_int] * 6 + [ctypes.c_double] * 5 + [f64p]
     if hasattr(L, "szg_debug_device_memory"):   # (as the masks: an older build for an A/B run does not count)
         L.szg_debug_device_memory.restype = ctypes.c_int
         L.szg_debug_device_memory.argtypes = [u64p, u64p]

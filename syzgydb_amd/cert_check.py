@@ -490,7 +490,7 @@ def _bf16_query(corpus, q):
 def bf16_emulated(corpus, Q, queries, rows=None):
     """The keys the bfloat16 sweeps would give rows `rows` (None: every row) for the listed queries if the matrix core
     summed exactly, and the float32-accumulation part of key_eps's bfloat16 branch at those keys (4 n u, cosine;
-    3 n u s^2, Euclid): two arrays [len(queries), len(rows)].
+    3 n u s^2 + 4 n 2^-126, Euclid: the second term is float32's underflow, which the float64 emulation does not have): two arrays [len(queries), len(rows)].
 
     Operands, as build_image_bf16 and the kernels form them: the query is q / |q| (cosine) or maxInt * q (Euclid, rows
     of 16 or 8 bits; q itself otherwise), narrowed to float32 and rounded to bfloat16.  A row element is the float32
@@ -524,7 +524,11 @@ def bf16_emulated(corpus, Q, queries, rows=None):
             return -dot / np.sqrt(nrm)[None, :], np.full(dot.shape, 4.0 * nn * u)
         key = nrm[None, :] + qnorm2[:, None] - 2 * dot
         s = 2.0 * np.sqrt(qnorm2)[:, None] + np.sqrt(np.abs(key))
-        return key, 3.0 * nn * u * s * s
+        # (the emulation sums in float64, whose range the sweep's float32 sums do not have: a term below the smallest
+        # normal float32 may be lost whole, to underflow or to the matrix core's flush -- 2^-126 per term of the three
+        # sums and the finish.  A query within a subnormal spacing of an all-zero row has an emulated key of 1e-90 and
+        # a float32 key of 0; key_eps carries 1e-30 for the same reason.)
+        return key, 3.0 * nn * u * s * s + 4.0 * nn * 2.0 ** -126
 
 
 def check_bf16_tight(corpus, Q, recs, ents, margins=None, what=()):

@@ -1,5 +1,6 @@
 // scan_query.cpp -- the query as the kernels want it, and the bounds on what their arithmetic loses.
 #include "scan_internal.h"
+#include "key_bound.h"
 
 namespace szgi {
 
@@ -178,79 +179,24 @@ int scan_planes(const szg_index *ix)
     return ix->bits == 8 && ix->is_sketch && ix->sketch_planes != 3 ? 2 : 3;
 }
 
-// Bound on |scan key - real-number key| (see DESIGN.md "certification").
+// Bound on |scan key - real-number key| (see DESIGN.md "certification"): the arithmetic is key_bound.h's, a pure
+// function of what is gathered here.
 double key_eps(const szg_index *ix, double key, const QMeta &m)
 {
-    const double k = std::fabs(key);
-    if (m.mq) {
-        // shared sweep: float32 everywhere (quantized rows decode to exact integers first).
-        // cosine: dot and norm each carry <= (dim+16) u relative error.  euclid: the key is
-        // |x|^2 - 2 x.g + |g|^2, three float32 sums whose magnitudes are bounded by
-        // (|x| + |g|)^2 <= (2|g| + sqrt(key))^2 -- an absolute bound, far looser than the
-        // difference form's when rows sit far from the origin; certification then simply
-        // escalates more often.
-        // (64-bit rows are narrowed to float32 element by element first: one more rounding of 2^-24 per operand,
-        // i.e. u |x||g| on the dot product and 2u |x|^2 on the norm -- four more units of n cover both)
-        const double u = 0x1p-24, n = (double)ix->dim + 16.0 + (ix->bits == 64 ? 4.0 : 0.0);
-        if (m.mq_bf16) {
-            // bfloat16 sweep: each operand is rounded to 8 significant bits -- a bfloat16 keeps 7 fraction bits, so the
-            // spacing at 1 is 2^-7 and round-to-nearest moves a value by at most 2^-8 of itself (the query once more
-            // from float32) -- the products are exact in float32 and summed by the matrix core in float32.
-            // |sum bf(x_i) bf(g_i) - sum x_i g_i| <= c |x| |g| (Cauchy-Schwarz) with
-            // c = (1 + 2^-8)^2 (1 + 2^-24) - 1 < 1.01 * 2^-7; the float32 part of the bound is doubled (the
-            // accumulation order and rounding of the matrix core are its own).  (Rounds 2-3 had 2^-9 per operand
-            // here, i.e. half this band: a 2-dimensional corpus far from the origin, where both elements can round
-            // the same way, showed a key 0.0044 off -- scripts/fuzz_gpu.py seed 311.  At >= 16 dimensions the
-            // errors never lined up, which is why nothing had caught it.)
-            const double c = 1.01 * 0x1p-7;
-            if (ix->metric == SZG_COSINE) return c + 4.0 * n * u + 1e-6;
-            // euclid: the key moves by 2 c |x| |g|, and |x| <= |g| + d with d^2 <= key + 2 c |x| |g|
-            // gives |x| <= 1.1 |g| + sqrt(key) for this c; the last term keeps key - eps(key) monotone
-            const double s = 2.0 * m.qnorm + std::sqrt(k);
-            return 2.0 * c * m.qnorm * (1.1 * m.qnorm + std::sqrt(k)) + c * c * m.qnorm2 + 3.0 * n * u * s * s + 1e-30;
-        }
-        if (ix->metric == SZG_COSINE) return 2.0 * n * u;
-        const double s = 2.0 * m.qnorm + std::sqrt(k);
-        return 1.5 * n * u * s * s + 1e-30;
-    }
-    if (m.mq_int) {
-        // as the integer branch below with the sweep's own quantization step; the row operand is
-        // v' = v - 128 (8-bit rows) or the nibble x in 0..15 (4-bit rows)
-        const double M = (double)((1u << ix->bits) - 1u);
-        const double V = ix->bits == 8 ? 128.0 : 16.0, Qmax = szg::kMqQmax;
-        const double fl = 16.0 * 0x1p-24 * m.mq_qscale * Qmax * V * (double)ix->dim;
-        if (ix->metric == SZG_COSINE)
-            return 0.5 * m.mq_qscale * std::sqrt((double)ix->dim) + fl / std::sqrt((double)ix->dim) + 0x1p-21;
-        return m.mq_qscale * M * (double)ix->dim + 2.0 * fl +
-               0x1p-21 * (k + m.qnorm2 + M * M * (double)ix->dim) + 1e-30;
-    }
-    if (ix->bits == 8 || ix->bits == 4) {
-        // integer paths: the per-lane sums are exact.  What is left is (a) the query's
-        // quantization, |v_i - qscale*Q_i| <= qscale/2, and (b) the float32 roundings of
-        // the row finish: the plane combination and the reduction over the lanes act on
-        // terms bounded by sum |Q_i||v'_i| <= Qmax*V*dim (V = 128 resp. 8), i.e. an
-        // absolute error <= 16*2^-24 * qscale*Qmax*V*dim in units of sum v n.
-        // Two planes on a sketch index (scan_planes; Qmax = 16000, qscale = vmax / 16000 the two-plane step): nothing
-        // in (a) or (b) depends on the plane count but through qscale and Qmax.  (a) grows with the step -- cosine:
-        // 0.5 qscale sqrt(dim), Euclid: qscale M dim, 62.5 times the three-plane terms.  (b) does not move: qscale*Qmax
-        // = vmax whatever Qmax is, and the two-plane key fmaf(128, M, L) rounds once where the three-plane one rounds
-        // twice, with |128 M + L| <= Qmax*V*(elements of the lane) as before.
-        const double M = (double)((1u << ix->bits) - 1u);
-        const double V = ix->bits == 8 ? 128.0 : 8.0;
-        const double Qmax = ix->bits == 8 ? scan_qmax8(ix) : szg::kQmax4;
-        const double fl = 16.0 * 0x1p-24 * m.qscale * Qmax * V * (double)ix->dim;
-        if (ix->metric == SZG_COSINE)  // divided by |n| >= sqrt(dim) (every n is odd)
-            return 0.5 * m.qscale * std::sqrt((double)ix->dim) + fl / std::sqrt((double)ix->dim) + 0x1p-21;
-        return m.qscale * M * (double)ix->dim + 2.0 * fl +
-               0x1p-21 * (k + m.qnorm2 + M * M * (double)ix->dim) + 1e-30;
-    }
-    const double u = ix->bits == 64 ? 0x1p-53 : 0x1p-24;
-    const double n = (double)ix->dim + 16.0;
-    if (ix->metric == SZG_COSINE) {
-        return 2.0 * n * u + (ix->bits == 64 ? 0x1p-22 : 0.0);
-    }
-    return 2.0 * n * u * k + 8.0 * u * m.qnorm * std::sqrt(k) + (ix->bits == 64 ? 0x1p-22 * k : 0.0) +
-           1e-37;
+    szg::KeyBoundIn b;
+    b.dim = ix->dim;
+    b.bits = ix->bits;
+    b.cosine = ix->metric == SZG_COSINE ? 1 : 0;
+    b.planes = scan_planes(ix);
+    b.mq_planes = szg::kMqPlanes;
+    b.mq = m.mq;
+    b.mq_bf16 = m.mq_bf16;
+    b.mq_int = m.mq_int;
+    b.qnorm = m.qnorm;
+    b.qnorm2 = m.qnorm2;
+    b.qscale = m.qscale;
+    b.mq_qscale = m.mq_qscale;
+    return szg::key_bound(b, key);
 }
 
 // ---- shared sweeps: B queries share one pass of the corpus ------------
@@ -332,3 +278,34 @@ int mq_blocks(const szg_index *ix, int nq, bool radius)
 }
 
 }  // namespace szgi
+
+// host-only test hook: key_bound.h's answer, no handle and no device (family: 0 the one-sweep kernel, 1 the int8 shared
+// sweep, 2 the bfloat16 shared sweep, 3 the plain float32 shared sweep)
+int szg_debug_key_eps(int dim, int quant_bits, int metric, int planes, int mq_planes, int family, double key, double qnorm,
+                      double qnorm2, double qscale, double mq_qscale, double *eps)
+{
+    using szgi::fail;
+    if (!eps) return fail(SZG_E_INVALID, "null argument");
+    if (dim <= 0 || dim > (1 << 20)) return fail(SZG_E_INVALID, "dim out of range");
+    if (szgi::row_bytes_of(quant_bits, dim) < 0) return fail(SZG_E_INVALID, "unsupported quantization");
+    if (metric != SZG_COSINE && metric != SZG_EUCLIDEAN) return fail(SZG_E_INVALID, "unknown metric");
+    if (planes != 2 && planes != 3) return fail(SZG_E_INVALID, "planes is 2 or 3");
+    if (mq_planes != 0 && mq_planes != 2 && mq_planes != 3) return fail(SZG_E_INVALID, "mq_planes is 0 (the build's), 2 or 3");
+    if (family < 0 || family > 3) return fail(SZG_E_INVALID, "family is 0 (one sweep), 1 (int8), 2 (bfloat16) or 3 (float32)");
+    if (family == 1 && quant_bits > 8) return fail(SZG_E_INVALID, "the int8 shared sweep serves 8- and 4-bit rows");
+    szg::KeyBoundIn b;
+    b.dim = dim;
+    b.bits = quant_bits;
+    b.cosine = metric == SZG_COSINE ? 1 : 0;
+    b.planes = planes;
+    b.mq_planes = mq_planes ? mq_planes : szg::kMqPlanes;
+    b.mq = family >= 2;
+    b.mq_bf16 = family == 2;
+    b.mq_int = family == 1;
+    b.qnorm = qnorm;
+    b.qnorm2 = qnorm2;
+    b.qscale = qscale;
+    b.mq_qscale = mq_qscale;
+    *eps = szg::key_bound(b, key);
+    return SZG_OK;
+}

@@ -1023,6 +1023,23 @@ def option_check(name, value):
     check(L.szg_debug_option_check(name.encode(), int(value)), "szg_debug_option_check")
 
 
+KEY_FAMILIES = {"one-sweep": 0, "int8": 1, "bf16": 2, "f32": 3}
+
+
+def key_eps(dim, quant_bits, metric, key, qnorm, qnorm2, family="one-sweep", planes=3, qscale=0.0, mq_qscale=0.0,
+            mq_planes=0):
+    """Host-only test hook (no device needed): the bound on |scan key - real-number key| that certification uses
+    (csrc/key_bound.h) for the arithmetic `family` -- "one-sweep", "int8", "bf16" or "f32" (the shared sweeps).  qnorm,
+    qnorm2: |g| and |g|^2 of the prepared query; qscale / mq_qscale: the integer paths' quantization steps; mq_planes: the
+    digit planes of the int8 shared sweep's query (0: this build's)."""
+    L = _lib.load()
+    eps = ctypes.c_double()
+    check(L.szg_debug_key_eps(int(dim), int(quant_bits), int(metric), int(planes), int(mq_planes), KEY_FAMILIES[family], float(key),
+                              float(qnorm), float(qnorm2), float(qscale), float(mq_qscale), ctypes.byref(eps)),
+          "szg_debug_key_eps")
+    return eps.value
+
+
 def reorder_plan(n_rows, src_rows, n_shards=1, live=None):
     """Host-only test hook (no device needed): the checks ScanIndex.reorder makes on its list -- SzgError with the same
     code and text -- and the new rows per shard.  live: bool[n_rows] (None: every row is live)."""
