@@ -219,7 +219,7 @@ int szg_index_mask_stats(szg_index *ix, szg_mask_stats *out);   /* szg_reset_sta
  *   the new allocation, a refused mask -- leaves rows, live bits, masks and the sketch exactly as they were.
  * Handles of several shards move rows between devices through the shards' staging buffers, at most 64 MiB at a time:
  *   two passes over the rows instead of one, at a cost that does not depend on how the list interleaves the shards.
- *   The internal sketch index of a float32 handle is dropped with the old rows (its memory is returned too) and built
+ *   The internal sketch index of a float32 (or float64) handle is dropped with the old rows (its memory is returned too) and built
  *   again by the next search that wants it.  Sharded-search communicators are unaffected.
  */
 
@@ -782,6 +782,20 @@ int szg_reset_stats(szg_index *ix);
  *                             default): masked launches keep the one-query kernel, one pass per query; the option is new
  *                             and off while it soaks, as sketch_radius was.  Radius searches, plain 8-bit handles and
  *                             lists of more than 64 entries stay as they are.  Other values are refused
+ *     sketch_f64          0   1 = a handle of 64-bit rows (float64, the reference's default quantization) keeps the 8-bit
+ *                             sketch too, under every rule a float32 handle's is under: sketch 0 / 1 / 2, sketch_min_rows,
+ *                             the 65 536-row and memory rules of automatic mode, the steps aside, k <= 34; sketch_radius
+ *                             and sketch_masked apply to it as they do there.  The sketch is an eighth of the rows'
+ *                             bytes (+12.5 % device memory); it is built from the doubles themselves (nothing is
+ *                             narrowed to float32: rows of any finite magnitude, subnormal ones included, get their
+ *                             nearest bytes), and a query it does not settle takes the handle's own 64-bit sweep.  Same
+ *                             answers, the reference's float64 distances bit for bit.  szg_stats.sketch_queries /
+ *                             sketch_fallbacks (and the sketch_radius_ pair) count on the handle as on a float32 one.
+ *                             0 = never (the default while the option soaks): a 64-bit handle keeps no sketch, allocates
+ *                             nothing more and takes the paths it took before the option existed; set back to 0, the
+ *                             handle behaves as a float32 handle does under sketch = 0 (an existing sketch index stays
+ *                             until the handle is closed or reloaded).  Handles of other widths ignore it.  Other values
+ *                             are refused
  *   shared sweeps
  *     multi_query         1   batches of >= mq_min queries share ONE sweep of the corpus, the dot products on the
  *                             matrix cores: 64- / 32- / 16-bit rows on bfloat16 roundings (v_mfma_f32_16x16x32_bf16,
@@ -957,7 +971,7 @@ int szg_debug_scan_group_ring(int dim, int quant_bits, int kp, int scan_group, i
 /*
  * Test hook, host only: would szg_set_option accept `value` for the one-sweep kernel's option `name` (scan_group,
  * scan_group_ring, scan_norms, sketch_planes, sketch_matrix, sketch_select, sketch_wide, sketch_share, sketch_bulk, sketch_radius,
- * sketch_masked)?  SZG_OK, or SZG_E_INVALID with szg_set_option's text; any other name is refused.
+ * sketch_masked, sketch_f64)?  SZG_OK, or SZG_E_INVALID with szg_set_option's text; any other name is refused.
  */
 int szg_debug_option_check(const char *name, int64_t value);
 
@@ -1029,11 +1043,11 @@ int szg_debug_refuse_device_alloc(int64_t nth);
  * [row_lo, row_hi) are the rows the record speaks for.  Safe beside finish_thread and coalesce (the trace has its own lock).
  */
 #define SZG_CERT_TOPK 0          /* first top-k pass: keys = ListKeys of the pass */
-#define SZG_CERT_SKETCH 1        /* sketch pre-pass (recorded on the float32 handle) */
+#define SZG_CERT_SKETCH 1        /* sketch pre-pass (recorded on the float32 -- sketch_f64: float64 -- handle) */
 #define SZG_CERT_ESCALATION 2    /* the collect sweep of a query whose first pass was not certified */
 #define SZG_CERT_RADIUS_SINGLE 3 /* radius collect, one sweep per query */
 #define SZG_CERT_RADIUS_SHARED 4 /* radius collect, one shared sweep per batch */
-#define SZG_CERT_SKETCH_RADIUS 5 /* radius collect on the sketch (recorded on the float32 handle, one record per query):
+#define SZG_CERT_SKETCH_RADIUS 5 /* radius collect on the sketch (recorded on the float32 / float64 handle, one record per query):
                                     thr / eps of the sketch sweep, D = the sketch-distance radius R (1 + 1e-9) + slack,
                                     keyed entries = the collected sketch rows with their sketch keys, NO_KEY entries =
                                     the rows without a usable sketch re-ranked beside them */
@@ -1073,11 +1087,13 @@ int szg_debug_certificates(szg_index *ix, szg_cert_record *records, uint64_t rec
                            uint64_t entry_capacity, uint64_t *out_records, uint64_t *out_entries, uint64_t *out_dropped);
 
 /*
- * Test hook: the state of the 8-bit sketch index of a float32 handle (option "sketch"), read only.  A
+ * Test hook: the state of the 8-bit sketch index of a float32 handle -- or of a float64 one, which keeps a sketch under
+ * sketch_f64 = 1 -- (option "sketch"), read only.  A
  * settled answer rests on the sketch bytes, on max_ang >= d(row, its sketch) and on the exception list; with these two
  * calls a test checks each against float64.  Neither call brings the sketch up to date or builds one: a test searches
  * first and looks at in_sync.  Both take the lock of the sync, allocate nothing on the device beyond what
- * szg_index_read_rows does, and return SZG_E_INVALID on a NULL argument or a handle whose rows are not float32.
+ * szg_index_read_rows does, and return SZG_E_INVALID on a NULL argument or a handle whose rows are neither float32 nor
+ * float64.
  *
  *   szg_debug_sketch_info(ix, out, exc_rows, exc_capacity)   *out is always written.  In the two-call style: with
  *                                          exc_rows == NULL only *out is written; with exc_capacity >= out->n_exc the

@@ -352,7 +352,8 @@ def sketch_slack(max_ang, gscale, dim):
 
 
 def sketch_reference(vec, metric, gscale):
-    """What sketch_build_kernel is specified to do with float32 rows vec[n, dim] (their values, float64) ->
+    """What sketch_build_kernel -- and sketch_build_f64_kernel, for float64 rows under option sketch_f64 -- is specified to
+    do with rows vec[n, dim] (the rows' values as float64: decode_rows(..., 32) or decode_rows(..., 64)) ->
     (t[n, dim] in LD, must_exc[n]): the ideal scaled value t = (x / scale + 1) * 127.5, whose nearest integer clipped to
     0..255 is the row's sketch byte -- scale is the row's largest |x_i| under cosine and gscale under Euclid -- and
     whether the row has no usable sketch: a non-finite element, no direction (all zero, cosine), an element beyond
@@ -375,7 +376,9 @@ def sketch_reference(vec, metric, gscale):
 
 def check_sketch_build(vec, sk_bytes, info, exc_rows, rebuilt, metric=None, rec_slack=None, what=()):
     """Assert B for the sketch state (info: ScanIndex.sketch_info(); sk_bytes: uint8[n, dim], ScanIndex.sketch_rows())
-    of float32 rows with values vec[n, dim]; rebuilt: the last sync built every row anew.
+    of float32 or float64 rows with values vec[n, dim]; rebuilt: the last sync built every row anew.  The reference is
+    computed in LD, whose exponent range (x87: 15 bits) holds the squares of any double: rows at 1e-150 or 1e200 are
+    checked like any other.
 
         B1  every byte of a sketched row is within 0.5 + 1e-9 of clip(t, 0, 255) (the device may fuse the multiply-add:
             a tie may fall either way); every byte of a row that must be an exception is 128

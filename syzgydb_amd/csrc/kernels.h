@@ -370,12 +370,13 @@ hipError_t launch_rerank_pairs(int qbits, int metric, const uint8_t *rows, RowLa
 // 8-bit sketch of float32 rows for the cosine pre-pass (kernels_exact.hip): rows [first_row, first_row + n_rows) of
 // `src` (or the listed rows), written into `dst` in its resident layout; *max_ang = max over the rows of the angular
 // distance row <-> sketch (bits of a double); rows without a direction or with a non-finite element are reported
-hipError_t launch_sketch_build(const uint8_t *src, RowLayout src_lay, int dim, uint8_t *dst, RowLayout dst_lay,
+hipError_t launch_sketch_build(const uint8_t *src, RowLayout src_lay, int src_bits, int dim, uint8_t *dst, RowLayout dst_lay,
                                uint64_t first_row, uint64_t n_rows, const uint32_t *row_list,
                                unsigned long long *max_ang, uint32_t *exc_rows, uint32_t *exc_count, uint32_t exc_cap,
                                double gscale, int max_only, hipStream_t stream);
 // (gscale > 0: Euclidean form -- one scale for the whole collection, *max_ang = largest Euclidean distance row <->
-//  sketch; max_only: report the largest finite |x_i| of the rows as float bits instead of building anything)
+//  sketch; max_only: report the largest finite |x_i| of the rows instead of building anything -- the bits of a float
+//  for src_bits = 32, of a double for src_bits = 64 (float64 rows, option sketch_f64); any other width is refused)
 hipError_t launch_repack(int qbits, uint8_t *ref, uint32_t row_bytes, uint8_t *rows, RowLayout layout,
                          uint64_t first_row, uint64_t n_rows, int to_reference, hipStream_t stream);
 

@@ -622,6 +622,119 @@ __global__ __launch_bounds__(256) void sketch_build_kernel(const uint8_t *src, R
     }
 }
 
+// ---- 8-bit sketch of float64 rows (option sketch_f64) ------------------------------------
+// The same contract as sketch_build_kernel -- one wave per row, the same bytes, exception list, running maximum, gscale,
+// max_only (the bits of a DOUBLE) and row_list -- for rows of doubles: 16 sketch elements are eight 16-byte pieces of the
+// row, the last of which may hold one element and padding.  Nothing is narrowed to float: a row of 1e-60 has a direction
+// and a row of 1e60 is finite.  What float32 rows never reach in float64 arithmetic and double rows do:
+//   1 / scale overflows for a subnormal scale, x * x underflows near 1e-160 and overflows near 1e154, and so does the
+//   square of a Euclidean difference.
+// So every element is first multiplied by 2^-e, e the binary exponent of the scale (the row's largest |x_i|, or gscale):
+// the scale becomes m in [0.5, 1), the elements y = x 2^-e lie in [-1, 1], and the sums run over y.  The angle does not
+// see the factor; the Euclidean distance is multiplied by 2^e after the square root.  A power of two commutes with every
+// rounding below (barring underflow of elements 2^-1000 below the scale, whose share of any sum is below its last bit),
+// so on values a float32 row can hold the bytes and the maximum are bit for bit sketch_build_kernel's.  A distance that
+// is not finite even so (a Euclidean one beyond DBL_MAX) makes the row an exception: no NaN or Inf reaches atomicMax.
+__global__ __launch_bounds__(256) void sketch_build_f64_kernel(const uint8_t *src, RowLayout src_lay, int dim, uint8_t *dst,
+                                                               RowLayout dst_lay, uint64_t first_row, uint64_t n_rows,
+                                                               const uint32_t *row_list, unsigned long long *max_ang,
+                                                               uint32_t *exc_rows, uint32_t *exc_count, uint32_t exc_cap,
+                                                               double gscale, int max_only)
+{
+    const int lane = threadIdx.x & 63;
+    const uint64_t i = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (i >= n_rows) return;
+    const uint64_t row = row_list ? (uint64_t)row_list[i] : first_row + i;
+    const int pieces = (dim + 15) / 16;  // 16-element pieces of the sketch row: eight 16-byte pieces of the source row
+    double mx = 0.0;
+    bool bad = false;
+    for (int p = lane; p < pieces; p += 64) {
+#pragma unroll
+        for (int t = 0; t < 8; t++) {
+            const int e0 = p * 16 + t * 2;
+            if (e0 >= dim) break;
+            const double2 v = *reinterpret_cast<const double2 *>(src + piece_offset(src_lay, row, (uint32_t)(p * 8 + t)));
+            const double x[2] = {v.x, v.y};
+#pragma unroll
+            for (int k = 0; k < 2; k++) {
+                if (e0 + k >= dim) continue;
+                const double ax = fabs(x[k]);
+                if (!(ax <= 1.7976931348623157e308)) bad = true;  // Inf or NaN (the largest finite double is a value like any other)
+                mx = fmax(mx, ax);
+            }
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) mx = fmax(mx, __shfl_xor(mx, o));
+    bad = __ballot(bad) != 0;
+    if (max_only) {
+        if (lane == 0 && !bad) atomicMax(max_ang, (unsigned long long)__double_as_longlong(mx));  // (finite, non-negative)
+        return;
+    }
+    if (gscale > 0.0) {
+        if (mx > gscale) bad = true;  // (an overwritten row beyond the scale: sketch_build_kernel)
+    } else {
+        bad = bad || !(mx > 0.0);
+    }
+    int e = 0;
+    const double m = bad ? 1.0 : frexp(gscale > 0.0 ? gscale : mx, &e);  // scale = m 2^e, m in [0.5, 1): subnormals too
+    const double inv = bad ? 0.0 : 1.0 / m;
+    double dot = 0.0, nx = 0.0, nn = 0.0;
+    for (int p = lane; p < pieces; p += 64) {
+        uint32_t w[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+        for (int t = 0; t < 8; t++) {
+            const int e0 = p * 16 + t * 2;
+            if (e0 >= dim) break;
+            const double2 v = *reinterpret_cast<const double2 *>(src + piece_offset(src_lay, row, (uint32_t)(p * 8 + t)));
+            const double x[2] = {v.x, v.y};
+#pragma unroll
+            for (int k = 0; k < 2; k++) {
+                if (e0 + k >= dim) continue;  // padding bytes stay 0, as the page-in leaves them
+                int q = 128;
+                if (!bad) {
+                    const double xd = ldexp(x[k], -e);
+                    q = (int)rint((xd * inv + 1.0) * 127.5);
+                    q = q < 0 ? 0 : (q > 255 ? 255 : q);
+                    const double n = (double)(2 * q - 255);
+                    if (gscale > 0.0) {
+                        const double df = xd - m * n / 255.0;
+                        dot += df * df;
+                    } else {
+                        dot += xd * n;
+                        nx += xd * xd;
+                        nn += n * n;
+                    }
+                }
+                w[t >> 1] |= (uint32_t)q << (8 * ((t & 1) * 2 + k));
+            }
+        }
+        *reinterpret_cast<uint4 *>(dst + piece_offset(dst_lay, row, (uint32_t)p)) = make_uint4(w[0], w[1], w[2], w[3]);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        dot += __shfl_xor(dot, o);
+        nx += __shfl_xor(nx, o);
+        nn += __shfl_xor(nn, o);
+    }
+    if (lane == 0) {
+        double d = 0.0;
+        if (!bad && gscale > 0.0) {
+            d = ldexp(sqrt(dot), e);
+        } else if (!bad) {
+            double c = dot / sqrt(nx * nn);
+            c = c > 1.0 ? 1.0 : (c < -1.0 ? -1.0 : c);
+            d = acos(c) / 3.14159265358979323846264338327950288;
+        }
+        if (bad || !(d >= 0.0 && d <= 1.7976931348623157e308)) {
+            const uint32_t at = atomicAdd(exc_count, 1u);
+            if (at < exc_cap) exc_rows[at] = (uint32_t)row;
+        } else {
+            atomicMax(max_ang, (unsigned long long)__double_as_longlong(d));  // non-negative finite doubles order as integers
+        }
+    }
+}
+
 __global__ void fill_bits_kernel(uint64_t *bits, uint64_t n_rows, uint64_t n_words)
 {
     const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -708,16 +821,21 @@ hipError_t launch_rerank_pairs(int qbits, int metric, const uint8_t *rows, RowLa
     }
 }
 
-hipError_t launch_sketch_build(const uint8_t *src, RowLayout src_lay, int dim, uint8_t *dst, RowLayout dst_lay,
+hipError_t launch_sketch_build(const uint8_t *src, RowLayout src_lay, int src_bits, int dim, uint8_t *dst, RowLayout dst_lay,
                                uint64_t first_row, uint64_t n_rows, const uint32_t *row_list,
                                unsigned long long *max_ang, uint32_t *exc_rows, uint32_t *exc_count, uint32_t exc_cap,
                                double gscale, int max_only, hipStream_t stream)
 {
+    if (src_bits != 32 && src_bits != 64) return hipErrorInvalidValue;
     if (n_rows == 0) return hipSuccess;
     const uint64_t grid = (n_rows + 3) / 4;
     if (grid > 0x7FFFFFFFull) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(sketch_build_kernel, dim3((unsigned)grid), dim3(256), 0, stream, src, src_lay, dim, dst, dst_lay,
-                       first_row, n_rows, row_list, max_ang, exc_rows, exc_count, exc_cap, gscale, max_only);
+    if (src_bits == 64)
+        hipLaunchKernelGGL(sketch_build_f64_kernel, dim3((unsigned)grid), dim3(256), 0, stream, src, src_lay, dim, dst, dst_lay,
+                           first_row, n_rows, row_list, max_ang, exc_rows, exc_count, exc_cap, gscale, max_only);
+    else
+        hipLaunchKernelGGL(sketch_build_kernel, dim3((unsigned)grid), dim3(256), 0, stream, src, src_lay, dim, dst, dst_lay,
+                           first_row, n_rows, row_list, max_ang, exc_rows, exc_count, exc_cap, gscale, max_only);
     return hipGetLastError();
 }
 

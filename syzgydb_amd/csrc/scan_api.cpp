@@ -546,7 +546,7 @@ int szg_debug_sketch_info(szg_index *ix, szg_sketch_info *out, uint64_t *out_exc
 {
     SZG_TRY
     if (!ix || !out) return fail(SZG_E_INVALID, "null argument");
-    if (ix->bits != 32) return fail(SZG_E_INVALID, "sketch info: only float32 handles keep a sketch");
+    if (ix->bits != 32 && ix->bits != 64) return fail(SZG_E_INVALID, "sketch info: only float32 and float64 handles keep a sketch");
     return sketch_debug_info(ix, out, out_exc_rows, exc_capacity);
     SZG_CATCH
 }
@@ -556,7 +556,7 @@ int szg_debug_sketch_rows(szg_index *ix, uint64_t first_row, uint64_t n_rows, ui
 {
     SZG_TRY
     if (!ix || (!out && n_rows)) return fail(SZG_E_INVALID, "null argument");
-    if (ix->bits != 32) return fail(SZG_E_INVALID, "sketch rows: only float32 handles keep a sketch");
+    if (ix->bits != 32 && ix->bits != 64) return fail(SZG_E_INVALID, "sketch rows: only float32 and float64 handles keep a sketch");
     return sketch_debug_rows(ix, first_row, n_rows, out, out_live_words, live_capacity);
     SZG_CATCH
 }

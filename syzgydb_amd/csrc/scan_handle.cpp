@@ -676,6 +676,7 @@ static const char *scan_option_refusal(const std::string &n, int64_t value, bool
     if (n == "sketch_bulk") return szg::sketch_bulk_known(value) ? nullptr : "sketch_bulk is 0 to 1024";
     if (n == "sketch_radius") return value == 0 || value == 1 ? nullptr : "sketch_radius is 0 or 1";
     if (n == "sketch_masked") return szg::sketch_masked_known(value) ? nullptr : "sketch_masked is 0 or 1";
+    if (n == "sketch_f64") return value == 0 || value == 1 ? nullptr : "sketch_f64 is 0 or 1";
     *known = false;
     return nullptr;
 }
@@ -756,6 +757,9 @@ int szg_set_option(szg_index *ix, const char *name, int64_t value)
         ix->sketch_radius = (int)value;
     } else if (n == "sketch_masked") {
         ix->sketch_masked = (int)value;
+    } else if (n == "sketch_f64") {
+        // (read on the handle whose rows are float64, sketch_applies_rows; the sketch index, 8-bit, carries it unread)
+        ix->sketch_f64 = (int)value;
     } else if (n == "query_batch") {
         if (value < 1 || value > kMaxBatch) return fail(SZG_E_INVALID, "query_batch out of range");
         ix->query_batch = (int)value;

@@ -390,7 +390,8 @@ struct szg_index {
     double norm_bias = 0;     // integer paths: sum n^2 = 4(SQ+SV) + norm_bias (padding removed)
     uint64_t row_base = 0;
     std::vector<szgi::Shard *> shards;
-    // 8-bit sketch pre-pass for float32 collections ("sketch" option, sketch_sync / search_topk_sketch)
+    // 8-bit sketch pre-pass for float32 collections -- float64 ones under sketch_f64 = 1 -- ("sketch" option, sketch_sync /
+    // search_topk_sketch)
     szg_index *sketch = nullptr;         // an internal 8-bit index over the same rows, same shard ranges
     int sketch_on = 2;                   // 0 off, 1 forced on, 2 auto (sketch_applies)
     int sketch_extra = 30;               // sketch neighbours asked for beyond k: k = 10 -> 40, which keeps the sketch
@@ -451,7 +452,10 @@ struct szg_index {
     int sketch_masked = 0;    // top-k launches of the sketch pre-pass with tombstones or filter masks take the matrix sweep's
                               // masked forms wherever the same launch without masks would take the matrix sweep: 0 = never
                               // (the default while the option soaks: masked launches keep the one-query kernel), 1 = always
-    bool is_sketch = false;   // this index is the internal sketch of a float32 handle: its keys only bound
+    int sketch_f64 = 0;       // float64 handles (the reference's default quantization) keep an 8-bit sketch too, an eighth of
+                              // their rows' bytes, under every rule of float32 handles: 0 = never (the default while the
+                              // option soaks: such a handle keeps no sketch and allocates nothing more), 1 = always
+    bool is_sketch = false;   // this index is the internal sketch of a float32 (or float64) handle: its keys only bound
     int tie_mode = 0;         // 0: exact full replay on ties/NaN, 1: keep the fast answer
     int serialize_scans = 1;  // scan launches of a shard never overlap each other
     int multi_query = 1;      // share one sweep between the queries of a batch (MFMA path)
@@ -751,7 +755,8 @@ int enqueue_collect_mq(szg_index *ix, Shard *sh, Ctx *c, int nq, int nb, bool ha
 
 // ---- scan_sketch.cpp
 bool sketch_applies(const szg_index *ix, int k);
-// ... without the clause on k: float32 rows, the row count rule, the steps aside (radius searches: sketch_radius)
+// ... without the clause on k: float32 rows (float64 under sketch_f64 = 1), the row count rule, the steps aside (radius
+// searches: sketch_radius)
 bool sketch_applies_rows(const szg_index *ix);
 // the sketch index brought up to date under sk_mu, as a search needs it.  Auto mode never turns a working handle into
 // an error: a failed sync gives back what was built and sets sk_nomem (the caller looks at sk_disabled / sk_nomem)

@@ -1,9 +1,10 @@
-// scan_sketch.cpp -- 8-bit sketch pre-pass for float32 collections (option "sketch", automatic by default).
+// scan_sketch.cpp -- 8-bit sketch pre-pass for float32 collections (option "sketch", automatic by default) and, under
+// option sketch_f64, for float64 ones.
 #include "scan_internal.h"
 
 namespace szgi {
 
-// ---- 8-bit sketch pre-pass (float32 rows) ------------------------------------------------------------------------
+// ---- 8-bit sketch pre-pass (float32 rows; float64 rows under sketch_f64 = 1) ---------------------------------------
 //
 // The reference's "cosine" distance IS the angle (acos(cos)/pi, collection.go:821-832), a metric on directions:
 // |d(q, x) - d(q, s)| <= d(x, s) for any sketch s of the row x (Euclidean distance likewise).  The library keeps an
@@ -16,6 +17,11 @@ namespace szgi {
 // lists (from the kp-th merged key and its error bound), d(q, x) >= D_lb - A for every row that was not re-ranked:
 // the answer is final when its k-th distance is below that.  Otherwise -- and for equal distances or a NaN among the
 // first k rows, where the reference's answer depends on its heap history -- the query takes the float32 path.
+//
+// Option sketch_f64 = 1 gives a float64 handle (the reference's default quantization) the same second index: an eighth
+// of its rows' bytes.  Nothing above depends on the width: the build kernel reads doubles (sketch_build_f64_kernel), the
+// rerank is launch_rerank on the handle's own 64-bit rows, and "the float32 path" below is, for such a handle, its own
+// full-precision path.
 
 constexpr uint64_t kAutoMinRows = 65536;  // auto mode: smaller collections keep no second index
 constexpr int kAutoWindow = 64;           // auto mode steps aside once kAutoFallbacks of the last kAutoWindow
@@ -32,7 +38,8 @@ bool sketch_applies(const szg_index *ix, int k)
 
 bool sketch_applies_rows(const szg_index *ix)
 {
-    if (!ix->sketch_on || ix->sk_disabled || ix->bits != 32) return false;
+    if (!ix->sketch_on || ix->sk_disabled) return false;
+    if (ix->bits != 32 && !(ix->bits == 64 && ix->sketch_f64 == 1)) return false;
     uint64_t n = 0;
     for (const Shard *sh : ix->shards) n += sh->n_rows;
     uint64_t min_rows = (uint64_t)ix->sketch_min_rows;
@@ -103,7 +110,8 @@ int sketch_sync(szg_index *ix)
     }
     if (ix->sk_dirty_rows.size() > 4096) full = true;
     const bool euclid = ix->metric != SZG_COSINE;
-    // Euclidean collections share ONE scale (the largest |x_i|): rows beyond it force a rebuild
+    // Euclidean collections share ONE scale (the largest |x_i|): rows beyond it force a rebuild.  The scale pass reports
+    // the bits of a float for float32 rows and of a double for float64 rows.
     auto max_abs = [&](bool only_new, double *out) -> int {
         double g = 0.0;
         for (size_t s = 0; s < n_sh; s++) {
@@ -116,14 +124,20 @@ int sketch_sync(szg_index *ix)
             if (int rc = d_max.ensure(2)) return rc;
             hipError_t e = hipMemset(d_max, 0, 16);
             if (e == hipSuccess)
-                e = szg::launch_sketch_build(a->rows, ix->layout, ix->dim, nullptr, sk->layout, have, a->n_rows - have,
-                                             nullptr, d_max, nullptr, nullptr, 0, 0.0, 1, nullptr);
+                e = szg::launch_sketch_build(a->rows, ix->layout, ix->bits, ix->dim, nullptr, sk->layout, have,
+                                             a->n_rows - have, nullptr, d_max, nullptr, nullptr, 0, 0.0, 1, nullptr);
             if (e == hipSuccess) e = hipMemcpy(&bits, d_max, sizeof(bits), hipMemcpyDeviceToHost);
             if (e != hipSuccess) return fail(SZG_E_DEVICE, "sketch scale pass", e);
-            const uint32_t fb = (uint32_t)bits;
-            float f;
-            memcpy(&f, &fb, 4);
-            g = std::max(g, (double)f);
+            double v;
+            if (ix->bits == 64) {
+                memcpy(&v, &bits, 8);
+            } else {
+                const uint32_t fb = (uint32_t)bits;
+                float f;
+                memcpy(&f, &fb, 4);
+                v = (double)f;
+            }
+            g = std::max(g, v);
         }
         *out = g;
         return SZG_OK;
@@ -178,13 +192,13 @@ int sketch_sync(szg_index *ix)
         HIPCHK(hipMemset(d_exc, 0, (exc_cap + 1) * sizeof(uint32_t)));
         hipError_t e = hipSuccess;
         if (a->n_rows > have)
-            e = szg::launch_sketch_build(a->rows, ix->layout, ix->dim, b->rows, sk->layout, have, a->n_rows - have, nullptr,
-                                         d_ang, d_exc + 1, d_exc, exc_cap, ix->sk_gscale, 0, nullptr);
+            e = szg::launch_sketch_build(a->rows, ix->layout, ix->bits, ix->dim, b->rows, sk->layout, have, a->n_rows - have,
+                                         nullptr, d_ang, d_exc + 1, d_exc, exc_cap, ix->sk_gscale, 0, nullptr);
         if (e == hipSuccess && !list.empty()) {
             e = hipMemcpy(d_list, list.data(), list.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
             if (e == hipSuccess)
-                e = szg::launch_sketch_build(a->rows, ix->layout, ix->dim, b->rows, sk->layout, 0, list.size(), d_list,
-                                             d_ang, d_exc + 1, d_exc, exc_cap, ix->sk_gscale, 0, nullptr);
+                e = szg::launch_sketch_build(a->rows, ix->layout, ix->bits, ix->dim, b->rows, sk->layout, 0, list.size(),
+                                             d_list, d_ang, d_exc + 1, d_exc, exc_cap, ix->sk_gscale, 0, nullptr);
         }
         unsigned long long ang_bits = 0;
         std::vector<uint32_t> exc(exc_cap + 1, 0);
@@ -195,7 +209,8 @@ int sketch_sync(szg_index *ix)
         memcpy(&ang, &ang_bits, sizeof(ang));
         ix->sk_max_ang = std::max(ix->sk_max_ang, ang);
         if (exc[0] > exc_cap || ix->sk_exc.size() + exc[0] > exc_cap) {
-            // a collection of zero / non-finite rows: nothing to gain -- give the second index (+25 % memory) back;
+            // a collection of zero / non-finite rows: nothing to gain -- give the second index (+25 % memory; +12.5 % of
+            // float64 rows) back;
             // the next load / synth gets a fresh try
             ix->sk_disabled = true;
             szg_index_destroy(ix->sketch);
@@ -350,7 +365,7 @@ std::vector<int> sketch_batch_sizes(int n_queries, int wide, int share, int quer
 // the batch's queries on the host -- a short call's first queries while its last sweeps still run -- and collects
 // the ones the certificate does not settle for the full sweep.
 struct SketchCall {
-    szg_index *ix;  // the float32 handle (rows, masks, results)
+    szg_index *ix;  // the float32 (sketch_f64: float64) handle (rows, masks, results)
     szg_index *sk;  // its sketch index (contexts, sweeps)
     const double *queries;
     int n_queries, k;
@@ -370,7 +385,7 @@ struct SketchCall {
     std::vector<Cand> cands;
     std::vector<HeapItem> res;
     std::vector<double> dd;
-    bool tracing = false;  // the float32 handle's certificate trace is on
+    bool tracing = false;  // the handle's certificate trace is on
 
     int run();
     Batch plan(int q0);
@@ -528,7 +543,9 @@ void SketchCall::settle(Batch &b, int j)
             const double x = -lb + 1e-15;  // (an upper bound of the cosine, rounding included)
             D = x >= 1.0 ? 0.0 : (x <= -1.0 ? 1.0 : std::acos(x) / M_PI * (1.0 - 1e-12));
         }
-        ok = (int)res.size() == k && res.back().priority * (1.0 + 1e-9) < D - p.slack;
+        // (float64 rows: at a scale near the largest double gs * sqrt(lb) overflows.  An infinite D bounds nothing --
+        // the product it stands for is finite and may be below slack -- so it settles nothing)
+        ok = (int)res.size() == k && std::isfinite(D) && res.back().priority * (1.0 + 1e-9) < D - p.slack;
         D_used = D;
     }
     if (ok && ix->tie_mode == 0) {

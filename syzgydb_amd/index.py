@@ -1018,7 +1018,7 @@ def merge_short_plan(n_lists, m, kp):
 def option_check(name, value):
     """Host-only test hook (no device needed): raises SzgError where ScanIndex.set_option would refuse `value` for the
     one-sweep kernel's option `name` (scan_group, scan_group_ring, scan_norms, sketch_planes, sketch_matrix, sketch_select,
-    sketch_wide, sketch_share, sketch_bulk, sketch_radius, sketch_masked)."""
+    sketch_wide, sketch_share, sketch_bulk, sketch_radius, sketch_masked, sketch_f64)."""
     L = _lib.load()
     check(L.szg_debug_option_check(name.encode(), int(value)), "szg_debug_option_check")
 
