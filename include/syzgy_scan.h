@@ -463,6 +463,53 @@ int szg_index_tombstone_mask(szg_index *ix, const szg_mask *mask, uint64_t *out_
 int szg_column_set_rows(szg_column *c, const uint64_t *rows, const void *values, const uint64_t *present_bits,
                         uint64_t n_rows);
 
+/* ---- ingest from device memory (added under ABI 4, additive) ----
+ *
+ * szg_index_append_f64 and szg_index_overwrite_rows_f64 for vectors that already lie in device memory -- the output of
+ * an embedding model, a torch tensor -- in float64, float32, float16 or bfloat16.  Every element widens to float64
+ * exactly (float32 subnormals included), so the handle ends exactly where the _f64 form would leave it given the same
+ * values widened on the host: resident bytes, live bits, row counts, row norms (refreshed at once where the handle keeps
+ * them) and sketch bookkeeping.  An append makes masks stale, an overwrite makes nothing stale, a tombstoned row stays
+ * dead, columns stay short until szg_column_append.
+ * Source: element (r, e) of the source is data[r * row_stride + e], e < the handle's dimension; row_stride counts
+ *   elements and is at least the dimension (larger: a column slice of a wider matrix).  data is aligned to its element
+ *   size, no more.  src_rows is a HOST array or NULL: NULL = entry i comes from source row i, and n_rows <=
+ *   src->n_rows is required; otherwise entry i comes from source row src_rows[i], in any order, duplicates allowed.
+ *   The list travels to the card at 8 bytes per row, in chunks of 64 MiB.
+ * Refusals, all decided on the host before anything on the card changes (no kernel is launched on a pointer that
+ *   failed a check), SZG_E_INVALID unless stated: a NULL argument (src_rows excepted); an unknown dtype; row_stride <
+ *   the dimension; data not aligned to its element size; n_rows > src->n_rows without a list; an entry of src_rows at
+ *   or past src->n_rows (SZG_E_RANGE); a device ordinal out of range; data that hipPointerGetAttributes does not
+ *   report as device memory of `device` ("not device memory": a pointer the runtime does not know counts as host
+ *   memory); source rows that do not all lie inside the allocation hipMemGetAddressRange reports -- the last element
+ *   addressed is the largest source row used x row_stride + the dimension -- (SZG_E_RANGE); and, for the overwrite
+ *   form, szg_index_overwrite_rows's rules: a row at or past the handle's rows is SZG_E_RANGE, a row listed twice
+ *   SZG_E_INVALID.  n_rows == 0 checks the descriptor only.
+ * Another device: a source on a device other than the target shard's (the append's target, every shard the overwrite's
+ *   list reaches) is refused, SZG_E_INVALID, "source on another device" -- no peer copy is made.  Shards that share
+ *   the source's device (devices = {0, 0}) are served.
+ * Synchronisation: the call synchronises the source's device before it reads (work queued on ANY stream, the
+ *   caller's framework's included, has finished) and returns with the rows resident: the caller may free or rewrite
+ *   the source as soon as the call has returned.
+ * Memory: the encoder reads the caller's memory in place; nothing is copied and the staging block does not grow for
+ *   the source.  The overwrite form still stages its linear block of encoded rows (at most 64 MiB) and its lists.
+ * There is no _dev form of szg_index_load (an append to an empty handle covers it) and none of the queries.
+ */
+#define SZG_SRC_F64 0
+#define SZG_SRC_F32 1
+#define SZG_SRC_F16 2
+#define SZG_SRC_BF16 3
+typedef struct szg_dev_vectors {
+    const void *data;      /* device memory, aligned to its element size */
+    int dtype;             /* SZG_SRC_* */
+    int device;            /* HIP ordinal the memory lives on */
+    uint64_t n_rows;       /* source rows available */
+    uint64_t row_stride;   /* elements from one source row to the next, >= dim */
+} szg_dev_vectors;
+int szg_index_append_dev(szg_index *ix, const szg_dev_vectors *src, const uint64_t *src_rows, uint64_t n_rows);
+int szg_index_overwrite_rows_dev(szg_index *ix, const uint64_t *rows, const szg_dev_vectors *src,
+                                 const uint64_t *src_rows, uint64_t n_rows);
+
 /*
  * The reference's float64 distance (c.distance, collection.go:596, :812-832) from
  * one query to each listed row, bit-identical to the reference: the gather-by-row

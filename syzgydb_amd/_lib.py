@@ -52,6 +52,8 @@ EXPORTS = [
     # bulk mutations: many rows per call (added under ABI 4)
     "szg_index_overwrite_rows", "szg_index_overwrite_rows_f64", "szg_index_tombstone_rows", "szg_index_tombstone_mask",
     "szg_column_set_rows", "szg_debug_bulk_plan",
+    # ingest from device memory (added under ABI 4)
+    "szg_index_append_dev", "szg_index_overwrite_rows_dev",
     # host-only test hook
     "szg_debug_scan_plan", "szg_debug_scan_group", "szg_debug_reorder_plan", "szg_debug_option_check",
     "szg_debug_scan_group_ring", "szg_debug_merge_short_plan", "szg_debug_scan_matrix",
@@ -77,6 +79,7 @@ SZG_MASK_AND, SZG_MASK_OR, SZG_MASK_ANDNOT, SZG_MASK_NOT = 0, 1, 2, 3
 SZG_COL_F64, SZG_COL_U32, SZG_COL_STR = 0, 1, 2
 SZG_CMP_EQ, SZG_CMP_NE, SZG_CMP_LT, SZG_CMP_LE, SZG_CMP_GT, SZG_CMP_GE = range(6)
 SZG_STR_STARTS_WITH, SZG_STR_ENDS_WITH, SZG_STR_CONTAINS = 6, 7, 8   # szg_mask_where_str only
+SZG_SRC_F64, SZG_SRC_F32, SZG_SRC_F16, SZG_SRC_BF16 = range(4)   # szg_dev_vectors.dtype
 SZG_STR_PATTERN_MAX = 256
 SZG_DFA_STATES_MAX = 32768     # szg_mask_where_dfa: states of an automaton
 SZG_DFA_TABLE_MAX = 1 << 20    # ... and n_states * n_classes entries of its table
@@ -167,6 +170,11 @@ class SzgDfa(ctypes.Structure):
     _fields_ = [("n_states", ctypes.c_uint32), ("n_classes", ctypes.c_uint32), ("start", ctypes.c_uint32),
                 ("class_of", ctypes.POINTER(ctypes.c_uint8)), ("next", ctypes.POINTER(ctypes.c_uint16)),
                 ("accept_bits", ctypes.POINTER(ctypes.c_uint64))]
+
+
+class SzgDevVectors(ctypes.Structure):
+    _fields_ = [("data", ctypes.c_void_p), ("dtype", ctypes.c_int), ("device", ctypes.c_int), ("n_rows", ctypes.c_uint64),
+                ("row_stride", ctypes.c_uint64)]
 
 
 class SzgMaskStats(ctypes.Structure):
@@ -350,6 +358,11 @@ def load():
         L.szg_debug_bulk_plan.restype = ctypes.c_int
         L.szg_debug_bulk_plan.argtypes = [ctypes.c_uint64, ctypes.c_uint64, u64p, ctypes.c_uint64, ctypes.c_int, ctypes.c_int,
                                           u64p, u64p, u64p, u64p, u64p]
+    if hasattr(L, "szg_index_append_dev"):   # (an older build for an A/B run takes vectors from the host only)
+        L.szg_index_append_dev.restype = ctypes.c_int
+        L.szg_index_append_dev.argtypes = [vp, ctypes.POINTER(SzgDevVectors), u64p, ctypes.c_uint64]
+        L.szg_index_overwrite_rows_dev.restype = ctypes.c_int
+        L.szg_index_overwrite_rows_dev.argtypes = [vp, u64p, ctypes.POINTER(SzgDevVectors), u64p, ctypes.c_uint64]
     L.szg_comm_unique_id.restype = ctypes.c_int
     L.szg_comm_unique_id.argtypes = [u8p]
     L.szg_comm_create.restype = ctypes.c_int

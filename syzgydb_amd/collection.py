@@ -213,9 +213,19 @@ class Collection:
     def AddDocuments(self, ids, vectors, metadatas=None):
         """Bulk upsert (not in the reference; the same state as AddDocument in a loop over the entries): new ids are
         appended by ONE append_vectors in first-seen order, existing ids rewritten by ONE overwrite_vectors -- both
-        quantize and pack on the device.  An id listed twice keeps its last entry."""
-        V = np.atleast_2d(np.asarray(vectors, dtype=np.float64))
-        if V.shape[1] != self.DimensionCount:
+        quantize and pack on the device.  An id listed twice keeps its last entry.
+        vectors may also lie in device memory -- a torch tensor on the card, or any object with
+        __cuda_array_interface__ (ScanIndex.append_tensor) -- and then never visit the host: the two lists of entries
+        become the src_rows of one overwrite_tensor and one append_tensor."""
+        on_device = bool(getattr(vectors, "is_cuda", False)) or (hasattr(vectors, "__cuda_array_interface__") and
+                                                                 not hasattr(vectors, "data_ptr"))
+        if on_device:
+            V = None
+            width = tuple(vectors.shape)[1] if len(tuple(vectors.shape)) == 2 else -1
+        else:
+            V = np.atleast_2d(np.asarray(vectors, dtype=np.float64))
+            width = V.shape[1]
+        if width != self.DimensionCount:
             raise ValueError("vector size does not match the expected number of dimensions")
         ids = [int(i) for i in ids]
         self._version += 1
@@ -231,14 +241,20 @@ class Collection:
         known = [i for i in last if i in self._row_of]
         if known:  # WriteRecord of an existing id replaces the record
             rows = [self._row_of[i] for i in known]
-            self._index.overwrite_vectors(rows, V[[last[i] for i in known]])  # szg_index_overwrite_rows_f64
+            if on_device:
+                self._index.overwrite_tensor(rows, vectors, src_rows=[last[i] for i in known])  # szg_index_overwrite_rows_dev
+            else:
+                self._index.overwrite_vectors(rows, V[[last[i] for i in known]])  # szg_index_overwrite_rows_f64
             for i, row in zip(known, rows):
                 self._meta[row] = meta(last[i])
             self._columns_set_rows(rows)
         if not fresh:
             return
-        # quantize + pack on the device (szg_index_append_f64)
-        self._index.append_vectors(V if len(fresh) == len(ids) else V[[last[i] for i in fresh]])
+        # quantize + pack on the device (szg_index_append_f64; szg_index_append_dev for vectors that are there already)
+        if on_device:
+            self._index.append_tensor(vectors, src_rows=[last[i] for i in fresh])
+        else:
+            self._index.append_vectors(V if len(fresh) == len(ids) else V[[last[i] for i in fresh]])
         for i in fresh:
             self._row_of[i] = len(self._id_of)
             self._id_of.append(i)

@@ -402,6 +402,13 @@ hipError_t launch_synth(int qbits, uint8_t *rows, RowLayout layout, uint64_t dst
                         uint64_t n_rows, uint64_t seed, uint64_t seed_first_row, const double *src,
                         hipStream_t stream);
 
+// launch_synth's second form for a source that stays where the caller has it on the card: elements of type src_type
+// (SZG_SRC_*: float64, float32, float16, bfloat16, aligned to the element only), row_stride elements from one source
+// row to the next, destination row dst_first_row + i from source row src_index[i] (a device array; nullptr: row i).
+// The bytes are launch_synth's on the values widened to float64.  n_rows * pitch / 16 must fit 2^39 (one launch).
+hipError_t launch_ingest(int qbits, uint8_t *rows, RowLayout layout, uint64_t dst_first_row, int dim, uint64_t n_rows,
+                         const void *data, int src_type, uint64_t row_stride, const uint64_t *src_index, hipStream_t stream);
+
 // Resident row norms (shared sweeps), out[first_row + i] for rows [first_row, first_row + n_rows) of the mirror:
 // 16-bit rows (linear): the float32 sum of n^2, n = 2v - 65535, over the row's real elements, as the direct bfloat16
 // sweep summed it; 8- and 4-bit rows (either layout): (float)(4 * sum (x'^2 + x')) + norm_bias, the int8 sweeps' norm.

@@ -7,6 +7,8 @@
 //    quantization.go:25-36) and evaluate the reference distance bit for bit.
 //  * synth_kernel: counter-based synthetic corpus, quantized and packed exactly
 //    as encodeDocument/quantize (collection.go:713-743, quantization.go:5-23).
+//  * ingest_kernel: the same encoder over vectors the caller keeps in device memory (float64,
+//    float32, float16 or bfloat16; a row stride; an optional list of source rows).
 //  * repack_kernel: page-in transform between the reference's big-endian
 //    element encoding and the resident little-endian, 16-byte-pitched layout.
 //  * gather_rows_kernel: rows copied piece by piece from one resident (or linear)
@@ -397,6 +399,28 @@ __device__ __forceinline__ uint64_t quantize(double value)
     return (uint64_t)round(q);  // half away from zero, like math.Round
 }
 
+// code q of element i of a 16-byte piece into the piece's four words (encodeDocument, collection.go:713-743):
+// synth_kernel's packing as a function, for ingest_kernel.  synth_kernel keeps its own lines: through this function
+// its 64-bit form compiles to other (equivalent) instructions, and its device code is what every corpus so far was
+// built by.
+template <int QBITS>
+__device__ __forceinline__ void pack_code(uint32_t (&w)[4], int i, uint64_t q)
+{
+    if (QBITS == 64) {
+        w[2 * i] = (uint32_t)q;
+        w[2 * i + 1] = (uint32_t)(q >> 32);
+    } else if (QBITS == 32) {
+        w[i] = (uint32_t)q;
+    } else if (QBITS == 16) {
+        w[i >> 1] |= (uint32_t)q << (16 * (i & 1));
+    } else if (QBITS == 8) {
+        w[i >> 2] |= (uint32_t)q << (8 * (i & 3));
+    } else {  // 4-bit: even element in the high nibble of byte i/2
+        const int b = i >> 1;
+        w[b >> 2] |= (uint32_t)(q & 0xF) << (8 * (b & 3) + ((i & 1) ? 0 : 4));
+    }
+}
+
 // one thread per 16-byte piece of the resident row.  src == nullptr: synthetic
 // values; otherwise row-major float64 vectors (bulk AddDocument: quantize + pack on
 // the device exactly as encodeDocument does, collection.go:713-743)
@@ -430,6 +454,91 @@ __global__ void synth_kernel(uint8_t *dst, RowLayout lay, uint64_t dst_first_row
         } else {  // 4-bit: even element in the high nibble of byte i/2
             const int b = i >> 1;
             w[b >> 2] |= (uint32_t)(q & 0xF) << (8 * (b & 3) + ((i & 1) ? 0 : 4));
+        }
+    }
+    *reinterpret_cast<uint4 *>(dst + piece_offset(lay, dst_first_row + row, j)) = make_uint4(w[0], w[1], w[2], w[3]);
+}
+
+// ---- ingest from device memory (szg_index_append_dev / szg_index_overwrite_rows_dev) -----------
+// synth_kernel's src != nullptr branch for a source the caller keeps on the card: elements of type SRC (SZG_SRC_*),
+// `row_stride` elements from one source row to the next, destination row i read from source row src_index[i]
+// (src_index == nullptr: row i).  Every SRC widens to float64 exactly -- float32 and float16 through the hardware
+// converts (subnormals kept: the build passes no flush flag), bfloat16 as the upper half of a float32 -- and
+// quantize / pack_code follow as above, so the bytes are those of szg_index_append_f64 on the widened values.
+//
+// `data` is aligned to its element only.  A thread's E elements are read W = min(16, E * sizeof) bytes at a time
+// where its first element's address is a multiple of W and the piece is full; otherwise (a row slice that starts
+// at an odd element, an odd row stride, the last piece of a row) element by element.
+template <int SRC>
+struct SrcElem;
+template <>
+struct SrcElem<0> {  // SZG_SRC_F64
+    typedef uint64_t bits;
+    static __device__ __forceinline__ double widen(bits b) { return __longlong_as_double((long long)b); }
+};
+template <>
+struct SrcElem<1> {  // SZG_SRC_F32
+    typedef uint32_t bits;
+    static __device__ __forceinline__ double widen(bits b) { return (double)__uint_as_float(b); }
+};
+template <>
+struct SrcElem<2> {  // SZG_SRC_F16
+    typedef uint16_t bits;
+    static __device__ __forceinline__ double widen(bits b) { return (double)(float)__builtin_bit_cast(_Float16, b); }
+};
+template <>
+struct SrcElem<3> {  // SZG_SRC_BF16
+    typedef uint16_t bits;
+    static __device__ __forceinline__ double widen(bits b) { return (double)__uint_as_float((uint32_t)b << 16); }
+};
+
+template <int QBITS, int SRC>
+__global__ __launch_bounds__(256) void ingest_kernel(uint8_t *dst, RowLayout lay, uint64_t dst_first_row, int dim,
+                                                     uint64_t n_rows, const void *data, uint64_t row_stride,
+                                                     const uint64_t *src_index)
+{
+    typedef typename SrcElem<SRC>::bits bits_t;
+    constexpr int E = 128 / QBITS;                 // elements per 16-byte piece
+    constexpr int ES = (int)sizeof(bits_t);        // bytes per source element
+    constexpr int W = E * ES < 16 ? E * ES : 16;   // bytes per wide load
+    constexpr int PER = W / ES;                    // elements per wide load
+    const uint32_t r16 = lay.pitch / 16;
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint64_t row = t / r16;
+    const uint32_t j = (uint32_t)(t - row * r16);
+    if (row >= n_rows) return;
+    uint32_t w[4] = {0, 0, 0, 0};
+    const int e0 = (int)j * E;
+    if (e0 < dim) {  // (pieces of the pitch behind the row's last element are zeros)
+        const uint64_t from = src_index ? src_index[row] : row;
+        const bits_t *p = static_cast<const bits_t *>(data) + from * row_stride + (uint64_t)e0;
+        if (e0 + E <= dim && (reinterpret_cast<uintptr_t>(p) & (uintptr_t)(W - 1)) == 0) {
+#pragma unroll
+            for (int c = 0; c < E / PER; c++) {
+                uint32_t raw[W / 4];
+                if constexpr (W == 16) {
+                    const uint4 v = reinterpret_cast<const uint4 *>(p)[c];
+                    raw[0] = v.x, raw[1] = v.y, raw[2] = v.z, raw[3] = v.w;
+                } else if constexpr (W == 8) {
+                    const uint2 v = reinterpret_cast<const uint2 *>(p)[c];
+                    raw[0] = v.x, raw[1] = v.y;
+                } else {
+                    raw[0] = reinterpret_cast<const uint32_t *>(p)[c];
+                }
+#pragma unroll
+                for (int k = 0; k < PER; k++) {
+                    bits_t b;
+                    if constexpr (ES == 8) b = ((uint64_t)raw[2 * k + 1] << 32) | raw[2 * k];
+                    else if constexpr (ES == 4) b = raw[k];
+                    else b = (bits_t)(raw[k >> 1] >> (16 * (k & 1)));
+                    pack_code<QBITS>(w, c * PER + k, quantize<QBITS>(SrcElem<SRC>::widen(b)));
+                }
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < E; i++) {
+                if (e0 + i < dim) pack_code<QBITS>(w, i, quantize<QBITS>(SrcElem<SRC>::widen(p[i])));
+            }
         }
     }
     *reinterpret_cast<uint4 *>(dst + piece_offset(lay, dst_first_row + row, j)) = make_uint4(w[0], w[1], w[2], w[3]);
@@ -889,6 +998,39 @@ hipError_t launch_synth(int qbits, uint8_t *rows, RowLayout lay, uint64_t dst_fi
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
+}
+
+namespace {
+template <int QBITS>
+hipError_t launch_ingest_q(uint8_t *rows, RowLayout lay, uint64_t dst_first_row, int dim, uint64_t n_rows, const void *data,
+                           int src_type, uint64_t row_stride, const uint64_t *src_index, hipStream_t stream)
+{
+    const uint64_t total = n_rows * (lay.pitch / 16);
+    if ((total + 255) / 256 > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    const dim3 g((unsigned)((total + 255) / 256)), b(256);
+    switch (src_type) {
+    case 0: hipLaunchKernelGGL((ingest_kernel<QBITS, 0>), g, b, 0, stream, rows, lay, dst_first_row, dim, n_rows, data, row_stride, src_index); break;
+    case 1: hipLaunchKernelGGL((ingest_kernel<QBITS, 1>), g, b, 0, stream, rows, lay, dst_first_row, dim, n_rows, data, row_stride, src_index); break;
+    case 2: hipLaunchKernelGGL((ingest_kernel<QBITS, 2>), g, b, 0, stream, rows, lay, dst_first_row, dim, n_rows, data, row_stride, src_index); break;
+    case 3: hipLaunchKernelGGL((ingest_kernel<QBITS, 3>), g, b, 0, stream, rows, lay, dst_first_row, dim, n_rows, data, row_stride, src_index); break;
+    default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+}  // namespace
+
+hipError_t launch_ingest(int qbits, uint8_t *rows, RowLayout lay, uint64_t dst_first_row, int dim, uint64_t n_rows,
+                         const void *data, int src_type, uint64_t row_stride, const uint64_t *src_index, hipStream_t stream)
+{
+    if (n_rows == 0) return hipSuccess;
+    switch (qbits) {
+    case 4: return launch_ingest_q<4>(rows, lay, dst_first_row, dim, n_rows, data, src_type, row_stride, src_index, stream);
+    case 8: return launch_ingest_q<8>(rows, lay, dst_first_row, dim, n_rows, data, src_type, row_stride, src_index, stream);
+    case 16: return launch_ingest_q<16>(rows, lay, dst_first_row, dim, n_rows, data, src_type, row_stride, src_index, stream);
+    case 32: return launch_ingest_q<32>(rows, lay, dst_first_row, dim, n_rows, data, src_type, row_stride, src_index, stream);
+    case 64: return launch_ingest_q<64>(rows, lay, dst_first_row, dim, n_rows, data, src_type, row_stride, src_index, stream);
+    default: return hipErrorInvalidValue;
+    }
 }
 
 hipError_t launch_fill_bits(uint64_t *bits, uint64_t n_rows, uint64_t n_words, hipStream_t stream)

@@ -1,5 +1,7 @@
 // scan_bulk.cpp -- bulk mutations: a list of rows overwritten, tombstoned or given new column values in ONE call
-// (szg_index_overwrite_rows, its _f64 form, szg_index_tombstone_rows / _mask, szg_column_set_rows).
+// (szg_index_overwrite_rows, its _f64 form, szg_index_tombstone_rows / _mask, szg_column_set_rows), and the two
+// mutations whose vectors lie in device memory (szg_index_append_dev, szg_index_overwrite_rows_dev: launch_ingest
+// reads the caller's memory in place, after dev_source_check has cleared the pointer on the host).
 //
 // Every list is checked and split per shard on the host (bulk_plan.h) and every staging block is reserved before
 // anything on the card changes: a bad list or a refused allocation leaves the handle as it was.  An overwrite then
@@ -81,16 +83,88 @@ void note_overwritten_rows(szg_index *ix, const uint64_t *rows, uint64_t n)
     }
 }
 
-// Both overwrite forms: entry i of `data` (entry_bytes each: a row in the reference encoding, or dim float64) replaces
-// row rows[i].
-int overwrite_rows(szg_index *ix, const uint64_t *rows, const uint8_t *data, size_t entry_bytes, uint64_t n, bool f64)
+// ---- vectors in device memory (szg_dev_vectors) ---------------------------------------------------------------------
+constexpr size_t kSrcElemBytes[4] = {8, 4, 2, 2};  // SZG_SRC_F64, _F32, _F16, _BF16
+
+// Every check of a device source that needs no handle state beyond dim, all of them on the host: the descriptor, the
+// list of source rows, what the runtime knows about the pointer (hipPointerGetAttributes) and the extent of its
+// allocation (hipMemGetAddressRange).  Nothing is launched, nothing on the card is touched.  n == 0 checks the
+// descriptor only (an empty tensor has no memory to ask about).
+int dev_source_check(const szg_index *ix, const szg_dev_vectors *src, const uint64_t *src_rows, uint64_t n)
+{
+    if (src->dtype < SZG_SRC_F64 || src->dtype > SZG_SRC_BF16) return fail(SZG_E_INVALID, "unknown source dtype");
+    const size_t es = kSrcElemBytes[src->dtype];
+    if (src->row_stride < (uint64_t)ix->dim) return fail(SZG_E_INVALID, "row_stride < dim");
+    if (n == 0) return SZG_OK;
+    if (!src->data) return fail(SZG_E_INVALID, "null argument");
+    if (reinterpret_cast<uintptr_t>(src->data) % es) return fail(SZG_E_INVALID, "data not aligned to its element size");
+    uint64_t last = n - 1;  // the largest source row used
+    if (!src_rows) {
+        if (n > src->n_rows) return fail(SZG_E_INVALID, "n_rows > src->n_rows");
+    } else {
+        last = 0;
+        for (uint64_t i = 0; i < n; i++) {
+            if (src_rows[i] >= src->n_rows) return fail(SZG_E_RANGE, "source row out of range");
+            last = std::max(last, src_rows[i]);
+        }
+    }
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess) count = 0;
+    if (src->device < 0 || src->device >= count) return fail(SZG_E_INVALID, "device ordinal out of range");
+    hipPointerAttribute_t attr;
+    std::memset(&attr, 0, sizeof attr);
+    if (hipPointerGetAttributes(&attr, src->data) != hipSuccess) {  // (a pointer the runtime does not know is host memory)
+        (void)hipGetLastError();
+        return fail(SZG_E_INVALID, "not device memory");
+    }
+    if (attr.type != hipMemoryTypeDevice) return fail(SZG_E_INVALID, "not device memory");
+    if (attr.device != src->device) return fail(SZG_E_INVALID, "not device memory of src->device");
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, const_cast<void *>(src->data)) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(SZG_E_INVALID, "not device memory");
+    }
+    // the last element addressed ends at data + (last * row_stride + dim) * es: inside [base, base + size)
+    const unsigned __int128 end = (unsigned __int128)(reinterpret_cast<uintptr_t>(src->data) - reinterpret_cast<uintptr_t>(base)) +
+                                  ((unsigned __int128)last * src->row_stride + (uint64_t)ix->dim) * es;
+    if (end > size) return fail(SZG_E_RANGE, "source rows reach past the allocation");
+    return SZG_OK;
+}
+
+// rows one launch_ingest may take: at most the bulk chunk's 8-byte list entries, and a grid that fits
+uint64_t ingest_chunk_rows(const szg_index *ix)
+{
+    return std::max<uint64_t>(1, std::min<uint64_t>(kBulkChunkBytes / sizeof(uint64_t), (0x7FFFFFFFull * 256) / (ix->pitch / 16)));
+}
+
+// what an overwrite's entries are: host memory -- rows in the reference encoding, or dim float64 each -- or vectors in
+// device memory, entry i from source row src_rows[i] (null: row i)
+struct RowSource {
+    const uint8_t *host = nullptr;
+    size_t entry_bytes = 0;
+    bool f64 = false;
+    const szg_dev_vectors *dev = nullptr;
+    const uint64_t *src_rows = nullptr;
+    const char *name = "overwrite_rows";
+};
+
+// All overwrite forms: entry i replaces row rows[i].  A device source is encoded where it lies: its part of the stage
+// holds the chunk's list of source rows (8 bytes per row) instead of data.
+int overwrite_rows(szg_index *ix, const uint64_t *rows, const RowSource &from, uint64_t n)
 {
     BulkPlan plan;
     if (int rc = plan_index_rows(ix, rows, n, 0, &plan)) return rc;
     if (n == 0) return SZG_OK;
     const size_t S = ix->shards.size();
-    const uint64_t chunk = std::max<uint64_t>(1, kBulkChunkBytes / entry_bytes);
-    // a chunk of m entries in the stage: the data | m linear resident rows | the list | m norms
+    const szg_dev_vectors *dev = from.dev;
+    if (dev)
+        for (size_t s = 0; s < S; s++)
+            if (!plan.local[s].empty() && ix->shards[s]->device != dev->device) return fail(SZG_E_INVALID, "source on another device");
+    const size_t entry_bytes = dev ? sizeof(uint64_t) : from.entry_bytes;
+    const uint64_t chunk = dev ? std::min<uint64_t>(ingest_chunk_rows(ix), std::max<uint64_t>(1, kBulkChunkBytes / ix->pitch))
+                               : std::max<uint64_t>(1, kBulkChunkBytes / entry_bytes);
+    // a chunk of m entries in the stage: the data (the source rows' list) | m linear resident rows | the list | m norms
     auto at_rows = [&](uint64_t m) { return up256((size_t)(m * entry_bytes)); };
     auto at_list = [&](uint64_t m) { return at_rows(m) + up256((size_t)(m * ix->pitch)); };
     auto at_norm = [&](uint64_t m) { return at_list(m) + up256((size_t)(m * sizeof(uint64_t))); };
@@ -103,12 +177,14 @@ int overwrite_rows(szg_index *ix, const uint64_t *rows, const uint8_t *data, siz
     note_overwritten_rows(ix, rows, n);
     const szg::RowLayout linear{ix->pitch, 0, 0};
     std::vector<uint8_t> tmp;
+    std::vector<uint64_t> from_rows;
     for (size_t s = 0; s < S; s++) {
         const uint64_t c = plan.local[s].size();
         if (c == 0) continue;
         Shard *sh = ix->shards[s];
         HIPCHK(hipSetDevice(sh->device));
-        HIPCHK(hipDeviceSynchronize());  // (searches in flight on this device finish first, as for one row)
+        HIPCHK(hipDeviceSynchronize());  // (searches in flight on this device finish first, as for one row; a device
+                                         // source lies on this device: whatever was queued to write it has finished too)
         const bool norms = sh->row_norm && sh->norm_valid;  // (the array only exists where the row width keeps norms)
         uint8_t *stage = sh->stage;
         hipError_t e = hipSuccess;
@@ -117,11 +193,25 @@ int overwrite_rows(szg_index *ix, const uint64_t *rows, const uint8_t *data, siz
             uint8_t *d_in = stage, *d_rows = stage + at_rows(m);
             uint64_t *d_list = reinterpret_cast<uint64_t *>(stage + at_list(m));
             float *d_norm = reinterpret_cast<float *>(stage + at_norm(m));
-            e = hipMemcpy(d_in, chunk_data(data, entry_bytes, plan.source[s], off, m, &tmp), m * entry_bytes, hipMemcpyHostToDevice);
+            if (dev) {
+                from_rows.resize((size_t)m);
+                for (uint64_t j = 0; j < m; j++) {
+                    const uint64_t i = plan.source[s][off + j];
+                    from_rows[(size_t)j] = from.src_rows ? from.src_rows[i] : i;
+                }
+                e = hipMemcpy(d_in, from_rows.data(), m * sizeof(uint64_t), hipMemcpyHostToDevice);
+            } else {
+                e = hipMemcpy(d_in, chunk_data(from.host, entry_bytes, plan.source[s], off, m, &tmp), m * entry_bytes, hipMemcpyHostToDevice);
+            }
             if (e == hipSuccess) e = hipMemcpy(d_list, plan.local[s].data() + off, m * sizeof(uint64_t), hipMemcpyHostToDevice);
-            if (e == hipSuccess)
-                e = f64 ? szg::launch_synth(ix->bits, d_rows, linear, 0, ix->dim, m, 0, 0, reinterpret_cast<const double *>(d_in), nullptr)
-                        : szg::launch_repack(ix->bits, d_in, ix->row_bytes, d_rows, linear, 0, m, 0, nullptr);
+            if (e == hipSuccess) {
+                if (dev)
+                    e = szg::launch_ingest(ix->bits, d_rows, linear, 0, ix->dim, m, dev->data, dev->dtype, dev->row_stride,
+                                           reinterpret_cast<const uint64_t *>(d_in), nullptr);
+                else
+                    e = from.f64 ? szg::launch_synth(ix->bits, d_rows, linear, 0, ix->dim, m, 0, 0, reinterpret_cast<const double *>(d_in), nullptr)
+                                 : szg::launch_repack(ix->bits, d_in, ix->row_bytes, d_rows, linear, 0, m, 0, nullptr);
+            }
             if (e == hipSuccess)
                 e = szg::launch_scatter_rows(d_rows, linear, sh->rows, ix->layout, ix->pitch / 16, d_list, m, sh->n_rows, nullptr);
             if (e == hipSuccess && norms)  // the norms of the staged rows, then to the listed rows below norm_valid
@@ -130,7 +220,7 @@ int overwrite_rows(szg_index *ix, const uint64_t *rows, const uint8_t *data, siz
                 e = szg::launch_column_scatter(d_norm, sizeof(float), d_list, m, sh->row_norm.data(), sh->norm_valid, nullptr);
         }
         if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-        if (e != hipSuccess) return fail(SZG_E_DEVICE, f64 ? "overwrite_rows_f64" : "overwrite_rows", e);
+        if (e != hipSuccess) return fail(SZG_E_DEVICE, from.name, e);
     }
     return SZG_OK;
 }
@@ -155,7 +245,9 @@ int szg_index_overwrite_rows(szg_index *ix, const uint64_t *rows, const uint8_t 
 {
     SZG_TRY
     if (!ix || (n_rows && (!rows || !row_bytes))) return fail(SZG_E_INVALID, "null argument");
-    return overwrite_rows(ix, rows, row_bytes, ix->row_bytes, n_rows, false);
+    RowSource from;
+    from.host = row_bytes, from.entry_bytes = ix->row_bytes;
+    return overwrite_rows(ix, rows, from, n_rows);
     SZG_CATCH
 }
 
@@ -163,7 +255,65 @@ int szg_index_overwrite_rows_f64(szg_index *ix, const uint64_t *rows, const doub
 {
     SZG_TRY
     if (!ix || (n_rows && (!rows || !vectors))) return fail(SZG_E_INVALID, "null argument");
-    return overwrite_rows(ix, rows, reinterpret_cast<const uint8_t *>(vectors), (size_t)ix->dim * sizeof(double), n_rows, true);
+    RowSource from;
+    from.host = reinterpret_cast<const uint8_t *>(vectors), from.entry_bytes = (size_t)ix->dim * sizeof(double);
+    from.f64 = true, from.name = "overwrite_rows_f64";
+    return overwrite_rows(ix, rows, from, n_rows);
+    SZG_CATCH
+}
+
+int szg_index_overwrite_rows_dev(szg_index *ix, const uint64_t *rows, const szg_dev_vectors *src, const uint64_t *src_rows,
+                                 uint64_t n_rows)
+{
+    SZG_TRY
+    if (!ix || !src || (n_rows && !rows)) return fail(SZG_E_INVALID, "null argument");
+    if (int rc = dev_source_check(ix, src, src_rows, n_rows)) return rc;
+    RowSource from;
+    from.dev = src, from.src_rows = src_rows, from.name = "overwrite_rows_dev";
+    return overwrite_rows(ix, rows, from, n_rows);
+    SZG_CATCH
+}
+
+// szg_index_append_f64 for vectors in device memory: the same target shard, growth, live bits and counts; the encoder
+// reads the caller's memory where it lies, and only a list of source rows (if given) goes through the stage
+int szg_index_append_dev(szg_index *ix, const szg_dev_vectors *src, const uint64_t *src_rows, uint64_t n_rows)
+{
+    SZG_TRY
+    if (!ix || !src) return fail(SZG_E_INVALID, "null argument");
+    if (int rc = dev_source_check(ix, src, src_rows, n_rows)) return rc;
+    Shard *sh = append_target(ix);
+    if (n_rows && sh->device != src->device) return fail(SZG_E_INVALID, "source on another device");
+    ix->gen++;
+    ix->mask_epoch++;  // (the row count moves: masks made before are stale)
+    if (n_rows == 0) return SZG_OK;
+    HIPCHK(hipSetDevice(sh->device));
+    HIPCHK(hipDeviceSynchronize());  // (the source's device: whatever was queued to write the source has finished)
+    int rc = shard_reserve(ix, sh, sh->n_rows + n_rows);
+    if (rc) return rc;
+    const uint64_t chunk = ingest_chunk_rows(ix);
+    const uint8_t *data = static_cast<const uint8_t *>(src->data);
+    const size_t row_step = (size_t)src->row_stride * kSrcElemBytes[src->dtype];
+    std::unique_lock<std::mutex> stage_lock(sh->stage_mu);
+    uint8_t *stage8 = nullptr;
+    if (src_rows)
+        if ((rc = shard_stage(sh, (size_t)(std::min(chunk, n_rows) * sizeof(uint64_t)), &stage8))) return rc;
+    uint64_t *d_from = reinterpret_cast<uint64_t *>(stage8);
+    hipError_t e = hipSuccess;
+    for (uint64_t off = 0; off < n_rows && e == hipSuccess; off += chunk) {
+        const uint64_t m = std::min(chunk, n_rows - off);
+        if (src_rows) e = hipMemcpy(d_from, src_rows + off, m * sizeof(uint64_t), hipMemcpyHostToDevice);
+        if (e == hipSuccess)
+            e = szg::launch_ingest(ix->bits, sh->rows, ix->layout, sh->n_rows + off, ix->dim, m, src_rows ? data : data + off * row_step,
+                                   src->dtype, src->row_stride, d_from, nullptr);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+    stage_lock.unlock();
+    if (e != hipSuccess) return fail(SZG_E_DEVICE, "append_dev", e);
+    rc = shard_set_live(sh, sh->n_rows, sh->n_rows + n_rows);
+    if (rc) return rc;
+    sh->n_rows += n_rows;
+    sh->n_live += n_rows;
+    return SZG_OK;
     SZG_CATCH
 }
 

@@ -17,7 +17,8 @@
 //   scan_column_carry.cpp  columns carried across a compaction / reorder (column_carry.h: its index arithmetic)
 //   scan_reorder.cpp  compaction and reorder of the resident rows on the device (reorder_plan.h: its host-only checks)
 //   scan_bulk.cpp     bulk mutations: lists of rows overwritten, tombstoned or given column values in one call
-//                     (bulk_plan.h: its host-only checks; kernels_bulk.hip: its scatters)
+//                     (bulk_plan.h: its host-only checks; kernels_bulk.hip: its scatters), and appends / overwrites from
+//                     vectors in device memory (szg_dev_vectors; kernels_exact.hip: ingest_kernel)
 //   scan_api.cpp      remaining C entry points (top-k with caller coalescing, distances)
 //
 // Who owns device memory: dev_mem.h.  Every block is held by a DevBuf / PinnedBuf (scratch of the device that is

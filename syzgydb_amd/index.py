@@ -39,6 +39,71 @@ def pack_allow_bits(mask):
     return np.ascontiguousarray(packed).view(np.uint64).reshape(nq, words)
 
 
+_TORCH_SRC = {"torch.float64": _lib.SZG_SRC_F64, "torch.float32": _lib.SZG_SRC_F32, "torch.float16": _lib.SZG_SRC_F16,
+              "torch.bfloat16": _lib.SZG_SRC_BF16}
+_CAI_SRC = {"<f8": _lib.SZG_SRC_F64, "<f4": _lib.SZG_SRC_F32, "<f2": _lib.SZG_SRC_F16}   # (no typestr names bfloat16)
+_SRC_BYTES = (8, 4, 2, 2)
+
+
+def dev_vectors(t, dim, device=None):
+    """The szg_dev_vectors descriptor of a 2-D array of vectors in device memory: a torch tensor (duck-typed on
+    data_ptr, dtype, shape, stride, device and is_cuda; torch is not imported) or any object with
+    __cuda_array_interface__.  Nothing is copied and no device is touched; the caller keeps `t` alive.
+    The rules: float64, float32, float16 or bfloat16 (else TypeError); shape (n, dim); inner stride 1; a row stride of
+    at least dim (larger: a column slice of a wider tensor); no negative stride (else ValueError).  A CPU tensor is a
+    TypeError: host memory goes through append_vectors / overwrite_vectors.  device: the ordinal to assume where the
+    object does not name one (the array interface has no such field)."""
+    if hasattr(t, "data_ptr"):
+        if not getattr(t, "is_cuda", False):
+            raise TypeError("a CPU tensor is host memory: use append_vectors / overwrite_vectors (or AddDocuments with "
+                            "an array), which take float64 on the host")
+        dtype = _TORCH_SRC.get(str(t.dtype))
+        if dtype is None:
+            raise TypeError("tensor dtype %s: float64, float32, float16 or bfloat16 expected" % (t.dtype,))
+        shape = tuple(int(x) for x in t.shape)
+        strides = tuple(int(x) for x in t.stride())
+        ptr = int(t.data_ptr())
+        if getattr(t.device, "index", None) is not None:
+            device = t.device.index
+    elif hasattr(t, "__cuda_array_interface__"):
+        cai = t.__cuda_array_interface__
+        dtype = _CAI_SRC.get(cai["typestr"])
+        if dtype is None:
+            raise TypeError("array typestr %r: '<f8', '<f4' or '<f2' expected" % (cai["typestr"],))
+        shape = tuple(int(x) for x in cai["shape"])
+        es = _SRC_BYTES[dtype]
+        if cai.get("strides") is None:   # C-contiguous
+            strides = tuple(int(np.prod(shape[i + 1:], dtype=np.int64)) for i in range(len(shape)))
+        else:
+            if any(int(s) % es for s in cai["strides"]):
+                raise ValueError("array strides %r are not multiples of the element size %d" % (cai["strides"], es))
+            strides = tuple(int(s) // es for s in cai["strides"])
+        ptr = int(cai["data"][0] or 0)
+        d = getattr(t, "device", None)
+        d = d if isinstance(d, int) else getattr(d, "id", getattr(d, "index", None))
+        if d is not None:
+            device = int(d)
+    else:
+        raise TypeError("vectors in device memory: a torch tensor or an object with __cuda_array_interface__ expected")
+    if len(shape) != 2:
+        raise ValueError("a 2-D array of vectors expected, got shape %r" % (shape,))
+    n, width = shape
+    if width != dim:
+        raise ValueError("vector size does not match the expected number of dimensions: expected %d, got %d" % (dim, width))
+    if any(s < 0 for s in strides):
+        raise ValueError("negative strides %r" % (strides,))
+    if strides[1] != 1:
+        raise ValueError("the inner stride is %d: the elements of a vector must be contiguous" % strides[1])
+    row_stride = strides[0]
+    if n <= 1:
+        row_stride = max(row_stride, dim)   # (no second row: whatever stride the array reports is never used)
+    elif row_stride < dim:
+        raise ValueError("the row stride %d is smaller than the dimension %d: rows overlap" % (row_stride, dim))
+    if device is None:
+        raise ValueError("the array does not say which device it lies on")
+    return _lib.SzgDevVectors(ptr or None, dtype, int(device), n, row_stride)
+
+
 class ScanMask:
     """A filter mask that lives on the card (szg_mask): made once per (filter, collection version) by
     ScanIndex.mask / mask_rows or composed from other masks with & | ~ and andnot, then passed to the searches as
@@ -359,6 +424,7 @@ class ScanIndex:
         check(self._L.szg_index_create(ctypes.byref(self._h), self.dim, self.quant_bits,
                                        self.metric, dev_arr, n_dev), "szg_index_create")
         self.row_bytes = int(self._L.szg_row_bytes(self.quant_bits, self.dim))
+        self._device0 = devices[0] if devices else None   # (assumed for arrays that do not name their device)
         self.options = {}   # tunables set through this object (the host mirrors consult tie_mode)
         self._comm = None
         self._masks = {}    # id -> (weak reference, handle) of every ScanMask of this handle that is still open
@@ -479,6 +545,35 @@ class ScanIndex:
             raise ValueError("%d vectors for %d rows" % (v.shape[0], r.size))
         check(self._L.szg_index_overwrite_rows_f64(self._h, _u64(r) if r.size else None, _f64(v) if r.size else None, r.size),
               "szg_index_overwrite_rows_f64")
+
+    # -- ingest from device memory: the vectors never visit the host ------------------
+    def _src_rows_arg(self, src_rows):
+        if src_rows is None:
+            return None, None
+        r = np.ascontiguousarray(src_rows, dtype=np.uint64).reshape(-1)
+        return r, (_u64(r) if r.size else None)
+
+    def append_tensor(self, t, src_rows=None):
+        """append_vectors() for vectors in device memory (dev_vectors: a torch tensor or __cuda_array_interface__, in
+        float64 / float32 / float16 / bfloat16, on the device of the shard that takes the rows): quantized and packed
+        where they lie, the same bytes as append_vectors of the values widened to float64.  src_rows: the source row of
+        each new row (any order, duplicates allowed); None appends every row of `t` in order.  The device is
+        synchronised first, and `t` may be freed or rewritten once the call has returned."""
+        d = dev_vectors(t, self.dim, getattr(self, "_device0", None))
+        r, p = self._src_rows_arg(src_rows)
+        check(self._L.szg_index_append_dev(self._h, ctypes.byref(d), p, d.n_rows if r is None else r.size),
+              "szg_index_append_dev")
+
+    def overwrite_tensor(self, rows, t, src_rows=None):
+        """overwrite_vectors() for vectors in device memory (see append_tensor): source row src_rows[i] -- row i of `t`
+        without a list -- replaces row rows[i].  A row out of range or listed twice refuses the whole call."""
+        d = dev_vectors(t, self.dim, getattr(self, "_device0", None))
+        rows = np.ascontiguousarray(rows, dtype=np.uint64).reshape(-1)
+        r, p = self._src_rows_arg(src_rows)
+        if r is not None and r.size != rows.size:
+            raise ValueError("%d source rows for %d rows" % (r.size, rows.size))
+        check(self._L.szg_index_overwrite_rows_dev(self._h, _u64(rows) if rows.size else None, ctypes.byref(d), p, rows.size),
+              "szg_index_overwrite_rows_dev")
 
     def tombstone_rows(self, rows):
         """tombstone() for a list (duplicates and dead rows allowed): the rows that were live and no longer are."""
