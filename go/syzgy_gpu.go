@@ -117,6 +117,15 @@ func newGPUMirror(c *Collection, devices []int) (*gpuMirror, error) {
 		C.szg_set_option(m.h, name, val)
 		C.free(unsafe.Pointer(name))
 	}
+	// Lone Searches with K of 35 or more are beyond the pre-pass's lists and sweep the rows themselves.  With
+	// SYZGY_GPU_SKETCH_TOPK_COLLECT=1 (option sketch_topk_collect, off by default while it soaks) they go through the
+	// sketch all the same: a sample pass bounds the K-th distance, a collect sweep at that radius contains the answer
+	// (DESIGN.md 4.5 item 16; same answers).  sketchTopkStats reads what the path served.
+	if os.Getenv("SYZGY_GPU_SKETCH_TOPK_COLLECT") == "1" {
+		name := C.CString("sketch_topk_collect")
+		C.szg_set_option(m.h, name, 1)
+		C.free(unsafe.Pointer(name))
+	}
 	if err := m.reload(c); err != nil {
 		m.close()
 		return nil, err
@@ -552,6 +561,16 @@ func (m *gpuMirror) fullReplays() uint64 {
 		return 0
 	}
 	return uint64(st.full_replays)
+}
+
+// sketchTopkStats reads what top-k Searches of large K through the sketch (option sketch_topk_collect) served since the
+// last reset: queries settled and queries handed to the full-precision path.
+func (m *gpuMirror) sketchTopkStats() (settled, handedOver uint64) {
+	var st C.szg_sketch_topk_stats
+	if C.szg_index_sketch_topk_stats(m.h, &st) != C.SZG_OK {
+		return 0, 0
+	}
+	return uint64(st.queries), uint64(st.fallbacks)
 }
 
 // searchExactKeyed: filterKey names args.Filter for the bitmask cache ("" = do not cache).

@@ -697,6 +697,22 @@ int szg_get_stats(szg_index *ix, szg_stats *out);
 int szg_reset_stats(szg_index *ix);
 
 /*
+ * Top-k searches of large k through the sketch (option sketch_topk_collect): what the path served on the handle since
+ * szg_reset_stats, which clears the five counters.  Kept beside szg_stats, whose layout stays as it is (ABI 4, additive):
+ * szg_stats.queries and scan_bytes count these searches as they count radius searches through the sketch -- a settled
+ * query once, the sample pass as its rows x the sketch's row bytes per launch, the collect sweeps as one pass per launch
+ * that shares its row reads and one per query elsewhere.
+ */
+typedef struct szg_sketch_topk_stats {
+    uint64_t queries;      /* top-k queries the path settled */
+    uint64_t fallbacks;    /* ... and those it handed to the full-precision path (the option's paragraph lists the reasons) */
+    uint64_t sample_rows;  /* rows scored by the sample passes, per launch (not per query) */
+    uint64_t candidates;   /* entries the collect sweeps and the staged rows left in the settled queries' buffers */
+    uint64_t overflows;    /* of the fallbacks: more candidates than the batch's buffers held */
+} szg_sketch_topk_stats;
+int szg_index_sketch_topk_stats(szg_index *ix, szg_sketch_topk_stats *out);
+
+/*
  * Tunables (name, default, meaning): the seventeen a deployment could want.  All are safe to change between calls.
  * (Rounds 1-3 exposed another fifteen -- ring depths, waves per CU, stream placement, sweep kinds per row width --
  * whose values measurement settled; they are compile-time constants now, csrc/scan_internal.h, and A/B runs go
@@ -843,6 +859,24 @@ int szg_reset_stats(szg_index *ix);
  *                             handle behaves as a float32 handle does under sketch = 0 (an existing sketch index stays
  *                             until the handle is closed or reloaded).  Handles of other widths ignore it.  Other values
  *                             are refused
+ *     sketch_topk_collect 0   1 = a top-k call that takes one sweep per query (a lone szg_search_topk, any call under
+ *                             multi_query = 0) with a k the pre-pass does not serve (k + sketch_extra beyond its lists: k >= 35
+ *                             by default) goes through the sketch all the same, wherever "sketch" applies to the handle's
+ *                             rows (float32, or float64 under sketch_f64 = 1; the row-count rule, the steps aside) and the
+ *                             sample plan serves every shard (szg_debug_sample_plan: k <= 2048 and at least 4 k rows in
+ *                             every second tile of 16): a SAMPLE pass scores every stride-th tile (stride 16, 8, 4 or 2)
+ *                             of the sketch on the matrix cores, 16 or 32 queries per row read; the (k + e)-th smallest
+ *                             sample key of a shard (e = its eligible sampled rows without a usable sketch) bounds the
+ *                             query's k-th distance from above by tau; a radius search at tau through the sketch -- the
+ *                             collect sweep, float64 re-rank and gather of sketch_radius, whatever that option says --
+ *                             contains the whole answer, ties included, and the reference's heap is replayed over it.
+ *                             A NaN among the first k rows or distances that tie among the best k + 1 (tie_mode = 0), a
+ *                             zero query under cosine, a non-finite query, tau widened to 1 or more under cosine, no shard
+ *                             with k + e eligible sample rows and more candidates than the batch's buffers hold take the
+ *                             full-precision path, all of a call as ONE call (szg_index_sketch_topk_stats counts them;
+ *                             they do not enter automatic mode's window).  Same answers.  0 = never (the default while
+ *                             the option soaks): no allocation, no launch, one test of the option.  Calls that share a
+ *                             sweep (multi_query = 1, mq_min queries or more) keep it.  Other values are refused
  *   shared sweeps
  *     multi_query         1   batches of >= mq_min queries share ONE sweep of the corpus, the dot products on the
  *                             matrix cores: 64- / 32- / 16-bit rows on bfloat16 roundings (v_mfma_f32_16x16x32_bf16,
@@ -1001,6 +1035,22 @@ int szg_debug_scan_collect(int dim, int quant_bits, int n_queries, int planes, i
                            int32_t *passes, uint64_t *lds_bytes, int32_t *steps_form);
 
 /*
+ * Test hook, host only: the sample plan of a top-k search through the sketch (option sketch_topk_collect; csrc/sample_plan.h)
+ * for a shard of shard_rows rows of dim elements at quant_bits (the sketch index is 8; any other width is not served),
+ * queries of `planes` digit planes (the sketch's are 2) and a launch of n_queries (1 .. 32).  serves = 0: the shard is
+ * not served (untiled rows -- dim no multiple of 64 --, an image beyond 64 KiB of LDS, k beyond 2048, fewer than 4 k rows
+ * in every second tile) and the other fields are 0.  stride: in tiles of 16 rows, the largest of 16, 8, 4, 2 that leaves
+ * sample_rows >= 4 k; tiles: the sample's; slots = 16 tiles: key slots per query (a partial last tile in the sample
+ * keeps all 16); key_bytes = 4 n_queries slots; cap: entries per query the collect buffers start with, 8 k stride rounded
+ * up to a power of two; blocks: column blocks of 16 queries the launch scores per row read (1 or 2); lds_bytes: its LDS.
+ */
+typedef struct szg_sample_plan {
+    int32_t serves, stride, blocks, reserved;
+    uint64_t tiles, sample_rows, slots, key_bytes, cap, lds_bytes;
+} szg_sample_plan;
+int szg_debug_sample_plan(uint64_t shard_rows, int k, int n_queries, int dim, int quant_bits, int planes, szg_sample_plan *out);
+
+/*
  * Test hook, host only: *fits = the sketch sweep's one-launch short-list merge serves n_lists block lists of m entries
  * at kp candidates; *sorts = the most entries under its threshold (the kp-th smallest first entry) that its selection
  * sorts in one network -- with more, and always when *sorts < kp, the launch runs the tournament.
@@ -1018,7 +1068,7 @@ int szg_debug_scan_group_ring(int dim, int quant_bits, int kp, int scan_group, i
 /*
  * Test hook, host only: would szg_set_option accept `value` for the one-sweep kernel's option `name` (scan_group,
  * scan_group_ring, scan_norms, sketch_planes, sketch_matrix, sketch_select, sketch_wide, sketch_share, sketch_bulk, sketch_radius,
- * sketch_masked, sketch_f64)?  SZG_OK, or SZG_E_INVALID with szg_set_option's text; any other name is refused.
+ * sketch_masked, sketch_f64, sketch_topk_collect)?  SZG_OK, or SZG_E_INVALID with szg_set_option's text; any other name is refused.
  */
 int szg_debug_option_check(const char *name, int64_t value);
 
@@ -1098,6 +1148,13 @@ int szg_debug_refuse_device_alloc(int64_t nth);
                                     thr / eps of the sketch sweep, D = the sketch-distance radius R (1 + 1e-9) + slack,
                                     keyed entries = the collected sketch rows with their sketch keys, NO_KEY entries =
                                     the rows without a usable sketch re-ranked beside them */
+#define SZG_CERT_SKETCH_TOPK_COLLECT 6 /* top-k of large k through the sketch (option sketch_topk_collect; recorded on the float32 /
+                                    float64 handle, one record per settled or handed-over query): thr / eps / D / slack as
+                                    for SZG_CERT_SKETCH_RADIUS, of the collect sweep at radius tau; kmax = U, the bound on the
+                                    real-number sketch key of k eligible sampled rows; thr_min = tau, the radius U implies
+                                    (+ slack); k; certified 1 = settled, 0 = handed over (before the sweep, or with more
+                                    candidates than the buffers held: thr, eps, D NaN and no entries).  Keyed entries = the collected sketch rows, NO_KEY entries = the rows
+                                    without a usable sketch and the query's first k eligible rows */
 #define SZG_CERT_KEYS_SINGLE 0
 #define SZG_CERT_KEYS_SHARED_INT8 1
 #define SZG_CERT_KEYS_SHARED_BF16 2

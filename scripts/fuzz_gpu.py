@@ -36,7 +36,7 @@ OPTS = [("queries_per_launch", [1, 3, 16]), ("multi_query", [0, 1]), ("force_mat
         ("sketch", [0, 1, 1]), ("sketch_extra", [0, 30]), ("sketch_min_rows", [1, 1, 4096]),
         ("force_no_refine", [0, 0, 1]), ("mask_dense", [0, 1]), ("coalesce", [0, 1]), ("finish_thread", [0, 1, 1]),
         ("radius_mq", [0, 1, 1]), ("query_batch", [5, 16]), ("scan_group", [0, 1, 2, 4]), ("sketch_radius", [0, 1, 1]),
-        ("sketch_share", [0, 1, 2, 2])]
+        ("sketch_share", [0, 1, 2, 2]), ("sketch_topk_collect", [0, 1, 1])]
 
 
 def same(got_r, got_d, want_r, want_d):

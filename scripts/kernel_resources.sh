@@ -12,6 +12,7 @@
 #   scripts/kernel_resources.sh scan mx 1     -> kernels_scan_mx.hip -DSZG_SCAN_METRIC=1 (the matrix sweep, cosine)
 #   VFLAGS=-DSZG_MX_COLLECT scripts/kernel_resources.sh scan mx 1
 #                                             -> its collect form (radius searches through the sketch)
+#   scripts/kernel_resources.sh sample        -> kernels_sample_mx.hip (the sample pass of top-k through the sketch)
 #   scripts/kernel_resources.sh exact         -> kernels_exact.hip (re-rank, page-in, row gather, ...)
 #   scripts/kernel_resources.sh mask          -> kernels_mask.hip (device-resident filter masks)
 #   scripts/kernel_resources.sh column        -> kernels_column.hip (resident metadata columns)
@@ -22,6 +23,7 @@ cd "$(dirname "$0")/../syzgydb_amd/csrc"
 kind=${1:-mq}; part=${2:-i8}
 if [ "$kind" = scan ] && [ "$part" = mx ]; then src=kernels_scan_mx.hip; def="-DSZG_SCAN_METRIC=${3:-1} -fno-slp-vectorize -DSZG_MX_NO_SLP"   # (the Makefile's MX_FLAGS)
 elif [ "$kind" = scan ]; then src=kernels_scan.hip; def="-DSZG_QBITS=${2:?row width (4, 8, 16, 32, 64) or mx} -DSZG_SCAN_METRIC=${3:-1}"
+elif [ "$kind" = sample ]; then src=kernels_sample_mx.hip; def=
 elif [ "$kind" = merge ]; then src=kernels_scan_merge.hip; def=
 elif [ "$kind" = exact ]; then src=kernels_exact.hip; def=-ffp-contract=off
 elif [ "$kind" = mask ]; then src=kernels_mask.hip; def=

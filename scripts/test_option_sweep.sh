@@ -27,7 +27,8 @@ run() {  # $1 = label, rest = pytest arguments
             force_matrix=1 multi_query=0 contexts=1,mask_dense=0,coalesce=0 mq_min=8,mq_hits=256 \
             sketch=1,sketch_min_rows=1 sketch=1,multi_query=0,sketch_extra=0,sketch_min_rows=1 force_no_refine=1 \
             finish_thread=0,radius_mq=0 scan_group=1 scan_group=2 sketch_planes=3,scan_norms=1 scan_group_ring=4 sketch_matrix=1 \
-            sketch_select=1 sketch_wide=1 sketch_f64=1,sketch=1,sketch_min_rows=1}; do
+            sketch_select=1 sketch_wide=1 sketch_f64=1,sketch=1,sketch_min_rows=1 \
+            sketch_topk_collect=1,sketch=1,sketch_min_rows=1,multi_query=0}; do
   run "$opts" tests -m gpu -q -x --ignore=tests/test_gpu_fullsize.py --ignore=tests/test_gpu_bench_launch.py \
       --deselect tests/test_gpu_multiquery.py::test_shared_sweep_matches_oracle \
       --deselect tests/test_gpu_multiquery.py::test_shared_sweep_quantized_rows \

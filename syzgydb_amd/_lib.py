@@ -68,10 +68,13 @@ EXPORTS = [
     "szg_debug_scan_masked", "szg_debug_sketch_masked",
     # the certification bound of a key as a pure function (csrc/key_bound.h), host only
     "szg_debug_key_eps",
+    # top-k of large k through the sketch (option sketch_topk_collect): the counters and the sample plan hook
+    "szg_index_sketch_topk_stats", "szg_debug_sample_plan",
 ]
 # szg_cert_record.pass / .keys, szg_cert_entry.flags
 SZG_CERT_TOPK, SZG_CERT_SKETCH, SZG_CERT_ESCALATION, SZG_CERT_RADIUS_SINGLE, SZG_CERT_RADIUS_SHARED = range(5)
 SZG_CERT_SKETCH_RADIUS = 5   # radius collect on the sketch (option sketch_radius), recorded on the float32 handle
+SZG_CERT_SKETCH_TOPK_COLLECT = 6   # top-k of large k through the sketch (option sketch_topk_collect): sample bound + collect
 (SZG_CERT_KEYS_SINGLE, SZG_CERT_KEYS_SHARED_INT8, SZG_CERT_KEYS_SHARED_BF16, SZG_CERT_KEYS_BF16_BAND,
  SZG_CERT_KEYS_BF16_RESCORED) = range(5)
 SZG_CERT_ENTRY_NO_KEY = 1
@@ -127,6 +130,15 @@ class SzgStats(ctypes.Structure):
         ("sketch_radius_queries", ctypes.c_uint64),
         ("sketch_radius_fallbacks", ctypes.c_uint64),
     ]
+
+
+class SzgSketchTopkStats(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_uint64) for name in ("queries", "fallbacks", "sample_rows", "candidates", "overflows")]
+
+
+class SzgSamplePlan(ctypes.Structure):
+    _fields_ = ([(name, ctypes.c_int32) for name in ("serves", "stride", "blocks", "reserved")] +
+                [(name, ctypes.c_uint64) for name in ("tiles", "sample_rows", "slots", "key_bytes", "cap", "lds_bytes")])
 
 
 class SzgScanPlan(ctypes.Structure):
@@ -437,6 +449,11 @@ def load():
         L.szg_debug_scan_masked.argtypes = [ctypes.c_int] * 15 + [ctypes.POINTER(SzgScanMaskedPlan)]
         L.szg_debug_sketch_masked.restype = ctypes.c_int
         L.szg_debug_sketch_masked.argtypes = [vp, ctypes.POINTER(SzgSketchMaskedInfo)]
+    if hasattr(L, "szg_index_sketch_topk_stats"):
+        L.szg_index_sketch_topk_stats.restype = ctypes.c_int
+        L.szg_index_sketch_topk_stats.argtypes = [vp, ctypes.POINTER(SzgSketchTopkStats)]
+        L.szg_debug_sample_plan.restype = ctypes.c_int
+        L.szg_debug_sample_plan.argtypes = [ctypes.c_uint64] + [ctypes.c_int] * 5 + [ctypes.POINTER(SzgSamplePlan)]
     if hasattr(L, "szg_debug_scan_collect"):
         L.szg_debug_scan_collect.restype = ctypes.c_int
         L.szg_debug_scan_collect.argtypes = ([ctypes.c_int] * 10 + [ctypes.POINTER(ctypes.c_int32)] * 3 +

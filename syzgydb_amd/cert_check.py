@@ -31,6 +31,18 @@ certificate, only completeness; with the sketch state check() asserts K_s on the
     S_r  D >= radius + slack for the radius the test passed, and every eligible row with distance <= radius is among
          the record's entries or is an exception row
 
+Top-k searches of large k through the sketch (option sketch_topk_collect, pass SZG_CERT_SKETCH_TOPK_COLLECT) find their
+radius from a sample and then run that radius search: with the sketch state and the oracle's distances check() asserts
+K_s, C_s and T as above on every record that carries a sweep (thr finite; an entry without a key is an exception row or
+one of the query's first k eligible rows) and
+
+    P    at least k eligible sketched rows have a real-number sketch key <= kmax (U), in LD where the case is small
+    R    thr_min (tau) >= the sketch distance kmax implies -- acos(clamp(-kmax)) / pi (cosine), gscale sqrt(max(kmax, 0))
+         / 255 (Euclid), in LD -- plus slack
+    S_k  D >= thr_min (1 + 1e-9) + slack, and every eligible row at reference distance <= thr_min is among the
+         record's entries or is an exception row
+    F    a certified record's k-th oracle distance over the eligible rows is <= thr_min
+
 Candidates the kernels force in carry no bound and are skipped and counted: cosine keys <= -1.5, rows with a non-finite
 element or an overflowing norm, keys clamped to 3e38.  A zero cosine query claims no bound at all.
 """
@@ -42,8 +54,10 @@ from . import _lib
 
 PASS_NAMES = {_lib.SZG_CERT_TOPK: "topk", _lib.SZG_CERT_SKETCH: "sketch", _lib.SZG_CERT_ESCALATION: "escalation",
               _lib.SZG_CERT_RADIUS_SINGLE: "radius", _lib.SZG_CERT_RADIUS_SHARED: "radius-shared",
-              _lib.SZG_CERT_SKETCH_RADIUS: "sketch-radius"}
-SKETCH_PASSES = (_lib.SZG_CERT_SKETCH, _lib.SZG_CERT_SKETCH_RADIUS)   # their keys are keys of the rows' sketches
+              _lib.SZG_CERT_SKETCH_RADIUS: "sketch-radius", _lib.SZG_CERT_SKETCH_TOPK_COLLECT: "sketch-topk-collect"}
+# their keys are keys of the rows' sketches
+SKETCH_PASSES = (_lib.SZG_CERT_SKETCH, _lib.SZG_CERT_SKETCH_RADIUS, _lib.SZG_CERT_SKETCH_TOPK_COLLECT)
+COLLECT_SKETCH_PASSES = (_lib.SZG_CERT_SKETCH_RADIUS, _lib.SZG_CERT_SKETCH_TOPK_COLLECT)   # ... collected under a threshold
 KEYS_NAMES = {-1: "-", _lib.SZG_CERT_KEYS_SINGLE: "Single", _lib.SZG_CERT_KEYS_SHARED_INT8: "SharedInt8",
               _lib.SZG_CERT_KEYS_SHARED_BF16: "SharedBf16", _lib.SZG_CERT_KEYS_BF16_BAND: "Bf16Band",
               _lib.SZG_CERT_KEYS_BF16_RESCORED: "Bf16Rescored"}
@@ -184,7 +198,8 @@ def check(corpus, Q, recs, ents, dropped, eligible=None, dists=None, margins=Non
              gscale sqrt(max(thr_min, 0)) / 255 (Euclid), in LD, plus that expression's own rounding
 
     and, for every sketch-radius record (which needs sketch=, dists= and radii=, the radius the test passed per query):
-    K_s, C_s, T and S_r as the module's docstring states them."""
+    K_s, C_s, T and S_r as the module's docstring states them; for every sketch-topk-collect record (sketch= and dists=):
+    P and R where kmax is finite, K_s, C_s, T and S_k where the record carries a sweep, F where it is certified."""
     Q = np.atleast_2d(np.asarray(Q, dtype=np.float64))
     nq, n = Q.shape[0], corpus.n
     assert dropped == 0, ("the trace dropped records", dropped, what)
@@ -264,8 +279,40 @@ def check(corpus, Q, recs, ents, dropped, eligible=None, dists=None, margins=Non
             assert sketch is not None and dists is not None and radii is not None, \
                 "sketch-radius records need the sketch state, the oracle's distances and the radii"
             assert not zero_q[qi], ("a zero cosine query is handed over, never recorded", where)
+        topk_c = p == _lib.SZG_CERT_SKETCH_TOPK_COLLECT
+        if topk_c:
+            assert sketch is not None and dists is not None, \
+                "sketch-topk-collect records need the sketch state and the oracle's distances"
+            k = int(rec["k"])
+            assert k >= 1 and rec["certified"] in (0, 1), ("a sketch-topk-collect record without k or its verdict", where)
+            if zero_q[qi]:
+                assert rec["certified"] == 0 and len(e) == 0, ("a zero cosine query is handed over", where)
+            elig_s = eligible[qi] & in_range & ~is_exc & np.isfinite(real_s[qi])
+            if np.isfinite(rec["kmax"]) and not zero_q[qi]:
+                kmax, tau = float(rec["kmax"]), float(rec["thr_min"])
+                # ---- P
+                under = int((elig_s & (real_s[qi] - err_s[qi] <= kmax)).sum())
+                assert under >= k, ("P: fewer than k eligible sketched rows with a real-number sketch key <= kmax", where,
+                                    "kmax", kmax, "rows under it", under, "k", k)
+                # ---- R
+                if euclid_s:
+                    implied = LD(gscale) * np.sqrt(LD(max(kmax, 0.0))) / LD(255)
+                else:
+                    implied = np.arccos(LD(max(-1.0, min(1.0, -kmax)))) / PI
+                implied = float(implied)
+                assert tau >= implied + float(rec["slack"]) - 4 * np.finfo(np.float64).eps * (implied + float(rec["slack"])), (
+                    "R: thr_min below the distance kmax implies plus slack", where, tau, implied, float(rec["slack"]), kmax)
+            # ---- F
+            if rec["certified"] == 1:
+                assert np.isfinite(rec["thr"]) and np.isfinite(rec["kmax"]), ("a certified record without its sweep", where)
+                d_el = dists[qi][eligible[qi] & in_range]
+                d_el = np.sort(d_el[~np.isnan(d_el)])
+                assert d_el.size >= k and d_el[k - 1] <= rec["thr_min"], (
+                    "F: the k-th oracle distance is above thr_min", where, float(rec["thr_min"]),
+                    float(d_el[k - 1]) if d_el.size >= k else None)
         if p in SKETCH_PASSES and sketch is not None and not zero_q[qi] and \
-                (p == _lib.SZG_CERT_SKETCH_RADIUS or np.isfinite(rec["thr_min"])):
+                (p == _lib.SZG_CERT_SKETCH_RADIUS or (topk_c and np.isfinite(rec["thr"])) or
+                 (p == _lib.SZG_CERT_SKETCH and np.isfinite(rec["thr_min"]))):
             lb = float(rec["thr_min"])
             s_real, s_err = real_s[qi, rows], err_s[qi, rows]
             forced = keyed & (~np.isfinite(s_real) | (key >= TAKE_ALL) | ((key <= -1.5) if not euclid_s else False))
@@ -283,7 +330,7 @@ def check(corpus, Q, recs, ents, dropped, eligible=None, dists=None, margins=Non
                 margins.note(("sketch K_s", kind[1], kind[2], 8, corpus.metric), float((off / eps).max()), int(ok.sum()))
             left = eligible[qi] & in_range & ~is_exc & np.isfinite(real_s[qi])
             left[rows[keyed]] = False
-            if p == _lib.SZG_CERT_SKETCH_RADIUS:
+            if p in COLLECT_SKETCH_PASSES:
                 # ---- C_s
                 thr, r_eps = float(rec["thr"]), float(rec["eps"])
                 assert (key[keyed] <= thr).all(), ("C_s: a collected sketch key above the threshold", where, thr,
@@ -298,13 +345,31 @@ def check(corpus, Q, recs, ents, dropped, eligible=None, dists=None, margins=Non
                 inel = ~eligible[qi, rows]
                 assert not inel.any(), ("C_s: a row that is not eligible was collected", where, rows[inel][:8])
                 assert not is_exc[rows[keyed]].any(), ("C_s: a row without a usable sketch among the keyed entries", where)
-                assert is_exc[rows[~keyed]].all(), ("C_s: an entry without a key that is no exception row", where)
+                beside = is_exc[rows[~keyed]]
+                if topk_c:   # (the query's first k eligible rows are staged beside the exception rows)
+                    first_k = np.zeros(n, dtype=bool)
+                    first_k[np.flatnonzero(eligible[qi])[:k]] = True
+                    beside = beside | first_k[rows[~keyed]]
+                assert beside.all(), ("C_s: an entry without a key that is no exception row", where)
                 # ---- T
                 D = LD(float(rec["D"]))
                 assert np.isfinite(float(D)) and (euclid_s or float(D) < 1.0), ("T: a radius that is handed over was recorded", where)
                 implied = float((LD(255) * D / LD(gscale)) ** 2 if euclid_s else -np.cos(PI * D))
                 assert thr - r_eps >= implied - 4 * np.finfo(np.float64).eps * abs(implied), (
                     "T: thr - eps below the key the sketch-distance radius implies", where, thr, r_eps, implied, float(D))
+                if topk_c:
+                    # ---- S_k
+                    tau = float(rec["thr_min"])
+                    assert rec["D"] >= tau * (1.0 + 1e-9) + rec["slack"], ("S_k: the sketch-distance radius does not cover "
+                                                                         "thr_min (1 + 1e-9) + slack", where, float(rec["D"]),
+                                                                         tau, float(rec["slack"]))
+                    d = dists[qi]
+                    hit = eligible[qi] & in_range & (d <= tau)
+                    hit[rows] = False
+                    bad = np.flatnonzero(hit & ~is_exc)
+                    assert bad.size == 0, ("S_k: a row within thr_min is neither an entry nor an exception row", where, tau,
+                                           "rows", bad[:8], "dist", d[bad[:8]])
+                    continue
                 # ---- S_r
                 radius = float(np.broadcast_to(np.asarray(radii, dtype=np.float64), (nq,))[qi])
                 assert rec["D"] >= radius + rec["slack"], ("S_r: the sketch-distance radius does not cover radius + slack", where,

@@ -243,6 +243,31 @@ hipError_t launch_scan_mxm_m0(const ScanMaskedArgs &s, const ScanVariant &v, int
 hipError_t launch_scan_mxm_m1(const ScanMaskedArgs &s, const ScanVariant &v, int grid, int block, size_t lds, hipStream_t stream);
 hipError_t launch_scan_mxms_m0(const ScanMaskedArgs &s, const ScanVariant &v, int grid, int block, size_t lds, hipStream_t stream);
 hipError_t launch_scan_mxms_m1(const ScanMaskedArgs &s, const ScanVariant &v, int grid, int block, size_t lds, hipStream_t stream);
+// ---- kernels_sample_mx.hip: the sample pass of a top-k search of large k through the sketch (option sketch_topk_collect;
+// sample_plan.h has the arithmetic) ----------------------------------------------------------------------------------
+// One launch scores sample tiles 0 .. tiles - 1 -- tile j of the sample is tile j * stride of the rows -- against the
+// launch's 1 .. 16 nb queries (nb = 1, 2 column blocks) and writes keys[q * slots + 16 j + t], the ordered key of row t of
+// the tile for query q, 0xFFFFFFFF where the row does not exist or is not eligible (a.live_bits; a.allow_bits: query q
+// reads a.allow_bits + q * a.allow_stride).  Of `a` the rows, their layout and norms, the queries, their constants and the
+// masks are read; tiled 8-bit rows in whole 64-byte steps, two-plane queries, an image of nb blocks within 64 KiB of LDS
+// (sample_mx_lds_bytes) -- everything else is hipErrorInvalidValue.
+struct SampleArgs {
+    ScanArgs a;
+    uint32_t stride, tiles, slots;  // slots = 16 * tiles
+    uint32_t *keys;
+};
+size_t sample_mx_lds_bytes(uint32_t steps, int nb);
+hipError_t launch_sample_mx(int metric, const SampleArgs &s, int nb, int grid, int block, hipStream_t stream);
+// One block per query: out[2 q] = the rank[q]-th smallest (1-based) of keys[q * slots .. + slots), out[2 q + 1] = the
+// slots that hold a key; fewer of them than the rank (or rank 0): out[2 q] = 0xFFFFFFFF.
+struct SampleSelectArgs {
+    const uint32_t *keys;
+    uint32_t slots;
+    uint32_t rank[kMatrixWideQueries];
+    uint32_t *out;
+};
+hipError_t launch_sample_select(const SampleSelectArgs &s, int n_queries, hipStream_t stream);
+
 // ---- shared (multi-query) sweeps (mq_device.h, kernels_mq*.hip): every row width, cosine and Euclidean ----------
 // queries per shared sweep: 48 (3 blocks of 16) for the int8 sweeps (4- and 8-bit rows), whose LDS images are 2-4
 // bytes per element and query; 96 for the bfloat16 sweeps (16-, 32- and 64-bit rows, and 8-bit rows in batches of

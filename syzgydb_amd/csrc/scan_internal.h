@@ -9,6 +9,8 @@
 //   scan_mq.cpp       shared (multi-query) sweeps on the matrix cores
 //   scan_sketch.cpp   8-bit sketch pre-pass
 //   scan_radius.cpp   radius search (single, batch, coalesced; through the sketch: sketch_radius; collect_plan.h: its buffers)
+//                     and top-k of large k through the sketch as a sample pass + that collect core (sketch_topk_collect;
+//                     sample_plan.h: its arithmetic; kernels_sample_mx.hip: its kernels)
 //   scan_comm.cpp     one-process-per-GPU exchange (RCCL all-gather + merge)
 //   scan_mask.cpp     device-resident filter masks (szg_mask) and the searches that take them
 //   scan_column.cpp   resident metadata columns (szg_column): comparisons against constants that write masks
@@ -456,6 +458,10 @@ struct szg_index {
     int sketch_f64 = 0;       // float64 handles (the reference's default quantization) keep an 8-bit sketch too, an eighth of
                               // their rows' bytes, under every rule of float32 handles: 0 = never (the default while the
                               // option soaks: such a handle keeps no sketch and allocates nothing more), 1 = always
+    int sketch_topk_collect = 0;  // top-k calls that take a sweep per query with a k the pre-pass does not serve go through
+                              // the sketch as a sample pass and a collect sweep (scan_radius.cpp, SketchTopkCall): 0 = never
+                              // (the default while the option soaks), 1 = wherever the sample plan serves every shard
+    szg_sketch_topk_stats sk_topk{};  // what that path served (stats_mu; szg_index_sketch_topk_stats, szg_reset_stats)
     bool is_sketch = false;   // this index is the internal sketch of a float32 (or float64) handle: its keys only bound
     int tie_mode = 0;         // 0: exact full replay on ties/NaN, 1: keep the fast answer
     int serialize_scans = 1;  // scan launches of a shard never overlap each other
@@ -733,6 +739,15 @@ int search_radius_impl(szg_index *ix, const double *queries, int n_queries, cons
 int search_radius_any(szg_index *ix, const double *queries, int n_queries, const double *radii,
                       const uint64_t *const *masks, std::vector<std::vector<HeapItem>> *results,
                       const szg_mask *const *handles = nullptr);
+
+// Top-k of large k through the sketch (option sketch_topk_collect): does the sample plan serve every shard of the
+// handle's sketch index for k (sample_plan.h)?  Called with the sketch in sync.
+bool sketch_topk_collect_serves(const szg_index *ix, int k);
+// ... and the call itself: a sample pass, the radius it implies, the collect core at that radius, the reference's heap
+// replayed over what was collected; the queries it does not settle go to search_topk_impl as ONE call
+int search_topk_collect(szg_index *ix, const double *queries, int n_queries, int k, const uint64_t *allow_bits,
+                        uint64_t *out_rows, double *out_dist, int32_t *out_count, const uint64_t *const *allow_ptrs,
+                        const szg_mask *const *handles);
 
 #ifndef SZG_BF16_8BIT_DEFAULT
 #define SZG_BF16_8BIT_DEFAULT 1  // tiled 8-bit rows take the bfloat16 sweep for top-k batches (SZG_BF16_8BIT=0: the int8 sweep)

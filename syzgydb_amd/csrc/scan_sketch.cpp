@@ -689,6 +689,10 @@ int search_topk_any(szg_index *ix, const double *queries, int n_queries, int k, 
     const bool shared = ix->multi_query && n_queries >= ix->mq_min;
     if (!shared && sketch_applies(ix, k))
         return search_topk_sketch(ix, queries, n_queries, k, allow_bits, out_rows, out_dist, out_count, allow_ptrs, handles);
+    // a k beyond the pre-pass's lists: a sample pass and a collect sweep of the sketch (scan_radius.cpp), where the option
+    // is on and the sample plan serves the handle -- else the path the call takes without the option
+    if (ix->sketch_topk_collect && !shared && n_queries >= 1 && k >= 1 && sketch_applies_rows(ix))
+        return search_topk_collect(ix, queries, n_queries, k, allow_bits, out_rows, out_dist, out_count, allow_ptrs, handles);
     return search_topk_impl(ix, queries, n_queries, k, allow_bits, out_rows, out_dist, out_count, allow_ptrs, handles);
 }
 

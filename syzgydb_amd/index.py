@@ -939,6 +939,19 @@ class ScanIndex:
         check(self._L.szg_debug_sketch_masked(self._h, ctypes.byref(info)), "szg_debug_sketch_masked")
         return {name: int(getattr(info, name)) for name, _ in _lib.SzgSketchMaskedInfo._fields_}
 
+    def sketch_topk_stats(self):
+        """What top-k searches of large k through the sketch (option sketch_topk_collect) served on the handle since
+        reset_stats (szg_index_sketch_topk_stats): queries settled, fallbacks handed to the full-precision path, sample_rows
+        scored (per launch), candidates gathered for the settled queries, overflows among the fallbacks."""
+        s = _lib.SzgSketchTopkStats()
+        check(self._L.szg_index_sketch_topk_stats(self._h, ctypes.byref(s)), "szg_index_sketch_topk_stats")
+        return {name: int(getattr(s, name)) for name, _ in _lib.SzgSketchTopkStats._fields_}
+
+    @staticmethod
+    def sample_plan(shard_rows, k, n_queries=1, dim=768, quant_bits=8, planes=2):
+        """Host-only test hook: sample_plan() of this module."""
+        return sample_plan(shard_rows, k, n_queries, dim, quant_bits, planes)
+
     def sketch_rows(self, first_row=0, n_rows=None):
         """Test hook: (sketch rows [first_row, first_row + n_rows) in the packed 8-bit form, uint8[n_rows, dim]; the live
         words of the sketch shards, uint64[ceil(sketch rows / 64)]) -- szg_debug_sketch_rows; never a sync."""
@@ -1110,10 +1123,24 @@ def merge_short_plan(n_lists, m, kp):
     return {"fits": bool(fits.value), "sorts": sorts.value}
 
 
+def sample_plan(shard_rows, k, n_queries=1, dim=768, quant_bits=8, planes=2):
+    """Host-only test hook (szg_debug_sample_plan): the sample plan of a top-k search through the sketch (option
+    sketch_topk_collect) for one shard of shard_rows rows -- serves, stride (tiles of 16 rows), blocks (column blocks of 16
+    queries per row read), tiles, sample_rows, slots (key slots per query), key_bytes, cap (entries per query the collect
+    buffers start with) and lds_bytes; every field 0 where the shard is not served."""
+    L = _lib.load()
+    out = _lib.SzgSamplePlan()
+    check(L.szg_debug_sample_plan(int(shard_rows), int(k), int(n_queries), int(dim), int(quant_bits), int(planes),
+                                  ctypes.byref(out)), "szg_debug_sample_plan")
+    d = {name: int(getattr(out, name)) for name, _ in _lib.SzgSamplePlan._fields_ if name != "reserved"}
+    d["serves"] = bool(d["serves"])
+    return d
+
+
 def option_check(name, value):
     """Host-only test hook (no device needed): raises SzgError where ScanIndex.set_option would refuse `value` for the
     one-sweep kernel's option `name` (scan_group, scan_group_ring, scan_norms, sketch_planes, sketch_matrix, sketch_select,
-    sketch_wide, sketch_share, sketch_bulk, sketch_radius, sketch_masked, sketch_f64)."""
+    sketch_wide, sketch_share, sketch_bulk, sketch_radius, sketch_masked, sketch_f64, sketch_topk_collect)."""
     L = _lib.load()
     check(L.szg_debug_option_check(name.encode(), int(value)), "szg_debug_option_check")
 
