@@ -300,6 +300,61 @@ func columnSetRows(col *C.szg_column, rows []uint64, values unsafe.Pointer, pres
 	return C.szg_column_set_rows(col, u64ptr(rows), values, u64ptr(present), C.uint64_t(len(rows))) == C.SZG_OK
 }
 
+// ---- vectors out to device memory, queries from it: thin wrappers again.  desc points at a C.szg_dev_vectors the
+// caller filled in (device pointer, SZG_SRC_* dtype, device ordinal, rows, row stride in elements); it lives in C
+// memory or is pinned for the call.  Reads: called under c.mutex.RLock like the searches.
+
+// fetchRowsDev is szg_index_fetch_rows_dev: stored row rows[i] -- or, with rows == nil, row firstRow + i, n of them --
+// decoded into row i of the caller's device memory.
+func (m *gpuMirror) fetchRowsDev(rows []uint64, firstRow, n uint64, desc unsafe.Pointer) bool {
+	if rows != nil {
+		n = uint64(len(rows))
+	}
+	return C.szg_index_fetch_rows_dev(m.h, u64ptr(rows), C.uint64_t(firstRow), C.uint64_t(n), (*C.szg_dev_vectors)(desc)) == C.SZG_OK
+}
+
+// searchTopKDev is szg_search_topk_dev: nq queries in device memory (source row srcRows[i], or row i with srcRows ==
+// nil), one mask for all of them or none; rows and dist hold nq x k entries, count nq.
+func (m *gpuMirror) searchTopKDev(desc unsafe.Pointer, srcRows []uint64, nq, k int, mask *C.szg_mask, rows []uint64,
+	dist []float64, count []int32) bool {
+	var masks **C.szg_mask
+	nMasks := 0
+	if mask != nil {
+		masks, nMasks = &mask, 1
+	}
+	return C.szg_search_topk_dev(m.h, (*C.szg_dev_vectors)(desc), u64ptr(srcRows), C.int(nq), C.int(k), masks, C.int(nMasks),
+		u64ptr(rows), (*C.double)(unsafe.Pointer(&dist[0])), (*C.int32_t)(unsafe.Pointer(&count[0]))) == C.SZG_OK
+}
+
+// searchRadiusDev is szg_search_radius_dev, grown and repeated on SZG_E_TRUNCATED as searchBatch does: the hits of
+// query i are rows[off[i]:off[i+1]] and dist[off[i]:off[i+1]].
+func (m *gpuMirror) searchRadiusDev(desc unsafe.Pointer, srcRows []uint64, radii []float64, mask *C.szg_mask) (rows []uint64,
+	dist []float64, off []uint64, ok bool) {
+	nq := len(radii)
+	if nq == 0 {
+		return nil, nil, []uint64{0}, true
+	}
+	var masks **C.szg_mask
+	nMasks := 0
+	if mask != nil {
+		masks, nMasks = &mask, 1
+	}
+	off = make([]uint64, nq+1)
+	capacity := 1 << 16
+	for {
+		rows = make([]uint64, capacity)
+		dist = make([]float64, capacity)
+		rc := C.szg_search_radius_dev(m.h, (*C.szg_dev_vectors)(desc), u64ptr(srcRows), C.int(nq),
+			(*C.double)(unsafe.Pointer(&radii[0])), masks, C.int(nMasks), u64ptr(rows), (*C.double)(unsafe.Pointer(&dist[0])),
+			C.uint64_t(capacity), u64ptr(off))
+		if rc == C.SZG_E_TRUNCATED {
+			capacity = int(off[nq])
+			continue
+		}
+		return rows, dist, off, rc == C.SZG_OK
+	}
+}
+
 // columnWhereDFA is szg_mask_where_dfa: the rows of a text column whose bytes a byte automaton accepts, as a mask.
 // The Go side owns the pattern language: a MATCHES leaf (query/compiler.go:420-431) compiles its pattern with
 // regexp/syntax (syntax.Parse(pattern, syntax.Perl), Simplify, syntax.Compile), determinises the program over bytes

@@ -493,22 +493,79 @@ int szg_column_set_rows(szg_column *c, const uint64_t *rows, const void *values,
  *   the source as soon as the call has returned.
  * Memory: the encoder reads the caller's memory in place; nothing is copied and the staging block does not grow for
  *   the source.  The overwrite form still stages its linear block of encoded rows (at most 64 MiB) and its lists.
- * There is no _dev form of szg_index_load (an append to an empty handle covers it) and none of the queries.
+ * There is no _dev form of szg_index_load (an append to an empty handle covers it).  The same descriptor serves the
+ *   two reverse directions below: szg_index_fetch_rows_dev WRITES through `data` (the const is the ingest's), and the
+ *   _dev searches read their queries through it.
  */
 #define SZG_SRC_F64 0
 #define SZG_SRC_F32 1
 #define SZG_SRC_F16 2
 #define SZG_SRC_BF16 3
 typedef struct szg_dev_vectors {
-    const void *data;      /* device memory, aligned to its element size */
+    const void *data;      /* device memory, aligned to its element size (szg_index_fetch_rows_dev writes through it) */
     int dtype;             /* SZG_SRC_* */
     int device;            /* HIP ordinal the memory lives on */
-    uint64_t n_rows;       /* source rows available */
+    uint64_t n_rows;       /* source rows available (fetch: destination rows available) */
     uint64_t row_stride;   /* elements from one source row to the next, >= dim */
 } szg_dev_vectors;
 int szg_index_append_dev(szg_index *ix, const szg_dev_vectors *src, const uint64_t *src_rows, uint64_t n_rows);
 int szg_index_overwrite_rows_dev(szg_index *ix, const uint64_t *rows, const szg_dev_vectors *src,
                                  const uint64_t *src_rows, uint64_t n_rows);
+
+/* ---- vectors out to device memory, queries from it (added under ABI 4, additive) ----
+ *
+ * szg_index_fetch_rows_dev: stored vectors decoded into the caller's device memory -- the vector half of GetDocument
+ * for whatever follows a search on the card (a re-ranker, diversification, clustering, a hit's vector as the next
+ * query) -- without the packed bytes, the host decode and the upload szg_index_read_rows would take.
+ * Rows: entry i is stored row rows[i]; `rows` is a HOST list in any order, duplicates allowed (this is a read), numbered
+ *   as searches return them (local + row base).  rows == NULL: entry i is row first_row + i (first_row is ignored when a
+ *   list is given).  Tombstoned rows are served as stored, as szg_index_read_rows serves them.  The sketch index is
+ *   never read.
+ * What is written: dst->data[i * row_stride + e], e < the handle's dimension, receives the reference's decodeVector
+ *   value of element e of entry i, converted to dst->dtype:
+ *     SZG_SRC_F64   that float64, bit for bit (what decoding the bytes of szg_index_read_rows gives);
+ *     SZG_SRC_F32   that float64 converted by ONE round-to-nearest-even (a C cast); for a 32-bit handle the stored float;
+ *     SZG_SRC_F16 / SZG_SRC_BF16   the float32 value above converted once more, round-to-nearest-even (two roundings,
+ *                   what a cast chain double -> float -> half gives);
+ *   overflow goes to +-inf and NaN stays NaN, as IEEE 754 says (which NaN is not promised).  Elements e >= dimension of
+ *   a destination row (row_stride > dimension: a column slice of a wider matrix) and destination rows >= n_rows are not
+ *   touched.
+ * Refusals, all decided on the host before any launch (a refused call writes nothing), with the ingest's codes and
+ *   words, `dst` checked as a source of n_rows rows: a NULL handle or descriptor; an unknown dtype; row_stride < the
+ *   dimension; data not aligned to its element size; n_rows > dst->n_rows; a device ordinal out of range; not device
+ *   memory of `device`; destination rows that reach past the allocation (SZG_E_RANGE).  A listed row, or first_row +
+ *   n_rows, past the handle's rows is SZG_E_RANGE.  A destination on a device other than that of any shard the rows
+ *   reach is SZG_E_INVALID, "destination on another device" -- no peer copy is made; shards that share the
+ *   destination's device (devices = {0, 0}) are served.  n_rows == 0 checks the descriptor only.
+ * Synchronisation: the call synchronises the destination's device before it writes and returns with the values written
+ *   and visible to any stream of that device.
+ * Memory: the only upload is the list, 8 bytes per row in chunks of 64 MiB, through a shard's staging block; the kernel
+ *   writes the caller's memory in place.
+ * Threads: a read, like szg_index_read_rows -- beside searches, not beside mutations.
+ *
+ * szg_search_topk_dev / szg_search_radius_dev: szg_search_topk_masked / szg_search_radius_masked for queries that lie in
+ * device memory.  Query i is source row src_rows[i] (a HOST list or NULL = row i, exactly as in the ingest), every
+ * element widened to float64 exactly, and the answer is what the masked call returns for those float64 values -- ids,
+ * float64 distances, counts, offsets, order, SZG_E_TRUNCATED -- on every path and under every option, because after
+ * the conversion it IS that call: a small kernel on the queries' device writes the dense n_queries x dim float64 batch
+ * into a buffer the handle keeps there, one copy brings it into pinned host memory, and the host prepares the queries
+ * as ever (preparing them on the card is not part of this).  Outputs are host arrays.
+ * The queries may lie on ANY device of the process: they are copied, not swept, so nothing is "on another device".
+ * Refusals: the descriptor's are the ingest's (n_queries source rows); everything else -- k, radii, masks, stale masks,
+ *   capacity, NULL outputs -- is refused by the masked call as today, after the conversion.
+ * Synchronisation: the call synchronises the queries' device before it reads; the caller may rewrite the queries once
+ *   the call has returned.
+ * Threads: as the masked searches, except that the _dev searches of one handle take turns (they share the handle's
+ *   conversion buffers for the length of a call).
+ */
+int szg_index_fetch_rows_dev(szg_index *ix, const uint64_t *rows, uint64_t first_row, uint64_t n_rows,
+                             const szg_dev_vectors *dst);
+int szg_search_topk_dev(szg_index *ix, const szg_dev_vectors *queries, const uint64_t *src_rows, int n_queries, int k,
+                        const szg_mask *const *masks, int n_masks,
+                        uint64_t *out_rows, double *out_dist, int32_t *out_count);
+int szg_search_radius_dev(szg_index *ix, const szg_dev_vectors *queries, const uint64_t *src_rows, int n_queries,
+                          const double *radii, const szg_mask *const *masks, int n_masks,
+                          uint64_t *out_rows, double *out_dist, uint64_t capacity, uint64_t *out_offsets);
 
 /*
  * The reference's float64 distance (c.distance, collection.go:596, :812-832) from

@@ -54,6 +54,8 @@ EXPORTS = [
     "szg_column_set_rows", "szg_debug_bulk_plan",
     # ingest from device memory (added under ABI 4)
     "szg_index_append_dev", "szg_index_overwrite_rows_dev",
+    # vectors out to device memory, queries from it (added under ABI 4)
+    "szg_index_fetch_rows_dev", "szg_search_topk_dev", "szg_search_radius_dev",
     # host-only test hook
     "szg_debug_scan_plan", "szg_debug_scan_group", "szg_debug_reorder_plan", "szg_debug_option_check",
     "szg_debug_scan_group_ring", "szg_debug_merge_short_plan", "szg_debug_scan_matrix",
@@ -375,6 +377,16 @@ def load():
         L.szg_index_append_dev.argtypes = [vp, ctypes.POINTER(SzgDevVectors), u64p, ctypes.c_uint64]
         L.szg_index_overwrite_rows_dev.restype = ctypes.c_int
         L.szg_index_overwrite_rows_dev.argtypes = [vp, u64p, ctypes.POINTER(SzgDevVectors), u64p, ctypes.c_uint64]
+    if hasattr(L, "szg_index_fetch_rows_dev"):   # (an older build for an A/B run serves vectors and queries on the host only)
+        i32p = ctypes.POINTER(ctypes.c_int32)
+        L.szg_index_fetch_rows_dev.restype = ctypes.c_int
+        L.szg_index_fetch_rows_dev.argtypes = [vp, u64p, ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(SzgDevVectors)]
+        L.szg_search_topk_dev.restype = ctypes.c_int
+        L.szg_search_topk_dev.argtypes = [vp, ctypes.POINTER(SzgDevVectors), u64p, ctypes.c_int, ctypes.c_int,
+                                          ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, u64p, f64p, i32p]
+        L.szg_search_radius_dev.restype = ctypes.c_int
+        L.szg_search_radius_dev.argtypes = [vp, ctypes.POINTER(SzgDevVectors), u64p, ctypes.c_int, f64p,
+                                            ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, u64p, f64p, ctypes.c_uint64, u64p]
     L.szg_comm_unique_id.restype = ctypes.c_int
     L.szg_comm_unique_id.argtypes = [u8p]
     L.szg_comm_create.restype = ctypes.c_int

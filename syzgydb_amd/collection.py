@@ -270,6 +270,18 @@ class Collection:
         vec = codec.decode_rows(data, self.DimensionCount, self.Quantization)[0]
         return Document(ID=int(id), Vector=vec, Metadata=self._meta[row])
 
+    def FetchVectors(self, ids, out):
+        """The vector half of GetDocument for many ids, into device memory (not in the reference): row i of the 2-D
+        device tensor `out` (ScanIndex.fetch_into) receives the stored vector of ids[i], decoded on the card.  An
+        unknown id is GetDocument's error, raised before anything is written.  Returns `out`."""
+        rows = []
+        for id in ids:
+            row = self._row_of.get(int(id))
+            if row is None:
+                raise KeyError("record not found")  # spanfile.go:516
+            rows.append(row)
+        return self._index.fetch_into(out, rows=rows)
+
     def UpdateDocument(self, id: int, new_metadata: bytes):
         row = self._row_of.get(int(id))
         if row is None:
@@ -809,6 +821,36 @@ class Collection:
         else:
             r, d, c = self._index.search_topk(Q, args_list[0].K, masks=masks)
             hits = [(r[i, : c[i]], d[i, : c[i]]) for i in range(len(args_list))]
+        for rows, dist in hits:
+            res = [SearchResult(ID=self._id_of[int(row)], Metadata=self._meta[int(row)], Distance=float(dd))
+                   for row, dd in zip(rows, dist)]
+            out.append(SearchResults(Results=res, PercentSearched=100.0))
+        return out
+
+    def SearchBatchTensor(self, queries, K=0, Radius=0.0, Filter=None, Where=None, FilterKey=None) -> List[SearchResults]:
+        """SearchBatch for queries that lie in device memory (not in the reference): row i of the 2-D device tensor
+        `queries` (ScanIndex.search_topk_tensor) is query i, all with one K -- or one Radius, which as ever wins over K
+        -- and ONE filter for the whole batch.  The results are SearchBatch's for the same vectors widened to float64
+        on the host, PercentSearched included.  Listing mode (K == 0 and Radius == 0) has no vector and is refused."""
+        shape = tuple(queries.shape)
+        if len(shape) != 2 or shape[1] != self.DimensionCount:
+            raise ValueError("query length does not match the dimension %d: shape %r" % (self.DimensionCount, shape))
+        if not (Radius > 0 or K > 0):
+            raise ValueError("SearchBatchTensor: K > 0 or Radius > 0 (listing mode takes no vectors: Search)")
+        args = SearchArgs(K=K, Radius=Radius, Filter=Filter, Where=Where, FilterKey=FilterKey)
+        flt = self._search_filter(args)[0]  # (Filter and Where are exclusive: said before anything is searched)
+        n_records = len(self._row_of)
+        if n_records == 0:
+            return [SearchResults(Results=[], PercentSearched=0.0) for _ in range(shape[0])]
+        if self._order_stale:
+            self._resort()   # (as SearchBatch: deterministic mode re-pages first)
+        mask = self._search_handle(args) if (flt is not None or Where is not None) else None
+        if Radius > 0:
+            hits = self._index.search_radius_tensor(queries, Radius, masks=mask)
+        else:
+            r, d, c = self._index.search_topk_tensor(queries, K, masks=mask)
+            hits = [(r[i, : c[i]], d[i, : c[i]]) for i in range(shape[0])]
+        out = []
         for rows, dist in hits:
             res = [SearchResult(ID=self._id_of[int(row)], Metadata=self._meta[int(row)], Distance=float(dd))
                    for row, dd in zip(rows, dist)]

@@ -434,6 +434,22 @@ hipError_t launch_synth(int qbits, uint8_t *rows, RowLayout layout, uint64_t dst
 hipError_t launch_ingest(int qbits, uint8_t *rows, RowLayout layout, uint64_t dst_first_row, int dim, uint64_t n_rows,
                          const void *data, int src_type, uint64_t row_stride, const uint64_t *src_index, hipStream_t stream);
 
+// launch_ingest backwards (szg_index_fetch_rows_dev): entry i of the launch, i < n, is resident row src_first + i of
+// `rows` -- or, with `list` (a device array), row list[i] - list_base where that is below shard_rows; other entries
+// are skipped: they are another shard's -- and its dim elements are decoded exactly (decodeVector's float64), converted
+// to dst_type (SZG_SRC_*: float64 as it is, float32 by one round-to-nearest-even, float16 / bfloat16 from that float32
+// by one more) and stored at data[i * row_stride + e].  data is device memory of the rows' device, aligned to its
+// element; the 16-byte store form is taken where data and row_stride * sizeof(element) are multiples of 16.
+// n * ceil(dim * qbits / 128) must fit 2^39 (one launch).
+hipError_t launch_fetch(int qbits, const uint8_t *rows, RowLayout layout, int dim, uint64_t n, const uint64_t *list,
+                        uint64_t list_base, uint64_t shard_rows, uint64_t src_first, void *data, int dst_type,
+                        uint64_t row_stride, hipStream_t stream);
+
+// out[i * dim + e] = the float64 of element e of source row src_index[i] (a device array; nullptr: row i) of vectors
+// in device memory as launch_ingest takes them, widened exactly: a batch of queries for the host's preparation.
+hipError_t launch_widen_rows(double *out, int dim, uint64_t n, const void *data, int src_type, uint64_t row_stride,
+                             const uint64_t *src_index, hipStream_t stream);
+
 // Resident row norms (shared sweeps), out[first_row + i] for rows [first_row, first_row + n_rows) of the mirror:
 // 16-bit rows (linear): the float32 sum of n^2, n = 2v - 65535, over the row's real elements, as the direct bfloat16
 // sweep summed it; 8- and 4-bit rows (either layout): (float)(4 * sum (x'^2 + x')) + norm_bias, the int8 sweeps' norm.

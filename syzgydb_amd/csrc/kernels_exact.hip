@@ -9,6 +9,9 @@
 //    as encodeDocument/quantize (collection.go:713-743, quantization.go:5-23).
 //  * ingest_kernel: the same encoder over vectors the caller keeps in device memory (float64,
 //    float32, float16 or bfloat16; a row stride; an optional list of source rows).
+//  * fetch_kernel: the decoder the other way -- stored rows, by range or by list, decoded into the
+//    caller's device memory in any of the four types; widen_rows_kernel: query rows in device
+//    memory as one dense float64 batch.
 //  * repack_kernel: page-in transform between the reference's big-endian
 //    element encoding and the resident little-endian, 16-byte-pitched layout.
 //  * gather_rows_kernel: rows copied piece by piece from one resident (or linear)
@@ -475,21 +478,30 @@ template <>
 struct SrcElem<0> {  // SZG_SRC_F64
     typedef uint64_t bits;
     static __device__ __forceinline__ double widen(bits b) { return __longlong_as_double((long long)b); }
+    static __device__ __forceinline__ bits narrow(double v) { return (bits)__double_as_longlong(v); }
 };
 template <>
 struct SrcElem<1> {  // SZG_SRC_F32
     typedef uint32_t bits;
     static __device__ __forceinline__ double widen(bits b) { return (double)__uint_as_float(b); }
+    static __device__ __forceinline__ bits narrow(double v) { return __float_as_uint((float)v); }
 };
 template <>
 struct SrcElem<2> {  // SZG_SRC_F16
     typedef uint16_t bits;
     static __device__ __forceinline__ double widen(bits b) { return (double)(float)__builtin_bit_cast(_Float16, b); }
+    static __device__ __forceinline__ bits narrow(double v) { return __builtin_bit_cast(bits, (_Float16)(float)v); }
 };
 template <>
 struct SrcElem<3> {  // SZG_SRC_BF16
     typedef uint16_t bits;
     static __device__ __forceinline__ double widen(bits b) { return (double)__uint_as_float((uint32_t)b << 16); }
+    static __device__ __forceinline__ bits narrow(double v)
+    {
+        const uint32_t u = __float_as_uint((float)v);
+        if ((u & 0x7FFFFFFFu) > 0x7F800000u) return (bits)((u >> 16) | 0x0040u);  // NaN stays NaN, quiet
+        return (bits)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);                    // nearest, ties to even; overflow -> inf
+    }
 };
 
 template <int QBITS, int SRC>
@@ -542,6 +554,83 @@ __global__ __launch_bounds__(256) void ingest_kernel(uint8_t *dst, RowLayout lay
         }
     }
     *reinterpret_cast<uint4 *>(dst + piece_offset(lay, dst_first_row + row, j)) = make_uint4(w[0], w[1], w[2], w[3]);
+}
+
+// ---- egress to device memory (szg_index_fetch_rows_dev) ----------------------------------------
+// ingest_kernel read backwards: one thread per 16-byte piece of a resident row that holds elements, one 16-byte load,
+// decode_elem_piece on each of its E elements (the reference's decodeVector value, float64), SrcElem<DST>::narrow --
+// float64 as it is; float32 by one round-to-nearest-even convert; float16 / bfloat16 from that float32 by one more
+// -- and the store into the caller's memory: entry i of the launch goes to data[i * row_stride + e].
+// Entry i is resident row src_first + i, or, with a list (a device array of rows numbered from list_base), row
+// list[i] - list_base where that is a row of this shard (< shard_rows): a list that reaches several shards is
+// uploaded once and every shard's launch serves its own entries of it.
+// VEC (chosen on the host: `data` and row_stride * sizeof(element) are both multiples of 16): a full piece is stored
+// W = min(16, E * sizeof) bytes at a time; the last piece of a row, and everything where VEC is false, element by
+// element.  Elements at and past dim, and the padding of row_stride, are never written.
+template <int QBITS, int DST, bool VEC>
+__global__ __launch_bounds__(256) void fetch_kernel(const uint8_t *rows, RowLayout lay, int dim, uint64_t n,
+                                                    const uint64_t *list, uint64_t list_base, uint64_t shard_rows,
+                                                    uint64_t src_first, void *data, uint64_t row_stride)
+{
+    typedef typename SrcElem<DST>::bits bits_t;
+    constexpr int E = 128 / QBITS;                 // elements per 16-byte piece
+    constexpr int ES = (int)sizeof(bits_t);        // bytes per destination element
+    constexpr int W = E * ES < 16 ? E * ES : 16;   // bytes per wide store
+    constexpr int PER = W / ES;                    // elements per wide store
+    const uint32_t pieces = (uint32_t)((dim + E - 1) / E);
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint64_t i = t / pieces;
+    const uint32_t j = (uint32_t)(t - i * pieces);
+    if (i >= n) return;
+    uint64_t row = src_first + i;
+    if (list) {
+        row = list[i] - list_base;
+        if (row >= shard_rows) return;  // (another shard's entry; a row below list_base wraps past every count)
+    }
+    const uint4 v = *reinterpret_cast<const uint4 *>(rows + piece_offset(lay, row, j));
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+    bits_t out[E];
+#pragma unroll
+    for (int k = 0; k < E; k++)
+        out[k] = SrcElem<DST>::narrow(decode_elem_piece<QBITS>(reinterpret_cast<const uint8_t *>(w), k));
+    const int e0 = (int)j * E;
+    bits_t *p = static_cast<bits_t *>(data) + i * row_stride + (uint64_t)e0;
+    if (VEC && e0 + E <= dim) {
+#pragma unroll
+        for (int c = 0; c < E / PER; c++) {
+            uint32_t raw[W / 4];
+#pragma unroll
+            for (int x = 0; x < W / 4; x++) {
+                if constexpr (ES == 8) raw[x] = (uint32_t)(out[c * PER + (x >> 1)] >> (32 * (x & 1)));
+                else if constexpr (ES == 4) raw[x] = (uint32_t)out[c * PER + x];
+                else raw[x] = (uint32_t)out[c * PER + 2 * x] | ((uint32_t)out[c * PER + 2 * x + 1] << 16);
+            }
+            if constexpr (W == 16) reinterpret_cast<uint4 *>(p)[c] = make_uint4(raw[0], raw[1], raw[2], raw[3]);
+            else if constexpr (W == 8) reinterpret_cast<uint2 *>(p)[c] = make_uint2(raw[0], raw[1]);
+            else reinterpret_cast<uint32_t *>(p)[c] = raw[0];
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < E; k++) {
+            if (e0 + k < dim) p[k] = out[k];
+        }
+    }
+}
+
+// ---- queries from device memory (szg_search_topk_dev / szg_search_radius_dev) ------------------
+// The dense n x dim float64 batch of the listed source rows (src_index == nullptr: row i), every element widened
+// exactly as ingest_kernel widens it.  One thread per element: the reads of a row and the writes are contiguous.
+template <int SRC>
+__global__ __launch_bounds__(256) void widen_rows_kernel(double *out, int dim, uint64_t n, const void *data,
+                                                         uint64_t row_stride, const uint64_t *src_index)
+{
+    typedef typename SrcElem<SRC>::bits bits_t;
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint64_t i = t / (uint32_t)dim;
+    const uint32_t e = (uint32_t)(t - i * (uint32_t)dim);
+    if (i >= n) return;
+    const uint64_t from = src_index ? src_index[i] : i;
+    out[t] = SrcElem<SRC>::widen(static_cast<const bits_t *>(data)[from * row_stride + e]);
 }
 
 // ---- page-in transform --------------------------------------------------------
@@ -1031,6 +1120,70 @@ hipError_t launch_ingest(int qbits, uint8_t *rows, RowLayout lay, uint64_t dst_f
     case 64: return launch_ingest_q<64>(rows, lay, dst_first_row, dim, n_rows, data, src_type, row_stride, src_index, stream);
     default: return hipErrorInvalidValue;
     }
+}
+
+namespace {
+template <int QBITS, int DST>
+hipError_t launch_fetch_qd(const uint8_t *rows, RowLayout lay, int dim, uint64_t n, const uint64_t *list, uint64_t list_base,
+                           uint64_t shard_rows, uint64_t src_first, void *data, uint64_t row_stride, bool vec, hipStream_t stream)
+{
+    const uint64_t total = n * (uint64_t)((dim + 128 / QBITS - 1) / (128 / QBITS));
+    if ((total + 255) / 256 > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    const dim3 g((unsigned)((total + 255) / 256)), b(256);
+    if (vec)
+        hipLaunchKernelGGL((fetch_kernel<QBITS, DST, true>), g, b, 0, stream, rows, lay, dim, n, list, list_base, shard_rows, src_first, data, row_stride);
+    else
+        hipLaunchKernelGGL((fetch_kernel<QBITS, DST, false>), g, b, 0, stream, rows, lay, dim, n, list, list_base, shard_rows, src_first, data, row_stride);
+    return hipGetLastError();
+}
+template <int QBITS>
+hipError_t launch_fetch_q(const uint8_t *rows, RowLayout lay, int dim, uint64_t n, const uint64_t *list, uint64_t list_base,
+                          uint64_t shard_rows, uint64_t src_first, void *data, int dst_type, uint64_t row_stride, bool vec,
+                          hipStream_t stream)
+{
+    switch (dst_type) {
+    case 0: return launch_fetch_qd<QBITS, 0>(rows, lay, dim, n, list, list_base, shard_rows, src_first, data, row_stride, vec, stream);
+    case 1: return launch_fetch_qd<QBITS, 1>(rows, lay, dim, n, list, list_base, shard_rows, src_first, data, row_stride, vec, stream);
+    case 2: return launch_fetch_qd<QBITS, 2>(rows, lay, dim, n, list, list_base, shard_rows, src_first, data, row_stride, vec, stream);
+    case 3: return launch_fetch_qd<QBITS, 3>(rows, lay, dim, n, list, list_base, shard_rows, src_first, data, row_stride, vec, stream);
+    default: return hipErrorInvalidValue;
+    }
+}
+}  // namespace
+
+hipError_t launch_fetch(int qbits, const uint8_t *rows, RowLayout lay, int dim, uint64_t n, const uint64_t *list,
+                        uint64_t list_base, uint64_t shard_rows, uint64_t src_first, void *data, int dst_type,
+                        uint64_t row_stride, hipStream_t stream)
+{
+    if (n == 0) return hipSuccess;
+    static const size_t elem_bytes[4] = {8, 4, 2, 2};
+    if (dst_type < 0 || dst_type > 3) return hipErrorInvalidValue;
+    const bool vec = reinterpret_cast<uintptr_t>(data) % 16 == 0 && (row_stride * elem_bytes[dst_type]) % 16 == 0;
+    switch (qbits) {
+    case 4: return launch_fetch_q<4>(rows, lay, dim, n, list, list_base, shard_rows, src_first, data, dst_type, row_stride, vec, stream);
+    case 8: return launch_fetch_q<8>(rows, lay, dim, n, list, list_base, shard_rows, src_first, data, dst_type, row_stride, vec, stream);
+    case 16: return launch_fetch_q<16>(rows, lay, dim, n, list, list_base, shard_rows, src_first, data, dst_type, row_stride, vec, stream);
+    case 32: return launch_fetch_q<32>(rows, lay, dim, n, list, list_base, shard_rows, src_first, data, dst_type, row_stride, vec, stream);
+    case 64: return launch_fetch_q<64>(rows, lay, dim, n, list, list_base, shard_rows, src_first, data, dst_type, row_stride, vec, stream);
+    default: return hipErrorInvalidValue;
+    }
+}
+
+hipError_t launch_widen_rows(double *out, int dim, uint64_t n, const void *data, int src_type, uint64_t row_stride,
+                             const uint64_t *src_index, hipStream_t stream)
+{
+    if (n == 0 || dim <= 0) return hipSuccess;
+    const uint64_t total = n * (uint64_t)dim;
+    if ((total + 255) / 256 > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    const dim3 g((unsigned)((total + 255) / 256)), b(256);
+    switch (src_type) {
+    case 0: hipLaunchKernelGGL((widen_rows_kernel<0>), g, b, 0, stream, out, dim, n, data, row_stride, src_index); break;
+    case 1: hipLaunchKernelGGL((widen_rows_kernel<1>), g, b, 0, stream, out, dim, n, data, row_stride, src_index); break;
+    case 2: hipLaunchKernelGGL((widen_rows_kernel<2>), g, b, 0, stream, out, dim, n, data, row_stride, src_index); break;
+    case 3: hipLaunchKernelGGL((widen_rows_kernel<3>), g, b, 0, stream, out, dim, n, data, row_stride, src_index); break;
+    default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
 }
 
 hipError_t launch_fill_bits(uint64_t *bits, uint64_t n_rows, uint64_t n_words, hipStream_t stream)

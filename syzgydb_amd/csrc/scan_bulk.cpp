@@ -1,7 +1,10 @@
 // scan_bulk.cpp -- bulk mutations: a list of rows overwritten, tombstoned or given new column values in ONE call
 // (szg_index_overwrite_rows, its _f64 form, szg_index_tombstone_rows / _mask, szg_column_set_rows), and the two
 // mutations whose vectors lie in device memory (szg_index_append_dev, szg_index_overwrite_rows_dev: launch_ingest
-// reads the caller's memory in place, after dev_source_check has cleared the pointer on the host).
+// reads the caller's memory in place, after dev_source_check has cleared the pointer on the host).  The same
+// descriptor and checks serve the two reverse directions: szg_index_fetch_rows_dev decodes stored rows into the
+// caller's device memory (launch_fetch), and szg_search_topk_dev / szg_search_radius_dev widen queries that lie there
+// into one float64 batch (launch_widen_rows) and hand it to the masked searches.
 //
 // Every list is checked and split per shard on the host (bulk_plan.h) and every staging block is reserved before
 // anything on the card changes: a bad list or a refused allocation leaves the handle as it was.  An overwrite then
@@ -314,6 +317,137 @@ int szg_index_append_dev(szg_index *ix, const szg_dev_vectors *src, const uint64
     sh->n_rows += n_rows;
     sh->n_live += n_rows;
     return SZG_OK;
+    SZG_CATCH
+}
+
+// Stored vectors decoded into the caller's device memory: launch_fetch writes it in place, after dev_source_check (with
+// n_rows destination rows) and the row checks have cleared everything on the host.  A list goes to the card once per
+// chunk, through the stage of the first shard it reaches; every shard it reaches (all on the destination's device)
+// then serves its own entries of that chunk.
+int szg_index_fetch_rows_dev(szg_index *ix, const uint64_t *rows, uint64_t first_row, uint64_t n_rows, const szg_dev_vectors *dst)
+{
+    SZG_TRY
+    if (!ix || !dst) return fail(SZG_E_INVALID, "null argument");
+    if (int rc = dev_source_check(ix, dst, nullptr, n_rows)) return rc;
+    if (n_rows == 0) return SZG_OK;  // (the descriptor only)
+    const uint64_t total = szg_index_rows(ix), base = ix->row_base;
+    const size_t S = ix->shards.size();
+    std::vector<char> reached(S, 0);
+    if (rows) {  // bulk_plan's checks, numbered with the row base; of its split only which shards are reached is used
+        std::vector<uint64_t> first, count;
+        for (const Shard *sh : ix->shards) first.push_back(sh->first), count.push_back(sh->n_rows);
+        BulkPlan plan;
+        const char *what = "";
+        if (int rc = bulk_plan(first.data(), count.data(), S, base, rows, n_rows, 1, &plan, &what)) return fail(rc, what);
+        for (size_t s = 0; s < S; s++) reached[s] = !plan.local[s].empty();
+    } else {
+        if (first_row < base || first_row - base > total || n_rows > total - (first_row - base))
+            return fail(SZG_E_RANGE, "row range out of bounds");
+        first_row -= base;
+        for (size_t s = 0; s < S; s++) {
+            const Shard *sh = ix->shards[s];
+            reached[s] = std::max(first_row, sh->first) < std::min(first_row + n_rows, sh->first + sh->n_rows);
+        }
+    }
+    Shard *lead = nullptr;  // the first shard reached: its stage carries the list
+    for (size_t s = 0; s < S; s++) {
+        if (!reached[s]) continue;
+        if (ix->shards[s]->device != dst->device) return fail(SZG_E_INVALID, "destination on another device");
+        if (!lead) lead = ix->shards[s];
+    }
+    HIPCHK(hipSetDevice(dst->device));
+    HIPCHK(hipDeviceSynchronize());  // (whatever was queued to read or write the destination has finished)
+    const uint64_t chunk = ingest_chunk_rows(ix);
+    uint8_t *data = static_cast<uint8_t *>(const_cast<void *>(dst->data));
+    const size_t row_step = (size_t)dst->row_stride * kSrcElemBytes[dst->dtype];
+    hipError_t e = hipSuccess;
+    if (!rows) {
+        for (size_t s = 0; s < S && e == hipSuccess; s++) {
+            const Shard *sh = ix->shards[s];
+            if (!reached[s]) continue;
+            const uint64_t lo = std::max(first_row, sh->first), hi = std::min(first_row + n_rows, sh->first + sh->n_rows);
+            for (uint64_t off = lo; off < hi && e == hipSuccess; off += chunk)
+                e = szg::launch_fetch(ix->bits, sh->rows, ix->layout, ix->dim, std::min(chunk, hi - off), nullptr, 0, sh->n_rows,
+                                      off - sh->first, data + (off - first_row) * row_step, dst->dtype, dst->row_stride, nullptr);
+        }
+        if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+    } else {
+        std::unique_lock<std::mutex> stage_lock(lead->stage_mu);
+        uint8_t *stage8 = nullptr;
+        if (int rc = shard_stage(lead, (size_t)(std::min(chunk, n_rows) * sizeof(uint64_t)), &stage8)) return rc;
+        HIPCHK(hipSetDevice(dst->device));
+        uint64_t *d_list = reinterpret_cast<uint64_t *>(stage8);
+        for (uint64_t off = 0; off < n_rows && e == hipSuccess; off += chunk) {
+            const uint64_t m = std::min(chunk, n_rows - off);
+            e = hipMemcpy(d_list, rows + off, m * sizeof(uint64_t), hipMemcpyHostToDevice);
+            for (size_t s = 0; s < S && e == hipSuccess; s++) {
+                const Shard *sh = ix->shards[s];
+                if (reached[s])
+                    e = szg::launch_fetch(ix->bits, sh->rows, ix->layout, ix->dim, m, d_list, base + sh->first, sh->n_rows, 0,
+                                          data + off * row_step, dst->dtype, dst->row_stride, nullptr);
+            }
+        }
+        if (e == hipSuccess) e = hipStreamSynchronize(nullptr);  // (before the stage is anyone else's)
+    }
+    if (e != hipSuccess) return fail(SZG_E_DEVICE, "fetch_rows_dev", e);
+    return SZG_OK;
+    SZG_CATCH
+}
+
+namespace {
+
+// The queries of a _dev search as the dense float64 batch on the host that the masked calls take: the descriptor's
+// checks, launch_widen_rows on the source's device into the handle's buffer there, one copy into the handle's pinned
+// buffer.  *lock holds ix->dq_mu from here on: the buffers are the caller's until it lets go.
+int dev_queries(szg_index *ix, const szg_dev_vectors *src, const uint64_t *src_rows, int n_queries, const double **out,
+                std::unique_lock<std::mutex> *lock)
+{
+    static const double none = 0.0;
+    *out = &none;  // (n_queries <= 0: nothing to convert, and the masked call says what it thinks of the count)
+    if (n_queries <= 0) return dev_source_check(ix, src, src_rows, 0);
+    const uint64_t n = (uint64_t)n_queries;
+    if (int rc = dev_source_check(ix, src, src_rows, n)) return rc;
+    *lock = std::unique_lock<std::mutex>(ix->dq_mu);
+    const size_t elems = (size_t)n * (size_t)ix->dim;  // the batch, then the list of source rows
+    if (ix->dq_dev.device() != src->device) ix->dq_dev = DevMem<double>(src->device);
+    if (int rc = ix->dq_dev.ensure(elems + (src_rows ? (size_t)n : 0), "hipMalloc(device queries)")) return rc;
+    if (int rc = ix->dq_host.ensure(elems, "hipHostMalloc(device queries)")) return rc;
+    HIPCHK(hipDeviceSynchronize());  // (the source's device, current since ensure: what was queued to write the queries has finished)
+    uint64_t *d_list = nullptr;
+    if (src_rows) {
+        d_list = reinterpret_cast<uint64_t *>(ix->dq_dev.data() + elems);
+        HIPCHK(hipMemcpy(d_list, src_rows, (size_t)n * sizeof(uint64_t), hipMemcpyHostToDevice));
+    }
+    HIPCHK(szg::launch_widen_rows(ix->dq_dev, ix->dim, n, src->data, src->dtype, src->row_stride, d_list, nullptr));
+    HIPCHK(hipMemcpy(ix->dq_host.data(), ix->dq_dev.data(), elems * sizeof(double), hipMemcpyDeviceToHost));
+    *out = ix->dq_host.data();
+    return SZG_OK;
+}
+
+}  // namespace
+
+int szg_search_topk_dev(szg_index *ix, const szg_dev_vectors *queries, const uint64_t *src_rows, int n_queries, int k,
+                        const szg_mask *const *masks, int n_masks, uint64_t *out_rows, double *out_dist, int32_t *out_count)
+{
+    SZG_TRY
+    if (!ix || !queries) return fail(SZG_E_INVALID, "null argument");
+    const double *q = nullptr;
+    std::unique_lock<std::mutex> lock;
+    if (int rc = dev_queries(ix, queries, src_rows, n_queries, &q, &lock)) return rc;
+    return szg_search_topk_masked(ix, q, n_queries, k, masks, n_masks, out_rows, out_dist, out_count);
+    SZG_CATCH
+}
+
+int szg_search_radius_dev(szg_index *ix, const szg_dev_vectors *queries, const uint64_t *src_rows, int n_queries,
+                          const double *radii, const szg_mask *const *masks, int n_masks, uint64_t *out_rows, double *out_dist,
+                          uint64_t capacity, uint64_t *out_offsets)
+{
+    SZG_TRY
+    if (!ix || !queries) return fail(SZG_E_INVALID, "null argument");
+    const double *q = nullptr;
+    std::unique_lock<std::mutex> lock;
+    if (int rc = dev_queries(ix, queries, src_rows, n_queries, &q, &lock)) return rc;
+    return szg_search_radius_masked(ix, q, n_queries, radii, masks, n_masks, out_rows, out_dist, capacity, out_offsets);
     SZG_CATCH
 }
 

@@ -20,7 +20,8 @@
 //   scan_reorder.cpp  compaction and reorder of the resident rows on the device (reorder_plan.h: its host-only checks)
 //   scan_bulk.cpp     bulk mutations: lists of rows overwritten, tombstoned or given column values in one call
 //                     (bulk_plan.h: its host-only checks; kernels_bulk.hip: its scatters), and appends / overwrites from
-//                     vectors in device memory (szg_dev_vectors; kernels_exact.hip: ingest_kernel)
+//                     vectors in device memory (szg_dev_vectors; kernels_exact.hip: ingest_kernel), stored vectors out
+//                     to device memory (fetch_kernel) and searches whose queries lie there (widen_rows_kernel)
 //   scan_api.cpp      remaining C entry points (top-k with caller coalescing, distances)
 //
 // Who owns device memory: dev_mem.h.  Every block is held by a DevBuf / PinnedBuf (scratch of the device that is
@@ -508,6 +509,11 @@ struct szg_index {
     szg_stats stats{};
     szgi::CertTrace cert;        // certificate trace (test hook)
     szg_comm *comm = nullptr;    // one process per GPU: the attached communicator (borrowed; scan_comm.cpp)
+    // queries from device memory (szg_search_*_dev, scan_bulk.cpp): the float64 batch on the source's device (and the
+    // list of source rows behind it) and its pinned host copy, kept between calls; dq_mu is held for the length of one
+    std::mutex dq_mu;
+    szgi::DevMem<double> dq_dev;
+    szgi::PinnedBuf<double> dq_host;
 };
 
 // A device-resident filter mask (scan_mask.cpp).  Words and counts never change after creation -- except that a

@@ -602,6 +602,24 @@ class ScanIndex:
                                           _u8(out) if n_rows else None), "szg_index_read_rows")
         return out
 
+    def fetch_into(self, t, rows=None, first_row=0, n_rows=None):
+        """Stored vectors decoded into the caller's 2-D tensor in device memory (dev_vectors; float64 / float32 /
+        float16 / bfloat16, on the device of the shards the rows lie on), without the host: row i of `t` receives
+        stored row rows[i] -- any order, duplicates allowed, numbered as searches return them -- or, without a list,
+        row first_row + i for n_rows rows (None: as many as `t` has).  The values are codec.decode_rows(read_rows(...))
+        in float64, cast once to float32 for a narrower tensor and once more to float16 / bfloat16.  Columns of a wider
+        tensor beside a slice and rows past the fetched ones keep what they held.  Returns `t`."""
+        if hasattr(t, "data_ptr") and not getattr(t, "is_cuda", False):
+            raise TypeError("a CPU tensor is host memory: read_rows() + codec.decode_rows() serve the host")
+        d = dev_vectors(t, self.dim, getattr(self, "_device0", None))
+        if rows is not None:
+            r = np.ascontiguousarray(rows, dtype=np.uint64).reshape(-1)
+            p, n, first_row = (_u64(r) if r.size else None), r.size, 0
+        else:
+            p, n = None, int(d.n_rows if n_rows is None else n_rows)
+        check(self._L.szg_index_fetch_rows_dev(self._h, p, int(first_row), n, ctypes.byref(d)), "szg_index_fetch_rows_dev")
+        return t
+
     # -- compaction / reorder on the device ---------------------------------------
     def _carry_arg(self, carry):
         """carry -> (the masks, their array, the columns, their array); the arrays are None where there is nothing."""
@@ -821,13 +839,20 @@ class ScanIndex:
         else:
             keep, allow_p = self._allow_arg(allow, nq)
             filt = (allow_p,)
+        ans = self._radius_retry(lambda *out: fn(self._h, _f64(q), nq, _f64(rad), *filt, *out), name, nq, capacity, refetch)
+        del keep
+        return ans
+
+    def _radius_retry(self, call, name, nq, capacity, refetch=None):
+        """The batch radius calls' buffers and their grow-and-retry on SZG_E_TRUNCATED: call(out_rows, out_dist,
+        capacity, out_offsets) -> the library's return code."""
         # (a truncated call is answered again from scratch: start generous, or with what the caller expects)
         cap = max(1 << 16, nq << 12) if capacity is None else max(int(capacity), 1)
         while True:
             out_rows = np.empty(max(cap, 1), dtype=np.uint64)
             out_dist = np.empty(max(cap, 1), dtype=np.float64)
             off = np.zeros(nq + 1, dtype=np.uint64)
-            rc = fn(self._h, _f64(q), nq, _f64(rad), *filt, _u64(out_rows), _f64(out_dist), cap, _u64(off))
+            rc = call(_u64(out_rows), _f64(out_dist), cap, _u64(off))
             if rc == _lib.SZG_E_TRUNCATED:
                 cap = int(off[nq])
                 if refetch is None:
@@ -838,7 +863,6 @@ class ScanIndex:
                 out_dist = np.empty(max(cap, 1), dtype=np.float64)
                 rc = refetch(nq, _u64(out_rows), _f64(out_dist), cap, _u64(off))
             check(rc, name)
-            del keep
             return [(out_rows[int(off[i]):int(off[i + 1])], out_dist[int(off[i]):int(off[i + 1])]) for i in range(nq)]
 
     def search_radius_batch(self, queries, radii, allow=None, masks=None, capacity=None):
@@ -851,6 +875,39 @@ class ScanIndex:
                                     masks=masks, capacity=capacity)
         return self._radius_csr(self._L.szg_search_radius_batch, "szg_search_radius_batch", queries, radii, allow,
                                 capacity=capacity)
+
+    # -- queries from device memory: converted on the card, searched as ever ---------------
+    def _queries_arg(self, t, src_rows):
+        if hasattr(t, "data_ptr") and not getattr(t, "is_cuda", False):
+            raise TypeError("a CPU tensor is host memory: search_topk() / search_radius_batch() take float64 on the host")
+        d = dev_vectors(t, self.dim, getattr(self, "_device0", None))
+        r, p = self._src_rows_arg(src_rows)
+        return d, r, p, int(d.n_rows if r is None else r.size)
+
+    def search_topk_tensor(self, t, k, src_rows=None, masks=None):
+        """search_topk() for queries in device memory (dev_vectors: a 2-D torch tensor or __cuda_array_interface__ in
+        float64 / float32 / float16 / bfloat16, on any device of the process): query i is row src_rows[i] of `t` (None:
+        row i), widened to float64 exactly, and the answer is search_topk's for those values -- (rows, dist, count).
+        masks: as search_topk's.  The tensor's device is synchronised first; `t` may be rewritten once the call returns."""
+        d, r, p, nq = self._queries_arg(t, src_rows)
+        k = int(k)
+        out_rows = np.zeros((nq, max(k, 0)), dtype=np.uint64)
+        out_dist = np.zeros((nq, max(k, 0)), dtype=np.float64)
+        out_count = np.zeros(nq, dtype=np.int32)
+        arr, n_masks = self._masks_arg(masks, None, nq) if masks is not None else (None, 0)
+        check(self._L.szg_search_topk_dev(self._h, ctypes.byref(d), p, nq, k, arr, n_masks, _u64(out_rows), _f64(out_dist),
+                                          out_count.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))), "szg_search_topk_dev")
+        return out_rows, out_dist, out_count
+
+    def search_radius_tensor(self, t, radii, src_rows=None, masks=None, capacity=None):
+        """search_radius_batch() for queries in device memory (see search_topk_tensor): a list of (rows, dist) per
+        query, the same values; radii, masks and capacity as there."""
+        d, r, p, nq = self._queries_arg(t, src_rows)
+        rad = np.ascontiguousarray(np.broadcast_to(np.asarray(radii, dtype=np.float64), (nq,)))
+        arr, n_masks = self._masks_arg(masks, None, nq) if masks is not None else (None, 0)
+        return self._radius_retry(lambda *out: self._L.szg_search_radius_dev(self._h, ctypes.byref(d), p, nq, _f64(rad), arr,
+                                                                              n_masks, *out),
+                                  "szg_search_radius_dev", nq, capacity)
 
     # -- one process per GPU: the exchange inside the library (syzgydb_amd/sharded.py: Comm) ------------
     def attach_comm(self, comm):
