@@ -9,7 +9,9 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <new>
 #include <string>
+#include <system_error>
 #include <thread>
 #include <vector>
 
@@ -101,7 +103,7 @@ ParsedSpan parse_span(const uint8_t *data, size_t len)
     uint64_t seq, idlen;
     if (!read7(data, len, &at, &seq)) return ps;
     if (!read7(data, len, &at, &idlen)) return ps;
-    if (at + idlen > len) return ps;
+    if (idlen > len - at) return ps;  // (at <= len here; at + idlen would wrap for a length near 2^64)
     ps.id.assign(reinterpret_cast<const char *>(data + at), (size_t)idlen);
     at += (size_t)idlen;
     if (at >= len) return ps;
@@ -112,7 +114,7 @@ ParsedSpan parse_span(const uint8_t *data, size_t len)
         const uint8_t sid = data[at++];
         uint64_t sl;
         if (!read7(data, len, &at, &sl)) return ps;
-        if (at + sl > len) return ps;
+        if (sl > len - at) return ps;
         // streams are addressed by POSITION in the reference (collection.go:476-477)
         if (i == 0) {
             ps.rec.meta = data + at;
@@ -130,7 +132,9 @@ ParsedSpan parse_span(const uint8_t *data, size_t len)
     return ps;
 }
 
-bool json_int(const std::string &js, const char *key, long *out)
+// A header field: after the first "key", the next ':', blanks and tabs, an optional '-', decimal digits (at least
+// one).  The value saturates far outside every accepted range instead of wrapping, so a caller's range check sees it.
+bool json_int(const std::string &js, const char *key, int64_t *out)
 {
     const std::string k = std::string("\"") + key + "\"";
     size_t p = js.find(k);
@@ -139,9 +143,27 @@ bool json_int(const std::string &js, const char *key, long *out)
     if (p == std::string::npos) return false;
     p++;
     while (p < js.size() && (js[p] == ' ' || js[p] == '\t')) p++;
-    char *end = nullptr;
-    const long v = strtol(js.c_str() + p, &end, 10);
-    if (end == js.c_str() + p) return false;
+    const bool neg = p < js.size() && js[p] == '-';
+    if (neg) p++;
+    if (p >= js.size() || js[p] < '0' || js[p] > '9') return false;
+    int64_t v = 0;
+    for (; p < js.size() && js[p] >= '0' && js[p] <= '9'; p++)
+        if (v < (int64_t)1 << 40) v = v * 10 + (js[p] - '0');
+    *out = neg ? -v : v;
+    return true;
+}
+
+// strconv.ParseUint(id, 10, 64) (collection.go:675): ASCII digits only, at least one, value below 2^64
+bool parse_uint64(const std::string &id, uint64_t *out)
+{
+    if (id.empty()) return false;
+    uint64_t v = 0;
+    for (const char c : id) {
+        if (c < '0' || c > '9') return false;
+        const uint64_t d = (uint64_t)(c - '0');
+        if (v > (UINT64_MAX - d) / 10) return false;
+        v = v * 10 + d;
+    }
     *out = v;
     return true;
 }
@@ -171,39 +193,19 @@ struct szg_pager {
     std::vector<Record> recs;     // same order
 };
 
-extern "C" {
+namespace {
 
-void szg_pager_close(szg_pager *p)
+// Map and scan the file into *p.  May throw (allocation); the caller owns p and closes it on every failure.
+int open_scan(szg_pager *p, const char *path, int n_threads)
 {
-    if (!p) return;
-    if (p->map && p->size) munmap(const_cast<uint8_t *>(p->map), p->size);
-    if (p->fd >= 0) close(p->fd);
-    delete p;
-}
-
-int szg_pager_open(szg_pager **out, const char *path, int n_threads)
-{
-    if (!out || !path) return SZG_E_INVALID;
-    *out = nullptr;
     crc_init();
-    szg_pager *p = new szg_pager();
     p->fd = open(path, O_RDONLY);
-    if (p->fd < 0) {
-        szg_pager_close(p);
-        return SZG_E_IO;
-    }
+    if (p->fd < 0) return SZG_E_IO;
     struct stat st;
-    if (fstat(p->fd, &st) != 0 || st.st_size <= 0) {
-        szg_pager_close(p);
-        return SZG_E_IO;
-    }
+    if (fstat(p->fd, &st) != 0 || st.st_size <= 0) return SZG_E_IO;
+    void *m = mmap(nullptr, (size_t)st.st_size, PROT_READ, MAP_PRIVATE, p->fd, 0);
+    if (m == MAP_FAILED) return SZG_E_IO;
     p->size = (size_t)st.st_size;
-    void *m = mmap(nullptr, p->size, PROT_READ, MAP_PRIVATE, p->fd, 0);
-    if (m == MAP_FAILED) {
-        p->map = nullptr;
-        szg_pager_close(p);
-        return SZG_E_IO;
-    }
     p->map = static_cast<const uint8_t *>(m);
 
     // pass 1 (sequential, headers only): span boundaries, spanfile.go:282-357
@@ -219,7 +221,7 @@ int szg_pager_open(szg_pager **out, const char *path, int n_threads)
         if (magic == 0) break;  // rest of the file is free space
         const uint32_t len = be32(p->map + off + 4);
         if ((uint64_t)off + len > p->size) break;
-        if (len == 0) break;    // "length is 0; can't continue"
+        if (len == 0) break;    // "length is 0; can't continue": the reference refuses the file, this keeps what it read
         if (magic == kActiveMagic) spans.push_back(Span{off, len});
         off += len;             // FREE and unknown magics are skipped by their length
     }
@@ -230,26 +232,41 @@ int szg_pager_open(szg_pager **out, const char *path, int n_threads)
     nt = std::max(1, std::min(nt, 64));
     if (spans.size() < 1024) nt = 1;
     std::atomic<size_t> next{0};
+    std::atomic<bool> out_of_memory{false};
     auto work = [&]() {
-        for (;;) {
-            const size_t i0 = next.fetch_add(256);
-            if (i0 >= spans.size()) break;
-            const size_t i1 = std::min(spans.size(), i0 + 256);
-            for (size_t i = i0; i < i1; i++) {
-                const uint8_t *d = p->map + spans[i].off;
-                const uint32_t len = spans[i].len;
-                if (len < kMinSpanLength) continue;
-                if (crc32_ieee(d, len - 4) != be32(d + len - 4)) continue;  // verifyChecksum
-                parsed[i] = parse_span(d, len);
+        // nothing may leave a thread's function: a record id is copied, and that allocation can fail
+        try {
+            for (;;) {
+                const size_t i0 = next.fetch_add(256);
+                if (i0 >= spans.size()) break;
+                const size_t i1 = std::min(spans.size(), i0 + 256);
+                for (size_t i = i0; i < i1; i++) {
+                    const uint8_t *d = p->map + spans[i].off;
+                    const uint32_t len = spans[i].len;
+                    if (len < kMinSpanLength) continue;
+                    if (crc32_ieee(d, len - 4) != be32(d + len - 4)) continue;  // verifyChecksum
+                    parsed[i] = parse_span(d, len);
+                }
             }
+        } catch (...) {
+            out_of_memory.store(true);
         }
     };
-    std::vector<std::thread> th;
-    for (int t = 1; t < nt; t++) th.emplace_back(work);
-    work();
-    for (auto &t : th) t.join();
+    {
+        std::vector<std::thread> th;
+        th.reserve((size_t)nt);
+        try {
+            for (int t = 1; t < nt; t++) th.emplace_back(work);
+        } catch (const std::system_error &) {
+            // no further thread to be had: the ones that started and this one share the work
+        }
+        work();
+        for (auto &t : th) t.join();
+    }
+    if (out_of_memory.load()) return SZG_E_NOMEM;
 
-    // pass 3 (sequential): highest sequence number per record id wins (spanfile.go:337-341)
+    // pass 3 (sequential): highest sequence number per record id wins, the earlier span on equal numbers
+    // (spanfile.go:337-341); every ACTIVE span that was not accepted is counted
     std::map<std::string, Record> index;
     for (size_t i = 0; i < parsed.size(); i++) {
         if (!parsed[i].ok) {
@@ -260,37 +277,64 @@ int szg_pager_open(szg_pager **out, const char *path, int n_threads)
         if (it == index.end() || parsed[i].rec.seq > it->second.seq) index[parsed[i].id] = parsed[i].rec;
     }
 
-    // header record "" : CollectionOptions JSON in stream 0 (collection.go:241-252)
+    // header record "" : CollectionOptions JSON in stream 0 (collection.go:241-252); every value is range-checked
+    // before it is narrowed to the int the options are
     auto h = index.find("");
-    if (h == index.end() || !h->second.meta) {
-        szg_pager_close(p);
-        return SZG_E_FORMAT;
-    }
+    if (h == index.end() || !h->second.meta) return SZG_E_FORMAT;
     const std::string js(reinterpret_cast<const char *>(h->second.meta), (size_t)h->second.meta_len);
-    long v;
-    if (!json_int(js, "dimension_count", &v)) {
-        szg_pager_close(p);
-        return SZG_E_FORMAT;
-    }
-    p->dim = (int)v;
-    p->bits = json_int(js, "quantization", &v) ? (int)v : 64;
-    p->metric = json_int(js, "distance_method", &v) ? (int)v : 0;
+    int64_t dim, bits = 64, metric = 0;
+    if (!json_int(js, "dimension_count", &dim)) return SZG_E_FORMAT;
+    json_int(js, "quantization", &bits);
+    json_int(js, "distance_method", &metric);
+    if (dim < 1 || dim > INT32_MAX || metric < INT32_MIN || metric > INT32_MAX) return SZG_E_FORMAT;
+    if (bits != 4 && bits != 8 && bits != 16 && bits != 32 && bits != 64) return SZG_E_FORMAT;
+    p->dim = (int)dim;
+    p->bits = (int)bits;
+    p->metric = (int)metric;
     p->row_bytes = row_bytes_of(p->bits, p->dim);
-    if (p->dim <= 0 || p->row_bytes <= 0) {
-        szg_pager_close(p);
-        return SZG_E_FORMAT;
-    }
 
     // std::map iterates its string keys in sort.Strings order (byte-wise), which is
     // IterateSortedRecords' order (spanfile.go:540-560)
     for (const auto &kv : index) {
-        if (kv.first.empty()) continue;
-        char *end = nullptr;
-        const unsigned long long id = strtoull(kv.first.c_str(), &end, 10);
-        if (*end != '\0' || end == kv.first.c_str()) continue;  // strconv.ParseUint failure: skipped (collection.go:676)
-        if (!kv.second.has_vec || (int64_t)kv.second.vec_len < p->row_bytes) continue;
-        p->ids.push_back((uint64_t)id);
+        uint64_t id;
+        if (!parse_uint64(kv.first, &id)) continue;  // strconv.ParseUint failure: skipped (collection.go:676)
+        if (!kv.second.has_vec || kv.second.vec_len < (uint64_t)p->row_bytes) continue;
+        p->ids.push_back(id);
         p->recs.push_back(kv.second);
+    }
+    return SZG_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+void szg_pager_close(szg_pager *p)
+{
+    if (!p) return;
+    if (p->map && p->size) munmap(const_cast<uint8_t *>(p->map), p->size);
+    if (p->fd >= 0) close(p->fd);
+    delete p;
+}
+
+// No exception leaves a szg_pager_* function: the ones that allocate catch here and return a negative code.
+int szg_pager_open(szg_pager **out, const char *path, int n_threads)
+{
+    if (!out || !path) return SZG_E_INVALID;
+    *out = nullptr;
+    szg_pager *p = new (std::nothrow) szg_pager();
+    if (!p) return SZG_E_NOMEM;
+    int rc;
+    try {
+        rc = open_scan(p, path, n_threads);
+    } catch (const std::bad_alloc &) {
+        rc = SZG_E_NOMEM;
+    } catch (...) {
+        rc = SZG_E_DEVICE;  // "unexpected exception", as the scan handle's functions report it
+    }
+    if (rc != SZG_OK) {
+        szg_pager_close(p);
+        return rc;
     }
     *out = p;
     return SZG_OK;
@@ -337,10 +381,16 @@ int szg_pager_metadata(const szg_pager *p, uint64_t row, const uint8_t **data, u
 int szg_pager_load(const szg_pager *p, szg_index *ix)
 {
     if (!p || !ix) return SZG_E_INVALID;
-    std::vector<uint8_t> buf((size_t)p->ids.size() * (size_t)p->row_bytes);
-    int rc = szg_pager_vectors(p, buf.data(), buf.size());
-    if (rc) return rc;
-    return szg_index_load(ix, buf.data(), p->ids.size());
+    try {
+        std::vector<uint8_t> buf((size_t)p->ids.size() * (size_t)p->row_bytes);
+        int rc = szg_pager_vectors(p, buf.data(), buf.size());
+        if (rc) return rc;
+        return szg_index_load(ix, buf.data(), p->ids.size());
+    } catch (const std::bad_alloc &) {
+        return SZG_E_NOMEM;
+    } catch (...) {
+        return SZG_E_DEVICE;
+    }
 }
 
 }  // extern "C"

@@ -41,6 +41,37 @@ def span(seq, record_id, streams, magic=ACTIVE, pad=0, corrupt=False):
     return buf + struct.pack(">I", crc)
 
 
+def code7(n, width=0):
+    """Any value as a 7-code, MSB first, at least `width` bytes (leading 0x80 bytes carry zeros): lengths the
+    writer above never makes, 2^64 - 1 in ten bytes among them."""
+    digits = [n & 0x7F]
+    n >>= 7
+    while n:
+        digits.append(n & 0x7F)
+        n >>= 7
+    digits += [0] * (width - len(digits))
+    return bytes([d | 0x80 for d in reversed(digits[1:])] + [digits[0]])
+
+
+def raw_span(body, magic=ACTIVE, length=None, crc=True):
+    """magic, length, body and the CRC32 of all three, whatever the body is: a malformed span with a good checksum."""
+    length = 8 + len(body) + 4 if length is None else length
+    buf = struct.pack(">II", magic, length & 0xFFFFFFFF) + body
+    c = zlib.crc32(buf) & 0xFFFFFFFF
+    return buf + struct.pack(">I", c if crc else c ^ 0x5A5A5A5A)
+
+
+def span_ending_in_a_code(prefix):
+    """prefix + continuation bytes (0x80 | x) chosen so that the CRC trailer's four bytes are continuation bytes too:
+    the 7-code that starts after the prefix runs to the very end of the span."""
+    for a in range(128):
+        for b in range(128):
+            s = raw_span(prefix + bytes([0x80 | a, 0x80 | b, 0x81, 0x82]))
+            if all(x & 0x80 for x in s[-4:]):
+                return s
+    raise AssertionError("no filler found")
+
+
 def header_span(seq, name, metric, dim, bits):
     js = json.dumps({"name": name, "distance_method": metric, "dimension_count": dim,
                      "quantization": bits}, separators=(",", ":")).encode()

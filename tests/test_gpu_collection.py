@@ -215,6 +215,93 @@ def test_collection_from_spanfile_end_to_end(tmp_path, bits, metric):
     c.Close()
 
 
+@pytest.mark.parametrize("bits,metric", [(4, 0), (32, 1)])
+def test_collection_from_a_damaged_spanfile(tmp_path, bits, metric):
+    """A collection file a tenth of whose spans are damaged -- lengths that wrap a 64-bit sum, 7-codes that run out,
+    stream counts, short vectors, length fields, magics, each with a good checksum unless the checksum is the damage
+    -- a tenth of whose records are rewritten at a higher sequence, and which holds the ids strconv.ParseUint refuses:
+    the search answers over exactly the rows the model of the read rules (tests/spanfile_model.py) serves, in its
+    order, bit for bit as the oracle computes them."""
+    import struct
+    import spanfile_model as sm
+    import spanfile_writer as sw
+    from syzgydb_amd import codec
+    dim, n = 33, 300
+    U64 = 1 << 64
+    rb = sm.row_bytes(bits, dim)
+    rows = codec.encode_rows(orc.synth_vectors(51, 0, n + 60, dim), bits)
+    spans = [sw.span(0, "", [], magic=sw.FREE), sw.header_span(1, "damaged", metric, dim, bits)]
+    damaged = 0
+    for i in range(n):
+        rid, seq, meta, vec = str(5 * i + 2), 2 + i, b"doc-%d" % i, rows[i].tobytes()
+        s = sw.span(seq, rid, [(0, meta), (1, vec)])
+        if i % 10 == 4:
+            damaged += 1
+            way = (i // 10) % 15
+            head = sw.code7(seq) + sw.code7(len(rid)) + rid.encode()            # as far as the stream count
+            at = 8 + len(sw.code7(seq)) + 10                                      # behind a 10-byte id length
+            m_at = 8 + len(head) + 2 + 10                                         # behind a 10-byte metadata length
+            streams = lambda count, v: bytes([count, 0]) + sw.code7(len(meta)) + meta + b"\x01" + sw.code7(len(v)) + v
+            s = [lambda: sw.span(seq, rid, [(0, meta), (1, vec)], corrupt=True),
+                 lambda: sw.raw_span(sw.code7(seq) + sw.code7(U64 - 1, 10) + rid.encode() + streams(2, vec)),
+                 lambda: sw.raw_span(sw.code7(seq) + sw.code7(U64 - at, 10) + rid.encode() + streams(2, vec)),
+                 lambda: sw.raw_span(head + bytes([2, 0]) + sw.code7(len(meta)) + meta + b"\x01" + sw.code7(U64 - 1, 10) + vec),
+                 lambda: sw.raw_span(head + bytes([2, 0]) + sw.code7(U64 - m_at + 1, 10) + meta + b"\x01" + sw.code7(rb) + vec),
+                 lambda: sw.span_ending_in_a_code(b""),
+                 lambda: sw.span_ending_in_a_code(sw.code7(seq)),
+                 lambda: sw.span_ending_in_a_code(head + bytes([1, 0])),
+                 lambda: sw.raw_span(head + streams(255, vec)),
+                 lambda: sw.span(seq, rid, [(0, meta)]),
+                 lambda: sw.span(seq, rid, [(0, meta), (1, vec[:rb - 1])]),
+                 lambda: sw.span(seq, rid, [(0, meta), (1, vec + b"xyz")]),         # served: the first row_bytes bytes
+                 lambda: struct.pack(">II", sw.ACTIVE, 8) + s,                       # a span of its header alone in front
+                 lambda: struct.pack(">I", 0x12345678) + s[4:],
+                 lambda: sw.span(seq, rid, [(0, meta), (1, vec)], magic=sw.FREE)][way]()
+        spans.append(s)
+    for i in range(7, n, 10):      # a tenth rewritten at a higher sequence, half of them once more at a lower one
+        spans.append(sw.span(1000 + i, str(5 * i + 2), [(0, b"rewritten"), (1, rows[n + i // 10].tobytes())]))
+        if i % 20 == 7:
+            spans.append(sw.span(500 + i, str(5 * i + 2), [(0, b"stale"), (1, rows[i].tobytes())]))
+    for j, rid in enumerate(("-5", " 6", "+7", "8 ", "0x9", "18446744073709551616", "18446744073709551615", "007")):
+        spans.append(sw.span(2000 + j, rid, [(0, b"odd"), (1, rows[n + 30 + j].tobytes())]))
+    # what ends or derails the walk comes last: a span one byte short with its checksum made again (seen), a length
+    # of 14, then a length one too long, a length of 0 and one past the end of the file, a good record behind each
+    late = [sw.span(3000 + j, str(9000 + j), [(0, b"late"), (1, rows[n + 40 + j].tobytes())]) for j in range(4)]
+    padded = sw.span(2900, "8999", [(0, b"short"), (1, rows[n + 50].tobytes())], pad=1)
+    spans += [sw.raw_span(padded[8:-5]), struct.pack(">II", sw.ACTIVE, 14) + b"\x01" * 6, late[0],
+              late[1][:4] + struct.pack(">I", len(late[1]) + 1) + late[1][8:], late[2],
+              struct.pack(">II", sw.ACTIVE, 0) + b"\x01" * 8, late[3],
+              struct.pack(">II", sw.ACTIVE, 1 << 24) + b"\x01" * 8]
+    blob = b"".join(spans) + b"\x00" * 64
+    path = tmp_path / "damaged.dat"
+    path.write_bytes(blob)
+
+    (rc, m_dim, m_bits, m_metric, skipped, served), stats = sm.scan_ex(blob)
+    assert (rc, m_dim, m_bits, m_metric) == (sm.OK, dim, bits, metric)
+    ids = [r[0] for r in served]
+    assert damaged == 30 and skipped >= 20 and stats["crc_valid_rejected"] >= 16 and stats["huge_lengths"] >= 8
+    assert 270 <= len(ids) <= 290 and ids.count(7) == 2 and 18446744073709551615 in ids and 8999 in ids and 9000 in ids
+    assert not {6, 8, 9, 9002, 9003} & set(ids) and 5 * 14 + 2 not in ids       # refused ids, unseen and damaged records
+    visit_rows = np.frombuffer(b"".join(r[2] for r in served), dtype=np.uint8).reshape(len(ids), rb)
+    assert (visit_rows[ids.index(5 * 7 + 2)] == rows[n]).all()                   # the rewrite won
+
+    c = Collection.from_spanfile(path)
+    assert (c.DimensionCount, c.Quantization, c.DistanceMethod) == (dim, bits, metric)
+    assert c._id_of == ids and c._meta == [r[1] for r in served]
+    for q in orc.synth_vectors(52, 0, 2, dim):
+        res = c.Search(SearchArgs(Vector=q, K=10, Precision="exact"))
+        o_rows, o_dist, _ = orc.search_exact(visit_rows, dim, bits, metric, q, k=10)
+        assert [r.ID for r in res.Results] == [ids[int(x)] for x in o_rows]
+        assert [r.Distance for r in res.Results] == list(o_dist)
+    radius = float(np.sort(orc.all_distances(visit_rows, dim, bits, metric, q))[25])
+    res = c.Search(SearchArgs(Vector=q, Radius=radius, Precision="exact"))
+    o_rows, o_dist, _ = orc.search_exact(visit_rows, dim, bits, metric, q, radius=radius)
+    assert len(o_rows) >= 26
+    assert [r.ID for r in res.Results] == [ids[int(x)] for x in o_rows]
+    assert [r.Distance for r in res.Results] == list(o_dist)
+    c.Close()
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("bits,metric", [(4, 1), (8, 0), (16, 1), (32, 1), (64, 0)])
 def test_pair_distances_and_average_distance(bits, metric):
