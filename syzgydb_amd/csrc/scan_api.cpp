@@ -564,8 +564,8 @@ int szg_debug_sketch_rows(szg_index *ix, uint64_t first_row, uint64_t n_rows, ui
 }  // extern "C"
 
 // ---- the plan hooks (test hooks, host only; include/syzgy_scan.h says what each answers): what a one-sweep call would
-// do, from the functions the launch path calls (row_format, scan_geometry, scan_variant, scan_lds_bytes), so tests derive
-// their shapes from the code's own rules.
+// do, from the functions the launch path calls (row_format, scan_geometry, scan_variant, scan_lds_bytes, and sketch_plan.h
+// for a call through the sketch), so tests derive their shapes from the code's own rules.
 namespace {
 
 // the option arguments the hooks share, checked in this order; null = the hook has no such argument
@@ -586,6 +586,7 @@ struct PlanHook {
     RowFormat f;
     LaunchGeom g;
     szg::ScanPlanIn in;
+    SketchShape s;           // (sketch_rows) the sketch index of the hook's arguments, under the default batch and launch sizes
     szg::ScanVariant first;  // the first launch's variant and LDS bytes
     uint64_t lds_bytes;
     int32_t passes;          // over the rows, of all launches (what launch_scans_chained adds to szg_stats.scan_bytes)
@@ -601,20 +602,21 @@ struct PlanHook {
         in.block = g.block;
         return SZG_OK;
     }
-    // ... for the four hooks of the sketch's launches: the options all four take, checked and filled in
+    // ... for the hooks of the sketch's launches: the options they take, checked and filled in (an option a hook does not
+    // know: the value that leaves the form out).  kp is the launches' list length, whatever the grid: sketch_list = kp.
     int sketch_rows(int dim, int quant_bits, int kp, bool collect, int planes, int norms, int tiled, int masked, int scan_group,
-                    int sketch_matrix, const int *sketch_select, const int *sketch_wide)
+                    int sketch_matrix, const int *sketch_select, const int *sketch_wide, int sketch_share = 1, int sketch_masked = 0)
     {
         if (const int rc = hook_options(&planes, &scan_group, &sketch_matrix, sketch_select, sketch_wide)) return rc;
         if (const int rc = rows(dim, quant_bits, tiled, kp, collect, masked)) return rc;
-        in.group = scan_group;
-        in.planes = planes;
-        in.matrix_opt = sketch_matrix;
-        in.norms = norms != 0;
-        if (sketch_select) in.select_opt = *sketch_select;
-        if (sketch_wide) in.wide_opt = *sketch_wide;
+        s = SketchShape{quant_bits, f.map, in.tiled, in.ring, in.no_shape_kernels, scan_group, planes, 0, sketch_matrix,
+                        sketch_select ? *sketch_select : 0, sketch_wide ? *sketch_wide : 1, sketch_share, sketch_masked, kp,
+                        16, szg::kMaxSweepsPerLaunch, norms != 0};
+        in = sketch_plan_in(s, kp, collect, masked != 0, 1, g.block);
         return SZG_OK;
     }
+    // ... and for the two that answer a whole top-k call through the sketch: its batches, launches and passes
+    SketchCallWalk call(int kp, int n_queries) const { return sketch_call_walk(s, g.grid, g.block, kp, n_queries, in.masked, true); }
     // the call's n_queries queries as launches of up to per_launch
     void walk(int n_queries, int per_launch)
     {
@@ -626,7 +628,7 @@ struct PlanHook {
                 first = v;
                 lds_bytes = szg::scan_lds_bytes(in.qbits, in.map, in.kp, in.block, v.group, in.planes, v.matrix_blocks());
             }
-            passes += (in.n_queries + v.group - 1) / v.group;
+            passes += launch_passes(in);
         }
     }
     // launches of 32 where one qualifies for the two-block form, else of 16
@@ -725,7 +727,8 @@ int szg_debug_scan_wide(int dim, int quant_bits, int n_queries, int kp, int plan
 
 // the matrix sweep's shared form (option sketch_share) for a one-sweep top-k call of n_queries through the sketch under the
 // default query_batch and queries_per_launch: whether a launch of min(n_queries, 64) takes it, and the call's batches,
-// launches and passes as sketch_call_plan, sketch_plan_batch and enqueue_topk split it
+// launches and passes as sketch_plan.h splits it for sketch_call_plan, plan_batch and enqueue_topk (the two parts of a
+// short call included)
 int szg_debug_scan_share(int dim, int quant_bits, int n_queries, int kp, int planes, int norms, int tiled, int masked,
                          int scan_group, int sketch_matrix, int sketch_select, int sketch_wide, int sketch_share, int32_t *serves,
                          int32_t *launches, int32_t *passes, int32_t *slices, uint64_t *lds_bytes, int32_t *batches,
@@ -736,43 +739,25 @@ int szg_debug_scan_share(int dim, int quant_bits, int n_queries, int kp, int pla
     if (kp < 0 || n_queries < 1 || batch_capacity < 0) return fail(SZG_E_INVALID, "kp, n_queries or batch_capacity out of range");
     if (!szg::sketch_share_known(sketch_share)) return fail(SZG_E_INVALID, "sketch_share is 0, 1 or 2");
     PlanHook h;
-    if (const int rc = h.sketch_rows(dim, quant_bits, kp, false, planes, norms, tiled, masked, scan_group, sketch_matrix, &sketch_select, &sketch_wide))
+    if (const int rc = h.sketch_rows(dim, quant_bits, kp, false, planes, norms, tiled, masked, scan_group, sketch_matrix, &sketch_select,
+                                     &sketch_wide, sketch_share))
         return rc;
-    h.in.share_opt = sketch_share;
-    const bool wide_serves = h.wide_launches() == szg::kMatrixWideQueries;
     h.in.n_queries = std::min(n_queries, szg::kMatrixShareQueries);
     const szg::ScanVariant v = szg::scan_variant(h.in);
     *serves = v.share;
     *slices = v.share ? szg::share_slices(szg::share_grid(h.g.grid)) : 0;
     *lds_bytes = szg::scan_lds_bytes(h.in.qbits, h.in.map, h.in.kp, h.in.block, v.group, h.in.planes, v.matrix_blocks());
-    // the call's plan (sketch_call_plan): shared batches need a shared launch of 64 to be served
-    h.in.n_queries = szg::kMatrixShareQueries;
-    const bool share_serves = wide_serves && szg::scan_variant(h.in).share != 0;
-    const int wide = !wide_serves || n_queries <= szg::kMatrixQueries ? 0 : (sketch_wide == 2 ? 2 : (n_queries >= kWideCallMin ? 1 : 0));
-    const int share = !share_serves || n_queries <= szg::kMatrixWideQueries
-                          ? 0
-                          : (sketch_share == 2 ? 2 : (wide == 1 && n_queries >= kShareCallMin ? 1 : 0));
-    const std::vector<int> sizes = sketch_batch_sizes(n_queries, wide, share, 16);
-    *n_batches = (int32_t)sizes.size();
-    *launches = *passes = 0;
-    for (size_t i = 0; i < sizes.size(); i++) {
-        if ((int32_t)i < batch_capacity) batches[i] = sizes[i];
-        const int nq = sizes[i];
-        const int per = share && nq > szg::kMatrixWideQueries
-                            ? szg::kMatrixShareQueries
-                            : ((wide || share) && nq > szg::kMatrixQueries ? szg::kMatrixWideQueries : szg::kMaxSweepsPerLaunch);
-        for (int j = 0; j < nq; j += per) {
-            h.in.n_queries = std::min(per, nq - j);
-            *launches += 1;
-            *passes += (h.in.n_queries + szg::scan_variant(h.in).group - 1) / szg::scan_variant(h.in).group;
-        }
-    }
+    const SketchCallWalk w = h.call(kp, n_queries);
+    *n_batches = (int32_t)w.batches.size();
+    std::copy_n(w.batches.begin(), std::min<size_t>(w.batches.size(), (size_t)batch_capacity), batches);
+    *launches = w.launches;
+    *passes = w.passes;
     return SZG_OK;
 }
 
 // the matrix sweep's masked forms (option sketch_masked) for a one-sweep top-k call of n_queries through the sketch whose
 // launches carry masks: the form a launch of min(n_queries, 64) takes, and the call's launches and passes as
-// sketch_call_plan, sketch_plan_batch and enqueue_topk split it (as szg_debug_scan_share walks the unmasked call)
+// szg_debug_scan_share counts the unmasked call's
 int szg_debug_scan_masked(int dim, int quant_bits, int n_queries, int kp, int planes, int norms, int tiled, int masked,
                           int scan_group, int sketch_matrix, int sketch_select, int sketch_wide, int sketch_share, int sketch_masked,
                           int shared_mask, szg_scan_masked_plan *out)
@@ -782,11 +767,9 @@ int szg_debug_scan_masked(int dim, int quant_bits, int n_queries, int kp, int pl
     if (!szg::sketch_share_known(sketch_share)) return fail(SZG_E_INVALID, "sketch_share is 0, 1 or 2");
     if (!szg::sketch_masked_known(sketch_masked)) return fail(SZG_E_INVALID, "sketch_masked is 0 or 1");
     PlanHook h;
-    if (const int rc = h.sketch_rows(dim, quant_bits, kp, false, planes, norms, tiled, masked, scan_group, sketch_matrix, &sketch_select, &sketch_wide))
+    if (const int rc = h.sketch_rows(dim, quant_bits, kp, false, planes, norms, tiled, masked, scan_group, sketch_matrix, &sketch_select,
+                                     &sketch_wide, sketch_share, sketch_masked))
         return rc;
-    h.in.share_opt = sketch_share;
-    h.in.masked_opt = sketch_masked;
-    const bool wide_serves = h.wide_launches() == szg::kMatrixWideQueries;
     h.in.n_queries = std::min(n_queries, szg::kMatrixShareQueries);
     const szg::ScanVariant v = szg::scan_variant(h.in);
     memset(out, 0, sizeof(*out));
@@ -795,23 +778,9 @@ int szg_debug_scan_masked(int dim, int quant_bits, int n_queries, int kp, int pl
     out->share = out->serves && v.share ? 1 : 0;
     out->tile_skip = out->serves && shared_mask ? 1 : 0;
     out->steps_form = out->serves ? v.matrix_steps : 0;
-    h.in.n_queries = szg::kMatrixShareQueries;
-    const bool share_serves = wide_serves && szg::scan_variant(h.in).share != 0;
-    const int wide = !wide_serves || n_queries <= szg::kMatrixQueries ? 0 : (sketch_wide == 2 ? 2 : (n_queries >= kWideCallMin ? 1 : 0));
-    const int share = !share_serves || n_queries <= szg::kMatrixWideQueries
-                          ? 0
-                          : (sketch_share == 2 ? 2 : (wide == 1 && n_queries >= kShareCallMin ? 1 : 0));
-    for (const int nq : sketch_batch_sizes(n_queries, wide, share, 16)) {
-        const int per = share && nq > szg::kMatrixWideQueries
-                            ? szg::kMatrixShareQueries
-                            : ((wide || share) && nq > szg::kMatrixQueries ? szg::kMatrixWideQueries : szg::kMaxSweepsPerLaunch);
-        for (int j = 0; j < nq; j += per) {
-            h.in.n_queries = std::min(per, nq - j);
-            const int group = szg::scan_variant(h.in).group;
-            out->launches += 1;
-            out->passes += (h.in.n_queries + group - 1) / group;
-        }
-    }
+    const SketchCallWalk w = h.call(kp, n_queries);
+    out->launches = w.launches;
+    out->passes = w.passes;
     return SZG_OK;
 }
 

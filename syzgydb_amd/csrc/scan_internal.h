@@ -37,6 +37,7 @@
 #include "dev_mem.h"
 #include "kernels.h"
 #include "reorder_plan.h"
+#include "sketch_plan.h"
 
 #include <algorithm>
 #include <atomic>
@@ -58,6 +59,7 @@
 namespace szgi {
 
 constexpr int kMaxBatch = 96;  // queries one batch may stage (szg::kMqMaxQueries: a bfloat16 shared sweep)
+static_assert(kShortCall <= kMaxBatch, "a short call is one batch");
 
 extern thread_local std::string g_last_error;
 int fail(int code, const char *what, hipError_t e = hipSuccess);
@@ -655,7 +657,7 @@ struct CertTag {
 // grid and block of a sweep over n_rows rows (kp = 0: a collect sweep); the second form reads them off a shard
 LaunchGeom scan_geometry(int bits, const szg::RowMap &map, uint32_t row_bytes, bool tiled, uint64_t n_rows, int cu_count,
                          int kp);
-LaunchGeom scan_geometry(const szg_index *ix, const Shard *sh, int kp, bool plain_topk = false);
+LaunchGeom scan_geometry(const szg_index *ix, const Shard *sh, int kp);
 size_t shard_words(const Shard *sh);
 // (handles: null, or the resident masks of the batch's queries -- then `masks` holds their host words -- and `shard_no`,
 // the shard's position in its index, which is also the position of its words in every handle)
@@ -689,22 +691,13 @@ struct RerankOn {
     bool share = false;  // ... and shared batches: a batch of 33 .. szg::kMatrixShareQueries queries is ONE launch of the
                          // shared form where it serves (sketch_share_serves)
 };
-// does the matrix sweep's shared form serve an unmasked top-k launch of 33 .. szg::kMatrixShareQueries queries of sketch
-// index `sk` on shard `sh`: the wide form serves the shard (sketch_wide_serves), no dead rows (or sketch_masked = 1: a
-// top-k launch with masks then takes the same form), option sketch_share not 1
-bool sketch_share_serves(const szg_index *sk, const Shard *sh, int kp, int list_opt);
-// The geometry of a shared launch on a shard whose plain sweep takes `g`: grid 2 S and S lists of m entries per query.
-// Everything that sizes or walks the lists of a shared launch reads S from here (szg::share_slices, as the kernel does).
-struct ShareGeom {
-    int grid, slices, m;
-};
-ShareGeom share_geometry(const LaunchGeom &g, int list_opt, int kp);
-// entries per wave and block list of a sketch sweep over `grid` blocks (option sketch_list)
-int sketch_list_len(int want, int kp, int grid);
-// does the matrix sweep's two-block form serve an unmasked launch of szg::kMatrixWideQueries queries of sketch index
-// `sk` on shard `sh`, for calls that keep kp candidates per query (scan_variant's answer for that launch)?  kp = 0: the
-// collect form (radius searches through the sketch; no lists, list_opt is not read)
+// the index as sketch_plan.h sees it: sk's rows and options, ix's sketch_list and query_batch (ix: the handle whose
+// sketch index sk is; a plain handle's one-sweep batches: ix = sk)
+SketchShape sketch_shape(const szg_index *ix, const szg_index *sk);
+// sketch_plan.h's questions of the same names on shard `sh` of sketch index `sk`, at the geometry of its plain sweep
+// (kp = 0: the collect form, list_opt is not read)
 bool sketch_wide_serves(const szg_index *sk, const Shard *sh, int kp, int list_opt);
+bool sketch_share_serves(const szg_index *sk, const Shard *sh, int kp, int list_opt);
 int enqueue_topk(szg_index *ix, Shard *sh, Ctx *c, int kp, int nq, bool has_allow, const RerankOn *on = nullptr);
 // candidates of staged query `slot` from a finished top-k pass and *lb, the lower bound of the real-number key of every
 // eligible row of the shard that is not among them
@@ -903,16 +896,6 @@ struct CtxGuard {  // returns a borrowed context on every exit path
 // as the shards have free contexts: a batch is planned (plan_batch), borrows one context per shard, is staged (its
 // queries prepared once, uploaded and its sweeps enqueued on every shard) and finished in order (run_batches).
 
-constexpr int kFirstBatch = 4;  // queries of a call's first (and last) one-sweep batch: the card starts sweeping sooner
-constexpr int kShortCall = 32;  // calls of up to this many one-sweep queries are ONE batch on the scan stream
-// Wide batches of the sketch pre-pass (option sketch_wide = 0): a call takes batches of szg::kMatrixWideQueries queries,
-// one launch each, from two of them between its first and last batch of kFirstBatch on -- below that a pipeline of
-// 32-query batches has nothing to overlap with
-constexpr int kWideCallMin = 2 * szg::kMatrixWideQueries + 2 * kFirstBatch;
-// Shared batches (option sketch_share = 0): batches of szg::kMatrixShareQueries queries, one shared launch each, by the
-// same rule -- from two of them between the first and last batch of kFirstBatch on.  Shorter calls keep their plan.
-constexpr int kShareCallMin = 2 * szg::kMatrixShareQueries + 2 * kFirstBatch;
-
 // the filter masks of a call's queries: one pointer per query (null = unfiltered), or masks back to back with one
 // bit per row of the index, or resident masks (one handle per query, null = unfiltered), or none.  operator() gives
 // the host words in every case (a handle keeps a host copy of its words)
@@ -966,18 +949,9 @@ struct Batch {
     std::vector<const szg_mask *> handles(const QueryMasks &mask_of) const;
 };
 
-// How a call splits into batches: the caller's parameters
-struct BatchRules {
-    int batch;        // queries of a one-sweep-per-query batch
-    int edge;         // ... of the call's first and last such batch
-    int short_max;    // a call of up to this many one-sweep queries is ONE batch on the scan stream
-    bool early_tail;  // ... whose first queries' tail runs beside its last sweeps
-    bool radius;      // radius batches (mq_uses_i8)
-};
 // the next batch of a call of n_queries, from query q0; nb = the query blocks of a shared sweep (0: one sweep per query)
+// (sketch_plan.h: the rules, a one-sweep batch's size and a short call's early tail)
 void plan_batch(szg_index *ix, int n_queries, int q0, int nb, const BatchRules &r, Batch *b);
-// ... its size when every query takes a sweep of its own (nb = 0): host arithmetic, what plan_batch itself takes
-int one_sweep_batch_size(int n_queries, int q0, const BatchRules &r);
 
 // Prepare the batch's queries q[0, nq) ONCE on its first context -- the single-query form (swizzled floats / digit
 // planes) for a batch of one sweep per query, the integer queries of the int8 shared sweep when int_planes -- and copy
@@ -1003,8 +977,6 @@ struct SketchPlan {
 SketchPlan sketch_call_plan(const szg_index *ix, int n_queries, int kp);
 // the next batch of such a call, from query q0, on the sketch index's contexts
 void sketch_plan_batch(const szg_index *ix, int n_queries, int q0, int wide, Batch *b, int share = 0);
-// the batch sizes of a top-k call of n_queries through the sketch, by the rules above (host arithmetic: the plan hook)
-std::vector<int> sketch_batch_sizes(int n_queries, int wide, int share, int query_batch);
 // float32 shard a's rows without a usable sketch (sk_exc): f(shard-local row, eligible: live and allowed by mask words m)
 template <class F>
 void sketchless_rows(const szg_index *ix, const Shard *a, const uint64_t *m, F &&f)

@@ -525,8 +525,9 @@ int sketch_collect_enqueue(szg_index *ix, szg_index *sk, const SketchPlan &p, Co
         norms = scan_row_norms(sk, h, &nrc);
         if (nrc) return nrc;
     }
-    const bool wide32 = p.wide && norms && t.nq > szg::kMatrixQueries && sketch_wide_serves(sk, h, 0, 0);
-    const int qpl = wide32 ? szg::kMatrixWideQueries : std::max(1, std::min(sk->queries_per_launch, szg::kMaxSweepsPerLaunch));
+    const LaunchGeom g = scan_geometry(sk, h, 0);
+    const int qpl = sketch_collect_launches(sketch_shape(ix, sk), g.grid, g.block, h->has_dead, p.wide, norms != nullptr, t.nq,
+                                            std::max(1, std::min(sk->queries_per_launch, szg::kMaxSweepsPerLaunch))).qpl;
     // one part -- or, for a short call (Pass::early_n), two, as enqueue_topk: the first queries' re-rank, sort and
     // copy-back leave the scan stream for the context's own and run beside the call's last sweeps
     const int early = c->pass.early_n > 0 && c->pass.early_n < t.nq ? c->pass.early_n : 0;
@@ -697,9 +698,12 @@ int SketchTopkCall::enqueue_sample(SketchTopkBatch &t, size_t s, const std::vect
     uint32_t *keys = reinterpret_cast<uint32_t *>(c->d_keys.data());
     uint32_t *d_sel = reinterpret_cast<uint32_t *>(c->d_thr.data());
     const bool masked = t.any_mask || h->has_dead;
-    const bool wide32 = p.wide && !masked && t.nq > szg::kMatrixQueries && sketch_wide_serves(sk, h, 0, 0) &&
-                        szg::sample_mx_lds_bytes(sk->layout.steps, 2) <= 64u * 1024u;
-    const int qpl = wide32 ? szg::kMatrixWideQueries : szg::kMatrixQueries;
+    const LaunchGeom g = scan_geometry(sk, h, 0);
+    // (wide launches: the sample's two-block image has to fit LDS as well)
+    const CollectLaunches cl = sketch_collect_launches(sketch_shape(ix, sk), g.grid, g.block, h->has_dead, p.wide,
+                                                       !masked && szg::sample_mx_lds_bytes(sk->layout.steps, 2) <= 64u * 1024u,
+                                                       t.nq, szg::kMatrixQueries);
+    const int qpl = cl.qpl;
     std::vector<szg::SampleArgs> launches;
     for (int j0 = 0; j0 < t.nq; j0 += qpl) {
         szg::SampleArgs x;
@@ -716,7 +720,7 @@ int SketchTopkCall::enqueue_sample(SketchTopkBatch &t, size_t s, const std::vect
     rc = chain_sweeps(sk, h, c, c->pass.work, 0, (int)launches.size(), "szg::launch_sample_mx", [&](hipStream_t st) {
         hipError_t e = hipSuccess;
         for (size_t i = 0; i < launches.size() && e == hipSuccess; i++)
-            e = szg::launch_sample_mx(sk->metric, launches[i], wide32 ? 2 : 1, grid, block, st);
+            e = szg::launch_sample_mx(sk->metric, launches[i], cl.wide32 ? 2 : 1, grid, block, st);
         return e;
     });
     if (rc) return rc;

@@ -304,58 +304,28 @@ SketchPlan sketch_call_plan(const szg_index *ix, int n_queries, int kp)
     // Twice the root (a float64 reference beside it; cert_check.sketch_angle_rounding) passes 1e-7 from dim 223 on.
     const double ang_round = p.gs > 0.0 ? 0.0 : std::max(1e-7, 2.0 * std::sqrt((ix->dim + 8) * 0x1p-52) / M_PI);
     p.slack = ix->sk_max_ang * (1.0 + 1e-9) + ang_round;
-    // Wide batches (option sketch_wide, read from the sketch index): only where every shard's launch of 32 qualifies
-    // for the two-block matrix sweep.  Automatic: long calls under the default batch and launch sizes; 2: every call
-    // of more than 16 queries.
-    if (sk->sketch_wide == 1 || n_queries <= szg::kMatrixQueries) return p;
-    bool any = false;
-    for (const Shard *sh : sk->shards) {
-        if (sh->n_rows == 0) continue;
-        any = true;
-        if (!sketch_wide_serves(sk, sh, kp, ix->sketch_list)) return p;
-    }
-    if (!any) return p;
-    if (sk->sketch_wide == 2) p.wide = 2;
-    else if (n_queries >= kWideCallMin && ix->query_batch == 16 && sk->queries_per_launch == 16) p.wide = 1;
-    // Shared batches (option sketch_share; top-k calls): only where every shard's launch of 33 .. 64 qualifies for the
-    // shared form.  Automatic: long calls under the default batch and launch sizes (they take wide batches too: a rest of
-    // 17 .. 32 queries is a wide launch); 2: every call of more than 32 queries.
-    if (kp < 1 || sk->sketch_share == 1 || n_queries <= szg::kMatrixWideQueries) return p;
-    for (const Shard *sh : sk->shards)
-        if (sh->n_rows != 0 && !sketch_share_serves(sk, sh, kp, ix->sketch_list)) return p;
-    if (sk->sketch_share == 2) p.share = 2;
-    else if (p.wide == 1 && n_queries >= kShareCallMin) p.share = 1;
+    // wide and shared batches (sketch_plan.h: the options are read from the sketch index): only where every non-empty
+    // shard's launch of 32 (33 .. 64) qualifies for the form, and there is one
+    auto every_shard = [&](bool (*serves)(const szg_index *, const Shard *, int, int)) {
+        bool any = false;
+        for (const Shard *sh : sk->shards) {
+            if (sh->n_rows == 0) continue;
+            any = true;
+            if (!serves(sk, sh, kp, ix->sketch_list)) return false;
+        }
+        return any;
+    };
+    const SketchShape s = sketch_shape(ix, sk);
+    p.wide = sketch_call_wide(s, n_queries, true);
+    if (p.wide && !every_shard(sketch_wide_serves)) p.wide = 0;
+    p.share = sketch_call_share(s, n_queries, kp, p.wide, true);
+    if (p.share && !every_shard(sketch_share_serves)) p.share = 0;
     return p;
-}
-
-// the rules a call through the sketch splits by (sketch_plan_batch, sketch_batch_sizes)
-static BatchRules sketch_batch_rules(int n_queries, int wide, int share, int query_batch)
-{
-    const int batch = std::max(1, std::min(query_batch, kMaxBatch));
-    // (a wide call is longer than kShortCall: first and last batch of kFirstBatch, 32 between them -- 64 in a shared call)
-    BatchRules r{share ? szg::kMatrixShareQueries : (wide ? szg::kMatrixWideQueries : batch), kFirstBatch,
-                 std::min(kShortCall, kMaxBatch), true, false};
-    // forced: batches of up to 32 (64) from the call's first query on, no small edges, no early tail
-    if (wide == 2) r = BatchRules{szg::kMatrixWideQueries, n_queries, szg::kMatrixWideQueries, false, false};
-    if (share == 2) r = BatchRules{szg::kMatrixShareQueries, n_queries, szg::kMatrixShareQueries, false, false};
-    return r;
 }
 
 void sketch_plan_batch(const szg_index *ix, int n_queries, int q0, int wide, Batch *b, int share)
 {
     plan_batch(ix->sketch, n_queries, q0, 0, sketch_batch_rules(n_queries, wide, share, ix->query_batch), b);
-}
-
-std::vector<int> sketch_batch_sizes(int n_queries, int wide, int share, int query_batch)
-{
-    std::vector<int> out;
-    const BatchRules r = sketch_batch_rules(n_queries, wide, share, query_batch);
-    for (int q0 = 0; q0 < n_queries;) {
-        const int nq = std::max(1, one_sweep_batch_size(n_queries, q0, r));
-        out.push_back(nq);
-        q0 += nq;
-    }
-    return out;
 }
 
 // ---- one search call through the sketch ---------------------------------------------------------------------------

@@ -36,9 +36,8 @@ LaunchGeom scan_geometry(int bits, const szg::RowMap &map, uint32_t row_bytes, b
     return LaunchGeom{(int)grid, block, (int)rows_per_block};
 }
 
-LaunchGeom scan_geometry(const szg_index *ix, const Shard *sh, int kp, bool plain_topk)
+LaunchGeom scan_geometry(const szg_index *ix, const Shard *sh, int kp)
 {
-    (void)plain_topk;
     return scan_geometry(ix->bits, ix->map, ix->row_bytes, ix->layout.tiled != 0, sh->n_rows, sh->cu_count, kp);
 }
 
@@ -196,19 +195,11 @@ int launch_scans_chained(szg_index *ix, Shard *sh, Ctx *c, const std::vector<szg
     });
     if (rc) return rc;
     std::lock_guard<std::mutex> lk(ix->stats_mu);
-    uint64_t sweeps = 0;  // passes over the rows: one per group of a launch's queries (one per query where the launch
-                          // does not qualify for groups); a shared launch counts one per column group, as requested --
-                          // what its second reader finds on the die is not taken off
-    // (a masked form: one pass per group of the form it takes, as scan_passes counts the unmasked launch)
+    uint64_t sweeps = 0;  // passes over the rows (launch_passes), of the variant the launcher above took
     for (int j = 0; j < n; j++) {
-        if (shared(j)) {
-            sweeps += (uint64_t)((a[j].n_queries + szg::kMatrixWideQueries - 1) / szg::kMatrixWideQueries);
-        } else if (mxm[j]) {
-            const int group = szg::scan_variant(szg::scan_masked_plan_in(ix->bits, a[j], ix->sketch_share, ix->sketch_masked, g.block)).group;
-            sweeps += (uint64_t)((a[j].n_queries + group - 1) / group);
-        } else {
-            sweeps += (uint64_t)szg::scan_passes(ix->bits, a[j], g.block);
-        }
+        sweeps += (uint64_t)launch_passes(mxm[j] ? szg::scan_masked_plan_in(ix->bits, a[j], ix->sketch_share, ix->sketch_masked, g.block)
+                                          : (shared(j) ? szg::scan_share_plan_in(ix->bits, a[j], (*hi)[j], g.block)
+                                                       : szg::scan_plan_in(ix->bits, a[j], g.block)));
         if (mxm[j]) {
             ix->mx_masked_launches++;
             ix->mx_masked_queries += (uint64_t)a[j].n_queries;
@@ -245,63 +236,43 @@ double mask_pass_rate(const Shard *sh, const Ctx *c, bool has_allow, int slot)
     return live * (seen ? (double)ones / (double)seen : 1.0);
 }
 
-// List length m of a sketch sweep over `grid` blocks (option sketch_list).  The query's kp best rows
-// fall about kp / grid to a block; automatic lists hold twice that plus 8 (8 at 512 blocks), so a block rarely has
-// more of them than its list keeps -- and when it has, the drop bound says so and the query falls back.  m >= kp (or
-// lists the one-launch merge cannot hold): the full lists and the two-level merge.
-int sketch_list_len(int want, int kp, int grid)
+SketchShape sketch_shape(const szg_index *ix, const szg_index *sk)
 {
-    const int m = want > 0 ? want : std::max(8, 2 * kp / std::max(grid, 1) + 8);
-    if (m >= kp || !szg::merge_short_fits(grid, m, kp)) return kp;
-    return m;
+    SketchShape s{};
+    s.bits = sk->bits;
+    s.map = sk->map;
+    s.tiled = sk->layout.tiled != 0;
+    s.ring = sk->ring;
+    s.no_shape_kernels = !sk->shape_kernels;
+    s.scan_group = sk->scan_group;
+    s.planes = scan_planes(sk);
+    s.scan_group_ring = sk->scan_group_ring;
+    s.sketch_matrix = sk->sketch_matrix;
+    s.sketch_select = sk->sketch_select;
+    s.sketch_wide = sk->sketch_wide;
+    s.sketch_share = sk->sketch_share;
+    s.sketch_masked = sk->sketch_masked;
+    s.sketch_list = ix->sketch_list;
+    s.query_batch = ix->query_batch;
+    s.queries_per_launch = sk->queries_per_launch;
+    s.norms = true;
+    return s;
 }
 
 bool sketch_wide_serves(const szg_index *sk, const Shard *sh, int kp, int list_opt)
 {
-    const bool collect = kp == 0;  // (no lists: nothing of kp or list_opt bears on the answer)
-    // (dead rows: a top-k launch takes the masked form of the same shape under sketch_masked = 1; a collect launch never)
-    if (sk->sketch_wide == 1 || (sh->has_dead && (collect || sk->sketch_masked != 1)) || kp > 64) return false;
-    const LaunchGeom g = scan_geometry(sk, sh, kp, true);
-    const int m = collect ? 0 : sketch_list_len(list_opt, kp, g.grid);
-    szg::ScanPlanIn in{sk->bits, sk->map, sk->layout.tiled != 0, m, collect, false, sk->ring, !sk->shape_kernels};
-    in.group = sk->scan_group;
-    in.n_queries = szg::kMatrixWideQueries;
-    in.block = g.block;
-    in.planes = scan_planes(sk);
-    in.group_ring = sk->scan_group_ring;
-    in.matrix_opt = sk->sketch_matrix;
-    in.norms = true;
-    in.select_opt = sk->sketch_select;
-    in.wide_opt = sk->sketch_wide;
-    return szg::scan_variant(in).wide != 0;
-}
-
-ShareGeom share_geometry(const LaunchGeom &g, int list_opt, int kp)
-{
-    const int grid = szg::share_grid(g.grid);
-    const int S = szg::share_slices(grid);
-    return ShareGeom{grid, S, sketch_list_len(list_opt, kp, S)};
+    SketchShape s = sketch_shape(sk, sk);
+    s.sketch_list = list_opt;
+    const LaunchGeom g = scan_geometry(sk, sh, kp);
+    return sketch_wide_serves(s, g.grid, g.block, sh->has_dead, kp);
 }
 
 bool sketch_share_serves(const szg_index *sk, const Shard *sh, int kp, int list_opt)
 {
-    if (sk->sketch_share == 1 || kp < 1 || (sh->has_dead && sk->sketch_masked != 1) || !sketch_wide_serves(sk, sh, kp, list_opt))
-        return false;
-    // (the wide form was asked with the plain launch's list length; the shared launch's S lists may be longer)
-    const LaunchGeom g = scan_geometry(sk, sh, kp, true);
-    const ShareGeom s = share_geometry(g, list_opt, kp);
-    szg::ScanPlanIn in{sk->bits, sk->map, sk->layout.tiled != 0, s.m, false, false, sk->ring, !sk->shape_kernels};
-    in.group = sk->scan_group;
-    in.n_queries = szg::kMatrixShareQueries;
-    in.block = g.block;
-    in.planes = scan_planes(sk);
-    in.group_ring = sk->scan_group_ring;
-    in.matrix_opt = sk->sketch_matrix;
-    in.norms = true;
-    in.select_opt = sk->sketch_select;
-    in.wide_opt = sk->sketch_wide;
-    in.share_opt = sk->sketch_share;
-    return szg::scan_variant(in).share != 0;
+    SketchShape s = sketch_shape(sk, sk);
+    s.sketch_list = list_opt;
+    const LaunchGeom g = scan_geometry(sk, sh, kp);
+    return sketch_share_serves(s, g.grid, g.block, sh->has_dead, kp);
 }
 
 // top-k pass for the nq staged queries of one shard: scan -> merges -> rerank -> D2H (async)
@@ -316,26 +287,13 @@ int enqueue_topk(szg_index *ix, Shard *sh, Ctx *c, int kp, int nq, bool has_allo
     c->pass.out_stride = stride;
     c->pass.keys = ListKeys::Single;
     HIPCHK(hipSetDevice(sh->device));
-    // (masked: the launches have masks AND keep the one-query kernel; under sketch_masked = 1 they split and launch as the
-    // unmasked call of the same size does, and every launch that qualifies takes the matrix sweep's masked form)
-    const bool masked = (has_allow || sh->has_dead) && !(on && ix->sketch_masked == 1);
-    LaunchGeom g = scan_geometry(ix, sh, kp, !masked);
-    // One part -- or, for a short call (Pass::early_n), two: the sweeps of queries [0, early_n), whose merges, re-rank and
-    // copy-back leave the scan stream for the context's own (one event), and the last few queries, whose tail is all
-    // that is left to do after the call's final sweep.
-    const int early = c->pass.early_n > 0 && c->pass.early_n < nq ? c->pass.early_n : 0;
-    // (a shared batch of the sketch pre-pass: 33 .. 64 queries in ONE launch of the matrix sweep's shared form, on a grid
-    // of 2 S blocks that leaves S lists per query -- unmasked, on every row, in one part)
-    const bool share = on && on->share && !masked && !early && nq > szg::kMatrixWideQueries &&
-                       nq <= szg::kMatrixShareQueries && sketch_share_serves(ix, sh, kp, on->list);
-    int lists0 = g.grid;                                            // block lists per query the sweeps leave
-    int m = on ? sketch_list_len(on->list, kp, g.grid) : kp;  // entries per wave and block list
-    if (share) {
-        const ShareGeom sg = share_geometry(g, on->list, kp);
-        g.grid = sg.grid;
-        lists0 = sg.slices;
-        m = sg.m;
-    }
+    // the batch's launches on this shard (sketch_plan.h): parts, forms, queries per launch, grid and lists
+    LaunchGeom g = scan_geometry(ix, sh, kp);
+    const SketchLaunches L = sketch_batch_launches(sketch_shape(on ? on->ix : ix, ix), on != nullptr, g.grid, g.block, kp, nq,
+                                                   c->pass.early_n, has_allow || sh->has_dead, on && on->wide, on && on->share);
+    const bool share = L.share;
+    const int lists0 = L.lists0, m = L.m, qpl = L.qpl;
+    g.grid = L.grid;
     if (on && on->extra < 1) return fail(SZG_E_INVALID, "sketch: no slot for the drop bound");
     int rc = c->ensure_lists((size_t)nq * lists0 * m);
     if (rc == SZG_OK) rc = c->d_out.ensure((size_t)nq * stride);
@@ -343,26 +301,17 @@ int enqueue_topk(szg_index *ix, Shard *sh, Ctx *c, int kp, int nq, bool has_allo
     if (rc) return rc;
     if (on && c->d_sent.capacity() < (size_t)nq * stride) return fail(SZG_E_INVALID, "sketch candidates not staged");
 
-    // (a wide batch of the sketch pre-pass: launches of up to 32 queries where the two-block matrix sweep serves them --
-    // unmasked, on every row: the same question the call asked before it planned wide batches)
-    const bool wide = on && on->wide && !masked && nq > szg::kMatrixQueries && sketch_wide_serves(ix, sh, kp, on->list);
-    const int qpl = share ? szg::kMatrixShareQueries : (wide ? szg::kMatrixWideQueries : std::max(1, ix->queries_per_launch));
-    for (int part = early ? 1 : 0; part >= 0; part--) {
-        const int q0 = part ? 0 : early, q1 = part ? early : nq, nqp = q1 - q0;
+    for (int part = L.first_part(); part >= 0; part--) {
+        const int q0 = L.q0(part), q1 = L.q1(part), nqp = q1 - q0;
         hipStream_t tl = part ? c->stream : c->pass.work;
-        std::vector<szg::ScanArgs> args((nqp + qpl - 1) / qpl);
+        std::vector<szg::ScanArgs> args(L.n_launches(part));
         std::vector<szg::ScanShareHi> hi(share ? args.size() : 0);
         for (int j = q0; j < q1; j += qpl) {  // one sweep per query, results side by side
             szg::ScanArgs &a = args[(j - q0) / qpl];
-            fill_scan_args(ix, sh, c, has_allow, j, std::min(qpl, q1 - j), &a);
+            fill_scan_args(ix, sh, c, has_allow, j, L.count(part, j), &a);
             a.mask_dense = mask_dense_vote(ix, sh, c, has_allow, j, a.n_queries);
             a.kp = m;
-            // (a call with wide batches: its launches take the matrix sweep whatever their count -- a rest of one or two
-            // queries too -- so that a query's keys do not depend on where the batches' edges fall)
-            if (on && on->wide && a.matrix == 0) a.matrix = 2;
-            // (a call that keeps more than 64 candidates per query -- lists that would not fit registers at full length --
-            // stays with the grouped kernels even where its short lists would fit)
-            if (kp > 64) a.matrix = 1;
+            a.matrix = L.matrix;
             a.block_lists = c->d_lists_a + (size_t)j * lists0 * m;
             if (share) {  // the constants of the launch's queries 32 .. 63, and the option
                 szg::ScanShareHi &h = hi[(j - q0) / qpl];
@@ -823,20 +772,6 @@ std::vector<const szg_mask *> Batch::handles(const QueryMasks &mask_of) const
     return h;
 }
 
-constexpr int kShortCallLast = 4;  // queries of a short call whose tail is left for after the final sweep
-
-int one_sweep_batch_size(int n_queries, int q0, const BatchRules &r)
-{
-    const int left = n_queries - q0;
-    if (q0 == 0 && n_queries <= r.short_max) return n_queries;
-    int nq = std::min(r.batch, left);
-    if (left > r.edge) {
-        if (q0 == 0) nq = std::min(nq, r.edge);
-        else if (left <= r.batch + r.edge) nq = left - r.edge;
-    }
-    return nq;
-}
-
 void plan_batch(szg_index *ix, int n_queries, int q0, int nb, const BatchRules &r, Batch *b)
 {
     const int left = n_queries - q0;
@@ -852,22 +787,11 @@ void plan_batch(szg_index *ix, int n_queries, int q0, int nb, const BatchRules &
         b->nq = std::min(left, 16 * nb * (two_groups ? 2 : 1));
         return;
     }
-    // A short call with one sweep per query is ONE batch on the scan stream (launches of <= 16 sweeps back to back,
-    // uploads ahead of them, no event on the critical path).  From 8 queries on, the merges, re-rank, copy-back and
-    // host assembly of all but its last few queries run on the context's own stream and the calling thread WHILE the
-    // last sweeps run; only those last queries' tail is left after the final sweep.
-    if (q0 == 0 && n_queries <= r.short_max) {
-        b->single = true;
-        b->nq = n_queries;
-        static const bool no_early = getenv("SZG_NO_EARLY_TAIL") != nullptr;  // (A/B hook of scripts/dev_short.py)
-        if (r.early_tail && n_queries >= 8 && ix->serialize_scans && !no_early)
-            b->early_n = n_queries - std::min(kShortCallLast, n_queries / 2);
-        return;
-    }
-    // the call's FIRST batch is small, so that the card starts sweeping after a few microseconds of preparation
-    // instead of a whole batch's (the next batch is prepared while it sweeps) ... and its LAST one too: what is left
-    // to do once the last sweep has ended is that batch's merges, re-rank, copy-back and result assembly
+    // one sweep per query (sketch_plan.h): a short call is ONE batch on the scan stream, from 8 queries on in two parts
     b->nq = one_sweep_batch_size(n_queries, q0, r);
+    b->single = q0 == 0 && n_queries <= r.short_max;
+    static const bool no_early = getenv("SZG_NO_EARLY_TAIL") != nullptr;  // (A/B hook of scripts/dev_short.py)
+    if (b->single && !no_early) b->early_n = short_call_early(n_queries, r, ix->serialize_scans != 0);
 }
 
 int stage_query_forms(szg_index *ix, Batch &b, const double *q, bool int_planes,

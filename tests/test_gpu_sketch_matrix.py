@@ -20,7 +20,7 @@ import pytest
 import oracle as orc
 from syzgydb_amd import ScanIndex, _lib
 from syzgydb_amd import cert_check as cc
-from syzgydb_amd.index import scan_plan, scan_matrix_plan
+from syzgydb_amd.index import scan_plan, scan_matrix_plan, scan_share_plan
 
 pytestmark = pytest.mark.gpu
 
@@ -73,6 +73,35 @@ def test_launch_plan_of_this_file():
         assert min(launch_sizes(nq)) >= 3
     assert [matrix_passes(q) for q in (3, 16, 17, 40)] == [1, 2, 2, 4]
     assert [grouped_passes(q) for q in (3, 16, 17, 40)] == [1, 4, 5, 10]
+
+
+def test_call_plan_hook_counts_the_launches_the_card_makes():
+    """The call-plan hook (szg_debug_scan_share) and the launch path compute from the same plan (sketch_plan.h): for calls
+    of 7, 8, 17, 32 and 40 queries over 20 000 rows of 64 dimensions (cosine, k = 10, lists of 8) the launches the
+    statistics count and the passes of scan_bytes are the hook's and this file's launch_sizes -- [7], [4, 4], [13, 4],
+    [16, 12, 4] and [4, 16, 16, 4], the two parts of a short call included.  Exact where the sketch settled every query
+    (assert_pass_count's guard: a query handed over adds sweeps of the float32 rows)."""
+    dim, k, n = 64, 10, 20000
+    rng = np.random.default_rng(5200)
+    V = rng.standard_normal((n, dim)).astype(np.float32).astype(np.float64)
+    Qall = rng.standard_normal((40, dim))
+    assert [launch_sizes(q) for q in (7, 8, 32)] == [[7], [4, 4], [16, 12, 4]]
+    with open_sketched(dim, COS, devices=[0], sketch_list=8) as ix:
+        ix.load(orc.encode_rows(V, 32))
+        ix.trace_certificates(False)
+        for nq in (7, 8, 17, 32, 40):
+            what = ("call plan", nq)
+            hook = scan_share_plan(dim, 8, nq, kp=8)
+            assert hook["launches"] == len(launch_sizes(nq)) and hook["passes"] == matrix_passes(nq), (what, hook)
+            ix.reset_stats()
+            ix.search_topk(Qall[:nq], k)
+            st = ix.stats()
+            print(what, "launches", st["scan_launches"], "passes", sketch_passes(st, n, dim, what), "hook", hook["launches"],
+                  hook["passes"], "settled", st["sketch_queries"], "of", nq)
+            assert_pass_count(st, n, dim, nq, hook["passes"], what)
+            if DEFAULT_TUNABLES and st["sketch_queries"] == nq and st["escalations"] == 0 and st["full_replays"] == 0:
+                assert st["scan_launches"] == hook["launches"] == len(launch_sizes(nq)), (what, st, hook)
+                assert sketch_passes(st, n, dim, what) == hook["passes"] == matrix_passes(nq), (what, st, hook)
 
 
 def rows_per_step(dim):

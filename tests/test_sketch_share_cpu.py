@@ -89,7 +89,9 @@ def test_batches_of_the_automatic_rule():
 
 def test_batches_when_forced():
     for nq, want, launches, passes in ((33, [33], 1, 2), (64, [64], 1, 2), (65, [64, 1], 2, 3), (96, [64, 32], 2, 3),
-                                       (97, [64, 33], 2, 4), (136, [64, 64, 8], 3, 5), (32, [32], 2, 2)):   # (32: not a share call)
+                                       (97, [64, 33], 2, 4), (136, [64, 64, 8], 3, 5), (32, [32], 3, 3)):
+        # (32: not a share call but a short one under the default plan -- one batch whose sweeps launch in two parts, 28
+        # queries as 16 + 12 and then the last 4: the hook counts the launches the call makes, sketch_plan.h's)
         p = scan_share_plan(768, 8, nq, sketch_share=2)
         assert (p["batches"], p["launches"], p["passes"]) == (want, launches, passes), (nq, p)
 
