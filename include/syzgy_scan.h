@@ -889,7 +889,8 @@ int szg_index_sketch_topk_stats(szg_index *ix, szg_sketch_topk_stats *out);
  *                             under cosine, a non-finite query or radius, a widened radius of 1 or more under cosine
  *                             and a query with more candidates than the batch's buffers hold take the float32 sweep.
  *                             Same answers.  0 = never (the default): the option is new and off, as the top-k pre-pass
- *                             was -- built as an option, soaked by the fuzzers, made the default by a later change.
+ *                             was -- built as an option, soaked by the fuzzers (scripts/fuzz_gpu.py and
+ *                             scripts/fuzz_state.py), made the default by a later change.
  *                             Batches that share a sweep (radius_mq = 1, two queries or more) keep it.  Other values
  *                             are refused
  *     sketch_masked       0   1 = a top-k launch of the sketch pre-pass with tombstones or filter masks (one resident mask

@@ -2,7 +2,8 @@
 
 Random shapes (dim, quantization, metric, rows, k, batch size), filter masks, tombstones,
 two-shard handles, duplicate-heavy and scaled corpora, queries at and within a few float32 spacings of stored rows
-("coincident", at every row width), random tunables.  Every answer must be
+("coincident", at every row width), random tunables -- the options that are soaking (sketch_radius, sketch_masked,
+sketch_f64, sketch_topk_collect) and the sketch sweep's forms among them.  Every answer must be
 the oracle's: same rows in the same order, bit-equal float64 distances (NaN == NaN).
 
     python scripts/fuzz_gpu.py [seconds] [seed] [--iterations N] [--certificates]
@@ -30,6 +31,7 @@ args = ap.parse_args()
 budget, seed = args.seconds, args.seed
 rng = np.random.default_rng(seed)
 rng_near = np.random.default_rng([seed, 0x6E656172])   # the coincident queries' own stream: every other draw of a seed stays as it was
+rng_more = np.random.default_rng([seed, 0x6D6F7265])   # ... and OPTS_MORE's
 DIMS = [1, 2, 3, 5, 16, 17, 31, 32, 33, 64, 100, 128, 129, 384, 500, 768, 1024]
 OPTS = [("queries_per_launch", [1, 3, 16]), ("multi_query", [0, 1]), ("force_matrix", [0, 0, 1]),
         ("serialize_scans", [0, 1]), ("mq_min", [2, 8]), ("slack", [0, 16, 40]), ("mq_hits", [64, 1024]),
@@ -37,6 +39,11 @@ OPTS = [("queries_per_launch", [1, 3, 16]), ("multi_query", [0, 1]), ("force_mat
         ("force_no_refine", [0, 0, 1]), ("mask_dense", [0, 1]), ("coalesce", [0, 1]), ("finish_thread", [0, 1, 1]),
         ("radius_mq", [0, 1, 1]), ("query_batch", [5, 16]), ("scan_group", [0, 1, 2, 4]), ("sketch_radius", [0, 1, 1]),
         ("sketch_share", [0, 1, 2, 2]), ("sketch_topk_collect", [0, 1, 1])]
+# the options that are soaking and the sketch sweep's forms: drawn from a stream of their own (rng_more), so that every other
+# draw of a seed stays what it was before they were added
+OPTS_MORE = [("sketch_masked", [0, 1, 1]), ("sketch_f64", [0, 1, 1]), ("sketch_matrix", [0, 1, 2]), ("sketch_select", [0, 1]),
+             ("sketch_wide", [0, 1, 2]), ("sketch_bulk", [0, 1, 2]), ("sketch_planes", [0, 3]), ("scan_norms", [0, 1]),
+             ("scan_group_ring", [0, 4, 6])]
 
 
 def same(got_r, got_d, want_r, want_d):
@@ -56,7 +63,7 @@ def certificates(ix, rows, dim, bits, metric, Q, eligible, desc, call, radii=Non
     corpus = cert_check.Corpus(rows, dim, bits, metric)
     Q = np.atleast_2d(Q)
     dists = sketch = None
-    if np.isin(recs["pass_"], (1, 5)).any():   # sketch passes, top-k and radius
+    if np.isin(recs["pass_"], (1, 5, 6)).any():   # sketch passes, top-k and radius
         dists = np.stack([orc.all_distances(rows, dim, bits, metric, q) for q in Q])
         info = ix.sketch_info()
         if info["exists"] and info["in_sync"]:   # the sketch sweep's own keys and lists too (K_s, L_s, D)
@@ -133,6 +140,7 @@ while (it < args.iterations) if args.iterations else (time.time() < t_end):
     resident = allow is not None and rng.random() < 1 / 3   # the filters go up once, as masks on the card
     devices = [0, 0] if rng.random() < 0.25 else [0]
     opts = {name: int(rng.choice(vals)) for name, vals in OPTS if rng.random() < 0.3}
+    opts.update({name: int(rng_more.choice(vals)) for name, vals in OPTS_MORE if rng_more.random() < 0.3})
     dead = []
     desc = dict(it=it, bits=bits, metric=metric, dim=dim, n=n, nq=nq, k=k, kind=kind, coincident=coincident, masked=allow is not None,
                 resident=resident, devices=devices, opts=opts)
