@@ -549,7 +549,9 @@ int szg_index_overwrite_rows_dev(szg_index *ix, const uint64_t *rows, const szg_
  * float64 distances, counts, offsets, order, SZG_E_TRUNCATED -- on every path and under every option, because after
  * the conversion it IS that call: a small kernel on the queries' device writes the dense n_queries x dim float64 batch
  * into a buffer the handle keeps there, one copy brings it into pinned host memory, and the host prepares the queries
- * as ever (preparing them on the card is not part of this).  Outputs are host arrays.
+ * as ever (under option query_prep the batches of a top-k call through the sketch are prepared on the card, from the
+ * float64 batch that goes up for the re-rank; the copy to the host stays: settling and the fall-back read it).  Outputs
+ * are host arrays.
  * The queries may lie on ANY device of the process: they are copied, not swept, so nothing is "on another device".
  * Refusals: the descriptor's are the ingest's (n_queries source rows); everything else -- k, radii, masks, stale masks,
  *   capacity, NULL outputs -- is refused by the masked call as today, after the conversion.
@@ -770,6 +772,17 @@ typedef struct szg_sketch_topk_stats {
 int szg_index_sketch_topk_stats(szg_index *ix, szg_sketch_topk_stats *out);
 
 /*
+ * Option query_prep: which side prepared the queries of the handle's top-k calls through the sketch since szg_reset_stats,
+ * which clears the three counters.  A getter of its own beside szg_stats, as szg_index_sketch_topk_stats is.
+ */
+typedef struct szg_query_prep_stats {
+    uint64_t queries_dev;   /* queries of sketch top-k batches that the card prepared */
+    uint64_t queries_host;  /* ... and that the host prepared (every one under query_prep = 0) */
+    uint64_t launches;      /* launches of the preparing kernel: one per such batch and shard */
+} szg_query_prep_stats;
+int szg_index_query_prep_stats(szg_index *ix, szg_query_prep_stats *out);
+
+/*
  * Tunables (name, default, meaning): the seventeen a deployment could want.  All are safe to change between calls.
  * (Rounds 1-3 exposed another fifteen -- ring depths, waves per CU, stream placement, sweep kinds per row width --
  * whose values measurement settled; they are compile-time constants now, csrc/scan_internal.h, and A/B runs go
@@ -935,6 +948,21 @@ int szg_index_sketch_topk_stats(szg_index *ix, szg_sketch_topk_stats *out);
  *                             they do not enter automatic mode's window).  Same answers.  0 = never (the default while
  *                             the option soaks): no allocation, no launch, one test of the option.  Calls that share a
  *                             sweep (multi_query = 1, mq_min queries or more) keep it.  Other values are refused
+ *     query_prep          0   the queries of a top-k call through the sketch (szg_search_topk and its _masked and _dev forms,
+ *                             coalesced lone callers) are prepared ON THE CARD: a small kernel per batch and shard turns the
+ *                             float64 batch that is uploaded for the re-rank anyway into the sweep's 8-bit image and the
+ *                             five constants of each query, by the rule the host follows (csrc/query_prep.h: the same
+ *                             bytes and the same bit patterns, the two order-sensitive sums added in element order), the
+ *                             sweeps read the constants where the kernel wrote them, and the host receives them, for the
+ *                             certificates, by the time it settles the batch.  Keys, lists, certificates and answers are
+ *                             the same bit for bit.  0 = never (the default while the option soaks): the host prepares
+ *                             every query, no allocation, no launch; 1 = batches of 8 queries or more (a lone search and
+ *                             the 4-query edges of a long call stay on the host: a launch would sit in front of their few
+ *                             sweeps); 2 = every batch, from one query on (the tests' setting).  Not covered, prepared on
+ *                             the host whatever the value: radius searches and sketch_topk_collect calls (they need the
+ *                             constants before their sweeps), the full-precision fall-back, shared sweeps (multi_query),
+ *                             plain 8-bit and 4-bit handles.  szg_index_query_prep_stats counts both sides.  Other values
+ *                             are refused
  *   shared sweeps
  *     multi_query         1   batches of >= mq_min queries share ONE sweep of the corpus, the dot products on the
  *                             matrix cores: 64- / 32- / 16-bit rows on bfloat16 roundings (v_mfma_f32_16x16x32_bf16,
@@ -1126,9 +1154,24 @@ int szg_debug_scan_group_ring(int dim, int quant_bits, int kp, int scan_group, i
 /*
  * Test hook, host only: would szg_set_option accept `value` for the one-sweep kernel's option `name` (scan_group,
  * scan_group_ring, scan_norms, sketch_planes, sketch_matrix, sketch_select, sketch_wide, sketch_share, sketch_bulk, sketch_radius,
- * sketch_masked, sketch_f64, sketch_topk_collect)?  SZG_OK, or SZG_E_INVALID with szg_set_option's text; any other name is refused.
+ * sketch_masked, sketch_f64, sketch_topk_collect, query_prep)?  SZG_OK, or SZG_E_INVALID with szg_set_option's text; any other name is refused.
  */
 int szg_debug_option_check(const char *name, int64_t value);
+
+/*
+ * Test hooks of option query_prep.
+ *   szg_debug_query_prep         the images (n_queries x 48 * ceil(dim / 16) bytes: three planes of 16 bytes per 16-byte
+ *                                piece of a sketch row, whatever sketch_planes says) and constants (out_meta:
+ *                                n_queries x 5 doubles: qnorm, m1, qscale, qconst, qnorm2) that a sweep of the handle's
+ *                                sketch would be given for these queries, prepared by the host (on_card = 0) or by the
+ *                                kernel (1) -- through the search path's own scaling and launch wrapper.  Brings the sketch
+ *                                up to date first, as a search does; SZG_E_UNSUPPORTED on a handle without a sketch.
+ *   szg_debug_query_prep_serves  host only: does the card prepare a batch of batch_queries queries under the option's value
+ *                                (1 / 0)?  *out_min, if not NULL, receives the smallest batch that value 1 serves.
+ */
+int szg_debug_query_prep(szg_index *ix, const double *queries, int n_queries, int on_card, uint8_t *out_image,
+                         double *out_meta);
+int szg_debug_query_prep_serves(int option, int batch_queries, int *out_min);
 
 /*
  * Test hook, host only: *eps = the bound on |scan key - real-number key| that certification uses for a key `key` (in

@@ -14,6 +14,7 @@
 #                                             -> its collect form (radius searches through the sketch)
 #   scripts/kernel_resources.sh sample        -> kernels_sample_mx.hip (the sample pass of top-k through the sketch)
 #   scripts/kernel_resources.sh exact         -> kernels_exact.hip (re-rank, page-in, row gather, ...)
+#   scripts/kernel_resources.sh prep          -> kernels_query_prep.hip (a sketch batch's queries prepared on the card)
 #   scripts/kernel_resources.sh mask          -> kernels_mask.hip (device-resident filter masks)
 #   scripts/kernel_resources.sh column        -> kernels_column.hip (resident metadata columns)
 #   scripts/kernel_resources.sh column carry  -> kernels_column_carry.hip (columns carried across compaction / reorder)
@@ -26,6 +27,7 @@ elif [ "$kind" = scan ]; then src=kernels_scan.hip; def="-DSZG_QBITS=${2:?row wi
 elif [ "$kind" = sample ]; then src=kernels_sample_mx.hip; def=
 elif [ "$kind" = merge ]; then src=kernels_scan_merge.hip; def=
 elif [ "$kind" = exact ]; then src=kernels_exact.hip; def=-ffp-contract=off
+elif [ "$kind" = prep ]; then src=kernels_query_prep.hip; def=-ffp-contract=off
 elif [ "$kind" = mask ]; then src=kernels_mask.hip; def=
 elif [ "$kind" = column ] && [ "$part" = carry ]; then src=kernels_column_carry.hip; def=
 elif [ "$kind" = column ]; then src=kernels_column.hip; def=

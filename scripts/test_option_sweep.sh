@@ -64,6 +64,16 @@ for opts in ${SWEEP_SHARE_SETS-sketch_share=1 sketch_share=2}; do
       tests/test_gpu_sketch_select.py tests/test_gpu_sketch_wide.py tests/test_gpu_sketch_bulk.py \
       tests/test_gpu_sketch_share.py tests/test_gpu_certificates.py -m gpu -q -x
 done
+# a sketch batch's queries prepared on the card, every batch from one query on (2), on the same files, the masked, float64
+# and device-query files and its own (SWEEP_PREP_SETS="" skips them)
+for opts in ${SWEEP_PREP_SETS-query_prep=2}; do
+  run "sketched handles, $opts" tests/test_gpu_sketch.py tests/test_gpu_sketch_default.py tests/test_gpu_sketch_lists.py \
+      tests/test_gpu_sketch_state.py tests/test_gpu_sketch_planes.py tests/test_gpu_sketch_matrix.py \
+      tests/test_gpu_sketch_select.py tests/test_gpu_sketch_wide.py tests/test_gpu_sketch_bulk.py \
+      tests/test_gpu_sketch_share.py tests/test_gpu_sketch_masked.py tests/test_gpu_sketch_f64.py \
+      tests/test_gpu_search_dev.py tests/test_gpu_coincident.py tests/test_gpu_certificates.py \
+      tests/test_gpu_query_prep.py -m gpu -q -x
+done
 # the shared sweeps without the resident row norms (a test hook of its own: an environment variable read once per process)
 if [ -z "$SWEEP_SKIP_NORMS" ]; then
   opts=""

@@ -72,6 +72,8 @@ EXPORTS = [
     "szg_debug_key_eps",
     # top-k of large k through the sketch (option sketch_topk_collect): the counters and the sample plan hook
     "szg_index_sketch_topk_stats", "szg_debug_sample_plan",
+    # a sketch batch's queries prepared on the card (option query_prep): the counters, the two-sided hook, the batch rule
+    "szg_index_query_prep_stats", "szg_debug_query_prep", "szg_debug_query_prep_serves",
 ]
 # szg_cert_record.pass / .keys, szg_cert_entry.flags
 SZG_CERT_TOPK, SZG_CERT_SKETCH, SZG_CERT_ESCALATION, SZG_CERT_RADIUS_SINGLE, SZG_CERT_RADIUS_SHARED = range(5)
@@ -136,6 +138,10 @@ class SzgStats(ctypes.Structure):
 
 class SzgSketchTopkStats(ctypes.Structure):
     _fields_ = [(name, ctypes.c_uint64) for name in ("queries", "fallbacks", "sample_rows", "candidates", "overflows")]
+
+
+class SzgQueryPrepStats(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_uint64) for name in ("queries_dev", "queries_host", "launches")]
 
 
 class SzgSamplePlan(ctypes.Structure):
@@ -466,6 +472,13 @@ def load():
         L.szg_index_sketch_topk_stats.argtypes = [vp, ctypes.POINTER(SzgSketchTopkStats)]
         L.szg_debug_sample_plan.restype = ctypes.c_int
         L.szg_debug_sample_plan.argtypes = [ctypes.c_uint64] + [ctypes.c_int] * 5 + [ctypes.POINTER(SzgSamplePlan)]
+    if hasattr(L, "szg_index_query_prep_stats"):   # (an older build for an A/B run has no such option)
+        L.szg_index_query_prep_stats.restype = ctypes.c_int
+        L.szg_index_query_prep_stats.argtypes = [vp, ctypes.POINTER(SzgQueryPrepStats)]
+        L.szg_debug_query_prep.restype = ctypes.c_int
+        L.szg_debug_query_prep.argtypes = [vp, f64p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_uint8), f64p]
+        L.szg_debug_query_prep_serves.restype = ctypes.c_int
+        L.szg_debug_query_prep_serves.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
     if hasattr(L, "szg_debug_scan_collect"):
         L.szg_debug_scan_collect.restype = ctypes.c_int
         L.szg_debug_scan_collect.argtypes = ([ctypes.c_int] * 10 + [ctypes.POINTER(ctypes.c_int32)] * 3 +

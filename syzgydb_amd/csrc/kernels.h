@@ -127,7 +127,19 @@ struct ScanArgs {
     // collect mode of the matrix sweep's wide launch: the thresholds of sweeps kMaxSweepsPerLaunch .. kMatrixWideQueries - 1
     // (behind everything else, like row_norm: the offsets the other kernels read stay as they were)
     uint32_t thr_ukeys_hi[kMatrixWideQueries - kMaxSweepsPerLaunch];
+    // (behind everything else again) null, or the constants of the launch's queries on the card, five doubles each
+    // (query_prep.h, kQueryPrepMeta: written by launch_query_prep ahead of the launch on its stream; option query_prep):
+    // the kernels then take float(qscale), float(qconst), float(qnorm2) of query q from qmeta[5 q + 2, 3, 4] -- the
+    // conversions the host makes when it fills the arrays above, which are not read -- a shared launch all its 64
+    const double *qmeta;
 };
+// a query's constants as the row finish consumes them, from the card's table (ScanArgs::qmeta)
+__device__ inline void scan_qmeta(const double *qmeta, int q, float *qscale, float *qconst, float *qnorm2)
+{
+    *qscale = (float)qmeta[5 * q + 2];
+    *qconst = (float)qmeta[5 * q + 3];
+    *qnorm2 = (float)qmeta[5 * q + 4];
+}
 // the collect threshold of sweep s of a launch (s < kMatrixWideQueries)
 __host__ __device__ inline uint32_t &scan_thr_ukey(ScanArgs &a, int s)
 {
@@ -389,6 +401,14 @@ hipError_t launch_rerank(int qbits, int metric, const uint8_t *rows, RowLayout l
 hipError_t launch_rerank_pairs(int qbits, int metric, const uint8_t *rows, RowLayout layout, int dim,
                                const uint32_t *left_rows, const uint64_t *right_cands, uint32_t n_pairs,
                                RerankOut *out, hipStream_t stream);
+
+// ---- kernels_query_prep.hip: a sketch batch's queries prepared on the card (option query_prep) ------------------------
+// From nq float64 queries of `dim` elements at d_q64 (unscaled; gs > 0: each element is divided by gs first, the
+// Euclidean sketch's scale) to their 8-bit one-sweep images (qsw_bytes = 3 * r16 * 16 apart at d_qsw, `planes` digit
+// planes) and constants (d_meta: qnorm, m1, qscale, qconst, qnorm2 per query), by the rule of query_prep.h: the bytes
+// and bit patterns of the host form.  One workgroup per query.
+hipError_t launch_query_prep(const double *d_q64, int nq, int dim, double gs, int cosine, int planes, int r16, uint32_t qsw_bytes,
+                             uint8_t *d_qsw, double *d_meta, hipStream_t stream);
 
 // Page-in transform: n_rows rows in the reference encoding at `ref` (big-endian 16/32/64-bit,
 // row_bytes apart) <-> rows [first_row, first_row + n_rows) of the resident mirror `rows`.

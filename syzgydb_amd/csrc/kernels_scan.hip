@@ -544,6 +544,7 @@ __global__ __launch_bounds__(256, G > 1 ? kGroupMinBlocks : SZG_MIN_BLOCKS) void
         wls[x].init(mylist + (size_t)x * nwaves * a.kp, COLLECT ? 0 : a.kp, lane);
         const int q = slot_query(x);
         qcs[x] = QConst{a.qscale[q], a.qconst[q], a.qnorm2[q], (float)a.norm_bias};
+        if (a.qmeta) scan_qmeta(a.qmeta, q, &qcs[x].qscale, &qcs[x].qconst, &qcs[x].qnorm2);  // (prepared on the card)
     }
     [[maybe_unused]] WaveList &wl = wls[0];
     [[maybe_unused]] const QConst &qc = qcs[0];

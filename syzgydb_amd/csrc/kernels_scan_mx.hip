@@ -240,12 +240,13 @@ __global__ __launch_bounds__(256, (ROWS && NB == 1 && STEPS != 0 && SZG_MX_FOUR_
             const int q = min(qi + x, a.n_queries - 1);  // (block-uniform: scalar loads of the arguments)
 #ifdef SZG_MX_SHARE
             const bool hi_ = q >= kMatrixWideQueries;  // (q < kMatrixShareQueries: the launcher's bound)
-            const float qs = hi_ ? sa.hi.qscale[q - kMatrixWideQueries] : a.qscale[q];
-            const float qc = hi_ ? sa.hi.qconst[q - kMatrixWideQueries] : a.qconst[q];
-            const float qn = hi_ ? sa.hi.qnorm2[q - kMatrixWideQueries] : a.qnorm2[q];
+            float qs = hi_ ? sa.hi.qscale[q - kMatrixWideQueries] : a.qscale[q];
+            float qc = hi_ ? sa.hi.qconst[q - kMatrixWideQueries] : a.qconst[q];
+            float qn = hi_ ? sa.hi.qnorm2[q - kMatrixWideQueries] : a.qnorm2[q];
 #else
-            const float qs = a.qscale[q], qc = a.qconst[q], qn = a.qnorm2[q];
+            float qs = a.qscale[q], qc = a.qconst[q], qn = a.qnorm2[q];
 #endif
+            if (a.qmeta) scan_qmeta(a.qmeta, q, &qs, &qc, &qn);  // (prepared on the card: the table holds every query)
             [[maybe_unused]] uint32_t tk = 0;
             if constexpr (COLLECT) tk = q < kMaxSweepsPerLaunch ? a.thr_ukeys[q] : a.thr_ukeys_hi[q - kMaxSweepsPerLaunch];
             if (tid == x) {

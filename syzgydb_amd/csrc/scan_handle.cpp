@@ -652,6 +652,7 @@ int szg_reset_stats(szg_index *ix)
     ix->mask_h2d = ix->mask_d2d = ix->mask_shared = 0;  // (szg_mask_stats' counters; live masks stay counted)
     ix->mx_masked_launches = ix->mx_masked_skip = ix->mx_masked_queries = 0;  // (szg_debug_sketch_masked's)
     ix->sk_topk = szg_sketch_topk_stats{};  // (szg_index_sketch_topk_stats')
+    ix->qp = szg_query_prep_stats{};        // (szg_index_query_prep_stats')
     if (ix->sketch) {
         std::lock_guard<std::mutex> lk2(ix->sketch->stats_mu);
         ix->sketch->stats = szg_stats{};
@@ -679,6 +680,7 @@ static const char *scan_option_refusal(const std::string &n, int64_t value, bool
     if (n == "sketch_masked") return szg::sketch_masked_known(value) ? nullptr : "sketch_masked is 0 or 1";
     if (n == "sketch_f64") return value == 0 || value == 1 ? nullptr : "sketch_f64 is 0 or 1";
     if (n == "sketch_topk_collect") return value == 0 || value == 1 ? nullptr : "sketch_topk_collect is 0 or 1";
+    if (n == "query_prep") return value >= 0 && value <= 2 ? nullptr : "query_prep is 0, 1 or 2";
     *known = false;
     return nullptr;
 }
@@ -765,6 +767,9 @@ int szg_set_option(szg_index *ix, const char *name, int64_t value)
     } else if (n == "sketch_topk_collect") {
         // (read on the handle the call is made on, search_topk_any; the sketch index carries it unread)
         ix->sketch_topk_collect = (int)value;
+    } else if (n == "query_prep") {
+        // (read on the handle the call is made on, SketchCall::stage; the sketch index carries it unread)
+        ix->query_prep = (int)value;
     } else if (n == "query_batch") {
         if (value < 1 || value > kMaxBatch) return fail(SZG_E_INVALID, "query_batch out of range");
         ix->query_batch = (int)value;

@@ -7,7 +7,8 @@
 //   scan_topk.cpp     the batch pipeline of top-k and radius calls; one-sweep-per-query top-k, certification,
 //                     escalation, exact replay
 //   scan_mq.cpp       shared (multi-query) sweeps on the matrix cores
-//   scan_sketch.cpp   8-bit sketch pre-pass
+//   scan_sketch.cpp   8-bit sketch pre-pass (option query_prep: its top-k batches' queries prepared on the card --
+//                     query_prep.h: the rule, shared with scan_query.cpp; kernels_query_prep.hip: the kernel)
 //   scan_radius.cpp   radius search (single, batch, coalesced; through the sketch: sketch_radius; collect_plan.h: its buffers)
 //                     and top-k of large k through the sketch as a sample pass + that collect core (sketch_topk_collect;
 //                     sample_plan.h: its arithmetic; kernels_sample_mx.hip: its kernels)
@@ -36,6 +37,7 @@
 #include "../../include/syzgy_scan.h"
 #include "dev_mem.h"
 #include "kernels.h"
+#include "query_prep.h"
 #include "reorder_plan.h"
 #include "sketch_plan.h"
 
@@ -251,6 +253,12 @@ struct Pass {
     uint32_t allow_stride = 0;
     // HIP-event timing: scan launches between ev_scan0 and ev_scan1 / ev_p0 and ev_p1 (0 = that pair was not recorded)
     int timed_n = 0, timed_part_n = 0;
+    // option query_prep: the batch's prep_n staged queries were prepared on the card (enqueue_query_prep).  Their images
+    // are in d_qsw and nowhere else; their constants are in d_meta, where the sweeps read them (ScanArgs::qmeta), on
+    // their way to h_meta behind the kernel on `work` -- take_card_meta moves them into meta[] once that stream has
+    // been waited for (prep_taken), and until then meta[0 .. prep_n) is NOT the batch's
+    int prep_n = 0;
+    bool prep_taken = false;
 };
 
 // A context is what a batch borrows per shard: a stream, events and scratch buffers that persist between batches,
@@ -302,6 +310,10 @@ struct Ctx {
     DevBuf<uint64_t> d_sent;
     PinnedBuf<szg::RerankOut> h_sent_out;
     DevBuf<szg::RerankOut> d_sent_out;
+    // option query_prep: the constants of queries prepared on the card, szg::kQueryPrepMeta doubles each (allocated by
+    // the first such batch: a handle that leaves the option at 0 holds neither)
+    PinnedBuf<double> h_meta;
+    DevBuf<double> d_meta;
 
     // both ping-pong buffers grow together, and both are freed before either comes back
     int ensure_lists(size_t need)
@@ -465,6 +477,10 @@ struct szg_index {
                               // the sketch as a sample pass and a collect sweep (scan_radius.cpp, SketchTopkCall): 0 = never
                               // (the default while the option soaks), 1 = wherever the sample plan serves every shard
     szg_sketch_topk_stats sk_topk{};  // what that path served (stats_mu; szg_index_sketch_topk_stats, szg_reset_stats)
+    int query_prep = 0;       // the batches of a top-k call through the sketch have their queries prepared on the card
+                              // (kernels_query_prep.hip) instead of by prep_query: 0 = never (the default while the option
+                              // soaks), 1 = batches of kQueryPrepMin queries or more, 2 = every batch (query_prep_serves)
+    szg_query_prep_stats qp{};  // which side prepared such calls' queries (stats_mu; szg_index_query_prep_stats, szg_reset_stats)
     bool is_sketch = false;   // this index is the internal sketch of a float32 (or float64) handle: its keys only bound
     int tie_mode = 0;         // 0: exact full replay on ties/NaN, 1: keep the fast answer
     int serialize_scans = 1;  // scan launches of a shard never overlap each other
@@ -661,8 +677,20 @@ LaunchGeom scan_geometry(const szg_index *ix, const Shard *sh, int kp);
 size_t shard_words(const Shard *sh);
 // (handles: null, or the resident masks of the batch's queries -- then `masks` holds their host words -- and `shard_no`,
 // the shard's position in its index, which is also the position of its words in every handle)
+// (card_prep: null, or the Euclidean sketch scale (0: none) of a batch whose queries the card prepares -- option
+// query_prep: enqueue_query_prep behind the float64 upload instead of the single-query forms' upload, the constants' copy
+// to the host behind the event the sweeps wait for)
 int enqueue_queries(szg_index *ix, Shard *sh, Ctx *c, const double *q, int nq, const uint64_t *const *masks,
-                    bool with_single_form = true, const szg_mask *const *handles = nullptr, size_t shard_no = 0);
+                    bool with_single_form = true, const szg_mask *const *handles = nullptr, size_t shard_no = 0,
+                    const double *card_prep = nullptr);
+// Option query_prep: the 8-bit index's staged float64 queries [0, nq) of the context (d_q64, enqueued on pass.work) ->
+// their one-sweep images in d_qsw and constants in d_meta, on pass.work (szg::launch_query_prep; gs: the Euclidean
+// sketch's scale, 0 = none).  The search path and the hook szg_debug_query_prep both launch through here.
+int enqueue_query_prep(szg_index *ix, Ctx *c, int nq, double gs);
+// ... the copy of those constants to h_meta, on pass.work; and, once that stream has been waited for, their move into
+// meta[] (flags false, as prep_query leaves them).  Once per batch: further calls do nothing.
+int enqueue_card_meta_copy(Ctx *c);
+void take_card_meta(Ctx *c);
 void fill_scan_args(const szg_index *ix, const Shard *sh, const Ctx *c, bool has_allow, int slot, int nq,
                     szg::ScanArgs *a);
 // ... of a collect launch: query slot + j's key threshold thr[j], its buffer buf + j * cap and its counter

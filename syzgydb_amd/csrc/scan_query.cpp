@@ -1,6 +1,7 @@
 // scan_query.cpp -- the query as the kernels want it, and the bounds on what their arithmetic loses.
 #include "scan_internal.h"
 #include "key_bound.h"
+#include "query_prep.h"
 
 namespace szgi {
 
@@ -59,15 +60,8 @@ int row_format(int dim, int quant_bits, RowFormat *f)
     return f->qsw_bytes > 48u * 1024u ? SZG_E_UNSUPPORTED : SZG_OK;
 }
 
-// round to nearest (ties away from zero) without a libm call; NaN -> 0, clamped to +-lim.
-// Any rounding rule serves: Q only has to be within 1/2 of v/qscale (key_eps).
-inline long long round_clamp(double t, double lim)
-{
-    if (!(t == t)) return 0;
-    if (t > lim) t = lim;
-    if (t < -lim) t = -lim;
-    return (long long)(t + (t >= 0 ? 0.5 : -0.5));
-}
+// round to nearest (ties away from zero), NaN -> 0, clamped to +-lim: query_prep.h's, with the rest of the 8-bit rule
+inline long long round_clamp(double t, double lim) { return szg::qp_round_clamp(t, lim); }
 
 // Query as the scan wants it (see RowAcc in kernels_scan.hip):
 //  * 16/32/64-bit rows: float (double for 64-bit), pre-normalised for cosine,
@@ -80,26 +74,10 @@ inline long long round_clamp(double t, double lim)
 // |prepared element| and the scale q -> prepared query.
 static double prep_query_norms(const szg_index *ix, const double *q, QMeta *meta, double *scale_out)
 {
-    const int dim = ix->dim, bits = ix->bits;
     *meta = QMeta{};
-    double m1 = 0.0;
-    for (int i = 0; i < dim; i++) m1 += q[i] * q[i];
-    meta->m1 = m1;
-    double scale = 1.0;
-    if (ix->metric == SZG_COSINE) {
-        scale = m1 > 0 ? 1.0 / std::sqrt(m1) : 0.0;
-    } else if (bits <= 16) {
-        scale = (double)((1u << bits) - 1u);
-    }
-    double nrm = 0.0, vmax = 0.0;
-    for (int e = 0; e < dim; e++) {
-        const double v = q[e] * scale;
-        nrm += v * v;
-        vmax = std::max(vmax, std::fabs(v));
-    }
-    meta->qnorm = std::sqrt(nrm);
-    meta->qnorm2 = nrm;
-    *scale_out = scale;
+    double vmax;  // (query_prep.h: the sums in element order, vmax by std::max's rule)
+    szg::qp_norms(q, ix->dim, ix->metric == SZG_COSINE ? 1 : 0, ix->bits, &meta->m1, scale_out, &meta->qnorm2, &vmax);
+    meta->qnorm = szg::qp_canon(std::sqrt(meta->qnorm2));
     return vmax;
 }
 
@@ -119,10 +97,13 @@ void prep_query(const szg_index *ix, const double *q, uint8_t *out_sw, QMeta *me
     memset(out_sw, 0, ix->qsw_bytes);
     double scale;
     const double vmax = prep_query_norms(ix, q, meta, &scale);
-    if (bits == 8 || bits == 4) {
-        // (a sketch index quantizes to two planes: |Q| <= 16000 leaves the h plane all zero, scan_planes)
-        const double Qmax = bits == 8 ? scan_qmax8(ix) : szg::kQmax4;
-        const int top8 = 3 - scan_planes(ix);  // the plane that takes what is left of Q (|m| <= 125 with two planes)
+    if (bits == 8) {  // the rule of query_prep.h, which the card follows too (option query_prep)
+        meta->qscale = szg::qp_step(vmax, scan_qmax8(ix));
+        meta->qconst = szg::qp_image8(q, dim, scale, meta->qscale, scan_planes(ix), r16, out_sw);
+        return;
+    }
+    if (bits == 4) {
+        const double Qmax = szg::kQmax4;
         const double qs = (vmax > 0 && std::isfinite(vmax)) ? vmax / Qmax : 1.0;
         meta->qscale = qs;
         double sumQ = 0.0;
@@ -131,19 +112,7 @@ void prep_query(const szg_index *ix, const double *q, uint8_t *out_sw, QMeta *me
             long long Q = round_clamp(q[e] * scale / qs, Qmax);
             sumQ += (double)Q;
             const int j = e / E, i = e % E;
-            if (bits == 8) {
-                const int d = i / 4, kb = i % 4;
-                for (int x = 2; x >= top8; x--) {  // planes: 0 = h (x16384), 1 = m (x128), 2 = l
-                    long long dig;
-                    if (x > top8) {
-                        dig = ((Q + 64) & 127) - 64;
-                        Q = (Q - dig) >> 7;
-                    } else {
-                        dig = Q;
-                    }
-                    planes[((size_t)x * r16 + j) * 4 + d] |= (uint32_t)((uint8_t)(int8_t)dig) << (8 * kb);
-                }
-            } else {
+            {
                 // byte b of the piece holds element 2b in its high nibble, 2b+1 in the low one
                 const int bb = i / 2, d = bb / 4, kb = bb % 4;
                 const int t4 = 2 * kb + ((i % 2 == 0) ? 1 : 0);

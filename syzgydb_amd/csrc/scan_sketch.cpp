@@ -409,13 +409,22 @@ int SketchCall::stage(Batch &b)
     const std::vector<const uint64_t *> masks = b.masks(mask_of);
     const uint64_t *const *mptr = b.any_mask ? masks.data() : nullptr;
     const std::vector<const szg_mask *> handles = b.handles(mask_of);
-    const double *q_sk = q;
-    if (p.gs > 0.0) {
-        q_scaled.resize((size_t)b.nq * dim);
-        for (size_t i = 0; i < q_scaled.size(); i++) q_scaled[i] = q[i] / p.gs;
-        q_sk = q_scaled.data();
+    // option query_prep: the card prepares the batch from the float64 queries that go up for the rerank anyway (the
+    // division by gs, the image, the constants: query_prep.h) -- no host loop here, no image upload below.  The sweeps
+    // read the constants on the card (ScanArgs::qmeta); the host gets them in finish(), before the first settle.
+    // Nothing between here and there reads the contexts' h_qsw or meta[] for such a batch: fill_scan_args, the one
+    // reader there was, hands the kernels the card's table instead.
+    const bool on_card = query_prep_serves(ix->query_prep, b.nq);
+    int rc = SZG_OK;
+    if (!on_card) {
+        const double *q_sk = q;
+        if (p.gs > 0.0) {
+            q_scaled.resize((size_t)b.nq * dim);
+            for (size_t i = 0; i < q_scaled.size(); i++) q_scaled[i] = q[i] / p.gs;
+            q_sk = q_scaled.data();
+        }
+        rc = stage_query_forms(sk, b, q_sk, false, [](int, QMeta &) {});
     }
-    int rc = stage_query_forms(sk, b, q_sk, false, [](int, QMeta &) {});
     // behind each query's list: the drop bound's slot (the short-list merge writes it), its first k eligible rows of
     // the shard (kInvalidCand-padded to k), then the shard's eligible rows without a usable sketch
     for (size_t s = 0; s < n_sh && rc == SZG_OK; s++) {
@@ -438,6 +447,7 @@ int SketchCall::stage(Batch &b)
         }
     }
     const double t_enq0 = now_us();
+    uint64_t n_prep_launches = 0;
     for (size_t s = 0; s < n_sh && rc == SZG_OK; s++) {
         Ctx *c = b.ctx[s];
         if (!c) continue;
@@ -453,11 +463,18 @@ int SketchCall::stage(Batch &b)
         }
         // (the float64 queries unscaled: the rerank is on the rows; a resident mask's shard words serve the sketch
         // shard too: same rows, same device)
-        rc = enqueue_queries(sk, h, c, q, b.nq, mptr, true, handles.empty() ? nullptr : handles.data(), s);
+        rc = enqueue_queries(sk, h, c, q, b.nq, mptr, !on_card, handles.empty() ? nullptr : handles.data(), s,
+                             on_card ? &p.gs : nullptr);
+        if (rc == SZG_OK && on_card) n_prep_launches++;
         const RerankOn on{ix, ix->shards[s], extra[s], ix->sketch_list, p.wide != 0 || p.share != 0, p.share != 0};
         if (rc == SZG_OK) rc = enqueue_topk(sk, h, c, kp, b.nq, b.any_mask, &on);
     }
     note_stage_times(ix, t_prep0, t_enq0);
+    if (rc == SZG_OK) {
+        std::lock_guard<std::mutex> lk(ix->stats_mu);
+        (on_card ? ix->qp.queries_dev : ix->qp.queries_host) += (uint64_t)b.nq;
+        ix->qp.launches += n_prep_launches;
+    }
     return rc;
 }
 
@@ -562,6 +579,9 @@ int SketchCall::finish(Batch &b)
             if (e == hipSuccess && phase) e = hipStreamSynchronize(c->stream);
             if (e != hipSuccess) rc = fail(SZG_E_DEVICE, "hipStreamSynchronize", e);
             if (rc == SZG_OK && phase) rc = finish_timing(sk, c);
+            // (queries prepared on the card: their constants' copy was enqueued on pass.work ahead of the sweeps.  An
+            // early part's stream waited for its sweeps, which are behind that copy on the scan stream)
+            if (rc == SZG_OK) take_card_meta(c);
         }
         if (rc) break;
         const double t0 = now_us();
@@ -667,3 +687,85 @@ int search_topk_any(szg_index *ix, const double *queries, int n_queries, int k, 
 }
 
 }  // namespace szgi
+
+using szgi::fail;
+
+extern "C" {
+
+int szg_index_query_prep_stats(szg_index *ix, szg_query_prep_stats *out)
+{
+    if (!ix || !out) return fail(SZG_E_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(ix->stats_mu);
+    *out = ix->qp;
+    return SZG_OK;
+}
+
+// host only: the batch rule of option query_prep (sketch_plan.h)
+int szg_debug_query_prep_serves(int option, int batch_queries, int *out_min)
+{
+    if (out_min) *out_min = szgi::kQueryPrepMin;
+    return szgi::query_prep_serves(option, batch_queries) ? 1 : 0;
+}
+
+// what a sweep of the handle's sketch would be given for these queries: by prep_query (on_card = 0) or by the kernel (1),
+// scaled as SketchCall::stage scales them and launched through enqueue_query_prep as a served batch's are
+int szg_debug_query_prep(szg_index *ix, const double *queries, int n_queries, int on_card, uint8_t *out_image, double *out_meta)
+{
+    SZG_TRY
+    using namespace szgi;
+    if (!ix || !queries || !out_image || !out_meta) return fail(SZG_E_INVALID, "null argument");
+    if (n_queries < 0 || (on_card != 0 && on_card != 1)) return fail(SZG_E_INVALID, "n_queries >= 0, on_card is 0 or 1");
+    if (!sketch_applies_rows(ix)) return fail(SZG_E_UNSUPPORTED, "query_prep: the handle keeps no sketch");
+    int rc = sketch_sync_for_search(ix);
+    if (rc) return rc;
+    szg_index *sk = ix->sketch;
+    if (!sk || ix->sk_disabled || ix->sk_nomem) return fail(SZG_E_UNSUPPORTED, "query_prep: the handle keeps no sketch");
+    const double gs = ix->sk_gscale;  // (sketch_call_plan's p.gs)
+    const int dim = ix->dim;
+    const size_t qb = sk->qsw_bytes;
+    if (!on_card) {
+        std::vector<double> scaled(dim);
+        for (int j = 0; j < n_queries; j++) {
+            const double *q = queries + (size_t)j * dim;
+            if (gs > 0.0) {
+                for (int e = 0; e < dim; e++) scaled[e] = q[e] / gs;
+                q = scaled.data();
+            }
+            QMeta m;
+            prep_query(sk, q, out_image + (size_t)j * qb, &m);
+            double *o = out_meta + (size_t)j * szg::kQueryPrepMeta;
+            o[szg::kQpQnorm] = m.qnorm;
+            o[szg::kQpM1] = m.m1;
+            o[szg::kQpQscale] = m.qscale;
+            o[szg::kQpQconst] = m.qconst;
+            o[szg::kQpQnorm2] = m.qnorm2;
+        }
+        return SZG_OK;
+    }
+    Shard *sh = nullptr;
+    for (Shard *s : sk->shards)
+        if (s->n_rows) {
+            sh = s;
+            break;
+        }
+    if (!sh) return fail(SZG_E_UNSUPPORTED, "query_prep: the sketch has no rows");
+    CtxGuard g{sh, ctx_acquire(sh)};
+    Ctx *c = g.c;
+    HIPCHK(hipSetDevice(sh->device));
+    for (int j0 = 0; j0 < n_queries; j0 += kMaxBatch) {
+        const int nq = std::min(kMaxBatch, n_queries - j0);
+        memcpy(c->h_q64, queries + (size_t)j0 * dim, sizeof(double) * dim * nq);
+        HIPCHK(hipMemcpyAsync(c->d_q64, c->h_q64, sizeof(double) * dim * nq, hipMemcpyHostToDevice, c->pass.work));
+        rc = enqueue_query_prep(sk, c, nq, gs);
+        if (rc == SZG_OK) rc = enqueue_card_meta_copy(c);
+        if (rc) return rc;
+        // (d_qsw has no pinned twin on this path: h_qsw is the host form's)
+        HIPCHK(hipMemcpyAsync(out_image + (size_t)j0 * qb, c->d_qsw, qb * nq, hipMemcpyDeviceToHost, c->pass.work));
+        HIPCHK(hipStreamSynchronize(c->pass.work));
+        memcpy(out_meta + (size_t)j0 * szg::kQueryPrepMeta, c->h_meta, sizeof(double) * szg::kQueryPrepMeta * nq);
+    }
+    return SZG_OK;
+    SZG_CATCH
+}
+
+}  // extern "C"

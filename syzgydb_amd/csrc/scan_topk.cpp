@@ -43,6 +43,43 @@ LaunchGeom scan_geometry(const szg_index *ix, const Shard *sh, int kp)
 
 size_t shard_words(const Shard *sh) { return (size_t)((sh->n_rows + 63) / 64); }
 
+// ---- option query_prep: a batch's queries prepared on the card (scan_internal.h) ----------------------------------------
+int enqueue_query_prep(szg_index *ix, Ctx *c, int nq, double gs)
+{
+    if (ix->bits != 8 || nq < 1 || nq > kMaxBatch) return fail(SZG_E_INVALID, "query_prep: an 8-bit index's batch");
+    int rc = c->d_meta.ensure((size_t)kMaxBatch * szg::kQueryPrepMeta);
+    if (rc == SZG_OK) rc = c->h_meta.ensure((size_t)kMaxBatch * szg::kQueryPrepMeta);
+    if (rc) return rc;
+    HIPCHK(szg::launch_query_prep(c->d_q64, nq, ix->dim, gs, ix->metric == SZG_COSINE ? 1 : 0, scan_planes(ix), ix->map.r16,
+                                  (uint32_t)ix->qsw_bytes, c->d_qsw, c->d_meta, c->pass.work));
+    c->pass.prep_n = nq;
+    c->pass.prep_taken = false;
+    return SZG_OK;
+}
+
+int enqueue_card_meta_copy(Ctx *c)
+{
+    HIPCHK(hipMemcpyAsync(c->h_meta, c->d_meta, sizeof(double) * szg::kQueryPrepMeta * (size_t)c->pass.prep_n,
+                          hipMemcpyDeviceToHost, c->pass.work));
+    return SZG_OK;
+}
+
+void take_card_meta(Ctx *c)
+{
+    if (!c->pass.prep_n || c->pass.prep_taken) return;
+    for (int j = 0; j < c->pass.prep_n; j++) {
+        const double *m = c->h_meta + (size_t)j * szg::kQueryPrepMeta;
+        QMeta &o = c->meta[j];
+        o = QMeta{};
+        o.qnorm = m[szg::kQpQnorm];
+        o.m1 = m[szg::kQpM1];
+        o.qscale = m[szg::kQpQscale];
+        o.qconst = m[szg::kQpQconst];
+        o.qnorm2 = m[szg::kQpQnorm2];
+    }
+    c->pass.prep_taken = true;
+}
+
 // Enqueue H2D of nq prepared queries (+ their masks) on the ctx stream.
 // masks: nullptr (no query of the batch is filtered), or nq pointers to index-level masks
 // ((total_rows + 63) / 64 words each); a null entry allows every row.
@@ -51,7 +88,7 @@ size_t shard_words(const Shard *sh) { return (size_t)((sh->n_rows + 63) / 64); }
 //   resident masks that differ, or some null   one mask_gather launch fills the batch's d_allow slots card-to-card
 //   words from the host                        staged in pinned memory and uploaded, as before
 int enqueue_queries(szg_index *ix, Shard *sh, Ctx *c, const double *q, int nq, const uint64_t *const *masks,
-                    bool with_single_form, const szg_mask *const *handles, size_t shard_no)
+                    bool with_single_form, const szg_mask *const *handles, size_t shard_no, const double *card_prep)
 {
     HIPCHK(hipSetDevice(sh->device));
     memcpy(c->h_q64, q, sizeof(double) * ix->dim * nq);
@@ -65,6 +102,11 @@ int enqueue_queries(szg_index *ix, Shard *sh, Ctx *c, const double *q, int nq, c
             HIPCHK(hipMemcpyAsync(c->d_qsw, c->h_qsw, ix->qsw_bytes * nq, hipMemcpyHostToDevice, c->pass.work));
         HIPCHK(hipMemcpyAsync(c->d_q64, c->h_q64, sizeof(double) * ix->dim * nq, hipMemcpyHostToDevice,
                               c->pass.work));
+    }
+    if (card_prep) {  // (the sweeps wait for ev_up below: the images and the constants they read are there by then)
+        if (with_single_form) return fail(SZG_E_INVALID, "query_prep: the batch's images come from one side");
+        int rc = enqueue_query_prep(ix, c, nq, *card_prep);
+        if (rc) return rc;
     }
     if (masks && handles) {
         bool same = handles[0] != nullptr;
@@ -108,6 +150,7 @@ int enqueue_queries(szg_index *ix, Shard *sh, Ctx *c, const double *q, int nq, c
     // what the sweeps wait for ends here: work enqueued on this stream afterwards (the first-k
     // rows' distances) runs beside the sweeps
     HIPCHK(hipEventRecord(c->ev_up, c->pass.work));
+    if (card_prep) return enqueue_card_meta_copy(c);  // (the host needs them when it settles: beside the sweeps)
     return SZG_OK;
 }
 
@@ -129,7 +172,9 @@ void fill_scan_args(const szg_index *ix, const Shard *sh, const Ctx *c, bool has
     a->query_stride = (uint32_t)ix->qsw_bytes;
     a->query = c->d_qsw + (size_t)slot * ix->qsw_bytes;
     a->n_queries = nq;
-    for (int j = 0; j < nq && j < szg::kMatrixWideQueries; j++) {
+    // (prepared on the card: the kernels read the constants where the card wrote them, the arrays stay zero)
+    if (c->pass.prep_n) a->qmeta = c->d_meta + (size_t)slot * szg::kQueryPrepMeta;
+    for (int j = 0; j < nq && j < szg::kMatrixWideQueries && !c->pass.prep_n; j++) {
         a->qscale[j] = (float)c->meta[slot + j].qscale;
         a->qconst[j] = (float)c->meta[slot + j].qconst;
         a->qnorm2[j] = (float)c->meta[slot + j].qnorm2;
@@ -316,7 +361,7 @@ int enqueue_topk(szg_index *ix, Shard *sh, Ctx *c, int kp, int nq, bool has_allo
             if (share) {  // the constants of the launch's queries 32 .. 63, and the option
                 szg::ScanShareHi &h = hi[(j - q0) / qpl];
                 memset(&h, 0, sizeof(h));
-                for (int x = szg::kMatrixWideQueries; x < a.n_queries; x++) {
+                for (int x = szg::kMatrixWideQueries; x < a.n_queries && !c->pass.prep_n; x++) {
                     h.qscale[x - szg::kMatrixWideQueries] = (float)c->meta[j + x].qscale;
                     h.qconst[x - szg::kMatrixWideQueries] = (float)c->meta[j + x].qconst;
                     h.qnorm2[x - szg::kMatrixWideQueries] = (float)c->meta[j + x].qnorm2;

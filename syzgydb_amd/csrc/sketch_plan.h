@@ -25,6 +25,19 @@ constexpr int kWideCallMin = 2 * szg::kMatrixWideQueries + 2 * kFirstBatch;
 // same rule -- from two of them between the first and last batch of kFirstBatch on.  Shorter calls keep their plan.
 constexpr int kShareCallMin = 2 * szg::kMatrixShareQueries + 2 * kFirstBatch;
 
+// Option query_prep = 1: batches of a sketch top-k call of at least this many queries have their queries prepared on the
+// card.  Below it a launch and a copy of constants sit in front of the batch's few sweeps and buy back less host time
+// than they cost: a lone search and the kFirstBatch-query edges of a long call stay on the host ("queries
+// prepared on the card", has the measurement the value is from)
+constexpr int kQueryPrepMin = 8;
+// does the card prepare a batch of batch_queries queries under the option's value?  0 never, 1 from kQueryPrepMin on, 2 every
+// batch (the tests' setting)
+inline bool query_prep_serves(int option, int batch_queries)
+{
+    if (batch_queries < 1) return false;
+    return option == 2 || (option == 1 && batch_queries >= kQueryPrepMin);
+}
+
 // How a call splits into batches: the caller's parameters
 struct BatchRules {
     int batch;        // queries of a one-sweep-per-query batch

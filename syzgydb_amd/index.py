@@ -1004,6 +1004,24 @@ class ScanIndex:
         check(self._L.szg_index_sketch_topk_stats(self._h, ctypes.byref(s)), "szg_index_sketch_topk_stats")
         return {name: int(getattr(s, name)) for name, _ in _lib.SzgSketchTopkStats._fields_}
 
+    def query_prep_stats(self):
+        """Which side prepared the queries of the handle's top-k calls through the sketch since reset_stats (option
+        query_prep; szg_index_query_prep_stats): queries_dev, queries_host, and launches of the preparing kernel."""
+        s = _lib.SzgQueryPrepStats()
+        check(self._L.szg_index_query_prep_stats(self._h, ctypes.byref(s)), "szg_index_query_prep_stats")
+        return {name: int(getattr(s, name)) for name, _ in _lib.SzgQueryPrepStats._fields_}
+
+    def debug_query_prep(self, Q, on_card):
+        """Test hook (szg_debug_query_prep): what a sweep of the handle's sketch would be given for the queries Q -- (images
+        uint8[n, 48 * ceil(dim / 16)], constants float64[n, 5] = qnorm, m1, qscale, qconst, qnorm2) -- prepared by the host
+        (on_card = 0) or by the kernel of option query_prep (1).  SzgError(SZG_E_UNSUPPORTED) on a handle without a sketch."""
+        Q = np.ascontiguousarray(Q, dtype=np.float64).reshape(-1, self.dim)
+        n = Q.shape[0]
+        image = np.zeros((n, 48 * ((self.dim + 15) // 16)), dtype=np.uint8)
+        meta = np.zeros((n, 5), dtype=np.float64)
+        check(self._L.szg_debug_query_prep(self._h, _f64(Q), n, int(on_card), _u8(image), _f64(meta)), "szg_debug_query_prep")
+        return image, meta
+
     @staticmethod
     def sample_plan(shard_rows, k, n_queries=1, dim=768, quant_bits=8, planes=2):
         """Host-only test hook: sample_plan() of this module."""
@@ -1194,10 +1212,19 @@ def sample_plan(shard_rows, k, n_queries=1, dim=768, quant_bits=8, planes=2):
     return d
 
 
+def query_prep_serves(option, batch_queries):
+    """Host-only test hook (szg_debug_query_prep_serves; csrc/sketch_plan.h): (does the card prepare a sketch top-k batch of
+    batch_queries queries under query_prep = option?, the smallest batch that option 1 serves)."""
+    L = _lib.load()
+    least = ctypes.c_int()
+    serves = L.szg_debug_query_prep_serves(int(option), int(batch_queries), ctypes.byref(least))
+    return bool(serves), least.value
+
+
 def option_check(name, value):
     """Host-only test hook (no device needed): raises SzgError where ScanIndex.set_option would refuse `value` for the
     one-sweep kernel's option `name` (scan_group, scan_group_ring, scan_norms, sketch_planes, sketch_matrix, sketch_select,
-    sketch_wide, sketch_share, sketch_bulk, sketch_radius, sketch_masked, sketch_f64, sketch_topk_collect)."""
+    sketch_wide, sketch_share, sketch_bulk, sketch_radius, sketch_masked, sketch_f64, sketch_topk_collect, query_prep)."""
     L = _lib.load()
     check(L.szg_debug_option_check(name.encode(), int(value)), "szg_debug_option_check")
 
