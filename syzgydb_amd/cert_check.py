@@ -405,14 +405,15 @@ def check(corpus, Q, recs, ents, dropped, eligible=None, dists=None, margins=Non
 # ---- the sketch index: bytes, exceptions and max_ang (B) ---------------------------------------------------------------
 
 def sketch_angle_rounding(dim):
-    """What sketch_call_plan adds to max_ang under cosine for the rounding of the build kernel's float64 angles: the
-    device's cosine of (row, sketch) is off by at most (dim + 8) u, which acos turns into at most sqrt(2 (dim + 8) u)
-    near c = 1; twice the root covers a float64 reference beside it.  1e-7 up to dim 222."""
+    """What sketch_slack (sketch_bound.h) adds to max_ang under cosine for the rounding of the build kernel's float64
+    angles: the device's cosine of (row, sketch) is off by at most (dim + 8) u, which acos turns into at most
+    sqrt(2 (dim + 8) u) near c = 1; twice the root covers a float64 reference beside it.  1e-7 up to dim 103."""
     return max(1e-7, 2.0 * np.sqrt((dim + 8) * 2.0 ** -52) / np.pi)
 
 
 def sketch_slack(max_ang, gscale, dim):
-    """slack as sketch_call_plan forms it from the sketch state."""
+    """slack as sketch_slack (sketch_bound.h) forms it from the sketch state; tests/test_sketch_bound_cpu.py holds the two
+    to equal bits."""
     return max_ang * (1.0 + 1e-9) + (0.0 if gscale > 0 else sketch_angle_rounding(dim))
 
 

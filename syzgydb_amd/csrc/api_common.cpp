@@ -48,6 +48,12 @@ void replay_topk(std::vector<Cand> &cands, int k, std::vector<HeapItem> *result)
     h.drain(result);
 }
 
+void unique_rows(std::vector<Cand> &cands)
+{
+    std::sort(cands.begin(), cands.end(), [](const Cand &x, const Cand &y) { return x.row < y.row; });
+    cands.erase(std::unique(cands.begin(), cands.end(), [](const Cand &x, const Cand &y) { return x.row == y.row; }), cands.end());
+}
+
 // True when the reference's answer may depend on its whole heap history: a NaN
 // distance, or two exactly equal distances among the best k+1 candidates.
 bool history_dependent(const double *dist, size_t n, int k)

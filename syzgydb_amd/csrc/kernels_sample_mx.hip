@@ -1,5 +1,5 @@
 // kernels_sample_mx.hip -- the sample pass of a top-k search of large k through the sketch (option sketch_topk_collect;
-// DESIGN.md 4.5 item 16; sample_plan.h has its arithmetic, scan_radius.cpp its caller).
+// DESIGN.md 4.5 item 16; sample_plan.h has its arithmetic, scan_sketch_topk.cpp its caller).
 //
 // sample_mx_kernel scores a strided sample of a sketch shard on the matrix cores: every stride-th tile of 16 tiled 8-bit
 // rows against the 16 (NB = 1) or 32 (NB = 2) two-plane queries of the launch.  The operands are scan_mx_kernel's

@@ -1,5 +1,5 @@
 // sample_plan.h -- the arithmetic of the sample pass of a top-k search of large k through the sketch (option
-// sketch_topk_collect; scan_radius.cpp, kernels_sample_mx.hip): which tiles of a sketch shard are
+// sketch_topk_collect; scan_sketch_topk.cpp, kernels_sample_mx.hip): which tiles of a sketch shard are
 // scored, where each (query, sampled row) pair's key goes, how large the key buffer is, and how many entries per query the
 // collect buffers of the sweep that follows start with.  Plain C++, no HIP, like collect_plan.h:
 // tests/cpp/test_sample_plan.cpp compiles it on its own under the address and undefined-behaviour sanitizers.

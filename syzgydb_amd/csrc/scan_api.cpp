@@ -27,6 +27,13 @@ szg_cert_record cert_record(int query, int pass)
     return r;
 }
 
+szg_cert_record cert_record(const szg_index *ix, int query, int pass)
+{
+    szg_cert_record r = cert_record(query, pass);
+    for (const Shard *sh : ix->shards) r.row_hi = std::max<uint64_t>(r.row_hi, sh->first + sh->n_rows);
+    return r;
+}
+
 bool cert_room(szg_index *ix, size_t n)
 {
     CertTrace &t = ix->cert;

@@ -4,13 +4,16 @@
 //   api_common.cpp    error text, container/heap replay, cross-shard merge (host only)
 //   scan_query.cpp    query preparation (swizzle / digit planes) and the key error bounds
 //   scan_handle.cpp   handle lifetime, contexts, mutations, options, statistics
-//   scan_topk.cpp     the batch pipeline of top-k and radius calls; one-sweep-per-query top-k, certification,
-//                     escalation, exact replay
+//   scan_topk.cpp     the batch pipeline of search calls (plan_batch, stage_query_forms; run_batches is below);
+//                     one-sweep-per-query top-k, certification, escalation, exact replay
 //   scan_mq.cpp       shared (multi-query) sweeps on the matrix cores
 //   scan_sketch.cpp   8-bit sketch pre-pass (option query_prep: its top-k batches' queries prepared on the card --
-//                     query_prep.h: the rule, shared with scan_query.cpp; kernels_query_prep.hip: the kernel)
-//   scan_radius.cpp   radius search (single, batch, coalesced; through the sketch: sketch_radius; collect_plan.h: its buffers)
-//                     and top-k of large k through the sketch as a sample pass + that collect core (sketch_topk_collect;
+//                     query_prep.h: the rule, shared with scan_query.cpp; kernels_query_prep.hip: the kernel) and what
+//                     every call through the sketch shares: its plan, its batches' query forms (sketch_bound.h: the
+//                     arithmetic of its certificates)
+//   scan_radius.cpp   radius search (single, batch, coalesced; through the sketch: sketch_radius) and the collect core
+//                     (scan_collect.h; collect_plan.h: its buffers)
+//   scan_sketch_topk.cpp  top-k of large k through the sketch as a sample pass + that collect core (sketch_topk_collect;
 //                     sample_plan.h: its arithmetic; kernels_sample_mx.hip: its kernels)
 //   scan_comm.cpp     one-process-per-GPU exchange (RCCL all-gather + merge)
 //   scan_mask.cpp     device-resident filter masks (szg_mask) and the searches that take them
@@ -39,6 +42,7 @@
 #include "kernels.h"
 #include "query_prep.h"
 #include "reorder_plan.h"
+#include "sketch_bound.h"
 #include "sketch_plan.h"
 
 #include <algorithm>
@@ -474,7 +478,7 @@ struct szg_index {
                               // their rows' bytes, under every rule of float32 handles: 0 = never (the default while the
                               // option soaks: such a handle keeps no sketch and allocates nothing more), 1 = always
     int sketch_topk_collect = 0;  // top-k calls that take a sweep per query with a k the pre-pass does not serve go through
-                              // the sketch as a sample pass and a collect sweep (scan_radius.cpp, SketchTopkCall): 0 = never
+                              // the sketch as a sample pass and a collect sweep (scan_sketch_topk.cpp, SketchTopkCall): 0 = never
                               // (the default while the option soaks), 1 = wherever the sample plan serves every shard
     szg_sketch_topk_stats sk_topk{};  // what that path served (stats_mu; szg_index_sketch_topk_stats, szg_reset_stats)
     int query_prep = 0;       // the batches of a top-k call through the sketch have their queries prepared on the card
@@ -600,6 +604,8 @@ struct RowFormat {
 double now_us();
 // consider()'s top-k branch replayed over the candidates in visit order, then the pop loop
 void replay_topk(std::vector<Cand> &cands, int k, std::vector<HeapItem> *result);
+// the candidates sorted by row, one entry per row (a row that reached them twice was re-ranked to the same distance twice)
+void unique_rows(std::vector<Cand> &cands);
 // a NaN distance, or two exactly equal ones among the best k+1: the reference's answer depends on its heap history
 bool history_dependent(const double *dist, size_t n, int k);
 
@@ -658,6 +664,8 @@ void note_overwritten(szg_index *ix, uint64_t row);
 inline bool cert_tracing(const szg_index *ix) { return ix->cert.on.load(std::memory_order_relaxed); }
 // a fresh record of query `query` of its call for pass `pass`: everything that does not apply is NaN / -1
 szg_cert_record cert_record(int query, int pass);
+// ... of a pass over every row of the handle: row_hi is the end of its last shard
+szg_cert_record cert_record(const szg_index *ix, int query, int pass);
 // append the record and its entries (dropped as a whole, and counted, when a cap would be passed)
 void cert_emit(szg_index *ix, szg_cert_record r, const std::vector<szg_cert_entry> &entries);
 // room for a record of n entries?  Asked BEFORE the entries are gathered, so that a record that will not fit costs no
@@ -767,6 +775,7 @@ int search_radius_any(szg_index *ix, const double *queries, int n_queries, const
                       const uint64_t *const *masks, std::vector<std::vector<HeapItem>> *results,
                       const szg_mask *const *handles = nullptr);
 
+// ---- scan_sketch_topk.cpp
 // Top-k of large k through the sketch (option sketch_topk_collect): does the sample plan serve every shard of the
 // handle's sketch index for k (sample_plan.h)?  Called with the sketch in sync.
 bool sketch_topk_collect_serves(const szg_index *ix, int k);
@@ -995,7 +1004,7 @@ int stage_single_form(szg_index *ix, Batch &b, const double *q, int j, QMeta *me
 // ---- scan_sketch.cpp: what a call through ix's sketch index -- the top-k pre-pass, a radius search -- fixes up front
 struct SketchPlan {
     double gs = 0.0;     // Euclidean: sketch distances are in units of gs (the sketch sweeps see q / gs); 0: cosine
-    double slack = 0.0;  // the largest d(row, its sketch) (1 + 1e-9), + the build kernel's angle rounding under cosine
+    double slack = 0.0;  // sketch_slack (sketch_bound.h) of the largest d(row, its sketch) the build measured
     int wide = 0;        // the call takes wide batches (32 queries, one launch of the two-block matrix sweep each):
                          // 1 = under the automatic rule, 2 = forced (option sketch_wide = 2)
     int share = 0;       // the call takes shared batches (up to 64 queries, one shared launch each; top-k calls only):
@@ -1005,6 +1014,11 @@ struct SketchPlan {
 SketchPlan sketch_call_plan(const szg_index *ix, int n_queries, int kp);
 // the next batch of such a call, from query q0, on the sketch index's contexts
 void sketch_plan_batch(const szg_index *ix, int n_queries, int q0, int wide, Batch *b, int share = 0);
+// ... and its queries q[0, nq) in the forms the sketch sweeps take: scaled as sketch_scale_query scales them -- zeros in
+// the slots marked handed (null: none is) -- into *scratch, which the call keeps between its batches, then
+// stage_query_forms on sketch index sk with the caller's adjust
+int sketch_stage_forms(szg_index *sk, double gs, Batch &b, const double *q, const uint8_t *handed, std::vector<double> *scratch,
+                       const std::function<void(int, QMeta &)> &adjust);
 // float32 shard a's rows without a usable sketch (sk_exc): f(shard-local row, eligible: live and allowed by mask words m)
 template <class F>
 void sketchless_rows(const szg_index *ix, const Shard *a, const uint64_t *m, F &&f)
@@ -1035,6 +1049,35 @@ struct HandedOver {
     const uint64_t *const *mask_ptrs() const { return handles.empty() && any ? masks.data() : nullptr; }
     const szg_mask *const *handle_ptrs() const { return !handles.empty() && any ? handles.data() : nullptr; }
 };
+// ... for a top-k call: search_topk_impl on them, traced under their indexes in the caller's call, and their answers
+// into the caller's arrays
+int search_topk_handed(szg_index *ix, const HandedOver &h, const std::vector<int> &redo, int k, uint64_t *out_rows,
+                       double *out_dist, int32_t *out_count);
+
+// The entry frame of every search through the sketch (the top-k pre-pass, top-k of large k, radius searches).  call: the
+// pipeline -- run() answers what it settles and leaves the rest in redo; its sk is set here, once the sketch is in sync.
+// serves(): the caller's further condition on the synced sketch.  whole(): the full-precision path on the whole call --
+// where the sketch has stepped aside or does not serve (the path the call takes without it: not a fallback, not
+// counted), and in auto mode after a failure inside the pipeline (an allocation of a sketch context, say): the sketch
+// index then stays until the next load and steps aside (sk_nomem).  handed(h, redo): ONE call of the full-precision path
+// on the queries handed over, redo as its trace index, and their answers scattered back.  (Only the pre-pass's
+// hand-overs enter the automatic window sk_hist: SketchCall::finish counts them.)
+template <class Call, class Serves, class Whole, class Handed>
+int sketch_served_call(szg_index *ix, Call &call, Serves &&serves, Whole &&whole, Handed &&handed)
+{
+    int rc = sketch_sync_for_search(ix);
+    if (rc) return rc;
+    if (ix->sk_disabled || ix->sk_nomem || !serves()) return whole();
+    call.sk = ix->sketch;
+    rc = call.run();
+    if (rc && ix->sketch_on == 2) {
+        ix->sk_nomem = true;
+        return whole();
+    }
+    if (rc || call.redo.empty()) return rc;
+    std::sort(call.redo.begin(), call.redo.end());
+    return handed(HandedOver(ix, call.queries, call.mask_of, call.redo), call.redo);
+}
 
 // The in-flight loop of a call: plan a batch, borrow its contexts (none free: finish the oldest batch in flight
 // first), stage it, and in the end finish the rest in order.  hand_over (optional): takes every staged batch instead

@@ -299,11 +299,7 @@ SketchPlan sketch_call_plan(const szg_index *ix, int n_queries, int kp)
     const szg_index *sk = ix->sketch;
     SketchPlan p;
     p.gs = ix->sk_gscale;
-    // + the rounding of the build kernel's angles: its float64 cosine of (row, sketch) is off by at most (dim + 8) u,
-    // which acos turns into at most sqrt(2 (dim + 8) u) where c is near 1 -- a row that its sketch all but reproduces.
-    // Twice the root (a float64 reference beside it; cert_check.sketch_angle_rounding) passes 1e-7 from dim 223 on.
-    const double ang_round = p.gs > 0.0 ? 0.0 : std::max(1e-7, 2.0 * std::sqrt((ix->dim + 8) * 0x1p-52) / M_PI);
-    p.slack = ix->sk_max_ang * (1.0 + 1e-9) + ang_round;
+    p.slack = sketch_slack(ix->sk_max_ang, p.gs, ix->dim);
     // wide and shared batches (sketch_plan.h: the options are read from the sketch index): only where every non-empty
     // shard's launch of 32 (33 .. 64) qualifies for the form, and there is one
     auto every_shard = [&](bool (*serves)(const szg_index *, const Shard *, int, int)) {
@@ -328,9 +324,25 @@ void sketch_plan_batch(const szg_index *ix, int n_queries, int q0, int wide, Bat
     plan_batch(ix->sketch, n_queries, q0, 0, sketch_batch_rules(n_queries, wide, share, ix->query_batch), b);
 }
 
+int sketch_stage_forms(szg_index *sk, double gs, Batch &b, const double *q, const uint8_t *handed, std::vector<double> *scratch,
+                       const std::function<void(int, QMeta &)> &adjust)
+{
+    const size_t dim = (size_t)sk->dim;
+    if (handed || gs > 0.0) {  // (cosine, every query served: the queries as they are)
+        scratch->resize((size_t)b.nq * dim);
+        for (int j = 0; j < b.nq; j++) {
+            double *o = scratch->data() + (size_t)j * dim;
+            if (handed && handed[j]) std::fill(o, o + dim, 0.0);  // (sweeps as zeros, collects nothing)
+            else sketch_scale_query(q + (size_t)j * dim, (int)dim, gs, o);
+        }
+        q = scratch->data();
+    }
+    return stage_query_forms(sk, b, q, false, adjust);
+}
+
 // ---- one search call through the sketch ---------------------------------------------------------------------------
 //
-// The batch pipeline of scan_topk.cpp (run_batches) on the sketch index's contexts: stage() uploads a batch's queries
+// The batch pipeline (run_batches, scan_internal.h) on the sketch index's contexts: stage() uploads a batch's queries
 // and extra rows and enqueues, per shard, the sketch sweeps, the merges and one float32-row rerank; finish() settles
 // the batch's queries on the host -- a short call's first queries while its last sweeps still run -- and collects
 // the ones the certificate does not settle for the full sweep.
@@ -416,15 +428,7 @@ int SketchCall::stage(Batch &b)
     // reader there was, hands the kernels the card's table instead.
     const bool on_card = query_prep_serves(ix->query_prep, b.nq);
     int rc = SZG_OK;
-    if (!on_card) {
-        const double *q_sk = q;
-        if (p.gs > 0.0) {
-            q_scaled.resize((size_t)b.nq * dim);
-            for (size_t i = 0; i < q_scaled.size(); i++) q_scaled[i] = q[i] / p.gs;
-            q_sk = q_scaled.data();
-        }
-        rc = stage_query_forms(sk, b, q_sk, false, [](int, QMeta &) {});
-    }
+    if (!on_card) rc = sketch_stage_forms(sk, p.gs, b, q, nullptr, &q_scaled, [](int, QMeta &) {});
     // behind each query's list: the drop bound's slot (the short-list merge writes it), its first k eligible rows of
     // the shard (kInvalidCand-padded to k), then the shard's eligible rows without a usable sketch
     for (size_t s = 0; s < n_sh && rc == SZG_OK; s++) {
@@ -514,26 +518,14 @@ void SketchCall::settle(Batch &b, int j)
         }
     }
     cands.erase(std::remove_if(cands.begin(), cands.end(), [](const Cand &c) { return std::isnan(c.dist); }), cands.end());
-    std::sort(cands.begin(), cands.end(), [](const Cand &x, const Cand &y) { return x.row < y.row; });
-    cands.erase(std::unique(cands.begin(), cands.end(), [](const Cand &x, const Cand &y) { return x.row == y.row; }),
-                cands.end());
+    unique_rows(cands);
     replay_topk(cands, k, &res);
     bool ok = (!nan_first || ix->tie_mode != 0) && !zero_query;
     double D_used = NAN;
     if (ok && lb < INFINITY) {
-        // D_lb: the sketch distance the key bound lb implies -- cosine: key = -cos, distance
-        // acos(cos) / pi; Euclid: key = (255 d)^2 in units of gs
-        double D;
-        if (p.gs > 0.0) {
-            D = p.gs * std::sqrt(std::max(lb, 0.0)) / 255.0 * (1.0 - 1e-9);
-        } else {
-            const double x = -lb + 1e-15;  // (an upper bound of the cosine, rounding included)
-            D = x >= 1.0 ? 0.0 : (x <= -1.0 ? 1.0 : std::acos(x) / M_PI * (1.0 - 1e-12));
-        }
-        // (float64 rows: at a scale near the largest double gs * sqrt(lb) overflows.  An infinite D bounds nothing --
-        // the product it stands for is finite and may be below slack -- so it settles nothing)
-        ok = (int)res.size() == k && std::isfinite(D) && res.back().priority * (1.0 + 1e-9) < D - p.slack;
-        D_used = D;
+        // D_lb: the sketch distance the key bound lb implies, rounded down (sketch_bound.h)
+        D_used = sketch_dist_below(p.gs, lb);
+        ok = (int)res.size() == k && sketch_settles(res.back().priority, D_used, p.slack);
     }
     if (ok && ix->tie_mode == 0) {
         dd.clear();
@@ -541,12 +533,11 @@ void SketchCall::settle(Batch &b, int j)
         if (history_dependent(dd.data(), dd.size(), k)) ok = false;  // the float32 path replays every row
     }
     if (tracing) {
-        szg_cert_record rec = cert_record(qi, SZG_CERT_SKETCH);
+        szg_cert_record rec = cert_record(ix, qi, SZG_CERT_SKETCH);
         rec.keys = SZG_CERT_KEYS_SINGLE;
         rec.sweep = 0;
         rec.certified = ok ? 1 : 0;
         rec.k = k;
-        for (const Shard *sh : ix->shards) rec.row_hi = std::max<uint64_t>(rec.row_hi, sh->first + sh->n_rows);
         rec.thr_min = lb;
         rec.D = D_used;
         rec.slack = p.slack;
@@ -639,34 +630,30 @@ int search_topk_sketch(szg_index *ix, const double *queries, int n_queries, int 
                        uint64_t *out_rows, double *out_dist, int32_t *out_count, const uint64_t *const *allow_ptrs,
                        const szg_mask *const *handles)
 {
-    int rc = sketch_sync_for_search(ix);
-    if (rc) return rc;
-    if (ix->sk_disabled || ix->sk_nomem)
-        return search_topk_impl(ix, queries, n_queries, k, allow_bits, out_rows, out_dist, out_count, allow_ptrs, handles);
-    SketchCall call{ix, ix->sketch, queries, n_queries, k, QueryMasks(ix, allow_bits, allow_ptrs, handles), out_rows,
-                    out_dist, out_count};
-    rc = call.run();
-    if (rc && ix->sketch_on == 2) {
-        // (a failure inside the pipeline, an allocation of a sketch context: the sketch index stays until the next
-        // load, the whole call goes the full-precision way)
-        ix->sk_nomem = true;
-        return search_topk_impl(ix, queries, n_queries, k, allow_bits, out_rows, out_dist, out_count, allow_ptrs, handles);
-    }
-    if (rc) return rc;
-    if (call.redo.empty()) return SZG_OK;
-    // the unsettled queries: ONE call of the full-precision path
-    const int m = (int)call.redo.size();
-    const HandedOver h(ix, queries, call.mask_of, call.redo);
+    SketchCall call{ix, nullptr, queries, n_queries, k, QueryMasks(ix, allow_bits, allow_ptrs, handles), out_rows, out_dist,
+                    out_count};
+    return sketch_served_call(
+        ix, call, [] { return true; },
+        [&] { return search_topk_impl(ix, queries, n_queries, k, allow_bits, out_rows, out_dist, out_count, allow_ptrs, handles); },
+        [&](const HandedOver &h, const std::vector<int> &redo) {
+            return search_topk_handed(ix, h, redo, k, out_rows, out_dist, out_count);
+        });
+}
+
+int search_topk_handed(szg_index *ix, const HandedOver &h, const std::vector<int> &redo, int k, uint64_t *out_rows,
+                       double *out_dist, int32_t *out_count)
+{
+    const int m = (int)redo.size();
     std::vector<uint64_t> r2((size_t)m * k);
     std::vector<double> d2((size_t)m * k);
     std::vector<int32_t> c2(m);
-    rc = search_topk_impl(ix, h.q.data(), m, k, nullptr, r2.data(), d2.data(), c2.data(), h.mask_ptrs(), h.handle_ptrs(),
-                          call.redo.data());
+    const int rc = search_topk_impl(ix, h.q.data(), m, k, nullptr, r2.data(), d2.data(), c2.data(), h.mask_ptrs(),
+                                    h.handle_ptrs(), redo.data());
     if (rc) return rc;
     for (int i = 0; i < m; i++) {
-        memcpy(out_rows + (size_t)call.redo[i] * k, &r2[(size_t)i * k], sizeof(uint64_t) * k);
-        memcpy(out_dist + (size_t)call.redo[i] * k, &d2[(size_t)i * k], sizeof(double) * k);
-        if (out_count) out_count[call.redo[i]] = c2[i];
+        memcpy(out_rows + (size_t)redo[i] * k, &r2[(size_t)i * k], sizeof(uint64_t) * k);
+        memcpy(out_dist + (size_t)redo[i] * k, &d2[(size_t)i * k], sizeof(double) * k);
+        if (out_count) out_count[redo[i]] = c2[i];
     }
     return SZG_OK;
 }
@@ -679,7 +666,7 @@ int search_topk_any(szg_index *ix, const double *queries, int n_queries, int k, 
     const bool shared = ix->multi_query && n_queries >= ix->mq_min;
     if (!shared && sketch_applies(ix, k))
         return search_topk_sketch(ix, queries, n_queries, k, allow_bits, out_rows, out_dist, out_count, allow_ptrs, handles);
-    // a k beyond the pre-pass's lists: a sample pass and a collect sweep of the sketch (scan_radius.cpp), where the option
+    // a k beyond the pre-pass's lists: a sample pass and a collect sweep of the sketch (scan_sketch_topk.cpp), where the option
     // is on and the sample plan serves the handle -- else the path the call takes without the option
     if (ix->sketch_topk_collect && !shared && n_queries >= 1 && k >= 1 && sketch_applies_rows(ix))
         return search_topk_collect(ix, queries, n_queries, k, allow_bits, out_rows, out_dist, out_count, allow_ptrs, handles);
@@ -728,7 +715,7 @@ int szg_debug_query_prep(szg_index *ix, const double *queries, int n_queries, in
         for (int j = 0; j < n_queries; j++) {
             const double *q = queries + (size_t)j * dim;
             if (gs > 0.0) {
-                for (int e = 0; e < dim; e++) scaled[e] = q[e] / gs;
+                sketch_scale_query(q, dim, gs, scaled.data());
                 q = scaled.data();
             }
             QMeta m;

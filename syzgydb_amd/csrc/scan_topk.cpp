@@ -1107,13 +1107,12 @@ int TopkCall::settle(TopkBatch &t, int j, std::vector<Cand> &cands, double thr_m
     if (nan_first && ix->tie_mode == 0) certified = true;  // answered by the replay below
     const int q_call = trace_index ? trace_index[t.first + j] : t.first + j;
     if (trace_now) {
-        szg_cert_record rec = cert_record(q_call, SZG_CERT_TOPK);
+        szg_cert_record rec = cert_record(ix, q_call, SZG_CERT_TOPK);
         for (size_t s = 0; s < n_sh; s++)
             if (t.ctx[s]) rec.keys = (int32_t)cert_keys(t.ctx[s]->pass.keys);
         rec.sweep = t.nb == 0 ? 0 : (t.bf16 ? 2 : 1);
         rec.certified = certified ? 1 : 0;
         rec.k = k;
-        for (const Shard *sh : ix->shards) rec.row_hi = std::max<uint64_t>(rec.row_hi, sh->first + sh->n_rows);
         rec.thr_min = thr_min;
         rec.kmax = kmax;
         cert_emit(ix, rec, traced);

@@ -1,7 +1,7 @@
 // sketch_plan.h -- the plan of a search call whose queries take one sweep each, and of a call through the sketch above
 // all: how the call splits into batches, a batch into parts and launches on one shard, which launches take the matrix
 // sweep's wide or shared form, and how many passes over the rows that makes.  The launch path (scan_sketch.cpp,
-// scan_topk.cpp, scan_radius.cpp) and the plan hooks (scan_api.cpp) both compute from here.  Plain C++, no HIP, header
+// scan_topk.cpp, scan_radius.cpp, scan_sketch_topk.cpp) and the plan hooks (scan_api.cpp) both compute from here.  Plain C++, no HIP, header
 // only -- what depends on the build's variants (scan_variant, scan_lds_bytes, merge_short_fits) is scan_plan.cpp's:
 // tests/cpp/test_sketch_plan.cpp compiles the two on their own under the address and undefined-behaviour sanitizers.
 #pragma once

@@ -8,6 +8,7 @@ import pytest
 
 import oracle as orc
 from syzgydb_amd import ScanIndex, SZG_COSINE, SZG_EUCLIDEAN
+from syzgydb_amd.index import sample_plan
 
 pytestmark = pytest.mark.gpu
 DEFAULT_TUNABLES = not os.environ.get("SZG_OPTIONS")
@@ -171,3 +172,105 @@ def test_refused_allocation_leaves_the_handle_working():
         check(ix, rows, dim, Q, 10)
         if DEFAULT_TUNABLES:
             assert through_sketch(ix) == 4
+
+
+def served_beyond_the_prepass(ix):
+    """Queries that radius searches and top-k searches of large k took through the sketch: settled and handed over."""
+    st, ts = ix.stats(), ix.sketch_topk_stats()
+    return st["sketch_radius_queries"] + st["sketch_radius_fallbacks"], ts["queries"] + ts["fallbacks"]
+
+
+@pytest.mark.parametrize("dim", [32, 64])
+@pytest.mark.parametrize("metric", [SZG_COSINE, SZG_EUCLIDEAN], ids=["cos", "euc"])
+def test_refused_allocation_on_the_radius_and_large_k_paths(metric, dim):
+    """The hook of the test above through the other two entry points of the sketch: a radius call, and a top-k call whose
+    k is beyond the pre-pass's lists (sketch_topk_collect).  2 005 rows (no multiple of 16) in two shards on one device, 5
+    queries, one of them masked: under sketch = 1 all three entry points report the refusal; once the hook is cleared
+    and the rows are loaded again the paths serve.  Two things the shape alone does not reach.  Auto mode keeps no
+    sketch below 65 536 rows -- at 2 005 it steps aside whatever the hook says -- so the auto-mode half runs at 65 536
+    rows as well, the smallest count at which the refusal is met inside the entry frame: no error, the oracle's answers,
+    nothing counted as served.  And the sample pass of the large-k path takes sketch rows of whole 64-byte steps only:
+    at dim 32 the entry frame's "does not serve" clause sends such a call the way it goes without the option -- its
+    counters stay 0 by that rule, which is asserted from the sample plan -- and dim 64 is where they rise."""
+    nq, k_big = 5, 100
+
+    def expected(n):   # (radius queries, large-k queries) through the sketch once it serves
+        per = (n // 2 + 63) // 64 * 64
+        plans = [sample_plan(rows, k_big, 1, dim)["serves"] for rows in (per, n - per)]
+        assert all(plans) == (dim == 64) and any(plans) == (dim == 64), plans
+        return nq, nq if all(plans) else 0
+
+    def case(n, seed):
+        rows = orc.synth_rows(seed, 0, n, dim, 32)
+        Q = orc.synth_vectors(seed + 1, 0, nq, dim)
+        allow = np.ones((nq, n), bool)
+        allow[2] = np.random.default_rng(seed).random(n) < 0.5
+        radii = np.zeros(nq)
+        want_r, want_k = [], []
+        for qi in range(nq):
+            m = allow[qi].astype(np.uint8)
+            d = np.sort(orc.all_distances(rows, dim, 32, metric, Q[qi])[allow[qi]])
+            radii[qi] = (d[19] + d[20]) / 2                    # 20 hits, none on the edge
+            want_r.append(orc.search_exact(rows, dim, 32, metric, Q[qi], radius=float(radii[qi]), allow=m)[:2])
+            want_k.append(orc.search_exact(rows, dim, 32, metric, Q[qi], k=k_big, allow=m)[:2])
+        return rows, Q, allow, radii, want_r, want_k
+
+    def radius_call(ix, c):
+        rows, Q, allow, radii, want_r, _ = c
+        got = ix.search_radius_batch(Q, radii, allow=allow)
+        for qi in range(nq):
+            assert len(want_r[qi][0]) == 20
+            assert [int(x) for x in got[qi][0]] == [int(x) for x in want_r[qi][0]], ("radius", qi)
+            assert (np.asarray(got[qi][1]) == want_r[qi][1]).all(), ("radius", qi)
+
+    def topk_call(ix, c):
+        rows, Q, allow, _, _, want_k = c
+        r, d, cnt = ix.search_topk(Q, k_big, allow=allow)
+        for qi in range(nq):
+            assert cnt[qi] == len(want_k[qi][0]) == k_big
+            assert [int(x) for x in r[qi]] == [int(x) for x in want_k[qi][0]], ("top-k", qi)
+            assert (d[qi] == want_k[qi][1]).all(), ("top-k", qi)
+
+    def open_index(**options):
+        ix = ScanIndex(dim, 32, metric, devices=[0, 0])
+        for name, value in dict({"multi_query": 0, "radius_mq": 0, "sketch_radius": 1, "sketch_topk_collect": 1},
+                                **options).items():
+            ix.set_option(name, value)
+        return ix
+
+    small = case(2005, 940 + metric)
+    with open_index(sketch=1, sketch_min_rows=1) as ix:
+        ix.load(small[0])
+        ix.set_option("force_sketch_nomem", 1)
+        for call in (lambda: ix.search_topk(small[1], 10), lambda: ix.search_topk(small[1], k_big),
+                     lambda: ix.search_radius_batch(small[1], small[3])):
+            with pytest.raises(Exception, match="force_sketch_nomem"):
+                call()
+        ix.set_option("sketch", 2)                             # auto mode: too few rows for a sketch, hook or no hook
+        radius_call(ix, small)
+        topk_call(ix, small)
+        assert served_beyond_the_prepass(ix) == (0, 0)
+        ix.set_option("sketch", 1)
+        ix.set_option("force_sketch_nomem", 0)
+        ix.load(small[0])
+        radius_call(ix, small)
+        topk_call(ix, small)
+        if DEFAULT_TUNABLES:
+            assert served_beyond_the_prepass(ix) == expected(2005)
+
+    big = case(N, 950 + metric)
+    with open_index(sketch=2) as ix:                           # automatic, as it is by default
+        ix.set_option("force_sketch_nomem", 1)
+        for call in (radius_call, topk_call):
+            ix.load(big[0])                                    # (a load re-arms the sketch: each call meets the refusal itself)
+            call(ix, big)                                      # no error: the full-precision path answers
+            assert served_beyond_the_prepass(ix) == (0, 0)
+        ix.set_option("force_sketch_nomem", 0)
+        radius_call(ix, big)
+        topk_call(ix, big)
+        assert served_beyond_the_prepass(ix) == (0, 0)         # aside until the next load
+        ix.load(big[0])
+        radius_call(ix, big)
+        topk_call(ix, big)
+        if DEFAULT_TUNABLES:
+            assert served_beyond_the_prepass(ix) == expected(N)

@@ -1,4 +1,4 @@
-"""Top-k searches of large k through the 8-bit sketch (option sketch_topk_collect; scan_radius.cpp SketchTopkCall,
+"""Top-k searches of large k through the 8-bit sketch (option sketch_topk_collect; scan_sketch_topk.cpp SketchTopkCall,
 kernels_sample_mx.hip, sample_plan.h): a sample pass bounds the k-th distance, a collect sweep at that radius contains the
 answer.
 
