@@ -1159,6 +1159,14 @@ int szg_debug_scan_group_ring(int dim, int quant_bits, int kp, int scan_group, i
 int szg_debug_option_check(const char *name, int64_t value);
 
 /*
+ * Test hook: *out = what option `name` of szg_set_option holds -- on the handle (on_sketch = 0) or on its internal sketch
+ * index (on_sketch = 1: SZG_E_UNSUPPORTED while there is none; never a sync).  "contexts" reads as the contexts in rotation
+ * on the first shard that has any, that is the free ones: call while no search is in flight.  An unknown name is refused
+ * with szg_set_option's text.
+ */
+int szg_debug_option_get(szg_index *ix, const char *name, int on_sketch, int64_t *out);
+
+/*
  * Test hooks of option query_prep.
  *   szg_debug_query_prep         the images (n_queries x 48 * ceil(dim / 16) bytes: three planes of 16 bytes per 16-byte
  *                                piece of a sketch row, whatever sketch_planes says) and constants (out_meta:

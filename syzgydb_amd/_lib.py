@@ -58,6 +58,7 @@ EXPORTS = [
     "szg_index_fetch_rows_dev", "szg_search_topk_dev", "szg_search_radius_dev",
     # host-only test hook
     "szg_debug_scan_plan", "szg_debug_scan_group", "szg_debug_reorder_plan", "szg_debug_option_check",
+    "szg_debug_option_get",   # (not host-only: reads an option back from a handle or its sketch index)
     "szg_debug_scan_group_ring", "szg_debug_merge_short_plan", "szg_debug_scan_matrix",
     "szg_debug_scan_select", "szg_debug_scan_wide", "szg_debug_scan_collect", "szg_debug_scan_share",
     # who owns device memory: the counters and the refusal countdown (added under ABI 4)
@@ -495,6 +496,9 @@ def load():
     if hasattr(L, "szg_debug_option_check"):
         L.szg_debug_option_check.restype = ctypes.c_int
         L.szg_debug_option_check.argtypes = [ctypes.c_char_p, ctypes.c_int64]
+    if hasattr(L, "szg_debug_option_get"):   # (an older build for an A/B run has no such hook)
+        L.szg_debug_option_get.restype = ctypes.c_int
+        L.szg_debug_option_get.argtypes = [vp, ctypes.c_char_p, ctypes.c_int, ctypes.POINTER(ctypes.c_int64)]
     if hasattr(L, "szg_debug_key_eps"):   # (an older build for an A/B run has no such hook)
         L.szg_debug_key_eps.restype = ctypes.c_int
         L.szg_debug_key_eps.argtypes = [ctypes.c_int] * 6 + [ctypes.c_double] * 5 + [f64p]

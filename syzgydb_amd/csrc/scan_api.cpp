@@ -575,16 +575,22 @@ int szg_debug_sketch_rows(szg_index *ix, uint64_t first_row, uint64_t n_rows, ui
 // for a call through the sketch), so tests derive their shapes from the code's own rules.
 namespace {
 
+// a hook's argument that stands for the option stored in `member`: held to that option's range, refused with its text
+int hook_option(int Options::*member, int value)
+{
+    const char *why = option_refusal(option_of(member), value);
+    return why ? fail(SZG_E_INVALID, why) : SZG_OK;
+}
+
 // the option arguments the hooks share, checked in this order; null = the hook has no such argument
 int hook_options(const int *planes, const int *scan_group, const int *sketch_matrix, const int *sketch_select, const int *sketch_wide)
 {
     if (planes && *planes != 2 && *planes != 3) return fail(SZG_E_INVALID, "planes is 2 or 3");
-    if (scan_group && *scan_group != 0 && *scan_group != 1 && *scan_group != 2 && *scan_group != 4)
-        return fail(SZG_E_INVALID, "scan_group is 0, 1, 2 or 4");
-    if (sketch_matrix && !szg::sketch_matrix_known(*sketch_matrix)) return fail(SZG_E_INVALID, "sketch_matrix is 0, 1 or 2");
-    if (sketch_select && !szg::sketch_select_known(*sketch_select)) return fail(SZG_E_INVALID, "sketch_select is 0 or 1");
-    if (sketch_wide && !szg::sketch_wide_known(*sketch_wide)) return fail(SZG_E_INVALID, "sketch_wide is 0, 1 or 2");
-    return SZG_OK;
+    int rc = scan_group ? hook_option(&Options::scan_group, *scan_group) : SZG_OK;
+    if (!rc && sketch_matrix) rc = hook_option(&Options::sketch_matrix, *sketch_matrix);
+    if (!rc && sketch_select) rc = hook_option(&Options::sketch_select, *sketch_select);
+    if (!rc && sketch_wide) rc = hook_option(&Options::sketch_wide, *sketch_wide);
+    return rc;
 }
 
 // One hook's call: the rows of (dim, quant_bits), the geometry of a sweep over them, the record of one launch -- the hook
@@ -744,7 +750,7 @@ int szg_debug_scan_share(int dim, int quant_bits, int n_queries, int kp, int pla
     if (!serves || !launches || !passes || !slices || !lds_bytes || !n_batches || (!batches && batch_capacity > 0))
         return fail(SZG_E_INVALID, "null argument");
     if (kp < 0 || n_queries < 1 || batch_capacity < 0) return fail(SZG_E_INVALID, "kp, n_queries or batch_capacity out of range");
-    if (!szg::sketch_share_known(sketch_share)) return fail(SZG_E_INVALID, "sketch_share is 0, 1 or 2");
+    if (const int rc = hook_option(&Options::sketch_share, sketch_share)) return rc;
     PlanHook h;
     if (const int rc = h.sketch_rows(dim, quant_bits, kp, false, planes, norms, tiled, masked, scan_group, sketch_matrix, &sketch_select,
                                      &sketch_wide, sketch_share))
@@ -771,8 +777,8 @@ int szg_debug_scan_masked(int dim, int quant_bits, int n_queries, int kp, int pl
 {
     if (!out) return fail(SZG_E_INVALID, "null argument");
     if (kp < 0 || n_queries < 1) return fail(SZG_E_INVALID, "kp or n_queries out of range");
-    if (!szg::sketch_share_known(sketch_share)) return fail(SZG_E_INVALID, "sketch_share is 0, 1 or 2");
-    if (!szg::sketch_masked_known(sketch_masked)) return fail(SZG_E_INVALID, "sketch_masked is 0 or 1");
+    if (const int rc = hook_option(&Options::sketch_share, sketch_share)) return rc;
+    if (const int rc = hook_option(&Options::sketch_masked, sketch_masked)) return rc;
     PlanHook h;
     if (const int rc = h.sketch_rows(dim, quant_bits, kp, false, planes, norms, tiled, masked, scan_group, sketch_matrix, &sketch_select,
                                      &sketch_wide, sketch_share, sketch_masked))
@@ -840,8 +846,7 @@ int szg_debug_scan_group_ring(int dim, int quant_bits, int kp, int scan_group, i
     if (!ring_depth || !depths || !n_depths) return fail(SZG_E_INVALID, "null argument");
     if (kp < 0 || n_queries < 1 || n_queries > szg::kMaxSweepsPerLaunch) return fail(SZG_E_INVALID, "kp or n_queries out of range");
     if (const int rc = hook_options(nullptr, &scan_group, nullptr, nullptr, nullptr)) return rc;
-    if (!szg::scan_group_ring_known(scan_group_ring))
-        return fail(SZG_E_INVALID, "scan_group_ring is 0 or a ring depth the library carries");
+    if (const int rc = hook_option(&Options::scan_group_ring, scan_group_ring)) return rc;
     PlanHook h;
     if (const int rc = h.rows(dim, quant_bits, 1, kp, false, 0)) return rc;
     h.in.group = scan_group;

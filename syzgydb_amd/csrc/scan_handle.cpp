@@ -662,35 +662,59 @@ int szg_reset_stats(szg_index *ix)
     return SZG_OK;
 }
 
-// the value ranges of the one-sweep kernel's options: the refusal's text, null when the value is accepted (*known:
-// the name is one of them).  szg_set_option and the host-only szg_debug_option_check ask here.
-static const char *scan_option_refusal(const std::string &n, int64_t value, bool *known)
+}  // extern "C"
+
+// ---- the options (options.h has the table: names, ranges, texts, stores and the two flags of each row)
+static_assert(kCarryStageMax == kCarryStageBytes, "carry_stage_bytes: up to the default window");
+
+// "contexts": value of the shard's contexts stay in rotation, the others are parked (call while no search is in flight)
+static void contexts_apply(szg_index *ix, int64_t value)
 {
-    *known = true;
-    if (n == "scan_group") return value == 0 || value == 1 || value == 2 || value == 4 ? nullptr : "scan_group is 0, 1, 2 or 4";
-    if (n == "scan_group_ring") return szg::scan_group_ring_known(value) ? nullptr : "scan_group_ring is 0 or a ring depth the library carries";
-    if (n == "scan_norms") return value == 0 || value == 1 ? nullptr : "scan_norms is 0 or 1";
-    if (n == "sketch_planes") return value == 0 || value == 2 || value == 3 ? nullptr : "sketch_planes is 0, 2 or 3";
-    if (n == "sketch_matrix") return szg::sketch_matrix_known(value) ? nullptr : "sketch_matrix is 0, 1 or 2";
-    if (n == "sketch_select") return szg::sketch_select_known(value) ? nullptr : "sketch_select is 0 or 1";
-    if (n == "sketch_wide") return szg::sketch_wide_known(value) ? nullptr : "sketch_wide is 0, 1 or 2";
-    if (n == "sketch_share") return szg::sketch_share_known(value) ? nullptr : "sketch_share is 0, 1 or 2";
-    if (n == "sketch_bulk") return szg::sketch_bulk_known(value) ? nullptr : "sketch_bulk is 0 to 1024";
-    if (n == "sketch_radius") return value == 0 || value == 1 ? nullptr : "sketch_radius is 0 or 1";
-    if (n == "sketch_masked") return szg::sketch_masked_known(value) ? nullptr : "sketch_masked is 0 or 1";
-    if (n == "sketch_f64") return value == 0 || value == 1 ? nullptr : "sketch_f64 is 0 or 1";
-    if (n == "sketch_topk_collect") return value == 0 || value == 1 ? nullptr : "sketch_topk_collect is 0 or 1";
-    if (n == "query_prep") return value >= 0 && value <= 2 ? nullptr : "query_prep is 0, 1 or 2";
-    *known = false;
-    return nullptr;
+    ix->n_ctx_active = (int)value;
+    for (Shard *sh : ix->shards) {
+        std::lock_guard<std::mutex> lk(sh->mu);
+        while (!sh->parked_ctx.empty()) {
+            sh->free_ctx.push_back(sh->parked_ctx.back());
+            sh->parked_ctx.pop_back();
+        }
+        // the contexts with the highest numbers leave the rotation, whatever order earlier calls returned them in:
+        // a one-sweep call keeps to the lowest numbers (one_sweep_contexts)
+        std::sort(sh->free_ctx.begin(), sh->free_ctx.end(), [](const Ctx *a, const Ctx *b) { return a->no < b->no; });
+        while ((int64_t)sh->free_ctx.size() > value) {
+            sh->parked_ctx.push_back(sh->free_ctx.back());
+            sh->free_ctx.pop_back();
+        }
+    }
 }
+
+// the one path by which an accepted value reaches a handle: szg_set_option, its forward and the replay
+static void option_apply(szg_index *ix, const OptionRow *row, int64_t value)
+{
+    if (row->store == OptionStore::kContexts) contexts_apply(ix, value);
+    else option_store(row, ix, value);
+}
+
+// The sketch index follows the forwarded options: those set on `ix` so far, with the values it holds now (the last
+// accepted "contexts" is n_ctx_active: a search may hold contexts while this runs), applied to its new sketch index.
+// In table order: no row's acceptance depends on another row's value ("contexts" is held
+// against n_ctx, which is the same constant on both), so the order the caller set them in does not matter.
+void szgi::options_replay(szg_index *ix, szg_index *sketch)
+{
+    int n = 0;
+    const OptionRow *rows = option_rows(&n);
+    for (int i = 0; i < n; i++)
+        if (ix->opt_set >> i & 1)
+            option_apply(sketch, &rows[i], rows[i].store == OptionStore::kContexts ? ix->n_ctx_active : option_load(&rows[i], *ix));
+}
+
+extern "C" {
 
 int szg_debug_option_check(const char *name, int64_t value)
 {
     if (!name) return fail(SZG_E_INVALID, "null argument");
-    bool known;
-    const char *why = scan_option_refusal(name, value, &known);
-    if (!known) return fail(SZG_E_INVALID, "not an option of the one-sweep kernel");
+    const OptionRow *row = option_find(name);
+    if (!row || !row->scan_check) return fail(SZG_E_INVALID, "not an option of the one-sweep kernel");
+    const char *why = option_refusal(row, value);
     return why ? fail(SZG_E_INVALID, why) : SZG_OK;
 }
 
@@ -698,140 +722,42 @@ int szg_set_option(szg_index *ix, const char *name, int64_t value)
 {
     SZG_TRY
     if (!ix || !name) return fail(SZG_E_INVALID, "null argument");
-    const std::string n(name);
-    bool scan_opt;
-    if (const char *why = scan_option_refusal(n, value, &scan_opt)) return fail(SZG_E_INVALID, why);
-    if (n == "sketch") {
-        if (value < 0 || value > 2) return fail(SZG_E_INVALID, "sketch is 0, 1 or 2");
-        ix->sketch_on = (int)value;
-        return SZG_OK;
+    const OptionRow *row = option_find(name);
+    if (!row) return fail(SZG_E_INVALID, "unknown option");
+    if (const char *why = option_refusal(row, value)) return fail(SZG_E_INVALID, why);
+    if (row->store == OptionStore::kContexts && value > ix->n_ctx) return fail(SZG_E_INVALID, row->refusal);
+    option_apply(ix, row, value);
+    if (row->forwarded) {  // the sketch index follows (options_replay: when it is created)
+        int n = 0;
+        ix->opt_set |= 1ull << (row - option_rows(&n));
+        if (ix->sketch) option_apply(ix->sketch, row, value);
     }
-    if (n == "force_sketch_nomem") {
-        ix->force_sketch_nomem = value != 0;
-        return SZG_OK;
-    }
-    if (n == "carry_stage_bytes") {   // (0 = the default; pieces of 16 bytes travel, so a window is a multiple of 16)
-        if (value < 0 || value % 16 || (uint64_t)value > kCarryStageBytes)
-            return fail(SZG_E_INVALID, "carry_stage_bytes is 0 or a multiple of 16 up to 64 MiB");
-        ix->carry_stage_bytes = (uint64_t)value;
-        return SZG_OK;
-    }
-    if (n == "sketch_min_rows") {
-        if (value < 1) return fail(SZG_E_INVALID, "sketch_min_rows out of range");
-        ix->sketch_min_rows = (int)std::min<int64_t>(value, 1 << 30);
-        return SZG_OK;
-    }
-    if (n == "sketch_list") {
-        if (value < 0 || value > 4096) return fail(SZG_E_INVALID, "sketch_list out of range");
-        ix->sketch_list = (int)value;
-        return SZG_OK;
-    }
-    if (n == "sketch_extra") {
-        if (value < 0 || value > 900) return fail(SZG_E_INVALID, "sketch_extra out of range");
-        ix->sketch_extra = (int)value;
-        return SZG_OK;
-    }
-    if (n == "slack") {
-        if (value < 0 || value > 4096) return fail(SZG_E_INVALID, "slack out of range");
-        ix->slack_min = (int)value;
-    } else if (n == "queries_per_launch") {
-        if (value < 1 || value > szg::kMaxSweepsPerLaunch)
-            return fail(SZG_E_INVALID, "queries_per_launch out of range");
-        ix->queries_per_launch = (int)value;
-    } else if (n == "scan_group") {
-        ix->scan_group = (int)value;
-    } else if (n == "scan_group_ring") {
-        ix->scan_group_ring = (int)value;
-    } else if (n == "scan_norms") {
-        ix->scan_norms = (int)value;
-    } else if (n == "sketch_planes") {
-        // (only queries are prepared differently: nothing resident depends on it)
-        ix->sketch_planes = (int)value;
-    } else if (n == "sketch_matrix") {
-        ix->sketch_matrix = (int)value;
-    } else if (n == "sketch_select") {
-        ix->sketch_select = (int)value;
-    } else if (n == "sketch_wide") {
-        ix->sketch_wide = (int)value;
-    } else if (n == "sketch_share") {
-        ix->sketch_share = (int)value;
-    } else if (n == "sketch_bulk") {
-        ix->sketch_bulk = (int)value;
-    } else if (n == "sketch_radius") {
-        ix->sketch_radius = (int)value;
-    } else if (n == "sketch_masked") {
-        ix->sketch_masked = (int)value;
-    } else if (n == "sketch_f64") {
-        // (read on the handle whose rows are float64, sketch_applies_rows; the sketch index, 8-bit, carries it unread)
-        ix->sketch_f64 = (int)value;
-    } else if (n == "sketch_topk_collect") {
-        // (read on the handle the call is made on, search_topk_any; the sketch index carries it unread)
-        ix->sketch_topk_collect = (int)value;
-    } else if (n == "query_prep") {
-        // (read on the handle the call is made on, SketchCall::stage; the sketch index carries it unread)
-        ix->query_prep = (int)value;
-    } else if (n == "query_batch") {
-        if (value < 1 || value > kMaxBatch) return fail(SZG_E_INVALID, "query_batch out of range");
-        ix->query_batch = (int)value;
-    } else if (n == "radius_mq") {
-        if (value < 0 || value > 1) return fail(SZG_E_INVALID, "radius_mq is 0 or 1");
-        ix->radius_mq = (int)value;
-    } else if (n == "finish_thread") {
-        if (value < 0 || value > 1) return fail(SZG_E_INVALID, "finish_thread is 0 or 1");
-        ix->finish_thread = (int)value;
-    } else if (n == "contexts") {
-        if (value < 1 || value > ix->n_ctx) return fail(SZG_E_INVALID, "contexts out of range");
-        for (Shard *sh : ix->shards) {   // call while no search is in flight
-            std::lock_guard<std::mutex> lk(sh->mu);
-            while (!sh->parked_ctx.empty()) {
-                sh->free_ctx.push_back(sh->parked_ctx.back());
-                sh->parked_ctx.pop_back();
-            }
-            // the contexts with the highest numbers leave the rotation, whatever order earlier calls returned them in:
-            // a one-sweep call keeps to the lowest numbers (one_sweep_contexts)
-            std::sort(sh->free_ctx.begin(), sh->free_ctx.end(), [](const Ctx *a, const Ctx *b) { return a->no < b->no; });
-            while ((int64_t)sh->free_ctx.size() > value) {
-                sh->parked_ctx.push_back(sh->free_ctx.back());
-                sh->free_ctx.pop_back();
-            }
-        }
-    } else if (n == "multi_query") {
-        ix->multi_query = value != 0;
-    } else if (n == "mask_dense") {
-        ix->mask_dense = value != 0;
-    } else if (n == "coalesce") {
-        ix->coalesce = value != 0;
-    } else if (n == "force_matrix") {
-        ix->force_matrix = value != 0;
-    } else if (n == "force_no_refine") {
-        ix->force_no_refine = value != 0;
-    } else if (n == "mq_hits") {
-        if (value < 64 || value > 65536) return fail(SZG_E_INVALID, "mq_hits out of range");
-        ix->mq_hits = (int)value;
-    } else if (n == "mq_min") {
-        if (value < 1 || value > 32) return fail(SZG_E_INVALID, "mq_min out of range");
-        ix->mq_min = (int)value;
-    } else if (n == "serialize_scans") {
-        ix->serialize_scans = value != 0;
-    } else if (n == "tie_mode") {
-        if (value != 0 && value != 1) return fail(SZG_E_INVALID, "tie_mode must be 0 or 1");
-        ix->tie_mode = (int)value;
-    } else if (n == "force_escalate") {
-        ix->force_escalate = value != 0;
-    } else {
-        return fail(SZG_E_INVALID, "unknown option");
-    }
-    // the sketch index follows the same tunables (the last value of each, replayed when it is created)
-    bool seen = false;
-    for (auto &o : ix->opt_log)
-        if (o.first == n) {
-            o.second = value;
-            seen = true;
-        }
-    if (!seen) ix->opt_log.emplace_back(n, value);
-    if (ix->sketch) (void)szg_set_option(ix->sketch, name, value);
     return SZG_OK;
     SZG_CATCH
+}
+
+// test hook: what an option holds, on the handle or (on_sketch) on its sketch index; never syncs.  "contexts": the
+// contexts in rotation on the first shard that has any -- the free ones, no search being in flight
+int szg_debug_option_get(szg_index *ix, const char *name, int on_sketch, int64_t *out)
+{
+    if (!ix || !name || !out) return fail(SZG_E_INVALID, "null argument");
+    const OptionRow *row = option_find(name);
+    if (!row) return fail(SZG_E_INVALID, "unknown option");
+    std::unique_lock<std::mutex> lk(ix->sk_mu, std::defer_lock);
+    if (on_sketch) {
+        lk.lock();
+        if (!ix->sketch) return fail(SZG_E_UNSUPPORTED, "no sketch index yet");
+        ix = ix->sketch;
+    }
+    *out = option_load(row, *ix);
+    if (row->store == OptionStore::kContexts)
+        for (Shard *sh : ix->shards) {
+            std::lock_guard<std::mutex> lks(sh->mu);
+            if (sh->all_ctx.empty()) continue;
+            *out = (int64_t)sh->free_ctx.size();
+            break;
+        }
+    return SZG_OK;
 }
 
 }  // extern "C"

@@ -4,6 +4,8 @@
 //   api_common.cpp    error text, container/heap replay, cross-shard merge (host only)
 //   scan_query.cpp    query preparation (swizzle / digit planes) and the key error bounds
 //   scan_handle.cpp   handle lifetime, contexts, mutations, options, statistics
+//   options.cpp       the option table: names, ranges, refusal texts, stores, sketch forwarding (options.h: the rows'
+//                     type and szgi::Options, the members szg_set_option writes; plain C++)
 //   scan_topk.cpp     the batch pipeline of search calls (plan_batch, stage_query_forms; run_batches is below);
 //                     one-sweep-per-query top-k, certification, escalation, exact replay
 //   scan_mq.cpp       shared (multi-query) sweeps on the matrix cores
@@ -40,6 +42,7 @@
 #include "../../include/syzgy_scan.h"
 #include "dev_mem.h"
 #include "kernels.h"
+#include "options.h"
 #include "query_prep.h"
 #include "reorder_plan.h"
 #include "sketch_bound.h"
@@ -63,8 +66,6 @@
 #include <vector>
 
 namespace szgi {
-
-constexpr int kMaxBatch = 96;  // queries one batch may stage (szg::kMqMaxQueries: a bfloat16 shared sweep)
 static_assert(kShortCall <= kMaxBatch, "a short call is one batch");
 
 extern thread_local std::string g_last_error;
@@ -403,7 +404,7 @@ struct PendingSearch {
     std::condition_variable cv;
 };
 
-struct szg_index {
+struct szg_index : szgi::Options {   // (the run-time options: options.h)
     int dim = 0, bits = 0, metric = 0;
     uint32_t row_bytes = 0, pitch = 0;
     szg::RowLayout layout{};  // of every shard's mirror (linear, or 16-row x 64-byte-step tiles)
@@ -415,12 +416,6 @@ struct szg_index {
     // 8-bit sketch pre-pass for float32 collections -- float64 ones under sketch_f64 = 1 -- ("sketch" option, sketch_sync /
     // search_topk_sketch)
     szg_index *sketch = nullptr;         // an internal 8-bit index over the same rows, same shard ranges
-    int sketch_on = 2;                   // 0 off, 1 forced on, 2 auto (sketch_applies)
-    int sketch_extra = 30;               // sketch neighbours asked for beyond k: k = 10 -> 40, which keeps the sketch
-                                         // sweep's lists in registers (kp <= 64); the pre-pass serves k <= 34
-    int sketch_min_rows = 4096;          // smaller collections are not worth a second index
-    int sketch_list = 0;                 // the sketch sweep's per-wave / per-block list length (0 = automatic, >= kp:
-                                         // kp, the full lists and the two-level merge)
     std::mutex sk_mu;                    // the sync
     uint64_t gen = 1, sk_gen = 0;        // mutation counter / the value the sketch was synced at
     bool sk_need_full = true;            // load / synth / reset since the last sync
@@ -436,70 +431,13 @@ struct szg_index {
     std::atomic<uint64_t> sk_off_gen{0}; // == gen: stepped aside for the fallback share (gen starts at 1)
     uint64_t sk_hist = 0;                // the last sk_hist_n eligible queries, newest in bit 0: 1 = handed over
     int sk_hist_n = 0;                   // (stats_mu)
-    std::vector<std::pair<std::string, int64_t>> opt_log;  // tunables set so far (replayed on the sketch index)
-    // tunables (szg_set_option; include/syzgy_scan.h lists them)
-    int slack_min = 16;
+    uint64_t opt_set = 0;                // the forwarded options (options.h) set so far, bit = table row: replayed,
+                                         // with the values the members hold, on the sketch index when it is created
     int n_ctx = 4;            // contexts (and streams) per shard (bfloat16 batches of 1M x 768: 3 -> 4 = 155 -> 162 k queries/s; 6: no more)
-    int n_ctx_active = 4;
-    int query_batch = 16;     // queries per scan launch
-    int radius_mq = 1;        // radius batches of 2+ queries share one sweep of the corpus (the shared sweeps' collect form)
-    int finish_thread = 1;    // shared-sweep calls of 3+ batches: a second host thread assembles the finished batches
-                              // while the caller's prepares and enqueues the next ones (0 = one thread does both)
-    int queries_per_launch = 16;  // sweeps one scan launch walks back to back (query-major)
-    int scan_group = 0;       // queries of a launch the one-sweep kernel scores per row read, where the launch qualifies
-                              // (8-bit rows, top-k, no masks, lists in registers): 0 = automatic, 1, 2 or 4
-    int scan_group_ring = 0;  // ring depth of the grouped row-shape kernels that exist at two: 0 = automatic, or one of the
-                              // depths the library carries (szg::scan_group_ring_known)
-    int scan_norms = 0;       // grouped one-sweep launches take the rows' norms from the resident array (ensure_row_norms):
-                              // 0 = automatic, 1 = always sum them in the sweep
-    int sketch_planes = 0;    // digit planes of a query prepared for a sketch sweep: 0 = automatic (2, |Q| <= 16000),
-                              // 3 = the plain 8-bit handles' (|Q| <= 10^6).  Only is_sketch indexes read it (scan_planes).
-    int sketch_matrix = 0;    // the matrix sweep (kernels_scan_mx.hip) for one-sweep launches that qualify -- tiled 8-bit rows,
-                              // two-plane queries, resident norms, no masks, scan_group = 0: 0 = automatic (launches of
-                              // szg::kMatrixMinQueries queries or more), 1 = never, 2 = every such launch
-    int sketch_select = 0;    // the matrix sweep's selection: 0 = automatic (row lists where the lists hold at most
-                              // szg::kRowListMax entries), 1 = the serial inserts everywhere
-    int sketch_wide = 0;      // the matrix sweep's two-block form (32 queries per row read): 0 = automatic (calls of
-                              // kWideCallMin one-sweep queries on, under the default query_batch and queries_per_launch),
-                              // 1 = never, 2 = every call of more than 16 queries where the shape allows
-    int sketch_share = 0;     // the matrix sweep's shared form (64 queries per launch, paired blocks walk the same rows):
-                              // 0 = automatic (calls of kShareCallMin one-sweep queries on, under the default query_batch
-                              // and queries_per_launch), 1 = never, 2 = every sketch call of more than 32 queries, in
-                              // batches of up to 64 from its first query on
-    int sketch_bulk = 0;      // the row lists' whole-tile merge: 0 = automatic (tiles with szg::kBulkMin passing pairs or more),
-                              // 1 = never (rounds only), n >= 2 = tiles with n passing pairs or more
-    int sketch_radius = 0;    // radius queries that would each take a sweep of their own (a lone query, radius_mq = 0) go
-                              // through the sketch where it applies to the handle: 0 = never (the default: the option
-                              // soaks, as the top-k pre-pass did, before a later change makes it automatic), 1 = always
-    int sketch_masked = 0;    // top-k launches of the sketch pre-pass with tombstones or filter masks take the matrix sweep's
-                              // masked forms wherever the same launch without masks would take the matrix sweep: 0 = never
-                              // (the default while the option soaks: masked launches keep the one-query kernel), 1 = always
-    int sketch_f64 = 0;       // float64 handles (the reference's default quantization) keep an 8-bit sketch too, an eighth of
-                              // their rows' bytes, under every rule of float32 handles: 0 = never (the default while the
-                              // option soaks: such a handle keeps no sketch and allocates nothing more), 1 = always
-    int sketch_topk_collect = 0;  // top-k calls that take a sweep per query with a k the pre-pass does not serve go through
-                              // the sketch as a sample pass and a collect sweep (scan_sketch_topk.cpp, SketchTopkCall): 0 = never
-                              // (the default while the option soaks), 1 = wherever the sample plan serves every shard
+    int n_ctx_active = 4;     // of them in rotation (the rest parked): the last accepted value of option "contexts"
     szg_sketch_topk_stats sk_topk{};  // what that path served (stats_mu; szg_index_sketch_topk_stats, szg_reset_stats)
-    int query_prep = 0;       // the batches of a top-k call through the sketch have their queries prepared on the card
-                              // (kernels_query_prep.hip) instead of by prep_query: 0 = never (the default while the option
-                              // soaks), 1 = batches of kQueryPrepMin queries or more, 2 = every batch (query_prep_serves)
     szg_query_prep_stats qp{};  // which side prepared such calls' queries (stats_mu; szg_index_query_prep_stats, szg_reset_stats)
     bool is_sketch = false;   // this index is the internal sketch of a float32 (or float64) handle: its keys only bound
-    int tie_mode = 0;         // 0: exact full replay on ties/NaN, 1: keep the fast answer
-    int serialize_scans = 1;  // scan launches of a shard never overlap each other
-    int multi_query = 1;      // share one sweep between the queries of a batch (MFMA path)
-    int mask_dense = 1;       // masked sweeps whose masks pass most rows use the dense phase
-    int coalesce = 1;         // concurrent single-query calls share sweeps (see Combiner)
-    int mq_min = 2;           // smallest batch worth a shared sweep (measured: 2 queries already break even)
-    int mq_hits = 1024;       // fused selection: candidates per query the full sweep is expected to collect
-                              // (sets the prefix: n_rows * kp / mq_hits rows)
-    // test hooks: paths that occur by themselves only on particular data
-    int force_escalate = 0;   // treat every first pass as uncertified
-    int force_matrix = 0;     // shared sweeps: the score-matrix form (what an overflowing candidate buffer falls back to)
-    int force_no_refine = 0;  // shared sweeps: the batch's tail as separate re-score / select / rerank launches (kp > 256)
-    int force_sketch_nomem = 0;  // the sketch's device allocation is refused (auto mode steps aside)
-    uint64_t carry_stage_bytes = 0;  // a carried column's staging window between two parts; 0 = kCarryStageBytes
     // settled by measurement (rounds 1-3): compile-time facts since round 4, A/B through -D and `make variant`
     static constexpr int blocks_per_cu = 0;     // 0 = waves per CU chosen from the row format (scan_geometry)
     static constexpr int block_threads = 256;
@@ -641,6 +579,8 @@ void ctx_free(Ctx *c);
 // limit > 0: only one of the shard's first `limit` contexts (Ctx::no < limit)
 Ctx *ctx_acquire(Shard *sh, int limit = 0);
 Ctx *ctx_try_acquire(Shard *sh, int limit = 0);
+// the forwarded options set on ix so far, applied to its newly created sketch index
+void options_replay(szg_index *ix, szg_index *sketch);
 // Contexts a call with one sweep per query keeps in flight per shard.  Its sweeps run on the shard's scan stream and
 // each batch's uploads, merge, re-rank and copy-back on its context's stream; streams take the hardware queues the
 // process opens (GPU_MAX_HW_QUEUES, HIP's default 4) in turn, so the shard's fourth context shares a queue with its scan

@@ -99,7 +99,7 @@ int sketch_sync(szg_index *ix)
         ix->sk_need_full = true;
         ix->sketch->is_sketch = true;  // (its queries take two digit planes: scan_planes)
         ix->sketch->timing = ix->timing;
-        for (const auto &o : ix->opt_log) (void)szg_set_option(ix->sketch, o.first.c_str(), o.second);
+        options_replay(ix, ix->sketch);
     }
     szg_index *sk = ix->sketch;
     const size_t n_sh = ix->shards.size();

@@ -1042,6 +1042,14 @@ class ScanIndex:
         check(self._L.szg_set_option(self._h, name.encode(), int(value)), "szg_set_option")
         self.options[name] = int(value)   # (what the host mirrors consult: e.g. tie_mode, collection.py)
 
+    def debug_option(self, name, on_sketch=False):
+        """Test hook (szg_debug_option_get): what option `name` holds on the handle, or on its internal sketch index
+        (SzgError SZG_E_UNSUPPORTED while there is none; never a sync).  "contexts": the contexts in rotation."""
+        out = ctypes.c_int64()
+        check(self._L.szg_debug_option_get(self._h, name.encode(), int(bool(on_sketch)), ctypes.byref(out)),
+              "szg_debug_option_get")
+        return out.value
+
 
 def f64_probe(op, a, b=None):
     """Device float64 primitive probe (tests): 0 div, 1 sqrt, 2 Go acos, 3 round, 4 f32 narrow."""
