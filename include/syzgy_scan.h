@@ -1081,6 +1081,26 @@ int szg_debug_scan_share(int dim, int quant_bits, int n_queries, int kp, int pla
                          int32_t *batches, int32_t batch_capacity, int32_t *n_batches);
 
 /*
+ * Test hook, host only: the matrix sweep's long-row form for ONE unmasked top-k launch of n_queries (1 .. 64) queries
+ * over 8-bit sketch rows of 16 .. 64 whole 64-byte steps (1 024 .. 4 096 dimensions), under the automatic options and the
+ * conditions of szg_debug_scan_matrix; kp = the entries of the launch's lists, block = the threads of the shard's plain
+ * launch (0: the default geometry's).  The form keeps the whole two-plane image of its queries in LDS, up to a CU's
+ * 160 KiB: *serves = 1: the launch takes it; *blocks = its column blocks (1: 16 queries per row read; 2: the wide form of
+ * 17 .. 32 and the shared form of 33 .. 64 queries, *share = 1, where two images, constants and lists fit); *block = its
+ * threads -- 256 and two blocks per CU where the form fits 80 KiB, else one block of 512 per CU on half the grid --
+ * *grid = its blocks, *lds_bytes = 16 b (2 dim + 12 + 8 waves kp), *passes = its passes over the rows.  Rows of fewer
+ * than 16 steps, masked and collect launches never take the form, and neither does any launch over rows that the
+ * one-block form of szg_debug_scan_matrix serves within 64 KiB (1 024 .. 1 856 dimensions at lists of 8: launches of 16
+ * through that form measured faster than the long wide and shared forms there) -- *serves = 0, today's plan.
+ */
+typedef struct szg_scan_long_plan {
+    int32_t serves, blocks, share, block, grid, passes;
+    uint64_t lds_bytes;
+} szg_scan_long_plan;
+int szg_debug_scan_long(int dim, int quant_bits, int n_queries, int kp, int planes, int norms, int tiled, int masked,
+                        int block, szg_scan_long_plan *out);
+
+/*
  * Test hook, host only: the matrix sweep's masked forms (option sketch_masked) for a one-sweep top-k call of n_queries
  * queries through the sketch whose launches carry masks, with the arguments of szg_debug_scan_share plus the option and
  * shared_mask (1: the launch's queries share one mask or have tombstones alone -- its eligibility is wave-uniform; 0:

@@ -69,6 +69,8 @@ EXPORTS = [
     "szg_debug_sketch_info", "szg_debug_sketch_rows",
     # the matrix sweep's masked forms (option sketch_masked): the plan hook and the counters
     "szg_debug_scan_masked", "szg_debug_sketch_masked",
+    # the matrix sweep's long-row form (1 024 .. 4 096 dimensions): the plan hook
+    "szg_debug_scan_long",
     # the certification bound of a key as a pure function (csrc/key_bound.h), host only
     "szg_debug_key_eps",
     # top-k of large k through the sketch (option sketch_topk_collect): the counters and the sample plan hook
@@ -176,6 +178,11 @@ class SzgSketchInfo(ctypes.Structure):
 
 class SzgScanMaskedPlan(ctypes.Structure):
     _fields_ = [(name, ctypes.c_int32) for name in ("serves", "wide", "share", "tile_skip", "steps_form", "launches", "passes")]
+
+
+class SzgScanLongPlan(ctypes.Structure):
+    _fields_ = ([(name, ctypes.c_int32) for name in ("serves", "blocks", "share", "block", "grid", "passes")] +
+                [("lds_bytes", ctypes.c_uint64)])
 
 
 class SzgSketchMaskedInfo(ctypes.Structure):
@@ -468,6 +475,9 @@ def load():
         L.szg_debug_scan_masked.argtypes = [ctypes.c_int] * 15 + [ctypes.POINTER(SzgScanMaskedPlan)]
         L.szg_debug_sketch_masked.restype = ctypes.c_int
         L.szg_debug_sketch_masked.argtypes = [vp, ctypes.POINTER(SzgSketchMaskedInfo)]
+    if hasattr(L, "szg_debug_scan_long"):
+        L.szg_debug_scan_long.restype = ctypes.c_int
+        L.szg_debug_scan_long.argtypes = [ctypes.c_int] * 9 + [ctypes.POINTER(SzgScanLongPlan)]
     if hasattr(L, "szg_index_sketch_topk_stats"):
         L.szg_index_sketch_topk_stats.restype = ctypes.c_int
         L.szg_index_sketch_topk_stats.argtypes = [vp, ctypes.POINTER(SzgSketchTopkStats)]

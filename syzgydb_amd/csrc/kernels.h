@@ -212,6 +212,9 @@ SZG_DECL_SCAN(4) SZG_DECL_SCAN(8) SZG_DECL_SCAN(16) SZG_DECL_SCAN(32) SZG_DECL_S
 SZG_DECL_G8(0) SZG_DECL_G8(1) SZG_DECL_G8(2) SZG_DECL_G8(3)
 SZG_DECL_SCAN_V(launch_scan_mx_m0) SZG_DECL_SCAN_V(launch_scan_mx_m1)
 SZG_DECL_SCAN_V(launch_scan_mxc_m0) SZG_DECL_SCAN_V(launch_scan_mxc_m1)
+// ... and with -DSZG_MX_LONG its long-row form (mxl; ScanVariant::long_rows): rows of 16 .. 64 steps, up to 160 KiB of LDS,
+// blocks of up to kLongBlockMax threads -- the one-block kernels (row lists, serial inserts) and the wide one
+SZG_DECL_SCAN_V(launch_scan_mxl_m0) SZG_DECL_SCAN_V(launch_scan_mxl_m1)
 #undef SZG_DECL_G8
 #undef SZG_DECL_SCAN_V
 // The matrix sweep's shared form (kernels_scan_mx.hip with -DSZG_MX_SHARE: objects of their own): ONE launch of 33 ..
@@ -221,6 +224,9 @@ hipError_t launch_scan_share(int qbits, int metric, const ScanArgs &a, const Sca
                              hipStream_t stream);
 hipError_t launch_scan_mxs_m0(const ScanShareArgs &s, const ScanVariant &v, int grid, int block, size_t lds, hipStream_t stream);
 hipError_t launch_scan_mxs_m1(const ScanShareArgs &s, const ScanVariant &v, int grid, int block, size_t lds, hipStream_t stream);
+// (the long-row shared form: -DSZG_MX_LONG -DSZG_MX_SHARE)
+hipError_t launch_scan_mxls_m0(const ScanShareArgs &s, const ScanVariant &v, int grid, int block, size_t lds, hipStream_t stream);
+hipError_t launch_scan_mxls_m1(const ScanShareArgs &s, const ScanVariant &v, int grid, int block, size_t lds, hipStream_t stream);
 // what scan_variant decides from for a shared launch
 inline ScanPlanIn scan_share_plan_in(int qbits, const ScanArgs &a, const ScanShareHi &hi, int block)
 {

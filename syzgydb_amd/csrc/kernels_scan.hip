@@ -1009,6 +1009,7 @@ hipError_t launch_scan_qmcm(const ScanArgs &a, int grid, int block, hipStream_t 
     if (!v.wide && a.n_queries > kMaxSweepsPerLaunch) return hipErrorInvalidValue;
     if constexpr (QBITS == 8 && !COLLECT && !MASKED) {
         // the matrix sweep: up to kMatrixQueries queries per row read on the matrix cores (kernels_scan_mx.hip)
+        if (v.matrix && v.long_rows) return METRIC == kCosine ? launch_scan_mxl_m1(a, v, grid, block, lds, stream) : launch_scan_mxl_m0(a, v, grid, block, lds, stream);
         if (v.matrix) return METRIC == kCosine ? launch_scan_mx_m1(a, v, grid, block, lds, stream) : launch_scan_mx_m0(a, v, grid, block, lds, stream);
         // G > 1: the form of the kernel -- two digit planes where the queries carry two (bit 0), resident norms where
         // the launch has them (bit 1); every form is an object of its own (SZG_GROUP_FORM)

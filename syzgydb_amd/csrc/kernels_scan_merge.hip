@@ -303,6 +303,7 @@ hipError_t launch_scan_share(int qbits, int metric, const ScanArgs &a, const Sca
     ScanShareArgs s;
     s.a = a;
     s.hi = hi;
+    if (v.long_rows) return (metric == kCosine ? launch_scan_mxls_m1 : launch_scan_mxls_m0)(s, v, grid, block, lds, stream);
     return (metric == kCosine ? launch_scan_mxs_m1 : launch_scan_mxs_m0)(s, v, grid, block, lds, stream);
 }
 

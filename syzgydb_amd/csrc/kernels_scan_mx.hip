@@ -53,6 +53,9 @@
 // a.kp rows, as scan_kernel leaves them.
 #include "kernels.h"
 #include "device_lists.h"
+#ifdef SZG_MX_LONG
+#include <atomic>
+#endif
 #ifdef SZG_MX_MASKED
 #include "mask_tiles.h"
 #endif
@@ -137,6 +140,29 @@ constexpr int mx_ring()
 // is neither loaded nor multiplied; the ring's look-ahead points at the tile the walk found.  With per-query masks the
 // walk sees the live words alone, and lane t < 4 NB of every lane-row fetches slot t's 16-bit allow slice beside the norm
 // (the idle columns read the launch's last query's); the finish hands slot r's slice to the lane-row's 16 lanes.
+// With -DSZG_MX_LONG the file builds the LONG-ROW forms instead (objects of their own, and with -DSZG_MX_SHARE on top the
+// long shared form; DESIGN.md 4.5 item 17, ScanVariant::long_rows): unmasked top-k sweeps over rows of kLongMinSteps ..
+// kLongMaxSteps steps (1 024 .. 4 096 dimensions), any-steps kernels only.  The image of a column block is 2 KiB per step
+// -- 32 .. 128 KiB -- and stays whole in LDS, of which a launch may take the CU's 160 KiB (scan_long_plan, scan_plan.h):
+//  * the block: 256 threads and two blocks per CU where image, constants and lists fit 80 KiB, else ONE block of 512
+//    threads per CU.  Its eight waves stage the image once and all walk tiles against it, so a SIMD holds two waves
+//    either way (one wave alone would expose every load); the kernels' bound is 512 threads, 256 registers, no scratch.
+//    The per-wave list area grows with the waves and is part of the fit rule.
+//  * the tile loop: a tile is 16 .. 64 DEPENDENT steps on one pair of accumulators per block, so a wave's steps are walked
+//    as one stream with kLongRing = 8 row loads in flight (a tile is at least two turns of the ring; the ring of 4 was
+//    tuned for rows that end after 1 .. 15 steps), and the A operands of step s + 1 are read from LDS into the other half
+//    of a double buffer while the matrix instructions of step s run: the LDS latency hides behind 2 NB of them instead
+//    of in front of each.
+//  * the keys: exactly the any-STEPS chain above -- fmaf(128, float(M), float(L)) and on -- so a (query, row) pair gets
+//    the bits the one-block any-steps kernel gives it where both can run (16 .. 29 steps).  Why 64 steps are safe: a
+//    digit |m|, |l| <= 128 and |v'| <= 128, so a plane sum is at most 128 * 128 * 4 096 = 2^26 < 2^27 in the int32
+//    accumulators; float(M) and float(L) round once each (|M|, |L| may pass 2^24), the two conversions the chain already
+//    counts; fmaf(128, M, L) rounds once; |128 M + L| <= 129 * 2^26 and |2 dot + qconst| < 2^35 are far inside float's
+//    range, and key_eps' integer branch (key_bound.h) bounds a key's error by a count of roundings -- 16, of which the
+//    chain takes 8 -- times an ulp of Qmax * 128 * dim, which scales with dim itself: nothing in it assumes a short row.
+#if defined(SZG_MX_LONG) && (defined(SZG_MX_MASKED) || defined(SZG_MX_COLLECT))
+#error "the long-row forms: unmasked top-k (SZG_MX_LONG alone, or with SZG_MX_SHARE)"
+#endif
 #if defined(SZG_MX_MASKED)
 #define SZG_MX_KERNEL_ARGS const ScanMaskedArgs ma
 #elif defined(SZG_MX_SHARE)
@@ -151,9 +177,19 @@ constexpr int mx_ring()
 #else
 #define SZG_MX_FOUR_WAVES(METRIC, STEPS) true
 #endif
+// (the long-row forms: blocks of up to kLongBlockMax threads, eight waves on a CU -- 256 registers)
+#ifdef SZG_MX_LONG
+#define SZG_MX_BOUNDS(METRIC, STEPS, ROWS, NB) __launch_bounds__(kLongBlockMax)
+#else
+#define SZG_MX_BOUNDS(METRIC, STEPS, ROWS, NB) \
+    __launch_bounds__(256, ((ROWS) && (NB) == 1 && (STEPS) != 0 && SZG_MX_FOUR_WAVES(METRIC, STEPS)) ? 4 : 2)
+#endif
 template <int METRIC, int STEPS, bool NT, bool ROWS, int NB = 1, bool COLLECT = false>
-__global__ __launch_bounds__(256, (ROWS && NB == 1 && STEPS != 0 && SZG_MX_FOUR_WAVES(METRIC, STEPS)) ? 4 : 2) void scan_mx_kernel(SZG_MX_KERNEL_ARGS)
+__global__ SZG_MX_BOUNDS(METRIC, STEPS, ROWS, NB) void scan_mx_kernel(SZG_MX_KERNEL_ARGS)
 {
+#ifdef SZG_MX_LONG
+    static_assert(STEPS == 0 && !COLLECT, "the long-row forms: any-steps top-k kernels");
+#endif
 #ifdef SZG_MX_MASKED
     static_assert(!COLLECT, "the masked forms: top-k");
     const ScanArgs &a = ma.a;
@@ -500,7 +536,13 @@ __global__ __launch_bounds__(256, (ROWS && NB == 1 && STEPS != 0 && SZG_MX_FOUR_
 #endif
             }
         } else {
+#ifdef SZG_MX_LONG
+            constexpr int D = kLongRing;
+            static_assert(D % 2 == 0, "a turn of the ring keeps the parity of the A operands' double buffer");
+            v4i32 qa[2][NB][2];  // the A operands of the step at hand and of the next: [u & 1][block][plane m, l]
+#else
             constexpr int D = 4;
+#endif
             u32x4 ring[D];
             v4i32 accM[NB], accL[NB];
 #pragma unroll
@@ -545,6 +587,36 @@ __global__ __launch_bounds__(256, (ROWS && NB == 1 && STEPS != 0 && SZG_MX_FOUR_
             iptr += 1024;                                                                \
         }                                                                                \
     }
+#ifdef SZG_MX_LONG
+// (the step's A operands came in with the previous step; the next step's -- the next tile's first after the last -- are
+// on their way while this step's matrix instructions run)
+#define SZG_MX_CONSUME(u)                                                                \
+    {                                                                                    \
+        const u32x4 v_ = ring[u];                                                        \
+        if (cs == 0) norm = a.row_norm[min(ctile * 16 + trow, last_row)];                \
+        const int ns_ = cs + 1 == steps ? 0 : cs + 1;                                    \
+        _Pragma("unroll") for (int b_ = 0; b_ < NB; b_++) {                             \
+            qa[((u) + 1) & 1][b_][0] = qimg[((b_ * steps + ns_) * 2 + 0) * 64];          \
+            qa[((u) + 1) & 1][b_][1] = qimg[((b_ * steps + ns_) * 2 + 1) * 64];          \
+        }                                                                                \
+        v4i32 bop_;                                                                      \
+        bop_[0] = (int)(v_.x ^ 0x80808080u);                                             \
+        bop_[1] = (int)(v_.y ^ 0x80808080u);                                             \
+        bop_[2] = (int)(v_.z ^ 0x80808080u);                                             \
+        bop_[3] = (int)(v_.w ^ 0x80808080u);                                             \
+        _Pragma("unroll") for (int b_ = 0; b_ < NB; b_++) {                             \
+            accM[b_] = __builtin_amdgcn_mfma_i32_16x16x64_i8(qa[(u) & 1][b_][0], bop_, accM[b_], 0, 0, 0); \
+            accL[b_] = __builtin_amdgcn_mfma_i32_16x16x64_i8(qa[(u) & 1][b_][1], bop_, accL[b_], 0, 0, 0); \
+        }                                                                                \
+        if (++cs == steps) {                                                             \
+            finish_tile(ctile, accM, accL, norm);                                        \
+            _Pragma("unroll") for (int b_ = 0; b_ < NB; b_++)                            \
+                accM[b_] = accL[b_] = v4i32{0, 0, 0, 0};                                 \
+            cs = 0;                                                                      \
+            SZG_MX_NEXT_C                                                                \
+        }                                                                                \
+    }
+#else
 #define SZG_MX_CONSUME(u)                                                                \
     {                                                                                    \
         const u32x4 v_ = ring[u];                                                        \
@@ -572,6 +644,7 @@ __global__ __launch_bounds__(256, (ROWS && NB == 1 && STEPS != 0 && SZG_MX_FOUR_
             SZG_MX_NEXT_C                                                                \
         }                                                                                \
     }
+#endif  // SZG_MX_LONG
 #ifndef SZG_MX_MASKED
             uint64_t issued = D, consumed = 0;
 #endif
@@ -582,6 +655,13 @@ __global__ __launch_bounds__(256, (ROWS && NB == 1 && STEPS != 0 && SZG_MX_FOUR_
             }
             __syncthreads();  // the image and the constants are complete
             read_consts();
+#ifdef SZG_MX_LONG
+#pragma unroll
+            for (int b_ = 0; b_ < NB; b_++) {  // step 0 of the first tile
+                qa[0][b_][0] = qimg[(b_ * steps * 2 + 0) * 64];
+                qa[0][b_][1] = qimg[(b_ * steps * 2 + 1) * 64];
+            }
+#endif
 #ifdef SZG_MX_MASKED
             // (no fixed count of steps: the stream ends on "no further tile")
             while (ctile < n_tiles) {
@@ -655,7 +735,35 @@ __global__ __launch_bounds__(256, (ROWS && NB == 1 && STEPS != 0 && SZG_MX_FOUR_
     }
 }
 
-#if defined(SZG_MX_MASKED) && defined(SZG_MX_SHARE)
+#if defined(SZG_MX_LONG)
+// a long-row kernel: its dynamic LDS may pass the 64 KiB a kernel gets unasked -- the limit of each instantiation is
+// raised once per device, to the most a long form may ask for, and not on the launch path again
+template <auto Kern, typename Args>
+hipError_t launch_mxl(const Args &s, int grid, int block, size_t lds, hipStream_t stream)
+{
+    static std::atomic<uint64_t> raised{0};  // bit d: done on device d
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return e;
+    const uint64_t bit = 1ull << (dev & 63);
+    if (dev > 63 || !(raised.load(std::memory_order_acquire) & bit)) {
+        e = hipFuncSetAttribute(reinterpret_cast<const void *>(Kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLongLdsCu);
+        if (e != hipSuccess) return e;
+        raised.fetch_or(bit, std::memory_order_release);
+    }
+    hipLaunchKernelGGL(Kern, dim3(grid), dim3(block), lds, stream, s);
+    return hipGetLastError();
+}
+// (scan_variant's conditions, once more, for every long form: a launch that does not meet them must not reach these kernels)
+bool mx_long_ok(const ScanArgs &a, const ScanVariant &v, int grid, int block, size_t lds)
+{
+    return v.matrix && v.long_rows && !v.masked && v.matrix_steps == 0 && v.nontemporal && a.tiled && (int)a.steps * 4 == a.map.r16 &&
+           scan_long_steps(a.map.r16) && a.planes == 2 && a.row_norm && a.block_lists && a.kp >= 1 && a.kp <= 64 && !a.collect &&
+           !scan_masked(a) && a.n_queries >= 1 && grid >= 1 && block >= 64 && block <= kLongBlockMax && block % 64 == 0 &&
+           lds <= kLongLdsCu && (v.row_lists != 0) == matrix_row_lists(a.kp, a.select) &&
+           lds == scan_lds_bytes(8, a.map, a.kp, block, v.group, a.planes, v.matrix_blocks());
+}
+#elif defined(SZG_MX_MASKED) && defined(SZG_MX_SHARE)
 template <int STEPS>
 hipError_t launch_mxms_steps(const ScanMaskedArgs &s, int grid, int block, size_t lds, hipStream_t stream)
 {
@@ -709,7 +817,33 @@ hipError_t launch_mxc_steps(const ScanArgs &a, bool wide, int grid, int block, s
 // (defined by its qualified name: it has to match its declaration in kernels.h)
 #define SZG_CAT2(a, b) a##b
 #define SZG_CAT(a, b) SZG_CAT2(a, b)
-#if defined(SZG_MX_MASKED)
+#if defined(SZG_MX_LONG) && defined(SZG_MX_SHARE)
+// the long-row shared form of ONE metric (objects of their own, -DSZG_MX_LONG -DSZG_MX_SHARE)
+hipError_t szg::SZG_CAT(launch_scan_mxls_m, SZG_SCAN_METRIC)(const ScanShareArgs &s, const ScanVariant &v, int grid, int block,
+                                                           size_t lds, hipStream_t stream)
+{
+    const ScanArgs &a = s.a;
+    // exactly the planned form: row lists, 33 .. 64 queries, an even grid (share_map pairs its blocks), the two-block LDS
+    if (!mx_long_ok(a, v, grid, block, lds) || !v.share || v.wide || !v.row_lists || a.wide == 1 || s.hi.share == 1 ||
+        a.n_queries <= kMatrixWideQueries || a.n_queries > kMatrixShareQueries || grid < 2 || grid % 2)
+        return hipErrorInvalidValue;
+    return launch_mxl<scan_mx_kernel<SZG_SCAN_METRIC, 0, true, true, 2>>(s, grid, block, lds, stream);
+}
+#elif defined(SZG_MX_LONG)
+// the long-row forms of ONE metric (objects of their own, -DSZG_MX_LONG): one block with row lists or serial inserts, wide
+hipError_t szg::SZG_CAT(launch_scan_mxl_m, SZG_SCAN_METRIC)(const ScanArgs &a, const ScanVariant &v, int grid, int block,
+                                                          size_t lds, hipStream_t stream)
+{
+    if (!mx_long_ok(a, v, grid, block, lds) || v.share) return hipErrorInvalidValue;
+    if (v.wide) {
+        if (!v.row_lists || a.wide == 1 || a.n_queries <= kMatrixQueries || a.n_queries > kMatrixWideQueries) return hipErrorInvalidValue;
+        return launch_mxl<scan_mx_kernel<SZG_SCAN_METRIC, 0, true, true, 2>>(a, grid, block, lds, stream);
+    }
+    if (a.n_queries > kMaxSweepsPerLaunch) return hipErrorInvalidValue;
+    if (v.row_lists) return launch_mxl<scan_mx_kernel<SZG_SCAN_METRIC, 0, true, true>>(a, grid, block, lds, stream);
+    return launch_mxl<scan_mx_kernel<SZG_SCAN_METRIC, 0, true, false>>(a, grid, block, lds, stream);
+}
+#elif defined(SZG_MX_MASKED)
 // the masked forms of ONE metric (objects of their own, -DSZG_MX_MASKED; with -DSZG_MX_SHARE the masked shared form)
 namespace szg {
 namespace {

@@ -768,6 +768,39 @@ int szg_debug_scan_share(int dim, int quant_bits, int n_queries, int kp, int pla
     return SZG_OK;
 }
 
+// the matrix sweep's long-row form for ONE top-k launch of n_queries over the sketch rows of (dim, quant_bits), under the
+// automatic options, with the geometry the launch path gives it (sketch_long_shape): a launch of more than 16 queries is
+// asked as a wide or shared one first and, where two blocks do not fit, as the one-block launch that walks its groups
+int szg_debug_scan_long(int dim, int quant_bits, int n_queries, int kp, int planes, int norms, int tiled, int masked, int block,
+                        szg_scan_long_plan *out)
+{
+    if (!out) return fail(SZG_E_INVALID, "null argument");
+    if (kp < 0 || n_queries < 1 || n_queries > szg::kMatrixShareQueries) return fail(SZG_E_INVALID, "kp or n_queries out of range");
+    if (block != 0 && (block < 64 || block > 1024 || block % 64)) return fail(SZG_E_INVALID, "block is 0 or a multiple of 64 up to 1024");
+    PlanHook h;
+    const int automatic = 0;
+    if (const int rc = h.sketch_rows(dim, quant_bits, kp, false, planes, norms, tiled, masked, 0, 0, &automatic, &automatic, 0, 0))
+        return rc;
+    const int plain = block ? block : h.g.block;
+    szg::ScanVariant v{};
+    LaunchShape g{};
+    for (int blocks = n_queries > szg::kMatrixQueries ? 2 : 1; blocks >= 1; blocks--) {
+        g = sketch_long_shape(h.s, h.g.grid, plain, masked != 0, kp, n_queries, blocks, 0);
+        h.in = sketch_plan_in(h.s, kp, false, masked != 0, n_queries, g.block);
+        v = szg::scan_variant(h.in);
+        if (v.matrix_blocks() == blocks) break;
+    }
+    memset(out, 0, sizeof(*out));
+    out->serves = v.long_rows;
+    out->blocks = v.long_rows ? v.matrix_blocks() : 0;
+    out->share = v.long_rows && v.share ? 1 : 0;
+    out->block = g.block;
+    out->grid = v.share ? szg::share_grid(g.grid) : g.grid;
+    out->lds_bytes = szg::scan_lds_bytes(h.in.qbits, h.in.map, h.in.kp, h.in.block, v.group, h.in.planes, v.matrix_blocks());
+    out->passes = launch_passes(h.in);
+    return SZG_OK;
+}
+
 // the matrix sweep's masked forms (option sketch_masked) for a one-sweep top-k call of n_queries through the sketch whose
 // launches carry masks: the form a launch of min(n_queries, 64) takes, and the call's launches and passes as
 // szg_debug_scan_share counts the unmasked call's

@@ -87,7 +87,51 @@ ScanVariant scan_variant(const ScanPlanIn &in)
             v.group = kMatrixWideQueries;
         }
     }
+    // The long-row form (kLongMinSteps .. kLongMaxSteps steps): unmasked top-k launches under the conditions above, but
+    // with up to kLongLdsCu of LDS and blocks of up to kLongBlockMax threads.  Launches of 17 .. 64 queries take its wide
+    // and shared forms where two blocks fit, every other one the long one-block form.
+    if (in.qbits == 8 && !in.masked && !in.collect && !v.deep && in.kp >= 1 && in.tiled && scan_long_steps(m.r16) &&
+        in.planes == 2 && in.norms && in.group == 0 && in.matrix_opt != 1 &&
+        in.n_queries >= (in.matrix_opt == 2 ? 1 : kMatrixMinQueries) && in.block >= kWave && in.block <= kLongBlockMax &&
+        in.block % kWave == 0) {
+        const bool rows = matrix_row_lists(in.kp, in.select_opt);
+        // Measured ("long rows"): at 1 024 dimensions the two-block forms on blocks of 256 were slower per
+        // query than the one-block form of 64 KiB.  Where that form serves the shape at the default block, every launch
+        // keeps today's plan: the long forms begin where it ends (1 920 dimensions with lists of 8).
+        const bool short_form = scan_lds_bytes(in.qbits, m, in.kp, 256, kMatrixQueries, in.planes, 1) <= kLdsMax;
+        // (two waves per SIMD: blocks of up to 256 threads come two to a CU and get half its LDS each -- which two column
+        // blocks of rows beyond the short form, 128 KiB and more, never fit: the wide and shared forms take the block of 512)
+        const size_t budget = in.block > 256 ? kLongLdsCu : kLongLdsHalf;
+        const bool two = rows && in.wide_opt != 1 && in.block > 256 &&
+                         scan_lds_bytes(in.qbits, m, in.kp, in.block, kMatrixWideQueries, in.planes, 2) <= kLongLdsCu;
+        const bool wide = two && in.n_queries > kMatrixQueries && in.n_queries <= kMatrixWideQueries;
+        const bool share = two && in.share_opt != 1 && in.n_queries > kMatrixWideQueries && in.n_queries <= kMatrixShareQueries;
+        const bool one = scan_lds_bytes(in.qbits, m, in.kp, in.block, kMatrixQueries, in.planes, 1) <= budget;
+        if (!short_form && (wide || share || one)) {
+            v.matrix = v.long_rows = 1;
+            v.masked = 0;
+            v.matrix_steps = 0;
+            v.shaped = 0;
+            v.ring_depth = kLongRing;
+            v.row_lists = rows ? 1 : 0;
+            v.wide = wide ? 1 : 0;
+            v.share = share ? 1 : 0;
+            v.group = wide || share ? kMatrixWideQueries : kMatrixQueries;
+        }
+    }
     return v;
+}
+
+LongPlan scan_long_plan(const RowMap &m, int kp, int blocks)
+{
+    if (!scan_long_steps(m.r16) || kp < 1 || kp > 64 || (blocks != 1 && blocks != 2)) return LongPlan{0, 0, 0};
+    // (rows that the one-block form of 64 KiB serves keep it: scan_variant)
+    const size_t half = scan_lds_bytes(8, m, kp, 256, kMatrixQueries, 2, 1);
+    if (half <= kLdsMax) return LongPlan{0, 0, 0};
+    if (blocks == 1 && half <= kLongLdsHalf) return LongPlan{256, 2, half};
+    const size_t whole = scan_lds_bytes(8, m, kp, kLongBlockMax, kMatrixQueries * blocks, 2, blocks);
+    if (whole <= kLongLdsCu) return LongPlan{kLongBlockMax, 1, whole};
+    return LongPlan{0, 0, 0};
 }
 
 size_t scan_lds_bytes(int qbits, const RowMap &m, int kp, int block, int group, int planes, int matrix)

@@ -97,6 +97,9 @@ struct ScanVariant {
                       // from HBM where the partner's lines are still on the die (its own launcher: launch_scan_share)
     int masked = 0;   // the matrix sweep's masked form (option sketch_masked; objects of their own, launch_scan_masked): the
                       // launch has tombstones or filter masks and takes the matrix sweep all the same
+    int long_rows = 0;  // the matrix sweep's long-row form (rows of kLongMinSteps .. kLongMaxSteps steps; objects of their own,
+                      // kernels_scan_mx.hip -DSZG_MX_LONG): the image may take the CU's whole LDS, blocks of up to kLongBlockMax
+                      // threads; set together with matrix / wide / share
 };
 // What "automatic" (scan_group = 0) asks for, where a launch qualifies.
 constexpr int kScanGroupAuto = 4;
@@ -135,6 +138,29 @@ constexpr bool sketch_share_known(int64_t v) { return v == 0 || v == 1 || v == 2
 // the matrix sweep -- one block, wide, shared -- wherever the same launch without masks would; 0 = masked launches keep
 // the one-query kernel.
 constexpr bool sketch_masked_known(int64_t v) { return v == 0 || v == 1; }
+
+// The long-row form: unmasked top-k launches over rows of kLongMinSteps .. kLongMaxSteps whole
+// 64-byte steps (1 024 .. 4 096 dimensions), whose image is too large for the 64 KiB the other forms keep to.  A gfx950 CU
+// has 160 KiB of LDS: a form that fits half of it runs two blocks of 256 threads per CU, as every other sweep over tiled
+// 8-bit rows does; a larger one runs ONE block of kLongBlockMax threads per CU, which stages the image once for its eight
+// waves -- either way a SIMD holds two waves.  Chosen by shape alone; sketch_matrix = 1 and sketch_wide = 1 leave it out
+// as they leave out the forms below 16 steps.  Rows that the one-block form of 64 KiB serves at the default block (up to
+// 1 856 dimensions at lists of 8) keep today's plan for every launch: the long forms measured slower there (scan_variant).
+constexpr int kLongMinSteps = 16, kLongMaxSteps = 64;
+constexpr int kLongBlockMax = 512;
+constexpr int kLongRing = 8;  // 16-byte loads a lane keeps in flight (a tile is at least two turns of the ring)
+constexpr size_t kLongLdsCu = 160u * 1024u, kLongLdsHalf = kLongLdsCu / 2;
+constexpr bool scan_long_steps(int r16) { return r16 % 4 == 0 && r16 / 4 >= kLongMinSteps && r16 / 4 <= kLongMaxSteps; }
+// Block size and LDS of the form with `blocks` column blocks (1, or 2: wide and shared) over rows of map m whose waves
+// keep lists of kp entries: one column block runs two blocks of 256 per CU where image, constants and lists fit
+// kLongLdsHalf; a larger one, and every two-block form, ONE block of kLongBlockMax where they fit kLongLdsCu (the lists
+// grow with the waves); else, and for rows that the one-block form of 64 KiB serves, block = 0: the form does not serve.
+// The launch path (sketch_plan.h) and the plan hooks both ask here.
+struct LongPlan {
+    int block, per_cu;
+    size_t lds;
+};
+LongPlan scan_long_plan(const RowMap &m, int kp, int blocks);
 
 // Ring depths of the G > 1 kernels.  A row-shape kernel of P pieces per lane exists at its shape's own depth (the
 // G = 1 kernel's) and, where kGroupRingAlt divides P and differs from it, at kGroupRingAlt as well: scan_group_ring

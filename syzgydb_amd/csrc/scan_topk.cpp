@@ -339,6 +339,7 @@ int enqueue_topk(szg_index *ix, Shard *sh, Ctx *c, int kp, int nq, bool has_allo
     const bool share = L.share;
     const int lists0 = L.lists0, m = L.m, qpl = L.qpl;
     g.grid = L.grid;
+    g.block = L.block;  // (long rows: one block of 512 per CU where the form takes more than half a CU's LDS)
     if (on && on->extra < 1) return fail(SZG_E_INVALID, "sketch: no slot for the drop bound");
     int rc = c->ensure_lists((size_t)nq * lists0 * m);
     if (rc == SZG_OK) rc = c->d_out.ensure((size_t)nq * stride);

@@ -138,6 +138,32 @@ inline ShareGeom share_geometry(int grid, int list_opt, int kp)
     const int S = szg::share_slices(G);
     return ShareGeom{G, S, sketch_list_len(list_opt, kp, S)};
 }
+// The long-row form's geometry (szg::scan_long_plan; rows of 16 .. 64 steps): an unmasked top-k launch of n_queries with
+// `blocks` column blocks, on a shard whose plain sweep takes `grid` blocks of `block` threads.  Where the form fits half a
+// CU's LDS the plain geometry stays; where it takes ONE block of szg::kLongBlockMax threads per CU, that block walks the
+// tiles of two plain blocks: half the grid, half the lists per query (of the length that grid asks for).  Everything
+// else -- shorter rows, masks, a shape or option under which scan_variant does not name the long form for exactly this
+// launch -- keeps (grid, block).
+struct LaunchShape {
+    int grid, block;
+};
+inline LaunchShape sketch_long_shape(const SketchShape &s, int grid, int block, bool masks, int kp, int n_queries, int blocks,
+                                     int matrix_opt)
+{
+    const LaunchShape plain{grid, block};
+    if (s.bits != 8 || masks || kp < 1 || kp > 64 || block != 256 || !szg::scan_long_steps(s.map.r16)) return plain;
+    const szg::LongPlan p = szg::scan_long_plan(s.map, sketch_list_len(s.sketch_list, kp, grid), blocks);
+    if (p.block != szg::kLongBlockMax) return plain;
+    const LaunchShape one{(grid + 1) / 2, p.block};
+    const int m = sketch_list_len(s.sketch_list, kp, blocks == 2 && n_queries > szg::kMatrixWideQueries
+                                                        ? szg::share_slices(szg::share_grid(one.grid))
+                                                        : one.grid);
+    if (szg::scan_long_plan(s.map, m, blocks).block != p.block) return plain;
+    szg::ScanPlanIn in = sketch_plan_in(s, m, false, false, n_queries, one.block);
+    in.matrix_opt = matrix_opt;
+    const szg::ScanVariant v = szg::scan_variant(in);
+    return v.long_rows && v.matrix_blocks() == blocks ? one : plain;
+}
 // Does the matrix sweep's two-block form serve a launch of szg::kMatrixWideQueries queries on the shard, for calls that
 // keep kp candidates per query (scan_variant's answer for that launch)?  kp = 0: the collect form (radius searches
 // through the sketch; no lists).  has_dead: a top-k launch takes the masked form of the same shape under
@@ -146,16 +172,18 @@ inline bool sketch_wide_serves(const SketchShape &s, int grid, int block, bool h
 {
     const bool collect = kp == 0;
     if (kp > 64) return false;
-    const int m = collect ? 0 : sketch_list_len(s.sketch_list, kp, grid);
-    return szg::scan_variant(sketch_plan_in(s, m, collect, has_dead, szg::kMatrixWideQueries, block)).wide != 0;
+    const LaunchShape g = sketch_long_shape(s, grid, block, has_dead, kp, szg::kMatrixWideQueries, 2, s.sketch_matrix);
+    const int m = collect ? 0 : sketch_list_len(s.sketch_list, kp, g.grid);
+    return szg::scan_variant(sketch_plan_in(s, m, collect, has_dead, szg::kMatrixWideQueries, g.block)).wide != 0;
 }
 // ... and its shared form a top-k launch of 33 .. szg::kMatrixShareQueries queries: where the wide form serves the shard
 // (asked with the plain launch's list length; the shared launch's S lists may be longer)
 inline bool sketch_share_serves(const SketchShape &s, int grid, int block, bool has_dead, int kp)
 {
     if (kp < 1 || !sketch_wide_serves(s, grid, block, has_dead, kp)) return false;
-    const int m = share_geometry(grid, s.sketch_list, kp).m;
-    return szg::scan_variant(sketch_plan_in(s, m, false, has_dead, szg::kMatrixShareQueries, block)).share != 0;
+    const LaunchShape g = sketch_long_shape(s, grid, block, has_dead, kp, szg::kMatrixShareQueries, 2, s.sketch_matrix);
+    const int m = share_geometry(g.grid, s.sketch_list, kp).m;
+    return szg::scan_variant(sketch_plan_in(s, m, false, has_dead, szg::kMatrixShareQueries, g.block)).share != 0;
 }
 
 // ---- the call rule: which batches a call through the sketch takes --------------------------------------------------
@@ -251,17 +279,31 @@ inline SketchLaunches sketch_batch_launches(const SketchShape &s, bool sketch, i
     l.m = sketch ? sketch_list_len(s.sketch_list, kp, grid) : kp;
     l.share = sketch && share && !l.masked && !l.early && nq > szg::kMatrixWideQueries && nq <= szg::kMatrixShareQueries &&
               sketch_share_serves(s, grid, block, masks, kp);
-    if (l.share) {
-        const ShareGeom sg = share_geometry(grid, s.sketch_list, kp);
-        l.grid = sg.grid;
-        l.lists0 = sg.slices;
-        l.m = sg.m;
-    }
     // (the same question the call asked before it planned wide batches)
     l.wide = sketch && (wide || share) && !l.masked && nq > szg::kMatrixQueries && sketch_wide_serves(s, grid, block, masks, kp);
     l.qpl = l.share ? szg::kMatrixShareQueries : (l.wide ? szg::kMatrixWideQueries : std::max(1, s.queries_per_launch));
     l.matrix = sketch && (wide || share) && s.sketch_matrix == 0 ? 2 : s.sketch_matrix;
     if (kp > 64) l.matrix = 1;
+    // Long rows: the batch's launches share one geometry, the long form's of its largest launch.  Where that is the block
+    // of 512, a batch of kMatrixMinQueries queries or more takes the matrix sweep whatever a launch's count (as a call with
+    // wide batches does): a rest of one or two queries is a one-block long launch of one pass, not a reason to send the
+    // batch back to blocks of 256.  A batch of one or two queries keeps the plain geometry and the G = 1 / G = 2 kernels.
+    if (sketch && !masks && nq >= szg::kMatrixMinQueries) {
+        const int matrix = l.matrix == 0 ? 2 : l.matrix;
+        const LaunchShape g = sketch_long_shape(s, grid, block, masks, kp, std::min(nq, l.qpl), l.share || l.wide ? 2 : 1, matrix);
+        if (g.block != block) {
+            l.grid = l.lists0 = g.grid;
+            l.block = g.block;
+            l.m = sketch_list_len(s.sketch_list, kp, g.grid);
+            l.matrix = matrix;
+        }
+    }
+    if (l.share) {
+        const ShareGeom sg = share_geometry(l.grid, s.sketch_list, kp);
+        l.grid = sg.grid;
+        l.lists0 = sg.slices;
+        l.m = sg.m;
+    }
     return l;
 }
 // passes of the batch's launch of n queries

@@ -1151,6 +1151,18 @@ def scan_share_plan(dim, quant_bits, n_queries, kp=8, planes=2, norms=True, tile
             "lds_bytes": lds.value, "batches": [int(batches[i]) for i in range(min(nb.value, cap))]}
 
 
+def scan_long_plan(dim, quant_bits, n_queries, kp=8, planes=2, norms=True, tiled=True, masked=False, block=0):
+    """Host-only test hook: the matrix sweep's long-row form (rows of 16 to 64 64-byte steps: 1 024 to 4 096 dimensions)
+    for ONE top-k launch of n_queries queries with lists of kp entries -- whether the launch takes it, its column blocks
+    (2: the wide or, with share, the shared form), its threads per block, grid, LDS bytes and passes over the rows."""
+    L = _lib.load()
+    p = _lib.SzgScanLongPlan()
+    check(L.szg_debug_scan_long(int(dim), int(quant_bits), int(n_queries), int(kp), int(planes), int(bool(norms)),
+                                int(bool(tiled)), int(bool(masked)), int(block), ctypes.byref(p)), "szg_debug_scan_long")
+    return {"serves": bool(p.serves), "blocks": int(p.blocks), "share": bool(p.share), "block": int(p.block),
+            "grid": int(p.grid), "passes": int(p.passes), "lds_bytes": int(p.lds_bytes)}
+
+
 def scan_masked_plan(dim, quant_bits, n_queries, kp=8, planes=2, norms=True, tiled=True, masked=True, scan_group=0,
                      sketch_matrix=0, sketch_select=0, sketch_wide=0, sketch_share=0, sketch_masked=0, shared_mask=True):
     """Host-only test hook: the matrix sweep's masked forms (option sketch_masked) for a one-sweep top-k call of n_queries
