@@ -911,7 +911,9 @@ int szg_index_query_prep_stats(szg_index *ix, szg_query_prep_stats *out);
  *                             wherever the same launch without masks would -- 16 queries per row read, 32 and 64 under the
  *                             sketch_wide and sketch_share rules, the call split as the unmasked call of its size -- with
  *                             a row's eligibility tested where its keys are; a launch whose queries share one mask (or
- *                             have tombstones alone) skips every tile of 16 rows none of which is eligible.  szg_stats.
+ *                             have tombstones alone) skips every tile of 16 rows none of which is eligible.  Rows of
+ *                             1 920 .. 4 096 dimensions take the masked long-row forms (up to a CU's 160 KiB of LDS) exactly
+ *                             where the unmasked launch takes a long form (szg_debug_scan_long_masked).  szg_stats.
  *                             scan_bytes counts one pass per group of such a launch.  Same answers.  0 = never (the
  *                             default): masked launches keep the one-query kernel, one pass per query; the option is new
  *                             and off while it soaks, as sketch_radius was.  Radius searches, plain 8-bit handles and
@@ -1099,6 +1101,18 @@ typedef struct szg_scan_long_plan {
 } szg_scan_long_plan;
 int szg_debug_scan_long(int dim, int quant_bits, int n_queries, int kp, int planes, int norms, int tiled, int masked,
                         int block, szg_scan_long_plan *out);
+/*
+ * ... and the same launch under option sketch_masked (0 or 1): with masked = 1 and sketch_masked = 1 the launch takes the
+ * masked long form wherever the unmasked launch of the same size takes a long form, with that launch's blocks, threads,
+ * grid, LDS bytes and passes (the masks take no LDS); *tile_skip = 1: it skips the tiles none of whose rows is eligible
+ * (shared_mask = 1: one mask for every query, or tombstones alone).  sketch_masked = 0 answers as szg_debug_scan_long.
+ */
+typedef struct szg_scan_long_masked_plan {
+    szg_scan_long_plan plan;
+    int32_t tile_skip;
+} szg_scan_long_masked_plan;
+int szg_debug_scan_long_masked(int dim, int quant_bits, int n_queries, int kp, int planes, int norms, int tiled, int masked,
+                               int block, int sketch_masked, int shared_mask, szg_scan_long_masked_plan *out);
 
 /*
  * Test hook, host only: the matrix sweep's masked forms (option sketch_masked) for a one-sweep top-k call of n_queries

@@ -70,7 +70,7 @@ EXPORTS = [
     # the matrix sweep's masked forms (option sketch_masked): the plan hook and the counters
     "szg_debug_scan_masked", "szg_debug_sketch_masked",
     # the matrix sweep's long-row form (1 024 .. 4 096 dimensions): the plan hook
-    "szg_debug_scan_long",
+    "szg_debug_scan_long", "szg_debug_scan_long_masked",
     # the certification bound of a key as a pure function (csrc/key_bound.h), host only
     "szg_debug_key_eps",
     # top-k of large k through the sketch (option sketch_topk_collect): the counters and the sample plan hook
@@ -183,6 +183,10 @@ class SzgScanMaskedPlan(ctypes.Structure):
 class SzgScanLongPlan(ctypes.Structure):
     _fields_ = ([(name, ctypes.c_int32) for name in ("serves", "blocks", "share", "block", "grid", "passes")] +
                 [("lds_bytes", ctypes.c_uint64)])
+
+
+class SzgScanLongMaskedPlan(ctypes.Structure):
+    _fields_ = [("plan", SzgScanLongPlan), ("tile_skip", ctypes.c_int32)]
 
 
 class SzgSketchMaskedInfo(ctypes.Structure):
@@ -478,6 +482,9 @@ def load():
     if hasattr(L, "szg_debug_scan_long"):
         L.szg_debug_scan_long.restype = ctypes.c_int
         L.szg_debug_scan_long.argtypes = [ctypes.c_int] * 9 + [ctypes.POINTER(SzgScanLongPlan)]
+    if hasattr(L, "szg_debug_scan_long_masked"):
+        L.szg_debug_scan_long_masked.restype = ctypes.c_int
+        L.szg_debug_scan_long_masked.argtypes = [ctypes.c_int] * 11 + [ctypes.POINTER(SzgScanLongMaskedPlan)]
     if hasattr(L, "szg_index_sketch_topk_stats"):
         L.szg_index_sketch_topk_stats.restype = ctypes.c_int
         L.szg_index_sketch_topk_stats.argtypes = [vp, ctypes.POINTER(SzgSketchTopkStats)]

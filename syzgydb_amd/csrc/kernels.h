@@ -261,6 +261,11 @@ hipError_t launch_scan_mxm_m0(const ScanMaskedArgs &s, const ScanVariant &v, int
 hipError_t launch_scan_mxm_m1(const ScanMaskedArgs &s, const ScanVariant &v, int grid, int block, size_t lds, hipStream_t stream);
 hipError_t launch_scan_mxms_m0(const ScanMaskedArgs &s, const ScanVariant &v, int grid, int block, size_t lds, hipStream_t stream);
 hipError_t launch_scan_mxms_m1(const ScanMaskedArgs &s, const ScanVariant &v, int grid, int block, size_t lds, hipStream_t stream);
+// (the masked long-row forms: -DSZG_MX_LONG -DSZG_MX_MASKED, with -DSZG_MX_SHARE the shared one; ScanVariant::long_rows and masked)
+hipError_t launch_scan_mxlm_m0(const ScanMaskedArgs &s, const ScanVariant &v, int grid, int block, size_t lds, hipStream_t stream);
+hipError_t launch_scan_mxlm_m1(const ScanMaskedArgs &s, const ScanVariant &v, int grid, int block, size_t lds, hipStream_t stream);
+hipError_t launch_scan_mxlms_m0(const ScanMaskedArgs &s, const ScanVariant &v, int grid, int block, size_t lds, hipStream_t stream);
+hipError_t launch_scan_mxlms_m1(const ScanMaskedArgs &s, const ScanVariant &v, int grid, int block, size_t lds, hipStream_t stream);
 // ---- kernels_sample_mx.hip: the sample pass of a top-k search of large k through the sketch (option sketch_topk_collect;
 // sample_plan.h has the arithmetic) ----------------------------------------------------------------------------------
 // One launch scores sample tiles 0 .. tiles - 1 -- tile j of the sample is tile j * stride of the rows -- against the

@@ -320,6 +320,10 @@ hipError_t launch_scan_masked(int qbits, int metric, const ScanArgs &a, const Sc
     s.a = a;
     s.hi = hi;
     s.masked = masked_opt;
+    if (v.long_rows) {
+        if (v.share) return (metric == kCosine ? launch_scan_mxlms_m1 : launch_scan_mxlms_m0)(s, v, grid, block, lds, stream);
+        return (metric == kCosine ? launch_scan_mxlm_m1 : launch_scan_mxlm_m0)(s, v, grid, block, lds, stream);
+    }
     if (v.share) return (metric == kCosine ? launch_scan_mxms_m1 : launch_scan_mxms_m0)(s, v, grid, block, lds, stream);
     return (metric == kCosine ? launch_scan_mxm_m1 : launch_scan_mxm_m0)(s, v, grid, block, lds, stream);
 }

@@ -141,7 +141,7 @@ constexpr int mx_ring()
 // walk sees the live words alone, and lane t < 4 NB of every lane-row fetches slot t's 16-bit allow slice beside the norm
 // (the idle columns read the launch's last query's); the finish hands slot r's slice to the lane-row's 16 lanes.
 // With -DSZG_MX_LONG the file builds the LONG-ROW forms instead (objects of their own, and with -DSZG_MX_SHARE on top the
-// long shared form; DESIGN.md 4.5 item 17, ScanVariant::long_rows): unmasked top-k sweeps over rows of kLongMinSteps ..
+// long shared form; DESIGN.md 4.5 item 17, ScanVariant::long_rows): top-k sweeps (masked ones: the next note) over rows of kLongMinSteps ..
 // kLongMaxSteps steps (1 024 .. 4 096 dimensions), any-steps kernels only.  The image of a column block is 2 KiB per step
 // -- 32 .. 128 KiB -- and stays whole in LDS, of which a launch may take the CU's 160 KiB (scan_long_plan, scan_plan.h):
 //  * the block: 256 threads and two blocks per CU where image, constants and lists fit 80 KiB, else ONE block of 512
@@ -160,8 +160,17 @@ constexpr int mx_ring()
 //    counts; fmaf(128, M, L) rounds once; |128 M + L| <= 129 * 2^26 and |2 dot + qconst| < 2^35 are far inside float's
 //    range, and key_eps' integer branch (key_bound.h) bounds a key's error by a count of roundings -- 16, of which the
 //    chain takes 8 -- times an ulp of Qmax * 128 * dim, which scales with dim itself: nothing in it assumes a short row.
-#if defined(SZG_MX_LONG) && (defined(SZG_MX_MASKED) || defined(SZG_MX_COLLECT))
-#error "the long-row forms: unmasked top-k (SZG_MX_LONG alone, or with SZG_MX_SHARE)"
+// With -DSZG_MX_LONG -DSZG_MX_MASKED the file builds the MASKED LONG-ROW forms (objects of their own, and with -DSZG_MX_SHARE
+// on top the masked long shared form): the long form's stream -- the ring of kLongRing loads, the A
+// operands' double buffer -- driven by the masked walk instead of a fixed count of steps.  The issue side and the consume
+// side each walk mask_next_tile on their own and the stream ends on "no further tile"; a skipped tile is neither loaded
+// nor multiplied.  The A operands fetched at a tile's last step are step 0's, whichever tile comes next, and the stream's
+// steps are consumed at ring slots u, u + 1, ... without a gap until its end, so the double buffer's half is the parity of
+// the stream's step count whatever the tiles' step count (30: no multiple of the ring; odd counts).  The per-tile hooks are
+// the masked any-steps kernel's: the slot's 16-bit allow slice beside the norm at a tile's first step (per-query masks),
+// the walk's slice for finish_tile at its last.  Keys: the same operations as the unmasked long form's.
+#if defined(SZG_MX_LONG) && defined(SZG_MX_COLLECT)
+#error "the long-row forms: top-k (SZG_MX_LONG, with SZG_MX_SHARE and / or SZG_MX_MASKED)"
 #endif
 #if defined(SZG_MX_MASKED)
 #define SZG_MX_KERNEL_ARGS const ScanMaskedArgs ma
@@ -593,7 +602,10 @@ __global__ SZG_MX_BOUNDS(METRIC, STEPS, ROWS, NB) void scan_mx_kernel(SZG_MX_KER
 #define SZG_MX_CONSUME(u)                                                                \
     {                                                                                    \
         const u32x4 v_ = ring[u];                                                        \
-        if (cs == 0) norm = a.row_norm[min(ctile * 16 + trow, last_row)];                \
+        if (cs == 0) {                                                                   \
+            norm = a.row_norm[min(ctile * 16 + trow, last_row)];                         \
+            SZG_MX_TILE_START                                                            \
+        }                                                                                \
         const int ns_ = cs + 1 == steps ? 0 : cs + 1;                                    \
         _Pragma("unroll") for (int b_ = 0; b_ < NB; b_++) {                             \
             qa[((u) + 1) & 1][b_][0] = qimg[((b_ * steps + ns_) * 2 + 0) * 64];          \
@@ -609,6 +621,7 @@ __global__ SZG_MX_BOUNDS(METRIC, STEPS, ROWS, NB) void scan_mx_kernel(SZG_MX_KER
             accL[b_] = __builtin_amdgcn_mfma_i32_16x16x64_i8(qa[(u) & 1][b_][1], bop_, accL[b_], 0, 0, 0); \
         }                                                                                \
         if (++cs == steps) {                                                             \
+            SZG_MX_TILE_END                                                              \
             finish_tile(ctile, accM, accL, norm);                                        \
             _Pragma("unroll") for (int b_ = 0; b_ < NB; b_++)                            \
                 accM[b_] = accL[b_] = v4i32{0, 0, 0, 0};                                 \
@@ -755,6 +768,17 @@ hipError_t launch_mxl(const Args &s, int grid, int block, size_t lds, hipStream_
     return hipGetLastError();
 }
 // (scan_variant's conditions, once more, for every long form: a launch that does not meet them must not reach these kernels)
+#ifdef SZG_MX_MASKED
+bool mx_long_masked_ok(const ScanMaskedArgs &s, const ScanVariant &v, int grid, int block, size_t lds)
+{
+    const ScanArgs &a = s.a;
+    return v.matrix && v.long_rows && v.masked && s.masked == 1 && scan_masked(a) && v.matrix_steps == 0 && v.nontemporal && a.tiled &&
+           (int)a.steps * 4 == a.map.r16 && scan_long_steps(a.map.r16) && a.planes == 2 && a.row_norm && a.block_lists && a.kp >= 1 &&
+           a.kp <= 64 && !a.collect && a.n_queries >= 1 && grid >= 1 && block >= 64 && block <= kLongBlockMax && block % 64 == 0 &&
+           lds <= kLongLdsCu && (v.row_lists != 0) == matrix_row_lists(a.kp, a.select) &&
+           lds == scan_lds_bytes(8, a.map, a.kp, block, v.group, a.planes, v.matrix_blocks());
+}
+#else
 bool mx_long_ok(const ScanArgs &a, const ScanVariant &v, int grid, int block, size_t lds)
 {
     return v.matrix && v.long_rows && !v.masked && v.matrix_steps == 0 && v.nontemporal && a.tiled && (int)a.steps * 4 == a.map.r16 &&
@@ -763,6 +787,7 @@ bool mx_long_ok(const ScanArgs &a, const ScanVariant &v, int grid, int block, si
            lds <= kLongLdsCu && (v.row_lists != 0) == matrix_row_lists(a.kp, a.select) &&
            lds == scan_lds_bytes(8, a.map, a.kp, block, v.group, a.planes, v.matrix_blocks());
 }
+#endif
 #elif defined(SZG_MX_MASKED) && defined(SZG_MX_SHARE)
 template <int STEPS>
 hipError_t launch_mxms_steps(const ScanMaskedArgs &s, int grid, int block, size_t lds, hipStream_t stream)
@@ -817,7 +842,35 @@ hipError_t launch_mxc_steps(const ScanArgs &a, bool wide, int grid, int block, s
 // (defined by its qualified name: it has to match its declaration in kernels.h)
 #define SZG_CAT2(a, b) a##b
 #define SZG_CAT(a, b) SZG_CAT2(a, b)
-#if defined(SZG_MX_LONG) && defined(SZG_MX_SHARE)
+#if defined(SZG_MX_LONG) && defined(SZG_MX_MASKED) && defined(SZG_MX_SHARE)
+// the masked long-row shared form of ONE metric (objects of their own, -DSZG_MX_LONG -DSZG_MX_MASKED -DSZG_MX_SHARE)
+hipError_t szg::SZG_CAT(launch_scan_mxlms_m, SZG_SCAN_METRIC)(const ScanMaskedArgs &s, const ScanVariant &v, int grid, int block,
+                                                            size_t lds, hipStream_t stream)
+{
+    const ScanArgs &a = s.a;
+    // exactly the planned form: row lists, 33 .. 64 queries, an even grid (share_map pairs its blocks), the two-block LDS
+    if (!mx_long_masked_ok(s, v, grid, block, lds) || !v.share || v.wide || !v.row_lists || a.wide == 1 || s.hi.share == 1 ||
+        a.n_queries <= kMatrixWideQueries || a.n_queries > kMatrixShareQueries || grid < 2 || grid % 2)
+        return hipErrorInvalidValue;
+    return launch_mxl<scan_mx_kernel<SZG_SCAN_METRIC, 0, true, true, 2>>(s, grid, block, lds, stream);
+}
+#elif defined(SZG_MX_LONG) && defined(SZG_MX_MASKED)
+// the masked long-row forms of ONE metric (objects of their own, -DSZG_MX_LONG -DSZG_MX_MASKED): one block with row lists
+// or serial inserts, wide
+hipError_t szg::SZG_CAT(launch_scan_mxlm_m, SZG_SCAN_METRIC)(const ScanMaskedArgs &s, const ScanVariant &v, int grid, int block,
+                                                           size_t lds, hipStream_t stream)
+{
+    const ScanArgs &a = s.a;
+    if (!mx_long_masked_ok(s, v, grid, block, lds) || v.share) return hipErrorInvalidValue;
+    if (v.wide) {
+        if (!v.row_lists || a.wide == 1 || a.n_queries <= kMatrixQueries || a.n_queries > kMatrixWideQueries) return hipErrorInvalidValue;
+        return launch_mxl<scan_mx_kernel<SZG_SCAN_METRIC, 0, true, true, 2>>(s, grid, block, lds, stream);
+    }
+    if (a.n_queries > kMaxSweepsPerLaunch) return hipErrorInvalidValue;
+    if (v.row_lists) return launch_mxl<scan_mx_kernel<SZG_SCAN_METRIC, 0, true, true>>(s, grid, block, lds, stream);
+    return launch_mxl<scan_mx_kernel<SZG_SCAN_METRIC, 0, true, false>>(s, grid, block, lds, stream);
+}
+#elif defined(SZG_MX_LONG) && defined(SZG_MX_SHARE)
 // the long-row shared form of ONE metric (objects of their own, -DSZG_MX_LONG -DSZG_MX_SHARE)
 hipError_t szg::SZG_CAT(launch_scan_mxls_m, SZG_SCAN_METRIC)(const ScanShareArgs &s, const ScanVariant &v, int grid, int block,
                                                            size_t lds, hipStream_t stream)

@@ -775,11 +775,25 @@ int szg_debug_scan_long(int dim, int quant_bits, int n_queries, int kp, int plan
                         szg_scan_long_plan *out)
 {
     if (!out) return fail(SZG_E_INVALID, "null argument");
+    szg_scan_long_masked_plan p;
+    if (const int rc = szg_debug_scan_long_masked(dim, quant_bits, n_queries, kp, planes, norms, tiled, masked, block, 0, 1, &p)) return rc;
+    *out = p.plan;
+    return SZG_OK;
+}
+
+// ... and with option sketch_masked: a launch with masks (masked = 1) takes the masked long form under sketch_masked = 1, on
+// the unmasked launch's geometry; tile_skip: it skips dead tiles (its eligibility is wave-uniform: shared_mask)
+int szg_debug_scan_long_masked(int dim, int quant_bits, int n_queries, int kp, int planes, int norms, int tiled, int masked, int block,
+                               int sketch_masked, int shared_mask, szg_scan_long_masked_plan *out_masked)
+{
+    if (!out_masked) return fail(SZG_E_INVALID, "null argument");
+    szg_scan_long_plan *out = &out_masked->plan;
+    if (const int rc = hook_option(&Options::sketch_masked, sketch_masked)) return rc;
     if (kp < 0 || n_queries < 1 || n_queries > szg::kMatrixShareQueries) return fail(SZG_E_INVALID, "kp or n_queries out of range");
     if (block != 0 && (block < 64 || block > 1024 || block % 64)) return fail(SZG_E_INVALID, "block is 0 or a multiple of 64 up to 1024");
     PlanHook h;
     const int automatic = 0;
-    if (const int rc = h.sketch_rows(dim, quant_bits, kp, false, planes, norms, tiled, masked, 0, 0, &automatic, &automatic, 0, 0))
+    if (const int rc = h.sketch_rows(dim, quant_bits, kp, false, planes, norms, tiled, masked, 0, 0, &automatic, &automatic, 0, sketch_masked))
         return rc;
     const int plain = block ? block : h.g.block;
     szg::ScanVariant v{};
@@ -790,7 +804,8 @@ int szg_debug_scan_long(int dim, int quant_bits, int n_queries, int kp, int plan
         v = szg::scan_variant(h.in);
         if (v.matrix_blocks() == blocks) break;
     }
-    memset(out, 0, sizeof(*out));
+    memset(out_masked, 0, sizeof(*out_masked));
+    out_masked->tile_skip = v.long_rows && v.masked && shared_mask ? 1 : 0;
     out->serves = v.long_rows;
     out->blocks = v.long_rows ? v.matrix_blocks() : 0;
     out->share = v.long_rows && v.share ? 1 : 0;

@@ -87,10 +87,12 @@ ScanVariant scan_variant(const ScanPlanIn &in)
             v.group = kMatrixWideQueries;
         }
     }
-    // The long-row form (kLongMinSteps .. kLongMaxSteps steps): unmasked top-k launches under the conditions above, but
+    // The long-row form (kLongMinSteps .. kLongMaxSteps steps): top-k launches under the conditions above, but
     // with up to kLongLdsCu of LDS and blocks of up to kLongBlockMax threads.  Launches of 17 .. 64 queries take its wide
-    // and shared forms where two blocks fit, every other one the long one-block form.
-    if (in.qbits == 8 && !in.masked && !in.collect && !v.deep && in.kp >= 1 && in.tiled && scan_long_steps(m.r16) &&
+    // and shared forms where two blocks fit, every other one the long one-block form.  A masked launch takes it under
+    // sketch_masked = 1 exactly where the unmasked launch of the same size does (the masked long forms: the masks need no
+    // LDS, so the fit rules are the same); under sketch_masked = 0 it keeps the one-query kernel.
+    if (in.qbits == 8 && (!in.masked || in.masked_opt == 1) && !in.collect && !v.deep && in.kp >= 1 && in.tiled && scan_long_steps(m.r16) &&
         in.planes == 2 && in.norms && in.group == 0 && in.matrix_opt != 1 &&
         in.n_queries >= (in.matrix_opt == 2 ? 1 : kMatrixMinQueries) && in.block >= kWave && in.block <= kLongBlockMax &&
         in.block % kWave == 0) {
@@ -109,7 +111,7 @@ ScanVariant scan_variant(const ScanPlanIn &in)
         const bool one = scan_lds_bytes(in.qbits, m, in.kp, in.block, kMatrixQueries, in.planes, 1) <= budget;
         if (!short_form && (wide || share || one)) {
             v.matrix = v.long_rows = 1;
-            v.masked = 0;
+            v.masked = in.masked ? 1 : 0;
             v.matrix_steps = 0;
             v.shaped = 0;
             v.ring_depth = kLongRing;

@@ -139,7 +139,8 @@ constexpr bool sketch_share_known(int64_t v) { return v == 0 || v == 1 || v == 2
 // the one-query kernel.
 constexpr bool sketch_masked_known(int64_t v) { return v == 0 || v == 1; }
 
-// The long-row form: unmasked top-k launches over rows of kLongMinSteps .. kLongMaxSteps whole
+// The long-row form: top-k launches -- unmasked ones, and under sketch_masked = 1 masked ones, on the
+// same plan -- over rows of kLongMinSteps .. kLongMaxSteps whole
 // 64-byte steps (1 024 .. 4 096 dimensions), whose image is too large for the 64 KiB the other forms keep to.  A gfx950 CU
 // has 160 KiB of LDS: a form that fits half of it runs two blocks of 256 threads per CU, as every other sweep over tiled
 // 8-bit rows does; a larger one runs ONE block of kLongBlockMax threads per CU, which stages the image once for its eight

@@ -138,11 +138,13 @@ inline ShareGeom share_geometry(int grid, int list_opt, int kp)
     const int S = szg::share_slices(G);
     return ShareGeom{G, S, sketch_list_len(list_opt, kp, S)};
 }
-// The long-row form's geometry (szg::scan_long_plan; rows of 16 .. 64 steps): an unmasked top-k launch of n_queries with
-// `blocks` column blocks, on a shard whose plain sweep takes `grid` blocks of `block` threads.  Where the form fits half a
+// The long-row form's geometry (szg::scan_long_plan; rows of 16 .. 64 steps): a top-k launch of n_queries with
+// `blocks` column blocks, on a shard whose plain sweep takes `grid` blocks of `block` threads.  masks: the launch carries
+// tombstones or filter masks -- under sketch_masked = 1 it takes the masked long form on the unmasked launch's geometry,
+// otherwise it keeps the one-query kernel and (grid, block).  Where the form fits half a
 // CU's LDS the plain geometry stays; where it takes ONE block of szg::kLongBlockMax threads per CU, that block walks the
 // tiles of two plain blocks: half the grid, half the lists per query (of the length that grid asks for).  Everything
-// else -- shorter rows, masks, a shape or option under which scan_variant does not name the long form for exactly this
+// else -- shorter rows, a shape or option under which scan_variant does not name the long form for exactly this
 // launch -- keeps (grid, block).
 struct LaunchShape {
     int grid, block;
@@ -151,7 +153,8 @@ inline LaunchShape sketch_long_shape(const SketchShape &s, int grid, int block, 
                                      int matrix_opt)
 {
     const LaunchShape plain{grid, block};
-    if (s.bits != 8 || masks || kp < 1 || kp > 64 || block != 256 || !szg::scan_long_steps(s.map.r16)) return plain;
+    if (s.bits != 8 || (masks && s.sketch_masked != 1) || kp < 1 || kp > 64 || block != 256 || !szg::scan_long_steps(s.map.r16))
+        return plain;
     const szg::LongPlan p = szg::scan_long_plan(s.map, sketch_list_len(s.sketch_list, kp, grid), blocks);
     if (p.block != szg::kLongBlockMax) return plain;
     const LaunchShape one{(grid + 1) / 2, p.block};
@@ -159,7 +162,7 @@ inline LaunchShape sketch_long_shape(const SketchShape &s, int grid, int block, 
                                                         ? szg::share_slices(szg::share_grid(one.grid))
                                                         : one.grid);
     if (szg::scan_long_plan(s.map, m, blocks).block != p.block) return plain;
-    szg::ScanPlanIn in = sketch_plan_in(s, m, false, false, n_queries, one.block);
+    szg::ScanPlanIn in = sketch_plan_in(s, m, false, masks, n_queries, one.block);
     in.matrix_opt = matrix_opt;
     const szg::ScanVariant v = szg::scan_variant(in);
     return v.long_rows && v.matrix_blocks() == blocks ? one : plain;
@@ -288,7 +291,8 @@ inline SketchLaunches sketch_batch_launches(const SketchShape &s, bool sketch, i
     // of 512, a batch of kMatrixMinQueries queries or more takes the matrix sweep whatever a launch's count (as a call with
     // wide batches does): a rest of one or two queries is a one-block long launch of one pass, not a reason to send the
     // batch back to blocks of 256.  A batch of one or two queries keeps the plain geometry and the G = 1 / G = 2 kernels.
-    if (sketch && !masks && nq >= szg::kMatrixMinQueries) {
+    // A batch with masks takes the same geometry where its launches take the masked matrix form (masks && !l.masked).
+    if (sketch && !l.masked && nq >= szg::kMatrixMinQueries) {
         const int matrix = l.matrix == 0 ? 2 : l.matrix;
         const LaunchShape g = sketch_long_shape(s, grid, block, masks, kp, std::min(nq, l.qpl), l.share || l.wide ? 2 : 1, matrix);
         if (g.block != block) {

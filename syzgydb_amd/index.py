@@ -1151,16 +1151,21 @@ def scan_share_plan(dim, quant_bits, n_queries, kp=8, planes=2, norms=True, tile
             "lds_bytes": lds.value, "batches": [int(batches[i]) for i in range(min(nb.value, cap))]}
 
 
-def scan_long_plan(dim, quant_bits, n_queries, kp=8, planes=2, norms=True, tiled=True, masked=False, block=0):
+def scan_long_plan(dim, quant_bits, n_queries, kp=8, planes=2, norms=True, tiled=True, masked=False, block=0,
+                   sketch_masked=0, shared_mask=True):
     """Host-only test hook: the matrix sweep's long-row form (rows of 16 to 64 64-byte steps: 1 024 to 4 096 dimensions)
     for ONE top-k launch of n_queries queries with lists of kp entries -- whether the launch takes it, its column blocks
-    (2: the wide or, with share, the shared form), its threads per block, grid, LDS bytes and passes over the rows."""
+    (2: the wide or, with share, the shared form), its threads per block, grid, LDS bytes and passes over the rows.
+    masked with sketch_masked = 1: the masked long form, on the unmasked launch's plan; tile_skip: it skips dead tiles
+    (shared_mask: one mask for every query or tombstones alone)."""
     L = _lib.load()
-    p = _lib.SzgScanLongPlan()
-    check(L.szg_debug_scan_long(int(dim), int(quant_bits), int(n_queries), int(kp), int(planes), int(bool(norms)),
-                                int(bool(tiled)), int(bool(masked)), int(block), ctypes.byref(p)), "szg_debug_scan_long")
+    m = _lib.SzgScanLongMaskedPlan()
+    check(L.szg_debug_scan_long_masked(int(dim), int(quant_bits), int(n_queries), int(kp), int(planes), int(bool(norms)),
+                                       int(bool(tiled)), int(bool(masked)), int(block), int(sketch_masked), int(bool(shared_mask)),
+                                       ctypes.byref(m)), "szg_debug_scan_long_masked")
+    p = m.plan
     return {"serves": bool(p.serves), "blocks": int(p.blocks), "share": bool(p.share), "block": int(p.block),
-            "grid": int(p.grid), "passes": int(p.passes), "lds_bytes": int(p.lds_bytes)}
+            "grid": int(p.grid), "passes": int(p.passes), "lds_bytes": int(p.lds_bytes), "tile_skip": bool(m.tile_skip)}
 
 
 def scan_masked_plan(dim, quant_bits, n_queries, kp=8, planes=2, norms=True, tiled=True, masked=True, scan_group=0,
