@@ -1148,11 +1148,31 @@ int szg_debug_sketch_masked(szg_index *ix, szg_sketch_masked_info *out);
  * call is split into launches of up to 32 queries where sketch_wide = 2 and a launch of 32 qualifies for the two-block
  * form, of up to 16 otherwise.  *serves / *wide / *steps_form / *lds_bytes describe the first launch (wide: it scores 32
  * queries per row read; lds_bytes: 16 b (2 dim64 + 16) with b column blocks), *passes = passes over the rows of the
- * whole call: one per launch the form serves, one per query elsewhere.
+ * whole call: one per launch the form serves, one per query elsewhere.  The hook describes the 64 KiB forms: rows whose
+ * collect image passes 64 KiB (2 048 dimensions and beyond) are answered with the one-query kernel those forms leave them
+ * to; what serves them is szg_debug_scan_long_collect's.
  */
 int szg_debug_scan_collect(int dim, int quant_bits, int n_queries, int planes, int norms, int tiled, int masked,
                            int scan_group, int sketch_matrix, int sketch_wide, int32_t *serves, int32_t *wide,
                            int32_t *passes, uint64_t *lds_bytes, int32_t *steps_form);
+
+/*
+ * Test hook, host only: the matrix sweep's long-row COLLECT form for ONE unmasked collect launch of n_queries (1 .. 32)
+ * queries over 8-bit sketch rows (radius searches through the sketch, option sketch_radius, and the collect sweep of
+ * option sketch_topk_collect), under the automatic options and the conditions of szg_debug_scan_matrix; block = the threads
+ * of the shard's plain launch (0: the default geometry's), sketch_wide = the option.  The form begins where the 64 KiB
+ * collect form of szg_debug_scan_collect ends -- 2 048 dimensions -- and keeps the image and four words per query in LDS,
+ * no lists: *lds_bytes = 16 b (2 dim + 16).  *serves = 1: the launch takes it; *blocks = its column blocks: 2 for a launch
+ * of 17 .. 32 queries where both images fit a CU's 160 KiB (through 2 496 dimensions; sketch_wide not 1) -- elsewhere such a
+ * count runs as launches of up to 16, which the hook then walks: *passes sums them, the other fields describe the first;
+ * *block = its threads -- 256 and two blocks per CU where one image fits 80 KiB (through 2 496 dimensions), else, and for two
+ * column blocks, one block of 512 per CU on half the grid -- *grid = its blocks, *passes = passes over the rows (one per
+ * launch served, one per query elsewhere); *share is 0.  Masked, three-plane, untiled, norm-less and non-8-bit launches and
+ * rows below 2 048 dimensions never take the form: *serves = 0 and the plan they keep.  Computed from the functions the
+ * launch path calls (sketch_collect_launches, sketch_collect_shape, scan_variant).
+ */
+int szg_debug_scan_long_collect(int dim, int quant_bits, int n_queries, int planes, int norms, int tiled, int masked,
+                                int block, int sketch_wide, szg_scan_long_plan *out);
 
 /*
  * Test hook, host only: the sample plan of a top-k search through the sketch (option sketch_topk_collect; csrc/sample_plan.h)
@@ -1169,6 +1189,22 @@ typedef struct szg_sample_plan {
     uint64_t tiles, sample_rows, slots, key_bytes, cap, lds_bytes;
 } szg_sample_plan;
 int szg_debug_sample_plan(uint64_t shard_rows, int k, int n_queries, int dim, int quant_bits, int planes, szg_sample_plan *out);
+/*
+ * (szg_debug_sample_plan describes the 64 KiB forms: at 2 048 dimensions and beyond it answers "not served".)  The LONG
+ * sample pass serves those rows -- 2 048 .. 4 096 dimensions, an image of up to 160 KiB -- and this hook is its plan, for a
+ * shard on cu_count compute units (0: 256): serves = 1: the long instantiation serves a launch of n_queries (1 .. 32);
+ * blocks: column blocks of 16 queries per row read, 2 for 17 .. 32 queries where both images fit 160 KiB (through 2 496
+ * dimensions); block: threads -- 256, two blocks per CU, where one image fits 80 KiB, else (and for two column blocks) 512,
+ * one per CU; grid: min(ceil(tiles / waves of a block), cu_count * blocks per CU): a block stages its image once;
+ * lds_bytes = blocks (2 KiB steps + 192); stride, tiles, slots, cap as szg_debug_sample_plan.  Rows the 64 KiB forms serve
+ * and shards the sample plan does not serve: every field 0.
+ */
+typedef struct szg_sample_long_plan {
+    int32_t serves, stride, blocks, block, grid, reserved;
+    uint64_t tiles, slots, cap, lds_bytes;
+} szg_sample_long_plan;
+int szg_debug_sample_long_plan(uint64_t shard_rows, int k, int n_queries, int dim, int quant_bits, int planes, int cu_count,
+                               szg_sample_long_plan *out);
 
 /*
  * Test hook, host only: *fits = the sketch sweep's one-launch short-list merge serves n_lists block lists of m entries

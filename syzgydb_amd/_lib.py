@@ -77,6 +77,8 @@ EXPORTS = [
     "szg_index_sketch_topk_stats", "szg_debug_sample_plan",
     # a sketch batch's queries prepared on the card (option query_prep): the counters, the two-sided hook, the batch rule
     "szg_index_query_prep_stats", "szg_debug_query_prep", "szg_debug_query_prep_serves",
+    # the long-row collect form and the long sample pass (2 048 .. 4 096 dimensions): the plan hooks
+    "szg_debug_scan_long_collect", "szg_debug_sample_long_plan",
 ]
 # szg_cert_record.pass / .keys, szg_cert_entry.flags
 SZG_CERT_TOPK, SZG_CERT_SKETCH, SZG_CERT_ESCALATION, SZG_CERT_RADIUS_SINGLE, SZG_CERT_RADIUS_SHARED = range(5)
@@ -150,6 +152,11 @@ class SzgQueryPrepStats(ctypes.Structure):
 class SzgSamplePlan(ctypes.Structure):
     _fields_ = ([(name, ctypes.c_int32) for name in ("serves", "stride", "blocks", "reserved")] +
                 [(name, ctypes.c_uint64) for name in ("tiles", "sample_rows", "slots", "key_bytes", "cap", "lds_bytes")])
+
+
+class SzgSampleLongPlan(ctypes.Structure):
+    _fields_ = ([(name, ctypes.c_int32) for name in ("serves", "stride", "blocks", "block", "grid", "reserved")] +
+                [(name, ctypes.c_uint64) for name in ("tiles", "slots", "cap", "lds_bytes")])
 
 
 class SzgScanPlan(ctypes.Structure):
@@ -490,6 +497,11 @@ def load():
         L.szg_index_sketch_topk_stats.argtypes = [vp, ctypes.POINTER(SzgSketchTopkStats)]
         L.szg_debug_sample_plan.restype = ctypes.c_int
         L.szg_debug_sample_plan.argtypes = [ctypes.c_uint64] + [ctypes.c_int] * 5 + [ctypes.POINTER(SzgSamplePlan)]
+    if hasattr(L, "szg_debug_scan_long_collect"):
+        L.szg_debug_scan_long_collect.restype = ctypes.c_int
+        L.szg_debug_scan_long_collect.argtypes = [ctypes.c_int] * 9 + [ctypes.POINTER(SzgScanLongPlan)]
+        L.szg_debug_sample_long_plan.restype = ctypes.c_int
+        L.szg_debug_sample_long_plan.argtypes = [ctypes.c_uint64] + [ctypes.c_int] * 6 + [ctypes.POINTER(SzgSampleLongPlan)]
     if hasattr(L, "szg_index_query_prep_stats"):   # (an older build for an A/B run has no such option)
         L.szg_index_query_prep_stats.restype = ctypes.c_int
         L.szg_index_query_prep_stats.argtypes = [vp, ctypes.POINTER(SzgQueryPrepStats)]

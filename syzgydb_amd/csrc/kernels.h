@@ -4,6 +4,7 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <atomic>
 
 #include "scan_plan.h"
 
@@ -215,6 +216,9 @@ SZG_DECL_SCAN_V(launch_scan_mxc_m0) SZG_DECL_SCAN_V(launch_scan_mxc_m1)
 // ... and with -DSZG_MX_LONG its long-row form (mxl; ScanVariant::long_rows): rows of 16 .. 64 steps, up to 160 KiB of LDS,
 // blocks of up to kLongBlockMax threads -- the one-block kernels (row lists, serial inserts) and the wide one
 SZG_DECL_SCAN_V(launch_scan_mxl_m0) SZG_DECL_SCAN_V(launch_scan_mxl_m1)
+// ... and with -DSZG_MX_LONG -DSZG_MX_COLLECT the long-row collect form (mxlc): unmasked collect launches over rows of 32 .. 64
+// steps, one column block or -- on the block of kLongBlockMax, 17 .. kMatrixWideQueries queries -- two
+SZG_DECL_SCAN_V(launch_scan_mxlc_m0) SZG_DECL_SCAN_V(launch_scan_mxlc_m1)
 #undef SZG_DECL_G8
 #undef SZG_DECL_SCAN_V
 // The matrix sweep's shared form (kernels_scan_mx.hip with -DSZG_MX_SHARE: objects of their own): ONE launch of 33 ..
@@ -290,6 +294,26 @@ struct SampleSelectArgs {
     uint32_t *out;
 };
 hipError_t launch_sample_select(const SampleSelectArgs &s, int n_queries, hipStream_t stream);
+
+// The launch of a long-row kernel (kernels_scan_mx.hip -DSZG_MX_LONG, kernels_sample_mx.hip's long instantiation): its
+// dynamic LDS may pass the 64 KiB a kernel gets unasked -- the limit of each instantiation is raised once per device, to
+// the most a long form may ask for (kLongLdsCu), and not on the launch path again.
+template <auto Kern, typename Args>
+hipError_t launch_mxl(const Args &s, int grid, int block, size_t lds, hipStream_t stream)
+{
+    static std::atomic<uint64_t> raised{0};  // bit d: done on device d
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return e;
+    const uint64_t bit = 1ull << (dev & 63);
+    if (dev > 63 || !(raised.load(std::memory_order_acquire) & bit)) {
+        e = hipFuncSetAttribute(reinterpret_cast<const void *>(Kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLongLdsCu);
+        if (e != hipSuccess) return e;
+        raised.fetch_or(bit, std::memory_order_release);
+    }
+    hipLaunchKernelGGL(Kern, dim3(grid), dim3(block), lds, stream, s);
+    return hipGetLastError();
+}
 
 // ---- shared (multi-query) sweeps (mq_device.h, kernels_mq*.hip): every row width, cosine and Euclidean ----------
 // queries per shared sweep: 48 (3 blocks of 16) for the int8 sweeps (4- and 8-bit rows), whose LDS images are 2-4

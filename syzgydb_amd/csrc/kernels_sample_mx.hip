@@ -24,6 +24,15 @@
 //   sample_mx_kernel NB = 1: 70 (cosine) / 74 (Euclid) VGPRs, 63 SGPRs, LDS 2 KiB per step + 192 bytes
 //   (768 dimensions: 24.2 KiB); NB = 2: 102 / 106 VGPRs, 72 SGPRs, LDS 4 KiB per step + 384 bytes (48.4 KiB); launch bound
 //   256 threads, two blocks per CU.  sample_select_kernel: 10 VGPRs, 256 threads, 1 KiB of histogram and four words of LDS.
+//
+// The LONG instantiation (LONG; sample_shape, scan_plan.h): rows of 32 .. 64 steps (2 048 .. 4 096
+// dimensions), whose image passes the 64 KiB a kernel gets unasked.  Operands, loads (four steps at a time), masks and the
+// any-steps key chain are the ones above -- a sampled pair gets the key the long collect sweep gives it -- and the image
+// stays whole in LDS, of which the launch may take the CU's 160 KiB: blocks of 256, two per CU, where one image fits 80 KiB
+// (through 2 496 dimensions), else ONE block of 512 per CU whose eight waves stage the image once; two column blocks where
+// both images fit 160 KiB (through 2 496 dimensions), on the block of 512.  A block stages 64 .. 156 KiB before its first
+// tile, so the grid is the blocks the card holds at once (sample_grid) and each walks its share of the sample tiles.
+//   LONG, bound 512 threads (256 registers), NB = 1: 70 / 74 VGPRs (cosine / Euclid); NB = 2: 102 / 106; no scratch.
 #include "kernels.h"
 #include "mask_tiles.h"
 
@@ -36,9 +45,10 @@ using u32x4 = __attribute__((ext_vector_type(4))) uint32_t;
 
 constexpr uint32_t kNoKey = 0xFFFFFFFFu;
 
-template <int METRIC, bool SHAPED, int NB>
-__global__ __launch_bounds__(256, 2) void sample_mx_kernel(const SampleArgs s)
+template <int METRIC, bool SHAPED, int NB, bool LONG = false>
+__global__ __launch_bounds__(LONG ? kLongBlockMax : 256, LONG ? 1 : 2) void sample_mx_kernel(const SampleArgs s)
 {
+    static_assert(!(LONG && SHAPED), "the long instantiation: any-steps rows");
     const ScanArgs &a = s.a;
     constexpr int kQ = kMatrixQueries * NB;  // queries of the launch's one group
     constexpr int NS = 4 * NB;               // slots (queries) per lane
@@ -201,9 +211,16 @@ __global__ __launch_bounds__(256) void sample_select_kernel(const SampleSelectAr
     if (tid == 0) s.out[2 * q] = prefix;
 }
 
+// (the long instantiation: its dynamic LDS passes the 64 KiB a kernel gets unasked -- kernels.h's launch_mxl raises the limit)
 template <int METRIC>
-hipError_t launch_sample_metric(const SampleArgs &s, bool shaped, int nb, int grid, int block, size_t lds, hipStream_t stream)
+hipError_t launch_sample_metric(const SampleArgs &s, bool shaped, bool long_form, int nb, int grid, int block, size_t lds,
+                                hipStream_t stream)
 {
+    if (long_form) {
+        if (shaped) return hipErrorInvalidValue;
+        if (nb == 2) return launch_mxl<sample_mx_kernel<METRIC, false, 2, true>>(s, grid, block, lds, stream);
+        return launch_mxl<sample_mx_kernel<METRIC, false, 1, true>>(s, grid, block, lds, stream);
+    }
     if (nb == 2) {
         if (shaped) hipLaunchKernelGGL((sample_mx_kernel<METRIC, true, 2>), dim3(grid), dim3(block), lds, stream, s);
         else hipLaunchKernelGGL((sample_mx_kernel<METRIC, false, 2>), dim3(grid), dim3(block), lds, stream, s);
@@ -218,7 +235,7 @@ hipError_t launch_sample_metric(const SampleArgs &s, bool shaped, int nb, int gr
 
 size_t sample_mx_lds_bytes(uint32_t steps, int nb)
 {
-    return (size_t)nb * steps * 2 * 64 * 16 + (size_t)3 * kMatrixQueries * nb * sizeof(float);
+    return sample_lds_bytes(steps, nb);
 }
 
 hipError_t launch_sample_mx(int metric, const SampleArgs &s, int nb, int grid, int block, hipStream_t stream)
@@ -227,16 +244,18 @@ hipError_t launch_sample_mx(int metric, const SampleArgs &s, int nb, int grid, i
     // (what the kernel takes for granted: a launch that does not meet it must not reach it)
     if ((nb != 1 && nb != 2) || !a.tiled || a.steps == 0 || (int)a.steps * 4 != a.map.r16 || a.planes != 2 || !a.row_norm ||
         !a.rows || !a.query || !s.keys || a.n_rows == 0 || a.n_queries < 1 || a.n_queries > kMatrixQueries * nb ||
-        block < 64 || block > 256 || block % 64 || grid < 1 || s.stride < 1)
+        block < 64 || block % 64 || grid < 1 || s.stride < 1)
         return hipErrorInvalidValue;
+    // (the form's block: up to 256 threads within 64 KiB, exactly the long form's beyond)
+    const SampleShape sh = sample_shape(a.steps, nb);
+    if (sh.block == 0 || (sh.long_form ? block != sh.block : block > 256)) return hipErrorInvalidValue;
     const uint64_t n_tiles = ((uint64_t)a.n_rows + 15) / 16;
     if (s.tiles != (n_tiles + s.stride - 1) / s.stride || (uint64_t)s.slots != (uint64_t)s.tiles * 16) return hipErrorInvalidValue;
-    const size_t lds = sample_mx_lds_bytes(a.steps, nb);
-    if (lds > 64u * 1024u) return hipErrorInvalidValue;
+    const size_t lds = sh.lds;
     // the conversion the collect sweep of these rows takes (kernels_scan_mx.hip: the shaped kernels combine as integers)
     const bool shaped = matrix_steps_form((int)a.steps) != 0;
-    return metric == kCosine ? launch_sample_metric<kCosine>(s, shaped, nb, grid, block, lds, stream)
-                             : launch_sample_metric<kEuclidean>(s, shaped, nb, grid, block, lds, stream);
+    return metric == kCosine ? launch_sample_metric<kCosine>(s, shaped, sh.long_form, nb, grid, block, lds, stream)
+                             : launch_sample_metric<kEuclidean>(s, shaped, sh.long_form, nb, grid, block, lds, stream);
 }
 
 hipError_t launch_sample_select(const SampleSelectArgs &s, int n_queries, hipStream_t stream)

@@ -1017,6 +1017,7 @@ hipError_t launch_scan_qmcm(const ScanArgs &a, int grid, int block, hipStream_t 
     }
     if constexpr (QBITS == 8 && COLLECT && !MASKED) {
         // ... and its collect form (objects of their own: the top-k kernels' code does not change with it)
+        if (v.matrix && v.long_rows) return METRIC == kCosine ? launch_scan_mxlc_m1(a, v, grid, block, lds, stream) : launch_scan_mxlc_m0(a, v, grid, block, lds, stream);
         if (v.matrix) return METRIC == kCosine ? launch_scan_mxc_m1(a, v, grid, block, lds, stream) : launch_scan_mxc_m0(a, v, grid, block, lds, stream);
     }
     if (v.group != 1) return hipErrorInvalidValue;

@@ -169,8 +169,25 @@ constexpr int mx_ring()
 // the stream's step count whatever the tiles' step count (30: no multiple of the ring; odd counts).  The per-tile hooks are
 // the masked any-steps kernel's: the slot's 16-bit allow slice beside the norm at a tile's first step (per-query masks),
 // the walk's slice for finish_tile at its last.  Keys: the same operations as the unmasked long form's.
-#if defined(SZG_MX_LONG) && defined(SZG_MX_COLLECT)
-#error "the long-row forms: top-k (SZG_MX_LONG, with SZG_MX_SHARE and / or SZG_MX_MASKED)"
+// With -DSZG_MX_LONG -DSZG_MX_COLLECT the file builds the LONG-ROW COLLECT form (objects of their own):
+// unmasked collect launches over rows of 32 .. 64 steps (2 048 .. 4 096 dimensions), where the 64 KiB collect form ends.
+// The stream is the long form's as it stands -- the ring of kLongRing loads walked across tile ends, the A operands one step
+// ahead in the double buffer, two matrix instructions per step and column block -- and the finish the collect form's: the
+// float pre-filter against the threshold, the exact test on the ordered key, one ballot per slot, the slice's first hit lane
+// claiming the popcount on collect_count, entries beyond collect_cap counted and not written.
+//  * LDS: the image and four words per query (qscale, qconst, qnorm2, the threshold's ordered key), no lists:
+//    16 NB (2 dim + 16) bytes.  One column block fits half a CU through 2 496 dimensions (80 128 bytes: blocks of 256, two
+//    per CU, the plain grid); beyond, up to 131 328 bytes at 4 096 dimensions, ONE block of 512 per CU on half the grid.
+//    Two column blocks (17 .. 32 queries per row read) fit the CU through 2 496 dimensions (160 256 bytes) and run on the
+//    block of 512 only, under the top-k long form's rule (scan_variant).
+//  * the keys: the any-steps chain again, so the argument above carries over word for word -- the collect form adds no
+//    arithmetic in front of the key, only the comparison of its ordered bits with the threshold's behind it.  A (query, row)
+//    pair gets the bits of the long top-k form and, at 16 .. 31 steps, of the 64 KiB collect form.
+// Resources (hipcc --offload-arch=gfx950 -O3, VFLAGS='-DSZG_MX_LONG -DSZG_MX_COLLECT' scripts/kernel_resources.sh scan mx 1,
+// and `... scan mx 0` for Euclid; bound 512 threads, 256 registers): no scratch.  NB = 1: 130 / 134 VGPRs (cosine / Euclid);
+// NB = 2: 202 / 210.
+#if defined(SZG_MX_LONG) && defined(SZG_MX_COLLECT) && (defined(SZG_MX_SHARE) || defined(SZG_MX_MASKED))
+#error "the long-row collect form: unmasked, never shared (SZG_MX_LONG SZG_MX_COLLECT alone)"
 #endif
 #if defined(SZG_MX_MASKED)
 #define SZG_MX_KERNEL_ARGS const ScanMaskedArgs ma
@@ -197,7 +214,7 @@ template <int METRIC, int STEPS, bool NT, bool ROWS, int NB = 1, bool COLLECT = 
 __global__ SZG_MX_BOUNDS(METRIC, STEPS, ROWS, NB) void scan_mx_kernel(SZG_MX_KERNEL_ARGS)
 {
 #ifdef SZG_MX_LONG
-    static_assert(STEPS == 0 && !COLLECT, "the long-row forms: any-steps top-k kernels");
+    static_assert(STEPS == 0, "the long-row forms: any-steps kernels");
 #endif
 #ifdef SZG_MX_MASKED
     static_assert(!COLLECT, "the masked forms: top-k");
@@ -749,24 +766,7 @@ __global__ SZG_MX_BOUNDS(METRIC, STEPS, ROWS, NB) void scan_mx_kernel(SZG_MX_KER
 }
 
 #if defined(SZG_MX_LONG)
-// a long-row kernel: its dynamic LDS may pass the 64 KiB a kernel gets unasked -- the limit of each instantiation is
-// raised once per device, to the most a long form may ask for, and not on the launch path again
-template <auto Kern, typename Args>
-hipError_t launch_mxl(const Args &s, int grid, int block, size_t lds, hipStream_t stream)
-{
-    static std::atomic<uint64_t> raised{0};  // bit d: done on device d
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    const uint64_t bit = 1ull << (dev & 63);
-    if (dev > 63 || !(raised.load(std::memory_order_acquire) & bit)) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(Kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLongLdsCu);
-        if (e != hipSuccess) return e;
-        raised.fetch_or(bit, std::memory_order_release);
-    }
-    hipLaunchKernelGGL(Kern, dim3(grid), dim3(block), lds, stream, s);
-    return hipGetLastError();
-}
+// (the long-row kernels are launched through kernels.h's launch_mxl, which raises their dynamic-LDS limit)
 // (scan_variant's conditions, once more, for every long form: a launch that does not meet them must not reach these kernels)
 #ifdef SZG_MX_MASKED
 bool mx_long_masked_ok(const ScanMaskedArgs &s, const ScanVariant &v, int grid, int block, size_t lds)
@@ -777,6 +777,15 @@ bool mx_long_masked_ok(const ScanMaskedArgs &s, const ScanVariant &v, int grid, 
            a.kp <= 64 && !a.collect && a.n_queries >= 1 && grid >= 1 && block >= 64 && block <= kLongBlockMax && block % 64 == 0 &&
            lds <= kLongLdsCu && (v.row_lists != 0) == matrix_row_lists(a.kp, a.select) &&
            lds == scan_lds_bytes(8, a.map, a.kp, block, v.group, a.planes, v.matrix_blocks());
+}
+#elif defined(SZG_MX_COLLECT)
+bool mx_long_collect_ok(const ScanArgs &a, const ScanVariant &v, int grid, int block, size_t lds)
+{
+    return v.matrix && v.long_rows && !v.masked && !v.share && !v.row_lists && v.matrix_steps == 0 && v.nontemporal && a.tiled &&
+           (int)a.steps * 4 == a.map.r16 && scan_long_steps(a.map.r16) && a.planes == 2 && a.row_norm && a.collect && a.collect_buf &&
+           a.collect_count && !scan_masked(a) && a.n_queries >= 1 && grid >= 1 && block >= 64 && block <= kLongBlockMax &&
+           block % 64 == 0 && lds > 64u * 1024u && lds <= (block > 256 ? kLongLdsCu : kLongLdsHalf) &&
+           lds == scan_lds_bytes(8, a.map, 0, block, v.group, a.planes, v.matrix_blocks());
 }
 #else
 bool mx_long_ok(const ScanArgs &a, const ScanVariant &v, int grid, int block, size_t lds)
@@ -842,7 +851,22 @@ hipError_t launch_mxc_steps(const ScanArgs &a, bool wide, int grid, int block, s
 // (defined by its qualified name: it has to match its declaration in kernels.h)
 #define SZG_CAT2(a, b) a##b
 #define SZG_CAT(a, b) SZG_CAT2(a, b)
-#if defined(SZG_MX_LONG) && defined(SZG_MX_MASKED) && defined(SZG_MX_SHARE)
+#if defined(SZG_MX_LONG) && defined(SZG_MX_COLLECT)
+// the long-row collect form of ONE metric (objects of their own, -DSZG_MX_LONG -DSZG_MX_COLLECT): one block or wide
+hipError_t szg::SZG_CAT(launch_scan_mxlc_m, SZG_SCAN_METRIC)(const ScanArgs &a, const ScanVariant &v, int grid, int block,
+                                                           size_t lds, hipStream_t stream)
+{
+    if (!mx_long_collect_ok(a, v, grid, block, lds)) return hipErrorInvalidValue;
+    // the wide form: the block of 512, 17 .. kMatrixWideQueries queries (the constants' and thresholds' arrays hold that
+    // many); every other launch holds at most kMaxSweepsPerLaunch
+    if (v.wide) {
+        if (a.wide == 1 || block <= 256 || a.n_queries <= kMatrixQueries || a.n_queries > kMatrixWideQueries) return hipErrorInvalidValue;
+        return launch_mxl<scan_mx_kernel<SZG_SCAN_METRIC, 0, true, true, 2, true>>(a, grid, block, lds, stream);
+    }
+    if (a.n_queries > kMaxSweepsPerLaunch) return hipErrorInvalidValue;
+    return launch_mxl<scan_mx_kernel<SZG_SCAN_METRIC, 0, true, true, 1, true>>(a, grid, block, lds, stream);
+}
+#elif defined(SZG_MX_LONG) && defined(SZG_MX_MASKED) && defined(SZG_MX_SHARE)
 // the masked long-row shared form of ONE metric (objects of their own, -DSZG_MX_LONG -DSZG_MX_MASKED -DSZG_MX_SHARE)
 hipError_t szg::SZG_CAT(launch_scan_mxlms_m, SZG_SCAN_METRIC)(const ScanMaskedArgs &s, const ScanVariant &v, int grid, int block,
                                                             size_t lds, hipStream_t stream)

@@ -860,6 +860,8 @@ int szg_debug_sketch_masked(szg_index *ix, szg_sketch_masked_info *out)
 }
 
 // the matrix sweep's collect form for a collect call of n_queries queries with one sweep each (launches of 32: sketch_wide = 2)
+// -- the 64 KiB forms: where scan_variant names the long collect form (szg_debug_scan_long_collect's subject), the hook
+// answers for the one-query kernel that the 64 KiB forms leave such rows to
 int szg_debug_scan_collect(int dim, int quant_bits, int n_queries, int planes, int norms, int tiled, int masked, int scan_group,
                            int sketch_matrix, int sketch_wide, int32_t *serves, int32_t *wide, int32_t *passes, uint64_t *lds_bytes, int32_t *steps_form)
 {
@@ -869,11 +871,47 @@ int szg_debug_scan_collect(int dim, int quant_bits, int n_queries, int planes, i
     if (const int rc = h.sketch_rows(dim, quant_bits, 0, true, planes, norms, tiled, masked, scan_group, sketch_matrix, nullptr, &sketch_wide))
         return rc;
     h.walk(n_queries, sketch_wide == 2 ? h.wide_launches() : szg::kMaxSweepsPerLaunch);
+    if (h.first.long_rows) {
+        h.in.matrix_opt = 1;
+        h.walk(n_queries, szg::kMaxSweepsPerLaunch);
+    }
     *serves = h.first.matrix;
     *wide = h.first.wide;
     *steps_form = h.first.matrix_steps;
     *lds_bytes = h.lds_bytes;
     *passes = h.passes;
+    return SZG_OK;
+}
+
+// the matrix sweep's long-row collect form for ONE collect launch of n_queries over the sketch rows of (dim, quant_bits),
+// with the geometry the launch path gives it (sketch_collect_shape, as collect_sweeps asks it): a launch of 17 .. 32 queries
+// is what a call with wide batches forms where sketch_wide_serves says the two-block form serves; where it does not, the
+// hook answers for the launches of up to 16 that such a call forms instead (their passes summed, the first one described)
+int szg_debug_scan_long_collect(int dim, int quant_bits, int n_queries, int planes, int norms, int tiled, int masked, int block,
+                                int sketch_wide, szg_scan_long_plan *out)
+{
+    if (!out) return fail(SZG_E_INVALID, "null argument");
+    if (n_queries < 1 || n_queries > szg::kMatrixWideQueries) return fail(SZG_E_INVALID, "n_queries out of range");
+    if (block != 0 && (block < 64 || block > 1024 || block % 64)) return fail(SZG_E_INVALID, "block is 0 or a multiple of 64 up to 1024");
+    PlanHook h;
+    if (const int rc = h.sketch_rows(dim, quant_bits, 0, true, planes, norms, tiled, masked, 0, 0, nullptr, &sketch_wide)) return rc;
+    const int plain = block ? block : h.g.block;
+    const bool ok = !masked && norms != 0;
+    const bool wide32 = n_queries > szg::kMatrixQueries &&
+                        sketch_collect_launches(h.s, h.g.grid, plain, masked != 0, 2, ok, n_queries, szg::kMaxSweepsPerLaunch).wide32;
+    const int qpl = wide32 ? szg::kMatrixWideQueries : szg::kMaxSweepsPerLaunch;
+    // (a launch of more than 16 belongs to a call with wide batches: its launches take the matrix sweep whatever their count)
+    const CollectShape cs = sketch_collect_shape(h.s, h.g.grid, plain, ok, n_queries > szg::kMatrixQueries ? 2 : 0, std::min(qpl, n_queries));
+    h.in = sketch_plan_in(h.s, 0, true, masked != 0, std::min(qpl, n_queries), cs.block);
+    h.in.matrix_opt = cs.matrix;
+    h.walk(n_queries, qpl);
+    memset(out, 0, sizeof(*out));
+    out->serves = h.first.long_rows;
+    out->blocks = h.first.long_rows ? h.first.matrix_blocks() : 0;
+    out->block = cs.block;
+    out->grid = cs.grid;
+    out->lds_bytes = h.lds_bytes;
+    out->passes = h.passes;
     return SZG_OK;
 }
 

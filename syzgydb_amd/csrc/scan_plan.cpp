@@ -92,23 +92,29 @@ ScanVariant scan_variant(const ScanPlanIn &in)
     // and shared forms where two blocks fit, every other one the long one-block form.  A masked launch takes it under
     // sketch_masked = 1 exactly where the unmasked launch of the same size does (the masked long forms: the masks need no
     // LDS, so the fit rules are the same); under sketch_masked = 0 it keeps the one-query kernel.
-    if (in.qbits == 8 && (!in.masked || in.masked_opt == 1) && !in.collect && !v.deep && in.kp >= 1 && in.tiled && scan_long_steps(m.r16) &&
+    // Unmasked collect launches take its collect form by the same rules with no lists (list_kp = 0:
+    // neither kp nor the selection matter): from where the 64 KiB one-block collect form ends (2 048 dimensions), wide on
+    // the block of 512 where two images and constants fit kLongLdsCu (through 2 496 dimensions), never shared.  A masked
+    // collect launch keeps the one-query kernel.
+    if (in.qbits == 8 && (in.collect ? !in.masked : (!in.masked || in.masked_opt == 1)) && !v.deep && (in.collect || in.kp >= 1) &&
+        in.tiled && scan_long_steps(m.r16) &&
         in.planes == 2 && in.norms && in.group == 0 && in.matrix_opt != 1 &&
         in.n_queries >= (in.matrix_opt == 2 ? 1 : kMatrixMinQueries) && in.block >= kWave && in.block <= kLongBlockMax &&
         in.block % kWave == 0) {
-        const bool rows = matrix_row_lists(in.kp, in.select_opt);
+        const bool rows = !in.collect && matrix_row_lists(in.kp, in.select_opt);
         // Measured ("long rows"): at 1 024 dimensions the two-block forms on blocks of 256 were slower per
         // query than the one-block form of 64 KiB.  Where that form serves the shape at the default block, every launch
         // keeps today's plan: the long forms begin where it ends (1 920 dimensions with lists of 8).
-        const bool short_form = scan_lds_bytes(in.qbits, m, in.kp, 256, kMatrixQueries, in.planes, 1) <= kLdsMax;
+        const bool short_form = scan_lds_bytes(in.qbits, m, list_kp, 256, kMatrixQueries, in.planes, 1) <= kLdsMax;
         // (two waves per SIMD: blocks of up to 256 threads come two to a CU and get half its LDS each -- which two column
         // blocks of rows beyond the short form, 128 KiB and more, never fit: the wide and shared forms take the block of 512)
         const size_t budget = in.block > 256 ? kLongLdsCu : kLongLdsHalf;
-        const bool two = rows && in.wide_opt != 1 && in.block > 256 &&
-                         scan_lds_bytes(in.qbits, m, in.kp, in.block, kMatrixWideQueries, in.planes, 2) <= kLongLdsCu;
+        const bool two = (rows || in.collect) && in.wide_opt != 1 && in.block > 256 &&
+                         scan_lds_bytes(in.qbits, m, list_kp, in.block, kMatrixWideQueries, in.planes, 2) <= kLongLdsCu;
         const bool wide = two && in.n_queries > kMatrixQueries && in.n_queries <= kMatrixWideQueries;
-        const bool share = two && in.share_opt != 1 && in.n_queries > kMatrixWideQueries && in.n_queries <= kMatrixShareQueries;
-        const bool one = scan_lds_bytes(in.qbits, m, in.kp, in.block, kMatrixQueries, in.planes, 1) <= budget;
+        const bool share = two && !in.collect && in.share_opt != 1 && in.n_queries > kMatrixWideQueries &&
+                           in.n_queries <= kMatrixShareQueries;
+        const bool one = scan_lds_bytes(in.qbits, m, list_kp, in.block, kMatrixQueries, in.planes, 1) <= budget;
         if (!short_form && (wide || share || one)) {
             v.matrix = v.long_rows = 1;
             v.masked = in.masked ? 1 : 0;
@@ -126,7 +132,8 @@ ScanVariant scan_variant(const ScanPlanIn &in)
 
 LongPlan scan_long_plan(const RowMap &m, int kp, int blocks)
 {
-    if (!scan_long_steps(m.r16) || kp < 1 || kp > 64 || (blocks != 1 && blocks != 2)) return LongPlan{0, 0, 0};
+    // (kp = 0: the collect form -- no lists, a fourth word per query)
+    if (!scan_long_steps(m.r16) || kp < 0 || kp > 64 || (blocks != 1 && blocks != 2)) return LongPlan{0, 0, 0};
     // (rows that the one-block form of 64 KiB serves keep it: scan_variant)
     const size_t half = scan_lds_bytes(8, m, kp, 256, kMatrixQueries, 2, 1);
     if (half <= kLdsMax) return LongPlan{0, 0, 0};

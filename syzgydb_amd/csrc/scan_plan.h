@@ -99,7 +99,8 @@ struct ScanVariant {
                       // launch has tombstones or filter masks and takes the matrix sweep all the same
     int long_rows = 0;  // the matrix sweep's long-row form (rows of kLongMinSteps .. kLongMaxSteps steps; objects of their own,
                       // kernels_scan_mx.hip -DSZG_MX_LONG): the image may take the CU's whole LDS, blocks of up to kLongBlockMax
-                      // threads; set together with matrix / wide / share
+                      // threads; set together with matrix / wide / share.  A collect launch's long form (no lists, never
+                      // shared) has objects of its own again (-DSZG_MX_LONG -DSZG_MX_COLLECT)
 };
 // What "automatic" (scan_group = 0) asks for, where a launch qualifies.
 constexpr int kScanGroupAuto = 4;
@@ -157,11 +158,61 @@ constexpr bool scan_long_steps(int r16) { return r16 % 4 == 0 && r16 / 4 >= kLon
 // kLongLdsHalf; a larger one, and every two-block form, ONE block of kLongBlockMax where they fit kLongLdsCu (the lists
 // grow with the waves); else, and for rows that the one-block form of 64 KiB serves, block = 0: the form does not serve.
 // The launch path (sketch_plan.h) and the plan hooks both ask here.
+// kp = 0 asks for the collect form (unmasked collect launches, no lists, a fourth word per query):
+// 16 blocks (2 dim + 16) bytes -- blocks of 256 at 2 048 .. 2 496 dimensions, the block of kLongBlockMax beyond and for
+// two column blocks (which fit through 2 496 dimensions).
 struct LongPlan {
     int block, per_cu;
     size_t lds;
 };
 LongPlan scan_long_plan(const RowMap &m, int kp, int blocks);
+
+// The sample pass of a top-k search of large k through the sketch (kernels_sample_mx.hip): LDS of a launch of nb column
+// blocks over rows of `steps` 64-byte steps -- per block an image of 2 KiB per step and three words per query -- and the
+// form that serves it.  Within 64 KiB: blocks of up to 256 threads, as ever.  Rows whose one-block image passes 64 KiB
+// (32 steps and more) take the LONG instantiation by the long sweep's rule: blocks of 256, two per CU, where one image fits
+// kLongLdsHalf, else ONE block of kLongBlockMax per CU; two column blocks where they fit kLongLdsCu, on that block.  block = 0:
+// no form serves (two blocks of 16 .. 31 steps, which pass 64 KiB on rows the 64 KiB forms keep; two of 40 steps and more).
+constexpr size_t sample_lds_bytes(uint32_t steps, int nb)
+{
+    return (size_t)nb * steps * 2 * 64 * 16 + (size_t)3 * kMatrixQueries * nb * sizeof(float);
+}
+struct SampleShape {
+    int block, per_cu;
+    bool long_form;
+    size_t lds;
+};
+constexpr SampleShape sample_shape(uint32_t steps, int nb)
+{
+    const size_t lds = sample_lds_bytes(steps, nb), kShort = 64u * 1024u;
+    if (nb != 1 && nb != 2) return SampleShape{0, 0, false, lds};
+    if (sample_lds_bytes(steps, 1) <= kShort) return lds <= kShort ? SampleShape{256, 2, false, lds} : SampleShape{0, 0, false, lds};
+    if (steps > (uint32_t)kLongMaxSteps) return SampleShape{0, 0, false, lds};
+    if (nb == 1 && lds <= kLongLdsHalf) return SampleShape{256, 2, true, lds};
+    if (lds <= kLongLdsCu) return SampleShape{kLongBlockMax, 1, true, lds};
+    return SampleShape{0, 0, false, lds};
+}
+// its grid over `tiles` sample tiles, one per wave and turn: within 64 KiB up to eight blocks of four waves per CU, as ever;
+// a long block stages its image once, so the grid is the blocks the card holds at once
+constexpr uint64_t sample_grid(uint64_t tiles, int cu_count, const SampleShape &sh)
+{
+    const uint64_t waves = (uint64_t)(sh.block > 0 ? sh.block : 256) / 64;
+    const uint64_t need = (tiles + waves - 1) / waves, most = (uint64_t)cu_count * (sh.long_form ? (uint64_t)sh.per_cu : 8u);
+    const uint64_t g = need < most ? need : most;
+    return g < 1 ? 1 : g;
+}
+// the fit rule at its edges: 31 | 32 steps (64 KiB), 39 | 40 (half a CU; two blocks against the whole), 64 | 65 (the longest rows)
+static_assert(sample_lds_bytes(32, 1) == 65728 && sample_lds_bytes(39, 2) == 160128, "2 KiB per step and block + 192 bytes");
+static_assert(sample_shape(31, 1).block == 256 && !sample_shape(31, 1).long_form && sample_shape(31, 2).block == 0, "64 KiB forms");
+static_assert(sample_shape(32, 1).block == 256 && sample_shape(32, 1).long_form && sample_shape(32, 1).per_cu == 2, "32 steps");
+static_assert(sample_shape(39, 1).block == 256 && sample_shape(40, 1).block == kLongBlockMax && sample_shape(40, 1).per_cu == 1, "80 KiB");
+static_assert(sample_shape(32, 2).block == kLongBlockMax && sample_shape(39, 2).block == kLongBlockMax && sample_shape(40, 2).block == 0,
+              "two blocks: through 39 steps, on the block of 512");
+static_assert(sample_shape(64, 1).block == kLongBlockMax && sample_shape(65, 1).block == 0 && sample_shape(32, 3).block == 0, "the ends");
+// (256 CUs; a long block of 512: one per CU, eight waves -- 1 000 tiles are 125 blocks, 10 000 the card's 256)
+static_assert(sample_grid(1000, 256, sample_shape(64, 1)) == 125 && sample_grid(10000, 256, sample_shape(64, 1)) == 256 &&
+              sample_grid(10000, 256, sample_shape(32, 1)) == 512 && sample_grid(10000, 256, sample_shape(12, 1)) == 2048 &&
+              sample_grid(0, 256, sample_shape(32, 1)) == 1, "the grid: the blocks the card holds at once");
 
 // Ring depths of the G > 1 kernels.  A row-shape kernel of P pieces per lane exists at its shape's own depth (the
 // G = 1 kernel's) and, where kGroupRingAlt divides P and differs from it, at kGroupRingAlt as well: scan_group_ring

@@ -71,13 +71,20 @@ int collect_buffers(CollectBatch &t, size_t s, bool limited, size_t head_max, si
 int collect_sweeps(szg_index *ix, Shard *sh, Ctx *c, const CollectBatch &t, size_t cap, int q0, int q1, int qpl,
                    hipStream_t after, int part, bool wide, const float *norms)
 {
-    const LaunchGeom g = scan_geometry(ix, sh, 0);
+    LaunchGeom g = scan_geometry(ix, sh, 0);
+    // (long rows: the launches take the long collect form's geometry where their largest takes the block of 512.
+    // norms == nullptr -- RadiusCall on a plain handle's own rows -- keeps everything as it was: the plain geometry, and
+    // matrix = 2 in wide batches, the handle's sketch_matrix elsewhere, which is what fill_scan_args set)
+    const CollectShape cs = sketch_collect_shape(sketch_shape(ix, ix), g.grid, g.block, norms && !t.any_mask && !sh->has_dead,
+                                                 wide && ix->sketch_matrix == 0 ? 2 : ix->sketch_matrix, std::min(qpl, q1 - q0));
+    g.grid = cs.grid;
+    g.block = cs.block;
     std::vector<szg::ScanArgs> a((q1 - q0 + qpl - 1) / qpl);
     for (int j0 = q0; j0 < q1; j0 += qpl) {
         szg::ScanArgs &x = a[(j0 - q0) / qpl];
         fill_collect_args(ix, sh, c, t.any_mask, j0, std::min(qpl, q1 - j0), &t.thr[j0], c->d_collect + (size_t)j0 * cap, cap,
                           c->d_count + (size_t)j0 * szg::kCandCountStride, true, &x);
-        if (wide && x.matrix == 0) x.matrix = 2;
+        x.matrix = cs.matrix;
         if (norms && szg::scan_wants_norms(ix->bits, x, g.block)) x.row_norm = norms;
     }
     return launch_scans_chained(ix, sh, c, a, g, after, part);

@@ -71,8 +71,8 @@ SamplePlan shard_sample_plan(const szg_index *sk, const Shard *h, int k, int nq)
     in.steps = sk->layout.steps;
     in.r16 = (uint32_t)sk->map.r16;
     SamplePlan sp = sample_plan(in);
-    // (the image of one column block has to fit the LDS)
-    if (sp.serves && szg::sample_mx_lds_bytes(in.steps, 1) > 64u * 1024u) sp = SamplePlan{};
+    // (the image of one column block has to fit the LDS: 64 KiB, or the long sample's up to 160 KiB -- szg::sample_shape)
+    if (sp.serves && szg::sample_shape(in.steps, 1).block == 0) sp = SamplePlan{};
     return sp;
 }
 
@@ -124,7 +124,7 @@ int SketchTopkCall::enqueue_sample(SketchTopkBatch &t, size_t s, const std::vect
     const LaunchGeom g = scan_geometry(sk, h, 0);
     // (wide launches: the sample's two-block image has to fit LDS as well)
     const CollectLaunches cl = sketch_collect_launches(sketch_shape(ix, sk), g.grid, g.block, h->has_dead, p.wide,
-                                                       !masked && szg::sample_mx_lds_bytes(sk->layout.steps, 2) <= 64u * 1024u,
+                                                       !masked && szg::sample_shape(sk->layout.steps, 2).block != 0,
                                                        t.nq, szg::kMatrixQueries);
     const int qpl = cl.qpl;
     std::vector<szg::SampleArgs> launches;
@@ -138,8 +138,10 @@ int SketchTopkCall::enqueue_sample(SketchTopkBatch &t, size_t s, const std::vect
         x.keys = keys + (size_t)j0 * sp.slots;
         launches.push_back(x);
     }
-    const int block = 256;
-    const int grid = (int)std::max<uint64_t>(1, std::min<uint64_t>((sp.tiles + 3) / 4, (uint64_t)h->cu_count * 8));
+    // (long rows: the long sample's block and a grid of the blocks the card holds at once)
+    const szg::SampleShape shape = szg::sample_shape(sk->layout.steps, cl.wide32 ? 2 : 1);
+    const int block = shape.block;
+    const int grid = (int)szg::sample_grid(sp.tiles, h->cu_count, shape);
     rc = chain_sweeps(sk, h, c, c->pass.work, 0, (int)launches.size(), "szg::launch_sample_mx", [&](hipStream_t st) {
         hipError_t e = hipSuccess;
         for (size_t i = 0; i < launches.size() && e == hipSuccess; i++)
@@ -379,7 +381,8 @@ int szg_index_sketch_topk_stats(szg_index *ix, szg_sketch_topk_stats *out)
     return SZG_OK;
 }
 
-// the sample plan of a top-k search through the sketch (sample_plan.h), for a shard of the given shape
+// the sample plan of a top-k search through the sketch (sample_plan.h), for a shard of the given shape -- as the 64 KiB
+// forms serve it: rows whose image passes 64 KiB (2 048 dimensions and more) are szg_debug_sample_long_plan's
 int szg_debug_sample_plan(uint64_t shard_rows, int k, int n_queries, int dim, int quant_bits, int planes, szg_sample_plan *out)
 {
     SZG_TRY
@@ -411,6 +414,49 @@ int szg_debug_sample_plan(uint64_t shard_rows, int k, int n_queries, int dim, in
     out->key_bytes = sp.key_bytes;
     out->cap = sp.cap;
     out->lds_bytes = szg::sample_mx_lds_bytes(in.steps, out->blocks);
+    return SZG_OK;
+    SZG_CATCH
+}
+
+// ... and of the long sample (szg::sample_shape): rows of 2 048 .. 4 096 dimensions, for a shard of
+// cu_count compute units (0 = 256).  serves: the long instantiation serves a launch of n_queries; blocks: its column blocks
+// -- two for 17 .. 32 queries where both images fit a CU's LDS, which is what a launch of 32 takes where the collect form's
+// two blocks serve as well.  Computed from what enqueue_sample calls.
+int szg_debug_sample_long_plan(uint64_t shard_rows, int k, int n_queries, int dim, int quant_bits, int planes, int cu_count,
+                               szg_sample_long_plan *out)
+{
+    SZG_TRY
+    using namespace szgi;
+    if (!out) return fail(SZG_E_INVALID, "null argument");
+    memset(out, 0, sizeof(*out));
+    if (n_queries < 1 || n_queries > szg::kMatrixWideQueries || cu_count < 0) return fail(SZG_E_INVALID, "n_queries or cu_count out of range");
+    RowFormat f;
+    const int rc = row_format(dim, quant_bits, &f);
+    if (rc == SZG_E_INVALID) return rc;
+    if (rc) return SZG_OK;
+    SamplePlanIn in;
+    in.rows = shard_rows;
+    in.k = k;
+    in.n_queries = n_queries;
+    in.bits = quant_bits;
+    in.planes = planes;
+    in.tiled = f.layout.tiled != 0;
+    in.steps = f.layout.steps;
+    in.r16 = (uint32_t)f.map.r16;
+    const SamplePlan sp = sample_plan(in);
+    int blocks = n_queries > szg::kMatrixQueries ? 2 : 1;
+    if (blocks == 2 && szg::sample_shape(in.steps, 2).block == 0) blocks = 1;
+    const szg::SampleShape shape = szg::sample_shape(in.steps, blocks);
+    if (!sp.serves || !shape.long_form) return SZG_OK;
+    out->serves = 1;
+    out->stride = (int32_t)sp.stride;
+    out->blocks = blocks;
+    out->block = shape.block;
+    out->grid = (int32_t)szg::sample_grid(sp.tiles, cu_count ? cu_count : 256, shape);
+    out->tiles = sp.tiles;
+    out->slots = sp.slots;
+    out->cap = sp.cap;
+    out->lds_bytes = shape.lds;
     return SZG_OK;
     SZG_CATCH
 }

@@ -153,7 +153,10 @@ inline LaunchShape sketch_long_shape(const SketchShape &s, int grid, int block, 
                                      int matrix_opt)
 {
     const LaunchShape plain{grid, block};
-    if (s.bits != 8 || (masks && s.sketch_masked != 1) || kp < 1 || kp > 64 || block != 256 || !szg::scan_long_steps(s.map.r16))
+    // kp = 0: a collect launch (the long collect form; no lists -- sketch_list_len answers 0 -- and never with masks)
+    const bool collect = kp == 0;
+    if (s.bits != 8 || (masks && (collect || s.sketch_masked != 1)) || kp < 0 || kp > 64 || block != 256 ||
+        !szg::scan_long_steps(s.map.r16))
         return plain;
     const szg::LongPlan p = szg::scan_long_plan(s.map, sketch_list_len(s.sketch_list, kp, grid), blocks);
     if (p.block != szg::kLongBlockMax) return plain;
@@ -162,7 +165,7 @@ inline LaunchShape sketch_long_shape(const SketchShape &s, int grid, int block, 
                                                         ? szg::share_slices(szg::share_grid(one.grid))
                                                         : one.grid);
     if (szg::scan_long_plan(s.map, m, blocks).block != p.block) return plain;
-    szg::ScanPlanIn in = sketch_plan_in(s, m, false, masks, n_queries, one.block);
+    szg::ScanPlanIn in = sketch_plan_in(s, m, collect, masks, n_queries, one.block);
     in.matrix_opt = matrix_opt;
     const szg::ScanVariant v = szg::scan_variant(in);
     return v.long_rows && v.matrix_blocks() == blocks ? one : plain;
@@ -360,6 +363,23 @@ inline CollectLaunches sketch_collect_launches(const SketchShape &s, int grid, i
 {
     const bool wide32 = wide && ok && nq > szg::kMatrixQueries && sketch_wide_serves(s, grid, block, has_dead, 0);
     return CollectLaunches{wide32, wide32 ? szg::kMatrixWideQueries : per_launch};
+}
+// The geometry that consecutive collect launches share, the largest of which holds n_max queries:
+// the long collect form's where that launch takes the block of szg::kLongBlockMax -- half the grid, and every launch takes the
+// matrix sweep whatever its count (matrix = 2), as a top-k batch on long rows does, so that a rest of one or two queries is
+// a one-block long launch of one pass and not a one-query kernel on a block it was not built for.  matrix: the launches'
+// sketch_matrix (2 already in a call with wide batches); ok: unmasked launches with resident norms.  Everything else keeps
+// (grid, block) and the option -- rows of 2 048 .. 2 496 dimensions in launches of up to 16 too: their long form runs on the
+// plain geometry, named by scan_variant for each launch on its own.
+struct CollectShape {
+    int grid, block, matrix;
+};
+inline CollectShape sketch_collect_shape(const SketchShape &s, int grid, int block, bool ok, int matrix, int n_max)
+{
+    const CollectShape plain{grid, block, matrix};
+    if (!ok || matrix == 1 || (matrix == 0 && n_max < szg::kMatrixMinQueries)) return plain;
+    const LaunchShape g = sketch_long_shape(s, grid, block, false, 0, n_max, n_max > szg::kMatrixQueries ? 2 : 1, 2);
+    return g.block != block ? CollectShape{g.grid, g.block, 2} : plain;
 }
 
 }  // namespace szgi

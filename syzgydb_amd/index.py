@@ -1237,6 +1237,33 @@ def sample_plan(shard_rows, k, n_queries=1, dim=768, quant_bits=8, planes=2):
     return d
 
 
+def scan_long_collect_plan(dim, quant_bits, n_queries, planes=2, norms=True, tiled=True, masked=False, block=0, sketch_wide=0):
+    """Host-only test hook (szg_debug_scan_long_collect): the matrix sweep's long-row collect form (2 048 to 4 096
+    dimensions) for ONE collect launch of n_queries (up to 32) queries -- whether it takes the form, its column blocks,
+    threads per block, grid, LDS bytes and passes over the rows (a count of 17 to 32 that two column blocks do not serve is
+    walked as launches of up to 16)."""
+    L = _lib.load()
+    p = _lib.SzgScanLongPlan()
+    check(L.szg_debug_scan_long_collect(int(dim), int(quant_bits), int(n_queries), int(planes), int(bool(norms)), int(bool(tiled)),
+                                        int(bool(masked)), int(block), int(sketch_wide), ctypes.byref(p)),
+          "szg_debug_scan_long_collect")
+    return {"serves": bool(p.serves), "blocks": int(p.blocks), "block": int(p.block), "grid": int(p.grid),
+            "passes": int(p.passes), "lds_bytes": int(p.lds_bytes)}
+
+
+def sample_long_plan(shard_rows, k, n_queries=1, dim=2048, quant_bits=8, planes=2, cu_count=0):
+    """Host-only test hook (szg_debug_sample_long_plan): the long sample pass of a top-k search through the sketch at 2 048
+    to 4 096 dimensions -- serves, stride, blocks, block (threads), grid, tiles, slots, cap and lds_bytes; every field 0
+    where the long instantiation does not serve."""
+    L = _lib.load()
+    out = _lib.SzgSampleLongPlan()
+    check(L.szg_debug_sample_long_plan(int(shard_rows), int(k), int(n_queries), int(dim), int(quant_bits), int(planes),
+                                       int(cu_count), ctypes.byref(out)), "szg_debug_sample_long_plan")
+    d = {name: int(getattr(out, name)) for name, _ in _lib.SzgSampleLongPlan._fields_ if name != "reserved"}
+    d["serves"] = bool(d["serves"])
+    return d
+
+
 def query_prep_serves(option, batch_queries):
     """Host-only test hook (szg_debug_query_prep_serves; csrc/sketch_plan.h): (does the card prepare a sketch top-k batch of
     batch_queries queries under query_prep = option?, the smallest batch that option 1 serves)."""
