@@ -161,9 +161,22 @@ struct ScanShareArgs {
     ScanShareHi hi;
 };
 
+// The matrix sweep's masked forms (option sketch_masked) take their option behind ScanShareHi again, in a struct that only
+// those kernels take: a top-k launch with tombstones (a.live_bits) or filter masks (query q of the launch reads
+// a.allow_bits + q * a.allow_stride) in the form the same launch without masks would take.  hi: the shared form's constants
+// (zero for the other forms).  The superset record: every launcher of the matrix sweep takes it and hands its kernel the
+// part that kernel reads (ScanArgs, ScanShareArgs or all of it).
+struct ScanMaskedArgs {
+    ScanArgs a;
+    ScanShareHi hi;
+    int masked;  // option sketch_masked: 1 = masked launches take the matrix sweep where they qualify
+};
+
 inline bool scan_masked(const ScanArgs &a) { return a.live_bits != nullptr || a.allow_bits != nullptr; }
-// what scan_variant decides from (scan_plan.h), for the launch `a` describes at `block` threads
-inline ScanPlanIn scan_plan_in(int qbits, const ScanArgs &a, int block)
+// what scan_variant decides from (scan_plan.h), for the launch `a` describes at `block` threads under the options
+// sketch_share and sketch_masked (their defaults: what a caller that does not know them gets -- never shared, masked
+// launches keep the one-query kernel)
+inline ScanPlanIn scan_plan_in(int qbits, const ScanArgs &a, int block, int share_opt = 1, int masked_opt = 0)
 {
     ScanPlanIn in{qbits, a.map, a.tiled != 0, a.kp, a.collect != 0, scan_masked(a), a.ring, a.no_shape_kernels != 0};
     in.group = a.group;
@@ -175,6 +188,8 @@ inline ScanPlanIn scan_plan_in(int qbits, const ScanArgs &a, int block)
     in.norms = a.row_norm != nullptr;
     in.select_opt = a.select;
     in.wide_opt = a.wide;
+    in.share_opt = share_opt;
+    in.masked_opt = masked_opt;
     return in;
 }
 // queries per row read of the variant launch_scan takes for `a`
@@ -185,91 +200,48 @@ inline int scan_passes(int qbits, const ScanArgs &a, int block)
     const int group = scan_group_of(qbits, a, block);
     return (a.n_queries + group - 1) / group;
 }
-// would launch_scan read resident row norms for `a`, if it had them (a G > 1 variant or the matrix sweep)?  The caller
-// then asks for them (scan_row_norms) before it launches.
-inline bool scan_wants_norms(int qbits, const ScanArgs &a, int block)
+// would launch_scan read resident row norms for `a`, if it had them (a G > 1 variant or the matrix sweep, its masked
+// forms under sketch_masked = 1 included)?  The caller then asks for them (scan_row_norms) before it launches.
+inline bool scan_wants_norms(int qbits, const ScanArgs &a, int block, int share_opt = 1, int masked_opt = 0)
 {
-    ScanPlanIn in = scan_plan_in(qbits, a, block);
+    ScanPlanIn in = scan_plan_in(qbits, a, block, share_opt, masked_opt);
     in.norms = true;
     return scan_variant(in).group > 1;
 }
 
-// Fused dequantize + distance + select.  QBITS in {4,8,16,32,64}.
-hipError_t launch_scan(int qbits, int metric, const ScanArgs &a, int grid, int block,
-                       hipStream_t stream);
+// Fused dequantize + distance + select.  QBITS in {4,8,16,32,64}.  The single entry of the one-sweep scan: it asks
+// scan_variant once; a launch of 8-bit rows that the matrix sweep serves goes to the launcher of its form
+// (matrix_form_of, SZG_MATRIX_FORMS) and metric, everything else to the launcher of its width.
+// hi: null, or what a launch of more than kMatrixWideQueries queries needs beyond ScanArgs (its `share` the option
+// sketch_share): such a launch must take a shared form -- ONE launch of 33 .. kMatrixShareQueries top-k queries on a grid of
+// 2 S blocks (share_map), the lists to a.block_lists as [n_queries][S][a.kp].  masked_opt = 1 (option sketch_masked): the
+// launch has masks and must take a masked form; the lists go where the unmasked form of the same launch leaves them.
+// A launch marked either way whose variant says otherwise is hipErrorInvalidValue.
+hipError_t launch_scan(int qbits, int metric, const ScanArgs &a, int grid, int block, hipStream_t stream,
+                       const ScanShareHi *hi = nullptr, int masked_opt = 0);
 // The launchers behind it, one per object of the build (m0 = Euclidean, m1 = cosine), declared once for the object that
 // defines one -- by its qualified name, so a definition that does not match is a compile error -- and for its caller.
-// kernels_scan.hip -DSZG_QBITS=q -DSZG_SCAN_METRIC=m: every launch of that width and metric starts here
+// kernels_scan.hip -DSZG_QBITS=q -DSZG_SCAN_METRIC=m: every launch of that width and metric that the matrix sweep does
+// not serve starts here
 #define SZG_DECL_SCAN(q)                                                                   \
     hipError_t launch_scan_q##q##m0(const ScanArgs &a, int grid, int block, hipStream_t stream); \
     hipError_t launch_scan_q##q##m1(const ScanArgs &a, int grid, int block, hipStream_t stream);
 SZG_DECL_SCAN(4) SZG_DECL_SCAN(8) SZG_DECL_SCAN(16) SZG_DECL_SCAN(32) SZG_DECL_SCAN(64)
 #undef SZG_DECL_SCAN
 // ... with -DSZG_GROUP_FORM=f on top: the G > 1 kernels of 8-bit rows in one form (bit 0 = two digit planes, bit 1 =
-// resident norms); kernels_scan_mx.hip: the matrix sweep (mx) and, with -DSZG_MX_COLLECT, its collect form (mxc)
-#define SZG_DECL_SCAN_V(name) \
-    hipError_t name(const ScanArgs &a, const ScanVariant &v, int grid, int block, size_t lds, hipStream_t stream);
-#define SZG_DECL_G8(f) SZG_DECL_SCAN_V(launch_scan_g8m0f##f) SZG_DECL_SCAN_V(launch_scan_g8m1f##f)
+// resident norms)
+#define SZG_DECL_G8(f)                                                                                                          \
+    hipError_t launch_scan_g8m0f##f(const ScanArgs &a, const ScanVariant &v, int grid, int block, size_t lds, hipStream_t stream); \
+    hipError_t launch_scan_g8m1f##f(const ScanArgs &a, const ScanVariant &v, int grid, int block, size_t lds, hipStream_t stream);
 SZG_DECL_G8(0) SZG_DECL_G8(1) SZG_DECL_G8(2) SZG_DECL_G8(3)
-SZG_DECL_SCAN_V(launch_scan_mx_m0) SZG_DECL_SCAN_V(launch_scan_mx_m1)
-SZG_DECL_SCAN_V(launch_scan_mxc_m0) SZG_DECL_SCAN_V(launch_scan_mxc_m1)
-// ... and with -DSZG_MX_LONG its long-row form (mxl; ScanVariant::long_rows): rows of 16 .. 64 steps, up to 160 KiB of LDS,
-// blocks of up to kLongBlockMax threads -- the one-block kernels (row lists, serial inserts) and the wide one
-SZG_DECL_SCAN_V(launch_scan_mxl_m0) SZG_DECL_SCAN_V(launch_scan_mxl_m1)
-// ... and with -DSZG_MX_LONG -DSZG_MX_COLLECT the long-row collect form (mxlc): unmasked collect launches over rows of 32 .. 64
-// steps, one column block or -- on the block of kLongBlockMax, 17 .. kMatrixWideQueries queries -- two
-SZG_DECL_SCAN_V(launch_scan_mxlc_m0) SZG_DECL_SCAN_V(launch_scan_mxlc_m1)
 #undef SZG_DECL_G8
-#undef SZG_DECL_SCAN_V
-// The matrix sweep's shared form (kernels_scan_mx.hip with -DSZG_MX_SHARE: objects of their own): ONE launch of 33 ..
-// kMatrixShareQueries top-k queries over 8-bit tiled rows, on a grid of 2 S blocks (share_map); the lists go to
-// a.block_lists as [n_queries][S][a.kp].  Everything that is not exactly that form is hipErrorInvalidValue.
-hipError_t launch_scan_share(int qbits, int metric, const ScanArgs &a, const ScanShareHi &hi, int grid, int block,
-                             hipStream_t stream);
-hipError_t launch_scan_mxs_m0(const ScanShareArgs &s, const ScanVariant &v, int grid, int block, size_t lds, hipStream_t stream);
-hipError_t launch_scan_mxs_m1(const ScanShareArgs &s, const ScanVariant &v, int grid, int block, size_t lds, hipStream_t stream);
-// (the long-row shared form: -DSZG_MX_LONG -DSZG_MX_SHARE)
-hipError_t launch_scan_mxls_m0(const ScanShareArgs &s, const ScanVariant &v, int grid, int block, size_t lds, hipStream_t stream);
-hipError_t launch_scan_mxls_m1(const ScanShareArgs &s, const ScanVariant &v, int grid, int block, size_t lds, hipStream_t stream);
-// what scan_variant decides from for a shared launch
-inline ScanPlanIn scan_share_plan_in(int qbits, const ScanArgs &a, const ScanShareHi &hi, int block)
-{
-    ScanPlanIn in = scan_plan_in(qbits, a, block);
-    in.share_opt = hi.share;
-    return in;
-}
-// The matrix sweep's masked forms (option sketch_masked; kernels_scan_mx.hip with -DSZG_MX_MASKED, and with -DSZG_MX_SHARE
-// on top for the shared form: objects of their own): a top-k launch with tombstones (a.live_bits) or filter masks
-// (query q of the launch reads a.allow_bits + q * a.allow_stride) in the form the same launch without masks would take.
-// The option rides behind ScanArgs in a struct that only these kernels take, as ScanShareHi does: ScanArgs, and with it the
-// code of every other kernel, stay as they were.  hi: the shared form's constants (zero for the other forms).
-struct ScanMaskedArgs {
-    ScanArgs a;
-    ScanShareHi hi;
-    int masked;  // option sketch_masked: 1 = masked launches take the matrix sweep where they qualify
-};
-// what scan_variant decides from for a launch that may take a masked form (share_opt: the sketch_share option)
-inline ScanPlanIn scan_masked_plan_in(int qbits, const ScanArgs &a, int share_opt, int masked_opt, int block)
-{
-    ScanPlanIn in = scan_plan_in(qbits, a, block);
-    in.share_opt = share_opt;
-    in.masked_opt = masked_opt;
-    return in;
-}
-// ONE masked top-k launch of the matrix sweep: scan_variant must name the masked form for exactly this launch (up to 16
-// queries, 17 .. 32 wide, 33 .. 64 shared: hi as launch_scan_share takes it, its `share` the option); everything else is
-// hipErrorInvalidValue.  The lists go to a.block_lists as the unmasked form of the same launch leaves them.
-hipError_t launch_scan_masked(int qbits, int metric, const ScanArgs &a, const ScanShareHi &hi, int masked_opt, int grid, int block,
-                              hipStream_t stream);
-hipError_t launch_scan_mxm_m0(const ScanMaskedArgs &s, const ScanVariant &v, int grid, int block, size_t lds, hipStream_t stream);
-hipError_t launch_scan_mxm_m1(const ScanMaskedArgs &s, const ScanVariant &v, int grid, int block, size_t lds, hipStream_t stream);
-hipError_t launch_scan_mxms_m0(const ScanMaskedArgs &s, const ScanVariant &v, int grid, int block, size_t lds, hipStream_t stream);
-hipError_t launch_scan_mxms_m1(const ScanMaskedArgs &s, const ScanVariant &v, int grid, int block, size_t lds, hipStream_t stream);
-// (the masked long-row forms: -DSZG_MX_LONG -DSZG_MX_MASKED, with -DSZG_MX_SHARE the shared one; ScanVariant::long_rows and masked)
-hipError_t launch_scan_mxlm_m0(const ScanMaskedArgs &s, const ScanVariant &v, int grid, int block, size_t lds, hipStream_t stream);
-hipError_t launch_scan_mxlm_m1(const ScanMaskedArgs &s, const ScanVariant &v, int grid, int block, size_t lds, hipStream_t stream);
-hipError_t launch_scan_mxlms_m0(const ScanMaskedArgs &s, const ScanVariant &v, int grid, int block, size_t lds, hipStream_t stream);
-hipError_t launch_scan_mxlms_m1(const ScanMaskedArgs &s, const ScanVariant &v, int grid, int block, size_t lds, hipStream_t stream);
+// kernels_scan_mx.hip: the matrix sweep, one object per form of SZG_MATRIX_FORMS (-DSZG_MX_LONG, -DSZG_MX_MASKED,
+// -DSZG_MX_SHARE, -DSZG_MX_COLLECT name its facts) and metric, one signature.  v names the kernel; a launch that is not
+// exactly a launch scan_variant plans for that form (matrix_launch_ok) is hipErrorInvalidValue.
+using ScanMatrixLauncher = hipError_t(const ScanMaskedArgs &s, const ScanVariant &v, int grid, int block, size_t lds, hipStream_t stream);
+#define SZG_DECL_MX(name, l, m, s, c) ScanMatrixLauncher launch_scan_##name##_m0, launch_scan_##name##_m1;
+SZG_MATRIX_FORMS(SZG_DECL_MX)
+#undef SZG_DECL_MX
 // ---- kernels_sample_mx.hip: the sample pass of a top-k search of large k through the sketch (option sketch_topk_collect;
 // sample_plan.h has the arithmetic) ----------------------------------------------------------------------------------
 // One launch scores sample tiles 0 .. tiles - 1 -- tile j of the sample is tile j * stride of the rows -- against the

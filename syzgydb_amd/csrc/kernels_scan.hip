@@ -1006,19 +1006,14 @@ hipError_t launch_scan_qmcm(const ScanArgs &a, int grid, int block, hipStream_t 
     const ScanVariant v = scan_variant(in);
     const size_t lds = scan_lds_bytes(QBITS, a.map, COLLECT ? 0 : a.kp, block, v.group, a.planes, v.matrix_blocks());
     // (the per-query constants of every launch but the wide one are read up to kMaxSweepsPerLaunch queries)
-    if (!v.wide && a.n_queries > kMaxSweepsPerLaunch) return hipErrorInvalidValue;
+    if (a.n_queries > kMaxSweepsPerLaunch) return hipErrorInvalidValue;
+    // (the matrix sweep -- kernels_scan_mx.hip -- has launchers of its own: launch_scan takes such a launch there and never
+    // comes here with it)
+    if (v.matrix) return hipErrorInvalidValue;
     if constexpr (QBITS == 8 && !COLLECT && !MASKED) {
-        // the matrix sweep: up to kMatrixQueries queries per row read on the matrix cores (kernels_scan_mx.hip)
-        if (v.matrix && v.long_rows) return METRIC == kCosine ? launch_scan_mxl_m1(a, v, grid, block, lds, stream) : launch_scan_mxl_m0(a, v, grid, block, lds, stream);
-        if (v.matrix) return METRIC == kCosine ? launch_scan_mx_m1(a, v, grid, block, lds, stream) : launch_scan_mx_m0(a, v, grid, block, lds, stream);
         // G > 1: the form of the kernel -- two digit planes where the queries carry two (bit 0), resident norms where
         // the launch has them (bit 1); every form is an object of its own (SZG_GROUP_FORM)
         if (v.group > 1) return launch_scan_g8(METRIC, (a.planes == 2 ? 1 : 0) | (a.row_norm ? 2 : 0), a, v, grid, block, lds, stream);
-    }
-    if constexpr (QBITS == 8 && COLLECT && !MASKED) {
-        // ... and its collect form (objects of their own: the top-k kernels' code does not change with it)
-        if (v.matrix && v.long_rows) return METRIC == kCosine ? launch_scan_mxlc_m1(a, v, grid, block, lds, stream) : launch_scan_mxlc_m0(a, v, grid, block, lds, stream);
-        if (v.matrix) return METRIC == kCosine ? launch_scan_mxc_m1(a, v, grid, block, lds, stream) : launch_scan_mxc_m0(a, v, grid, block, lds, stream);
     }
     if (v.group != 1) return hipErrorInvalidValue;
     return launch_scan_group<QBITS, METRIC, COLLECT, MASKED, 1>(a, v, g, b, lds, stream);

@@ -278,10 +278,34 @@ __global__ __launch_bounds__(1024) void merge_kernel(const uint64_t *in, int n_l
 
 }  // namespace
 
-hipError_t launch_scan(int qbits, int metric, const ScanArgs &a, int grid, int block, hipStream_t stream)
+hipError_t launch_scan(int qbits, int metric, const ScanArgs &a, int grid, int block, hipStream_t stream, const ScanShareHi *hi,
+                       int masked_opt)
 {
     static_assert(kEuclidean == 0 && kCosine == 1, "the scan objects are named by the metric's number");
     const bool cosine = metric == kCosine;
+    // what the caller says the launch is: shared (more queries than a wide launch holds), masked (sketch_masked = 1)
+    const bool shared = hi && a.n_queries > kMatrixWideQueries, masked = masked_opt == 1;
+    if ((shared || masked) && (qbits != 8 || (!cosine && metric != kEuclidean) || a.collect || scan_masked(a) != masked))
+        return hipErrorInvalidValue;
+    if (qbits == 8) {
+        const ScanVariant v = scan_variant(scan_plan_in(qbits, a, block, hi ? hi->share : 1, masked_opt));
+        // (a launch marked masked or shared whose variant says otherwise: an error, never another kernel)
+        if (masked ? !(v.matrix && v.masked) : (shared && !(v.matrix && v.share))) return hipErrorInvalidValue;
+        if (v.matrix) {
+#define SZG_MX_ROW(name, l, m, s, c) {launch_scan_##name##_m0, launch_scan_##name##_m1},
+            static ScanMatrixLauncher *const forms[kMatrixFormCount][2] = {SZG_MATRIX_FORMS(SZG_MX_ROW)};
+#undef SZG_MX_ROW
+            const int form = matrix_form_index(matrix_form_of(v, a.collect != 0));
+            if (form < 0) return hipErrorInvalidValue;
+            ScanMaskedArgs s{};  // (no hi: zero constants, never shared)
+            s.a = a;
+            s.hi.share = 1;
+            if (hi) s.hi = *hi;
+            s.masked = masked_opt;
+            const size_t lds = scan_lds_bytes(qbits, a.map, a.collect ? 0 : a.kp, block, v.group, a.planes, v.matrix_blocks());
+            return forms[form][cosine ? 1 : 0](s, v, grid, block, lds, stream);
+        }
+    }
     switch (qbits) {
     case 4: return (cosine ? launch_scan_q4m1 : launch_scan_q4m0)(a, grid, block, stream);
     case 8: return (cosine ? launch_scan_q8m1 : launch_scan_q8m0)(a, grid, block, stream);
@@ -290,42 +314,6 @@ hipError_t launch_scan(int qbits, int metric, const ScanArgs &a, int grid, int b
     case 64: return (cosine ? launch_scan_q64m1 : launch_scan_q64m0)(a, grid, block, stream);
     default: return hipErrorInvalidValue;
     }
-}
-
-// the matrix sweep's shared launch: scan_variant must name the shared form for exactly this launch
-hipError_t launch_scan_share(int qbits, int metric, const ScanArgs &a, const ScanShareHi &hi, int grid, int block,
-                             hipStream_t stream)
-{
-    if (qbits != 8 || (metric != kCosine && metric != kEuclidean) || a.collect || scan_masked(a)) return hipErrorInvalidValue;
-    const ScanVariant v = scan_variant(scan_share_plan_in(qbits, a, hi, block));
-    if (!v.matrix || !v.share) return hipErrorInvalidValue;
-    const size_t lds = scan_lds_bytes(qbits, a.map, a.kp, block, v.group, a.planes, v.matrix_blocks());
-    ScanShareArgs s;
-    s.a = a;
-    s.hi = hi;
-    if (v.long_rows) return (metric == kCosine ? launch_scan_mxls_m1 : launch_scan_mxls_m0)(s, v, grid, block, lds, stream);
-    return (metric == kCosine ? launch_scan_mxs_m1 : launch_scan_mxs_m0)(s, v, grid, block, lds, stream);
-}
-
-// the matrix sweep's masked launch (option sketch_masked): scan_variant must name the masked form for exactly this launch
-hipError_t launch_scan_masked(int qbits, int metric, const ScanArgs &a, const ScanShareHi &hi, int masked_opt, int grid, int block,
-                              hipStream_t stream)
-{
-    if (qbits != 8 || (metric != kCosine && metric != kEuclidean) || a.collect || !scan_masked(a) || masked_opt != 1)
-        return hipErrorInvalidValue;
-    const ScanVariant v = scan_variant(scan_masked_plan_in(qbits, a, hi.share, masked_opt, block));
-    if (!v.matrix || !v.masked) return hipErrorInvalidValue;
-    const size_t lds = scan_lds_bytes(qbits, a.map, a.kp, block, v.group, a.planes, v.matrix_blocks());
-    ScanMaskedArgs s;
-    s.a = a;
-    s.hi = hi;
-    s.masked = masked_opt;
-    if (v.long_rows) {
-        if (v.share) return (metric == kCosine ? launch_scan_mxlms_m1 : launch_scan_mxlms_m0)(s, v, grid, block, lds, stream);
-        return (metric == kCosine ? launch_scan_mxlm_m1 : launch_scan_mxlm_m0)(s, v, grid, block, lds, stream);
-    }
-    if (v.share) return (metric == kCosine ? launch_scan_mxms_m1 : launch_scan_mxms_m0)(s, v, grid, block, lds, stream);
-    return (metric == kCosine ? launch_scan_mxm_m1 : launch_scan_mxm_m0)(s, v, grid, block, lds, stream);
 }
 
 hipError_t launch_merge(const uint64_t *in, int n_lists, int kp, int n_queries, uint64_t *out,

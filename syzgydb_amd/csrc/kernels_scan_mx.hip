@@ -186,9 +186,38 @@ constexpr int mx_ring()
 // Resources (hipcc --offload-arch=gfx950 -O3, VFLAGS='-DSZG_MX_LONG -DSZG_MX_COLLECT' scripts/kernel_resources.sh scan mx 1,
 // and `... scan mx 0` for Euclid; bound 512 threads, 256 registers): no scratch.  NB = 1: 130 / 134 VGPRs (cosine / Euclid);
 // NB = 2: 202 / 210.
-#if defined(SZG_MX_LONG) && defined(SZG_MX_COLLECT) && (defined(SZG_MX_SHARE) || defined(SZG_MX_MASKED))
-#error "the long-row collect form: unmasked, never shared (SZG_MX_LONG SZG_MX_COLLECT alone)"
+// The form this object builds, by its four facts, and their letters in its launcher's name (launch_scan_mx[l][m|c][s]_m<metric>)
+#ifdef SZG_MX_LONG
+#define SZG_MX_TAG_L l
+#define SZG_MX_IS_LONG true
+#else
+#define SZG_MX_TAG_L
+#define SZG_MX_IS_LONG false
 #endif
+#ifdef SZG_MX_MASKED
+#define SZG_MX_TAG_M m
+#define SZG_MX_IS_MASKED true
+#else
+#define SZG_MX_TAG_M
+#define SZG_MX_IS_MASKED false
+#endif
+#ifdef SZG_MX_COLLECT
+#define SZG_MX_TAG_C c
+#define SZG_MX_IS_COLLECT true
+#else
+#define SZG_MX_TAG_C
+#define SZG_MX_IS_COLLECT false
+#endif
+#ifdef SZG_MX_SHARE
+#define SZG_MX_TAG_S s
+#define SZG_MX_IS_SHARE true
+#else
+#define SZG_MX_TAG_S
+#define SZG_MX_IS_SHARE false
+#endif
+constexpr MatrixForm kMxForm{SZG_MX_IS_LONG, SZG_MX_IS_MASKED, SZG_MX_IS_SHARE, SZG_MX_IS_COLLECT};
+static_assert(matrix_form_index(kMxForm) >= 0,
+              "no such form of the matrix sweep (SZG_MATRIX_FORMS, scan_plan.h): a collect form is unmasked and never shared");
 #if defined(SZG_MX_MASKED)
 #define SZG_MX_KERNEL_ARGS const ScanMaskedArgs ma
 #elif defined(SZG_MX_SHARE)
@@ -765,288 +794,82 @@ __global__ SZG_MX_BOUNDS(METRIC, STEPS, ROWS, NB) void scan_mx_kernel(SZG_MX_KER
     }
 }
 
-#if defined(SZG_MX_LONG)
-// (the long-row kernels are launched through kernels.h's launch_mxl, which raises their dynamic-LDS limit)
-// (scan_variant's conditions, once more, for every long form: a launch that does not meet them must not reach these kernels)
-#ifdef SZG_MX_MASKED
-bool mx_long_masked_ok(const ScanMaskedArgs &s, const ScanVariant &v, int grid, int block, size_t lds)
-{
-    const ScanArgs &a = s.a;
-    return v.matrix && v.long_rows && v.masked && s.masked == 1 && scan_masked(a) && v.matrix_steps == 0 && v.nontemporal && a.tiled &&
-           (int)a.steps * 4 == a.map.r16 && scan_long_steps(a.map.r16) && a.planes == 2 && a.row_norm && a.block_lists && a.kp >= 1 &&
-           a.kp <= 64 && !a.collect && a.n_queries >= 1 && grid >= 1 && block >= 64 && block <= kLongBlockMax && block % 64 == 0 &&
-           lds <= kLongLdsCu && (v.row_lists != 0) == matrix_row_lists(a.kp, a.select) &&
-           lds == scan_lds_bytes(8, a.map, a.kp, block, v.group, a.planes, v.matrix_blocks());
-}
-#elif defined(SZG_MX_COLLECT)
-bool mx_long_collect_ok(const ScanArgs &a, const ScanVariant &v, int grid, int block, size_t lds)
-{
-    return v.matrix && v.long_rows && !v.masked && !v.share && !v.row_lists && v.matrix_steps == 0 && v.nontemporal && a.tiled &&
-           (int)a.steps * 4 == a.map.r16 && scan_long_steps(a.map.r16) && a.planes == 2 && a.row_norm && a.collect && a.collect_buf &&
-           a.collect_count && !scan_masked(a) && a.n_queries >= 1 && grid >= 1 && block >= 64 && block <= kLongBlockMax &&
-           block % 64 == 0 && lds > 64u * 1024u && lds <= (block > 256 ? kLongLdsCu : kLongLdsHalf) &&
-           lds == scan_lds_bytes(8, a.map, 0, block, v.group, a.planes, v.matrix_blocks());
-}
-#else
-bool mx_long_ok(const ScanArgs &a, const ScanVariant &v, int grid, int block, size_t lds)
-{
-    return v.matrix && v.long_rows && !v.masked && v.matrix_steps == 0 && v.nontemporal && a.tiled && (int)a.steps * 4 == a.map.r16 &&
-           scan_long_steps(a.map.r16) && a.planes == 2 && a.row_norm && a.block_lists && a.kp >= 1 && a.kp <= 64 && !a.collect &&
-           !scan_masked(a) && a.n_queries >= 1 && grid >= 1 && block >= 64 && block <= kLongBlockMax && block % 64 == 0 &&
-           lds <= kLongLdsCu && (v.row_lists != 0) == matrix_row_lists(a.kp, a.select) &&
-           lds == scan_lds_bytes(8, a.map, a.kp, block, v.group, a.planes, v.matrix_blocks());
-}
-#endif
-#elif defined(SZG_MX_MASKED) && defined(SZG_MX_SHARE)
-template <int STEPS>
-hipError_t launch_mxms_steps(const ScanMaskedArgs &s, int grid, int block, size_t lds, hipStream_t stream)
-{
-    hipLaunchKernelGGL((scan_mx_kernel<SZG_SCAN_METRIC, STEPS, true, true, 2>), dim3(grid), dim3(block), lds, stream, s);
-    return hipGetLastError();
-}
-#elif defined(SZG_MX_MASKED)
-template <int STEPS>
-hipError_t launch_mxm_steps(const ScanMaskedArgs &s, bool rows, bool wide, int grid, int block, size_t lds, hipStream_t stream)
-{
-    if (wide) hipLaunchKernelGGL((scan_mx_kernel<SZG_SCAN_METRIC, STEPS, true, true, 2>), dim3(grid), dim3(block), lds, stream, s);
-    else if (rows) hipLaunchKernelGGL((scan_mx_kernel<SZG_SCAN_METRIC, STEPS, true, true>), dim3(grid), dim3(block), lds, stream, s);
-    else hipLaunchKernelGGL((scan_mx_kernel<SZG_SCAN_METRIC, STEPS, true, false>), dim3(grid), dim3(block), lds, stream, s);
-    return hipGetLastError();
-}
-#elif defined(SZG_MX_SHARE)
 // the rows' loads of the shared form: streamed past the caches like the two-block form's (1), or plain (0) -- the second
 // reader of a line has to find it on the die (DESIGN.md 6, round 15 keeps the measured choice)
 #ifndef SZG_MX_SHARE_NT
 #define SZG_MX_SHARE_NT 1
 #endif
-template <int STEPS>
-hipError_t launch_mxs_steps(const ScanShareArgs &s, int grid, int block, size_t lds, hipStream_t stream)
+constexpr bool kMxNT = kMxForm.share && !kMxForm.masked && !kMxForm.long_rows ? SZG_MX_SHARE_NT != 0 : true;
+
+// One kernel of this object, launched (the long-row kernels through kernels.h's launch_mxl, which raises their dynamic-LDS limit)
+template <int STEPS, bool ROWS, int NB, typename Args>
+hipError_t launch_mx_kernel(const Args &k, int grid, int block, size_t lds, hipStream_t stream)
 {
-    hipLaunchKernelGGL((scan_mx_kernel<SZG_SCAN_METRIC, STEPS, SZG_MX_SHARE_NT != 0, true, 2>), dim3(grid), dim3(block), lds, stream, s);
-    return hipGetLastError();
+    constexpr auto kern = scan_mx_kernel<SZG_SCAN_METRIC, STEPS, kMxNT, ROWS, NB, kMxForm.collect>;
+    if constexpr (kMxForm.long_rows) {
+        return launch_mxl<kern>(k, grid, block, lds, stream);
+    } else {
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(block), lds, stream, k);
+        return hipGetLastError();
+    }
 }
-#elif !defined(SZG_MX_COLLECT)
-template <int STEPS>
-hipError_t launch_mx_steps(const ScanArgs &a, bool rows, bool wide, int grid, int block, size_t lds, hipStream_t stream)
+// ... chosen among the object's kernels of STEPS steps as v names it: a shared form has the two-block row-list kernel alone,
+// a collect form one and two blocks (instantiated with ROWS set), a top-k form two blocks, one with row lists, one with
+// serial inserts.  (Templates, so that `if constexpr` leaves out the kernels the object does not carry.)
+template <int STEPS, typename Args>
+hipError_t launch_mx_steps(const Args &k, const ScanVariant &v, int grid, int block, size_t lds, hipStream_t stream)
 {
-    if (wide) hipLaunchKernelGGL((scan_mx_kernel<SZG_SCAN_METRIC, STEPS, true, true, 2>), dim3(grid), dim3(block), lds, stream, a);
-    else if (rows) hipLaunchKernelGGL((scan_mx_kernel<SZG_SCAN_METRIC, STEPS, true, true>), dim3(grid), dim3(block), lds, stream, a);
-    else hipLaunchKernelGGL((scan_mx_kernel<SZG_SCAN_METRIC, STEPS, true, false>), dim3(grid), dim3(block), lds, stream, a);
-    return hipGetLastError();
+    if constexpr (kMxForm.share) {
+        return launch_mx_kernel<STEPS, true, 2>(k, grid, block, lds, stream);
+    } else {
+        if (v.wide) return launch_mx_kernel<STEPS, true, 2>(k, grid, block, lds, stream);
+        if constexpr (kMxForm.collect) {
+            return launch_mx_kernel<STEPS, true, 1>(k, grid, block, lds, stream);
+        } else {
+            if (v.row_lists) return launch_mx_kernel<STEPS, true, 1>(k, grid, block, lds, stream);
+            return launch_mx_kernel<STEPS, false, 1>(k, grid, block, lds, stream);
+        }
+    }
 }
-#else
-template <int STEPS>
-hipError_t launch_mxc_steps(const ScanArgs &a, bool wide, int grid, int block, size_t lds, hipStream_t stream)
+// the part of the record this form's kernels take: all of it, the shared launch's, or the plain launch's
+template <typename S>
+decltype(auto) mx_kernel_args(const S &s)
 {
-    if (wide) hipLaunchKernelGGL((scan_mx_kernel<SZG_SCAN_METRIC, STEPS, true, true, 2, true>), dim3(grid), dim3(block), lds, stream, a);
-    else hipLaunchKernelGGL((scan_mx_kernel<SZG_SCAN_METRIC, STEPS, true, true, 1, true>), dim3(grid), dim3(block), lds, stream, a);
-    return hipGetLastError();
+    if constexpr (kMxForm.masked) return (s);
+    else if constexpr (kMxForm.share) return ScanShareArgs{s.a, s.hi};
+    else return (s.a);
 }
-#endif
+// The object's launcher: the guard (scan_plan.h: scan_variant's conditions, once more -- a launch that does not meet them
+// must not reach these kernels), then the kernel of the row's steps.
+template <typename S>
+hipError_t launch_mx_form(const S &s, const ScanVariant &v, int grid, int block, size_t lds, hipStream_t stream)
+{
+    const ScanArgs &a = s.a;
+    const MatrixLaunch l{(int)a.steps, a.block_lists != nullptr, a.collect_buf != nullptr && a.collect_count != nullptr, grid, lds};
+    if (!matrix_launch_ok(kMxForm, scan_plan_in(8, a, block, s.hi.share, s.masked), v, l)) return hipErrorInvalidValue;
+    const auto &k = mx_kernel_args(s);
+    if constexpr (kMxForm.long_rows) {
+        return launch_mx_steps<0>(k, v, grid, block, lds, stream);
+    } else {
+        switch (v.matrix_steps) {
+        case 12: return launch_mx_steps<12>(k, v, grid, block, lds, stream);
+        case 6: return launch_mx_steps<6>(k, v, grid, block, lds, stream);
+        default: return launch_mx_steps<0>(k, v, grid, block, lds, stream);
+        }
+    }
+}
 
 }  // namespace
 
 }  // namespace szg
 
-// (defined by its qualified name: it has to match its declaration in kernels.h)
-#define SZG_CAT2(a, b) a##b
-#define SZG_CAT(a, b) SZG_CAT2(a, b)
-#if defined(SZG_MX_LONG) && defined(SZG_MX_COLLECT)
-// the long-row collect form of ONE metric (objects of their own, -DSZG_MX_LONG -DSZG_MX_COLLECT): one block or wide
-hipError_t szg::SZG_CAT(launch_scan_mxlc_m, SZG_SCAN_METRIC)(const ScanArgs &a, const ScanVariant &v, int grid, int block,
-                                                           size_t lds, hipStream_t stream)
+// the launcher of ONE form and metric (defined by its qualified name: it has to match its declaration in kernels.h)
+#define SZG_MX_CAT(l, m, c, s, metric) launch_scan_mx##l##m##c##s##_m##metric
+#define SZG_MX_NAME(l, m, c, s, metric) SZG_MX_CAT(l, m, c, s, metric)
+hipError_t szg::SZG_MX_NAME(SZG_MX_TAG_L, SZG_MX_TAG_M, SZG_MX_TAG_C, SZG_MX_TAG_S, SZG_SCAN_METRIC)(const ScanMaskedArgs &s, const ScanVariant &v,
+                                                                                                   int grid, int block, size_t lds,
+                                                                                                   hipStream_t stream)
 {
-    if (!mx_long_collect_ok(a, v, grid, block, lds)) return hipErrorInvalidValue;
-    // the wide form: the block of 512, 17 .. kMatrixWideQueries queries (the constants' and thresholds' arrays hold that
-    // many); every other launch holds at most kMaxSweepsPerLaunch
-    if (v.wide) {
-        if (a.wide == 1 || block <= 256 || a.n_queries <= kMatrixQueries || a.n_queries > kMatrixWideQueries) return hipErrorInvalidValue;
-        return launch_mxl<scan_mx_kernel<SZG_SCAN_METRIC, 0, true, true, 2, true>>(a, grid, block, lds, stream);
-    }
-    if (a.n_queries > kMaxSweepsPerLaunch) return hipErrorInvalidValue;
-    return launch_mxl<scan_mx_kernel<SZG_SCAN_METRIC, 0, true, true, 1, true>>(a, grid, block, lds, stream);
+    return launch_mx_form(s, v, grid, block, lds, stream);
 }
-#elif defined(SZG_MX_LONG) && defined(SZG_MX_MASKED) && defined(SZG_MX_SHARE)
-// the masked long-row shared form of ONE metric (objects of their own, -DSZG_MX_LONG -DSZG_MX_MASKED -DSZG_MX_SHARE)
-hipError_t szg::SZG_CAT(launch_scan_mxlms_m, SZG_SCAN_METRIC)(const ScanMaskedArgs &s, const ScanVariant &v, int grid, int block,
-                                                            size_t lds, hipStream_t stream)
-{
-    const ScanArgs &a = s.a;
-    // exactly the planned form: row lists, 33 .. 64 queries, an even grid (share_map pairs its blocks), the two-block LDS
-    if (!mx_long_masked_ok(s, v, grid, block, lds) || !v.share || v.wide || !v.row_lists || a.wide == 1 || s.hi.share == 1 ||
-        a.n_queries <= kMatrixWideQueries || a.n_queries > kMatrixShareQueries || grid < 2 || grid % 2)
-        return hipErrorInvalidValue;
-    return launch_mxl<scan_mx_kernel<SZG_SCAN_METRIC, 0, true, true, 2>>(s, grid, block, lds, stream);
-}
-#elif defined(SZG_MX_LONG) && defined(SZG_MX_MASKED)
-// the masked long-row forms of ONE metric (objects of their own, -DSZG_MX_LONG -DSZG_MX_MASKED): one block with row lists
-// or serial inserts, wide
-hipError_t szg::SZG_CAT(launch_scan_mxlm_m, SZG_SCAN_METRIC)(const ScanMaskedArgs &s, const ScanVariant &v, int grid, int block,
-                                                           size_t lds, hipStream_t stream)
-{
-    const ScanArgs &a = s.a;
-    if (!mx_long_masked_ok(s, v, grid, block, lds) || v.share) return hipErrorInvalidValue;
-    if (v.wide) {
-        if (!v.row_lists || a.wide == 1 || a.n_queries <= kMatrixQueries || a.n_queries > kMatrixWideQueries) return hipErrorInvalidValue;
-        return launch_mxl<scan_mx_kernel<SZG_SCAN_METRIC, 0, true, true, 2>>(s, grid, block, lds, stream);
-    }
-    if (a.n_queries > kMaxSweepsPerLaunch) return hipErrorInvalidValue;
-    if (v.row_lists) return launch_mxl<scan_mx_kernel<SZG_SCAN_METRIC, 0, true, true>>(s, grid, block, lds, stream);
-    return launch_mxl<scan_mx_kernel<SZG_SCAN_METRIC, 0, true, false>>(s, grid, block, lds, stream);
-}
-#elif defined(SZG_MX_LONG) && defined(SZG_MX_SHARE)
-// the long-row shared form of ONE metric (objects of their own, -DSZG_MX_LONG -DSZG_MX_SHARE)
-hipError_t szg::SZG_CAT(launch_scan_mxls_m, SZG_SCAN_METRIC)(const ScanShareArgs &s, const ScanVariant &v, int grid, int block,
-                                                           size_t lds, hipStream_t stream)
-{
-    const ScanArgs &a = s.a;
-    // exactly the planned form: row lists, 33 .. 64 queries, an even grid (share_map pairs its blocks), the two-block LDS
-    if (!mx_long_ok(a, v, grid, block, lds) || !v.share || v.wide || !v.row_lists || a.wide == 1 || s.hi.share == 1 ||
-        a.n_queries <= kMatrixWideQueries || a.n_queries > kMatrixShareQueries || grid < 2 || grid % 2)
-        return hipErrorInvalidValue;
-    return launch_mxl<scan_mx_kernel<SZG_SCAN_METRIC, 0, true, true, 2>>(s, grid, block, lds, stream);
-}
-#elif defined(SZG_MX_LONG)
-// the long-row forms of ONE metric (objects of their own, -DSZG_MX_LONG): one block with row lists or serial inserts, wide
-hipError_t szg::SZG_CAT(launch_scan_mxl_m, SZG_SCAN_METRIC)(const ScanArgs &a, const ScanVariant &v, int grid, int block,
-                                                          size_t lds, hipStream_t stream)
-{
-    if (!mx_long_ok(a, v, grid, block, lds) || v.share) return hipErrorInvalidValue;
-    if (v.wide) {
-        if (!v.row_lists || a.wide == 1 || a.n_queries <= kMatrixQueries || a.n_queries > kMatrixWideQueries) return hipErrorInvalidValue;
-        return launch_mxl<scan_mx_kernel<SZG_SCAN_METRIC, 0, true, true, 2>>(a, grid, block, lds, stream);
-    }
-    if (a.n_queries > kMaxSweepsPerLaunch) return hipErrorInvalidValue;
-    if (v.row_lists) return launch_mxl<scan_mx_kernel<SZG_SCAN_METRIC, 0, true, true>>(a, grid, block, lds, stream);
-    return launch_mxl<scan_mx_kernel<SZG_SCAN_METRIC, 0, true, false>>(a, grid, block, lds, stream);
-}
-#elif defined(SZG_MX_MASKED)
-// the masked forms of ONE metric (objects of their own, -DSZG_MX_MASKED; with -DSZG_MX_SHARE the masked shared form)
-namespace szg {
-namespace {
-// (scan_variant's conditions, once more, for every masked form: a launch that does not meet them must not reach these kernels)
-bool mx_masked_ok(const ScanMaskedArgs &s, const ScanVariant &v, int block, size_t lds)
-{
-    const ScanArgs &a = s.a;
-    return v.matrix && v.masked && s.masked == 1 && scan_masked(a) && v.nontemporal && a.tiled && a.steps != 0 &&
-           (int)a.steps * 4 == a.map.r16 && a.planes == 2 && a.row_norm && a.block_lists && a.kp >= 1 && a.kp <= 64 && !a.collect &&
-           a.n_queries >= 1 && block >= 64 && block <= 256 && block % 64 == 0 && lds <= 64u * 1024u &&
-           v.matrix_steps == matrix_steps_form((int)a.steps) && (v.row_lists != 0) == matrix_row_lists(a.kp, a.select);
-}
-}  // namespace
-}  // namespace szg
-#if defined(SZG_MX_SHARE)
-hipError_t szg::SZG_CAT(launch_scan_mxms_m, SZG_SCAN_METRIC)(const ScanMaskedArgs &s, const ScanVariant &v, int grid, int block,
-                                                           size_t lds, hipStream_t stream)
-{
-    const ScanArgs &a = s.a;
-    // exactly the planned form: row lists, 33 .. 64 queries, an even grid -- share_map pairs its blocks -- the two-block LDS
-    if (!mx_masked_ok(s, v, block, lds) || !v.share || v.wide || !v.row_lists || a.kp > kRowListMax || a.wide == 1 ||
-        s.hi.share == 1)
-        return hipErrorInvalidValue;
-    if (a.n_queries <= kMatrixWideQueries || a.n_queries > kMatrixShareQueries) return hipErrorInvalidValue;
-    if (grid < 2 || grid % 2) return hipErrorInvalidValue;
-    if (lds != scan_lds_bytes(8, a.map, a.kp, block, kMatrixWideQueries, a.planes, 2)) return hipErrorInvalidValue;
-    switch (v.matrix_steps) {
-    case 12: return launch_mxms_steps<12>(s, grid, block, lds, stream);
-    case 6: return launch_mxms_steps<6>(s, grid, block, lds, stream);
-    default: return launch_mxms_steps<0>(s, grid, block, lds, stream);
-    }
-}
-#else
-hipError_t szg::SZG_CAT(launch_scan_mxm_m, SZG_SCAN_METRIC)(const ScanMaskedArgs &s, const ScanVariant &v, int grid, int block,
-                                                          size_t lds, hipStream_t stream)
-{
-    const ScanArgs &a = s.a;
-    if (!mx_masked_ok(s, v, block, lds) || v.share) return hipErrorInvalidValue;
-    const bool rows = v.row_lists != 0;
-    // the wide form: row lists, 17 .. kMatrixWideQueries queries, exactly the two-block LDS; every other launch holds at most
-    // kMaxSweepsPerLaunch
-    const bool wide = v.wide != 0;
-    if (wide && (!rows || a.wide == 1 || a.n_queries <= kMatrixQueries || a.n_queries > kMatrixWideQueries ||
-                 lds != scan_lds_bytes(8, a.map, a.kp, block, kMatrixWideQueries, a.planes, v.matrix_blocks())))
-        return hipErrorInvalidValue;
-    if (!wide && (a.n_queries > kMaxSweepsPerLaunch || lds != scan_lds_bytes(8, a.map, a.kp, block, kMatrixQueries, a.planes, 1)))
-        return hipErrorInvalidValue;
-    switch (v.matrix_steps) {
-    case 12: return launch_mxm_steps<12>(s, rows, wide, grid, block, lds, stream);
-    case 6: return launch_mxm_steps<6>(s, rows, wide, grid, block, lds, stream);
-    default: return launch_mxm_steps<0>(s, rows, wide, grid, block, lds, stream);
-    }
-}
-#endif
-#elif defined(SZG_MX_SHARE)
-// the shared form of ONE metric (objects of their own, -DSZG_MX_SHARE)
-hipError_t szg::SZG_CAT(launch_scan_mxs_m, SZG_SCAN_METRIC)(const ScanShareArgs &s, const ScanVariant &v, int grid, int block,
-                                                          size_t lds, hipStream_t stream)
-{
-    const ScanArgs &a = s.a;
-    // (scan_variant's conditions, once more; and exactly the planned form: unmasked top-k with row lists, 33 .. 64 queries,
-    // an even grid -- share_map pairs its blocks -- and the two-block LDS)
-    if (!v.matrix || !v.share || v.wide || !v.row_lists || !v.nontemporal || !a.tiled || a.steps == 0 ||
-        (int)a.steps * 4 != a.map.r16 || a.planes != 2 || !a.row_norm || !a.block_lists || a.kp < 1 || a.kp > kRowListMax ||
-        !matrix_row_lists(a.kp, a.select) || a.collect || scan_masked(a) || a.wide == 1 || s.hi.share == 1 || block < 64 ||
-        block > 256 || block % 64 || lds > 64u * 1024u)
-        return hipErrorInvalidValue;
-    if (a.n_queries <= kMatrixWideQueries || a.n_queries > kMatrixShareQueries) return hipErrorInvalidValue;
-    if (grid < 2 || grid % 2) return hipErrorInvalidValue;
-    if (lds != scan_lds_bytes(8, a.map, a.kp, block, kMatrixWideQueries, a.planes, 2)) return hipErrorInvalidValue;
-    if (v.matrix_steps != matrix_steps_form((int)a.steps)) return hipErrorInvalidValue;
-    switch (v.matrix_steps) {
-    case 12: return launch_mxs_steps<12>(s, grid, block, lds, stream);
-    case 6: return launch_mxs_steps<6>(s, grid, block, lds, stream);
-    default: return launch_mxs_steps<0>(s, grid, block, lds, stream);
-    }
-}
-#elif defined(SZG_MX_COLLECT)
-// the collect form of ONE metric (objects of their own, -DSZG_MX_COLLECT): v names the form
-hipError_t szg::SZG_CAT(launch_scan_mxc_m, SZG_SCAN_METRIC)(const ScanArgs &a, const ScanVariant &v, int grid, int block,
-                                                          size_t lds, hipStream_t stream)
-{
-    // (scan_variant's conditions, once more: a launch that does not meet them must not reach these kernels)
-    if (!v.matrix || !v.nontemporal || !a.tiled || a.steps == 0 || (int)a.steps * 4 != a.map.r16 || a.planes != 2 ||
-        !a.row_norm || !a.collect || !a.collect_buf || !a.collect_count || a.n_queries < 1 || scan_masked(a) || block < 64 ||
-        block > 256 || block % 64 || lds > 64u * 1024u)
-        return hipErrorInvalidValue;
-    if (v.matrix_steps != matrix_steps_form((int)a.steps)) return hipErrorInvalidValue;
-    // the wide form: a launch of 17 .. kMatrixWideQueries queries (the constants' and thresholds' arrays hold that many)
-    // and exactly the two-block LDS; every other launch holds at most kMaxSweepsPerLaunch
-    const bool wide = v.wide != 0;
-    if (wide && (a.wide == 1 || a.n_queries <= kMatrixQueries || a.n_queries > kMatrixWideQueries)) return hipErrorInvalidValue;
-    if (!wide && a.n_queries > kMaxSweepsPerLaunch) return hipErrorInvalidValue;
-    if (lds != scan_lds_bytes(8, a.map, 0, block, wide ? kMatrixWideQueries : kMatrixQueries, a.planes, v.matrix_blocks()))
-        return hipErrorInvalidValue;
-    switch (v.matrix_steps) {
-    case 12: return launch_mxc_steps<12>(a, wide, grid, block, lds, stream);
-    case 6: return launch_mxc_steps<6>(a, wide, grid, block, lds, stream);
-    default: return launch_mxc_steps<0>(a, wide, grid, block, lds, stream);
-    }
-}
-#else
-// the matrix sweep of ONE metric (one object each, as the scan objects): v names the form (ScanVariant::matrix_steps)
-hipError_t szg::SZG_CAT(launch_scan_mx_m, SZG_SCAN_METRIC)(const ScanArgs &a, const ScanVariant &v, int grid, int block,
-                                                         size_t lds, hipStream_t stream)
-{
-    // (scan_variant's conditions, once more: a launch that does not meet them must not reach these kernels)
-    if (!v.matrix || !v.nontemporal || !a.tiled || a.steps == 0 || (int)a.steps * 4 != a.map.r16 || a.planes != 2 ||
-        !a.row_norm || a.kp < 1 || a.kp > 64 || a.collect || scan_masked(a) || block < 64 || block > 256 || block % 64 ||
-        lds > 64u * 1024u)
-        return hipErrorInvalidValue;
-    if (v.matrix_steps != matrix_steps_form((int)a.steps)) return hipErrorInvalidValue;
-    // (row lists hold at most kRowListMax entries: a longer list must never reach that form)
-    if ((v.row_lists != 0) != matrix_row_lists(a.kp, a.select)) return hipErrorInvalidValue;
-    const bool rows = v.row_lists != 0;
-    // the wide form: row lists, a launch of 17 .. kMatrixWideQueries queries (the constants' arrays hold that many),
-    // option sketch_wide not 1, and exactly the two-block LDS; every other launch holds at most kMaxSweepsPerLaunch
-    const bool wide = v.wide != 0;
-    if (wide && (!rows || a.wide == 1 || a.n_queries <= kMatrixQueries || a.n_queries > kMatrixWideQueries ||
-                 lds != scan_lds_bytes(8, a.map, a.kp, block, kMatrixWideQueries, a.planes, v.matrix_blocks())))
-        return hipErrorInvalidValue;
-    if (!wide && a.n_queries > kMaxSweepsPerLaunch) return hipErrorInvalidValue;
-    switch (v.matrix_steps) {
-    case 12: return launch_mx_steps<12>(a, rows, wide, grid, block, lds, stream);
-    case 6: return launch_mx_steps<6>(a, rows, wide, grid, block, lds, stream);
-    default: return launch_mx_steps<0>(a, rows, wide, grid, block, lds, stream);
-    }
-}
-#endif  // SZG_MX_COLLECT
+

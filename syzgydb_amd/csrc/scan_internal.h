@@ -649,11 +649,9 @@ void fill_collect_args(const szg_index *ix, const Shard *sh, const Ctx *c, bool 
 // (after: the stream that goes on once the sweeps are done -- default the work stream; part 1: the early part of a short
 // call, timed with its own event pair)
 // (hi: null, or one entry per launch -- a launch of more than szg::kMatrixWideQueries queries is then a shared launch of
-// the matrix sweep, on the grid g names: szg::launch_scan_share)
+// the matrix sweep, on the grid g names: szg::launch_scan takes it with its entry)
 int launch_scans_chained(szg_index *ix, Shard *sh, Ctx *c, const std::vector<szg::ScanArgs> &a, const LaunchGeom &g,
                          hipStream_t after = nullptr, int part = 0, const std::vector<szg::ScanShareHi> *hi = nullptr);
-// does launch `a` (8-bit rows, `block` threads) take a masked form of the matrix sweep under the index's options?
-bool scan_takes_masked_form(const szg_index *ix, const szg::ScanArgs &a, int block);
 // the sketch pre-pass: the sweep runs over a sketch shard, its merged lists are re-ranked on the float32 rows of the
 // shard it stands for, together with `extra` more rows per query that the caller has uploaded behind each list in
 // c->d_sent (kp + extra entries per query)

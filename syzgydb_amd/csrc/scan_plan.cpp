@@ -157,6 +157,48 @@ size_t scan_lds_bytes(int qbits, const RowMap &m, int kp, int block, int group, 
            (size_t)(block / kWave) * kStepList * sizeof(uint32_t);
 }
 
+bool matrix_launch_ok(const MatrixForm &f, const ScanPlanIn &in, const ScanVariant &v, const MatrixLaunch &l)
+{
+    const RowMap &m = in.map;
+    const int nq = in.n_queries, blocks = v.matrix_blocks();
+    // the form the variant names, and every kernel's shape: tiled rows of whole steps, two planes, resident norms, whole waves
+    if (matrix_form_index(f) < 0 || !v.matrix || !(f == matrix_form_of(v, in.collect)) || in.qbits != 8 || !v.nontemporal || !in.tiled ||
+        l.steps == 0 || l.steps * 4 != m.r16 || in.planes != 2 || !in.norms || nq < 1 || l.grid < 1 || in.block < kWave ||
+        in.block % kWave != 0)
+        return false;
+    // masks: the masked forms under sketch_masked = 1 and no other
+    if (in.masked != f.masked || (f.masked && in.masked_opt != 1)) return false;
+    // rows: the long forms' any-steps kernels on up to the CU's LDS, the others' within 64 KiB on blocks of up to 256
+    if (f.long_rows) {
+        if (v.matrix_steps != 0 || !scan_long_steps(m.r16) || in.block > kLongBlockMax || l.lds > kLongLdsCu) return false;
+        // (two column blocks never fit half a CU: scan_variant plans them on the block of kLongBlockMax alone)
+        if (blocks == 2 && in.block <= 256) return false;
+        if (f.collect && (l.lds <= kLdsMax || l.lds > (in.block > 256 ? kLongLdsCu : kLongLdsHalf))) return false;
+    } else if (v.matrix_steps != matrix_steps_form(l.steps) || in.block > 256 || l.lds > kLdsMax) {
+        return false;
+    }
+    // lists: top-k launches keep 1 .. 64 entries, as row lists exactly where matrix_row_lists says (a longer list must never
+    // reach that form); a collect launch keeps none and appends to its buffer
+    if (f.collect) {
+        if (!l.collect_out || v.row_lists) return false;
+    } else if (!l.lists || in.kp < 1 || in.kp > 64 || (v.row_lists != 0) != matrix_row_lists(in.kp, in.select_opt)) {
+        return false;
+    }
+    // queries: 33 .. 64 shared (an even grid: share_map pairs its blocks), 17 .. 32 wide -- the constants' and thresholds'
+    // arrays hold that many, both with row lists (or none) and not under sketch_wide = 1 -- and at most 16 else
+    if (f.share) {
+        if (v.wide || !v.row_lists || in.kp > kRowListMax || in.wide_opt == 1 || in.share_opt == 1 || nq <= kMatrixWideQueries ||
+            nq > kMatrixShareQueries || l.grid < 2 || l.grid % 2 != 0)
+            return false;
+    } else if (v.wide) {
+        if ((!f.collect && !v.row_lists) || in.wide_opt == 1 || nq <= kMatrixQueries || nq > kMatrixWideQueries) return false;
+    } else if (nq > kMaxSweepsPerLaunch) {
+        return false;
+    }
+    // exactly the LDS the kernel lays out: images, constants and lists of its column blocks
+    return l.lds == scan_lds_bytes(in.qbits, m, f.collect ? 0 : in.kp, in.block, v.group, in.planes, blocks);
+}
+
 int merge_fan(int kp)
 {
     if (kp <= 128) return kWave;                       // tournament: one list per lane

@@ -94,8 +94,8 @@ struct ScanVariant {
     int matrix_blocks() const { return matrix ? (wide || share ? 2 : 1) : 0; }
     int share = 0;    // the two-block form shared between paired blocks (share_map): a launch of kMatrixWideQueries + 1 ..
                       // kMatrixShareQueries queries, one pass per column group of kMatrixWideQueries, both over one row read
-                      // from HBM where the partner's lines are still on the die (its own launcher: launch_scan_share)
-    int masked = 0;   // the matrix sweep's masked form (option sketch_masked; objects of their own, launch_scan_masked): the
+                      // from HBM where the partner's lines are still on the die (objects of their own)
+    int masked = 0;   // the matrix sweep's masked form (option sketch_masked; objects of their own): the
                       // launch has tombstones or filter masks and takes the matrix sweep all the same
     int long_rows = 0;  // the matrix sweep's long-row form (rows of kLongMinSteps .. kLongMaxSteps steps; objects of their own,
                       // kernels_scan_mx.hip -DSZG_MX_LONG): the image may take the CU's whole LDS, blocks of up to kLongBlockMax
@@ -292,6 +292,48 @@ ScanVariant scan_variant(const ScanPlanIn &in);
 // two-plane images laid out for the matrix cores, their constants, and kMatrixQueries x waves lists of kp entries
 // (its collect form keeps no lists: kp = 0, the images and constants alone -- 48.4 KiB for two blocks at 768 dimensions)
 size_t scan_lds_bytes(int qbits, const RowMap &m, int kp, int block, int group = 1, int planes = 3, int matrix = 0);
+
+// The forms of the matrix sweep (kernels_scan_mx.hip): one object per form and metric, named by four facts.  The table of
+// the forms that exist, X(name, long rows, masked, shared, collect) -- the build's objects (kernels_scan_<name>_c / _e),
+// their launchers (kernels.h) and launch_scan's route all come from it; a form's index is its place in the table.
+#define SZG_MATRIX_FORMS(X)                                                                                     \
+    X(mx, 0, 0, 0, 0) X(mxc, 0, 0, 0, 1) X(mxs, 0, 0, 1, 0) X(mxm, 0, 1, 0, 0) X(mxms, 0, 1, 1, 0)                  \
+    X(mxl, 1, 0, 0, 0) X(mxls, 1, 0, 1, 0) X(mxlm, 1, 1, 0, 0) X(mxlms, 1, 1, 1, 0) X(mxlc, 1, 0, 0, 1)
+struct MatrixForm {
+    bool long_rows, masked, share, collect;
+};
+constexpr bool operator==(const MatrixForm &a, const MatrixForm &b)
+{
+    return a.long_rows == b.long_rows && a.masked == b.masked && a.share == b.share && a.collect == b.collect;
+}
+#define SZG_FORM_ROW(name, l, m, s, c) MatrixForm{l != 0, m != 0, s != 0, c != 0},
+constexpr MatrixForm kMatrixForms[] = {SZG_MATRIX_FORMS(SZG_FORM_ROW)};
+#undef SZG_FORM_ROW
+constexpr int kMatrixFormCount = (int)(sizeof(kMatrixForms) / sizeof(kMatrixForms[0]));
+// a form's index in the table; -1: no such form is built (a masked or shared collect form)
+constexpr int matrix_form_index(const MatrixForm &f)
+{
+    for (int i = 0; i < kMatrixFormCount; i++)
+        if (kMatrixForms[i] == f) return i;
+    return -1;
+}
+// the form that serves a launch whose variant names the matrix sweep (v.matrix)
+constexpr MatrixForm matrix_form_of(const ScanVariant &v, bool collect)
+{
+    return MatrixForm{v.long_rows != 0, v.masked != 0, v.share != 0, collect};
+}
+// What a launch of the matrix sweep has beyond its plan input: the rows' 64-byte steps as the kernel reads them
+// (ScanArgs::steps), whether it has block lists (top-k) and a collect buffer with its counter (collect), its grid and LDS.
+struct MatrixLaunch {
+    int steps;
+    bool lists, collect_out;
+    int grid;
+    size_t lds;
+};
+// The last check before a kernel of form f: scan_variant's conditions for that form, once more, on the launch as it
+// stands -- a launch that does not meet every one of them must not reach the kernel (it would read or write out of bounds).
+// True for exactly one form per launch that scan_variant planned, matrix_form_of's (tests/cpp/test_scan_plan.cpp).
+bool matrix_launch_ok(const MatrixForm &f, const ScanPlanIn &in, const ScanVariant &v, const MatrixLaunch &l);
 
 // Merge n_lists sorted lists of kp candidates into ceil(n_lists/merge_fan(kp)) lists.
 int merge_fan(int kp);

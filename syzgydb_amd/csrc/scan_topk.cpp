@@ -214,6 +214,26 @@ void fill_collect_args(const szg_index *ix, const Shard *sh, const Ctx *c, bool 
     if (dense_vote) a->mask_dense = mask_dense_vote(ix, sh, c, has_allow, slot, nq);
 }
 
+// What szg::launch_scan decides from for launch `a` of the index at `block` threads (hi: null, or the launch's record
+// beyond ScanArgs), its options included: the sketch index's top-k launches with masks take the matrix sweep's masked forms
+// under sketch_masked = 1 where scan_variant has one for them (plain 8-bit handles and collect launches stay as they are;
+// a launch without a masked form keeps the one-query kernel, in.masked_opt = 0).
+struct ScanRoute {
+    szg::ScanPlanIn in;
+    bool mxm;  // the launch takes a masked form of the matrix sweep
+};
+static ScanRoute scan_route(const szg_index *ix, const szg::ScanArgs &a, const szg::ScanShareHi *hi, int block)
+{
+    ScanRoute r{szg::scan_plan_in(ix->bits, a, block, hi ? hi->share : 1), false};
+    if (ix->sketch_masked == 1 && ix->is_sketch && ix->bits == 8 && !a.collect && szg::scan_masked(a)) {
+        r.in.masked_opt = 1;
+        const szg::ScanVariant v = szg::scan_variant(r.in);
+        r.mxm = v.matrix != 0 && v.masked != 0;
+        if (!r.mxm) r.in.masked_opt = 0;
+    }
+    return r;
+}
+
 // Launch the fused scan for each of the batch's queries (n = a->size()) as the
 // next links of the shard's scan chain; the ctx stream resumes after the last.
 int launch_scans_chained(szg_index *ix, Shard *sh, Ctx *c, const std::vector<szg::ScanArgs> &a,
@@ -221,31 +241,21 @@ int launch_scans_chained(szg_index *ix, Shard *sh, Ctx *c, const std::vector<szg
 {
     const int n = (int)a.size();
     if (hi && (int)hi->size() != n) return fail(SZG_E_INVALID, "shared launches: one record per launch");
-    auto shared = [&](int j) { return hi && a[j].n_queries > szg::kMatrixWideQueries; };
-    // launches with masks that take a masked form of the matrix sweep (option sketch_masked; szg::launch_scan_masked)
-    std::vector<char> mxm(n, 0);
-    for (int j = 0; j < n; j++) mxm[j] = scan_takes_masked_form(ix, a[j], g.block) ? 1 : 0;
-    szg::ScanShareHi no_hi;
-    memset(&no_hi, 0, sizeof(no_hi));
-    no_hi.share = ix->sketch_share;
+    std::vector<ScanRoute> route(n);
+    for (int j = 0; j < n; j++) route[j] = scan_route(ix, a[j], hi ? &(*hi)[j] : nullptr, g.block);
     // (ev_up: recorded by enqueue_queries)
     int rc = chain_sweeps(ix, sh, c, after ? after : c->pass.work, part, n, "szg::launch_scan", [&](hipStream_t st) {
         hipError_t e = hipSuccess;
         for (int j = 0; j < n && e == hipSuccess; j++)
-            e = mxm[j] ? szg::launch_scan_masked(ix->bits, ix->metric, a[j], hi ? (*hi)[j] : no_hi, ix->sketch_masked, g.grid,
-                                                 g.block, st)
-                       : (shared(j) ? szg::launch_scan_share(ix->bits, ix->metric, a[j], (*hi)[j], g.grid, g.block, st)
-                                    : szg::launch_scan(ix->bits, ix->metric, a[j], g.grid, g.block, st));
+            e = szg::launch_scan(ix->bits, ix->metric, a[j], g.grid, g.block, st, hi ? &(*hi)[j] : nullptr, route[j].in.masked_opt);
         return e;
     });
     if (rc) return rc;
     std::lock_guard<std::mutex> lk(ix->stats_mu);
     uint64_t sweeps = 0;  // passes over the rows (launch_passes), of the variant the launcher above took
     for (int j = 0; j < n; j++) {
-        sweeps += (uint64_t)launch_passes(mxm[j] ? szg::scan_masked_plan_in(ix->bits, a[j], ix->sketch_share, ix->sketch_masked, g.block)
-                                          : (shared(j) ? szg::scan_share_plan_in(ix->bits, a[j], (*hi)[j], g.block)
-                                                       : szg::scan_plan_in(ix->bits, a[j], g.block)));
-        if (mxm[j]) {
+        sweeps += (uint64_t)launch_passes(route[j].in);
+        if (route[j].mxm) {
             ix->mx_masked_launches++;
             ix->mx_masked_queries += (uint64_t)a[j].n_queries;
             if (!a[j].allow_bits || a[j].allow_stride == 0) ix->mx_masked_skip++;
@@ -254,14 +264,6 @@ int launch_scans_chained(szg_index *ix, Shard *sh, Ctx *c, const std::vector<szg
     ix->stats.scan_launches += n;
     ix->stats.scan_bytes += sweeps * sh->n_rows * (uint64_t)ix->row_bytes;
     return SZG_OK;
-}
-
-bool scan_takes_masked_form(const szg_index *ix, const szg::ScanArgs &a, int block)
-{
-    // (the sketch index's top-k launches: plain 8-bit handles and collect launches stay as they are)
-    if (ix->sketch_masked != 1 || !ix->is_sketch || ix->bits != 8 || a.collect || !szg::scan_masked(a) || !a.row_norm) return false;
-    const szg::ScanVariant v = szg::scan_variant(szg::scan_masked_plan_in(ix->bits, a, ix->sketch_share, ix->sketch_masked, block));
-    return v.matrix != 0 && v.masked != 0;
 }
 
 // A resident mask knows its exact count; the pass rate of words that came from the host is estimated from a sample.
@@ -376,12 +378,7 @@ int enqueue_topk(szg_index *ix, Shard *sh, Ctx *c, int kp, int nq, bool has_allo
         const float *norms = nullptr;
         bool asked = false;
         for (szg::ScanArgs &a : args) {
-            bool wants = szg::scan_wants_norms(ix->bits, a, g.block);
-            if (!wants && ix->sketch_masked == 1 && szg::scan_masked(a)) {  // (a masked form of the matrix sweep reads them too)
-                szg::ScanPlanIn in = szg::scan_masked_plan_in(ix->bits, a, ix->sketch_share, ix->sketch_masked, g.block);
-                in.norms = true;
-                wants = szg::scan_variant(in).matrix != 0;
-            }
+            const bool wants = szg::scan_wants_norms(ix->bits, a, g.block, ix->sketch_share, ix->sketch_masked);
             if (!wants) continue;
             if (!asked) {
                 int nrc = SZG_OK;

@@ -36,8 +36,111 @@ static ScanPlanIn sketch_launch(int n_queries, int kp)
     return in;
 }
 
+// The guard of the matrix sweep's launchers (matrix_launch_ok) against scan_variant, over tiled 8-bit rows of 6 .. 64 steps:
+// every launch that scan_variant gives to the matrix sweep, built as launch_scan builds it (scan_lds_bytes of the variant's
+// group and column blocks; where scan_long_plan names the block, its LDS), passes the guard for the form matrix_form_of
+// names and for no other, and no longer passes after any one of the corruptions below.
+static void check_matrix_guard()
+{
+    const int steps_of[] = {6, 12, 13, 30, 32, 39, 64}, kps[] = {1, 8, 15, 16, 17, 64}, nqs[] = {1, 3, 16, 17, 32, 33, 64};
+    const int blocks_of[] = {256, 512};
+    int reached[kMatrixFormCount] = {};
+    long accepted = 0;
+    for (int steps : steps_of)
+    for (int kp : kps)
+    for (int masked = 0; masked < 2; masked++)
+    for (int collect = 0; collect < 2; collect++)
+    for (int nq : nqs)
+    for (int share_on = 0; share_on < 2; share_on++)
+    for (int masked_on = 0; masked_on < 2; masked_on++)
+    for (int block : blocks_of)
+    for (int select_opt = 0; select_opt < 2; select_opt++)
+    for (int wide_opt = 0; wide_opt < 2; wide_opt++) {
+        const RowMap map{steps * 4, 4, steps, 16, 1, 1};
+        ScanPlanIn in{8, map, true, kp, collect != 0, masked != 0, 0, false};
+        in.group = 0;
+        in.n_queries = nq;
+        in.block = block;
+        in.planes = 2;
+        in.matrix_opt = 2;
+        in.norms = true;
+        in.select_opt = select_opt;
+        in.wide_opt = wide_opt;
+        in.share_opt = share_on ? 0 : 1;
+        in.masked_opt = masked_on;
+        const ScanVariant v = scan_variant(in);
+        if (!v.matrix) continue;
+        const MatrixForm form = matrix_form_of(v, in.collect);
+        const int list_kp = collect ? 0 : kp;
+        MatrixLaunch l{steps, !collect, collect != 0, v.share ? share_grid(5) : 5, 0};
+        l.lds = scan_lds_bytes(8, map, list_kp, block, v.group, 2, v.matrix_blocks());
+        // the host's long plan, where it names this block: the same LDS
+        const LongPlan lp = scan_long_plan(map, list_kp, v.matrix_blocks());
+        if (v.long_rows && lp.block == block) EXPECT(lp.lds == l.lds);
+        EXPECT(matrix_form_index(form) >= 0);
+        if (matrix_form_index(form) < 0) continue;
+        // (scan_variant answers for any count of queries: one column block walks them in groups of 16.  A LAUNCH of one
+        // block holds at most kMaxSweepsPerLaunch -- its constants' arrays do -- which is what the host forms and what the
+        // launchers have always insisted on: more is refused by every form)
+        if (!v.wide && !v.share && nq > kMaxSweepsPerLaunch) {
+            for (int f = 0; f < kMatrixFormCount; f++) EXPECT(!matrix_launch_ok(kMatrixForms[f], in, v, l));
+            continue;
+        }
+        reached[matrix_form_index(form)]++;
+        accepted++;
+        for (int f = 0; f < kMatrixFormCount; f++) EXPECT(matrix_launch_ok(kMatrixForms[f], in, v, l) == (kMatrixForms[f] == form));
+        // single corruptions of the accepted launch
+        auto refused = [&](const ScanPlanIn &i2, const MatrixLaunch &l2) { return !matrix_launch_ok(form, i2, v, l2); };
+        MatrixLaunch l2 = l;
+        l2.lds = l.lds + 16;
+        EXPECT(refused(in, l2));
+        l2.lds = l.lds - 16;
+        EXPECT(refused(in, l2));
+        l2 = l;
+        l2.steps = steps + 1;  // steps * 4 != r16
+        EXPECT(refused(in, l2));
+        l2 = l;
+        l2.grid = 0;
+        EXPECT(refused(in, l2));
+        if (form.share) {
+            l2.grid = l.grid + 1;  // odd
+            EXPECT(refused(in, l2));
+        }
+        l2 = l;
+        (collect ? l2.collect_out : l2.lists) = false;  // no collect buffer / no lists
+        EXPECT(refused(in, l2));
+        // one past the form's range of queries, at either end (LDS does not depend on the count)
+        ScanPlanIn i2 = in;
+        i2.n_queries = v.share ? kMatrixShareQueries + 1 : (v.wide ? kMatrixWideQueries + 1 : kMaxSweepsPerLaunch + 1);
+        EXPECT(refused(i2, l));
+        i2.n_queries = v.share ? kMatrixWideQueries : (v.wide ? kMatrixQueries : 0);
+        EXPECT(refused(i2, l));
+        if (v.row_lists) {  // a list longer than the row lists hold, its LDS as that list's
+            i2 = in;
+            i2.kp = kRowListMax + 1;
+            l2 = l;
+            l2.lds = scan_lds_bytes(8, map, i2.kp, block, v.group, 2, v.matrix_blocks());
+            EXPECT(refused(i2, l2));
+        }
+        if (!form.long_rows) {  // a block the short forms' kernels are not bounded for, with its own LDS
+            i2 = in;
+            i2.block = 320;
+            l2 = l;
+            l2.lds = scan_lds_bytes(8, map, list_kp, 320, v.group, 2, v.matrix_blocks());
+            EXPECT(refused(i2, l2));
+        }
+    }
+    EXPECT(accepted > 1000);
+    for (int f = 0; f < kMatrixFormCount; f++) EXPECT(reached[f] > 0);
+    // the table: ten forms, each at its own index; a masked or shared collect form is none
+    EXPECT(kMatrixFormCount == 10 && matrix_form_index(MatrixForm{false, false, false, false}) == 0 &&
+           matrix_form_index(MatrixForm{true, false, false, true}) == 9);
+    EXPECT(matrix_form_index(MatrixForm{false, true, false, true}) < 0 && matrix_form_index(MatrixForm{true, false, true, true}) < 0);
+}
+
 int main()
 {
+    check_matrix_guard();
     // the record's defaults are the defaults the positional parameters had
     {
         const ScanPlanIn d{};
