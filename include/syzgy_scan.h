@@ -772,6 +772,52 @@ typedef struct szg_sketch_topk_stats {
 int szg_index_sketch_topk_stats(szg_index *ix, szg_sketch_topk_stats *out);
 
 /*
+ * Neighbours of stored rows (added under ABI 4, additive).  Entry i of the outputs -- host arrays [n_queries][k] -- is
+ * exactly what szg_search_topk_masked answers on this handle for the query decodeVector(stored row q_i) in float64 with
+ * `mask` (NULL: none) for every query: ids, float64 distances bit for bit, order, out_count (nullable) and error codes.
+ * q_i = rows[i], or first_row + i when rows == NULL: szg_index_fetch_rows_dev's rules -- a host list in any order,
+ * duplicates allowed, numbered as searches return them.  A tombstoned query row is served as stored.  The row itself is a
+ * candidate like any other: a caller who does not want it asks for k + 1.  Refused on the host before any launch: a NULL
+ * handle or output, k < 1 (SZG_E_INVALID), a listed row or first_row + n_queries past the handle's rows (SZG_E_RANGE), a
+ * stale mask; n_queries == 0 checks its arguments only.  Threads: a search -- beside other searches, not beside mutations.
+ * Where the handle keeps a tiled 8-bit sketch (float32 rows, float64 ones under sketch_f64 = 1; dim a multiple of 64 up to
+ * 4 096), k is within the pre-pass's list rule, all shards lie on one device and the call has at least min_queries
+ * queries (szg_debug_join_plan; by default no call has: szg_debug_join_min_queries), the queries' own resident sketch
+ * rows are swept against the sketch on the matrix cores
+ * and settled by the pre-pass's certificate with twice the row-to-sketch distance; everything else, and every query that
+ * does not settle, is decoded on the card and handed to the masked search as ONE call.  The route changes the time only.
+ */
+int szg_index_neighbors(szg_index *ix, const uint64_t *rows, uint64_t first_row, uint64_t n_queries, int k,
+                        const szg_mask *mask, uint64_t *out_rows, double *out_dist, int32_t *out_count);
+typedef struct szg_neighbors_stats {
+    uint64_t queries;         /* queries of szg_index_neighbors calls */
+    uint64_t join_queries;    /* ... that were tried through the join */
+    uint64_t join_fallbacks;  /* ... of which it handed over to the masked search */
+    uint64_t join_launches;   /* launches of the join kernel (one per launch of up to 1 024 queries and shard) */
+    uint64_t join_bytes;      /* sketch bytes they asked for: rows x dim per query block of a launch */
+} szg_neighbors_stats;
+int szg_index_neighbors_stats(szg_index *ix, szg_neighbors_stats *out);   /* szg_reset_stats clears them */
+/* host only: the plan of one join launch of n_queries (1 .. 1 024) queries keeping kp candidates on a shard of shard_rows
+ * rows of `dim` sketch bytes on a device of cu_count compute units (0 = 256).  served = 0: the kernel does not serve it
+ * (an untiled dim, kp > 96); everything else is then zero. */
+typedef struct szg_join_plan {
+    int32_t served;
+    int32_t qb;               /* query rows per block: 64, 32 or 16 */
+    int32_t areg;             /* the query operand stays in registers (dim <= 1 024 at qb = 64) */
+    int32_t masked;
+    int32_t query_blocks, slices, tiles_per_slice;
+    int32_t m;                /* entries per (query, slice) list */
+    uint64_t lds_bytes;       /* below 160 KiB */
+    int32_t min_queries;      /* calls of fewer queries take the masked search's route */
+    int32_t reserved;
+} szg_join_plan;
+int szg_debug_join_plan(int dim, int n_queries, int kp, int masked, int cu_count, uint64_t shard_rows, szg_join_plan *out);
+/* Test and measurement hook: calls of at least min_queries (>= 1) queries on the handle try the join; 0 restores the
+ * default, min_queries of szg_debug_join_plan -- which the measurements put at "no call": on one MI355X at 1M x 768 the
+ * join is slower than the masked search's route at 64, 1 024 and 16 384 queries.  Not beside searches. */
+int szg_debug_join_min_queries(szg_index *ix, int min_queries);
+
+/*
  * Option query_prep: which side prepared the queries of the handle's top-k calls through the sketch since szg_reset_stats,
  * which clears the three counters.  A getter of its own beside szg_stats, as szg_index_sketch_topk_stats is.
  */
@@ -1334,6 +1380,9 @@ int szg_debug_refuse_device_alloc(int64_t nth);
                                     (+ slack); k; certified 1 = settled, 0 = handed over (before the sweep, or with more
                                     candidates than the buffers held: thr, eps, D NaN and no entries).  Keyed entries = the collected sketch rows, NO_KEY entries = the rows
                                     without a usable sketch and the query's first k eligible rows */
+#define SZG_CERT_JOIN 7          /* the sketch-on-sketch join of szg_index_neighbors (one record per query it tried): as
+                                    SZG_CERT_SKETCH with the join's key bound (exact under Euclid up to the float32 rounding
+                                    of the integer key) and slack = TWICE the largest row-to-sketch distance */
 #define SZG_CERT_KEYS_SINGLE 0
 #define SZG_CERT_KEYS_SHARED_INT8 1
 #define SZG_CERT_KEYS_SHARED_BF16 2

@@ -79,11 +79,14 @@ EXPORTS = [
     "szg_index_query_prep_stats", "szg_debug_query_prep", "szg_debug_query_prep_serves",
     # the long-row collect form and the long sample pass (2 048 .. 4 096 dimensions): the plan hooks
     "szg_debug_scan_long_collect", "szg_debug_sample_long_plan",
+    # neighbours of stored rows (added under ABI 4): the call, its counters, the join's plan hook
+    "szg_index_neighbors", "szg_index_neighbors_stats", "szg_debug_join_plan", "szg_debug_join_min_queries",
 ]
 # szg_cert_record.pass / .keys, szg_cert_entry.flags
 SZG_CERT_TOPK, SZG_CERT_SKETCH, SZG_CERT_ESCALATION, SZG_CERT_RADIUS_SINGLE, SZG_CERT_RADIUS_SHARED = range(5)
 SZG_CERT_SKETCH_RADIUS = 5   # radius collect on the sketch (option sketch_radius), recorded on the float32 handle
 SZG_CERT_SKETCH_TOPK_COLLECT = 6   # top-k of large k through the sketch (option sketch_topk_collect): sample bound + collect
+SZG_CERT_JOIN = 7   # the sketch-on-sketch join of szg_index_neighbors
 (SZG_CERT_KEYS_SINGLE, SZG_CERT_KEYS_SHARED_INT8, SZG_CERT_KEYS_SHARED_BF16, SZG_CERT_KEYS_BF16_BAND,
  SZG_CERT_KEYS_BF16_RESCORED) = range(5)
 SZG_CERT_ENTRY_NO_KEY = 1
@@ -147,6 +150,16 @@ class SzgSketchTopkStats(ctypes.Structure):
 
 class SzgQueryPrepStats(ctypes.Structure):
     _fields_ = [(name, ctypes.c_uint64) for name in ("queries_dev", "queries_host", "launches")]
+
+
+class SzgNeighborsStats(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_uint64) for name in ("queries", "join_queries", "join_fallbacks", "join_launches", "join_bytes")]
+
+
+class SzgJoinPlan(ctypes.Structure):
+    _fields_ = ([(name, ctypes.c_int32) for name in ("served", "qb", "areg", "masked", "query_blocks", "slices",
+                                                     "tiles_per_slice", "m")] +
+                [("lds_bytes", ctypes.c_uint64), ("min_queries", ctypes.c_int32), ("reserved", ctypes.c_int32)])
 
 
 class SzgSamplePlan(ctypes.Structure):
@@ -502,6 +515,15 @@ def load():
         L.szg_debug_scan_long_collect.argtypes = [ctypes.c_int] * 9 + [ctypes.POINTER(SzgScanLongPlan)]
         L.szg_debug_sample_long_plan.restype = ctypes.c_int
         L.szg_debug_sample_long_plan.argtypes = [ctypes.c_uint64] + [ctypes.c_int] * 6 + [ctypes.POINTER(SzgSampleLongPlan)]
+    if hasattr(L, "szg_index_neighbors"):   # (an older build for an A/B run has no such call)
+        L.szg_index_neighbors.restype = ctypes.c_int
+        L.szg_index_neighbors.argtypes = [vp, u64p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int, vp, u64p, f64p, i32p]
+        L.szg_index_neighbors_stats.restype = ctypes.c_int
+        L.szg_index_neighbors_stats.argtypes = [vp, ctypes.POINTER(SzgNeighborsStats)]
+        L.szg_debug_join_min_queries.restype = ctypes.c_int
+        L.szg_debug_join_min_queries.argtypes = [vp, ctypes.c_int]
+        L.szg_debug_join_plan.restype = ctypes.c_int
+        L.szg_debug_join_plan.argtypes = [ctypes.c_int] * 5 + [ctypes.c_uint64, ctypes.POINTER(SzgJoinPlan)]
     if hasattr(L, "szg_index_query_prep_stats"):   # (an older build for an A/B run has no such option)
         L.szg_index_query_prep_stats.restype = ctypes.c_int
         L.szg_index_query_prep_stats.argtypes = [vp, ctypes.POINTER(SzgQueryPrepStats)]

@@ -54,9 +54,10 @@ from . import _lib
 
 PASS_NAMES = {_lib.SZG_CERT_TOPK: "topk", _lib.SZG_CERT_SKETCH: "sketch", _lib.SZG_CERT_ESCALATION: "escalation",
               _lib.SZG_CERT_RADIUS_SINGLE: "radius", _lib.SZG_CERT_RADIUS_SHARED: "radius-shared",
-              _lib.SZG_CERT_SKETCH_RADIUS: "sketch-radius", _lib.SZG_CERT_SKETCH_TOPK_COLLECT: "sketch-topk-collect"}
+              _lib.SZG_CERT_SKETCH_RADIUS: "sketch-radius", _lib.SZG_CERT_SKETCH_TOPK_COLLECT: "sketch-topk-collect", _lib.SZG_CERT_JOIN: "join"}
 # their keys are keys of the rows' sketches
-SKETCH_PASSES = (_lib.SZG_CERT_SKETCH, _lib.SZG_CERT_SKETCH_RADIUS, _lib.SZG_CERT_SKETCH_TOPK_COLLECT)
+SKETCH_PASSES = (_lib.SZG_CERT_SKETCH, _lib.SZG_CERT_SKETCH_RADIUS, _lib.SZG_CERT_SKETCH_TOPK_COLLECT, _lib.SZG_CERT_JOIN)
+LIST_SKETCH_PASSES = (_lib.SZG_CERT_SKETCH, _lib.SZG_CERT_JOIN)   # ... that keep lists: thr_min = lb, D, slack, S
 COLLECT_SKETCH_PASSES = (_lib.SZG_CERT_SKETCH_RADIUS, _lib.SZG_CERT_SKETCH_TOPK_COLLECT)   # ... collected under a threshold
 KEYS_NAMES = {-1: "-", _lib.SZG_CERT_KEYS_SINGLE: "Single", _lib.SZG_CERT_KEYS_SHARED_INT8: "SharedInt8",
               _lib.SZG_CERT_KEYS_SHARED_BF16: "SharedBf16", _lib.SZG_CERT_KEYS_BF16_BAND: "Bf16Band",
@@ -182,7 +183,8 @@ class Margins:
 Summary = collections.namedtuple("Summary", "records kinds skipped skipped_rows checked")
 
 
-def check(corpus, Q, recs, ents, dropped, eligible=None, dists=None, margins=None, what=(), sketch=None, radii=None):
+def check(corpus, Q, recs, ents, dropped, eligible=None, dists=None, margins=None, what=(), sketch=None, radii=None,
+          join_rows=None):
     """Assert K, L, C and S for the records of ONE call with queries Q.  eligible: bool[n] or bool[nq, n] (None: every
     row); dists: float64[nq, n], the oracle's distances (needed for sketch records).  -> Summary; skipped_rows are the
     rows whose candidates carried no bound.
@@ -199,7 +201,11 @@ def check(corpus, Q, recs, ents, dropped, eligible=None, dists=None, margins=Non
 
     and, for every sketch-radius record (which needs sketch=, dists= and radii=, the radius the test passed per query):
     K_s, C_s, T and S_r as the module's docstring states them; for every sketch-topk-collect record (sketch= and dists=):
-    P and R where kmax is finite, K_s, C_s, T and S_k where the record carries a sweep, F where it is certified."""
+    P and R where kmax is finite, K_s, C_s, T and S_k where the record carries a sweep, F where it is certified.
+
+    Join records (szg_index_neighbors; sketch=, dists= and join_rows=, the stored row that is query i, Q its decode): K_s,
+    L_s, D and S as for sketch records, with the real-number sketch key taken between the row's sketch and the QUERY
+    ROW'S SKETCH -- what the join multiplies -- and the record's slack, which is twice the handle's."""
     Q = np.atleast_2d(np.asarray(Q, dtype=np.float64))
     nq, n = Q.shape[0], corpus.n
     assert dropped == 0, ("the trace dropped records", dropped, what)
@@ -212,6 +218,9 @@ def check(corpus, Q, recs, ents, dropped, eligible=None, dists=None, margins=Non
         real_s, err_s = sk_corpus.keys(Q / gscale if euclid_s else Q)
         is_exc = np.zeros(n, dtype=bool)
         is_exc[np.asarray(exc_rows, dtype=np.int64)] = True
+        real_pre = real_s, err_s
+        if join_rows is not None:   # (a decoded 8-bit row is n / 255: |n_a - n_b|^2 under Euclid, the direction under cosine)
+            real_join = sk_corpus.keys(sk_corpus.X[np.asarray(join_rows, dtype=np.int64)])
     if eligible is None:
         eligible = np.ones(n, dtype=bool)
     eligible = np.broadcast_to(np.asarray(eligible, dtype=bool), (nq, n))
@@ -231,6 +240,12 @@ def check(corpus, Q, recs, ents, dropped, eligible=None, dists=None, margins=Non
         in_range = np.zeros(n, dtype=bool)
         in_range[lo:hi] = True
         keyed = (e["flags"] & _lib.SZG_CERT_ENTRY_NO_KEY) == 0
+        if p == _lib.SZG_CERT_JOIN:
+            assert sketch is not None and dists is not None and join_rows is not None, \
+                "join records need the sketch state, the oracle's distances and the query rows"
+            assert rec["certified"] == 1 or not is_exc[int(join_rows[qi])] or len(e) == 0, ("a query row without a sketch", where)
+        if sketch is not None:
+            real_s, err_s = real_join if p == _lib.SZG_CERT_JOIN else real_pre
         key = e["key"].astype(np.float64)
         ub = e["ub"]
         # ---- K
@@ -312,7 +327,7 @@ def check(corpus, Q, recs, ents, dropped, eligible=None, dists=None, margins=Non
                     float(d_el[k - 1]) if d_el.size >= k else None)
         if p in SKETCH_PASSES and sketch is not None and not zero_q[qi] and \
                 (p == _lib.SZG_CERT_SKETCH_RADIUS or (topk_c and np.isfinite(rec["thr"])) or
-                 (p == _lib.SZG_CERT_SKETCH and np.isfinite(rec["thr_min"]))):
+                 (p in LIST_SKETCH_PASSES and np.isfinite(rec["thr_min"]))):
             lb = float(rec["thr_min"])
             s_real, s_err = real_s[qi, rows], err_s[qi, rows]
             forced = keyed & (~np.isfinite(s_real) | (key >= TAKE_ALL) | ((key <= -1.5) if not euclid_s else False))
@@ -393,7 +408,7 @@ def check(corpus, Q, recs, ents, dropped, eligible=None, dists=None, margins=Non
                 assert rec["D"] <= implied + 4 * np.finfo(np.float64).eps * implied, ("D: above the distance thr_min implies",
                                                                                       where, float(rec["D"]), implied, lb)
         # ---- S
-        if p == _lib.SZG_CERT_SKETCH and rec["certified"] == 1 and np.isfinite(rec["D"]):
+        if p in LIST_SKETCH_PASSES and rec["certified"] == 1 and np.isfinite(rec["D"]):
             assert dists is not None, "sketch records need the oracle's distances"
             d = dists[qi]
             bad = np.flatnonzero(outside & (d < rec["D"] - rec["slack"]))

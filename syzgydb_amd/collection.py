@@ -856,3 +856,20 @@ class Collection:
                    for row, dd in zip(rows, dist)]
             out.append(SearchResults(Results=res, PercentSearched=100.0))
         return out
+
+    def Neighbors(self, ids, K, Where=None, Filter=None, FilterKey=None) -> List[SearchResults]:
+        """Neighbours of stored documents (not in the reference): entry i is SearchBatch's answer for the stored vector of
+        document ids[i] as the query -- the document itself included: ask for K + 1 to drop it -- with ONE filter for
+        every query, through the cached filter mask as SearchBatch.  ScanIndex.neighbors: no vector leaves the card."""
+        if K <= 0:
+            raise ValueError("Neighbors: K > 0")
+        args = SearchArgs(K=K, Filter=Filter, Where=Where, FilterKey=FilterKey)
+        flt = self._search_filter(args)[0]
+        if self._order_stale:
+            self._resort()
+        rows = np.array([self._row_of[i] for i in ids], dtype=np.uint64)
+        mask = self._search_handle(args) if (flt is not None or Where is not None) else None
+        r, d, c = self._index.neighbors(rows=rows, k=K, mask=mask)
+        return [SearchResults(Results=[SearchResult(ID=self._id_of[int(row)], Metadata=self._meta[int(row)], Distance=float(dd))
+                                       for row, dd in zip(r[i, : c[i]], d[i, : c[i]])], PercentSearched=100.0)
+                for i in range(len(rows))]

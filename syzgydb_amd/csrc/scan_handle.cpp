@@ -653,6 +653,7 @@ int szg_reset_stats(szg_index *ix)
     ix->mx_masked_launches = ix->mx_masked_skip = ix->mx_masked_queries = 0;  // (szg_debug_sketch_masked's)
     ix->sk_topk = szg_sketch_topk_stats{};  // (szg_index_sketch_topk_stats')
     ix->qp = szg_query_prep_stats{};        // (szg_index_query_prep_stats')
+    ix->nb = szg_neighbors_stats{};         // (szg_index_neighbors_stats')
     if (ix->sketch) {
         std::lock_guard<std::mutex> lk2(ix->sketch->stats_mu);
         ix->sketch->stats = szg_stats{};

@@ -28,6 +28,8 @@
 //                     (bulk_plan.h: its host-only checks; kernels_bulk.hip: its scatters), and appends / overwrites from
 //                     vectors in device memory (szg_dev_vectors; kernels_exact.hip: ingest_kernel), stored vectors out
 //                     to device memory (fetch_kernel) and searches whose queries lie there (widen_rows_kernel)
+//   scan_join.cpp     neighbours of stored rows (szg_index_neighbors): the sketch-on-sketch join (join_plan.h: its plan;
+//                     kernels_join.hip: its kernels; row_offer.h: the row lists' tile step) and the parent's route
 //   scan_api.cpp      remaining C entry points (top-k with caller coalescing, distances)
 //
 // Who owns device memory: dev_mem.h.  Every block is held by a DevBuf / PinnedBuf (scratch of the device that is
@@ -41,6 +43,7 @@
 #pragma once
 #include "../../include/syzgy_scan.h"
 #include "dev_mem.h"
+#include "join_plan.h"
 #include "kernels.h"
 #include "options.h"
 #include "query_prep.h"
@@ -384,6 +387,18 @@ struct Shard : ShardRows {
     std::mutex stage_mu;         // szg_index_read_rows may run beside other readers (szg_pair_distances)
 };
 
+// The scratch of szg_index_neighbors' join (scan_join.cpp), kept between calls under szg_index::join_mu: device blocks
+// on the shards' one device, pinned twins of what travels
+struct JoinScratch {
+    DevMem<szg::JoinRowStat> row_stat, q_stat;  // per sketch row of every shard / per query of a launch
+    DevMem<uint8_t> qtiles;                     // a launch's query sketch rows, tiled
+    DevMem<double> q64;                         // ... and their float64 decode (the re-rank's queries)
+    DevMem<uint64_t> qlist, lists, cand;        // query rows; [query][slice][m] lists; merged lists + staged rows
+    DevMem<szg::RerankOut> out;
+    PinnedBuf<uint64_t> h_qlist, h_cand;
+    PinnedBuf<szg::RerankOut> h_out;
+};
+
 }  // namespace szgi
 
 // One caller of szg_search_topk(n_queries == 1) or szg_search_radius waiting to be answered as part of a batch.
@@ -436,6 +451,10 @@ struct szg_index : szgi::Options {   // (the run-time options: options.h)
     int n_ctx = 4;            // contexts (and streams) per shard (bfloat16 batches of 1M x 768: 3 -> 4 = 155 -> 162 k queries/s; 6: no more)
     int n_ctx_active = 4;     // of them in rotation (the rest parked): the last accepted value of option "contexts"
     szg_sketch_topk_stats sk_topk{};  // what that path served (stats_mu; szg_index_sketch_topk_stats, szg_reset_stats)
+    szg_neighbors_stats nb{};   // szg_index_neighbors (stats_mu; szg_index_neighbors_stats, szg_reset_stats)
+    std::mutex join_mu;         // one join at a time: it owns `join`
+    int join_min = szg::kJoinMinQueries;  // calls of at least this many queries try the join (szg_debug_join_min_queries)
+    szgi::JoinScratch join;
     szg_query_prep_stats qp{};  // which side prepared such calls' queries (stats_mu; szg_index_query_prep_stats, szg_reset_stats)
     bool is_sketch = false;   // this index is the internal sketch of a float32 (or float64) handle: its keys only bound
     // settled by measurement (rounds 1-3): compile-time facts since round 4, A/B through -D and `make variant`

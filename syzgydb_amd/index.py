@@ -1004,6 +1004,39 @@ class ScanIndex:
         check(self._L.szg_index_sketch_topk_stats(self._h, ctypes.byref(s)), "szg_index_sketch_topk_stats")
         return {name: int(getattr(s, name)) for name, _ in _lib.SzgSketchTopkStats._fields_}
 
+    def neighbors(self, rows=None, first=0, n=None, k=10, mask=None):
+        """Neighbours of stored rows (szg_index_neighbors): entry i is what search_topk answers for the float64 decode of
+        stored row rows[i] -- or first + i, n of them (default: to the end of the handle) -- with the ScanMask `mask` for
+        every query.  The row itself is a candidate: ask for k + 1 to drop it.  Returns (ids uint64[n, k], dist
+        float64[n, k], count int32[n])."""
+        if rows is not None:
+            r = np.ascontiguousarray(rows, dtype=np.uint64).reshape(-1)
+            nq, rp, first = r.size, _u64(r), 0
+        else:
+            nq = max(int(self.rows + self._row_base - int(first)), 0) if n is None else int(n)   # (past the end: the library refuses)
+            rp = None
+        k = int(k)
+        out_rows = np.zeros((nq, max(k, 0)), dtype=np.uint64)
+        out_dist = np.zeros((nq, max(k, 0)), dtype=np.float64)
+        out_count = np.zeros(nq, dtype=np.int32)
+        check(self._L.szg_index_neighbors(self._h, rp, int(first), nq, k, mask._h if mask is not None else None, _u64(out_rows),
+                                          _f64(out_dist), out_count.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))),
+              "szg_index_neighbors")
+        return out_rows, out_dist, out_count
+
+    def debug_join_min_queries(self, min_queries):
+        """Test and measurement hook (szg_debug_join_min_queries): neighbors() calls of at least min_queries queries try
+        the sketch-on-sketch join; 0 restores the default, under which no call does (it measured slower)."""
+        check(self._L.szg_debug_join_min_queries(self._h, int(min_queries)), "szg_debug_join_min_queries")
+
+    def neighbors_stats(self):
+        """What neighbors() served on the handle since reset_stats (szg_index_neighbors_stats): queries, the join_queries
+        tried through the sketch-on-sketch join, the join_fallbacks it handed to the masked search, join_launches and the
+        sketch bytes they asked for."""
+        s = _lib.SzgNeighborsStats()
+        check(self._L.szg_index_neighbors_stats(self._h, ctypes.byref(s)), "szg_index_neighbors_stats")
+        return {name: int(getattr(s, name)) for name, _ in _lib.SzgNeighborsStats._fields_}
+
     def query_prep_stats(self):
         """Which side prepared the queries of the handle's top-k calls through the sketch since reset_stats (option
         query_prep; szg_index_query_prep_stats): queries_dev, queries_host, and launches of the preparing kernel."""
@@ -1271,6 +1304,15 @@ def query_prep_serves(option, batch_queries):
     least = ctypes.c_int()
     serves = L.szg_debug_query_prep_serves(int(option), int(batch_queries), ctypes.byref(least))
     return bool(serves), least.value
+
+
+def join_plan(dim, n_queries, kp, masked=0, cu_count=0, shard_rows=1 << 20):
+    """Host-only hook (szg_debug_join_plan): the plan of one launch of the sketch-on-sketch join -- served, qb (query rows
+    per block), areg, slices, tiles_per_slice, m, lds_bytes, and min_queries, the fewest queries of a call that takes it."""
+    out = _lib.SzgJoinPlan()
+    check(_lib.load().szg_debug_join_plan(int(dim), int(n_queries), int(kp), int(masked), int(cu_count), int(shard_rows),
+                                          ctypes.byref(out)), "szg_debug_join_plan")
+    return {name: int(getattr(out, name)) for name, _ in _lib.SzgJoinPlan._fields_ if name != "reserved"}
 
 
 def option_check(name, value):
